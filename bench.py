@@ -7,13 +7,24 @@ temporal LK, stereo LK fwd/bwd + gates, FAST + grid add/prune, publish) with gri
 features per frame, run for S independent streams per GPU (frames of one stream are sequential,
 streams are the parallel axis).  One "step" = one stereo frame of every stream.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the bench measures:
+the front-end-only loop after the timed steps, the small-batch regime lines, the CPU baselines with the trajectory
+comparison against the CPU path, and warm-up steps with front-end and filter strictly alternating (roofline_msckf.exclusive).
+`--dump-outputs DIR` writes what the timed path returned for its last step as float64 .npy files (see dump_outputs).
 
 Without a torchrun environment `--gpus N` (N > 1) starts the N ranks itself as fresh child processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) BEFORE anything touches the GPU, relays rank 0's line and exits non-zero
 if any rank failed.  Prints ONE JSON line on rank 0 (contract in the task statement).  Inputs are resident in HBM
 before the timed region; IMU samples are pushed from the host inside it (they are part of the path).
+
+At most --max-resident-frames frames per stream are rendered and kept in HBM (fewer when device memory is short).  A run that
+steps through more frames than that shows frames 0..P-1 once, then goes back and forth between P-1 and B = P/2 (frames in motion,
+past every stream's standstill at the start).  Timestamps keep increasing and the IMU feed follows the mirrored motion (body rates
+negated on the backward legs, the velocity reversal of each turn in the accelerometer sample that spans it), so the filters keep
+tracking.  Runs that fit in the pool step through the frames once.
 
 The timed region is always the steady state: before the `--warmup` steps the bench pre-rolls, un-timed, until every
 filter holds its full camera-state window and has run the camera pruning (PREROLL frames), so the result does not depend
@@ -104,6 +115,131 @@ def frame_bytes(n_t, n_trk, n_cand):
 def make_config(grid=(4, 5, 15)):
     from uav_airvision_amd.config import ConfigEuRoC
     return ConfigEuRoC(grid_row=grid[0], grid_col=grid[1], grid_min_feature_num=3, grid_max_feature_num=grid[2])
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, feats, flt_out):
+    """What a caller of the timed path receives for its last step, as float64 .npy files in out_dir: the features the
+    front-end published (feature_counts [m], feature_ids [n], feature_uv [n, 4] = u0 v0 u1 v1, concatenated in stream order)
+    and, with the filter in the step, its output (filter_output [m, 12] = published, t, p, q, v).  stream_index [m] names the
+    streams written: all of them, or above DUMP_CAP_BYTES a fixed, seeded sample of them."""
+    S = len(feats)
+    per_stream = np.array([8 * (2 + 5 * len(f[0]) + (12 if flt_out is not None else 0)) for f in feats], np.int64)
+    if per_stream.sum() <= DUMP_CAP_BYTES:
+        keep = np.arange(S)
+    else:
+        order = np.random.default_rng(0).permutation(S)
+        keep = np.sort(order[:int(np.searchsorted(np.cumsum(per_stream[order]), DUMP_CAP_BYTES, side='right'))])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'stream_index': keep.astype(np.float64),
+              'feature_counts': np.array([len(feats[s][0]) for s in keep], np.float64),
+              'feature_ids': np.concatenate([feats[s][0] for s in keep] + [np.zeros(0, np.int64)]).astype(np.float64),
+              'feature_uv': np.concatenate([feats[s][1].reshape(-1, 4) for s in keep] + [np.zeros((0, 4))]).astype(np.float64)}
+    if flt_out is not None:
+        arrays['filter_output'] = np.asarray(flt_out, dtype=np.float64)[keep]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def pool_index(k, P, B):
+    """Resident frame shown at step k: frames 0..P-1 once, then back and forth between P-1 and B."""
+    if k < P or P - 1 <= B:
+        return min(k, P - 1)
+    D = P - 1 - B
+    m = (k - (P - 1)) % (2 * D)
+    return P - 1 - m if m <= D else B + (m - D)
+
+
+def mirrored_imu(st, P, B, t_end):
+    """(t [n], gyro [n, 3], acc [n, 3]): the IMU feed of SyntheticStream st for a run that shows frames as pool_index(k, P, B) does,
+    up to time t_end.  The stream's own samples up to frame P-1; after that, on the same sample clock, the sample at the mirrored
+    content time (nearest recorded sample; body rate negated on backward legs), plus the velocity reversal of every turn as a
+    specific-force impulse in the sample spanning it."""
+    from uav_airvision_amd.synth import IMU_RATE
+    T = np.array([m.timestamp for m in st.imu])
+    G = np.array([m.angular_velocity for m in st.imu], np.float64).reshape(-1, 3)
+    A = np.array([m.linear_acceleration for m in st.imu], np.float64).reshape(-1, 3)
+    tE, tB, dt = st.frame_time(P - 1), st.frame_time(B), 1.0 / IMU_RATE
+    n0 = int(np.searchsorted(T, tE, side='right'))
+    n1 = int(np.floor((t_end - T[0]) / dt + 1e-9)) + 1                  # clock ticks up to t_end
+    if n1 <= n0 or P - 1 <= B:
+        return T[:n0], G[:n0], A[:n0]
+    h = 1e-4
+
+    def vel(t):
+        return (st.position(t + h) - st.position(t - h)) / (2 * h)
+    tau = T[0] + np.arange(n0, n1) * dt
+    D = tE - tB
+    x = tau - tE
+    m = np.mod(x, 2 * D)
+    back = m <= D
+    tc = np.where(back, tE - m, tB + (m - D))
+    j = np.clip(np.rint((tc - T[0]) / dt).astype(np.int64), 0, len(T) - 1)
+    g = G[j] * np.where(back, -1.0, 1.0)[:, None]
+    f = A[j].copy()
+    n_now = np.floor(x / D)
+    turn = n_now != np.floor((x - dt) / D)                               # turn n_now lies in (tau - dt, tau]
+    f[turn & (n_now % 2 == 0)] += st.R_i_w(tE).T @ (-2.0 * vel(tE)) / dt   # at frame P-1: v -> -v
+    f[turn & (n_now % 2 == 1)] += st.R_i_w(tB).T @ (2.0 * vel(tB)) / dt    # at frame B: -v -> v
+    return np.concatenate([T[:n0], tau]), np.concatenate([G[:n0], g]), np.concatenate([A[:n0], f])
+
+
+def imu_feed_steps(feeds, frame_times, S):
+    """Per step k, the IMU samples the S streams receive before frame k, as flat arrays (stream index int32, t, gyro [., 3],
+    acc [., 3]): the feed of rendered stream u (feeds[u] = (t, gyro, acc)) goes to its replicas s = u, u + U, ..; frame_times
+    [F, U].  Order: rendered stream, then replica, then sample."""
+    U = len(feeds)
+    offs = np.concatenate([[0], np.cumsum([len(f[0]) for f in feeds])[:-1]]).astype(np.int64)
+    T, G, A = [np.concatenate([f[i] for f in feeds]) for i in range(3)]
+    ends = np.stack([np.searchsorted(f[0], frame_times[:, u], side='right') for u, f in enumerate(feeds)], 1)
+    starts = np.vstack([np.zeros((1, U), np.int64), ends[:-1]])
+    n_rep = np.array([len(range(u, S, U)) for u in range(U)], np.int64)
+    steps, layouts = [], {}
+    for k in range(len(frame_times)):
+        m = ends[k] - starts[k]                       # samples of each rendered stream in this step
+        lay = layouts.get(m.tobytes())                # (stream index, rendered stream, sample) per entry; shared by equal counts
+        if lay is None:
+            n = m * n_rep                             # its block: replicas x samples
+            blk = np.repeat(np.arange(U), n)
+            p = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            mb = m[blk]
+            lay = layouts[m.tobytes()] = ((blk + U * (p // mb)).astype(np.int32), blk, p % mb)
+        idx, blk, j = lay
+        gi = (offs + starts[k])[blk] + j
+        steps.append((idx, T[gi], G[gi], A[gi]))
+    return steps
+
+
+def render_frames_torch(torch, st, state, ks, generator):
+    """(cam0, cam1) uint8 tensors [len(ks), H, W]: SyntheticStream.frame_torch for many frames of one stream at once (same
+    scene, geometry and noise statistics; a few dozen launches per batch of frames instead of per frame)."""
+    from uav_airvision_amd.synth import TEX_SCALE
+    tex = state['tex']
+    th, tw = tex.shape
+    dev = tex.device
+    n = torch.from_numpy(st.wall_n).to(dev)
+    e1, e2 = torch.from_numpy(st.wall_e1).to(dev), torch.from_numpy(st.wall_e2).to(dev)
+    poses = [(st.R_i_w(st.frame_time(k)), st.position(st.frame_time(k))) for k in ks]
+    out = []
+    for rays, T in ((state['rays0'], st.T_c0_i), (state['rays1'], st.T_c1_i)):
+        R_c_w = torch.from_numpy(np.stack([R @ T[:3, :3] for R, p in poses])).to(dev)
+        c_w = torch.from_numpy(np.stack([p + R @ T[:3, 3] for R, p in poses])).to(dev)
+        r = rays.unsqueeze(0) @ R_c_w.transpose(1, 2).unsqueeze(1)                 # [nk, H, W, 3]
+        s_ = (st.wall_d - c_w @ n)[:, None, None] / (r @ n)
+        X = c_w[:, None, None, :] + r * s_[..., None]
+        u = (X @ e1) * TEX_SCALE + tw / 2 + st.tex_offset[0]
+        v = (X @ e2) * TEX_SCALE + th / 2 + st.tex_offset[1]
+        u0 = torch.floor(u); v0 = torch.floor(v)
+        fu = (u - u0).to(torch.float32); fv = (v - v0).to(torch.float32)
+        ui = torch.remainder(u0.to(torch.int64), tw); vi = torch.remainder(v0.to(torch.int64), th)
+        ui1 = torch.remainder(ui + 1, tw); vi1 = torch.remainder(vi + 1, th)
+        img = (tex[vi, ui] * (1 - fu) + tex[vi, ui1] * fu) * (1 - fv) + (tex[vi1, ui] * (1 - fu) + tex[vi1, ui1] * fu) * fv
+        if st.pixel_noise > 0:
+            img = img + torch.randn(img.shape, generator=generator, device=dev, dtype=torch.float32) * st.pixel_noise
+        out.append(torch.clamp(torch.round(img), 0, 255).to(torch.uint8))
+    return out[0], out[1]
 
 
 def cpu_baseline(cfg, with_msckf, budget_s=10.0, max_frames=400, seed=0, traj_frames=0):
@@ -431,8 +567,12 @@ def main():
     ap.add_argument('--no-stagger', action='store_true', help='start every replica at frame 0 (all filters then prune on the same frames)')
     ap.add_argument('--host-images', action='store_true', help='front-end only, images handed over as host numpy arrays every step '
                     '(av_frontend_step_host: the PCIe-inclusive rate quoted in DESIGN.md; never the contract value)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-regimes', action='store_true', help='skip the small-batch regime lines (S = 1, 8 x 1500 features, 64, host-fed)')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: front-end-only loop, small-batch regimes, '
+                    'CPU baselines with the trajectory comparison, exclusive filter chain in serial warm-up steps')
+    ap.add_argument('--max-resident-frames', type=int, default=80, help='frames per stream rendered and kept in HBM; a longer run plays them forward and back')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the timed path returned for its last step as float64 .npy files into DIR')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-regimes', action='store_true', help='with --full: skip the small-batch regime lines (S = 1, 8 x 1500 features, 64, host-fed)')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--cpu-budget', type=float, default=6.0, help=argparse.SUPPRESS)
     ap.add_argument('--cpu-seed', type=int, default=0, help=argparse.SUPPRESS)
@@ -479,7 +619,7 @@ def main():
     PRE = PREROLL_FULL if with_msckf else PREROLL_FE
     stagger = 0 if args.no_stagger else 1
     PRE += stagger                              # the replicas that start one frame later reach the steady state one step later
-    F = PRE + Wm + K + (K if with_msckf else 0)  # a second timed loop measures the front-end alone
+    F = PRE + Wm + K + (K if with_msckf and args.full else 0)  # --full: a second timed loop measures the front-end alone
     # config/seed broadcast from rank 0 over RCCL (config broadcast, no data-path collective)
     from uav_airvision_amd import shard
     run_cfg = shard.broadcast_object({'seed': 1234, 'streams': S, 'steps': K, 'warmup': Wm} if rank == 0 else None)
@@ -489,6 +629,13 @@ def main():
     # Replica 0 of every rendered stream carries no extra noise: GPU stream 0 is exactly SyntheticStream(seed) -- the one the
     # CPU path replays for `ate_vs_cpu_ref`.
     U = max(1, min(args.unique, S))
+    # P resident frames per stream (the pool): every frame of the run when they fit, else the run plays the pool forward and back
+    per_frame = 2 * (S + U) * H_IMG * W_IMG
+    P = min(F, args.max_resident_frames, int(0.85 * torch.cuda.mem_get_info(dev)[0] // per_frame))
+    if P < min(F, 48):
+        sys.stderr.write('bench.py: %d streams leave room for %d resident frames (48 needed): use fewer --streams\n' % (S, P))
+        return 2
+    B = P // 2                                  # longer runs turn back at frame B: past every stream's standstill (at most 2 s = 40 frames)
     t_gen = time.time()
     stream_seed0 = base_seed + 97 * rank
     # U distinct streams.  Stream 0 is exactly SyntheticStream(seed) rendered by numpy (the CPU path replays it for `ate_vs_cpu_ref`);
@@ -502,55 +649,58 @@ def main():
     streams = []
     for u in range(U):
         if u == 0:
-            st = SyntheticStream(cfg, seed=stream_seed0, n_frames=F, texture=tex_pool[0])
+            st = SyntheticStream(cfg, seed=stream_seed0, n_frames=P, texture=tex_pool[0])
         else:
-            st = SyntheticStream(cfg, seed=stream_seed0 + u, n_frames=F, texture=tex_pool[u % len(tex_pool)], render=False,
+            st = SyntheticStream(cfg, seed=stream_seed0 + u, n_frames=P, texture=tex_pool[u % len(tex_pool)], render=False,
                                  motion_scale=float(prng.uniform(0.7, 1.6)), rest=float(prng.uniform(0.0, 2.0)),
                                  tex_offset=(0.0, 0.0) if u < len(tex_pool) else (float(prng.uniform(0, 2048)), float(prng.uniform(0, 1536))))
             st.tex, st.rays0, st.rays1 = tex_pool[u % len(tex_pool)], streams[0].rays0, streams[0].rays1
         streams.append(st)
-    b0 = torch.empty((U, F, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
-    b1 = torch.empty((U, F, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
-    for k in range(F):
-        m = streams[0].frame(k)
-        b0[0, k] = torch.from_numpy(m.cam0_image).to(dev)
-        b1[0, k] = torch.from_numpy(m.cam1_image).to(dev)
+    import threading
+    h0 = np.empty((P, H_IMG, W_IMG), np.uint8)
+    h1 = np.empty((P, H_IMG, W_IMG), np.uint8)
+
+    render0_err = []
+
+    def render0():                                  # numpy renderer of stream 0 (the CPU path's input), beside the GPU renders
+        try:
+            for k in range(P):
+                m = streams[0].frame(k)
+                h0[k], h1[k] = m.cam0_image, m.cam1_image
+        except BaseException as e:
+            render0_err.append(e)
+    th0 = threading.Thread(target=render0, name='render0')
+    th0.start()
+    b0 = torch.empty((U, P, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
+    b1 = torch.empty((U, P, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
     g = torch.Generator(device=dev)
     g.manual_seed(base_seed + rank)
     rays_dev = (torch.from_numpy(streams[0].rays0).to(dev), torch.from_numpy(streams[0].rays1).to(dev))
     tex_dev = [torch.from_numpy(t).to(dev) for t in tex_pool]
     for u in range(1, U):
         state = dict(tex=tex_dev[u % len(tex_pool)], rays0=rays_dev[0], rays1=rays_dev[1])
-        for k in range(F):
-            b0[u, k], b1[u, k] = streams[u].frame_torch(k, state, g)
-    img0 = torch.empty((F, S, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
-    img1 = torch.empty((F, S, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
-    for s in range(S):
-        u = s % U
+        for k0 in range(0, P, 16):
+            b0[u, k0:k0 + 16], b1[u, k0:k0 + 16] = render_frames_torch(torch, streams[u], state, range(k0, min(P, k0 + 16)), g)
+    th0.join()
+    if render0_err:
+        raise render0_err[0]
+    b0[0].copy_(torch.from_numpy(h0))
+    b1[0].copy_(torch.from_numpy(h1))
+    del h0, h1
+    img0 = torch.empty((P, S, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
+    img1 = torch.empty((P, S, H_IMG, W_IMG), dtype=torch.uint8, device=dev)
+    for u in range(U):                              # stream s is a replica of rendered stream s % U; replica 0 without extra noise
+        n_rep = len(range(u, S, U))
         for dst, src in ((img0, b0), (img1, b1)):
-            if s < U:
-                dst[:, s] = src[u]
-            else:
-                noise = torch.randint(-2, 3, (F, H_IMG, W_IMG), generator=g, device=dev, dtype=torch.int16)
-                dst[:, s] = (src[u].to(torch.int16) + noise).clamp_(0, 255).to(torch.uint8)
+            dst[:, u] = src[u]
+            for j0 in range(1, n_rep, 8):
+                j1 = min(n_rep, j0 + 8)
+                noise = torch.randint(-2, 3, (P, j1 - j0, H_IMG, W_IMG), generator=g, device=dev, dtype=torch.int16)
+                dst[:, u + U * j0:u + U * j1:U] = (src[u].to(torch.int16).unsqueeze(1) + noise).clamp_(0, 255).to(torch.uint8)
     del b0, b1, tex_dev, rays_dev
     # IMU samples per step, all streams, as flat arrays for the batched push
-    imu_steps = []
-    its = [iter(st.imu) for st in streams]
-    pend = [next(it, None) for it in its]
-    for k in range(F):
-        idx, ts, gy, ac = [], [], [], []
-        for u, st in enumerate(streams):
-            tf = st.frame_time(k)
-            batch = []
-            while pend[u] is not None and pend[u].timestamp <= tf:
-                batch.append(pend[u])
-                pend[u] = next(its[u], None)
-            for s in range(u, S, U):
-                for m in batch:
-                    idx.append(s); ts.append(m.timestamp); gy.append(m.angular_velocity); ac.append(m.linear_acceleration)
-        imu_steps.append((np.array(idx, np.int32), np.array(ts, np.float64), np.array(gy, np.float64).reshape(-1, 3),
-                          np.array(ac, np.float64).reshape(-1, 3)))
+    frame_times = np.array([[st.frame_time(k) for st in streams] for k in range(F)])
+    imu_steps = imu_feed_steps([mirrored_imu(st, P, B, frame_times[-1, u]) for u, st in enumerate(streams)], frame_times, S)
     # The filter's copy of the IMU feed.  Staggered start: the filters of the odd replicas never see their first 10 IMU samples
     # (one frame period), so the sample that completes their gravity initialisation (the 200th, msckf.py:172-175) is newer than
     # frame 0: by the data-defined rule of the library they are not live at step 0 (that frame's features are dropped,
@@ -562,7 +712,8 @@ def main():
         i0, t0_, g0, a0 = imu_steps[0]
         drop = (((i0 // U) % 2) == 1) & (t0_ < t0_.min() + 10.0 / 200.0 - 1e-6)
         imu_steps_f[0] = (i0[~drop], t0_[~drop], g0[~drop], a0[~drop])
-    frame_ts = [[streams[s % U].frame_time(k) for s in range(S)] for k in range(F)]
+    rep_of = np.arange(S) % U
+    frame_ts = [frame_times[k][rep_of] for k in range(F)]
     gen_s = time.time() - t_gen
 
     # Optional CU partition (AV_FE_CUS="first:count" for the front-end's stream, AV_MSCKF_CUS for the filter's inside the
@@ -615,7 +766,7 @@ def main():
         torch.cuda.empty_cache()
 
     path = CompletePath(torch, dev, eng, flt, filt_stream,
-                        (lambda k: (host0[k], host1[k])) if host0 is not None else (lambda k: (img0[k], img1[k])),
+                        (lambda k: (host0[pool_index(k, P, B)], host1[pool_index(k, P, B)])) if host0 is not None else (lambda k: (img0[pool_index(k, P, B)], img1[pool_index(k, P, B)])),
                         host0 is not None, imu_steps, imu_steps_f, frame_ts)
     path.step_times = [] if os.environ.get('AV_BENCH_STEP_TIMES') else None     # diagnostic: wall time at which every frame's features were handed to the filter
     path.n_frames = len(frame_ts)
@@ -641,11 +792,11 @@ def main():
         sys.stderr.write('bench.py: pre-roll did not reach the steady state: %s\n' % c_pre)
         return 3
     # ---- the contract's W untimed warm-up steps ----
-    # (device-resident filter: stepped with front-end and filter strictly alternating, the filter's phase chains under HIP events --
-    #  what the chain takes with the GPU to itself, reported beside the in-path figure as roofline_msckf.exclusive)
+    # (--full with the device-resident filter: stepped with front-end and filter strictly alternating, the filter's phase chains under
+    #  HIP events -- what the chain takes with the GPU to itself, reported beside the in-path figure as roofline_msckf.exclusive)
     w_e0 = None
     if flt is not None and Wm > 0:
-        if flt.device_resident():
+        if args.full and flt.device_resident():
             w_e0 = flt.work(enable=1); w_e0.update(flt.work_executed())
             path.force_serial = True
         run_pipelined(PRE, PRE + Wm)
@@ -679,12 +830,16 @@ def main():
     if step_times:
         tt = [t for k, t in step_times if k >= T0]
         sys.stderr.write('[step intervals ms] ' + ' '.join('%.1f' % ((b_ - a_) * 1e3) for a_, b_ in zip(tt[:-1], tt[1:])) + '\n')
+    if args.dump_outputs and rank == 0:             # the last timed step's results, before anything else runs on the engines
+        if flt is not None:
+            assert poses0[-1][0] == T0 + K - 1
+        dump_outputs(args.dump_outputs, eng.read_features(), poses0[-1][1][:] if flt is not None else None)
     c_t1 = flt.counters() if flt is not None else None
     w_t1 = flt.work(enable=0) if flt is not None else None
     if w_t1 is not None: w_t1.update(flt.work_executed())
     fe_elapsed = None
     timing_fe = None
-    if with_msckf:                                   # same engine state, next K frames, front-end only
+    if with_msckf and args.full:                     # same engine state, next K frames, front-end only
         barrier()
         t1 = time.perf_counter()
         for k in range(T0 + K, F):
@@ -706,9 +861,9 @@ def main():
 
     # ---- the batch sizes the EuRoC configs really have (latency-bound regimes), same frames, own small engine pairs ----
     regimes = None
-    if with_msckf and world == 1 and not args.no_regimes and tuple(args.grid) == (4, 5, 15):
+    if args.full and with_msckf and world == 1 and not args.no_regimes and tuple(args.grid) == (4, 5, 15):
         n_pre_r = PREROLL_FULL + 1
-        n_st_r = max(1, min(20, F - n_pre_r))
+        n_st_r = max(1, min(20, P - n_pre_r))      # regimes step through resident frames only
         regimes = []
         for name, grid_r, S_r, host_r, what in (
                 ('single_stream', (4, 5, 15), 1, False, 'BASELINE configs[2] batch size: one sequence on one GPU (also configs[3] per GPU)'),
@@ -741,7 +896,7 @@ def main():
                              ('followed in the same step by the batched HIP MSCKF (propagation, augmentation, triangulation, Jacobians + '
                               'null-space + gate, QR-compressed update, pruning) on the published features'
                               if with_msckf else 'MSCKF not in the step (configs[1] literally)')),
-                'streams_per_gpu': S, 'unique_rendered_streams': U, 'parallelism': 'stream-sharded x%d' % world,
+                'streams_per_gpu': S, 'unique_rendered_streams': U, 'resident_frames': P, 'frames_stepped': F, 'turn_frames': [B, P - 1] if F > P else None, 'parallelism': 'stream-sharded x%d' % world,
                 'pipelines_per_gpu': n_pipes,
                 'replication': ('%d distinct streams (own scene, trajectory speed 0.7-1.6x, 0-2 s phase; stream 0 = the stream the CPU path replays), '
                                 'replicated to %d per GPU with +-2 grey levels of per-replica noise' % (U, S)) +
@@ -792,6 +947,7 @@ def main():
             'filter_state': ('device-resident (state, observation map, selections and injection on the device; the feature message is read from the front-end\'s device buffers)' if (flt is not None and flt.device_resident()) else ('host bookkeeping (AV_MSCKF_STORE=host)' if flt is not None else None)),
             'msckf_in_step': with_msckf, 'msckf_wall_ms_per_step': 1e3 * msckf_s[0] / K, 'msckf_push_imu_ms_per_step': 1e3 * push_s[0] / K,
             'frontend_only_frames_per_s': (world * S * K / fe_elapsed) if fe_elapsed else None,
+            'full': args.full,
         }
         if regimes is not None:
             out['regimes'] = regimes
@@ -831,15 +987,15 @@ def main():
                        'summed over the %d groups, inside the timed region of the complete path (so it includes waiting for CUs the front-end holds)'
                        % int(os.environ.get('AV_MSCKF_GROUPS', ('2' if S >= 1024 else '1') if flt.device_resident() else ('4' if S >= 256 else ('2' if S >= 64 else '1')))),
             }
-        if world == 1 and not args.no_cpu_baseline:
-            n_traj = (T0 + K) if with_msckf else 0
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            n_traj = min(T0 + K, P) if with_msckf else 0        # the frames before the first turn
             cb = cpu_baseline(cfg, with_msckf, seed=stream_seed0, max_frames=max(400, n_traj), traj_frames=n_traj)
             cpu_traj, truth = cb.pop('_traj', None), cb.pop('_truth', None)
             out['cpu_baseline'] = cb
             out['cpu_baseline_all_cores'] = cpu_baseline_all_cores(with_msckf, grid=args.grid)
             if with_msckf and cpu_traj:
                 from uav_airvision_amd.evaluate import ate
-                gpu_traj = np.array([[frame_ts[k][0]] + [float(v) for v in o[0, 2:9]] for k, o in sorted(poses0, key=lambda e: e[0]) if o[0, 0] > 0.5])
+                gpu_traj = np.array([[frame_ts[k][0]] + [float(v) for v in o[0, 2:9]] for k, o in sorted(poses0, key=lambda e: e[0]) if o[0, 0] > 0.5 and k < n_traj])
                 cpu_traj, truth = np.array(cpu_traj), np.array(truth)
                 a_gc, a_gt, a_ct = ate(gpu_traj, cpu_traj, max_dt=1e-6), ate(gpu_traj, truth, max_dt=1e-6), ate(cpu_traj, truth, max_dt=1e-6)
                 n_c = min(len(gpu_traj), len(cpu_traj))
@@ -850,7 +1006,7 @@ def main():
                     'frames': int(a_gc['n']),
                     'what': 'stream 0 of the GPU batch (frames 0..%d, pre-roll included) against the CPU port of the reference path on the same '
                             'images and IMU samples; truth = the synthetic trajectory; ATE = RMSE after SE(3) alignment '
-                            '(uav_airvision_amd/evaluate.py)' % (T0 + K - 1)}
+                            '(uav_airvision_amd/evaluate.py)' % (n_traj - 1)}
         # sanity of the roofline figures: the line is printed either way (a failed check must not cost the measurement), the exit
         # code says whether it can be trusted
         r_ = out['roofline']

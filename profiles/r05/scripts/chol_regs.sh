@@ -4,7 +4,7 @@ set -o pipefail
 O=$PWD/gpurun_out/r05q; mkdir -p $O
 timeout -k 10 900 python -m pytest tests/test_gpu_msckf.py -x -q -m gpu -k "golden" > $O/pytest_msckf.txt 2>&1 || { tail -30 $O/pytest_msckf.txt; exit 1; }
 tail -2 $O/pytest_msckf.txt
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_i.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_i.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
 python3 - $O/bench_i.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); m=d.get('roofline_msckf') or {}

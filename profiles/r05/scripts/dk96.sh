@@ -2,7 +2,7 @@
 set -o pipefail
 O=$PWD/gpurun_out/r05q; mkdir -p $O
 for v in "AV_X=0" "AV_X=1" "AV_X=2"; do
-env $v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_m.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+env $v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_m.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
 python3 - $O/bench_m.json "$v" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); m=d.get('roofline_msckf') or {}

@@ -5,7 +5,7 @@ O=$PWD/gpurun_out/r05q; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests/test_gpu_msckf.py tests/test_gpu_pipeline.py -x -q -m gpu > $O/pytest_msckf.txt 2>&1 || { tail -30 $O/pytest_msckf.txt; exit 1; }
 tail -2 $O/pytest_msckf.txt
 for v in "AV_X=0" "AV_DK_WG=256" "AV_X=1"; do
-env $v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_l.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+env $v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_l.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
 python3 - $O/bench_l.json "$v" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); m=d.get('roofline_msckf') or {}

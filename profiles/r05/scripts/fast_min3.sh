@@ -4,8 +4,8 @@ set -o pipefail
 O=$PWD/gpurun_out/r05q; mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_ops.py tests/test_gpu_frontend.py -m gpu -x -q > $O/pytest_subset.txt 2>&1; rc=$?; tail -3 $O/pytest_subset.txt; [ $rc -eq 0 ] || exit 1
 for rep in 1 2; do
-python bench.py --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_$rep.json 2> $O/e.txt; echo "fe rc $?"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_full_$rep.json 2> $O/e.txt; echo "full rc $?"
+python bench.py --full --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_$rep.json 2> $O/e.txt; echo "fe rc $?"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_full_$rep.json 2> $O/e.txt; echo "full rc $?"
 done
 for f in $O/bench_fe_*.json $O/bench_full_*.json; do python3 - $f <<'PY'
 import json,sys

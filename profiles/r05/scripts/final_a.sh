@@ -2,10 +2,10 @@
 # round-5 final bench lines: driver command, default, front-end only, configs[4] shape
 set -o pipefail
 O=$PWD/gpurun_out/r05_final; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmd_s2048_r05.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
-python bench.py > $O/bench_default_s2048_r05.json 2> $O/e2.txt || { tail -5 $O/e2.txt; exit 1; }
-python bench.py --frontend-only --no-cpu-baseline > $O/bench_frontend_only_s2048_r05.json 2> $O/e3.txt || { tail -5 $O/e3.txt; exit 1; }
-python bench.py --grid 10 15 10 --streams 256 --steps 20 --warmup 5 > $O/bench_config5_grid10x15x10_s256_r05.json 2> $O/e4.txt || { tail -5 $O/e4.txt; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmd_s2048_r05.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+python bench.py --full > $O/bench_default_s2048_r05.json 2> $O/e2.txt || { tail -5 $O/e2.txt; exit 1; }
+python bench.py --full --frontend-only --no-cpu-baseline > $O/bench_frontend_only_s2048_r05.json 2> $O/e3.txt || { tail -5 $O/e3.txt; exit 1; }
+python bench.py --full --grid 10 15 10 --streams 256 --steps 20 --warmup 5 > $O/bench_config5_grid10x15x10_s256_r05.json 2> $O/e4.txt || { tail -5 $O/e4.txt; exit 1; }
 for f in bench_driver_cmd_s2048_r05 bench_default_s2048_r05 bench_frontend_only_s2048_r05 bench_config5_grid10x15x10_s256_r05; do python3 - $O/$f.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']; m=d.get('roofline_msckf') or {}

@@ -4,9 +4,9 @@ set -o pipefail
 O=$PWD/gpurun_out/r05e; mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_ops.py tests/test_gpu_frontend.py -m gpu -x -q > $O/pytest_subset.txt 2>&1; rc=$?; tail -5 $O/pytest_subset.txt; [ $rc -eq 0 ] || exit 1
 for dma in 1 0; do
-AV_LK_DMA=$dma python bench.py --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_dma$dma.json 2> $O/e_fe_dma$dma.txt; echo "fe dma=$dma rc $?"
-AV_LK_DMA=$dma python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_dma$dma.json 2> $O/e_dma$dma.txt; echo "full dma=$dma rc $?"
-AV_LK_DMA=$dma AV_LK_PROF=1 python bench.py --frontend-only --steps 10 --warmup 3 --no-cpu-baseline --no-regimes > $O/bench_fe_prof_dma$dma.json 2> $O/lk_phase_stamps_dma$dma.txt; grep AV_LK_PROF $O/lk_phase_stamps_dma$dma.txt
+AV_LK_DMA=$dma python bench.py --full --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_dma$dma.json 2> $O/e_fe_dma$dma.txt; echo "fe dma=$dma rc $?"
+AV_LK_DMA=$dma python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_dma$dma.json 2> $O/e_dma$dma.txt; echo "full dma=$dma rc $?"
+AV_LK_DMA=$dma AV_LK_PROF=1 python bench.py --full --frontend-only --steps 10 --warmup 3 --no-cpu-baseline --no-regimes > $O/bench_fe_prof_dma$dma.json 2> $O/lk_phase_stamps_dma$dma.txt; grep AV_LK_PROF $O/lk_phase_stamps_dma$dma.txt
 done
 for f in bench_fe_dma1 bench_fe_dma0 bench_dma1 bench_dma0; do python3 - $O/$f.json <<'PY'
 import json,sys

@@ -9,9 +9,9 @@ d=json.load(open(sys.argv[1]))
 for r in d['rows']: print("%-28s w1 %6.2f  w2 %6.2f  w4 %6.2f  w5 %6.2f  w5 %.3f ns  ticks/us %s" % (r["op"], r["w1"], r["w2"], r["w4"], r["w5"], r["w5_ns"], r.get("ticks_per_us")))
 PY
 timeout -k 10 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_frontend.py tests/test_gpu_msckf.py -m gpu -x -q > $O/pytest_subset.txt 2>&1; rc=$?; tail -5 $O/pytest_subset.txt; [ $rc -eq 0 ] || exit 1
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_tile48.json 2> $O/e_tile48.txt; echo "tile48 rc $?"; tail -2 $O/e_tile48.txt
-AV_UPD_TILE=64 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_tile64.json 2> $O/e_tile64.txt; echo "tile64 rc $?"; tail -2 $O/e_tile64.txt
-AV_LK_PROF=1 python bench.py --frontend-only --steps 10 --warmup 3 --no-cpu-baseline --no-regimes > $O/bench_fe_prof.json 2> $O/lk_phase_stamps.txt; echo "prof rc $?"; grep AV_LK_PROF $O/lk_phase_stamps.txt
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_tile48.json 2> $O/e_tile48.txt; echo "tile48 rc $?"; tail -2 $O/e_tile48.txt
+AV_UPD_TILE=64 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_tile64.json 2> $O/e_tile64.txt; echo "tile64 rc $?"; tail -2 $O/e_tile64.txt
+AV_LK_PROF=1 python bench.py --full --frontend-only --steps 10 --warmup 3 --no-cpu-baseline --no-regimes > $O/bench_fe_prof.json 2> $O/lk_phase_stamps.txt; echo "prof rc $?"; grep AV_LK_PROF $O/lk_phase_stamps.txt
 for f in bench_tile48 bench_tile64; do python3 - $O/$f.json <<'PY'
 import json,sys
 try:

@@ -5,13 +5,13 @@ O=$PWD/gpurun_out/r05q; mkdir -p $O
 AV_LK_WG=64 timeout -k 10 600 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "lk or LK or track" > $O/pytest_lk.txt 2>&1 || { tail -30 $O/pytest_lk.txt; exit 1; }
 tail -2 $O/pytest_lk.txt
 for v in "AV_LK_WG=64" "AV_X=0"; do
-env $v python bench.py --frontend-only --no-cpu-baseline > $O/bench_g.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+env $v python bench.py --full --frontend-only --no-cpu-baseline > $O/bench_g.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
 python3 - $O/bench_g.json "$v fe-only" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']
 print('%-30s value %.0f ms/step %.2f lk_ms %.3f kernels %s' % (sys.argv[2], d['value'], d['ms_per_step'], r['avg_launch_ms'], json.dumps({k: round(v,2) for k,v in d.get('kernel_ms_per_step',{}).items()})))
 PY
-env $v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_g.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+env $v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_g.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
 python3 - $O/bench_g.json "$v" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); m=d.get('roofline_msckf') or {}

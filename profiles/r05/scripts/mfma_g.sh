@@ -2,7 +2,7 @@
 set -o pipefail
 O=$PWD/gpurun_out/r05q; mkdir -p $O
 for v in "AV_X=0" "AV_MSCKF_PRIO=2" "AV_MSCKF_GROUPS=1" "AV_MSCKF_GROUPS=3" "AV_MSCKF_GROUPS=4 GPU_MAX_HW_QUEUES=8"; do
-env $v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_h.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
+env $v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_h.json 2> $O/e1.txt || { tail -5 $O/e1.txt; exit 1; }
 python3 - $O/bench_h.json "$v" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); m=d.get('roofline_msckf') or {}

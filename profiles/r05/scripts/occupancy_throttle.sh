@@ -4,7 +4,7 @@ set -o pipefail
 O=$PWD/gpurun_out/r05i; mkdir -p $O
 run() { # name, env...
   local name=$1; shift
-  env "$@" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_$name.json 2> $O/e_$name.txt
+  env "$@" python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_$name.json 2> $O/e_$name.txt
   python3 - $O/bench_$name.json $name <<'PY'
 import json,sys
 try:

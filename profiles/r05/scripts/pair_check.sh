@@ -10,10 +10,10 @@ for r in d['rows']: print("%-28s w1 %6.2f  w2 %6.2f  w4 %6.2f  w5 %6.2f  ticks/u
 PY
 timeout -k 10 600 python -m pytest tests/test_gpu_ops.py tests/test_gpu_frontend.py tests/test_gpu_pipeline.py tests/test_gpu_bench.py -m gpu -x -q > $O/pytest_subset.txt 2>&1; rc=$?; tail -4 $O/pytest_subset.txt; [ $rc -eq 0 ] || exit 1
 for pr in 1 0 1 0; do
-AV_LK_PAIR=$pr python bench.py --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_pair${pr}_$RANDOM.json 2> $O/e.txt; echo "fe pair=$pr rc $?"
+AV_LK_PAIR=$pr python bench.py --full --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_pair${pr}_$RANDOM.json 2> $O/e.txt; echo "fe pair=$pr rc $?"
 done
 for pr in 1 0; do
-AV_LK_PAIR=$pr python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_pair$pr.json 2> $O/e_pair$pr.txt; echo "full pair=$pr rc $?"; tail -2 $O/e_pair$pr.txt
+AV_LK_PAIR=$pr python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_pair$pr.json 2> $O/e_pair$pr.txt; echo "full pair=$pr rc $?"; tail -2 $O/e_pair$pr.txt
 done
 for f in $O/bench_fe_pair*.json $O/bench_pair1.json $O/bench_pair0.json; do python3 - $f <<'PY'
 import json,sys

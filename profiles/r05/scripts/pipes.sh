@@ -4,7 +4,7 @@ set -o pipefail
 O=$PWD/gpurun_out/r05q; mkdir -p $O
 for v in "--pipelines 2" "--pipelines 4" "--pipelines 4 X AV_MSCKF_GROUPS=1" "--pipelines 3"; do
 a=${v%% X *}; e=${v##* X }; [ "$e" = "$v" ] && e="AV_X=0"
-env $e python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes $a > $O/bench_t.json 2> $O/e1.txt || { tail -8 $O/e1.txt; exit 1; }
+env $e python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes $a > $O/bench_t.json 2> $O/e1.txt || { tail -8 $O/e1.txt; exit 1; }
 python3 - $O/bench_t.json "$v" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); m=d.get('roofline_msckf') or {}; r=d['roofline']

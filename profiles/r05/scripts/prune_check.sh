@@ -4,8 +4,8 @@ set -o pipefail
 O=$PWD/gpurun_out/r05g; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; rc=$?; tail -4 $O/pytest_gpu.txt; [ $rc -eq 0 ] || exit 1
 for fa in 0 1; do
-AV_FE_FAST_ASYNC=$fa python bench.py --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_fa$fa.json 2> $O/e.txt; echo "fe fast_async=$fa rc $?"
-AV_FE_FAST_ASYNC=$fa python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fa$fa.json 2> $O/e.txt; echo "full fast_async=$fa rc $?"
+AV_FE_FAST_ASYNC=$fa python bench.py --full --frontend-only --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fe_fa$fa.json 2> $O/e.txt; echo "fe fast_async=$fa rc $?"
+AV_FE_FAST_ASYNC=$fa python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_fa$fa.json 2> $O/e.txt; echo "full fast_async=$fa rc $?"
 done
 for f in bench_fe_fa0 bench_fe_fa1 bench_fa0 bench_fa1; do python3 - $O/$f.json <<'PY'
 import json,sys

@@ -2,7 +2,7 @@
 set -o pipefail
 O=$PWD/gpurun_out/r05l; mkdir -p $O
 for S in 3072 2560 2048; do
-python bench.py --streams $S --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_s$S.json 2> $O/e_s$S.txt; echo "S=$S rc $?"; tail -2 $O/e_s$S.txt
+python bench.py --full --streams $S --steps 20 --warmup 5 --no-cpu-baseline --no-regimes > $O/bench_s$S.json 2> $O/e_s$S.txt; echo "S=$S rc $?"; tail -2 $O/e_s$S.txt
 python3 - $O/bench_s$S.json <<'PY'
 import json,sys
 try:

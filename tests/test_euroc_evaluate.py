@@ -1,4 +1,5 @@
 """Host-side 'next' rows: EuRoC reader + deterministic replay, trajectory format, ATE/RTE."""
+import gzip
 import os
 
 import numpy as np
@@ -89,9 +90,16 @@ def test_trajectory_line_format_and_concatenated_runs(tmp_path):
     assert a.shape == (4, 8) and a[0, 0] == 1.0 and a[-1, 1] == 1.15
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/results/txts'), reason='reference results only exist in the build container')
-def test_parser_reads_the_reference_result_files():
-    d = '/root/reference/results/txts'
+REF_TXTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_txts')
+
+
+def test_parser_reads_the_reference_result_files(tmp_path):
+    """The reference's eight result files (results/txts/output_<seq>_offset<o>.txt), stored gzipped under
+    tests/golden/reference_txts/ and unpacked as the text files the reference wrote."""
+    d = str(tmp_path)
+    for name in sorted(os.listdir(REF_TXTS)):
+        with gzip.open(os.path.join(REF_TXTS, name), 'rb') as src, open(os.path.join(d, name[:-len('.gz')]), 'wb') as dst:
+            dst.write(src.read())
     files = sorted(os.listdir(d))
     assert len(files) == 8
     a = evaluate.load_trajectory_txt(os.path.join(d, 'output_MH_01_easy_offset40.txt'))

@@ -61,22 +61,22 @@ def test_two_rank_gloo_sharding():
     assert all0[4] == ((7, 8), 81.0) and k0 == k1 == [0.0, 1.0, 2.0, 3.0]
 
 
-REF_TXTS = '/root/reference/results/txts'
+REF_TXTS = os.path.join(ROOT, 'tests', 'golden', 'reference_txts')
 
 
 def _eight_trajectories():
-    """BASELINE configs[3]'s gather: one trajectory per EuRoC sequence, ragged lengths.  In the build container these ARE the
-    reference's eight result files (results/txts/output_<seq>_offset<o>.txt: 295 ... 2,862 poses); elsewhere, arrays of the same
-    shape family from a seeded generator."""
+    """BASELINE configs[3]'s gather: one trajectory per EuRoC sequence, ragged lengths -- the reference's eight result files
+    (results/txts/output_<seq>_offset<o>.txt: 295 ... 2,862 poses, stored gzipped under tests/golden/reference_txts/)."""
+    import gzip
+    import tempfile
     from uav_airvision_amd import evaluate
-    if os.path.isdir(REF_TXTS):
-        return [evaluate.load_trajectory_txt(os.path.join(REF_TXTS, f)) for f in sorted(os.listdir(REF_TXTS))]
-    rng = np.random.default_rng(8)
     out = []
-    for n in (2862, 1517, 2481, 295, 2592, 729, 1659, 385):
-        t = 1403636580.0 + 0.05 * np.arange(n)
-        q = rng.normal(size=(n, 4)); q /= np.linalg.norm(q, axis=1, keepdims=True)
-        out.append(np.column_stack([t, np.cumsum(rng.normal(0, 0.01, (n, 3)), 0), q]))
+    with tempfile.TemporaryDirectory() as d:
+        for name in sorted(os.listdir(REF_TXTS)):
+            path = os.path.join(d, name[:-len('.gz')])
+            with gzip.open(os.path.join(REF_TXTS, name), 'rb') as src, open(path, 'wb') as dst:
+                dst.write(src.read())
+            out.append(evaluate.load_trajectory_txt(path))
     return out
 
 

@@ -201,7 +201,8 @@ class SyntheticStream(object):
     def frame_torch(self, k, state, generator=None):
         """(cam0, cam1) uint8 tensors of frame k: `_render` restated with torch ops (fp64 geometry, fp32 bilinear lookup).  The
         sensor noise comes from torch's generator, not numpy's, so the pixels are NOT those of `frame(k)`: same scene, same
-        statistics.  Streams that must equal the CPU path's input are rendered with `frame`."""
+        statistics.  Streams that must equal the CPU path's input are rendered with `frame`.  bench.py keeps a copy of this renderer
+        with a batch axis over frames (render_frames_torch), held to it by tests/test_bench_inputs.py: change both together."""
         import torch
         t = self.frame_time(k)
         R_i_w, p = self.R_i_w(t), self.position(t)
