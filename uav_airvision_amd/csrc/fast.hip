@@ -45,10 +45,9 @@ struct FastArgs {
     int64_t mask_stride;
     int w, h, threshold;
     uint32_t* kp; int* count; int cap;
-    uint32_t* tile_kp; int* tile_count;          // [n_img][tiles][TCAP], [n_img][tiles] (tiles row-major: blockIdx.y * gridDim.x + blockIdx.x)
+    uint32_t* tile_kp; int* tile_count;          // [n_img][tiles][TCAP], [n_img][tiles] (tiles row-major: by * tiles_x + bx)
     int* overflow; int stat_stride;
-    int dbg;
-    int n_img, tiles_x, tiles_y;                 // XCD-aware 1-D launch when tiles_x > 0 (fast_kernel)
+    int n_img, tiles_x, tiles_y;                 // XCD-aware 1-D launch (fast_kernel)
     const int* index;                            // optional: image i of the launch is storage entry index[i] (shared frame store)
 };
 
@@ -116,17 +115,14 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
     constexpr int NQ = SH * PWD;                                  // 900 quad positions
     constexpr int SEG = ((NQ + 255) / 256) * 64 * 4;
     __shared__ uint16_t cand[4 * SEG];
-    // workgroup -> (image, tile).  1-D launch (a.tiles_x > 0): all tiles of an image on ONE XCD (workgroups are dealt round-robin
+    // workgroup -> (image, tile).  1-D launch: all tiles of an image on ONE XCD (workgroups are dealt round-robin
     // over the 8 XCDs, each with its own L2): neighbouring tiles share their halo rows and, with 752-byte image rows, most of
     // their 128-byte lines -- spread over eight L2s every line was fetched ~3.7x (PMC, profiles/r03), on one L2 once.
-    int img_i, bx, by;
-    if (a.tiles_x > 0) {
-        const int L = blockIdx.x, j = L >> 3, per = a.tiles_x * a.tiles_y;
-        img_i = (L & 7) + 8 * (j / per);
-        if (img_i >= a.n_img) return;
-        const int t = j % per;
-        by = t / a.tiles_x; bx = t - by * a.tiles_x;
-    } else { img_i = blockIdx.z; bx = blockIdx.x; by = blockIdx.y; }
+    const int L = blockIdx.x, wg = L >> 3, per = a.tiles_x * a.tiles_y;
+    int img_i = (L & 7) + 8 * (wg / per);
+    if (img_i >= a.n_img) return;
+    const int tl = wg % per;
+    const int by = tl / a.tiles_x, bx = tl - by * a.tiles_x;
     if (a.index) img_i = a.index[img_i];                     // storage entry of this image (shared frame store): image, mask and lists
     const uint8_t* img = a.img + img_i * a.img_stride;
     const int x0 = bx * TW, y0 = by * TH;
@@ -192,7 +188,7 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
             sr = i / PWD; q = i - sr * PWD;
             scw[i] = 0;
             const int y = y0 - 1 + sr;
-            if (y >= 3 && y < a.h - 3 && !(a.dbg & 2)) {
+            if (y >= 3 && y < a.h - 3) {
                 const uint32_t* rowc = pixw + (sr + 3) * PWD + q;
                 const uint32_t C = rowc[0], L = q > 0 ? rowc[-1] : 0u, R = rowc[1];
                 const uint32_t U = rowc[-3 * PWD], D = rowc[3 * PWD];
@@ -234,7 +230,7 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!(a.dbg & 1)) for (int k = lane; k < wcnt; k += 64) {
+    for (int k = lane; k < wcnt; k += 64) {
         const int i = cand[wave * SEG + k];
         const int sr = i / SP, pc = i - sr * SP;
         sc[i] = (uint8_t)fast_score(&pix[(sr + 3) * PW + pc], t);
@@ -254,7 +250,7 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
         const int r = i / (TW / 4), q = 1 + (i - r * (TW / 4));
         const uint32_t* rowc = scw + (r + 1) * SPD + q;
         const uint32_t B = rowc[0];
-        if (B == 0 || (a.dbg & 4)) continue;                                 // no positive score among the four pixels
+        if (B == 0) continue;                                 // no positive score among the four pixels
         // per score row the 6-byte window [pc-1 .. pc+4] as (lo, hi): pixel k sees bytes k, k+1, k+2
         uint32_t lo[3], hi[3];
 #pragma unroll
@@ -280,7 +276,7 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
             const int x = x0 + 4 * (q - 1) + k, y = y0 + r;
             bool keep = ((gt[k >> 1] >> (16 * (k & 1))) & 0xFFFFu) != 0 && x < a.w && y < a.h;
             if (keep && a.mask) keep = mask_dw ? ((mask4[it] >> (8 * k)) & 0xFF) != 0 : a.mask[img_i * a.mask_stride + (size_t)y * a.w + x] != 0;
-            if (keep && !(a.dbg & 8)) {
+            if (keep) {
                 const int slot = atomicAdd(&nsurv, 1);            // LDS atomic; a tile has <= TCAP strict maxima
                 surv_word[slot] = ((uint32_t)s << AV_KP_RASTER_BITS) | (AV_KP_RASTER_MASK - (uint32_t)(y * a.w + x));
             }
@@ -289,8 +285,7 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
     __syncthreads();
     const int ns = nsurv;
     if (a.tile_kp) {
-        const size_t tile = a.tiles_x > 0 ? (size_t)img_i * (a.tiles_x * a.tiles_y) + by * a.tiles_x + bx
-                                          : (size_t)img_i * (gridDim.x * gridDim.y) + blockIdx.y * gridDim.x + blockIdx.x;
+        const size_t tile = (size_t)img_i * (a.tiles_x * a.tiles_y) + by * a.tiles_x + bx;
         if (tid == 0) a.tile_count[tile] = ns;
         for (int q = tid; q < ns; q += 256) a.tile_kp[tile * TCAP + q] = surv_word[q];
         return;
@@ -329,11 +324,9 @@ int av_launch_fast(const uint8_t* img, int64_t img_stride, int img_pitch, int bo
     a.w = w; a.h = h; a.threshold = threshold;
     a.kp = kp; a.count = count; a.cap = cap;
     a.tile_kp = tile_kp; a.tile_count = tile_count; a.overflow = overflow; a.stat_stride = stat_stride;
-    { const char* e = getenv("AV_FAST_DBG"); a.dbg = e ? atoi(e) : 0; }
-    static const bool xcd_map = [] { const char* e = getenv("AV_FAST_XCD"); return !(e && atoi(e) == 0); }();      // A/B switch
     const int tx = (w + TW - 1) / TW, ty = (h + TH - 1) / TH;
-    a.n_img = n_img; a.tiles_x = xcd_map ? tx : 0; a.tiles_y = ty; a.index = index;
-    dim3 grid = xcd_map ? dim3((unsigned)(tx * ty) * 8u * (unsigned)((n_img + 7) / 8)) : dim3(tx, ty, n_img);
+    a.n_img = n_img; a.tiles_x = tx; a.tiles_y = ty; a.index = index;
+    dim3 grid((unsigned)(tx * ty) * 8u * (unsigned)((n_img + 7) / 8));
     // (An occupancy throttle -- unused dynamic LDS holding the detector to 6 / 5 / 4 workgroups per CU so that the filter's kernels find
     //  room beside it -- was measured in round 5: 156.9 / 154.7 / 149.7 k against 157.5 k frames/s.  profiles/r05/README.md)
     // (The same 64 x 48 tile worked by two / one wavefront instead of four -- a workgroup of fewer wavefronts is easier to place beside the

@@ -781,7 +781,6 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     const int cur0 = par ^ 1;                // curr cam0 pyramid slot (0/1), cam1 pyramid is slot 2
     int64_t sstride = 3 * fe->lay.bytes; const int64_t slotb = fe->lay.bytes;
     int rc;
-    static const bool zc_off = [] { const char* e = getenv("AV_FE_ZERO_COPY"); return e && atoi(e) == 0; }();      // A/B switch
     const uint8_t *I_prev0, *I_cur0, *I_cur1, *P_prev0, *P_cur0, *P_cur1; int64_t st_prev0;
     if (frames) {
         // pyramids and level-0 images of both cameras lie in the store, built when the frame was uploaded: entry e of camera c at
@@ -794,7 +793,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         bool wrote_l0 = true;
         if (fe->pre_on && fe->pre_img0 == img0 && fe->pre_img1 == img1 && fe->pre_stride == img_stride) wrote_l0 = fe->pre_wrote_l0;      // built by av_frontend_prestage
         else { Span sp(fe, 0, st);
-          if ((rc = av_launch_pyramid(img0, img1, img_stride, S, 2, fe->geom, fe->pyr, sstride, slotb, cur0, 2, st, !(inputs_persist && !zc_off), &wrote_l0))) return rc; }
+          if ((rc = av_launch_pyramid(img0, img1, img_stride, S, 2, fe->geom, fe->pyr, sstride, slotb, cur0, 2, st, !inputs_persist, &wrote_l0))) return rc; }
         fe->pre_on = false;
         fe->l0_img[cur0] = wrote_l0 ? nullptr : img0; fe->l0_img[2] = wrote_l0 ? nullptr : img1;
         fe->l0_stride[cur0] = fe->l0_stride[2] = img_stride;
@@ -815,31 +814,30 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         return av_launch_fast(fast_img, sstride, fe->geom.pitch[0], AV_PYR_BORDER, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold,
                               nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, fs);
     };
-    // per-stream glue kernels: 256-thread workgroups.  (AV_FE_GLUE_WG=64, one wavefront per stream -- bit-exact, the kernels take any
-    // workgroup size -- measured in round 5: glue 0.78 against 0.66 ms alone, 0.94 against 1.07 beside the filter, and the detector next
+    // per-stream glue kernels: 256-thread workgroups.  (64, one wavefront per stream -- bit-exact, the kernels take any
+    // workgroup size -- was measured in round 5: glue 0.78 against 0.66 ms alone, 0.94 against 1.07 beside the filter, and the detector next
     // to them 2.46 against 2.31: front-end alone 216.9 against 220.3 k, complete path 173.3 against 174.3 k.  profiles/r05/README.md)
-    static const int gwg = [] { const char* e = getenv("AV_FE_GLUE_WG"); return (e && atoi(e) == 64) ? 64 : 256; }();
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(track_prepare_kernel, dim3((d.NT + 255) / 256, S), dim3(256), 0, st, d, par);
       AV_LAUNCH_CHECK(); }
     { Span sp(fe, 1, st);
       if ((rc = av_launch_lk(P_prev0, P_cur0, sstride, S, fe->geom, d.trk_prev, d.trk_next, d.trk_status, d.trk_count, d.NT, d.NT, fe->lk, st, nullptr, I_prev0, st_prev0, I_cur0, img_stride, map_prev, map_cur))) return rc; }
     { Span sp(fe, 3, st);
-      hipLaunchKernelGGL(track_gate_kernel, dim3(S), dim3(gwg), 0, st, d);
+      hipLaunchKernelGGL(track_gate_kernel, dim3(S), dim3(256), 0, st, d);
       AV_LAUNCH_CHECK(); }
     { Span sp(fe, 1, st);
       if ((rc = av_launch_lk(P_cur0, P_cur1, sstride, S, fe->geom, d.sv_p0, d.sv_p1, d.sv_st, d.sv_count, d.NT, d.NT, fe->lk, st, nullptr, I_cur0, img_stride, I_cur1, img_stride, map_cur, map_cur))) return rc; }
     { Span sp(fe, 1, st);
       if ((rc = av_launch_lk(P_cur1, P_cur0, sstride, S, fe->geom, d.sv_p1, d.sv_back, d.sv_st2, d.sv_count, d.NT, d.NT, fe->lk, st, nullptr, I_cur1, img_stride, I_cur0, img_stride, map_cur, map_cur))) return rc; }
     { Span sp(fe, 3, st);
-      hipLaunchKernelGGL(rebin_kernel, dim3(S), dim3(gwg), 0, st, d, par);
+      hipLaunchKernelGGL(rebin_kernel, dim3(S), dim3(256), 0, st, d, par);
       AV_LAUNCH_CHECK(); }
     // (FAST on a second HIP stream beside the temporal / stereo LK launches -- it reads only the new cam0 image and is first needed by
     //  select_kernel -- was measured in round 5: front-end alone 196.6 k against 205.1 k frames/s, complete path 157.7 against 157.3 k:
     //  the LK launches slow down by more than the detector's time; profiles/r05/README.md)
     if (!frames && (rc = launch_fast(st))) return rc;                           // (frame store: FAST ran when the frame was uploaded)
     { Span sp(fe, 3, st);
-      hipLaunchKernelGGL(select_kernel, dim3(S), dim3(gwg), sizeof(int) * (3 * d.C + 1 + d.n_tiles + 1), st, d);
+      hipLaunchKernelGGL(select_kernel, dim3(S), dim3(256), sizeof(int) * (3 * d.C + 1 + d.n_tiles + 1), st, d);
       AV_LAUNCH_CHECK(); }
     const int r1_launch = any_first ? d.CC : d.C * (d.gmax < CAND_R1 ? d.gmax : CAND_R1);
     { Span sp(fe, 1, st);
@@ -847,7 +845,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     { Span sp(fe, 1, st);
       if ((rc = av_launch_lk(P_cur1, P_cur0, sstride, S, fe->geom, d.cand_p1, d.cand_back, d.cand_st2, d.r1_count, d.CC, r1_launch, fe->lk, st, d.r1_list, I_cur1, img_stride, I_cur0, img_stride, map_cur, map_cur))) return rc; }
     { Span sp(fe, 3, st);
-      hipLaunchKernelGGL(cand_round2_kernel, dim3(S), dim3(gwg), 0, st, d);
+      hipLaunchKernelGGL(cand_round2_kernel, dim3(S), dim3(256), 0, st, d);
       AV_LAUNCH_CHECK(); }
     if (d.gmax > CAND_R1) {                       // round 2: the rest of the cells that are still short of inliers (usually none)
         const int r2_launch = d.C * (d.gmax - CAND_R1);
@@ -858,7 +856,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     }
     size_t fin_lds = sizeof(unsigned long long) * d.NSORT + sizeof(int) * (2 * d.C * d.gmin + 2 * d.C + 3 * (d.C + 1) + 4);
     { Span sp(fe, 3, st);
-      hipLaunchKernelGGL(finalize_kernel, dim3(S), dim3(gwg), fin_lds, st, d, par);
+      hipLaunchKernelGGL(finalize_kernel, dim3(S), dim3(256), fin_lds, st, d, par);
       AV_LAUNCH_CHECK(); }
     fe->parity = par ^ 1;
     if (frames) { AV_HIP(hipEventRecord(fe->fs.stepped, st)); fe->fs.any_step = true; }
@@ -1040,12 +1038,11 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
-    static const bool zc_off = [] { const char* e = getenv("AV_FE_ZERO_COPY"); return e && atoi(e) == 0; }();
     const int cur0 = fe->parity ^ 1;         // the slots the next step will call cur0 / 2
     int rc;
     bool wrote_l0 = true;
     { Span sp(fe, 0, st);
-      if ((rc = av_launch_pyramid(img0_dev, img1_dev, img_stride, fe->d.S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur0, 2, st, zc_off, &wrote_l0))) return rc; }
+      if ((rc = av_launch_pyramid(img0_dev, img1_dev, img_stride, fe->d.S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur0, 2, st, false, &wrote_l0))) return rc; }
     // (The detector's pass over the new cam0 image -- it reads nothing but the image -- enqueued here as well ran at its exclusive speed,
     //  1.55 ms against 2.3 beside the filter's back end, and the LK launches took what it gave back: 173.4-173.9 against 174.1-175.2 k
     //  frames/s.  profiles/r05/README.md)

@@ -60,7 +60,7 @@ struct LKArgs {
     // >= min_eig; the step-length test is decided in float outside (eps_lo, eps_hi) = eps2 (1 -+ 2^-18) and in fp64 inside
     float min_eig_up, eps_lo, eps_hi;
     double min_eig;             // the general kernel's fp64 form
-    int n_set, gx;              // XCD-aware 1-D launch (gx > 0): gx workgroups per point set, see lk_track_g16_body
+    int n_set, gx;              // XCD-aware 1-D launch of the 16-lane kernels: gx workgroups per point set, see lk_track_g16_body
     // Level 0 straight from the caller's image (w x h, tightly packed rows) instead of a padded copy in the pyramid: non-null =
     // the I (resp. J) side reads level 0 at img + set * img_stride, with BORDER_REFLECT_101 indexing for the few windows that
     // reach over the image border (what the padded level's frame holds).  Levels >= 1 always come from the padded pyramid.
@@ -379,9 +379,8 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
     // one stream land on all eight XCDs and every L2 fetches that stream's two pyramids (profiles/r03/fetch_calib.json, rows32: a
     // window gather in image order reads 2.6x the image bytes).  The 1-D launch keeps a set's workgroups on ONE XCD: id L ->
     // XCD label L & 7, set = label + 8 * ((L >> 3) / gx), block = (L >> 3) % gx.  Placement only: any mapping is correct.
-    int s, bx;
-    if (a.gx > 0) { const int L = blockIdx.x, j = L >> 3; s = (L & 7) + 8 * (j / a.gx); bx = j % a.gx; if (s >= a.n_set) return false; }
-    else { s = blockIdx.y; bx = blockIdx.x; }
+    const int L = blockIdx.x, wg = L >> 3, s = (L & 7) + 8 * (wg / a.gx), bx = wg % a.gx;
+    if (s >= a.n_set) return false;
     const int slot = bx * PTS + g;
     const int sI = a.mapI ? a.mapI[s] : s, sJ = a.mapJ ? a.mapJ[s] : s;      // storage entries of the two images (scalar loads)
     if (sI < 0 || sJ < 0) return false;
@@ -632,15 +631,15 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
 // filter's single-wavefront tasks, each of which takes ONE slot on ONE SIMD, a CU with three free slots starts nothing -- every
 // resident filter wavefront can keep a whole LK workgroup out: complete path 161.6 -> 168.9 k.  (profiles/r05/README.md)
 template <int WIN> __global__ __launch_bounds__(64, 5) void lk_track_g16_kernel(LKArgs a) { lk_track_g16_body<WIN, 5, false, 4>(a); }
-// AV_LK_WG=256 (A/B): four wavefronts (16 points) per workgroup, rounds 2-4's launch shape.  (Two wavefronts per workgroup lie in
-// between: front-end alone 218.3 k against 220.2 k, complete path 166.2 against 168.7 k.  profiles/r05/README.md)
-template <int WIN> __global__ __launch_bounds__(256, 5) void lk_track_g16_w4_kernel(LKArgs a) { lk_track_g16_body<WIN, 5>(a); }
+// (Two wavefronts per workgroup lie in between: front-end alone 218.3 k against 220.2 k, complete path 166.2 against 168.7 k.
+//  profiles/r05/README.md)
 // (Forward and backward pass of a stereo match as ONE launch -- the 16 lanes that tracked a point forward track it back, three launches
 //  fewer per front-end step -- was built and measured in round 5: front-end alone 207.9 / 206.2 k against 206.1 / 206.8 k frames/s, one
 //  stream 0.649 against 0.645 ms per frame: nothing, removed.  profiles/r05/README.md)
 // (a four-wave build that leaves 128 register rows per SIMD to the filter's kernels: 146.7 k against 152.8 k frames/s, round 4)
-// AV_LK_PROF=1: the same body with s_memtime stamps at the phase boundaries (I staging / patch set-up / J staging / Newton
-// iterations), summed over the wavefronts of every launch and printed at exit (profiles/r05/lk_phase_stamps.txt).
+// AV_LK_PROF=1: the same body, four wavefronts (16 points) per workgroup, with s_memtime stamps at the phase boundaries (I staging /
+// patch set-up / J staging / Newton iterations), summed over the wavefronts of every launch and printed at exit
+// (profiles/r05/lk_phase_stamps.txt).
 template <int WIN> __global__ __launch_bounds__(256, 5) void lk_track_g16_prof_kernel(LKArgs a) { lk_track_g16_body<WIN, 5, true>(a); }
 
 static unsigned long long* g_lk_prof = nullptr;
@@ -858,13 +857,11 @@ static bool lk_prof_on()
     return prof;
 }
 
-// grid of the 16-lane kernels: XCD-aware 1-D launch (lk_track_g16_body) unless AV_LK_XCD=0
+// grid of the 16-lane kernels: XCD-aware 1-D launch (lk_track_g16_body)
 static dim3 lk_g16_grid(LKArgs& a, int n_set, int launch_pts, int pts_per_wg)
 {
-    static const bool xcd_map = [] { const char* e = getenv("AV_LK_XCD"); return !(e && atoi(e) == 0); }();      // A/B switch
-    const int gx = (launch_pts + pts_per_wg - 1) / pts_per_wg;
-    a.n_set = n_set; a.gx = xcd_map ? gx : 0;
-    return xcd_map ? dim3((unsigned)gx * 8u * (unsigned)((n_set + 7) / 8)) : dim3(gx, n_set);
+    a.n_set = n_set; a.gx = (launch_pts + pts_per_wg - 1) / pts_per_wg;
+    return dim3((unsigned)a.gx * 8u * (unsigned)((n_set + 7) / 8));
 }
 
 int av_launch_lk(const uint8_t* pyrI, const uint8_t* pyrJ, int64_t stream_stride, int n_set, const PyrGeom& g,
@@ -884,13 +881,11 @@ int av_launch_lk(const uint8_t* pyrI, const uint8_t* pyrJ, int64_t stream_stride
         return AV_OK;
     }
     const bool prof = lk_prof_on();
-    static const bool w1 = [] { const char* e = getenv("AV_LK_WG"); return !(e && atoi(e) == 256); }();      // one wavefront per workgroup; AV_LK_WG=256 (A/B): four
-    const int wgp = (prof || !w1) ? 256 : 64;
+    const int wgp = prof ? 256 : 64;             // one wavefront per workgroup; the profiling kernel: four
     const dim3 grid = lk_g16_grid(a, n_set, launch_pts, wgp / 16);
     a.prof = g_lk_prof;
     if (prof) hipLaunchKernelGGL(lk_track_g16_prof_kernel<15>, grid, dim3(256), 0, st, a);
-    else if (wgp == 64) hipLaunchKernelGGL(lk_track_g16_kernel<15>, grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(lk_track_g16_w4_kernel<15>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(lk_track_g16_kernel<15>, grid, dim3(64), 0, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -353,7 +353,7 @@ struct FeatArgs {
     const int* feat_list;                // optional: team t processes feature feat_list[t] (launch buckets by track length)
     int n_list;                          // teams to run in this launch
     int team_doubles;                    // LDS doubles per team (wavefront teams: four per workgroup)
-    unsigned long long* prof;            // optional [8] phase stamps of team 0 (diagnostic runs, AV_MSCKF_TIMING)
+    unsigned long long* prof;            // optional [8] phase stamps of team 0 (diagnostic runs, AV_DEV_FPROF)
     int compact;                         // > 0: the output rows hold ONLY the feature's own 6 M camera columns, `compact` doubles per row (the pruning phase of the
                                          // device-resident filter: every candidate has the same two cameras, and the update gathers exactly these columns)
     int zero_fill;                       // 1: clear the full-width output rows first (columns of cameras the feature was not seen
@@ -841,7 +841,7 @@ static int launch_feature_kernel(FeatArgs a, int cnt, int Mx, hipStream_t st)
     a.Mmax = Mx; a.n_list = cnt;
     // team size: 16 lanes (one DPP row, 16 features per workgroup) for the two-observation features of the prune path,
     // one wavefront up to 4 observations, one workgroup beyond.  (env: A/B and debugging aid, forces workgroup teams)
-    const int team = getenv("AV_FEATURE_BLOCK_TEAMS") ? 256 : (Mx <= 2 ? 16 : (Mx <= 4 ? 64 : 256));
+    const int team = Mx <= 2 ? 16 : (Mx <= 4 ? 64 : 256);
     const size_t per = (feature_lds_bytes(Mx, team) + 7) / 8 * 8;
     a.team_doubles = (int)(per / 8);
     const size_t lds = per * (256 / team);
@@ -2045,13 +2045,6 @@ template <typename UA> __device__ __forceinline__ void upd_info_body(const UA& a
 
 __global__ __launch_bounds__(UT) void update_front_kernel(UpdArgs a) { update_front(a); }
 __global__ __launch_bounds__(UT) void update_back_kernel(UpdArgs a) { update_back(a); }
-// `list` (optional): the streams to run, so that the 1024-thread workgroups exist only for the streams that really compress
-__global__ __launch_bounds__(UT) void update_front_batch_kernel(const UpdArgs* __restrict__ arr, const int* __restrict__ list)
-{
-    const UpdArgs a = arr[list ? list[blockIdx.x] : (int)blockIdx.x];  // block-uniform: lives in scalar registers
-    // (a listed stream may turn out not to compress: the chained path lists every stream that COULD exceed a chunk)
-    if (a.m > 0 && a.mode == 0 && a.kdir <= 0 && upd_compress(a.m, a.nc)) update_front(a);
-}
 // Streams whose stacked Jacobian is NOT compressed (upd_compress: at most 144 rows) only need the gated feature blocks
 // gathered into the transposed work matrix: a 256-thread workgroup, no QR machinery.
 __global__ __launch_bounds__(256) void upd_gather_kernel(const UpdArgs* __restrict__ arr)
@@ -2088,7 +2081,7 @@ __global__ __launch_bounds__(256) void upd_gather_kernel(const UpdArgs* __restri
 // A is singular (the projected Jacobian is blind to a rigid motion of the observing cameras), hence E: a relative 1e-12 on the
 // diagonal, six orders below the 1e-6 parity tolerance and four above the rounding of the sums.  The Gram matrix is a sum over the
 // rows -- a wide-grid tile GEMM, split over chunks of 256 rows with the partial sums added in a fixed order (no atomics) -- and the
-// only dependent chain is one n_c-sized Cholesky in a 256-thread workgroup.  This replaces update_front_batch_kernel (a
+// only dependent chain is one n_c-sized Cholesky in a 256-thread workgroup.  This replaces a batched form of update_front (a
 // 1024-thread, 128-VGPR Householder workgroup that had to wait ~1 ms for a whole free CU) on the batched path.
 //   upd_rowmap_kernel     stacked row -> row of the block buffer (scan of the gated blocks), int[m] in the stream's Kt buffer
 //   upd_gram_mfma_kernel       Gram matrix of [Hc | r], a 32 x 32 block of the lower triangle per wavefront, into the stream's Sbuf (msckf_mfma.inc)
@@ -2128,8 +2121,8 @@ template <typename UA> __device__ __forceinline__ void upd_rowmap_one(const UA& 
 
 // ================================================================================================
 // Stacking decisions of remove_lost_features / prune_cam_state_buffer ON THE DEVICE (msckf.py:658-668, 759-763): which gated
-// blocks are stacked (in feature = map order, up to the `> 1500 rows` cut), which camera columns they touch, and how the
-// stacked rows are split into the sequential chunks of the batched back end.  One wavefront per stream.  The host only
+// blocks are stacked (in feature = map order, up to the `> 1500 rows` cut), which camera columns they touch, and whether the
+// stacked rows fit one pass of the batched back end or are compressed first.  One wavefront per stream.  The host only
 // knows upper bounds (it launches `rounds` rounds of back-end kernels; rounds a stream does not need see m = 0 and exit),
 // so the gate flags never travel to the host between the feature kernels and the update.
 // ================================================================================================
@@ -2143,8 +2136,7 @@ struct StackArgs {
     int* cols; int cols_stride;      // out: touched state columns of stream s at cols + s * cols_stride (ascending)
     const UpdArgs* base;             // [S] per-stream constants (pointers, n, ld, ...); base.mode = 1: information form allowed, 2: no update
     UpdArgs* out;                    // [rounds][S]
-    int S, rounds, cut1500, kch;
-    int compress;                    // 1: a stream with more than kch rows is QR-compressed (update_front_batch_kernel) and updated in ONE round
+    int S, rounds, cut1500, kch;     // kch: rows of one back-end pass; a stream with more is compressed to its nc columns' worth of rows and updated in ONE round
     int* stacked;                    // out [S]: rows stacked (0 = no update), -1 = more chunks than `rounds` (nothing is updated)
     // ---- device-resident filter (msckf_dev.inc); all NULL / 0 on the host-driven path ------------------------------------------
     const int* n_cand; int fs_stride;        // rbeg == NULL: the features of stream s are [s * fs_stride, s * fs_stride + n_cand[s])
@@ -2160,9 +2152,6 @@ struct StackArgs {
 __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
 {
     AV_FILTER_PRIO();
-    __shared__ int s_len[STACK_LDS_BLOCKS];
-    __shared__ int s_chunk[64];                          // first block of chunk c (c < rounds <= 63), then the end
-    __shared__ int s_nch;
     const int s = blockIdx.x, lane = threadIdx.x;
     const int i0 = a.rbeg ? a.rbeg[s] : s * a.fs_stride, i1 = a.rbeg ? a.rbeg[s + 1] : i0 + a.n_cand[s];
     const bool two_pass = a.over && a.over[s];
@@ -2203,7 +2192,7 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
         const unsigned long long mask = __ballot(take);
         const int pos = nb + __popcll(mask & ((1ull << lane) - 1ull));
         if (take) {
-            if (pos < STACK_LDS_BLOCKS) s_len[pos] = rows; else overflow = true;
+            if (pos >= STACK_LDS_BLOCKS) overflow = true;
             int ro = a.row_off[i];
             if (two_pass) {      // every passing feature up to the cut is stacked, so the rows stacked before this one are its compact offset
                 ro = before; a.row_off_w[i] = ro;
@@ -2229,31 +2218,14 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
     const int m = (overflow || dead) ? 0 : stacked;
     // (the information form holds for any m >= 1; a stream the host marked for it never needs a Cholesky round)
     const int mode = (m > 0 && b.mode == 1 && !a.no_info && nc <= INFO_NC && m <= INFO_MAXROWS) ? 1 : 0;
-    __syncthreads();
+    const int nch = (m > 0 && mode == 0) ? 1 : 0;       // one round: direct if m <= kch, else compressed to nc rows first
+    const bool too_many = nch > a.rounds;
     if (lane == 0) {
         int c = 0;
         for (int ci = 0; ci < 64; ++ci) if (used >> ci & 1ull) for (int e = 0; e < 6; ++e) a.cols[(size_t)s * a.cols_stride + c++] = IMU_DIM + 6 * ci + e;
-        int nch = 0;
-        if (m > 0 && mode == 0 && a.compress) nch = 1;   // one round: direct if m <= kch, else thin QR to nc rows first
-        else if (m > 0 && mode == 0) {                   // next-fit chunks of at most kch rows (a block is never split)
-            int acc = 0;
-            s_chunk[nch++] = 0;
-            for (int k = 0; k < nb; ++k) {
-                const int len = s_len[k];
-                if (acc + len > a.kch) { if (nch < 63) s_chunk[nch] = k; ++nch; acc = 0; }
-                acc += len;
-            }
-            if (nch <= 62) s_chunk[nch] = nb;
-        }
-        s_nch = nch;
-    }
-    __syncthreads();
-    const int nch = s_nch;
-    const bool too_many = nch > a.rounds || nch > 62;
-    if (lane == 0) {
         a.stacked[s] = overflow || too_many || dead ? -1 : m;
         const bool upd = m > 0 && !too_many;
-        if (upd && a.clist && mode == 0 && a.compress && m > a.kch) a.clist[atomicAdd(a.clist_count, 1)] = s;
+        if (upd && a.clist && mode == 0 && m > a.kch) a.clist[atomicAdd(a.clist_count, 1)] = s;
         if (upd && a.work) {     // per update of m stacked rows with k = min(m, n) rows kept, the reference's thin QR counted apart
             const double mm = m, n = (double)n_state, k = mm < n ? mm : n;
             a.work[8 * s + 1] += 2 * k * n * n + 2 * k * k * n + k * k * k / 3.0 + 2 * k * k * n + 4 * k * n * n;
@@ -2270,7 +2242,7 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
             const double c = (double)nc;
             if (mode == 1) a.work[8 * s + 7] += mm * c * c + 2 * mm * c + 4 * c * c * c + 2 * n * c * c + 2 * n * n * c;
             else {
-                const bool comp = a.compress && m > a.kch;
+                const bool comp = m > a.kch;
                 const int kki = comp ? nc : m;
                 auto t16 = [](int x) { return (double)((x + 15) / 16); };
                 auto q4 = [](int x) { return (double)((x + 3) / 4); };
@@ -2287,17 +2259,8 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
         UpdArgs u = b;
         u.mode = mode; u.round = r; u.kdir = 0; u.nc = nc; u.hld = a.hld; u.cols = a.cols + (size_t)s * a.cols_stride; u.status = a.stacked + s;
         u.blk_row = a.blk_row + i0; u.blk_len = a.blk_len + i0; u.n_blk = nb; u.m = (too_many || overflow) ? 0 : m;
-        if (u.m > 0 && mode == 0 && a.compress) {
-            if (r > 0) u.m = 0;
-            else u.kdir = m <= a.kch ? m : 0;            // 0: k = upd_k(m, nc) = nc rows after the QR (m > kch >= nc compresses)
-        } else if (u.m > 0 && mode == 0) {
-            if (r < nch) {
-                const int b0 = s_chunk[r], b1 = s_chunk[r + 1];
-                int rows = 0;
-                for (int k = b0; k < b1; ++k) rows += s_len[k];
-                u.blk_row += b0; u.blk_len += b0; u.n_blk = b1 - b0; u.m = rows; u.kdir = rows;
-            } else u.m = 0;
-        } else if (r > 0) u.m = 0;                       // information form: one launch, round 0 only
+        if (r > 0) u.m = 0;                              // one round (Cholesky back end) or one launch (information form): round 0 only
+        else if (u.m > 0 && mode == 0) u.kdir = m <= a.kch ? m : 0;      // 0: k = upd_k(m, nc) = nc rows after the compression (m > kch >= nc compresses)
         a.out[(size_t)r * a.S + s] = u;
     }
 }
@@ -2317,9 +2280,9 @@ static int msckf_lds_opt_in()
 {
     static const int rc = [] {
         const int lim = 160 * 1024;
-        const void* fns[6] = {reinterpret_cast<const void*>(feature_kernel8),
+        const void* fns[5] = {reinterpret_cast<const void*>(feature_kernel8),
                               reinterpret_cast<const void*>(feature_kernel<16>), reinterpret_cast<const void*>(feature_kernel<64>), reinterpret_cast<const void*>(feature_kernel<256>),
-                              reinterpret_cast<const void*>(update_front_kernel), reinterpret_cast<const void*>(update_front_batch_kernel)};
+                              reinterpret_cast<const void*>(update_front_kernel)};
         const void* fns2[3] = {reinterpret_cast<const void*>(update_back_kernel), reinterpret_cast<const void*>(update_back_batch_kernel),
                                reinterpret_cast<const void*>(upd_info_kernel)};
         for (const void* f : fns2) {
@@ -2558,16 +2521,16 @@ AV_EXPORT int av_msckf_update(av_msckf* c, const int32_t* blk_row_dev, const int
 
 // The back end of one round of batched updates: T^T, S, its factor, the substitution, the covariance update -- for all S streams of
 // `arr` (streams without an update of this kind exit on their first instruction).  kmax / nmax: the longest pass / largest state the
-// grids have to cover.  skipk: timing experiments of the host-store path (AV_MSCKF_SKIP).
-static inline void launch_upd_back(const UpdArgs* arr, int S, int kmax, int nmax, hipStream_t stm, int skipk = 0)
+// grids have to cover.
+static inline void launch_upd_back(const UpdArgs* arr, int S, int kmax, int nmax, hipStream_t stm)
 {
     const int bk = (kmax + MBW - 1) / MBW, bn = (nmax + MBW - 1) / MBW;
-    if (!(skipk & 8)) hipLaunchKernelGGL(upd_tt_mfma_kernel, dim3(mfma_grid(bn * bk, S)), dim3(64), 0, stm, arr, S, bn, bk);
-    if (!(skipk & 8)) hipLaunchKernelGGL(upd_s_mfma_kernel, dim3(mfma_grid(bk * (bk + 1) / 2, S)), dim3(64), 0, stm, arr, S, bk);
-    if (!(skipk & 16)) hipLaunchKernelGGL(upd_chol_mfma_kernel, dim3(mfma_grid(1, S)), dim3(64), 0, stm, arr, S);
+    hipLaunchKernelGGL(upd_tt_mfma_kernel, dim3(mfma_grid(bn * bk, S)), dim3(64), 0, stm, arr, S, bn, bk);
+    hipLaunchKernelGGL(upd_s_mfma_kernel, dim3(mfma_grid(bk * (bk + 1) / 2, S)), dim3(64), 0, stm, arr, S, bk);
+    hipLaunchKernelGGL(upd_chol_mfma_kernel, dim3(mfma_grid(1, S)), dim3(64), 0, stm, arr, S);
     const int parts = nmax / 16 + 1;
-    if (!(skipk & 32)) hipLaunchKernelGGL(upd_fsolve_mfma_kernel, dim3(mfma_grid(parts, S)), dim3(64), 0, stm, arr, S, parts);
-    if (!(skipk & 64)) hipLaunchKernelGGL(upd_p_mfma_kernel, dim3(mfma_grid(bn * (bn + 1) / 2, S)), dim3(64), 0, stm, arr, S, bn);
+    hipLaunchKernelGGL(upd_fsolve_mfma_kernel, dim3(mfma_grid(parts, S)), dim3(64), 0, stm, arr, S, parts);
+    hipLaunchKernelGGL(upd_p_mfma_kernel, dim3(mfma_grid(bn * (bn + 1) / 2, S)), dim3(64), 0, stm, arr, S, bn);
 }
 // Row compression of the streams on `list` (n_list_dev: device-written count, the tasks stride over the list; NULL: n_list entries):
 // Gram matrix of [Hc | r], then its bordered Cholesky factor -> the k = n_c rows [F | f] of W

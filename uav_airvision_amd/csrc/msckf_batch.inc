@@ -265,13 +265,6 @@ template <typename T>
 struct DevBuf {
     T* p = nullptr; size_t cap = 0;
     T* stage = nullptr; size_t stage_cap = 0;          // pinned staging: async H2D without a sync per upload
-    // zc ("zero copy"): an upload-only buffer whose kernels read the pinned staging memory directly over the host link -- `p`
-    // aliases `stage` and no copy is enqueued.  Every H2D copy of a few KB is a blit-kernel dispatch on the group's stream
-    // (rocprofv3: ~70 of them per group-step next to ~20 kernels), and a dependent dispatch is what the chain pays for when it
-    // shares the GPU with the front-end's kernels.  Only for arrays a kernel reads about once (per-feature CSR lists, argument
-    // records); arrays every feature re-reads (camera states) keep their device copy.  Same reuse rule as the staging buffers:
-    // the stream is synchronised between two fills of the same buffer.
-    bool zc = false;
     // Growth never frees inside a step: hipFree synchronises the whole device and queued copies / kernels of this or of
     // another stream group may still read the old allocation, so outgrown buffers are parked here until release().
     // sub_reserve() sizes every buffer for the worst case of a message capacity before the first step; `growths`
@@ -280,7 +273,6 @@ struct DevBuf {
     long long growths = 0;
     int ensure(size_t n)
     {
-        if (zc) return ensure_stage(n);
         if (n <= cap) return AV_OK;
         const size_t ncap = n + n / 2 + 64;
         T* q = nullptr;
@@ -297,11 +289,6 @@ struct DevBuf {
         AV_HIP(hipHostMalloc((void**)&q, ncap * sizeof(T), hipHostMallocMapped));
         if (stage) { old_host.push_back(stage); ++growths; }
         stage = q; stage_cap = ncap;
-        if (zc) {
-            void* dp = nullptr;
-            AV_HIP(hipHostGetDevicePointer(&dp, q, 0));
-            p = reinterpret_cast<T*>(dp); cap = ncap;
-        }
         return AV_OK;
     }
     int reserve(size_t n, bool with_stage) { int rc = ensure(n); if (!rc && with_stage) rc = ensure_stage(n); return rc; }
@@ -314,7 +301,7 @@ struct DevBuf {
         if (h.empty()) return AV_OK;
         if ((rc = ensure_stage(h.size()))) return rc;
         memcpy(stage, h.data(), h.size() * sizeof(T));
-        if (!zc) AV_HIP(hipMemcpyAsync(p, stage, h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+        AV_HIP(hipMemcpyAsync(p, stage, h.size() * sizeof(T), hipMemcpyHostToDevice, st));
         return AV_OK;
     }
     // Fill the pinned staging buffer in place (no intermediate std::vector), then commit(n) enqueues the copy.
@@ -329,13 +316,13 @@ struct DevBuf {
     }
     int commit(size_t n, hipStream_t st)
     {
-        if (n == 0 || zc) return AV_OK;
+        if (n == 0) return AV_OK;
         AV_HIP(hipMemcpyAsync(p, stage, n * sizeof(T), hipMemcpyHostToDevice, st));
         return AV_OK;
     }
     void release()
     {
-        if (p && !zc) (void)hipFree(p);
+        if (p) (void)hipFree(p);
         if (stage) (void)hipHostFree(stage);
         for (void* q : old_dev) (void)hipFree(q);
         for (void* q : old_host) (void)hipHostFree(q);
@@ -393,12 +380,10 @@ struct av_msckf_batch {
     std::thread worker; std::mutex wmu; std::condition_variable wcv;
     struct Job { std::function<int()> launch, finish; };
     std::deque<Job> jobs; long long n_submitted = 0, n_done = 0; bool quit = false; int job_rc = 0; char job_err[512] = "";
-    // diagnostic switches (INTEGRATION.md), read ONCE at create so that the chained path and its synchronous fallback always agree
     DevPath* dev = nullptr;                     // device-resident state + observation store (msckf_dev.inc); NULL: the host-bookkeeping path (AV_MSCKF_STORE=host)
     long long dev_seq = 0;                      // steps submitted (ring slot = dev_seq % DEV_RING)
     hipEvent_t ev_msg[4] = {nullptr, nullptr, nullptr, nullptr};      // submit_dev: the message copy of ring slot k has been enqueued
     std::deque<std::pair<int, double*>> direct_pending;      // one group, no worker: steps launched and not yet finished (slot, caller's out)
-    struct Env { bool heavy_qr = false, no_chain = false, no_info = false, multi_round = false, debug = false, front_qr = false, zero_copy = false; int skip = 0, timing = 0; } env;
     explicit av_msckf_batch(int n) : st(n) {}
 };
 
@@ -714,11 +699,6 @@ int b_launch_buckets(av_msckf_batch* b, FeatArgs a, const std::vector<FeatRef>& 
 // cut1500: apply the `> 1500 rows` break of remove_lost_features (msckf.py:667-668).
 int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool& pool, bool cut1500, hipStream_t stm)
 {
-    const bool dbg_t = b->env.timing != 0;
-    const bool dbg_sync = b->env.timing == 1;      // =2: host laps only, no extra synchronisation
-    auto tp = std::chrono::steady_clock::now();
-    double tb[6] = {0};
-    auto lapb = [&](int i) { if (!dbg_t) return; if (dbg_sync) (void)hipStreamSynchronize(stm); auto n = std::chrono::steady_clock::now(); tb[i] += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; };
     const int S = b->S;
     if (refs.empty()) return AV_OK;
     const int nf = (int)refs.size();
@@ -756,7 +736,6 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
         }
         for (int e = 0; e < 3; ++e) pos[(size_t)i * 3 + e] = r.f->pos[e];
     }
-    lapb(0);
     if ((rc = b->d_obs_off.upload(off, stm)) || (rc = b->d_obs_cam.commit((size_t)off[nf], stm)) || (rc = b->d_obs_z.commit((size_t)off[nf] * 4, stm)) ||
         (rc = b->d_fstream.upload(fs, stm)) || (rc = b->d_dof.upload(dof, stm)) || (rc = b->d_rowoff.upload(rowoff, stm)) ||
         (rc = b->d_pos.commit((size_t)nf * 3, stm)) || (rc = b->d_gamma.ensure(nf)) || (rc = b->d_pass.ensure(nf))) return rc;
@@ -770,24 +749,15 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
     a.feat_stream = b->d_fstream.p; a.stream_ncam = b->d_ncam.p; a.stream_gravity = b->d_grav.p; a.cam_stride = b->cam_slots;
     a.p_stride = b->pstride; a.h_stride = b->hstride; a.r_stride = b->rstride; a.feat_list = nullptr;
     a.tri_idx = nullptr; a.tri_pos = nullptr; a.tri_valid = nullptr;
-    static unsigned long long* fprof_dev = nullptr;
-    if (dbg_t && !fprof_dev) (void)hipMalloc((void**)&fprof_dev, 64);
-    a.prof = dbg_sync ? fprof_dev : nullptr;
+    a.prof = nullptr;
     // camera pruning stacks only features seen from BOTH removed cameras and factorises exactly those 12 columns, so every
     // column the update gathers is written by the feature itself: no need to clear 141-wide rows (5.6 KB per feature)
     a.zero_fill = cut1500 ? 1 : 0;
-    lapb(1);
     auto launch_buckets = [&](const std::vector<int>& sel) -> int { return b_launch_buckets(b, a, refs, sel, maxobs, stm); };
     {
         std::vector<int> all(nf);
         for (int i = 0; i < nf; ++i) all[i] = i;
         if ((rc = launch_buckets(all))) return rc;
-    }
-    lapb(2);
-    if (dbg_sync) {
-        unsigned long long t[8];
-        (void)hipMemcpy(t, fprof_dev, 64, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[feature kernel team0 us] n=%d setup->jac %.1f G %.1f reflect %.1f write %.1f gate %.1f\n", refs[0].n, (t[1]-t[0])/100.0, (t[2]-t[1])/100.0, (t[3]-t[2])/100.0, (t[4]-t[3])/100.0, (t[5]-t[4])/100.0);
     }
     std::vector<int> pass(nf);
     AV_HIP(hipMemcpyAsync(pass.data(), b->d_pass.p, sizeof(int) * nf, hipMemcpyDeviceToHost, stm));
@@ -826,7 +796,7 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
     std::vector<int> all_r, all_l, all_cols;
     std::vector<size_t> col_off(S, 0);
     std::vector<UpdArgs> ua(S);
-    int kmax = 0, nmax = 0, ncinfo = 0, ninfo = 0, minfo = 0; bool any = false, any_info = false, any_qr = false;
+    int nmax = 0, ncinfo = 0, ninfo = 0, minfo = 0; bool any = false, any_info = false, any_qr = false;
     for (int s = 0; s < S; ++s) {
         UpdArgs& u = ua[s];
         memset(&u, 0, sizeof(u));
@@ -846,54 +816,37 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
         u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
         u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
         u.Sbuf = b->scratch + (size_t)s * b->pstride;          // free between the camera removals that use it
-        u.mode = (upd_info_form(u.m, u.nc) && !b->env.no_info) ? 1 : 0;
+        u.mode = upd_info_form(u.m, u.nc) ? 1 : 0;
         if (u.mode) { any_info = true; if (u.nc > ncinfo) ncinfo = u.nc; if (T.n > ninfo) ninfo = T.n; if (u.m > minfo) minfo = u.m; continue; }
         any_qr = true;
-        const int k = upd_k(u.m, u.nc);                        // (single-round path only, AV_MSCKF_QR=heavy)
-        if (k > kmax) kmax = k;
         if (T.n > nmax) nmax = T.n;
     }
     if (!any) return AV_OK;
-    {   // timing experiments only (results are then wrong): AV_MSCKF_SKIP bit 0 / 1 = no update for the lost-feature / pruning path
-        const int skip = b->env.skip;
-        if ((skip & 1) && cut1500) return AV_OK;
-        if ((skip & 2) && !cut1500) return AV_OK;
-    }
-    lapb(3);
     if ((rc = b->d_blk_row.upload(all_r, stm)) || (rc = b->d_blk_len.upload(all_l, stm)) || (rc = b->d_cols.upload(all_cols, stm))) return rc;
     for (int s = 0; s < S; ++s) if (ua[s].m > 0) {
         size_t o = reinterpret_cast<size_t>(ua[s].blk_row);
         ua[s].blk_row = b->d_blk_row.p + o; ua[s].blk_len = b->d_blk_len.p + o;
         ua[s].cols = b->d_cols.p + col_off[s];
     }
-    static unsigned long long* prof_dev = nullptr;
-    const bool prof_on = dbg_sync;
-    if (prof_on && !prof_dev) (void)hipMalloc((void**)&prof_dev, 128);
-    for (int s = 0; s < S; ++s) ua[s].prof = (prof_on && s == 0) ? prof_dev : nullptr;
     if ((rc = msckf_lds_opt_in())) return rc;
-    const int skipk = b->env.skip;      // timing experiments only
-    const bool heavy_qr = b->env.heavy_qr;
     // ---- sequential chunks instead of a QR.  A stream that stacks more rows than the back end keeps (KCH) is updated in
     //      several rounds of at most KCH rows each: the EKF update with [H0; H1] equals the update with H0 followed by the
     //      update with H1 on the updated covariance and the residual r1 - H1 dx (independent noise), so no stream needs the
     //      1024-thread QR workgroup any more -- it waited ~1 ms per launch for a whole CU to drain and was the largest item of
     //      the step's chain.  Round r of all streams runs as one set of launches; most streams have one round.
-    //      (AV_MSCKF_QR=heavy restores the single-round path with QR compression for A/B runs.)
     constexpr int KCH = 144;
     std::vector<std::vector<int>> cstart(S);                 // first block of every chunk of stream s (+ end)
     int R = 1;
-    if (!heavy_qr) {
-        for (int s = 0; s < S; ++s) {
-            if (ua[s].m <= 0 || ua[s].mode != 0) continue;
-            int acc = 0;
-            cstart[s].push_back(0);
-            for (int k = 0; k < (int)bl[s].size(); ++k) {
-                if (acc + bl[s][k] > KCH) { cstart[s].push_back(k); acc = 0; }
-                acc += bl[s][k];
-            }
-            cstart[s].push_back((int)bl[s].size());
-            if ((int)cstart[s].size() - 1 > R) R = (int)cstart[s].size() - 1;
+    for (int s = 0; s < S; ++s) {
+        if (ua[s].m <= 0 || ua[s].mode != 0) continue;
+        int acc = 0;
+        cstart[s].push_back(0);
+        for (int k = 0; k < (int)bl[s].size(); ++k) {
+            if (acc + bl[s][k] > KCH) { cstart[s].push_back(k); acc = 0; }
+            acc += bl[s][k];
         }
+        cstart[s].push_back((int)bl[s].size());
+        if ((int)cstart[s].size() - 1 > R) R = (int)cstart[s].size() - 1;
     }
     std::vector<UpdArgs> uar((size_t)R * S);
     std::vector<int> kmax_r(R, 0);
@@ -903,7 +856,7 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
             u = ua[s];
             u.round = r; u.kdir = 0;
             if (ua[s].m <= 0) continue;
-            if (ua[s].mode != 0 || heavy_qr) { if (r > 0) u.m = 0; continue; }
+            if (ua[s].mode != 0) { if (r > 0) u.m = 0; continue; }
             const int nch = (int)cstart[s].size() - 1;
             if (r >= nch) { u.m = 0; continue; }
             const int b0 = cstart[s][r], b1 = cstart[s][r + 1];
@@ -913,17 +866,7 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
             u.m = rows_; u.kdir = rows_;
             if (rows_ > kmax_r[r]) kmax_r[r] = rows_;
         }
-    if (heavy_qr) kmax_r[0] = kmax;
     if ((rc = b->d_upd.upload(uar, stm))) return rc;
-    size_t lds_f = 0;
-    std::vector<int> clist;                                  // AV_MSCKF_QR=heavy only: streams whose stacked Jacobian is QR-compressed
-    if (heavy_qr) for (int s = 0; s < S; ++s) if (ua[s].m > 0 && ua[s].mode == 0 && upd_compress(ua[s].m, ua[s].nc)) {
-        const size_t f = update_front_lds(ua[s].m);
-        if (f > lds_f) lds_f = f;
-        clist.push_back(s);
-    }
-    if ((rc = b->d_clist.upload(clist, stm))) return rc;
-    if (lds_f > 160 * 1024) { av_set_error("batched MSCKF: update needs %zu B of LDS", lds_f); return AV_E_CAPACITY; }
     if (any_info) {                                          // few-column streams (camera pruning): information form, one light kernel
         const size_t lds_i = upd_info_lds(ncinfo, ninfo, minfo);
         if (lds_i > 160 * 1024) { av_set_error("batched MSCKF: information-form update needs %zu B of LDS", lds_i); return AV_E_CAPACITY; }
@@ -933,9 +876,8 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
         const UpdArgs* arr = b->d_upd.p + (size_t)r * S;
         if (kmax_r[r] <= 0) continue;
         hipLaunchKernelGGL(upd_gather_kernel, dim3(S), dim3(256), 0, stm, arr);
-        if (heavy_qr && !clist.empty() && !(skipk & 4)) hipLaunchKernelGGL(update_front_batch_kernel, dim3((unsigned)clist.size()), dim3(UT), lds_f, stm, arr, b->d_clist.p);
         // back end: the products around the per-stream factor kernel (msckf.hip: launch_upd_back)
-        launch_upd_back(arr, S, kmax_r[r], nmax, stm, skipk);
+        launch_upd_back(arr, S, kmax_r[r], nmax, stm);
     }
     AV_LAUNCH_CHECK();
     std::vector<double> dx((size_t)S * b->ld);
@@ -961,21 +903,7 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
             (void)hipMemcpy2D(T.dbg_P[ph].data(), sizeof(double) * T.n, b->P + (size_t)s * b->pstride, sizeof(double) * b->ld, sizeof(double) * T.n, T.n, hipMemcpyDeviceToHost);
         }
     }
-    lapb(4);
     for (int s = 0; s < S; ++s) if (ua[s].m > 0) b_inject(b->st[s], dx.data() + (size_t)s * b->ld);
-    lapb(5);
-    if (dbg_t) fprintf(stderr, "[blocks+update ms] nf=%d csr %.3f upload %.3f feature-kernels %.3f stacking %.3f update-kernel %.3f inject %.3f\n", nf, tb[0], tb[1], tb[2], tb[3], tb[4], tb[5]);
-    if (prof_on && ua[0].m > 0) {
-        unsigned long long t[16];
-        (void)hipMemcpy(t, prof_dev, 128, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[update kernel stream0 us] m=%d nc=%d gather %.0f front %.0f T %.0f S %.0f chol %.0f solve %.0f dx %.0f P-YtY %.0f sym %.0f\n", ua[0].m, ua[0].nc,
-                (t[1]-t[0])/100.0, (t[2]-t[1])/100.0, (t[8]-t[7])/100.0, (t[3]-t[8])/100.0, (t[4]-t[3])/100.0, (t[5]-t[4])/100.0, (t[9]-t[5])/100.0, (t[10]-t[9])/100.0, (t[6]-t[10])/100.0);
-    }
-    if (b->env.debug) {
-        int np_ = 0; for (int i = 0; i < nf; ++i) np_ += pass[i];
-        double nrm = 0; for (int i = 0; i < b->st[0].n; ++i) nrm += dx[i] * dx[i];
-        fprintf(stderr, "[msckf-batch] cut=%d nfeat=%d pass=%d stacked0=%d n0=%d |dx0|=%.12e\n", (int)cut1500, nf, np_, stacked[0], b->st[0].n, sqrt(nrm));
-    }
     return AV_OK;
 }
 
@@ -990,7 +918,7 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
 // everything including the read-backs; the caller may queue more work on the stream (camera removal, position
 // variances), waits, and calls b_chain_finish, which applies the results to the host-side bookkeeping.  ok[i] = 0 marks a
 // feature whose triangulation failed.  Cases the chain does not cover run the synchronous path inside b_chain_launch
-// (ctx.done): a stream whose candidates exceed rows_cap (two-pass gating), AV_MSCKF_QR=heavy, AV_MSCKF_CHAIN=0.
+// (ctx.done): a stream whose candidates exceed rows_cap (two-pass gating), more than 60 rounds.
 // ------------------------------------------------------------------------------------------------
 struct ChainCtx {
     std::vector<int> todo;          // refs triangulated by this phase
@@ -1010,13 +938,10 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
     ctx.nf = nf; ctx.cut1500 = cut1500;
     if (b->debug_capture) { ctx.n_at_launch.resize(S); for (int s = 0; s < S; ++s) ctx.n_at_launch[s] = b->st[s].n; }
     if (nf == 0) { ctx.done = true; return AV_OK; }
-    const bool heavy_qr = b->env.heavy_qr, no_chain = b->env.no_chain, no_info = b->env.no_info;
     // One round for every stream: a stream that stacks more rows than one back-end pass holds is first compressed to its n_c
-    // non-zero columns' worth of rows by the register-resident Householder QR (update_front_batch_kernel, one 1024-thread
-    // workgroup per such stream -- a few per cent of the streams of a frame).  Sequential chunk rounds (AV_MSCKF_ROUNDS=multi) cost
-    // every stream of the group the latency of the LONGEST stream's rounds: at 512 streams per group the longest stacks 300-500
-    // rows when the mean stacks 130, i.e. 3-5 rounds of six launches where one would do.
-    const bool multi_round = b->env.multi_round;
+    // non-zero columns' worth of rows (the Gram compression below -- a few per cent of the streams of a frame).  Sequential chunk
+    // rounds cost every stream of the group the latency of the LONGEST stream's rounds: at 512 streams per group the longest
+    // stacks 300-500 rows when the mean stacks 130, i.e. 3-5 rounds of six launches where one would do.
     int rc;
     // per-feature offsets, per-stream row reservations, cameras touched, all-pass chunk count (upper bound of the rounds)
     std::vector<int> off(nf + 1, 0), fs(nf), dof(nf), rowoff(nf), rbeg(S + 1, 0);
@@ -1047,12 +972,12 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
     }
     for (int s = 0; s < S; ++s) { if (rbeg[s + 1] < rbeg[s]) rbeg[s + 1] = rbeg[s]; if (stream_rows[s] > b->rows_cap) any_over = true; }
     int R = 0, nmax = 0; bool any_info = false; int ncinfo = 0, ninfo = 0, minfo = 0;
-    std::vector<int> clist; int front_rows = 0;          // streams that may need the QR compression, the most rows among them
+    std::vector<int> clist;                              // streams that may need the compression
     std::vector<char> info_ok(S, 0), dead(S, 0);
     for (int s = 0; s < S; ++s) {
         if (stream_rows[s] == 0) continue;
         const int nct = 6 * __builtin_popcountll(touched[s]);
-        if (!no_info && nct <= INFO_NC) {                    // the stacked Jacobian cannot touch more than INFO_NC columns: information form
+        if (nct <= INFO_NC) {                    // the stacked Jacobian cannot touch more than INFO_NC columns: information form
             info_ok[s] = 1; any_info = true;                 // (or, with m <= nc rows, one ordinary round)
             if (nct > ncinfo) ncinfo = nct;
             if (b->st[s].n > ninfo) ninfo = b->st[s].n;
@@ -1060,18 +985,18 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
             if (mm > minfo) minfo = mm;
             rounds_s[s] = stream_rows[s] > INFO_MAXROWS ? rounds_s[s] : 0;      // information form whatever the gate leaves: no round
         }
-        if (!multi_round && rounds_s[s] > 1) {
-            // rows the QR may be handed: behind the `> 1500 rows` cut at most 1500 + one block; its two row maps must fit the LDS
+        if (rounds_s[s] > 1) {
+            // rows the compression may be handed: behind the `> 1500 rows` cut at most 1500 + one block; its row map must fit the stream's Kt buffer
             const int fr = cut1500 && stream_rows[s] > 1500 + 81 ? 1500 + 81 : stream_rows[s];
             rounds_s[s] = 1;
-            const bool fits = b->env.front_qr ? update_front_lds(fr) <= 160 * 1024 : (size_t)fr <= 2 * b->pstride;      // QR: two row maps in LDS; Gram: the row map in the stream's Kt buffer
+            const bool fits = (size_t)fr <= 2 * b->pstride;
             if (!fits) { dead[s] = 1; b_fail_stream(b, s, AV_E_CAPACITY, "a %d-row update over more than %d columns exceeds the compression stage", fr, INFO_NC); }
-            else { clist.push_back(s); if (fr > front_rows) front_rows = fr; }
+            else clist.push_back(s);
         }
         if (rounds_s[s] > R) R = rounds_s[s];
         if (b->st[s].n > nmax) nmax = b->st[s].n;
     }
-    if (any_over || heavy_qr || no_chain || R > 60) {
+    if (any_over || R > 60) {
         // synchronous path: positions first, then the features that have one
         ctx.done = true;
         std::vector<char> ok;
@@ -1141,7 +1066,7 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
     StackArgs sa; memset(&sa, 0, sizeof(sa));
     sa.rbeg = b->d_rbeg.p; sa.pass = b->d_pass.p; sa.obs_off = b->d_obs_off.p; sa.obs_cam = b->d_obs_cam.p; sa.row_off = b->d_rowoff.p;
     sa.blk_row = b->d_blk_row.p; sa.blk_len = b->d_blk_len.p; sa.cols = b->d_cols.p; sa.cols_stride = 6 * b->cam_slots;
-    sa.base = b->d_updbase.p; sa.out = b->d_upd.p; sa.S = S; sa.rounds = R > 0 ? R : 1; sa.cut1500 = cut1500 ? 1 : 0; sa.kch = CHAIN_KCH; sa.stacked = b->d_stacked.p; sa.compress = multi_round ? 0 : 1;
+    sa.base = b->d_updbase.p; sa.out = b->d_upd.p; sa.S = S; sa.rounds = R > 0 ? R : 1; sa.cut1500 = cut1500 ? 1 : 0; sa.kch = CHAIN_KCH; sa.stacked = b->d_stacked.p;
     hipLaunchKernelGGL(upd_stack_kernel, dim3(S), dim3(64), 0, stm, sa);
     if ((rc = msckf_lds_opt_in())) return rc;
     if (any_info) {
@@ -1154,11 +1079,7 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
     if (R > 0) {
         for (int r = 0; r < R; ++r) {
             const UpdArgs* arr = b->d_upd.p + (size_t)r * S;
-            if (r == 0 && !clist.empty() && b->env.front_qr) {
-                const size_t lds_f = update_front_lds(front_rows);
-                if (lds_f > 160 * 1024) { av_set_error("batched MSCKF: update needs %zu B of LDS", lds_f); return AV_E_CAPACITY; }
-                hipLaunchKernelGGL(update_front_batch_kernel, dim3((unsigned)clist.size()), dim3(UT), lds_f, stm, arr, b->d_clist.p);
-            } else if (r == 0 && !clist.empty()) {
+            if (r == 0 && !clist.empty()) {
                 // streams that exceed a pass: Gram compression (msckf.hip "Row compression WITHOUT a QR"): row map, partial Gram slabs
                 // per 256-row chunk and lower tile, bordered Cholesky -> the k = n_c rows [F | f] of W
                 const unsigned nl = (unsigned)clist.size();
@@ -1247,10 +1168,6 @@ int b_chain_finish(av_msckf_batch* b, std::vector<FeatRef>& refs, ChainCtx& ctx)
             }
         }
     }
-    if (b->env.debug) {
-        double nrm = 0; for (int i = 0; i < b->st[0].n; ++i) nrm += b->h_dx[i] * b->h_dx[i];
-        fprintf(stderr, "[msckf-batch chain] nfeat=%d stacked0=%d n0=%d |dx0|=%.12e\n", ctx.nf, stacked[0], b->st[0].n, sqrt(nrm));
-    }
     return AV_OK;
 }
 
@@ -1262,8 +1179,8 @@ namespace { void dev_release(DevPath* d); int dev_launch(av_msckf_batch* b, int 
 // Stream for the filter's kernels.  AV_MSCKF_CUS="first:count" confines them to `count` compute units starting at CU `first`
 // (hipExtStreamCreateWithCUMask) -- together with a complementary mask on the caller's front-end stream this partitions the
 // chip, so that the filter's latency-bound kernels never queue behind the front-end's resident workgroups.  Without the
-// variable: an ordinary stream at the highest priority.
-static hipError_t make_filter_stream(hipStream_t* out, bool aux = false)
+// variable: an ordinary stream, at the highest priority for the host-bookkeeping path, at the default priority otherwise.
+static hipError_t make_filter_stream(hipStream_t* out, bool host_store)
 {
     const char* e = getenv("AV_MSCKF_CUS");
     int first = 0, count = 0;
@@ -1278,18 +1195,7 @@ static hipError_t make_filter_stream(hipStream_t* out, bool aux = false)
     // front-end's kernels keep their speed (11.5 instead of 16 ms of spans per 2,048-stream step) and the complete path gains
     // (DESIGN.md section 7: 131 k vs 114 k frames/s).  The host-bookkeeping path (AV_MSCKF_STORE=host) keeps the highest priority:
     // its launches are interleaved with host phases and must be scheduled at once.
-    {
-        const char* st = getenv("AV_MSCKF_STORE");
-        if (!(st && !strcmp(st, "host")) && !getenv("AV_MSCKF_PRIO")) hi = (lo + hi) / 2;
-        // A/B: the auxiliary streams (the long-track buckets of feature_kernel: 43-69 KB of LDS per workgroup, which starve behind
-        // the front-end's small workgroups at equal priority) at the highest priority
-        if (aux && getenv("AV_MSCKF_AUX_PRIO") && atoi(getenv("AV_MSCKF_AUX_PRIO")) == 2) { int l2 = 0, h2 = 0; (void)hipDeviceGetStreamPriorityRange(&l2, &h2); hi = h2; }
-    }
-    // A/B knobs (DESIGN.md section 7): AV_MSCKF_PRIO=0 lowest, =1 default stream priority.  At the default priority the
-    // front-end keeps its speed (11.3 instead of 14.3 ms per step) but the filter's chain doubles behind the front-end's launches.
-    if (getenv("AV_MSCKF_PRIO") && atoi(getenv("AV_MSCKF_PRIO")) == 0) hi = lo;
-    if (getenv("AV_MSCKF_PRIO") && atoi(getenv("AV_MSCKF_PRIO")) == 1) hi = (lo + hi) / 2;
-    return hipStreamCreateWithPriority(out, hipStreamNonBlocking, hi);
+    return hipStreamCreateWithPriority(out, hipStreamNonBlocking, host_store ? hi : (lo + hi) / 2);
 }
 
 // Rows of the overflow pool behind the last stream's block-buffer region (device-resident path).  A stream whose lost-feature
@@ -1313,7 +1219,7 @@ static size_t b_pool_rows(const av_msckf_batch* b, int rows_cap)
 static int sub_create(int n_streams, int max_cam_states, int rows_cap, const double* chi2_table_100, const double gravity[3],
                                     const double* T_cam0_cam1_rowmajor44, const double* R_imu_cam0_t_cam0_imu12, const double cov_init5[5],
                                     const double noise4[4], double obs_noise, double position_std_threshold, const double velocity0[3],
-                                    const double* opt6, int device, av_msckf_batch** out)
+                                    const double* opt6, int device, bool host_store, av_msckf_batch** out)
 {
     if (!out || n_streams <= 0 || max_cam_states < 4 || max_cam_states > 30 || (rows_cap != 0 && rows_cap < 1664) || !chi2_table_100 || !gravity || !T_cam0_cam1_rowmajor44 ||
         !R_imu_cam0_t_cam0_imu12 || !cov_init5 || !noise4 || !velocity0 || !opt6) { av_set_error("av_msckf_batch_create: bad arguments"); return AV_E_INVALID; }
@@ -1341,16 +1247,6 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
     av_msckf_batch* b = new (std::nothrow) av_msckf_batch(n_streams);
     if (!b) { av_set_error("out of host memory"); return AV_E_INVALID; }
     b->device = device; b->S = n_streams; b->max_cam = max_cam_states; b->cam_slots = max_cam_states + 1; b->rows_cap = rows_cap;
-    {
-        auto is = [](const char* name, const char* val) { const char* e = getenv(name); return e && !strcmp(e, val); };
-        auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
-        b->env.heavy_qr = is("AV_MSCKF_QR", "heavy"); b->env.no_chain = getenv("AV_MSCKF_CHAIN") && num("AV_MSCKF_CHAIN") == 0;
-        b->env.no_info = getenv("AV_MSCKF_NO_INFO") != nullptr; b->env.multi_round = is("AV_MSCKF_ROUNDS", "multi");
-        b->env.zero_copy = is("AV_MSCKF_ZC", "1");               // A/B: upload-only arrays read in place from pinned host memory
-        b->env.front_qr = is("AV_MSCKF_FRONT", "qr");          // A/B: the round-2 Householder workgroup instead of the Gram compression
-        b->env.debug = getenv("AV_MSCKF_DEBUG") != nullptr; b->env.skip = num("AV_MSCKF_SKIP");
-        b->env.timing = getenv("AV_MSCKF_TIMING") ? (num("AV_MSCKF_TIMING") >= 2 ? 2 : 1) : 0;
-    }
     b->ld = ((IMU_DIM + 6 * b->cam_slots) + 7) & ~7;
     for (int i = 0; i < 3; ++i) { b->gravity0[i] = gravity[i]; b->vel0[i] = velocity0[i]; }
     for (int i = 0; i < 16; ++i) b->T01[i] = T_cam0_cam1_rowmajor44[i];
@@ -1361,18 +1257,9 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
     for (int i = 0; i < 4; ++i) b->noise[i] = noise4[i];
     for (int i = 0; i < 100; ++i) b->chi2[i] = chi2_table_100[i];
     b->obs_noise = obs_noise; b->pos_std_thr = position_std_threshold;
-    if (b->env.zero_copy) {
-        b->d_prop.zc = b->d_first.zc = b->d_aug.zc = b->d_rem.zc = b->d_clist.zc = b->d_flist.zc = true;
-        b->d_obs_off.zc = b->d_obs_cam.zc = b->d_obs_z.zc = b->d_fstream.zc = b->d_dof.zc = b->d_rowoff.zc = b->d_pos.zc = true;
-        b->d_tri_idx.zc = b->d_rbeg.zc = b->d_updbase.zc = b->d_tobs_off.zc = b->d_tobs_cam.zc = b->d_tobs_z.zc = b->d_tfs.zc = true;
-    }
     // The filter's state and observation map live on the device (msckf_dev.inc) unless AV_MSCKF_STORE=host asks for the
-    // host-bookkeeping path (A/B runs; also taken by the diagnostic switches that only that path implements).
-    {
-        const char* e = getenv("AV_MSCKF_STORE");
-        const bool host_store = (e && !strcmp(e, "host")) || b->env.heavy_qr || b->env.no_chain || b->env.multi_round || b->env.front_qr || b->env.zero_copy || b->env.skip || b->env.timing;
-        b->pool_on = !host_store;
-    }
+    // host-bookkeeping path (A/B runs).
+    b->pool_on = !host_store;
     const size_t S = n_streams;
     b->pstride = (size_t)b->ld * b->ld; b->hstride = (size_t)rows_cap * b->ld; b->rstride = rows_cap; b->wstride = (size_t)rows_cap * (b->ld + 1);
     int rc;
@@ -1384,7 +1271,7 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
     AV_HIP(hipMemcpy(b->chi2_dev, chi2_table_100, sizeof(double) * 100, hipMemcpyHostToDevice));
     AV_HIP(hipHostMalloc((void**)&b->h_dx, sizeof(double) * S * b->ld + 64, hipHostMallocDefault));
     AV_HIP(hipHostMalloc((void**)&b->h_pv, sizeof(double) * 3 * S + 64, hipHostMallocDefault));
-    for (int i = 0; i < 4; ++i) { AV_HIP(make_filter_stream(&b->aux[i], true)); AV_HIP(hipEventCreateWithFlags(&b->ev_join[i], hipEventDisableTiming)); }
+    for (int i = 0; i < 4; ++i) { AV_HIP(make_filter_stream(&b->aux[i], host_store)); AV_HIP(hipEventCreateWithFlags(&b->ev_join[i], hipEventDisableTiming)); }
     AV_HIP(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
     AV_HIP(hipEventCreateWithFlags(&b->ev_wait, hipEventDisableTiming | hipEventBlockingSync));
     for (int i = 0; i < 2; ++i) { AV_HIP(hipEventCreate(&b->ev_t0[i])); AV_HIP(hipEventCreate(&b->ev_t1[i])); }
@@ -1527,11 +1414,6 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
     if ((rc = sub_reserve(b, cap))) return rc;
     ++b->n_steps;
     if (b->debug_capture) for (BStream& T : b->st) for (int ph = 0; ph < 2; ++ph) { T.dbg_gamma[ph].clear(); T.dbg_dx[ph].clear(); T.dbg_P[ph].clear(); T.dbg_rows[ph] = 0; T.dbg_n[ph] = 0; }
-    const bool dbg_t = b->env.timing != 0;
-    const bool dbg_sync = b->env.timing == 1;
-    auto t_prev = std::chrono::steady_clock::now();
-    double t_ph[16] = {0};
-    auto lap = [&](int i) { if (!dbg_t) return; if (dbg_sync) (void)hipStreamSynchronize(stm); auto n = std::chrono::steady_clock::now(); t_ph[i] += std::chrono::duration<double, std::milli>(n - t_prev).count(); t_prev = n; };
     // ---- batch_imu_processing + process_model (msckf.py:251-339) ---------------------------------
     // two passes: count the IMU samples of this frame per stream, then every stream writes its PropArgs at its offset of
     // the pinned staging buffer (no per-stream vectors, no serial concatenation)
@@ -1656,9 +1538,7 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
             AV_LAUNCH_CHECK();
         }
     }
-    lap(0);
     par_streams(S, [&](int s) { ph_addobs(s); ph_lost_select(s); });      // overlaps the two kernels above
-    lap(2);
     if ((rc = b_upload_cams(b, stm))) return rc;
     // concatenation of per-stream FeatRef lists + observation pools, in stream order
     auto concat = [&](std::vector<std::vector<FeatRef>>& rs, std::vector<ObsPool>& ps, std::vector<FeatRef>& out, ObsPool& pool) {
@@ -1682,8 +1562,6 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
         std::vector<FeatRef> cand;
         std::vector<size_t> cbeg;
         concat_refs(cand_s, cand, cbeg);
-        lap(6);
-        lap(7);
         // every candidate goes down the chain (triangulation results are consumed on the device; a feature that fails it is
         // not evaluated), and every candidate is deleted afterwards: processed or invalid (msckf.py:646-656, 675-676)
         std::vector<std::vector<FeatRef>> proc_s(S); std::vector<ObsPool> pool_s(S);
@@ -1700,20 +1578,16 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
         });
         std::vector<FeatRef> proc; ObsPool pool;
         concat(proc_s, pool_s, proc, pool);
-        lap(8);
         ChainCtx cx;
         if ((rc = b_chain_launch(b, proc, pool, true, stm, cx))) return rc;
-        lap(14);
         if (cx.launched) { if ((rc = b_wait(b, stm)) || (rc = b_chain_finish(b, proc, cx))) return rc; }
         if (!proc.empty()) synced = true;
-        lap(9);
         par_streams(S, [&](int s) {
             BStream& T = b->st[s];
             for (const FeatRef& r : proc_s[s]) invalid[s].push_back(r.fs);
             for (int fs : invalid[s]) T.map.erase(fs);
         });
     }
-    lap(3);
     // ---- prune_cam_state_buffer (msckf.py:678-786) ----------------------------------------------------
     bool have_pv = false;         // position variances already read back (with the pruning phase's results)
     {
@@ -1741,7 +1615,6 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
             }
             if (sel[0] > sel[1]) std::swap(sel[0], sel[1]);
             rm[s] = {sel[0], sel[1]};
-            if (b->env.debug && s == 0) fprintf(stderr, "[msckf-batch] prune rm = %lld %lld (tracking_rate %.6f)\n", sel[0], sel[1], T.tracking_rate);
         });
         bool any = false;
         for (int s = 0; s < S; ++s) if (prune[s]) { any = true; ++b->n_prune_stream_steps; }
@@ -1774,13 +1647,10 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
                 // dict order (a reference keeps its own pool slice, so sorting the references is enough)
                 std::sort(proc_s[s].begin(), proc_s[s].end(), [](const FeatRef& x, const FeatRef& y) { return x.f->birth < y.f->birth; });
             });
-            lap(10);
             std::vector<FeatRef> proc; ObsPool pool;
             concat(proc_s, pool_s, proc, pool);
-            lap(12);
             ChainCtx cx;
             if ((rc = b_chain_launch(b, proc, pool, false, stm, cx))) return rc;
-            lap(15);
             // the two camera states leave the covariance right behind the update (nothing here depends on the host's copy of the
             // state); the position variances of `publish` ride on the same wait
             std::vector<RemArgs> ra(S);
@@ -1801,7 +1671,6 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
             AV_HIP(hipMemcpyAsync(b->h_pv, b->pvar, sizeof(double) * 3 * S, hipMemcpyDeviceToHost, stm));
             if ((rc = b_wait(b, stm)) || (rc = b_chain_finish(b, proc, cx))) return rc;
             have_pv = true;
-            lap(13);
             // the two frames go (with them both observations of every candidate and the single ones of the other features), then the cameras
             par_streams(S, [&](int s) {
                 if (!prune[s]) return;
@@ -1813,7 +1682,6 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
             });
         }
     }
-    lap(4);
     // ---- publish + online_reset (msckf.py:821-867) -----------------------------------------------------
     if (!have_pv) {
         hipLaunchKernelGGL(pos_var_kernel, dim3((3 * S + 255) / 256), dim3(256), 0, stm, b->P, b->pstride, b->ld, S, b->pvar);
@@ -1834,9 +1702,6 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
         T.cams.clear(); T.map.clear();
         if ((rc = b_reset_cov(b, s, stm))) return rc;
     }
-    lap(5);
-    if (dbg_t) fprintf(stderr, "[msckf-batch timing ms] propagate %.3f augment %.3f addobs %.3f | lost: select %.3f init %.3f build %.3f blocks+update %.3f erase %.3f | prune: select %.3f init %.3f build %.3f blocks+update %.3f remove %.3f | publish %.3f | chain: lost-launch %.3f prune-launch %.3f\n",
-                       t_ph[0], t_ph[1], t_ph[2], t_ph[6], t_ph[7], t_ph[8], t_ph[9], t_ph[3], t_ph[10], t_ph[11], t_ph[12], t_ph[13], t_ph[4], t_ph[5], t_ph[14], t_ph[15]);
     return AV_OK;
 }
 
@@ -1985,14 +1850,12 @@ void group_worker(av_msckf_batch* g)
     }
 }
 
-int default_groups(int n_streams)
+int default_groups(int n_streams, bool host_store)
 {
     const char* e = getenv("AV_MSCKF_GROUPS");
     // host-bookkeeping path: 4 groups overlap one group's host phases with the others' kernels.  Device-resident path: the groups only
     // add concurrency between two latency chains; more of them just compete (2,048 streams: 1 / 2 / 3 / 4 / 8 groups = 132 / 128-134 /
     // 121 / 101 / 80 k frames/s at the default priority)
-    const char* st = getenv("AV_MSCKF_STORE");
-    const bool host_store = st && !strcmp(st, "host");
     int g = e ? atoi(e) : (host_store ? (n_streams >= 256 ? 4 : (n_streams >= 64 ? 2 : 1)) : (n_streams >= 1024 ? 2 : 1));
     if (g > 8) g = 8;
     if (g > n_streams) g = n_streams;
@@ -2007,10 +1870,12 @@ AV_EXPORT int av_msckf_batch_create(int n_streams, int max_cam_states, int rows_
                                     const double* opt6, int device, av_msckf_batch** out)
 {
     if (!out || n_streams <= 0) { av_set_error("av_msckf_batch_create: bad arguments"); return AV_E_INVALID; }
-    const int G = default_groups(n_streams);
+    const char* store = getenv("AV_MSCKF_STORE");           // read once: the groups, their streams' priority and the filter's path follow it
+    const bool host_store = store && !strcmp(store, "host");
+    const int G = default_groups(n_streams, host_store);
     if (G == 1)
         return sub_create(n_streams, max_cam_states, rows_cap, chi2_table_100, gravity, T_cam0_cam1_rowmajor44, R_imu_cam0_t_cam0_imu12, cov_init5, noise4,
-                          obs_noise, position_std_threshold, velocity0, opt6, device, out);
+                          obs_noise, position_std_threshold, velocity0, opt6, device, host_store, out);
     av_msckf_batch* p = new (std::nothrow) av_msckf_batch(0);
     if (!p) { av_set_error("out of host memory"); return AV_E_INVALID; }
     p->device = device; p->S = n_streams; p->per_sub = (n_streams + G - 1) / G;
@@ -2020,11 +1885,11 @@ AV_EXPORT int av_msckf_batch_create(int n_streams, int max_cam_states, int rows_
         const int cnt = n_streams - s0 < p->per_sub ? n_streams - s0 : p->per_sub;
         av_msckf_batch* g = nullptr;
         int rc = sub_create(cnt, max_cam_states, rows_cap, chi2_table_100, gravity, T_cam0_cam1_rowmajor44, R_imu_cam0_t_cam0_imu12, cov_init5, noise4,
-                            obs_noise, position_std_threshold, velocity0, opt6, device, &g);
+                            obs_noise, position_std_threshold, velocity0, opt6, device, host_store, &g);
         if (rc == AV_OK) {
             // highest priority: the filter's kernels are short, latency-bound and on the step's critical path; the
             // front-end's throughput kernels (other streams) fill whatever they leave free
-            if (make_filter_stream(&g->own) != hipSuccess) { av_set_error("hipStreamCreate failed"); rc = AV_E_HIP; }
+            if (make_filter_stream(&g->own, host_store) != hipSuccess) { av_set_error("hipStreamCreate failed"); rc = AV_E_HIP; }
         }
         if (rc) { if (g) sub_destroy(g); av_msckf_batch_destroy(p); return rc; }
         g->host_cap = share;

@@ -82,7 +82,7 @@ struct DevArgs {
     // dk_begin triangulates the lost features itself (dev_triangulate_own)
     double huber, precision, damping; int outer_max, inner_max;
     double* Hblk; double* rblk; size_t hstride, rstride; const double* chi2; double obs_noise; double* gamma; int* pass;
-    const UpdArgs* updbase; UpdArgs* upd; int* cols; int cols_stride; int* blk_row; int* blk_len; int* stacked_out; double* work; int no_info;
+    const UpdArgs* updbase; UpdArgs* upd; int* cols; int cols_stride; int* blk_row; int* blk_len; int* stacked_out; double* work;
 };
 
 // triangulate_kernel's arguments for the candidates of one phase: lost features from their own CSR, pruning candidates from the

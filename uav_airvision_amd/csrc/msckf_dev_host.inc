@@ -121,7 +121,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
     A.huber = b->opt5[0]; A.precision = b->opt5[1]; A.damping = b->opt5[2]; A.outer_max = (int)b->opt5[3]; A.inner_max = (int)b->opt5[4];
     A.Hblk = b->Hblk; A.rblk = b->rblk; A.hstride = b->hstride; A.rstride = b->rstride; A.chi2 = b->chi2_dev; A.obs_noise = b->obs_noise;
     A.gamma = d->gamma; A.pass = d->pass; A.updbase = d->updbase; A.upd = d->upd; A.cols = d->cols; A.cols_stride = 6 * b->cam_slots;
-    A.blk_row = d->blk_row; A.blk_len = d->blk_len; A.stacked_out = d->stacked1; A.work = d->work; A.no_info = b->env.no_info ? 1 : 0;
+    A.blk_row = d->blk_row; A.blk_len = d->blk_len; A.stacked_out = d->stacked1; A.work = d->work;
     A.stacked = nullptr; A.dx = b->dx; A.ctl = nullptr; A.imu = nullptr; A.prop = nullptr; A.cov = d->cov_d; A.msg_ids = nullptr; A.msg_uv = nullptr; A.msg_n = nullptr; A.msg_cap = cap; A.out = d->out_d;
     if (!grow) {
         std::vector<DState> st(S);
@@ -163,7 +163,7 @@ int dev_upload_updbase(av_msckf_batch* b)
         u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
         u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
         u.Sbuf = b->scratch + (size_t)s * b->pstride;
-        u.mode = b->env.no_info ? 0 : 1;
+        u.mode = 1;
         if (s == 0) u.prof = dev_uprof();
     }
     AV_HIP(hipMemcpy(d->updbase, base.data(), sizeof(UpdArgs) * base.size(), hipMemcpyHostToDevice));
@@ -185,8 +185,7 @@ int launch_feature_dev(FeatArgs a, int teams, int Mx, hipStream_t st)
     // teams of a wavefront or less: ONE wavefront per workgroup.  Beside the front-end a 256-thread workgroup needs a free slot on all
     // four SIMDs of a CU at once; a single wavefront takes the first hole a retiring wavefront leaves (profiles/r05/README.md: the
     // kernels of the chain that are launched as single wavefronts run at their exclusive speed in the shared run, the others 2-5x slower)
-    static const int small_wg = [] { const char* e = getenv("AV_FEAT_WG"); const int v = e ? atoi(e) : 64; return v == 256 ? 256 : 64; }();      // A/B switch
-    const int wg = team == 256 ? 256 : small_wg;
+    const int wg = team == 256 ? 256 : 64;
     const int tpb = wg / team;
     const size_t lds = per * tpb;
     if (lds > 160 * 1024) { av_set_error("MSCKF feature blocks: %d observations per feature need %zu B of LDS", Mx, lds); return AV_E_CAPACITY; }
@@ -210,8 +209,7 @@ int dev_grid_hint(const DevPath* d, int idx, int worst, int floor_teams = 256)
     // of 16 teams per stream the five lost-feature buckets launched 16,384 workgroups each for ~2,000 features per group-step and
     // took 0.84 ms with the GPU to themselves, 3.9 ms in the shared path.  A step whose load jumps (every stream prunes at once, a
     // blank frame drops every track) strides over its lists with the previous step's grid once; the next step's grid follows.
-    static const int pct = [] { const char* e = getenv("AV_MSCKF_GRID_PCT"); const int v = e ? atoi(e) : 112; return v < 25 ? 25 : (v > 400 ? 400 : v); }();
-    long long g = (long long)d->hint[idx] * pct / 100 + 64;
+    long long g = (long long)d->hint[idx] * 112 / 100 + 64;
     if (g < floor_teams) g = floor_teams;
     if (g > worst) g = worst;
     return g < 1 ? 1 : (int)g;
@@ -260,13 +258,9 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
     // does this phase ever need the Cholesky back end?  If not (the pruning phase as a rule) its only reader is upd_info_kernel, which gathers
     // the 12 columns of the two cameras that go -- the columns every candidate writes: the rows are then stored compact, 12 doubles
     // each (480 contiguous bytes per feature instead of ten 48-byte pieces 1.2 KB apart, for the writer and for the reader)
-    const bool rounds = ph == 0 || 5 * cap > INFO_MAXROWS || b->env.no_info;
+    const bool rounds = ph == 0 || 5 * cap > INFO_MAXROWS;
     const int hld = rounds ? 0 : 12;
     f.compact = hld;
-    static const int dev_skip = [] { const char* e = getenv("AV_DEV_SKIP"); return e ? atoi(e) : 0; }();      // timing experiments only (results are then wrong): bit 0 = no pruning-phase feature kernel, bit 1 = no lost-phase buckets
-    if (ph == 0 && (dev_skip & 2)) {
-    } else if (ph == 1 && (dev_skip & 1)) {
-    } else
     if (ph == 0) {
         // length buckets (the LDS footprint grows with the square of the track length), one launch after the other on the group's own
         // stream.  Round 3 forked them onto four auxiliary streams; with ~2 lost features per stream and step the kernels are short
@@ -316,7 +310,6 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
     sa.pass = d->pass; sa.obs_off = A.f_off; sa.obs_cam = A.obs_cam; sa.row_off = A.f_rowoff;
     sa.blk_row = d->blk_row; sa.blk_len = d->blk_len; sa.cols = d->cols; sa.cols_stride = 6 * b->cam_slots;
     sa.base = d->updbase; sa.out = d->upd; sa.S = S; sa.rounds = 1; sa.cut1500 = cut1500 ? 1 : 0; sa.kch = DEV_KCH; sa.stacked = ph == 0 ? d->stacked0 : d->stacked1;
-    sa.compress = 1;
     sa.over = A.over; sa.row_off_w = A.f_rowoff; sa.again_list = d->again; sa.again_count = cnt + 7;
     sa.clist = d->clist; sa.clist_count = cnt + 6; sa.work = d->work;
     sa.hld = hld;
@@ -326,7 +319,7 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
     // (no second feature pass: a stream whose candidates outgrow its region of the block buffers takes rows from the shared pool,
     //  dev_build_candidates -- the pass had to be launched every step and waited ~1.1 ms for a CU beside the front-end to do nothing)
     if ((rc = msckf_lds_opt_in())) return rc;
-    if (ph == 1 && !b->env.no_info) {
+    if (ph == 1) {
         const int minfo = 5 * cap < INFO_MAXROWS ? 5 * cap : INFO_MAXROWS;
         const size_t lds_i = upd_info_lds(12, b->ld, minfo);
         if (lds_i > 160 * 1024) { av_set_error("batched MSCKF: information-form update needs %zu B of LDS", lds_i); return AV_E_CAPACITY; }
@@ -548,9 +541,6 @@ int dev_finish(av_msckf_batch* b, int k, double* out)
     memcpy(out, sl.out_h, sizeof(double) * 12 * b->S);
     for (int i = 0; i < 16; ++i) d->hint[i] = sl.cnt_h[i];
     d->have_hint = true;
-    if (b->env.debug && (d->steps % 8) == 0)
-        fprintf(stderr, "[msckf-dev] step %lld lists: lost buckets %d %d %d %d %d tri %d long %d again %d | prune feat %d tri %d long %d\n", d->steps,
-                sl.cnt_h[0], sl.cnt_h[1], sl.cnt_h[2], sl.cnt_h[3], sl.cnt_h[4], sl.cnt_h[5], sl.cnt_h[6], sl.cnt_h[7], sl.cnt_h[8], sl.cnt_h[13], sl.cnt_h[14]);
     for (int ph = 0; ph < 2; ++ph) if (sl.t_used[ph]) {       // the whole step has retired: both phases' event pairs of this slot are complete
         float ms = 0;
         if (hipEventElapsedTime(&ms, sl.t0[ph], sl.t1[ph]) == hipSuccess) b->w_chain_ms += ms; else ++b->w_chain_dropped;

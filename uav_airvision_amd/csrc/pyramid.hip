@@ -28,7 +28,7 @@ struct PyrArgs {
     int64_t stream_stride, slot_stride;
     int slot0, slot1;
     PyrGeom g;
-    int n_img, tiles_x, tiles_y;       // pyr_l0l1_kernel: XCD-aware 1-D launch when tiles_x > 0
+    int n_img, tiles_x, tiles_y;       // pyr_l0l1_kernel: XCD-aware 1-D launch
     const int* index;                  // optional: image group i (a "stream") is storage entry index[i] of img0 / img1 / pyr_base (shared frame store)
 };
 
@@ -106,14 +106,11 @@ __global__ __launch_bounds__(256) void pyr_l0l1_kernel(PyrArgs a)
     // L2 each): horizontally adjacent tiles share every 128-byte line a 752-byte image row lays across their boundary, and
     // vertically adjacent ones their 4 halo rows -- on eight L2s each of those lines is fetched once per XCD that meets it
     // (PMC: 2.3x the image bytes), on one L2 once.
-    int img, bx, by;
-    if (a.tiles_x > 0) {
-        const int L = blockIdx.x, j = L >> 3, per = a.tiles_x * a.tiles_y;
-        img = (L & 7) + 8 * (j / per);
-        if (img >= a.n_img) return;
-        const int t = j % per;
-        by = t / a.tiles_x; bx = t - by * a.tiles_x;
-    } else { img = blockIdx.z; bx = blockIdx.x; by = blockIdx.y; }
+    const int L = blockIdx.x, wg = L >> 3, per = a.tiles_x * a.tiles_y;
+    const int img = (L & 7) + 8 * (wg / per);
+    if (img >= a.n_img) return;
+    const int tile = wg % per;
+    const int by = tile / a.tiles_x, bx = tile - by * a.tiles_x;
     const int x0 = bx * FT_W, y0 = by * FT_H;
     int s, cam;
     pyr_entry(a, img, s, cam);
@@ -459,16 +456,13 @@ int av_launch_pyramid(const uint8_t* img0, const uint8_t* img1, int64_t img_stri
     const int w = g.w[0], h = g.h[0];
     // the fused level-0 + level-1 kernel needs: dword-aligned rows, whole 32-row tiles, a last tile column that still holds the
     // 17 pixels its frame mirrors, images large enough that a pixel is never in two mirror bands
-    static const bool tall_ok = [] { const char* e = getenv("AV_PYR_TALL"); return !(e && atoi(e) == 0); }();      // A/B switch
-    const int FT_H = (tall_ok && (h % FT_H_TALL) == 0 && h >= 2 * FT_H_TALL) ? FT_H_TALL : FT_H_BASE;
+    const int FT_H = ((h % FT_H_TALL) == 0 && h >= 2 * FT_H_TALL) ? FT_H_TALL : FT_H_BASE;
     const bool fused = g.levels >= 2 && (w & 15) == 0 && (h % FT_H) == 0 && h >= 64 && w >= 64 && (w % FT_W == 0 || w % FT_W >= 20) &&
-                       (img_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img0) & 3) == 0 && (!img1 || (reinterpret_cast<uintptr_t>(img1) & 3) == 0) &&
-                       !getenv("AV_PYR_UNFUSED");
+                       (img_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img0) & 3) == 0 && (!img1 || (reinterpret_cast<uintptr_t>(img1) & 3) == 0);
     if (fused) {
-        static const bool xcd_map = [] { const char* e = getenv("AV_PYR_XCD"); return !(e && atoi(e) == 0); }();      // A/B switch
         const int tx = (w + FT_W - 1) / FT_W, ty = h / FT_H;
-        a.n_img = n_img; a.tiles_x = xcd_map ? tx : 0; a.tiles_y = ty;
-        dim3 grid = xcd_map ? dim3((unsigned)(tx * ty) * 8u * (unsigned)((n_img + 7) / 8)) : dim3(tx, ty, n_img);
+        a.n_img = n_img; a.tiles_x = tx; a.tiles_y = ty;
+        dim3 grid((unsigned)(tx * ty) * 8u * (unsigned)((n_img + 7) / 8));
         if (FT_H == FT_H_TALL) {
             if (write_level0) hipLaunchKernelGGL((pyr_l0l1_kernel<true, FT_H_TALL>), grid, dim3(256), 0, st, a);
             else { hipLaunchKernelGGL((pyr_l0l1_kernel<false, FT_H_TALL>), grid, dim3(256), 0, st, a); if (wrote_level0) *wrote_level0 = false; }
@@ -485,7 +479,7 @@ int av_launch_pyramid(const uint8_t* img0, const uint8_t* img1, int64_t img_stri
     }
     // levels 2 + 3 by one workgroup per image when the level-2 image fits in LDS
     const size_t lds23 = g.levels == 4 ? ((((size_t)g.h[2] * ((g.w[2] + 3) & ~3) + 15) & ~(size_t)15) + (size_t)g.h[3] * ((g.w[3] + 3) & ~3) + 16) : 0;
-    const bool fused23 = g.levels == 4 && lds23 <= 60 * 1024 && (g.pitch[1] & 3) == 0 && !getenv("AV_PYR_UNFUSED");
+    const bool fused23 = g.levels == 4 && lds23 <= 60 * 1024 && (g.pitch[1] & 3) == 0;
     int lbeg = fused ? 2 : 1;
     if (fused23) {
         if (!fused) {
