@@ -143,6 +143,10 @@ typedef struct av_frontend_config {
     double  norm_unit;                       /* 4/(2fx+2fy) of cam0 (stereo_matcher.py:103-104)     */
     int32_t cam0_distortion_model;           /* AV_DISTORTION_* (config.py:98); 0 = radtan          */
     int32_t cam1_distortion_model;           /* config.py:117                                       */
+    double  ransac_threshold;                /* config.ransac_threshold (config.py:29), pixels; read only with AV_FE_RANSAC */
+    double  ransac_success_probability;      /* config.ransac_success_probability, 0 < p < 1 (0.99)  */
+    uint32_t ransac_seed;                    /* config.ransac_seed: first word of the draw hash      */
+    int32_t reserved0;                       /* keeps the size a multiple of 8; must be 0            */
 } av_frontend_config;
 
 typedef struct av_frontend av_frontend;
@@ -165,6 +169,12 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * the call's own kernels and level 0 is copied (the round-1/2 behaviour).  av_frontend_step_host always works in place: the
  * images live in the library's own staging slots.  Results are bit-identical either way. */
 #define AV_FE_INPUTS_PERSIST 1
+/* AV_FE_RANSAC: two-point RANSAC outlier rejection between the stereo re-match and the re-binning of the tracked features (the
+ * step feature_tracker.py:135-136 leaves empty: both inlier vectors are all ones there).  A tracked feature survives iff its cam0
+ * problem and its cam1 problem (av_two_point_ransac below: previous / current points of that camera, cam*_R_p_c of
+ * imu_processor.py:28-67) both mark it; a rejected feature is absent from the published message and from the FAST mask.  Without
+ * the flag the step enqueues exactly what it always did.  Needs grid_num * grid_max <= AV_RANSAC_MAX_PAIRS. */
+#define AV_FE_RANSAC 2
 
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
@@ -246,6 +256,58 @@ int av_frontend_read_counters(av_frontend* fe, int stream_idx, int32_t out[8], v
  * best inliers per cell; the first grid_min + 2 candidates of a cell decide that unless too few of them are inliers):
  * [candidates matched in round 1, in round 2] of the last step, i.e. the LK point passes actually run.  Synchronises. */
 int av_frontend_read_match_counts(av_frontend* fe, int stream_idx, int32_t out[2], void* stream);
+
+/* [after_ransac, cam0 markers set, cam1 markers set, path bits] of the last step for one stream of an engine created with
+ * AV_FE_RANSAC (zeros otherwise, and on a step that tracked nothing).  path bits = cam0 path | cam1 path << 4 with the
+ * AV_RANSAC_PATH_* codes below.  Synchronises. */
+int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, int32_t out[4], void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Two-point RANSAC on the temporal matches of ONE camera (no counterpart in the reference: feature_tracker.py:135-136 is where
+ * it would run; the stereo MSCKF the reference descends from has it).  The IMU gives the rotation, so two point pairs fix the
+ * translation direction.  One problem: n pairs (p1_i, p2_i) of float32 pixel positions of the same feature in the previous and the
+ * current image, R = rotation previous -> current camera frame, the camera's model, thr (pixels), success probability p.
+ * Output: one marker (0 / 1) per pair.  All arithmetic in fp64, products summed left to right, no contraction:
+ *   1. u1_i = undistort(p1_i), u2_i = undistort(p2_i): normalised coordinates, identity rectification (av_undistort_points_model)
+ *   2. h = R (u1_i.x, u1_i.y, 1);  u1_i = (h.x / h.z, h.y / h.z)
+ *   3. s = sqrt(2) * 2n / sum_i (|u1_i| + |u2_i|);  u1_i *= s, u2_i *= s;  unit = s * 2 / (fx + fy)
+ *   4. d_i = u1_i - u2_i.  |d_i| > 50 unit: marker 0.  The others are the raw set (index order), m of them, mean |d_i| = mean
+ *   5. m < 3: all markers 0                                                              (AV_RANSAC_PATH_FEW)
+ *   6. mean < unit (standstill / pure rotation): raw pairs with |d_i| > thr unit get 0, the others 1   (AV_RANSAC_PATH_STILL)
+ *   7. c_i = (d_i.y, -d_i.x, u1_i.x u2_i.y - u1_i.y u2_i.x): a translation direction t consistent with pair i has c_i . t = 0
+ *   8. N = av_ransac_num_hypotheses(p).  Hypothesis k: r0 = av_ransac_hash(seed, frame, camera, k, 0), r1 = (.., k, 1);
+ *      a = r0 mod m, b = (a + 1 + r1 mod (m - 1)) mod m index the raw set.  The column of [c_a; c_b] with the smallest L1 norm
+ *      (first on ties) is the base j: t_j = 1, the other two (p < q) solve the 2 x 2 system: det = c_a[p] c_b[q] - c_a[q] c_b[p],
+ *      t_p = (c_a[q] c_b[j] - c_a[j] c_b[q]) / det, t_q = (c_a[j] c_b[p] - c_a[p] c_b[j]) / det.  det == 0 or a non-finite t skips
+ *      the hypothesis.  A raw pair is an inlier if |c_i . t| < thr unit.  Fewer inliers than 0.2 n skips the hypothesis.  The
+ *      hypothesis with strictly more inliers than the best so far becomes the best.                  (AV_RANSAC_PATH_MODEL)
+ *   9. markers = the best inlier set; all 0 if no hypothesis qualified                    (.. | AV_RANSAC_PATH_NONE)
+ * The draws are a stateless hash of (seed, the stream's own frame number, camera, k, draw) and of nothing else, so a problem gives
+ * the same markers alone, anywhere in a batch and in any launch shape:
+ *   mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16          (uint32, wrapping)
+ *   av_ransac_hash(seed, frame, camera, k, draw) = mix(mix(mix(seed + 0x9e3779b9) ^ frame) ^ (camera << 16 | k << 1 | draw))
+ * av_ransac_hash and av_ransac_num_hypotheses are pure host functions (the kernels inline the same code):
+ *   N = ceil(log(1 - p) / log(1 - 0.7^2)) clamped to 1 .. AV_RANSAC_MAX_HYPOTHESES; 7 at p = 0.99; 0 if p is outside (0, 1).
+ *
+ * av_two_point_ransac runs n_problems problems in one launch (one wavefront each).  Problem b owns the pairs off_dev[b] ..
+ * off_dev[b + 1] - 1 of pts1_dev / pts2_dev (float32 x, y), at most max_pairs <= AV_RANSAC_MAX_PAIRS of them; R_dev[9 b ..] is its
+ * rotation (row-major), camera_dev[b] and frame_dev[b] its hash words (NULL = all 0).  intr / dist / model as in
+ * av_undistort_points_model (host pointers, one camera model per call).  markers_dev: uint8 per pair.  info_dev (optional):
+ * int32 [n_problems][2] = {markers set, AV_RANSAC_PATH_* code}; {-1, -1} for a problem with more than max_pairs pairs (its markers
+ * are not written).
+ * ------------------------------------------------------------------------------------------- */
+#define AV_RANSAC_MAX_PAIRS       1920     /* per problem: the pairs of a problem live in one workgroup's LDS (33 B each) */
+#define AV_RANSAC_MAX_HYPOTHESES  64
+#define AV_RANSAC_PATH_FEW    1
+#define AV_RANSAC_PATH_STILL  2
+#define AV_RANSAC_PATH_MODEL  4
+#define AV_RANSAC_PATH_NONE   8
+uint32_t av_ransac_hash(uint32_t seed, uint32_t frame, uint32_t camera, uint32_t k, uint32_t draw);
+int av_ransac_num_hypotheses(double success_probability);
+int av_two_point_ransac(const float* pts1_dev, const float* pts2_dev, const int32_t* off_dev, int n_problems, int max_pairs,
+                        const double* R_dev, const int32_t* camera_dev, const int32_t* frame_dev,
+                        const double* intr, const double* dist, int model, double inlier_error, double success_probability,
+                        uint32_t seed, uint8_t* markers_dev, int32_t* info_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * MSCKF back-end: the batched small-dense fp64 linear algebra of MSCKF.feature_callback

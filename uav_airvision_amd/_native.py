@@ -16,6 +16,10 @@ AV_MAX_LEVELS = 5
 AV_PYR_BORDER = 16
 AV_OK, AV_E_INVALID, AV_E_HIP, AV_E_CAPACITY, AV_E_NODEVICE, AV_E_NUMERIC = 0, -1, -2, -3, -4, -5
 AV_FE_INPUTS_PERSIST = 1
+AV_FE_RANSAC = 2
+AV_RANSAC_MAX_PAIRS = 1920
+AV_RANSAC_MAX_HYPOTHESES = 64
+AV_RANSAC_PATH_FEW, AV_RANSAC_PATH_STILL, AV_RANSAC_PATH_MODEL, AV_RANSAC_PATH_NONE = 1, 2, 4, 8
 
 
 DISTORTION_MODELS = {'radtan': 0, 'equidistant': 1}          # AV_DISTORTION_* (include/airvision.h)
@@ -51,7 +55,9 @@ class FrontendConfig(C.Structure):
                 ('cam1_intrinsics', C.c_double * 4), ('cam1_distortion', C.c_double * 4),
                 ('R_cam0_imu', C.c_double * 9), ('R_cam1_imu', C.c_double * 9),
                 ('R0to1', C.c_double * 9), ('E', C.c_double * 9), ('norm_unit', C.c_double),
-                ('cam0_distortion_model', C.c_int32), ('cam1_distortion_model', C.c_int32)]
+                ('cam0_distortion_model', C.c_int32), ('cam1_distortion_model', C.c_int32),
+                ('ransac_threshold', C.c_double), ('ransac_success_probability', C.c_double),
+                ('ransac_seed', C.c_uint32), ('reserved0', C.c_int32)]
 
 
 # name -> (restype, argtypes); the list doubles as the export check of tests/test_abi.py
@@ -123,6 +129,11 @@ SIGNATURES = {
     'av_msckf_batch_work_executed': (C.c_int, [_P, C.POINTER(C.c_double * 2)]),
     'av_msckf_batch_get_state': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 32), _P, _P, C.c_int, C.POINTER(C.c_int32)]),
     'av_msckf_batch_stream_status': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_int]),
+    'av_frontend_read_ransac_counts': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 4), _P]),
+    'av_ransac_hash': (C.c_uint32, [C.c_uint32] * 5),
+    'av_ransac_num_hypotheses': (C.c_int, [C.c_double]),
+    'av_two_point_ransac': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
+                                      C.c_double, C.c_double, C.c_uint32, _P, _P, _P]),
     'av_frontend_enable_timing': (C.c_int, [_P, C.c_int]),
     'av_frontend_read_timing': (C.c_int, [_P, C.POINTER(C.c_double * 4), C.POINTER(C.c_int32 * 4)]),
 }

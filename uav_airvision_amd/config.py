@@ -38,7 +38,12 @@ class ConfigEuRoC(object):
         self.grid_min_feature_num = grid_min_feature_num
         self.grid_max_feature_num = grid_max_feature_num
         self.fast_threshold = 15
-        self.ransac_threshold = 3      # stored, never read by the reference
+        self.ransac_threshold = 3      # pixels; the reference stores it and never reads it; read here when use_ransac is set
+        # two-point RANSAC on the tracked features (no counterpart in the reference: feature_tracker.py:135-136 is the empty step).
+        # Off by default: with it off the front-end is the reference's, bit for bit.
+        self.use_ransac = False
+        self.ransac_success_probability = 0.99
+        self.ransac_seed = 0
         self.stereo_threshold = 5
         self.max_iteration = 30
         self.track_precision = 0.01

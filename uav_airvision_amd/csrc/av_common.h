@@ -46,7 +46,32 @@ struct CamModel {
 #define AV_KP_RASTER_BITS 19
 #define AV_KP_RASTER_MASK ((1u << AV_KP_RASTER_BITS) - 1u)
 
+// ---- draw hash of the two-point RANSAC (written out in include/airvision.h; host and device) ---
 #ifdef __HIPCC__
+#define AV_HD __host__ __device__
+#else
+#define AV_HD
+#endif
+AV_HD inline uint32_t av_ransac_mix(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+AV_HD inline uint32_t av_ransac_hash_inl(uint32_t seed, uint32_t frame, uint32_t camera, uint32_t k, uint32_t draw)
+{
+    return av_ransac_mix(av_ransac_mix(av_ransac_mix(seed + 0x9e3779b9u) ^ frame) ^ (camera << 16 | k << 1 | draw));
+}
+
+#ifdef __HIPCC__
+// 7x7 box of the FAST mask around (int)p with numpy slice semantics (feature_adder.py:59-62): element j of the box
+__device__ __forceinline__ void av_mask_box(uint8_t* m, int w, int h, float px, float py, int j, uint8_t val)
+{
+    int fx = (int)px, fy = (int)py;
+    if (fx < 3 || fy < 3) return;                 // negative slice start => empty slice
+    int yy = fy - 3 + j / 7, xx = fx - 3 + j % 7;
+    if (yy < h && xx < w) m[(size_t)yy * w + xx] = val;
+}
+
 // cv::borderInterpolate(p, len, BORDER_REFLECT_101) for |overshoot| < len
 __device__ __forceinline__ int av_reflect101(int p, int len)
 {
@@ -178,3 +203,19 @@ int av_launch_fast(const uint8_t* img, int64_t img_stride, int img_pitch, int bo
                    uint32_t* kp, int* count, int cap,                               // flat output (ops API) or NULL
                    uint32_t* tile_kp, int* tile_count,                              // per-tile output (front-end engine) or NULL
                    int* overflow, int stat_stride, hipStream_t st, const int* index = nullptr);      // index: image i of the launch is storage entry index[i]
+
+// ransac.hip: the engine's outlier-rejection stage (AV_FE_RANSAC), one single-wavefront workgroup per stream: both camera problems,
+// ordered compaction of cur_* to the survivors, cur_count, counts[s][4], then the FAST mask boxes of the survivors
+struct RansacStage {
+    int S, NT, MAXF, w, h;
+    CamModel cam[2];
+    const float* prev_p0; const float* prev_p1;      // the previous grid [S][MAXF][2]
+    long long* cur_id; int* cur_life; float* cur_p0; float* cur_p1; int* cur_cell; const int* cur_src; int* cur_count;
+    uint8_t* mask;
+    const double* Rpc;                               // [S][2][9]: cam0_R_p_c, cam1_R_p_c
+    const int* frame_no;                             // [S]
+    const int* slot_cur;                             // frame-store step: < 0 = the stream idles (null otherwise)
+    int* counts;                                     // [S][4]
+    double thr; int N; uint32_t seed;
+};
+int av_launch_ransac_stage(const RansacStage& a, hipStream_t st);

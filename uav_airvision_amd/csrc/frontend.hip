@@ -58,6 +58,7 @@ struct FeDev {
     int* sv_src; float* sv_p0; float* sv_init; float* sv_p1; uint8_t* sv_st; float* sv_back; uint8_t* sv_st2; int* sv_count;
     // curr_features after the tracker (insertion order)
     long long* cur_id; int* cur_life; float* cur_p0; float* cur_p1; int* cur_cell; int* cur_count;
+    int* cur_src;                                         // AV_FE_RANSAC: index of every curr feature in the previous grid (null without the flag)
     // FAST per-cell lists + mask
     uint32_t* cell_kp; int* cell_count; uint8_t* mask;
     uint32_t* tile_kp; int* tile_count; int n_tiles, tile_cap;      // FAST survivors per detector tile (fast.hip), binned into cells by select_kernel
@@ -189,13 +190,12 @@ __global__ __launch_bounds__(256) void track_gate_kernel(FeDev d)
 // 7x7 box of the FAST mask with numpy slice semantics (feature_adder.py:59-62)
 __device__ __forceinline__ void mask_box(const FeDev& d, uint8_t* m, float px, float py, int j, uint8_t val)
 {
-    int fx = (int)px, fy = (int)py;
-    if (fx < 3 || fy < 3) return;                 // negative slice start => empty slice
-    int yy = fy - 3 + j / 7, xx = fx - 3 + j % 7;
-    if (yy < d.h && xx < d.w) m[(size_t)yy * d.w + xx] = val;
+    av_mask_box(m, d.w, d.h, px, py, j, val);
 }
 
 // ---- G3: stereo gate of the survivors, re-bin into curr_features, set FAST mask ----------------
+// With AV_FE_RANSAC (d.cur_src set) the features also record where they came from in the previous grid, and the mask is left to
+// the outlier-rejection stage that follows (ransac.hip): it is built from the features that survive it.
 __global__ __launch_bounds__(256) void rebin_kernel(FeDev d, int par)
 {
     __shared__ int lds4[4];
@@ -220,9 +220,11 @@ __global__ __launch_bounds__(256) void rebin_kernel(FeDev d, int par)
             d.cur_p0[2 * o] = x; d.cur_p0[2 * o + 1] = y;
             d.cur_p1[2 * o] = d.sv_p1[2 * t]; d.cur_p1[2 * o + 1] = d.sv_p1[2 * t + 1];
             d.cur_cell[o] = cell_of(d, x, y);
+            if (d.cur_src) d.cur_src[o] = d.sv_src[t];
         }
     }
     if (threadIdx.x == 0) { d.cur_count[s] = base; d.counters[s * NCNT + CNT_MATCHED] = base; }
+    if (d.cur_src) return;
     __syncthreads();
     uint8_t* m = d.mask + (size_t)s * d.w * d.h;
     for (int q = threadIdx.x; q < base * 49; q += NTB) {
@@ -590,6 +592,7 @@ struct StreamHost {
     std::mutex mu;
     double t_prev = 0.0;
     bool first = true;
+    int frame = 0;                     // frames this stream has been given so far (the RANSAC draw hash takes it)
 };
 
 inline void mat3_mul(const double* A, const double* B, double* o)
@@ -661,6 +664,8 @@ struct av_frontend {
     // optional HIP-event timing per kernel class (bench.py's roofline leg)
     bool timing = false;
     std::vector<hipEvent_t> ev; std::vector<int> ev_cls; size_t ev_used = 0;
+    // AV_FE_RANSAC: the stage's arguments; Rpc / frame_no are uploaded with the homographies, behind them in the same staging slot
+    bool ransac = false; RansacStage rs; int* rs_counts = nullptr;
 
     explicit av_frontend(int S) : streams(S) {}
 };
@@ -678,12 +683,14 @@ int dev_alloc(av_frontend* fe, T** p, size_t count, int fill = 0)
     return AV_OK;
 }
 
-int integrate_imu(av_frontend* fe, int s, double t_curr, double* H)
+// Rpc (optional): [cam0_R_p_c, cam1_R_p_c] of imu_processor.py:56-65, 18 doubles
+int integrate_imu(av_frontend* fe, int s, double t_curr, double* H, double* Rpc = nullptr)
 {
     // imu_processor.py:28-67 + feature_tracker.py:166-171
     StreamHost& sh = fe->streams[s];
     const av_frontend_config& c = fe->cfg;
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (Rpc) for (int i = 0; i < 18; ++i) Rpc[i] = (i % 9) % 4 == 0 ? 1.0 : 0.0;
     {
         std::lock_guard<std::mutex> g(sh.mu);
         int ib = -1, ie = -1;
@@ -704,6 +711,15 @@ int integrate_imu(av_frontend* fe, int s, double t_curr, double* H)
             double Rr[9];
             rodrigues(rv, Rr);
             for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[i * 3 + j] = Rr[j * 3 + i];      // .T
+            if (Rpc) {
+                const double* R1 = c.R_cam1_imu;
+                double c1[3];
+                for (int i = 0; i < 3; ++i) c1[i] = (R1[0 * 3 + i] * m[0] + R1[1 * 3 + i] * m[1]) + R1[2 * 3 + i] * m[2];
+                double rv1[3] = {c1[0] * dt, c1[1] * dt, c1[2] * dt};
+                double Rr1[9];
+                rodrigues(rv1, Rr1);
+                for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { Rpc[i * 3 + j] = R[i * 3 + j]; Rpc[9 + i * 3 + j] = Rr1[j * 3 + i]; }
+            }
             sh.imu.erase(sh.imu.begin(), sh.imu.begin() + ie);
         }
     }
@@ -748,12 +764,15 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     double* hH = fe->hH[slot];
     bool any_first = false;
     int* hmap = reinterpret_cast<int*>(hH + (size_t)9 * S);      // [2][S] behind the homographies: this frame's / the previous frame's store entry
+    double* hR = hH + (size_t)10 * S;                            // AV_FE_RANSAC: [S][18] rotations, then [S] frame numbers
+    int* hframe = reinterpret_cast<int*>(hR + (size_t)18 * S);
     for (int s = 0; s < S; ++s) {
         StreamHost& sh = fe->streams[s];
         if (frames) {
             hmap[s] = slots[s] < 0 ? -1 : slots[s]; hmap[S + s] = fe->fs.prev[s];
             if (slots[s] < 0) {                  // no frame for this stream in this step: its IMU buffer, t_prev and grid stay as they are
                 for (int i = 0; i < 9; ++i) hH[s * 9 + i] = (i % 4 == 0) ? 1.0 : 0.0;
+                if (fe->ransac) { for (int i = 0; i < 18; ++i) hR[s * 18 + i] = (i % 9) % 4 == 0 ? 1.0 : 0.0; hframe[s] = sh.frame; }
                 continue;
             }
             fe->fs.prev[s] = slots[s];
@@ -761,13 +780,17 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         if (sh.first) {
             any_first = true;
             for (int i = 0; i < 9; ++i) hH[s * 9 + i] = (i % 4 == 0) ? 1.0 : 0.0;
+            if (fe->ransac) for (int i = 0; i < 18; ++i) hR[s * 18 + i] = (i % 9) % 4 == 0 ? 1.0 : 0.0;
         } else {
-            integrate_imu(fe, s, ts[s], hH + s * 9);
+            integrate_imu(fe, s, ts[s], hH + s * 9, fe->ransac ? hR + s * 18 : nullptr);
         }
+        if (fe->ransac) hframe[s] = sh.frame;
+        sh.frame += 1;
         sh.t_prev = ts[s];
         sh.first = false;
     }
-    AV_HIP(hipMemcpyAsync(fe->dH, hH, sizeof(double) * 9 * S + (frames ? sizeof(int) * 2 * S : 0), hipMemcpyHostToDevice, st));
+    if (fe->ransac) AV_HIP(hipMemcpyAsync(fe->dH, hH, sizeof(double) * 28 * S + sizeof(int) * S, hipMemcpyHostToDevice, st));
+    else AV_HIP(hipMemcpyAsync(fe->dH, hH, sizeof(double) * 9 * S + (frames ? sizeof(int) * 2 * S : 0), hipMemcpyHostToDevice, st));
     AV_HIP(hipEventRecord(fe->hH_ev[slot], st));
     AV_HIP(hipMemsetAsync(fe->zero_region, 0, fe->zero_bytes, st));
     const int* map_cur = nullptr; const int* map_prev = nullptr;
@@ -832,6 +855,12 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(rebin_kernel, dim3(S), dim3(256), 0, st, d, par);
       AV_LAUNCH_CHECK(); }
+    if (fe->ransac) {                          // outlier rejection on the tracked features (ransac.hip), one wavefront per stream
+        Span sp(fe, 3, st);
+        RansacStage a = fe->rs;
+        a.prev_p0 = d.feat_p0[par]; a.prev_p1 = d.feat_p1[par]; a.slot_cur = d.slot_cur;
+        if ((rc = av_launch_ransac_stage(a, st))) return rc;
+    }
     // (FAST on a second HIP stream beside the temporal / stereo LK launches -- it reads only the new cam0 image and is first needed by
     //  select_kernel -- was measured in round 5: front-end alone 196.6 k against 205.1 k frames/s, complete path 157.7 against 157.3 k:
     //  the LK launches slow down by more than the detector's time; profiles/r05/README.md)
@@ -889,6 +918,13 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     double e = cfg->lk_eps < 0 ? 0. : (cfg->lk_eps > 10. ? 10. : cfg->lk_eps);
     fe->lk.eps2 = e * e;
     fe->lk.min_eig = cfg->lk_min_eig;
+    const bool ransac = (cfg->flags & AV_FE_RANSAC) != 0;
+    const int rs_N = ransac ? av_ransac_num_hypotheses(cfg->ransac_success_probability) : 0;
+    if (ransac && (C * cfg->grid_max_feature_num > AV_RANSAC_MAX_PAIRS || rs_N <= 0 || !(cfg->ransac_threshold >= 0.0))) {
+        av_set_error("av_frontend_create: AV_FE_RANSAC needs grid_num * grid_max <= %d (%d), a success probability inside (0, 1) (%g) and a threshold >= 0 (%g)",
+                     AV_RANSAC_MAX_PAIRS, C * cfg->grid_max_feature_num, cfg->ransac_success_probability, cfg->ransac_threshold);
+        delete fe; return AV_E_INVALID;
+    }
     if (fe->lk.win < 3 || fe->lk.win > 31) { av_set_error("av_frontend_create: lk_win %d outside 3 .. 31", fe->lk.win); delete fe; return AV_E_INVALID; }      // 15: the 16-lane kernel; others: the general one
 
     FeDev& d = fe->d;
@@ -919,7 +955,7 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     }
     A(d.next_id, S)
     if ((rc = dev_alloc(fe, &d.first_frame, (size_t)S, 1))) { av_frontend_destroy(fe); return rc; }   // bytes 0x01 -> non-zero ints
-    A(fe->dH, 9 * S + S)                       // + [2][S] ints: the frame-store maps of the step (step_impl)
+    A(fe->dH, 9 * S + S + (ransac ? 19 * S : 0))      // + [2][S] ints: the frame-store maps of the step (step_impl); AV_FE_RANSAC: + [S][18] rotations, [S] frame numbers
     d.Hmat = fe->dH;
     A(d.trk_prev, 2 * S * d.NT) A(d.trk_next, 2 * S * d.NT) A(d.trk_status, S * d.NT)
     A(d.sv_src, S * d.NT) A(d.sv_p0, 2 * S * d.NT) A(d.sv_init, 2 * S * d.NT) A(d.sv_p1, 2 * S * d.NT) A(d.sv_st, S * d.NT)
@@ -944,9 +980,20 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         d.cell_count = z + 4 * S; d.counters = z + 4 * S + (size_t)S * C;
     }
     A(fe->pyr, (size_t)S * 3 * fe->lay.bytes)
+    if (ransac) {
+        A(d.cur_src, S * d.NT) A(fe->rs_counts, 4 * S)
+        RansacStage& a = fe->rs;
+        memset(&a, 0, sizeof(a));
+        a.S = S; a.NT = d.NT; a.MAXF = d.MAXF; a.w = w; a.h = h; a.cam[0] = d.cam0; a.cam[1] = d.cam1;
+        a.cur_id = d.cur_id; a.cur_life = d.cur_life; a.cur_p0 = d.cur_p0; a.cur_p1 = d.cur_p1; a.cur_cell = d.cur_cell; a.cur_src = d.cur_src;
+        a.cur_count = d.cur_count; a.mask = d.mask; a.counts = fe->rs_counts;
+        a.Rpc = fe->dH + (size_t)10 * S; a.frame_no = reinterpret_cast<const int*>(fe->dH + (size_t)28 * S);
+        a.thr = cfg->ransac_threshold; a.N = rs_N; a.seed = cfg->ransac_seed;
+        fe->ransac = true;
+    }
 #undef A
     for (int i = 0; i < 8; ++i) {
-        if (hipHostMalloc((void**)&fe->hH[i], sizeof(double) * (9 * S + S), hipHostMallocDefault) != hipSuccess ||
+        if (hipHostMalloc((void**)&fe->hH[i], sizeof(double) * (9 * S + S + (ransac ? 19 * S : 0)), hipHostMallocDefault) != hipSuccess ||
             hipEventCreateWithFlags(&fe->hH_ev[i], hipEventDisableTiming) != hipSuccess) {
             av_set_error("av_frontend_create: pinned staging allocation failed");
             av_frontend_destroy(fe);
@@ -1306,6 +1353,17 @@ AV_EXPORT int av_frontend_read_counters(av_frontend* fe, int stream_idx, int32_t
     AV_HIP(hipSetDevice(fe->device));
     AV_HIP(hipStreamSynchronize((hipStream_t)stream));
     AV_HIP(hipMemcpy(out, fe->d.counters + (size_t)stream_idx * NCNT, sizeof(int) * NCNT, hipMemcpyDeviceToHost));
+    return AV_OK;
+}
+
+AV_EXPORT int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, int32_t out[4], void* stream)
+{
+    if (!fe || stream_idx < 0 || stream_idx >= fe->d.S || !out) { av_set_error("av_frontend_read_ransac_counts: bad arguments"); return AV_E_INVALID; }
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (!fe->ransac) return AV_OK;
+    AV_HIP(hipSetDevice(fe->device));
+    AV_HIP(hipStreamSynchronize((hipStream_t)stream));
+    AV_HIP(hipMemcpy(out, fe->rs_counts + (size_t)stream_idx * 4, sizeof(int) * 4, hipMemcpyDeviceToHost));
     return AV_OK;
 }
 

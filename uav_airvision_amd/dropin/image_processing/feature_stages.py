@@ -77,7 +77,10 @@ class FeatureTracker(object):
     def __init__(self, lk_params, imu_processor, stereo_matcher, cam0_intrinsics, cam0_distortion_model,
                  cam0_distortion_coeffs, cam1_intrinsics, cam1_distortion_model, cam1_distortion_coeffs,
                  prev_cam0_pyramid, curr_cam0_pyramid, prev_features, curr_features, num_features,
-                 grid_row, grid_col, ransac_threshold):
+                 grid_row, grid_col, ransac_threshold, use_ransac=False, ransac_success_probability=0.99, ransac_seed=0,
+                 frame_number=0):
+        """The last four arguments have no counterpart in the reference (its tracker has no outlier rejection): use_ransac switches
+        the two-point RANSAC on; frame_number is the stream's own frame count (0 = first frame), the draw hash takes it."""
         self.lk_params = lk_params
         self.integrate_imu_data = imu_processor.integrate_imu_data
         self.R_cam0_imu, self.R_cam1_imu = imu_processor.R_cam0_imu, imu_processor.R_cam1_imu
@@ -87,7 +90,9 @@ class FeatureTracker(object):
         self.prev_cam0_pyramid, self.curr_cam0_pyramid = prev_cam0_pyramid, curr_cam0_pyramid
         self.prev_features, self.curr_features, self.num_features = prev_features, curr_features, num_features
         self.grid_row, self.grid_col = grid_row, grid_col
-        self.ransac_threshold = ransac_threshold            # stored, never read (no RANSAC exists)
+        self.ransac_threshold = ransac_threshold            # pixels; read when use_ransac is set (the reference never reads it)
+        self.use_ransac, self.ransac_success_probability = bool(use_ransac), ransac_success_probability
+        self.ransac_seed, self.frame_number = ransac_seed, frame_number
 
     def get_grid_size(self, img):
         return _grid_size(img, self.grid_row, self.grid_col)
@@ -101,7 +106,7 @@ class FeatureTracker(object):
         """feature_tracker.py:74-157."""
         img = self.curr_cam0_pyramid
         gh, gw = self.get_grid_size(img)
-        cam0_R_p_c, _cam1_R_p_c = self.integrate_imu_data()
+        cam0_R_p_c, cam1_R_p_c = self.integrate_imu_data()
         prev = list(chain.from_iterable(self.prev_features))
         self.num_features['before_tracking'] = len(prev)
         if not prev:
@@ -115,16 +120,26 @@ class FeatureTracker(object):
         self.num_features['after_tracking'] = len(keep)
         tracked = [curr_pts[i] for i in keep]
         cam1_pts, match = self.stereo_match(tracked)
+        sel = [(k, i) for k, i in enumerate(keep) if match[k]]
+        self.num_features['after_matching'] = len(sel)
+        if self.use_ransac and sel:
+            # the step feature_tracker.py:135-136 leaves empty: a feature survives iff both cameras' problems mark it
+            kw = dict(inlier_error=self.ransac_threshold, success_probability=self.ransac_success_probability, seed=self.ransac_seed,
+                      frame=self.frame_number)
+            m0 = ops.two_point_ransac(np.array([prev[i].cam0_point for _k, i in sel], dtype=np.float32),
+                                      np.array([tracked[k] for k, _i in sel], dtype=np.float32), cam0_R_p_c, self.cam0_intrinsics,
+                                      self.cam0_dist_model, self.cam0_dist_coeffs, camera=0, **kw)
+            m1 = ops.two_point_ransac(np.array([prev[i].cam1_point for _k, i in sel], dtype=np.float32),
+                                      np.array([cam1_pts[k] for k, _i in sel], dtype=np.float32), cam1_R_p_c, self.cam1_intrinsics,
+                                      self.cam1_dist_model, self.cam1_dist_coeffs, camera=1, **kw)
+            sel = [ki for ki, a, b in zip(sel, m0, m1) if a and b]
         n = 0
-        for k, i in enumerate(keep):
-            if not match[k]:
-                continue
+        for k, i in sel:
             f = FeatureMetaData()
             f.id, f.lifetime = prev[i].id, prev[i].lifetime + 1
             f.cam0_point, f.cam1_point = tracked[k], cam1_pts[k]
             self.curr_features[int(f.cam0_point[1] / gh) * self.grid_col + int(f.cam0_point[0] / gw)].append(f)
             n += 1
-        self.num_features['after_matching'] = n
         self.num_features['after_ransac'] = n
 
 

@@ -69,9 +69,12 @@ class ImageProcessingPipeline(object):
     @property
     def num_features(self):
         c = self._engine.read_counters(0)
+        # after_ransac: the engine's own count when config.use_ransac is set; the reference's tracker has no such step and reports
+        # after_matching again (feature_tracker.py:135-136, 157)
+        ransac = getattr(self.config, 'use_ransac', False) and c['after_matching'] > 0
         d = defaultdict(int)
-        d.update(before_tracking=c['before_tracking'], after_tracking=c['after_tracking'],
-                 after_matching=c['after_matching'], after_ransac=c['after_matching'])
+        d.update(before_tracking=c['before_tracking'], after_tracking=c['after_tracking'], after_matching=c['after_matching'],
+                 after_ransac=self._engine.read_ransac_counts(0)['after_ransac'] if ransac else c['after_matching'])
         return d
 
     def close(self):

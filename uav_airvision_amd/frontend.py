@@ -55,11 +55,19 @@ def pack_frontend_config(config, max_corners=8192):
     c.R0to1[:] = [float(v) for v in R0to1.reshape(-1)]
     c.E[:] = [float(v) for v in E.reshape(-1)]
     c.norm_unit = float(4.0 / (2 * config.cam0_intrinsics[0] + 2 * config.cam0_intrinsics[1]))
+    # two-point RANSAC on the tracked features (AV_FE_RANSAC); getattr: the reference's own config object has no such switch
+    c.ransac_threshold = float(getattr(config, 'ransac_threshold', 3))
+    c.ransac_success_probability = float(getattr(config, 'ransac_success_probability', 0.99))
+    c.ransac_seed = int(getattr(config, 'ransac_seed', 0)) & 0xFFFFFFFF
+    c.flags = N.AV_FE_RANSAC if getattr(config, 'use_ransac', False) else 0
     return c
 
 
 COUNTER_NAMES = ('before_tracking', 'after_tracking', 'after_matching', 'n_fast', 'n_candidates', 'n_new',
                  'n_published', 'overflow')
+
+
+RANSAC_COUNT_NAMES = ('after_ransac', 'cam0_set', 'cam1_set', 'path')
 
 
 class FrontendEngine(object):
@@ -72,7 +80,7 @@ class FrontendEngine(object):
         self.n_streams = int(n_streams)
         self.device = int(device)
         self._cfg = pack_frontend_config(config, max_corners)
-        self._cfg.flags = N.AV_FE_INPUTS_PERSIST if inputs_persist else 0
+        self._cfg.flags |= N.AV_FE_INPUTS_PERSIST if inputs_persist else 0
         self._keep = None
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -236,6 +244,14 @@ class FrontendEngine(object):
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_match_counts(self._h, int(stream), C.byref(out), self._stream()))
         return int(out[0]), int(out[1])
+
+    def read_ransac_counts(self, stream=0):
+        """Outlier rejection of the last step (config.use_ransac): dict(after_ransac, cam0_set, cam1_set, path) with path = cam0
+        code | cam1 code << 4 of the AV_RANSAC_PATH_* codes; zeros when the switch is off or nothing was tracked."""
+        out = (C.c_int32 * 4)()
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_read_ransac_counts(self._h, int(stream), C.byref(out), self._stream()))
+        return dict(zip(RANSAC_COUNT_NAMES, [int(v) for v in out]))
 
     def enable_timing(self, max_spans):
         """Bracket every launch group with HIP events on the step's stream (bench roofline leg)."""

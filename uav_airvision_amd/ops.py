@@ -136,3 +136,61 @@ def distort_points(pts_in, intrinsics, distortion_coeffs, device=0, distortion_m
     camera_model.py:49-75)."""
     extra = (N.darr(intrinsics), N.darr(distortion_coeffs), N.distortion_model_code(distortion_model))
     return _points_op('av_distort_points_model', pts_in, extra, device)
+
+
+def ransac_num_hypotheses(success_probability=0.99):
+    """Hypotheses the two-point RANSAC draws for a success probability (av_ransac_num_hypotheses): 7 at 0.99."""
+    return int(N.lib().av_ransac_num_hypotheses(float(success_probability)))
+
+
+def ransac_hash(seed, frame, camera, k, draw):
+    """The draw hash of the two-point RANSAC (include/airvision.h writes it out)."""
+    return int(N.lib().av_ransac_hash(int(seed) & 0xFFFFFFFF, int(frame) & 0xFFFFFFFF, int(camera), int(k), int(draw)))
+
+
+def two_point_ransac_batch(pts1, pts2, R_p_c, intrinsics, distortion_model, distortion_coeffs, inlier_error, success_probability=0.99,
+                           seed=0, frames=None, cameras=None, device=0):
+    """B problems of one camera model in one launch (av_two_point_ransac): pts1 / pts2 lists of float32[n_b, 2], R_p_c [B, 3, 3],
+    frames / cameras int[B] (default 0).  Returns (markers: list of uint8[n_b], info int32[B, 2] = markers set, path code)."""
+    B = len(pts1)
+    assert len(pts2) == B
+    p1 = [np.asarray(p, dtype=np.float32).reshape(-1, 2) for p in pts1]
+    p2 = [np.asarray(p, dtype=np.float32).reshape(-1, 2) for p in pts2]
+    sizes = [len(p) for p in p1]
+    assert sizes == [len(p) for p in p2], 'pts1 and pts2 must pair up'
+    if B == 0:
+        return [], np.zeros((0, 2), np.int32)
+    off = np.zeros(B + 1, np.int32)
+    off[1:] = np.cumsum(sizes)
+    total, max_pairs = int(off[-1]), max(sizes)
+    if max_pairs > N.AV_RANSAC_MAX_PAIRS:
+        raise ValueError('two_point_ransac: %d pairs in one problem, at most %d' % (max_pairs, N.AV_RANSAC_MAX_PAIRS))
+    dev = _dev(device)
+    cat = lambda ps: np.ascontiguousarray(np.concatenate(ps, axis=0)) if total else np.zeros((1, 2), np.float32)      # noqa: E731
+    d1 = torch.from_numpy(cat(p1)).to(dev)
+    d2 = torch.from_numpy(cat(p2)).to(dev)
+    d_off = torch.from_numpy(off).to(dev)
+    d_R = torch.from_numpy(np.ascontiguousarray(np.asarray(R_p_c, dtype=np.float64).reshape(B, 9))).to(dev)
+    d_fr = torch.from_numpy(np.ascontiguousarray(np.zeros(B) if frames is None else frames, dtype=np.int64).astype(np.uint32).view(np.int32)).to(dev)
+    d_cam = torch.from_numpy(np.ascontiguousarray(np.zeros(B) if cameras is None else cameras, dtype=np.int32)).to(dev)
+    d_mark = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+    d_info = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(device):
+        N.check(N.lib().av_two_point_ransac(N.dptr(d1), N.dptr(d2), N.dptr(d_off), B, max_pairs, N.dptr(d_R), N.dptr(d_cam), N.dptr(d_fr),
+                                            N.darr(intrinsics), N.darr(distortion_coeffs), N.distortion_model_code(distortion_model),
+                                            float(inlier_error), float(success_probability), int(seed) & 0xFFFFFFFF,
+                                            N.dptr(d_mark), N.dptr(d_info), N.current_stream()))
+        torch.cuda.synchronize()
+    mark = d_mark.cpu().numpy()
+    return [mark[off[b]:off[b + 1]].copy() for b in range(B)], d_info.cpu().numpy()
+
+
+def two_point_ransac(pts1, pts2, R_p_c, intrinsics, distortion_model, distortion_coeffs, inlier_error, success_probability=0.99,
+                     seed=0, frame=0, camera=0, device=0):
+    """Two-point RANSAC on the temporal matches of one camera: pts1 / pts2 float32[n, 2] pixel positions of the same features in the
+    previous / current image, R_p_c the rotation previous -> current camera frame (IMUProcessor.integrate_imu_data), inlier_error in
+    pixels (config.ransac_threshold).  Returns uint8[n] markers.  This is the step feature_tracker.py:135-136 leaves empty; the
+    algorithm is written out in include/airvision.h."""
+    marks, _info = two_point_ransac_batch([pts1], [pts2], [R_p_c], intrinsics, distortion_model, distortion_coeffs, inlier_error,
+                                          success_probability, seed, [frame], [camera], device)
+    return marks[0]

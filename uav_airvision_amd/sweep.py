@@ -248,6 +248,8 @@ def main(argv=None):
     ap.add_argument('--grid', nargs=3, type=int, default=None, metavar=('ROWS', 'COLS', 'MAX'), help='feature grid (default 4 5 5; 10 15 10 = the 1500-feature sweep)')
     ap.add_argument('--out', default='results/txts')
     ap.add_argument('--no-share-frames', action='store_true', help="round 4's per-stream staging instead of the shared frame store (A/B)")
+    ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
+    ap.add_argument('--ransac-threshold', type=float, default=None, metavar='T', help='inlier error in pixels (config.ransac_threshold, default 3)')
     args = ap.parse_args(argv)
 
     import torch
@@ -263,6 +265,9 @@ def main(argv=None):
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     cfg = ConfigEuRoC(grid_row=args.grid[0], grid_col=args.grid[1], grid_max_feature_num=args.grid[2]) if args.grid else ConfigEuRoC()
+    cfg.use_ransac = bool(args.ransac)
+    if args.ransac_threshold is not None:
+        cfg.ransac_threshold = args.ransac_threshold
     root = args.root
     if args.make_synthetic:
         root = args.make_synthetic

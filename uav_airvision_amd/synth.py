@@ -88,7 +88,13 @@ class SyntheticStream(object):
     """
 
     def __init__(self, config, seed=0, n_frames=20, t0=100.0, lead_in=1.0, motion_scale=1.0,
-                 pixel_noise=1.0, texture=None, render=True, rest=0.0, tex_offset=(0.0, 0.0)):
+                 pixel_noise=1.0, texture=None, render=True, rest=0.0, tex_offset=(0.0, 0.0),
+                 moving_region=None, moving_amplitude=0.15, moving_rate=1.5):
+        """moving_region = (x0, y0, x1, y1) in pixels (default none: the renders are what they always were): inside that rectangle of
+        BOTH images the scene is rendered from the rig's pose shifted by `region_offset(t)`, a rigid offset that swings with
+        moving_amplitude metres at moving_rate Hz.  The rectangle therefore shows a stereo-consistent scene (it passes the stereo
+        gates) that moves against the ego-motion from frame to frame: an independently moving object, the case the tracker's
+        outlier rejection (config.use_ransac) is for."""
         self.config = config
         self.seed = int(seed)
         self.n_frames = int(n_frames)
@@ -98,6 +104,8 @@ class SyntheticStream(object):
         self.motion_scale = float(motion_scale)
         self.tex_offset = (float(tex_offset[0]), float(tex_offset[1]))      # texels: which part of the (wrapping) texture the wall shows
         self.pixel_noise = float(pixel_noise)
+        self.moving_region = None if moving_region is None else tuple(int(v) for v in moving_region)
+        self.moving_amplitude, self.moving_rate = float(moving_amplitude), float(moving_rate)
         self.rng = np.random.default_rng(0xA1B0 + self.seed)
         self.tex = (make_texture(0xA1B0 + self.seed) if texture is None else texture) if render else None
 
@@ -178,12 +186,29 @@ class SyntheticStream(object):
         R_i_w, p = self.R_i_w(t), self.position(t)
         return R_i_w @ self.T_c0_i[:3, :3], p + R_i_w @ self.T_c0_i[:3, 3]
 
+    def region_offset(self, t):
+        """World-frame offset of the rig's pose as the moving region sees it at time t (zero at frame 0)."""
+        ph = 2.0 * np.pi * self.moving_rate * (t - self.t0)
+        return self.moving_amplitude * np.array([0.0, np.sin(ph), 0.5 * np.sin(ph + 1.0) - 0.5 * np.sin(1.0)])
+
+    def in_moving_region(self, x, y):
+        if self.moving_region is None:
+            return False
+        x0, y0, x1, y1 = self.moving_region
+        return x0 <= x < x1 and y0 <= y < y1
+
     def frame(self, k):
         t = self.frame_time(k)
         R_i_w, p = self.R_i_w(t), self.position(t)
         nrng = np.random.default_rng((0xA1B0 + self.seed) * 100003 + k)
         img0 = self._render(self.rays0, R_i_w @ self.T_c0_i[:3, :3], p + R_i_w @ self.T_c0_i[:3, 3], nrng)
         img1 = self._render(self.rays1, R_i_w @ self.T_c1_i[:3, :3], p + R_i_w @ self.T_c1_i[:3, 3], nrng)
+        if self.moving_region is not None:
+            x0, y0, x1, y1 = self.moving_region
+            q = p + self.region_offset(t)
+            mrng = np.random.default_rng((0xA1B0 + self.seed) * 100003 + 50021 + k)      # own noise: the frame's generator stays as it was
+            img0[y0:y1, x0:x1] = self._render(self.rays0, R_i_w @ self.T_c0_i[:3, :3], q + R_i_w @ self.T_c0_i[:3, 3], mrng)[y0:y1, x0:x1]
+            img1[y0:y1, x0:x1] = self._render(self.rays1, R_i_w @ self.T_c1_i[:3, :3], q + R_i_w @ self.T_c1_i[:3, 3], mrng)[y0:y1, x0:x1]
         m0, m1 = img_msg_t(t, img0), img_msg_t(t, img1)
         return stereo_msg_t(t, img0, img1, m0, m1)
 
