@@ -147,6 +147,8 @@ typedef struct av_frontend_config {
     double  ransac_success_probability;      /* config.ransac_success_probability, 0 < p < 1 (0.99)  */
     uint32_t ransac_seed;                    /* config.ransac_seed: first word of the draw hash      */
     int32_t reserved0;                       /* keeps the size a multiple of 8; must be 0            */
+    double  clahe_clip_limit;                /* config.clahe_clip_limit (2.0); the three are read only with AV_FE_CLAHE */
+    int32_t clahe_tiles_x, clahe_tiles_y;    /* config.clahe_tiles (8, 8); 1 .. AV_CLAHE_MAX_TILES    */
 } av_frontend_config;
 
 typedef struct av_frontend av_frontend;
@@ -175,6 +177,19 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * imu_processor.py:28-67) both mark it; a rejected feature is absent from the published message and from the FAST mask.  Without
  * the flag the step enqueues exactly what it always did.  Needs grid_num * grid_max <= AV_RANSAC_MAX_PAIRS. */
 #define AV_FE_RANSAC 2
+/* AV_FE_CLAHE: every frame of both cameras goes through av_clahe (below; clahe_clip_limit, clahe_tiles_x / _y of the configuration)
+ * before anything reads it: pyramids, LK and FAST see equalised pixels only, and the published message is that of the unmodified
+ * pipeline run on equalised frames.  No counterpart in the reference (pipeline.py:46-150 works on the camera's own pixels).  The
+ * caller's images are never written: the engine owns the equalised level 0 -- [3][n_streams][width * height], cam0 of alternating
+ * frames and cam1, like the pyramid slots -- and past the stage runs as if those were persisting inputs: level 0 is read in place,
+ * only levels 1.. are built.  That holds for av_frontend_step with and without AV_FE_INPUTS_PERSIST, for av_frontend_prestage (the
+ * stage runs there, and the step that follows with the same pointers skips both), and for av_frontend_step_host (the stage reads the
+ * staging slot).  In the shared frame store av_frontend_frames_upload equalises every entry once, in place in the store, on the copy
+ * stream, before the entry's pyramids and FAST pass (one upload must then not name an entry twice: AV_E_INVALID);
+ * av_frontend_step_frames is what it was.  The stage's launches count under class 0
+ * (pyramid) of av_frontend_enable_timing.  Without the flag the step enqueues exactly what it always did and nothing more is
+ * allocated. */
+#define AV_FE_CLAHE 4
 
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
@@ -261,6 +276,43 @@ int av_frontend_read_match_counts(av_frontend* fe, int stream_idx, int32_t out[2
  * AV_FE_RANSAC (zeros otherwise, and on a step that tracked nothing).  path bits = cam0 path | cam1 path << 4 with the
  * AV_RANSAC_PATH_* codes below.  Synchronises. */
 int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, int32_t out[4], void* stream);
+
+/* The level-0 image the last step used for camera `cam` (0 / 1) of one stream of an engine created with AV_FE_CLAHE, i.e. the
+ * equalised frame: width * height bytes into out_host.  AV_E_INVALID without the flag (level 0 is then the caller's own image),
+ * before the first step, and for a stream whose av_frontend_step_frames entries were negative from the start.  The image comes from where
+ * the LAST step read it: the frame store after av_frontend_step_frames, the engine's own buffer after the other steps.  Between an
+ * av_frontend_prestage and the step it serves the cam1 image of the last step is gone (its slot holds the next frame's): cam 1 is then
+ * refused, AV_E_INVALID; cam 0 is still the last step's.  Synchronises. */
+int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* out_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Contrast-limited adaptive histogram equalisation of n_img 8-bit images (tightly packed w * h, image i at img_dev + i * img_stride,
+ * result at out_dev + i * out_stride; out_dev == img_dev with equal strides works in place).  No counterpart in the reference; the
+ * definition restates cv::CLAHE::apply of OpenCV 4.x for 8-bit input.  Its parity with cv2 is unpinned (there is no cv2 to check
+ * against), so this text is the contract.  One difference is known: OpenCV pads both axes as soon as one of them is ragged, here
+ * each axis is padded only if it is ragged itself.
+ *   Geometry.  w % tiles_x != 0: the image is extended on the right by tiles_x - w % tiles_x columns, BORDER_REFLECT_101; the same at
+ *     the bottom with tiles_y.  tw, th = padded size / tiles; area = tw * th.
+ *   Look-up table of a tile.
+ *     1. hist = 256-bin histogram of the tile's pixels of the padded image
+ *     2. clip_limit > 0: clip = max(1, (int)(clip_limit * area / 256)), the product in double;
+ *        clipped = sum over bins of max(hist - clip, 0), those bins are set to clip;
+ *        batch = clipped / 256, residual = clipped - 256 batch; every bin gets + batch;
+ *        residual != 0: step = max(256 / residual, 1); bins 0, step, 2 step, .. get + 1 while residual-- > 0 and the index is < 256
+ *     3. scale = 255.0f / area (float32)
+ *     4. lut[i] = saturate_u8(round_half_even((float)(hist[0] + .. + hist[i]) * scale))
+ *   Interpolation.  Pixel (x, y) of the unpadded image with value v:
+ *     txf = x * (1.0f / tw) - 0.5f; tx1 = floor(txf); tx2 = tx1 + 1; xa = txf - tx1; xa1 = 1.0f - xa; then tx1 = max(tx1, 0),
+ *     tx2 = min(tx2, tiles_x - 1); ty1, ty2, ya, ya1 the same from y and th;
+ *     res = (lut[ty1][tx1][v] * xa1 + lut[ty1][tx2][v] * xa) * ya1 + (lut[ty2][tx1][v] * xa1 + lut[ty2][tx2][v] * xa) * ya
+ *     in float32, in exactly this order, without fused multiply-add; out = saturate_u8(round_half_even(res)).
+ * Limits: 1 <= tiles_x, tiles_y <= AV_CLAHE_MAX_TILES, clip_limit >= 0 (0 = no clipping), w * h <= 2^19 (as for FAST); anything else
+ * is AV_E_INVALID with text.  lut_dev (optional): the tables, uint8 [n_img][tiles_y * tiles_x][256], 16-byte aligned (the images may lie
+ * at any address and stride: unaligned ones are read and written byte by byte).
+ * ------------------------------------------------------------------------------------------- */
+#define AV_CLAHE_MAX_TILES 16
+int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h, double clip_limit, int tiles_x, int tiles_y,
+             uint8_t* out_dev, int64_t out_stride, uint8_t* lut_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Two-point RANSAC on the temporal matches of ONE camera (no counterpart in the reference: feature_tracker.py:135-136 is where

@@ -17,6 +17,8 @@ AV_PYR_BORDER = 16
 AV_OK, AV_E_INVALID, AV_E_HIP, AV_E_CAPACITY, AV_E_NODEVICE, AV_E_NUMERIC = 0, -1, -2, -3, -4, -5
 AV_FE_INPUTS_PERSIST = 1
 AV_FE_RANSAC = 2
+AV_FE_CLAHE = 4
+AV_CLAHE_MAX_TILES = 16
 AV_RANSAC_MAX_PAIRS = 1920
 AV_RANSAC_MAX_HYPOTHESES = 64
 AV_RANSAC_PATH_FEW, AV_RANSAC_PATH_STILL, AV_RANSAC_PATH_MODEL, AV_RANSAC_PATH_NONE = 1, 2, 4, 8
@@ -57,7 +59,8 @@ class FrontendConfig(C.Structure):
                 ('R0to1', C.c_double * 9), ('E', C.c_double * 9), ('norm_unit', C.c_double),
                 ('cam0_distortion_model', C.c_int32), ('cam1_distortion_model', C.c_int32),
                 ('ransac_threshold', C.c_double), ('ransac_success_probability', C.c_double),
-                ('ransac_seed', C.c_uint32), ('reserved0', C.c_int32)]
+                ('ransac_seed', C.c_uint32), ('reserved0', C.c_int32),
+                ('clahe_clip_limit', C.c_double), ('clahe_tiles_x', C.c_int32), ('clahe_tiles_y', C.c_int32)]
 
 
 # name -> (restype, argtypes); the list doubles as the export check of tests/test_abi.py
@@ -134,6 +137,8 @@ SIGNATURES = {
     'av_ransac_num_hypotheses': (C.c_int, [C.c_double]),
     'av_two_point_ransac': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
                                       C.c_double, C.c_double, C.c_uint32, _P, _P, _P]),
+    'av_frontend_read_image': (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    'av_clahe': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     'av_frontend_enable_timing': (C.c_int, [_P, C.c_int]),
     'av_frontend_read_timing': (C.c_int, [_P, C.POINTER(C.c_double * 4), C.POINTER(C.c_int32 * 4)]),
 }

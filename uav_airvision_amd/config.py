@@ -44,6 +44,12 @@ class ConfigEuRoC(object):
         self.use_ransac = False
         self.ransac_success_probability = 0.99
         self.ransac_seed = 0
+        # contrast-limited adaptive histogram equalisation of every frame ahead of the pyramids, LK and FAST (no counterpart in the
+        # reference; av_clahe in include/airvision.h).  Off by default: with it off the front-end is the reference's, bit for bit.
+        # fast_threshold and the LK thresholds are not retuned for equalised images.
+        self.use_clahe = False
+        self.clahe_clip_limit = 2.0
+        self.clahe_tiles = (8, 8)       # (tiles_x, tiles_y)
         self.stereo_threshold = 5
         self.max_iteration = 30
         self.track_precision = 0.01

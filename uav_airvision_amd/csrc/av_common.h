@@ -219,3 +219,11 @@ struct RansacStage {
     double thr; int N; uint32_t seed;
 };
 int av_launch_ransac_stage(const RansacStage& a, hipStream_t st);
+
+// clahe.hip: equalise n_groups images of one camera (src1 / dst1 null) or of two (image pairs: camera c of group g at
+// src_c + e * src_stride with e = index ? index[g] : g).  dst may be src.  lut: [n_groups * cameras][tiles_y * tiles_x][256] scratch
+// (the look-up tables of the launch, camera-minor).  av_clahe_check: the argument limits of av_clahe, with `who` in the text.
+int av_clahe_check(int w, int h, double clip_limit, int tiles_x, int tiles_y, const char* who);
+int av_launch_clahe(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
+                    int n_groups, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* lut, hipStream_t st,
+                    const int* index = nullptr);

@@ -666,6 +666,10 @@ struct av_frontend {
     std::vector<hipEvent_t> ev; std::vector<int> ev_cls; size_t ev_used = 0;
     // AV_FE_RANSAC: the stage's arguments; Rpc / frame_no are uploaded with the homographies, behind them in the same staging slot
     bool ransac = false; RansacStage rs; int* rs_counts = nullptr;
+    // AV_FE_CLAHE: the equalised level 0 of every frame, [3][S][w * h] laid out like the pyramid slots (0 / 1: cam0 of alternating
+    // frames, 2: cam1), and the look-up tables of one launch [2 S][tiles][256]; the frame store keeps tables of its own (fs_lut)
+    bool clahe = false; uint8_t* eq = nullptr; uint8_t* eq_lut = nullptr; uint8_t* fs_lut = nullptr;
+    bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
     explicit av_frontend(int S) : streams(S) {}
 };
@@ -749,6 +753,19 @@ struct Span {
     }
 };
 
+// AV_FE_CLAHE: both cameras' images of every stream -> the engine's equalised level 0 (slots cur0 and 2), then levels 1.. from there
+int clahe_and_pyramids(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int cur0, hipStream_t st, bool* wrote_l0)
+{
+    const int S = fe->d.S;
+    const int64_t hw = (int64_t)fe->d.w * fe->d.h;
+    uint8_t* e0 = fe->eq + (size_t)cur0 * S * hw; uint8_t* e1 = fe->eq + (size_t)2 * S * hw;
+    const av_frontend_config& c = fe->cfg;
+    Span sp(fe, 0, st);
+    int rc = av_launch_clahe(img0, img1, img_stride, e0, e1, hw, S, fe->d.w, fe->d.h, c.clahe_clip_limit, c.clahe_tiles_x, c.clahe_tiles_y, fe->eq_lut, st);
+    if (rc) return rc;
+    return av_launch_pyramid(e0, e1, hw, S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur0, 2, st, false, wrote_l0);
+}
+
 // slots != nullptr: the step reads the shared frame store (stream s: entry slots[s], < 0 = no frame in this step); img0 / img1 unused.
 int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t img_stride, const double* ts, hipStream_t st, bool inputs_persist,
               const int32_t* slots = nullptr)
@@ -815,9 +832,14 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     } else {
         bool wrote_l0 = true;
         if (fe->pre_on && fe->pre_img0 == img0 && fe->pre_img1 == img1 && fe->pre_stride == img_stride) wrote_l0 = fe->pre_wrote_l0;      // built by av_frontend_prestage
+        else if (fe->clahe) { if ((rc = clahe_and_pyramids(fe, img0, img1, img_stride, cur0, st, &wrote_l0))) return rc; }
         else { Span sp(fe, 0, st);
           if ((rc = av_launch_pyramid(img0, img1, img_stride, S, 2, fe->geom, fe->pyr, sstride, slotb, cur0, 2, st, !inputs_persist, &wrote_l0))) return rc; }
         fe->pre_on = false;
+        if (fe->clahe) {                   // from here on the equalised images are the step's inputs, and they persist
+            const int64_t hw = (int64_t)d.w * d.h;
+            img0 = fe->eq + (size_t)cur0 * S * hw; img1 = fe->eq + (size_t)2 * S * hw; img_stride = hw;
+        }
         fe->l0_img[cur0] = wrote_l0 ? nullptr : img0; fe->l0_img[2] = wrote_l0 ? nullptr : img1;
         fe->l0_stride[cur0] = fe->l0_stride[2] = img_stride;
         I_prev0 = fe->l0_img[par]; st_prev0 = fe->l0_stride[par];      // (first frame: nothing is tracked from it)
@@ -888,6 +910,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
       hipLaunchKernelGGL(finalize_kernel, dim3(S), dim3(256), fin_lds, st, d, par);
       AV_LAUNCH_CHECK(); }
     fe->parity = par ^ 1;
+    fe->stepped = true; fe->stepped_frames = frames;
     if (frames) { AV_HIP(hipEventRecord(fe->fs.stepped, st)); fe->fs.any_step = true; }
     return AV_OK;
 }
@@ -925,6 +948,8 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
                      AV_RANSAC_MAX_PAIRS, C * cfg->grid_max_feature_num, cfg->ransac_success_probability, cfg->ransac_threshold);
         delete fe; return AV_E_INVALID;
     }
+    const bool clahe = (cfg->flags & AV_FE_CLAHE) != 0;
+    if (clahe && av_clahe_check(cfg->width, cfg->height, cfg->clahe_clip_limit, cfg->clahe_tiles_x, cfg->clahe_tiles_y, "av_frontend_create")) { delete fe; return AV_E_INVALID; }
     if (fe->lk.win < 3 || fe->lk.win > 31) { av_set_error("av_frontend_create: lk_win %d outside 3 .. 31", fe->lk.win); delete fe; return AV_E_INVALID; }      // 15: the 16-lane kernel; others: the general one
 
     FeDev& d = fe->d;
@@ -990,6 +1015,10 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         a.Rpc = fe->dH + (size_t)10 * S; a.frame_no = reinterpret_cast<const int*>(fe->dH + (size_t)28 * S);
         a.thr = cfg->ransac_threshold; a.N = rs_N; a.seed = cfg->ransac_seed;
         fe->ransac = true;
+    }
+    if (clahe) {
+        A(fe->eq, (size_t)3 * S * w * h) A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
+        fe->clahe = true;
     }
 #undef A
     for (int i = 0; i < 8; ++i) {
@@ -1088,7 +1117,8 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
     const int cur0 = fe->parity ^ 1;         // the slots the next step will call cur0 / 2
     int rc;
     bool wrote_l0 = true;
-    { Span sp(fe, 0, st);
+    if (fe->clahe) { if ((rc = clahe_and_pyramids(fe, img0_dev, img1_dev, img_stride, cur0, st, &wrote_l0))) return rc; }
+    else { Span sp(fe, 0, st);
       if ((rc = av_launch_pyramid(img0_dev, img1_dev, img_stride, fe->d.S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur0, 2, st, false, &wrote_l0))) return rc; }
     // (The detector's pass over the new cam0 image -- it reads nothing but the image -- enqueued here as well ran at its exclusive speed,
     //  1.55 ms against 2.3 beside the filter's back end, and the LK launches took what it gave back: 173.4-173.9 against 174.1-175.2 k
@@ -1165,6 +1195,7 @@ AV_EXPORT int av_frontend_frames_reserve(av_frontend* fe, int n_slots)
     int rc;
     if ((rc = dev_alloc(fe, &fs.img, (size_t)n_slots * 2 * hw)) || (rc = dev_alloc(fe, &fs.pyr, (size_t)n_slots * 2 * fe->lay.bytes)) ||
         (rc = dev_alloc(fe, &fs.tile_kp, (size_t)n_slots * d.n_tiles * d.tile_cap)) || (rc = dev_alloc(fe, &fs.tile_count, (size_t)n_slots * d.n_tiles))) return rc;
+    if (fe->clahe && (rc = dev_alloc(fe, &fe->fs_lut, (size_t)n_slots * 2 * fe->cfg.clahe_tiles_x * fe->cfg.clahe_tiles_y * 256))) return rc;
     AV_HIP(hipEventCreateWithFlags(&fs.uploaded, hipEventDisableTiming));
     AV_HIP(hipEventCreateWithFlags(&fs.stepped, hipEventDisableTiming));
     if (!fe->copy_stream) AV_HIP(hipStreamCreateWithFlags(&fe->copy_stream, hipStreamNonBlocking));
@@ -1186,6 +1217,13 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     if (n == 0) return AV_OK;
     for (int i = 0; i < n; ++i)
         if (slots[i] < 0 || slots[i] >= fs.n_slots) { av_set_error("av_frontend_frames_upload: entry %d outside the store (%d entries)", slots[i], fs.n_slots); return AV_E_INVALID; }
+    if (fe->clahe) {                 // the entries are equalised where they lie: one named twice would be equalised twice, or half
+        std::vector<char> seen((size_t)fs.n_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            if (seen[slots[i]]) { av_set_error("av_frontend_frames_upload: entry %d is named twice in one upload (not allowed with AV_FE_CLAHE)", slots[i]); return AV_E_INVALID; }
+            seen[slots[i]] = 1;
+        }
+    }
     AV_HIP(hipSetDevice(fe->device));
     const FeDev& d = fe->d;
     const size_t hw = (size_t)d.w * d.h;
@@ -1220,6 +1258,9 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     }
     int rc;
     bool wrote_l0 = true;
+    // AV_FE_CLAHE: the entries are equalised once, where they lie, before anything reads them (the tables by position in this upload)
+    if (fe->clahe && (rc = av_launch_clahe(fs.img, fs.img + hw, (int64_t)(2 * hw), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->cfg.clahe_clip_limit,
+                                           fe->cfg.clahe_tiles_x, fe->cfg.clahe_tiles_y, fe->fs_lut, cs, u.idx_d))) return rc;
     if ((rc = av_launch_pyramid(fs.img, fs.img + hw, (int64_t)(2 * hw), n, 2, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0, u.idx_d))) return rc;
     fs.l0_in_place = !wrote_l0;
     if (fs.l0_in_place) rc = av_launch_fast(fs.img, (int64_t)(2 * hw), d.w, 0, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold,
@@ -1364,6 +1405,31 @@ AV_EXPORT int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, in
     AV_HIP(hipSetDevice(fe->device));
     AV_HIP(hipStreamSynchronize((hipStream_t)stream));
     AV_HIP(hipMemcpy(out, fe->rs_counts + (size_t)stream_idx * 4, sizeof(int) * 4, hipMemcpyDeviceToHost));
+    return AV_OK;
+}
+
+AV_EXPORT int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* out_host, void* stream)
+{
+    if (!fe || stream_idx < 0 || stream_idx >= fe->d.S || cam < 0 || cam > 1 || !out_host) { av_set_error("av_frontend_read_image: bad arguments"); return AV_E_INVALID; }
+    if (!fe->clahe) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE: level 0 is the caller's own image"); return AV_E_INVALID; }
+    if (!fe->stepped) { av_set_error("av_frontend_read_image: no step has run yet"); return AV_E_INVALID; }
+    if (cam == 1 && fe->pre_on && !fe->stepped_frames) {
+        av_set_error("av_frontend_read_image: the cam1 image of the last step has been replaced by av_frontend_prestage (read it before prestaging)");
+        return AV_E_INVALID;
+    }
+    const size_t hw = (size_t)fe->d.w * fe->d.h;
+    const uint8_t* src;
+    if (fe->stepped_frames) {                        // the last step read the frame store
+        const int e = fe->fs.prev[stream_idx];
+        if (e < 0) { av_set_error("av_frontend_read_image: stream %d has not had a frame yet", stream_idx); return AV_E_INVALID; }
+        src = fe->fs.img + ((size_t)2 * e + cam) * hw;
+    } else {
+        src = fe->eq + ((size_t)(cam ? 2 : fe->parity) * fe->d.S + stream_idx) * hw;      // after a step, parity is the slot of the frame just used
+    }
+    AV_HIP(hipSetDevice(fe->device));
+    AV_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (fe->copy_stream) AV_HIP(hipStreamSynchronize(fe->copy_stream));
+    AV_HIP(hipMemcpy(out_host, src, hw, hipMemcpyDeviceToHost));
     return AV_OK;
 }
 

@@ -6,6 +6,7 @@ These are the host-list "plugin" flavour of the stages: Python lists of FeatureM
 every OpenCV call replaced by a HIP operator (uav_airvision_amd/ops.py).  The throughput path
 (ImageProcessingPipeline / FrontendEngine) runs the same semantics device-resident; both are bit-identical to
 the CPU oracle (tests/test_gpu_stages.py)."""
+import warnings
 from collections import namedtuple
 from itertools import chain
 
@@ -40,12 +41,22 @@ def FastFeatureDetector_create(threshold):
     return _FastDetector(threshold)
 
 
+def _warn_if_clahe(config, who):
+    """config.use_clahe is honoured by the engine (ImageProcessingPipeline / FrontendEngine).  The stage classes work on the images
+    of the messages they are handed and do not equalise them: say so instead of silently running on raw pixels."""
+    if getattr(config, 'use_clahe', False):
+        warnings.warn('%s: config.use_clahe is set, but the stage-wise classes do not equalise: they work on the images of the '
+                      'messages as given.  Hand them messages whose images went through ops.clahe, or use ImageProcessingPipeline.' % who,
+                      RuntimeWarning, stacklevel=3)
+
+
 class FeatureInitializer(object):
     def __init__(self, detector, stereo_matcher, config, cam0_curr_img_msg, curr_features, next_feature_id,
                  grid_row, grid_col, grid_min_feature_num):
         self.detector = detector
         self.stereo_match = stereo_matcher.stereo_match
         self.config = config
+        _warn_if_clahe(config, 'FeatureInitializer')
         self.cam0_curr_img_msg = cam0_curr_img_msg
         self.curr_features = curr_features
         self.next_feature_id = next_feature_id
@@ -150,6 +161,7 @@ class FeatureAdder(object):
         self.stereo_matcher = stereo_matcher
         self.stereo_match = stereo_matcher.stereo_match
         self.config = config
+        _warn_if_clahe(config, 'FeatureAdder')
         self.cam0_curr_img_msg = cam0_curr_img_msg
         self.curr_features = curr_features
         self.next_feature_id = next_feature_id

@@ -24,6 +24,10 @@ class ImageProcessingPipeline(object):
         self.first_frame = True
         self.prev_pyr0 = None
         self.curr_features = [[] for _ in range(config.grid_num)]
+        # config.use_clahe (no counterpart in the reference): the engine equalises every frame ahead of everything else; a viewer set
+        # here is shown the image the front-end actually worked on (update_image, the hook of viewer.py:45-49)
+        self.use_clahe = bool(getattr(config, 'use_clahe', False))
+        self.viewer = None
 
     # ---- reference callbacks -----------------------------------------------------------------
     def imu_callback(self, imu_msg):
@@ -48,6 +52,8 @@ class ImageProcessingPipeline(object):
         self.prev_cam0_msg = cam0_msg
         self.prev_pyr0 = cam0_msg.image
         self.first_frame = False
+        if self.use_clahe and self.viewer is not None:
+            self.viewer.update_image(self.equalized_image(0))
         return _feature_msg(cam0_msg.timestamp, feats)
 
     # ---- pipeline state visible to callers (pipeline.py:33-40,145-148) -----------------------
@@ -76,6 +82,10 @@ class ImageProcessingPipeline(object):
         d.update(before_tracking=c['before_tracking'], after_tracking=c['after_tracking'], after_matching=c['after_matching'],
                  after_ransac=self._engine.read_ransac_counts(0)['after_ransac'] if ransac else c['after_matching'])
         return d
+
+    def equalized_image(self, cam=0):
+        """The equalised frame of camera `cam` the last stereo_callback worked on (config.use_clahe); refused without the switch."""
+        return self._engine.read_image(0, cam)
 
     def close(self):
         self._engine.close()

@@ -60,6 +60,11 @@ def pack_frontend_config(config, max_corners=8192):
     c.ransac_success_probability = float(getattr(config, 'ransac_success_probability', 0.99))
     c.ransac_seed = int(getattr(config, 'ransac_seed', 0)) & 0xFFFFFFFF
     c.flags = N.AV_FE_RANSAC if getattr(config, 'use_ransac', False) else 0
+    # CLAHE ahead of everything that reads a frame (AV_FE_CLAHE); the fields are carried either way, read only with the flag
+    c.clahe_clip_limit = float(getattr(config, 'clahe_clip_limit', 2.0))
+    c.clahe_tiles_x, c.clahe_tiles_y = [int(v) for v in getattr(config, 'clahe_tiles', (8, 8))]
+    if getattr(config, 'use_clahe', False):
+        c.flags |= N.AV_FE_CLAHE
     return c
 
 
@@ -252,6 +257,14 @@ class FrontendEngine(object):
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_ransac_counts(self._h, int(stream), C.byref(out), self._stream()))
         return dict(zip(RANSAC_COUNT_NAMES, [int(v) for v in out]))
+
+    def read_image(self, stream=0, cam=0):
+        """The level-0 image the last step used for camera `cam` of `stream` (config.use_clahe: the equalised frame), uint8[h, w].
+        Refused (AirvisionError, AV_E_INVALID) when the switch is off: level 0 is then the caller's own image."""
+        out = np.empty((self.height, self.width), np.uint8)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_read_image(self._h, int(stream), int(cam), out.ctypes.data_as(C.c_void_p), self._stream()))
+        return out
 
     def enable_timing(self, max_spans):
         """Bracket every launch group with HIP events on the step's stream (bench roofline leg)."""

@@ -194,3 +194,27 @@ def two_point_ransac(pts1, pts2, R_p_c, intrinsics, distortion_model, distortion
     marks, _info = two_point_ransac_batch([pts1], [pts2], [R_p_c], intrinsics, distortion_model, distortion_coeffs, inlier_error,
                                           success_probability, seed, [frame], [camera], device)
     return marks[0]
+
+
+def clahe(img, clip_limit=2.0, tiles=(8, 8), out=None, return_lut=False, device=0):
+    """Contrast-limited adaptive histogram equalisation (av_clahe; the definition is written out in include/airvision.h): img uint8
+    [n, h, w] or [h, w], a cuda tensor or anything torch.as_tensor takes; tiles = (tiles_x, tiles_y).  Returns a uint8 cuda tensor of
+    the same shape -- `out` itself if given (a contiguous uint8 cuda tensor of that shape; out = img works in place) -- and with
+    return_lut the look-up tables as well, uint8 [n, tiles_y * tiles_x, 256]."""
+    t = torch.as_tensor(img)
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3):
+        raise ValueError('clahe: uint8 [n, h, w] or [h, w] images, got %s %s' % (t.dtype, tuple(t.shape)))
+    t = t.to(_dev(device)).contiguous()
+    shape = tuple(t.shape)
+    h, w = shape[-2:]
+    n = shape[0] if t.dim() == 3 else 1
+    if out is None:
+        out = torch.empty_like(t)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError('clahe: out must be a contiguous uint8 cuda tensor of shape %s' % (shape,))
+    tx, ty = [int(v) for v in tiles]
+    lut = torch.empty((n, max(tx * ty, 1), 256), dtype=torch.uint8, device=_dev(device)) if return_lut else None
+    with torch.cuda.device(device):
+        N.check(N.lib().av_clahe(N.dptr(t), w * h, n, w, h, float(clip_limit), tx, ty, N.dptr(out), w * h,
+                                 None if lut is None else N.dptr(lut), N.current_stream()))
+    return (out, lut) if return_lut else out

@@ -236,7 +236,7 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
     return trajs, dss
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--root', help='directory holding the EuRoC sequences')
     ap.add_argument('--make-synthetic', metavar='DIR', help='first write EuRoC-layout synthetic sequences (one per --sequences name) into DIR and use it as --root')
@@ -250,6 +250,27 @@ def main(argv=None):
     ap.add_argument('--no-share-frames', action='store_true', help="round 4's per-stream staging instead of the shared frame store (A/B)")
     ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
     ap.add_argument('--ransac-threshold', type=float, default=None, metavar='T', help='inlier error in pixels (config.ransac_threshold, default 3)')
+    ap.add_argument('--clahe', action='store_true', help='equalise every frame (CLAHE) ahead of the pyramids, LK and FAST (config.use_clahe; off = the reference front-end)')
+    ap.add_argument('--clahe-clip', type=float, default=None, metavar='C', help='clip limit (config.clahe_clip_limit, default 2.0; 0 = no clipping)')
+    ap.add_argument('--clahe-tiles', nargs=2, type=int, default=None, metavar=('X', 'Y'), help='tile grid (config.clahe_tiles, default 8 8)')
+    return ap
+
+
+def apply_args(cfg, args):
+    """The command line's front-end switches on a config object."""
+    cfg.use_ransac = bool(args.ransac)
+    if args.ransac_threshold is not None:
+        cfg.ransac_threshold = args.ransac_threshold
+    cfg.use_clahe = bool(args.clahe)
+    if args.clahe_clip is not None:
+        cfg.clahe_clip_limit = args.clahe_clip
+    if args.clahe_tiles is not None:
+        cfg.clahe_tiles = (int(args.clahe_tiles[0]), int(args.clahe_tiles[1]))
+    return cfg
+
+
+def main(argv=None):
+    ap = make_parser()
     args = ap.parse_args(argv)
 
     import torch
@@ -265,9 +286,7 @@ def main(argv=None):
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     cfg = ConfigEuRoC(grid_row=args.grid[0], grid_col=args.grid[1], grid_max_feature_num=args.grid[2]) if args.grid else ConfigEuRoC()
-    cfg.use_ransac = bool(args.ransac)
-    if args.ransac_threshold is not None:
-        cfg.ransac_threshold = args.ransac_threshold
+    apply_args(cfg, args)
     root = args.root
     if args.make_synthetic:
         root = args.make_synthetic
@@ -307,7 +326,10 @@ def main(argv=None):
             with open(os.path.join(args.out, 'output_%s_offset%d.txt' % (seq, int(off))), 'w') as f:
                 for row in allt[j]:
                     f.write(format_state_line(row[0], row[1:4], row[4:8]))
-        print(json.dumps(sweep_report(jobs, per_rank, elapsed, world)))
+        rep = sweep_report(jobs, per_rank, elapsed, world)
+        if cfg.use_clahe:
+            rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
+        print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
 

@@ -89,8 +89,11 @@ class SyntheticStream(object):
 
     def __init__(self, config, seed=0, n_frames=20, t0=100.0, lead_in=1.0, motion_scale=1.0,
                  pixel_noise=1.0, texture=None, render=True, rest=0.0, tex_offset=(0.0, 0.0),
-                 moving_region=None, moving_amplitude=0.15, moving_rate=1.5):
-        """moving_region = (x0, y0, x1, y1) in pixels (default none: the renders are what they always were): inside that rectangle of
+                 moving_region=None, moving_amplitude=0.15, moving_rate=1.5, contrast=1.0, brightness_offset=0.0):
+        """contrast, brightness_offset (defaults 1, 0: the renders are what they always were): every rendered grey value goes to
+        mean + contrast * (value - mean) + brightness_offset, mean being the texture's mean grey value, before sensor noise and
+        quantisation -- a dim or flat scene, the case config.use_clahe is for.  `frame` and `frame_torch` apply the same mapping.
+        moving_region = (x0, y0, x1, y1) in pixels (default none: the renders are what they always were): inside that rectangle of
         BOTH images the scene is rendered from the rig's pose shifted by `region_offset(t)`, a rigid offset that swings with
         moving_amplitude metres at moving_rate Hz.  The rectangle therefore shows a stereo-consistent scene (it passes the stereo
         gates) that moves against the ego-motion from frame to frame: an independently moving object, the case the tracker's
@@ -106,8 +109,10 @@ class SyntheticStream(object):
         self.pixel_noise = float(pixel_noise)
         self.moving_region = None if moving_region is None else tuple(int(v) for v in moving_region)
         self.moving_amplitude, self.moving_rate = float(moving_amplitude), float(moving_rate)
+        self.contrast, self.brightness_offset = float(contrast), float(brightness_offset)
         self.rng = np.random.default_rng(0xA1B0 + self.seed)
         self.tex = (make_texture(0xA1B0 + self.seed) if texture is None else texture) if render else None
+        self.tex_mean = np.float32(self.tex.mean(dtype=np.float64)) if render else np.float32(0)
 
         # camera <-> imu geometry (T_imu_cam*: imu-frame vector -> camera frame)
         self.T_c0_i = np.linalg.inv(config.T_imu_cam0)      # cam0 -> imu
@@ -174,6 +179,8 @@ class SyntheticStream(object):
         ui1 = (ui + 1) % tw; vi1 = (vi + 1) % th
         t = self.tex
         img = (t[vi, ui] * (1 - fu) + t[vi, ui1] * fu) * (1 - fv) + (t[vi1, ui] * (1 - fu) + t[vi1, ui1] * fu) * fv
+        if self.contrast != 1.0 or self.brightness_offset != 0.0:
+            img = (self.tex_mean + np.float32(self.contrast) * (img - self.tex_mean)) + np.float32(self.brightness_offset)
         if self.pixel_noise > 0:
             img = img + noise_rng.normal(0, self.pixel_noise, img.shape).astype(np.float32)
         return np.ascontiguousarray(np.clip(np.rint(img), 0, 255).astype(np.uint8))
@@ -250,6 +257,8 @@ class SyntheticStream(object):
             ui = torch.remainder(u0.to(torch.int64), tw); vi = torch.remainder(v0.to(torch.int64), th)
             ui1 = torch.remainder(ui + 1, tw); vi1 = torch.remainder(vi + 1, th)
             img = (tex[vi, ui] * (1 - fu) + tex[vi, ui1] * fu) * (1 - fv) + (tex[vi1, ui] * (1 - fu) + tex[vi1, ui1] * fu) * fv
+            if self.contrast != 1.0 or self.brightness_offset != 0.0:
+                img = (float(self.tex_mean) + self.contrast * (img - float(self.tex_mean))) + self.brightness_offset
             if self.pixel_noise > 0:
                 img = img + torch.randn(img.shape, generator=generator, device=dev, dtype=torch.float32) * self.pixel_noise
             out.append(torch.clamp(torch.round(img), 0, 255).to(torch.uint8))
