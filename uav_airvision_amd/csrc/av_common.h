@@ -178,6 +178,13 @@ __device__ __forceinline__ void av_distort(const CamModel& c, double x, double y
 #endif  // __HIPCC__
 
 // ---- kernel launchers (defined in the .hip files, used by ops_api and the engine) -------------
+// Where one camera's frames lie for an LK or FAST launch: set (LK) / image (FAST) s is storage entry e = map ? map[s] : s.
+struct ImgView {
+    const uint8_t* pyr; int64_t pyr_stride;      // padded pyramid of entry e at pyr + e * pyr_stride
+    const uint8_t* img; int64_t img_stride;      // level 0 read in place, w-pitched, at img + e * img_stride; null: level 0 of the pyramid
+    const int* map;                              // shared frame store (LK: a negative entry = the set has no frame in this step); or null
+};
+
 // pyramid.hip
 int av_launch_pyramid(const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int n_streams, int imgs_per_stream,
                       const PyrGeom& g, uint8_t* pyr_base, int64_t stream_stride, int64_t slot_stride, int slot0, int slot1,
@@ -190,19 +197,20 @@ struct LKParams {
     int win, max_iter;
     double eps2, min_eig;
 };
-int av_launch_lk(const uint8_t* pyrI, const uint8_t* pyrJ, int64_t stream_stride, int n_set, const PyrGeom& g,
+// I -> J; the two views share one pyramid stride (LKArgs::stream_stride)
+int av_launch_lk(const ImgView& I, const ImgView& J, int n_set, const PyrGeom& g,
                  const float* prev, float* next, uint8_t* status, const int* count, int cap, int launch_pts,
-                 const LKParams& p, hipStream_t st, const int* index = nullptr,
-                 const uint8_t* imgI = nullptr, int64_t imgI_stride = 0, const uint8_t* imgJ = nullptr, int64_t imgJ_stride = 0,      // level 0 of I / J from the caller's image (lk.hip: LKArgs)
-                 const int* mapI = nullptr, const int* mapJ = nullptr);      // set -> storage entry of the I / J pyramids and images (shared frame store)
+                 const LKParams& p, hipStream_t st, const int* index = nullptr);
 
 // fast.hip
 void av_fast_tiles(int w, int h, int* tiles, int* tile_cap);         // tile count of a w x h image, entries per tile list
-int av_launch_fast(const uint8_t* img, int64_t img_stride, int img_pitch, int border, const uint8_t* mask, int64_t mask_stride,
+// scans src.img in place, or -- src.img null -- the interior of level 0 of src.pyr with its AV_PYR_BORDER-pixel frame (g: its geometry;
+// may be null when src.img is given); image i of the launch is storage entry src.map[i] of the image, the mask and the lists
+int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, int64_t mask_stride,
                    int n_img, int w, int h, int threshold,
                    uint32_t* kp, int* count, int cap,                               // flat output (ops API) or NULL
                    uint32_t* tile_kp, int* tile_count,                              // per-tile output (front-end engine) or NULL
-                   int* overflow, int stat_stride, hipStream_t st, const int* index = nullptr);      // index: image i of the launch is storage entry index[i]
+                   int* overflow, int stat_stride, hipStream_t st);
 
 // ransac.hip: the engine's outlier-rejection stage (AV_FE_RANSAC), one single-wavefront workgroup per stream: both camera problems,
 // ordered compaction of cur_* to the survivors, cur_count, counts[s][4], then the FAST mask boxes of the survivors

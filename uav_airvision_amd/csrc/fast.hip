@@ -309,23 +309,28 @@ void av_fast_tiles(int w, int h, int* tiles, int* tile_cap)
 }
 
 // Exactly one of (kp, count, cap) -- a flat list per image -- and (tile_kp, tile_count) -- per-tile lists, see av_fast_tiles -- is given.
-int av_launch_fast(const uint8_t* img, int64_t img_stride, int img_pitch, int border, const uint8_t* mask, int64_t mask_stride,
+int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, int64_t mask_stride,
                    int n_img, int w, int h, int threshold,
                    uint32_t* kp, int* count, int cap, uint32_t* tile_kp, int* tile_count,
-                   int* overflow, int stat_stride, hipStream_t st, const int* index)
+                   int* overflow, int stat_stride, hipStream_t st)
 {
     if (n_img <= 0) return AV_OK;
+    if (!src.img && !g) { av_set_error("av_fast_detect: a pyramid source needs its geometry"); return AV_E_INVALID; }
     if ((int64_t)w * h > (int64_t)(AV_KP_RASTER_MASK + 1)) {
         av_set_error("av_fast_detect: image %dx%d exceeds 2^19 pixels", w, h);
         return AV_E_INVALID;
     }
     FastArgs a;
-    a.img = img; a.img_stride = img_stride; a.img_pitch = img_pitch; a.border = border; a.mask = mask; a.mask_stride = mask_stride;
+    // the image in place, or level 0 of the pyramid: the same pixels with a frame (every tile but the right-most column then copies
+    // whole dwords without clamping)
+    if (src.img) { a.img = src.img; a.img_stride = src.img_stride; a.img_pitch = w; a.border = 0; }
+    else { a.img = src.pyr + g->off[0] + (size_t)AV_PYR_BORDER * g->pitch[0] + AV_PYR_BORDER; a.img_stride = src.pyr_stride; a.img_pitch = g->pitch[0]; a.border = AV_PYR_BORDER; }
+    a.mask = mask; a.mask_stride = mask_stride;
     a.w = w; a.h = h; a.threshold = threshold;
     a.kp = kp; a.count = count; a.cap = cap;
     a.tile_kp = tile_kp; a.tile_count = tile_count; a.overflow = overflow; a.stat_stride = stat_stride;
     const int tx = (w + TW - 1) / TW, ty = (h + TH - 1) / TH;
-    a.n_img = n_img; a.tiles_x = tx; a.tiles_y = ty; a.index = index;
+    a.n_img = n_img; a.tiles_x = tx; a.tiles_y = ty; a.index = src.map;
     dim3 grid((unsigned)(tx * ty) * 8u * (unsigned)((n_img + 7) / 8));
     // (An occupancy throttle -- unused dynamic LDS holding the detector to 6 / 5 / 4 workgroups per CU so that the filter's kernels find
     //  room beside it -- was measured in round 5: 156.9 / 154.7 / 149.7 k against 157.5 k frames/s.  profiles/r05/README.md)
@@ -348,6 +353,6 @@ AV_EXPORT int av_fast_detect(const uint8_t* img_dev, int64_t img_stride, const u
     }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipMemsetAsync(count_dev, 0, sizeof(int) * (size_t)n_img, st));
-    return av_launch_fast(img_dev, img_stride, w, 0, mask_dev, mask_stride, n_img, w, h, threshold, kp_dev, count_dev, cap,
+    return av_launch_fast(ImgView{nullptr, 0, img_dev, img_stride, nullptr}, nullptr, mask_dev, mask_stride, n_img, w, h, threshold, kp_dev, count_dev, cap,
                           nullptr, nullptr, nullptr, 0, st);
 }

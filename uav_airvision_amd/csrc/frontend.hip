@@ -753,17 +753,34 @@ struct Span {
     }
 };
 
-// AV_FE_CLAHE: both cameras' images of every stream -> the engine's equalised level 0 (slots cur0 and 2), then levels 1.. from there
-int clahe_and_pyramids(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int cur0, hipStream_t st, bool* wrote_l0)
+// AV_FE_CLAHE: the equalised level 0 that goes with pyramid slot `slot`
+uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot * fe->d.S * fe->d.w * fe->d.h; }
+
+// The input stage of a step (step_impl, av_frontend_prestage): the pyramids of both cameras' images into slots cur and 2; with
+// AV_FE_CLAHE the images are first equalised into the engine's own level 0 and the pyramids built from there.  One class-0 span.
+// *wrote_l0 = false: level 0 stays the image itself (never asked for unless the inputs persist: the equalised ones always do).
+int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int cur, bool inputs_persist, hipStream_t st, bool* wrote_l0)
 {
-    const int S = fe->d.S;
-    const int64_t hw = (int64_t)fe->d.w * fe->d.h;
-    uint8_t* e0 = fe->eq + (size_t)cur0 * S * hw; uint8_t* e1 = fe->eq + (size_t)2 * S * hw;
+    const FeDev& d = fe->d;
     const av_frontend_config& c = fe->cfg;
     Span sp(fe, 0, st);
-    int rc = av_launch_clahe(img0, img1, img_stride, e0, e1, hw, S, fe->d.w, fe->d.h, c.clahe_clip_limit, c.clahe_tiles_x, c.clahe_tiles_y, fe->eq_lut, st);
-    if (rc) return rc;
-    return av_launch_pyramid(e0, e1, hw, S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur0, 2, st, false, wrote_l0);
+    if (fe->clahe) {
+        uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
+        const int64_t hw = (int64_t)d.w * d.h;
+        int rc = av_launch_clahe(img0, img1, img_stride, e0, e1, hw, d.S, d.w, d.h, c.clahe_clip_limit, c.clahe_tiles_x, c.clahe_tiles_y, fe->eq_lut, st);
+        if (rc) return rc;
+        img0 = e0; img1 = e1; img_stride = hw; inputs_persist = true;
+    }
+    return av_launch_pyramid(img0, img1, img_stride, d.S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur, 2, st, !inputs_persist, wrote_l0);
+}
+
+// pyramid slot `slot` of the engine (0 / 1: cam0 of alternating frames, 2: cam1) with the level 0 that was recorded for it
+ImgView slot_view(const av_frontend* fe, int slot) { return ImgView{fe->pyr + slot * fe->lay.bytes, 3 * fe->lay.bytes, fe->l0_img[slot], fe->l0_stride[slot], nullptr}; }
+// camera `cam` of the shared frame store: entry e at pyr + (2 e + cam) * bytes / img + (2 e + cam) * w * h, reached through `map`
+ImgView store_view(const av_frontend* fe, int cam, const int* map)
+{
+    const int64_t hw = (int64_t)fe->d.w * fe->d.h;
+    return ImgView{fe->fs.pyr + cam * fe->lay.bytes, 2 * fe->lay.bytes, fe->fs.l0_in_place ? fe->fs.img + cam * hw : nullptr, 2 * hw, map};
 }
 
 // slots != nullptr: the step reads the shared frame store (stream s: entry slots[s], < 0 = no frame in this step); img0 / img1 unused.
@@ -810,54 +827,36 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     else AV_HIP(hipMemcpyAsync(fe->dH, hH, sizeof(double) * 9 * S + (frames ? sizeof(int) * 2 * S : 0), hipMemcpyHostToDevice, st));
     AV_HIP(hipEventRecord(fe->hH_ev[slot], st));
     AV_HIP(hipMemsetAsync(fe->zero_region, 0, fe->zero_bytes, st));
-    const int* map_cur = nullptr; const int* map_prev = nullptr;
-    if (frames) {
-        map_cur = reinterpret_cast<const int*>(fe->dH + (size_t)9 * S); map_prev = map_cur + S;
-        d.slot_cur = map_cur; d.tile_kp = fe->fs.tile_kp; d.tile_count = fe->fs.tile_count;
-        if (fe->fs.any_upload) AV_HIP(hipStreamWaitEvent(st, fe->fs.uploaded, 0));      // the frames this step reads are in the store, pyramids and FAST lists with them
-    }
 
     const int par = fe->parity;              // prev grid buffer / prev cam0 pyramid slot
-    const int cur0 = par ^ 1;                // curr cam0 pyramid slot (0/1), cam1 pyramid is slot 2
-    int64_t sstride = 3 * fe->lay.bytes; const int64_t slotb = fe->lay.bytes;
+    const int cur = par ^ 1;                 // curr cam0 pyramid slot (0/1), cam1 pyramid is slot 2
     int rc;
-    const uint8_t *I_prev0, *I_cur0, *I_cur1, *P_prev0, *P_cur0, *P_cur1; int64_t st_prev0;
+    ImgView prev0, cur0, cur1;               // cam0 of the previous frame, cam0 and cam1 of this one
     if (frames) {
-        // pyramids and level-0 images of both cameras lie in the store, built when the frame was uploaded: entry e of camera c at
-        // pyr + (2 e + c) * bytes / img + (2 e + c) * w * h; the LK launches index it through map_prev / map_cur
-        const size_t hw = (size_t)d.w * d.h;
-        sstride = 2 * slotb; img_stride = (int64_t)(2 * hw); st_prev0 = img_stride;
-        P_prev0 = P_cur0 = fe->fs.pyr; P_cur1 = fe->fs.pyr + slotb;
-        I_prev0 = I_cur0 = fe->fs.l0_in_place ? fe->fs.img : nullptr; I_cur1 = fe->fs.l0_in_place ? fe->fs.img + hw : nullptr;
+        // pyramids, level-0 images and FAST lists of both cameras lie in the store, built when the frame was uploaded
+        const int* map_cur = reinterpret_cast<const int*>(fe->dH + (size_t)9 * S);
+        d.slot_cur = map_cur; d.tile_kp = fe->fs.tile_kp; d.tile_count = fe->fs.tile_count;
+        if (fe->fs.any_upload) AV_HIP(hipStreamWaitEvent(st, fe->fs.uploaded, 0));      // the frames this step reads are in the store, pyramids and FAST lists with them
+        prev0 = store_view(fe, 0, map_cur + S); cur0 = store_view(fe, 0, map_cur); cur1 = store_view(fe, 1, map_cur);
     } else {
         bool wrote_l0 = true;
         if (fe->pre_on && fe->pre_img0 == img0 && fe->pre_img1 == img1 && fe->pre_stride == img_stride) wrote_l0 = fe->pre_wrote_l0;      // built by av_frontend_prestage
-        else if (fe->clahe) { if ((rc = clahe_and_pyramids(fe, img0, img1, img_stride, cur0, st, &wrote_l0))) return rc; }
-        else { Span sp(fe, 0, st);
-          if ((rc = av_launch_pyramid(img0, img1, img_stride, S, 2, fe->geom, fe->pyr, sstride, slotb, cur0, 2, st, !inputs_persist, &wrote_l0))) return rc; }
+        else if ((rc = input_stage(fe, img0, img1, img_stride, cur, inputs_persist, st, &wrote_l0))) return rc;
         fe->pre_on = false;
-        if (fe->clahe) {                   // from here on the equalised images are the step's inputs, and they persist
-            const int64_t hw = (int64_t)d.w * d.h;
-            img0 = fe->eq + (size_t)cur0 * S * hw; img1 = fe->eq + (size_t)2 * S * hw; img_stride = hw;
-        }
-        fe->l0_img[cur0] = wrote_l0 ? nullptr : img0; fe->l0_img[2] = wrote_l0 ? nullptr : img1;
-        fe->l0_stride[cur0] = fe->l0_stride[2] = img_stride;
-        I_prev0 = fe->l0_img[par]; st_prev0 = fe->l0_stride[par];      // (first frame: nothing is tracked from it)
-        I_cur0 = fe->l0_img[cur0]; I_cur1 = fe->l0_img[2];
-        P_prev0 = fe->pyr + par * slotb;
-        P_cur0 = fe->pyr + cur0 * slotb;
-        P_cur1 = fe->pyr + 2 * slotb;
+        if (fe->clahe) { img0 = eq_slot(fe, cur); img1 = eq_slot(fe, 2); img_stride = (int64_t)d.w * d.h; }      // from here on the equalised images are the step's inputs
+        fe->l0_img[cur] = wrote_l0 ? nullptr : img0; fe->l0_img[2] = wrote_l0 ? nullptr : img1;
+        fe->l0_stride[cur] = fe->l0_stride[2] = img_stride;
+        prev0 = slot_view(fe, par); cur0 = slot_view(fe, cur); cur1 = slot_view(fe, 2);      // (first frame: nothing is tracked from prev0)
     }
 
-    // FAST reads level 0 of the cam0 pyramid built above (same pixels as the input image, with a 16-pixel frame: every
-    // tile but the right-most column copies whole dwords without clamping) or the caller's image in place
-    auto launch_fast = [&](hipStream_t fs) -> int {
-        Span sp(fe, 2, fs);
-        const uint8_t* fast_img = P_cur0 + fe->geom.off[0] + (size_t)AV_PYR_BORDER * fe->geom.pitch[0] + AV_PYR_BORDER;
-        if (I_cur0) return av_launch_fast(I_cur0, img_stride, d.w, 0, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold,
-                                          nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, fs);
-        return av_launch_fast(fast_img, sstride, fe->geom.pitch[0], AV_PYR_BORDER, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold,
-                              nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, fs);
+    auto lk = [&](const ImgView& I, const ImgView& J, const float* prev, float* next, uint8_t* status, const int* count, int cap, int launch_pts, const int* list) -> int {
+        Span sp(fe, 1, st);
+        return av_launch_lk(I, J, S, fe->geom, prev, next, status, count, cap, launch_pts, fe->lk, st, list);
+    };
+    // forward / backward stereo pair: p0 in camera A -> p1 in camera B, p1 -> back in camera A
+    auto lk_pair = [&](const ImgView& A, const ImgView& B, const float* p0, float* p1, uint8_t* st1, float* back, uint8_t* st2, const int* count, int cap, int launch_pts, const int* list) -> int {
+        const int e = lk(A, B, p0, p1, st1, count, cap, launch_pts, list);
+        return e ? e : lk(B, A, p1, back, st2, count, cap, launch_pts, list);
     };
     // per-stream glue kernels: 256-thread workgroups.  (64, one wavefront per stream -- bit-exact, the kernels take any
     // workgroup size -- was measured in round 5: glue 0.78 against 0.66 ms alone, 0.94 against 1.07 beside the filter, and the detector next
@@ -865,15 +864,11 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(track_prepare_kernel, dim3((d.NT + 255) / 256, S), dim3(256), 0, st, d, par);
       AV_LAUNCH_CHECK(); }
-    { Span sp(fe, 1, st);
-      if ((rc = av_launch_lk(P_prev0, P_cur0, sstride, S, fe->geom, d.trk_prev, d.trk_next, d.trk_status, d.trk_count, d.NT, d.NT, fe->lk, st, nullptr, I_prev0, st_prev0, I_cur0, img_stride, map_prev, map_cur))) return rc; }
+    if ((rc = lk(prev0, cur0, d.trk_prev, d.trk_next, d.trk_status, d.trk_count, d.NT, d.NT, nullptr))) return rc;
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(track_gate_kernel, dim3(S), dim3(256), 0, st, d);
       AV_LAUNCH_CHECK(); }
-    { Span sp(fe, 1, st);
-      if ((rc = av_launch_lk(P_cur0, P_cur1, sstride, S, fe->geom, d.sv_p0, d.sv_p1, d.sv_st, d.sv_count, d.NT, d.NT, fe->lk, st, nullptr, I_cur0, img_stride, I_cur1, img_stride, map_cur, map_cur))) return rc; }
-    { Span sp(fe, 1, st);
-      if ((rc = av_launch_lk(P_cur1, P_cur0, sstride, S, fe->geom, d.sv_p1, d.sv_back, d.sv_st2, d.sv_count, d.NT, d.NT, fe->lk, st, nullptr, I_cur1, img_stride, I_cur0, img_stride, map_cur, map_cur))) return rc; }
+    if ((rc = lk_pair(cur0, cur1, d.sv_p0, d.sv_p1, d.sv_st, d.sv_back, d.sv_st2, d.sv_count, d.NT, d.NT, nullptr))) return rc;
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(rebin_kernel, dim3(S), dim3(256), 0, st, d, par);
       AV_LAUNCH_CHECK(); }
@@ -886,25 +881,20 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     // (FAST on a second HIP stream beside the temporal / stereo LK launches -- it reads only the new cam0 image and is first needed by
     //  select_kernel -- was measured in round 5: front-end alone 196.6 k against 205.1 k frames/s, complete path 157.7 against 157.3 k:
     //  the LK launches slow down by more than the detector's time; profiles/r05/README.md)
-    if (!frames && (rc = launch_fast(st))) return rc;                           // (frame store: FAST ran when the frame was uploaded)
+    if (!frames) {                             // (frame store: FAST ran when the frame was uploaded)
+        Span sp(fe, 2, st);
+        if ((rc = av_launch_fast(cur0, &fe->geom, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold, nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, st))) return rc;
+    }
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(select_kernel, dim3(S), dim3(256), sizeof(int) * (3 * d.C + 1 + d.n_tiles + 1), st, d);
       AV_LAUNCH_CHECK(); }
     const int r1_launch = any_first ? d.CC : d.C * (d.gmax < CAND_R1 ? d.gmax : CAND_R1);
-    { Span sp(fe, 1, st);
-      if ((rc = av_launch_lk(P_cur0, P_cur1, sstride, S, fe->geom, d.cand_p0, d.cand_p1, d.cand_st, d.r1_count, d.CC, r1_launch, fe->lk, st, d.r1_list, I_cur0, img_stride, I_cur1, img_stride, map_cur, map_cur))) return rc; }
-    { Span sp(fe, 1, st);
-      if ((rc = av_launch_lk(P_cur1, P_cur0, sstride, S, fe->geom, d.cand_p1, d.cand_back, d.cand_st2, d.r1_count, d.CC, r1_launch, fe->lk, st, d.r1_list, I_cur1, img_stride, I_cur0, img_stride, map_cur, map_cur))) return rc; }
+    if ((rc = lk_pair(cur0, cur1, d.cand_p0, d.cand_p1, d.cand_st, d.cand_back, d.cand_st2, d.r1_count, d.CC, r1_launch, d.r1_list))) return rc;
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(cand_round2_kernel, dim3(S), dim3(256), 0, st, d);
       AV_LAUNCH_CHECK(); }
-    if (d.gmax > CAND_R1) {                       // round 2: the rest of the cells that are still short of inliers (usually none)
-        const int r2_launch = d.C * (d.gmax - CAND_R1);
-        { Span sp(fe, 1, st);
-          if ((rc = av_launch_lk(P_cur0, P_cur1, sstride, S, fe->geom, d.cand_p0, d.cand_p1, d.cand_st, d.r2_count, d.CC, r2_launch, fe->lk, st, d.r2_list, I_cur0, img_stride, I_cur1, img_stride, map_cur, map_cur))) return rc; }
-        { Span sp(fe, 1, st);
-          if ((rc = av_launch_lk(P_cur1, P_cur0, sstride, S, fe->geom, d.cand_p1, d.cand_back, d.cand_st2, d.r2_count, d.CC, r2_launch, fe->lk, st, d.r2_list, I_cur1, img_stride, I_cur0, img_stride, map_cur, map_cur))) return rc; }
-    }
+    // round 2: the rest of the cells that are still short of inliers (usually none)
+    if (d.gmax > CAND_R1 && (rc = lk_pair(cur0, cur1, d.cand_p0, d.cand_p1, d.cand_st, d.cand_back, d.cand_st2, d.r2_count, d.CC, d.C * (d.gmax - CAND_R1), d.r2_list))) return rc;
     size_t fin_lds = sizeof(unsigned long long) * d.NSORT + sizeof(int) * (2 * d.C * d.gmin + 2 * d.C + 3 * (d.C + 1) + 4);
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(finalize_kernel, dim3(S), dim3(256), fin_lds, st, d, par);
@@ -1114,12 +1104,9 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
-    const int cur0 = fe->parity ^ 1;         // the slots the next step will call cur0 / 2
-    int rc;
     bool wrote_l0 = true;
-    if (fe->clahe) { if ((rc = clahe_and_pyramids(fe, img0_dev, img1_dev, img_stride, cur0, st, &wrote_l0))) return rc; }
-    else { Span sp(fe, 0, st);
-      if ((rc = av_launch_pyramid(img0_dev, img1_dev, img_stride, fe->d.S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur0, 2, st, false, &wrote_l0))) return rc; }
+    const int rc = input_stage(fe, img0_dev, img1_dev, img_stride, fe->parity ^ 1, true, st, &wrote_l0);      // the slots the next step will call cur / 2
+    if (rc) return rc;
     // (The detector's pass over the new cam0 image -- it reads nothing but the image -- enqueued here as well ran at its exclusive speed,
     //  1.55 ms against 2.3 beside the filter's back end, and the LK launches took what it gave back: 173.4-173.9 against 174.1-175.2 k
     //  frames/s.  profiles/r05/README.md)
@@ -1258,16 +1245,14 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     }
     int rc;
     bool wrote_l0 = true;
+    // (not input_stage: these launches are indexed, in place in the store, on the copy stream and outside the step's timing spans)
     // AV_FE_CLAHE: the entries are equalised once, where they lie, before anything reads them (the tables by position in this upload)
     if (fe->clahe && (rc = av_launch_clahe(fs.img, fs.img + hw, (int64_t)(2 * hw), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->cfg.clahe_clip_limit,
                                            fe->cfg.clahe_tiles_x, fe->cfg.clahe_tiles_y, fe->fs_lut, cs, u.idx_d))) return rc;
     if ((rc = av_launch_pyramid(fs.img, fs.img + hw, (int64_t)(2 * hw), n, 2, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0, u.idx_d))) return rc;
     fs.l0_in_place = !wrote_l0;
-    if (fs.l0_in_place) rc = av_launch_fast(fs.img, (int64_t)(2 * hw), d.w, 0, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold,
-                                            nullptr, nullptr, 0, fs.tile_kp, fs.tile_count, nullptr, 0, cs, u.idx_d);
-    else rc = av_launch_fast(fs.pyr + fe->geom.off[0] + (size_t)AV_PYR_BORDER * fe->geom.pitch[0] + AV_PYR_BORDER, 2 * fe->lay.bytes, fe->geom.pitch[0], AV_PYR_BORDER,
-                             nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold, nullptr, nullptr, 0, fs.tile_kp, fs.tile_count, nullptr, 0, cs, u.idx_d);
-    if (rc) return rc;
+    if ((rc = av_launch_fast(store_view(fe, 0, u.idx_d), &fe->geom, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold,
+                             nullptr, nullptr, 0, fs.tile_kp, fs.tile_count, nullptr, 0, cs))) return rc;
     AV_HIP(hipEventRecord(u.done, cs));
     AV_HIP(hipEventRecord(fs.uploaded, cs));
     u.used = true; fs.any_upload = true;

@@ -35,6 +35,7 @@
 //     to the scalar CPU oracle.
 // Bound: VALU issue (PMC: ~1,400 VALU instructions per point pass; the staged tiles come from
 // L2/MALL: the padded pyramids of a stream are ~560 KB); HBM sees each pyramid once per frame.
+#include <assert.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -819,13 +820,13 @@ __global__ __launch_bounds__(256) void lk_track_generic_kernel(LKArgs a, int WIN
 
 }  // namespace
 
-static int lk_fill_args(LKArgs& a, const uint8_t* pyrI, const uint8_t* pyrJ, int64_t stream_stride, const PyrGeom& g,
+static int lk_fill_args(LKArgs& a, const ImgView& I, const ImgView& J, const PyrGeom& g,
                         const float* prev, float* next, uint8_t* status, const int* count, int cap,
-                        const LKParams& p, const int* index,
-                        const uint8_t* imgI, int64_t imgI_stride, const uint8_t* imgJ, int64_t imgJ_stride, const int* mapI, const int* mapJ)
+                        const LKParams& p, const int* index)
 {
     if (p.win < 3 || p.win > LKG_MAX_WIN) { av_set_error("av_lk_track: winSize %d outside 3 .. %d", p.win, LKG_MAX_WIN); return AV_E_INVALID; }
-    a.pyrI = pyrI; a.pyrJ = pyrJ; a.stream_stride = stream_stride; a.g = g;
+    assert(I.pyr_stride == J.pyr_stride);        // the kernels step both pyramids by LKArgs::stream_stride
+    a.pyrI = I.pyr; a.pyrJ = J.pyr; a.stream_stride = I.pyr_stride; a.g = g;
     // cv::buildOpticalFlowPyramid stops at the first level whose successor would be no larger than the window in either
     // dimension (OpenCV 4.x lkpyramid.cpp: `if (sz.width <= winSize.width || sz.height <= winSize.height) return level`);
     // level 0 is always tracked.  Not reached by the reference's 752 x 480 / 15 / 3.
@@ -838,7 +839,7 @@ static int lk_fill_args(LKArgs& a, const uint8_t* pyrI, const uint8_t* pyrJ, int
     if (p.eps2 >= 1e-30) { a.eps_lo = (float)(p.eps2 * (1. - 0x1p-18)); a.eps_hi = (float)(p.eps2 * (1. + 0x1p-18)); }
     else { a.eps_lo = -1.f; a.eps_hi = INFINITY; }                 // e32 may underflow: every test in fp64
     a.min_eig = p.min_eig;
-    a.imgI = imgI; a.imgJ = imgJ; a.imgI_stride = imgI_stride; a.imgJ_stride = imgJ_stride; a.mapI = mapI; a.mapJ = mapJ; a.prof = nullptr;
+    a.imgI = I.img; a.imgJ = J.img; a.imgI_stride = I.img_stride; a.imgJ_stride = J.img_stride; a.mapI = I.map; a.mapJ = J.map; a.prof = nullptr;
     a.n_set = 0; a.gx = 0;
     return AV_OK;
 }
@@ -864,14 +865,13 @@ static dim3 lk_g16_grid(LKArgs& a, int n_set, int launch_pts, int pts_per_wg)
     return dim3((unsigned)a.gx * 8u * (unsigned)((n_set + 7) / 8));
 }
 
-int av_launch_lk(const uint8_t* pyrI, const uint8_t* pyrJ, int64_t stream_stride, int n_set, const PyrGeom& g,
+int av_launch_lk(const ImgView& I, const ImgView& J, int n_set, const PyrGeom& g,
                  const float* prev, float* next, uint8_t* status, const int* count, int cap, int launch_pts,
-                 const LKParams& p, hipStream_t st, const int* index,
-                 const uint8_t* imgI, int64_t imgI_stride, const uint8_t* imgJ, int64_t imgJ_stride, const int* mapI, const int* mapJ)
+                 const LKParams& p, hipStream_t st, const int* index)
 {
     if (n_set <= 0 || launch_pts <= 0) return AV_OK;
     LKArgs a;
-    int rc = lk_fill_args(a, pyrI, pyrJ, stream_stride, g, prev, next, status, count, cap, p, index, imgI, imgI_stride, imgJ, imgJ_stride, mapI, mapJ);
+    int rc = lk_fill_args(a, I, J, g, prev, next, status, count, cap, p, index);
     if (rc) return rc;
     if (launch_pts > cap) launch_pts = cap;
     if (p.win != 15) {           // any other window of config.win_size: the general kernel (one wavefront per point)
@@ -909,6 +909,6 @@ AV_EXPORT int av_lk_track(const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int6
     double e = eps < 0 ? 0. : (eps > 10. ? 10. : eps);
     p.eps2 = e * e;
     p.min_eig = min_eig_threshold;
-    return av_launch_lk(pyrI_dev, pyrJ_dev, pyr_stride, n_set, av_make_geom(lay), prev_dev, next_dev, status_dev,
-                        count_dev, cap, cap, p, (hipStream_t)stream, nullptr);
+    return av_launch_lk(ImgView{pyrI_dev, pyr_stride, nullptr, 0, nullptr}, ImgView{pyrJ_dev, pyr_stride, nullptr, 0, nullptr}, n_set, av_make_geom(lay),
+                        prev_dev, next_dev, status_dev, count_dev, cap, cap, p, (hipStream_t)stream);
 }
