@@ -32,6 +32,11 @@ extern "C" {
 
 #define AV_MAX_LEVELS    5   /* pyramid levels 0..4 (the reference uses maxLevel = 3, config.py:34) */
 #define AV_PYR_BORDER   16   /* border (pixels) of every padded pyramid level; >= LK win + 1 */
+/* The one limit on the size of an image: width * height <= AV_MAX_IMAGE_PIXELS for the front-end engine (every entry path),
+ * av_fast_detect_wide and av_clahe; the pyramids and av_lk_track take at least that.  (av_fast_detect alone keeps the 2^19 pixels its
+ * word format holds.)  The minimum sizes are each function's own: every pyramid level wider and higher than AV_PYR_BORDER, 7 x 7 for
+ * the detector. */
+#define AV_MAX_IMAGE_PIXELS (1 << 24)
 
 /* Thread-local text of the last error raised on the calling thread. */
 const char* av_last_error(void);
@@ -85,10 +90,17 @@ int av_lk_track(const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_st
  * kp_dev[i*cap + k] = score << 19 | (2^19 - 1 - (y*w + x)); keypoints are UNORDERED (sort the
  * packed words descending within equal score to recover raster order).  Requires w*h <= 2^19.
  * If more than cap keypoints exist count_dev[i] still reports the true number.
+ *
+ * av_fast_detect_wide: the same detector, same arguments, for images of up to AV_MAX_IMAGE_PIXELS = 2^24 pixels.  Only the word
+ * differs: kp_dev[i*cap + k] = score << 24 | (2^24 - 1 - (y*w + x)).  A score is at most 254, so the word fits 32 bits and orders
+ * exactly like the narrow one: by score, then by raster descending.  The two entries return the same keypoints wherever both apply.
  * ------------------------------------------------------------------------------------------- */
 int av_fast_detect(const uint8_t* img_dev, int64_t img_stride, const uint8_t* mask_dev, int64_t mask_stride,
                    int n_img, int w, int h, int threshold, uint32_t* kp_dev, int32_t* count_dev, int cap,
                    void* stream);
+int av_fast_detect_wide(const uint8_t* img_dev, int64_t img_stride, const uint8_t* mask_dev, int64_t mask_stride,
+                        int n_img, int w, int h, int threshold, uint32_t* kp_dev, int32_t* count_dev, int cap,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cv2.undistortPoints(pts, K, D, None, R, P = identity) for pinhole + radtan
@@ -122,7 +134,7 @@ int av_distort_points_model(const double* pts_dev, int n, const double* intr, co
  * imu_processor.py:22-67).
  * ------------------------------------------------------------------------------------------- */
 typedef struct av_frontend_config {
-    int32_t width, height;                   /* config.cam0_resolution (config.py:102)             */
+    int32_t width, height;                   /* config.cam0_resolution (config.py:102); width * height <= AV_MAX_IMAGE_PIXELS */
     int32_t grid_row, grid_col;              /* config.py:23-24                                     */
     int32_t grid_min_feature_num;            /* config.py:26                                        */
     int32_t grid_max_feature_num;            /* config.py:27                                        */
@@ -153,6 +165,10 @@ typedef struct av_frontend_config {
 
 typedef struct av_frontend av_frontend;
 
+/* Any width x height of at most AV_MAX_IMAGE_PIXELS pixels whose pyramid levels are all wider and higher than AV_PYR_BORDER; a larger
+ * image is refused here, AV_E_INVALID, before a device is touched.  Capacities that depend on the image: max_corners must hold the
+ * corners of a whole first frame (they grow with the area: the Python engine scales its default of 8192 at 752 x 480 by the pixel
+ * count); the per-cell lists are sized by the area of a grid cell. */
 int  av_frontend_create(const av_frontend_config* cfg, int n_streams, int device, av_frontend** out);
 void av_frontend_destroy(av_frontend* fe);
 
@@ -167,7 +183,7 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
 /* av_frontend_config.flags.  AV_FE_INPUTS_PERSIST: the device images handed to av_frontend_step stay valid and unmodified
  * until the kernels of the NEXT av_frontend_step of this engine have completed.  The engine then reads pyramid level 0 in place
  * (LK and FAST index the caller's image, with BORDER_REFLECT_101 arithmetic at the border) and builds only levels 1..3 -- no
- * padded copy of the 752x480 level: 0.8 MB less HBM traffic per stereo frame.  Without the flag the inputs are only read during
+ * padded copy of level 0: 0.8 MB less HBM traffic per stereo frame at 752x480.  Without the flag the inputs are only read during
  * the call's own kernels and level 0 is copied (the round-1/2 behaviour).  av_frontend_step_host always works in place: the
  * images live in the library's own staging slots.  Results are bit-identical either way. */
 #define AV_FE_INPUTS_PERSIST 1
@@ -306,8 +322,8 @@ int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* ou
  *     tx2 = min(tx2, tiles_x - 1); ty1, ty2, ya, ya1 the same from y and th;
  *     res = (lut[ty1][tx1][v] * xa1 + lut[ty1][tx2][v] * xa) * ya1 + (lut[ty2][tx1][v] * xa1 + lut[ty2][tx2][v] * xa) * ya
  *     in float32, in exactly this order, without fused multiply-add; out = saturate_u8(round_half_even(res)).
- * Limits: 1 <= tiles_x, tiles_y <= AV_CLAHE_MAX_TILES, clip_limit >= 0 (0 = no clipping), w * h <= 2^19 (as for FAST); anything else
- * is AV_E_INVALID with text.  lut_dev (optional): the tables, uint8 [n_img][tiles_y * tiles_x][256], 16-byte aligned (the images may lie
+ * Limits: 1 <= tiles_x, tiles_y <= AV_CLAHE_MAX_TILES, clip_limit >= 0 (0 = no clipping), w * h <= AV_MAX_IMAGE_PIXELS (a tile then has at most
+ * 2^24 pixels: every count and prefix sum is exact in int32 and in float32); anything else is AV_E_INVALID with text.  lut_dev (optional): the tables, uint8 [n_img][tiles_y * tiles_x][256], 16-byte aligned (the images may lie
  * at any address and stride: unaligned ones are read and written byte by byte).
  * ------------------------------------------------------------------------------------------- */
 #define AV_CLAHE_MAX_TILES 16

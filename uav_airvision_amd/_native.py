@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, 'libairvision_hip.so')
 
 AV_MAX_LEVELS = 5
 AV_PYR_BORDER = 16
+AV_MAX_IMAGE_PIXELS = 1 << 24
 AV_OK, AV_E_INVALID, AV_E_HIP, AV_E_CAPACITY, AV_E_NODEVICE, AV_E_NUMERIC = 0, -1, -2, -3, -4, -5
 AV_FE_INPUTS_PERSIST = 1
 AV_FE_RANSAC = 2
@@ -74,6 +75,7 @@ SIGNATURES = {
     'av_lk_track': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int,
                               C.c_int, C.c_int, C.c_double, C.c_double, _P]),
     'av_fast_detect': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
+    'av_fast_detect_wide': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     'av_undistort_points': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),
     'av_distort_points': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),
     'av_undistort_points_model': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P, _P]),

@@ -42,9 +42,16 @@ struct CamModel {
     int model;                                    // AV_DISTORTION_RADTAN (0) / AV_DISTORTION_EQUIDISTANT (1)
 };
 
-// packed FAST keypoint word: score << 19 | (2^19-1 - raster)
+// packed FAST keypoint word: score << B | (2^B - 1 - raster), B = the raster bits of the launch.  B = 19 is the documented format of
+// av_fast_detect and what the engine uses for images of up to 2^19 pixels; B = 24 (av_fast_detect_wide, larger engines) holds any
+// raster below AV_MAX_IMAGE_PIXELS.  A FAST score is at most 254, so the largest 24-bit word is 0xFEFFFFFF: every word lies strictly
+// between the two sentinels of the selection loops, 0 and 0xFFFFFFFF (a word is 0 only for score 0 at the last pixel, which lies in the
+// 3-pixel border and is never a corner).  Words order by (score, then raster descending) in either format.
 #define AV_KP_RASTER_BITS 19
-#define AV_KP_RASTER_MASK ((1u << AV_KP_RASTER_BITS) - 1u)
+#define AV_KP_RASTER_BITS_WIDE 24
+static_assert((1 << AV_KP_RASTER_BITS_WIDE) == AV_MAX_IMAGE_PIXELS, "the wide keypoint word holds every raster of the largest image");
+static_assert(((254ull << AV_KP_RASTER_BITS_WIDE) | ((1ull << AV_KP_RASTER_BITS_WIDE) - 1ull)) < 0xFFFFFFFFull, "the largest keypoint word stays below the sentinel");
+inline int av_kp_raster_bits(int w, int h) { return (int64_t)w * h <= (1 << AV_KP_RASTER_BITS) ? AV_KP_RASTER_BITS : AV_KP_RASTER_BITS_WIDE; }
 
 // ---- draw hash of the two-point RANSAC (written out in include/airvision.h; host and device) ---
 #ifdef __HIPCC__
@@ -206,8 +213,9 @@ int av_launch_lk(const ImgView& I, const ImgView& J, int n_set, const PyrGeom& g
 void av_fast_tiles(int w, int h, int* tiles, int* tile_cap);         // tile count of a w x h image, entries per tile list
 // scans src.img in place, or -- src.img null -- the interior of level 0 of src.pyr with its AV_PYR_BORDER-pixel frame (g: its geometry;
 // may be null when src.img is given); image i of the launch is storage entry src.map[i] of the image, the mask and the lists
+// raster_bits: AV_KP_RASTER_BITS (w * h <= 2^19) or AV_KP_RASTER_BITS_WIDE (w * h <= AV_MAX_IMAGE_PIXELS): the format of the words written
 int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, int64_t mask_stride,
-                   int n_img, int w, int h, int threshold,
+                   int n_img, int w, int h, int threshold, int raster_bits,
                    uint32_t* kp, int* count, int cap,                               // flat output (ops API) or NULL
                    uint32_t* tile_kp, int* tile_count,                              // per-tile output (front-end engine) or NULL
                    int* overflow, int stat_stride, hipStream_t st);

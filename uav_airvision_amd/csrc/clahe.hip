@@ -183,9 +183,12 @@ __global__ __launch_bounds__(256) void clahe_apply_kernel(ClaheArgs a)
 
 int av_clahe_check(int w, int h, double clip_limit, int tiles_x, int tiles_y, const char* who)
 {
-    if (w <= 0 || h <= 0 || (int64_t)w * h > (1 << 19) || tiles_x < 1 || tiles_x > AV_CLAHE_MAX_TILES || tiles_y < 1 || tiles_y > AV_CLAHE_MAX_TILES ||
+    // w * h <= AV_MAX_IMAGE_PIXELS = 2^24 is what keeps the arithmetic exact: a tile has at most 2^24 pixels (one tile, nothing padded),
+    // so every histogram bin, the clipped total and every prefix sum is an int of at most 2^24, and (float)sum is that integer itself;
+    // scale = 255.0f / (float)area with (float)area exact as well.  No product of 255 and a count is ever formed in integers.
+    if (w <= 0 || h <= 0 || (int64_t)w * h > AV_MAX_IMAGE_PIXELS || tiles_x < 1 || tiles_x > AV_CLAHE_MAX_TILES || tiles_y < 1 || tiles_y > AV_CLAHE_MAX_TILES ||
         !(clip_limit >= 0.0)) {
-        av_set_error("%s: CLAHE needs 1 <= tiles <= %d (%d x %d), a clip limit >= 0 (%g) and w * h <= 2^19 (%d x %d)", who, AV_CLAHE_MAX_TILES,
+        av_set_error("%s: CLAHE needs 1 <= tiles <= %d (%d x %d), a clip limit >= 0 (%g) and w * h <= 2^24 (%d x %d)", who, AV_CLAHE_MAX_TILES,
                      tiles_x, tiles_y, clip_limit, w, h);
         return AV_E_INVALID;
     }
@@ -215,9 +218,14 @@ int av_launch_clahe(const uint8_t* src0, const uint8_t* src1, int64_t src_stride
     a.dwords = (w & 3) == 0 && (src_stride & 3) == 0 && (dst_stride & 3) == 0 && al4(src0) && al4(src1) && al4(dst0) && al4(dst1);
     const unsigned groups8 = (unsigned)((a.n_img + 7) / 8) * 8u;
     a.per = tiles_x * tiles_y;
+    const int apply_chunks = (a.th + 2 + CL_ROWS - 1) / CL_ROWS;
+    if ((int64_t)(tiles_y + 1) * apply_chunks * groups8 * 256 > 0xFFFFFFFFll) {      // a launch holds fewer than 2^32 threads
+        av_set_error("av_clahe: %d images of %d x %d are more than one launch holds", a.n_img, w, h);
+        return AV_E_INVALID;
+    }
     hipLaunchKernelGGL(clahe_lut_kernel, dim3((unsigned)a.per * groups8), dim3(256), 0, st, a);
     AV_LAUNCH_CHECK();
-    a.chunks = (a.th + 2 + CL_ROWS - 1) / CL_ROWS;      // a band has th rows, one more or less where 1.0f / th rounds a boundary row across
+    a.chunks = apply_chunks;                            // a band has th rows, one more or less where 1.0f / th rounds a boundary row across
     a.per = (tiles_y + 1) * a.chunks;
     hipLaunchKernelGGL(clahe_apply_kernel, dim3((unsigned)a.per * groups8), dim3(256), (size_t)2 * tiles_x * 256, st, a);
     AV_LAUNCH_CHECK();

@@ -22,6 +22,8 @@
 // coalesced stores, every tile writes its count, no atomics and nothing to wait for -- the returning global atomics of a
 // per-cell list were a quarter of the kernel's time); its select kernel bins them into grid cells.  The stand-alone
 // detector (av_fast_detect) appends them to one flat list per image with one returning atomic per tile.
+// A survivor is one packed word, score << B | (2^B - 1 - raster) (av_common.h): B is an argument of the launch -- 19 for av_fast_detect and
+// for engines of up to 2^19 pixels, whose words are what they always were, 24 for av_fast_detect_wide and larger engines.
 // Bound: HBM read of the image (w*h bytes) -- the score arithmetic is ~200 VALU ops per candidate.
 #include <stdlib.h>
 
@@ -44,6 +46,7 @@ struct FastArgs {
     const uint8_t* mask;
     int64_t mask_stride;
     int w, h, threshold;
+    int rbits;                  // raster bits of the packed words (av_common.h)
     uint32_t* kp; int* count; int cap;
     uint32_t* tile_kp; int* tile_count;          // [n_img][tiles][TCAP], [n_img][tiles] (tiles row-major: by * tiles_x + bx)
     int* overflow; int stat_stride;
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
             if (keep && a.mask) keep = mask_dw ? ((mask4[it] >> (8 * k)) & 0xFF) != 0 : a.mask[img_i * a.mask_stride + (size_t)y * a.w + x] != 0;
             if (keep) {
                 const int slot = atomicAdd(&nsurv, 1);            // LDS atomic; a tile has <= TCAP strict maxima
-                surv_word[slot] = ((uint32_t)s << AV_KP_RASTER_BITS) | (AV_KP_RASTER_MASK - (uint32_t)(y * a.w + x));
+                surv_word[slot] = ((uint32_t)s << a.rbits) | (((1u << a.rbits) - 1u) - (uint32_t)(y * a.w + x));
             }
         }
     }
@@ -310,14 +313,19 @@ void av_fast_tiles(int w, int h, int* tiles, int* tile_cap)
 
 // Exactly one of (kp, count, cap) -- a flat list per image -- and (tile_kp, tile_count) -- per-tile lists, see av_fast_tiles -- is given.
 int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, int64_t mask_stride,
-                   int n_img, int w, int h, int threshold,
+                   int n_img, int w, int h, int threshold, int raster_bits,
                    uint32_t* kp, int* count, int cap, uint32_t* tile_kp, int* tile_count,
                    int* overflow, int stat_stride, hipStream_t st)
 {
     if (n_img <= 0) return AV_OK;
     if (!src.img && !g) { av_set_error("av_fast_detect: a pyramid source needs its geometry"); return AV_E_INVALID; }
-    if ((int64_t)w * h > (int64_t)(AV_KP_RASTER_MASK + 1)) {
-        av_set_error("av_fast_detect: image %dx%d exceeds 2^19 pixels", w, h);
+    if ((raster_bits != AV_KP_RASTER_BITS && raster_bits != AV_KP_RASTER_BITS_WIDE) || (int64_t)w * h > ((int64_t)1 << raster_bits)) {
+        av_set_error("av_fast_detect: image %dx%d exceeds 2^%d pixels", w, h, raster_bits);
+        return AV_E_INVALID;
+    }
+    const int64_t n_wg = (int64_t)((w + TW - 1) / TW) * ((h + TH - 1) / TH) * 8 * ((n_img + 7) / 8);
+    if (n_wg * 256 > 0xFFFFFFFFll) {                       // a launch holds fewer than 2^32 threads
+        av_set_error("av_fast_detect: %d images of %dx%d are more than one launch holds (%lld workgroups)", n_img, w, h, (long long)n_wg);
         return AV_E_INVALID;
     }
     FastArgs a;
@@ -326,7 +334,7 @@ int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, in
     if (src.img) { a.img = src.img; a.img_stride = src.img_stride; a.img_pitch = w; a.border = 0; }
     else { a.img = src.pyr + g->off[0] + (size_t)AV_PYR_BORDER * g->pitch[0] + AV_PYR_BORDER; a.img_stride = src.pyr_stride; a.img_pitch = g->pitch[0]; a.border = AV_PYR_BORDER; }
     a.mask = mask; a.mask_stride = mask_stride;
-    a.w = w; a.h = h; a.threshold = threshold;
+    a.w = w; a.h = h; a.threshold = threshold; a.rbits = raster_bits;
     a.kp = kp; a.count = count; a.cap = cap;
     a.tile_kp = tile_kp; a.tile_count = tile_count; a.overflow = overflow; a.stat_stride = stat_stride;
     const int tx = (w + TW - 1) / TW, ty = (h + TH - 1) / TH;
@@ -343,16 +351,37 @@ int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, in
     return AV_OK;
 }
 
-AV_EXPORT int av_fast_detect(const uint8_t* img_dev, int64_t img_stride, const uint8_t* mask_dev, int64_t mask_stride,
-                             int n_img, int w, int h, int threshold, uint32_t* kp_dev, int32_t* count_dev, int cap,
-                             void* stream)
+namespace {
+
+int fast_detect_impl(const uint8_t* img_dev, int64_t img_stride, const uint8_t* mask_dev, int64_t mask_stride,
+                     int n_img, int w, int h, int threshold, int raster_bits, uint32_t* kp_dev, int32_t* count_dev, int cap, void* stream)
 {
     if (!img_dev || !kp_dev || !count_dev || cap <= 0 || n_img < 0 || w < 7 || h < 7 || img_stride < (int64_t)w * h) {
         av_set_error("av_fast_detect: bad arguments");
         return AV_E_INVALID;
     }
+    if ((int64_t)w * h > ((int64_t)1 << raster_bits)) {     // before anything is enqueued
+        av_set_error("av_fast_detect: image %dx%d exceeds 2^%d pixels", w, h, raster_bits);
+        return AV_E_INVALID;
+    }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipMemsetAsync(count_dev, 0, sizeof(int) * (size_t)n_img, st));
-    return av_launch_fast(ImgView{nullptr, 0, img_dev, img_stride, nullptr}, nullptr, mask_dev, mask_stride, n_img, w, h, threshold, kp_dev, count_dev, cap,
-                          nullptr, nullptr, nullptr, 0, st);
+    return av_launch_fast(ImgView{nullptr, 0, img_dev, img_stride, nullptr}, nullptr, mask_dev, mask_stride, n_img, w, h, threshold, raster_bits,
+                          kp_dev, count_dev, cap, nullptr, nullptr, nullptr, 0, st);
+}
+
+}  // namespace
+
+AV_EXPORT int av_fast_detect(const uint8_t* img_dev, int64_t img_stride, const uint8_t* mask_dev, int64_t mask_stride,
+                             int n_img, int w, int h, int threshold, uint32_t* kp_dev, int32_t* count_dev, int cap,
+                             void* stream)
+{
+    return fast_detect_impl(img_dev, img_stride, mask_dev, mask_stride, n_img, w, h, threshold, AV_KP_RASTER_BITS, kp_dev, count_dev, cap, stream);
+}
+
+AV_EXPORT int av_fast_detect_wide(const uint8_t* img_dev, int64_t img_stride, const uint8_t* mask_dev, int64_t mask_stride,
+                                  int n_img, int w, int h, int threshold, uint32_t* kp_dev, int32_t* count_dev, int cap,
+                                  void* stream)
+{
+    return fast_detect_impl(img_dev, img_stride, mask_dev, mask_stride, n_img, w, h, threshold, AV_KP_RASTER_BITS_WIDE, kp_dev, count_dev, cap, stream);
 }

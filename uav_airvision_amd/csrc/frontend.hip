@@ -44,6 +44,7 @@ struct FeDev {
     int NT;          // capacity of tracker work lists = MAXF
     int CC;          // capacity of the candidate list = max(max_corners, C * gmax)
     int cell_cap;    // capacity of one cell's FAST list
+    int rbits;       // raster bits of the packed keypoint words (av_common.h): fixed at creation, 19 up to 2^19 pixels, else 24
     int NSORT;       // pow2 >= C * (gmax + gmin)
     CamModel cam0, cam1;
     double R0to1[9], E[9], I3[9];
@@ -264,6 +265,7 @@ __global__ __launch_bounds__(256) void select_kernel(FeDev d)
     {
         __shared__ int tmax;
         const int nt = d.n_tiles;
+        const uint32_t rmask = (1u << d.rbits) - 1u;
         constexpr int BK = 32, BU = 5;
         if (threadIdx.x == 0) tmax = 0;
         for (int c = threadIdx.x; c < d.C; c += NTB) ccnt[c] = 0;
@@ -284,7 +286,7 @@ __global__ __launch_bounds__(256) void select_kernel(FeDev d)
                 }
 #pragma unroll
                 for (int u = 0; u < BU; ++u) {
-                    const uint32_t raster = AV_KP_RASTER_MASK - (word[u] & AV_KP_RASTER_MASK);
+                    const uint32_t raster = rmask - (word[u] & rmask);
                     y[u] = (int)(raster / (uint32_t)d.w); x[u] = (int)(raster % (uint32_t)d.w);
                     // detect(img, mask) drops keypoints on masked pixels AFTER the non-max suppression (fast.hip header): the mask
                     // byte is read here, for the few thousand survivors, instead of for every pixel inside the detector
@@ -368,7 +370,8 @@ __global__ __launch_bounds__(256) void select_kernel(FeDev d)
     const int total = off[d.C];
     for (int i = threadIdx.x; i < total; i += NTB) {
         const size_t o = (size_t)s * d.CC + i;
-        uint32_t raster = AV_KP_RASTER_MASK - (d.cand_key[o] & AV_KP_RASTER_MASK);
+        const uint32_t rmask = (1u << d.rbits) - 1u;
+        uint32_t raster = rmask - (d.cand_key[o] & rmask);
         float y = (float)(raster / (uint32_t)d.w), x = (float)(raster % (uint32_t)d.w);
         d.cand_p0[2 * o] = x; d.cand_p0[2 * o + 1] = y;
         float ix, iy;
@@ -883,7 +886,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     //  the LK launches slow down by more than the detector's time; profiles/r05/README.md)
     if (!frames) {                             // (frame store: FAST ran when the frame was uploaded)
         Span sp(fe, 2, st);
-        if ((rc = av_launch_fast(cur0, &fe->geom, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold, nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, st))) return rc;
+        if ((rc = av_launch_fast(cur0, &fe->geom, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold, d.rbits, nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, st))) return rc;
     }
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(select_kernel, dim3(S), dim3(256), sizeof(int) * (3 * d.C + 1 + d.n_tiles + 1), st, d);
@@ -910,6 +913,10 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
 AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, int device, av_frontend** out)
 {
     if (!cfg || !out || n_streams <= 0) { av_set_error("av_frontend_create: bad arguments"); return AV_E_INVALID; }
+    if (cfg->width <= 0 || cfg->height <= 0 || (int64_t)cfg->width * cfg->height > AV_MAX_IMAGE_PIXELS) {
+        av_set_error("av_frontend_create: the engine takes images of 1 .. AV_MAX_IMAGE_PIXELS = %d pixels (%d x %d)", AV_MAX_IMAGE_PIXELS, cfg->width, cfg->height);
+        return AV_E_INVALID;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { av_set_error("av_frontend_create: no HIP device visible"); return AV_E_NODEVICE; }
     if (device < 0 || device >= ndev) { av_set_error("av_frontend_create: device %d out of range (%d visible)", device, ndev); return AV_E_INVALID; }
@@ -951,8 +958,11 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     d.gmin = cfg->grid_min_feature_num; d.gmax = cfg->grid_max_feature_num;
     d.MAXF = C * d.gmax; d.NT = d.MAXF;
     d.CC = cfg->max_corners > C * d.gmax ? cfg->max_corners : C * d.gmax;
-    d.cell_cap = (d.gh * d.gw) / 4 + 64;
+    // a cell's list holds every corner the cell can have -- strict 3 x 3 maxima: at most one per 2 x 2 block, so the bound grows with the
+    // cell's area, whatever the image size -- unless the candidate list (max_corners) is shorter than that
+    d.cell_cap = (d.gh * d.gw) / 4 + (d.gh + d.gw) / 4 + 64;
     if (d.cell_cap > d.CC) d.cell_cap = d.CC;
+    d.rbits = av_kp_raster_bits(w, h);
     int ns = 2; while (ns < C * (d.gmax + d.gmin)) ns <<= 1;
     d.NSORT = ns;
     if (ns > 4096) { av_set_error("av_frontend_create: grid_num*(grid_max+grid_min) = %d exceeds 4096", C * (d.gmax + d.gmin)); delete fe; return AV_E_INVALID; }
@@ -978,6 +988,10 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     A(d.cur_id, S * d.NT) A(d.cur_life, S * d.NT) A(d.cur_p0, 2 * S * d.NT) A(d.cur_p1, 2 * S * d.NT) A(d.cur_cell, S * d.NT)
     A(d.cell_kp, (size_t)S * C * d.cell_cap)
     av_fast_tiles(w, h, &d.n_tiles, &d.tile_cap);
+    if (sizeof(int) * (size_t)(3 * C + 1 + d.n_tiles + 1) + 64 > 64 * 1024) {      // select_kernel's LDS; not reached by an image every pyramid level of which is > 16 pixels high
+        av_set_error("av_frontend_create: %d x %d has %d detector tiles, more than the selection kernel's LDS holds", w, h, d.n_tiles);
+        av_frontend_destroy(fe); return AV_E_INVALID;
+    }
     A(d.tile_kp, (size_t)S * d.n_tiles * d.tile_cap) A(d.tile_count, (size_t)S * d.n_tiles)
     if ((rc = dev_alloc(fe, &d.mask, (size_t)S * w * h, 1))) { av_frontend_destroy(fe); return rc; }
     A(d.cand_key, (size_t)S * d.CC) A(d.cand_p0, 2 * (size_t)S * d.CC) A(d.cand_init, 2 * (size_t)S * d.CC) A(d.cand_p1, 2 * (size_t)S * d.CC)
@@ -1251,7 +1265,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
                                            fe->cfg.clahe_tiles_x, fe->cfg.clahe_tiles_y, fe->fs_lut, cs, u.idx_d))) return rc;
     if ((rc = av_launch_pyramid(fs.img, fs.img + hw, (int64_t)(2 * hw), n, 2, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0, u.idx_d))) return rc;
     fs.l0_in_place = !wrote_l0;
-    if ((rc = av_launch_fast(store_view(fe, 0, u.idx_d), &fe->geom, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold,
+    if ((rc = av_launch_fast(store_view(fe, 0, u.idx_d), &fe->geom, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold, d.rbits,
                              nullptr, nullptr, 0, fs.tile_kp, fs.tile_count, nullptr, 0, cs))) return rc;
     AV_HIP(hipEventRecord(u.done, cs));
     AV_HIP(hipEventRecord(fs.uploaded, cs));

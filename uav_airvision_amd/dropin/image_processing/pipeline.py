@@ -17,7 +17,7 @@ _feature_msg = namedtuple('feature_msg', ['timestamp', 'features'])
 
 
 class ImageProcessingPipeline(object):
-    def __init__(self, config, device=0, max_corners=8192):
+    def __init__(self, config, device=0, max_corners=None):
         self.config = config
         self.prev_cam0_msg = None
         self._engine = FrontendEngine(config, n_streams=1, device=device, max_corners=max_corners)

@@ -13,12 +13,20 @@ import torch
 from . import _native as N
 
 
-def pack_frontend_config(config, max_corners=8192):
+def default_max_corners(width, height):
+    """Capacity for the FAST corners of one image when the caller names none: 8192 at 752 x 480 and below, and as many more as the
+    image has more pixels (a first frame keeps every corner, and at a given corner density their number grows with the area)."""
+    return max(8192, -(-8192 * int(width) * int(height) // (752 * 480)))
+
+
+def pack_frontend_config(config, max_corners=None):
     """Build the packed av_frontend_config from a reference-style config object.  The
     extrinsics-derived matrices are computed with numpy exactly as the reference does
-    (imu_processor.py:10-16, stereo_matcher.py:47,90-91,103-104)."""
+    (imu_processor.py:10-16, stereo_matcher.py:47,90-91,103-104).  max_corners None: default_max_corners of the image size."""
     c = N.FrontendConfig()
     w, h = [int(v) for v in config.cam0_resolution]
+    if max_corners is None:
+        max_corners = default_max_corners(w, h)
     c.width, c.height = w, h
     c.grid_row, c.grid_col = int(config.grid_row), int(config.grid_col)
     c.grid_min_feature_num = int(config.grid_min_feature_num)
@@ -76,8 +84,10 @@ RANSAC_COUNT_NAMES = ('after_ransac', 'cam0_set', 'cam1_set', 'path')
 
 
 class FrontendEngine(object):
-    def __init__(self, config, n_streams=1, device=0, max_corners=8192, inputs_persist=False):
-        """inputs_persist: promise that the cuda tensors handed to `step` stay unmodified until the NEXT step has run
+    def __init__(self, config, n_streams=1, device=0, max_corners=None, inputs_persist=False):
+        """The image size is config.cam0_resolution: any width x height of up to AV_MAX_IMAGE_PIXELS = 2^24 pixels.  max_corners:
+        capacity for the FAST corners of one image (None: 8192 at 752 x 480, scaled by the pixel count above that).
+        inputs_persist: promise that the cuda tensors handed to `step` stay unmodified until the NEXT step has run
         (AV_FE_INPUTS_PERSIST, include/airvision.h): pyramid level 0 is then read in place instead of being copied.  The engine
         keeps a reference to the last cam0 tensor, so dropping yours is fine; overwriting it in place is not.  `step_host`
         always works in place on the library's own staging slots.  Same results either way."""

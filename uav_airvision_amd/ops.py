@@ -82,28 +82,57 @@ def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, next_pts, winSize=(15
     return d_next.cpu().numpy(), d_status.cpu().numpy().reshape(-1, 1), None
 
 
+KP_RASTER_BITS, KP_RASTER_BITS_WIDE = 19, 24         # av_fast_detect / av_fast_detect_wide (include/airvision.h)
+
+
+def kp_raster_bits(w, h):
+    """Raster bits of the keypoint words of a w x h image: the narrow format wherever it fits, so that sizes up to 2^19 pixels go
+    through av_fast_detect as they always did."""
+    if w * h > N.AV_MAX_IMAGE_PIXELS:
+        raise ValueError('fast_detect: %d x %d exceeds AV_MAX_IMAGE_PIXELS = 2^24 pixels' % (w, h))
+    return KP_RASTER_BITS if w * h <= (1 << KP_RASTER_BITS) else KP_RASTER_BITS_WIDE
+
+
+def pack_keypoints(x, y, score, w, bits):
+    """(x, y, score) -> packed words uint32: score << bits | (2^bits - 1 - (y * w + x))."""
+    raster = np.asarray(y, np.int64) * int(w) + np.asarray(x, np.int64)
+    score = np.asarray(score, np.int64)
+    if raster.size and (raster.min() < 0 or raster.max() >= (1 << bits) or score.min() < 0 or (score.max() << bits) >= (1 << 32)):
+        raise ValueError('pack_keypoints: raster or score outside the %d-bit format' % bits)
+    return ((score << bits) | (((1 << bits) - 1) - raster)).astype(np.uint32)
+
+
+def unpack_keypoints(words, w, bits):
+    """Packed words of either format -> (x, y, score) int arrays in raster order."""
+    words = np.asarray(words).view(np.uint32)
+    m = np.uint32((1 << bits) - 1)
+    raster = (m - (words & m)).astype(np.int64)
+    score = (words >> np.uint32(bits)).astype(np.int32)
+    order = np.argsort(raster, kind='stable')
+    raster, score = raster[order], score[order]
+    return (raster % w).astype(np.int32), (raster // w).astype(np.int32), score
+
+
 def fast_detect(img, threshold, mask=None, cap=1 << 16, device=0):
     """cv2.FastFeatureDetector_create(threshold).detect(img, mask): (x, y, response) int arrays in
-    raster order (reference: pipeline.py:23-25, feature_initializer.py:52, feature_adder.py:64)."""
+    raster order (reference: pipeline.py:23-25, feature_initializer.py:52, feature_adder.py:64).  Images of up to 2^19 pixels go
+    through av_fast_detect, larger ones (up to AV_MAX_IMAGE_PIXELS) through av_fast_detect_wide; the result is decoded either way."""
     dev = _dev(device)
     t = torch.as_tensor(np.ascontiguousarray(img, dtype=np.uint8)).to(dev)
     h, w = t.shape
+    bits = kp_raster_bits(w, h)
+    entry = N.lib().av_fast_detect if bits == KP_RASTER_BITS else N.lib().av_fast_detect_wide
     m = None if mask is None else torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8)).to(dev)
     kp = torch.empty(cap, dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(device):
-        N.check(N.lib().av_fast_detect(N.dptr(t), w * h, None if m is None else N.dptr(m), w * h, 1, w, h, int(threshold),
-                                       N.dptr(kp), N.dptr(cnt), cap, N.current_stream()))
+        N.check(entry(N.dptr(t), w * h, None if m is None else N.dptr(m), w * h, 1, w, h, int(threshold),
+                      N.dptr(kp), N.dptr(cnt), cap, N.current_stream()))
         torch.cuda.synchronize()
     n = int(cnt.item())
     if n > cap:
         raise N.AirvisionError(N.AV_E_CAPACITY, 'FAST found %d keypoints, capacity %d' % (n, cap))
-    words = kp[:n].cpu().numpy().view(np.uint32)
-    raster = (np.uint32((1 << 19) - 1) - (words & np.uint32((1 << 19) - 1))).astype(np.int64)
-    score = (words >> np.uint32(19)).astype(np.int32)
-    order = np.argsort(raster, kind='stable')
-    raster, score = raster[order], score[order]
-    return (raster % w).astype(np.int32), (raster // w).astype(np.int32), score
+    return unpack_keypoints(kp[:n].cpu().numpy(), w, bits)
 
 
 def _points_op(fn_name, pts_in, extra, device):

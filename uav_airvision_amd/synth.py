@@ -63,11 +63,11 @@ def _so3_log(R):
     return w * th / (2 * np.sin(th))
 
 
-def _undistorted_rays(intr, dist, iters=25):
+def _undistorted_rays(intr, dist, iters=25, width=W, height=H):
     """Normalised undistorted coordinates of every pixel centre (radtan inverse, fixed point)."""
     fx, fy, cx, cy = intr
     k1, k2, p1, p2 = dist
-    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    u, v = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
     x0 = (u - cx) / fx; y0 = (v - cy) / fy
     x, y = x0.copy(), y0.copy()
     for _ in range(iters):
@@ -77,6 +77,19 @@ def _undistorted_rays(intr, dist, iters=25):
         dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
         x = (x0 - dx) * ic; y = (y0 - dy) * ic
     return np.stack([x, y, np.ones_like(x)], axis=-1)
+
+
+def scaled_config(config, width, height):
+    """`config` (modified in place and returned) for the same stereo rig with width x height sensors: both resolutions set, both
+    cameras' intrinsics scaled by width / (the old width) horizontally and height / (the old height) vertically.  The distortion
+    coefficients act on normalised coordinates and stay."""
+    for cam in ('cam0', 'cam1'):
+        w0, h0 = [float(v) for v in getattr(config, cam + '_resolution')]
+        sx, sy = width / w0, height / h0
+        fx, fy, cx, cy = [float(v) for v in getattr(config, cam + '_intrinsics')]
+        setattr(config, cam + '_intrinsics', np.array([fx * sx, fy * sy, cx * sx, cy * sy]))
+        setattr(config, cam + '_resolution', np.array([int(width), int(height)]))
+    return config
 
 
 class SyntheticStream(object):
@@ -89,8 +102,11 @@ class SyntheticStream(object):
 
     def __init__(self, config, seed=0, n_frames=20, t0=100.0, lead_in=1.0, motion_scale=1.0,
                  pixel_noise=1.0, texture=None, render=True, rest=0.0, tex_offset=(0.0, 0.0),
-                 moving_region=None, moving_amplitude=0.15, moving_rate=1.5, contrast=1.0, brightness_offset=0.0):
-        """contrast, brightness_offset (defaults 1, 0: the renders are what they always were): every rendered grey value goes to
+                 moving_region=None, moving_amplitude=0.15, moving_rate=1.5, contrast=1.0, brightness_offset=0.0,
+                 width=None, height=None):
+        """width, height (default: config.cam0_resolution, 752 x 480 in ConfigEuRoC): the size of the rendered images.  The rays go
+        through the config's intrinsics, so a config for another size carries intrinsics scaled with it (`scaled_config`).
+        contrast, brightness_offset (defaults 1, 0: the renders are what they always were): every rendered grey value goes to
         mean + contrast * (value - mean) + brightness_offset, mean being the texture's mean grey value, before sensor noise and
         quantisation -- a dim or flat scene, the case config.use_clahe is for.  `frame` and `frame_torch` apply the same mapping.
         moving_region = (x0, y0, x1, y1) in pixels (default none: the renders are what they always were): inside that rectangle of
@@ -99,6 +115,9 @@ class SyntheticStream(object):
         gates) that moves against the ego-motion from frame to frame: an independently moving object, the case the tracker's
         outlier rejection (config.use_ransac) is for."""
         self.config = config
+        res = getattr(config, 'cam0_resolution', (W, H))
+        self.width = int(res[0] if width is None else width)
+        self.height = int(res[1] if height is None else height)
         self.seed = int(seed)
         self.n_frames = int(n_frames)
         self.t0 = float(t0)
@@ -126,8 +145,8 @@ class SyntheticStream(object):
         e1 = np.cross(self.wall_n, [0., 0., 1.]); self.wall_e1 = e1 / np.linalg.norm(e1)
         self.wall_e2 = np.cross(self.wall_n, self.wall_e1)
         if render:
-            self.rays0 = _undistorted_rays(config.cam0_intrinsics, config.cam0_distortion_coeffs)
-            self.rays1 = _undistorted_rays(config.cam1_intrinsics, config.cam1_distortion_coeffs)
+            self.rays0 = _undistorted_rays(config.cam0_intrinsics, config.cam0_distortion_coeffs, width=self.width, height=self.height)
+            self.rays1 = _undistorted_rays(config.cam1_intrinsics, config.cam1_distortion_coeffs, width=self.width, height=self.height)
         self.imu = self._make_imu()
 
     # ---- trajectory ------------------------------------------------------------------------
