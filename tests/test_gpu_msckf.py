@@ -505,12 +505,19 @@ def test_overflow_pool_exhaustion_stops_the_stream_with_a_capacity_error(cfg, mo
     bat.close()
 
 
-def test_blank_frame_drops_every_track_at_once(cfg):
+@pytest.mark.parametrize('store', ['device', 'host'])
+def test_blank_frame_drops_every_track_at_once(cfg, store, monkeypatch):
     """A blank / blurred frame: the feature message is empty, so every live track is lost in the same frame and the
     lost-feature candidates reserve far more rows than rows_cap (here ~3-4 k against 2048).  The reference handles any
     number (msckf.py:614-676: gate in map order, stop after > 1500 stacked rows); the device-resident batch gives such a
     stream rows from the overflow pool all streams share (the host-bookkeeping path gates first and stores only the stacked
-    features second).  Must equal the numpy oracle on every frame, before, at and after."""
+    features second).  Must equal the numpy oracle on every frame, before, at and after.
+    store='host' (AV_MSCKF_STORE=host) is the only GPU test that takes the host chain's synchronous fallback (b_blocks_and_update:
+    a stream's candidates outgrow rows_cap), at frames 17 and 18."""
+    if store == 'host':
+        monkeypatch.setenv('AV_MSCKF_STORE', 'host')
+    else:
+        monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
     from oracle.msckf_np import OracleMSCKF
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.synth import SyntheticFeatureStream, feature_msg_t
@@ -519,6 +526,7 @@ def test_blank_frame_drops_every_track_at_once(cfg):
                SyntheticFeatureStream(cfg, seed=92, n_frames=n_frames, n_features=60)]
     S = len(streams)
     bat = BatchedMSCKF(cfg, S, rows_cap=2048)
+    assert bat.device_resident() == (store == 'device')
     oras = [OracleMSCKF(cfg) for _ in streams]
     its = [iter(s.imu) for s in streams]
     pend = [next(it, None) for it in its]

@@ -140,6 +140,27 @@ struct TriArgs {
     const int* list; const int* n_list_dev; int fs_stride;
     const int* f_mslot; double* meta_pos; int* meta_init; int meta_stride;
 };
+// cam0 -> cam1 as the records carry it (TriArgs, FeatArgs, DevArgs), from the row-major 4x4 transform of the configuration
+inline void unpack_T01(const double* T01, double R01[9], double t01[3])
+{
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R01[r * 3 + c] = T01[r * 4 + c]; t01[r] = T01[r * 4 + 3]; }
+}
+// the optimiser options of the triangulation (TriArgs, DevArgs) from the caller's opt5 = huber, precision, damping, outer_max, inner_max
+template <typename Rec>
+inline void unpack_opt5(const double* opt5, Rec& a)
+{
+    a.huber = opt5[0]; a.precision = opt5[1]; a.damping = opt5[2]; a.outer_max = (int)opt5[3]; a.inner_max = (int)opt5[4];
+}
+// A zeroed TriArgs with what does not depend on the features: the camera states (cam_stride slots per stream, 0: single filter),
+// the extrinsics and the optimiser options.  The caller adds the observation CSR, the outputs and its list / stream / table fields.
+inline TriArgs tri_args_base(const double* cam_q, const double* cam_p, int cam_stride, const double* T01, const double* opt5)
+{
+    TriArgs a; memset(&a, 0, sizeof(a));
+    a.cam_q = cam_q; a.cam_p = cam_p; a.cam_stride = cam_stride;
+    unpack_T01(T01, a.R01, a.t01);
+    unpack_opt5(opt5, a);
+    return a;
+}
 
 __device__ __forceinline__ void solve3(const double A[9], const double b[3], double x[3])
 {
@@ -2446,11 +2467,8 @@ AV_EXPORT int av_msckf_triangulate(av_msckf* c, int n_feat, const int32_t* obs_o
     }
     if (max_views > 64) { av_set_error("av_msckf_triangulate: %d views per feature exceed one wavefront (64)", max_views); return AV_E_CAPACITY; }
     if (n_feat == 0) return AV_OK;
-    TriArgs a; memset(&a, 0, sizeof(a));
-    a.n_feat = n_feat; a.obs_off = obs_off_dev; a.obs_cam = obs_cam_dev; a.obs_z = obs_z_dev; a.cam_q = cam_q_dev; a.cam_p = cam_p_dev;
-    a.feat_stream = nullptr; a.cam_stride = 0;
-    for (int r = 0; r < 3; ++r) { for (int cc = 0; cc < 3; ++cc) a.R01[r * 3 + cc] = T_cam0_cam1_rowmajor44[r * 4 + cc]; a.t01[r] = T_cam0_cam1_rowmajor44[r * 4 + 3]; }
-    a.huber = opt5[0]; a.precision = opt5[1]; a.damping = opt5[2]; a.outer_max = (int)opt5[3]; a.inner_max = (int)opt5[4];
+    TriArgs a = tri_args_base(cam_q_dev, cam_p_dev, 0, T_cam0_cam1_rowmajor44, opt5);
+    a.n_feat = n_feat; a.obs_off = obs_off_dev; a.obs_cam = obs_cam_dev; a.obs_z = obs_z_dev;
     a.out_pos = pos_dev; a.out_valid = valid_dev;
     AV_HIP(hipSetDevice(c->device));
     hipLaunchKernelGGL(triangulate_kernel, dim3((n_feat + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
@@ -2477,7 +2495,8 @@ AV_EXPORT int av_msckf_feature_blocks(av_msckf* c, int n_feat, int n_cam, int ma
     a.n_feat = n_feat; a.n_cam = n_cam; a.ld = c->ld;
     a.obs_off = obs_off_dev; a.obs_cam = obs_cam_dev; a.obs_z = obs_z_dev; a.pos = pos_dev; a.dof = dof_dev; a.row_off = row_off_dev;
     a.cam_q = cam_q_dev; a.cam_p = cam_p_dev; a.cam_qn = cam_qn_dev; a.cam_pn = cam_pn_dev; a.P = c->P; a.chi2 = c->chi2;
-    for (int r = 0; r < 3; ++r) { for (int cc = 0; cc < 3; ++cc) a.R01[r * 3 + cc] = T_cam0_cam1_rowmajor44[r * 4 + cc]; a.t01[r] = T_cam0_cam1_rowmajor44[r * 4 + 3]; a.gravity[r] = gravity[r]; }
+    unpack_T01(T_cam0_cam1_rowmajor44, a.R01, a.t01);
+    for (int i = 0; i < 3; ++i) a.gravity[i] = gravity[i];
     a.obs_noise = obs_noise; a.Hout = c->Hblk; a.rout = c->rblk; a.gamma = gamma_dev; a.pass = pass_dev; a.Mmax = max_obs;
     a.feat_stream = nullptr; a.stream_ncam = nullptr; a.stream_gravity = nullptr; a.cam_stride = 0; a.p_stride = a.h_stride = a.r_stride = 0;
     a.feat_list = nullptr; a.prof = nullptr; a.zero_fill = 1; a.tri_idx = nullptr; a.tri_pos = nullptr; a.tri_valid = nullptr;

@@ -389,6 +389,37 @@ struct av_msckf_batch {
 
 namespace {
 
+// ---- the kernels' argument records, the part every caller of a batch shares (the device-resident filter, the host-bookkeeping chain
+//      and its synchronous fallback); each caller adds what is its own.  TriArgs: tri_args_base (msckf.hip).
+
+// A zeroed FeatArgs with the camera states, the covariance, the block buffers, their strides and the constants of the batch.  The caller
+// adds the observation CSR, the per-feature arrays (pos, dof, row_off, gamma, pass), and how a feature finds its stream and its gravity.
+inline FeatArgs b_feat_args(const av_msckf_batch* b, bool cut1500, const double* cam_q, const double* cam_p, const double* cam_qn)
+{
+    FeatArgs a; memset(&a, 0, sizeof(a));
+    a.cam_q = cam_q; a.cam_p = cam_p; a.cam_qn = cam_qn; a.cam_pn = cam_p;      // position_null aliases position (msckf.py:403-404)
+    a.ld = b->ld; a.P = b->P; a.chi2 = b->chi2_dev;
+    unpack_T01(b->T01, a.R01, a.t01);                       // (gravity stays zero: every stream has its own, stream_gravity)
+    a.obs_noise = b->obs_noise; a.Hout = b->Hblk; a.rout = b->rblk;
+    a.cam_stride = b->cam_slots; a.p_stride = b->pstride; a.h_stride = b->hstride; a.r_stride = b->rstride;
+    // camera pruning stacks only features seen from BOTH removed cameras and factorises exactly those 12 columns, so every
+    // column the update gathers is written by the feature itself: no need to clear 141-wide rows (5.6 KB per feature)
+    a.zero_fill = cut1500 ? 1 : 0;
+    return a;
+}
+
+// A zeroed UpdArgs with the work buffers of stream s and their strides.  The caller adds n, m, nc, mode, its block lists and prof.
+inline UpdArgs b_upd_args(const av_msckf_batch* b, int s)
+{
+    UpdArgs u; memset(&u, 0, sizeof(u));
+    u.P = b->P + (size_t)s * b->pstride; u.ld = b->ld;
+    u.Hsrc = b->Hblk + (size_t)s * b->hstride; u.rsrc = b->rblk + (size_t)s * b->rstride;
+    u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
+    u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
+    u.Sbuf = b->scratch + (size_t)s * b->pstride;          // free between the camera removals that use it
+    return u;
+}
+
 // A feature selected for a batched kernel: its observations are a slice [first, first+n) of the pools
 // (no per-feature heap allocation; the prune path builds ~300 of these per stream and frame).
 struct ObsPool { std::vector<int> cam; std::vector<const double*> z; };
@@ -619,11 +650,9 @@ int b_tri_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, std::vector<char
     }
     if ((rc = b->d_tobs_off.upload(off, stm)) || (rc = b->d_tobs_cam.commit((size_t)off[nf], stm)) || (rc = b->d_tobs_z.commit((size_t)off[nf] * 4, stm)) ||
         (rc = b->d_tfs.upload(fs, stm)) || (rc = b->d_tpos.reserve((size_t)nf * 3, true)) || (rc = b->d_tvalid.reserve(nf, true))) return rc;
-    TriArgs a; memset(&a, 0, sizeof(a));
-    a.n_feat = nf; a.obs_off = b->d_tobs_off.p; a.obs_cam = b->d_tobs_cam.p; a.obs_z = b->d_tobs_z.p; a.cam_q = b->d_cam_q.p; a.cam_p = b->d_cam_p.p;
-    a.feat_stream = b->d_tfs.p; a.cam_stride = b->cam_slots;
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) a.R01[r * 3 + c] = b->T01[r * 4 + c]; a.t01[r] = b->T01[r * 4 + 3]; }
-    a.huber = b->opt5[0]; a.precision = b->opt5[1]; a.damping = b->opt5[2]; a.outer_max = (int)b->opt5[3]; a.inner_max = (int)b->opt5[4];
+    TriArgs a = tri_args_base(b->d_cam_q.p, b->d_cam_p.p, b->cam_slots, b->T01, b->opt5);
+    a.n_feat = nf; a.obs_off = b->d_tobs_off.p; a.obs_cam = b->d_tobs_cam.p; a.obs_z = b->d_tobs_z.p;
+    a.feat_stream = b->d_tfs.p;
     a.out_pos = b->d_tpos.p; a.out_valid = b->d_tvalid.p;
     hipLaunchKernelGGL(triangulate_kernel, dim3((nf + 3) / 4), dim3(256), 0, stm, a);
     AV_LAUNCH_CHECK();
@@ -739,20 +768,10 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
     if ((rc = b->d_obs_off.upload(off, stm)) || (rc = b->d_obs_cam.commit((size_t)off[nf], stm)) || (rc = b->d_obs_z.commit((size_t)off[nf] * 4, stm)) ||
         (rc = b->d_fstream.upload(fs, stm)) || (rc = b->d_dof.upload(dof, stm)) || (rc = b->d_rowoff.upload(rowoff, stm)) ||
         (rc = b->d_pos.commit((size_t)nf * 3, stm)) || (rc = b->d_gamma.ensure(nf)) || (rc = b->d_pass.ensure(nf))) return rc;
-    FeatArgs a; memset(&a, 0, sizeof(a));
-    a.n_feat = nf; a.n_cam = 0; a.ld = b->ld;
+    FeatArgs a = b_feat_args(b, cut1500, b->d_cam_q.p, b->d_cam_p.p, b->d_cam_qn.p);
+    a.n_feat = nf; a.Mmax = maxobs; a.feat_stream = b->d_fstream.p; a.stream_ncam = b->d_ncam.p; a.stream_gravity = b->d_grav.p;
     a.obs_off = b->d_obs_off.p; a.obs_cam = b->d_obs_cam.p; a.obs_z = b->d_obs_z.p; a.pos = b->d_pos.p; a.dof = b->d_dof.p; a.row_off = b->d_rowoff.p;
-    a.cam_q = b->d_cam_q.p; a.cam_p = b->d_cam_p.p; a.cam_qn = b->d_cam_qn.p; a.cam_pn = b->d_cam_p.p;      // position_null aliases position
-    a.P = b->P; a.chi2 = b->chi2_dev;
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) a.R01[r * 3 + c] = b->T01[r * 4 + c]; a.t01[r] = b->T01[r * 4 + 3]; a.gravity[r] = 0; }
-    a.obs_noise = b->obs_noise; a.Hout = b->Hblk; a.rout = b->rblk; a.gamma = b->d_gamma.p; a.pass = b->d_pass.p; a.Mmax = maxobs;
-    a.feat_stream = b->d_fstream.p; a.stream_ncam = b->d_ncam.p; a.stream_gravity = b->d_grav.p; a.cam_stride = b->cam_slots;
-    a.p_stride = b->pstride; a.h_stride = b->hstride; a.r_stride = b->rstride; a.feat_list = nullptr;
-    a.tri_idx = nullptr; a.tri_pos = nullptr; a.tri_valid = nullptr;
-    a.prof = nullptr;
-    // camera pruning stacks only features seen from BOTH removed cameras and factorises exactly those 12 columns, so every
-    // column the update gathers is written by the feature itself: no need to clear 141-wide rows (5.6 KB per feature)
-    a.zero_fill = cut1500 ? 1 : 0;
+    a.gamma = b->d_gamma.p; a.pass = b->d_pass.p;
     auto launch_buckets = [&](const std::vector<int>& sel) -> int { return b_launch_buckets(b, a, refs, sel, maxobs, stm); };
     {
         std::vector<int> all(nf);
@@ -799,23 +818,19 @@ int b_blocks_and_update(av_msckf_batch* b, std::vector<FeatRef>& refs, const Obs
     int nmax = 0, ncinfo = 0, ninfo = 0, minfo = 0; bool any = false, any_info = false, any_qr = false;
     for (int s = 0; s < S; ++s) {
         UpdArgs& u = ua[s];
-        memset(&u, 0, sizeof(u));
-        u.m = stacked[s];
-        if (u.m == 0) continue;
+        memset(&u, 0, sizeof(u));                           // a stream without an update: m = 0, nothing else is read
+        if (stacked[s] == 0) continue;
         any = true;
         const BStream& T = b->st[s];
-        u.P = b->P + (size_t)s * b->pstride; u.n = T.n; u.ld = b->ld;
-        u.Hsrc = b->Hblk + (size_t)s * b->hstride; u.rsrc = b->rblk + (size_t)s * b->rstride;
+        const int n_blk = (int)br[s].size();
+        if (n_blk > 4 * UT) { b_fail_stream(b, s, AV_E_CAPACITY, "stream stacks %d blocks > %d in one update", n_blk, 4 * UT); stacked[s] = 0; continue; }
+        u = b_upd_args(b, s);
+        u.m = stacked[s]; u.n = T.n; u.n_blk = n_blk;
         u.blk_row = reinterpret_cast<const int*>((size_t)all_r.size());       // patched to device addresses below
-        u.n_blk = (int)br[s].size();
-        if (u.n_blk > 4 * UT) { b_fail_stream(b, s, AV_E_CAPACITY, "stream stacks %d blocks > %d in one update", u.n_blk, 4 * UT); u.m = 0; stacked[s] = 0; continue; }
         all_r.insert(all_r.end(), br[s].begin(), br[s].end()); all_l.insert(all_l.end(), bl[s].begin(), bl[s].end());
         col_off[s] = all_cols.size();
         for (size_t ci = 0; ci < used[s].size(); ++ci) if (used[s][ci]) for (int e = 0; e < 6; ++e) all_cols.push_back(IMU_DIM + 6 * (int)ci + e);
         u.nc = (int)(all_cols.size() - col_off[s]);
-        u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
-        u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
-        u.Sbuf = b->scratch + (size_t)s * b->pstride;          // free between the camera removals that use it
         u.mode = upd_info_form(u.m, u.nc) ? 1 : 0;
         if (u.mode) { any_info = true; if (u.nc > ncinfo) ncinfo = u.nc; if (T.n > ninfo) ninfo = T.n; if (u.m > minfo) minfo = u.m; continue; }
         any_qr = true;
@@ -1032,16 +1047,10 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
         (rc = b->d_fstream.upload(fs, stm)) || (rc = b->d_dof.upload(dof, stm)) || (rc = b->d_rowoff.upload(rowoff, stm)) ||
         (rc = b->d_pos.commit((size_t)nf * 3, stm)) || (rc = b->d_gamma.ensure(nf)) || (rc = b->d_pass.ensure(nf)) ||
         (rc = b->d_tri_idx.upload(tri_idx, stm)) || (rc = b->d_rbeg.upload(rbeg, stm))) return rc;
-    FeatArgs a; memset(&a, 0, sizeof(a));
-    a.n_feat = nf; a.n_cam = 0; a.ld = b->ld;
+    FeatArgs a = b_feat_args(b, cut1500, b->d_cam_q.p, b->d_cam_p.p, b->d_cam_qn.p);
+    a.n_feat = nf; a.Mmax = maxobs; a.feat_stream = b->d_fstream.p; a.stream_ncam = b->d_ncam.p; a.stream_gravity = b->d_grav.p;
     a.obs_off = b->d_obs_off.p; a.obs_cam = b->d_obs_cam.p; a.obs_z = b->d_obs_z.p; a.pos = b->d_pos.p; a.dof = b->d_dof.p; a.row_off = b->d_rowoff.p;
-    a.cam_q = b->d_cam_q.p; a.cam_p = b->d_cam_p.p; a.cam_qn = b->d_cam_qn.p; a.cam_pn = b->d_cam_p.p;      // position_null aliases position
-    a.P = b->P; a.chi2 = b->chi2_dev;
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) a.R01[r * 3 + c] = b->T01[r * 4 + c]; a.t01[r] = b->T01[r * 4 + 3]; a.gravity[r] = 0; }
-    a.obs_noise = b->obs_noise; a.Hout = b->Hblk; a.rout = b->rblk; a.gamma = b->d_gamma.p; a.pass = b->d_pass.p; a.Mmax = maxobs;
-    a.feat_stream = b->d_fstream.p; a.stream_ncam = b->d_ncam.p; a.stream_gravity = b->d_grav.p; a.cam_stride = b->cam_slots;
-    a.p_stride = b->pstride; a.h_stride = b->hstride; a.r_stride = b->rstride; a.feat_list = nullptr; a.prof = nullptr;
-    a.zero_fill = cut1500 ? 1 : 0;            // see b_blocks_and_update
+    a.gamma = b->d_gamma.p; a.pass = b->d_pass.p;
     a.tri_idx = b->d_tri_idx.p; a.tri_pos = b->d_tpos.p; a.tri_valid = b->d_tvalid.p;
     {
         std::vector<int> all(nf);
@@ -1051,14 +1060,8 @@ int b_chain_launch(av_msckf_batch* b, std::vector<FeatRef>& refs, const ObsPool&
     // ---- stacking on the device, then the back end for R rounds (streams that need fewer see m = 0)
     std::vector<UpdArgs> base(S);
     for (int s = 0; s < S; ++s) {
-        UpdArgs& u = base[s];
-        memset(&u, 0, sizeof(u));
-        const BStream& T = b->st[s];
-        u.P = b->P + (size_t)s * b->pstride; u.n = T.n; u.ld = b->ld;
-        u.Hsrc = b->Hblk + (size_t)s * b->hstride; u.rsrc = b->rblk + (size_t)s * b->rstride;
-        u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
-        u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
-        u.Sbuf = b->scratch + (size_t)s * b->pstride;
+        UpdArgs& u = base[s] = b_upd_args(b, s);
+        u.n = b->st[s].n;
         u.mode = dead[s] ? 2 : info_ok[s];      // 2: the stream takes no update in this phase (it was stopped above)
     }
     if ((rc = b->d_clist.upload(clist, stm)) || (rc = b->d_updbase.upload(base, stm)) || (rc = b->d_upd.ensure((size_t)(R > 0 ? R : 1) * S)) || (rc = b->d_blk_row.ensure(nf)) || (rc = b->d_blk_len.ensure(nf)) ||

@@ -114,11 +114,11 @@ int dev_reserve(av_msckf_batch* b, int cap)
     }
 #undef DA
 #undef DAF
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) A.R01[r * 3 + c] = b->T01[r * 4 + c]; A.t01[r] = b->T01[r * 4 + 3]; }
+    unpack_T01(b->T01, A.R01, A.t01);
     for (int i = 0; i < 4; ++i) A.noise[i] = b->noise[i];
     for (int i = 0; i < 5; ++i) A.cov0[i] = b->cov0[i];
     A.trans_thr = b->trans_thr; A.pos_std_thr = b->pos_std_thr;
-    A.huber = b->opt5[0]; A.precision = b->opt5[1]; A.damping = b->opt5[2]; A.outer_max = (int)b->opt5[3]; A.inner_max = (int)b->opt5[4];
+    unpack_opt5(b->opt5, A);
     A.Hblk = b->Hblk; A.rblk = b->rblk; A.hstride = b->hstride; A.rstride = b->rstride; A.chi2 = b->chi2_dev; A.obs_noise = b->obs_noise;
     A.gamma = d->gamma; A.pass = d->pass; A.updbase = d->updbase; A.upd = d->upd; A.cols = d->cols; A.cols_stride = 6 * b->cam_slots;
     A.blk_row = d->blk_row; A.blk_len = d->blk_len; A.stacked_out = d->stacked1; A.work = d->work;
@@ -144,27 +144,44 @@ int dev_reserve(av_msckf_batch* b, int cap)
     return AV_OK;
 }
 
-// per-stream constants of the update kernels (pointers into the group's work buffers); rebuilt when rows_cap changes
-// diagnostic stamp buffer of the update kernels (AV_DEV_UPROF=1), NULL otherwise
-unsigned long long* dev_uprof()
+// Diagnostic phase stamps (AV_DEV_FPROF, AV_DEV_UPROF): the first team or workgroup of a kernel writes clock ticks into a small device
+// buffer, the host reads them back after every 16th launch, which synchronises the stream (timing runs only).  One instance per
+// switch, built where it is first used: with the switch unset nothing is allocated and nothing ever waits.
+struct DevStamps {
+    unsigned long long* dev = nullptr;       // [32] on the device; NULL: the switch is unset
+    int calls = 0;
+    explicit DevStamps(bool on)
+    {
+        if (on && hipMalloc((void**)&dev, 256) == hipSuccess) { (void)hipMemset(dev, 0, 256); (void)hipStreamSynchronize(nullptr); } else dev = nullptr;
+    }
+    // call once behind every stamped launch; true: the stamps are in t (a read that fails prints nothing, the step's own checks report the error)
+    bool read(hipStream_t stm, unsigned long long t[32])
+    {
+        return dev && (++calls & 15) == 0 && hipStreamSynchronize(stm) == hipSuccess && hipMemcpy(t, dev, 256, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+};
+// "[label, 10 ns ticks] name t[1]-t[0]  name t[2]-t[1] ..." on stderr
+void print_stamps(const char* label, const unsigned long long* t, std::initializer_list<const char*> names)
 {
-    static unsigned long long* buf = [] { unsigned long long* p = nullptr; if (getenv("AV_DEV_UPROF") && hipMalloc((void**)&p, 256) == hipSuccess) (void)hipMemset(p, 0, 256); return p; }();
-    return buf;
+    char line[512];
+    int w = snprintf(line, sizeof(line), "[%s, 10 ns ticks]", label);
+    const char* sep = " ";
+    for (const char* nm : names) { w += snprintf(line + w, sizeof(line) - w, "%s%s %llu", sep, nm, t[1] - t[0]); ++t; sep = "  "; }
+    fprintf(stderr, "%s\n", line);
 }
+DevStamps& dev_uprof() { static DevStamps st(getenv("AV_DEV_UPROF") != nullptr); return st; }                                  // the dk_* and update kernels, stream 0
+DevStamps& dev_fprof_team() { static DevStamps st(getenv("AV_DEV_FPROF") != nullptr); return st; }                             // the pruning phase's feature kernel, team 0
+DevStamps& dev_fprof_long() { static DevStamps st(getenv("AV_DEV_FPROF") && atoi(getenv("AV_DEV_FPROF")) == 2); return st; }   // the long-track bucket, workgroup 0
+
+// per-stream constants of the update kernels (pointers into the group's work buffers); rebuilt when rows_cap changes
 int dev_upload_updbase(av_msckf_batch* b)
 {
     DevPath* d = b->dev;
     std::vector<UpdArgs> base((size_t)b->S);
     for (int s = 0; s < b->S; ++s) {
-        UpdArgs& u = base[s];
-        memset(&u, 0, sizeof(u));
-        u.P = b->P + (size_t)s * b->pstride; u.n = IMU_DIM; u.ld = b->ld;
-        u.Hsrc = b->Hblk + (size_t)s * b->hstride; u.rsrc = b->rblk + (size_t)s * b->rstride;
-        u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
-        u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
-        u.Sbuf = b->scratch + (size_t)s * b->pstride;
-        u.mode = 1;
-        if (s == 0) u.prof = dev_uprof();
+        UpdArgs& u = base[s] = b_upd_args(b, s);
+        u.n = IMU_DIM; u.mode = 1;
+        if (s == 0) u.prof = dev_uprof().dev;
     }
     AV_HIP(hipMemcpy(d->updbase, base.data(), sizeof(UpdArgs) * base.size(), hipMemcpyHostToDevice));
     d->A.rows_cap = b->rows_cap; d->A.pool_rows = (int)b_pool_rows(b, b->rows_cap); d->A.Hblk = b->Hblk; d->A.rblk = b->rblk; d->A.hstride = b->hstride; d->A.rstride = b->rstride;
@@ -230,31 +247,20 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
     const int worst = S * cap;
     if (ph == 1) {   // pruning phase, unfused form: triangulation of the listed features from the t_* CSR (= all their observations); the lost
                      // features' triangulation runs inside dk_begin
-        TriArgs t; memset(&t, 0, sizeof(t));
-        t.n_feat = 0; t.obs_off = ph == 0 ? A.f_off : A.t_off; t.obs_cam = ph == 0 ? A.obs_cam : A.t_obs_cam; t.obs_z = ph == 0 ? A.obs_z : A.t_obs_z;
-        t.cam_q = A.cam_q; t.cam_p = A.cam_p; t.feat_stream = nullptr; t.cam_stride = b->cam_slots;
-        for (int i = 0; i < 9; ++i) t.R01[i] = A.R01[i];
-        for (int i = 0; i < 3; ++i) t.t01[i] = A.t01[i];
-        t.huber = b->opt5[0]; t.precision = b->opt5[1]; t.damping = b->opt5[2]; t.outer_max = (int)b->opt5[3]; t.inner_max = (int)b->opt5[4];
+        TriArgs t = tri_args_base(A.cam_q, A.cam_p, b->cam_slots, b->T01, b->opt5);
+        t.obs_off = A.t_off; t.obs_cam = A.t_obs_cam; t.obs_z = A.t_obs_z;
         t.out_pos = A.f_pos; t.out_valid = A.f_valid;
-        t.list = A.tlist; t.n_list_dev = cnt + 5; t.fs_stride = A.FS;
-        if (ph == 1) { t.f_mslot = A.f_mslot; t.meta_pos = A.m_pos; t.meta_init = A.m_init; t.meta_stride = A.mcap; }
+        t.list = A.tlist; t.n_list_dev = cnt + 5; t.fs_stride = A.FS;      // (n_feat and feat_stream stay 0: the list is the device's, the stream is f / fs_stride)
+        t.f_mslot = A.f_mslot; t.meta_pos = A.m_pos; t.meta_init = A.m_init; t.meta_stride = A.mcap;
         int blocks = dev_grid_hint(d, 8 * ph + 5, worst);       // a wavefront per workgroup (launch_feature_dev has the reason)
         if (blocks > 262144) blocks = 262144;
         hipLaunchKernelGGL(triangulate_kernel, dim3(blocks), dim3(64), 0, stm, t);
         AV_LAUNCH_CHECK();
     }
-    FeatArgs f; memset(&f, 0, sizeof(f));
-    f.n_feat = 0; f.n_cam = 0; f.ld = b->ld;
+    FeatArgs f = b_feat_args(b, cut1500, A.cam_q, A.cam_p, A.cam_qn);
+    f.fs_stride = A.FS; f.stream_ncam = A.ncam; f.stream_gravity = A.grav;      // (n_feat and feat_stream stay 0: device-written lists, stream = f / fs_stride)
     f.obs_off = A.f_off; f.obs_cam = A.obs_cam; f.obs_z = A.obs_z; f.pos = A.f_pos; f.dof = A.f_dof; f.row_off = A.f_rowoff;
-    f.cam_q = A.cam_q; f.cam_p = A.cam_p; f.cam_qn = A.cam_qn; f.cam_pn = A.cam_p;      // position_null aliases position (msckf.py:403-404)
-    f.P = b->P; f.chi2 = b->chi2_dev;
-    for (int i = 0; i < 9; ++i) f.R01[i] = A.R01[i];
-    for (int i = 0; i < 3; ++i) { f.t01[i] = A.t01[i]; f.gravity[i] = 0; }
-    f.obs_noise = b->obs_noise; f.Hout = b->Hblk; f.rout = b->rblk; f.gamma = d->gamma; f.pass = d->pass;
-    f.feat_stream = nullptr; f.fs_stride = A.FS; f.stream_ncam = A.ncam; f.stream_gravity = A.grav; f.cam_stride = b->cam_slots;
-    f.p_stride = b->pstride; f.h_stride = b->hstride; f.r_stride = b->rstride; f.valid = A.f_valid;
-    f.zero_fill = cut1500 ? 1 : 0;          // the pruning update gathers only the 12 columns every stacked feature writes itself
+    f.gamma = d->gamma; f.pass = d->pass; f.valid = A.f_valid;
     // does this phase ever need the Cholesky back end?  If not (the pruning phase as a rule) its only reader is upd_info_kernel, which gathers
     // the 12 columns of the two cameras that go -- the columns every candidate writes: the rows are then stored compact, 12 doubles
     // each (480 contiguous bytes per feature instead of ten 48-byte pieces 1.2 KB apart, for the writer and for the reader)
@@ -274,35 +280,20 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
             if (bk > 0 && edges[bk - 1] >= b->cam_slots) break;
             f.feat_list = A.blist + (size_t)bk * S * cap; f.n_list_dev = cnt + bk;
             const int Mx = edges[bk] < b->cam_slots ? edges[bk] : b->cam_slots;
-            // diagnostic (AV_DEV_FPROF=2): phase stamps of the long-track bucket's first workgroup, every 16th launch (synchronises)
-            static const bool lprof_on = getenv("AV_DEV_FPROF") && atoi(getenv("AV_DEV_FPROF")) == 2;
-            static unsigned long long* lprof_dev = nullptr;
-            static int lprof_calls = 0;
-            f.prof = nullptr;
-            if (lprof_on && bk == DEV_BUCKETS - 1) { if (!lprof_dev) AV_HIP(hipMalloc((void**)&lprof_dev, 64)); f.prof = lprof_dev; }
+            // diagnostic (AV_DEV_FPROF=2): phase stamps of the long-track bucket's first workgroup
+            const bool stamped = bk == DEV_BUCKETS - 1 && dev_fprof_long().dev;
+            f.prof = stamped ? dev_fprof_long().dev : nullptr;
             if ((rc = launch_feature_dev(f, dev_grid_hint(d, bk, worst), Mx < 5 ? 5 : Mx, stm))) return rc;
-            if (f.prof && (++lprof_calls & 15) == 0) {
-                unsigned long long t[8];
-                AV_HIP(hipStreamSynchronize(stm));
-                AV_HIP(hipMemcpy(t, lprof_dev, 64, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[feature<256> workgroup 0, 10 ns ticks] jacobian %llu  G %llu  reflectors %llu  rows out %llu  gate %llu\n", t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4]);
-            }
+            unsigned long long t[32];
+            if (stamped && dev_fprof_long().read(stm, t)) print_stamps("feature<256> workgroup 0", t, {"jacobian", "G", "reflectors", "rows out", "gate"});
             f.prof = nullptr;
         }
     } else {
         f.feat_list = A.blist; f.n_list_dev = cnt;           // every pruning candidate has exactly two observations: one bucket, 16-lane teams
-        // diagnostic (AV_DEV_FPROF=1): phase stamps of the grid's first team, printed every 16th launch (synchronises: timing runs only)
-        static const bool fprof_on = getenv("AV_DEV_FPROF") != nullptr;
-        static unsigned long long* fprof_dev = nullptr;
-        static int fprof_calls = 0;
-        if (fprof_on) { if (!fprof_dev) AV_HIP(hipMalloc((void**)&fprof_dev, 64)); f.prof = fprof_dev; }
+        f.prof = dev_fprof_team().dev;                       // diagnostic (AV_DEV_FPROF=1): phase stamps of the grid's first team
         if ((rc = launch_feature_dev(f, dev_grid_hint(d, 8, worst), 2, stm))) return rc;
-        if (fprof_on && (++fprof_calls & 15) == 0) {
-            unsigned long long t[8];
-            AV_HIP(hipStreamSynchronize(stm));
-            AV_HIP(hipMemcpy(t, fprof_dev, 64, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[feature<16> team 0, 10 ns ticks] jacobian %llu  G %llu  reflectors %llu  rows out %llu  gate %llu\n", t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4]);
-        }
+        unsigned long long t[32];
+        if (dev_fprof_team().read(stm, t)) print_stamps("feature<16> team 0", t, {"jacobian", "G", "reflectors", "rows out", "gate"});
     }
     // ---- stacking decisions
     StackArgs sa; memset(&sa, 0, sizeof(sa));
@@ -324,17 +315,10 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
         const size_t lds_i = upd_info_lds(12, b->ld, minfo);
         if (lds_i > 160 * 1024) { av_set_error("batched MSCKF: information-form update needs %zu B of LDS", lds_i); return AV_E_CAPACITY; }
         hipLaunchKernelGGL(upd_info_kernel, dim3(S), dim3(256), lds_i, stm, d->upd);
-        if (dev_uprof()) {                                  // diagnostic (AV_DEV_UPROF=1): phase stamps of stream 0's workgroup, every 16th launch
-            static int calls = 0;
-            if ((++calls & 15) == 0) {
-                unsigned long long t[32];
-                AV_HIP(hipStreamSynchronize(stm));
-                AV_HIP(hipMemcpy(t, dev_uprof(), sizeof(t), hipMemcpyDeviceToHost));
-                fprintf(stderr, "[dk_begin stream 0, 10 ns ticks] imu steps %llu  cross block %llu  augment+gap %llu  add frame %llu  select lost %llu  candidates %llu  triangulate %llu  erase %llu\n",
-                        t[17] - t[16], t[18] - t[17], t[19] - t[18], t[20] - t[19], t[21] - t[20], t[22] - t[21], t[23] - t[22], t[24] - t[23]);
-                fprintf(stderr, "[upd_info stream 0, 10 ns ticks] row map %llu  gram %llu  Pc %llu  F,G %llu  gauss-jordan %llu  scale %llu  P update %llu\n",
-                        t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6]);
-            }
+        unsigned long long t[32];
+        if (dev_uprof().read(stm, t)) {                     // diagnostic (AV_DEV_UPROF=1): phase stamps of stream 0's workgroups
+            print_stamps("dk_begin stream 0", t + 16, {"imu steps", "cross block", "augment+gap", "add frame", "select lost", "candidates", "triangulate", "erase"});
+            print_stamps("upd_info stream 0", t, {"row map", "gram", "Pc", "F,G", "gauss-jordan", "scale", "P update"});
         }
     }
     if (rounds) {
@@ -501,7 +485,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     // list counters: two sets, used by alternate steps (a step's first kernel zeroes the other set for the step after it)
     const int par = (int)((d->steps + 1) & 1);
     a.cnt = d->A.cnt + 16 * par; a.cnt_next = d->A.cnt + 16 * (par ^ 1);
-    a.prof = dev_uprof() ? dev_uprof() + 16 : nullptr;
+    a.prof = dev_uprof().dev ? dev_uprof().dev + 16 : nullptr;
     // Launch shapes of the per-stream kernels.  From 1,024 streams up ONE wavefront per stream: their phases are chains of short memory
     // round trips, and beside the front-end a 256-thread workgroup waits for a free slot on all four SIMDs of a CU at once (a 0.25-ms
     // kernel took 1.5 ms in the shared run: profiles/r05/README.md).  Below that the GPU is not full and what counts is the time ONE
