@@ -161,6 +161,8 @@ typedef struct av_frontend_config {
     int32_t reserved0;                       /* keeps the size a multiple of 8; must be 0            */
     double  clahe_clip_limit;                /* config.clahe_clip_limit (2.0); the three are read only with AV_FE_CLAHE */
     int32_t clahe_tiles_x, clahe_tiles_y;    /* config.clahe_tiles (8, 8); 1 .. AV_CLAHE_MAX_TILES    */
+    int32_t pixel_format;                    /* config.image_format: AV_PIX_* of the frames handed to every entry path; 0 = 8-bit grey */
+    int32_t gray16_shift;                    /* config.gray16_shift: 0 .. 8, read only with AV_PIX_GRAY16 (checked always)            */
 } av_frontend_config;
 
 typedef struct av_frontend av_frontend;
@@ -206,6 +208,21 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * (pyramid) of av_frontend_enable_timing.  Without the flag the step enqueues exactly what it always did and nothing more is
  * allocated. */
 #define AV_FE_CLAHE 4
+
+/* av_frontend_config.pixel_format other than AV_PIX_GRAY8 (av_to_gray8 below has the formats and the arithmetic): the `uint8_t*` image
+ * arguments of av_frontend_step, _prestage, _step_host and av_frontend_frames_upload are BYTE pointers to frames of that format, and
+ * img_stride is in bytes, at least width * height * bytes per pixel.  Every frame of both cameras is converted to 8-bit grey before
+ * anything else reads it, into the engine-owned level 0 that AV_FE_CLAHE uses ([3][n_streams][width * height], allocated when either
+ * feature needs it); with AV_FE_CLAHE the grey frames are then equalised there in place; past that the step runs as if those were
+ * persisting inputs.  That holds for av_frontend_step with and without AV_FE_INPUTS_PERSIST, for av_frontend_prestage and for
+ * av_frontend_step_host (the staging slots and the host-to-device copy carry the raw format).  av_frontend_frames_upload keeps the raw
+ * frames in its pinned ring and in a device staging buffer per ring entry and converts them into the store on the copy stream, before
+ * CLAHE (if on), the pyramids and FAST; the conversion is not in place, so an upload may name an entry twice when only the format is
+ * set (the later frame wins, as with grey frames).  av_frontend_step_frames is what it was.  The conversion counts under class 0 of
+ * av_frontend_enable_timing, inside the input stage's span.  The caller's images are never written.  The published message is that
+ * of the unmodified pipeline run on the converted frames.  With AV_PIX_GRAY8 nothing is launched and nothing more is allocated.
+ * Both cameras have one size and one format.  av_frontend_create refuses an unknown format or a shift outside 0 .. 8, AV_E_INVALID,
+ * before a device is touched. */
 
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
@@ -253,6 +270,17 @@ int av_frontend_step_frames(av_frontend* fe, const int32_t* slot_of_stream, cons
  * colour type / size / interlaced: the caller may decode that file by other means), 2 unreadable or corrupt.  Returns AV_OK,
  * AV_E_CAPACITY if the worst status is 1, AV_E_INVALID if any file was unreadable.  Pure host function. */
 int av_png_decode_gray8(const char* const* paths, int n, int width, int height, uint8_t* out, int64_t out_stride, int threads, int32_t* status);
+/* The same for the PNG flavour that holds pixel_format: AV_PIX_GRAY8 = colour type 0 at depth 8, AV_PIX_GRAY16 = colour type 0 at depth
+ * 16 (the file's big-endian samples are swapped to host byte order), AV_PIX_RGB8 = colour type 2 at depth 8, AV_PIX_RGBA8 = colour type
+ * 6 at depth 8; non-interlaced.  (PNG stores no BGR order, no palette-free 16-bit colour is taken: AV_E_INVALID for the other formats.)
+ * File i lands in out + i * out_stride_bytes as width * height * bytes-per-pixel tightly packed bytes.  A file of another flavour than
+ * the one asked for gets status 1.  Status and return codes as above.  Pure host function. */
+int av_png_decode(const char* const* paths, int n, int width, int height, int pixel_format, void* out, int64_t out_stride_bytes, int threads,
+                  int32_t* status);
+/* Size and flavour of one PNG file from its IHDR alone: *pixel_format = the AV_PIX_* av_png_decode would take for it, or -1 for a
+ * flavour it does not decode (palette, 16-bit colour, grey + alpha, depth below 8, interlaced): AV_OK either way.  AV_E_INVALID for a
+ * file that cannot be opened or does not begin with a PNG signature and an IHDR chunk.  Pure host function. */
+int av_png_probe(const char* path, int32_t* width, int32_t* height, int32_t* pixel_format);
 
 /* Capacity (features per stream) of the published feature message = grid_num * grid_max. */
 int av_frontend_max_features(const av_frontend* fe);
@@ -293,8 +321,9 @@ int av_frontend_read_match_counts(av_frontend* fe, int stream_idx, int32_t out[2
  * AV_RANSAC_PATH_* codes below.  Synchronises. */
 int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, int32_t out[4], void* stream);
 
-/* The level-0 image the last step used for camera `cam` (0 / 1) of one stream of an engine created with AV_FE_CLAHE, i.e. the
- * equalised frame: width * height bytes into out_host.  AV_E_INVALID without the flag (level 0 is then the caller's own image),
+/* The level-0 image the last step used for camera `cam` (0 / 1) of one stream of an engine created with AV_FE_CLAHE or with a
+ * pixel_format other than AV_PIX_GRAY8, i.e. the grey frame the step worked on, equalised if AV_FE_CLAHE is set: width * height bytes
+ * into out_host.  AV_E_INVALID with neither (level 0 is then the caller's own image),
  * before the first step, and for a stream whose av_frontend_step_frames entries were negative from the start.  The image comes from where
  * the LAST step read it: the frame store after av_frontend_step_frames, the engine's own buffer after the other steps.  Between an
  * av_frontend_prestage and the step it serves the cam1 image of the last step is gone (its slot holds the next frame's): cam 1 is then
@@ -329,6 +358,40 @@ int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* ou
 #define AV_CLAHE_MAX_TILES 16
 int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h, double clip_limit, int tiles_x, int tiles_y,
              uint8_t* out_dev, int64_t out_stride, uint8_t* lut_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pixel formats of camera frames and their conversion to 8-bit grey.  No counterpart in the reference (streaming/dataset.py:101 hands
+ * on whatever cv2.imread(path, -1) returns, and the pipeline assumes 8-bit grey).  Parity with cv2.cvtColor is unpinned (there is no
+ * cv2 to check against), so this text is the contract; tests/pixfmt_ref.py states it in NumPy.
+ *   format          bytes per pixel   layout
+ *   AV_PIX_GRAY8    1                 one sample
+ *   AV_PIX_GRAY16   2                 one 16-bit sample in host byte order
+ *   AV_PIX_RGB8     3                 R G B interleaved            AV_PIX_BGR8   3   B G R
+ *   AV_PIX_RGBA8    4                 R G B A interleaved          AV_PIX_BGRA8  4   B G R A
+ *   GRAY16 to grey:  min(255, v >> shift), shift in 0 .. 8, default 8 (the high byte).  It truncates, it does not round.  A sensor with
+ *                    10, 12 or 14 significant bits uses shift 2, 4 or 6.
+ *   colour to grey:  (9798 R + 19235 G + 3735 B + 16384) >> 15 in integer arithmetic.  The coefficients sum to 2^15, so R = G = B = g
+ *                    gives g exactly and the result never exceeds 255.  Alpha is ignored.
+ *   GRAY8:           the identity.
+ * Not covered: Bayer mosaics, 16-bit colour, cameras of two sizes or formats, percentile or auto-range scaling of 16-bit data (CLAHE
+ * after a fixed shift is the answer for now).
+ *
+ * av_to_gray8: n_img images of w x h pixels, image i at img_dev + i * img_stride_bytes (tightly packed rows), to tightly packed u8 at
+ * out_dev + i * out_stride.  Images at 16-byte aligned addresses and strides (the strides count only when n_img > 1) go through as whole
+ * vectors with the last w * h % 16 pixels byte by byte; a launch with any other address or stride goes byte by byte altogether.
+ * shift is read for AV_PIX_GRAY16 only but checked always.  AV_E_INVALID with text for an unknown format, a shift outside 0 .. 8,
+ * w * h > AV_MAX_IMAGE_PIXELS, strides smaller than an image, and out_dev overlapping the input.  The one exception: AV_PIX_GRAY8 with
+ * out_dev == img_dev and equal strides is the identity in place and does nothing (any other AV_PIX_GRAY8 call is a strided copy, and
+ * an overlap is refused like for the other formats).
+ * ------------------------------------------------------------------------------------------- */
+#define AV_PIX_GRAY8  0
+#define AV_PIX_GRAY16 1
+#define AV_PIX_RGB8   2
+#define AV_PIX_BGR8   3
+#define AV_PIX_RGBA8  4
+#define AV_PIX_BGRA8  5
+int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_img, int w, int h, int pixel_format, int shift,
+                uint8_t* out_dev, int64_t out_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Two-point RANSAC on the temporal matches of ONE camera (no counterpart in the reference: feature_tracker.py:135-136 is where

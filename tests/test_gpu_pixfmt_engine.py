@@ -1,0 +1,168 @@
+"""The front-end engine fed 16-bit and colour frames (config.image_format) against the unmodified CPU oracle front-end fed the frames
+the NumPy reference of tests/pixfmt_ref.py converted, in every entry path; grey equivalence; with CLAHE; placement in a batch; off."""
+import numpy as np
+import pytest
+
+import clahe_ref as cr
+from pixfmt_helpers import MODES, Encoded, make_cfg as _cfg, run_engine, run_oracle, same as _same
+
+pytestmark = pytest.mark.gpu
+
+NF = 8
+STREAM = dict(seed=17, n_frames=NF, motion_scale=2.0)
+
+
+@pytest.fixture(scope='module')
+def base():
+    from uav_airvision_amd.synth import SyntheticStream
+    return SyntheticStream(_cfg(), **STREAM)
+
+
+@pytest.fixture(scope='module')
+def encoded(base):
+    """Per format: the raw stream and the oracle's output on its reference-converted frames (computed once, shared, never changed)."""
+    out = {}
+    for i, fmt in enumerate(('gray16', 'bgr8', 'rgba8')):
+        st = Encoded(base, fmt, NF, seed=40 + i)
+        out[fmt] = (st, run_oracle(_cfg(), st))
+    return out
+
+
+def _against_oracle(fmt, mode, st, ref, **cfg_kw):
+    got, images = run_engine(_cfg(image_format=fmt, **cfg_kw), [st], mode=mode, images_of=0)
+    assert len(ref) == len(got[0]) == NF and all(len(r['ids']) > 40 for r in ref)      # (a guard against a vacuous comparison: the scene has features)
+    for k, (r, g, im) in enumerate(zip(ref, got[0], images)):
+        ids, uv, cnt = g
+        where = '%s %s frame %d' % (fmt, mode, k)
+        assert np.array_equal(im[0], st.frame(k).cam0_image) and np.array_equal(im[1], st.frame(k).cam1_image), where      # read_image: the converted frames
+        if k > 0:
+            assert [cnt['before_tracking'], cnt['after_tracking'], cnt['after_matching']] == \
+                   [r['nf'].get('before_tracking', 0), r['nf'].get('after_tracking', 0), r['nf'].get('after_matching', 0)], where
+        assert cnt['overflow'] == 0 and cnt['n_published'] == len(r['ids']) and np.array_equal(ids, r['ids']), where
+        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('fmt', ['gray16', 'bgr8'])
+def test_engine_matches_the_oracle_on_converted_frames(encoded, fmt, mode):
+    """ids, uv bits, the tracker's stage counters and n_published on every frame; read_image returns exactly the reference-converted
+    frames; the caller's arrays and tensors are unchanged (asserted inside run_engine)."""
+    _against_oracle(fmt, mode, *encoded[fmt])
+
+
+@pytest.mark.parametrize('mode', ['step', 'frames'])
+def test_rgba_matches_the_oracle(encoded, mode):
+    _against_oracle('rgba8', mode, *encoded['rgba8'])
+
+
+def test_the_raw_frames_are_not_trivially_grey(encoded, base):
+    """The inputs above exercise the arithmetic: low bytes and channel offsets are there, and the converted frames differ from the
+    stream's own grey frames for the colour formats."""
+    st16, stc = encoded['gray16'][0], encoded['bgr8'][0]
+    assert (st16.raw[0][1] & 0xFF).std() > 50 and np.array_equal(st16.frame(0).cam0_image, base.frame(0).cam0_image)
+    b = stc.raw[0][1].astype(int)
+    assert np.abs(b[..., 0] - b[..., 2]).mean() > 10 and not np.array_equal(stc.frame(0).cam0_image, base.frame(0).cam0_image)
+
+
+def test_grey_equivalence(base):
+    """An RGB stream with R = G = B = g and a 16-bit stream g << 8 publish bit for bit what a gray8 engine publishes on g."""
+    from clahe_helpers import Cached, run_engine as run_gray
+    want = run_gray(_cfg(), [Cached(base, equalise=False)], n_frames=NF)[0]
+    assert all(len(w[0]) > 40 for w in want)
+    for fmt, mode in (('rgb8', 'step'), ('gray16', 'step'), ('rgb8', 'frames'), ('gray16', 'host')):
+        got = run_engine(_cfg(image_format=fmt), [Encoded(base, fmt, NF, exact=True)], mode=mode)[0]
+        assert all(_same(a, b) for a, b in zip(want, got)), (fmt, mode)
+
+
+def test_gray16_with_clahe_in_the_host_path(base):
+    """Conversion, then equalisation in place: against the oracle on clahe_ref.clahe(pixfmt_ref(...)); a shift other than 8 reaches the
+    stage (12 significant bits: frames are g << 4 | noise4, shift 4)."""
+    st = Encoded(base, 'gray16', NF, seed=44, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
+    _against_oracle('gray16', 'host', st, run_oracle(_cfg(), st), use_clahe=True)
+    st4 = Encoded(base, 'gray16', 3, seed=45)
+    for k in range(3):                                   # re-scale the raw frames to 12 bits; the reference conversion uses shift 4
+        t, r0, r1 = st4.raw[k]
+        st4.raw[k] = (t, (r0 >> 4).astype(np.uint16), (r1 >> 4).astype(np.uint16))
+    import pixfmt_ref as pr
+    got, images = run_engine(_cfg(image_format='gray16', gray16_shift=4), [st4], mode='step', images_of=0)
+    for k in range(3):
+        assert np.array_equal(images[k][0], pr.to_gray8(st4.raw[k][1], 'gray16', 4)) and np.array_equal(images[k][0], base.frame(k).cam0_image), k
+
+
+def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
+    """Three distinct streams in one batch, in the device path and through the frame store (entries out of order): each publishes
+    what it publishes alone."""
+    from uav_airvision_amd.synth import SyntheticStream
+    cfg = _cfg(image_format='bgr8')
+    nf = NF
+    batch = [Encoded(SyntheticStream(cfg, seed=200 + i, n_frames=nf, motion_scale=1.0 + 0.3 * i), 'bgr8', nf, seed=50 + i) for i in range(3)]
+    assert not np.array_equal(batch[0].raw[0][1], batch[1].raw[0][1])
+    alone = [run_engine(cfg, [b])[0] for b in batch]
+    assert all(len(a[0]) > 20 for al in alone for a in al)
+    assert not all(_same(a, b) for a, b in zip(alone[0], alone[1]))
+    for mode in ('step', 'frames'):
+        got = run_engine(cfg, batch, mode=mode)
+        for pos in range(3):
+            assert all(_same(a, b) for a, b in zip(alone[pos], got[pos])), (mode, pos)
+
+
+def test_an_entry_named_twice_takes_the_later_frame(encoded):
+    """The conversion is not in place, so an upload may name an entry twice when only the format is set: the later frame wins, as
+    with grey frames."""
+    from uav_airvision_amd.frontend import FrontendEngine
+    st = encoded['gray16'][0]
+    eng = FrontendEngine(_cfg(image_format='gray16'), n_streams=1)
+    eng.frames_reserve(4)
+    t, a0, a1 = st.raw[0]
+    _t, b0, b1 = st.raw[1]
+    eng.frames_upload(np.array([2, 2], np.int32), np.stack([b0, a0]), np.stack([b1, a1]))
+    eng.step_frames([2], [t])
+    eng.read_features()
+    assert np.array_equal(eng.read_image(0, 0), st.frame(0).cam0_image) and np.array_equal(eng.read_image(0, 1), st.frame(0).cam1_image)
+    eng.close()
+
+
+def test_off_is_off(base):
+    """image_format = 'gray8' equals a bare config without the two attributes, with the same timing spans per step, and read_image is
+    still refused; a format other than gray8 adds no span."""
+    from clahe_helpers import Cached, run_engine as run_gray
+    from uav_airvision_amd import _native as N
+    from uav_airvision_amd.frontend import FrontendEngine
+
+    class Bare(object):
+        pass
+    bare = Bare()
+    for k, v in vars(_cfg()).items():
+        if k not in ('image_format', 'gray16_shift'):
+            setattr(bare, k, v)
+    assert not hasattr(bare, 'image_format') and not hasattr(bare, 'gray16_shift')
+    st = Cached(base, equalise=False)
+    off, sp_off = run_gray(_cfg(image_format='gray8'), [st], n_frames=NF, timing=True)
+    none, sp_none = run_gray(bare, [st], n_frames=NF, timing=True)
+    assert all(_same(a, b) for a, b in zip(off[0], none[0])) and sp_off == sp_none
+    for mode in ('step', 'host'):
+        on, sp_on = run_engine(_cfg(image_format='rgb8'), [Encoded(base, 'rgb8', NF, exact=True)], mode=mode, timing=True)
+        ref_sp = sp_off if mode == 'step' else run_gray(_cfg(), [st], mode='host', n_frames=NF, timing=True)[1]
+        assert sp_on == ref_sp and all(s['pyramid'] == 1 for s in sp_on), mode
+    eng = FrontendEngine(_cfg(image_format='gray8'), n_streams=1)
+    m = base.frame(0)
+    eng.step_host(m.cam0_image, m.cam1_image, [m.timestamp])
+    eng.read_features()
+    with pytest.raises(N.AirvisionError) as e:
+        eng.read_image(0, 0)
+    assert e.value.code == N.AV_E_INVALID
+    eng.close()
+
+
+def test_wrong_frames_are_refused_by_name(base):
+    import torch
+    from uav_airvision_amd.frontend import FrontendEngine
+    eng = FrontendEngine(_cfg(image_format='gray16'), n_streams=1)
+    m = base.frame(0)
+    with pytest.raises(ValueError, match=r'uint8.*\(1, 480, 752\)|uint8 \(480, 752\)'):
+        eng.step_host(m.cam0_image, m.cam1_image, [m.timestamp])
+    with pytest.raises(ValueError, match='uint16'):
+        eng.step(torch.zeros((1, 480, 752), dtype=torch.uint8, device='cuda'), torch.zeros((1, 480, 752), dtype=torch.uint8, device='cuda'), [0.0])
+    with pytest.raises(ValueError, match='uint16'):
+        eng.frames_upload([0], np.zeros((1, 480, 752, 3), np.uint8), np.zeros((1, 480, 752, 3), np.uint8))
+    eng.close()

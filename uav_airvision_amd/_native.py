@@ -20,9 +20,31 @@ AV_FE_INPUTS_PERSIST = 1
 AV_FE_RANSAC = 2
 AV_FE_CLAHE = 4
 AV_CLAHE_MAX_TILES = 16
+AV_PIX_GRAY8, AV_PIX_GRAY16, AV_PIX_RGB8, AV_PIX_BGR8, AV_PIX_RGBA8, AV_PIX_BGRA8 = 0, 1, 2, 3, 4, 5
 AV_RANSAC_MAX_PAIRS = 1920
 AV_RANSAC_MAX_HYPOTHESES = 64
 AV_RANSAC_PATH_FEW, AV_RANSAC_PATH_STILL, AV_RANSAC_PATH_MODEL, AV_RANSAC_PATH_NONE = 1, 2, 4, 8
+
+
+PIXEL_FORMATS = {'gray8': 0, 'gray16': 1, 'rgb8': 2, 'bgr8': 3, 'rgba8': 4, 'bgra8': 5}      # config.image_format -> AV_PIX_* (include/airvision.h)
+PIXEL_FORMAT_NAMES = {v: k for k, v in PIXEL_FORMATS.items()}
+PIXEL_BYTES = {0: 1, 1: 2, 2: 3, 3: 3, 4: 4, 5: 4}
+
+
+def pixel_format_code(name):
+    """config.image_format ('gray8', 'gray16', 'rgb8', 'bgr8', 'rgba8', 'bgra8') or an AV_PIX_* code -> AV_PIX_*; ValueError otherwise."""
+    if isinstance(name, str) and name in PIXEL_FORMATS:
+        return PIXEL_FORMATS[name]
+    if isinstance(name, int) and not isinstance(name, bool) and name in PIXEL_FORMAT_NAMES:
+        return name
+    raise ValueError('unknown image format %r (one of %s)' % (name, ', '.join(sorted(PIXEL_FORMATS, key=PIXEL_FORMATS.get))))
+
+
+def gray16_shift_value(shift):
+    """config.gray16_shift -> int in 0 .. 8; ValueError otherwise."""
+    if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= 8:
+        raise ValueError('gray16_shift %r outside 0 .. 8' % (shift,))
+    return int(shift)
 
 
 DISTORTION_MODELS = {'radtan': 0, 'equidistant': 1}          # AV_DISTORTION_* (include/airvision.h)
@@ -61,7 +83,8 @@ class FrontendConfig(C.Structure):
                 ('cam0_distortion_model', C.c_int32), ('cam1_distortion_model', C.c_int32),
                 ('ransac_threshold', C.c_double), ('ransac_success_probability', C.c_double),
                 ('ransac_seed', C.c_uint32), ('reserved0', C.c_int32),
-                ('clahe_clip_limit', C.c_double), ('clahe_tiles_x', C.c_int32), ('clahe_tiles_y', C.c_int32)]
+                ('clahe_clip_limit', C.c_double), ('clahe_tiles_x', C.c_int32), ('clahe_tiles_y', C.c_int32),
+                ('pixel_format', C.c_int32), ('gray16_shift', C.c_int32)]
 
 
 # name -> (restype, argtypes); the list doubles as the export check of tests/test_abi.py
@@ -123,6 +146,9 @@ SIGNATURES = {
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_png_decode_gray8': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P]),
+    'av_png_decode': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P]),
+    'av_png_probe': (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'av_to_gray8': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     'av_quat_to_rotation': (C.c_int, [_P, _P]),
     'av_rotation_to_quat': (C.c_int, [_P, _P]),
     'av_quat_multiply': (C.c_int, [_P, _P, _P]),

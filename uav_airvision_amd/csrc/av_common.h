@@ -243,3 +243,12 @@ int av_clahe_check(int w, int h, double clip_limit, int tiles_x, int tiles_y, co
 int av_launch_clahe(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
                     int n_groups, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* lut, hipStream_t st,
                     const int* index = nullptr);
+
+// pixfmt.hip: n_groups frames of one camera (src1 / dst1 null) or of two, of pixel format fmt (AV_PIX_*, not GRAY8), to tightly packed
+// 8-bit grey.  Camera c of group g is read at src_c + g * src_stride (bytes) and written to dst_c + e * dst_stride with
+// e = index ? index[g] : g; a negative entry skips the group.  Never in place.  av_pixfmt_bytes: bytes per pixel, 0 = unknown format;
+// av_pixfmt_check: the limits of format and shift, with `who` in the text.
+int av_pixfmt_bytes(int fmt);
+int av_pixfmt_check(int fmt, int shift, const char* who);
+int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
+                       int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index = nullptr);

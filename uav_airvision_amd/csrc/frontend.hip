@@ -648,7 +648,8 @@ struct av_frontend {
         uint32_t* tile_kp = nullptr; int* tile_count = nullptr;      // FAST survivor lists of cam0, per slot
         bool l0_in_place = true;                 // false if the pyramid launcher had to write padded level-0 copies (unaligned geometry)
         std::vector<int> prev;                   // host: slot of every stream's previous frame (-1: none yet)
-        struct Up { uint8_t* pin = nullptr; int* idx_h = nullptr; int* idx_d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
+        struct Up { uint8_t* pin = nullptr; int* idx_h = nullptr; int* idx_d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false;
+                    uint8_t* raw_d = nullptr; };      // pixel_format != GRAY8: the raw frames on the device; idx_h / idx_d then hold a second list, the conversion's
         Up up[4]; int up_next = 0;               // upload staging ring (pinned frames + the slot list of the upload's kernels)
         hipEvent_t uploaded = nullptr; bool any_upload = false;      // copy stream: the newest upload's kernels have finished
         hipEvent_t stepped = nullptr; bool any_step = false;          // step stream: the newest step has finished
@@ -672,6 +673,9 @@ struct av_frontend {
     // AV_FE_CLAHE: the equalised level 0 of every frame, [3][S][w * h] laid out like the pyramid slots (0 / 1: cam0 of alternating
     // frames, 2: cam1), and the look-up tables of one launch [2 S][tiles][256]; the frame store keeps tables of its own (fs_lut)
     bool clahe = false; uint8_t* eq = nullptr; uint8_t* eq_lut = nullptr; uint8_t* fs_lut = nullptr;
+    // pixel_format != AV_PIX_GRAY8: the frames are converted to 8-bit grey into the same level 0 (pixfmt.hip), ahead of the equalisation;
+    // own_l0 = the engine owns level 0 (either feature); bpp = bytes per pixel of the frames the entry points are handed
+    int fmt = AV_PIX_GRAY8, fmt_shift = 8, bpp = 1; bool own_l0 = false;
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
     explicit av_frontend(int S) : streams(S) {}
@@ -756,17 +760,25 @@ struct Span {
     }
 };
 
-// AV_FE_CLAHE: the equalised level 0 that goes with pyramid slot `slot`
+// the engine-owned level 0 (AV_FE_CLAHE, pixel_format != AV_PIX_GRAY8) that goes with pyramid slot `slot`
 uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot * fe->d.S * fe->d.w * fe->d.h; }
 
 // The input stage of a step (step_impl, av_frontend_prestage): the pyramids of both cameras' images into slots cur and 2; with
-// AV_FE_CLAHE the images are first equalised into the engine's own level 0 and the pyramids built from there.  One class-0 span.
+// AV_FE_CLAHE the images are first equalised into the engine's own level 0 and the pyramids built from there; frames of another pixel
+// format are first converted to grey into that level 0 and, with AV_FE_CLAHE, equalised there in place.  One class-0 span.
 // *wrote_l0 = false: level 0 stays the image itself (never asked for unless the inputs persist: the equalised ones always do).
 int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int cur, bool inputs_persist, hipStream_t st, bool* wrote_l0)
 {
     const FeDev& d = fe->d;
     const av_frontend_config& c = fe->cfg;
     Span sp(fe, 0, st);
+    if (fe->fmt != AV_PIX_GRAY8) {
+        uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
+        const int64_t hw = (int64_t)d.w * d.h;
+        int rc = av_launch_to_gray8(img0, img1, img_stride, e0, e1, hw, d.S, d.w, d.h, fe->fmt, fe->fmt_shift, st);
+        if (rc) return rc;
+        img0 = e0; img1 = e1; img_stride = hw; inputs_persist = true;
+    }
     if (fe->clahe) {
         uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
         const int64_t hw = (int64_t)d.w * d.h;
@@ -846,7 +858,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         if (fe->pre_on && fe->pre_img0 == img0 && fe->pre_img1 == img1 && fe->pre_stride == img_stride) wrote_l0 = fe->pre_wrote_l0;      // built by av_frontend_prestage
         else if ((rc = input_stage(fe, img0, img1, img_stride, cur, inputs_persist, st, &wrote_l0))) return rc;
         fe->pre_on = false;
-        if (fe->clahe) { img0 = eq_slot(fe, cur); img1 = eq_slot(fe, 2); img_stride = (int64_t)d.w * d.h; }      // from here on the equalised images are the step's inputs
+        if (fe->own_l0) { img0 = eq_slot(fe, cur); img1 = eq_slot(fe, 2); img_stride = (int64_t)d.w * d.h; }      // from here on the engine's own grey (equalised) images are the step's inputs
         fe->l0_img[cur] = wrote_l0 ? nullptr : img0; fe->l0_img[2] = wrote_l0 ? nullptr : img1;
         fe->l0_stride[cur] = fe->l0_stride[2] = img_stride;
         prev0 = slot_view(fe, par); cur0 = slot_view(fe, cur); cur1 = slot_view(fe, 2);      // (first frame: nothing is tracked from prev0)
@@ -917,6 +929,7 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         av_set_error("av_frontend_create: the engine takes images of 1 .. AV_MAX_IMAGE_PIXELS = %d pixels (%d x %d)", AV_MAX_IMAGE_PIXELS, cfg->width, cfg->height);
         return AV_E_INVALID;
     }
+    if (av_pixfmt_check(cfg->pixel_format, cfg->gray16_shift, "av_frontend_create")) return AV_E_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { av_set_error("av_frontend_create: no HIP device visible"); return AV_E_NODEVICE; }
     if (device < 0 || device >= ndev) { av_set_error("av_frontend_create: device %d out of range (%d visible)", device, ndev); return AV_E_INVALID; }
@@ -1020,8 +1033,11 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         a.thr = cfg->ransac_threshold; a.N = rs_N; a.seed = cfg->ransac_seed;
         fe->ransac = true;
     }
+    fe->fmt = cfg->pixel_format; fe->fmt_shift = cfg->gray16_shift; fe->bpp = av_pixfmt_bytes(cfg->pixel_format);
+    fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8;
+    if (fe->own_l0) A(fe->eq, (size_t)3 * S * w * h)
     if (clahe) {
-        A(fe->eq, (size_t)3 * S * w * h) A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
+        A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
         fe->clahe = true;
     }
 #undef A
@@ -1067,6 +1083,7 @@ AV_EXPORT void av_frontend_destroy(av_frontend* fe)
         if (u.pin) (void)hipHostFree(u.pin);
         if (u.idx_h) (void)hipHostFree(u.idx_h);
         if (u.idx_d) (void)hipFree(u.idx_d);
+        if (u.raw_d) (void)hipFree(u.raw_d);
         if (u.done) (void)hipEventDestroy(u.done);
     }
     if (fe->fs.uploaded) (void)hipEventDestroy(fe->fs.uploaded);
@@ -1114,7 +1131,7 @@ AV_EXPORT int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_
 // Needs AV_FE_INPUTS_PERSIST (the images are read again by the step itself); a step that comes with other images builds its own.
 AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride, void* stream)
 {
-    if (!fe || !img0_dev || !img1_dev || img_stride < (int64_t)fe->d.w * fe->d.h) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
+    if (!fe || !img0_dev || !img1_dev || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
@@ -1131,7 +1148,7 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
 AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride,
                                const double* timestamps, void* stream)
 {
-    if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < (int64_t)fe->d.w * fe->d.h) {
+    if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) {
         av_set_error("av_frontend_step: bad arguments");
         return AV_E_INVALID;
     }
@@ -1141,12 +1158,12 @@ AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const u
 AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, const uint8_t* img1_host, int64_t img_stride,
                                     const double* timestamps, void* stream)
 {
-    if (!fe || !img0_host || !img1_host || !timestamps || img_stride < (int64_t)fe->d.w * fe->d.h) {
+    if (!fe || !img0_host || !img1_host || !timestamps || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) {
         av_set_error("av_frontend_step_host: bad arguments");
         return AV_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t img_bytes = (size_t)fe->d.w * fe->d.h;
+    const size_t img_bytes = (size_t)fe->d.w * fe->d.h * fe->bpp;      // the staging slots carry the frames in their own format
     const int S = fe->d.S;
     AV_HIP(hipSetDevice(fe->device));
     av_frontend::HostSlot& h = fe->hs[fe->hs_next];
@@ -1209,7 +1226,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
                                         int64_t img_stride, void* stream)
 {
     (void)stream;
-    if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < (int64_t)fe->d.w * fe->d.h) {
+    if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) {
         av_set_error("av_frontend_frames_upload: bad arguments");
         return AV_E_INVALID;
     }
@@ -1228,36 +1245,49 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     AV_HIP(hipSetDevice(fe->device));
     const FeDev& d = fe->d;
     const size_t hw = (size_t)d.w * d.h;
+    const bool raw = fe->fmt != AV_PIX_GRAY8;
+    const size_t fb = hw * fe->bpp;                                 // bytes of one camera's frame as the caller hands it over
     av_frontend::FrameStore::Up& u = fs.up[fs.up_next];
     fs.up_next = (fs.up_next + 1) % 4;
     if (u.used) AV_HIP(hipEventSynchronize(u.done));                // the staging area's previous upload has left it
     if ((size_t)n > u.cap) {
         if (u.pin) { (void)hipHostFree(u.pin); (void)hipHostFree(u.idx_h); (void)hipFree(u.idx_d); u.pin = nullptr; u.idx_h = nullptr; u.idx_d = nullptr; }
+        if (u.raw_d) { (void)hipFree(u.raw_d); u.raw_d = nullptr; }
         const size_t cap = (size_t)n + 16;
-        AV_HIP(hipHostMalloc((void**)&u.pin, cap * 2 * hw, hipHostMallocDefault));
-        AV_HIP(hipHostMalloc((void**)&u.idx_h, cap * sizeof(int), hipHostMallocDefault));
-        AV_HIP(hipMalloc((void**)&u.idx_d, cap * sizeof(int)));
+        AV_HIP(hipHostMalloc((void**)&u.pin, cap * 2 * fb, hipHostMallocDefault));
+        AV_HIP(hipHostMalloc((void**)&u.idx_h, (raw ? 2 : 1) * cap * sizeof(int), hipHostMallocDefault));
+        AV_HIP(hipMalloc((void**)&u.idx_d, (raw ? 2 : 1) * cap * sizeof(int)));
+        if (raw) AV_HIP(hipMalloc((void**)&u.raw_d, cap * 2 * fb));
         if (!u.done) AV_HIP(hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
         u.cap = cap;
     }
 #pragma omp parallel for schedule(static) num_threads(n >= 8 ? 8 : 1)
     for (int i = 0; i < 2 * n; ++i) {
         const int f = i >> 1, cam = i & 1;
-        memcpy(u.pin + ((size_t)2 * f + cam) * hw, (cam ? img1_host : img0_host) + (size_t)f * img_stride, hw);
+        memcpy(u.pin + ((size_t)2 * f + cam) * fb, (cam ? img1_host : img0_host) + (size_t)f * img_stride, fb);
     }
     for (int i = 0; i < n; ++i) u.idx_h[i] = slots[i];
+    if (raw) {                       // the conversion's list: an entry named twice is written by its last frame only (what the copies of grey frames leave)
+        std::vector<int> last((size_t)fs.n_slots, -1);
+        for (int i = 0; i < n; ++i) last[slots[i]] = i;
+        for (int i = 0; i < n; ++i) u.idx_h[n + i] = last[slots[i]] == i ? slots[i] : -1;
+    }
     hipStream_t cs = fe->copy_stream;
     // The entries handed to an upload are free as of the newest ENQUEUED step (the caller's promise): the copies wait for that step
     // and run beside whatever the caller enqueues next -- upload the frames of step k + 1 before enqueueing step k and the two overlap.
     if (fs.any_step) AV_HIP(hipStreamWaitEvent(cs, fs.stepped, 0));
-    AV_HIP(hipMemcpyAsync(u.idx_d, u.idx_h, sizeof(int) * n, hipMemcpyHostToDevice, cs));
-    for (int i = 0; i < n;) {                                        // runs of consecutive entries go down in one copy
+    AV_HIP(hipMemcpyAsync(u.idx_d, u.idx_h, sizeof(int) * (raw ? 2 : 1) * n, hipMemcpyHostToDevice, cs));
+    int rc;
+    if (raw) {                       // raw frames to the ring entry's device buffer in one copy, then converted into their store entries
+        AV_HIP(hipMemcpyAsync(u.raw_d, u.pin, (size_t)n * 2 * fb, hipMemcpyHostToDevice, cs));
+        if ((rc = av_launch_to_gray8(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->fmt, fe->fmt_shift, cs, u.idx_d + n))) return rc;
+    }
+    for (int i = 0; i < n && !raw;) {                                // runs of consecutive entries go down in one copy
         int j = i + 1;
         while (j < n && slots[j] == slots[j - 1] + 1) ++j;
         AV_HIP(hipMemcpyAsync(fs.img + (size_t)slots[i] * 2 * hw, u.pin + (size_t)i * 2 * hw, (size_t)(j - i) * 2 * hw, hipMemcpyHostToDevice, cs));
         i = j;
     }
-    int rc;
     bool wrote_l0 = true;
     // (not input_stage: these launches are indexed, in place in the store, on the copy stream and outside the step's timing spans)
     // AV_FE_CLAHE: the entries are equalised once, where they lie, before anything reads them (the tables by position in this upload)
@@ -1410,7 +1440,7 @@ AV_EXPORT int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, in
 AV_EXPORT int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* out_host, void* stream)
 {
     if (!fe || stream_idx < 0 || stream_idx >= fe->d.S || cam < 0 || cam > 1 || !out_host) { av_set_error("av_frontend_read_image: bad arguments"); return AV_E_INVALID; }
-    if (!fe->clahe) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE: level 0 is the caller's own image"); return AV_E_INVALID; }
+    if (!fe->own_l0) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE and with 8-bit grey input: level 0 is the caller's own image"); return AV_E_INVALID; }
     if (!fe->stepped) { av_set_error("av_frontend_read_image: no step has run yet"); return AV_E_INVALID; }
     if (cam == 1 && fe->pre_on && !fe->stepped_frames) {
         av_set_error("av_frontend_read_image: the cam1 image of the last step has been replaced by av_frontend_prestage (read it before prestaging)");

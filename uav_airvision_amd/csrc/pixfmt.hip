@@ -1,0 +1,151 @@
+// pixfmt.hip -- camera frames of the other pixel formats (16-bit grey, RGB / BGR, RGBA / BGRA) to tightly packed 8-bit grey (gfx950).
+// The arithmetic is written out in include/airvision.h (av_to_gray8); tests/pixfmt_ref.py states it in NumPy and the kernel is held
+// to it bit for bit.  A pure streaming pass: an image is one run of w * h pixels (rows are tightly packed on both sides), a workgroup
+// takes PF_BLOCK of them.
+//   aligned body   bases and (with more than one image per camera) strides are whole 16-byte vectors: a lane takes 16 pixels,
+//                  2 / 3 / 4 uint4 loads in, one uint4 store out
+//   byte-wise      the ragged last 1 .. 15 pixels of an image, and every pixel of a launch whose addresses or strides are not whole
+//                  vectors: one pixel per lane and round, neighbouring lanes on neighbouring pixels
+// All byte offsets are 64-bit: 2^24 pixels x 4 B x thousands of streams passes 2^32.
+#include "av_common.h"
+
+namespace {
+
+constexpr int PF_LANE = 16;                    // output pixels of one lane = one 16-byte store
+constexpr int PF_BLOCK = 256 * PF_LANE;        // pixels of one workgroup
+
+struct PixArgs {
+    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
+    uint8_t* dst0; uint8_t* dst1;
+    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
+    int n_src;                                     // 1 or 2
+    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
+    int n_img, npix, fmt, shift;
+    int per;                                       // workgroups per image
+    int vec;                                       // every base, and every stride that is applied, is a whole 16-byte vector
+};
+
+__host__ __device__ constexpr int pf_bytes(int fmt) { return fmt == AV_PIX_GRAY8 ? 1 : fmt == AV_PIX_GRAY16 ? 2 : (fmt == AV_PIX_RGB8 || fmt == AV_PIX_BGR8) ? 3 : 4; }
+
+__device__ __forceinline__ uint32_t pf_luma(uint32_t r, uint32_t g, uint32_t b) { return (9798u * r + 19235u * g + 3735u * b + 16384u) >> 15; }
+__device__ __forceinline__ uint32_t pf_byte(const uint32_t* d, int b) { return (d[b >> 2] >> (8 * (b & 3))) & 255u; }
+
+// one pixel, byte by byte (16-bit samples are in host byte order: little endian, like the device)
+template <int FMT>
+__device__ __forceinline__ uint8_t pf_pixel(const uint8_t* p, int shift)
+{
+    if (FMT == AV_PIX_GRAY16) return (uint8_t)min(255u, ((uint32_t)p[0] | (uint32_t)p[1] << 8) >> shift);
+    constexpr bool bgr = FMT == AV_PIX_BGR8 || FMT == AV_PIX_BGRA8;
+    return (uint8_t)pf_luma(p[bgr ? 2 : 0], p[1], p[bgr ? 0 : 2]);
+}
+
+// 16 pixels from whole vectors
+template <int FMT>
+__device__ __forceinline__ uint4 pf_group(const uint4* in, int shift)
+{
+    constexpr int B = pf_bytes(FMT);
+    constexpr bool bgr = FMT == AV_PIX_BGR8 || FMT == AV_PIX_BGRA8;
+    uint32_t d[4 * B];
+#pragma unroll
+    for (int i = 0; i < B; ++i) { const uint4 q = in[i]; d[4 * i] = q.x; d[4 * i + 1] = q.y; d[4 * i + 2] = q.z; d[4 * i + 3] = q.w; }
+    uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < PF_LANE; ++k) {
+        uint32_t v;
+        if (FMT == AV_PIX_GRAY16) v = min(255u, ((d[k >> 1] >> (16 * (k & 1))) & 0xFFFFu) >> shift);
+        else v = pf_luma(pf_byte(d, B * k + (bgr ? 2 : 0)), pf_byte(d, B * k + 1), pf_byte(d, B * k + (bgr ? 0 : 2)));
+        o[k >> 2] |= v << (8 * (k & 3));
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void to_gray8_kernel(PixArgs a)
+{
+    constexpr int B = pf_bytes(FMT);
+    const int img = blockIdx.x / a.per, blk = blockIdx.x - img * a.per;
+    const int cam = img % a.n_src, g = img / a.n_src;
+    const int64_t e = a.index ? a.index[g] : g;
+    if (e < 0) return;
+    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
+    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
+    const int tid = threadIdx.x;
+    const int p0 = blk * PF_BLOCK;                                // < 2^24
+    if (a.vec) {
+        const int p = p0 + tid * PF_LANE;
+        if (p + PF_LANE <= a.npix) {
+            *reinterpret_cast<uint4*>(dst + p) = pf_group<FMT>(reinterpret_cast<const uint4*>(src + (int64_t)p * B), a.shift);
+        } else {
+            for (int q = p; q < a.npix; ++q) dst[q] = pf_pixel<FMT>(src + (int64_t)q * B, a.shift);      // the image's ragged end: one lane, < 16 pixels
+        }
+        return;
+    }
+#pragma unroll 4
+    for (int j = 0; j < PF_LANE; ++j) {
+        const int p = p0 + j * 256 + tid;
+        if (p < a.npix) dst[p] = pf_pixel<FMT>(src + (int64_t)p * B, a.shift);
+    }
+}
+
+}  // namespace
+
+int av_pixfmt_bytes(int fmt) { return fmt >= AV_PIX_GRAY8 && fmt <= AV_PIX_BGRA8 ? pf_bytes(fmt) : 0; }
+
+int av_pixfmt_check(int fmt, int shift, const char* who)
+{
+    if (fmt < AV_PIX_GRAY8 || fmt > AV_PIX_BGRA8) { av_set_error("%s: unknown pixel format %d (AV_PIX_GRAY8 = 0 .. AV_PIX_BGRA8 = 5)", who, fmt); return AV_E_INVALID; }
+    if (shift < 0 || shift > 8) { av_set_error("%s: gray16 shift %d outside 0 .. 8", who, shift); return AV_E_INVALID; }
+    return AV_OK;
+}
+
+int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
+                       int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index)
+{
+    if (n_groups <= 0) return AV_OK;
+    PixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src0 = src0; a.src1 = src1; a.dst0 = dst0; a.dst1 = dst1; a.src_stride = src_stride; a.dst_stride = dst_stride;
+    a.n_src = src1 ? 2 : 1; a.index = index; a.n_img = n_groups * a.n_src; a.npix = w * h; a.fmt = fmt; a.shift = shift;
+    a.per = (a.npix + PF_BLOCK - 1) / PF_BLOCK;
+    auto al16 = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool strides16 = n_groups == 1 || ((src_stride & 15) == 0 && (dst_stride & 15) == 0);      // one group: the strides are never applied
+    a.vec = strides16 && al16(src0) && al16(src1) && al16(dst0) && al16(dst1);
+    if ((int64_t)a.per * a.n_img > 0x7FFFFFFFll) { av_set_error("av_to_gray8: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
+    const dim3 grid((unsigned)(a.per * a.n_img)), block(256);
+    switch (fmt) {
+    case AV_PIX_GRAY16: hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_GRAY16>, grid, block, 0, st, a); break;
+    case AV_PIX_RGB8:   hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_RGB8>, grid, block, 0, st, a); break;
+    case AV_PIX_BGR8:   hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_BGR8>, grid, block, 0, st, a); break;
+    case AV_PIX_RGBA8:  hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_RGBA8>, grid, block, 0, st, a); break;
+    case AV_PIX_BGRA8:  hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_BGRA8>, grid, block, 0, st, a); break;
+    default: av_set_error("av_to_gray8: no conversion kernel for pixel format %d", fmt); return AV_E_INVALID;
+    }
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+AV_EXPORT int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_img, int w, int h, int pixel_format, int shift,
+                          uint8_t* out_dev, int64_t out_stride, void* stream)
+{
+    int rc = av_pixfmt_check(pixel_format, shift, "av_to_gray8");
+    if (rc) return rc;
+    if (w <= 0 || h <= 0 || (int64_t)w * h > AV_MAX_IMAGE_PIXELS) { av_set_error("av_to_gray8: w * h must be 1 .. AV_MAX_IMAGE_PIXELS = 2^24 (%d x %d)", w, h); return AV_E_INVALID; }
+    const int64_t npix = (int64_t)w * h, in_bytes = npix * pf_bytes(pixel_format);
+    if (!img_dev || !out_dev || n_img < 0 || img_stride_bytes < in_bytes || out_stride < npix) {
+        av_set_error("av_to_gray8: bad arguments (n_img %d, strides %lld / %lld bytes for %d x %d of %d bytes per pixel)", n_img, (long long)img_stride_bytes,
+                     (long long)out_stride, w, h, pf_bytes(pixel_format));
+        return AV_E_INVALID;
+    }
+    if (n_img == 0) return AV_OK;
+    const uint8_t* in = static_cast<const uint8_t*>(img_dev);
+    hipStream_t st = (hipStream_t)stream;
+    if (pixel_format == AV_PIX_GRAY8 && in == out_dev && img_stride_bytes == out_stride) return AV_OK;      // the identity in place: nothing to do
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (uint64_t)(n_img - 1) * img_stride_bytes + in_bytes;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + (uint64_t)(n_img - 1) * out_stride + npix;
+    if (o0 < i1 && i0 < o1) { av_set_error("av_to_gray8: out_dev overlaps the input (the conversion does not work in place)"); return AV_E_INVALID; }
+    if (pixel_format == AV_PIX_GRAY8) {            // the identity out of place: a strided copy
+        AV_HIP(hipMemcpy2DAsync(out_dev, (size_t)out_stride, in, (size_t)img_stride_bytes, (size_t)npix, (size_t)n_img, hipMemcpyDeviceToDevice, st));
+        return AV_OK;
+    }
+    return av_launch_to_gray8(in, nullptr, img_stride_bytes, out_dev, nullptr, out_stride, n_img, w, h, pixel_format, shift, st, nullptr);
+}

@@ -165,9 +165,46 @@ void unfilter_paeth4(const uint8_t* in, size_t pitch, uint8_t* o, int width)
 }
 #undef AV_PAETH_PX
 
-// 0 ok, 1 unsupported flavour (not 8-bit greyscale, interlaced, wrong size), 2 unreadable / corrupt
-int decode_one(const char* path, int width, int height, uint8_t* out, char* why, size_t why_cap)
+// the PNG flavour that holds a pixel format: bit depth, colour type, bytes per pixel; false: PNG has none for it
+bool png_flavour(int fmt, int* depth, int* colour, int* bpp)
 {
+    switch (fmt) {
+    case AV_PIX_GRAY8:  *depth = 8;  *colour = 0; *bpp = 1; return true;
+    case AV_PIX_GRAY16: *depth = 16; *colour = 0; *bpp = 2; return true;
+    case AV_PIX_RGB8:   *depth = 8;  *colour = 2; *bpp = 3; return true;
+    case AV_PIX_RGBA8:  *depth = 8;  *colour = 6; *bpp = 4; return true;
+    default: return false;
+    }
+}
+
+// one row of any bytes-per-pixel (PNG spec 9.2): a and c are bpp bytes back, b is the byte above; n = bytes of the row
+void unfilter_row(int ft, const uint8_t* in, const uint8_t* prev, uint8_t* o, int n, int bpp)
+{
+    switch (ft) {
+    case 0: memcpy(o, in, (size_t)n); break;
+    case 1:
+        for (int x = 0; x < n; ++x) o[x] = (uint8_t)(in[x] + (x >= bpp ? o[x - bpp] : 0));
+        break;
+    case 2:
+        if (prev) { for (int x = 0; x < n; ++x) o[x] = (uint8_t)(in[x] + prev[x]); } else memcpy(o, in, (size_t)n);
+        break;
+    case 3:
+        for (int x = 0; x < n; ++x) { const int a = x >= bpp ? o[x - bpp] : 0, b = prev ? prev[x] : 0; o[x] = (uint8_t)(in[x] + ((a + b) >> 1)); }
+        break;
+    default:
+        for (int x = 0; x < n; ++x) {
+            const int a = x >= bpp ? o[x - bpp] : 0, b = prev ? prev[x] : 0, c = (prev && x >= bpp) ? prev[x - bpp] : 0;
+            o[x] = (uint8_t)(in[x] + paeth(a, b, c));
+        }
+        break;
+    }
+}
+
+// 0 ok, 1 unsupported flavour (not the one asked for, interlaced, wrong size), 2 unreadable / corrupt
+int decode_one(const char* path, int width, int height, int fmt, uint8_t* out, char* why, size_t why_cap)
+{
+    int want_depth = 8, want_colour = 0, bpp = 1;
+    (void)png_flavour(fmt, &want_depth, &want_colour, &bpp);      // (the entry points have checked the format)
     FILE* f = fopen(path, "rb");
     if (!f) { snprintf(why, why_cap, "cannot open %s", path); return 2; }
     // per-thread buffers that only grow: a fresh 200 KB + 360 KB vector per frame is an mmap, ~140 page faults and a munmap each time
@@ -200,8 +237,9 @@ int decode_one(const char* path, int width, int height, uint8_t* out, char* why,
             if (len < 13) break;
             const uint32_t w = be32(data), h = be32(data + 4);
             const int depth = data[8], colour = data[9], interlace = data[12];
-            if ((int)w != width || (int)h != height || depth != 8 || colour != 0 || interlace != 0) {
-                snprintf(why, why_cap, "%s: %ux%u depth %d colour type %d interlace %d (expected %dx%d 8-bit greyscale)", path, w, h, depth, colour, interlace, width, height);
+            if ((int)w != width || (int)h != height || depth != want_depth || colour != want_colour || interlace != 0) {
+                if (fmt == AV_PIX_GRAY8) snprintf(why, why_cap, "%s: %ux%u depth %d colour type %d interlace %d (expected %dx%d 8-bit greyscale)", path, w, h, depth, colour, interlace, width, height);
+                else snprintf(why, why_cap, "%s: %ux%u depth %d colour type %d interlace %d (expected %dx%d depth %d colour type %d)", path, w, h, depth, colour, interlace, width, height, want_depth, want_colour);
                 return 1;
             }
             have_hdr = true;
@@ -219,13 +257,29 @@ int decode_one(const char* path, int width, int height, uint8_t* out, char* why,
         pos += 12 + (size_t)len;
     }
     if (n_idat > 1) { z = joined.data(); zn = joined.size(); }
-    const size_t pitch = (size_t)width + 1;                      // filter byte + one row of 8-bit grey samples
+    const int row = width * bpp;                                 // bytes of one row of samples
+    const size_t pitch = (size_t)row + 1;                        // filter byte + one row
     if (raw.size() < pitch * (size_t)height) raw.resize(pitch * (size_t)height);
     const size_t raw_bytes = pitch * (size_t)height;
     // complete = the deflate stream ends where it says it does, holds exactly the image and its Adler-32 matches
     const bool complete = have_hdr && !crc_bad && !order_bad && n_idat > 0 && inflate_all(z, zn, raw.data(), raw_bytes);
     if (!complete) { snprintf(why, why_cap, "%s: corrupt or truncated PNG%s", path, crc_bad ? " (chunk CRC mismatch)" : ""); return 2; }
-    // un-filter (PNG spec 9.2; bpp = 1): row r of the image lands in out + r * width
+    // un-filter (PNG spec 9.2): row r of the image lands in out + r * row.  bpp = 1 has the fast paths below; the others go row by row
+    if (bpp != 1) {
+        const uint8_t* prev = nullptr;
+        for (int r = 0; r < height; ++r) {
+            const uint8_t* in = &raw[(size_t)r * pitch];
+            if (in[0] > 4) { snprintf(why, why_cap, "%s: bad filter type %d", path, in[0]); return 2; }
+            uint8_t* o = out + (size_t)r * row;
+            unfilter_row(in[0], in + 1, prev, o, row, bpp);
+            prev = o;
+        }
+        if (fmt == AV_PIX_GRAY16) {                              // the file's samples are big-endian: to host order, once every row is un-filtered
+            const size_t ns = (size_t)width * height;
+            for (size_t i = 0; i < ns; ++i) { const uint8_t hi = out[2 * i], lo = out[2 * i + 1]; const uint16_t v = (uint16_t)(hi << 8 | lo); memcpy(out + 2 * i, &v, 2); }
+        }
+        return 0;
+    }
     for (int r = 0; r < height; ++r) if (raw[(size_t)r * pitch] > 4) { snprintf(why, why_cap, "%s: bad filter type %d", path, raw[(size_t)r * pitch]); return 2; }
     const uint8_t* prev = nullptr;
     for (int r = 0; r < height; ++r) {
@@ -268,9 +322,9 @@ int decode_one(const char* path, int width, int height, uint8_t* out, char* why,
 
 }  // namespace
 
-AV_EXPORT int av_png_decode_gray8(const char* const* paths, int n, int width, int height, uint8_t* out, int64_t out_stride, int threads, int32_t* status)
+namespace {
+int decode_many(const char* who, const char* const* paths, int n, int width, int height, int fmt, uint8_t* out, int64_t out_stride, int threads, int32_t* status)
 {
-    if (!paths || n < 0 || width <= 0 || height <= 0 || !out || out_stride < (int64_t)width * height) { av_set_error("av_png_decode_gray8: bad arguments"); return AV_E_INVALID; }
     if (threads < 1) threads = 1;
     if (threads > 64) threads = 64;
     int worst = 0;
@@ -278,13 +332,50 @@ AV_EXPORT int av_png_decode_gray8(const char* const* paths, int n, int width, in
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads < n ? threads : (n > 0 ? n : 1))
     for (int i = 0; i < n; ++i) {
         char why[400] = "";
-        const int rc = paths[i] ? decode_one(paths[i], width, height, out + (size_t)i * out_stride, why, sizeof(why)) : 2;
+        const int rc = paths[i] ? decode_one(paths[i], width, height, fmt, out + (size_t)i * out_stride, why, sizeof(why)) : 2;
         if (status) status[i] = rc;
         if (rc) {
 #pragma omp critical(av_png_err)
             { if (rc > worst) { worst = rc; memcpy(msg, why, sizeof(msg)); } }
         }
     }
-    if (worst) { av_set_error("av_png_decode_gray8: %s", msg[0] ? msg : "null path"); return worst == 1 ? AV_E_CAPACITY : AV_E_INVALID; }
+    if (worst) { av_set_error("%s: %s", who, msg[0] ? msg : "null path"); return worst == 1 ? AV_E_CAPACITY : AV_E_INVALID; }
+    return AV_OK;
+}
+}  // namespace
+
+AV_EXPORT int av_png_decode_gray8(const char* const* paths, int n, int width, int height, uint8_t* out, int64_t out_stride, int threads, int32_t* status)
+{
+    if (!paths || n < 0 || width <= 0 || height <= 0 || !out || out_stride < (int64_t)width * height) { av_set_error("av_png_decode_gray8: bad arguments"); return AV_E_INVALID; }
+    return decode_many("av_png_decode_gray8", paths, n, width, height, AV_PIX_GRAY8, out, out_stride, threads, status);
+}
+
+AV_EXPORT int av_png_decode(const char* const* paths, int n, int width, int height, int pixel_format, void* out, int64_t out_stride_bytes, int threads,
+                            int32_t* status)
+{
+    int depth, colour, bpp;
+    if (!png_flavour(pixel_format, &depth, &colour, &bpp)) { av_set_error("av_png_decode: no PNG flavour holds pixel format %d (GRAY8, GRAY16, RGB8, RGBA8 are decoded)", pixel_format); return AV_E_INVALID; }
+    if (!paths || n < 0 || width <= 0 || height <= 0 || !out || out_stride_bytes < (int64_t)width * height * bpp) { av_set_error("av_png_decode: bad arguments"); return AV_E_INVALID; }
+    return decode_many("av_png_decode", paths, n, width, height, pixel_format, static_cast<uint8_t*>(out), out_stride_bytes, threads, status);
+}
+
+AV_EXPORT int av_png_probe(const char* path, int32_t* width, int32_t* height, int32_t* pixel_format)
+{
+    if (!path || !width || !height || !pixel_format) { av_set_error("av_png_probe: bad arguments"); return AV_E_INVALID; }
+    FILE* f = fopen(path, "rb");
+    if (!f) { av_set_error("av_png_probe: cannot open %s", path); return AV_E_INVALID; }
+    uint8_t b[33];
+    const size_t got = fread(b, 1, sizeof(b), f);
+    fclose(f);
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    if (got != sizeof(b) || memcmp(b, sig, 8) != 0 || memcmp(b + 12, "IHDR", 4) != 0 || be32(b + 8) < 13) { av_set_error("av_png_probe: %s: not a PNG file", path); return AV_E_INVALID; }
+    *width = (int32_t)be32(b + 16); *height = (int32_t)be32(b + 20);
+    const int depth = b[24], colour = b[25], interlace = b[28];
+    *pixel_format = -1;
+    if (!interlace)
+        for (int fmt = AV_PIX_GRAY8; fmt <= AV_PIX_BGRA8; ++fmt) {
+            int d, c, bpp;
+            if (png_flavour(fmt, &d, &c, &bpp) && d == depth && c == colour) *pixel_format = fmt;
+        }
     return AV_OK;
 }

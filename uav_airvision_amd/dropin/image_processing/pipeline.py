@@ -37,11 +37,16 @@ class ImageProcessingPipeline(object):
     def stereo_callback(self, stereo_msg):
         """pipeline.py:46-150: returns feature_msg(timestamp, [FeatureMeasurement])."""
         cam0_msg, cam1_msg = stereo_msg.cam0_msg, stereo_msg.cam1_msg
-        img0 = np.ascontiguousarray(cam0_msg.image, dtype=np.uint8)
-        img1 = np.ascontiguousarray(cam1_msg.image, dtype=np.uint8)
-        if img0.ndim != 2 or img0.shape != (self._engine.height, self._engine.width) or img1.shape != img0.shape:
-            raise ValueError('expected two uint8[%d,%d] images' % (self._engine.height, self._engine.width))
-        self._engine.step_host(img0, img1, [cam0_msg.timestamp])
+        if self._engine.pixel_format != 0:
+            # config.image_format (no counterpart in the reference): colour or 16-bit frames go to the engine as they are and are
+            # converted to 8-bit grey on the GPU; step_host refuses a wrong dtype or shape with a ValueError naming both
+            self._engine.step_host(cam0_msg.image, cam1_msg.image, [cam0_msg.timestamp])
+        else:
+            img0 = np.ascontiguousarray(cam0_msg.image, dtype=np.uint8)
+            img1 = np.ascontiguousarray(cam1_msg.image, dtype=np.uint8)
+            if img0.ndim != 2 or img0.shape != (self._engine.height, self._engine.width) or img1.shape != img0.shape:
+                raise ValueError('expected two uint8[%d,%d] images' % (self._engine.height, self._engine.width))
+            self._engine.step_host(img0, img1, [cam0_msg.timestamp])
         (ids, uv), = self._engine.read_features()
         feats = []
         for k in range(len(ids)):
@@ -84,7 +89,8 @@ class ImageProcessingPipeline(object):
         return d
 
     def equalized_image(self, cam=0):
-        """The equalised frame of camera `cam` the last stereo_callback worked on (config.use_clahe); refused without the switch."""
+        """The grey frame of camera `cam` the last stereo_callback worked on: equalised (config.use_clahe) and / or converted from
+        config.image_format; refused with neither."""
         return self._engine.read_image(0, cam)
 
     def close(self):

@@ -73,7 +73,44 @@ def pack_frontend_config(config, max_corners=None):
     c.clahe_tiles_x, c.clahe_tiles_y = [int(v) for v in getattr(config, 'clahe_tiles', (8, 8))]
     if getattr(config, 'use_clahe', False):
         c.flags |= N.AV_FE_CLAHE
+    # pixel format of the frames (AV_PIX_*); getattr: a config object without the two attributes is an 8-bit grey engine
+    c.pixel_format = N.pixel_format_code(getattr(config, 'image_format', 'gray8'))
+    c.gray16_shift = N.gray16_shift_value(getattr(config, 'gray16_shift', 8))
     return c
+
+
+def frame_shape(pixel_format, n, height, width):
+    """Shape of n frames of an AV_PIX_* format: [n, h, w] for the grey formats, [n, h, w, 3 | 4] for the colour ones."""
+    bpp = N.PIXEL_BYTES[pixel_format]
+    return (n, height, width) if bpp <= 2 else (n, height, width, bpp)
+
+
+def check_host_frames(what, a, pixel_format, n, height, width):
+    """A NumPy batch of n frames of an AV_PIX_* format as a C-contiguous array of exactly the dtype and shape the engine reads: uint16
+    [n, h, w] for gray16, uint8 [n, h, w, 3 | 4] for colour, uint8 [n, h, w] for gray8 ([h, w] / [h, w, c] is taken for n = 1).  Nothing
+    is converted: a wrong dtype or shape is a ValueError naming both."""
+    a = np.asarray(a)
+    want_dtype = np.uint16 if pixel_format == N.AV_PIX_GRAY16 else np.uint8
+    want = frame_shape(pixel_format, n, height, width)
+    shape = tuple(a.shape)
+    if n == 1 and shape == want[1:]:
+        shape = want
+    if a.dtype != want_dtype or shape != want:
+        raise ValueError('%s: %s frames are %s %s, got %s %s' % (what, N.PIXEL_FORMAT_NAMES[pixel_format], np.dtype(want_dtype).name, want, a.dtype, tuple(a.shape)))
+    return np.ascontiguousarray(a).reshape(want)
+
+
+def check_device_frames(what, t, pixel_format, n, height, width):
+    """The same for a cuda tensor; 16-bit frames are torch.uint16, or torch.int16 holding the same bits (older torch has no
+    unsigned 16-bit type).  The tensor must be contiguous: it is read where it lies."""
+    want = frame_shape(pixel_format, n, height, width)
+    dtypes = (torch.uint8,) if pixel_format != N.AV_PIX_GRAY16 else tuple(d for d in (getattr(torch, 'uint16', None), torch.int16) if d is not None)
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != want:
+        raise ValueError('%s: %s frames are %s %s, got %s %s' % (what, N.PIXEL_FORMAT_NAMES[pixel_format], ' / '.join(str(d) for d in dtypes), want,
+                                                               getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+    if not t.is_cuda or not t.is_contiguous():
+        raise ValueError('%s: a contiguous cuda tensor is needed' % what)
+    return t
 
 
 COUNTER_NAMES = ('before_tracking', 'after_tracking', 'after_matching', 'n_fast', 'n_candidates', 'n_new',
@@ -90,7 +127,13 @@ class FrontendEngine(object):
         inputs_persist: promise that the cuda tensors handed to `step` stay unmodified until the NEXT step has run
         (AV_FE_INPUTS_PERSIST, include/airvision.h): pyramid level 0 is then read in place instead of being copied.  The engine
         keeps a reference to the last cam0 tensor, so dropping yours is fine; overwriting it in place is not.  `step_host`
-        always works in place on the library's own staging slots.  Same results either way."""
+        always works in place on the library's own staging slots.  Same results either way.
+
+        config.image_format other than 'gray8' (and config.gray16_shift): every entry below takes frames of that format instead --
+        uint16 [S,h,w] for 'gray16' (cuda: torch.uint16, or torch.int16 holding the same bits), uint8 [S,h,w,3] for 'rgb8' / 'bgr8',
+        uint8 [S,h,w,4] for 'rgba8' / 'bgra8' -- and converts them to 8-bit grey on the GPU ahead of everything else (av_to_gray8 in
+        include/airvision.h has the arithmetic).  Nothing is cast on the way: a wrong dtype or shape is a ValueError naming both.
+        The caller's frames are never written; `read_image` returns the grey frame the step used."""
         self.config = config
         self.n_streams = int(n_streams)
         self.device = int(device)
@@ -102,6 +145,8 @@ class FrontendEngine(object):
             N.check(N.lib().av_frontend_create(C.byref(self._cfg), self.n_streams, self.device, C.byref(self._h)))
         self.max_features = N.lib().av_frontend_max_features(self._h)
         self.width, self.height = self._cfg.width, self._cfg.height
+        self.pixel_format = int(self._cfg.pixel_format)
+        self._frame_bytes = self.width * self.height * N.PIXEL_BYTES[self.pixel_format]      # img_stride of every entry point
         S, cap = self.n_streams, self.max_features
         self._ids = np.zeros((S, cap), np.int64)
         self._uv = np.zeros((S, cap, 4), np.float64)
@@ -137,33 +182,45 @@ class FrontendEngine(object):
     def step(self, img0, img1, timestamps):
         """img0/img1: uint8 cuda tensors [S,h,w] (contiguous); timestamps: S floats.  Enqueues only."""
         S = self.n_streams
-        assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
-        assert tuple(img0.shape) == (S, self.height, self.width) == tuple(img1.shape), (img0.shape, img1.shape)
-        assert img0.is_contiguous() and img1.is_contiguous()
+        if self.pixel_format != N.AV_PIX_GRAY8:
+            check_device_frames('step: img0', img0, self.pixel_format, S, self.height, self.width)
+            check_device_frames('step: img1', img1, self.pixel_format, S, self.height, self.width)
+        else:
+            assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
+            assert tuple(img0.shape) == (S, self.height, self.width) == tuple(img1.shape), (img0.shape, img1.shape)
+            assert img0.is_contiguous() and img1.is_contiguous()
         ts = (C.c_double * S)(*[float(t) for t in timestamps])
         with torch.cuda.device(self.device):
-            N.check(N.lib().av_frontend_step(self._h, N.dptr(img0), N.dptr(img1), self.height * self.width, ts, self._stream()))
+            N.check(N.lib().av_frontend_step(self._h, N.dptr(img0), N.dptr(img1), self._frame_bytes, ts, self._stream()))
         self._keep = (self._keep[1] if self._keep else None, (img0, img1))       # this frame's and the previous frame's tensors stay alive
 
     def prestage(self, img0, img1):
         """Build the pyramids of the NEXT step's images now (av_frontend_prestage): `step` with the same tensors then starts with its
         tracking launch.  Same results; the engine must have been created with inputs_persist=True."""
         S = self.n_streams
-        assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
-        assert tuple(img0.shape) == (S, self.height, self.width) == tuple(img1.shape) and img0.is_contiguous() and img1.is_contiguous()
+        if self.pixel_format != N.AV_PIX_GRAY8:
+            check_device_frames('prestage: img0', img0, self.pixel_format, S, self.height, self.width)
+            check_device_frames('prestage: img1', img1, self.pixel_format, S, self.height, self.width)
+        else:
+            assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
+            assert tuple(img0.shape) == (S, self.height, self.width) == tuple(img1.shape) and img0.is_contiguous() and img1.is_contiguous()
         with torch.cuda.device(self.device):
-            N.check(N.lib().av_frontend_prestage(self._h, N.dptr(img0), N.dptr(img1), self.height * self.width, self._stream()))
+            N.check(N.lib().av_frontend_prestage(self._h, N.dptr(img0), N.dptr(img1), self._frame_bytes, self._stream()))
         self._pre = (img0, img1)                                                # alive until the step that uses them
 
     def step_host(self, img0, img1, timestamps):
-        """numpy uint8 [S,h,w] (or [h,w] when S == 1)."""
+        """numpy uint8 [S,h,w] (or [h,w] when S == 1); frames of config.image_format otherwise (class docstring)."""
         S = self.n_streams
-        a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(S, self.height, self.width)
-        a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(S, self.height, self.width)
+        if self.pixel_format != N.AV_PIX_GRAY8:
+            a0 = check_host_frames('step_host: img0', img0, self.pixel_format, S, self.height, self.width)
+            a1 = check_host_frames('step_host: img1', img1, self.pixel_format, S, self.height, self.width)
+        else:
+            a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(S, self.height, self.width)
+            a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(S, self.height, self.width)
         ts = (C.c_double * S)(*[float(t) for t in np.atleast_1d(timestamps)])
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_step_host(self._h, a0.ctypes.data_as(C.c_void_p), a1.ctypes.data_as(C.c_void_p),
-                                                  self.height * self.width, ts, self._stream()))
+                                                  self._frame_bytes, ts, self._stream()))
 
     def frames_reserve(self, n_slots):
         """Allocate the shared frame store (av_frontend_frames_reserve): `n_slots` resident stereo frames."""
@@ -177,11 +234,15 @@ class FrontendEngine(object):
         n = len(sl)
         if n == 0:
             return
-        a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(n, self.height, self.width)
-        a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(n, self.height, self.width)
+        if self.pixel_format != N.AV_PIX_GRAY8:
+            a0 = check_host_frames('frames_upload: img0', img0, self.pixel_format, n, self.height, self.width)
+            a1 = check_host_frames('frames_upload: img1', img1, self.pixel_format, n, self.height, self.width)
+        else:
+            a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(n, self.height, self.width)
+            a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(n, self.height, self.width)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_frames_upload(self._h, sl.ctypes.data_as(C.c_void_p), n, a0.ctypes.data_as(C.c_void_p),
-                                                      a1.ctypes.data_as(C.c_void_p), self.height * self.width, self._stream()))
+                                                      a1.ctypes.data_as(C.c_void_p), self._frame_bytes, self._stream()))
 
     def step_frames(self, slot_of_stream, timestamps):
         """One step with stream s reading store entry slot_of_stream[s]; < 0 = no frame for that stream in this step."""
@@ -269,8 +330,9 @@ class FrontendEngine(object):
         return dict(zip(RANSAC_COUNT_NAMES, [int(v) for v in out]))
 
     def read_image(self, stream=0, cam=0):
-        """The level-0 image the last step used for camera `cam` of `stream` (config.use_clahe: the equalised frame), uint8[h, w].
-        Refused (AirvisionError, AV_E_INVALID) when the switch is off: level 0 is then the caller's own image."""
+        """The level-0 image the last step used for camera `cam` of `stream`, uint8[h, w]: the frame converted to 8-bit grey
+        (config.image_format other than 'gray8'), equalised with config.use_clahe.  Refused (AirvisionError, AV_E_INVALID) with
+        neither: level 0 is then the caller's own image."""
         out = np.empty((self.height, self.width), np.uint8)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_image(self._h, int(stream), int(cam), out.ctypes.data_as(C.c_void_p), self._stream()))

@@ -82,9 +82,11 @@ class BatchedRunner(object):
         if staged and share_frames:
             self.plan = SharedFramePlan(datasets, max_frames=max_frames)
             self.eng.frames_reserve(self.plan.n_slots)
-            stager = SharedFrameStager(self.plan, self.eng.height, self.eng.width, threads=host_threads)
+            stager = SharedFrameStager(self.plan, self.eng.height, self.eng.width, threads=host_threads, pixel_format=self.eng.pixel_format)
         elif staged:
-            stager = FrameStager(datasets, self.eng.height, self.eng.width, max_frames=max_frames, threads=host_threads)
+            stager = FrameStager(datasets, self.eng.height, self.eng.width, max_frames=max_frames, threads=host_threads, pixel_format=self.eng.pixel_format)
+        elif self.eng.pixel_format != 0:
+            raise ValueError('datasets that do not list their files are read as 8-bit grey frames: config.image_format must be gray8')
         try:
             return self._run(datasets, stager, max_frames, on_step)
         finally:
@@ -236,6 +238,29 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
     return trajs, dss
 
 
+def batch_pixel_format(dataset_paths, choice='gray8'):
+    """The config.image_format of one batch of sequences for --pixel-format `choice`.  'auto' probes the header of the first cam0 file
+    of every sequence (av_png_probe); all sequences of a batch must agree, since one engine reads one format: ValueError otherwise."""
+    if choice != 'auto':
+        return choice
+    from .euroc import EuRoCDataset, probe_png
+    found = {}
+    for p in dataset_paths:
+        if p in found:
+            continue
+        files = EuRoCDataset._list_images(os.path.join(p, 'mav0', 'cam0', 'data'))[0]
+        if not files:
+            raise ValueError('--pixel-format auto: %s has no cam0 frames to probe' % p)
+        fmt = probe_png(files[0])[2]
+        if fmt is None:
+            raise ValueError('--pixel-format auto: %s is a PNG flavour the decoder does not take (8 / 16-bit grey, RGB, RGBA are)' % files[0])
+        found[p] = fmt
+    if len(set(found.values())) > 1:
+        raise ValueError('--pixel-format auto: the sequences of one batch must share one pixel format, found ' +
+                         ', '.join('%s: %s' % (os.path.basename(os.path.normpath(p)), f) for p, f in found.items()))
+    return next(iter(found.values()))
+
+
 def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--root', help='directory holding the EuRoC sequences')
@@ -253,6 +278,9 @@ def make_parser():
     ap.add_argument('--clahe', action='store_true', help='equalise every frame (CLAHE) ahead of the pyramids, LK and FAST (config.use_clahe; off = the reference front-end)')
     ap.add_argument('--clahe-clip', type=float, default=None, metavar='C', help='clip limit (config.clahe_clip_limit, default 2.0; 0 = no clipping)')
     ap.add_argument('--clahe-tiles', nargs=2, type=int, default=None, metavar=('X', 'Y'), help='tile grid (config.clahe_tiles, default 8 8)')
+    ap.add_argument('--pixel-format', choices=['gray8', 'gray16', 'rgb8', 'rgba8', 'auto'], default='gray8',
+                    help='PNG flavour of the camera frames (config.image_format); auto = probe the first cam0 file of every sequence, which must agree within a batch')
+    ap.add_argument('--gray16-shift', type=int, default=None, metavar='N', help='16-bit frames: grey = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
     return ap
 
 
@@ -266,6 +294,10 @@ def apply_args(cfg, args):
         cfg.clahe_clip_limit = args.clahe_clip
     if args.clahe_tiles is not None:
         cfg.clahe_tiles = (int(args.clahe_tiles[0]), int(args.clahe_tiles[1]))
+    if getattr(args, 'pixel_format', 'gray8') != 'auto':          # auto: set per batch (batch_pixel_format)
+        cfg.image_format = getattr(args, 'pixel_format', 'gray8')
+    if getattr(args, 'gray16_shift', None) is not None:
+        cfg.gray16_shift = args.gray16_shift
     return cfg
 
 
@@ -309,6 +341,7 @@ def main(argv=None):
     t_all = time.perf_counter()
     for b0 in range(0, len(mine), args.batch):
         chunk = mine[b0:b0 + args.batch]
+        cfg.image_format = batch_pixel_format([os.path.join(root, jobs[j][0]) for j in chunk], args.pixel_format)
         trajs, dss = run_batched(cfg, [os.path.join(root, jobs[j][0]) for j in chunk], [jobs[j][1] for j in chunk], device=local, max_frames=args.max_frames,
                                  share_frames=not args.no_share_frames, stats=stats)
         for j, traj, ds in zip(chunk, trajs, dss):
@@ -329,6 +362,8 @@ def main(argv=None):
         rep = sweep_report(jobs, per_rank, elapsed, world)
         if cfg.use_clahe:
             rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
+        if args.pixel_format != 'gray8':
+            rep['pixel_format'] = dict(asked=args.pixel_format, last_batch=cfg.image_format, gray16_shift=cfg.gray16_shift)
         print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
