@@ -162,7 +162,7 @@ typedef struct av_frontend_config {
     double  clahe_clip_limit;                /* config.clahe_clip_limit (2.0); the three are read only with AV_FE_CLAHE */
     int32_t clahe_tiles_x, clahe_tiles_y;    /* config.clahe_tiles (8, 8); 1 .. AV_CLAHE_MAX_TILES    */
     int32_t pixel_format;                    /* config.image_format: AV_PIX_* of the frames handed to every entry path; 0 = 8-bit grey */
-    int32_t gray16_shift;                    /* config.gray16_shift: 0 .. 8, read only with AV_PIX_GRAY16 (checked always)            */
+    int32_t gray16_shift;                    /* config.gray16_shift: 0 .. 8, read only with the 16-bit formats (checked always)       */
 } av_frontend_config;
 
 typedef struct av_frontend av_frontend;
@@ -373,16 +373,43 @@ int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h
  *   colour to grey:  (9798 R + 19235 G + 3735 B + 16384) >> 15 in integer arithmetic.  The coefficients sum to 2^15, so R = G = B = g
  *                    gives g exactly and the result never exceeds 255.  Alpha is ignored.
  *   GRAY8:           the identity.
- * Not covered: Bayer mosaics, 16-bit colour, cameras of two sizes or formats, percentile or auto-range scaling of 16-bit data (CLAHE
- * after a fixed shift is the answer for now).
+ * Not covered: 16-bit colour, cameras of two sizes or formats, percentile or auto-range scaling of 16-bit data (CLAHE after a fixed
+ * shift is the answer for now).
+ *
+ * Bayer mosaics: the raw colour-filter-array frame of a colour machine-vision camera, one sample per pixel.  A pattern is named by the
+ * colours of the TOP-LEFT 2 x 2 block in reading order (OpenCV's BayerBG .. BayerGR name another corner: do not carry those names over).
+ *   format                     code   sample                      colours of pixels (0,0) (1,0) / (0,1) (1,1), as (x, y)
+ *   AV_PIX_BAYER_RGGB8  / 16   16/20  u8 / u16, host byte order   R G / G B
+ *   AV_PIX_BAYER_BGGR8  / 16   17/21                              B G / G R
+ *   AV_PIX_BAYER_GRBG8  / 16   18/22                              G R / B G
+ *   AV_PIX_BAYER_GBRG8  / 16   19/23                              G B / R G
+ * Bytes per pixel are 1 and 2.  The image has w >= 2 and h >= 2 samples (smaller: AV_E_INVALID).  Parity with cv2 is unpinned like the
+ * other formats' (OpenCV's own Bayer-to-grey is another filter and does not interpolate its border): this text is the contract,
+ * tests/bayer_ref.py states it in NumPy.
+ *   1. reduce    8-bit: s = v.  16-bit: s = min(255, v >> shift) for every sample before anything else (the GRAY16 rule; sensors with
+ *                10, 12 or 14 significant bits use shift 2, 4 or 6).
+ *   2. extend    BORDER_REFLECT_101 beyond the border: index -1 reads 1, index w reads w - 2.  Reflection keeps parity, so every
+ *                sample keeps its colour.
+ *   3. channels  at (x, y), each times four (plain bilinear demosaicing, no division yet): c = s(x, y), hs = s(x-1, y) + s(x+1, y),
+ *                vs = s(x, y-1) + s(x, y+1), ds = the sum of the four diagonal neighbours.
+ *                  R site:                             R4 = 4c,  G4 = hs + vs,  B4 = ds
+ *                  B site:                             B4 = 4c,  G4 = hs + vs,  R4 = ds
+ *                  G site whose row neighbours are R:  G4 = 4c,  R4 = 2 hs,     B4 = 2 vs
+ *                  G site whose row neighbours are B:  G4 = 4c,  B4 = 2 hs,     R4 = 2 vs
+ *   4. grey      (9798 R4 + 19235 G4 + 3735 B4 + 65536) >> 17 in integer arithmetic (at most 32768 * 1020 + 65536: it fits 32 bits).
+ *                The coefficients are the colour formats' own: a uniform mosaic of value g gives g exactly, nothing exceeds 255.
+ * Example: the RGGB image [[10, 200], [30, 90]] gives [[81, 131], [31, 81]].
+ * Not covered for mosaics: edge-aware demosaicing, packed 10 / 12-bit transports (Mono12p, RAW12), white balance beyond the fixed
+ * luma weights, two cameras of different patterns.
  *
  * av_to_gray8: n_img images of w x h pixels, image i at img_dev + i * img_stride_bytes (tightly packed rows), to tightly packed u8 at
  * out_dev + i * out_stride.  Images at 16-byte aligned addresses and strides (the strides count only when n_img > 1) go through as whole
  * vectors with the last w * h % 16 pixels byte by byte; a launch with any other address or stride goes byte by byte altogether.
- * shift is read for AV_PIX_GRAY16 only but checked always.  AV_E_INVALID with text for an unknown format, a shift outside 0 .. 8,
+ * A Bayer mosaic goes 16 columns per lane when w % 16 == 0 and the addresses and strides are aligned as above, one pixel per lane
+ * otherwise.  shift is read for AV_PIX_GRAY16 and the 16-bit Bayer formats only but checked always.  AV_E_INVALID with text for an unknown format, a shift outside 0 .. 8,
  * w * h > AV_MAX_IMAGE_PIXELS, strides smaller than an image, and out_dev overlapping the input.  The one exception: AV_PIX_GRAY8 with
  * out_dev == img_dev and equal strides is the identity in place and does nothing (any other AV_PIX_GRAY8 call is a strided copy, and
- * an overlap is refused like for the other formats).
+ * an overlap is refused like for the other formats).  Codes 6 .. 15 and 24 upwards are unknown formats.
  * ------------------------------------------------------------------------------------------- */
 #define AV_PIX_GRAY8  0
 #define AV_PIX_GRAY16 1
@@ -390,6 +417,14 @@ int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h
 #define AV_PIX_BGR8   3
 #define AV_PIX_RGBA8  4
 #define AV_PIX_BGRA8  5
+#define AV_PIX_BAYER_RGGB8  16
+#define AV_PIX_BAYER_BGGR8  17
+#define AV_PIX_BAYER_GRBG8  18
+#define AV_PIX_BAYER_GBRG8  19
+#define AV_PIX_BAYER_RGGB16 20
+#define AV_PIX_BAYER_BGGR16 21
+#define AV_PIX_BAYER_GRBG16 22
+#define AV_PIX_BAYER_GBRG16 23
 int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_img, int w, int h, int pixel_format, int shift,
                 uint8_t* out_dev, int64_t out_stride, void* stream);
 

@@ -21,18 +21,35 @@ AV_FE_RANSAC = 2
 AV_FE_CLAHE = 4
 AV_CLAHE_MAX_TILES = 16
 AV_PIX_GRAY8, AV_PIX_GRAY16, AV_PIX_RGB8, AV_PIX_BGR8, AV_PIX_RGBA8, AV_PIX_BGRA8 = 0, 1, 2, 3, 4, 5
+AV_PIX_BAYER_RGGB8, AV_PIX_BAYER_BGGR8, AV_PIX_BAYER_GRBG8, AV_PIX_BAYER_GBRG8 = 16, 17, 18, 19
+AV_PIX_BAYER_RGGB16, AV_PIX_BAYER_BGGR16, AV_PIX_BAYER_GRBG16, AV_PIX_BAYER_GBRG16 = 20, 21, 22, 23
 AV_RANSAC_MAX_PAIRS = 1920
 AV_RANSAC_MAX_HYPOTHESES = 64
 AV_RANSAC_PATH_FEW, AV_RANSAC_PATH_STILL, AV_RANSAC_PATH_MODEL, AV_RANSAC_PATH_NONE = 1, 2, 4, 8
 
 
-PIXEL_FORMATS = {'gray8': 0, 'gray16': 1, 'rgb8': 2, 'bgr8': 3, 'rgba8': 4, 'bgra8': 5}      # config.image_format -> AV_PIX_* (include/airvision.h)
+PIXEL_FORMATS = {'gray8': 0, 'gray16': 1, 'rgb8': 2, 'bgr8': 3, 'rgba8': 4, 'bgra8': 5,      # config.image_format -> AV_PIX_* (include/airvision.h)
+                 # Bayer mosaics, named by the colours of the top-left 2 x 2 block in reading order (not OpenCV's BayerBG .. names)
+                 'bayer_rggb8': 16, 'bayer_bggr8': 17, 'bayer_grbg8': 18, 'bayer_gbrg8': 19,
+                 'bayer_rggb16': 20, 'bayer_bggr16': 21, 'bayer_grbg16': 22, 'bayer_gbrg16': 23}
 PIXEL_FORMAT_NAMES = {v: k for k, v in PIXEL_FORMATS.items()}
-PIXEL_BYTES = {0: 1, 1: 2, 2: 3, 3: 3, 4: 4, 5: 4}
+PIXEL_BYTES = {0: 1, 1: 2, 2: 3, 3: 3, 4: 4, 5: 4, 16: 1, 17: 1, 18: 1, 19: 1, 20: 2, 21: 2, 22: 2, 23: 2}
+BAYER_PATTERNS = ('rggb', 'bggr', 'grbg', 'gbrg')             # pattern of code c: BAYER_PATTERNS[(c - 16) & 3]
+
+
+def is_bayer(fmt):
+    """An AV_PIX_* code names a Bayer mosaic."""
+    return AV_PIX_BAYER_RGGB8 <= fmt <= AV_PIX_BAYER_GBRG16
+
+
+def is_16bit(fmt):
+    """An AV_PIX_* code whose frames are uint16 arrays (gray16 and the 16-bit mosaics): the formats that read gray16_shift."""
+    return fmt == AV_PIX_GRAY16 or AV_PIX_BAYER_RGGB16 <= fmt <= AV_PIX_BAYER_GBRG16
 
 
 def pixel_format_code(name):
-    """config.image_format ('gray8', 'gray16', 'rgb8', 'bgr8', 'rgba8', 'bgra8') or an AV_PIX_* code -> AV_PIX_*; ValueError otherwise."""
+    """config.image_format ('gray8', 'gray16', 'rgb8', 'bgr8', 'rgba8', 'bgra8', 'bayer_{rggb,bggr,grbg,gbrg}{8,16}') or an AV_PIX_* code
+    -> AV_PIX_*; ValueError otherwise."""
     if isinstance(name, str) and name in PIXEL_FORMATS:
         return PIXEL_FORMATS[name]
     if isinstance(name, int) and not isinstance(name, bool) and name in PIXEL_FORMAT_NAMES:

@@ -51,7 +51,8 @@ class ConfigEuRoC(object):
         self.clahe_clip_limit = 2.0
         self.clahe_tiles = (8, 8)       # (tiles_x, tiles_y)
         # pixel format of the camera frames handed to the front-end (no counterpart in the reference, which assumes 8-bit grey):
-        # 'gray8' | 'gray16' | 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8'.  Anything but 'gray8' is converted to 8-bit grey on the GPU ahead of
+        # 'gray8' | 'gray16' | 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8' | 'bayer_{rggb,bggr,grbg,gbrg}{8,16}' (a raw Bayer mosaic, named by the
+        # colours of its top-left 2 x 2 block; gray16_shift applies to the 16-bit ones).  Anything but 'gray8' is converted to 8-bit grey on the GPU ahead of
         # everything else (av_to_gray8 in include/airvision.h).  gray16_shift: a 16-bit sample v becomes min(255, v >> shift); 8 = the
         # high byte, a sensor with 10 / 12 / 14 significant bits uses 2 / 4 / 6.
         self.image_format = 'gray8'

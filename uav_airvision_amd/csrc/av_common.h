@@ -252,3 +252,6 @@ int av_pixfmt_bytes(int fmt);
 int av_pixfmt_check(int fmt, int shift, const char* who);
 int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
                        int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index = nullptr);
+// bayer.hip: the same for the Bayer mosaic formats (AV_PIX_BAYER_*), w >= 2 and h >= 2; av_launch_to_gray8 hands them on
+int av_launch_bayer_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
+                             int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index);

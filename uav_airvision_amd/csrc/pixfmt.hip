@@ -89,11 +89,18 @@ __global__ __launch_bounds__(256) void to_gray8_kernel(PixArgs a)
 
 }  // namespace
 
-int av_pixfmt_bytes(int fmt) { return fmt >= AV_PIX_GRAY8 && fmt <= AV_PIX_BGRA8 ? pf_bytes(fmt) : 0; }
+int av_pixfmt_bytes(int fmt)
+{
+    if (fmt >= AV_PIX_BAYER_RGGB8 && fmt <= AV_PIX_BAYER_GBRG16) return fmt >= AV_PIX_BAYER_RGGB16 ? 2 : 1;      // one sample per pixel (bayer.hip)
+    return fmt >= AV_PIX_GRAY8 && fmt <= AV_PIX_BGRA8 ? pf_bytes(fmt) : 0;
+}
 
 int av_pixfmt_check(int fmt, int shift, const char* who)
 {
-    if (fmt < AV_PIX_GRAY8 || fmt > AV_PIX_BGRA8) { av_set_error("%s: unknown pixel format %d (AV_PIX_GRAY8 = 0 .. AV_PIX_BGRA8 = 5)", who, fmt); return AV_E_INVALID; }
+    if (av_pixfmt_bytes(fmt) == 0) {
+        av_set_error("%s: unknown pixel format %d (AV_PIX_GRAY8 = 0 .. AV_PIX_BGRA8 = 5, AV_PIX_BAYER_RGGB8 = 16 .. AV_PIX_BAYER_GBRG16 = 23)", who, fmt);
+        return AV_E_INVALID;
+    }
     if (shift < 0 || shift > 8) { av_set_error("%s: gray16 shift %d outside 0 .. 8", who, shift); return AV_E_INVALID; }
     return AV_OK;
 }
@@ -102,6 +109,7 @@ int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_str
                        int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index)
 {
     if (n_groups <= 0) return AV_OK;
+    if (fmt >= AV_PIX_BAYER_RGGB8) return av_launch_bayer_to_gray8(src0, src1, src_stride, dst0, dst1, dst_stride, n_groups, w, h, fmt, shift, st, index);      // a 3 x 3 stencil over rows: bayer.hip
     PixArgs a;
     memset(&a, 0, sizeof(a));
     a.src0 = src0; a.src1 = src1; a.dst0 = dst0; a.dst1 = dst1; a.src_stride = src_stride; a.dst_stride = dst_stride;
@@ -130,10 +138,13 @@ AV_EXPORT int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_i
     int rc = av_pixfmt_check(pixel_format, shift, "av_to_gray8");
     if (rc) return rc;
     if (w <= 0 || h <= 0 || (int64_t)w * h > AV_MAX_IMAGE_PIXELS) { av_set_error("av_to_gray8: w * h must be 1 .. AV_MAX_IMAGE_PIXELS = 2^24 (%d x %d)", w, h); return AV_E_INVALID; }
-    const int64_t npix = (int64_t)w * h, in_bytes = npix * pf_bytes(pixel_format);
+    const bool bayer = pixel_format >= AV_PIX_BAYER_RGGB8;
+    if (bayer && (w < 2 || h < 2)) { av_set_error("av_to_gray8: a Bayer mosaic is at least 2 x 2 samples (%d x %d)", w, h); return AV_E_INVALID; }
+    const int bpp = av_pixfmt_bytes(pixel_format);
+    const int64_t npix = (int64_t)w * h, in_bytes = npix * bpp;
     if (!img_dev || !out_dev || n_img < 0 || img_stride_bytes < in_bytes || out_stride < npix) {
         av_set_error("av_to_gray8: bad arguments (n_img %d, strides %lld / %lld bytes for %d x %d of %d bytes per pixel)", n_img, (long long)img_stride_bytes,
-                     (long long)out_stride, w, h, pf_bytes(pixel_format));
+                     (long long)out_stride, w, h, bpp);
         return AV_E_INVALID;
     }
     if (n_img == 0) return AV_OK;

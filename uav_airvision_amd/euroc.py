@@ -106,20 +106,26 @@ class EuRoCDataset(object):
 
 
 def frame_array(pixel_format, n, height, width, zeros=True):
-    """A host batch of n frames of a pixel format ('gray8' / 'gray16' / 'rgb8' / 'rgba8' or the AV_PIX_* code) as decode_batch fills it
-    and the front-end takes it: uint8 [n, h, w], uint16 [n, h, w], uint8 [n, h, w, 3 | 4]."""
+    """A host batch of n frames of a pixel format ('gray8' / 'gray16' / 'rgb8' / 'rgba8' / 'bayer_*8' / 'bayer_*16' or the AV_PIX_* code)
+    as decode_batch fills it and the front-end takes it: uint8 [n, h, w], uint16 [n, h, w], uint8 [n, h, w, 3 | 4]; a Bayer mosaic is
+    one sample per pixel, uint8 [n, h, w] or uint16 [n, h, w]."""
     from . import _native as N
     fmt = N.pixel_format_code(pixel_format)
     bpp = N.PIXEL_BYTES[fmt]
     shape = (n, height, width) if bpp <= 2 else (n, height, width, bpp)
-    return (np.zeros if zeros else np.empty)(shape, np.uint16 if fmt == N.AV_PIX_GRAY16 else np.uint8)
+    return (np.zeros if zeros else np.empty)(shape, np.uint16 if N.is_16bit(fmt) else np.uint8)
 
 
 def png_pixel_format(pixel_format):
     """The name of a pixel format that a PNG file can hold ('gray8', 'gray16', 'rgb8', 'rgba8'), from a name or an AV_PIX_* code.  PNG
-    stores no BGR order: 'bgr8' / 'bgra8' are a ValueError here, so that RGB files are never handed to an engine that reads BGR."""
+    stores no BGR order: 'bgr8' / 'bgra8' are a ValueError here, so that RGB files are never handed to an engine that reads BGR.
+    A raw Bayer mosaic on disk is a grey PNG: 'bayer_*8' gives 'gray8', 'bayer_*16' gives 'gray16' (the file cannot say that it is a
+    mosaic; the engine's config.image_format does)."""
     from . import _native as N
-    name = N.PIXEL_FORMAT_NAMES[N.pixel_format_code(pixel_format)]
+    fmt = N.pixel_format_code(pixel_format)
+    if N.is_bayer(fmt):
+        return 'gray16' if N.is_16bit(fmt) else 'gray8'
+    name = N.PIXEL_FORMAT_NAMES[fmt]
     if name not in ('gray8', 'gray16', 'rgb8', 'rgba8'):
         raise ValueError('PNG files hold gray8, gray16, rgb8 or rgba8 frames, not %s: decode such a sequence as rgb8 / rgba8 '
                          '(config.image_format) -- the files are in RGB order' % name)
@@ -210,7 +216,8 @@ class FrameStager(object):
     loader thread, the one just returned, the one returned before it)."""
 
     def __init__(self, datasets, height, width, max_frames=None, threads=16, pixel_format='gray8'):
-        """pixel_format: the flavour of the files and of the arrays returned (frame_array): 'gray8', 'gray16', 'rgb8', 'rgba8'."""
+        """pixel_format: the flavour of the files and of the arrays returned (frame_array): 'gray8', 'gray16', 'rgb8', 'rgba8'; a Bayer
+        name reads the grey flavour that holds the mosaic (png_pixel_format)."""
         from concurrent.futures import ThreadPoolExecutor
         self.S = len(datasets)
         self.its = [iter(d.stereo_files) for d in datasets]
@@ -313,7 +320,8 @@ class SharedFrameStager(object):
     asked for in order."""
 
     def __init__(self, plan, height, width, threads=16, ahead=3, pixel_format='gray8'):
-        """pixel_format: the flavour of the files and of the arrays returned (frame_array): 'gray8', 'gray16', 'rgb8', 'rgba8'."""
+        """pixel_format: the flavour of the files and of the arrays returned (frame_array): 'gray8', 'gray16', 'rgb8', 'rgba8'; a Bayer
+        name reads the grey flavour that holds the mosaic (png_pixel_format)."""
         from concurrent.futures import ThreadPoolExecutor
         self.plan, self.h, self.w, self.threads, self.ahead = plan, height, width, threads, ahead
         self.pixel_format = png_pixel_format(pixel_format)
@@ -368,14 +376,34 @@ def replay(dataset, imu_sinks, on_stereo, max_frames=None):
     return n
 
 
-def encode_frame(image, pixel_format='gray8'):
-    """An 8-bit grey frame as a frame of another format that converts back to it exactly: 'gray16' = g << 8, 'rgb8' / 'rgba8' / 'bgr8' /
-    'bgra8' = equal colour channels (alpha 255)."""
+BAYER_GAINS = (0.8, 1.0, 0.6)                    # default R, G, B gains of a synthetic mosaic (encode_frame)
+
+
+def bayer_site_colours(pixel_format, height, width):
+    """int [h, w]: the colour (0 R, 1 G, 2 B) of every site of a Bayer format, from the colours of its top-left 2 x 2 block."""
+    from . import _native as N
+    fmt = N.pixel_format_code(pixel_format)
+    if not N.is_bayer(fmt):
+        raise ValueError('%r is no Bayer mosaic format' % (pixel_format,))
+    block = np.array(['RGB'.index(ch) for ch in N.BAYER_PATTERNS[(fmt - 16) & 3].upper()]).reshape(2, 2)      # [y & 1, x & 1]
+    yy, xx = np.mgrid[0:height, 0:width]
+    return block[yy & 1, xx & 1]
+
+
+def encode_frame(image, pixel_format='gray8', gains=BAYER_GAINS, shift=8):
+    """An 8-bit grey frame as a frame of another format.  'gray16' = g << 8, 'rgb8' / 'rgba8' / 'bgr8' / 'bgra8' = equal colour channels
+    (alpha 255): these convert back to the frame exactly.  A Bayer format gives the raw mosaic of a scene whose R, G, B are the grey
+    value times `gains`: every site holds rint(g * gain of its colour) clipped to 255, as uint8 [..., h, w], or that value << shift as
+    uint16 for the 16-bit mosaics (config.gray16_shift = shift reads it back)."""
     from . import _native as N
     fmt = N.pixel_format_code(pixel_format)
     g = np.asarray(image, np.uint8)
     if fmt == N.AV_PIX_GRAY8:
         return g
+    if N.is_bayer(fmt):
+        gain = np.asarray(gains, np.float64)[bayer_site_colours(fmt, g.shape[-2], g.shape[-1])]
+        m = np.clip(np.rint(g.astype(np.float64) * gain), 0, 255).astype(np.uint8)
+        return m.astype(np.uint16) << N.gray16_shift_value(shift) if N.is_16bit(fmt) else m
     if fmt == N.AV_PIX_GRAY16:
         return g.astype(np.uint16) << 8
     out = np.repeat(g[..., None], N.PIXEL_BYTES[fmt], axis=-1)
@@ -384,7 +412,8 @@ def encode_frame(image, pixel_format='gray8'):
     return out
 
 
-def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None, write_csv=True, compress_level=6, pixel_format='gray8'):
+def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None, write_csv=True, compress_level=6, pixel_format='gray8',
+                       bayer_gains=BAYER_GAINS, gray16_shift=8):
     """Write a seeded synthetic stream (uav_airvision_amd.synth.SyntheticStream) as an EuRoC-layout directory
     `root/mav0/{cam0,cam1}/data/<ns>.png`, `imu0/data.csv`, `state_groundtruth_estimate0/data.csv`, so that the same
     reader / replay / sweep code that runs on the real dataset (which is not redistributable and not present on the build
@@ -392,18 +421,22 @@ def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None
     Ground truth = the analytic trajectory of the stream (position of the IMU frame; identity orientation columns).
     `frame_range=(a, b)` writes only the images of frames a..b-1 (several writer processes can share one sequence);
     `write_csv=False` skips the IMU / ground-truth files; `compress_level` is zlib's (any level is lossless; 1 writes 5x faster).
-    `pixel_format` 'gray16' / 'rgb8' / 'rgba8' writes the same frames as 16-bit grey / RGB / RGBA PNGs (encode_frame)."""
+    `pixel_format` 'gray16' / 'rgb8' / 'rgba8' writes the same frames as 16-bit grey / RGB / RGBA PNGs (encode_frame); a Bayer name
+    writes the raw mosaic of the frames coloured by `bayer_gains` as 8- or 16-bit grey PNGs (16-bit samples << `gray16_shift`)."""
     from PIL import Image
-    if pixel_format not in ('gray8', 'gray16', 'rgb8', 'rgba8'):
-        raise ValueError('write_euroc_layout: PNG holds gray8, gray16, rgb8 or rgba8 frames, not %r' % (pixel_format,))
+    from . import _native as N
+    bayer = pixel_format in N.PIXEL_FORMATS and N.is_bayer(N.PIXEL_FORMATS[pixel_format])
+    if pixel_format not in ('gray8', 'gray16', 'rgb8', 'rgba8') and not bayer:
+        raise ValueError('write_euroc_layout: PNG holds gray8, gray16, rgb8 or rgba8 frames or a Bayer mosaic, not %r' % (pixel_format,))
+    enc = (lambda im: encode_frame(im, pixel_format, bayer_gains, gray16_shift)) if bayer else (lambda im: encode_frame(im, pixel_format))
     for cam in ('cam0', 'cam1'):
         os.makedirs(os.path.join(root, 'mav0', cam, 'data'), exist_ok=True)
     a, b = (0, stream.n_frames) if frame_range is None else frame_range
     for k in range(a, b):
         m = stream.frame(k)
         name = '%d.png' % int(round(m.timestamp * 1e9))
-        Image.fromarray(encode_frame(m.cam0_image, pixel_format)).save(os.path.join(root, 'mav0', 'cam0', 'data', name), compress_level=compress_level)
-        Image.fromarray(encode_frame(m.cam1_image, pixel_format)).save(os.path.join(root, 'mav0', 'cam1', 'data', name), compress_level=compress_level)
+        Image.fromarray(enc(m.cam0_image)).save(os.path.join(root, 'mav0', 'cam0', 'data', name), compress_level=compress_level)
+        Image.fromarray(enc(m.cam1_image)).save(os.path.join(root, 'mav0', 'cam1', 'data', name), compress_level=compress_level)
     if not write_csv:
         return root
     os.makedirs(os.path.join(root, 'mav0', 'imu0'), exist_ok=True)

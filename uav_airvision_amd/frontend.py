@@ -87,10 +87,10 @@ def frame_shape(pixel_format, n, height, width):
 
 def check_host_frames(what, a, pixel_format, n, height, width):
     """A NumPy batch of n frames of an AV_PIX_* format as a C-contiguous array of exactly the dtype and shape the engine reads: uint16
-    [n, h, w] for gray16, uint8 [n, h, w, 3 | 4] for colour, uint8 [n, h, w] for gray8 ([h, w] / [h, w, c] is taken for n = 1).  Nothing
-    is converted: a wrong dtype or shape is a ValueError naming both."""
+    [n, h, w] for gray16 and the 16-bit Bayer mosaics, uint8 [n, h, w, 3 | 4] for colour, uint8 [n, h, w] for gray8 and the 8-bit
+    mosaics ([h, w] / [h, w, c] is taken for n = 1).  Nothing is converted: a wrong dtype or shape is a ValueError naming both."""
     a = np.asarray(a)
-    want_dtype = np.uint16 if pixel_format == N.AV_PIX_GRAY16 else np.uint8
+    want_dtype = np.uint16 if N.is_16bit(pixel_format) else np.uint8
     want = frame_shape(pixel_format, n, height, width)
     shape = tuple(a.shape)
     if n == 1 and shape == want[1:]:
@@ -104,7 +104,7 @@ def check_device_frames(what, t, pixel_format, n, height, width):
     """The same for a cuda tensor; 16-bit frames are torch.uint16, or torch.int16 holding the same bits (older torch has no
     unsigned 16-bit type).  The tensor must be contiguous: it is read where it lies."""
     want = frame_shape(pixel_format, n, height, width)
-    dtypes = (torch.uint8,) if pixel_format != N.AV_PIX_GRAY16 else tuple(d for d in (getattr(torch, 'uint16', None), torch.int16) if d is not None)
+    dtypes = (torch.uint8,) if not N.is_16bit(pixel_format) else tuple(d for d in (getattr(torch, 'uint16', None), torch.int16) if d is not None)
     if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != want:
         raise ValueError('%s: %s frames are %s %s, got %s %s' % (what, N.PIXEL_FORMAT_NAMES[pixel_format], ' / '.join(str(d) for d in dtypes), want,
                                                                getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
@@ -131,7 +131,7 @@ class FrontendEngine(object):
 
         config.image_format other than 'gray8' (and config.gray16_shift): every entry below takes frames of that format instead --
         uint16 [S,h,w] for 'gray16' (cuda: torch.uint16, or torch.int16 holding the same bits), uint8 [S,h,w,3] for 'rgb8' / 'bgr8',
-        uint8 [S,h,w,4] for 'rgba8' / 'bgra8' -- and converts them to 8-bit grey on the GPU ahead of everything else (av_to_gray8 in
+        uint8 [S,h,w,4] for 'rgba8' / 'bgra8', the raw mosaic as uint8 [S,h,w] for 'bayer_*8' and uint16 [S,h,w] for 'bayer_*16' -- and converts them to 8-bit grey on the GPU ahead of everything else (av_to_gray8 in
         include/airvision.h has the arithmetic).  Nothing is cast on the way: a wrong dtype or shape is a ValueError naming both.
         The caller's frames are never written; `read_image` returns the grey frame the step used."""
         self.config = config

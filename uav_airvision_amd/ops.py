@@ -251,22 +251,25 @@ def clahe(img, clip_limit=2.0, tiles=(8, 8), out=None, return_lut=False, device=
 
 def to_gray8(img, pixel_format, shift=8, out=None, device=0):
     """Camera frames of another pixel format to 8-bit grey (av_to_gray8; formats and arithmetic are written out in include/airvision.h).
-    pixel_format: 'gray8' | 'gray16' | 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8' or the AV_PIX_* code.  img: [n, h, w] or [h, w] for the grey
-    formats -- uint16 for 'gray16' (a cuda tensor may also be torch.int16 holding the same bits) -- and uint8 [n, h, w, c] or [h, w, c]
+    pixel_format: 'gray8' | 'gray16' | 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8' | 'bayer_{rggb,bggr,grbg,gbrg}{8,16}' or the AV_PIX_* code.
+    img: [n, h, w] or [h, w] for the grey formats and the Bayer mosaics (at least 2 x 2: ValueError otherwise) -- uint16 for 'gray16' and
+    'bayer_*16' (a cuda tensor may also be torch.int16 holding the same bits) -- and uint8 [n, h, w, c] or [h, w, c]
     with c = 3 / 4 for the colour ones; a cuda tensor or anything torch.as_tensor takes.  A cuda tensor is read where it lies: each
-    image must be contiguous, the images may be any distance apart (a slice of a larger tensor), at any address.  shift: 'gray16' only,
-    0 .. 8.  Returns a uint8 cuda tensor [n, h, w] or [h, w] -- `out` itself if given (uint8 cuda, that shape, each image contiguous;
+    image must be contiguous, the images may be any distance apart (a slice of a larger tensor), at any address.  shift: the 16-bit
+    formats only, 0 .. 8.  Returns a uint8 cuda tensor [n, h, w] or [h, w] -- `out` itself if given (uint8 cuda, that shape, each image contiguous;
     it must not overlap img)."""
     fmt = N.pixel_format_code(pixel_format)
     shift = N.gray16_shift_value(shift)
     t = torch.as_tensor(img)
     bpp = N.PIXEL_BYTES[fmt]
     colour = bpp >= 3
-    dtypes = (torch.uint16, torch.int16) if fmt == N.AV_PIX_GRAY16 else (torch.uint8,)
+    dtypes = (torch.uint16, torch.int16) if N.is_16bit(fmt) else (torch.uint8,)
     core = 3 if colour else 2                                  # dimensions of one image
     if t.dtype not in dtypes or t.dim() not in (core, core + 1) or (colour and t.shape[-1] != bpp):
         raise ValueError('to_gray8: %s images are %s [n, h, w%s] or [h, w%s], got %s %s' % (
             N.PIXEL_FORMAT_NAMES[fmt], ' / '.join(str(d) for d in dtypes), ', %d' % bpp if colour else '', ', %d' % bpp if colour else '', t.dtype, tuple(t.shape)))
+    if N.is_bayer(fmt) and (t.shape[-1] < 2 or t.shape[-2] < 2):
+        raise ValueError('to_gray8: a Bayer mosaic is at least 2 x 2 samples, got %s' % (tuple(t.shape),))
     t = t.to(_dev(device))
     batched = t.dim() == core + 1
     tb = t if batched else t.unsqueeze(0)

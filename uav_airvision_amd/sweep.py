@@ -261,6 +261,9 @@ def batch_pixel_format(dataset_paths, choice='gray8'):
     return next(iter(found.values()))
 
 
+BAYER_FORMATS = ['bayer_%s%d' % (p, b) for b in (8, 16) for p in ('rggb', 'bggr', 'grbg', 'gbrg')]
+
+
 def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--root', help='directory holding the EuRoC sequences')
@@ -278,9 +281,12 @@ def make_parser():
     ap.add_argument('--clahe', action='store_true', help='equalise every frame (CLAHE) ahead of the pyramids, LK and FAST (config.use_clahe; off = the reference front-end)')
     ap.add_argument('--clahe-clip', type=float, default=None, metavar='C', help='clip limit (config.clahe_clip_limit, default 2.0; 0 = no clipping)')
     ap.add_argument('--clahe-tiles', nargs=2, type=int, default=None, metavar=('X', 'Y'), help='tile grid (config.clahe_tiles, default 8 8)')
-    ap.add_argument('--pixel-format', choices=['gray8', 'gray16', 'rgb8', 'rgba8', 'auto'], default='gray8',
-                    help='PNG flavour of the camera frames (config.image_format); auto = probe the first cam0 file of every sequence, which must agree within a batch')
-    ap.add_argument('--gray16-shift', type=int, default=None, metavar='N', help='16-bit frames: grey = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
+    ap.add_argument('--pixel-format', choices=['gray8', 'gray16', 'rgb8', 'rgba8', 'auto'] + BAYER_FORMATS, default='gray8',
+                    help='PNG flavour of the camera frames (config.image_format); auto = probe the first cam0 file of every sequence, which must agree within a batch.  '
+                         'bayer_<pattern>8 / bayer_<pattern>16 (pattern = the colours of the top-left 2 x 2 block): the files are grey PNGs holding a raw Bayer mosaic, '
+                         'demosaiced to grey on the GPU; auto never chooses a Bayer format, since a file cannot say that it is a mosaic')
+    ap.add_argument('--gray16-shift', type=int, default=None, metavar='N',
+                    help='16-bit frames, grey or Bayer: sample = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
     return ap
 
 
