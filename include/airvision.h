@@ -163,6 +163,8 @@ typedef struct av_frontend_config {
     int32_t clahe_tiles_x, clahe_tiles_y;    /* config.clahe_tiles (8, 8); 1 .. AV_CLAHE_MAX_TILES    */
     int32_t pixel_format;                    /* config.image_format: AV_PIX_* of the frames handed to every entry path; 0 = 8-bit grey */
     int32_t gray16_shift;                    /* config.gray16_shift: 0 .. 8, read only with the 16-bit formats (checked always)       */
+    int32_t image_downscale;                 /* config.image_downscale: 0 / 1 = off, 2 or 4 = bin the grey frames f x f ("Binning" below) */
+    int32_t reserved1;                       /* keeps the size a multiple of 8; must be 0            */
 } av_frontend_config;
 
 typedef struct av_frontend av_frontend;
@@ -223,6 +225,31 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * of the unmodified pipeline run on the converted frames.  With AV_PIX_GRAY8 nothing is launched and nothing more is allocated.
  * Both cameras have one size and one format.  av_frontend_create refuses an unknown format or a shift outside 0 .. 8, AV_E_INVALID,
  * before a device is touched. */
+
+/* Binning: av_frontend_config.image_downscale = f = 2 or 4 (av_downscale below has the arithmetic).  width / height stay the size of
+ * the frames handed to the entry points and the intrinsics stay those of the full-size camera; the engine works on the binned image
+ * of w = width / f by h = height / f pixels (both must divide) and derives its calibration itself, from the pixel-centre map
+ * X = f x + (f - 1) / 2, in double precision and in exactly this order:
+ *   fx' = fx / f;  fy' = fy / f;  cx' = (cx - (f - 1) / 2) / f;  cy' = (cy - (f - 1) / 2) / f;  norm_unit' = norm_unit * f
+ * for both cameras.  Distortion coefficients, extrinsics, R0to1 and E are unchanged; stereo_threshold, ransac_threshold, fast_threshold,
+ * the grid, lk_win and max_corners apply to the binned image as they stand.  Order of the input stage: raw frame -> conversion to grey
+ * (pixel_format other than AV_PIX_GRAY8) -> binning -> CLAHE (AV_FE_CLAHE, at the binned size) -> pyramids / LK / FAST.  Everything past
+ * the stage is sized by w x h: pyramids, FAST mask, cell lists, raster bits, the engine-owned level 0 ([3][n_streams][w * h], which
+ * binning always uses) and the frame store's entries.  Only the entry points' image arguments (img_stride >= width * height * bytes per
+ * pixel), the staging slots of av_frontend_step_host and the pinned ring and device staging of av_frontend_frames_upload are sized by
+ * the input.  With AV_PIX_GRAY8 the binning reads the caller's (or the staging slot's) frames directly; with any other format the
+ * conversion writes a full-size grey scratch of the engine's ([2][n_streams][width * height]; the frame store has one of its own, sized by the largest upload)
+ * that the binning then reads.  It holds for av_frontend_step with and without AV_FE_INPUTS_PERSIST, av_frontend_prestage (the stage
+ * runs there, the step that follows with the same pointers skips it) and av_frontend_step_host: past the stage the step runs as with
+ * persisting inputs.  av_frontend_frames_upload copies the full-size frames to its device staging and bins them into the store on the
+ * copy stream, after the conversion and before CLAHE, the pyramids and FAST (an entry named twice gets its later frame);
+ * av_frontend_step_frames is what it was.  The launches count under class 0 of av_frontend_enable_timing, inside the input stage's
+ * span.  The caller's images are never written.  The published message is in normalised undistorted coordinates and is that of the
+ * unmodified pipeline run on the binned frames with the calibration above; av_frontend_read_image returns the w x h frame and the
+ * pixel coordinates of av_frontend_read_grid are pixels of the binned image.  av_frontend_create refuses a factor outside {0, 1, 2, 4},
+ * a non-zero reserved1, a size the factor does not divide and a binned size that fails the size rules (a pyramid level not larger
+ * than AV_PYR_BORDER), AV_E_INVALID, before a device is touched.  With 0 or 1 the step enqueues exactly what it always did and nothing
+ * more is allocated.  Box filter only; one factor for both cameras; the thresholds are not retuned for the smaller image. */
 
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
@@ -303,7 +330,8 @@ int av_frontend_features_dev(av_frontend* fe, const int64_t** ids_dev, const dou
 
 /* Pipeline state visible to callers (pipeline.py:33-40): the grid of the frame just published
  * (= prev_features after the callback returns).  Per feature k of stream `stream`:
- * ids[k], lifetime[k], cell[k], pts[k*4] = cam0 x,y, cam1 x,y (pixels, float32).  Synchronises. */
+ * ids[k], lifetime[k], cell[k], pts[k*4] = cam0 x,y, cam1 x,y (pixels, float32; with image_downscale = 2 or 4: pixels of the
+ * binned image the engine works on).  Synchronises. */
 int av_frontend_read_grid(av_frontend* fe, int stream_idx, int64_t* ids, int32_t* lifetime, int32_t* cell,
                           float* pts, int cap, int32_t* n_out, int64_t* next_feature_id, void* stream);
 
@@ -321,9 +349,10 @@ int av_frontend_read_match_counts(av_frontend* fe, int stream_idx, int32_t out[2
  * AV_RANSAC_PATH_* codes below.  Synchronises. */
 int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, int32_t out[4], void* stream);
 
-/* The level-0 image the last step used for camera `cam` (0 / 1) of one stream of an engine created with AV_FE_CLAHE or with a
- * pixel_format other than AV_PIX_GRAY8, i.e. the grey frame the step worked on, equalised if AV_FE_CLAHE is set: width * height bytes
- * into out_host.  AV_E_INVALID with neither (level 0 is then the caller's own image),
+/* The level-0 image the last step used for camera `cam` (0 / 1) of one stream of an engine created with AV_FE_CLAHE, with a
+ * pixel_format other than AV_PIX_GRAY8 or with image_downscale = 2 or 4, i.e. the grey frame the step worked on, binned if
+ * image_downscale is set and equalised if AV_FE_CLAHE is set: (width / f) * (height / f) bytes, the processed size, into out_host
+ * (width * height without binning).  AV_E_INVALID with none of the three (level 0 is then the caller's own image),
  * before the first step, and for a stream whose av_frontend_step_frames entries were negative from the start.  The image comes from where
  * the LAST step read it: the frame store after av_frontend_step_frames, the engine's own buffer after the other steps.  Between an
  * av_frontend_prestage and the step it serves the cam1 image of the last step is gone (its slot holds the next frame's): cam 1 is then
@@ -427,6 +456,31 @@ int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h
 #define AV_PIX_BAYER_GBRG16 23
 int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_img, int w, int h, int pixel_format, int shift,
                 uint8_t* out_dev, int64_t out_stride, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Binning of 8-bit grey frames by f = 2 or 4.  No counterpart in the reference (other VIO stacks run their front-end on a reduced
+ * image with scaled intrinsics -- OpenVINS' downsample_cameras -- and most sensors bin 2 x 2 themselves); this text is the contract,
+ * tests/downscale_ref.py states it in NumPy.
+ *   input    W x H samples with W % f == 0 and H % f == 0; output w x h with w = W / f, h = H / f
+ *   pixel    out(x, y) = (sum of the f x f input block at (f x .. f x + f - 1, f y .. f y + f - 1) + f * f / 2) >> (2 log2 f):
+ *            (a + b + c + d + 2) >> 2 for f = 2, (sum of 16 + 8) >> 4 for f = 4.  Integers only, no border rule.
+ *   camera   output pixel x covers input pixels f x .. f x + f - 1, centre X = f x + (f - 1) / 2: a pinhole camera of the binned image
+ *            has fx' = fx / f, fy' = fy / f, cx' = (cx - (f - 1) / 2) / f, cy' = (cy - (f - 1) / 2) / f and the distortion coefficients
+ *            of the full-size one (av_frontend_config.image_downscale applies exactly these).
+ * Example: f = 2 on [[1, 2], [3, 5]] gives [[3]] (13 >> 2); a uniform image of value g gives g.
+ * av_downscale: n_img images, image i at img_dev + i * img_stride (tightly packed W * H u8), to tightly packed w * h u8 at
+ * out_dev + i * out_stride.  With w % 16 == 0 and 16-byte aligned addresses and strides (the strides count only when n_img > 1) a lane
+ * takes 16 output pixels from f rows of f 16-byte vectors; anything else goes one output pixel per lane.  AV_E_INVALID with text for a
+ * factor other than 2 or 4, W or H the factor does not divide, W * H > AV_MAX_IMAGE_PIXELS, strides smaller than an image, null
+ * pointers, n_img < 0 and out_dev overlapping the input (never in place).  n_img == 0 is AV_OK.
+ * Not covered: Gaussian / pyrDown filtering, odd factors, cropping, a fused convert-and-bin pass.
+ * ------------------------------------------------------------------------------------------- */
+int av_downscale(const uint8_t* img_dev, int64_t img_stride, int n_img, int W, int H, int factor,
+                 uint8_t* out_dev, int64_t out_stride, void* stream);
+/* TEST-ONLY observable, not part of the supported interface (it may change or go without notice): 1 if av_downscale with these
+ * arguments takes 16 output pixels per lane, 0 if one (or if the arguments are not a valid call).  It is the launcher's own rule,
+ * exported so that tests/test_gpu_downscale_op.py can assert which kernel a case reached.  Pure host function. */
+int av_downscale_vector_path(const uint8_t* img_dev, int64_t img_stride, int n_img, int W, int factor, const uint8_t* out_dev, int64_t out_stride);
 
 /* ---------------------------------------------------------------------------------------------
  * Two-point RANSAC on the temporal matches of ONE camera (no counterpart in the reference: feature_tracker.py:135-136 is where

@@ -1,0 +1,185 @@
+"""The front-end engine with config.image_downscale = f fed full-size frames against the unmodified CPU oracle front-end fed the frames
+tests/downscale_ref.py binned and the calibration of frontend.downscaled_config: published ids and uv bit for bit on every frame, in
+every entry path; with CLAHE and RANSAC; behind the Bayer conversion; placement in a batch; read-backs; factor 1 is off."""
+import numpy as np
+import pytest
+
+import clahe_ref as cr
+from clahe_helpers import MODES, Cached, make_cfg as _cfg, run_engine, run_oracle, same as _same
+from downscale_helpers import MIN_FEATURES, Binned, against_oracle, check_reference
+
+pytestmark = pytest.mark.gpu
+
+NF = 6                       # 752 x 480
+NF_BIG = 4                   # 832 x 640
+STREAM = dict(seed=17, n_frames=NF, motion_scale=2.0)
+
+
+def _dcfg(cfg):
+    from uav_airvision_amd.frontend import downscaled_config
+    return downscaled_config(cfg)
+
+
+@pytest.fixture(scope='module')
+def base():
+    from uav_airvision_amd.synth import SyntheticStream
+    return Cached(SyntheticStream(_cfg(), **STREAM), equalise=False)
+
+
+@pytest.fixture(scope='module')
+def ref2(base):
+    """The oracle on the 2 x 2 binned frames of `base` (computed once, shared, never changed)."""
+    binned = Binned(base, 2)
+    ref = run_oracle(_dcfg(_cfg(image_downscale=2)), binned)
+    check_reference(ref, NF)
+    return binned, ref
+
+
+def _big_cfg(**kw):
+    from uav_airvision_amd.synth import scaled_config
+    cfg = scaled_config(_cfg(), 832, 640)
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+@pytest.fixture(scope='module')
+def big():
+    from uav_airvision_amd.synth import SyntheticStream
+    return Cached(SyntheticStream(_big_cfg(), seed=21, n_frames=NF_BIG, motion_scale=1.5), equalise=False)
+
+
+@pytest.mark.parametrize('mode', MODES)
+def test_752x480_by_two_in_every_entry_path(base, ref2, mode):
+    """Processed width 376: one output pixel per lane.  step, step + INPUTS_PERSIST, prestage, step_host and the frame store; the
+    caller's arrays and tensors are unchanged (asserted inside run_engine); read_image is the binned frame."""
+    binned, ref = ref2
+    got, images = run_engine(_cfg(image_downscale=2), [base], mode=mode, images_of=0)
+    against_oracle(ref, got[0], '752x480 f2 ' + mode, images, binned)
+
+
+@pytest.mark.parametrize('mode', ['step', 'frames'])
+@pytest.mark.parametrize('f', [2, 4])
+def test_832x640_by_two_and_four(big, f, mode):
+    """Processed widths 416 and 208: whole vectors.  At f = 4 the last pyramid level is 26 x 20, just above AV_PYR_BORDER."""
+    cfg = _big_cfg(image_downscale=f)
+    binned = Binned(big, f)
+    assert binned.frame(0).cam0_image.shape == (640 // f, 832 // f)
+    ref = run_oracle(_dcfg(cfg), binned)
+    got, images = run_engine(cfg, [big], mode=mode, images_of=0)
+    against_oracle(ref, got[0], '832x640 f%d %s' % (f, mode), images, binned)
+
+
+def test_with_clahe_and_ransac(base):
+    """Binning, then CLAHE at the binned size, then the tracker with its outlier rejection: against the RANSAC oracle on
+    clahe_ref.clahe(downscale_ref.downscale(frame)); the reference's decisions are clear of their thresholds (margin >= 1e-9)."""
+    from test_gpu_ransac_engine import run_oracle as run_ransac_oracle
+    cfg = _cfg(image_downscale=2, use_clahe=True, use_ransac=True)
+    binned = Binned(base, 2, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
+    ref = run_ransac_oracle(_dcfg(cfg), binned)
+    assert all(r['margin'] >= 1e-9 for r in ref), [r['margin'] for r in ref]
+    for mode in ('step', 'frames'):
+        got, images = run_engine(cfg, [base], mode=mode, images_of=0)
+        against_oracle(ref, got[0], 'clahe + ransac ' + mode, images, binned)
+
+
+@pytest.mark.parametrize('mode', ['step', 'host', 'frames'])
+def test_behind_the_bayer_conversion(base, mode):
+    """image_format = 'bayer_rggb8': conversion into the full-size scratch, then binning: against the oracle on
+    downscale_ref.downscale(bayer_ref.to_gray8(mosaic))."""
+    from bayer_helpers import Mosaicked, run_engine as run_raw
+    st = Mosaicked(base, 'bayer_rggb8', NF)
+    cfg = _cfg(image_downscale=2, image_format='bayer_rggb8')
+    binned = Binned(st, 2)
+    ref = run_oracle(_dcfg(_cfg(image_downscale=2)), binned)
+    got, images = run_raw(cfg, [st], mode=mode, images_of=0)
+    against_oracle(ref, got[0], 'bayer f2 ' + mode, images, binned)
+    assert not np.array_equal(st.frame(0).cam0_image, base.frame(0).cam0_image)      # (the conversion is not the identity)
+
+
+def test_the_frame_store_scratch_grows_with_a_larger_upload(base):
+    """Bayer conversion and binning together: an upload of one frame, then one of three (the full-size grey scratch of the store has
+    to grow), then a step on an entry of each: read_image is downscale_ref.downscale(bayer_ref.to_gray8(mosaic)) of the right frame."""
+    from bayer_helpers import Mosaicked
+    from uav_airvision_amd.frontend import FrontendEngine
+    st = Mosaicked(base, 'bayer_rggb8', 4)
+    binned = Binned(st, 2)
+    eng = FrontendEngine(_cfg(image_downscale=2, image_format='bayer_rggb8'), n_streams=1)
+    eng.frames_reserve(40)
+    eng.frames_upload(np.array([5], np.int32), st.raw[0][1][None], st.raw[0][2][None])
+    many = list(range(1, 4)) * 7                                  # 21 frames: more than the first upload's capacity and its slack of 16
+    eng.frames_upload(np.arange(10, 10 + len(many), dtype=np.int32), np.stack([st.raw[k][1] for k in many]), np.stack([st.raw[k][2] for k in many]))
+    for entry, k in ((5, 0), (10, 1), (10 + len(many) - 1, 3)):
+        eng.step_frames([entry], [st.raw[k][0]])
+        eng.read_features()
+        assert np.array_equal(eng.read_image(0, 0), binned.frame(k).cam0_image) and np.array_equal(eng.read_image(0, 1), binned.frame(k).cam1_image), (entry, k)
+    eng.close()
+
+
+def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
+    """Three distinct streams in one batch, in the device path and through the frame store: each publishes what it publishes alone
+    (and what the oracle publishes on its binned frames)."""
+    from uav_airvision_amd.synth import SyntheticStream
+    cfg = _cfg(image_downscale=2)
+    batch = [Cached(SyntheticStream(cfg, seed=201 + i, n_frames=NF, motion_scale=1.0 + 0.3 * i), equalise=False) for i in range(3)]
+    assert not np.array_equal(batch[0].frame(0).cam0_image, batch[1].frame(0).cam0_image)
+    refs = [run_oracle(_dcfg(cfg), Binned(b, 2)) for b in batch]
+    assert not all(np.array_equal(a['uv'], b['uv']) for a, b in zip(refs[0], refs[1]))
+    for mode in ('step', 'frames'):
+        got = run_engine(cfg, batch, mode=mode)
+        for pos in range(3):
+            against_oracle(refs[pos], got[pos], 'batch %s stream %d' % (mode, pos))
+
+
+def test_sizes_and_read_backs(base, ref2):
+    from uav_airvision_amd import _native as N
+    from uav_airvision_amd.frontend import FrontendEngine
+    binned, ref = ref2
+    eng = FrontendEngine(_cfg(image_downscale=2), n_streams=1)
+    assert (eng.width, eng.height, eng.input_width, eng.input_height, eng.downscale) == (376, 240, 752, 480, 2)
+    m = base.frame(0)
+    with pytest.raises(ValueError):
+        eng.step_host(binned.frame(0).cam0_image, binned.frame(0).cam1_image, [m.timestamp])      # processed-size frames are not what it takes
+    eng.step_host(m.cam0_image, m.cam1_image, [m.timestamp])
+    (ids, uv), = eng.read_features()
+    assert np.array_equal(ids, ref[0]['ids']) and np.array_equal(uv.view(np.uint64), ref[0]['uv'].view(np.uint64))
+    im = eng.read_image(0, 0)
+    assert im.shape == (240, 376) and np.array_equal(im, binned.frame(0).cam0_image)
+    g = eng.read_grid(0)                                                # pixel coordinates of the binned image
+    assert len(g['ids']) >= MIN_FEATURES and g['cam0'][:, 0].max() < 376 and g['cam0'][:, 1].max() < 240
+    assert g['cam0'][:, 0].max() > 376 * 0.6 and g['cam0'][:, 1].max() > 240 * 0.6
+    eng.close()
+    # 752 x 480 by 4 leaves 188 x 120, which does not hold the four pyramid levels of the default configuration
+    with pytest.raises(N.AirvisionError, match='downscale') as e:
+        FrontendEngine(_cfg(image_downscale=4), n_streams=1)
+    assert e.value.code == N.AV_E_INVALID
+
+
+def test_factor_one_is_off(base):
+    """image_downscale = 1 equals a config object without the attribute: the same outputs and the same launch-span counts per step;
+    read_image is still refused.  A factor of 2 adds no span either: the binning runs inside the input stage's one."""
+    from uav_airvision_amd import _native as N
+    from uav_airvision_amd.frontend import FrontendEngine
+
+    class Bare(object):
+        pass
+    bare = Bare()
+    for k, v in vars(_cfg()).items():
+        if k != 'image_downscale':
+            setattr(bare, k, v)
+    assert not hasattr(bare, 'image_downscale')
+    for mode in ('step', 'host', 'frames'):
+        off, sp_off = run_engine(_cfg(image_downscale=1), [base], mode=mode, timing=True)
+        none, sp_none = run_engine(bare, [base], mode=mode, timing=True)
+        assert all(len(a[0]) >= MIN_FEATURES for a in off[0][1:])
+        assert all(_same(a, b) for a, b in zip(off[0], none[0])) and sp_off == sp_none, mode
+        _on, sp_on = run_engine(_cfg(image_downscale=2), [base], mode=mode, timing=True)
+        assert [s['pyramid'] for s in sp_on] == [s['pyramid'] for s in sp_off], mode
+    eng = FrontendEngine(_cfg(image_downscale=1), n_streams=1)
+    m = base.frame(0)
+    eng.step_host(m.cam0_image, m.cam1_image, [m.timestamp])
+    eng.read_features()
+    with pytest.raises(N.AirvisionError) as e:
+        eng.read_image(0, 0)
+    assert e.value.code == N.AV_E_INVALID
+    eng.close()

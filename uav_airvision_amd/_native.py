@@ -5,6 +5,7 @@ raises when the HIP call fails.  torch is imported first so that the library bin
 runtime torch already loaded (same SONAME), i.e. one runtime / one context per process.
 """
 import ctypes as C
+import numbers
 import os
 
 import torch  # noqa: F401  (must be loaded before libairvision_hip.so, see module docstring)
@@ -64,6 +65,13 @@ def gray16_shift_value(shift):
     return int(shift)
 
 
+def downscale_value(factor):
+    """config.image_downscale -> 1, 2 or 4; ValueError otherwise (bool, 0, fractions, other factors)."""
+    if isinstance(factor, bool) or not isinstance(factor, numbers.Real) or int(factor) != factor or int(factor) not in (1, 2, 4):
+        raise ValueError('image_downscale %r is none of 1, 2, 4' % (factor,))
+    return int(factor)
+
+
 DISTORTION_MODELS = {'radtan': 0, 'equidistant': 1}          # AV_DISTORTION_* (include/airvision.h)
 
 
@@ -101,7 +109,8 @@ class FrontendConfig(C.Structure):
                 ('ransac_threshold', C.c_double), ('ransac_success_probability', C.c_double),
                 ('ransac_seed', C.c_uint32), ('reserved0', C.c_int32),
                 ('clahe_clip_limit', C.c_double), ('clahe_tiles_x', C.c_int32), ('clahe_tiles_y', C.c_int32),
-                ('pixel_format', C.c_int32), ('gray16_shift', C.c_int32)]
+                ('pixel_format', C.c_int32), ('gray16_shift', C.c_int32),
+                ('image_downscale', C.c_int32), ('reserved1', C.c_int32)]
 
 
 # name -> (restype, argtypes); the list doubles as the export check of tests/test_abi.py
@@ -166,6 +175,8 @@ SIGNATURES = {
     'av_png_decode': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P]),
     'av_png_probe': (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'av_to_gray8': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    'av_downscale': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    'av_downscale_vector_path': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     'av_quat_to_rotation': (C.c_int, [_P, _P]),
     'av_rotation_to_quat': (C.c_int, [_P, _P]),
     'av_quat_multiply': (C.c_int, [_P, _P, _P]),

@@ -57,6 +57,11 @@ class ConfigEuRoC(object):
         # high byte, a sensor with 10 / 12 / 14 significant bits uses 2 / 4 / 6.
         self.image_format = 'gray8'
         self.gray16_shift = 8
+        # 2 x 2 / 4 x 4 binning of every (grey) frame on the GPU ahead of CLAHE and the pyramids (no counterpart in the reference;
+        # av_downscale in include/airvision.h): 1 = off, 2 or 4.  cam*_resolution and cam*_intrinsics stay those of the full-size camera;
+        # the engine works on the binned image with the calibration of frontend.downscaled_config.  The thresholds below, the grid
+        # and patch_size apply to the binned image as they stand.
+        self.image_downscale = 1
         self.stereo_threshold = 5
         self.max_iteration = 30
         self.track_precision = 0.01

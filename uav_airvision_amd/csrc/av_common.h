@@ -255,3 +255,8 @@ int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_str
 // bayer.hip: the same for the Bayer mosaic formats (AV_PIX_BAYER_*), w >= 2 and h >= 2; av_launch_to_gray8 hands them on
 int av_launch_bayer_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
                              int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index);
+// downscale.hip: 2 x 2 / 4 x 4 binning (f = 2 or 4) of n_groups tightly packed W x H grey frames of one camera (src1 / dst1 null) or of
+// two into tightly packed (W / f) x (H / f) ones; W % f == 0 and H % f == 0.  Groups, strides and index as av_launch_to_gray8 (a negative
+// entry skips the group).  Never in place.
+int av_launch_downscale(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
+                        int n_groups, int W, int H, int f, hipStream_t st, const int* index = nullptr);

@@ -649,7 +649,8 @@ struct av_frontend {
         bool l0_in_place = true;                 // false if the pyramid launcher had to write padded level-0 copies (unaligned geometry)
         std::vector<int> prev;                   // host: slot of every stream's previous frame (-1: none yet)
         struct Up { uint8_t* pin = nullptr; int* idx_h = nullptr; int* idx_d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false;
-                    uint8_t* raw_d = nullptr; };      // pixel_format != GRAY8: the raw frames on the device; idx_h / idx_d then hold a second list, the conversion's
+                    uint8_t* raw_d = nullptr; };      // pixel_format != GRAY8 or binning: the frames as uploaded, on the device; idx_h / idx_d then hold a second list, that of the launch that writes the store
+        uint8_t* gray_d = nullptr; size_t gray_cap = 0;       // both: the conversion's full-size grey frames of ONE upload, read by the binning that follows it on the copy stream (uploads are serialised there: one scratch serves the whole ring)
         Up up[4]; int up_next = 0;               // upload staging ring (pinned frames + the slot list of the upload's kernels)
         hipEvent_t uploaded = nullptr; bool any_upload = false;      // copy stream: the newest upload's kernels have finished
         hipEvent_t stepped = nullptr; bool any_step = false;          // step stream: the newest step has finished
@@ -676,6 +677,10 @@ struct av_frontend {
     // pixel_format != AV_PIX_GRAY8: the frames are converted to 8-bit grey into the same level 0 (pixfmt.hip), ahead of the equalisation;
     // own_l0 = the engine owns level 0 (either feature); bpp = bytes per pixel of the frames the entry points are handed
     int fmt = AV_PIX_GRAY8, fmt_shift = 8, bpp = 1; bool own_l0 = false;
+    // image_downscale = 2 / 4: the frames the entry points are handed are in_w x in_h and are binned into that level 0 (downscale.hip),
+    // after the conversion and ahead of the equalisation; cfg then holds the PROCESSED size d.w x d.h and the calibration scaled to it.
+    // gray_full: the conversion's full-size grey output when both are set, [2][S][in_w * in_h] (the frame store: FrameStore::gray_d)
+    int ds = 1, in_w = 0, in_h = 0; uint8_t* gray_full = nullptr;
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
     explicit av_frontend(int S) : streams(S) {}
@@ -772,7 +777,18 @@ int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64
     const FeDev& d = fe->d;
     const av_frontend_config& c = fe->cfg;
     Span sp(fe, 0, st);
-    if (fe->fmt != AV_PIX_GRAY8) {
+    if (fe->ds > 1) {                          // (conversion into the full-size scratch,) binning into the engine's level 0
+        uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
+        const int64_t hw = (int64_t)d.w * d.h, in_hw = (int64_t)fe->in_w * fe->in_h;
+        int rc;
+        if (fe->fmt != AV_PIX_GRAY8) {
+            uint8_t* g0 = fe->gray_full; uint8_t* g1 = fe->gray_full + (size_t)d.S * in_hw;
+            if ((rc = av_launch_to_gray8(img0, img1, img_stride, g0, g1, in_hw, d.S, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st))) return rc;
+            img0 = g0; img1 = g1; img_stride = in_hw;
+        }
+        if ((rc = av_launch_downscale(img0, img1, img_stride, e0, e1, hw, d.S, fe->in_w, fe->in_h, fe->ds, st))) return rc;
+        img0 = e0; img1 = e1; img_stride = hw; inputs_persist = true;
+    } else if (fe->fmt != AV_PIX_GRAY8) {
         uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
         const int64_t hw = (int64_t)d.w * d.h;
         int rc = av_launch_to_gray8(img0, img1, img_stride, e0, e1, hw, d.S, d.w, d.h, fe->fmt, fe->fmt_shift, st);
@@ -930,6 +946,30 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         return AV_E_INVALID;
     }
     if (av_pixfmt_check(cfg->pixel_format, cfg->gray16_shift, "av_frontend_create")) return AV_E_INVALID;
+    // image_downscale: from here on `cfg` is the configuration of the PROCESSED image (binned size, calibration scaled to it, in the
+    // order include/airvision.h gives); in_w x in_h is what the entry points are handed
+    const int in_w = cfg->width, in_h = cfg->height;
+    const int ds = cfg->image_downscale == 0 ? 1 : cfg->image_downscale;
+    av_frontend_config scaled;
+    if ((ds != 1 && ds != 2 && ds != 4) || cfg->reserved1 != 0) {
+        av_set_error("av_frontend_create: image_downscale %d is none of 0, 1, 2, 4 (or reserved1 = %d is not 0)", cfg->image_downscale, cfg->reserved1);
+        return AV_E_INVALID;
+    }
+    if (ds > 1) {
+        if (in_w % ds || in_h % ds) { av_set_error("av_frontend_create: image_downscale %d does not divide %d x %d", ds, in_w, in_h); return AV_E_INVALID; }
+        scaled = *cfg;
+        scaled.width = in_w / ds; scaled.height = in_h / ds;
+        const double f = (double)ds, half = (f - 1.0) / 2.0;
+        for (double* k : {scaled.cam0_intrinsics, scaled.cam1_intrinsics}) { k[0] = k[0] / f; k[1] = k[1] / f; k[2] = (k[2] - half) / f; k[3] = (k[3] - half) / f; }
+        scaled.norm_unit = scaled.norm_unit * f;
+        av_pyr_layout probe;
+        if (av_pyramid_layout(scaled.width, scaled.height, scaled.lk_levels, &probe)) {
+            av_set_error("av_frontend_create: image_downscale %d leaves %d x %d, which does not hold %d pyramid levels larger than %d pixels", ds, scaled.width, scaled.height,
+                         scaled.lk_levels, AV_PYR_BORDER);
+            return AV_E_INVALID;
+        }
+        cfg = &scaled;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { av_set_error("av_frontend_create: no HIP device visible"); return AV_E_NODEVICE; }
     if (device < 0 || device >= ndev) { av_set_error("av_frontend_create: device %d out of range (%d visible)", device, ndev); return AV_E_INVALID; }
@@ -1034,8 +1074,10 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         fe->ransac = true;
     }
     fe->fmt = cfg->pixel_format; fe->fmt_shift = cfg->gray16_shift; fe->bpp = av_pixfmt_bytes(cfg->pixel_format);
-    fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8;
+    fe->ds = ds; fe->in_w = in_w; fe->in_h = in_h;
+    fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8 || ds > 1;
     if (fe->own_l0) A(fe->eq, (size_t)3 * S * w * h)
+    if (ds > 1 && fe->fmt != AV_PIX_GRAY8) A(fe->gray_full, (size_t)2 * S * in_w * in_h)
     if (clahe) {
         A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
         fe->clahe = true;
@@ -1086,6 +1128,7 @@ AV_EXPORT void av_frontend_destroy(av_frontend* fe)
         if (u.raw_d) (void)hipFree(u.raw_d);
         if (u.done) (void)hipEventDestroy(u.done);
     }
+    if (fe->fs.gray_d) (void)hipFree(fe->fs.gray_d);
     if (fe->fs.uploaded) (void)hipEventDestroy(fe->fs.uploaded);
     if (fe->fs.stepped) (void)hipEventDestroy(fe->fs.stepped);
     if (fe->copy_stream) (void)hipStreamDestroy(fe->copy_stream);
@@ -1131,7 +1174,7 @@ AV_EXPORT int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_
 // Needs AV_FE_INPUTS_PERSIST (the images are read again by the step itself); a step that comes with other images builds its own.
 AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride, void* stream)
 {
-    if (!fe || !img0_dev || !img1_dev || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
+    if (!fe || !img0_dev || !img1_dev || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
@@ -1148,7 +1191,7 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
 AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride,
                                const double* timestamps, void* stream)
 {
-    if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) {
+    if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) {
         av_set_error("av_frontend_step: bad arguments");
         return AV_E_INVALID;
     }
@@ -1158,12 +1201,12 @@ AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const u
 AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, const uint8_t* img1_host, int64_t img_stride,
                                     const double* timestamps, void* stream)
 {
-    if (!fe || !img0_host || !img1_host || !timestamps || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) {
+    if (!fe || !img0_host || !img1_host || !timestamps || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) {
         av_set_error("av_frontend_step_host: bad arguments");
         return AV_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t img_bytes = (size_t)fe->d.w * fe->d.h * fe->bpp;      // the staging slots carry the frames in their own format
+    const size_t img_bytes = (size_t)fe->in_w * fe->in_h * fe->bpp;    // the staging slots carry the frames in their own format and size
     const int S = fe->d.S;
     AV_HIP(hipSetDevice(fe->device));
     av_frontend::HostSlot& h = fe->hs[fe->hs_next];
@@ -1226,7 +1269,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
                                         int64_t img_stride, void* stream)
 {
     (void)stream;
-    if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < (int64_t)fe->d.w * fe->d.h * fe->bpp) {
+    if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) {
         av_set_error("av_frontend_frames_upload: bad arguments");
         return AV_E_INVALID;
     }
@@ -1245,8 +1288,10 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     AV_HIP(hipSetDevice(fe->device));
     const FeDev& d = fe->d;
     const size_t hw = (size_t)d.w * d.h;
-    const bool raw = fe->fmt != AV_PIX_GRAY8;
-    const size_t fb = hw * fe->bpp;                                 // bytes of one camera's frame as the caller hands it over
+    const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
+    const bool raw = conv || bin;                                   // the frames go through a kernel on their way into the store
+    const size_t in_hw = (size_t)fe->in_w * fe->in_h;
+    const size_t fb = in_hw * fe->bpp;                              // bytes of one camera's frame as the caller hands it over
     av_frontend::FrameStore::Up& u = fs.up[fs.up_next];
     fs.up_next = (fs.up_next + 1) % 4;
     if (u.used) AV_HIP(hipEventSynchronize(u.done));                // the staging area's previous upload has left it
@@ -1261,13 +1306,20 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
         if (!u.done) AV_HIP(hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
         u.cap = cap;
     }
+    // grows only.  Earlier uploads' launches on the copy stream may still read the old scratch, so the copy stream is drained before it is
+    // freed: the caller stalls once per growth (an upload larger than any before it), never otherwise
+    if (conv && bin && (size_t)n > fs.gray_cap) {
+        if (fs.gray_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.gray_d); fs.gray_d = nullptr; fs.gray_cap = 0; }
+        AV_HIP(hipMalloc((void**)&fs.gray_d, ((size_t)n + 16) * 2 * in_hw));
+        fs.gray_cap = (size_t)n + 16;
+    }
 #pragma omp parallel for schedule(static) num_threads(n >= 8 ? 8 : 1)
     for (int i = 0; i < 2 * n; ++i) {
         const int f = i >> 1, cam = i & 1;
         memcpy(u.pin + ((size_t)2 * f + cam) * fb, (cam ? img1_host : img0_host) + (size_t)f * img_stride, fb);
     }
     for (int i = 0; i < n; ++i) u.idx_h[i] = slots[i];
-    if (raw) {                       // the conversion's list: an entry named twice is written by its last frame only (what the copies of grey frames leave)
+    if (raw) {                       // the list of the launch that writes the store: an entry named twice is written by its last frame only (what the copies of grey frames leave)
         std::vector<int> last((size_t)fs.n_slots, -1);
         for (int i = 0; i < n; ++i) last[slots[i]] = i;
         for (int i = 0; i < n; ++i) u.idx_h[n + i] = last[slots[i]] == i ? slots[i] : -1;
@@ -1278,9 +1330,18 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     if (fs.any_step) AV_HIP(hipStreamWaitEvent(cs, fs.stepped, 0));
     AV_HIP(hipMemcpyAsync(u.idx_d, u.idx_h, sizeof(int) * (raw ? 2 : 1) * n, hipMemcpyHostToDevice, cs));
     int rc;
-    if (raw) {                       // raw frames to the ring entry's device buffer in one copy, then converted into their store entries
+    if (raw) {                       // the frames to the ring entry's device buffer in one copy, then converted and / or binned into their store entries
         AV_HIP(hipMemcpyAsync(u.raw_d, u.pin, (size_t)n * 2 * fb, hipMemcpyHostToDevice, cs));
-        if ((rc = av_launch_to_gray8(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->fmt, fe->fmt_shift, cs, u.idx_d + n))) return rc;
+        if (!bin) {
+            if ((rc = av_launch_to_gray8(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->fmt, fe->fmt_shift, cs, u.idx_d + n))) return rc;
+        } else {
+            const uint8_t* g = u.raw_d;
+            if (conv) {              // every frame of the upload to full-size grey, in upload order; the binning then picks the ones that reach the store
+                if ((rc = av_launch_to_gray8(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb), fs.gray_d, fs.gray_d + in_hw, (int64_t)(2 * in_hw), n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, cs, nullptr))) return rc;
+                g = fs.gray_d;
+            }
+            if ((rc = av_launch_downscale(g, g + in_hw, (int64_t)(2 * in_hw), fs.img, fs.img + hw, (int64_t)(2 * hw), n, fe->in_w, fe->in_h, fe->ds, cs, u.idx_d + n))) return rc;
+        }
     }
     for (int i = 0; i < n && !raw;) {                                // runs of consecutive entries go down in one copy
         int j = i + 1;
@@ -1440,7 +1501,7 @@ AV_EXPORT int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, in
 AV_EXPORT int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* out_host, void* stream)
 {
     if (!fe || stream_idx < 0 || stream_idx >= fe->d.S || cam < 0 || cam > 1 || !out_host) { av_set_error("av_frontend_read_image: bad arguments"); return AV_E_INVALID; }
-    if (!fe->own_l0) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE and with 8-bit grey input: level 0 is the caller's own image"); return AV_E_INVALID; }
+    if (!fe->own_l0) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE, with 8-bit grey input and without image_downscale: level 0 is the caller's own image"); return AV_E_INVALID; }
     if (!fe->stepped) { av_set_error("av_frontend_read_image: no step has run yet"); return AV_E_INVALID; }
     if (cam == 1 && fe->pre_on && !fe->stepped_frames) {
         av_set_error("av_frontend_read_image: the cam1 image of the last step has been replaced by av_frontend_prestage (read it before prestaging)");

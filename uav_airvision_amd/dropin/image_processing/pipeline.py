@@ -26,7 +26,9 @@ class ImageProcessingPipeline(object):
         self.curr_features = [[] for _ in range(config.grid_num)]
         # config.use_clahe (no counterpart in the reference): the engine equalises every frame ahead of everything else; a viewer set
         # here is shown the image the front-end actually worked on (update_image, the hook of viewer.py:45-49)
+        # config.image_downscale 2 / 4: the callbacks still take full-size frames; the same hook shows the binned frame
         self.use_clahe = bool(getattr(config, 'use_clahe', False))
+        self.downscale = self._engine.downscale
         self.viewer = None
 
     # ---- reference callbacks -----------------------------------------------------------------
@@ -44,8 +46,8 @@ class ImageProcessingPipeline(object):
         else:
             img0 = np.ascontiguousarray(cam0_msg.image, dtype=np.uint8)
             img1 = np.ascontiguousarray(cam1_msg.image, dtype=np.uint8)
-            if img0.ndim != 2 or img0.shape != (self._engine.height, self._engine.width) or img1.shape != img0.shape:
-                raise ValueError('expected two uint8[%d,%d] images' % (self._engine.height, self._engine.width))
+            if img0.ndim != 2 or img0.shape != (self._engine.input_height, self._engine.input_width) or img1.shape != img0.shape:
+                raise ValueError('expected two uint8[%d,%d] images' % (self._engine.input_height, self._engine.input_width))
             self._engine.step_host(img0, img1, [cam0_msg.timestamp])
         (ids, uv), = self._engine.read_features()
         feats = []
@@ -57,7 +59,7 @@ class ImageProcessingPipeline(object):
         self.prev_cam0_msg = cam0_msg
         self.prev_pyr0 = cam0_msg.image
         self.first_frame = False
-        if self.use_clahe and self.viewer is not None:
+        if (self.use_clahe or self.downscale > 1) and self.viewer is not None:
             self.viewer.update_image(self.equalized_image(0))
         return _feature_msg(cam0_msg.timestamp, feats)
 
@@ -89,8 +91,8 @@ class ImageProcessingPipeline(object):
         return d
 
     def equalized_image(self, cam=0):
-        """The grey frame of camera `cam` the last stereo_callback worked on: equalised (config.use_clahe) and / or converted from
-        config.image_format; refused with neither."""
+        """The grey frame of camera `cam` the last stereo_callback worked on, at the processed size: converted from
+        config.image_format, binned (config.image_downscale) and / or equalised (config.use_clahe); refused with none of them."""
         return self._engine.read_image(0, cam)
 
     def close(self):

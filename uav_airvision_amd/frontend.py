@@ -5,6 +5,7 @@ One engine owns S independent stereo streams on one GPU.  This is the throughput
 Reference surface mirrored: ImageProcessingPipeline.{__init__, imu_callback, stereo_callback}
 (reference: src/image_processing/pipeline.py:14-150).
 """
+import copy
 import ctypes as C
 
 import numpy as np
@@ -19,14 +20,47 @@ def default_max_corners(width, height):
     return max(8192, -(-8192 * int(width) * int(height) // (752 * 480)))
 
 
+def downscale_factor(config):
+    """config.image_downscale (1 when the object has no such attribute) as 1, 2 or 4; ValueError for anything else and for an image
+    size the factor does not divide."""
+    f = N.downscale_value(getattr(config, 'image_downscale', 1))
+    w, h = [int(v) for v in config.cam0_resolution]
+    if w % f or h % f:
+        raise ValueError('image_downscale %d does not divide the image size %d x %d' % (f, w, h))
+    return f
+
+
+def downscaled_config(config):
+    """A copy of `config` for the image the engine works on when config.image_downscale = f is 2 or 4: cam0 / cam1_resolution divided
+    by f, cam0 / cam1_intrinsics scaled by the pixel-centre map X = f x + (f - 1) / 2 -- fx / f, fy / f, (cx - (f - 1) / 2) / f,
+    (cy - (f - 1) / 2) / f, in double precision and in this order, exactly what the engine does (include/airvision.h) -- and
+    image_downscale = 1.  Distortion, extrinsics and thresholds are unchanged.  An engine of this configuration, handed frames binned
+    with ops.downscale, publishes what the engine of `config` publishes from the full-size ones."""
+    f = downscale_factor(config)
+    out = copy.copy(config)
+    half = (f - 1) / 2.0
+    for cam in ('cam0', 'cam1'):
+        w, h = [int(v) for v in getattr(config, cam + '_resolution')]
+        if w % f or h % f:
+            raise ValueError('image_downscale %d does not divide the %s size %d x %d' % (f, cam, w, h))
+        fx, fy, cx, cy = [float(v) for v in getattr(config, cam + '_intrinsics')]
+        setattr(out, cam + '_resolution', np.array([w // f, h // f]))
+        setattr(out, cam + '_intrinsics', np.array([fx / f, fy / f, (cx - half) / f, (cy - half) / f]))
+    out.image_downscale = 1
+    return out
+
+
 def pack_frontend_config(config, max_corners=None):
     """Build the packed av_frontend_config from a reference-style config object.  The
     extrinsics-derived matrices are computed with numpy exactly as the reference does
-    (imu_processor.py:10-16, stereo_matcher.py:47,90-91,103-104).  max_corners None: default_max_corners of the image size."""
+    (imu_processor.py:10-16, stereo_matcher.py:47,90-91,103-104).  max_corners None: default_max_corners of the processed image
+    size (the image size divided by config.image_downscale).  width / height, the intrinsics and norm_unit are those of the full-size
+    camera: the engine derives the binned size and calibration itself."""
     c = N.FrontendConfig()
     w, h = [int(v) for v in config.cam0_resolution]
+    f = downscale_factor(config)
     if max_corners is None:
-        max_corners = default_max_corners(w, h)
+        max_corners = default_max_corners(w // f, h // f)
     c.width, c.height = w, h
     c.grid_row, c.grid_col = int(config.grid_row), int(config.grid_col)
     c.grid_min_feature_num = int(config.grid_min_feature_num)
@@ -76,6 +110,9 @@ def pack_frontend_config(config, max_corners=None):
     # pixel format of the frames (AV_PIX_*); getattr: a config object without the two attributes is an 8-bit grey engine
     c.pixel_format = N.pixel_format_code(getattr(config, 'image_format', 'gray8'))
     c.gray16_shift = N.gray16_shift_value(getattr(config, 'gray16_shift', 8))
+    # 2 x 2 / 4 x 4 binning ahead of CLAHE and the pyramids; getattr: a config object without the attribute is a full-size engine
+    c.image_downscale = f
+    c.reserved1 = 0
     return c
 
 
@@ -133,7 +170,13 @@ class FrontendEngine(object):
         uint16 [S,h,w] for 'gray16' (cuda: torch.uint16, or torch.int16 holding the same bits), uint8 [S,h,w,3] for 'rgb8' / 'bgr8',
         uint8 [S,h,w,4] for 'rgba8' / 'bgra8', the raw mosaic as uint8 [S,h,w] for 'bayer_*8' and uint16 [S,h,w] for 'bayer_*16' -- and converts them to 8-bit grey on the GPU ahead of everything else (av_to_gray8 in
         include/airvision.h has the arithmetic).  Nothing is cast on the way: a wrong dtype or shape is a ValueError naming both.
-        The caller's frames are never written; `read_image` returns the grey frame the step used."""
+        The caller's frames are never written; `read_image` returns the grey frame the step used.
+
+        config.image_downscale = 2 or 4: every entry below still takes frames of config.cam0_resolution (`input_width` x
+        `input_height`) with the calibration of the full-size camera; the engine bins them f x f on the GPU (after the conversion,
+        ahead of CLAHE) and works on the `width` x `height` = processed image with the calibration of `downscaled_config(config)`.
+        `read_image` returns that frame and `read_grid` pixel coordinates are its pixels; the published message is in normalised
+        coordinates and needs no change downstream."""
         self.config = config
         self.n_streams = int(n_streams)
         self.device = int(device)
@@ -144,13 +187,20 @@ class FrontendEngine(object):
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_create(C.byref(self._cfg), self.n_streams, self.device, C.byref(self._h)))
         self.max_features = N.lib().av_frontend_max_features(self._h)
-        self.width, self.height = self._cfg.width, self._cfg.height
-        self.pixel_format = int(self._cfg.pixel_format)
-        self._frame_bytes = self.width * self.height * N.PIXEL_BYTES[self.pixel_format]      # img_stride of every entry point
+        self._set_sizes(self._cfg)
         S, cap = self.n_streams, self.max_features
         self._ids = np.zeros((S, cap), np.int64)
         self._uv = np.zeros((S, cap, 4), np.float64)
         self._n = np.zeros(S, np.int32)
+
+    def _set_sizes(self, cfg):
+        """The sizes that follow from a packed configuration: input_* = the frames the entry points take, width / height = the image
+        the engine works on (the input binned by config.image_downscale)."""
+        self.downscale = max(1, int(cfg.image_downscale))
+        self.input_width, self.input_height = int(cfg.width), int(cfg.height)
+        self.width, self.height = self.input_width // self.downscale, self.input_height // self.downscale
+        self.pixel_format = int(cfg.pixel_format)
+        self._frame_bytes = self.input_width * self.input_height * N.PIXEL_BYTES[self.pixel_format]      # img_stride of every entry point
 
     def close(self):
         if self._h:
@@ -183,11 +233,11 @@ class FrontendEngine(object):
         """img0/img1: uint8 cuda tensors [S,h,w] (contiguous); timestamps: S floats.  Enqueues only."""
         S = self.n_streams
         if self.pixel_format != N.AV_PIX_GRAY8:
-            check_device_frames('step: img0', img0, self.pixel_format, S, self.height, self.width)
-            check_device_frames('step: img1', img1, self.pixel_format, S, self.height, self.width)
+            check_device_frames('step: img0', img0, self.pixel_format, S, self.input_height, self.input_width)
+            check_device_frames('step: img1', img1, self.pixel_format, S, self.input_height, self.input_width)
         else:
             assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
-            assert tuple(img0.shape) == (S, self.height, self.width) == tuple(img1.shape), (img0.shape, img1.shape)
+            assert tuple(img0.shape) == (S, self.input_height, self.input_width) == tuple(img1.shape), (img0.shape, img1.shape)
             assert img0.is_contiguous() and img1.is_contiguous()
         ts = (C.c_double * S)(*[float(t) for t in timestamps])
         with torch.cuda.device(self.device):
@@ -199,11 +249,11 @@ class FrontendEngine(object):
         tracking launch.  Same results; the engine must have been created with inputs_persist=True."""
         S = self.n_streams
         if self.pixel_format != N.AV_PIX_GRAY8:
-            check_device_frames('prestage: img0', img0, self.pixel_format, S, self.height, self.width)
-            check_device_frames('prestage: img1', img1, self.pixel_format, S, self.height, self.width)
+            check_device_frames('prestage: img0', img0, self.pixel_format, S, self.input_height, self.input_width)
+            check_device_frames('prestage: img1', img1, self.pixel_format, S, self.input_height, self.input_width)
         else:
             assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
-            assert tuple(img0.shape) == (S, self.height, self.width) == tuple(img1.shape) and img0.is_contiguous() and img1.is_contiguous()
+            assert tuple(img0.shape) == (S, self.input_height, self.input_width) == tuple(img1.shape) and img0.is_contiguous() and img1.is_contiguous()
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_prestage(self._h, N.dptr(img0), N.dptr(img1), self._frame_bytes, self._stream()))
         self._pre = (img0, img1)                                                # alive until the step that uses them
@@ -212,11 +262,11 @@ class FrontendEngine(object):
         """numpy uint8 [S,h,w] (or [h,w] when S == 1); frames of config.image_format otherwise (class docstring)."""
         S = self.n_streams
         if self.pixel_format != N.AV_PIX_GRAY8:
-            a0 = check_host_frames('step_host: img0', img0, self.pixel_format, S, self.height, self.width)
-            a1 = check_host_frames('step_host: img1', img1, self.pixel_format, S, self.height, self.width)
+            a0 = check_host_frames('step_host: img0', img0, self.pixel_format, S, self.input_height, self.input_width)
+            a1 = check_host_frames('step_host: img1', img1, self.pixel_format, S, self.input_height, self.input_width)
         else:
-            a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(S, self.height, self.width)
-            a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(S, self.height, self.width)
+            a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(S, self.input_height, self.input_width)
+            a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(S, self.input_height, self.input_width)
         ts = (C.c_double * S)(*[float(t) for t in np.atleast_1d(timestamps)])
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_step_host(self._h, a0.ctypes.data_as(C.c_void_p), a1.ctypes.data_as(C.c_void_p),
@@ -235,11 +285,11 @@ class FrontendEngine(object):
         if n == 0:
             return
         if self.pixel_format != N.AV_PIX_GRAY8:
-            a0 = check_host_frames('frames_upload: img0', img0, self.pixel_format, n, self.height, self.width)
-            a1 = check_host_frames('frames_upload: img1', img1, self.pixel_format, n, self.height, self.width)
+            a0 = check_host_frames('frames_upload: img0', img0, self.pixel_format, n, self.input_height, self.input_width)
+            a1 = check_host_frames('frames_upload: img1', img1, self.pixel_format, n, self.input_height, self.input_width)
         else:
-            a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(n, self.height, self.width)
-            a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(n, self.height, self.width)
+            a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(n, self.input_height, self.input_width)
+            a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(n, self.input_height, self.input_width)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_frames_upload(self._h, sl.ctypes.data_as(C.c_void_p), n, a0.ctypes.data_as(C.c_void_p),
                                                       a1.ctypes.data_as(C.c_void_p), self._frame_bytes, self._stream()))
@@ -330,9 +380,9 @@ class FrontendEngine(object):
         return dict(zip(RANSAC_COUNT_NAMES, [int(v) for v in out]))
 
     def read_image(self, stream=0, cam=0):
-        """The level-0 image the last step used for camera `cam` of `stream`, uint8[h, w]: the frame converted to 8-bit grey
-        (config.image_format other than 'gray8'), equalised with config.use_clahe.  Refused (AirvisionError, AV_E_INVALID) with
-        neither: level 0 is then the caller's own image."""
+        """The level-0 image the last step used for camera `cam` of `stream`, uint8[height, width] (the processed size): the frame
+        converted to 8-bit grey (config.image_format other than 'gray8'), binned (config.image_downscale 2 or 4), equalised with
+        config.use_clahe.  Refused (AirvisionError, AV_E_INVALID) with none of them: level 0 is then the caller's own image."""
         out = np.empty((self.height, self.width), np.uint8)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_image(self._h, int(stream), int(cam), out.ctypes.data_as(C.c_void_p), self._stream()))

@@ -291,3 +291,40 @@ def to_gray8(img, pixel_format, shift=8, out=None, device=0):
     with torch.cuda.device(device):
         N.check(N.lib().av_to_gray8(N.dptr(tb), in_stride, n, w, h, fmt, shift, N.dptr(ob), out_stride, N.current_stream()))
     return out
+
+
+def downscale(img, factor, out=None, device=0):
+    """2 x 2 / 4 x 4 binning of 8-bit grey frames (av_downscale; the arithmetic is written out in include/airvision.h):
+    out(x, y) = (sum of the f x f block + f * f / 2) >> 2 log2 f.  img: uint8 [n, H, W] or [H, W] with H and W divisible by factor (2 or
+    4; ValueError otherwise), a cuda tensor or anything torch.as_tensor takes.  A cuda tensor is read where it lies: each image must be
+    contiguous, the images may be any distance apart, at any address.  Returns a uint8 cuda tensor [n, H / f, W / f] or [H / f, W / f]
+    -- `out` itself if given (uint8 cuda, that shape, each image contiguous; it must not overlap img)."""
+    if isinstance(factor, bool) or factor not in (2, 4):
+        raise ValueError('downscale: factor %r is neither 2 nor 4' % (factor,))
+    f = int(factor)
+    t = torch.as_tensor(img)
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3):
+        raise ValueError('downscale: images are torch.uint8 [n, H, W] or [H, W], got %s %s' % (t.dtype, tuple(t.shape)))
+    H, W = int(t.shape[-2]), int(t.shape[-1])
+    if H == 0 or W == 0 or H % f or W % f:
+        raise ValueError('downscale: %d x %d is not divisible by the factor %d' % (W, H, f))
+    t = t.to(_dev(device))
+    batched = t.dim() == 3
+    tb = t if batched else t.unsqueeze(0)
+    n = tb.shape[0]
+    if (n and not tb[0].is_contiguous()) or (n > 1 and tb.stride(0) < H * W):
+        tb = tb.contiguous()
+    h, w = H // f, W // f
+    oshape = (n, h, w) if batched else (h, w)
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.uint8, device=_dev(device))
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == oshape):
+        raise ValueError('downscale: out must be a uint8 cuda tensor of shape %s' % (oshape,))
+    ob = out if batched else out.unsqueeze(0)
+    if (n and not ob[0].is_contiguous()) or (n > 1 and ob.stride(0) < h * w):
+        raise ValueError('downscale: every image of out must be contiguous')
+    in_stride = tb.stride(0) if n > 1 else H * W
+    out_stride = ob.stride(0) if n > 1 else h * w
+    with torch.cuda.device(device):
+        N.check(N.lib().av_downscale(N.dptr(tb), in_stride, n, W, H, f, N.dptr(ob), out_stride, N.current_stream()))
+    return out

@@ -79,7 +79,8 @@ class EngineSet(object):
         self.pipes = [_Pipe(torch.device('cuda', device)) for _ in self.parts]
         self.engs = [FrontendEngine(config, n_streams=hi - lo, device=device, **kw) for lo, hi in self.parts]
         self.max_features = self.engs[0].max_features
-        self.height, self.width = self.engs[0].height, self.engs[0].width
+        self.height, self.width = self.engs[0].height, self.engs[0].width      # the image the engines work on (config.image_downscale)
+        self.input_height, self.input_width = self.engs[0].input_height, self.engs[0].input_width      # the frames `step` / `prestage` take
 
     # ---- enqueue-only calls -------------------------------------------------------------------------------------------------------
     def _split_rows(self, idx, *cols):

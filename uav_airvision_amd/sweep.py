@@ -82,9 +82,9 @@ class BatchedRunner(object):
         if staged and share_frames:
             self.plan = SharedFramePlan(datasets, max_frames=max_frames)
             self.eng.frames_reserve(self.plan.n_slots)
-            stager = SharedFrameStager(self.plan, self.eng.height, self.eng.width, threads=host_threads, pixel_format=self.eng.pixel_format)
+            stager = SharedFrameStager(self.plan, self.eng.input_height, self.eng.input_width, threads=host_threads, pixel_format=self.eng.pixel_format)
         elif staged:
-            stager = FrameStager(datasets, self.eng.height, self.eng.width, max_frames=max_frames, threads=host_threads, pixel_format=self.eng.pixel_format)
+            stager = FrameStager(datasets, self.eng.input_height, self.eng.input_width, max_frames=max_frames, threads=host_threads, pixel_format=self.eng.pixel_format)
         elif self.eng.pixel_format != 0:
             raise ValueError('datasets that do not list their files are read as 8-bit grey frames: config.image_format must be gray8')
         try:
@@ -107,7 +107,7 @@ class BatchedRunner(object):
         pos = [0 if a is None else int(np.searchsorted(a[:, 0], d.starttime, 'left')) for a, d in zip(arr, datasets)]
         its_imu = [iter(d.imu) if a is None else None for a, d in zip(arr, datasets)]
         pend = [None if it is None else next(it, None) for it in its_imu]
-        img0 = np.zeros((S, eng.height, eng.width), np.uint8) if plan is None else None
+        img0 = np.zeros((S, eng.input_height, eng.input_width), np.uint8) if plan is None else None
         img1 = np.zeros_like(img0) if plan is None else None
         traj = [[] for _ in range(S)]
         last_t = np.zeros(S)
@@ -285,6 +285,9 @@ def make_parser():
                     help='PNG flavour of the camera frames (config.image_format); auto = probe the first cam0 file of every sequence, which must agree within a batch.  '
                          'bayer_<pattern>8 / bayer_<pattern>16 (pattern = the colours of the top-left 2 x 2 block): the files are grey PNGs holding a raw Bayer mosaic, '
                          'demosaiced to grey on the GPU; auto never chooses a Bayer format, since a file cannot say that it is a mosaic')
+    ap.add_argument('--downscale', type=int, choices=[1, 2, 4], default=None,
+                    help='bin every frame f x f on the GPU ahead of CLAHE and the pyramids and run the front-end on the smaller image with the '
+                         'calibration scaled to it (config.image_downscale, default 1 = off); the files stay full size')
     ap.add_argument('--gray16-shift', type=int, default=None, metavar='N',
                     help='16-bit frames, grey or Bayer: sample = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
     return ap
@@ -304,6 +307,8 @@ def apply_args(cfg, args):
         cfg.image_format = getattr(args, 'pixel_format', 'gray8')
     if getattr(args, 'gray16_shift', None) is not None:
         cfg.gray16_shift = args.gray16_shift
+    if getattr(args, 'downscale', None) is not None:          # (a factor already set on the config object stays unless the switch is given)
+        cfg.image_downscale = int(args.downscale)
     return cfg
 
 
@@ -370,6 +375,8 @@ def main(argv=None):
             rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
         if args.pixel_format != 'gray8':
             rep['pixel_format'] = dict(asked=args.pixel_format, last_batch=cfg.image_format, gray16_shift=cfg.gray16_shift)
+        if getattr(cfg, 'image_downscale', 1) != 1:
+            rep['downscale'] = cfg.image_downscale
         print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
