@@ -192,12 +192,44 @@ struct ImgView {
     const int* map;                              // shared frame store (LK: a negative entry = the set has no frame in this step); or null
 };
 
-// pyramid.hip
-int av_launch_pyramid(const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int n_streams, int imgs_per_stream,
+// Where the frames of one stage of the input chain lie (the producer side of ImgView): camera c of group g at base[c] + e * stride
+// bytes with e = map ? map[g] : g; base[1] null = one camera.  A launcher reads its source set and writes its destination set, and
+// a launch has ONE list, its destination's: conversion and binning apply it to the destination only (their source is read at
+// g * stride, its map stays null) and skip a group whose entry is negative; CLAHE and the pyramid apply it to both sides (the
+// source's map is the destination's, or both are null) and take no negative entry.
+struct FrameSet {
+    uint8_t* base[2]; int64_t stride;
+    const int* map;                              // device, one int per group; or null
+};
+// (a set that is only read may be made from const pointers: nothing writes through a launcher's source)
+inline FrameSet av_frames(const uint8_t* b0, const uint8_t* b1, int64_t stride, const int* map = nullptr)
+{
+    return FrameSet{{const_cast<uint8_t*>(b0), const_cast<uint8_t*>(b1)}, stride, map};
+}
+// The vector bodies of pixfmt.hip, bayer.hip and downscale.hip load and store whole 16-byte vectors: every base, and every stride
+// that is applied, has to be a multiple of 16.  One group at its own place (no list) applies no stride.  The width condition of
+// each kernel stays with its launcher.
+inline bool av_frames_vec16(const FrameSet& src, const FrameSet& dst, int n_groups)
+{
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool strides16 = (n_groups == 1 && !src.map && !dst.map) || ((src.stride & 15) == 0 && (dst.stride & 15) == 0);
+    return strides16 && al16(src.base[0]) && al16(src.base[1]) && al16(dst.base[0]) && al16(dst.base[1]);
+}
+// n frames of in_bytes at in + i * in_stride against n of out_bytes at out + i * out_stride: do the two spans share a byte?  (The
+// refusal of the operators that do not work in place.)
+inline bool av_spans_overlap(const void* in, int64_t in_stride, int64_t in_bytes, const void* out, int64_t out_stride, int64_t out_bytes, int n)
+{
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (uint64_t)(n - 1) * in_stride + in_bytes;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uint64_t)(n - 1) * out_stride + out_bytes;
+    return o0 < i1 && i0 < o1;
+}
+
+// pyramid.hip: the pyramids of n_groups images of one camera or of two (img: read in place, its map is also the list of the pyramid
+// side: group i reads / writes storage entry img.map[i] of the image and pyramid arrays)
+int av_launch_pyramid(const FrameSet& img, int n_groups,
                       const PyrGeom& g, uint8_t* pyr_base, int64_t stream_stride, int64_t slot_stride, int slot0, int slot1,
-                      hipStream_t st, bool write_level0 = true, bool* wrote_level0 = nullptr, const int* index = nullptr);
+                      hipStream_t st, bool write_level0 = true, bool* wrote_level0 = nullptr);
 // write_level0 = false: levels 1.. only, level 0 stays the caller's image (honoured by the fused kernel; *wrote_level0 tells)
-// index (device, n_streams ints): image group i reads / writes storage entry index[i] of the image and pyramid arrays
 
 // lk.hip
 struct LKParams {
@@ -236,27 +268,21 @@ struct RansacStage {
 };
 int av_launch_ransac_stage(const RansacStage& a, hipStream_t st);
 
-// clahe.hip: equalise n_groups images of one camera (src1 / dst1 null) or of two (image pairs: camera c of group g at
-// src_c + e * src_stride with e = index ? index[g] : g).  dst may be src.  lut: [n_groups * cameras][tiles_y * tiles_x][256] scratch
-// (the look-up tables of the launch, camera-minor).  av_clahe_check: the argument limits of av_clahe, with `who` in the text.
+// clahe.hip: equalise n_groups images of one camera or of two (FrameSet; the list on both sides).  dst may be src.
+// lut: [n_groups * cameras][tiles_y * tiles_x][256] scratch (the look-up tables of the launch, camera-minor).
+// av_clahe_check: the argument limits of av_clahe, with `who` in the text.
 int av_clahe_check(int w, int h, double clip_limit, int tiles_x, int tiles_y, const char* who);
-int av_launch_clahe(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                    int n_groups, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* lut, hipStream_t st,
-                    const int* index = nullptr);
+int av_launch_clahe(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, double clip_limit, int tiles_x, int tiles_y,
+                    uint8_t* lut, hipStream_t st);
 
-// pixfmt.hip: n_groups frames of one camera (src1 / dst1 null) or of two, of pixel format fmt (AV_PIX_*, not GRAY8), to tightly packed
-// 8-bit grey.  Camera c of group g is read at src_c + g * src_stride (bytes) and written to dst_c + e * dst_stride with
-// e = index ? index[g] : g; a negative entry skips the group.  Never in place.  av_pixfmt_bytes: bytes per pixel, 0 = unknown format;
-// av_pixfmt_check: the limits of format and shift, with `who` in the text.
+// pixfmt.hip: n_groups frames of one camera or of two, of pixel format fmt (AV_PIX_*, not GRAY8), to tightly packed 8-bit grey
+// (FrameSet; the list on the destination only, a negative entry skips the group).  Never in place.
+// av_pixfmt_bytes: bytes per pixel, 0 = unknown format; av_pixfmt_check: the limits of format and shift, with `who` in the text.
 int av_pixfmt_bytes(int fmt);
 int av_pixfmt_check(int fmt, int shift, const char* who);
-int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                       int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index = nullptr);
+int av_launch_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st);
 // bayer.hip: the same for the Bayer mosaic formats (AV_PIX_BAYER_*), w >= 2 and h >= 2; av_launch_to_gray8 hands them on
-int av_launch_bayer_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                             int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index);
-// downscale.hip: 2 x 2 / 4 x 4 binning (f = 2 or 4) of n_groups tightly packed W x H grey frames of one camera (src1 / dst1 null) or of
-// two into tightly packed (W / f) x (H / f) ones; W % f == 0 and H % f == 0.  Groups, strides and index as av_launch_to_gray8 (a negative
-// entry skips the group).  Never in place.
-int av_launch_downscale(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                        int n_groups, int W, int H, int f, hipStream_t st, const int* index = nullptr);
+int av_launch_bayer_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st);
+// downscale.hip: 2 x 2 / 4 x 4 binning (f = 2 or 4) of n_groups tightly packed W x H grey frames of one camera or of two into tightly
+// packed (W / f) x (H / f) ones; W % f == 0 and H % f == 0.  Sets and list as av_launch_to_gray8.  Never in place.
+int av_launch_downscale(const FrameSet& src, const FrameSet& dst, int n_groups, int W, int H, int f, hipStream_t st);

@@ -210,8 +210,7 @@ __global__ __launch_bounds__(256) void bayer_to_gray8_generic_kernel(BayerArgs a
 
 }  // namespace
 
-int av_launch_bayer_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                             int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index)
+int av_launch_bayer_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st)
 {
     if (n_groups <= 0) return AV_OK;
     if (fmt < AV_PIX_BAYER_RGGB8 || fmt > AV_PIX_BAYER_GBRG16) { av_set_error("av_to_gray8: pixel format %d is no Bayer mosaic", fmt); return AV_E_INVALID; }
@@ -220,12 +219,10 @@ int av_launch_bayer_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t s
     const int pat = (fmt - AV_PIX_BAYER_RGGB8) & 3;               // rggb, bggr, grbg, gbrg
     BayerArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src0; a.src1 = src1; a.dst0 = dst0; a.dst1 = dst1; a.src_stride = src_stride; a.dst_stride = dst_stride; a.index = index;
-    a.n_src = src1 ? 2 : 1; a.n_img = n_groups * a.n_src; a.w = w; a.h = h; a.shift = shift;
+    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride; a.index = dst.map;
+    a.n_src = src.base[1] ? 2 : 1; a.n_img = n_groups * a.n_src; a.w = w; a.h = h; a.shift = shift;
     a.rx = pat == 1 || pat == 2; a.ry = pat == 1 || pat == 3;
-    auto al16 = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool strides16 = (n_groups == 1 && !index) || ((src_stride & 15) == 0 && (dst_stride & 15) == 0);      // one group at its own place: the strides are never applied
-    const bool vec = (w % BY_LANE) == 0 && strides16 && al16(src0) && al16(src1) && al16(dst0) && al16(dst1);
+    const bool vec = (w % BY_LANE) == 0 && av_frames_vec16(src, dst, n_groups);
     if (vec) {
         a.nvx = w / BY_LANE;
         a.items = a.nvx * ((h + BY_ROWS - 1) / BY_ROWS);

@@ -195,14 +195,14 @@ int av_clahe_check(int w, int h, double clip_limit, int tiles_x, int tiles_y, co
     return AV_OK;
 }
 
-int av_launch_clahe(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                    int n_groups, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* lut, hipStream_t st, const int* index)
+int av_launch_clahe(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, double clip_limit, int tiles_x, int tiles_y,
+                    uint8_t* lut, hipStream_t st)
 {
     if (n_groups <= 0) return AV_OK;
     ClaheArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src0; a.src1 = src1; a.dst0 = dst0; a.dst1 = dst1; a.src_stride = src_stride; a.dst_stride = dst_stride;
-    a.n_src = src1 ? 2 : 1; a.index = index; a.lut = lut;
+    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
+    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.lut = lut;
     a.n_img = n_groups * a.n_src; a.w = w; a.h = h; a.tiles_x = tiles_x; a.tiles_y = tiles_y;
     const int wp = w % tiles_x ? w + tiles_x - w % tiles_x : w, hp = h % tiles_y ? h + tiles_y - h % tiles_y : h;
     a.tw = wp / tiles_x; a.th = hp / tiles_y;
@@ -214,8 +214,8 @@ int av_launch_clahe(const uint8_t* src0, const uint8_t* src1, int64_t src_stride
     }
     a.scale = 255.0f / (float)area;
     a.inv_tw = 1.0f / (float)a.tw; a.inv_th = 1.0f / (float)a.th;
-    auto al4 = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
-    a.dwords = (w & 3) == 0 && (src_stride & 3) == 0 && (dst_stride & 3) == 0 && al4(src0) && al4(src1) && al4(dst0) && al4(dst1);
+    auto al4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
+    a.dwords = (w & 3) == 0 && (src.stride & 3) == 0 && (dst.stride & 3) == 0 && al4(src.base[0]) && al4(src.base[1]) && al4(dst.base[0]) && al4(dst.base[1]);
     const unsigned groups8 = (unsigned)((a.n_img + 7) / 8) * 8u;
     a.per = tiles_x * tiles_y;
     const int apply_chunks = (a.th + 2 + CL_ROWS - 1) / CL_ROWS;
@@ -249,7 +249,7 @@ AV_EXPORT int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, in
         hipError_t e = hipMallocAsync((void**)&lut, (size_t)n_img * tiles_x * tiles_y * 256, st);
         if (e != hipSuccess) { av_set_error("av_clahe: no memory for the look-up tables (%s)", hipGetErrorString(e)); return AV_E_HIP; }
     }
-    rc = av_launch_clahe(img_dev, nullptr, img_stride, out_dev, nullptr, out_stride, n_img, w, h, clip_limit, tiles_x, tiles_y, lut, st, nullptr);
+    rc = av_launch_clahe(av_frames(img_dev, nullptr, img_stride), FrameSet{{out_dev, nullptr}, out_stride, nullptr}, n_img, w, h, clip_limit, tiles_x, tiles_y, lut, st);
     if (!lut_dev) (void)hipFreeAsync(lut, st);
     return rc;
 }

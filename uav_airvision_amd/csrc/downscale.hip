@@ -108,26 +108,20 @@ __global__ __launch_bounds__(256) void downscale_generic_kernel(DsArgs a)
     }
 }
 
-// the one rule that picks the kernel (av_launch_downscale; av_downscale_vector_path reports it)
-bool ds_vector_ok(const void* src0, const void* src1, int64_t src_stride, const void* dst0, const void* dst1, int64_t dst_stride, int n_groups, int w, bool indexed)
-{
-    auto al16 = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool strides16 = (n_groups == 1 && !indexed) || ((src_stride & 15) == 0 && (dst_stride & 15) == 0);      // one group at its own place: the strides are never applied
-    return (w % DS_LANE) == 0 && strides16 && al16(src0) && al16(src1) && al16(dst0) && al16(dst1);
-}
+// the one rule that picks the kernel (av_launch_downscale; av_downscale_vector_path reports it); w: the output width
+bool ds_vector_ok(const FrameSet& src, const FrameSet& dst, int n_groups, int w) { return (w % DS_LANE) == 0 && av_frames_vec16(src, dst, n_groups); }
 
 }  // namespace
 
-int av_launch_downscale(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                        int n_groups, int W, int H, int f, hipStream_t st, const int* index)
+int av_launch_downscale(const FrameSet& src, const FrameSet& dst, int n_groups, int W, int H, int f, hipStream_t st)
 {
     if (n_groups <= 0) return AV_OK;
     if ((f != 2 && f != 4) || W <= 0 || H <= 0 || W % f || H % f) { av_set_error("av_downscale: factor %d does not bin %d x %d (2 or 4, dividing both sides)", f, W, H); return AV_E_INVALID; }
     DsArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src0; a.src1 = src1; a.dst0 = dst0; a.dst1 = dst1; a.src_stride = src_stride; a.dst_stride = dst_stride; a.index = index;
-    a.n_src = src1 ? 2 : 1; a.n_img = n_groups * a.n_src; a.W = W; a.w = W / f; a.h = H / f;
-    const bool vec = ds_vector_ok(src0, src1, src_stride, dst0, dst1, dst_stride, n_groups, a.w, index != nullptr);
+    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride; a.index = dst.map;
+    a.n_src = src.base[1] ? 2 : 1; a.n_img = n_groups * a.n_src; a.W = W; a.w = W / f; a.h = H / f;
+    const bool vec = ds_vector_ok(src, dst, n_groups, a.w);
     if (vec) {
         a.nvx = a.w / DS_LANE;
         a.items = a.nvx * a.h;
@@ -161,14 +155,12 @@ AV_EXPORT int av_downscale(const uint8_t* img_dev, int64_t img_stride, int n_img
         return AV_E_INVALID;
     }
     if (n_img == 0) return AV_OK;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(img_dev), i1 = i0 + (uint64_t)(n_img - 1) * img_stride + in_bytes;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + (uint64_t)(n_img - 1) * out_stride + out_bytes;
-    if (o0 < i1 && i0 < o1) { av_set_error("av_downscale: out_dev overlaps the input (the binning does not work in place)"); return AV_E_INVALID; }
-    return av_launch_downscale(img_dev, nullptr, img_stride, out_dev, nullptr, out_stride, n_img, W, H, factor, (hipStream_t)stream, nullptr);
+    if (av_spans_overlap(img_dev, img_stride, in_bytes, out_dev, out_stride, out_bytes, n_img)) { av_set_error("av_downscale: out_dev overlaps the input (the binning does not work in place)"); return AV_E_INVALID; }
+    return av_launch_downscale(av_frames(img_dev, nullptr, img_stride), FrameSet{{out_dev, nullptr}, out_stride, nullptr}, n_img, W, H, factor, (hipStream_t)stream);
 }
 
 AV_EXPORT int av_downscale_vector_path(const uint8_t* img_dev, int64_t img_stride, int n_img, int W, int factor, const uint8_t* out_dev, int64_t out_stride)
 {
     if ((factor != 2 && factor != 4) || W <= 0 || W % factor || n_img <= 0) return 0;
-    return ds_vector_ok(img_dev, nullptr, img_stride, out_dev, nullptr, out_stride, n_img, W / factor, false) ? 1 : 0;
+    return ds_vector_ok(av_frames(img_dev, nullptr, img_stride), av_frames(out_dev, nullptr, out_stride), n_img, W / factor) ? 1 : 0;
 }

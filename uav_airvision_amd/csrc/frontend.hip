@@ -649,8 +649,8 @@ struct av_frontend {
         bool l0_in_place = true;                 // false if the pyramid launcher had to write padded level-0 copies (unaligned geometry)
         std::vector<int> prev;                   // host: slot of every stream's previous frame (-1: none yet)
         struct Up { uint8_t* pin = nullptr; int* idx_h = nullptr; int* idx_d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false;
-                    uint8_t* raw_d = nullptr; };      // pixel_format != GRAY8 or binning: the frames as uploaded, on the device; idx_h / idx_d then hold a second list, that of the launch that writes the store
-        uint8_t* gray_d = nullptr; size_t gray_cap = 0;       // both: the conversion's full-size grey frames of ONE upload, read by the binning that follows it on the copy stream (uploads are serialised there: one scratch serves the whole ring)
+                    uint8_t* raw_d = nullptr; };      // raw_d: grey_chain's `raw` when a stage writes the store; idx_h / idx_d then hold its `first` list behind the entries' own
+        uint8_t* gray_d = nullptr; size_t gray_cap = 0;       // grey_chain's `gray_full` of ONE upload (uploads are serialised on the copy stream: one scratch serves the whole ring)
         Up up[4]; int up_next = 0;               // upload staging ring (pinned frames + the slot list of the upload's kernels)
         hipEvent_t uploaded = nullptr; bool any_upload = false;      // copy stream: the newest upload's kernels have finished
         hipEvent_t stepped = nullptr; bool any_step = false;          // step stream: the newest step has finished
@@ -674,12 +674,12 @@ struct av_frontend {
     // AV_FE_CLAHE: the equalised level 0 of every frame, [3][S][w * h] laid out like the pyramid slots (0 / 1: cam0 of alternating
     // frames, 2: cam1), and the look-up tables of one launch [2 S][tiles][256]; the frame store keeps tables of its own (fs_lut)
     bool clahe = false; uint8_t* eq = nullptr; uint8_t* eq_lut = nullptr; uint8_t* fs_lut = nullptr;
-    // pixel_format != AV_PIX_GRAY8: the frames are converted to 8-bit grey into the same level 0 (pixfmt.hip), ahead of the equalisation;
-    // own_l0 = the engine owns level 0 (either feature); bpp = bytes per pixel of the frames the entry points are handed
+    // pixel_format != AV_PIX_GRAY8: the frames are converted to 8-bit grey into the same level 0 (pixfmt.hip);
+    // own_l0 = some stage of grey_chain is on, so the engine owns level 0; bpp = bytes per pixel of the frames the entry points are handed
     int fmt = AV_PIX_GRAY8, fmt_shift = 8, bpp = 1; bool own_l0 = false;
-    // image_downscale = 2 / 4: the frames the entry points are handed are in_w x in_h and are binned into that level 0 (downscale.hip),
-    // after the conversion and ahead of the equalisation; cfg then holds the PROCESSED size d.w x d.h and the calibration scaled to it.
-    // gray_full: the conversion's full-size grey output when both are set, [2][S][in_w * in_h] (the frame store: FrameStore::gray_d)
+    // image_downscale = 2 / 4: the frames the entry points are handed are in_w x in_h and are binned into that level 0 (downscale.hip);
+    // cfg then holds the PROCESSED size d.w x d.h and the calibration scaled to it.  The order of the stages: grey_chain.
+    // gray_full: grey_chain's scratch of that name for the step paths, [2][S][in_w * in_h] (the frame store: FrameStore::gray_d)
     int ds = 1, in_w = 0, in_h = 0; uint8_t* gray_full = nullptr;
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
@@ -768,41 +768,56 @@ struct Span {
 // the engine-owned level 0 (AV_FE_CLAHE, pixel_format != AV_PIX_GRAY8) that goes with pyramid slot `slot`
 uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot * fe->d.S * fe->d.w * fe->d.h; }
 
-// The input stage of a step (step_impl, av_frontend_prestage): the pyramids of both cameras' images into slots cur and 2; with
-// AV_FE_CLAHE the images are first equalised into the engine's own level 0 and the pyramids built from there; frames of another pixel
-// format are first converted to grey into that level 0 and, with AV_FE_CLAHE, equalised there in place.  One class-0 span.
-// *wrote_l0 = false: level 0 stays the image itself (never asked for unless the inputs persist: the equalised ones always do).
+// The grey stages between the frames an entry point is handed and level 0, enqueued on st: [convert] -> [bin] -> [equalise], each
+// only if the engine was created with it.  This is the one place a stage is wired; the step paths (input_stage) and the frame
+// store's upload both come through here.
+//   raw        n groups of frames as handed over (fe->fmt, in_w x in_h).  Its map is null, unless the frames already lie in the
+//              entries of l0 (8-bit grey copied into the store): then it is l0 itself
+//   l0         where a finished level 0 goes: the engine's eq slots, or the store's entries with the list that CLAHE, the pyramid and
+//              FAST read and write them through (every group, none negative)
+//   first      the list of the stage that first writes l0 (conversion or binning), or null: l0's list with -1 for every frame but
+//              the last of an entry named twice
+//   gray_full  the caller's full-size grey scratch, between conversion and binning when both are on
+//   lut        the look-up tables of one equalisation
+// *level0 = the set the pyramid launch reads: l0 if any stage ran (fe->own_l0: the engine then owns level 0, which outlives the call
+// whatever the caller's frames do), else raw.
+int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, const int* first, const FrameSet& gray_full, uint8_t* lut,
+               hipStream_t st, FrameSet* level0)
+{
+    const av_frontend_config& c = fe->cfg;
+    const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
+    const FrameSet l0_first{{l0.base[0], l0.base[1]}, l0.stride, first};
+    FrameSet at = raw;                         // where the frames lie after the stages so far
+    int rc;
+    if (conv) {
+        const FrameSet& to = bin ? gray_full : l0_first;
+        if ((rc = av_launch_to_gray8(at, to, n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st))) return rc;
+        at = to;
+    }
+    if (bin && (rc = av_launch_downscale(at, l0_first, n, fe->in_w, fe->in_h, fe->ds, st))) return rc;
+    if (conv || bin) at = l0;
+    if (fe->clahe) {
+        if ((rc = av_launch_clahe(at, l0, n, fe->d.w, fe->d.h, c.clahe_clip_limit, c.clahe_tiles_x, c.clahe_tiles_y, lut, st))) return rc;
+        at = l0;
+    }
+    *level0 = at;
+    return AV_OK;
+}
+
+// The input stage of a step (step_impl, av_frontend_prestage): the grey chain into the engine's own level 0 (slots cur and 2 of eq),
+// then the pyramids of both cameras' images into pyramid slots cur and 2.  One class-0 span.
+// *wrote_l0 = false: level 0 stays the image itself (never asked for unless the inputs persist: the engine's own level 0 always does).
 int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int cur, bool inputs_persist, hipStream_t st, bool* wrote_l0)
 {
     const FeDev& d = fe->d;
-    const av_frontend_config& c = fe->cfg;
+    const int64_t hw = (int64_t)d.w * d.h, in_hw = (int64_t)fe->in_w * fe->in_h;
     Span sp(fe, 0, st);
-    if (fe->ds > 1) {                          // (conversion into the full-size scratch,) binning into the engine's level 0
-        uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
-        const int64_t hw = (int64_t)d.w * d.h, in_hw = (int64_t)fe->in_w * fe->in_h;
-        int rc;
-        if (fe->fmt != AV_PIX_GRAY8) {
-            uint8_t* g0 = fe->gray_full; uint8_t* g1 = fe->gray_full + (size_t)d.S * in_hw;
-            if ((rc = av_launch_to_gray8(img0, img1, img_stride, g0, g1, in_hw, d.S, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st))) return rc;
-            img0 = g0; img1 = g1; img_stride = in_hw;
-        }
-        if ((rc = av_launch_downscale(img0, img1, img_stride, e0, e1, hw, d.S, fe->in_w, fe->in_h, fe->ds, st))) return rc;
-        img0 = e0; img1 = e1; img_stride = hw; inputs_persist = true;
-    } else if (fe->fmt != AV_PIX_GRAY8) {
-        uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
-        const int64_t hw = (int64_t)d.w * d.h;
-        int rc = av_launch_to_gray8(img0, img1, img_stride, e0, e1, hw, d.S, d.w, d.h, fe->fmt, fe->fmt_shift, st);
-        if (rc) return rc;
-        img0 = e0; img1 = e1; img_stride = hw; inputs_persist = true;
-    }
-    if (fe->clahe) {
-        uint8_t* e0 = eq_slot(fe, cur); uint8_t* e1 = eq_slot(fe, 2);
-        const int64_t hw = (int64_t)d.w * d.h;
-        int rc = av_launch_clahe(img0, img1, img_stride, e0, e1, hw, d.S, d.w, d.h, c.clahe_clip_limit, c.clahe_tiles_x, c.clahe_tiles_y, fe->eq_lut, st);
-        if (rc) return rc;
-        img0 = e0; img1 = e1; img_stride = hw; inputs_persist = true;
-    }
-    return av_launch_pyramid(img0, img1, img_stride, d.S, 2, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur, 2, st, !inputs_persist, wrote_l0);
+    const FrameSet l0 = fe->own_l0 ? FrameSet{{eq_slot(fe, cur), eq_slot(fe, 2)}, hw, nullptr} : FrameSet{};
+    const FrameSet gray = fe->gray_full ? FrameSet{{fe->gray_full, fe->gray_full + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
+    FrameSet level0;
+    int rc = grey_chain(fe, av_frames(img0, img1, img_stride), d.S, l0, nullptr, gray, fe->eq_lut, st, &level0);
+    if (rc) return rc;
+    return av_launch_pyramid(level0, d.S, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur, 2, st, !(inputs_persist || fe->own_l0), wrote_l0);
 }
 
 // pyramid slot `slot` of the engine (0 / 1: cam0 of alternating frames, 2: cam1) with the level 0 that was recorded for it
@@ -1330,31 +1345,23 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     if (fs.any_step) AV_HIP(hipStreamWaitEvent(cs, fs.stepped, 0));
     AV_HIP(hipMemcpyAsync(u.idx_d, u.idx_h, sizeof(int) * (raw ? 2 : 1) * n, hipMemcpyHostToDevice, cs));
     int rc;
-    if (raw) {                       // the frames to the ring entry's device buffer in one copy, then converted and / or binned into their store entries
-        AV_HIP(hipMemcpyAsync(u.raw_d, u.pin, (size_t)n * 2 * fb, hipMemcpyHostToDevice, cs));
-        if (!bin) {
-            if ((rc = av_launch_to_gray8(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->fmt, fe->fmt_shift, cs, u.idx_d + n))) return rc;
-        } else {
-            const uint8_t* g = u.raw_d;
-            if (conv) {              // every frame of the upload to full-size grey, in upload order; the binning then picks the ones that reach the store
-                if ((rc = av_launch_to_gray8(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb), fs.gray_d, fs.gray_d + in_hw, (int64_t)(2 * in_hw), n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, cs, nullptr))) return rc;
-                g = fs.gray_d;
-            }
-            if ((rc = av_launch_downscale(g, g + in_hw, (int64_t)(2 * in_hw), fs.img, fs.img + hw, (int64_t)(2 * hw), n, fe->in_w, fe->in_h, fe->ds, cs, u.idx_d + n))) return rc;
-        }
-    }
-    for (int i = 0; i < n && !raw;) {                                // runs of consecutive entries go down in one copy
+    if (raw) AV_HIP(hipMemcpyAsync(u.raw_d, u.pin, (size_t)n * 2 * fb, hipMemcpyHostToDevice, cs));      // to the ring entry's device buffer in one copy: the grey chain takes them into their store entries
+    for (int i = 0; i < n && !raw;) {                                // 8-bit grey at full size: straight into the entries, runs of consecutive ones in one copy
         int j = i + 1;
         while (j < n && slots[j] == slots[j - 1] + 1) ++j;
         AV_HIP(hipMemcpyAsync(fs.img + (size_t)slots[i] * 2 * hw, u.pin + (size_t)i * 2 * hw, (size_t)(j - i) * 2 * hw, hipMemcpyHostToDevice, cs));
         i = j;
     }
+    // grey_chain as in a step, but indexed, in place in the store, on the copy stream and outside the step's timing spans.  With both
+    // conversion and binning every frame of the upload goes to full-size grey in upload order and the binning picks the ones that
+    // reach the store; AV_FE_CLAHE equalises the entries once, where they lie, before anything reads them (the tables by position in
+    // this upload)
+    const FrameSet l0{{fs.img, fs.img + hw}, (int64_t)(2 * hw), u.idx_d};
+    const FrameSet gray = fs.gray_d ? FrameSet{{fs.gray_d, fs.gray_d + in_hw}, (int64_t)(2 * in_hw), nullptr} : FrameSet{};
+    FrameSet level0;
+    if ((rc = grey_chain(fe, raw ? av_frames(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb)) : l0, n, l0, raw ? u.idx_d + n : nullptr, gray, fe->fs_lut, cs, &level0))) return rc;
     bool wrote_l0 = true;
-    // (not input_stage: these launches are indexed, in place in the store, on the copy stream and outside the step's timing spans)
-    // AV_FE_CLAHE: the entries are equalised once, where they lie, before anything reads them (the tables by position in this upload)
-    if (fe->clahe && (rc = av_launch_clahe(fs.img, fs.img + hw, (int64_t)(2 * hw), fs.img, fs.img + hw, (int64_t)(2 * hw), n, d.w, d.h, fe->cfg.clahe_clip_limit,
-                                           fe->cfg.clahe_tiles_x, fe->cfg.clahe_tiles_y, fe->fs_lut, cs, u.idx_d))) return rc;
-    if ((rc = av_launch_pyramid(fs.img, fs.img + hw, (int64_t)(2 * hw), n, 2, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0, u.idx_d))) return rc;
+    if ((rc = av_launch_pyramid(level0, n, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0))) return rc;
     fs.l0_in_place = !wrote_l0;
     if ((rc = av_launch_fast(store_view(fe, 0, u.idx_d), &fe->geom, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold, d.rbits,
                              nullptr, nullptr, 0, fs.tile_kp, fs.tile_count, nullptr, 0, cs))) return rc;

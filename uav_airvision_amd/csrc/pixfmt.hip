@@ -105,19 +105,16 @@ int av_pixfmt_check(int fmt, int shift, const char* who)
     return AV_OK;
 }
 
-int av_launch_to_gray8(const uint8_t* src0, const uint8_t* src1, int64_t src_stride, uint8_t* dst0, uint8_t* dst1, int64_t dst_stride,
-                       int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const int* index)
+int av_launch_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st)
 {
     if (n_groups <= 0) return AV_OK;
-    if (fmt >= AV_PIX_BAYER_RGGB8) return av_launch_bayer_to_gray8(src0, src1, src_stride, dst0, dst1, dst_stride, n_groups, w, h, fmt, shift, st, index);      // a 3 x 3 stencil over rows: bayer.hip
+    if (fmt >= AV_PIX_BAYER_RGGB8) return av_launch_bayer_to_gray8(src, dst, n_groups, w, h, fmt, shift, st);      // a 3 x 3 stencil over rows: bayer.hip
     PixArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src0; a.src1 = src1; a.dst0 = dst0; a.dst1 = dst1; a.src_stride = src_stride; a.dst_stride = dst_stride;
-    a.n_src = src1 ? 2 : 1; a.index = index; a.n_img = n_groups * a.n_src; a.npix = w * h; a.fmt = fmt; a.shift = shift;
+    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
+    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.n_img = n_groups * a.n_src; a.npix = w * h; a.fmt = fmt; a.shift = shift;
     a.per = (a.npix + PF_BLOCK - 1) / PF_BLOCK;
-    auto al16 = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool strides16 = n_groups == 1 || ((src_stride & 15) == 0 && (dst_stride & 15) == 0);      // one group: the strides are never applied
-    a.vec = strides16 && al16(src0) && al16(src1) && al16(dst0) && al16(dst1);
+    a.vec = av_frames_vec16(src, dst, n_groups);
     if ((int64_t)a.per * a.n_img > 0x7FFFFFFFll) { av_set_error("av_to_gray8: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
     const dim3 grid((unsigned)(a.per * a.n_img)), block(256);
     switch (fmt) {
@@ -151,12 +148,10 @@ AV_EXPORT int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_i
     const uint8_t* in = static_cast<const uint8_t*>(img_dev);
     hipStream_t st = (hipStream_t)stream;
     if (pixel_format == AV_PIX_GRAY8 && in == out_dev && img_stride_bytes == out_stride) return AV_OK;      // the identity in place: nothing to do
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (uint64_t)(n_img - 1) * img_stride_bytes + in_bytes;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + (uint64_t)(n_img - 1) * out_stride + npix;
-    if (o0 < i1 && i0 < o1) { av_set_error("av_to_gray8: out_dev overlaps the input (the conversion does not work in place)"); return AV_E_INVALID; }
+    if (av_spans_overlap(in, img_stride_bytes, in_bytes, out_dev, out_stride, npix, n_img)) { av_set_error("av_to_gray8: out_dev overlaps the input (the conversion does not work in place)"); return AV_E_INVALID; }
     if (pixel_format == AV_PIX_GRAY8) {            // the identity out of place: a strided copy
         AV_HIP(hipMemcpy2DAsync(out_dev, (size_t)out_stride, in, (size_t)img_stride_bytes, (size_t)npix, (size_t)n_img, hipMemcpyDeviceToDevice, st));
         return AV_OK;
     }
-    return av_launch_to_gray8(in, nullptr, img_stride_bytes, out_dev, nullptr, out_stride, n_img, w, h, pixel_format, shift, st, nullptr);
+    return av_launch_to_gray8(av_frames(in, nullptr, img_stride_bytes), FrameSet{{out_dev, nullptr}, out_stride, nullptr}, n_img, w, h, pixel_format, shift, st);
 }

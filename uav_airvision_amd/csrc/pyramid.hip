@@ -441,24 +441,24 @@ PyrGeom av_make_geom(const av_pyr_layout& l)
     return g;
 }
 
-int av_launch_pyramid(const uint8_t* img0, const uint8_t* img1, int64_t img_stride, int n_streams, int imgs_per_stream,
+int av_launch_pyramid(const FrameSet& img, int n_groups,
                       const PyrGeom& g, uint8_t* pyr_base, int64_t stream_stride, int64_t slot_stride, int slot0, int slot1,
-                      hipStream_t st, bool write_level0, bool* wrote_level0, const int* index)
+                      hipStream_t st, bool write_level0, bool* wrote_level0)
 {
     if (wrote_level0) *wrote_level0 = true;
-    if (n_streams <= 0) return AV_OK;
+    if (n_groups <= 0) return AV_OK;
     PyrArgs a;
-    a.img0 = img0; a.img1 = img1; a.img_stride = img_stride; a.imgs_per_stream = imgs_per_stream;
+    a.img0 = img.base[0]; a.img1 = img.base[1]; a.img_stride = img.stride; a.imgs_per_stream = img.base[1] ? 2 : 1;
     a.pyr_base = pyr_base; a.stream_stride = stream_stride; a.slot_stride = slot_stride;
     a.slot0 = slot0; a.slot1 = slot1; a.g = g;
-    a.n_img = 0; a.tiles_x = 0; a.tiles_y = 0; a.index = index;
-    const int n_img = n_streams * imgs_per_stream;
+    a.n_img = 0; a.tiles_x = 0; a.tiles_y = 0; a.index = img.map;
+    const int n_img = n_groups * a.imgs_per_stream;
     const int w = g.w[0], h = g.h[0];
     // the fused level-0 + level-1 kernel needs: dword-aligned rows, whole 32-row tiles, a last tile column that still holds the
     // 17 pixels its frame mirrors, images large enough that a pixel is never in two mirror bands
     const int FT_H = ((h % FT_H_TALL) == 0 && h >= 2 * FT_H_TALL) ? FT_H_TALL : FT_H_BASE;
     const bool fused = g.levels >= 2 && (w & 15) == 0 && (h % FT_H) == 0 && h >= 64 && w >= 64 && (w % FT_W == 0 || w % FT_W >= 20) &&
-                       (img_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img0) & 3) == 0 && (!img1 || (reinterpret_cast<uintptr_t>(img1) & 3) == 0);
+                       (img.stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img.base[0]) & 3) == 0 && (reinterpret_cast<uintptr_t>(img.base[1]) & 3) == 0;
     if (fused) {
         const int tx = (w + FT_W - 1) / FT_W, ty = h / FT_H;
         a.n_img = n_img; a.tiles_x = tx; a.tiles_y = ty;
@@ -539,6 +539,5 @@ AV_EXPORT int av_pyramid_build(const uint8_t* img_dev, int64_t img_stride, int n
         av_set_error("av_pyramid_build: bad arguments");
         return AV_E_INVALID;
     }
-    return av_launch_pyramid(img_dev, nullptr, img_stride, n_img, 1, av_make_geom(lay), pyr_dev, pyr_stride, 0, 0, 0,
-                             (hipStream_t)stream);
+    return av_launch_pyramid(av_frames(img_dev, nullptr, img_stride), n_img, av_make_geom(lay), pyr_dev, pyr_stride, 0, 0, 0, (hipStream_t)stream);
 }
