@@ -251,6 +251,36 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * than AV_PYR_BORDER), AV_E_INVALID, before a device is touched.  With 0 or 1 the step enqueues exactly what it always did and nothing
  * more is allocated.  Box filter only; one factor for both cameras; the thresholds are not retuned for the smaller image. */
 
+/* Static masks: the parts of a camera's image that are never scene -- the corners outside a fisheye lens's image circle, an
+ * airframe or propeller arcs in view, a sensor's dead border.  No counterpart in the reference, which has only the transient 7 x 7
+ * mask around existing features (feature_adder.py:56-62); a static mask is the same detect(img, mask) argument with a second source
+ * (OpenVINS use_mask, VINS-Fusion fisheye_mask).
+ * One mask per camera, for all streams of an engine: the engine has one calibration, so it has one rig geometry.  A mask is
+ * height x width bytes (the size of the frames handed to the entry points), tightly packed: non-zero = scene, 0 = never scene.  Either
+ * camera's mask may be absent, which means all valid.  A pixel coordinate (x, y) is mapped to a mask pixel by truncation,
+ * m[int(y)][int(x)] -- the reference's own rule for its 7 x 7 mask (feature_adder.py:59-62).
+ *  1. Detection (cam0 mask).  A FAST keypoint whose cam0 mask pixel is 0 is dropped after the non-max suppression: detect(img, mask)
+ *     with mask = static & 7x7.  It applies on the first frame (feature_initializer.py:52, which has no mask today) and in
+ *     add_new_features.  n_fast (av_frontend_read_counters) counts what is left.
+ *  2. Temporal tracking (cam0 mask).  A tracked point that passed the LK status and the bounds test (feature_tracker.py:110-121) but
+ *     sits on a masked cam0 pixel is dropped there, before the stereo re-match and before RANSAC.  after_tracking counts what is left.
+ *  3. Stereo (cam1 mask).  A stereo match (tracked or new candidate, first frame included) that passed the in-image test of
+ *     stereo_matcher.py:75-88 but whose cam1 point sits on a masked cam1 pixel is not an inlier.
+ *  4. Binning.  With image_downscale = f the masks are given at the input size; the engine works with the binned mask: pixel (x, y)
+ *     of it is valid iff all f x f source pixels are non-zero.  Stored bytes are 0 / 1.
+ *  5. LK windows, pyramids, CLAHE and RANSAC read masked pixels as they always did.  Only the three gates above change.
+ * av_frontend_set_masks takes two tightly packed height x width u8 HOST arrays; either may be NULL (no mask for that camera), both
+ * NULL clears.  It is blocking (the masks are binned on the host and copied before it returns; the arrays are free again then) and is
+ * accepted only while the engine has not yet been handed a frame: after an av_frontend_step*, _prestage or _frames_upload it returns
+ * AV_E_INVALID, because the FAST lists of frames already uploaded would disagree with the mask.  The first call allocates two device
+ * buffers of w * h bytes (the processed size); an engine that is never given a mask allocates nothing and enqueues exactly what it
+ * always did.  av_frontend_read_mask copies the processed-size 0 / 1 mask of camera `cam` (0 / 1) into out_host (w * h bytes);
+ * AV_E_INVALID if none is set for that camera.
+ * Not covered: per-stream masks, masks that change during a run, excluding masked pixels from the LK windows, drop counters of their
+ * own, two cameras of different sizes. */
+int av_frontend_set_masks(av_frontend* fe, const uint8_t* mask0_host, const uint8_t* mask1_host);
+int av_frontend_read_mask(av_frontend* fe, int cam, uint8_t* out_host);
+
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
  * img0_dev + s*img_stride and img1_dev + s*img_stride; timestamps[s] is the frame time.  All

@@ -195,6 +195,8 @@ SIGNATURES = {
                                       C.c_double, C.c_double, C.c_uint32, _P, _P, _P]),
     'av_frontend_read_image': (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     'av_clahe': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    'av_frontend_set_masks': (C.c_int, [_P, _P, _P]),
+    'av_frontend_read_mask': (C.c_int, [_P, C.c_int, _P]),
     'av_frontend_enable_timing': (C.c_int, [_P, C.c_int]),
     'av_frontend_read_timing': (C.c_int, [_P, C.POINTER(C.c_double * 4), C.POINTER(C.c_int32 * 4)]),
 }

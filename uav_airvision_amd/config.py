@@ -62,6 +62,12 @@ class ConfigEuRoC(object):
         # the engine works on the binned image with the calibration of frontend.downscaled_config.  The thresholds below, the grid
         # and patch_size apply to the binned image as they stand.
         self.image_downscale = 1
+        # static masks of the two cameras, for every stream of an engine (no counterpart in the reference; "Static masks" in
+        # include/airvision.h): what is never scene -- the corners outside a fisheye's image circle, airframe in view.  None, a uint8 /
+        # bool array of shape (height, width) of cam*_resolution with non-zero = scene, or the path of an 8-bit grey PNG of that size
+        # (frontend.circle_mask builds the circle).  None: the front-end is the reference's, bit for bit.
+        self.cam0_mask = None
+        self.cam1_mask = None
         self.stereo_threshold = 5
         self.max_iteration = 30
         self.track_precision = 0.01

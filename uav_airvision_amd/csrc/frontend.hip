@@ -74,9 +74,20 @@ struct FeDev {
     // handed to the LK launches, of the images and pyramids); < 0 = the stream has no frame in this step: its workgroups return at
     // once and its state stays as it is.  Null = every stream owns entry s (av_frontend_step / _step_host).
     const int* slot_cur;
+    // Static per-camera masks (av_frontend_set_masks): [w * h] bytes, 1 = scene, 0 = never scene, one per camera for ALL streams; null =
+    // none set, and every kernel then does exactly what it did without them
+    const uint8_t* smask0; const uint8_t* smask1;
 };
 
 __device__ __forceinline__ bool fe_idle(const FeDev& d, int s) { return d.slot_cur != nullptr && d.slot_cur[s] < 0; }
+
+// the static mask byte under pixel coordinate (x, y): m[int(y)][int(x)], truncation (the reference's rule for its 7x7 mask,
+// feature_adder.py:59-62).  The callers have tested the point against the image; the clamp only keeps a NaN inside the buffer.
+__device__ __forceinline__ bool smask_valid(const FeDev& d, const uint8_t* m, float x, float y)
+{
+    const int xi = min(max((int)x, 0), d.w - 1), yi = min(max((int)y, 0), d.h - 1);
+    return m[(size_t)yi * d.w + xi] != 0;
+}
 
 __device__ __forceinline__ int cell_of(const FeDev& d, float x, float y)
 {
@@ -128,6 +139,7 @@ __device__ __forceinline__ bool stereo_gate(const FeDev& d, float p0x, float p0y
     float disp = fabsf(iny - p1y);
     if (!(disp < 20.f)) return false;
     if (p1x < 0 || p1x >= (float)d.w || p1y < 0 || p1y >= (float)d.h) return false;
+    if (d.smask1 && !smask_valid(d, d.smask1, p1x, p1y)) return false;      // the cam1 point lies on a pixel that is never scene
     double ax, ay, bxx, byy;
     av_undistort(d.cam0, d.I3, (double)p0x, (double)p0y, ax, ay);
     av_undistort(d.cam0, d.I3, (double)p1x, (double)p1y, bxx, byy);
@@ -157,7 +169,7 @@ __global__ __launch_bounds__(256) void track_prepare_kernel(FeDev d, int par)
     d.trk_next[2 * t] = (float)(h0 / h2); d.trk_next[2 * t + 1] = (float)(h1 / h2);
 }
 
-// ---- G2: bounds mask + ordered compaction + stereo initial guess (feature_tracker.py:110-126) --
+// ---- G2: bounds mask (+ static cam0 mask) + ordered compaction + stereo initial guess (feature_tracker.py:110-126) --
 __global__ __launch_bounds__(256) void track_gate_kernel(FeDev d)
 {
     __shared__ int lds4[4];
@@ -172,6 +184,7 @@ __global__ __launch_bounds__(256) void track_gate_kernel(FeDev d)
         if (i < n) {
             x = d.trk_next[2 * t]; y = d.trk_next[2 * t + 1];
             keep = d.trk_status[t] != 0 && !(x < 0 || x > (float)(d.w - 1) || y < 0 || y > (float)(d.h - 1));
+            if (keep && d.smask0) keep = smask_valid(d, d.smask0, x, y);      // tracked onto a cam0 pixel that is never scene
         }
         int pos = block_ordered_pos(keep, base, lds4);
         if (keep) {
@@ -681,6 +694,9 @@ struct av_frontend {
     // cfg then holds the PROCESSED size d.w x d.h and the calibration scaled to it.  The order of the stages: grey_chain.
     // gray_full: grey_chain's scratch of that name for the step paths, [2][S][in_w * in_h] (the frame store: FrameStore::gray_d)
     int ds = 1, in_w = 0, in_h = 0; uint8_t* gray_full = nullptr;
+    // av_frontend_set_masks: the engine's two mask buffers ([w * h] each, allocated by the first call; d.smask0 / smask1 point at them
+    // while a mask is set) and whether the engine has been handed a frame (step, prestage or frames_upload): masks are then refused
+    uint8_t* smask_buf[2] = {nullptr, nullptr}; bool fed = false;
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
     explicit av_frontend(int S) : streams(S) {}
@@ -894,6 +910,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         fe->l0_stride[cur] = fe->l0_stride[2] = img_stride;
         prev0 = slot_view(fe, par); cur0 = slot_view(fe, cur); cur1 = slot_view(fe, 2);      // (first frame: nothing is tracked from prev0)
     }
+    fe->fed = true;                          // the engine has a frame from here on (av_frontend_set_masks)
 
     auto lk = [&](const ImgView& I, const ImgView& J, const float* prev, float* next, uint8_t* status, const int* count, int cap, int launch_pts, const int* list) -> int {
         Span sp(fe, 1, st);
@@ -929,7 +946,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     //  the LK launches slow down by more than the detector's time; profiles/r05/README.md)
     if (!frames) {                             // (frame store: FAST ran when the frame was uploaded)
         Span sp(fe, 2, st);
-        if ((rc = av_launch_fast(cur0, &fe->geom, nullptr, 0, S, d.w, d.h, fe->cfg.fast_threshold, d.rbits, nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, st))) return rc;
+        if ((rc = av_launch_fast(cur0, &fe->geom, d.smask0, 0, S, d.w, d.h, fe->cfg.fast_threshold, d.rbits, nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, st))) return rc;
     }
     { Span sp(fe, 3, st);
       hipLaunchKernelGGL(select_kernel, dim3(S), dim3(256), sizeof(int) * (3 * d.C + 1 + d.n_tiles + 1), st, d);
@@ -1196,6 +1213,7 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
     bool wrote_l0 = true;
     const int rc = input_stage(fe, img0_dev, img1_dev, img_stride, fe->parity ^ 1, true, st, &wrote_l0);      // the slots the next step will call cur / 2
     if (rc) return rc;
+    fe->fed = true;
     // (The detector's pass over the new cam0 image -- it reads nothing but the image -- enqueued here as well ran at its exclusive speed,
     //  1.55 ms against 2.3 beside the filter's back end, and the LK launches took what it gave back: 173.4-173.9 against 174.1-175.2 k
     //  frames/s.  profiles/r05/README.md)
@@ -1363,7 +1381,8 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     bool wrote_l0 = true;
     if ((rc = av_launch_pyramid(level0, n, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0))) return rc;
     fs.l0_in_place = !wrote_l0;
-    if ((rc = av_launch_fast(store_view(fe, 0, u.idx_d), &fe->geom, nullptr, 0, n, d.w, d.h, fe->cfg.fast_threshold, d.rbits,
+    fe->fed = true;                                 // the detector reads the masks now: from here on they stay (av_frontend_set_masks)
+    if ((rc = av_launch_fast(store_view(fe, 0, u.idx_d), &fe->geom, d.smask0, 0, n, d.w, d.h, fe->cfg.fast_threshold, d.rbits,
                              nullptr, nullptr, 0, fs.tile_kp, fs.tile_count, nullptr, 0, cs))) return rc;
     AV_HIP(hipEventRecord(u.done, cs));
     AV_HIP(hipEventRecord(fs.uploaded, cs));
@@ -1527,6 +1546,51 @@ AV_EXPORT int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, u
     AV_HIP(hipStreamSynchronize((hipStream_t)stream));
     if (fe->copy_stream) AV_HIP(hipStreamSynchronize(fe->copy_stream));
     AV_HIP(hipMemcpy(out_host, src, hw, hipMemcpyDeviceToHost));
+    return AV_OK;
+}
+
+// ---- static per-camera masks ("Static masks" in include/airvision.h) ------------------------------------------------------
+AV_EXPORT int av_frontend_set_masks(av_frontend* fe, const uint8_t* mask0_host, const uint8_t* mask1_host)
+{
+    if (!fe) { av_set_error("av_frontend_set_masks: bad arguments"); return AV_E_INVALID; }
+    if (fe->fed) {
+        av_set_error("av_frontend_set_masks: the engine has already been handed a frame (step, prestage or frames_upload): the corners found in it "
+                     "would disagree with the new masks; set the masks of an engine before its first frame");
+        return AV_E_INVALID;
+    }
+    AV_HIP(hipSetDevice(fe->device));
+    FeDev& d = fe->d;
+    const size_t hw = (size_t)d.w * d.h;
+    const int f = fe->ds;
+    const uint8_t* src[2] = {mask0_host, mask1_host};
+    const uint8_t* set[2] = {nullptr, nullptr};
+    std::vector<uint8_t> bin(hw);
+    for (int cam = 0; cam < 2; ++cam) {
+        if (!src[cam]) continue;
+        // the mask of the processed image: a pixel is scene iff all f x f input pixels under it are; stored as 0 / 1
+        for (int y = 0; y < d.h; ++y)
+            for (int x = 0; x < d.w; ++x) {
+                uint8_t v = 1;
+                for (int j = 0; j < f; ++j)
+                    for (int i = 0; i < f; ++i) v &= src[cam][(size_t)(y * f + j) * fe->in_w + (size_t)x * f + i] != 0;
+                bin[(size_t)y * d.w + x] = v;
+            }
+        int rc;
+        if (!fe->smask_buf[cam] && (rc = dev_alloc(fe, &fe->smask_buf[cam], hw))) return rc;
+        AV_HIP(hipMemcpy(fe->smask_buf[cam], bin.data(), hw, hipMemcpyHostToDevice));
+        set[cam] = fe->smask_buf[cam];
+    }
+    d.smask0 = set[0]; d.smask1 = set[1];
+    return AV_OK;
+}
+
+AV_EXPORT int av_frontend_read_mask(av_frontend* fe, int cam, uint8_t* out_host)
+{
+    if (!fe || cam < 0 || cam > 1 || !out_host) { av_set_error("av_frontend_read_mask: bad arguments"); return AV_E_INVALID; }
+    const uint8_t* m = cam ? fe->d.smask1 : fe->d.smask0;
+    if (!m) { av_set_error("av_frontend_read_mask: no mask is set for camera %d", cam); return AV_E_INVALID; }
+    AV_HIP(hipSetDevice(fe->device));
+    AV_HIP(hipMemcpy(out_host, m, (size_t)fe->d.w * fe->d.h, hipMemcpyDeviceToHost));
     return AV_OK;
 }
 

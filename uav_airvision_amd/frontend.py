@@ -7,6 +7,7 @@ Reference surface mirrored: ImageProcessingPipeline.{__init__, imu_callback, ste
 """
 import copy
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -150,6 +151,40 @@ def check_device_frames(what, t, pixel_format, n, height, width):
     return t
 
 
+def circle_mask(width, height, cx, cy, radius):
+    """A static mask (uint8 [height, width], 1 = scene) of a fisheye lens's image circle: pixel (x, y) is valid iff
+    (x - cx)^2 + (y - cy)^2 <= radius^2."""
+    y, x = np.mgrid[0:int(height), 0:int(width)]
+    return ((x - float(cx)) ** 2 + (y - float(cy)) ** 2 <= float(radius) ** 2).astype(np.uint8)
+
+
+def check_mask(cam, mask, height, width):
+    """The static mask of camera `cam` (0 / 1) as a C-contiguous uint8 [height, width] array, or None for None.  `mask` is an ndarray,
+    uint8 or bool, of exactly that shape (non-zero = scene, 0 = never scene), or the path of an 8-bit grey PNG of that size (decoded by
+    the library's own av_png_decode).  Host only; nothing is cast or resized: a wrong dtype or shape is a ValueError naming the
+    camera, the shape wanted and the shape it got."""
+    if mask is None:
+        return None
+    want = (int(height), int(width))
+    if isinstance(mask, (str, os.PathLike)):
+        path = os.fspath(mask)
+        w, h, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        if N.lib().av_png_probe(os.fsencode(path), C.byref(w), C.byref(h), C.byref(f)) != 0:
+            raise ValueError('cam%d mask: %s: %s' % (cam, path, N.lib().av_last_error().decode('utf-8', 'replace')))
+        if (int(h.value), int(w.value)) != want or int(f.value) != N.AV_PIX_GRAY8:
+            raise ValueError('cam%d mask: %s: an 8-bit grey PNG of shape %s is wanted, got %s %s' % (cam, path, want, N.PIXEL_FORMAT_NAMES.get(int(f.value), 'an undecodable flavour'),
+                                                                                                       (int(h.value), int(w.value))))
+        out = np.empty(want, np.uint8)
+        paths = (C.c_char_p * 1)(os.fsencode(path))
+        status = (C.c_int32 * 1)()
+        N.check(N.lib().av_png_decode(paths, 1, want[1], want[0], N.AV_PIX_GRAY8, out.ctypes.data_as(C.c_void_p), out.nbytes, 1, status))
+        return out
+    a = np.asarray(mask)
+    if a.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)) or tuple(a.shape) != want:
+        raise ValueError('cam%d mask: a uint8 or bool array of shape %s is wanted, got %s %s' % (cam, want, a.dtype, tuple(a.shape)))
+    return np.ascontiguousarray(a).astype(np.uint8, copy=False)
+
+
 COUNTER_NAMES = ('before_tracking', 'after_tracking', 'after_matching', 'n_fast', 'n_candidates', 'n_new',
                  'n_published', 'overflow')
 
@@ -176,7 +211,12 @@ class FrontendEngine(object):
         `input_height`) with the calibration of the full-size camera; the engine bins them f x f on the GPU (after the conversion,
         ahead of CLAHE) and works on the `width` x `height` = processed image with the calibration of `downscaled_config(config)`.
         `read_image` returns that frame and `read_grid` pixel coordinates are its pixels; the published message is in normalised
-        coordinates and needs no change downstream."""
+        coordinates and needs no change downstream.
+
+        config.cam0_mask / config.cam1_mask (a config object without them has none): the static mask of each camera, for all streams
+        -- None, a uint8 / bool array of shape (input_height, input_width) with non-zero = scene, or the path of an 8-bit grey PNG of
+        that size; `set_masks` has the rules.  They are read here, so every owner of an engine (the drop-in ImageProcessor, EngineSet,
+        the sweep) gets them from its config object."""
         self.config = config
         self.n_streams = int(n_streams)
         self.device = int(device)
@@ -184,6 +224,7 @@ class FrontendEngine(object):
         self._cfg.flags |= N.AV_FE_INPUTS_PERSIST if inputs_persist else 0
         self._keep = None
         self._h = C.c_void_p()
+        masks = [check_mask(cam, getattr(config, 'cam%d_mask' % cam, None), self._cfg.height, self._cfg.width) for cam in (0, 1)]      # before any device call
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_create(C.byref(self._cfg), self.n_streams, self.device, C.byref(self._h)))
         self.max_features = N.lib().av_frontend_max_features(self._h)
@@ -192,6 +233,12 @@ class FrontendEngine(object):
         self._ids = np.zeros((S, cap), np.int64)
         self._uv = np.zeros((S, cap, 4), np.float64)
         self._n = np.zeros(S, np.int32)
+        if masks[0] is not None or masks[1] is not None:
+            try:
+                self.set_masks(*masks)
+            except Exception:
+                self.close()
+                raise
 
     def _set_sizes(self, cfg):
         """The sizes that follow from a packed configuration: input_* = the frames the entry points take, width / height = the image
@@ -271,6 +318,28 @@ class FrontendEngine(object):
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_step_host(self._h, a0.ctypes.data_as(C.c_void_p), a1.ctypes.data_as(C.c_void_p),
                                                   self._frame_bytes, ts, self._stream()))
+
+    def set_masks(self, mask0=None, mask1=None):
+        """The static masks of cam0 and cam1, shared by all streams (av_frontend_set_masks; "Static masks" in include/airvision.h): what
+        is never scene -- outside a fisheye's image circle, airframe in view.  Each is None (all valid), a uint8 / bool array of shape
+        (input_height, input_width) with non-zero = scene, or the path of an 8-bit grey PNG of that size; both None clears.  FAST
+        corners on a masked cam0 pixel are dropped, tracked points that land on one are dropped, and a stereo match whose cam1 point
+        lies on a masked cam1 pixel is no inlier.  With config.image_downscale = f the engine bins them: a pixel is valid iff all f x f
+        pixels under it are.  Blocking.  Accepted only before the engine's first frame: after a step, prestage or frames_upload it is
+        refused (AirvisionError, AV_E_INVALID).  A wrong dtype or shape is a ValueError before anything reaches the device."""
+        m0 = check_mask(0, mask0, self.input_height, self.input_width)
+        m1 = check_mask(1, mask1, self.input_height, self.input_width)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_set_masks(self._h, None if m0 is None else m0.ctypes.data_as(C.c_void_p),
+                                                  None if m1 is None else m1.ctypes.data_as(C.c_void_p)))
+
+    def read_mask(self, cam=0):
+        """The mask of camera `cam` the engine works with: uint8 [height, width] (the processed size) of 0 / 1; refused (AirvisionError,
+        AV_E_INVALID) when none is set for that camera."""
+        out = np.empty((self.height, self.width), np.uint8)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_read_mask(self._h, int(cam), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def frames_reserve(self, n_slots):
         """Allocate the shared frame store (av_frontend_frames_reserve): `n_slots` resident stereo frames."""

@@ -288,6 +288,10 @@ def make_parser():
     ap.add_argument('--downscale', type=int, choices=[1, 2, 4], default=None,
                     help='bin every frame f x f on the GPU ahead of CLAHE and the pyramids and run the front-end on the smaller image with the '
                          'calibration scaled to it (config.image_downscale, default 1 = off); the files stay full size')
+    ap.add_argument('--mask0', metavar='PNG', default=None,
+                    help='static mask of cam0 for every stream: an 8-bit grey PNG of the frame size, 0 = never scene (outside a fisheye image circle, airframe in view), '
+                         'anything else = scene (config.cam0_mask; default: none)')
+    ap.add_argument('--mask1', metavar='PNG', default=None, help='the same for cam1 (config.cam1_mask)')
     ap.add_argument('--gray16-shift', type=int, default=None, metavar='N',
                     help='16-bit frames, grey or Bayer: sample = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
     return ap
@@ -309,6 +313,9 @@ def apply_args(cfg, args):
         cfg.gray16_shift = args.gray16_shift
     if getattr(args, 'downscale', None) is not None:          # (a factor already set on the config object stays unless the switch is given)
         cfg.image_downscale = int(args.downscale)
+    for cam in (0, 1):                                         # (a mask already set on the config object stays unless the switch is given)
+        if getattr(args, 'mask%d' % cam, None) is not None:
+            setattr(cfg, 'cam%d_mask' % cam, getattr(args, 'mask%d' % cam))
     return cfg
 
 
@@ -377,6 +384,8 @@ def main(argv=None):
             rep['pixel_format'] = dict(asked=args.pixel_format, last_batch=cfg.image_format, gray16_shift=cfg.gray16_shift)
         if getattr(cfg, 'image_downscale', 1) != 1:
             rep['downscale'] = cfg.image_downscale
+        if args.mask0 is not None or args.mask1 is not None:
+            rep['masks'] = dict(mask0=args.mask0, mask1=args.mask1)
         print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
