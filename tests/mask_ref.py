@@ -11,6 +11,7 @@ import math
 
 import numpy as np
 
+from fe_harness import run_oracle
 from oracle.frontend import Feat, OracleFrontend, cell_of, cvops, grid_size, integrate_imu, matvec3, predict_feature_tracking, tracking_homography
 
 
@@ -190,23 +191,12 @@ class MaskedOracle(OracleFrontend):
         self.debug['add'] = dict(n_candidates=len(cand), n_new=n_new, n_fast=len(xs))
 
 
-def run_masked_oracle(cfg, stream, mask0=None, mask1=None, n_frames=None, oracle=MaskedOracle):
-    """Replay `stream` (anything with .imu, .n_frames, .frame(k)) through the oracle; per frame dict(ids, uv, nf, add), and the oracle
-    itself (its .drops).  oracle=OracleFrontend runs the plain one (the masks must then be None)."""
-    from uav_airvision_amd.synth import replay
-    fe = oracle(cfg) if oracle is OracleFrontend else oracle(cfg, mask0, mask1)
-    out = []
+def run_masked_oracle(cfg, stream, mask0=None, mask1=None, n_frames=None):
+    """fe_harness.run_oracle with the masked oracle: per frame also the pixel coordinates p0, p1 of the grid's points in both cameras;
+    and the oracle itself (its .drops)."""
+    fe = MaskedOracle(cfg, mask0, mask1)
 
-    def on_frame(m):
-        msg = fe.stereo_callback(m)
-        ids = np.array([f.id for f in msg.features], np.int64)
-        uv = np.array([[f.u0, f.v0, f.u1, f.v1] for f in msg.features], np.float64).reshape(-1, 4)
-        p0 = np.array([f.cam0_point for cell in fe.prev_features for f in cell], np.float64).reshape(-1, 2)
-        p1 = np.array([f.cam1_point for cell in fe.prev_features for f in cell], np.float64).reshape(-1, 2)
-        out.append(dict(ids=ids, uv=uv, nf=dict(fe.num_features), add=dict(fe.debug.get('add', {})), p0=p0, p1=p1))
-
-    class Head(object):
-        imu, frame = stream.imu, staticmethod(stream.frame)
-    Head.n_frames = stream.n_frames if n_frames is None else n_frames
-    replay(Head, [fe.imu_callback], on_frame)
-    return out, fe
+    def points(fe, _msg):
+        return {name: np.array([getattr(f, attr) for cell in fe.prev_features for f in cell], np.float64).reshape(-1, 2)
+                for name, attr in (('p0', 'cam0_point'), ('p1', 'cam1_point'))}
+    return run_oracle(cfg, stream, n_frames, fe, points), fe

@@ -6,18 +6,12 @@ import numpy as np
 import pytest
 
 import downscale_ref as dr
+from fe_harness import make_cfg as _cfg
 from uav_airvision_amd import _native as N
 from uav_airvision_amd.config import ConfigEuRoC
 from uav_airvision_amd.frontend import check_device_frames, check_host_frames, default_max_corners, downscaled_config, pack_frontend_config
 
 pytestmark = pytest.mark.filterwarnings('ignore')
-
-
-def _cfg(**kw):
-    cfg = ConfigEuRoC()
-    for k, v in kw.items():
-        setattr(cfg, k, v)
-    return cfg
 
 
 # ---- the reference itself ----

@@ -5,7 +5,8 @@ import pytest
 
 import bayer_ref as br
 import clahe_ref as cr
-from bayer_helpers import MODES, Mosaicked, make_cfg as _cfg, run_engine, run_oracle, same as _same
+from bayer_helpers import mosaicked_stream
+from fe_harness import MODES, Frames, against_oracle, bare_cfg, make_cfg as _cfg, run_engine, run_oracle, same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +26,15 @@ def mosaicked(base):
     """Per format: the raw stream and the oracle's output on its reference-converted frames (computed once, shared, never changed)."""
     out = {}
     for fmt, shift in SHIFTS.items():
-        st = Mosaicked(base, fmt, NF, shift=shift)
+        st = mosaicked_stream(base, fmt, NF, shift=shift)
         out[fmt] = (st, run_oracle(_cfg(), st))
     return out
 
 
 def _against_oracle(fmt, mode, st, ref, **cfg_kw):
-    got, images = run_engine(_cfg(image_format=fmt, gray16_shift=SHIFTS[fmt], **cfg_kw), [st], mode=mode, images_of=0)
-    assert len(ref) == len(got[0]) == NF and all(len(r['ids']) > 40 for r in ref)      # (a guard against a vacuous comparison: the scene has features)
-    for k, (r, g, im) in enumerate(zip(ref, got[0], images)):
-        ids, uv, cnt = g
-        where = '%s %s frame %d' % (fmt, mode, k)
-        assert np.array_equal(im[0], st.frame(k).cam0_image) and np.array_equal(im[1], st.frame(k).cam1_image), where      # read_image: the converted frames
-        if k > 0:
-            assert [cnt['before_tracking'], cnt['after_tracking'], cnt['after_matching']] == \
-                   [r['nf'].get('before_tracking', 0), r['nf'].get('after_tracking', 0), r['nf'].get('after_matching', 0)], where
-        assert cnt['overflow'] == 0 and cnt['n_published'] == len(r['ids']) and np.array_equal(ids, r['ids']), where
-        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
+    got, images = run_engine(_cfg(image_format=fmt, gray16_shift=SHIFTS[fmt], **cfg_kw), [st], mode=mode, raw=True, images_of=0)
+    assert len(ref) == NF
+    against_oracle(ref, got[0], '%s %s' % (fmt, mode), images, st, min_features=41)      # read_image: the converted frames; the scene has features
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -71,7 +64,7 @@ def test_the_mosaics_are_not_trivially_grey(mosaicked, base):
 
 def test_with_clahe_in_the_host_path(base):
     """Demosaicing, then equalisation in place: against the oracle on clahe_ref.clahe(bayer_ref(...))."""
-    st = Mosaicked(base, 'bayer_rggb8', NF, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
+    st = mosaicked_stream(base, 'bayer_rggb8', NF, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
     _against_oracle('bayer_rggb8', 'host', st, run_oracle(_cfg(), st), use_clahe=True)
 
 
@@ -81,13 +74,13 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
     from uav_airvision_amd.synth import SyntheticStream
     fmt = 'bayer_grbg8'
     cfg = _cfg(image_format=fmt)
-    batch = [Mosaicked(SyntheticStream(cfg, seed=200 + i, n_frames=NF, motion_scale=1.0 + 0.3 * i), fmt, NF) for i in range(2)]
+    batch = [mosaicked_stream(SyntheticStream(cfg, seed=200 + i, n_frames=NF, motion_scale=1.0 + 0.3 * i), fmt, NF) for i in range(2)]
     assert not np.array_equal(batch[0].raw[0][1], batch[1].raw[0][1])
-    alone = [run_engine(cfg, [b])[0] for b in batch]
+    alone = [run_engine(cfg, [b], raw=True)[0] for b in batch]
     assert all(len(a[0]) > 20 for al in alone for a in al)
     assert not all(_same(a, b) for a, b in zip(alone[0], alone[1]))
     for mode in ('step', 'frames'):
-        got = run_engine(cfg, batch, mode=mode)
+        got = run_engine(cfg, batch, mode=mode, raw=True)
         for pos in range(2):
             assert all(_same(a, b) for a, b in zip(alone[pos], got[pos])), (mode, pos)
 
@@ -95,20 +88,13 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
 def test_gray8_is_what_it_was(base):
     """image_format = 'gray8' equals a bare config without the two attributes, outputs and timing span counts per step; a Bayer format
     adds no span to a step (the conversion counts inside the input stage's)."""
-    from clahe_helpers import Cached, run_engine as run_gray
-
-    class Bare(object):
-        pass
-    bare = Bare()
-    for k, v in vars(_cfg()).items():
-        if k not in ('image_format', 'gray16_shift'):
-            setattr(bare, k, v)
-    st = Cached(base, equalise=False)
-    off, sp_off = run_gray(_cfg(image_format='gray8'), [st], n_frames=NF, timing=True)
-    none, sp_none = run_gray(bare, [st], n_frames=NF, timing=True)
+    bare = bare_cfg(lambda k: k in ('image_format', 'gray16_shift'))
+    st = Frames.cached(base)
+    off, sp_off = run_engine(_cfg(image_format='gray8'), [st], n_frames=NF, timing=True)
+    none, sp_none = run_engine(bare, [st], n_frames=NF, timing=True)
     assert all(len(a[0]) > 40 for a in off[0])
     assert all(_same(a, b) for a, b in zip(off[0], none[0])) and sp_off == sp_none
-    on, sp_on = run_engine(_cfg(image_format='bayer_rggb8'), [Mosaicked(base, 'bayer_rggb8', NF)], mode='step', timing=True)
+    on, sp_on = run_engine(_cfg(image_format='bayer_rggb8'), [mosaicked_stream(base, 'bayer_rggb8', NF)], mode='step', raw=True, timing=True)
     assert sp_on == sp_off and all(s['pyramid'] == 1 for s in sp_on)
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import bayer_ref as br
+from fe_harness import Frames
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +29,11 @@ def sequence(tmp_path_factory):
     from uav_airvision_amd.synth import SyntheticStream
     root = tmp_path_factory.mktemp('bayer_sweep')
     st = SyntheticStream(ConfigEuRoC(), seed=77, n_frames=N_FRAMES, motion_scale=1.5, t0=1403636580.0, rest=1.0)
-    frames = [st.frame(k) for k in range(N_FRAMES)]
-    st.frame = lambda k: frames[k]
+    frames = Frames.cached(st)
+    st.frame = frames.frame                               # rendered once, written twice
     bayer = write_euroc_layout(str(root / 'SEQ_bayer'), st, compress_level=1, pixel_format=FMT)
-    conv = []
-    for m in frames:
-        a, b = (br.to_gray8(br.mosaic(im, FMT), FMT) for im in (m.cam0_image, m.cam1_image))
-        conv.append(type(m)(m.timestamp, a, b, type(m.cam0_msg)(m.timestamp, a), type(m.cam1_msg)(m.timestamp, b)))
-    st.frame = lambda k: conv[k]
+    conv = frames.map(lambda im: br.to_gray8(br.mosaic(im, FMT), FMT))
+    st.frame = conv.frame
     grey = write_euroc_layout(str(root / 'SEQ_conv'), st, compress_level=1, pixel_format='gray8')
     return bayer, grey, conv
 
@@ -64,7 +62,7 @@ def test_the_sweep_equals_the_engine_fed_the_converted_frames(sequence):
     files = EuRoCDataset._list_images(os.path.join(bayer, 'mav0', 'cam0', 'data'))[0]
     arr = frame_array(FMT, 2, 480, 752)
     decode_batch(files[:2], arr)
-    assert np.array_equal(br.to_gray8(arr, FMT), np.stack([conv[0].cam0_image, conv[1].cam0_image]))
+    assert np.array_equal(br.to_gray8(arr, FMT), np.stack([conv.frame(0).cam0_image, conv.frame(1).cam0_image]))
     want, want_traj = _sweep(grey, 'gray8', True)
     assert len(want) == N_FRAMES and all(len(w[1]) > 30 for w in want)
     for share in (True, False):
@@ -73,7 +71,7 @@ def test_the_sweep_equals_the_engine_fed_the_converted_frames(sequence):
         for k, (w, g) in enumerate(zip(want, got)):
             assert w[0] == g[0] and np.array_equal(w[1], g[1]) and np.array_equal(w[2].view(np.uint64), g[2].view(np.uint64)), (share, k)
         assert traj.shape == want_traj.shape and np.array_equal(traj.view(np.uint64), want_traj.view(np.uint64)), share
-    assert not np.array_equal(arr[0], conv[0].cam0_image)             # (the files do hold a mosaic, not the grey frames)
+    assert not np.array_equal(arr[0], conv.frame(0).cam0_image)       # (the files do hold a mosaic, not the grey frames)
 
 
 def test_the_command_line(sequence, tmp_path):

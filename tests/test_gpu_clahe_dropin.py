@@ -7,8 +7,10 @@ import sys
 import numpy as np
 import pytest
 
+import clahe_ref as cr
+from clahe_helpers import STREAM
 from conftest import ROOT
-from clahe_helpers import STREAM, Cached, make_cfg as _cfg, run_engine
+from fe_harness import Frames, make_cfg as _cfg, run_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +24,8 @@ def test_drop_in_pipeline_honours_the_switch_and_shows_the_viewer_the_equalised_
     import image_processing as ip
     from viewer import HeadlessViewer
     cfg = _cfg(use_clahe=True)
-    st = Cached(SyntheticStream(cfg, **dict(STREAM, n_frames=6)))
+    st = Frames.cached(SyntheticStream(cfg, **dict(STREAM, n_frames=6)))
+    eq = st.map(cr.clahe)
     eng = run_engine(cfg, [st], mode='host')[0]
     proc = ip.ImageProcessor(cfg)
     assert proc.use_clahe is True
@@ -33,8 +36,8 @@ def test_drop_in_pipeline_honours_the_switch_and_shows_the_viewer_the_equalised_
     for k, (msg, (ids, uv, _cnt)) in enumerate(zip(seen, eng)):
         assert np.array_equal(np.array([f.id for f in msg.features], np.int64), ids), k
         assert np.array_equal(np.array([[f.u0, f.v0, f.u1, f.v1] for f in msg.features]).reshape(-1, 4).view(np.uint64), uv.view(np.uint64)), k
-        assert np.array_equal(shown[k], st.equalised().frame(k).cam0_image), k
-    assert np.array_equal(proc.equalized_image(1), st.equalised().frame(5).cam1_image)
+        assert np.array_equal(shown[k], eq.frame(k).cam0_image), k
+    assert np.array_equal(proc.equalized_image(1), eq.frame(5).cam1_image)
     proc.close()
     off = ip.ImageProcessor(_cfg())
     assert off.use_clahe is False
@@ -107,7 +110,7 @@ def test_front_end_with_clahe_feeds_the_filter():
     from uav_airvision_amd.frontend import FrontendEngine
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.synth import SyntheticStream
-    st = Cached(SyntheticStream(_cfg(), **dict(STREAM, n_frames=60)), equalise=False)
+    st = Frames.cached(SyntheticStream(_cfg(), **dict(STREAM, n_frames=60)))
     res = {}
     for on in (True, False):
         cfg = _cfg(use_clahe=on)
@@ -135,7 +138,7 @@ def test_front_end_with_clahe_feeds_the_filter():
         res[on] = (float('nan'), len(traj), float(np.mean(nfeat)))
         if len(traj) > 20:
             traj = np.array(traj)
-            gt = np.array([[t] + list(st.base.position(t)) for t in traj[:, 0]])
+            gt = np.array([[t] + list(st.position(t)) for t in traj[:, 0]])
             res[on] = (ate(traj, gt)['rmse'], len(traj), float(np.mean(nfeat)))
     assert res[True][1] >= 40 and res[True][2] >= 2 * res[False][2]
     print('ATE rmse over %d frames: CLAHE on %.4f m (%d poses, %.1f features / frame), off %.4f m (%d poses, %.1f features / frame)'

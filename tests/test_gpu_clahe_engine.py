@@ -3,7 +3,9 @@ tests/clahe_ref.py, in every entry path; the switch off; placement independence 
 import numpy as np
 import pytest
 
-from clahe_helpers import MODES, STREAM, Cached, make_cfg as _cfg, run_engine, run_oracle, same as _same
+import clahe_ref as cr
+from clahe_helpers import STREAM
+from fe_harness import MODES, Frames, against_oracle, bare_cfg, make_cfg as _cfg, run_engine, run_oracle, same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -11,8 +13,9 @@ pytestmark = pytest.mark.gpu
 def flat():
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _cfg(use_clahe=True)
-    st = Cached(SyntheticStream(cfg, **STREAM))
-    return cfg, st, run_oracle(cfg, st.equalised())
+    st = Frames.cached(SyntheticStream(cfg, **STREAM))
+    eq = st.map(cr.clahe)
+    return cfg, st, eq, run_oracle(cfg, eq)
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -20,32 +23,21 @@ def test_engine_with_clahe_matches_the_oracle_on_equalised_frames(flat, mode):
     """26 frames (past the first prune): ids, coordinates and the tracker's stage counters identical to the unmodified oracle run on
     frames the NumPy reference equalised, on every frame, in each entry path; read_image returns exactly those frames; the caller's
     images are untouched (asserted inside run_engine)."""
-    cfg, st, ref = flat
-    assert len(ref) == 26 and all(len(r['ids']) > 40 for r in ref[1:])
+    cfg, st, eq, ref = flat
+    assert len(ref) == 26
     got, images = run_engine(cfg, [st], mode=mode, images_of=0)
-    eq = st.equalised()
-    for k, (r, g, im) in enumerate(zip(ref, got[0], images)):
-        ids, uv, cnt = g
-        where = '%s frame %d' % (mode, k)
-        assert np.array_equal(im[0], eq.frame(k).cam0_image) and np.array_equal(im[1], eq.frame(k).cam1_image), where
-        if k > 0:
-            assert [cnt['before_tracking'], cnt['after_tracking'], cnt['after_matching']] == \
-                   [r['nf'].get('before_tracking', 0), r['nf'].get('after_tracking', 0), r['nf'].get('after_matching', 0)], where
-        assert cnt['overflow'] == 0 and cnt['n_published'] == len(r['ids']) and np.array_equal(ids, r['ids']), where
-        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
+    against_oracle(ref, got[0], mode, images, eq, min_features=41, floor_from=1)
 
 
 def test_other_clip_limit_and_tile_grid(flat):
     """clahe_clip_limit and clahe_tiles reach the stage: 4.0 and (4, 6) over six frames, against the reference with the same."""
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _cfg(use_clahe=True, clahe_clip_limit=4.0, clahe_tiles=(4, 6))
-    st = Cached(SyntheticStream(cfg, **dict(STREAM, n_frames=6)), 4.0, (4, 6))
-    ref = run_oracle(cfg, st.equalised())
+    st = Frames.cached(SyntheticStream(cfg, **dict(STREAM, n_frames=6)))
+    eq = st.map(lambda a: cr.clahe(a, 4.0, (4, 6)))
     got, images = run_engine(cfg, [st], images_of=0)
-    for k, (r, g, im) in enumerate(zip(ref, got[0], images)):
-        assert np.array_equal(im[0], st.equalised().frame(k).cam0_image), k
-        assert np.array_equal(g[0], r['ids']) and np.array_equal(g[1].view(np.uint64), r['uv'].view(np.uint64)), k
-    assert not np.array_equal(images[0][0], flat[1].equalised().frame(0).cam0_image)
+    against_oracle(run_oracle(cfg, eq), got[0], 'clip 4, tiles 4 x 6', images, eq)
+    assert not np.array_equal(images[0][0], flat[2].frame(0).cam0_image)
 
 
 def test_off_is_off(flat):
@@ -53,14 +45,9 @@ def test_off_is_off(flat):
     read_image is refused; the switch on adds no span (the stage shares the pyramid launch's, class 0) and changes what is published."""
     from uav_airvision_amd import _native as N
     from uav_airvision_amd.frontend import FrontendEngine
-    _cfg_on, st, _ref = flat
+    _cfg_on, st, _eq, _ref = flat
 
-    class Bare(object):
-        pass
-    bare = Bare()
-    for k, v in vars(_cfg()).items():
-        if 'clahe' not in k:
-            setattr(bare, k, v)
+    bare = bare_cfg(lambda k: 'clahe' in k)
     assert not hasattr(bare, 'use_clahe')
     off, sp_off = run_engine(_cfg(use_clahe=False), [st], n_frames=8, timing=True)
     none, sp_none = run_engine(bare, [st], n_frames=8, timing=True)
@@ -93,7 +80,8 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
                              contrast=1.0 - 0.013 * i, brightness_offset=float(i % 9) * 8.0 - 30.0, render=False)
         st.tex, st.tex_mean, st.rays0, st.rays1 = first.tex, first.tex_mean, first.rays0, first.rays1      # the per-pixel rays depend on the cameras only
         return st
-    batch = [Cached(stream(i), equalise=i == 17) for i in range(64)]
+    batch = [Frames.cached(stream(i)) for i in range(64)]
+    eq = batch[17].map(cr.clahe)
     frames0 = [b.frame(0).cam0_image for b in batch]
     assert all(not np.array_equal(frames0[i], frames0[j]) for i in range(64) for j in range(i))
     alone = {pos: run_engine(cfg, [batch[pos]])[0] for pos in (0, 17, 63)}
@@ -103,7 +91,6 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
             assert all(len(a[0]) > 20 for a in alone[pos])
             assert all(_same(a, b) for a, b in zip(alone[pos], got[pos])), (mode, pos)
         assert not all(_same(a, b) for a, b in zip(alone[17], got[16])), mode
-        eq = batch[17].equalised()
         assert all(np.array_equal(im[0], eq.frame(k).cam0_image) and np.array_equal(im[1], eq.frame(k).cam1_image) for k, im in enumerate(images)), mode
 
 
@@ -112,8 +99,7 @@ def test_read_image_follows_the_path_of_the_last_step_and_duplicate_entries_are_
     buffer; with the switch on an upload that names an entry twice is refused (the entries are equalised where they lie)."""
     from uav_airvision_amd import _native as N
     from uav_airvision_amd.frontend import FrontendEngine
-    cfg, st, _ref = flat
-    eq = st.equalised()
+    cfg, st, eq, _ref = flat
     eng = FrontendEngine(cfg, n_streams=1)
     eng.frames_reserve(4)
     m0, m1, m2 = st.frame(0), st.frame(1), st.frame(2)
@@ -153,7 +139,7 @@ def test_a_low_contrast_stream_gets_its_features_back(flat):
     at frame 10 the oracle publishes 13 features on the raw frames and 100 on the reference-equalised ones (0.2: 99 against 100, no
     difference to speak of; 0.08: 0 against 100).  The engine with the switch publishes at least twice what the engine without it
     does at that frame."""
-    cfg_on, st, ref = flat
+    cfg_on, st, _eq, ref = flat
     raw = run_oracle(_cfg(), st, n_frames=11)
     n_raw, n_eq = len(raw[10]['ids']), len(ref[10]['ids'])
     print('oracle at frame 10: raw %d, equalised %d' % (n_raw, n_eq))

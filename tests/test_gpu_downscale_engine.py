@@ -5,8 +5,10 @@ import numpy as np
 import pytest
 
 import clahe_ref as cr
-from clahe_helpers import MODES, Cached, make_cfg as _cfg, run_engine, run_oracle, same as _same
-from downscale_helpers import MIN_FEATURES, Binned, against_oracle, check_reference
+from bayer_helpers import mosaicked_stream
+from downscale_helpers import FLOOR, MIN_FEATURES, binned_stream, check_reference
+from fe_harness import MODES, Frames, against_oracle, bare_cfg, make_cfg as _cfg, run_engine, run_oracle, same as _same, scaled_cfg
+from ransac_helpers import run_ransac_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -23,30 +25,26 @@ def _dcfg(cfg):
 @pytest.fixture(scope='module')
 def base():
     from uav_airvision_amd.synth import SyntheticStream
-    return Cached(SyntheticStream(_cfg(), **STREAM), equalise=False)
+    return Frames.cached(SyntheticStream(_cfg(), **STREAM))
 
 
 @pytest.fixture(scope='module')
 def ref2(base):
     """The oracle on the 2 x 2 binned frames of `base` (computed once, shared, never changed)."""
-    binned = Binned(base, 2)
+    binned = binned_stream(base, 2)
     ref = run_oracle(_dcfg(_cfg(image_downscale=2)), binned)
     check_reference(ref, NF)
     return binned, ref
 
 
 def _big_cfg(**kw):
-    from uav_airvision_amd.synth import scaled_config
-    cfg = scaled_config(_cfg(), 832, 640)
-    for k, v in kw.items():
-        setattr(cfg, k, v)
-    return cfg
+    return scaled_cfg(832, 640, **kw)
 
 
 @pytest.fixture(scope='module')
 def big():
     from uav_airvision_amd.synth import SyntheticStream
-    return Cached(SyntheticStream(_big_cfg(), seed=21, n_frames=NF_BIG, motion_scale=1.5), equalise=False)
+    return Frames.cached(SyntheticStream(_big_cfg(), seed=21, n_frames=NF_BIG, motion_scale=1.5))
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -55,7 +53,7 @@ def test_752x480_by_two_in_every_entry_path(base, ref2, mode):
     caller's arrays and tensors are unchanged (asserted inside run_engine); read_image is the binned frame."""
     binned, ref = ref2
     got, images = run_engine(_cfg(image_downscale=2), [base], mode=mode, images_of=0)
-    against_oracle(ref, got[0], '752x480 f2 ' + mode, images, binned)
+    against_oracle(ref, got[0], '752x480 f2 ' + mode, images, binned, **FLOOR)
 
 
 @pytest.mark.parametrize('mode', ['step', 'frames'])
@@ -63,47 +61,44 @@ def test_752x480_by_two_in_every_entry_path(base, ref2, mode):
 def test_832x640_by_two_and_four(big, f, mode):
     """Processed widths 416 and 208: whole vectors.  At f = 4 the last pyramid level is 26 x 20, just above AV_PYR_BORDER."""
     cfg = _big_cfg(image_downscale=f)
-    binned = Binned(big, f)
+    binned = binned_stream(big, f)
     assert binned.frame(0).cam0_image.shape == (640 // f, 832 // f)
     ref = run_oracle(_dcfg(cfg), binned)
     got, images = run_engine(cfg, [big], mode=mode, images_of=0)
-    against_oracle(ref, got[0], '832x640 f%d %s' % (f, mode), images, binned)
+    against_oracle(ref, got[0], '832x640 f%d %s' % (f, mode), images, binned, **FLOOR)
 
 
 def test_with_clahe_and_ransac(base):
     """Binning, then CLAHE at the binned size, then the tracker with its outlier rejection: against the RANSAC oracle on
     clahe_ref.clahe(downscale_ref.downscale(frame)); the reference's decisions are clear of their thresholds (margin >= 1e-9)."""
-    from test_gpu_ransac_engine import run_oracle as run_ransac_oracle
     cfg = _cfg(image_downscale=2, use_clahe=True, use_ransac=True)
-    binned = Binned(base, 2, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
+    binned = binned_stream(base, 2, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
     ref = run_ransac_oracle(_dcfg(cfg), binned)
     assert all(r['margin'] >= 1e-9 for r in ref), [r['margin'] for r in ref]
     for mode in ('step', 'frames'):
         got, images = run_engine(cfg, [base], mode=mode, images_of=0)
-        against_oracle(ref, got[0], 'clahe + ransac ' + mode, images, binned)
+        against_oracle(ref, got[0], 'clahe + ransac ' + mode, images, binned, **FLOOR)
 
 
 @pytest.mark.parametrize('mode', ['step', 'host', 'frames'])
 def test_behind_the_bayer_conversion(base, mode):
     """image_format = 'bayer_rggb8': conversion into the full-size scratch, then binning: against the oracle on
     downscale_ref.downscale(bayer_ref.to_gray8(mosaic))."""
-    from bayer_helpers import Mosaicked, run_engine as run_raw
-    st = Mosaicked(base, 'bayer_rggb8', NF)
+    st = mosaicked_stream(base, 'bayer_rggb8', NF)
     cfg = _cfg(image_downscale=2, image_format='bayer_rggb8')
-    binned = Binned(st, 2)
+    binned = binned_stream(st, 2)
     ref = run_oracle(_dcfg(_cfg(image_downscale=2)), binned)
-    got, images = run_raw(cfg, [st], mode=mode, images_of=0)
-    against_oracle(ref, got[0], 'bayer f2 ' + mode, images, binned)
+    got, images = run_engine(cfg, [st], mode=mode, raw=True, images_of=0)
+    against_oracle(ref, got[0], 'bayer f2 ' + mode, images, binned, **FLOOR)
     assert not np.array_equal(st.frame(0).cam0_image, base.frame(0).cam0_image)      # (the conversion is not the identity)
 
 
 def test_the_frame_store_scratch_grows_with_a_larger_upload(base):
     """Bayer conversion and binning together: an upload of one frame, then one of three (the full-size grey scratch of the store has
     to grow), then a step on an entry of each: read_image is downscale_ref.downscale(bayer_ref.to_gray8(mosaic)) of the right frame."""
-    from bayer_helpers import Mosaicked
     from uav_airvision_amd.frontend import FrontendEngine
-    st = Mosaicked(base, 'bayer_rggb8', 4)
-    binned = Binned(st, 2)
+    st = mosaicked_stream(base, 'bayer_rggb8', 4)
+    binned = binned_stream(st, 2)
     eng = FrontendEngine(_cfg(image_downscale=2, image_format='bayer_rggb8'), n_streams=1)
     eng.frames_reserve(40)
     eng.frames_upload(np.array([5], np.int32), st.raw[0][1][None], st.raw[0][2][None])
@@ -121,14 +116,14 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
     (and what the oracle publishes on its binned frames)."""
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _cfg(image_downscale=2)
-    batch = [Cached(SyntheticStream(cfg, seed=201 + i, n_frames=NF, motion_scale=1.0 + 0.3 * i), equalise=False) for i in range(3)]
+    batch = [Frames.cached(SyntheticStream(cfg, seed=201 + i, n_frames=NF, motion_scale=1.0 + 0.3 * i)) for i in range(3)]
     assert not np.array_equal(batch[0].frame(0).cam0_image, batch[1].frame(0).cam0_image)
-    refs = [run_oracle(_dcfg(cfg), Binned(b, 2)) for b in batch]
+    refs = [run_oracle(_dcfg(cfg), binned_stream(b, 2)) for b in batch]
     assert not all(np.array_equal(a['uv'], b['uv']) for a, b in zip(refs[0], refs[1]))
     for mode in ('step', 'frames'):
         got = run_engine(cfg, batch, mode=mode)
         for pos in range(3):
-            against_oracle(refs[pos], got[pos], 'batch %s stream %d' % (mode, pos))
+            against_oracle(refs[pos], got[pos], 'batch %s stream %d' % (mode, pos), **FLOOR)
 
 
 def test_sizes_and_read_backs(base, ref2):
@@ -160,13 +155,7 @@ def test_factor_one_is_off(base):
     read_image is still refused.  A factor of 2 adds no span either: the binning runs inside the input stage's one."""
     from uav_airvision_amd import _native as N
     from uav_airvision_amd.frontend import FrontendEngine
-
-    class Bare(object):
-        pass
-    bare = Bare()
-    for k, v in vars(_cfg()).items():
-        if k != 'image_downscale':
-            setattr(bare, k, v)
+    bare = bare_cfg(lambda k: k == 'image_downscale')
     assert not hasattr(bare, 'image_downscale')
     for mode in ('step', 'host', 'frames'):
         off, sp_off = run_engine(_cfg(image_downscale=1), [base], mode=mode, timing=True)

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import downscale_ref as dr
-from clahe_helpers import make_cfg
 from downscale_helpers import check_reference
+from fe_harness import make_cfg, with_images
 
 pytestmark = pytest.mark.gpu
 
@@ -27,8 +27,7 @@ def _oracle_on_binned_files(cfg, path, f):
 
     def on_stereo(m):
         assert m.cam0_image.shape == (480, 752)
-        a, b = dr.downscale(m.cam0_image, f), dr.downscale(m.cam1_image, f)
-        msg = fe.stereo_callback(type(m)(m.timestamp, a, b, type(m.cam0_msg)(m.timestamp, a), type(m.cam1_msg)(m.timestamp, b)))
+        msg = fe.stereo_callback(with_images(m, dr.downscale(m.cam0_image, f), dr.downscale(m.cam1_image, f)))
         out.append(dict(ts=m.timestamp, ids=np.array([x.id for x in msg.features], np.int64),
                         uv=np.array([[x.u0, x.v0, x.u1, x.v1] for x in msg.features], np.float64).reshape(-1, 4)))
     replay(ds, [fe.imu_callback], on_stereo)

@@ -6,9 +6,9 @@ import pytest
 
 import clahe_ref as cr
 import downscale_ref as dr
-from bayer_helpers import MODES, Mosaicked, make_cfg as _cfg, run_engine, run_oracle, same as _same
-from clahe_helpers import Cached
-from downscale_helpers import Binned, against_oracle, check_reference
+from bayer_helpers import mosaicked_stream
+from downscale_helpers import FLOOR, binned_stream, check_reference
+from fe_harness import MODES, Frames, against_oracle, make_cfg as _cfg, run_engine, run_oracle, same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ def _all_on():
 @pytest.fixture(scope='module')
 def bases():
     from uav_airvision_amd.synth import SyntheticStream
-    return [Cached(SyntheticStream(_cfg(), seed=17 + i, n_frames=NF, motion_scale=2.0 - 0.5 * i), equalise=False) for i in range(2)]
+    return [Frames.cached(SyntheticStream(_cfg(), seed=17 + i, n_frames=NF, motion_scale=2.0 - 0.5 * i)) for i in range(2)]
 
 
 @pytest.fixture(scope='module')
@@ -31,7 +31,7 @@ def chain(bases):
     """Two streams as 16-bit mosaics, their reference grey frames (converted, binned by two, equalised: what read_image has to give)
     and the oracle on those, computed once and never changed."""
     from uav_airvision_amd.frontend import downscaled_config
-    streams = [Mosaicked(b, FMT, NF, post=lambda a: cr.clahe(dr.downscale(a, 2), 2.0, (8, 8))) for b in bases]
+    streams = [mosaicked_stream(b, FMT, NF, post=lambda a: cr.clahe(dr.downscale(a, 2), 2.0, (8, 8))) for b in bases]
     assert streams[0].frame(0).cam0_image.shape == (240, 376)
     refs = [run_oracle(downscaled_config(_cfg(image_downscale=2)), s) for s in streams]
     for r in refs:
@@ -43,7 +43,7 @@ def chain(bases):
 def runs(chain):
     """Every entry path once: per mode the features of both streams and the images of stream 1."""
     streams, _refs = chain
-    return {mode: run_engine(_all_on(), streams, mode=mode, images_of=1) for mode in MODES}
+    return {mode: run_engine(_all_on(), streams, mode=mode, raw=True, images_of=1) for mode in MODES}
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -52,8 +52,8 @@ def test_all_three_stages_in_every_entry_path(chain, runs, mode):
     reference chain byte for byte, ids, points and counts are the oracle's on those grey frames, for both streams of the batch."""
     streams, refs = chain
     got, images = runs[mode]
-    against_oracle(refs[1], got[1], 'all stages %s stream 1' % mode, images, streams[1])
-    against_oracle(refs[0], got[0], 'all stages %s stream 0' % mode)
+    against_oracle(refs[1], got[1], 'all stages %s stream 1' % mode, images, streams[1], **FLOOR)
+    against_oracle(refs[0], got[0], 'all stages %s stream 0' % mode, **FLOOR)
 
 
 def test_all_three_stages_agree_across_the_entry_paths(runs):
@@ -70,7 +70,7 @@ def test_an_entry_named_twice_takes_the_later_frame_with_binning_alone(bases):
     write list as the conversion does (tests/test_gpu_pixfmt_engine.py): of an entry named twice the later frame wins, as with plain
     grey frames, and the entry named once between the two is its own frame."""
     from uav_airvision_amd.frontend import FrontendEngine
-    binned = [Binned(b, 2, n_frames=2) for b in bases]
+    binned = [binned_stream(b, 2, n_frames=2) for b in bases]
     eng = FrontendEngine(_cfg(image_downscale=2), n_streams=2)
     eng.frames_reserve(4)
     a, b, x = bases[0].frame(0), bases[0].frame(1), bases[1].frame(0)

@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 
 import clahe_ref as cr
-from clahe_helpers import MODES, run_engine, run_oracle
+from fe_harness import MODES, Frames, against_oracle, read_ransac_counts, run_engine, run_oracle, scaled_cfg as _scaled_cfg
+from ransac_helpers import check_ransac_counts, run_ransac_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -119,47 +120,16 @@ def test_clahe_above_the_old_limit_is_bit_identical_to_the_numpy_definition(w, h
 
 
 # ---- engine --------------------------------------------------------------------------------------------------------------------
-class Cached(object):
-    """A synthetic stream with its frames rendered once."""
-
-    def __init__(self, base):
-        self.base, self.imu, self.n_frames, self.position = base, base.imu, base.n_frames, base.position
-        self._frames = [base.frame(k) for k in range(base.n_frames)]
-
-    def frame(self, k):
-        return self._frames[k]
-
-
-def _scaled_cfg(w, h, **kw):
-    from uav_airvision_amd.config import ConfigEuRoC
-    from uav_airvision_amd.synth import scaled_config
-    cfg = scaled_config(ConfigEuRoC(), w, h)
-    for k, v in kw.items():
-        setattr(cfg, k, v)
-    return cfg
-
-
 def _streams(cfg, seeds, n_frames, **kw):
     from uav_airvision_amd.synth import SyntheticStream, make_texture
     tex = make_texture(0xA1B0 + 3)               # one texture, another part of it and another trajectory noise per seed
-    return [Cached(SyntheticStream(cfg, seed=s, n_frames=n_frames, motion_scale=1.5, texture=tex, tex_offset=(37.0 * i, 11.0 * i), **kw))
+    return [Frames.cached(SyntheticStream(cfg, seed=s, n_frames=n_frames, motion_scale=1.5, texture=tex, tex_offset=(37.0 * i, 11.0 * i), **kw))
             for i, s in enumerate(seeds)]
 
 
 def _check(ref, got, tag):
-    """ids and coordinates bit-identical, the tracker's counters equal, no overflow, a full grid from the third frame on."""
-    assert len(ref) == len(got)
-    for k, (r, g) in enumerate(zip(ref, got)):
-        ids, uv, cnt = g
-        where = '%s frame %d' % (tag, k)
-        assert cnt['overflow'] == 0, where
-        if k > 0:
-            assert [cnt['before_tracking'], cnt['after_tracking'], cnt['after_matching']] == \
-                   [r['nf'].get('before_tracking', 0), r['nf'].get('after_tracking', 0), r['nf'].get('after_matching', 0)], where
-        assert cnt['n_published'] == len(r['ids']) and np.array_equal(ids, r['ids']), where
-        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
-        if k >= 2:
-            assert len(ids) >= GRID_FLOOR, (where, len(ids))
+    """The harness's comparison, and a full grid from the third frame on."""
+    against_oracle(ref, got, tag, min_features=GRID_FLOOR, floor_from=2)
 
 
 @pytest.fixture(scope='module')
@@ -205,22 +175,14 @@ def test_engine_at_1280x720_matches_the_oracle(at_1280x720, mode):
 def test_engine_at_832x640_with_clahe_and_ransac_matches_the_oracle_with_both_references_inserted():
     """use_clahe and use_ransac together: the oracle runs on frames the NumPy CLAHE definition equalised, with the reference RANSAC
     inserted where the engine runs its stage (the patterns of test_gpu_clahe_engine.py and test_gpu_ransac_engine.py)."""
-    import clahe_helpers
-    from test_gpu_ransac_engine import run_engine as run_ransac_engine, run_oracle as run_ransac_oracle
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _scaled_cfg(832, 640, use_clahe=True, use_ransac=True)
-    st = clahe_helpers.Cached(SyntheticStream(cfg, seed=13, n_frames=6, motion_scale=3.0, moving_region=(280, 200, 550, 440), moving_amplitude=0.3))
-    ref = run_ransac_oracle(cfg, st.equalised())
+    st = Frames.cached(SyntheticStream(cfg, seed=13, n_frames=6, motion_scale=3.0, moving_region=(280, 200, 550, 440), moving_amplitude=0.3))
+    ref = run_ransac_oracle(cfg, st.map(cr.clahe))
     assert all(r['margin'] >= 1e-9 for r in ref), [r['margin'] for r in ref]
-    assert all(len(r['ids']) >= GRID_FLOOR for r in ref[2:])
-    got = run_ransac_engine(cfg, [st], mode='step')[0]
-    for k, (r, g) in enumerate(zip(ref, got)):
-        ids, uv, cnt, rc = g
-        if k > 0:
-            assert cnt['after_matching'] == r['nf'].get('after_matching', 0), k
-        assert [rc['after_ransac'], rc['cam0_set'], rc['cam1_set'], rc['path']] == r['counts'], (k, rc, r['counts'])
-        assert cnt['overflow'] == 0 and np.array_equal(ids, r['ids']), k
-        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), k
+    got = run_engine(cfg, [st], mode='step', read=read_ransac_counts)[0]
+    _check(ref, got, 'clahe + ransac')
+    check_ransac_counts(ref, got, 'clahe + ransac')
 
 
 # ---- EuRoC-layout sweep --------------------------------------------------------------------------------------------------------

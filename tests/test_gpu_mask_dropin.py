@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import mask_ref as mr
-from clahe_helpers import Cached, make_cfg as _cfg
 from conftest import ROOT
+from fe_harness import Frames, make_cfg as _cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ def test_drop_in_pipeline_reads_the_masks_from_its_config(tmp_path):
     import image_processing as ip
     m0, m1 = mr.comb_mask(W, H, 96, 24, 0), mr.comb_mask(W, H, 96, 24, 48)
     Image.fromarray(m0 * 255).save(str(tmp_path / 'cam0_mask.png'))
-    st = Cached(SyntheticStream(_cfg(), seed=13, n_frames=6, motion_scale=3.0), equalise=False)
+    st = Frames.cached(SyntheticStream(_cfg(), seed=13, n_frames=6, motion_scale=3.0))
     ref, fe = mr.run_masked_oracle(_cfg(), st, m0, m1)
     assert fe.drops['track'] + fe.drops['stereo'] >= 100, fe.drops
     proc = ip.ImageProcessor(_cfg(cam0_mask=str(tmp_path / 'cam0_mask.png'), cam1_mask=m1))

@@ -4,44 +4,29 @@ entry path; circles; off is off; binning; CLAHE; RANSAC; placement in a batch; a
 import numpy as np
 import pytest
 
+import clahe_ref as cr
 import mask_ref as mr
-from clahe_helpers import MODES, Cached, make_cfg as _cfg, run_engine, same as _same
-from downscale_helpers import Binned
+from downscale_helpers import binned_stream
+from fe_harness import MODES, Frames, against_oracle as against, bare_cfg, make_cfg as _cfg, read_grid, read_ransac_counts, run_engine, run_oracle, \
+    same as _same, scaled_cfg
 
 pytestmark = pytest.mark.gpu
 
 W, H = 752, 480
 STREAM = dict(seed=13, n_frames=10, motion_scale=3.0)
-COUNTERS = ('after_tracking', 'after_matching')
-ADDED = ('n_fast', 'n_candidates', 'n_new')
-
-
-def against(ref, got, tag):
-    """ids and uv bit-identical, after_tracking / after_matching / n_fast / n_candidates / n_new equal, no overflow, on every frame."""
-    assert len(ref) == len(got) and len(ref) > 0, tag
-    for k, (r, g) in enumerate(zip(ref, got)):
-        ids, uv, cnt = g[0], g[1], g[2]
-        where = '%s frame %d' % (tag, k)
-        assert cnt['overflow'] == 0, where
-        assert np.array_equal(ids, r['ids']), where
-        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
-        if k > 0:
-            assert [cnt[c] for c in COUNTERS] == [r['nf'].get(c, 0) for c in COUNTERS], (where, cnt, r['nf'])
-        assert [cnt[c] for c in ADDED] == [r['add'][c] for c in ADDED], (where, cnt, r['add'])
 
 
 @pytest.fixture(scope='module')
 def base():
-    """The stream of every test at 752 x 480, rendered once, with its reference-equalised twin."""
+    """The stream of every test at 752 x 480, rendered once."""
     from uav_airvision_amd.synth import SyntheticStream
-    return Cached(SyntheticStream(_cfg(), **STREAM))
+    return Frames.cached(SyntheticStream(_cfg(), **STREAM))
 
 
 @pytest.fixture(scope='module')
 def plain(base):
     """The plain oracle's run (computed once, shared, never changed)."""
-    from oracle.frontend import OracleFrontend
-    return mr.run_masked_oracle(_cfg(), base, oracle=OracleFrontend)[0]
+    return run_oracle(_cfg(), base)
 
 
 @pytest.fixture(scope='module')
@@ -82,12 +67,7 @@ def test_off_is_off(base, plain, combs):
     m0, m1, _ref = combs
     ones = np.ones((H, W), np.uint8)
 
-    class Bare(object):
-        pass
-    bare = Bare()
-    for k, v in vars(_cfg()).items():
-        if k not in ('cam0_mask', 'cam1_mask'):
-            setattr(bare, k, v)
+    bare = bare_cfg(lambda k: k in ('cam0_mask', 'cam1_mask'))
     assert not hasattr(bare, 'cam0_mask') and not hasattr(bare, 'cam1_mask')
     n = 6
     for mode in ('step', 'frames'):
@@ -116,7 +96,7 @@ def test_binning(base):
     b0, b1 = mr.bin_mask(m0, 2), mr.bin_mask(m1, 2)
     assert b0[0, 11] == 0 and b0[0, 12] == 1 and b0[0, 46] == 1 and b0[0, 47] == 0 and b0.sum() < m0.sum() // 4
     cfg = _cfg(image_downscale=2, cam0_mask=m0 * 255, cam1_mask=m1.astype(bool))          # any non-zero value, or bool, is valid
-    ref, fe = mr.run_masked_oracle(downscaled_config(_cfg(image_downscale=2)), Binned(base, 2), b0, b1)
+    ref, fe = mr.run_masked_oracle(downscaled_config(_cfg(image_downscale=2)), binned_stream(base, 2), b0, b1)
     assert fe.drops['track'] >= 1 and fe.drops['stereo'] >= 50, fe.drops
     for mode in ('step', 'frames'):
         got = run_engine(cfg, [base], mode=mode)
@@ -137,7 +117,7 @@ def test_binning(base):
 def test_with_clahe(base, combs):
     """The masks do not change what CLAHE sees: against the masked oracle fed reference-equalised frames."""
     m0, m1, _ref = combs
-    ref, fe = mr.run_masked_oracle(_cfg(), base.equalised(), m0, m1)
+    ref, fe = mr.run_masked_oracle(_cfg(), base.map(cr.clahe), m0, m1)
     assert fe.drops['track'] >= 1 and fe.drops['stereo'] >= 100, fe.drops
     for mode in ('step', 'frames'):
         got = run_engine(_cfg(use_clahe=True, cam0_mask=m0, cam1_mask=m1), [base], mode=mode)
@@ -147,26 +127,12 @@ def test_with_clahe(base, combs):
 def test_with_ransac_every_published_point_lies_on_valid_pixels(base, combs):
     """No oracle combines the masks with the outlier rejection, so the property: on every frame every point of read_grid lies on a valid
     pixel of its camera's mask, and at least one frame publishes fewer features than the run without masks."""
-    from uav_airvision_amd.frontend import FrontendEngine
     m0, m1, _ref = combs
 
     def run(cfg):
-        eng = FrontendEngine(cfg, n_streams=1)
-        it = iter(base.imu)
-        pend = next(it, None)
-        out = []
-        for k in range(base.n_frames):
-            m = base.frame(k)
-            while pend is not None and pend.timestamp <= m.timestamp:
-                eng.push_imu(0, pend.timestamp, pend.angular_velocity)
-                pend = next(it, None)
-            eng.step_host(m.cam0_image, m.cam1_image, [m.timestamp])
-            (ids, _uv), = eng.read_features()
-            g = eng.read_grid(0)
-            assert len(g['ids']) == len(ids) and eng.read_counters(0)['overflow'] == 0
-            out.append((len(ids), g['cam0'], g['cam1'], eng.read_ransac_counts(0)))
-        eng.close()
-        return out
+        got = run_engine(cfg, [base], mode='host', read=lambda eng, i: read_grid(eng, i) + read_ransac_counts(eng, i))[0]
+        assert all(len(g['ids']) == len(ids) and cnt['overflow'] == 0 for ids, _uv, cnt, g, _rc in got)
+        return [(len(ids), g['cam0'], g['cam1'], rc) for ids, _uv, _cnt, g, rc in got]
     masked, free = run(_cfg(use_ransac=True, cam0_mask=m0, cam1_mask=m1)), run(_cfg(use_ransac=True))
     assert any(r[3]['after_ransac'] > 0 for r in masked[1:])                   # the stage ran
     for k, (n, p0, p1, _rc) in enumerate(masked):
@@ -187,7 +153,7 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch(base, combs):
     cfg = _cfg(cam0_mask=m0, cam1_mask=m1)
     tex = make_texture(0xA1B0 + 3)
     # the other 61 entries replay three other streams (rendering 61 would take minutes): what matters is that they are not the probe
-    pool = [Cached(SyntheticStream(cfg, seed=100 + i, n_frames=nf, motion_scale=1.0 + 0.4 * i, texture=tex, tex_offset=(37.0 * i, 11.0 * i)), equalise=False)
+    pool = [Frames.cached(SyntheticStream(cfg, seed=100 + i, n_frames=nf, motion_scale=1.0 + 0.4 * i, texture=tex, tex_offset=(37.0 * i, 11.0 * i)))
             for i in range(3)]
     batch = [pool[i % 3] for i in range(61)]
     for pos in (0, 17, 63):
@@ -202,16 +168,12 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch(base, combs):
 
 def test_a_width_that_is_no_multiple_of_four():
     """374 x 240: the detector reads the mask byte by byte instead of a dword per four pixels."""
-    from uav_airvision_amd.config import ConfigEuRoC
-    from uav_airvision_amd.synth import SyntheticStream, scaled_config
+    from uav_airvision_amd.synth import SyntheticStream
     w, h = 374, 240
 
     def cfg(**kw):
-        c = scaled_config(ConfigEuRoC(), w, h)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
-    st = Cached(SyntheticStream(cfg(), seed=13, n_frames=5, motion_scale=3.0), equalise=False)
+        return scaled_cfg(w, h, **kw)
+    st = Frames.cached(SyntheticStream(cfg(), seed=13, n_frames=5, motion_scale=3.0))
     m0, m1 = mr.comb_mask(w, h, 48, 12, 0), mr.comb_mask(w, h, 48, 12, 24)
     ref, fe = mr.run_masked_oracle(cfg(), st, m0, m1)
     assert fe.drops['stereo'] >= 50 and all(len(r['ids']) >= 50 for r in ref), fe.drops

@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 
 import clahe_ref as cr
-from pixfmt_helpers import MODES, Encoded, make_cfg as _cfg, run_engine, run_oracle, same as _same
+from fe_harness import MODES, Frames, against_oracle, bare_cfg, make_cfg as _cfg, run_engine, run_oracle, same as _same
+from pixfmt_helpers import encoded_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -23,23 +24,15 @@ def encoded(base):
     """Per format: the raw stream and the oracle's output on its reference-converted frames (computed once, shared, never changed)."""
     out = {}
     for i, fmt in enumerate(('gray16', 'bgr8', 'rgba8')):
-        st = Encoded(base, fmt, NF, seed=40 + i)
+        st = encoded_stream(base, fmt, NF, seed=40 + i)
         out[fmt] = (st, run_oracle(_cfg(), st))
     return out
 
 
 def _against_oracle(fmt, mode, st, ref, **cfg_kw):
-    got, images = run_engine(_cfg(image_format=fmt, **cfg_kw), [st], mode=mode, images_of=0)
-    assert len(ref) == len(got[0]) == NF and all(len(r['ids']) > 40 for r in ref)      # (a guard against a vacuous comparison: the scene has features)
-    for k, (r, g, im) in enumerate(zip(ref, got[0], images)):
-        ids, uv, cnt = g
-        where = '%s %s frame %d' % (fmt, mode, k)
-        assert np.array_equal(im[0], st.frame(k).cam0_image) and np.array_equal(im[1], st.frame(k).cam1_image), where      # read_image: the converted frames
-        if k > 0:
-            assert [cnt['before_tracking'], cnt['after_tracking'], cnt['after_matching']] == \
-                   [r['nf'].get('before_tracking', 0), r['nf'].get('after_tracking', 0), r['nf'].get('after_matching', 0)], where
-        assert cnt['overflow'] == 0 and cnt['n_published'] == len(r['ids']) and np.array_equal(ids, r['ids']), where
-        assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
+    got, images = run_engine(_cfg(image_format=fmt, **cfg_kw), [st], mode=mode, raw=True, images_of=0)
+    assert len(ref) == NF
+    against_oracle(ref, got[0], '%s %s' % (fmt, mode), images, st, min_features=41)      # read_image: the converted frames; the scene has features
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -66,25 +59,24 @@ def test_the_raw_frames_are_not_trivially_grey(encoded, base):
 
 def test_grey_equivalence(base):
     """An RGB stream with R = G = B = g and a 16-bit stream g << 8 publish bit for bit what a gray8 engine publishes on g."""
-    from clahe_helpers import Cached, run_engine as run_gray
-    want = run_gray(_cfg(), [Cached(base, equalise=False)], n_frames=NF)[0]
+    want = run_engine(_cfg(), [Frames.cached(base)], n_frames=NF)[0]
     assert all(len(w[0]) > 40 for w in want)
     for fmt, mode in (('rgb8', 'step'), ('gray16', 'step'), ('rgb8', 'frames'), ('gray16', 'host')):
-        got = run_engine(_cfg(image_format=fmt), [Encoded(base, fmt, NF, exact=True)], mode=mode)[0]
+        got = run_engine(_cfg(image_format=fmt), [encoded_stream(base, fmt, NF, exact=True)], mode=mode, raw=True)[0]
         assert all(_same(a, b) for a, b in zip(want, got)), (fmt, mode)
 
 
 def test_gray16_with_clahe_in_the_host_path(base):
     """Conversion, then equalisation in place: against the oracle on clahe_ref.clahe(pixfmt_ref(...)); a shift other than 8 reaches the
     stage (12 significant bits: frames are g << 4 | noise4, shift 4)."""
-    st = Encoded(base, 'gray16', NF, seed=44, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
+    st = encoded_stream(base, 'gray16', NF, seed=44, post=lambda a: cr.clahe(a, 2.0, (8, 8)))
     _against_oracle('gray16', 'host', st, run_oracle(_cfg(), st), use_clahe=True)
-    st4 = Encoded(base, 'gray16', 3, seed=45)
+    st4 = encoded_stream(base, 'gray16', 3, seed=45)
     for k in range(3):                                   # re-scale the raw frames to 12 bits; the reference conversion uses shift 4
         t, r0, r1 = st4.raw[k]
         st4.raw[k] = (t, (r0 >> 4).astype(np.uint16), (r1 >> 4).astype(np.uint16))
     import pixfmt_ref as pr
-    got, images = run_engine(_cfg(image_format='gray16', gray16_shift=4), [st4], mode='step', images_of=0)
+    got, images = run_engine(_cfg(image_format='gray16', gray16_shift=4), [st4], mode='step', raw=True, images_of=0)
     for k in range(3):
         assert np.array_equal(images[k][0], pr.to_gray8(st4.raw[k][1], 'gray16', 4)) and np.array_equal(images[k][0], base.frame(k).cam0_image), k
 
@@ -95,13 +87,13 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _cfg(image_format='bgr8')
     nf = NF
-    batch = [Encoded(SyntheticStream(cfg, seed=200 + i, n_frames=nf, motion_scale=1.0 + 0.3 * i), 'bgr8', nf, seed=50 + i) for i in range(3)]
+    batch = [encoded_stream(SyntheticStream(cfg, seed=200 + i, n_frames=nf, motion_scale=1.0 + 0.3 * i), 'bgr8', nf, seed=50 + i) for i in range(3)]
     assert not np.array_equal(batch[0].raw[0][1], batch[1].raw[0][1])
-    alone = [run_engine(cfg, [b])[0] for b in batch]
+    alone = [run_engine(cfg, [b], raw=True)[0] for b in batch]
     assert all(len(a[0]) > 20 for al in alone for a in al)
     assert not all(_same(a, b) for a, b in zip(alone[0], alone[1]))
     for mode in ('step', 'frames'):
-        got = run_engine(cfg, batch, mode=mode)
+        got = run_engine(cfg, batch, mode=mode, raw=True)
         for pos in range(3):
             assert all(_same(a, b) for a, b in zip(alone[pos], got[pos])), (mode, pos)
 
@@ -125,24 +117,17 @@ def test_an_entry_named_twice_takes_the_later_frame(encoded):
 def test_off_is_off(base):
     """image_format = 'gray8' equals a bare config without the two attributes, with the same timing spans per step, and read_image is
     still refused; a format other than gray8 adds no span."""
-    from clahe_helpers import Cached, run_engine as run_gray
     from uav_airvision_amd import _native as N
     from uav_airvision_amd.frontend import FrontendEngine
-
-    class Bare(object):
-        pass
-    bare = Bare()
-    for k, v in vars(_cfg()).items():
-        if k not in ('image_format', 'gray16_shift'):
-            setattr(bare, k, v)
+    bare = bare_cfg(lambda k: k in ('image_format', 'gray16_shift'))
     assert not hasattr(bare, 'image_format') and not hasattr(bare, 'gray16_shift')
-    st = Cached(base, equalise=False)
-    off, sp_off = run_gray(_cfg(image_format='gray8'), [st], n_frames=NF, timing=True)
-    none, sp_none = run_gray(bare, [st], n_frames=NF, timing=True)
+    st = Frames.cached(base)
+    off, sp_off = run_engine(_cfg(image_format='gray8'), [st], n_frames=NF, timing=True)
+    none, sp_none = run_engine(bare, [st], n_frames=NF, timing=True)
     assert all(_same(a, b) for a, b in zip(off[0], none[0])) and sp_off == sp_none
     for mode in ('step', 'host'):
-        on, sp_on = run_engine(_cfg(image_format='rgb8'), [Encoded(base, 'rgb8', NF, exact=True)], mode=mode, timing=True)
-        ref_sp = sp_off if mode == 'step' else run_gray(_cfg(), [st], mode='host', n_frames=NF, timing=True)[1]
+        on, sp_on = run_engine(_cfg(image_format='rgb8'), [encoded_stream(base, 'rgb8', NF, exact=True)], mode=mode, raw=True, timing=True)
+        ref_sp = sp_off if mode == 'step' else run_engine(_cfg(), [st], mode='host', n_frames=NF, timing=True)[1]
         assert sp_on == ref_sp and all(s['pyramid'] == 1 for s in sp_on), mode
     eng = FrontendEngine(_cfg(image_format='gray8'), n_streams=1)
     m = base.frame(0)

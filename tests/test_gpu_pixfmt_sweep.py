@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from fe_harness import Frames
+
 pytestmark = pytest.mark.gpu
 
 N_FRAMES = 40                     # 2 s at 20 Hz: the first second initialises the filter, the second publishes poses
@@ -19,8 +21,7 @@ def sequences(tmp_path_factory):
     from uav_airvision_amd.synth import SyntheticStream
     root = tmp_path_factory.mktemp('pixfmt_sweep')
     st = SyntheticStream(ConfigEuRoC(), seed=77, n_frames=N_FRAMES, motion_scale=1.5, t0=1403636580.0, rest=1.0)
-    frames = [st.frame(k) for k in range(N_FRAMES)]
-    st.frame = lambda k: frames[k]                        # rendered once, written three times
+    st.frame = Frames.cached(st).frame                    # rendered once, written three times
     return {fmt: write_euroc_layout(str(root / ('SEQ_' + fmt)), st, compress_level=1, pixel_format=fmt) for fmt in ('gray8', 'gray16', 'rgb8')}
 
 

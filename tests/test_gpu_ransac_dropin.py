@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_gpu_ransac_engine import STREAM, Cached, _cfg, run_engine
+from fe_harness import Frames, make_cfg as _cfg, read_ransac_counts, run_engine
+from ransac_helpers import STREAM
 
 pytestmark = pytest.mark.gpu
 
@@ -78,8 +79,8 @@ def _stage_pipeline(cfg, stream):
 def test_stage_tracker_with_ransac_gives_the_engines_ids_and_counts():
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _cfg(use_ransac=True)
-    st = Cached(SyntheticStream(cfg, **dict(STREAM, n_frames=10)))
-    eng = run_engine(cfg, [st])[0]
+    st = Frames.cached(SyntheticStream(cfg, **dict(STREAM, n_frames=10)))
+    eng = run_engine(cfg, [st], read=read_ransac_counts)[0]
     got = _stage_pipeline(cfg, st)
     assert any(g[2] < g[1] for g in got)
     for k, ((ids, am, ar), (ids_e, _uv, cnt, rc)) in enumerate(zip(got, eng)):
@@ -103,7 +104,7 @@ def test_front_end_with_ransac_feeds_the_filter():
     from uav_airvision_amd.frontend import FrontendEngine
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.synth import SyntheticStream
-    st = Cached(SyntheticStream(_cfg(), **dict(STREAM, n_frames=60)))
+    st = Frames.cached(SyntheticStream(_cfg(), **dict(STREAM, n_frames=60)))
     res = {}
     for on in (True, False):
         cfg = _cfg(use_ransac=on)
@@ -128,6 +129,6 @@ def test_front_end_with_ransac_feeds_the_filter():
         eng.close(); flt.close()
         assert len(traj) >= 40
         traj = np.array(traj)
-        gt = np.array([[t] + list(st.base.position(t)) for t in traj[:, 0]])
+        gt = np.array([[t] + list(st.position(t)) for t in traj[:, 0]])
         res[on] = ate(traj, gt)['rmse']
     print('ATE rmse over %d frames: RANSAC on %.4f m, off %.4f m' % (st.n_frames, res[True], res[False]))

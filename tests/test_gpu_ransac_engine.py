@@ -4,160 +4,18 @@ import numpy as np
 import pytest
 
 import ransac_ref as rr
-from oracle.frontend import (Feat, OracleFrontend, cell_of, cvops, grid_size, integrate_imu, predict_feature_tracking,
-                             tracking_homography)
+from fe_harness import Frames, against_oracle, bare_cfg, make_cfg as _cfg, read_ransac_counts, run_engine, same as _same
+from ransac_helpers import REGION, STREAM, check_ransac_counts, run_ransac_oracle
 
 pytestmark = pytest.mark.gpu
-
-REGION = (250, 150, 500, 330)          # the independently moving rectangle of the synthetic stream (x0, y0, x1, y1)
-STREAM = dict(seed=13, n_frames=26, motion_scale=3.0, moving_region=REGION, moving_amplitude=0.3)
-
-
-class RansacOracle(OracleFrontend):
-    """OracleFrontend with the reference RANSAC between the stereo match and the re-binning of FeatureTracker.track_features
-    (feature_tracker.py:135-136 is the empty step), cam1_R_p_c kept, the stream's own frame number counted."""
-
-    def __init__(self, config):
-        OracleFrontend.__init__(self, config)
-        self.frame_no = 0
-        self.ransac_counts = [0, 0, 0, 0]
-        self.margin = np.inf
-        self.rejected = []                 # cam0 points (current frame) of the features the stage rejected in the last frame
-
-    def stereo_callback(self, stereo_msg):
-        self.ransac_counts, self.margin, self.rejected = [0, 0, 0, 0], np.inf, []
-        msg = OracleFrontend.stereo_callback(self, stereo_msg)
-        self.frame_no += 1
-        return msg
-
-    def _track(self, prev_img0, img0, img1, t_prev, t_curr):
-        cfg = self.config
-        gh, gw = grid_size(img0, cfg)
-        R0, R1, self.imu_buffer = integrate_imu(self.imu_buffer, t_prev, t_curr, self.geom)
-        prev = [f for cell in self.prev_features for f in cell]
-        self.num_features['before_tracking'] = len(prev)
-        if not prev:
-            return
-        prev_pts = np.array([f.cam0_point for f in prev], dtype=np.float32)
-        H = tracking_homography(R0, cfg.cam0_intrinsics)
-        pred = predict_feature_tracking(prev_pts, H)
-        curr_pts, mask, _ = cvops.calc_optical_flow_pyr_lk(prev_img0, img0, prev_pts, pred, cache_pyramids=self.cache_pyramids, **cfg.lk_params)
-        h, w = img0.shape[:2]
-        keep = [i for i, p in enumerate(curr_pts) if mask[i] and not (p[0] < 0 or p[0] > w - 1 or p[1] < 0 or p[1] > h - 1)]
-        self.num_features['after_tracking'] = len(keep)
-        tracked = [curr_pts[i] for i in keep]
-        cam1_pts, match, _ = self._stereo(img0, img1, tracked)
-        sel = [(k, i) for k, i in enumerate(keep) if match[k]]
-        self.num_features['after_matching'] = len(sel)
-        survive = np.ones(len(sel), bool)
-        if sel:
-            common = dict(inlier_error=cfg.ransac_threshold, success_probability=cfg.ransac_success_probability, seed=cfg.ransac_seed,
-                          frame=self.frame_no)
-            m0, i0 = rr.two_point_ransac(np.array([prev[i].cam0_point for _k, i in sel], np.float32), np.array([tracked[k] for k, _i in sel], np.float32),
-                                         R0, cfg.cam0_intrinsics, cfg.cam0_distortion_model, cfg.cam0_distortion_coeffs, camera=0, **common)
-            m1, i1 = rr.two_point_ransac(np.array([prev[i].cam1_point for _k, i in sel], np.float32), np.array([cam1_pts[k] for k, _i in sel], np.float32),
-                                         R1, cfg.cam1_intrinsics, cfg.cam1_distortion_model, cfg.cam1_distortion_coeffs, camera=1, **common)
-            survive = (m0 == 1) & (m1 == 1)
-            self.ransac_counts = [int(survive.sum()), i0['n_set'], i1['n_set'], i0['path'] | i1['path'] << 4]
-            self.margin = min(i0['margin'], i1['margin'])
-        for ok, (k, i) in zip(survive, sel):
-            if not ok:
-                self.rejected.append(tracked[k])
-                continue
-            f = Feat()
-            f.id = prev[i].id
-            f.lifetime = prev[i].lifetime + 1
-            f.cam0_point = tracked[k]
-            f.cam1_point = cam1_pts[k]
-            self.curr_features[cell_of(f.cam0_point, gh, gw, cfg)].append(f)
-        self.num_features['after_ransac'] = int(survive.sum())
-
-
-class Cached(object):
-    """A synthetic stream with its frames rendered once (several engine runs replay them)."""
-
-    def __init__(self, base):
-        self.base, self.imu, self.n_frames = base, base.imu, base.n_frames
-        self._frames = [base.frame(k) for k in range(base.n_frames)]
-        self.in_moving_region = base.in_moving_region
-
-    def frame(self, k):
-        return self._frames[k]
-
-
-def _cfg(**kw):
-    from uav_airvision_amd.config import ConfigEuRoC
-    cfg = ConfigEuRoC()
-    for k, v in kw.items():
-        setattr(cfg, k, v)
-    return cfg
-
-
-def run_oracle(cfg, stream):
-    from uav_airvision_amd.synth import replay
-    fe = RansacOracle(cfg)
-    out = []
-
-    def on_frame(m):
-        msg = fe.stereo_callback(m)
-        ids = np.array([f.id for f in msg.features], np.int64)
-        uv = np.array([[f.u0, f.v0, f.u1, f.v1] for f in msg.features], np.float64).reshape(-1, 4)
-        out.append(dict(ids=ids, uv=uv, nf=dict(fe.num_features), counts=list(fe.ransac_counts), margin=fe.margin, rejected=list(fe.rejected)))
-    replay(stream, [fe.imu_callback], on_frame)
-    return out
-
-
-def run_engine(cfg, streams, mode='step', persist=False, timing=False):
-    """mode: 'step' (device tensors), 'host' (step_host), 'frames' (frame store).  Returns per stream a list of
-    (ids, uv, counters, ransac_counts) and, with timing, the glue / total span counts of every step."""
-    import torch
-    from uav_airvision_amd.frontend import FrontendEngine
-    S = len(streams)
-    eng = FrontendEngine(cfg, n_streams=S, inputs_persist=persist)
-    if mode == 'frames':
-        eng.frames_reserve(2 * S)
-    if timing:
-        eng.enable_timing(64)
-    out = [[] for _ in streams]
-    spans = []
-    its = [iter(s.imu) for s in streams]
-    pend = [next(it, None) for it in its]
-    for k in range(streams[0].n_frames):
-        msgs = [s.frame(k) for s in streams]
-        for i, m in enumerate(msgs):
-            while pend[i] is not None and pend[i].timestamp <= m.timestamp:
-                eng.push_imu(i, pend[i].timestamp, pend[i].angular_velocity)
-                pend[i] = next(its[i], None)
-        a0, a1 = np.stack([m.cam0_image for m in msgs]), np.stack([m.cam1_image for m in msgs])
-        ts = [m.timestamp for m in msgs]
-        if mode == 'step':
-            eng.step(torch.from_numpy(a0).cuda(), torch.from_numpy(a1).cuda(), ts)
-        elif mode == 'host':
-            eng.step_host(a0, a1, ts)
-        else:
-            slots = np.arange(S, dtype=np.int32) + (k & 1) * S
-            eng.frames_upload(slots, a0, a1)
-            eng.step_frames(slots, ts)
-        feats = eng.read_features()
-        for i in range(S):
-            out[i].append((feats[i][0], feats[i][1], eng.read_counters(i), eng.read_ransac_counts(i)))
-        if timing:
-            t = eng.read_timing()
-            spans.append((t['glue'][1], sum(v[1] for v in t.values())))
-    eng.close()
-    return (out, spans) if timing else out
-
-
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint64), b[1].view(np.uint64)) and a[2] == b[2] and a[3] == b[3]
 
 
 @pytest.fixture(scope='module')
 def moving():
     from uav_airvision_amd.synth import SyntheticStream
     cfg = _cfg(use_ransac=True)
-    st = Cached(SyntheticStream(cfg, **STREAM))
-    return cfg, st, run_oracle(cfg, st)
+    st = Frames.cached(SyntheticStream(cfg, **STREAM))
+    return cfg, st, run_ransac_oracle(cfg, st)
 
 
 def test_engine_with_ransac_matches_the_oracle_on_a_stream_with_a_moving_region(moving):
@@ -179,17 +37,10 @@ def test_engine_with_ransac_matches_the_oracle_on_a_stream_with_a_moving_region(
     print('frames with rejections %d of %d, rejected %d, inside the moving region %d' % (len(rej_frames), n, len(rejected), inside))
     assert len(rejected) >= 20 and inside >= 0.8 * len(rejected), (inside, len(rejected))
     assert any((r['counts'][3] & 15) == rr.PATH_MODEL for r in ref)
-    for tag, kw in (('copy', dict(mode='step', persist=False)), ('in place', dict(mode='step', persist=True)), ('host', dict(mode='host')),
-                    ('frames', dict(mode='frames'))):
-        got = run_engine(cfg, [st], **kw)[0]
-        for k, (r, g) in enumerate(zip(ref, got)):
-            ids, uv, cnt, rc = g
-            where = '%s frame %d' % (tag, k)
-            if k > 0:
-                assert cnt['after_matching'] == r['nf'].get('after_matching', 0), where
-            assert [rc['after_ransac'], rc['cam0_set'], rc['cam1_set'], rc['path']] == r['counts'], (where, rc, r['counts'])
-            assert cnt['overflow'] == 0 and np.array_equal(ids, r['ids']), where
-            assert np.array_equal(uv.view(np.uint64), r['uv'].view(np.uint64)), where
+    for tag, mode in (('copy', 'step'), ('in place', 'persist'), ('host', 'host'), ('frames', 'frames')):
+        got = run_engine(cfg, [st], mode=mode, read=read_ransac_counts)[0]
+        against_oracle(ref, got, tag)
+        check_ransac_counts(ref, got, tag)
 
 
 def test_off_is_off(moving):
@@ -197,22 +48,17 @@ def test_off_is_off(moving):
     the switch on shows exactly one span more, in the glue class; and it changes what is published."""
     _cfg_on, st, _ref = moving
     from uav_airvision_amd.synth import SyntheticStream
-    short = Cached(SyntheticStream(_cfg(), **dict(STREAM, n_frames=8)))
+    short = Frames.cached(SyntheticStream(_cfg(), **dict(STREAM, n_frames=8)))
 
-    class Bare(object):
-        pass
-    bare = Bare()
-    for k, v in vars(_cfg()).items():
-        if not k.startswith('ransac_') and k != 'use_ransac':
-            setattr(bare, k, v)
+    bare = bare_cfg(lambda k: k.startswith('ransac_') or k == 'use_ransac')
     assert not hasattr(bare, 'use_ransac')
-    off, sp_off = run_engine(_cfg(use_ransac=False), [short], timing=True)
-    none, sp_none = run_engine(bare, [short], timing=True)
-    on, sp_on = run_engine(_cfg(use_ransac=True), [short], timing=True)
+    off, sp_off = run_engine(_cfg(use_ransac=False), [short], timing=True, read=read_ransac_counts)
+    none, sp_none = run_engine(bare, [short], timing=True, read=read_ransac_counts)
+    on, sp_on = run_engine(_cfg(use_ransac=True), [short], timing=True, read=read_ransac_counts)
     assert all(_same(a, b) for a, b in zip(off[0], none[0]))
     assert sp_off == sp_none
     assert all(g[3] == dict(after_ransac=0, cam0_set=0, cam1_set=0, path=0) for g in off[0])
-    assert [(g + 1, t + 1) for g, t in sp_off] == sp_on, (sp_off, sp_on)
+    assert [(s['glue'] + 1, sum(s.values()) + 1) for s in sp_off] == [(s['glue'], sum(s.values())) for s in sp_on], (sp_off, sp_on)
     assert any(not np.array_equal(a[0], b[0]) for a, b in zip(off[0], on[0]))
 
 
@@ -222,18 +68,18 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
     cfg = _cfg(use_ransac=True)
     nf = 5
     tex = make_texture(0xA1B0 + 3)
-    probe = Cached(SyntheticStream(cfg, **dict(STREAM, n_frames=nf)))
-    alone = run_engine(cfg, [probe])[0]
+    probe = Frames.cached(SyntheticStream(cfg, **dict(STREAM, n_frames=nf)))
+    alone = run_engine(cfg, [probe], read=read_ransac_counts)[0]
     assert any(g[3]['after_ransac'] < g[2]['after_matching'] for g in alone)
     # the other 61 entries replay six other streams (rendering 61 would take minutes): what matters is that they are not the probe
-    pool = [Cached(SyntheticStream(cfg, seed=100 + i, n_frames=nf, motion_scale=1.0 + 0.4 * i, texture=tex, tex_offset=(37.0 * i, 11.0 * i),
+    pool = [Frames.cached(SyntheticStream(cfg, seed=100 + i, n_frames=nf, motion_scale=1.0 + 0.4 * i, texture=tex, tex_offset=(37.0 * i, 11.0 * i),
                                    moving_region=REGION if i % 2 else None)) for i in range(6)]
     others = [pool[i % 6] for i in range(61)]
     batch = list(others)
     for pos in (0, 17, 63):
         batch.insert(pos, probe)
     assert len(batch) == 64 and all(batch[p] is probe for p in (0, 17, 63))
-    got = run_engine(cfg, batch)
+    got = run_engine(cfg, batch, read=read_ransac_counts)
     for pos in (0, 17, 63):
         assert all(_same(a, b) for a, b in zip(alone, got[pos])), pos
     assert not all(_same(a, b) for a, b in zip(alone, got[1]))

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import mask_ref as mr
-from oracle.frontend import OracleFrontend
+from fe_harness import Frames, run_oracle
 
 W, H = 752, 480
 STREAM = dict(seed=13, n_frames=10, motion_scale=3.0)
@@ -54,11 +54,8 @@ def stream():
     from uav_airvision_amd.config import ConfigEuRoC
     from uav_airvision_amd.synth import SyntheticStream
     cfg = ConfigEuRoC()
-    st = SyntheticStream(cfg, **STREAM)
-    frames = [st.frame(k) for k in range(st.n_frames)]
-    st.frame = lambda k: frames[k]
-    plain, _fe = mr.run_masked_oracle(cfg, st, oracle=OracleFrontend)
-    return cfg, st, plain
+    st = Frames.cached(SyntheticStream(cfg, **STREAM))
+    return cfg, st, run_oracle(cfg, st)
 
 
 def _same(a, b):
