@@ -224,7 +224,14 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * av_frontend_enable_timing, inside the input stage's span.  The caller's images are never written.  The published message is that
  * of the unmodified pipeline run on the converted frames.  With AV_PIX_GRAY8 nothing is launched and nothing more is allocated.
  * Both cameras have one size and one format.  av_frontend_create refuses an unknown format or a shift outside 0 .. 8, AV_E_INVALID,
- * before a device is touched. */
+ * before a device is touched.
+ * Packed 10 / 12-bit transports (AV_PIX_GRAY10P .. AV_PIX_BAYER_GBRG12_CSI2): a frame is av_pixfmt_frame_bytes(pixel_format, width,
+ * height) = width * height * d / 8 bytes, and that -- not a number of bytes per pixel -- is what img_stride must at least be and what
+ * the staging slots, the pinned ring and the device staging carry: 1.25 or 1.5 bytes per pixel over the host-to-device link instead
+ * of 2.  A packed mosaic is converted in two passes through an engine-owned 8-bit mosaic scratch ([2][n_streams][width * height]; the
+ * frame store has one of its own, sized by the largest upload), allocated only when such a format is configured.  With binning the
+ * chain is raw -> mosaic scratch -> full-size grey scratch -> level 0.  av_frontend_create refuses a width that is not whole groups
+ * (4 samples at 10 bits, 2 at 12), AV_E_INVALID with the format's name in the text, before a device is touched. */
 
 /* Binning: av_frontend_config.image_downscale = f = 2 or 4 (av_downscale below has the arithmetic).  width / height stay the size of
  * the frames handed to the entry points and the intrinsics stay those of the full-size camera; the engine works on the binned image
@@ -458,17 +465,49 @@ int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h
  *   4. grey      (9798 R4 + 19235 G4 + 3735 B4 + 65536) >> 17 in integer arithmetic (at most 32768 * 1020 + 65536: it fits 32 bits).
  *                The coefficients are the colour formats' own: a uniform mosaic of value g gives g exactly, nothing exceeds 255.
  * Example: the RGGB image [[10, 200], [30, 90]] gives [[81, 131], [31, 81]].
- * Not covered for mosaics: edge-aware demosaicing, packed 10 / 12-bit transports (Mono12p, RAW12), white balance beyond the fixed
- * luma weights, two cameras of different patterns.
+ * Not covered for mosaics: edge-aware demosaicing, white balance beyond the fixed luma weights, two cameras of different patterns.
+ *
+ * Packed 10 / 12-bit transports: how USB3 Vision / GigE cameras (PFNC Mono10p, Mono12p, BayerRG12p ..) and MIPI CSI-2 sensors (RAW10,
+ * RAW12) deliver 10- and 12-bit data.  A packed frame is a pure TRANSPORT of a 16-bit frame: w x h samples of depth d = 10 or 12 bits,
+ * rows tightly packed, no padding at line ends.  w % 4 == 0 is required for d = 10 and w % 2 == 0 for d = 12, so an image is a run of
+ * whole groups and is w * h * d / 8 bytes long (av_pixfmt_frame_bytes).  tests/packed_ref.py states all of this in NumPy.
+ *   packing                                     group        bytes of a group (p0, p1, .. are its samples, bit ranges inclusive)
+ *   10p      PFNC Mono10p: a little-endian      4 px = 5 B   p0[7:0],  p1[5:0]<<2 | p0[9:8],  p2[3:0]<<4 | p1[9:6],  p3[1:0]<<6 | p2[9:4],  p3[9:2]
+ *            bit stream, LSB first
+ *   12p      PFNC Mono12p                       2 px = 3 B   p0[7:0],  p1[3:0]<<4 | p0[11:8],  p1[11:4]
+ *   10_csi2  MIPI CSI-2 RAW10                   4 px = 5 B   p0[9:2],  p1[9:2],  p2[9:2],  p3[9:2],  p3[1:0]<<6 | p2[1:0]<<4 | p1[1:0]<<2 | p0[1:0]
+ *   12_csi2  MIPI CSI-2 RAW12                   2 px = 3 B   p0[11:4],  p1[11:4],  p1[3:0]<<4 | p0[3:0]
+ * Examples: the samples 0xABC, 0x123 are the bytes BC 3A 12 as 12p and AB 12 3C as 12_csi2; the samples 0x2A5, 0x13C, 0x3FF, 0x001 are
+ * A5 F2 F4 7F 00 as 10p and A9 4F FF 00 71 as 10_csi2.
+ *   value rule   for every sample v before anything else: s = min(255, (v << (16 - d)) >> shift) with shift = gray16_shift (0 .. 8), in
+ *                32-bit integers.  Unpacking left-justifies the sample to 16 bits and the GRAY16 rule applies unchanged, so the default
+ *                shift 8 gives the top eight bits of a 10- or 12-bit sample.  With shift 8 the examples give 171, 18 and 169, 79, 255, 0;
+ *                with shift 6 the 12-bit pair gives 255, 72.
+ *   grey         AV_PIX_GRAY10P .. AV_PIX_GRAY12_CSI2 stop there: s is the grey value.
+ *   mosaics      AV_PIX_BAYER_*10P .. AV_PIX_BAYER_*12_CSI2 continue with steps 2 - 4 of the Bayer definition above on the reduced
+ *                samples s: a packed mosaic equals the 8-bit mosaic of its s values.  The pattern is code & 3, in the order above.
+ *                Two passes: the reduced 8-bit mosaic goes to a scratch, then the 8-bit Bayer kernels run on it unchanged.
+ *   format                                      code
+ *   AV_PIX_GRAY10P / 12P / 10_CSI2 / 12_CSI2    32 / 33 / 34 / 35
+ *   AV_PIX_BAYER_{RGGB,BGGR,GRBG,GBRG}10P       40 .. 43        AV_PIX_BAYER_{..}12P       44 .. 47
+ *   AV_PIX_BAYER_{RGGB,BGGR,GRBG,GBRG}10_CSI2   48 .. 51        AV_PIX_BAYER_{..}12_CSI2   52 .. 55
+ * Frames of a packed format are BYTE arrays of h rows of w * d / 8 bytes.  No PNG flavour holds one: av_png_decode refuses these codes
+ * and av_png_probe never returns them.
+ * Not covered for packed transports: line padding or a row stride; GigE Vision's Mono12Packed / Mono10Packed (another bit order);
+ * 14-bit packings; widths that are not whole groups; two cameras of different formats; a fused unpack-and-demosaic kernel.
  *
  * av_to_gray8: n_img images of w x h pixels, image i at img_dev + i * img_stride_bytes (tightly packed rows), to tightly packed u8 at
  * out_dev + i * out_stride.  Images at 16-byte aligned addresses and strides (the strides count only when n_img > 1) go through as whole
  * vectors with the last w * h % 16 pixels byte by byte; a launch with any other address or stride goes byte by byte altogether.
  * A Bayer mosaic goes 16 columns per lane when w % 16 == 0 and the addresses and strides are aligned as above, one pixel per lane
- * otherwise.  shift is read for AV_PIX_GRAY16 and the 16-bit Bayer formats only but checked always.  AV_E_INVALID with text for an unknown format, a shift outside 0 .. 8,
+ * otherwise.  A packed frame goes 32 (12-bit) or 64 (10-bit) samples per lane as whole vectors when aligned as above, with the ragged
+ * end of an image group by group in one lane, and group by group altogether otherwise; img_stride_bytes is at least
+ * av_pixfmt_frame_bytes, and a width that is not whole groups is AV_E_INVALID with the format's name in the text.  A packed mosaic
+ * allocates its 8-bit mosaic scratch (n_img frames of w * h bytes, 16-byte aligned strides) for the call and waits for the stream before
+ * freeing it: for these formats alone the operator blocks the host and cannot be captured into a graph (the engine owns its scratch and does neither).  shift is read for AV_PIX_GRAY16, the 16-bit Bayer formats and the packed formats only but checked always.  AV_E_INVALID with text for an unknown format, a shift outside 0 .. 8,
  * w * h > AV_MAX_IMAGE_PIXELS, strides smaller than an image, and out_dev overlapping the input.  The one exception: AV_PIX_GRAY8 with
  * out_dev == img_dev and equal strides is the identity in place and does nothing (any other AV_PIX_GRAY8 call is a strided copy, and
- * an overlap is refused like for the other formats).  Codes 6 .. 15 and 24 upwards are unknown formats.
+ * an overlap is refused like for the other formats).  Codes 6 .. 15, 24 .. 31, 36 .. 39 and 56 upwards are unknown formats.
  * ------------------------------------------------------------------------------------------- */
 #define AV_PIX_GRAY8  0
 #define AV_PIX_GRAY16 1
@@ -484,8 +523,31 @@ int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h
 #define AV_PIX_BAYER_BGGR16 21
 #define AV_PIX_BAYER_GRBG16 22
 #define AV_PIX_BAYER_GBRG16 23
+#define AV_PIX_GRAY10P      32
+#define AV_PIX_GRAY12P      33
+#define AV_PIX_GRAY10_CSI2  34
+#define AV_PIX_GRAY12_CSI2  35
+#define AV_PIX_BAYER_RGGB10P     40
+#define AV_PIX_BAYER_BGGR10P     41
+#define AV_PIX_BAYER_GRBG10P     42
+#define AV_PIX_BAYER_GBRG10P     43
+#define AV_PIX_BAYER_RGGB12P     44
+#define AV_PIX_BAYER_BGGR12P     45
+#define AV_PIX_BAYER_GRBG12P     46
+#define AV_PIX_BAYER_GBRG12P     47
+#define AV_PIX_BAYER_RGGB10_CSI2 48
+#define AV_PIX_BAYER_BGGR10_CSI2 49
+#define AV_PIX_BAYER_GRBG10_CSI2 50
+#define AV_PIX_BAYER_GBRG10_CSI2 51
+#define AV_PIX_BAYER_RGGB12_CSI2 52
+#define AV_PIX_BAYER_BGGR12_CSI2 53
+#define AV_PIX_BAYER_GRBG12_CSI2 54
+#define AV_PIX_BAYER_GBRG12_CSI2 55
 int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_img, int w, int h, int pixel_format, int shift,
                 uint8_t* out_dev, int64_t out_stride, void* stream);
+/* Bytes of one tightly packed w x h frame of a pixel format: w * h * bytes per pixel, or w * h * d / 8 for a packed transport.  0 for an
+ * unknown format, for w or h below 1, and for a packed width that is not whole groups.  Host only. */
+int64_t av_pixfmt_frame_bytes(int pixel_format, int w, int h);
 
 /* ---------------------------------------------------------------------------------------------
  * Binning of 8-bit grey frames by f = 2 or 4.  No counterpart in the reference (other VIO stacks run their front-end on a reduced

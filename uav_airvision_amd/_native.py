@@ -24,6 +24,8 @@ AV_CLAHE_MAX_TILES = 16
 AV_PIX_GRAY8, AV_PIX_GRAY16, AV_PIX_RGB8, AV_PIX_BGR8, AV_PIX_RGBA8, AV_PIX_BGRA8 = 0, 1, 2, 3, 4, 5
 AV_PIX_BAYER_RGGB8, AV_PIX_BAYER_BGGR8, AV_PIX_BAYER_GRBG8, AV_PIX_BAYER_GBRG8 = 16, 17, 18, 19
 AV_PIX_BAYER_RGGB16, AV_PIX_BAYER_BGGR16, AV_PIX_BAYER_GRBG16, AV_PIX_BAYER_GBRG16 = 20, 21, 22, 23
+AV_PIX_GRAY10P, AV_PIX_GRAY12P, AV_PIX_GRAY10_CSI2, AV_PIX_GRAY12_CSI2 = 32, 33, 34, 35
+AV_PIX_BAYER_RGGB10P, AV_PIX_BAYER_RGGB12P, AV_PIX_BAYER_RGGB10_CSI2, AV_PIX_BAYER_RGGB12_CSI2 = 40, 44, 48, 52      # + pattern (rggb, bggr, grbg, gbrg)
 AV_RANSAC_MAX_PAIRS = 1920
 AV_RANSAC_MAX_HYPOTHESES = 64
 AV_RANSAC_PATH_FEW, AV_RANSAC_PATH_STILL, AV_RANSAC_PATH_MODEL, AV_RANSAC_PATH_NONE = 1, 2, 4, 8
@@ -33,29 +35,76 @@ PIXEL_FORMATS = {'gray8': 0, 'gray16': 1, 'rgb8': 2, 'bgr8': 3, 'rgba8': 4, 'bgr
                  # Bayer mosaics, named by the colours of the top-left 2 x 2 block in reading order (not OpenCV's BayerBG .. names)
                  'bayer_rggb8': 16, 'bayer_bggr8': 17, 'bayer_grbg8': 18, 'bayer_gbrg8': 19,
                  'bayer_rggb16': 20, 'bayer_bggr16': 21, 'bayer_grbg16': 22, 'bayer_gbrg16': 23}
-PIXEL_FORMAT_NAMES = {v: k for k, v in PIXEL_FORMATS.items()}
+BAYER_PATTERNS = ('rggb', 'bggr', 'grbg', 'gbrg')             # pattern of code c: BAYER_PATTERNS[(c - 16) & 3] = BAYER_PATTERNS[c & 3]
+# Packed 10 / 12-bit transports (PFNC Mono10p / Mono12p, MIPI CSI-2 RAW10 / RAW12): a table of their own, because a frame of one is a
+# byte array with no whole number of bytes per pixel -- PIXEL_FORMATS and PIXEL_BYTES stay the formats that have one array element per
+# sample.  pixel_format_code and PIXEL_FORMAT_NAMES know both tables; frame_bytes sizes a frame of either.
+PACKINGS = ('10p', '12p', '10_csi2', '12_csi2')               # grey: 32 + k; mosaics: 40 + 4 k + pattern
+PACKED_FORMATS = dict([('gray' + k, 32 + i) for i, k in enumerate(PACKINGS)] +
+                      [('bayer_%s%s' % (p, k), 40 + 4 * i + j) for i, k in enumerate(PACKINGS) for j, p in enumerate(BAYER_PATTERNS)])
+PIXEL_FORMAT_NAMES = {v: k for k, v in list(PIXEL_FORMATS.items()) + list(PACKED_FORMATS.items())}
 PIXEL_BYTES = {0: 1, 1: 2, 2: 3, 3: 3, 4: 4, 5: 4, 16: 1, 17: 1, 18: 1, 19: 1, 20: 2, 21: 2, 22: 2, 23: 2}
-BAYER_PATTERNS = ('rggb', 'bggr', 'grbg', 'gbrg')             # pattern of code c: BAYER_PATTERNS[(c - 16) & 3]
+
+
+def is_packed(fmt):
+    """An AV_PIX_* code names a packed 10 / 12-bit transport (grey or mosaic): its frames are uint8 [n, h, w * d / 8]."""
+    return AV_PIX_GRAY10P <= fmt <= AV_PIX_GRAY12_CSI2 or AV_PIX_BAYER_RGGB10P <= fmt <= AV_PIX_BAYER_RGGB12_CSI2 + 3
+
+
+def packed_depth(fmt):
+    """Bits per sample of a packed format, 10 or 12; 0 for any other code."""
+    if not is_packed(fmt):
+        return 0
+    return 12 if ((fmt - 32) if fmt < 40 else (fmt - 40) >> 2) & 1 else 10
+
+
+def packing(fmt):
+    """'10p' | '12p' | '10_csi2' | '12_csi2' of a packed format."""
+    if not is_packed(fmt):
+        raise ValueError('%r is no packed format' % (fmt,))
+    return PACKINGS[(fmt - 32) if fmt < 40 else (fmt - 40) >> 2]
+
+
+def packed_group(fmt):
+    """(samples, bytes) of one group of a packed format: (4, 5) at 10 bits, (2, 3) at 12."""
+    return (4, 5) if packed_depth(fmt) == 10 else (2, 3)
+
+
+def frame_bytes(fmt, w, h):
+    """Bytes of one tightly packed w x h frame of an AV_PIX_* code (av_pixfmt_frame_bytes): w * h * bytes per pixel, w * h * d / 8 for
+    a packed format; 0 for an unknown code and for a packed width that is not whole groups (4 samples at 10 bits, 2 at 12)."""
+    return int(lib().av_pixfmt_frame_bytes(int(fmt), int(w), int(h)))
+
+
+def packed_row_bytes(fmt, width):
+    """Bytes of one row of a packed format; ValueError, naming the format, for a width that is not whole groups."""
+    gpx, gb = packed_group(fmt)
+    if not is_packed(fmt) or width <= 0 or width % gpx:
+        raise ValueError('%s: a row is whole groups of %d samples, width %d is not' % (PIXEL_FORMAT_NAMES.get(fmt, fmt), gpx, width))
+    return width // gpx * gb
 
 
 def is_bayer(fmt):
-    """An AV_PIX_* code names a Bayer mosaic."""
-    return AV_PIX_BAYER_RGGB8 <= fmt <= AV_PIX_BAYER_GBRG16
+    """An AV_PIX_* code names a Bayer mosaic, packed or not."""
+    return AV_PIX_BAYER_RGGB8 <= fmt <= AV_PIX_BAYER_GBRG16 or AV_PIX_BAYER_RGGB10P <= fmt <= AV_PIX_BAYER_RGGB12_CSI2 + 3
 
 
 def is_16bit(fmt):
-    """An AV_PIX_* code whose frames are uint16 arrays (gray16 and the 16-bit mosaics): the formats that read gray16_shift."""
+    """An AV_PIX_* code whose frames are uint16 arrays (gray16 and the 16-bit mosaics).  The packed formats read gray16_shift too, but
+    their frames are uint8 arrays: is_packed."""
     return fmt == AV_PIX_GRAY16 or AV_PIX_BAYER_RGGB16 <= fmt <= AV_PIX_BAYER_GBRG16
 
 
 def pixel_format_code(name):
-    """config.image_format ('gray8', 'gray16', 'rgb8', 'bgr8', 'rgba8', 'bgra8', 'bayer_{rggb,bggr,grbg,gbrg}{8,16}') or an AV_PIX_* code
-    -> AV_PIX_*; ValueError otherwise."""
+    """config.image_format ('gray8', 'gray16', 'rgb8', 'bgr8', 'rgba8', 'bgra8', 'bayer_{rggb,bggr,grbg,gbrg}{8,16}', 'gray{10p,12p,10_csi2,
+    12_csi2}', 'bayer_{rggb,bggr,grbg,gbrg}{10p,12p,10_csi2,12_csi2}') or an AV_PIX_* code -> AV_PIX_*; ValueError otherwise."""
     if isinstance(name, str) and name in PIXEL_FORMATS:
         return PIXEL_FORMATS[name]
+    if isinstance(name, str) and name in PACKED_FORMATS:
+        return PACKED_FORMATS[name]
     if isinstance(name, int) and not isinstance(name, bool) and name in PIXEL_FORMAT_NAMES:
         return name
-    raise ValueError('unknown image format %r (one of %s)' % (name, ', '.join(sorted(PIXEL_FORMATS, key=PIXEL_FORMATS.get))))
+    raise ValueError('unknown image format %r (one of %s)' % (name, ', '.join(PIXEL_FORMAT_NAMES[c] for c in sorted(PIXEL_FORMAT_NAMES))))
 
 
 def gray16_shift_value(shift):
@@ -175,6 +224,7 @@ SIGNATURES = {
     'av_png_decode': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P]),
     'av_png_probe': (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'av_to_gray8': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    'av_pixfmt_frame_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     'av_downscale': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     'av_downscale_vector_path': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     'av_quat_to_rotation': (C.c_int, [_P, _P]),

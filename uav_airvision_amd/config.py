@@ -55,6 +55,10 @@ class ConfigEuRoC(object):
         # colours of its top-left 2 x 2 block; gray16_shift applies to the 16-bit ones).  Anything but 'gray8' is converted to 8-bit grey on the GPU ahead of
         # everything else (av_to_gray8 in include/airvision.h).  gray16_shift: a 16-bit sample v becomes min(255, v >> shift); 8 = the
         # high byte, a sensor with 10 / 12 / 14 significant bits uses 2 / 4 / 6.
+        # Packed 10 / 12-bit transports, unpacked on the GPU: 'gray10p' | 'gray12p' (PFNC Mono10p / Mono12p) | 'gray10_csi2' | 'gray12_csi2'
+        # (MIPI CSI-2 RAW10 / RAW12) and 'bayer_{rggb,bggr,grbg,gbrg}{10p,12p,10_csi2,12_csi2}'.  Frames are uint8 [n, h, w * d / 8] (rows
+        # tightly packed, the width whole groups: a multiple of 4 at 10 bits, of 2 at 12).  A sample is left-justified to 16 bits before
+        # gray16_shift applies, so the default 8 gives its top eight bits.  No line stride, no Mono12Packed, no PNG or sweep source.
         self.image_format = 'gray8'
         self.gray16_shift = 8
         # 2 x 2 / 4 x 4 binning of every (grey) frame on the GPU ahead of CLAHE and the pyramids (no counterpart in the reference;

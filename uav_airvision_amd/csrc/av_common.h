@@ -278,9 +278,22 @@ int av_launch_clahe(const FrameSet& src, const FrameSet& dst, int n_groups, int 
 // pixfmt.hip: n_groups frames of one camera or of two, of pixel format fmt (AV_PIX_*, not GRAY8), to tightly packed 8-bit grey
 // (FrameSet; the list on the destination only, a negative entry skips the group).  Never in place.
 // av_pixfmt_bytes: bytes per pixel, 0 = unknown format; av_pixfmt_check: the limits of format and shift, with `who` in the text.
+// Packed 10 / 12-bit transports have no whole bytes per pixel (av_pixfmt_bytes gives 0 for them as for an unknown code): they are
+// known by av_pixfmt_packed_depth (10 / 12; 0 = not packed), av_pixfmt_packed_csi2 (MIPI CSI-2 byte order instead of PFNC "p") and sized
+// by av_pixfmt_frame_bytes (include/airvision.h), which is what sizes a frame of ANY format.  av_pixfmt_is_bayer: a mosaic, packed or
+// not (its pattern is fmt & 3).  av_pixfmt_name: config.image_format's name of a code (a thread-local text).  av_pixfmt_check_size: a
+// packed format's rows are whole groups, with `who` and the format's name in the text.
+// A packed mosaic is converted in two passes and needs `mosaic`, a scratch set of n_groups frames of w * h bytes per camera (no list).
 int av_pixfmt_bytes(int fmt);
+int av_pixfmt_packed_depth(int fmt);
+bool av_pixfmt_packed_csi2(int fmt);
+bool av_pixfmt_is_bayer(int fmt);
+const char* av_pixfmt_name(int fmt);
 int av_pixfmt_check(int fmt, int shift, const char* who);
-int av_launch_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st);
+int av_pixfmt_check_size(int fmt, int w, int h, const char* who);
+int av_launch_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st, const FrameSet* mosaic = nullptr);
+// packed.hip: the same for the packed transports, every sample reduced to 8 bits (a packed mosaic: its reduced 8-bit mosaic)
+int av_launch_unpack_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st);
 // bayer.hip: the same for the Bayer mosaic formats (AV_PIX_BAYER_*), w >= 2 and h >= 2; av_launch_to_gray8 hands them on
 int av_launch_bayer_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, int fmt, int shift, hipStream_t st);
 // downscale.hip: 2 x 2 / 4 x 4 binning (f = 2 or 4) of n_groups tightly packed W x H grey frames of one camera or of two into tightly

@@ -664,6 +664,7 @@ struct av_frontend {
         struct Up { uint8_t* pin = nullptr; int* idx_h = nullptr; int* idx_d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false;
                     uint8_t* raw_d = nullptr; };      // raw_d: grey_chain's `raw` when a stage writes the store; idx_h / idx_d then hold its `first` list behind the entries' own
         uint8_t* gray_d = nullptr; size_t gray_cap = 0;       // grey_chain's `gray_full` of ONE upload (uploads are serialised on the copy stream: one scratch serves the whole ring)
+        uint8_t* mosaic_d = nullptr; size_t mosaic_cap = 0;   // grey_chain's `mosaic` of one upload, likewise (packed mosaics only)
         Up up[4]; int up_next = 0;               // upload staging ring (pinned frames + the slot list of the upload's kernels)
         hipEvent_t uploaded = nullptr; bool any_upload = false;      // copy stream: the newest upload's kernels have finished
         hipEvent_t stepped = nullptr; bool any_step = false;          // step stream: the newest step has finished
@@ -688,8 +689,10 @@ struct av_frontend {
     // frames, 2: cam1), and the look-up tables of one launch [2 S][tiles][256]; the frame store keeps tables of its own (fs_lut)
     bool clahe = false; uint8_t* eq = nullptr; uint8_t* eq_lut = nullptr; uint8_t* fs_lut = nullptr;
     // pixel_format != AV_PIX_GRAY8: the frames are converted to 8-bit grey into the same level 0 (pixfmt.hip);
-    // own_l0 = some stage of grey_chain is on, so the engine owns level 0; bpp = bytes per pixel of the frames the entry points are handed
-    int fmt = AV_PIX_GRAY8, fmt_shift = 8, bpp = 1; bool own_l0 = false;
+    // own_l0 = some stage of grey_chain is on, so the engine owns level 0; frame_bytes = av_pixfmt_frame_bytes of the frames the entry
+    // points are handed (in_w x in_h of fmt).  mosaic: grey_chain's scratch of that name for the step paths, [2][S][in_w * in_h], with a
+    // packed mosaic format only (the frame store: FrameStore::mosaic_d)
+    int fmt = AV_PIX_GRAY8, fmt_shift = 8; int64_t frame_bytes = 0; bool own_l0 = false; uint8_t* mosaic = nullptr;
     // image_downscale = 2 / 4: the frames the entry points are handed are in_w x in_h and are binned into that level 0 (downscale.hip);
     // cfg then holds the PROCESSED size d.w x d.h and the calibration scaled to it.  The order of the stages: grey_chain.
     // gray_full: grey_chain's scratch of that name for the step paths, [2][S][in_w * in_h] (the frame store: FrameStore::gray_d)
@@ -794,11 +797,12 @@ uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot
 //   first      the list of the stage that first writes l0 (conversion or binning), or null: l0's list with -1 for every frame but
 //              the last of an entry named twice
 //   gray_full  the caller's full-size grey scratch, between conversion and binning when both are on
+//   mosaic     the caller's 8-bit mosaic scratch, between the two passes of a packed mosaic's conversion (n frames per camera, no list)
 //   lut        the look-up tables of one equalisation
 // *level0 = the set the pyramid launch reads: l0 if any stage ran (fe->own_l0: the engine then owns level 0, which outlives the call
 // whatever the caller's frames do), else raw.
-int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, const int* first, const FrameSet& gray_full, uint8_t* lut,
-               hipStream_t st, FrameSet* level0)
+int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, const int* first, const FrameSet& gray_full, const FrameSet& mosaic,
+               uint8_t* lut, hipStream_t st, FrameSet* level0)
 {
     const av_frontend_config& c = fe->cfg;
     const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
@@ -807,7 +811,7 @@ int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, 
     int rc;
     if (conv) {
         const FrameSet& to = bin ? gray_full : l0_first;
-        if ((rc = av_launch_to_gray8(at, to, n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st))) return rc;
+        if ((rc = av_launch_to_gray8(at, to, n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st, &mosaic))) return rc;
         at = to;
     }
     if (bin && (rc = av_launch_downscale(at, l0_first, n, fe->in_w, fe->in_h, fe->ds, st))) return rc;
@@ -830,8 +834,9 @@ int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64
     Span sp(fe, 0, st);
     const FrameSet l0 = fe->own_l0 ? FrameSet{{eq_slot(fe, cur), eq_slot(fe, 2)}, hw, nullptr} : FrameSet{};
     const FrameSet gray = fe->gray_full ? FrameSet{{fe->gray_full, fe->gray_full + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
+    const FrameSet mosaic = fe->mosaic ? FrameSet{{fe->mosaic, fe->mosaic + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
     FrameSet level0;
-    int rc = grey_chain(fe, av_frames(img0, img1, img_stride), d.S, l0, nullptr, gray, fe->eq_lut, st, &level0);
+    int rc = grey_chain(fe, av_frames(img0, img1, img_stride), d.S, l0, nullptr, gray, mosaic, fe->eq_lut, st, &level0);
     if (rc) return rc;
     return av_launch_pyramid(level0, d.S, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur, 2, st, !(inputs_persist || fe->own_l0), wrote_l0);
 }
@@ -978,6 +983,7 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         return AV_E_INVALID;
     }
     if (av_pixfmt_check(cfg->pixel_format, cfg->gray16_shift, "av_frontend_create")) return AV_E_INVALID;
+    if (av_pixfmt_check_size(cfg->pixel_format, cfg->width, cfg->height, "av_frontend_create")) return AV_E_INVALID;
     // image_downscale: from here on `cfg` is the configuration of the PROCESSED image (binned size, calibration scaled to it, in the
     // order include/airvision.h gives); in_w x in_h is what the entry points are handed
     const int in_w = cfg->width, in_h = cfg->height;
@@ -1105,11 +1111,12 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         a.thr = cfg->ransac_threshold; a.N = rs_N; a.seed = cfg->ransac_seed;
         fe->ransac = true;
     }
-    fe->fmt = cfg->pixel_format; fe->fmt_shift = cfg->gray16_shift; fe->bpp = av_pixfmt_bytes(cfg->pixel_format);
-    fe->ds = ds; fe->in_w = in_w; fe->in_h = in_h;
+    fe->fmt = cfg->pixel_format; fe->fmt_shift = cfg->gray16_shift;
+    fe->ds = ds; fe->in_w = in_w; fe->in_h = in_h; fe->frame_bytes = av_pixfmt_frame_bytes(fe->fmt, in_w, in_h);
     fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8 || ds > 1;
     if (fe->own_l0) A(fe->eq, (size_t)3 * S * w * h)
     if (ds > 1 && fe->fmt != AV_PIX_GRAY8) A(fe->gray_full, (size_t)2 * S * in_w * in_h)
+    if (av_pixfmt_packed_depth(fe->fmt) && av_pixfmt_is_bayer(fe->fmt)) A(fe->mosaic, (size_t)2 * S * in_w * in_h)
     if (clahe) {
         A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
         fe->clahe = true;
@@ -1161,6 +1168,7 @@ AV_EXPORT void av_frontend_destroy(av_frontend* fe)
         if (u.done) (void)hipEventDestroy(u.done);
     }
     if (fe->fs.gray_d) (void)hipFree(fe->fs.gray_d);
+    if (fe->fs.mosaic_d) (void)hipFree(fe->fs.mosaic_d);
     if (fe->fs.uploaded) (void)hipEventDestroy(fe->fs.uploaded);
     if (fe->fs.stepped) (void)hipEventDestroy(fe->fs.stepped);
     if (fe->copy_stream) (void)hipStreamDestroy(fe->copy_stream);
@@ -1206,7 +1214,7 @@ AV_EXPORT int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_
 // Needs AV_FE_INPUTS_PERSIST (the images are read again by the step itself); a step that comes with other images builds its own.
 AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride, void* stream)
 {
-    if (!fe || !img0_dev || !img1_dev || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
+    if (!fe || !img0_dev || !img1_dev || img_stride < fe->frame_bytes) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
@@ -1224,7 +1232,7 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
 AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride,
                                const double* timestamps, void* stream)
 {
-    if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) {
+    if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < fe->frame_bytes) {
         av_set_error("av_frontend_step: bad arguments");
         return AV_E_INVALID;
     }
@@ -1234,12 +1242,12 @@ AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const u
 AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, const uint8_t* img1_host, int64_t img_stride,
                                     const double* timestamps, void* stream)
 {
-    if (!fe || !img0_host || !img1_host || !timestamps || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) {
+    if (!fe || !img0_host || !img1_host || !timestamps || img_stride < fe->frame_bytes) {
         av_set_error("av_frontend_step_host: bad arguments");
         return AV_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t img_bytes = (size_t)fe->in_w * fe->in_h * fe->bpp;    // the staging slots carry the frames in their own format and size
+    const size_t img_bytes = (size_t)fe->frame_bytes;                  // the staging slots carry the frames in their own format and size
     const int S = fe->d.S;
     AV_HIP(hipSetDevice(fe->device));
     av_frontend::HostSlot& h = fe->hs[fe->hs_next];
@@ -1302,7 +1310,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
                                         int64_t img_stride, void* stream)
 {
     (void)stream;
-    if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < (int64_t)fe->in_w * fe->in_h * fe->bpp) {
+    if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < fe->frame_bytes) {
         av_set_error("av_frontend_frames_upload: bad arguments");
         return AV_E_INVALID;
     }
@@ -1324,7 +1332,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
     const bool raw = conv || bin;                                   // the frames go through a kernel on their way into the store
     const size_t in_hw = (size_t)fe->in_w * fe->in_h;
-    const size_t fb = in_hw * fe->bpp;                              // bytes of one camera's frame as the caller hands it over
+    const size_t fb = (size_t)fe->frame_bytes;                           // bytes of one camera's frame as the caller hands it over
     av_frontend::FrameStore::Up& u = fs.up[fs.up_next];
     fs.up_next = (fs.up_next + 1) % 4;
     if (u.used) AV_HIP(hipEventSynchronize(u.done));                // the staging area's previous upload has left it
@@ -1345,6 +1353,11 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
         if (fs.gray_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.gray_d); fs.gray_d = nullptr; fs.gray_cap = 0; }
         AV_HIP(hipMalloc((void**)&fs.gray_d, ((size_t)n + 16) * 2 * in_hw));
         fs.gray_cap = (size_t)n + 16;
+    }
+    if (fe->mosaic && (size_t)n > fs.mosaic_cap) {                  // a packed mosaic format: the same rule for the store's mosaic scratch
+        if (fs.mosaic_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.mosaic_d); fs.mosaic_d = nullptr; fs.mosaic_cap = 0; }
+        AV_HIP(hipMalloc((void**)&fs.mosaic_d, ((size_t)n + 16) * 2 * in_hw));
+        fs.mosaic_cap = (size_t)n + 16;
     }
 #pragma omp parallel for schedule(static) num_threads(n >= 8 ? 8 : 1)
     for (int i = 0; i < 2 * n; ++i) {
@@ -1376,8 +1389,9 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     // this upload)
     const FrameSet l0{{fs.img, fs.img + hw}, (int64_t)(2 * hw), u.idx_d};
     const FrameSet gray = fs.gray_d ? FrameSet{{fs.gray_d, fs.gray_d + in_hw}, (int64_t)(2 * in_hw), nullptr} : FrameSet{};
+    const FrameSet mosaic = fs.mosaic_d ? FrameSet{{fs.mosaic_d, fs.mosaic_d + in_hw}, (int64_t)(2 * in_hw), nullptr} : FrameSet{};
     FrameSet level0;
-    if ((rc = grey_chain(fe, raw ? av_frames(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb)) : l0, n, l0, raw ? u.idx_d + n : nullptr, gray, fe->fs_lut, cs, &level0))) return rc;
+    if ((rc = grey_chain(fe, raw ? av_frames(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb)) : l0, n, l0, raw ? u.idx_d + n : nullptr, gray, mosaic, fe->fs_lut, cs, &level0))) return rc;
     bool wrote_l0 = true;
     if ((rc = av_launch_pyramid(level0, n, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0))) return rc;
     fs.l0_in_place = !wrote_l0;

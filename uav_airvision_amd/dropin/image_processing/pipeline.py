@@ -40,8 +40,8 @@ class ImageProcessingPipeline(object):
         """pipeline.py:46-150: returns feature_msg(timestamp, [FeatureMeasurement])."""
         cam0_msg, cam1_msg = stereo_msg.cam0_msg, stereo_msg.cam1_msg
         if self._engine.pixel_format != 0:
-            # config.image_format (no counterpart in the reference): colour or 16-bit frames go to the engine as they are and are
-            # converted to 8-bit grey on the GPU; step_host refuses a wrong dtype or shape with a ValueError naming both
+            # config.image_format (no counterpart in the reference): colour, 16-bit, mosaic or packed 10 / 12-bit frames (uint8 [h, w * d / 8])
+            # go to the engine as they are and are converted to 8-bit grey on the GPU; step_host refuses a wrong dtype or shape with a ValueError naming both
             self._engine.step_host(cam0_msg.image, cam1_msg.image, [cam0_msg.timestamp])
         else:
             img0 = np.ascontiguousarray(cam0_msg.image, dtype=np.uint8)

@@ -105,12 +105,22 @@ class EuRoCDataset(object):
         return g[:, :8].copy()
 
 
+def _refuse_packed(who, fmt):
+    """The packed 10 / 12-bit transports are what a camera link delivers, not what a file holds: no PNG flavour carries one, so nothing
+    that reads or writes the EuRoC layout takes them (feed such frames to the engine directly: FrontendEngine, frontend.pack_frames)."""
+    from . import _native as N
+    if N.is_packed(fmt):
+        raise ValueError('%s: %s is a packed transport, which no PNG file holds: the EuRoC reader, writer and stagers do not take it '
+                         '(hand packed frames to FrontendEngine.step / step_host / frames_upload)' % (who, N.PIXEL_FORMAT_NAMES[fmt]))
+
+
 def frame_array(pixel_format, n, height, width, zeros=True):
     """A host batch of n frames of a pixel format ('gray8' / 'gray16' / 'rgb8' / 'rgba8' / 'bayer_*8' / 'bayer_*16' or the AV_PIX_* code)
     as decode_batch fills it and the front-end takes it: uint8 [n, h, w], uint16 [n, h, w], uint8 [n, h, w, 3 | 4]; a Bayer mosaic is
     one sample per pixel, uint8 [n, h, w] or uint16 [n, h, w]."""
     from . import _native as N
     fmt = N.pixel_format_code(pixel_format)
+    _refuse_packed('frame_array', fmt)
     bpp = N.PIXEL_BYTES[fmt]
     shape = (n, height, width) if bpp <= 2 else (n, height, width, bpp)
     return (np.zeros if zeros else np.empty)(shape, np.uint16 if N.is_16bit(fmt) else np.uint8)
@@ -123,6 +133,7 @@ def png_pixel_format(pixel_format):
     mosaic; the engine's config.image_format does)."""
     from . import _native as N
     fmt = N.pixel_format_code(pixel_format)
+    _refuse_packed('png_pixel_format', fmt)
     if N.is_bayer(fmt):
         return 'gray16' if N.is_16bit(fmt) else 'gray8'
     name = N.PIXEL_FORMAT_NAMES[fmt]
@@ -397,6 +408,7 @@ def encode_frame(image, pixel_format='gray8', gains=BAYER_GAINS, shift=8):
     uint16 for the 16-bit mosaics (config.gray16_shift = shift reads it back)."""
     from . import _native as N
     fmt = N.pixel_format_code(pixel_format)
+    _refuse_packed('encode_frame', fmt)
     g = np.asarray(image, np.uint8)
     if fmt == N.AV_PIX_GRAY8:
         return g
@@ -425,6 +437,8 @@ def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None
     writes the raw mosaic of the frames coloured by `bayer_gains` as 8- or 16-bit grey PNGs (16-bit samples << `gray16_shift`)."""
     from PIL import Image
     from . import _native as N
+    if pixel_format in N.PACKED_FORMATS:
+        _refuse_packed('write_euroc_layout', N.PACKED_FORMATS[pixel_format])
     bayer = pixel_format in N.PIXEL_FORMATS and N.is_bayer(N.PIXEL_FORMATS[pixel_format])
     if pixel_format not in ('gray8', 'gray16', 'rgb8', 'rgba8') and not bayer:
         raise ValueError('write_euroc_layout: PNG holds gray8, gray16, rgb8 or rgba8 frames or a Bayer mosaic, not %r' % (pixel_format,))

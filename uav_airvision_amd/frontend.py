@@ -118,7 +118,10 @@ def pack_frontend_config(config, max_corners=None):
 
 
 def frame_shape(pixel_format, n, height, width):
-    """Shape of n frames of an AV_PIX_* format: [n, h, w] for the grey formats, [n, h, w, 3 | 4] for the colour ones."""
+    """Shape of n frames of an AV_PIX_* format: [n, h, w] for the grey formats and the mosaics, [n, h, w, 3 | 4] for the colour ones,
+    [n, h, w * d / 8] (bytes) for the packed 10 / 12-bit transports."""
+    if N.is_packed(pixel_format):
+        return (n, height, N.packed_row_bytes(pixel_format, width))
     bpp = N.PIXEL_BYTES[pixel_format]
     return (n, height, width) if bpp <= 2 else (n, height, width, bpp)
 
@@ -126,7 +129,7 @@ def frame_shape(pixel_format, n, height, width):
 def check_host_frames(what, a, pixel_format, n, height, width):
     """A NumPy batch of n frames of an AV_PIX_* format as a C-contiguous array of exactly the dtype and shape the engine reads: uint16
     [n, h, w] for gray16 and the 16-bit Bayer mosaics, uint8 [n, h, w, 3 | 4] for colour, uint8 [n, h, w] for gray8 and the 8-bit
-    mosaics ([h, w] / [h, w, c] is taken for n = 1).  Nothing is converted: a wrong dtype or shape is a ValueError naming both."""
+    mosaics, uint8 [n, h, w * d / 8] for the packed transports ([h, w] / [h, w, c] is taken for n = 1).  Nothing is converted: a wrong dtype or shape is a ValueError naming both."""
     a = np.asarray(a)
     want_dtype = np.uint16 if N.is_16bit(pixel_format) else np.uint8
     want = frame_shape(pixel_format, n, height, width)
@@ -149,6 +152,65 @@ def check_device_frames(what, t, pixel_format, n, height, width):
     if not t.is_cuda or not t.is_contiguous():
         raise ValueError('%s: a contiguous cuda tensor is needed' % what)
     return t
+
+
+def _packing_of(fmt):
+    code = N.pixel_format_code(fmt)
+    if not N.is_packed(code):
+        raise ValueError('%r is no packed format (one of %s)' % (fmt, ', '.join(sorted(N.PACKED_FORMATS, key=N.PACKED_FORMATS.get))))
+    return code, N.packed_depth(code), N.packing(code).endswith('csi2')
+
+
+def pack_frames(samples_u16, fmt):
+    """Right-aligned d-bit samples, uint16 [..., h, w], as the bytes of packed format `fmt` ('gray12p', 'bayer_rggb10_csi2', .. or the
+    AV_PIX_* code), uint8 [..., h, w * d / 8]: the layouts of include/airvision.h ("Packed 10 / 12-bit transports"), in NumPy on the
+    host.  ValueError for a value at or above 2^d and for a width that is not whole groups (4 samples at 10 bits, 2 at 12)."""
+    code, d, csi2 = _packing_of(fmt)
+    v = np.asarray(samples_u16)
+    if v.dtype != np.uint16 or v.ndim < 2:
+        raise ValueError('pack_frames: %s samples are uint16 [..., h, w], got %s %s' % (N.PIXEL_FORMAT_NAMES[code], v.dtype, tuple(v.shape)))
+    wb = N.packed_row_bytes(code, v.shape[-1])
+    if v.size and int(v.max()) >> d:
+        raise ValueError('pack_frames: %s samples are below 2^%d = %d, got %d' % (N.PIXEL_FORMAT_NAMES[code], d, 1 << d, int(v.max())))
+    gpx, gb = N.packed_group(code)
+    p = v.astype(np.uint32).reshape(v.shape[:-1] + (v.shape[-1] // gpx, gpx))
+    out = np.empty(p.shape[:-1] + (gb,), np.uint8)
+    if csi2:
+        out[..., :gpx] = p >> (d - 8)
+        low = np.zeros(p.shape[:-1], np.uint32)
+        for j in range(gpx):
+            low |= (p[..., j] & ((1 << (d - 8)) - 1)) << ((d - 8) * j)
+        out[..., gpx] = low
+    else:
+        word = np.zeros(p.shape[:-1], np.uint64)
+        for j in range(gpx):
+            word |= p[..., j].astype(np.uint64) << np.uint64(d * j)
+        for i in range(gb):
+            out[..., i] = (word >> np.uint64(8 * i)) & np.uint64(255)
+    return out.reshape(v.shape[:-1] + (wb,))
+
+
+def unpack_frames(raw_u8, fmt):
+    """The inverse of pack_frames: uint8 [..., h, w * d / 8] -> right-aligned d-bit samples, uint16 [..., h, w].  ValueError for a row
+    that is not whole groups of bytes."""
+    code, d, csi2 = _packing_of(fmt)
+    r = np.asarray(raw_u8)
+    gpx, gb = N.packed_group(code)
+    if r.dtype != np.uint8 or r.ndim < 2 or r.shape[-1] == 0 or r.shape[-1] % gb:
+        raise ValueError('unpack_frames: %s frames are uint8 [..., h, w * %d / 8] with rows of whole %d-byte groups, got %s %s' % (
+            N.PIXEL_FORMAT_NAMES[code], d, gb, r.dtype, tuple(r.shape)))
+    b = r.astype(np.uint32).reshape(r.shape[:-1] + (r.shape[-1] // gb, gb))
+    out = np.empty(b.shape[:-1] + (gpx,), np.uint16)
+    if csi2:
+        for j in range(gpx):
+            out[..., j] = b[..., j] << (d - 8) | ((b[..., gpx] >> ((d - 8) * j)) & ((1 << (d - 8)) - 1))
+    else:
+        word = np.zeros(b.shape[:-1], np.uint64)
+        for i in range(gb):
+            word |= b[..., i].astype(np.uint64) << np.uint64(8 * i)
+        for j in range(gpx):
+            out[..., j] = (word >> np.uint64(d * j)) & np.uint64((1 << d) - 1)
+    return out.reshape(r.shape[:-1] + (r.shape[-1] // gb * gpx,))
 
 
 def circle_mask(width, height, cx, cy, radius):
@@ -203,7 +265,10 @@ class FrontendEngine(object):
 
         config.image_format other than 'gray8' (and config.gray16_shift): every entry below takes frames of that format instead --
         uint16 [S,h,w] for 'gray16' (cuda: torch.uint16, or torch.int16 holding the same bits), uint8 [S,h,w,3] for 'rgb8' / 'bgr8',
-        uint8 [S,h,w,4] for 'rgba8' / 'bgra8', the raw mosaic as uint8 [S,h,w] for 'bayer_*8' and uint16 [S,h,w] for 'bayer_*16' -- and converts them to 8-bit grey on the GPU ahead of everything else (av_to_gray8 in
+        uint8 [S,h,w,4] for 'rgba8' / 'bgra8', the raw mosaic as uint8 [S,h,w] for 'bayer_*8' and uint16 [S,h,w] for 'bayer_*16', the packed
+        bytes as uint8 [S,h,w*d/8] for the 10 / 12-bit transports 'gray{10p,12p,10_csi2,12_csi2}' and 'bayer_*{10p,12p,10_csi2,12_csi2}' (PFNC
+        Mono10p / Mono12p, MIPI CSI-2 RAW10 / RAW12: rows tightly packed, width a multiple of 4 / 2 samples; `pack_frames` / `unpack_frames`
+        are their NumPy twins; a sample is left-justified to 16 bits before gray16_shift applies) -- and converts them to 8-bit grey on the GPU ahead of everything else (av_to_gray8 in
         include/airvision.h has the arithmetic).  Nothing is cast on the way: a wrong dtype or shape is a ValueError naming both.
         The caller's frames are never written; `read_image` returns the grey frame the step used.
 
@@ -247,7 +312,7 @@ class FrontendEngine(object):
         self.input_width, self.input_height = int(cfg.width), int(cfg.height)
         self.width, self.height = self.input_width // self.downscale, self.input_height // self.downscale
         self.pixel_format = int(cfg.pixel_format)
-        self._frame_bytes = self.input_width * self.input_height * N.PIXEL_BYTES[self.pixel_format]      # img_stride of every entry point
+        self._frame_bytes = N.frame_bytes(self.pixel_format, self.input_width, self.input_height)      # img_stride of every entry point
 
     def close(self):
         if self._h:

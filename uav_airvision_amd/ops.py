@@ -251,16 +251,22 @@ def clahe(img, clip_limit=2.0, tiles=(8, 8), out=None, return_lut=False, device=
 
 def to_gray8(img, pixel_format, shift=8, out=None, device=0):
     """Camera frames of another pixel format to 8-bit grey (av_to_gray8; formats and arithmetic are written out in include/airvision.h).
-    pixel_format: 'gray8' | 'gray16' | 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8' | 'bayer_{rggb,bggr,grbg,gbrg}{8,16}' or the AV_PIX_* code.
+    pixel_format: 'gray8' | 'gray16' | 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8' | 'bayer_{rggb,bggr,grbg,gbrg}{8,16}' | 'gray{10p,12p,10_csi2,
+    12_csi2}' | 'bayer_{rggb,bggr,grbg,gbrg}{10p,12p,10_csi2,12_csi2}' or the AV_PIX_* code.
     img: [n, h, w] or [h, w] for the grey formats and the Bayer mosaics (at least 2 x 2: ValueError otherwise) -- uint16 for 'gray16' and
     'bayer_*16' (a cuda tensor may also be torch.int16 holding the same bits) -- and uint8 [n, h, w, c] or [h, w, c]
-    with c = 3 / 4 for the colour ones; a cuda tensor or anything torch.as_tensor takes.  A cuda tensor is read where it lies: each
+    with c = 3 / 4 for the colour ones, and uint8 [n, h, w * d / 8] or [h, w * d / 8] for the packed 10 / 12-bit transports ('gray12p',
+    'bayer_rggb10_csi2', ..: w is taken from the last dimension, which must be whole groups of 5 / 3 bytes; shift applies to the sample
+    left-justified to 16 bits; a packed MOSAIC is converted in two passes through a scratch that the call allocates and frees, so for
+    those formats alone the call waits for the stream and cannot be captured into a graph -- the engine owns its scratch and does neither); a cuda tensor or anything torch.as_tensor takes.  A cuda tensor is read where it lies: each
     image must be contiguous, the images may be any distance apart (a slice of a larger tensor), at any address.  shift: the 16-bit
     formats only, 0 .. 8.  Returns a uint8 cuda tensor [n, h, w] or [h, w] -- `out` itself if given (uint8 cuda, that shape, each image contiguous;
     it must not overlap img)."""
     fmt = N.pixel_format_code(pixel_format)
     shift = N.gray16_shift_value(shift)
     t = torch.as_tensor(img)
+    if N.is_packed(fmt):
+        return _packed_to_gray8(t, fmt, shift, out, device)
     bpp = N.PIXEL_BYTES[fmt]
     colour = bpp >= 3
     dtypes = (torch.uint16, torch.int16) if N.is_16bit(fmt) else (torch.uint8,)
@@ -287,6 +293,38 @@ def to_gray8(img, pixel_format, shift=8, out=None, device=0):
     if not ob[0].is_contiguous() or (n > 1 and ob.stride(0) < h * w):
         raise ValueError('to_gray8: every image of out must be contiguous')
     in_stride = (tb.stride(0) if n > 1 else h * w * (bpp if colour else 1)) * tb.element_size()
+    out_stride = ob.stride(0) if n > 1 else h * w
+    with torch.cuda.device(device):
+        N.check(N.lib().av_to_gray8(N.dptr(tb), in_stride, n, w, h, fmt, shift, N.dptr(ob), out_stride, N.current_stream()))
+    return out
+
+
+def _packed_to_gray8(t, fmt, shift, out, device):
+    """to_gray8 for the packed transports: t uint8 [n, h, w * d / 8] or [h, w * d / 8]."""
+    name, d = N.PIXEL_FORMAT_NAMES[fmt], N.packed_depth(fmt)
+    gpx, gb = N.packed_group(fmt)
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3) or t.shape[-1] == 0 or t.shape[-1] % gb:
+        raise ValueError('to_gray8: %s images are torch.uint8 [n, h, w * %d / 8] or [h, w * %d / 8] with rows of whole %d-byte groups, got %s %s' % (
+            name, d, d, gb, t.dtype, tuple(t.shape)))
+    wb = int(t.shape[-1])
+    w = wb // gb * gpx
+    if N.is_bayer(fmt) and (w < 2 or t.shape[-2] < 2):
+        raise ValueError('to_gray8: a Bayer mosaic is at least 2 x 2 samples, got %s' % (tuple(t.shape),))
+    t = t.to(_dev(device))
+    batched = t.dim() == 3
+    tb = t if batched else t.unsqueeze(0)
+    n, h = tb.shape[0], tb.shape[1]
+    if not tb[0].is_contiguous() or (n > 1 and tb.stride(0) < h * wb):
+        tb = tb.contiguous()
+    oshape = (n, h, w) if batched else (h, w)
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.uint8, device=_dev(device))
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == oshape):
+        raise ValueError('to_gray8: out must be a uint8 cuda tensor of shape %s' % (oshape,))
+    ob = out if batched else out.unsqueeze(0)
+    if not ob[0].is_contiguous() or (n > 1 and ob.stride(0) < h * w):
+        raise ValueError('to_gray8: every image of out must be contiguous')
+    in_stride = tb.stride(0) if n > 1 else h * wb
     out_stride = ob.stride(0) if n > 1 else h * w
     with torch.cuda.device(device):
         N.check(N.lib().av_to_gray8(N.dptr(tb), in_stride, n, w, h, fmt, shift, N.dptr(ob), out_stride, N.current_stream()))
