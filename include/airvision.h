@@ -288,6 +288,52 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
 int av_frontend_set_masks(av_frontend* fe, const uint8_t* mask0_host, const uint8_t* mask1_host);
 int av_frontend_read_mask(av_frontend* fe, int cam, uint8_t* out_host);
 
+/* Photometric calibration: AV_FE_PHOTOMETRIC in av_frontend_config.flags.  A real lens and sensor do not give a linear, spatially
+ * uniform measurement of the scene: a wide-angle lens loses half its light or more towards the rim (vignetting) and the sensor's
+ * response curve is not a straight line.  No counterpart in the reference, which works on the camera's own pixels; the convention is
+ * that of the TUM mono-VO dataset: an inverse response table G^-1 (256 entries, pcalib.txt) and a vignette map V(x) (vignette.png), and
+ * the corrected image is I'(x) = G^-1(I(x)) / V(x).  Here in integers only, which makes this text the contract (tests/photometric_ref.py
+ * states it in NumPy).  Per camera two optional tables, shared by all streams of an engine (one rig, one calibration):
+ *   response  uint16[256] in Q8: entry p is G^-1(p) * 256, every entry <= AV_PHOTOMETRIC_RESPONSE_MAX = 65280 (255 * 256).  Absent means
+ *             p * 256.
+ *   gain      uint16[height * width] in Q12, at the size of the frames handed to the entry points, tightly packed: 4096 / V(x).  Absent
+ *             means 4096 everywhere.  The range covers gains up to 15.9998.
+ * For a grey pixel p at x:
+ *   out = min(255, (response[p] * gain[x] + (1 << 19)) >> 20)
+ * The intermediate fits 32 bits unsigned, 65280 * 65535 + 2^19 < 2^32: that bound is why a response entry above 65280 is refused.
+ * With only a response the rule reduces to (response[p] + 128) >> 8, with only a gain to (p * gain[x] + 2048) >> 12 (the min still
+ * applies); the kernels compute the one formula.  The float tables are quantised once, on the host, in float64 (the Python
+ * frontend.photometric_tables: response floor(clip(U, 0, 255) * 256 + 0.5), gain min(65535, floor(4096 / V + 0.5)), V <= 0 -> 65535);
+ * everything after that is integer, so a kernel is either bit-identical to the reference or wrong.
+ * Place in the input stage: raw frame -> conversion to grey -> PHOTOMETRIC -> binning -> CLAHE -> pyramids / LK / FAST.  The stage runs
+ * at the input size, ahead of the binning: the vignette is a property of the full-size sensor, and binning corrected pixels is the
+ * physically right order.  Any pixel_format works: the stage sees the 8-bit grey after the conversion (after the demosaic for a
+ * mosaic).  Static masks are independent: a masked pixel is corrected like any other.
+ * An engine created with the flag owns level 0 (as with AV_FE_CLAHE) and av_frontend_read_image returns the frame after the whole
+ * chain.  After a conversion the stage runs in place on what the conversion wrote; without one it reads the caller's frames (the
+ * staging slot's, the upload ring's) and writes the engine's own memory: the caller's frames are never written.  It holds for
+ * av_frontend_step with and without AV_FE_INPUTS_PERSIST, av_frontend_prestage (the stage runs there; the step that follows with the same
+ * pointers skips it), av_frontend_step_host and av_frontend_frames_upload, which then takes the frames through its device staging into
+ * the store entries on the copy stream; an entry named twice in one upload receives its later frame, corrected exactly once (with
+ * AV_FE_CLAHE the refusal of duplicates stands).  The launches count under class 0 of av_frontend_enable_timing, inside the input
+ * stage's span.  Without the flag the step enqueues exactly what it always did and nothing more is allocated.
+ * av_frontend_set_photometric takes HOST arrays: response0 / response1 [256], gain0 / gain1 [height * width] (the input size).  Any
+ * pointer may be NULL = the identity for that part; all four NULL is the identity stage.  Blocking (the arrays are free again on
+ * return).  It needs the flag, refuses a response entry above 65280, and is accepted only while the engine has not yet been handed a
+ * frame (av_frontend_step*, _prestage, _frames_upload), like av_frontend_set_masks and for the same reason: frames already in the engine
+ * would disagree with the new tables.  All of these are AV_E_INVALID with a text.  An engine with the flag that has not been given
+ * its tables refuses every step, prestage and upload, AV_E_INVALID, with a text that names av_frontend_set_photometric.
+ * av_frontend_read_photometric copies the tables of camera `cam` (0 / 1) back: response_out_host [256], gain_out_host
+ * [height * width]; either may be NULL; a part that was given as NULL reads back as the identity (p * 256, 4096).
+ * Not covered: per-stream tables, tables that change during a run, a per-pixel dark frame, exposure-time normalisation between
+ * frames, fusing the stage into the conversion / Bayer / unpack kernels, gains of 16 and above, estimating the calibration itself,
+ * two cameras of different sizes; fast_threshold and the LK thresholds are not retuned for corrected images. */
+#define AV_FE_PHOTOMETRIC 8
+#define AV_PHOTOMETRIC_RESPONSE_MAX 65280
+int av_frontend_set_photometric(av_frontend* fe, const uint16_t* response0_host, const uint16_t* gain0_host,
+                                const uint16_t* response1_host, const uint16_t* gain1_host);
+int av_frontend_read_photometric(av_frontend* fe, int cam, uint16_t* response_out_host, uint16_t* gain_out_host);
+
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
  * img0_dev + s*img_stride and img1_dev + s*img_stride; timestamps[s] is the frame time.  All
@@ -387,9 +433,10 @@ int av_frontend_read_match_counts(av_frontend* fe, int stream_idx, int32_t out[2
 int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, int32_t out[4], void* stream);
 
 /* The level-0 image the last step used for camera `cam` (0 / 1) of one stream of an engine created with AV_FE_CLAHE, with a
- * pixel_format other than AV_PIX_GRAY8 or with image_downscale = 2 or 4, i.e. the grey frame the step worked on, binned if
- * image_downscale is set and equalised if AV_FE_CLAHE is set: (width / f) * (height / f) bytes, the processed size, into out_host
- * (width * height without binning).  AV_E_INVALID with none of the three (level 0 is then the caller's own image),
+ * pixel_format other than AV_PIX_GRAY8, with AV_FE_PHOTOMETRIC or with image_downscale = 2 or 4, i.e. the grey frame the step
+ * worked on, photometrically corrected if AV_FE_PHOTOMETRIC is set, binned if image_downscale is set and equalised if AV_FE_CLAHE
+ * is set: (width / f) * (height / f) bytes, the processed size, into out_host
+ * (width * height without binning).  AV_E_INVALID with none of the four (level 0 is then the caller's own image),
  * before the first step, and for a stream whose av_frontend_step_frames entries were negative from the start.  The image comes from where
  * the LAST step read it: the frame store after av_frontend_step_frames, the engine's own buffer after the other steps.  Between an
  * av_frontend_prestage and the step it serves the cam1 image of the last step is gone (its slot holds the next frame's): cam 1 is then
@@ -573,6 +620,26 @@ int av_downscale(const uint8_t* img_dev, int64_t img_stride, int n_img, int W, i
  * arguments takes 16 output pixels per lane, 0 if one (or if the arguments are not a valid call).  It is the launcher's own rule,
  * exported so that tests/test_gpu_downscale_op.py can assert which kernel a case reached.  Pure host function. */
 int av_downscale_vector_path(const uint8_t* img_dev, int64_t img_stride, int n_img, int W, int factor, const uint8_t* out_dev, int64_t out_stride);
+
+/* ---------------------------------------------------------------------------------------------
+ * Photometric calibration of 8-bit grey frames ("Photometric calibration" above has the definition):
+ *   out = min(255, (response[p] * gain[x] + (1 << 19)) >> 20)
+ * av_photometric: n images, image i at in_dev + i * in_stride (tightly packed w * h u8), to out_dev + i * out_stride.  response_dev:
+ * uint16[256] Q8 on the device or NULL (p * 256); gain_dev: uint16[w * h] Q12 on the device or NULL (4096), one map for all n images.
+ * out_dev == in_dev with equal strides (they count only when n > 1) works in place; any other overlap of the two spans is refused.  With 16-byte aligned image
+ * addresses, strides (they count only when n > 1) and gain address a lane takes 16 pixels from whole vectors, and the last w * h % 16
+ * pixels of every image go byte by byte; anything else goes one pixel per lane.  AV_E_INVALID with text for w * h outside
+ * 1 .. AV_MAX_IMAGE_PIXELS, strides smaller than an image, null images, n < 0, both tables NULL, a partially overlapping output and
+ * a response entry above AV_PHOTOMETRIC_RESPONSE_MAX (the call reads the 512-byte table back to check it, so it waits for the stream
+ * when a response is given; the engine checks its tables once, when they are set).  n == 0 is AV_OK.
+ * ------------------------------------------------------------------------------------------- */
+int av_photometric(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                   const uint16_t* response_dev, const uint16_t* gain_dev, void* stream);
+/* TEST-ONLY observable, not part of the supported interface (it may change or go without notice): 1 if av_photometric with these
+ * arguments takes 16 pixels per lane, 0 if one (or if the arguments are not a valid call).  The launcher's own rule, exported so that
+ * tests/test_gpu_photometric_op.py can assert which body a case reached.  Pure host function. */
+int av_photometric_vector_path(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                               const uint16_t* response_dev, const uint16_t* gain_dev);
 
 /* ---------------------------------------------------------------------------------------------
  * Two-point RANSAC on the temporal matches of ONE camera (no counterpart in the reference: feature_tracker.py:135-136 is where

@@ -20,6 +20,8 @@ AV_OK, AV_E_INVALID, AV_E_HIP, AV_E_CAPACITY, AV_E_NODEVICE, AV_E_NUMERIC = 0, -
 AV_FE_INPUTS_PERSIST = 1
 AV_FE_RANSAC = 2
 AV_FE_CLAHE = 4
+AV_FE_PHOTOMETRIC = 8
+AV_PHOTOMETRIC_RESPONSE_MAX = 65280
 AV_CLAHE_MAX_TILES = 16
 AV_PIX_GRAY8, AV_PIX_GRAY16, AV_PIX_RGB8, AV_PIX_BGR8, AV_PIX_RGBA8, AV_PIX_BGRA8 = 0, 1, 2, 3, 4, 5
 AV_PIX_BAYER_RGGB8, AV_PIX_BAYER_BGGR8, AV_PIX_BAYER_GRBG8, AV_PIX_BAYER_GBRG8 = 16, 17, 18, 19
@@ -247,6 +249,10 @@ SIGNATURES = {
     'av_clahe': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     'av_frontend_set_masks': (C.c_int, [_P, _P, _P]),
     'av_frontend_read_mask': (C.c_int, [_P, C.c_int, _P]),
+    'av_frontend_set_photometric': (C.c_int, [_P, _P, _P, _P, _P]),
+    'av_frontend_read_photometric': (C.c_int, [_P, C.c_int, _P, _P]),
+    'av_photometric': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
+    'av_photometric_vector_path': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P]),
     'av_frontend_enable_timing': (C.c_int, [_P, C.c_int]),
     'av_frontend_read_timing': (C.c_int, [_P, C.POINTER(C.c_double * 4), C.POINTER(C.c_int32 * 4)]),
 }

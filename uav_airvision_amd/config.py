@@ -72,6 +72,16 @@ class ConfigEuRoC(object):
         # (frontend.circle_mask builds the circle).  None: the front-end is the reference's, bit for bit.
         self.cam0_mask = None
         self.cam1_mask = None
+        # photometric calibration of the two cameras, for every stream of an engine (no counterpart in the reference; "Photometric
+        # calibration" in include/airvision.h; the TUM mono-VO convention): cam*_response = the inverse response G^-1, 256 floats in
+        # [0, 255] or the path of a pcalib.txt-style text file of 256 numbers; cam*_vignette = V(x), a float array of shape (height, width)
+        # of cam*_resolution with values in (0, 1] or the path of a 16-bit grey PNG of that size (normalised by its maximum).  Every grey
+        # pixel becomes G^-1(p) / V(x) on the GPU, after the conversion to grey and ahead of binning and CLAHE
+        # (frontend.photometric_tables quantises the tables).  All four None: the front-end is the reference's, bit for bit.
+        self.cam0_response = None
+        self.cam1_response = None
+        self.cam0_vignette = None
+        self.cam1_vignette = None
         self.stereo_threshold = 5
         self.max_iteration = 30
         self.track_precision = 0.01

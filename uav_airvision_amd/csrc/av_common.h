@@ -299,3 +299,10 @@ int av_launch_bayer_to_gray8(const FrameSet& src, const FrameSet& dst, int n_gro
 // downscale.hip: 2 x 2 / 4 x 4 binning (f = 2 or 4) of n_groups tightly packed W x H grey frames of one camera or of two into tightly
 // packed (W / f) x (H / f) ones; W % f == 0 and H % f == 0.  Sets and list as av_launch_to_gray8.  Never in place.
 int av_launch_downscale(const FrameSet& src, const FrameSet& dst, int n_groups, int W, int H, int f, hipStream_t st);
+// photometric.hip: photometric calibration of n_groups tightly packed w x h grey frames of one camera or of two ("Photometric
+// calibration" in include/airvision.h): out = min(255, (resp[p] * gain[x] + 2^19) >> 20), resp* [256] Q8 and gain* [w * h] Q12 on the
+// device, one per camera, null = that part is the identity (at least one part is given; cameras that differ in their parts take one
+// launch each).  Sets and list as av_launch_to_gray8 -- the destination's list, a negative entry skips the group -- but dst may be src:
+// a source with a list (the destination's own) is read through it, which is the in-place call on a listed set.
+int av_launch_photometric(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
+                          const uint16_t* gain0, const uint16_t* gain1, hipStream_t st);

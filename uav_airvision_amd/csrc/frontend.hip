@@ -700,6 +700,11 @@ struct av_frontend {
     // av_frontend_set_masks: the engine's two mask buffers ([w * h] each, allocated by the first call; d.smask0 / smask1 point at them
     // while a mask is set) and whether the engine has been handed a frame (step, prestage or frames_upload): masks are then refused
     uint8_t* smask_buf[2] = {nullptr, nullptr}; bool fed = false;
+    // AV_FE_PHOTOMETRIC: the tables of the two cameras on the device -- ph_resp_buf [2][256] Q8 (allocated with the engine), ph_gain_buf
+    // [in_w * in_h] Q12 per camera (allocated by the first av_frontend_set_photometric that brings one) -- and what the stage's launches are
+    // handed, ph_resp / ph_gain: null = that part is the identity for that camera.  photo_set: the tables have been given (a step before that is refused)
+    bool photo = false, photo_set = false; uint16_t* ph_resp_buf = nullptr; uint16_t* ph_gain_buf[2] = {nullptr, nullptr};
+    const uint16_t* ph_resp[2] = {nullptr, nullptr}; const uint16_t* ph_gain[2] = {nullptr, nullptr};
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
     explicit av_frontend(int S) : streams(S) {}
@@ -787,8 +792,8 @@ struct Span {
 // the engine-owned level 0 (AV_FE_CLAHE, pixel_format != AV_PIX_GRAY8) that goes with pyramid slot `slot`
 uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot * fe->d.S * fe->d.w * fe->d.h; }
 
-// The grey stages between the frames an entry point is handed and level 0, enqueued on st: [convert] -> [bin] -> [equalise], each
-// only if the engine was created with it.  This is the one place a stage is wired; the step paths (input_stage) and the frame
+// The grey stages between the frames an entry point is handed and level 0, enqueued on st: [convert] -> [photometric] -> [bin] ->
+// [equalise], each only if the engine was created with it.  This is the one place a stage is wired; the step paths (input_stage) and the frame
 // store's upload both come through here.
 //   raw        n groups of frames as handed over (fe->fmt, in_w x in_h).  Its map is null, unless the frames already lie in the
 //              entries of l0 (8-bit grey copied into the store): then it is l0 itself
@@ -796,7 +801,7 @@ uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot
 //              FAST read and write them through (every group, none negative)
 //   first      the list of the stage that first writes l0 (conversion or binning), or null: l0's list with -1 for every frame but
 //              the last of an entry named twice
-//   gray_full  the caller's full-size grey scratch, between conversion and binning when both are on
+//   gray_full  the caller's full-size grey scratch, ahead of the binning when a conversion or the photometric stage feeds it
 //   mosaic     the caller's 8-bit mosaic scratch, between the two passes of a packed mosaic's conversion (n frames per camera, no list)
 //   lut        the look-up tables of one equalisation
 // *level0 = the set the pyramid launch reads: l0 if any stage ran (fe->own_l0: the engine then owns level 0, which outlives the call
@@ -814,8 +819,15 @@ int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, 
         if ((rc = av_launch_to_gray8(at, to, n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st, &mosaic))) return rc;
         at = to;
     }
+    if (fe->photo) {
+        // after a conversion: in place on its target, through the list that target was written through (`first` for l0, none for
+        // gray_full); without one: out of the raw frames, which are the caller's and are never written
+        const FrameSet& to = conv ? at : bin ? gray_full : l0_first;
+        if ((rc = av_launch_photometric(at, to, n, fe->in_w, fe->in_h, fe->ph_resp[0], fe->ph_resp[1], fe->ph_gain[0], fe->ph_gain[1], st))) return rc;
+        at = to;
+    }
     if (bin && (rc = av_launch_downscale(at, l0_first, n, fe->in_w, fe->in_h, fe->ds, st))) return rc;
-    if (conv || bin) at = l0;
+    if (conv || bin || fe->photo) at = l0;
     if (fe->clahe) {
         if ((rc = av_launch_clahe(at, l0, n, fe->d.w, fe->d.h, c.clahe_clip_limit, c.clahe_tiles_x, c.clahe_tiles_y, lut, st))) return rc;
         at = l0;
@@ -1113,9 +1125,11 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     }
     fe->fmt = cfg->pixel_format; fe->fmt_shift = cfg->gray16_shift;
     fe->ds = ds; fe->in_w = in_w; fe->in_h = in_h; fe->frame_bytes = av_pixfmt_frame_bytes(fe->fmt, in_w, in_h);
-    fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8 || ds > 1;
+    fe->photo = (cfg->flags & AV_FE_PHOTOMETRIC) != 0;
+    fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8 || ds > 1 || fe->photo;
     if (fe->own_l0) A(fe->eq, (size_t)3 * S * w * h)
-    if (ds > 1 && fe->fmt != AV_PIX_GRAY8) A(fe->gray_full, (size_t)2 * S * in_w * in_h)
+    if (ds > 1 && (fe->fmt != AV_PIX_GRAY8 || fe->photo)) A(fe->gray_full, (size_t)2 * S * in_w * in_h)
+    if (fe->photo) A(fe->ph_resp_buf, 2 * 256)
     if (av_pixfmt_packed_depth(fe->fmt) && av_pixfmt_is_bayer(fe->fmt)) A(fe->mosaic, (size_t)2 * S * in_w * in_h)
     if (clahe) {
         A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
@@ -1206,6 +1220,14 @@ AV_EXPORT int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_
     return AV_OK;
 }
 
+// AV_FE_PHOTOMETRIC: an engine with the flag takes no frame before it has its tables
+static int photo_ready(const av_frontend* fe, const char* who)
+{
+    if (!fe->photo || fe->photo_set) return AV_OK;
+    av_set_error("%s: the engine was created with AV_FE_PHOTOMETRIC but has no tables yet: call av_frontend_set_photometric first", who);
+    return AV_E_INVALID;
+}
+
 // The pyramids of the images the NEXT av_frontend_step will get, enqueued now (behind the step just enqueued): that step then starts
 // with its tracking launch.  Same kernels, same slots, same results -- only their place in the stream moves.  A caller that hands a
 // step's feature message to the batched filter AFTER this call (av_msckf_batch_submit_dev copies it on this stream) starts the
@@ -1216,6 +1238,7 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
 {
     if (!fe || !img0_dev || !img1_dev || img_stride < fe->frame_bytes) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
+    if (photo_ready(fe, "av_frontend_prestage")) return AV_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
     bool wrote_l0 = true;
@@ -1236,6 +1259,7 @@ AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const u
         av_set_error("av_frontend_step: bad arguments");
         return AV_E_INVALID;
     }
+    if (photo_ready(fe, "av_frontend_step")) return AV_E_INVALID;
     return step_impl(fe, img0_dev, img1_dev, img_stride, timestamps, (hipStream_t)stream, (fe->cfg.flags & AV_FE_INPUTS_PERSIST) != 0);
 }
 
@@ -1246,6 +1270,7 @@ AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, c
         av_set_error("av_frontend_step_host: bad arguments");
         return AV_E_INVALID;
     }
+    if (photo_ready(fe, "av_frontend_step_host")) return AV_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t img_bytes = (size_t)fe->frame_bytes;                  // the staging slots carry the frames in their own format and size
     const int S = fe->d.S;
@@ -1316,6 +1341,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     }
     av_frontend::FrameStore& fs = fe->fs;
     if (!fs.n_slots) { av_set_error("av_frontend_frames_upload: no frame store (av_frontend_frames_reserve first)"); return AV_E_INVALID; }
+    if (photo_ready(fe, "av_frontend_frames_upload")) return AV_E_INVALID;
     if (n == 0) return AV_OK;
     for (int i = 0; i < n; ++i)
         if (slots[i] < 0 || slots[i] >= fs.n_slots) { av_set_error("av_frontend_frames_upload: entry %d outside the store (%d entries)", slots[i], fs.n_slots); return AV_E_INVALID; }
@@ -1330,7 +1356,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     const FeDev& d = fe->d;
     const size_t hw = (size_t)d.w * d.h;
     const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
-    const bool raw = conv || bin;                                   // the frames go through a kernel on their way into the store
+    const bool raw = conv || bin || fe->photo;                      // the frames go through a kernel on their way into the store
     const size_t in_hw = (size_t)fe->in_w * fe->in_h;
     const size_t fb = (size_t)fe->frame_bytes;                           // bytes of one camera's frame as the caller hands it over
     av_frontend::FrameStore::Up& u = fs.up[fs.up_next];
@@ -1349,7 +1375,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     }
     // grows only.  Earlier uploads' launches on the copy stream may still read the old scratch, so the copy stream is drained before it is
     // freed: the caller stalls once per growth (an upload larger than any before it), never otherwise
-    if (conv && bin && (size_t)n > fs.gray_cap) {
+    if ((conv || fe->photo) && bin && (size_t)n > fs.gray_cap) {
         if (fs.gray_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.gray_d); fs.gray_d = nullptr; fs.gray_cap = 0; }
         AV_HIP(hipMalloc((void**)&fs.gray_d, ((size_t)n + 16) * 2 * in_hw));
         fs.gray_cap = (size_t)n + 16;
@@ -1541,7 +1567,7 @@ AV_EXPORT int av_frontend_read_ransac_counts(av_frontend* fe, int stream_idx, in
 AV_EXPORT int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, uint8_t* out_host, void* stream)
 {
     if (!fe || stream_idx < 0 || stream_idx >= fe->d.S || cam < 0 || cam > 1 || !out_host) { av_set_error("av_frontend_read_image: bad arguments"); return AV_E_INVALID; }
-    if (!fe->own_l0) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE, with 8-bit grey input and without image_downscale: level 0 is the caller's own image"); return AV_E_INVALID; }
+    if (!fe->own_l0) { av_set_error("av_frontend_read_image: the engine was created without AV_FE_CLAHE or AV_FE_PHOTOMETRIC, with 8-bit grey input and without image_downscale: level 0 is the caller's own image"); return AV_E_INVALID; }
     if (!fe->stepped) { av_set_error("av_frontend_read_image: no step has run yet"); return AV_E_INVALID; }
     if (cam == 1 && fe->pre_on && !fe->stepped_frames) {
         av_set_error("av_frontend_read_image: the cam1 image of the last step has been replaced by av_frontend_prestage (read it before prestaging)");
@@ -1605,6 +1631,72 @@ AV_EXPORT int av_frontend_read_mask(av_frontend* fe, int cam, uint8_t* out_host)
     if (!m) { av_set_error("av_frontend_read_mask: no mask is set for camera %d", cam); return AV_E_INVALID; }
     AV_HIP(hipSetDevice(fe->device));
     AV_HIP(hipMemcpy(out_host, m, (size_t)fe->d.w * fe->d.h, hipMemcpyDeviceToHost));
+    return AV_OK;
+}
+
+// ---- photometric calibration ("Photometric calibration" in include/airvision.h) ----------------------------------------------
+AV_EXPORT int av_frontend_set_photometric(av_frontend* fe, const uint16_t* response0_host, const uint16_t* gain0_host,
+                                          const uint16_t* response1_host, const uint16_t* gain1_host)
+{
+    if (!fe) { av_set_error("av_frontend_set_photometric: bad arguments"); return AV_E_INVALID; }
+    if (!fe->photo) { av_set_error("av_frontend_set_photometric: the engine was created without AV_FE_PHOTOMETRIC"); return AV_E_INVALID; }
+    if (fe->fed) {
+        av_set_error("av_frontend_set_photometric: the engine has already been handed a frame (step, prestage or frames_upload): the frames in it "
+                     "would disagree with the new tables; set the tables of an engine before its first frame");
+        return AV_E_INVALID;
+    }
+    const uint16_t* resp[2] = {response0_host, response1_host};
+    const uint16_t* gain[2] = {gain0_host, gain1_host};
+    for (int cam = 0; cam < 2; ++cam)
+        for (int i = 0; resp[cam] && i < 256; ++i)
+            if (resp[cam][i] > AV_PHOTOMETRIC_RESPONSE_MAX) {
+                av_set_error("av_frontend_set_photometric: response%d[%d] = %d is above %d (255 in Q8)", cam, i, (int)resp[cam][i], AV_PHOTOMETRIC_RESPONSE_MAX);
+                return AV_E_INVALID;
+            }
+    AV_HIP(hipSetDevice(fe->device));
+    const size_t in_hw = (size_t)fe->in_w * fe->in_h;
+    // a camera without either part gets the identity response, so that one stage serves both cameras (with no part at all: the
+    // identity stage).  The engine has no tables while the copies run: a call that fails half way leaves it refusing frames, not
+    // holding half of the new tables
+    fe->photo_set = false;
+    for (int cam = 0; cam < 2; ++cam) { fe->ph_resp[cam] = nullptr; fe->ph_gain[cam] = nullptr; }
+    uint16_t ident[256];
+    for (int i = 0; i < 256; ++i) ident[i] = (uint16_t)(i << 8);
+    const uint16_t* new_resp[2] = {nullptr, nullptr};
+    const uint16_t* new_gain[2] = {nullptr, nullptr};
+    for (int cam = 0; cam < 2; ++cam) {
+        const bool bare = !resp[cam] && !gain[cam];
+        const uint16_t* r = resp[cam] ? resp[cam] : bare ? ident : nullptr;
+        if (r) {
+            AV_HIP(hipMemcpy(fe->ph_resp_buf + 256 * cam, r, sizeof(ident), hipMemcpyHostToDevice));
+            new_resp[cam] = fe->ph_resp_buf + 256 * cam;
+        }
+        if (gain[cam]) {
+            int rc;
+            if (!fe->ph_gain_buf[cam] && (rc = dev_alloc(fe, &fe->ph_gain_buf[cam], in_hw))) return rc;
+            AV_HIP(hipMemcpy(fe->ph_gain_buf[cam], gain[cam], in_hw * sizeof(uint16_t), hipMemcpyHostToDevice));
+            new_gain[cam] = fe->ph_gain_buf[cam];
+        }
+    }
+    for (int cam = 0; cam < 2; ++cam) { fe->ph_resp[cam] = new_resp[cam]; fe->ph_gain[cam] = new_gain[cam]; }
+    fe->photo_set = true;
+    return AV_OK;
+}
+
+AV_EXPORT int av_frontend_read_photometric(av_frontend* fe, int cam, uint16_t* response_out_host, uint16_t* gain_out_host)
+{
+    if (!fe || cam < 0 || cam > 1) { av_set_error("av_frontend_read_photometric: bad arguments"); return AV_E_INVALID; }
+    if (!fe->photo || !fe->photo_set) { av_set_error("av_frontend_read_photometric: no tables are set (AV_FE_PHOTOMETRIC and av_frontend_set_photometric)"); return AV_E_INVALID; }
+    AV_HIP(hipSetDevice(fe->device));
+    const size_t in_hw = (size_t)fe->in_w * fe->in_h;
+    if (response_out_host) {
+        if (fe->ph_resp[cam]) AV_HIP(hipMemcpy(response_out_host, fe->ph_resp[cam], 256 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        else for (int i = 0; i < 256; ++i) response_out_host[i] = (uint16_t)(i << 8);
+    }
+    if (gain_out_host) {
+        if (fe->ph_gain[cam]) AV_HIP(hipMemcpy(gain_out_host, fe->ph_gain[cam], in_hw * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        else for (size_t i = 0; i < in_hw; ++i) gain_out_host[i] = 4096;
+    }
     return AV_OK;
 }
 

@@ -1,0 +1,190 @@
+// photometric.hip -- photometric calibration of 8-bit grey frames: inverse response table and vignette gain map (gfx950).
+// The arithmetic is written out in include/airvision.h ("Photometric calibration"); tests/photometric_ref.py states it in NumPy and the
+// kernel is held to it bit for bit:
+//     out = min(255, (response[p] * gain[x] + (1 << 19)) >> 20)        response Q8 (absent: p << 8), gain Q12 (absent: 4096)
+// A pure streaming pass shaped like to_gray8_kernel (pixfmt.hip): an image is one run of w * h pixels, a workgroup takes PH_BLOCK.
+//   aligned body   bases, applied strides and the gain base are whole 16-byte vectors: a lane takes 16 pixels -- one uint4 of pixels and
+//                  two uint4 of gains in, 16 table look-ups, one uint4 out
+//   byte-wise      the ragged last 1 .. 15 pixels of an image, and every pixel of a launch whose addresses or strides are not whole
+//                  vectors: one pixel per lane and round, neighbouring lanes on neighbouring pixels
+// The 512-byte response table of the workgroup's camera is staged into LDS once per workgroup (256 lanes, one entry each).
+// In place (src == dst, same list) is correct: a lane reads its own pixels before it writes them and no lane reads another's.
+// Workgroup order: image-minor (id = block * n_img + image).  The gain map is one per camera for ALL images of a launch, so the
+// workgroups in flight at any time read the same few KB of it from L2 while the pixels stream; with the image-major order of
+// pixfmt.hip every image would walk the whole map (4.6 MB per camera at 1920 x 1200, more than one L2) on its own.
+// All byte offsets are 64-bit.
+#include "av_common.h"
+
+namespace {
+
+constexpr int PH_LANE = 16;                    // pixels of one lane = one 16-byte store
+constexpr int PH_BLOCK = 256 * PH_LANE;        // pixels of one workgroup
+
+struct PhArgs {
+    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
+    uint8_t* dst0; uint8_t* dst1;
+    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
+    int n_src;                                     // 1 or 2
+    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
+    int src_listed;                                // the source lies in entries too (in place in a listed set): read at index[g] as well
+    int n_img, npix;
+    int vec;                                       // every base (the gains' too), and every stride that is applied, is a whole 16-byte vector
+    const uint16_t* resp0; const uint16_t* resp1;  // [256] Q8 per camera
+    const uint16_t* gain0; const uint16_t* gain1;  // [npix] Q12 per camera
+};
+
+__device__ __forceinline__ uint32_t ph_out(uint32_t r, uint32_t g) { return min(255u, (r * g + (1u << 19)) >> 20); }      // r <= 65280: r * g + 2^19 < 2^32
+
+template <bool HAS_RESPONSE, bool HAS_GAIN>
+__global__ __launch_bounds__(256) void photometric_kernel(PhArgs a)
+{
+    __shared__ uint16_t tab[256];
+    const int blk = blockIdx.x / a.n_img, img = blockIdx.x - blk * a.n_img;
+    const int cam = img % a.n_src, g = img / a.n_src;
+    const int64_t e = a.index ? a.index[g] : g;
+    if (e < 0) return;
+    const uint8_t* src = (cam ? a.src1 : a.src0) + (a.src_listed ? e : (int64_t)g) * a.src_stride;
+    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
+    const uint16_t* gain = cam ? a.gain1 : a.gain0;
+    const int tid = threadIdx.x;
+    if (HAS_RESPONSE) {
+        tab[tid] = (cam ? a.resp1 : a.resp0)[tid];
+        __syncthreads();
+    }
+    auto resp = [&](uint32_t p) -> uint32_t { return HAS_RESPONSE ? (uint32_t)tab[p] : p << 8; };
+    const int p0 = blk * PH_BLOCK;                                // < 2^24
+    if (a.vec) {
+        const int p = p0 + tid * PH_LANE;
+        if (p + PH_LANE <= a.npix) {
+            const uint4 q = *reinterpret_cast<const uint4*>(src + p);
+            const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+            uint32_t gw[8];
+            if (HAS_GAIN) {
+                const uint4* gp = reinterpret_cast<const uint4*>(gain + p);
+                const uint4 g0 = gp[0], g1 = gp[1];
+                gw[0] = g0.x; gw[1] = g0.y; gw[2] = g0.z; gw[3] = g0.w; gw[4] = g1.x; gw[5] = g1.y; gw[6] = g1.z; gw[7] = g1.w;
+            }
+            uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < PH_LANE; ++k) {
+                const uint32_t px = (d[k >> 2] >> (8 * (k & 3))) & 255u;
+                const uint32_t gk = HAS_GAIN ? (gw[k >> 1] >> (16 * (k & 1))) & 0xFFFFu : 4096u;
+                o[k >> 2] |= ph_out(resp(px), gk) << (8 * (k & 3));
+            }
+            *reinterpret_cast<uint4*>(dst + p) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+            for (int k = p; k < a.npix; ++k) dst[k] = (uint8_t)ph_out(resp(src[k]), HAS_GAIN ? (uint32_t)gain[k] : 4096u);      // the image's ragged end: one lane, < 16 pixels
+        }
+        return;
+    }
+#pragma unroll 4
+    for (int j = 0; j < PH_LANE; ++j) {
+        const int p = p0 + j * 256 + tid;
+        if (p < a.npix) dst[p] = (uint8_t)ph_out(resp(src[p]), HAS_GAIN ? (uint32_t)gain[p] : 4096u);
+    }
+}
+
+// the one rule that picks the body (av_launch_photometric; av_photometric_vector_path reports it)
+bool ph_vector_ok(const FrameSet& src, const FrameSet& dst, int n_groups, const uint16_t* gain0, const uint16_t* gain1)
+{
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    return av_frames_vec16(src, dst, n_groups) && al16(gain0) && al16(gain1);
+}
+
+int ph_launch(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
+              const uint16_t* gain0, const uint16_t* gain1, hipStream_t st)
+{
+    PhArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
+    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.src_listed = src.map != nullptr; a.n_img = n_groups * a.n_src; a.npix = w * h;
+    a.resp0 = resp0; a.resp1 = resp1; a.gain0 = gain0; a.gain1 = gain1;
+    a.vec = ph_vector_ok(src, dst, n_groups, gain0, gain1);
+    const int per = (a.npix + PH_BLOCK - 1) / PH_BLOCK;
+    if ((int64_t)per * a.n_img > 0x7FFFFFFFll) { av_set_error("av_photometric: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
+    const dim3 grid((unsigned)(per * a.n_img)), block(256);
+    if (resp0 && gain0) hipLaunchKernelGGL((photometric_kernel<true, true>), grid, block, 0, st, a);
+    else if (resp0) hipLaunchKernelGGL((photometric_kernel<true, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((photometric_kernel<false, true>), grid, block, 0, st, a);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+}  // namespace
+
+int av_launch_photometric(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
+                          const uint16_t* gain0, const uint16_t* gain1, hipStream_t st)
+{
+    if (n_groups <= 0) return AV_OK;
+    if (src.map && src.map != dst.map) { av_set_error("av_photometric: a listed source is read through the destination's list"); return AV_E_INVALID; }
+    const bool two = src.base[1] != nullptr;
+    if (!two) {
+        if (!resp0 && !gain0) { av_set_error("av_photometric: neither a response table nor a gain map"); return AV_E_INVALID; }
+        return ph_launch(src, dst, n_groups, w, h, resp0, nullptr, gain0, nullptr, st);
+    }
+    if ((resp0 != nullptr) == (resp1 != nullptr) && (gain0 != nullptr) == (gain1 != nullptr)) {      // both cameras have the same parts: one launch
+        if (!resp0 && !gain0) { av_set_error("av_photometric: neither a response table nor a gain map"); return AV_E_INVALID; }
+        return ph_launch(src, dst, n_groups, w, h, resp0, resp1, gain0, gain1, st);
+    }
+    // the cameras differ in which parts they have: one launch per camera, each with its own kernel (a camera with neither part is
+    // the identity: copied if it is not in place)
+    const uint16_t* resp[2] = {resp0, resp1};
+    const uint16_t* gain[2] = {gain0, gain1};
+    for (int cam = 0; cam < 2; ++cam) {
+        const FrameSet s1{{src.base[cam], nullptr}, src.stride, src.map}, d1{{dst.base[cam], nullptr}, dst.stride, dst.map};
+        if (resp[cam] || gain[cam]) {
+            const int rc = ph_launch(s1, d1, n_groups, w, h, resp[cam], nullptr, gain[cam], nullptr, st);
+            if (rc) return rc;
+        } else if (src.base[cam] != dst.base[cam] || src.stride != dst.stride) {
+            av_set_error("av_photometric: a camera without tables next to one with tables is only taken in place");
+            return AV_E_INVALID;
+        }
+    }
+    return AV_OK;
+}
+
+static int ph_check(const char* who, const void* in_dev, const void* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride, bool quiet)
+{
+    if (w <= 0 || h <= 0 || (int64_t)w * h > AV_MAX_IMAGE_PIXELS) {
+        if (!quiet) av_set_error("%s: w * h must be 1 .. AV_MAX_IMAGE_PIXELS = 2^24 (%d x %d)", who, w, h);
+        return AV_E_INVALID;
+    }
+    const int64_t npix = (int64_t)w * h;
+    if (!in_dev || !out_dev || n < 0 || in_stride < npix || out_stride < npix) {
+        if (!quiet) av_set_error("%s: bad arguments (n %d, strides %lld / %lld bytes for %d x %d)", who, n, (long long)in_stride, (long long)out_stride, w, h);
+        return AV_E_INVALID;
+    }
+    return AV_OK;
+}
+
+AV_EXPORT int av_photometric(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                             const uint16_t* response_dev, const uint16_t* gain_dev, void* stream)
+{
+    int rc = ph_check("av_photometric", in_dev, out_dev, n, w, h, in_stride, out_stride, false);
+    if (rc) return rc;
+    if (!response_dev && !gain_dev) { av_set_error("av_photometric: neither a response table nor a gain map (both null)"); return AV_E_INVALID; }
+    if (n == 0) return AV_OK;
+    const int64_t npix = (int64_t)w * h;
+    const bool in_place = in_dev == out_dev && (n == 1 || in_stride == out_stride);      // (one image applies no stride)
+    if (!in_place && av_spans_overlap(in_dev, in_stride, npix, out_dev, out_stride, npix, n)) {
+        av_set_error("av_photometric: out_dev overlaps the input without being the input itself (in place needs the same address and stride)");
+        return AV_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (response_dev) {                            // an entry above 65280 would overflow the 32-bit product: checked here, once per call (blocking for 512 bytes)
+        uint16_t tab[256];
+        AV_HIP(hipMemcpyAsync(tab, response_dev, sizeof(tab), hipMemcpyDeviceToHost, st));
+        AV_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < 256; ++i)
+            if (tab[i] > AV_PHOTOMETRIC_RESPONSE_MAX) { av_set_error("av_photometric: response[%d] = %d is above %d (255 in Q8)", i, (int)tab[i], AV_PHOTOMETRIC_RESPONSE_MAX); return AV_E_INVALID; }
+    }
+    return av_launch_photometric(av_frames(in_dev, nullptr, in_stride), FrameSet{{out_dev, nullptr}, out_stride, nullptr}, n, w, h,
+                                 response_dev, nullptr, gain_dev, nullptr, st);
+}
+
+AV_EXPORT int av_photometric_vector_path(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                                         const uint16_t* response_dev, const uint16_t* gain_dev)
+{
+    if (ph_check("av_photometric_vector_path", in_dev, out_dev, n, w, h, in_stride, out_stride, true) || n == 0 || (!response_dev && !gain_dev)) return 0;
+    return ph_vector_ok(av_frames(in_dev, nullptr, in_stride), av_frames(out_dev, nullptr, out_stride), n, gain_dev, nullptr) ? 1 : 0;
+}

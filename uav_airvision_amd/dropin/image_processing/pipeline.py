@@ -27,6 +27,7 @@ class ImageProcessingPipeline(object):
         # config.use_clahe (no counterpart in the reference): the engine equalises every frame ahead of everything else; a viewer set
         # here is shown the image the front-end actually worked on (update_image, the hook of viewer.py:45-49)
         # config.image_downscale 2 / 4: the callbacks still take full-size frames; the same hook shows the binned frame
+        # config.cam*_response / cam*_vignette: the engine reads them from the config object; the same hook shows the corrected frame
         self.use_clahe = bool(getattr(config, 'use_clahe', False))
         self.downscale = self._engine.downscale
         self.viewer = None
@@ -59,7 +60,7 @@ class ImageProcessingPipeline(object):
         self.prev_cam0_msg = cam0_msg
         self.prev_pyr0 = cam0_msg.image
         self.first_frame = False
-        if (self.use_clahe or self.downscale > 1) and self.viewer is not None:
+        if (self.use_clahe or self.downscale > 1 or self._engine.photometric) and self.viewer is not None:
             self.viewer.update_image(self.equalized_image(0))
         return _feature_msg(cam0_msg.timestamp, feats)
 

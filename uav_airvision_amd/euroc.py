@@ -425,7 +425,7 @@ def encode_frame(image, pixel_format='gray8', gains=BAYER_GAINS, shift=8):
 
 
 def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None, write_csv=True, compress_level=6, pixel_format='gray8',
-                       bayer_gains=BAYER_GAINS, gray16_shift=8):
+                       bayer_gains=BAYER_GAINS, gray16_shift=8, vignette=None):
     """Write a seeded synthetic stream (uav_airvision_amd.synth.SyntheticStream) as an EuRoC-layout directory
     `root/mav0/{cam0,cam1}/data/<ns>.png`, `imu0/data.csv`, `state_groundtruth_estimate0/data.csv`, so that the same
     reader / replay / sweep code that runs on the real dataset (which is not redistributable and not present on the build
@@ -434,7 +434,9 @@ def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None
     `frame_range=(a, b)` writes only the images of frames a..b-1 (several writer processes can share one sequence);
     `write_csv=False` skips the IMU / ground-truth files; `compress_level` is zlib's (any level is lossless; 1 writes 5x faster).
     `pixel_format` 'gray16' / 'rgb8' / 'rgba8' writes the same frames as 16-bit grey / RGB / RGBA PNGs (encode_frame); a Bayer name
-    writes the raw mosaic of the frames coloured by `bayer_gains` as 8- or 16-bit grey PNGs (16-bit samples << `gray16_shift`)."""
+    writes the raw mosaic of the frames coloured by `bayer_gains` as 8- or 16-bit grey PNGs (16-bit samples << `gray16_shift`).
+    `vignette` = (V0, V1) or (V0, V1, response_forward): every frame of cam0 / cam1 is degraded with frontend.apply_vignette before it is
+    encoded (what a vignetting lens and a non-linear sensor would have recorded); None writes the frames as they are."""
     from PIL import Image
     from . import _native as N
     if pixel_format in N.PACKED_FORMATS:
@@ -443,14 +445,19 @@ def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None
     if pixel_format not in ('gray8', 'gray16', 'rgb8', 'rgba8') and not bayer:
         raise ValueError('write_euroc_layout: PNG holds gray8, gray16, rgb8 or rgba8 frames or a Bayer mosaic, not %r' % (pixel_format,))
     enc = (lambda im: encode_frame(im, pixel_format, bayer_gains, gray16_shift)) if bayer else (lambda im: encode_frame(im, pixel_format))
+    deg0 = deg1 = (lambda im: im)
+    if vignette is not None:
+        from .frontend import apply_vignette
+        forward = vignette[2] if len(vignette) > 2 else None
+        deg0, deg1 = (lambda im: apply_vignette(im, vignette[0], forward)), (lambda im: apply_vignette(im, vignette[1], forward))
     for cam in ('cam0', 'cam1'):
         os.makedirs(os.path.join(root, 'mav0', cam, 'data'), exist_ok=True)
     a, b = (0, stream.n_frames) if frame_range is None else frame_range
     for k in range(a, b):
         m = stream.frame(k)
         name = '%d.png' % int(round(m.timestamp * 1e9))
-        Image.fromarray(enc(m.cam0_image)).save(os.path.join(root, 'mav0', 'cam0', 'data', name), compress_level=compress_level)
-        Image.fromarray(enc(m.cam1_image)).save(os.path.join(root, 'mav0', 'cam1', 'data', name), compress_level=compress_level)
+        Image.fromarray(enc(deg0(m.cam0_image))).save(os.path.join(root, 'mav0', 'cam0', 'data', name), compress_level=compress_level)
+        Image.fromarray(enc(deg1(m.cam1_image))).save(os.path.join(root, 'mav0', 'cam1', 'data', name), compress_level=compress_level)
     if not write_csv:
         return root
     os.makedirs(os.path.join(root, 'mav0', 'imu0'), exist_ok=True)

@@ -247,6 +247,111 @@ def check_mask(cam, mask, height, width):
     return np.ascontiguousarray(a).astype(np.uint8, copy=False)
 
 
+def quantise_response(response):
+    """The inverse response G^-1 (256 values in [0, 255]) as the engine's table: uint16[256] in Q8, floor(clip(U, 0, 255) * 256 + 0.5) in
+    float64, so every entry is <= 65280."""
+    u = np.asarray(response, dtype=np.float64).reshape(-1)
+    if u.shape != (256,):
+        raise ValueError('response: 256 numbers in [0, 255] are wanted, got %d' % u.size)
+    if not np.isfinite(u).all():
+        raise ValueError('response: entry %d is not finite (%r)' % (int(np.flatnonzero(~np.isfinite(u))[0]), float(u[~np.isfinite(u)][0])))
+    return np.floor(np.clip(u, 0.0, 255.0) * 256.0 + 0.5).astype(np.uint16)
+
+
+def quantise_vignette(vignette):
+    """The vignette map V(x) in (0, 1] as the engine's gain map: uint16 [h, w] in Q12, min(65535, floor(4096 / V + 0.5)) in float64;
+    V <= 0 (and a NaN) gives 65535.  Gains of 16 and above saturate at 15.9998."""
+    v = np.asarray(vignette, dtype=np.float64)
+    if v.ndim != 2 or v.size == 0:
+        raise ValueError('vignette: a float array of shape (height, width) is wanted, got %s' % (tuple(v.shape),))
+    ok = v > 0
+    g = np.full(v.shape, 65535.0)
+    g[ok] = np.minimum(65535.0, np.floor(4096.0 / v[ok] + 0.5))
+    return g.astype(np.uint16)
+
+
+def read_response_file(path):
+    """A pcalib.txt-style text file: 256 numbers separated by white space (one line in the TUM mono-VO dataset), the inverse response
+    G^-1 with values in [0, 255]."""
+    with open(os.fspath(path)) as f:
+        vals = f.read().split()
+    try:
+        u = np.array([float(v) for v in vals], np.float64)
+    except ValueError:
+        raise ValueError('response: %s holds something that is no number' % (path,))
+    if u.shape != (256,):
+        raise ValueError('response: %s holds %d numbers, 256 are wanted' % (path, u.size))
+    return u
+
+
+def read_vignette_png(path):
+    """A vignette.png of the TUM mono-VO convention: a 16-bit grey PNG (decoded by the library's own av_png_decode), normalised by its
+    maximum -> float64 [h, w] in [0, 1]."""
+    path = os.fspath(path)
+    w, h, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if N.lib().av_png_probe(os.fsencode(path), C.byref(w), C.byref(h), C.byref(f)) != 0:
+        raise ValueError('vignette: %s: %s' % (path, N.lib().av_last_error().decode('utf-8', 'replace')))
+    if int(f.value) != N.AV_PIX_GRAY16:
+        raise ValueError('vignette: %s: a 16-bit grey PNG is wanted, got %s' % (path, N.PIXEL_FORMAT_NAMES.get(int(f.value), 'an undecodable flavour')))
+    out = np.empty((int(h.value), int(w.value)), np.uint16)
+    paths = (C.c_char_p * 1)(os.fsencode(path))
+    status = (C.c_int32 * 1)()
+    N.check(N.lib().av_png_decode(paths, 1, int(w.value), int(h.value), N.AV_PIX_GRAY16, out.ctypes.data_as(C.c_void_p), out.nbytes, 1, status))
+    top = int(out.max())
+    if top == 0:
+        raise ValueError('vignette: %s is all zero' % path)
+    return out.astype(np.float64) / float(top)
+
+
+def photometric_tables(response=None, vignette=None):
+    """The photometric calibration of one camera as the engine's integer tables ("Photometric calibration" in include/airvision.h):
+    (response_u16 or None, gain_u16 or None).  response: the inverse response G^-1, 256 floats in [0, 255], or the path of a
+    pcalib.txt-style text file of 256 numbers -> uint16[256] in Q8 (quantise_response).  vignette: V(x), an [h, w] float array with
+    values in (0, 1], or the path of a 16-bit grey PNG, normalised by its maximum as TUM does -> uint16 [h, w] in Q12
+    (quantise_vignette).  The quantisation happens here, once, on the host, in float64; everything after it is integer."""
+    r = g = None
+    if response is not None:
+        r = quantise_response(read_response_file(response) if isinstance(response, (str, os.PathLike)) else response)
+    if vignette is not None:
+        g = quantise_vignette(read_vignette_png(vignette) if isinstance(vignette, (str, os.PathLike)) else vignette)
+    return r, g
+
+
+def apply_vignette(img_u8, vignette, response_forward=None):
+    """The forward model of a vignetting lens and a non-linear sensor, for synthesising degraded frames: round(G(img * V)) clipped to
+    0 .. 255, uint8 of img's shape.  vignette: V, float [h, w] in (0, 1] (broadcast against img [..., h, w]).  response_forward: G, the
+    sensor's response -- None (the identity), a callable on float64 arrays of irradiance in [0, 255], or 256 values G(0) .. G(255)
+    (interpolated linearly)."""
+    x = np.asarray(img_u8).astype(np.float64) * np.asarray(vignette, dtype=np.float64)
+    if callable(response_forward):
+        x = np.asarray(response_forward(x), dtype=np.float64)
+    elif response_forward is not None:
+        tab = np.asarray(response_forward, dtype=np.float64).reshape(-1)
+        if tab.shape != (256,):
+            raise ValueError('apply_vignette: response_forward is a callable or 256 values, got %d' % tab.size)
+        x = np.interp(x, np.arange(256.0), tab)
+    return np.clip(np.floor(x + 0.5), 0, 255).astype(np.uint8)
+
+
+def check_photometric(cam, response, gain, height, width):
+    """The integer tables of camera `cam` as C-contiguous uint16 arrays of the shapes the engine reads ([256], [height, width]), or None
+    for None.  Nothing is cast: a wrong dtype or shape is a ValueError naming the camera; so is a response entry above 65280."""
+    r = g = None
+    if response is not None:
+        r = np.asarray(response)
+        if r.dtype != np.uint16 or r.shape != (256,):
+            raise ValueError('cam%d response: a uint16 array of shape (256,) is wanted (photometric_tables makes one), got %s %s' % (cam, r.dtype, tuple(r.shape)))
+        if int(r.max()) > N.AV_PHOTOMETRIC_RESPONSE_MAX:
+            raise ValueError('cam%d response: entry %d is above %d (255 in Q8)' % (cam, int(r.max()), N.AV_PHOTOMETRIC_RESPONSE_MAX))
+        r = np.ascontiguousarray(r)
+    if gain is not None:
+        g = np.asarray(gain)
+        if g.dtype != np.uint16 or tuple(g.shape) != (int(height), int(width)):
+            raise ValueError('cam%d gain: a uint16 array of shape %s is wanted (photometric_tables makes one), got %s %s' % (cam, (int(height), int(width)), g.dtype, tuple(g.shape)))
+        g = np.ascontiguousarray(g)
+    return r, g
+
+
 COUNTER_NAMES = ('before_tracking', 'after_tracking', 'after_matching', 'n_fast', 'n_candidates', 'n_new',
                  'n_published', 'overflow')
 
@@ -281,7 +386,12 @@ class FrontendEngine(object):
         config.cam0_mask / config.cam1_mask (a config object without them has none): the static mask of each camera, for all streams
         -- None, a uint8 / bool array of shape (input_height, input_width) with non-zero = scene, or the path of an 8-bit grey PNG of
         that size; `set_masks` has the rules.  They are read here, so every owner of an engine (the drop-in ImageProcessor, EngineSet,
-        the sweep) gets them from its config object."""
+        the sweep) gets them from its config object.
+
+        config.cam0_response / cam1_response / cam0_vignette / cam1_vignette (a config object without them has none): the photometric
+        calibration of each camera, for all streams -- each None, an array or a path as `photometric_tables` takes them.  With any of
+        them the engine is created with AV_FE_PHOTOMETRIC and corrects every grey frame, G^-1(p) / V(x) in the integer arithmetic of
+        include/airvision.h, after the conversion to grey and ahead of binning and CLAHE; `set_photometric` has the rules."""
         self.config = config
         self.n_streams = int(n_streams)
         self.device = int(device)
@@ -290,6 +400,11 @@ class FrontendEngine(object):
         self._keep = None
         self._h = C.c_void_p()
         masks = [check_mask(cam, getattr(config, 'cam%d_mask' % cam, None), self._cfg.height, self._cfg.width) for cam in (0, 1)]      # before any device call
+        photo = [photometric_tables(getattr(config, 'cam%d_response' % cam, None), getattr(config, 'cam%d_vignette' % cam, None)) for cam in (0, 1)]
+        photo = [check_photometric(cam, r, g, self._cfg.height, self._cfg.width) for cam, (r, g) in enumerate(photo)]
+        self.photometric = any(t is not None for pair in photo for t in pair)
+        if self.photometric:
+            self._cfg.flags |= N.AV_FE_PHOTOMETRIC
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_create(C.byref(self._cfg), self.n_streams, self.device, C.byref(self._h)))
         self.max_features = N.lib().av_frontend_max_features(self._h)
@@ -298,12 +413,14 @@ class FrontendEngine(object):
         self._ids = np.zeros((S, cap), np.int64)
         self._uv = np.zeros((S, cap, 4), np.float64)
         self._n = np.zeros(S, np.int32)
-        if masks[0] is not None or masks[1] is not None:
-            try:
+        try:
+            if masks[0] is not None or masks[1] is not None:
                 self.set_masks(*masks)
-            except Exception:
-                self.close()
-                raise
+            if self.photometric:
+                self.set_photometric(photo[0][0], photo[0][1], photo[1][0], photo[1][1])
+        except Exception:
+            self.close()
+            raise
 
     def _set_sizes(self, cfg):
         """The sizes that follow from a packed configuration: input_* = the frames the entry points take, width / height = the image
@@ -405,6 +522,28 @@ class FrontendEngine(object):
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_mask(self._h, int(cam), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def set_photometric(self, response0=None, gain0=None, response1=None, gain1=None):
+        """The photometric tables of cam0 and cam1, shared by all streams (av_frontend_set_photometric; "Photometric calibration" in
+        include/airvision.h): response* uint16[256] in Q8, gain* uint16 [input_height, input_width] in Q12, as `photometric_tables`
+        returns them; each may be None = the identity for that part.  Blocking.  The engine must have been created with the
+        calibration switched on (one of the four config attributes set), and the call is accepted only before the engine's first
+        frame: otherwise AirvisionError, AV_E_INVALID.  A wrong dtype or shape, or a response entry above 65280, is a ValueError before
+        anything reaches the device."""
+        r0, g0 = check_photometric(0, response0, gain0, self.input_height, self.input_width)
+        r1, g1 = check_photometric(1, response1, gain1, self.input_height, self.input_width)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_set_photometric(self._h, ptr(r0), ptr(g0), ptr(r1), ptr(g1)))
+
+    def read_photometric(self, cam=0):
+        """The tables of camera `cam` the engine works with: (response uint16[256], gain uint16 [input_height, input_width]); a part that
+        was set as None reads back as the identity (p * 256, 4096).  Refused (AirvisionError, AV_E_INVALID) when none are set."""
+        r = np.empty(256, np.uint16)
+        g = np.empty((self.input_height, self.input_width), np.uint16)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_read_photometric(self._h, int(cam), r.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p)))
+        return r, g
 
     def frames_reserve(self, n_slots):
         """Allocate the shared frame store (av_frontend_frames_reserve): `n_slots` resident stereo frames."""
@@ -515,8 +654,9 @@ class FrontendEngine(object):
 
     def read_image(self, stream=0, cam=0):
         """The level-0 image the last step used for camera `cam` of `stream`, uint8[height, width] (the processed size): the frame
-        converted to 8-bit grey (config.image_format other than 'gray8'), binned (config.image_downscale 2 or 4), equalised with
-        config.use_clahe.  Refused (AirvisionError, AV_E_INVALID) with none of them: level 0 is then the caller's own image."""
+        converted to 8-bit grey (config.image_format other than 'gray8'), photometrically corrected (config.cam*_response /
+        cam*_vignette), binned (config.image_downscale 2 or 4), equalised with config.use_clahe.  Refused (AirvisionError,
+        AV_E_INVALID) with none of them: level 0 is then the caller's own image."""
         out = np.empty((self.height, self.width), np.uint8)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_image(self._h, int(stream), int(cam), out.ctypes.data_as(C.c_void_p), self._stream()))

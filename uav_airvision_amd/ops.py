@@ -366,3 +366,51 @@ def downscale(img, factor, out=None, device=0):
     with torch.cuda.device(device):
         N.check(N.lib().av_downscale(N.dptr(tb), in_stride, n, W, H, f, N.dptr(ob), out_stride, N.current_stream()))
     return out
+
+
+def photometric(images, response=None, gain=None, out=None, device=0):
+    """Photometric calibration of 8-bit grey frames (av_photometric; the arithmetic is written out in include/airvision.h):
+    out = min(255, (response[p] * gain[x] + 2^19) >> 20).  images: uint8 [n, h, w] or [h, w], a cuda tensor or anything torch.as_tensor
+    takes.  A cuda tensor is read where it lies: each image must be contiguous, the images may be any distance apart, at any address.
+    response: uint16[256] in Q8 (entries <= 65280) or None; gain: uint16 [h, w] in Q12, one map for all images, or None
+    (frontend.photometric_tables makes both); a cuda tensor (torch.uint16, or torch.int16 holding the same bits) is used where it lies.
+    At least one of the two.  Returns a uint8 cuda tensor of images' shape -- `out` itself if given (uint8 cuda, that shape, each image
+    contiguous); out may be the input itself (in place), any other overlap is refused."""
+    t = torch.as_tensor(images)
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3):
+        raise ValueError('photometric: images are torch.uint8 [n, h, w] or [h, w], got %s %s' % (t.dtype, tuple(t.shape)))
+    if response is None and gain is None:
+        raise ValueError('photometric: neither a response table nor a gain map')
+    t = t.to(_dev(device))
+    batched = t.dim() == 3
+    tb = t if batched else t.unsqueeze(0)
+    n, h, w = tb.shape
+    if (n and not tb[0].is_contiguous()) or (n > 1 and tb.stride(0) < h * w):
+        tb = tb.contiguous()
+
+    def table(a, what, shape):
+        if isinstance(a, torch.Tensor):
+            ok = a.dtype in tuple(d for d in (getattr(torch, 'uint16', None), torch.int16) if d is not None) and tuple(a.shape) == shape
+            if not ok or not a.is_cuda or not a.is_contiguous():
+                raise ValueError('photometric: %s is a contiguous uint16 cuda tensor of shape %s, got %s %s' % (what, shape, a.dtype, tuple(a.shape)))
+            return a
+        a = np.asarray(a)
+        if a.dtype != np.uint16 or tuple(a.shape) != shape:
+            raise ValueError('photometric: %s is uint16 %s, got %s %s' % (what, shape, a.dtype, tuple(a.shape)))
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(_dev(device))
+    r = None if response is None else table(response, 'response', (256,))
+    g = None if gain is None else table(gain, 'gain', (h, w))
+    oshape = tuple(t.shape)
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.uint8, device=_dev(device))
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == oshape):
+        raise ValueError('photometric: out must be a uint8 cuda tensor of shape %s' % (oshape,))
+    ob = out if batched else out.unsqueeze(0)
+    if (n and not ob[0].is_contiguous()) or (n > 1 and ob.stride(0) < h * w):
+        raise ValueError('photometric: every image of out must be contiguous')
+    in_stride = tb.stride(0) if n > 1 else h * w
+    out_stride = ob.stride(0) if n > 1 else h * w
+    with torch.cuda.device(device):
+        N.check(N.lib().av_photometric(N.dptr(tb), N.dptr(ob), n, w, h, in_stride, out_stride, None if r is None else N.dptr(r),
+                                       None if g is None else N.dptr(g), N.current_stream()))
+    return out

@@ -292,6 +292,14 @@ def make_parser():
                     help='static mask of cam0 for every stream: an 8-bit grey PNG of the frame size, 0 = never scene (outside a fisheye image circle, airframe in view), '
                          'anything else = scene (config.cam0_mask; default: none)')
     ap.add_argument('--mask1', metavar='PNG', default=None, help='the same for cam1 (config.cam1_mask)')
+    ap.add_argument('--response0', metavar='TXT', default=None,
+                    help='photometric calibration of cam0 for every stream: a pcalib.txt-style text file of 256 numbers in [0, 255], the inverse response G^-1 '
+                         '(config.cam0_response; default: none)')
+    ap.add_argument('--response1', metavar='TXT', default=None, help='the same for cam1 (config.cam1_response)')
+    ap.add_argument('--vignette0', metavar='PNG', default=None,
+                    help='vignette map of cam0 for every stream: a 16-bit grey PNG of the frame size, normalised by its maximum; every pixel is divided by it on the GPU '
+                         '(config.cam0_vignette; default: none)')
+    ap.add_argument('--vignette1', metavar='PNG', default=None, help='the same for cam1 (config.cam1_vignette)')
     ap.add_argument('--gray16-shift', type=int, default=None, metavar='N',
                     help='16-bit frames, grey or Bayer: sample = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
     return ap
@@ -316,6 +324,9 @@ def apply_args(cfg, args):
     for cam in (0, 1):                                         # (a mask already set on the config object stays unless the switch is given)
         if getattr(args, 'mask%d' % cam, None) is not None:
             setattr(cfg, 'cam%d_mask' % cam, getattr(args, 'mask%d' % cam))
+        for part in ('response', 'vignette'):                  # (a table already set on the config object stays unless the switch is given)
+            if getattr(args, '%s%d' % (part, cam), None) is not None:
+                setattr(cfg, 'cam%d_%s' % (cam, part), getattr(args, '%s%d' % (part, cam)))
     return cfg
 
 
@@ -386,6 +397,11 @@ def main(argv=None):
             rep['downscale'] = cfg.image_downscale
         if args.mask0 is not None or args.mask1 is not None:
             rep['masks'] = dict(mask0=args.mask0, mask1=args.mask1)
+        # every table the sweep ran with, from a switch or already on the config object: its file, or 'array' for one given as values
+        photo = {k: getattr(cfg, 'cam%s_%s' % (k[-1], k[:-1]), None) for k in ('response0', 'response1', 'vignette0', 'vignette1')}
+        photo = {k: (os.fspath(v) if isinstance(v, (str, os.PathLike)) else 'array') for k, v in photo.items() if v is not None}
+        if photo:
+            rep['photometric'] = photo
         print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
