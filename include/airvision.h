@@ -486,8 +486,8 @@ int av_clahe(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h
  *   colour to grey:  (9798 R + 19235 G + 3735 B + 16384) >> 15 in integer arithmetic.  The coefficients sum to 2^15, so R = G = B = g
  *                    gives g exactly and the result never exceeds 255.  Alpha is ignored.
  *   GRAY8:           the identity.
- * Not covered: 16-bit colour, cameras of two sizes or formats, percentile or auto-range scaling of 16-bit data (CLAHE after a fixed
- * shift is the answer for now).
+ * Not covered: 16-bit colour, cameras of two sizes or formats.  (A window or an automatic range instead of the shift: "Range scaling of
+ * 16-bit grey" below, AV_PIX_GRAY16 only.)
  *
  * Bayer mosaics: the raw colour-filter-array frame of a colour machine-vision camera, one sample per pixel.  A pattern is named by the
  * colours of the TOP-LEFT 2 x 2 block in reading order (OpenCV's BayerBG .. BayerGR name another corner: do not carry those names over).
@@ -595,6 +595,75 @@ int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_img, int w,
 /* Bytes of one tightly packed w x h frame of a pixel format: w * h * bytes per pixel, or w * h * d / 8 for a packed transport.  0 for an
  * unknown format, for w or h below 1, and for a packed width that is not whole groups.  Host only. */
 int64_t av_pixfmt_frame_bytes(int pixel_format, int w, int h);
+
+/* ---------------------------------------------------------------------------------------------
+ * Range scaling of 16-bit grey: a window (lo, hi) instead of the fixed shift of av_to_gray8, for sources whose signal does not fill its
+ * container -- a thermal core whose scene occupies a few hundred counts around a drifting offset, a machine-vision camera in low light.
+ * No counterpart in the reference; this text is the contract, tests/range16_ref.py states it in NumPy and frontend.gray16_range is the
+ * same arithmetic as product code.  AV_PIX_GRAY16 only.  Integer arithmetic throughout; every quantity fits an unsigned 32-bit register.
+ *   mapping   given 0 <= lo < hi <= 65535 and span = hi - lo:
+ *                 m   = ((255 << 16) + span / 2) / span          once per range, <= 255 << 16   (integer divisions)
+ *                 d   = min(max(v, lo), hi) - lo                 0 .. span
+ *                 out = min(255, (d * m + 32768) >> 16)
+ *             For every span in 1 .. 65535: out(lo) = 0, out(hi) = 255, out is monotone in v, d * m + 32768 < 2^24 + 2^16, and out is less
+ *             than one grey level from 255 d / span.  The formula is the definition, the exact quotient is not.
+ *   window    AV_GRAY16_WINDOW: one (lo, hi) for every image (config.gray16_window).  No reduction.
+ *   auto      AV_GRAY16_AUTO: every range GROUP gets its own (lo, hi) from a 4,096-bin histogram of v >> 4.
+ *     group     the two images of one stereo pair -- cam0 and cam1 of one stream-frame -- POOLED: stereo LK assumes the same brightness in
+ *               both views, so both images of a pair share one mapping.  av_to_gray8_range pools `pool` = 1 or 2 consecutive images.
+ *               The range depends on the group alone, never on a stream's past (the frame store converts a frame once for all the
+ *               offset streams that read it): there is no temporal damping.
+ *     N         the samples of the group, w * h * images.
+ *     clip      (ppm_lo, ppm_hi), default (100, 100): integers >= 0 whose sum is at most AV_GRAY16_MAX_CLIP_PPM = 500000, the share of
+ *               samples that may saturate at each end in parts per million.  k_lo = N * ppm_lo / 10^6 and k_hi = N * ppm_hi / 10^6
+ *               (integer division, 64 bits, on the host).
+ *     bins      b_lo = the smallest bin b with hist[0 .. b].sum() > k_lo; b_hi = the largest bin b with hist[b .. 4095].sum() > k_hi.
+ *               A cumulative count exactly equal to k moves on to the next bin.  k_lo + k_hi < N, so b_lo <= b_hi.
+ *     range     lo = 16 b_lo, hi = 16 b_hi + 15.
+ *     min span  min_span, default 256, 16 .. 65535 (with 256 no count becomes more than one grey level: a lens cap or an empty sky is
+ *               not turned into amplified noise).  If hi - lo < min_span:
+ *                 need = min_span - (hi - lo);  lo = max(0, min(lo - need / 2, 65535 - min_span));  hi = lo + min_span
+ *               The new range always contains the old one.
+ *   Histogram counts are integers added with integer atomics: the result does not depend on their order and is bit-identical from run
+ *   to run.
+ * The engine: av_frontend_set_gray16_scale(fe, scale, lo, hi, clip_lo_ppm, clip_hi_ppm, min_span) -- config.gray16_scale as
+ * AV_GRAY16_SHIFT / _WINDOW / _AUTO, config.gray16_window, config.gray16_auto_clip, config.gray16_auto_min_span; each is checked for the
+ * scale that reads it -- chooses the scale of an engine before its first frame, like av_frontend_set_masks (after a step, a prestage or
+ * an upload: AV_E_INVALID, the frames in the engine would disagree with the new scale).  av_frontend_config is unchanged, so a caller that
+ * never makes the call has the shift.  A scale other than AV_GRAY16_SHIFT needs pixel_format = AV_PIX_GRAY16 (any other format:
+ * AV_E_INVALID with both settings in the text; the Python engine refuses it when it is created) and replaces the shift conversion, at its
+ * place in the input chain, in all entry paths and in av_frontend_frames_upload; gray16_shift is then not read.  Everything downstream -- photometric calibration, binning,
+ * CLAHE, masks -- is unchanged, and av_frontend_read_image returns the grey frame the step used.  With AV_GRAY16_AUTO the engine owns a
+ * histogram and a record per stream (the frame store: per frame of one upload), allocated by that call and only then; the three launches go on the
+ * stream of the step (the copy stream for an upload), with no host wait and no read-back inside a step.  With AV_GRAY16_SHIFT nothing is
+ * launched and nothing more is allocated.
+ * av_frontend_read_range: int32 [n_streams][2], the (lo, hi) the frames of the last step were scaled with, for av_frontend_step (with or
+ * without persisting inputs, prestaged or not) and av_frontend_step_host.  AV_E_INVALID with text before the first step, after an
+ * av_frontend_step_frames (a store entry is shared by streams and keeps no range) and with AV_GRAY16_SHIFT.
+ * av_to_gray8_range: n_img images of w x h uint16 samples, image i at img_dev + i * img_stride_bytes, in groups of `pool` (1 or 2;
+ * n_img % pool == 0) consecutive images, to tightly packed u8.  index_dev (or null) is a device list of one int per GROUP: group g is
+ * written to the output images (index[g] * pool + c) * out_stride, c < pool; a negative entry skips the group -- no histogram, no range, no
+ * pixel -- and the caller names no entry twice (null: group g goes to entry g; with a list the overlap of input and output is the
+ * caller's to avoid).  range_dev (or null): int32 [n_img / pool][2], (lo, hi) of every group written.  AV_GRAY16_AUTO works in work_dev,
+ * AV_GRAY16_WORK_WORDS uint32 per group, ZERO before the first call and left zero in its histogram part by every call (records: the words
+ * behind the n_img / pool histograms of 4096); with work_dev null the operator allocates it for the call and waits for the stream before
+ * freeing it (it then blocks the host and cannot be captured into a graph).  Alignment as av_to_gray8: 16-byte aligned addresses and
+ * strides go as whole vectors, the ragged end and any other launch sample by sample.  AV_E_INVALID with text for a mode other than 1 or 2,
+ * a window outside 0 <= lo < hi <= 65535, a clip below 0 or above 500000 in sum, a minimum span outside 16 .. 65535 (each checked for the
+ * mode that reads it), pool other than 1 or 2, strides smaller than an image, and out_dev overlapping the input.
+ * Not covered: temporal damping of the range (see "group"); finer than 16-count granularity of lo and hi; 16-bit mosaics and packed
+ * transports; per-camera ranges; a region of interest for the statistics; fusion with the histograms CLAHE builds.
+ * ------------------------------------------------------------------------------------------- */
+#define AV_GRAY16_SHIFT  0
+#define AV_GRAY16_WINDOW 1
+#define AV_GRAY16_AUTO   2
+#define AV_GRAY16_MAX_CLIP_PPM 500000
+#define AV_GRAY16_WORK_WORDS 4100
+int av_to_gray8_range(const void* img_dev, int64_t img_stride_bytes, int n_img, int w, int h, int mode, int lo, int hi,
+                      int ppm_lo, int ppm_hi, int min_span, int pool, const int32_t* index_dev,
+                      uint8_t* out_dev, int64_t out_stride, int32_t* range_dev, uint32_t* work_dev, void* stream);
+int av_frontend_set_gray16_scale(av_frontend* fe, int scale, int lo, int hi, int clip_lo_ppm, int clip_hi_ppm, int min_span);
+int av_frontend_read_range(av_frontend* fe, int32_t* range_out_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Binning of 8-bit grey frames by f = 2 or 4.  No counterpart in the reference (other VIO stacks run their front-end on a reduced

@@ -23,6 +23,10 @@ AV_FE_CLAHE = 4
 AV_FE_PHOTOMETRIC = 8
 AV_PHOTOMETRIC_RESPONSE_MAX = 65280
 AV_CLAHE_MAX_TILES = 16
+AV_GRAY16_SHIFT, AV_GRAY16_WINDOW, AV_GRAY16_AUTO = 0, 1, 2
+GRAY16_SCALES = {'shift': AV_GRAY16_SHIFT, 'window': AV_GRAY16_WINDOW, 'auto': AV_GRAY16_AUTO}      # config.gray16_scale
+AV_GRAY16_MAX_CLIP_PPM = 500000
+AV_GRAY16_WORK_WORDS = 4100
 AV_PIX_GRAY8, AV_PIX_GRAY16, AV_PIX_RGB8, AV_PIX_BGR8, AV_PIX_RGBA8, AV_PIX_BGRA8 = 0, 1, 2, 3, 4, 5
 AV_PIX_BAYER_RGGB8, AV_PIX_BAYER_BGGR8, AV_PIX_BAYER_GRBG8, AV_PIX_BAYER_GBRG8 = 16, 17, 18, 19
 AV_PIX_BAYER_RGGB16, AV_PIX_BAYER_BGGR16, AV_PIX_BAYER_GRBG16, AV_PIX_BAYER_GBRG16 = 20, 21, 22, 23
@@ -114,6 +118,39 @@ def gray16_shift_value(shift):
     if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= 8:
         raise ValueError('gray16_shift %r outside 0 .. 8' % (shift,))
     return int(shift)
+
+
+def _int_in(v, lo, hi):
+    return not isinstance(v, bool) and isinstance(v, numbers.Real) and int(v) == v and lo <= int(v) <= hi
+
+
+def gray16_range_settings(scale='shift', window=None, clip=(100, 100), min_span=256):
+    """config.gray16_scale / gray16_window / gray16_auto_clip / gray16_auto_min_span -> (mode, lo, hi, ppm_lo, ppm_hi, min_span) as the
+    C ABI takes them ("Range scaling of 16-bit grey" in include/airvision.h); ValueError, naming the setting, for a scale that is none of
+    'shift', 'window', 'auto', and for what the chosen scale reads: a window that does not satisfy 0 <= lo < hi <= 65535, a clip that is
+    not two integers >= 0 with a sum of at most 500000 ppm, a minimum span outside 16 .. 65535.  What a scale does not read is carried as
+    its default and not checked."""
+    if scale not in GRAY16_SCALES:
+        raise ValueError("gray16_scale %r is none of 'shift', 'window', 'auto'" % (scale,))
+    mode, lo, hi, ppm, span = GRAY16_SCALES[scale], 0, 65535, (100, 100), 256
+    if mode == AV_GRAY16_WINDOW:
+        try:
+            lo, hi = window
+        except (TypeError, ValueError):
+            raise ValueError("gray16_scale 'window' needs gray16_window = (lo, hi), got %r" % (window,))
+        if not (_int_in(lo, 0, 65535) and _int_in(hi, 0, 65535) and lo < hi):
+            raise ValueError('gray16_window %r does not satisfy 0 <= lo < hi <= 65535' % (window,))
+    if mode == AV_GRAY16_AUTO:
+        try:
+            ppm = tuple(clip)
+        except TypeError:
+            ppm = ()
+        if len(ppm) != 2 or not all(_int_in(v, 0, AV_GRAY16_MAX_CLIP_PPM) for v in ppm) or sum(ppm) > AV_GRAY16_MAX_CLIP_PPM:
+            raise ValueError('gray16_auto_clip %r: two integers >= 0 in parts per million whose sum is at most %d' % (clip, AV_GRAY16_MAX_CLIP_PPM))
+        if not _int_in(min_span, 16, 65535):
+            raise ValueError('gray16_auto_min_span %r outside 16 .. 65535' % (min_span,))
+        span = min_span
+    return mode, int(lo), int(hi), int(ppm[0]), int(ppm[1]), int(span)
 
 
 def downscale_value(factor):
@@ -227,6 +264,9 @@ SIGNATURES = {
     'av_png_probe': (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'av_to_gray8': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     'av_pixfmt_frame_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'av_to_gray8_range': (C.c_int, [_P, C.c_int64] + [C.c_int] * 10 + [_P, _P, C.c_int64, _P, _P, _P]),
+    'av_frontend_set_gray16_scale': (C.c_int, [_P] + [C.c_int] * 6),
+    'av_frontend_read_range': (C.c_int, [_P, _P, _P]),
     'av_downscale': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     'av_downscale_vector_path': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     'av_quat_to_rotation': (C.c_int, [_P, _P]),

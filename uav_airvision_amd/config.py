@@ -82,6 +82,15 @@ class ConfigEuRoC(object):
         self.cam1_response = None
         self.cam0_vignette = None
         self.cam1_vignette = None
+        # scaling of 16-bit grey samples (image_format 'gray16' only; no counterpart in the reference; "Range scaling of 16-bit grey" in
+        # include/airvision.h): 'shift' = min(255, v >> gray16_shift), 'window' = gray16_window = (lo, hi) mapped to 0 .. 255 for every
+        # image, 'auto' = a range per stereo pair from the pair's own histogram on the GPU: gray16_auto_clip = the parts per million of
+        # samples that may saturate at the low / high end, gray16_auto_min_span = the smallest hi - lo (16 .. 65535; 256 keeps one count
+        # at most one grey level).  A thermal core or a low-light camera whose signal does not fill its container wants 'auto'.
+        self.gray16_scale = 'shift'
+        self.gray16_window = None
+        self.gray16_auto_clip = (100, 100)
+        self.gray16_auto_min_span = 256
         self.stereo_threshold = 5
         self.max_iteration = 30
         self.track_precision = 0.01

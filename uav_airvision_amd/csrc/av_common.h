@@ -306,3 +306,16 @@ int av_launch_downscale(const FrameSet& src, const FrameSet& dst, int n_groups, 
 // a source with a list (the destination's own) is read through it, which is the in-place call on a listed set.
 int av_launch_photometric(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
                           const uint16_t* gain0, const uint16_t* gain1, hipStream_t st);
+// range16.hip: n_groups 16-bit grey frames of one camera or of two to tightly packed 8-bit grey through a window instead of a shift
+// ("Range scaling of 16-bit grey" in include/airvision.h).  Sets and list as av_launch_to_gray8 -- the destination's list, a negative
+// entry skips the group (its histogram, its record and its pixels).  A group is the images of one FrameSet group: the two cameras'
+// frames are pooled into one histogram and share one record.  AV_GRAY16_AUTO: hist [n_groups][4096] is zero on entry and zero again when
+// the launches have run, rec [n_groups][4] receives {lo, hi, m, 0} by group (not by entry); AV_GRAY16_WINDOW reads neither.  range_out
+// (or null): int32 [n_groups][2], (lo, hi) of every group that is written.  Three launches (one for a window) on st, no host wait.
+// av_range16_check: the limits of the settings a mode reads, with `who` in the text.
+struct Range16 {
+    int mode, lo, hi, ppm_lo, ppm_hi, min_span;
+    uint32_t* hist; uint32_t* rec; int32_t* range_out;
+};
+int av_range16_check(int mode, int lo, int hi, int ppm_lo, int ppm_hi, int min_span, const char* who);
+int av_launch_gray16_range(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const Range16& r, hipStream_t st);

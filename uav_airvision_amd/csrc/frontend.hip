@@ -665,6 +665,7 @@ struct av_frontend {
                     uint8_t* raw_d = nullptr; };      // raw_d: grey_chain's `raw` when a stage writes the store; idx_h / idx_d then hold its `first` list behind the entries' own
         uint8_t* gray_d = nullptr; size_t gray_cap = 0;       // grey_chain's `gray_full` of ONE upload (uploads are serialised on the copy stream: one scratch serves the whole ring)
         uint8_t* mosaic_d = nullptr; size_t mosaic_cap = 0;   // grey_chain's `mosaic` of one upload, likewise (packed mosaics only)
+        uint32_t* range_d = nullptr; size_t range_cap = 0;    // grey_chain's `range` of one upload, likewise (AV_GRAY16_AUTO only): histograms, then records
         Up up[4]; int up_next = 0;               // upload staging ring (pinned frames + the slot list of the upload's kernels)
         hipEvent_t uploaded = nullptr; bool any_upload = false;      // copy stream: the newest upload's kernels have finished
         hipEvent_t stepped = nullptr; bool any_step = false;          // step stream: the newest step has finished
@@ -705,6 +706,10 @@ struct av_frontend {
     // handed, ph_resp / ph_gain: null = that part is the identity for that camera.  photo_set: the tables have been given (a step before that is refused)
     bool photo = false, photo_set = false; uint16_t* ph_resp_buf = nullptr; uint16_t* ph_gain_buf[2] = {nullptr, nullptr};
     const uint16_t* ph_resp[2] = {nullptr, nullptr}; const uint16_t* ph_gain[2] = {nullptr, nullptr};
+    // av_frontend_set_gray16_scale ("Range scaling of 16-bit grey" in include/airvision.h): the settings, and for
+    // AV_GRAY16_AUTO the step paths' histograms [S][4096] (zero between launches) and records [2][S][4] -- by cam0's pyramid slot, so
+    // that a prestaged frame does not replace the records of the step before it (the frame store: FrameStore::range_d)
+    Range16 g16 = {AV_GRAY16_SHIFT, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr}; uint32_t* g16_hist = nullptr; uint32_t* g16_rec = nullptr;
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
 
     explicit av_frontend(int S) : streams(S) {}
@@ -804,10 +809,11 @@ uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot
 //   gray_full  the caller's full-size grey scratch, ahead of the binning when a conversion or the photometric stage feeds it
 //   mosaic     the caller's 8-bit mosaic scratch, between the two passes of a packed mosaic's conversion (n frames per camera, no list)
 //   lut        the look-up tables of one equalisation
+//   range      gray16_scale = AV_GRAY16_AUTO: the caller's histograms [n][4096] (zero, and left zero) and records [n][4], by group
 // *level0 = the set the pyramid launch reads: l0 if any stage ran (fe->own_l0: the engine then owns level 0, which outlives the call
 // whatever the caller's frames do), else raw.
 int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, const int* first, const FrameSet& gray_full, const FrameSet& mosaic,
-               uint8_t* lut, hipStream_t st, FrameSet* level0)
+               uint8_t* lut, uint32_t* range_hist, uint32_t* range_rec, hipStream_t st, FrameSet* level0)
 {
     const av_frontend_config& c = fe->cfg;
     const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
@@ -816,7 +822,11 @@ int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, 
     int rc;
     if (conv) {
         const FrameSet& to = bin ? gray_full : l0_first;
-        if ((rc = av_launch_to_gray8(at, to, n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st, &mosaic))) return rc;
+        if (fe->g16.mode != AV_GRAY16_SHIFT) {       // a window or the pair's own range instead of the shift (range16.hip): same target, same list
+            Range16 r = fe->g16;
+            r.hist = range_hist; r.rec = range_rec;
+            if ((rc = av_launch_gray16_range(at, to, n, fe->in_w, fe->in_h, r, st))) return rc;
+        } else if ((rc = av_launch_to_gray8(at, to, n, fe->in_w, fe->in_h, fe->fmt, fe->fmt_shift, st, &mosaic))) return rc;
         at = to;
     }
     if (fe->photo) {
@@ -848,7 +858,8 @@ int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64
     const FrameSet gray = fe->gray_full ? FrameSet{{fe->gray_full, fe->gray_full + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
     const FrameSet mosaic = fe->mosaic ? FrameSet{{fe->mosaic, fe->mosaic + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
     FrameSet level0;
-    int rc = grey_chain(fe, av_frames(img0, img1, img_stride), d.S, l0, nullptr, gray, mosaic, fe->eq_lut, st, &level0);
+    int rc = grey_chain(fe, av_frames(img0, img1, img_stride), d.S, l0, nullptr, gray, mosaic, fe->eq_lut, fe->g16_hist,
+                        fe->g16_rec ? fe->g16_rec + (size_t)cur * 4 * d.S : nullptr, st, &level0);
     if (rc) return rc;
     return av_launch_pyramid(level0, d.S, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur, 2, st, !(inputs_persist || fe->own_l0), wrote_l0);
 }
@@ -1183,6 +1194,7 @@ AV_EXPORT void av_frontend_destroy(av_frontend* fe)
     }
     if (fe->fs.gray_d) (void)hipFree(fe->fs.gray_d);
     if (fe->fs.mosaic_d) (void)hipFree(fe->fs.mosaic_d);
+    if (fe->fs.range_d) (void)hipFree(fe->fs.range_d);
     if (fe->fs.uploaded) (void)hipEventDestroy(fe->fs.uploaded);
     if (fe->fs.stepped) (void)hipEventDestroy(fe->fs.stepped);
     if (fe->copy_stream) (void)hipStreamDestroy(fe->copy_stream);
@@ -1385,6 +1397,13 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
         AV_HIP(hipMalloc((void**)&fs.mosaic_d, ((size_t)n + 16) * 2 * in_hw));
         fs.mosaic_cap = (size_t)n + 16;
     }
+    if (fe->g16.mode == AV_GRAY16_AUTO && (size_t)n > fs.range_cap) {      // the same rule for the store's histograms and records; zeroed once, on the copy stream
+        if (fs.range_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.range_d); fs.range_d = nullptr; fs.range_cap = 0; }
+        const size_t cap = (size_t)n + 16;
+        AV_HIP(hipMalloc((void**)&fs.range_d, cap * AV_GRAY16_WORK_WORDS * sizeof(uint32_t)));
+        AV_HIP(hipMemsetAsync(fs.range_d, 0, cap * AV_GRAY16_WORK_WORDS * sizeof(uint32_t), fe->copy_stream));
+        fs.range_cap = cap;
+    }
 #pragma omp parallel for schedule(static) num_threads(n >= 8 ? 8 : 1)
     for (int i = 0; i < 2 * n; ++i) {
         const int f = i >> 1, cam = i & 1;
@@ -1417,7 +1436,8 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     const FrameSet gray = fs.gray_d ? FrameSet{{fs.gray_d, fs.gray_d + in_hw}, (int64_t)(2 * in_hw), nullptr} : FrameSet{};
     const FrameSet mosaic = fs.mosaic_d ? FrameSet{{fs.mosaic_d, fs.mosaic_d + in_hw}, (int64_t)(2 * in_hw), nullptr} : FrameSet{};
     FrameSet level0;
-    if ((rc = grey_chain(fe, raw ? av_frames(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb)) : l0, n, l0, raw ? u.idx_d + n : nullptr, gray, mosaic, fe->fs_lut, cs, &level0))) return rc;
+    if ((rc = grey_chain(fe, raw ? av_frames(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb)) : l0, n, l0, raw ? u.idx_d + n : nullptr, gray, mosaic, fe->fs_lut,
+                         fs.range_d, fs.range_d ? fs.range_d + fs.range_cap * 4096 : nullptr, cs, &level0))) return rc;
     bool wrote_l0 = true;
     if ((rc = av_launch_pyramid(level0, n, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0))) return rc;
     fs.l0_in_place = !wrote_l0;
@@ -1586,6 +1606,51 @@ AV_EXPORT int av_frontend_read_image(av_frontend* fe, int stream_idx, int cam, u
     AV_HIP(hipStreamSynchronize((hipStream_t)stream));
     if (fe->copy_stream) AV_HIP(hipStreamSynchronize(fe->copy_stream));
     AV_HIP(hipMemcpy(out_host, src, hw, hipMemcpyDeviceToHost));
+    return AV_OK;
+}
+
+// ---- range scaling of 16-bit grey ("Range scaling of 16-bit grey" in include/airvision.h) -----------------------------------
+AV_EXPORT int av_frontend_set_gray16_scale(av_frontend* fe, int scale, int lo, int hi, int clip_lo_ppm, int clip_hi_ppm, int min_span)
+{
+    if (!fe) { av_set_error("av_frontend_set_gray16_scale: bad arguments"); return AV_E_INVALID; }
+    if (fe->fed) {
+        av_set_error("av_frontend_set_gray16_scale: the engine has already been handed a frame (step, prestage or frames_upload): the frames in it "
+                     "would disagree with the new scale; set the scale of an engine before its first frame");
+        return AV_E_INVALID;
+    }
+    if (scale != AV_GRAY16_SHIFT) {
+        if (av_range16_check(scale, lo, hi, clip_lo_ppm, clip_hi_ppm, min_span, "av_frontend_set_gray16_scale")) return AV_E_INVALID;
+        if (fe->fmt != AV_PIX_GRAY16) {
+            av_set_error("av_frontend_set_gray16_scale: gray16_scale %d ('%s') applies to pixel_format AV_PIX_GRAY16 ('gray16') only, not to %d ('%s')", scale,
+                         scale == AV_GRAY16_WINDOW ? "window" : "auto", fe->fmt, av_pixfmt_name(fe->fmt));
+            return AV_E_INVALID;
+        }
+    }
+    if (scale == AV_GRAY16_AUTO && !fe->g16_rec) {      // histograms [S][4096] and records [2][S][4], zeroed; once per engine
+        AV_HIP(hipSetDevice(fe->device));
+        int rc;
+        if ((rc = dev_alloc(fe, &fe->g16_hist, (size_t)fe->d.S * 4096)) || (rc = dev_alloc(fe, &fe->g16_rec, (size_t)2 * fe->d.S * 4))) return rc;
+    }
+    fe->g16.mode = scale; fe->g16.lo = lo; fe->g16.hi = hi; fe->g16.ppm_lo = clip_lo_ppm; fe->g16.ppm_hi = clip_hi_ppm; fe->g16.min_span = min_span;
+    return AV_OK;
+}
+
+AV_EXPORT int av_frontend_read_range(av_frontend* fe, int32_t* range_out_host, void* stream)
+{
+    if (!fe || !range_out_host) { av_set_error("av_frontend_read_range: bad arguments"); return AV_E_INVALID; }
+    if (fe->g16.mode == AV_GRAY16_SHIFT) { av_set_error("av_frontend_read_range: the engine scales 16-bit data by a fixed shift (no av_frontend_set_gray16_scale to a window or a range): there is no range"); return AV_E_INVALID; }
+    if (!fe->stepped) { av_set_error("av_frontend_read_range: no step has run yet"); return AV_E_INVALID; }
+    if (fe->stepped_frames) { av_set_error("av_frontend_read_range: the last step read the frame store, whose entries are shared by streams and keep no range"); return AV_E_INVALID; }
+    const int S = fe->d.S;
+    if (fe->g16.mode == AV_GRAY16_WINDOW) {
+        for (int s = 0; s < S; ++s) { range_out_host[2 * s] = fe->g16.lo; range_out_host[2 * s + 1] = fe->g16.hi; }
+        return AV_OK;
+    }
+    AV_HIP(hipSetDevice(fe->device));
+    AV_HIP(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<uint32_t> rec((size_t)4 * S);
+    AV_HIP(hipMemcpy(rec.data(), fe->g16_rec + (size_t)fe->parity * 4 * S, rec.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));      // after a step, parity is the slot of the frame just used
+    for (int s = 0; s < S; ++s) { range_out_host[2 * s] = (int32_t)rec[4 * s]; range_out_host[2 * s + 1] = (int32_t)rec[4 * s + 1]; }
     return AV_OK;
 }
 

@@ -28,9 +28,15 @@ class ImageProcessingPipeline(object):
         # here is shown the image the front-end actually worked on (update_image, the hook of viewer.py:45-49)
         # config.image_downscale 2 / 4: the callbacks still take full-size frames; the same hook shows the binned frame
         # config.cam*_response / cam*_vignette: the engine reads them from the config object; the same hook shows the corrected frame
+        # config.gray16_scale 'window' / 'auto' (image_format 'gray16'): likewise; gray16_range() returns the (lo, hi) of the last frame
         self.use_clahe = bool(getattr(config, 'use_clahe', False))
         self.downscale = self._engine.downscale
         self.viewer = None
+
+    def gray16_range(self):
+        """(lo, hi) the last stereo frame was scaled with (config.gray16_scale 'window' or 'auto'; refused with 'shift')."""
+        lo, hi = self._engine.read_range()[0]
+        return int(lo), int(hi)
 
     # ---- reference callbacks -----------------------------------------------------------------
     def imu_callback(self, imu_msg):

@@ -117,6 +117,56 @@ def pack_frontend_config(config, max_corners=None):
     return c
 
 
+def gray16_scale_settings(config):
+    """config.gray16_scale / gray16_window / gray16_auto_clip / gray16_auto_min_span as av_frontend_set_gray16_scale takes them: (scale,
+    lo, hi, clip_lo_ppm, clip_hi_ppm, min_span).  getattr: a config object without the attributes scales by the shift.  ValueError for a
+    setting outside its limits (N.gray16_range_settings) and, naming both settings, for a scale other than 'shift' with an image_format
+    other than 'gray16'."""
+    scale = getattr(config, 'gray16_scale', 'shift')
+    settings = N.gray16_range_settings(scale, getattr(config, 'gray16_window', None), getattr(config, 'gray16_auto_clip', (100, 100)),
+                                       getattr(config, 'gray16_auto_min_span', 256))
+    fmt = N.pixel_format_code(getattr(config, 'image_format', 'gray8'))
+    if settings[0] != N.AV_GRAY16_SHIFT and fmt != N.AV_PIX_GRAY16:
+        raise ValueError("gray16_scale %r applies to image_format 'gray16' only, not to image_format %r" % (scale, N.PIXEL_FORMAT_NAMES[fmt]))
+    return settings
+
+
+def gray16_range(frames, scale='auto', window=None, clip=(100, 100), min_span=256, pool=1):
+    """What the engine and ops.to_gray8_range compute, in NumPy ("Range scaling of 16-bit grey" in include/airvision.h): frames uint16
+    [n, h, w] in groups of `pool` (1 or 2) consecutive images -> (uint8 [n, h, w], int32 [n // pool, 2]), the grey frames and the (lo, hi)
+    of every group.  scale 'window' applies `window` = (lo, hi) to every image; 'auto' takes each group's range from its 4,096-bin
+    histogram of v >> 4 with `clip` = (ppm_lo, ppm_hi) and `min_span`.  The two images of a stereo pair are one group: pool = 2 on
+    frames interleaved cam0, cam1."""
+    mode, lo, hi, ppm_lo, ppm_hi, span_min = N.gray16_range_settings(scale, window, clip, min_span)
+    if mode == N.AV_GRAY16_SHIFT:
+        raise ValueError("gray16_range: scale is 'window' or 'auto'")
+    a = np.asarray(frames)
+    if a.dtype != np.uint16 or a.ndim != 3 or pool not in (1, 2) or a.shape[0] % pool:
+        raise ValueError('gray16_range: frames are uint16 [n, h, w] with n a multiple of pool = 1 or 2, got %s %s, pool %r' % (a.dtype, a.shape, pool))
+    n, h, w = a.shape
+    out = np.empty((n, h, w), np.uint8)
+    ranges = np.empty((n // pool, 2), np.int32)
+    for g in range(n // pool):
+        grp = a[g * pool:(g + 1) * pool]
+        if mode == N.AV_GRAY16_AUTO:
+            N_samples = grp.size
+            k_lo, k_hi = N_samples * ppm_lo // 10 ** 6, N_samples * ppm_hi // 10 ** 6
+            hist = np.bincount((grp >> 4).reshape(-1), minlength=4096).astype(np.int64)
+            b_lo = int(np.argmax(np.cumsum(hist) > k_lo))
+            b_hi = 4095 - int(np.argmax(np.cumsum(hist[::-1]) > k_hi))
+            lo, hi = 16 * b_lo, 16 * b_hi + 15
+            if hi - lo < span_min:
+                need = span_min - (hi - lo)
+                lo = max(0, min(lo - need // 2, 65535 - span_min))
+                hi = lo + span_min
+        span = hi - lo
+        m = ((255 << 16) + span // 2) // span
+        d = np.clip(grp.astype(np.int64), lo, hi) - lo
+        out[g * pool:(g + 1) * pool] = np.minimum(255, (d * m + 32768) >> 16).astype(np.uint8)
+        ranges[g] = (lo, hi)
+    return out, ranges
+
+
 def frame_shape(pixel_format, n, height, width):
     """Shape of n frames of an AV_PIX_* format: [n, h, w] for the grey formats and the mosaics, [n, h, w, 3 | 4] for the colour ones,
     [n, h, w * d / 8] (bytes) for the packed 10 / 12-bit transports."""
@@ -391,7 +441,13 @@ class FrontendEngine(object):
         config.cam0_response / cam1_response / cam0_vignette / cam1_vignette (a config object without them has none): the photometric
         calibration of each camera, for all streams -- each None, an array or a path as `photometric_tables` takes them.  With any of
         them the engine is created with AV_FE_PHOTOMETRIC and corrects every grey frame, G^-1(p) / V(x) in the integer arithmetic of
-        include/airvision.h, after the conversion to grey and ahead of binning and CLAHE; `set_photometric` has the rules."""
+        include/airvision.h, after the conversion to grey and ahead of binning and CLAHE; `set_photometric` has the rules.
+
+        config.gray16_scale = 'window' or 'auto' (a config object without the attribute: 'shift'), image_format 'gray16' only: 16-bit
+        samples are scaled through config.gray16_window = (lo, hi), or through a range the GPU takes from every stereo pair's own
+        histogram (config.gray16_auto_clip ppm at each end, config.gray16_auto_min_span), instead of config.gray16_shift -- `gray16_range`
+        is the arithmetic in NumPy, `read_range` returns the ranges of the last step.  Any other image_format with such a scale is a
+        ValueError naming both settings."""
         self.config = config
         self.n_streams = int(n_streams)
         self.device = int(device)
@@ -403,6 +459,8 @@ class FrontendEngine(object):
         photo = [photometric_tables(getattr(config, 'cam%d_response' % cam, None), getattr(config, 'cam%d_vignette' % cam, None)) for cam in (0, 1)]
         photo = [check_photometric(cam, r, g, self._cfg.height, self._cfg.width) for cam, (r, g) in enumerate(photo)]
         self.photometric = any(t is not None for pair in photo for t in pair)
+        g16 = gray16_scale_settings(config)
+        self.gray16_scale = {v: k for k, v in N.GRAY16_SCALES.items()}[g16[0]]
         if self.photometric:
             self._cfg.flags |= N.AV_FE_PHOTOMETRIC
         with torch.cuda.device(self.device):
@@ -418,6 +476,9 @@ class FrontendEngine(object):
                 self.set_masks(*masks)
             if self.photometric:
                 self.set_photometric(photo[0][0], photo[0][1], photo[1][0], photo[1][1])
+            if g16[0] != N.AV_GRAY16_SHIFT:
+                with torch.cuda.device(self.device):
+                    N.check(N.lib().av_frontend_set_gray16_scale(self._h, *g16))
         except Exception:
             self.close()
             raise
@@ -660,6 +721,15 @@ class FrontendEngine(object):
         out = np.empty((self.height, self.width), np.uint8)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_read_image(self._h, int(stream), int(cam), out.ctypes.data_as(C.c_void_p), self._stream()))
+        return out
+
+    def read_range(self):
+        """int32 [S, 2]: the (lo, hi) the frames of the last step were scaled with (config.gray16_scale 'window' or 'auto'), after
+        `step` (prestaged or not) and `step_host`.  Refused (AirvisionError, AV_E_INVALID) with gray16_scale 'shift', before the first
+        step and after a `step_frames`: an entry of the frame store is shared by streams and keeps no range."""
+        out = np.empty((self.n_streams, 2), np.int32)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_read_range(self._h, out.ctypes.data_as(C.c_void_p), self._stream()))
         return out
 
     def enable_timing(self, max_spans):

@@ -414,3 +414,61 @@ def photometric(images, response=None, gain=None, out=None, device=0):
         N.check(N.lib().av_photometric(N.dptr(tb), N.dptr(ob), n, w, h, in_stride, out_stride, None if r is None else N.dptr(r),
                                        None if g is None else N.dptr(g), N.current_stream()))
     return out
+
+
+def to_gray8_range(img, scale='auto', window=None, clip=(100, 100), min_span=256, pool=1, index=None, out=None, work=None, device=0):
+    """16-bit grey frames to 8-bit grey through a window instead of a fixed shift (av_to_gray8_range; "Range scaling of 16-bit grey" in
+    include/airvision.h has the arithmetic, frontend.gray16_range is its NumPy twin).  img: uint16 [n, h, w] or [h, w] (a cuda tensor may
+    also be torch.int16 holding the same bits), read where it lies: each image contiguous, any distance apart, at any address.
+    scale 'window': `window` = (lo, hi) for every image.  scale 'auto': every group of `pool` (1 or 2) consecutive images -- 2 = the
+    cam0 and cam1 frames of a stereo pair, interleaved -- gets its own range from the group's pooled histogram, with `clip` = (ppm_lo,
+    ppm_hi) and `min_span`.  index: one int per group, or None: group g is written to images index[g] * pool .. of `out` (which must then
+    be given, uint8 cuda [m, h, w]); a negative entry skips the group, of an entry named twice the last group is written.  work: None, or
+    a torch.int32 cuda tensor of at least (n // pool) * AV_GRAY16_WORK_WORDS zeros that 'auto' works in and leaves zero in its histogram
+    part, the first 4096 * (n // pool) words (without it the call allocates one and waits for the stream).
+    Returns (grey, ranges): the uint8 cuda tensor of img's shape (`out` itself if given) and an int32 cuda tensor [n // pool, 2] of the
+    (lo, hi) of every group, (-1, -1) for a group that was not written."""
+    mode, lo, hi, ppm_lo, ppm_hi, span = N.gray16_range_settings(scale, window, clip, min_span)
+    if mode == N.AV_GRAY16_SHIFT:
+        raise ValueError("to_gray8_range: scale is 'window' or 'auto' (ops.to_gray8 is the shift)")
+    t = torch.as_tensor(img)
+    if t.dtype not in (torch.uint16, torch.int16) or t.dim() not in (2, 3):
+        raise ValueError('to_gray8_range: images are torch.uint16 / torch.int16 [n, h, w] or [h, w], got %s %s' % (t.dtype, tuple(t.shape)))
+    t = t.to(_dev(device))
+    batched = t.dim() == 3
+    tb = t if batched else t.unsqueeze(0)
+    n, h, w = tb.shape
+    if pool not in (1, 2) or n % pool:
+        raise ValueError('to_gray8_range: pool is 1 or 2 and divides the number of images (%d), got %r' % (n, pool))
+    if (n and not tb[0].is_contiguous()) or (n > 1 and tb.stride(0) < h * w):
+        tb = tb.contiguous()
+    groups = n // pool
+    oshape = tuple(t.shape)
+    if out is None:
+        if index is not None:
+            raise ValueError('to_gray8_range: an index needs `out`')
+        out = torch.empty(oshape, dtype=torch.uint8, device=_dev(device))
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and (
+            tuple(out.shape) == oshape if index is None else out.dim() == 3 and tuple(out.shape[1:]) == (h, w))):
+        raise ValueError('to_gray8_range: out must be a uint8 cuda tensor of shape %s' % (oshape if index is None else ('m', h, w),))
+    ob = out if out.dim() == 3 else out.unsqueeze(0)
+    if (ob.shape[0] and not ob[0].is_contiguous()) or (ob.shape[0] > 1 and ob.stride(0) < h * w):
+        raise ValueError('to_gray8_range: every image of out must be contiguous')
+    first = None
+    if index is not None:
+        idx = [int(v) for v in index]
+        if len(idx) != groups or any(e >= 0 and (e + 1) * pool > ob.shape[0] for e in idx):
+            raise ValueError('to_gray8_range: index has one entry per group (%d), each negative or inside out (%d images)' % (groups, ob.shape[0]))
+        last = {e: g for g, e in enumerate(idx)}
+        first = torch.tensor([e if e >= 0 and last[e] == g else -1 for g, e in enumerate(idx)], dtype=torch.int32, device=_dev(device))
+    if work is not None and not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.int32 and work.is_contiguous()
+                                 and work.numel() >= groups * N.AV_GRAY16_WORK_WORDS):
+        raise ValueError('to_gray8_range: work is a contiguous torch.int32 cuda tensor of at least %d elements' % (groups * N.AV_GRAY16_WORK_WORDS))
+    ranges = torch.full((groups, 2), -1, dtype=torch.int32, device=_dev(device))
+    in_stride = (tb.stride(0) if n > 1 else h * w) * tb.element_size()
+    out_stride = ob.stride(0) if ob.shape[0] > 1 else h * w
+    with torch.cuda.device(device):
+        N.check(N.lib().av_to_gray8_range(N.dptr(tb), in_stride, n, w, h, mode, lo, hi, ppm_lo, ppm_hi, span, pool,
+                                          None if first is None else N.dptr(first), N.dptr(ob), out_stride, N.dptr(ranges),
+                                          None if work is None else N.dptr(work), N.current_stream()))
+    return out, ranges

@@ -302,6 +302,15 @@ def make_parser():
     ap.add_argument('--vignette1', metavar='PNG', default=None, help='the same for cam1 (config.cam1_vignette)')
     ap.add_argument('--gray16-shift', type=int, default=None, metavar='N',
                     help='16-bit frames, grey or Bayer: sample = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
+    ap.add_argument('--gray16-scale', choices=['shift', 'window', 'auto'], default=None,
+                    help="16-bit grey frames (--pixel-format gray16): 'shift' = the fixed shift, 'window' = --gray16-window mapped to 0 .. 255, 'auto' = a range per "
+                         "stereo pair from the pair's own histogram on the GPU, for thermal and low-light sources (config.gray16_scale, default shift)")
+    ap.add_argument('--gray16-window', type=int, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='--gray16-scale window: 0 <= LO < HI <= 65535 (config.gray16_window)')
+    ap.add_argument('--gray16-clip', type=int, nargs=2, default=None, metavar=('PPM_LO', 'PPM_HI'),
+                    help='--gray16-scale auto: parts per million of samples that may saturate at the low / high end (config.gray16_auto_clip, default 100 100)')
+    ap.add_argument('--gray16-min-span', type=int, default=None, metavar='N',
+                    help='--gray16-scale auto: the smallest hi - lo of a range, 16 .. 65535 (config.gray16_auto_min_span, default 256)')
     return ap
 
 
@@ -319,6 +328,10 @@ def apply_args(cfg, args):
         cfg.image_format = getattr(args, 'pixel_format', 'gray8')
     if getattr(args, 'gray16_shift', None) is not None:
         cfg.gray16_shift = args.gray16_shift
+    for arg, attr in (('gray16_scale', 'gray16_scale'), ('gray16_window', 'gray16_window'), ('gray16_clip', 'gray16_auto_clip'), ('gray16_min_span', 'gray16_auto_min_span')):
+        v = getattr(args, arg, None)                            # (a setting already on the config object stays unless the switch is given)
+        if v is not None:
+            setattr(cfg, attr, tuple(v) if isinstance(v, list) else v)
     if getattr(args, 'downscale', None) is not None:          # (a factor already set on the config object stays unless the switch is given)
         cfg.image_downscale = int(args.downscale)
     for cam in (0, 1):                                         # (a mask already set on the config object stays unless the switch is given)
@@ -393,6 +406,8 @@ def main(argv=None):
             rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
         if args.pixel_format != 'gray8':
             rep['pixel_format'] = dict(asked=args.pixel_format, last_batch=cfg.image_format, gray16_shift=cfg.gray16_shift)
+        if getattr(cfg, 'gray16_scale', 'shift') != 'shift':
+            rep['gray16_scale'] = dict(scale=cfg.gray16_scale, window=cfg.gray16_window, clip=list(cfg.gray16_auto_clip), min_span=cfg.gray16_auto_min_span)
         if getattr(cfg, 'image_downscale', 1) != 1:
             rep['downscale'] = cfg.image_downscale
         if args.mask0 is not None or args.mask1 is not None:
