@@ -25,7 +25,7 @@ def kernel_stats(path):
     out = {}
     with open(path) as f:
         for row in csv.DictReader(f):
-            if 'to_gray8_kernel' in row.get('Name', ''):
+            if 'PixOp' in row.get('Name', ''):                  # stream_pass_kernel<PixOp<format>>
                 out[row['Name']] = dict(calls=int(row['Calls']), ms_per_launch=float(row['AverageNs']) * 1e-6)
     return out
 

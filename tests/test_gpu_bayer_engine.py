@@ -85,6 +85,24 @@ def test_a_stream_gives_the_same_result_anywhere_in_a_batch():
             assert all(_same(a, b) for a, b in zip(alone[pos], got[pos])), (mode, pos)
 
 
+def test_an_entry_named_twice_takes_the_later_frame(mosaicked):
+    """One upload that names an entry twice: the demosaic writes the store through the list whose entry for the earlier frame is
+    negative, so the later frame wins, as with the other conversions (tests/test_gpu_pixfmt_engine.py)."""
+    from uav_airvision_amd.frontend import FrontendEngine
+    fmt = 'bayer_gbrg16'
+    st = mosaicked[fmt][0]
+    eng = FrontendEngine(_cfg(image_format=fmt, gray16_shift=SHIFTS[fmt]), n_streams=1)
+    eng.frames_reserve(4)
+    t, a0, a1 = st.raw[0]
+    _t, b0, b1 = st.raw[1]
+    eng.frames_upload(np.array([2, 2], np.int32), np.stack([b0, a0]), np.stack([b1, a1]))
+    eng.step_frames([2], [t])
+    eng.read_features()
+    assert np.array_equal(eng.read_image(0, 0), st.frame(0).cam0_image) and np.array_equal(eng.read_image(0, 1), st.frame(0).cam1_image)
+    assert not np.array_equal(st.frame(0).cam0_image, st.frame(1).cam0_image)
+    eng.close()
+
+
 def test_gray8_is_what_it_was(base):
     """image_format = 'gray8' equals a bare config without the two attributes, outputs and timing span counts per step; a Bayer format
     adds no span to a step (the conversion counts inside the input stage's)."""

@@ -194,9 +194,10 @@ struct ImgView {
 
 // Where the frames of one stage of the input chain lie (the producer side of ImgView): camera c of group g at base[c] + e * stride
 // bytes with e = map ? map[g] : g; base[1] null = one camera.  A launcher reads its source set and writes its destination set, and
-// a launch has ONE list, its destination's: conversion and binning apply it to the destination only (their source is read at
-// g * stride, its map stays null) and skip a group whose entry is negative; CLAHE and the pyramid apply it to both sides (the
-// source's map is the destination's, or both are null) and take no negative entry.
+// a launch has ONE list, its destination's.  A group whose entry is negative is skipped.  A source without a map is read at
+// g * stride (conversion, binning, range scaling, photometric out of the caller's frames); a source with a map -- always the
+// destination's own -- is read at e like the destination (photometric in place in a listed set, CLAHE, the pyramid; the last two are
+// handed no negative entry).  This is the whole rule; FramePlace / av_frame_at below are its one implementation.
 struct FrameSet {
     uint8_t* base[2]; int64_t stride;
     const int* map;                              // device, one int per group; or null
@@ -206,9 +207,50 @@ inline FrameSet av_frames(const uint8_t* b0, const uint8_t* b1, int64_t stride, 
 {
     return FrameSet{{const_cast<uint8_t*>(b0), const_cast<uint8_t*>(b1)}, stride, map};
 }
-// The vector bodies of pixfmt.hip, bayer.hip and downscale.hip load and store whole 16-byte vectors: every base, and every stride
-// that is applied, has to be a multiple of 16.  One group at its own place (no list) applies no stride.  The width condition of
-// each kernel stays with its launcher.
+
+// The device side of a (src, dst) pair of FrameSets, by value: the first member of every input stage's argument record.  Image i of
+// a launch is camera i % n_src of group i / n_src; how a kernel maps blockIdx.x onto (image, block of the image) is its own.
+struct FramePlace {
+    const uint8_t* src0; const uint8_t* src1;
+    uint8_t* dst0; uint8_t* dst1;
+    int64_t src_stride, dst_stride;              // bytes between the groups of one camera
+    const int* index;                            // the destination's list, or null
+    int n_src;                                   // 1 or 2
+    int src_listed;                              // the source has the list too
+    int n_img;                                   // n_groups * n_src
+    int per;                                     // workgroups per image (of the kernel launched)
+};
+// Fills p and returns the workgroups of the launch, per * n_img with n_img rounded up to a multiple of img_round (8 for the kernels
+// that interleave eight images over the XCDs); 0 with the error set (who, w x h in the text) if that is more than max_wg.
+inline unsigned av_frame_place(FramePlace* p, const FrameSet& src, const FrameSet& dst, int n_groups, int per, int img_round,
+                               const char* who, int w, int h, int64_t max_wg = 0x7FFFFFFFll)
+{
+    p->src0 = src.base[0]; p->src1 = src.base[1]; p->dst0 = dst.base[0]; p->dst1 = dst.base[1];
+    p->src_stride = src.stride; p->dst_stride = dst.stride; p->index = dst.map;
+    p->n_src = src.base[1] ? 2 : 1; p->src_listed = src.map != nullptr; p->n_img = n_groups * p->n_src; p->per = per;
+    const int64_t n_wg = (int64_t)per * ((p->n_img + img_round - 1) / img_round * img_round);
+    if (n_wg > max_wg) { av_set_error("%s: %d images of %d x %d are more than one launch holds", who, p->n_img, w, h); return 0u; }
+    return (unsigned)n_wg;
+}
+#ifdef __HIPCC__
+// storage entry of group g; negative: the group is skipped
+__device__ __forceinline__ int64_t av_frame_entry(const FramePlace& p, int g) { return p.index ? p.index[g] : g; }
+// image img of the launch: its camera, its group and where it is read and written; false = its group is skipped
+struct FrameAt { int cam, g; const uint8_t* src; uint8_t* dst; };
+__device__ __forceinline__ bool av_frame_at(const FramePlace& p, int img, FrameAt& f)
+{
+    f.cam = img % p.n_src; f.g = img / p.n_src;
+    const int64_t e = av_frame_entry(p, f.g);
+    if (e < 0) return false;
+    f.src = (f.cam ? p.src1 : p.src0) + (p.src_listed ? e : (int64_t)f.g) * p.src_stride;
+    f.dst = (f.cam ? p.dst1 : p.dst0) + e * p.dst_stride;
+    return true;
+}
+#endif
+
+// The vector bodies of the input stages (stream_pass.h, bayer.hip, downscale.hip, the histogram of range16.hip) load and store whole
+// 16-byte vectors: every base, and every stride that is applied, has to be a multiple of 16.  One group at its own place (no list)
+// applies no stride.  The width condition of each kernel stays with its launcher.
 inline bool av_frames_vec16(const FrameSet& src, const FrameSet& dst, int n_groups)
 {
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };

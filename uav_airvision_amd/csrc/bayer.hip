@@ -23,13 +23,9 @@ constexpr int BY_ROWS = 16;                    // output rows a lane walks down 
 constexpr int BY_GEN = 256 * 16;               // pixels of one workgroup of the generic path
 
 struct BayerArgs {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
-    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
-    int n_src, n_img, w, h, shift;
+    FramePlace place;
+    int w, h, shift;
     int rx, ry;                                    // the R site: (x & 1, y & 1) == (rx, ry); the B site is the opposite corner
-    int per;                                       // workgroups per image
     int nvx, items;                                // vector path: vectors per row, (strip, vector) items per image
 };
 
@@ -62,9 +58,9 @@ __device__ __forceinline__ uint32_t bayer_sample(const uint8_t* row, int x, int 
 __device__ __forceinline__ bool bayer_place(const BayerArgs& a, int& img, int& blk)
 {
     const int L = blockIdx.x, wg = L >> 3;
-    img = (L & 7) + 8 * (wg / a.per);
-    blk = wg % a.per;
-    return img < a.n_img;
+    img = (L & 7) + 8 * (wg / a.place.per);
+    blk = wg % a.place.per;
+    return img < a.place.n_img;
 }
 
 // one row of 16 reduced samples of a lane, even and odd columns apart, two per dword in 16-bit halves: e[j] = columns 4j, 4j + 2,
@@ -135,12 +131,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void bayer_to_gray8_kernel(BayerArgs a)
 {
     int img, blk;
-    if (!bayer_place(a, img, blk)) return;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return;
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
+    FrameAt f;
+    if (!bayer_place(a, img, blk) || !av_frame_at(a.place, img, f)) return;
+    const uint8_t* src = f.src; uint8_t* dst = f.dst;
     const int item = blk * 256 + (int)threadIdx.x, lane = threadIdx.x & 63;
     const bool live = item < a.items;
     const int it = live ? item : a.items - 1;                     // idle lanes follow the last item: every lane takes part in the shuffles
@@ -184,12 +177,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void bayer_to_gray8_generic_kernel(BayerArgs a)
 {
     int img, blk;
-    if (!bayer_place(a, img, blk)) return;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return;
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
+    FrameAt f;
+    if (!bayer_place(a, img, blk) || !av_frame_at(a.place, img, f)) return;
+    const uint8_t* src = f.src; uint8_t* dst = f.dst;
     const int w = a.w, h = a.h, npix = w * h;
     const int64_t pitch = (int64_t)w * sizeof(T);
     const int p0 = blk * BY_GEN;                                  // < 2^24
@@ -219,20 +209,18 @@ int av_launch_bayer_to_gray8(const FrameSet& src, const FrameSet& dst, int n_gro
     const int pat = (fmt - AV_PIX_BAYER_RGGB8) & 3;               // rggb, bggr, grbg, gbrg
     BayerArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride; a.index = dst.map;
-    a.n_src = src.base[1] ? 2 : 1; a.n_img = n_groups * a.n_src; a.w = w; a.h = h; a.shift = shift;
+    a.w = w; a.h = h; a.shift = shift;
     a.rx = pat == 1 || pat == 2; a.ry = pat == 1 || pat == 3;
     const bool vec = (w % BY_LANE) == 0 && av_frames_vec16(src, dst, n_groups);
+    int per = (int)(((int64_t)w * h + BY_GEN - 1) / BY_GEN);
     if (vec) {
         a.nvx = w / BY_LANE;
         a.items = a.nvx * ((h + BY_ROWS - 1) / BY_ROWS);
-        a.per = (a.items + 255) / 256;
-    } else {
-        a.per = (int)(((int64_t)w * h + BY_GEN - 1) / BY_GEN);
+        per = (a.items + 255) / 256;
     }
-    const int64_t n_wg = (int64_t)8 * a.per * ((a.n_img + 7) / 8);
-    if (n_wg > 0x7FFFFFFFll) { av_set_error("av_to_gray8: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
-    const dim3 grid((unsigned)n_wg), block(256);
+    const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, per, 8, "av_to_gray8", w, h);      // eight images interleaved: bayer_place
+    if (!n_wg) return AV_E_INVALID;
+    const dim3 grid(n_wg), block(256);
     if (vec) {
         if (wide) hipLaunchKernelGGL(bayer_to_gray8_kernel<uint16_t>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(bayer_to_gray8_kernel<uint8_t>, grid, block, 0, st, a);

@@ -13,27 +13,14 @@ namespace {
 constexpr int CL_ROWS = 16;            // image rows per apply workgroup (a band of th rows is cut into ceil(th / CL_ROWS) chunks)
 
 struct ClaheArgs {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // between the groups of one camera
-    int n_src;                                     // 1 or 2
-    const int* index;                              // group g reads / writes storage entry index[g] (null: g itself)
+    FramePlace place;                              // (the list on both sides)
     uint8_t* lut;                                  // [n_img][tiles_y * tiles_x][256], by launch image
-    int n_img, w, h, tiles_x, tiles_y, tw, th;
+    int w, h, tiles_x, tiles_y, tw, th;
     int clip;                                      // 0: no clipping
     float scale, inv_tw, inv_th;
-    int per;                                       // workgroups per image
     int chunks;                                    // apply: chunks per band
     int dwords;                                    // rows, strides and bases are whole dwords
 };
-
-__device__ __forceinline__ void clahe_image(const ClaheArgs& a, int img, const uint8_t*& src, uint8_t*& dst)
-{
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    src = (cam ? a.src1 : a.src0) + e * a.src_stride;
-    dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
-}
 
 __device__ __forceinline__ uint32_t clahe_round_u8(float v)      // saturate_u8(round half to even)
 {
@@ -45,13 +32,14 @@ __global__ __launch_bounds__(256) void clahe_lut_kernel(ClaheArgs a)
     __shared__ int hist[4][256];
     __shared__ int part[8];
     const int L = blockIdx.x, wg = L >> 3;
-    const int img = (L & 7) + 8 * (wg / a.per);
-    if (img >= a.n_img) return;
-    const int tile = wg % a.per;
+    const int per = a.place.per;
+    const int img = (L & 7) + 8 * (wg / per);
+    FrameAt f;
+    if (img >= a.place.n_img || !av_frame_at(a.place, img, f)) return;
+    const int tile = wg % per;
     const int by = tile / a.tiles_x, bx = tile - by * a.tiles_x;
     const int tid = threadIdx.x, wave = tid >> 6;
-    const uint8_t* src; uint8_t* dst;
-    clahe_image(a, img, src, dst);
+    const uint8_t* src = f.src;
     for (int i = tid; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0;
     __syncthreads();
     int* my = hist[wave];
@@ -109,7 +97,7 @@ __global__ __launch_bounds__(256) void clahe_lut_kernel(ClaheArgs a)
     uint32_t b = clahe_round_u8((float)sum * a.scale);
     b |= (uint32_t)__shfl_down((int)b, 1) << 8;
     b |= (uint32_t)__shfl_down((int)b, 2) << 16;
-    if ((tid & 3) == 0) *reinterpret_cast<uint32_t*>(a.lut + ((size_t)img * a.per + tile) * 256 + tid) = b;
+    if ((tid & 3) == 0) *reinterpret_cast<uint32_t*>(a.lut + ((size_t)img * per + tile) * 256 + tid) = b;
 }
 
 // first row whose unclamped upper tile row floor(y / th - 0.5) is >= k, in the kernel's own float arithmetic
@@ -139,16 +127,16 @@ __global__ __launch_bounds__(256) void clahe_apply_kernel(ClaheArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t luts[];      // [2][tiles_x][256]
     const int L = blockIdx.x, wg = L >> 3;
-    const int img = (L & 7) + 8 * (wg / a.per);
-    if (img >= a.n_img) return;
-    const int sub = wg % a.per;
+    const int img = (L & 7) + 8 * (wg / a.place.per);
+    FrameAt f;
+    if (img >= a.place.n_img || !av_frame_at(a.place, img, f)) return;
+    const int sub = wg % a.place.per;
     const int band = sub / a.chunks - 1, chunk = sub - (band + 1) * a.chunks;      // band: the unclamped upper tile row, -1 .. tiles_y - 1
     const int yb = clahe_band_start(band, a.th, a.inv_th, a.h), ye = clahe_band_start(band + 1, a.th, a.inv_th, a.h);
     const int ya0 = yb + chunk * CL_ROWS, ya1r = min(ya0 + CL_ROWS, ye);
     if (ya0 >= ya1r) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint8_t* src; uint8_t* dst;
-    clahe_image(a, img, src, dst);
+    const uint8_t* src = f.src; uint8_t* dst = f.dst;
     const int ty1 = max(band, 0), ty2 = min(band + 1, a.tiles_y - 1);
     const int row_bytes = a.tiles_x * 256;
     {
@@ -199,11 +187,10 @@ int av_launch_clahe(const FrameSet& src, const FrameSet& dst, int n_groups, int 
                     uint8_t* lut, hipStream_t st)
 {
     if (n_groups <= 0) return AV_OK;
+    if (src.map != dst.map) { av_set_error("av_clahe: a listed set is read and written through one list"); return AV_E_INVALID; }
     ClaheArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
-    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.lut = lut;
-    a.n_img = n_groups * a.n_src; a.w = w; a.h = h; a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+    a.lut = lut; a.w = w; a.h = h; a.tiles_x = tiles_x; a.tiles_y = tiles_y;
     const int wp = w % tiles_x ? w + tiles_x - w % tiles_x : w, hp = h % tiles_y ? h + tiles_y - h % tiles_y : h;
     a.tw = wp / tiles_x; a.th = hp / tiles_y;
     const int area = a.tw * a.th;
@@ -216,18 +203,16 @@ int av_launch_clahe(const FrameSet& src, const FrameSet& dst, int n_groups, int 
     a.inv_tw = 1.0f / (float)a.tw; a.inv_th = 1.0f / (float)a.th;
     auto al4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
     a.dwords = (w & 3) == 0 && (src.stride & 3) == 0 && (dst.stride & 3) == 0 && al4(src.base[0]) && al4(src.base[1]) && al4(dst.base[0]) && al4(dst.base[1]);
-    const unsigned groups8 = (unsigned)((a.n_img + 7) / 8) * 8u;
-    a.per = tiles_x * tiles_y;
-    const int apply_chunks = (a.th + 2 + CL_ROWS - 1) / CL_ROWS;
-    if ((int64_t)(tiles_y + 1) * apply_chunks * groups8 * 256 > 0xFFFFFFFFll) {      // a launch holds fewer than 2^32 threads
-        av_set_error("av_clahe: %d images of %d x %d are more than one launch holds", a.n_img, w, h);
-        return AV_E_INVALID;
-    }
-    hipLaunchKernelGGL(clahe_lut_kernel, dim3((unsigned)a.per * groups8), dim3(256), 0, st, a);
+    // both kernels interleave eight images over the XCDs; the apply launch is the larger: a launch holds fewer than 2^32 threads
+    a.chunks = (a.th + 2 + CL_ROWS - 1) / CL_ROWS;      // a band has th rows, one more or less where 1.0f / th rounds a boundary row across
+    const int per_lut = tiles_x * tiles_y, per_apply = (tiles_y + 1) * a.chunks;
+    const unsigned n_apply = av_frame_place(&a.place, src, dst, n_groups, per_apply, 8, "av_clahe", w, h, 0xFFFFFFFFll / 256);
+    if (!n_apply) return AV_E_INVALID;
+    a.place.per = per_lut;
+    hipLaunchKernelGGL(clahe_lut_kernel, dim3(n_apply / per_apply * per_lut), dim3(256), 0, st, a);
     AV_LAUNCH_CHECK();
-    a.chunks = apply_chunks;                            // a band has th rows, one more or less where 1.0f / th rounds a boundary row across
-    a.per = (tiles_y + 1) * a.chunks;
-    hipLaunchKernelGGL(clahe_apply_kernel, dim3((unsigned)a.per * groups8), dim3(256), (size_t)2 * tiles_x * 256, st, a);
+    a.place.per = per_apply;
+    hipLaunchKernelGGL(clahe_apply_kernel, dim3(n_apply), dim3(256), (size_t)2 * tiles_x * 256, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -20,34 +20,19 @@ constexpr int DS_LANE = 16;                    // output pixels of one lane of t
 constexpr int DS_GEN = 256 * 16;               // output pixels of one workgroup of the generic path
 
 struct DsArgs {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
-    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
-    int n_src, n_img;
+    FramePlace place;
     int W;                                         // input width = f * w (the input's row pitch)
     int w, h;                                      // output size
-    int per;                                       // workgroups per image
     int nvx, items;                                // vector path: vectors per output row, (row, vector) items per image
 };
-
-__device__ __forceinline__ bool ds_place(const DsArgs& a, const uint8_t*& src, uint8_t*& dst, int& blk)
-{
-    const int img = blockIdx.x / a.per;
-    blk = blockIdx.x - img * a.per;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return false;
-    src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
-    return true;
-}
 
 template <int F>
 __global__ __launch_bounds__(256) void downscale_kernel(DsArgs a)
 {
-    const uint8_t* src; uint8_t* dst; int blk;
-    if (!ds_place(a, src, dst, blk)) return;
+    const int img = blockIdx.x / a.place.per, blk = blockIdx.x - img * a.place.per;
+    FrameAt f;
+    if (!av_frame_at(a.place, img, f)) return;
+    const uint8_t* src = f.src; uint8_t* dst = f.dst;
     const int item = blk * 256 + (int)threadIdx.x;                // < 2^24 / 16
     if (item >= a.items) return;
     const int y = item / a.nvx, vx = item - y * a.nvx;
@@ -89,8 +74,10 @@ __global__ __launch_bounds__(256) void downscale_kernel(DsArgs a)
 template <int F>
 __global__ __launch_bounds__(256) void downscale_generic_kernel(DsArgs a)
 {
-    const uint8_t* src; uint8_t* dst; int blk;
-    if (!ds_place(a, src, dst, blk)) return;
+    const int img = blockIdx.x / a.place.per, blk = blockIdx.x - img * a.place.per;
+    FrameAt f;
+    if (!av_frame_at(a.place, img, f)) return;
+    const uint8_t* src = f.src; uint8_t* dst = f.dst;
     const int w = a.w, npix = a.w * a.h;
     const int p0 = blk * DS_GEN;                                  // < 2^24
 #pragma unroll 2
@@ -119,19 +106,17 @@ int av_launch_downscale(const FrameSet& src, const FrameSet& dst, int n_groups, 
     if ((f != 2 && f != 4) || W <= 0 || H <= 0 || W % f || H % f) { av_set_error("av_downscale: factor %d does not bin %d x %d (2 or 4, dividing both sides)", f, W, H); return AV_E_INVALID; }
     DsArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride; a.index = dst.map;
-    a.n_src = src.base[1] ? 2 : 1; a.n_img = n_groups * a.n_src; a.W = W; a.w = W / f; a.h = H / f;
+    a.W = W; a.w = W / f; a.h = H / f;
     const bool vec = ds_vector_ok(src, dst, n_groups, a.w);
+    int per = (int)(((int64_t)a.w * a.h + DS_GEN - 1) / DS_GEN);
     if (vec) {
         a.nvx = a.w / DS_LANE;
         a.items = a.nvx * a.h;
-        a.per = (a.items + 255) / 256;
-    } else {
-        a.per = (int)(((int64_t)a.w * a.h + DS_GEN - 1) / DS_GEN);
+        per = (a.items + 255) / 256;
     }
-    const int64_t n_wg = (int64_t)a.per * a.n_img;
-    if (n_wg > 0x7FFFFFFFll) { av_set_error("av_downscale: %d images of %d x %d are more than one launch holds", a.n_img, W, H); return AV_E_INVALID; }
-    const dim3 grid((unsigned)n_wg), block(256);
+    const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, per, 1, "av_downscale", W, H);
+    if (!n_wg) return AV_E_INVALID;
+    const dim3 grid(n_wg), block(256);
     if (vec) {
         if (f == 2) hipLaunchKernelGGL(downscale_kernel<2>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(downscale_kernel<4>, grid, block, 0, st, a);

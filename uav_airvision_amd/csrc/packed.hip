@@ -1,31 +1,20 @@
 // packed.hip -- packed 10 / 12-bit camera transports (PFNC Mono10p / Mono12p, MIPI CSI-2 RAW10 / RAW12) to tightly packed 8-bit samples
 // (gfx950).  The byte layouts and the value rule are written out in include/airvision.h ("Packed 10 / 12-bit transports");
-// tests/packed_ref.py states them in NumPy and the kernel is held to it bit for bit.  A pure streaming pass like pixfmt.hip's: an image
-// is one run of groups (4 samples in 5 bytes, or 2 in 3; rows are tightly packed on both sides and a row is whole groups, so the image
-// is), a workgroup takes 256 lane spans of them.
-//   aligned body   bases and (with more than one image per camera) strides are whole 16-byte vectors: a lane owns a span that is whole
-//                  vectors on both sides -- 12-bit: 32 samples, three uint4 loads in, two uint4 stores out; 10-bit: 64 samples, five in,
-//                  four out -- and lane i's span follows lane i - 1's, as in pixfmt.hip's rgb8 body.  No lane reads a neighbour's bytes.
-//   group-wise     the ragged last groups of an image (one lane), and every group of a launch whose addresses or strides are not
-//                  whole vectors: one group per lane and round, neighbouring lanes on neighbouring groups, byte loads and stores
+// tests/packed_ref.py states them in NumPy and the kernel is held to it bit for bit.  A streaming pass (stream_pass.h) over groups (4
+// samples in 5 bytes, or 2 in 3; a row is whole groups, so the image is): the unit is one group, a lane's span is what is whole
+// vectors on both sides -- 12-bit: 32 samples, three uint4 loads in, two uint4 stores out; 10-bit: 64 samples, five in, four out.
 // Every sample goes through the GRAY16 rule on its left-justified value: s = min(255, (v << (16 - d)) >> shift).  For a packed mosaic
 // that is all this file does: the reduced 8-bit mosaic goes to a scratch and bayer.hip's 8-bit kernels run on it unchanged.
-// All byte offsets are 64-bit.
-#include "av_common.h"
+#include "stream_pass.h"
 
 namespace {
 
 constexpr int PK_P = 0, PK_CSI2 = 1;           // LAYOUT: PFNC "p" (little-endian bit stream, LSB first) / MIPI CSI-2 (high bytes first, low bits in the group's last byte)
 
 struct PackArgs {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // bytes between the frames of one camera
-    int n_src;                                     // 1 or 2
-    const int* index;                              // frame g is written to storage entry index[g] (null: g itself; negative: skipped)
-    int n_img, npix, shift;
-    int per;                                       // workgroups per image
-    int vec;                                       // every base, and every stride that is applied, is a whole 16-byte vector
+    FramePlace place;
+    int npix, vec;                                 // (stream_pass.h)
+    int shift;
 };
 
 template <int DEPTH> struct PkGeom {
@@ -34,7 +23,6 @@ template <int DEPTH> struct PkGeom {
     static constexpr int SPAN = DEPTH == 10 ? 64 : 32;     // samples of one lane's span in the aligned body
     static constexpr int IN_VEC = SPAN * DEPTH / 128;      // 5 / 3 uint4 in
     static constexpr int OUT_VEC = SPAN / 16;              // 4 / 2 uint4 out
-    static constexpr int BLOCK = 256 * SPAN;               // samples of one workgroup
 };
 
 template <int DEPTH>
@@ -72,44 +60,30 @@ __device__ __forceinline__ void pk_group(const uint8_t* p, uint8_t* q, int shift
 }
 
 template <int DEPTH, int LAYOUT>
-__global__ __launch_bounds__(256) void unpack_to_gray8_kernel(PackArgs a)
-{
+struct PackOp {
+    using Args = PackArgs;
     using G = PkGeom<DEPTH>;
-    const int img = blockIdx.x / a.per, blk = blockIdx.x - img * a.per;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return;
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
-    const int tid = threadIdx.x;
-    const int p0 = blk * G::BLOCK;                                // < 2^24
-    if (a.vec) {
-        const int p = p0 + tid * G::SPAN;
-        if (p + G::SPAN <= a.npix) {
-            const uint4* in = reinterpret_cast<const uint4*>(src + (int64_t)(p / G::GPX) * G::GB);      // SPAN samples are whole vectors: 48 p / 32 or 80 p / 64 bytes in
-            uint32_t d[4 * G::IN_VEC];
+    static constexpr int SPAN = G::SPAN, UNIT = G::GPX, UNROLL = 2;
+    static constexpr bool IMAGE_MINOR = false;
+    int shift;
+    __device__ __forceinline__ PackOp(const PackArgs& a, const FrameAt&, int, int) : shift(a.shift) {}
+    __device__ __forceinline__ void span(const uint8_t* src, uint8_t* dst, int p) const
+    {
+        const uint4* in = reinterpret_cast<const uint4*>(src + (int64_t)(p / G::GPX) * G::GB);      // SPAN samples are whole vectors: 48 p / 32 or 80 p / 64 bytes in
+        uint32_t d[4 * G::IN_VEC];
 #pragma unroll
-            for (int i = 0; i < G::IN_VEC; ++i) { const uint4 q = in[i]; d[4 * i] = q.x; d[4 * i + 1] = q.y; d[4 * i + 2] = q.z; d[4 * i + 3] = q.w; }
-            uint32_t o[4 * G::OUT_VEC];
+        for (int i = 0; i < G::IN_VEC; ++i) { const uint4 q = in[i]; d[4 * i] = q.x; d[4 * i + 1] = q.y; d[4 * i + 2] = q.z; d[4 * i + 3] = q.w; }
+        uint32_t o[4 * G::OUT_VEC];
 #pragma unroll
-            for (int i = 0; i < 4 * G::OUT_VEC; ++i) o[i] = 0u;
+        for (int i = 0; i < 4 * G::OUT_VEC; ++i) o[i] = 0u;
 #pragma unroll
-            for (int k = 0; k < G::SPAN; ++k) o[k >> 2] |= pk_reduce<DEPTH>(pk_sample<DEPTH, LAYOUT>(d, k), a.shift) << (8 * (k & 3));
-            uint4* out = reinterpret_cast<uint4*>(dst + p);
+        for (int k = 0; k < G::SPAN; ++k) o[k >> 2] |= pk_reduce<DEPTH>(pk_sample<DEPTH, LAYOUT>(d, k), shift) << (8 * (k & 3));
+        uint4* out = reinterpret_cast<uint4*>(dst + p);
 #pragma unroll
-            for (int i = 0; i < G::OUT_VEC; ++i) out[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
-        } else {
-            for (int q = p; q < a.npix; q += G::GPX) pk_group<DEPTH, LAYOUT>(src + (int64_t)(q / G::GPX) * G::GB, dst + q, a.shift);      // the image's ragged end: one lane, fewer than SPAN / GPX groups
-        }
-        return;
+        for (int i = 0; i < G::OUT_VEC; ++i) out[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
     }
-    const int n_grp = a.npix / G::GPX, g0 = p0 / G::GPX;
-#pragma unroll 2
-    for (int j = 0; j < G::SPAN / G::GPX; ++j) {
-        const int q = g0 + j * 256 + tid;
-        if (q < n_grp) pk_group<DEPTH, LAYOUT>(src + (int64_t)q * G::GB, dst + (int64_t)q * G::GPX, a.shift);
-    }
-}
+    __device__ __forceinline__ void unit(const uint8_t* src, uint8_t* dst, int q) const { pk_group<DEPTH, LAYOUT>(src + (int64_t)q * G::GB, dst + (int64_t)q * G::GPX, shift); }
+};
 
 }  // namespace
 
@@ -121,19 +95,18 @@ int av_launch_unpack_to_gray8(const FrameSet& src, const FrameSet& dst, int n_gr
     const bool csi2 = av_pixfmt_packed_csi2(fmt);
     PackArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
-    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.n_img = n_groups * a.n_src; a.npix = w * h; a.shift = shift;
-    const int block = depth == 10 ? PkGeom<10>::BLOCK : PkGeom<12>::BLOCK;
-    a.per = (a.npix + block - 1) / block;
+    a.npix = w * h; a.shift = shift;
     a.vec = av_frames_vec16(src, dst, n_groups);
-    if ((int64_t)a.per * a.n_img > 0x7FFFFFFFll) { av_set_error("av_to_gray8: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
-    const dim3 grid((unsigned)(a.per * a.n_img)), blockdim(256);
+    const int block = 256 * (depth == 10 ? PkGeom<10>::SPAN : PkGeom<12>::SPAN);      // samples of one workgroup
+    const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, (a.npix + block - 1) / block, 1, "av_to_gray8", w, h);
+    if (!n_wg) return AV_E_INVALID;
+    const dim3 grid(n_wg), blockdim(256);
     if (depth == 10) {
-        if (csi2) hipLaunchKernelGGL((unpack_to_gray8_kernel<10, PK_CSI2>), grid, blockdim, 0, st, a);
-        else hipLaunchKernelGGL((unpack_to_gray8_kernel<10, PK_P>), grid, blockdim, 0, st, a);
+        if (csi2) hipLaunchKernelGGL((stream_pass_kernel<PackOp<10, PK_CSI2>>), grid, blockdim, 0, st, a);
+        else hipLaunchKernelGGL((stream_pass_kernel<PackOp<10, PK_P>>), grid, blockdim, 0, st, a);
     } else {
-        if (csi2) hipLaunchKernelGGL((unpack_to_gray8_kernel<12, PK_CSI2>), grid, blockdim, 0, st, a);
-        else hipLaunchKernelGGL((unpack_to_gray8_kernel<12, PK_P>), grid, blockdim, 0, st, a);
+        if (csi2) hipLaunchKernelGGL((stream_pass_kernel<PackOp<12, PK_CSI2>>), grid, blockdim, 0, st, a);
+        else hipLaunchKernelGGL((stream_pass_kernel<PackOp<12, PK_P>>), grid, blockdim, 0, st, a);
     }
     AV_LAUNCH_CHECK();
     return AV_OK;

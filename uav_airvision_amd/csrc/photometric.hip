@@ -2,87 +2,69 @@
 // The arithmetic is written out in include/airvision.h ("Photometric calibration"); tests/photometric_ref.py states it in NumPy and the
 // kernel is held to it bit for bit:
 //     out = min(255, (response[p] * gain[x] + (1 << 19)) >> 20)        response Q8 (absent: p << 8), gain Q12 (absent: 4096)
-// A pure streaming pass shaped like to_gray8_kernel (pixfmt.hip): an image is one run of w * h pixels, a workgroup takes PH_BLOCK.
-//   aligned body   bases, applied strides and the gain base are whole 16-byte vectors: a lane takes 16 pixels -- one uint4 of pixels and
-//                  two uint4 of gains in, 16 table look-ups, one uint4 out
-//   byte-wise      the ragged last 1 .. 15 pixels of an image, and every pixel of a launch whose addresses or strides are not whole
-//                  vectors: one pixel per lane and round, neighbouring lanes on neighbouring pixels
+// A streaming pass (stream_pass.h): a lane's span is 16 pixels -- one uint4 of pixels and two uint4 of gains in, 16 table look-ups,
+// one uint4 out -- and the unit is one pixel.  The aligned body needs the gain bases to be whole 16-byte vectors too (ph_vector_ok).
 // The 512-byte response table of the workgroup's camera is staged into LDS once per workgroup (256 lanes, one entry each).
 // In place (src == dst, same list) is correct: a lane reads its own pixels before it writes them and no lane reads another's.
 // Workgroup order: image-minor (id = block * n_img + image).  The gain map is one per camera for ALL images of a launch, so the
 // workgroups in flight at any time read the same few KB of it from L2 while the pixels stream; with the image-major order of
 // pixfmt.hip every image would walk the whole map (4.6 MB per camera at 1920 x 1200, more than one L2) on its own.
-// All byte offsets are 64-bit.
-#include "av_common.h"
+#include "stream_pass.h"
 
 namespace {
 
 constexpr int PH_LANE = 16;                    // pixels of one lane = one 16-byte store
-constexpr int PH_BLOCK = 256 * PH_LANE;        // pixels of one workgroup
 
 struct PhArgs {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
-    int n_src;                                     // 1 or 2
-    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
-    int src_listed;                                // the source lies in entries too (in place in a listed set): read at index[g] as well
-    int n_img, npix;
-    int vec;                                       // every base (the gains' too), and every stride that is applied, is a whole 16-byte vector
+    FramePlace place;
+    int npix, vec;                                 // (stream_pass.h; vec: the gain bases are whole vectors as well)
     const uint16_t* resp0; const uint16_t* resp1;  // [256] Q8 per camera
     const uint16_t* gain0; const uint16_t* gain1;  // [npix] Q12 per camera
 };
 
+__shared__ uint16_t ph_tab[256];               // the response table of the workgroup's camera (instances with one)
+
 __device__ __forceinline__ uint32_t ph_out(uint32_t r, uint32_t g) { return min(255u, (r * g + (1u << 19)) >> 20); }      // r <= 65280: r * g + 2^19 < 2^32
 
 template <bool HAS_RESPONSE, bool HAS_GAIN>
-__global__ __launch_bounds__(256) void photometric_kernel(PhArgs a)
-{
-    __shared__ uint16_t tab[256];
-    const int blk = blockIdx.x / a.n_img, img = blockIdx.x - blk * a.n_img;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return;
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (a.src_listed ? e : (int64_t)g) * a.src_stride;
-    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
-    const uint16_t* gain = cam ? a.gain1 : a.gain0;
-    const int tid = threadIdx.x;
-    if (HAS_RESPONSE) {
-        tab[tid] = (cam ? a.resp1 : a.resp0)[tid];
-        __syncthreads();
-    }
-    auto resp = [&](uint32_t p) -> uint32_t { return HAS_RESPONSE ? (uint32_t)tab[p] : p << 8; };
-    const int p0 = blk * PH_BLOCK;                                // < 2^24
-    if (a.vec) {
-        const int p = p0 + tid * PH_LANE;
-        if (p + PH_LANE <= a.npix) {
-            const uint4 q = *reinterpret_cast<const uint4*>(src + p);
-            const uint32_t d[4] = {q.x, q.y, q.z, q.w};
-            uint32_t gw[8];
-            if (HAS_GAIN) {
-                const uint4* gp = reinterpret_cast<const uint4*>(gain + p);
-                const uint4 g0 = gp[0], g1 = gp[1];
-                gw[0] = g0.x; gw[1] = g0.y; gw[2] = g0.z; gw[3] = g0.w; gw[4] = g1.x; gw[5] = g1.y; gw[6] = g1.z; gw[7] = g1.w;
-            }
-            uint32_t o[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k < PH_LANE; ++k) {
-                const uint32_t px = (d[k >> 2] >> (8 * (k & 3))) & 255u;
-                const uint32_t gk = HAS_GAIN ? (gw[k >> 1] >> (16 * (k & 1))) & 0xFFFFu : 4096u;
-                o[k >> 2] |= ph_out(resp(px), gk) << (8 * (k & 3));
-            }
-            *reinterpret_cast<uint4*>(dst + p) = make_uint4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (int k = p; k < a.npix; ++k) dst[k] = (uint8_t)ph_out(resp(src[k]), HAS_GAIN ? (uint32_t)gain[k] : 4096u);      // the image's ragged end: one lane, < 16 pixels
+struct PhOp {
+    using Args = PhArgs;
+    static constexpr int SPAN = PH_LANE, UNIT = 1, UNROLL = 4;
+    static constexpr bool IMAGE_MINOR = true;
+    const uint16_t* gain;
+    __device__ __forceinline__ PhOp(const PhArgs& a, const FrameAt& f, int, int tid) : gain(f.cam ? a.gain1 : a.gain0)
+    {
+        if constexpr (HAS_RESPONSE) {
+            ph_tab[tid] = (f.cam ? a.resp1 : a.resp0)[tid];
+            __syncthreads();
         }
-        return;
     }
-#pragma unroll 4
-    for (int j = 0; j < PH_LANE; ++j) {
-        const int p = p0 + j * 256 + tid;
-        if (p < a.npix) dst[p] = (uint8_t)ph_out(resp(src[p]), HAS_GAIN ? (uint32_t)gain[p] : 4096u);
+    __device__ __forceinline__ uint32_t resp(uint32_t p) const
+    {
+        if constexpr (HAS_RESPONSE) return ph_tab[p];
+        else return p << 8;
     }
-}
+    __device__ __forceinline__ void span(const uint8_t* src, uint8_t* dst, int p) const
+    {
+        const uint4 q = *reinterpret_cast<const uint4*>(src + p);
+        const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+        uint32_t gw[8];
+        if (HAS_GAIN) {
+            const uint4* gp = reinterpret_cast<const uint4*>(gain + p);
+            const uint4 g0 = gp[0], g1 = gp[1];
+            gw[0] = g0.x; gw[1] = g0.y; gw[2] = g0.z; gw[3] = g0.w; gw[4] = g1.x; gw[5] = g1.y; gw[6] = g1.z; gw[7] = g1.w;
+        }
+        uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < PH_LANE; ++k) {
+            const uint32_t px = (d[k >> 2] >> (8 * (k & 3))) & 255u;
+            const uint32_t gk = HAS_GAIN ? (gw[k >> 1] >> (16 * (k & 1))) & 0xFFFFu : 4096u;
+            o[k >> 2] |= ph_out(resp(px), gk) << (8 * (k & 3));
+        }
+        *reinterpret_cast<uint4*>(dst + p) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    __device__ __forceinline__ void unit(const uint8_t* src, uint8_t* dst, int p) const { dst[p] = (uint8_t)ph_out(resp(src[p]), HAS_GAIN ? (uint32_t)gain[p] : 4096u); }
+};
 
 // the one rule that picks the body (av_launch_photometric; av_photometric_vector_path reports it)
 bool ph_vector_ok(const FrameSet& src, const FrameSet& dst, int n_groups, const uint16_t* gain0, const uint16_t* gain1)
@@ -96,16 +78,15 @@ int ph_launch(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int
 {
     PhArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
-    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.src_listed = src.map != nullptr; a.n_img = n_groups * a.n_src; a.npix = w * h;
+    a.npix = w * h;
     a.resp0 = resp0; a.resp1 = resp1; a.gain0 = gain0; a.gain1 = gain1;
     a.vec = ph_vector_ok(src, dst, n_groups, gain0, gain1);
-    const int per = (a.npix + PH_BLOCK - 1) / PH_BLOCK;
-    if ((int64_t)per * a.n_img > 0x7FFFFFFFll) { av_set_error("av_photometric: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
-    const dim3 grid((unsigned)(per * a.n_img)), block(256);
-    if (resp0 && gain0) hipLaunchKernelGGL((photometric_kernel<true, true>), grid, block, 0, st, a);
-    else if (resp0) hipLaunchKernelGGL((photometric_kernel<true, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((photometric_kernel<false, true>), grid, block, 0, st, a);
+    const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, (a.npix + 256 * PH_LANE - 1) / (256 * PH_LANE), 1, "av_photometric", w, h);
+    if (!n_wg) return AV_E_INVALID;
+    const dim3 grid(n_wg), block(256);
+    if (resp0 && gain0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, true>>), grid, block, 0, st, a);
+    else if (resp0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, false>>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((stream_pass_kernel<PhOp<false, true>>), grid, block, 0, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

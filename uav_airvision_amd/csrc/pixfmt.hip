@@ -1,28 +1,17 @@
 // pixfmt.hip -- camera frames of the other pixel formats (16-bit grey, RGB / BGR, RGBA / BGRA) to tightly packed 8-bit grey (gfx950).
 // The arithmetic is written out in include/airvision.h (av_to_gray8); tests/pixfmt_ref.py states it in NumPy and the kernel is held
-// to it bit for bit.  A pure streaming pass: an image is one run of w * h pixels (rows are tightly packed on both sides), a workgroup
-// takes PF_BLOCK of them.
-//   aligned body   bases and (with more than one image per camera) strides are whole 16-byte vectors: a lane takes 16 pixels,
-//                  2 / 3 / 4 uint4 loads in, one uint4 store out
-//   byte-wise      the ragged last 1 .. 15 pixels of an image, and every pixel of a launch whose addresses or strides are not whole
-//                  vectors: one pixel per lane and round, neighbouring lanes on neighbouring pixels
-// All byte offsets are 64-bit: 2^24 pixels x 4 B x thousands of streams passes 2^32.
-#include "av_common.h"
+// to it bit for bit.  A streaming pass (stream_pass.h): a lane's span is 16 pixels, 2 / 3 / 4 uint4 loads in and one uint4 store out;
+// the unit is one pixel.  Never in place.
+#include "stream_pass.h"
 
 namespace {
 
 constexpr int PF_LANE = 16;                    // output pixels of one lane = one 16-byte store
-constexpr int PF_BLOCK = 256 * PF_LANE;        // pixels of one workgroup
 
 struct PixArgs {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
-    int n_src;                                     // 1 or 2
-    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
-    int n_img, npix, fmt, shift;
-    int per;                                       // workgroups per image
-    int vec;                                       // every base, and every stride that is applied, is a whole 16-byte vector
+    FramePlace place;
+    int npix, vec;                                 // (stream_pass.h)
+    int shift;
 };
 
 __host__ __device__ constexpr int pf_bytes(int fmt) { return fmt == AV_PIX_GRAY8 ? 1 : fmt == AV_PIX_GRAY16 ? 2 : (fmt == AV_PIX_RGB8 || fmt == AV_PIX_BGR8) ? 3 : 4; }
@@ -60,32 +49,18 @@ __device__ __forceinline__ uint4 pf_group(const uint4* in, int shift)
 }
 
 template <int FMT>
-__global__ __launch_bounds__(256) void to_gray8_kernel(PixArgs a)
-{
-    constexpr int B = pf_bytes(FMT);
-    const int img = blockIdx.x / a.per, blk = blockIdx.x - img * a.per;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return;
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
-    const int tid = threadIdx.x;
-    const int p0 = blk * PF_BLOCK;                                // < 2^24
-    if (a.vec) {
-        const int p = p0 + tid * PF_LANE;
-        if (p + PF_LANE <= a.npix) {
-            *reinterpret_cast<uint4*>(dst + p) = pf_group<FMT>(reinterpret_cast<const uint4*>(src + (int64_t)p * B), a.shift);
-        } else {
-            for (int q = p; q < a.npix; ++q) dst[q] = pf_pixel<FMT>(src + (int64_t)q * B, a.shift);      // the image's ragged end: one lane, < 16 pixels
-        }
-        return;
+struct PixOp {
+    using Args = PixArgs;
+    static constexpr int SPAN = PF_LANE, UNIT = 1, UNROLL = 4, B = pf_bytes(FMT);
+    static constexpr bool IMAGE_MINOR = false;
+    int shift;
+    __device__ __forceinline__ PixOp(const PixArgs& a, const FrameAt&, int, int) : shift(a.shift) {}
+    __device__ __forceinline__ void span(const uint8_t* src, uint8_t* dst, int p) const
+    {
+        *reinterpret_cast<uint4*>(dst + p) = pf_group<FMT>(reinterpret_cast<const uint4*>(src + (int64_t)p * B), shift);
     }
-#pragma unroll 4
-    for (int j = 0; j < PF_LANE; ++j) {
-        const int p = p0 + j * 256 + tid;
-        if (p < a.npix) dst[p] = pf_pixel<FMT>(src + (int64_t)p * B, a.shift);
-    }
-}
+    __device__ __forceinline__ void unit(const uint8_t* src, uint8_t* dst, int p) const { dst[p] = pf_pixel<FMT>(src + (int64_t)p * B, shift); }
+};
 
 }  // namespace
 
@@ -164,18 +139,17 @@ int av_launch_to_gray8(const FrameSet& src, const FrameSet& dst, int n_groups, i
     if (fmt >= AV_PIX_BAYER_RGGB8) return av_launch_bayer_to_gray8(src, dst, n_groups, w, h, fmt, shift, st);      // a 3 x 3 stencil over rows: bayer.hip
     PixArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
-    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.n_img = n_groups * a.n_src; a.npix = w * h; a.fmt = fmt; a.shift = shift;
-    a.per = (a.npix + PF_BLOCK - 1) / PF_BLOCK;
+    a.npix = w * h; a.shift = shift;
     a.vec = av_frames_vec16(src, dst, n_groups);
-    if ((int64_t)a.per * a.n_img > 0x7FFFFFFFll) { av_set_error("av_to_gray8: %d images of %d x %d are more than one launch holds", a.n_img, w, h); return AV_E_INVALID; }
-    const dim3 grid((unsigned)(a.per * a.n_img)), block(256);
+    const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, (a.npix + 256 * PF_LANE - 1) / (256 * PF_LANE), 1, "av_to_gray8", w, h);
+    if (!n_wg) return AV_E_INVALID;
+    const dim3 grid(n_wg), block(256);
     switch (fmt) {
-    case AV_PIX_GRAY16: hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_GRAY16>, grid, block, 0, st, a); break;
-    case AV_PIX_RGB8:   hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_RGB8>, grid, block, 0, st, a); break;
-    case AV_PIX_BGR8:   hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_BGR8>, grid, block, 0, st, a); break;
-    case AV_PIX_RGBA8:  hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_RGBA8>, grid, block, 0, st, a); break;
-    case AV_PIX_BGRA8:  hipLaunchKernelGGL(to_gray8_kernel<AV_PIX_BGRA8>, grid, block, 0, st, a); break;
+    case AV_PIX_GRAY16: hipLaunchKernelGGL(stream_pass_kernel<PixOp<AV_PIX_GRAY16>>, grid, block, 0, st, a); break;
+    case AV_PIX_RGB8:   hipLaunchKernelGGL(stream_pass_kernel<PixOp<AV_PIX_RGB8>>, grid, block, 0, st, a); break;
+    case AV_PIX_BGR8:   hipLaunchKernelGGL(stream_pass_kernel<PixOp<AV_PIX_BGR8>>, grid, block, 0, st, a); break;
+    case AV_PIX_RGBA8:  hipLaunchKernelGGL(stream_pass_kernel<PixOp<AV_PIX_RGBA8>>, grid, block, 0, st, a); break;
+    case AV_PIX_BGRA8:  hipLaunchKernelGGL(stream_pass_kernel<PixOp<AV_PIX_BGRA8>>, grid, block, 0, st, a); break;
     default: av_set_error("av_to_gray8: no conversion kernel for pixel format %d", fmt); return AV_E_INVALID;
     }
     AV_LAUNCH_CHECK();

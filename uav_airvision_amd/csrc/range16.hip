@@ -8,9 +8,10 @@
 //                          bins: neighbouring samples mostly share one); sample by sample for the ragged end and unaligned launches
 //   range16_pick_kernel    one wavefront per group, 64 lanes x 64 bins: prefix sums across the wavefront, b_lo and b_hi, the
 //                          minimum-span rule, the record {lo, hi, m}; the group's histogram is left zeroed for the next launch
-//   range16_apply_kernel   the streaming shape of to_gray8_kernel<AV_PIX_GRAY16>: 16 pixels per lane, two 16-byte loads, one store
+//   apply                  a streaming pass (stream_pass.h): a lane's span is 16 pixels, two 16-byte loads in and one store out;
+//                          the unit is one pixel.  Its state is the group's record (or the caller's window)
 // A group is the images of one FrameSet group (one camera or the two of a stereo pair, pooled).  All byte offsets are 64-bit.
-#include "av_common.h"
+#include "stream_pass.h"
 
 namespace {
 
@@ -18,17 +19,10 @@ constexpr int R16_BINS = 4096;
 static_assert(R16_BINS + 4 == AV_GRAY16_WORK_WORDS, "a group's histogram and record are what the header promises");
 constexpr int R16_CHUNK = 65536;               // samples of one histogram workgroup: 32 rounds of 256 lanes x 8 samples
 constexpr int R16_LANE = 16;                   // output pixels of one lane of the apply kernel = one 16-byte store
-constexpr int R16_BLOCK = 256 * R16_LANE;      // pixels of one apply workgroup
 
 struct Range16Args {
-    const uint8_t* src0; const uint8_t* src1;      // image i of the launch: camera i % n_src, group i / n_src
-    uint8_t* dst0; uint8_t* dst1;
-    int64_t src_stride, dst_stride;                // bytes between the groups of one camera
-    int n_src;                                     // 1 or 2: the images pooled into one group
-    const int* index;                              // group g is written to storage entry index[g] (null: g itself; negative: skipped)
-    int npix;
-    int per;                                       // workgroups per image (of the kernel launched)
-    int vec;                                       // every base, and every stride that is applied, is a whole 16-byte vector
+    FramePlace place;                              // (n_src: the images pooled into one group)
+    int npix, vec;                                 // (stream_pass.h; the histogram: the source's alignment alone)
     uint32_t* hist;                                // [groups][R16_BINS], zero between launches
     uint32_t* rec;                                 // [groups][4]: lo, hi, m, 0; apply: null = the window below for every group
     uint32_t k_lo, k_hi, min_span;                 // pick: samples that may saturate at each end, smallest span
@@ -42,11 +36,11 @@ __device__ __forceinline__ uint32_t r16_map(uint32_t v, uint32_t lo, uint32_t hi
 __global__ __launch_bounds__(256) void range16_hist_kernel(Range16Args a)
 {
     __shared__ uint32_t bins[R16_BINS];
-    const int img = blockIdx.x / a.per, blk = blockIdx.x - img * a.per;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    if (a.index && a.index[g] < 0) return;
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    const int tid = threadIdx.x;
+    const int img = blockIdx.x / a.place.per, blk = blockIdx.x - img * a.place.per;
+    FrameAt f;
+    if (!av_frame_at(a.place, img, f)) return;      // (no destination: f.dst is not used)
+    const uint8_t* src = f.src;
+    const int tid = threadIdx.x, g = f.g;
     for (int b = tid; b < R16_BINS; b += 256) bins[b] = 0u;
     __syncthreads();
     const int p0 = blk * R16_CHUNK, p1 = min(a.npix, p0 + R16_CHUNK);      // < 2^24
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(256) void range16_hist_kernel(Range16Args a)
 __global__ __launch_bounds__(64) void range16_pick_kernel(Range16Args a)
 {
     const int g = blockIdx.x, lane = threadIdx.x;
-    if (a.index && a.index[g] < 0) return;
+    if (av_frame_entry(a.place, g) < 0) return;
     uint4* mine = reinterpret_cast<uint4*>(a.hist + (size_t)g * R16_BINS + lane * 64);      // bins 64 lane .. 64 lane + 63
     uint32_t v[64];
 #pragma unroll
@@ -136,34 +130,22 @@ __device__ __forceinline__ uint4 r16_group(const uint4* in, uint32_t lo, uint32_
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-__global__ __launch_bounds__(256) void range16_apply_kernel(Range16Args a)
-{
-    const int img = blockIdx.x / a.per, blk = blockIdx.x - img * a.per;
-    const int cam = img % a.n_src, g = img / a.n_src;
-    const int64_t e = a.index ? a.index[g] : g;
-    if (e < 0) return;
-    uint32_t lo = a.lo, hi = a.hi, m = a.m;
-    if (a.rec) { const uint32_t* r = a.rec + 4 * (size_t)g; lo = r[0]; hi = r[1]; m = r[2]; }
-    const uint8_t* src = (cam ? a.src1 : a.src0) + (int64_t)g * a.src_stride;
-    uint8_t* dst = (cam ? a.dst1 : a.dst0) + e * a.dst_stride;
-    const int tid = threadIdx.x;
-    if (a.range_out && blk == 0 && cam == 0 && tid == 0) { a.range_out[2 * g] = (int32_t)lo; a.range_out[2 * g + 1] = (int32_t)hi; }
-    const int p0 = blk * R16_BLOCK;                               // < 2^24
-    if (a.vec) {
-        const int p = p0 + tid * R16_LANE;
-        if (p + R16_LANE <= a.npix) {
-            *reinterpret_cast<uint4*>(dst + p) = r16_group(reinterpret_cast<const uint4*>(src + (int64_t)p * 2), lo, hi, m);
-        } else {
-            for (int q = p; q < a.npix; ++q) dst[q] = (uint8_t)r16_map(r16_sample(src + (int64_t)q * 2), lo, hi, m);      // the image's ragged end: one lane, < 16 pixels
-        }
-        return;
+struct Range16Op {
+    using Args = Range16Args;
+    static constexpr int SPAN = R16_LANE, UNIT = 1, UNROLL = 4;
+    static constexpr bool IMAGE_MINOR = false;
+    uint32_t lo, hi, m;
+    __device__ __forceinline__ Range16Op(const Range16Args& a, const FrameAt& f, int blk, int tid) : lo(a.lo), hi(a.hi), m(a.m)
+    {
+        if (a.rec) { const uint32_t* r = a.rec + 4 * (size_t)f.g; lo = r[0]; hi = r[1]; m = r[2]; }
+        if (a.range_out && blk == 0 && f.cam == 0 && tid == 0) { a.range_out[2 * f.g] = (int32_t)lo; a.range_out[2 * f.g + 1] = (int32_t)hi; }
     }
-#pragma unroll 4
-    for (int j = 0; j < R16_LANE; ++j) {
-        const int p = p0 + j * 256 + tid;
-        if (p < a.npix) dst[p] = (uint8_t)r16_map(r16_sample(src + (int64_t)p * 2), lo, hi, m);
+    __device__ __forceinline__ void span(const uint8_t* src, uint8_t* dst, int p) const
+    {
+        *reinterpret_cast<uint4*>(dst + p) = r16_group(reinterpret_cast<const uint4*>(src + (int64_t)p * 2), lo, hi, m);
     }
-}
+    __device__ __forceinline__ void unit(const uint8_t* src, uint8_t* dst, int p) const { dst[p] = (uint8_t)r16_map(r16_sample(src + (int64_t)p * 2), lo, hi, m); }
+};
 
 }  // namespace
 
@@ -184,20 +166,19 @@ int av_launch_gray16_range(const FrameSet& src, const FrameSet& dst, int n_group
     if (n_groups <= 0) return AV_OK;
     Range16Args a;
     memset(&a, 0, sizeof(a));
-    a.src0 = src.base[0]; a.src1 = src.base[1]; a.dst0 = dst.base[0]; a.dst1 = dst.base[1]; a.src_stride = src.stride; a.dst_stride = dst.stride;
-    a.n_src = src.base[1] ? 2 : 1; a.index = dst.map; a.npix = w * h;
+    a.npix = w * h;
     a.hist = r.hist; a.range_out = r.range_out;
-    const int n_img = n_groups * a.n_src;
-    const int per_hist = (a.npix + R16_CHUNK - 1) / R16_CHUNK, per_apply = (a.npix + R16_BLOCK - 1) / R16_BLOCK;
-    if ((int64_t)per_apply * n_img > 0x7FFFFFFFll) { av_set_error("av_to_gray8_range: %d images of %d x %d are more than one launch holds", n_img, w, h); return AV_E_INVALID; }
+    const int per_hist = (a.npix + R16_CHUNK - 1) / R16_CHUNK, per_apply = (a.npix + 256 * R16_LANE - 1) / (256 * R16_LANE);
+    const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, per_apply, 1, "av_to_gray8_range", w, h);      // the larger of the two grids
+    if (!n_wg) return AV_E_INVALID;
     if (r.mode == AV_GRAY16_AUTO) {
         if (!r.hist || !r.rec) { av_set_error("av_to_gray8_range: AV_GRAY16_AUTO needs a histogram and a record buffer"); return AV_E_INVALID; }
-        const int64_t N = (int64_t)a.npix * a.n_src;                                          // samples of a group: 64 bits on the host
+        const int64_t N = (int64_t)a.npix * a.place.n_src;                                          // samples of a group: 64 bits on the host
         a.k_lo = (uint32_t)(N * r.ppm_lo / 1000000); a.k_hi = (uint32_t)(N * r.ppm_hi / 1000000); a.min_span = (uint32_t)r.min_span;
         a.rec = r.rec;
-        a.per = per_hist;
+        a.place.per = per_hist;
         a.vec = av_frames_vec16(src, FrameSet{{nullptr, nullptr}, 0, dst.map}, n_groups);      // the histogram reads only: the source's alignment alone
-        hipLaunchKernelGGL(range16_hist_kernel, dim3((unsigned)(per_hist * n_img)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(range16_hist_kernel, dim3((unsigned)(per_hist * a.place.n_img)), dim3(256), 0, st, a);
         AV_LAUNCH_CHECK();
         hipLaunchKernelGGL(range16_pick_kernel, dim3((unsigned)n_groups), dim3(64), 0, st, a);
         AV_LAUNCH_CHECK();
@@ -205,9 +186,9 @@ int av_launch_gray16_range(const FrameSet& src, const FrameSet& dst, int n_group
         const uint32_t span = (uint32_t)(r.hi - r.lo);
         a.lo = (uint32_t)r.lo; a.hi = (uint32_t)r.hi; a.m = ((255u << 16) + span / 2) / span;
     }
-    a.per = per_apply;
+    a.place.per = per_apply;
     a.vec = av_frames_vec16(src, dst, n_groups);
-    hipLaunchKernelGGL(range16_apply_kernel, dim3((unsigned)(per_apply * n_img)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(stream_pass_kernel<Range16Op>, dim3(n_wg), dim3(256), 0, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
