@@ -65,6 +65,12 @@ int av_pyramid_layout(int w, int h, int levels, av_pyr_layout* out);
  * (reference: image_processing/pyramid_builder.py:22-48 is a pass-through). */
 int av_pyramid_build(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h, int levels,
                      uint8_t* pyr_dev, int64_t pyr_stride, void* stream);
+/* The same, levels 1 and up only: the level-0 region of every pyramid is left as it is -- for a caller that keeps the image itself as
+ * level 0 (what the front-end engine does with resident frames).  That holds where the fused level-0 + level-1 kernel takes the image
+ * (w a multiple of 16 with w % 128 == 0 or >= 32, h a multiple of 32, both >= 64, image rows dword-aligned); any other image has its
+ * level 1 filtered from the padded level 0, which is then written as by av_pyramid_build. */
+int av_pyramid_build_levels(const uint8_t* img_dev, int64_t img_stride, int n_img, int w, int h, int levels,
+                            uint8_t* pyr_dev, int64_t pyr_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cv2.calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(win,win),

@@ -209,6 +209,7 @@ SIGNATURES = {
     'av_device_count': (C.c_int, []),
     'av_pyramid_layout': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(PyrLayout)]),
     'av_pyramid_build': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    'av_pyramid_build_levels': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     'av_lk_track': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int,
                               C.c_int, C.c_int, C.c_double, C.c_double, _P]),
     'av_fast_detect': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),

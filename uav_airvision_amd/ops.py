@@ -22,18 +22,25 @@ def pyramid_layout(w, h, levels):
     return lay
 
 
-def build_pyramids(images, levels, device=0):
-    """images: uint8[n,h,w] (numpy or cuda tensor) -> (uint8 cuda tensor [n, bytes], layout)."""
+def build_pyramids(images, levels, device=0, write_level0=True, out=None):
+    """images: uint8[n,h,w] (numpy or cuda tensor) -> (uint8 cuda tensor [n, bytes], layout).
+
+    write_level0=False builds levels 1 and up only (av_pyramid_build_levels): the level-0 region keeps what `out` (a uint8 cuda
+    tensor [n, bytes], or a fresh uninitialised one) held."""
     t = torch.as_tensor(images)
     if t.dim() == 2:
         t = t[None]
     t = t.to(_dev(device), dtype=torch.uint8).contiguous()
     n, h, w = t.shape
     lay = pyramid_layout(w, h, levels)
-    pyr = torch.empty((n, lay.bytes), dtype=torch.uint8, device=_dev(device))
+    if out is None:
+        out = torch.empty((n, lay.bytes), dtype=torch.uint8, device=_dev(device))
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, lay.bytes) or not out.is_contiguous() or out.device != t.device:
+        raise ValueError('out must be a contiguous uint8 tensor [%d, %d] on %s' % (n, lay.bytes, t.device))
+    build = N.lib().av_pyramid_build if write_level0 else N.lib().av_pyramid_build_levels
     with torch.cuda.device(device):
-        N.check(N.lib().av_pyramid_build(N.dptr(t), w * h, n, w, h, levels, N.dptr(pyr), lay.bytes, N.current_stream()))
-    return pyr, lay
+        N.check(build(N.dptr(t), w * h, n, w, h, levels, N.dptr(out), lay.bytes, N.current_stream()))
+    return out, lay
 
 
 def pyramid_level(pyr_row, lay, level, with_border=False):
