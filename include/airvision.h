@@ -906,6 +906,16 @@ int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* st
  * reallocations after the first step (0 in a correctly pre-sized run), min camera states, max camera states,
  * min map features, max map features].  bench.py uses it to prove that the timed region is the steady state. */
 int  av_msckf_batch_counters(av_msckf_batch* b, int64_t out8[8]);
+/* What the batch really launched (no reference counterpart; drains the queue first): out17[0] = number of stream groups (a batch
+ * without sub-batches reports 1; at most 8), and for group g out17[1 + 2g] = its stream count, out17[2 + 2g] = the workgroup size the
+ * per-stream filter kernels (dk_begin4 / dk_cov / dk_mid / dk_finish) were launched with in the group's LAST enqueued step: 64 (one
+ * wavefront per stream) or 256 (four); 0 before the group's first step and under AV_MSCKF_STORE=host.  The value is recorded at
+ * the launch, not recomputed here.  The rule it reports is per GROUP, not per batch: a device-resident batch of n_streams >= 1,024 is
+ * split into 2 groups of ceil(n_streams / 2) streams (the last one holds the remainder; AV_MSCKF_GROUPS overrides the count), and
+ * each group takes 64 when ITS stream count is >= 1,024, else 256 (AV_DK_WG=64|256 forces one for all groups).  So 1,023 streams run as
+ * [(1023, 256)], 1,024 as [(512, 256), (512, 256)], 2,047 as [(1024, 64), (1023, 256)], and only from 2,048 streams up --
+ * [(1024, 64), (1024, 64)] -- is a batch "two groups, one wavefront per stream" throughout. */
+int  av_msckf_batch_launch_shape(av_msckf_batch* b, int32_t out17[17]);
 /* Parity-test tap (SURVEY 8b "get_state / get_cov for parity tests"): the values the reference computes inside gating_test and
  * measurement_update (msckf.py:604-612, 548-602) but never returns.  After av_msckf_batch_debug_capture(b, 1) every stream keeps
  * them for the two update phases of its LAST step: phase 0 = remove_lost_features, 1 = prune_cam_state_buffer.  debug_read:

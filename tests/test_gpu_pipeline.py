@@ -201,7 +201,7 @@ def test_bench_scale_batch_is_stream_independent(dropin_path):
         eng.close(); flt.close()
         return feats, poses
 
-    big_f, big_p = run(256)                                 # 4 stream groups
+    big_f, big_p = run(256)                                 # one stream group (device store: two groups only from 1,024 streams up), 256-wide kernels
     small_f, small_p = run(2)
     for k in range(n_frames):
         ids, uv, n = big_f[k]

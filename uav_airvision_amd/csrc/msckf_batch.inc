@@ -2241,6 +2241,26 @@ AV_EXPORT int av_msckf_batch_counters(av_msckf_batch* b, int64_t out8[8])
     return AV_OK;
 }
 
+// What the batch launched: out17[0] = stream groups (1 without sub-batches), then per group its stream count and the workgroup size
+// dev_enqueue gave the per-stream kernels (dk_begin4 / dk_cov / dk_mid / dk_finish) in the group's last enqueued step: 64 or 256, 0
+// before its first step and on the host-bookkeeping path.  Reported as recorded at the launch, never recomputed.  Drains the queue
+// first (the groups' workers write the record).
+AV_EXPORT int av_msckf_batch_launch_shape(av_msckf_batch* b, int32_t out17[17])
+{
+    if (!b || !out17) { av_set_error("av_msckf_batch_launch_shape: bad arguments"); return AV_E_INVALID; }
+    const int rc = av_msckf_batch_wait(b, 0);
+    if (rc) return rc;
+    std::vector<av_msckf_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    for (int i = 0; i < 17; ++i) out17[i] = 0;
+    out17[0] = (int32_t)parts.size();          // (default_groups caps the groups at 8)
+    for (size_t g = 0; g < parts.size() && g < 8; ++g) {
+        out17[1 + 2 * g] = parts[g]->S;
+        out17[2 + 2 * g] = parts[g]->dev ? parts[g]->dev->launched_wg : 0;
+    }
+    return AV_OK;
+}
+
 // ---- the filter's quaternion / rotation helpers for host callers (src/utils.py:12-120; JPL convention [x, y, z, w]) --------
 // The drop-in Python classes (dropin/utils.py) call these instead of restating the formulas: one implementation, the one the
 // batched filter itself uses.  Pure host functions: no device, no context.

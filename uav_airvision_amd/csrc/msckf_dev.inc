@@ -643,7 +643,8 @@ struct DevPath {
     DevSlot slot[DEV_RING];
     double* out_d = nullptr; int* stacked0 = nullptr; int* stacked1 = nullptr; UpdArgs* updbase = nullptr; UpdArgs* upd = nullptr;
     DCov* cov_d = nullptr;           // [S] dk_begin -> dk_cov
-    int dk_wg = 0;                   // AV_DK_WG read when the path is prepared: 64 / 256 = workgroup size of the per-stream kernels, 0 = by batch size
+    int dk_wg = 0;                   // AV_DK_WG read when the path is prepared: 64 / 256 = workgroup size of the per-stream kernels, 0 = by the group's stream count
+    int launched_wg = 0;             // workgroup size dev_enqueue launched them with in the last enqueued step (0: no step yet); av_msckf_batch_launch_shape
     int* cols = nullptr; int* blk_row = nullptr; int* blk_len = nullptr; int* clist = nullptr; int* again = nullptr;
     double* work = nullptr; double* gamma = nullptr; int* pass = nullptr;
     std::vector<void*> dev_allocs, host_allocs;

@@ -486,11 +486,14 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     const int par = (int)((d->steps + 1) & 1);
     a.cnt = d->A.cnt + 16 * par; a.cnt_next = d->A.cnt + 16 * (par ^ 1);
     a.prof = dev_uprof().dev ? dev_uprof().dev + 16 : nullptr;
-    // Launch shapes of the per-stream kernels.  From 1,024 streams up ONE wavefront per stream: their phases are chains of short memory
+    // Launch shapes of the per-stream kernels.  S is the stream count of THIS GROUP, not of the batch (a batch of 1,024 streams is two
+    // groups of 512: four wavefronts; 2,047 is 1,024 + 1,023: one group of each; av_msckf_batch_launch_shape reports what was launched).
+    // From 1,024 streams of the group up ONE wavefront per stream: their phases are chains of short memory
     // round trips, and beside the front-end a 256-thread workgroup waits for a free slot on all four SIMDs of a CU at once (a 0.25-ms
     // kernel took 1.5 ms in the shared run: profiles/r05/README.md).  Below that the GPU is not full and what counts is the time ONE
     // stream takes: four wavefronts (one stream 0.59 against 0.78 ms per frame, 256 streams x 1,500 features 36 against 29 k frames/s).
-    const int dk_wg = d->dk_wg ? d->dk_wg : (S >= 1024 ? 64 : 256);       // (AV_DK_WG=64|256 forces one: A/B runs, and the parity tests of the shape small batches do not take)
+    const int dk_wg = d->dk_wg ? d->dk_wg : (S >= 1024 ? 64 : 256);       // (AV_DK_WG=64|256 forces one: A/B runs, and the parity tests of the shape small groups do not take)
+    d->launched_wg = dk_wg;
     hipLaunchKernelGGL(dk_state, dim3((S + 63) / 64), dim3(64), 0, stm, a);     // state integration + the new camera state: a lane per stream
     hipLaunchKernelGGL(dk_begin4, dim3(S), dim3(dk_wg), 0, stm, a);
     if (dk_wg == 64) hipLaunchKernelGGL(dk_cov<64>, dim3(S), dim3(64), 0, stm, a);          // the covariance half of the prediction and of the augmentation

@@ -280,6 +280,15 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_counters(self._h, C.byref(o)))
         return dict(zip(self.COUNTER_NAMES, [int(v) for v in o]))
 
+    def launch_shape(self):
+        """[(streams, workgroup size), ...] per stream group, as launched (av_msckf_batch_launch_shape); drains the queue first.  The
+        workgroup size is what the per-stream kernels of the group's last step ran with: 64 (one wavefront per stream: groups of at least
+        1,024 streams, or AV_DK_WG=64), 256 (four), 0 before the first step and on the host-bookkeeping path."""
+        self.wait(0)
+        o = (C.c_int32 * 17)()
+        N.check(N.lib().av_msckf_batch_launch_shape(self._h, C.byref(o)))
+        return [(int(o[1 + 2 * g]), int(o[2 + 2 * g])) for g in range(int(o[0]))]
+
     def get_cov(self, s):
         n = self.sizes(s)[0]
         P = np.empty((n, n))
