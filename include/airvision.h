@@ -809,6 +809,10 @@ int  av_msckf_feature_blocks(av_msckf* ctx, int n_feat, int n_cam, int max_obs, 
                              const double* cam_q_dev, const double* cam_p_dev, const double* cam_qn_dev, const double* cam_pn_dev,
                              const double* T_cam0_cam1_rowmajor44, const double gravity[3], double obs_noise,
                              double* gamma_dev, int32_t* pass_dev, void* stream);
+/* Parity-test tap (tests only): rows row0 .. row0 + n_rows - 1 of the block buffer av_msckf_feature_blocks filled -- H_host gets
+ * n_rows x av_msckf_ld doubles (full-width rows: IMU columns and the columns of cameras the feature was not seen from read zero),
+ * r_host n_rows.  Synchronises.  row0 + n_rows <= rows_cap, else AV_E_CAPACITY. */
+int  av_msckf_read_blocks(av_msckf* ctx, int row0, int n_rows, double* H_host, double* r_host, void* stream);
 /* MSCKF.measurement_update (msckf.py:548-602) on the blocks (first row, length) selected by the
  * caller after gating: thin QR when rows > n, S, gain, P <- sym((I-KH)P).  Synchronises and returns
  * delta_x (n doubles) for the caller's state injection (msckf.py:568-595). */
@@ -926,6 +930,28 @@ int  av_msckf_batch_launch_shape(av_msckf_batch* b, int32_t out17[17]);
 int  av_msckf_batch_debug_capture(av_msckf_batch* b, int enable);
 int  av_msckf_batch_debug_read(av_msckf_batch* b, int stream_idx, int phase, double* gamma, int gamma_cap, int32_t* n_gamma,
                                double* dx, double* P_after, int n_cap, int32_t* n_state, int32_t* rows);
+/* Parity-test entry (tests only; no step of the filter calls it): the per-feature kernels in the launch shapes of the device-resident
+ * filter, on the caller's device arrays.  Feature.initialize_position for the features tri_list_dev[0 .. *n_tri_dev) (triangulation
+ * kernel in list form, one wavefront per workgroup; NULL list: skipped, pos_dev / valid_dev are then inputs), then feature_jacobian +
+ * gating_test for feat_list_dev[0 .. *n_feat_dev) (NULL list: skipped) the way the filter's update phases launch them: both counts are
+ * read ON THE DEVICE, both kernels stride over their lists with a grid sized for `teams` features in flight (teams of 8 lanes -- max_obs
+ * <= 2 -- come eight to a workgroup, longer tracks one team per workgroup; the triangulation gets `teams` workgroups), a feature with
+ * valid_dev[f] = 0 is not evaluated and reads gamma = 0, pass = 0.  Feature f belongs to stream f / fs_stride of n_streams: its cameras
+ * are cam_*[stream * cam_stride + obs_cam], its covariance P_dev + stream * p_stride (row-major, leading dimension ld >= 21 + 6 *
+ * cam_stride), its gravity gravity_dev[3 * stream ..], its rows H_dev + stream * h_stride / r_dev + stream * r_stride, first row
+ * row_off_dev[f] (< 0: gate only).  compact = 0: rows of ld doubles (zero_fill = 1 clears them first, 0 writes only the feature's own
+ * camera columns); compact = c >= 6 * max_obs: rows of c doubles that hold ONLY the feature's own camera columns in observation order
+ * (zero_fill must be 0).  max_obs <= 2 evaluates two-observation features only (others read pass = 0); max_obs <= 32, else
+ * AV_E_CAPACITY before any launch.  The other arguments are those of av_msckf_triangulate / av_msckf_feature_blocks; ctx lends its
+ * chi^2 table and its device.  Nothing is synchronised. */
+int  av_msckf_feature_ops_dev(av_msckf* ctx, int n_streams, int fs_stride, int cam_stride, int max_obs, int compact, int zero_fill, int teams,
+                              const int32_t* tri_list_dev, const int32_t* n_tri_dev, const int32_t* feat_list_dev, const int32_t* n_feat_dev,
+                              const int32_t* obs_off_dev, const int32_t* obs_cam_dev, const double* obs_z_dev, const int32_t* dof_dev, const int32_t* row_off_dev,
+                              const double* cam_q_dev, const double* cam_p_dev, const double* cam_qn_dev, const double* cam_pn_dev,
+                              const double* P_dev, int ld, int64_t p_stride, const double* gravity_dev,
+                              const double* T_cam0_cam1_rowmajor44, const double* opt5, double obs_noise,
+                              double* pos_dev, int32_t* valid_dev, double* H_dev, int64_t h_stride, double* r_dev, int64_t r_stride,
+                              double* gamma_dev, int32_t* pass_dev, void* stream);
 /* Work done so far, for the filter stage's roofline (drain first): out8 = [algorithmic fp64 flops of the gating tests
  * (per feature with r = 4M-3 rows, n columns: 2rn^2 + 2r^2n + r^3/3; msckf.py:604-612), of the measurement updates on the
  * k = min(m, n) rows kept (S 2kn^2 + 2k^2n, Cholesky k^3/3, solve 2k^2n, (I-KH)P 4kn^2; msckf.py:562-602), of the reference's

@@ -2504,6 +2504,20 @@ AV_EXPORT int av_msckf_feature_blocks(av_msckf* c, int n_feat, int n_cam, int ma
     return launch_feature_kernel(a, n_feat, max_obs, (hipStream_t)stream);
 }
 
+// Parity-test tap (tests only): rows row0 .. row0 + n_rows - 1 of the block buffer av_msckf_feature_blocks wrote, ld doubles each, and of r
+AV_EXPORT int av_msckf_read_blocks(av_msckf* c, int row0, int n_rows, double* H_host, double* r_host, void* stream)
+{
+    if (!c || row0 < 0 || n_rows < 0 || !H_host || !r_host) { av_set_error("av_msckf_read_blocks: bad arguments"); return AV_E_INVALID; }
+    if (row0 + (long long)n_rows > c->rows_cap) { av_set_error("av_msckf_read_blocks: rows %d .. %lld exceed rows_cap %d", row0, row0 + (long long)n_rows, c->rows_cap); return AV_E_CAPACITY; }
+    if (n_rows == 0) return AV_OK;
+    hipStream_t st = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(c->device));
+    AV_HIP(hipMemcpyAsync(H_host, c->Hblk + (size_t)row0 * c->ld, sizeof(double) * (size_t)n_rows * c->ld, hipMemcpyDeviceToHost, st));
+    AV_HIP(hipMemcpyAsync(r_host, c->rblk + row0, sizeof(double) * n_rows, hipMemcpyDeviceToHost, st));
+    AV_HIP(hipStreamSynchronize(st));
+    return AV_OK;
+}
+
 AV_EXPORT int av_msckf_update(av_msckf* c, const int32_t* blk_row_dev, const int32_t* blk_len_dev, int n_blk, int total_rows,
                               double obs_noise, double* dx_host, void* stream)
 {

@@ -2160,6 +2160,54 @@ AV_EXPORT int av_msckf_batch_debug_read(av_msckf_batch* b, int stream_idx, int p
     return AV_OK;
 }
 
+// Parity-test entry for the per-feature launch shapes of the device-resident filter (tests only; no step of the filter calls it): on the
+// caller's device arrays, triangulate_kernel in its list form with one wavefront per workgroup, then launch_feature_dev, both exactly as
+// dev_phase launches them -- device-side counts, valid[] written by the triangulation and read by the gate, stream of feature f =
+// f / fs_stride, `teams` as dev_grid_hint would give it (the kernels stride over their lists whatever the grid).  No kernel of its own.
+// tri_list_dev = NULL skips the triangulation: pos_dev / valid_dev are then the caller's.  `ctx` lends its chi^2 table and its device.
+AV_EXPORT int av_msckf_feature_ops_dev(av_msckf* c, int n_streams, int fs_stride, int cam_stride, int max_obs, int compact, int zero_fill, int teams,
+                                       const int32_t* tri_list_dev, const int32_t* n_tri_dev, const int32_t* feat_list_dev, const int32_t* n_feat_dev,
+                                       const int32_t* obs_off_dev, const int32_t* obs_cam_dev, const double* obs_z_dev, const int32_t* dof_dev, const int32_t* row_off_dev,
+                                       const double* cam_q_dev, const double* cam_p_dev, const double* cam_qn_dev, const double* cam_pn_dev,
+                                       const double* P_dev, int ld, int64_t p_stride, const double* gravity_dev,
+                                       const double* T_cam0_cam1_rowmajor44, const double* opt5, double obs_noise,
+                                       double* pos_dev, int32_t* valid_dev, double* H_dev, int64_t h_stride, double* r_dev, int64_t r_stride,
+                                       double* gamma_dev, int32_t* pass_dev, void* stream)
+{
+    if (!c || n_streams < 1 || fs_stride < 1 || cam_stride < 1 || max_obs < 1 || teams < 1 || teams > 262144 || (tri_list_dev && !n_tri_dev) ||
+        !obs_off_dev || !obs_cam_dev || !obs_z_dev || !cam_q_dev || !cam_p_dev || !T_cam0_cam1_rowmajor44 || !opt5 || !pos_dev || !valid_dev ||
+        (feat_list_dev && (!n_feat_dev || !dof_dev || !row_off_dev || !cam_qn_dev || !cam_pn_dev || !P_dev || !gravity_dev || !H_dev || !r_dev || !gamma_dev || !pass_dev)) ||
+        ld < IMU_DIM + 6 * cam_stride || p_stride < 0 || h_stride < 0 || r_stride < 0 ||
+        compact < 0 || (compact > 0 && (compact < 6 * max_obs || zero_fill))) {         // (the zero fill clears full-width rows: compact rows have no room for it)
+        av_set_error("av_msckf_feature_ops_dev: bad arguments");
+        return AV_E_INVALID;
+    }
+    if (2 * max_obs > 64) { av_set_error("av_msckf_feature_ops_dev: %d observations per feature exceed one wavefront (32)", max_obs); return AV_E_CAPACITY; }
+    hipStream_t stm = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(c->device));
+    if (tri_list_dev) {
+        TriArgs t = tri_args_base(cam_q_dev, cam_p_dev, cam_stride, T_cam0_cam1_rowmajor44, opt5);
+        t.obs_off = obs_off_dev; t.obs_cam = obs_cam_dev; t.obs_z = obs_z_dev;
+        t.out_pos = pos_dev; t.out_valid = valid_dev;
+        t.list = tri_list_dev; t.n_list_dev = n_tri_dev; t.fs_stride = fs_stride;
+        hipLaunchKernelGGL(triangulate_kernel, dim3(teams), dim3(64), 0, stm, t);
+        AV_LAUNCH_CHECK();
+    }
+    if (!feat_list_dev) return AV_OK;
+    FeatArgs f; memset(&f, 0, sizeof(f));
+    f.cam_q = cam_q_dev; f.cam_p = cam_p_dev; f.cam_qn = cam_qn_dev; f.cam_pn = cam_pn_dev;
+    f.ld = ld; f.P = P_dev; f.chi2 = c->chi2;
+    unpack_T01(T_cam0_cam1_rowmajor44, f.R01, f.t01);
+    f.obs_noise = obs_noise; f.Hout = H_dev; f.rout = r_dev;
+    f.cam_stride = cam_stride; f.p_stride = (size_t)p_stride; f.h_stride = (size_t)h_stride; f.r_stride = (size_t)r_stride;
+    f.zero_fill = zero_fill ? 1 : 0; f.compact = compact;
+    f.fs_stride = fs_stride; f.stream_gravity = gravity_dev;
+    f.obs_off = obs_off_dev; f.obs_cam = obs_cam_dev; f.obs_z = obs_z_dev; f.pos = pos_dev; f.dof = dof_dev; f.row_off = row_off_dev;
+    f.gamma = gamma_dev; f.pass = pass_dev; f.valid = valid_dev;
+    f.feat_list = feat_list_dev; f.n_list_dev = n_feat_dev;
+    return launch_feature_dev(f, teams, max_obs, stm);
+}
+
 // Work done so far, for the filter's roofline (drain first): [algorithmic fp64 flops of the gates, of the updates without the
 // reference's QR, of that QR by the survey's formula, features gated, updates run, rows stacked, device time of the phase chains
 // in ms (sum over stream groups; 0 unless timing was switched on with enable != 0 -- two HIP events per phase and group), phase

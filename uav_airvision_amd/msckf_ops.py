@@ -132,6 +132,77 @@ class MsckfDevice(object):
             torch.cuda.synchronize()
         return row_off, rows, gamma.cpu().numpy(), ok.cpu().numpy().astype(bool)
 
+    def read_blocks(self, row0, n_rows):
+        """Parity-test tap (tests only): rows of the block buffer feature_blocks filled -> (H float64[n_rows, ld], r float64[n_rows])."""
+        ld = N.lib().av_msckf_ld(self._h)
+        H = np.empty((int(n_rows), ld)); r = np.empty(int(n_rows))
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_read_blocks(self._h, int(row0), int(n_rows), H.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), self._st()))
+        return H, r
+
+    def feature_ops_dev(self, obs_cam_lists, obs_z_lists, fs_stride, cam_q, cam_p, cam_qn, cam_pn, P, gravity, T_cam0_cam1, opt, obs_noise, dofs,
+                        max_obs, teams, tri_list=None, feat_list=None, positions=None, valid=None, compact=0, zero_fill=0):
+        """Parity-test entry (av_msckf_feature_ops_dev; tests only): the per-feature kernels in the launch shapes of the device-resident
+        filter.  Feature slot f = stream * fs_stride + k (obs_cam_lists / obs_z_lists / dofs have one entry per slot, empty = unused);
+        cam_* are [streams * cam_stride] rows, P is [streams, n, n] with n = 21 + 6 * cam_stride, gravity [streams, 3].  tri_list /
+        feat_list: slots to triangulate / to evaluate (device lists with device-side counts; None skips the stage); positions / valid
+        preset the arrays the triangulation would write.  Every index is checked here, on the host, before anything is launched.
+        -> dict(pos, valid, H [streams, rows, ld or compact] (NaN where nothing was written), r, gamma, ok, row_off)."""
+        n_slots = len(obs_cam_lists)
+        counts = np.array([len(c) for c in obs_cam_lists], np.int64)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        S, ld = P.shape[0], P.shape[1]
+        cam_q = np.ascontiguousarray(cam_q, dtype=np.float64).reshape(-1, 4)
+        cam_stride = len(cam_q) // S
+        if fs_stride < 1 or n_slots != S * fs_stride or len(cam_q) != S * cam_stride or P.shape != (S, ld, ld) or ld != 21 + 6 * cam_stride or len(dofs) != n_slots:
+            raise ValueError('feature_ops_dev: inconsistent shapes')
+        for name, a in (('cam_p', cam_p), ('cam_qn', cam_qn), ('cam_pn', cam_pn)):
+            if len(a) != len(cam_q):
+                raise ValueError('feature_ops_dev: %s has %d rows, cam_q %d' % (name, len(a), len(cam_q)))
+        lists = []
+        for lst in (tri_list, feat_list):
+            lst = None if lst is None else np.ascontiguousarray(lst, dtype=np.int32)
+            if lst is not None and len(lst) and (lst.min() < 0 or lst.max() >= n_slots or counts[lst].min() < 1 or (max_obs > 2 and counts[lst].max() > max_obs)):
+                raise ValueError('feature_ops_dev: a listed slot is out of range, empty or longer than max_obs')
+            lists.append(lst)
+        tri_list, feat_list = lists
+        if any(len(c) and (min(c) < 0 or max(c) >= cam_stride) for c in obs_cam_lists) or min(dofs) < 0 or max(dofs) > 99:
+            raise ValueError('feature_ops_dev: camera index or dof out of range')
+        if not (compact == 0 or (compact >= 6 * max_obs and not zero_fill)) or not 1 <= int(teams) <= 262144:
+            raise ValueError('feature_ops_dev: bad compact / zero_fill / teams')
+        batch = FeatureBatch([c if len(c) else [] for c in obs_cam_lists], [z if len(z) else np.zeros((0, 4)) for z in obs_z_lists], self.device)
+        rows = np.maximum(4 * counts - 3, 0).reshape(S, fs_stride)
+        row_off = (np.cumsum(rows, axis=1) - rows).astype(np.int32).reshape(-1)
+        rows_cap = max(int(rows.sum(axis=1).max()), 1)
+        width = compact if compact > 0 else ld
+        dev = self.dev
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        q, p = self._cams(cam_q, cam_p)
+        qn, pn = self._cams(cam_qn, cam_pn)
+        pos = up(np.zeros((n_slots, 3)) if positions is None else np.asarray(positions).reshape(n_slots, 3), np.float64)
+        val = up(np.zeros(n_slots) if valid is None else valid, np.int32)
+        H = torch.full((S, rows_cap, width), float('nan'), dtype=torch.float64, device=dev)
+        r = torch.full((S, rows_cap), float('nan'), dtype=torch.float64, device=dev)
+        gam = torch.full((n_slots,), float('nan'), dtype=torch.float64, device=dev)
+        ok = torch.full((n_slots,), -1, dtype=torch.int32, device=dev)
+        Pd, grav, dof, ro = up(P, np.float64), up(np.asarray(gravity).reshape(S, 3), np.float64), up(dofs, np.int32), up(row_off, np.int32)
+        tl = None if tri_list is None else up(tri_list, np.int32)
+        fl = None if feat_list is None else up(feat_list, np.int32)
+        nt = up([0 if tri_list is None else len(tri_list)], np.int32)
+        nf = up([0 if feat_list is None else len(feat_list)], np.int32)
+        opt5 = _d([opt.huber_epsilon, opt.estimation_precision, opt.initial_damping, opt.outer_loop_max_iteration, opt.inner_loop_max_iteration])
+        null = C.c_void_p(None)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_feature_ops_dev(
+                self._h, S, int(fs_stride), cam_stride, int(max_obs), int(compact), int(zero_fill), int(teams),
+                null if tl is None else N.dptr(tl), N.dptr(nt), null if fl is None else N.dptr(fl), N.dptr(nf),
+                N.dptr(batch.off), N.dptr(batch.cam), N.dptr(batch.z), N.dptr(dof), N.dptr(ro), N.dptr(q), N.dptr(p), N.dptr(qn), N.dptr(pn),
+                N.dptr(Pd), ld, ld * ld, N.dptr(grav), _d(np.asarray(T_cam0_cam1, dtype=np.float64).reshape(-1)), opt5, float(obs_noise),
+                N.dptr(pos), N.dptr(val), N.dptr(H), rows_cap * width, N.dptr(r), rows_cap, N.dptr(gam), N.dptr(ok), self._st()))
+            torch.cuda.synchronize()
+        return dict(pos=pos.cpu().numpy(), valid=val.cpu().numpy(), H=H.cpu().numpy(), r=r.cpu().numpy(), gamma=gam.cpu().numpy(), ok=ok.cpu().numpy(),
+                    row_off=row_off, rows=rows.reshape(-1))
+
     def update(self, blk_rows, blk_lens, obs_noise):
         """Stacked EKF update on the selected blocks; returns delta_x (n doubles)."""
         n = self.dim
