@@ -952,6 +952,32 @@ int  av_msckf_feature_ops_dev(av_msckf* ctx, int n_streams, int fs_stride, int c
                               const double* T_cam0_cam1_rowmajor44, const double* opt5, double obs_noise,
                               double* pos_dev, int32_t* valid_dev, double* H_dev, int64_t h_stride, double* r_dev, int64_t r_stride,
                               double* gamma_dev, int32_t* pass_dev, void* stream);
+/* Parity-test entry (tests only; no step of the filter calls it): the prediction of the device-resident filter -- batch_imu_processing
+ * with predict_new_state and process_model, then state_augmentation (msckf.py:251-423) -- for n_streams streams in ONE launch sequence,
+ * exactly the one a filter step begins with: the state kernel (a lane per stream), then the covariance kernel with wg = 64 (one
+ * wavefront per stream) or 256 threads per stream, through the helper the step itself launches them with.  The streams are described by
+ * flat HOST arrays, per stream:
+ *   state_io[43]     ts, q[4], p[3], v[3], bg[3], ba[3], R_imu_cam0[9], t_cam0_imu[3], q_null[4], p_null[3], v_null[3], gravity[3],
+ *                    tracking_rate (read and written back)
+ *   state_int_io[6]  n_state, n_cam, failed, null_aliased, first_img (read and written back), active (written)
+ *   t_frame[1]       the frame's time stamp
+ *   ctl[6]           active, first IMU sample, number of IMU samples, ops, rm0, rm1
+ *   imu[n_imu][7]    t, gyro[3], acc[3] per sample (raw: the biases are the state's)
+ * and by DEVICE arrays the kernels work on in place: camera states cam_q / cam_p / cam_qn at [stream * cam_stride + k], covariances at
+ * P_dev + stream * p_stride, row-major with leading dimension ld.  A stream with active = 0 or failed != 0 is left alone; one whose window
+ * is full (n_cam == cam_stride) comes back with failed = 1 (no room for the new camera state) and nothing else of it touched.
+ * ops (applied after the prediction, to the window as it then stands, through a probe kernel only this entry launches): bit 0 =
+ * find_redundant_cam_states (msckf.py:678-709) with the state's tracking_rate -> redundant_out[2] (window positions, ascending; -1 where
+ * not asked for); bit 1 = removal of the camera states at window positions rm0 < rm1 from the covariance (msckf.py:774-786), both in one
+ * pass, at wg threads.  Checked before anything is launched (AV_E_INVALID, or AV_E_CAPACITY for n_cam > cam_stride): wg, the counts,
+ * ld >= 21 + 6 * cam_stride, p_stride >= ld * ld, n_state == 21 + 6 * n_cam, samples inside imu[], four camera states for the redundancy
+ * rule, removal positions ascending and inside the window.  noise4 = continuous variances [gyro, gyro_bias, acc, acc_bias]; ctx lends
+ * its device.  Synchronises. */
+int  av_msckf_predict_ops_dev(av_msckf* ctx, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
+                              double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
+                              const double* imu, int n_imu, const double noise4[4],
+                              double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
+                              int32_t* redundant_out, void* stream);
 /* Work done so far, for the filter stage's roofline (drain first): out8 = [algorithmic fp64 flops of the gating tests
  * (per feature with r = 4M-3 rows, n columns: 2rn^2 + 2r^2n + r^3/3; msckf.py:604-612), of the measurement updates on the
  * k = min(m, n) rows kept (S 2kn^2 + 2k^2n, Cholesky k^3/3, solve 2k^2n, (I-KH)P 4kn^2; msckf.py:562-602), of the reference's

@@ -13,6 +13,12 @@ the left null space of H_f, A A^T = Pi, hence for H_o = A^T H_x, r_o = A^T r
 gamma = r_o^T (H_o P H_o^T + s^2 I)^-1 r_o is basis-free as well.
 
 An observation list is [(camera index, (u0, v0, u1, v1)), ...] in observation order; cam_q / cam_p are indexed by camera index.
+
+The second half restates what a step does before it looks at any feature, after the oracle's predict_new_state, process_model (per IMU
+sample, in the reference's order, with the symmetrisation of the whole matrix and the hand-over of the null states), state_augmentation,
+the removal loop of prune_cam_state_buffer and find_redundant_cam_states.  The IMU state is a dict of mpf arrays (IMU_FIELDS), the
+covariance an object array.  Every decision reports its relative margin in 50 digits: the `> 1e-5` rate branch, and the 0.2618 rad,
+0.4 m and 0.5 tracking-rate tests of the redundancy rule.
 """
 import numpy as np
 from mpmath import mp, mpf
@@ -322,3 +328,179 @@ def gamma(rows, P_sub, obs_noise):
 def own_columns(obs):
     """Indices of the feature's own camera columns in the full state (21 + 6 * camera + 0..5), observation order."""
     return np.concatenate([21 + 6 * ci + np.arange(6) for ci, _ in obs])
+
+
+# ---- prediction, augmentation, pruning (the part of a step that runs before any feature is looked at) --
+# The thresholds are the fp64 literals the code compares with, entered exactly.
+RATE_THR = mpf(1e-5)
+ANGLE_THR, DIST_THR, TRACK_THR = mpf(0.2618), mpf(0.4), mpf(0.5)
+IMU_FIELDS = ('ts', 'q', 'p', 'v', 'bg', 'ba', 'R_ic', 't_ci', 'qn', 'pn', 'vn', 'gravity')
+
+
+def to_quaternion(R):
+    """utils.py:25-47."""
+    if R[2, 2] < 0:
+        if R[0, 0] > R[1, 1]:
+            q = [1 + R[0, 0] - R[1, 1] - R[2, 2], R[0, 1] + R[1, 0], R[2, 0] + R[0, 2], R[1, 2] - R[2, 1]]
+        else:
+            q = [R[0, 1] + R[1, 0], 1 - R[0, 0] + R[1, 1] - R[2, 2], R[2, 1] + R[1, 2], R[2, 0] - R[0, 2]]
+    else:
+        if R[0, 0] < -R[1, 1]:
+            q = [R[0, 2] + R[2, 0], R[2, 1] + R[1, 2], 1 - R[0, 0] - R[1, 1] + R[2, 2], R[0, 1] - R[1, 0]]
+        else:
+            q = [R[1, 2] - R[2, 1], R[2, 0] - R[0, 2], R[0, 1] - R[1, 0], 1 + R[0, 0] + R[1, 1] + R[2, 2]]
+    q = np.array(q, dtype=object)
+    return q / norm(q)
+
+
+def imu_state(d):
+    """dict of fp64 fields (IMU_FIELDS; R_ic 3 x 3) -> the same in mpf."""
+    return {k: (M(d[k]) if np.ndim(d[k]) else mpf(float(d[k]))) for k in IMU_FIELDS}
+
+
+def predict_new_state(s, dt, gyro, acc):
+    """predict_new_state (msckf.py:341-388): RK4 with k2 and k3 sharing the half-step rotation; s['q'], s['v'], s['p'] are replaced.
+    -> relative margin of the `> 1e-5` rate branch."""
+    gn = norm(gyro)
+    Om = zeros(4, 4)
+    Om[:3, :3] = -skew(gyro)
+    Om[:3, 3] = gyro
+    Om[3, :3] = -gyro
+    q, v, p, g = s['q'], s['v'], s['p'], s['gravity']
+    if gn > RATE_THR:
+        dq_dt = (eye(4) * mp.cos(gn * dt / 2) + Om * (mp.sin(gn * dt / 2) / gn)).dot(q)
+        dq_dt2 = (eye(4) * mp.cos(gn * dt / 4) + Om * (mp.sin(gn * dt / 4) / gn)).dot(q)
+    else:
+        dq_dt = ((eye(4) + Om * (dt / 2)) * mp.cos(gn * dt / 2)).dot(q)
+        dq_dt2 = ((eye(4) + Om * (dt / 4)) * mp.cos(gn * dt / 4)).dot(q)
+    Rt, Rt2 = to_rotation(dq_dt).T, to_rotation(dq_dt2).T
+    k1v = to_rotation(q).T.dot(acc) + g
+    k1p = v
+    k2v = Rt2.dot(acc) + g
+    k2p = v + k1v * (dt / 2)
+    k3v = Rt2.dot(acc) + g
+    k3p = v + k2v * (dt / 2)
+    k4v = Rt.dot(acc) + g
+    k4p = v + k3v * dt
+    s['q'] = dq_dt / norm(dq_dt)
+    s['v'] = v + (k1v + k2v * 2 + k3v * 2 + k4v) * (dt / 6)
+    s['p'] = p + (k1p + k2p * 2 + k3p * 2 + k4p) * (dt / 6)
+    return abs(gn - RATE_THR) / RATE_THR
+
+
+def process_model(s, P, time, m_gyro, m_acc, noise):
+    """process_model (msckf.py:275-339) for one IMU sample, state and covariance, in the reference's order: F, G, Phi to third order
+    from the OLD orientation, predict_new_state, the observability patches of Phi from the null-space states, Q = Phi G Qc G^T Phi^T dt,
+    the IMU block, the cross blocks, (P + P^T) / 2 of the whole matrix, the null states handed over.  s is updated in place (its
+    time stamp is batch_imu_processing's to set).  noise = the four continuous variances.  -> (P, rate margin)."""
+    dt = mpf(float(time)) - s['ts']
+    gyro, acc = M(m_gyro) - s['bg'], M(m_acc) - s['ba']
+    Fm, G = zeros(21, 21), zeros(21, 12)
+    R_w_i = to_rotation(s['q'])
+    Fm[:3, :3] = -skew(gyro)
+    Fm[:3, 3:6] = -eye(3)
+    Fm[6:9, :3] = -R_w_i.T.dot(skew(acc))
+    Fm[6:9, 9:12] = -R_w_i.T
+    Fm[12:15, 6:9] = eye(3)
+    G[:3, :3] = -eye(3)
+    G[3:6, 3:6] = eye(3)
+    G[6:9, 6:9] = -R_w_i.T
+    G[9:12, 9:12] = eye(3)
+    Fdt = Fm * dt
+    Fdt2 = Fdt.dot(Fdt)
+    Fdt3 = Fdt2.dot(Fdt)
+    Phi = eye(21) + Fdt + Fdt2 / 2 + Fdt3 / 6
+    margin = predict_new_state(s, dt, gyro, acc)
+    g = s['gravity']
+    R_kk_1 = to_rotation(s['qn'])
+    Phi[:3, :3] = to_rotation(s['q']).dot(R_kk_1.T)
+    u = R_kk_1.dot(g)
+    sv = u / u.dot(u)
+    A1 = Phi[6:9, :3]
+    w1 = skew(s['vn'] - s['v']).dot(g)
+    Phi[6:9, :3] = A1 - np.outer(A1.dot(u) - w1, sv)
+    A2 = Phi[12:15, :3]
+    w2 = skew(s['vn'] * dt + s['pn'] - s['p']).dot(g)
+    Phi[12:15, :3] = A2 - np.outer(A2.dot(u) - w2, sv)
+    Qc = zeros(12, 12)
+    for i in range(12):
+        Qc[i, i] = mpf(float(noise[i // 3]))
+    Q = Phi.dot(G).dot(Qc).dot(G.T).dot(Phi.T) * dt
+    P = np.array(P, dtype=object)
+    P[:21, :21] = Phi.dot(P[:21, :21]).dot(Phi.T) + Q
+    if len(P) > 21:
+        P[:21, 21:] = Phi.dot(P[:21, 21:])
+        P[21:, :21] = P[21:, :21].dot(Phi.T)
+    P = (P + P.T) / 2
+    s['qn'], s['pn'], s['vn'] = s['q'], s['p'], s['v']
+    return P, margin
+
+
+def batch_imu_processing(s, P, samples, noise):
+    """The loop of batch_imu_processing (msckf.py:251-273) over the samples it applies: [(t, gyro, acc), ...] -> (P, smallest rate margin)."""
+    margin = mp.inf
+    for t, w, a in samples:
+        P, m = process_model(s, P, t, w, a, noise)
+        s['ts'] = mpf(float(t))
+        margin = min(margin, m)
+    return P, margin
+
+
+def state_augmentation(s, P):
+    """state_augmentation (msckf.py:390-423) -> (orientation, position of the new camera state, the grown covariance)."""
+    R_i_c, t_c_i = s['R_ic'], s['t_ci']
+    R_w_i = to_rotation(s['q'])
+    cam_q = to_quaternion(R_i_c.dot(R_w_i))
+    cam_p = s['p'] + R_w_i.T.dot(t_c_i)
+    J = zeros(6, 21)
+    J[:3, :3] = R_i_c
+    J[:3, 15:18] = eye(3)
+    J[3:6, :3] = skew(R_w_i.T.dot(t_c_i))
+    J[3:6, 12:15] = eye(3)
+    J[3:6, 18:21] = eye(3)
+    n = len(P)
+    Pn = zeros(n + 6, n + 6)
+    Pn[:n, :n] = P
+    Pn[n:, :n] = J.dot(Pn[:21, :n])
+    Pn[:n, n:] = Pn[n:, :n].T
+    Pn[n:, n:] = J.dot(Pn[:21, :21]).dot(J.T)
+    return cam_q, cam_p, (Pn + Pn.T) / 2
+
+
+def remove_cam_states(P, positions):
+    """The removal loop of prune_cam_state_buffer (msckf.py:774-786): the camera states at the given window positions (ascending, in
+    the numbering before any removal) leave one after the other, each at the position it has by then."""
+    P = np.asarray(P)
+    for k, i in enumerate(positions):
+        a = 21 + 6 * (i - k)
+        keep = np.r_[0:a, a + 6:len(P)]
+        P = P[np.ix_(keep, keep)].copy()
+    return P
+
+
+def find_redundant_cam_states(cam_q, cam_p, tracking_rate):
+    """find_redundant_cam_states (msckf.py:678-709) on a window of camera states -> (the two window positions, ascending,
+    [dict(angle, dist, rate: relative margins to 0.2618 rad, 0.4 m, 0.5; redundant; margin) for the two candidates]).  `margin` is the margin
+    of the decision: the smallest of the computed two (angle, distance) where all three tests hold, else the largest among the tests that
+    fail (one clear failure decides; a failing rate test is exact)."""
+    n = len(cam_q)
+    key, idx, first = n - 4, n - 3, 0
+    key_p, key_R = M(cam_p[key]), to_rotation(cam_q[key])
+    rate = mpf(float(tracking_rate))
+    out, info = [], []
+    for _ in range(2):
+        dist = norm(M(cam_p[idx]) - key_p)
+        angle = 2 * mp.acos(to_quaternion(to_rotation(cam_q[idx]).dot(key_R.T))[3])
+        tests = ((angle < ANGLE_THR, abs(angle - ANGLE_THR) / ANGLE_THR), (dist < DIST_THR, abs(dist - DIST_THR) / DIST_THR),
+                 (rate > TRACK_THR, abs(rate - TRACK_THR) / TRACK_THR))
+        red = all(t for t, _ in tests)
+        dec = (tests[0], tests[1], (tests[2][0], mp.inf))      # the rate is an input compared as it is: exact in any precision
+        info.append(dict(angle=tests[0][1], dist=tests[1][1], rate=tests[2][1], redundant=red,
+                         margin=min(m for _, m in dec) if red else max(m for t, m in dec if not t)))
+        if red:
+            out.append(idx)
+        else:
+            out.append(first)
+            first += 1
+        idx += 1
+    return sorted(out), info

@@ -281,6 +281,7 @@ SIGNATURES = {
     'av_msckf_batch_debug_read': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'av_msckf_feature_ops_dev': (C.c_int, [_P] + [C.c_int] * 7 + [_P] * 14 +[C.c_int, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                            _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    'av_msckf_predict_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6),
     'av_msckf_batch_work': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 8)]),
     'av_msckf_batch_work_executed': (C.c_int, [_P, C.POINTER(C.c_double * 2)]),
     'av_msckf_batch_get_state': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 32), _P, _P, C.c_int, C.POINTER(C.c_int32)]),

@@ -2208,6 +2208,113 @@ AV_EXPORT int av_msckf_feature_ops_dev(av_msckf* c, int n_streams, int fs_stride
     return launch_feature_dev(f, teams, max_obs, stm);
 }
 
+// Parity-test entry for the prediction of the device-resident filter (tests only; no step of the filter calls it): for n_streams
+// streams described by flat host arrays, what a step launches before any feature is looked at -- dk_state, then dk_cov<wg>, through
+// dev_launch_predict, the helper dev_enqueue itself calls -- on the caller's device arrays of camera states and covariances; then, for
+// the streams that ask for it, dev_find_redundant and remove_two_cams_body through dk_prune_probe (the one kernel only this entry
+// launches).  Layouts (doubles / ints per stream):
+//   state_io[43]    ts, q[4], p[3], v[3], bg[3], ba[3], R_ic[9], t_ci[3], qn[4], pn[3], vn[3], gravity[3], tracking_rate   (in / out)
+//   state_int_io[6] n, ncam, failed, null_aliased, first_img (in / out), active (out)
+//   ctl[6]          active, imu_first, imu_cnt, ops (bit 0: redundancy rule, bit 1: removal), rm0, rm1 (window positions, after the prediction)
+//   imu[7]          t, w[3], a[3] per sample
+//   redundant_out[2] the two positions of the redundancy rule, -1 where it was not asked for
+// Every argument is checked before anything is launched: no input can send a kernel out of bounds.  Synchronises.
+AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
+                                       double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
+                                       const double* imu, int n_imu, const double* noise4,
+                                       double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
+                                       int32_t* redundant_out, void* stream)
+{
+    constexpr int SD = 43, SI = 6, CI = 6;
+    if (!c || n_streams < 1 || n_streams > 65536 || (wg != 64 && wg != 256) || cam_stride < 1 || cam_stride > 64 || n_imu < 0 || (n_imu > 0 && !imu) ||
+        !state_io || !state_int_io || !t_frame || !ctl || !noise4 || !cam_q_dev || !cam_p_dev || !cam_qn_dev || !P_dev || !redundant_out ||
+        ld < IMU_DIM + 6 * cam_stride || p_stride < (int64_t)ld * ld) {
+        av_set_error("av_msckf_predict_ops_dev: bad arguments");
+        return AV_E_INVALID;
+    }
+    const int S = n_streams;
+    bool any_ops = false;
+    for (int s = 0; s < S; ++s) {
+        const int32_t* I = state_int_io + (size_t)s * SI; const int32_t* C = ctl + (size_t)s * CI;
+        const int n = I[0], ncam = I[1];
+        if (ncam < 0 || n != IMU_DIM + 6 * ncam || C[1] < 0 || C[2] < 0 || (int64_t)C[1] + C[2] > n_imu || (C[3] & ~3)) {
+            av_set_error("av_msckf_predict_ops_dev: stream %d: inconsistent sizes, samples outside their array or unknown ops", s);
+            return AV_E_INVALID;
+        }
+        // a full window (ncam == cam_stride) is the kernel's own refusal to test (DFAIL_CAMS: nothing of the stream is touched); more is not representable
+        if (ncam > cam_stride) { av_set_error("av_msckf_predict_ops_dev: stream %d holds %d camera states, cam_stride is %d", s, ncam, cam_stride); return AV_E_CAPACITY; }
+        const bool grows = C[0] && !I[2] && ncam + 1 <= cam_stride;          // what dk_state decides
+        const int after = ncam + (grows ? 1 : 0);
+        if ((C[3] & 1) && after < 4) { av_set_error("av_msckf_predict_ops_dev: stream %d: the redundancy rule needs four camera states", s); return AV_E_INVALID; }
+        if ((C[3] & 2) && !(C[4] >= 0 && C[4] < C[5] && C[5] < after)) {
+            av_set_error("av_msckf_predict_ops_dev: stream %d: removal positions %d, %d are not ascending inside a window of %d", s, C[4], C[5], after);
+            return AV_E_INVALID;
+        }
+        any_ops = any_ops || C[3];
+    }
+    hipStream_t stm = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(c->device));
+    // one device allocation for everything the kernels need besides the caller's arrays, released on every way out
+    struct Arena { char* p = nullptr; size_t used = 0; ~Arena() { if (p) (void)hipFree(p); }
+                   size_t take(size_t bytes) { const size_t o = used; used += (bytes + 255) / 256 * 256; return o; } } ar;
+    const size_t nimu = (size_t)(n_imu > 0 ? n_imu : 1), ncs = (size_t)S * cam_stride;
+    const size_t o_st = ar.take(sizeof(DState) * S), o_ctl = ar.take(sizeof(DCtl) * S), o_imu = ar.take(sizeof(DImu) * nimu), o_prop = ar.take(sizeof(PropArgs) * nimu),
+                 o_cov = ar.take(sizeof(DCov) * S), o_cnt = ar.take(sizeof(int) * 16), o_id = ar.take(sizeof(long long) * ncs), o_nc = ar.take(sizeof(int) * S),
+                 o_ns = ar.take(sizeof(int) * S), o_gr = ar.take(sizeof(double) * 3 * S), o_ops = ar.take(sizeof(int) * S), o_rm = ar.take(sizeof(int) * 2 * S),
+                 o_red = ar.take(sizeof(int) * 2 * S), o_scr = ar.take(any_ops ? sizeof(double) * (size_t)p_stride * S : 8);
+    AV_HIP(hipMalloc((void**)&ar.p, ar.used));
+    std::vector<DState> st((size_t)S); std::vector<DCtl> ct((size_t)S); std::vector<DImu> im(nimu);
+    std::vector<int> ops((size_t)S), rm((size_t)2 * S), red((size_t)2 * S, -1);
+    memset(st.data(), 0, sizeof(DState) * S); memset(ct.data(), 0, sizeof(DCtl) * S); memset(im.data(), 0, sizeof(DImu) * nimu);
+    for (int s = 0; s < S; ++s) {
+        const double* d = state_io + (size_t)s * SD; const int32_t* I = state_int_io + (size_t)s * SI; const int32_t* C = ctl + (size_t)s * CI;
+        DState& D = st[s];
+        D.ts = d[0];
+        memcpy(D.q, d + 1, 32); memcpy(D.p, d + 5, 24); memcpy(D.v, d + 8, 24); memcpy(D.bg, d + 11, 24); memcpy(D.ba, d + 14, 24);
+        memcpy(D.R_ic, d + 17, 72); memcpy(D.t_ci, d + 26, 24); memcpy(D.qn, d + 29, 32); memcpy(D.pn, d + 33, 24); memcpy(D.vn, d + 36, 24);
+        memcpy(D.gravity, d + 39, 24); D.tracking_rate = d[42];
+        D.n = I[0]; D.ncam = I[1]; D.failed = I[2]; D.null_aliased = I[3]; D.first_img = I[4];
+        DCtl& K = ct[s];
+        K.t_frame = t_frame[s]; K.active = C[0]; K.has_init = 0; K.imu_first = C[1]; K.imu_cnt = C[2];
+        ops[s] = C[3]; rm[2 * s] = C[4]; rm[2 * s + 1] = C[5];
+    }
+    for (int i = 0; i < n_imu; ++i) { im[i].t = imu[7 * i]; for (int e = 0; e < 3; ++e) { im[i].w[e] = imu[7 * i + 1 + e]; im[i].a[e] = imu[7 * i + 4 + e]; } }
+    DevArgs a; memset(&a, 0, sizeof(a));
+    a.S = S; a.cs = cam_stride; a.max_cam = cam_stride - 1; a.ld = ld; a.pstride = (size_t)p_stride;
+    a.P = P_dev; a.scratch = (double*)(ar.p + o_scr);
+    a.st = (DState*)(ar.p + o_st); a.cam_id = (long long*)(ar.p + o_id); a.cam_q = cam_q_dev; a.cam_p = cam_p_dev; a.cam_qn = cam_qn_dev;
+    a.ncam = (int*)(ar.p + o_nc); a.nstate = (int*)(ar.p + o_ns); a.grav = (double*)(ar.p + o_gr);
+    a.cnt = a.cnt_next = (int*)(ar.p + o_cnt);
+    a.ctl = (const DCtl*)(ar.p + o_ctl); a.imu = (const DImu*)(ar.p + o_imu); a.prop = (PropArgs*)(ar.p + o_prop); a.cov = (DCov*)(ar.p + o_cov);
+    for (int i = 0; i < 4; ++i) a.noise[i] = noise4[i];
+    AV_HIP(hipMemcpyAsync(a.st, st.data(), sizeof(DState) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_ctl, ct.data(), sizeof(DCtl) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_imu, im.data(), sizeof(DImu) * nimu, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_ops, ops.data(), sizeof(int) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_rm, rm.data(), sizeof(int) * 2 * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_red, red.data(), sizeof(int) * 2 * S, hipMemcpyHostToDevice, stm));
+    dev_launch_predict(a, S, wg, false, stm);
+    AV_LAUNCH_CHECK();
+    if (any_ops) {
+        hipLaunchKernelGGL(dk_prune_probe, dim3(S), dim3(wg), 0, stm, a, (const int*)(ar.p + o_ops), (const int*)(ar.p + o_rm), (int*)(ar.p + o_red));
+        AV_LAUNCH_CHECK();
+    }
+    AV_HIP(hipMemcpyAsync(st.data(), a.st, sizeof(DState) * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(red.data(), ar.p + o_red, sizeof(int) * 2 * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipStreamSynchronize(stm));
+    for (int s = 0; s < S; ++s) {
+        double* d = state_io + (size_t)s * SD; int32_t* I = state_int_io + (size_t)s * SI;
+        const DState& D = st[s];
+        d[0] = D.ts;
+        memcpy(d + 1, D.q, 32); memcpy(d + 5, D.p, 24); memcpy(d + 8, D.v, 24); memcpy(d + 11, D.bg, 24); memcpy(d + 14, D.ba, 24);
+        memcpy(d + 17, D.R_ic, 72); memcpy(d + 26, D.t_ci, 24); memcpy(d + 29, D.qn, 32); memcpy(d + 33, D.pn, 24); memcpy(d + 36, D.vn, 24);
+        memcpy(d + 39, D.gravity, 24); d[42] = D.tracking_rate;
+        I[0] = D.n; I[1] = D.ncam; I[2] = D.failed; I[3] = D.null_aliased; I[4] = D.first_img; I[5] = D.active;
+        redundant_out[2 * s] = red[2 * s]; redundant_out[2 * s + 1] = red[2 * s + 1];
+    }
+    return AV_OK;
+}
+
 // Work done so far, for the filter's roofline (drain first): [algorithmic fp64 flops of the gates, of the updates without the
 // reference's QR, of that QR by the survey's formula, features gated, updates run, rows stacked, device time of the phase chains
 // in ms (sum over stream groups; 0 unless timing was switched on with enable != 0 -- two HIP events per phase and group), phase

@@ -620,6 +620,19 @@ __global__ __launch_bounds__(256, 5) void dk_finish(DevArgs a)
     dk_finish_body(a, blockIdx.x);
 }
 
+// ------------------------------------------------------------------------------------------------
+// dk_prune_probe: parity tests only (av_msckf_predict_ops_dev; no step launches it).  Per stream, on the window as it stands:
+// ops bit 0: dev_find_redundant -> red[2 s], red[2 s + 1]; bit 1: remove_two_cams_body for the window positions rm[2 s] < rm[2 s + 1],
+// with the workgroup's threads as dk_finish has them.  The entry has checked every position against the window.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dk_prune_probe(DevArgs a, const int* ops, const int* rm, int* red)
+{
+    const int s = blockIdx.x;
+    const DState* D = a.st + s;
+    if ((ops[s] & 1) && threadIdx.x == 0) { int r0, r1; dev_find_redundant(a, s, *D, &r0, &r1); red[2 * s] = r0; red[2 * s + 1] = r1; }
+    if (ops[s] & 2)                                            // (workgroup-uniform)
+        remove_two_cams_body(a.P + (size_t)s * a.pstride, a.scratch + (size_t)s * a.pstride, D->n, a.ld, IMU_DIM + 6 * rm[2 * s], IMU_DIM + 6 * rm[2 * s + 1]);
+}
 
 }  // namespace
 

@@ -465,6 +465,17 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
     return AV_OK;
 }
 
+// The prediction's launches of a step, in a step's order: dk_state, [dk_begin4: the frame's observations, independent of the covariance],
+// dk_cov<dk_wg>.  One place for the step (dev_enqueue, append = true) and for the parity-test entry av_msckf_predict_ops_dev (append =
+// false: it has no observation store), so that the entry launches what the step launches.
+void dev_launch_predict(const DevArgs& a, int S, int dk_wg, bool append, hipStream_t stm)
+{
+    hipLaunchKernelGGL(dk_state, dim3((S + 63) / 64), dim3(64), 0, stm, a);     // state integration + the new camera state: a lane per stream
+    if (append) hipLaunchKernelGGL(dk_begin4, dim3(S), dim3(dk_wg), 0, stm, a);
+    if (dk_wg == 64) hipLaunchKernelGGL(dk_cov<64>, dim3(S), dim3(64), 0, stm, a);          // the covariance half of the prediction and of the augmentation
+    else hipLaunchKernelGGL(dk_cov<256>, dim3(S), dim3(256), 0, stm, a);
+}
+
 // the device side of one step on slot k: uploads of the slot's staging, the kernels, the read-back of the poses (no waits, no
 // host decisions: the sequence is the same every step, which is what lets it be captured as a graph)
 int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_t stm)
@@ -494,10 +505,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     // stream takes: four wavefronts (one stream 0.59 against 0.78 ms per frame, 256 streams x 1,500 features 36 against 29 k frames/s).
     const int dk_wg = d->dk_wg ? d->dk_wg : (S >= 1024 ? 64 : 256);       // (AV_DK_WG=64|256 forces one: A/B runs, and the parity tests of the shape small groups do not take)
     d->launched_wg = dk_wg;
-    hipLaunchKernelGGL(dk_state, dim3((S + 63) / 64), dim3(64), 0, stm, a);     // state integration + the new camera state: a lane per stream
-    hipLaunchKernelGGL(dk_begin4, dim3(S), dim3(dk_wg), 0, stm, a);
-    if (dk_wg == 64) hipLaunchKernelGGL(dk_cov<64>, dim3(S), dim3(64), 0, stm, a);          // the covariance half of the prediction and of the augmentation
-    else hipLaunchKernelGGL(dk_cov<256>, dim3(S), dim3(256), 0, stm, a);
+    dev_launch_predict(a, S, dk_wg, true, stm);
     AV_LAUNCH_CHECK();
     if ((rc = dev_phase(b, 0, stm, sl, a.cnt))) return rc;
     if (b->debug_capture && (rc = dev_debug_capture(b, 0, stm))) return rc;

@@ -203,6 +203,57 @@ class MsckfDevice(object):
         return dict(pos=pos.cpu().numpy(), valid=val.cpu().numpy(), H=H.cpu().numpy(), r=r.cpu().numpy(), gamma=gam.cpu().numpy(), ok=ok.cpu().numpy(),
                     row_off=row_off, rows=rows.reshape(-1))
 
+    STATE_FIELDS = (('ts', 1), ('q', 4), ('p', 3), ('v', 3), ('bg', 3), ('ba', 3), ('R_ic', 9), ('t_ci', 3), ('qn', 4), ('pn', 3), ('vn', 3),
+                    ('gravity', 3), ('tracking_rate', 1))          # state_io of av_msckf_predict_ops_dev, 43 doubles
+    STATE_INTS = ('n', 'ncam', 'failed', 'null_aliased', 'first_img', 'active')
+
+    def predict_ops_dev(self, streams, imu, cam_q, cam_p, cam_qn, P, noise, wg):
+        """Parity-test entry (av_msckf_predict_ops_dev; tests only): the prediction of the device-resident filter -- state integration,
+        covariance propagation, augmentation -- in the launch sequence a step begins with, for all `streams` at once, at wg = 64 or 256.
+        streams: one dict per stream with the STATE_FIELDS (R_ic 3 x 3 or 9), n, ncam, and optionally failed, null_aliased, first_img,
+        active (default 1), t_frame (default ts), imu_first / imu_cnt (default 0 / 0), find_redundant (bool), remove ((i0, i1) or None).
+        imu: float64[n_imu, 7] (t, gyro, acc).  cam_q / cam_p / cam_qn: [streams, cam_stride, 4 | 3 | 4]; P: [streams, ld, ld] (whatever
+        lies outside a stream's own square is the caller's pre-fill and must come back untouched).  The library checks every count and
+        position before it launches anything.
+        -> dict(streams: list of dicts (STATE_FIELDS + STATE_INTS as they come back, redundant: (r0, r1) or None), cam_q, cam_p, cam_qn, P)."""
+        S = len(streams)
+        cam_q = np.ascontiguousarray(cam_q, dtype=np.float64)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if cam_q.ndim != 3 or cam_q.shape[0] != S or P.ndim != 3 or P.shape[0] != S or P.shape[1] != P.shape[2]:
+            raise ValueError('predict_ops_dev: inconsistent shapes')
+        cs, ld = cam_q.shape[1], P.shape[1]
+        if np.shape(cam_p) != (S, cs, 3) or np.shape(cam_qn) != (S, cs, 4):
+            raise ValueError('predict_ops_dev: cam_p / cam_qn do not match cam_q')
+        sd, si, tf, ctl = np.zeros((S, 43)), np.zeros((S, 6), np.int32), np.zeros(S), np.zeros((S, 6), np.int32)
+        for s, st in enumerate(streams):
+            o = 0
+            for name, k in self.STATE_FIELDS:
+                sd[s, o:o + k] = np.asarray(st[name], dtype=np.float64).reshape(-1)
+                o += k
+            si[s, :5] = [st['n'], st['ncam'], st.get('failed', 0), st.get('null_aliased', 0), st.get('first_img', 0)]
+            tf[s] = st.get('t_frame', st['ts'])
+            rm = st.get('remove') or (0, 0)
+            ctl[s] = [st.get('active', 1), st.get('imu_first', 0), st.get('imu_cnt', 0), (1 if st.get('find_redundant') else 0) | (2 if st.get('remove') else 0), rm[0], rm[1]]
+        imu = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 7)
+        red = np.full((S, 2), -1, np.int32)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
+        q, p, qn, Pd = up(cam_q), up(cam_p), up(cam_qn), up(P)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_predict_ops_dev(self._h, S, int(wg), cs, ld, ld * ld, hp(sd), hp(si), hp(tf), hp(ctl), hp(imu), len(imu), _d(noise),
+                                                     N.dptr(q), N.dptr(p), N.dptr(qn), N.dptr(Pd), hp(red), self._st()))
+            torch.cuda.synchronize()
+        out = []
+        for s, st in enumerate(streams):
+            d, o = {}, 0
+            for name, k in self.STATE_FIELDS:
+                d[name] = sd[s, o:o + k].copy() if k > 1 else float(sd[s, o])
+                o += k
+            d.update(zip(self.STATE_INTS, (int(v) for v in si[s])))
+            d['redundant'] = (int(red[s, 0]), int(red[s, 1])) if st.get('find_redundant') else None
+            out.append(d)
+        return dict(streams=out, cam_q=q.cpu().numpy(), cam_p=p.cpu().numpy(), cam_qn=qn.cpu().numpy(), P=Pd.cpu().numpy())
+
     def update(self, blk_rows, blk_lens, obs_noise):
         """Stacked EKF update on the selected blocks; returns delta_x (n doubles)."""
         n = self.dim
