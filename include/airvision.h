@@ -331,14 +331,48 @@ int av_frontend_read_mask(av_frontend* fe, int cam, uint8_t* out_host);
  * its tables refuses every step, prestage and upload, AV_E_INVALID, with a text that names av_frontend_set_photometric.
  * av_frontend_read_photometric copies the tables of camera `cam` (0 / 1) back: response_out_host [256], gain_out_host
  * [height * width]; either may be NULL; a part that was given as NULL reads back as the identity (p * 256, 4096).
- * Not covered: per-stream tables, tables that change during a run, a per-pixel dark frame, exposure-time normalisation between
- * frames, fusing the stage into the conversion / Bayer / unpack kernels, gains of 16 and above, estimating the calibration itself,
+ * Not covered: per-stream tables, tables that change during a run, a per-pixel dark frame, fusing the stage into the conversion / Bayer / unpack kernels, gains of 16 and above, estimating the calibration itself,
  * two cameras of different sizes; fast_threshold and the LK thresholds are not retuned for corrected images. */
 #define AV_FE_PHOTOMETRIC 8
 #define AV_PHOTOMETRIC_RESPONSE_MAX 65280
 int av_frontend_set_photometric(av_frontend* fe, const uint16_t* response0_host, const uint16_t* gain0_host,
                                 const uint16_t* response1_host, const uint16_t* gain1_host);
 int av_frontend_read_photometric(av_frontend* fe, int cam, uint16_t* response_out_host, uint16_t* gain_out_host);
+
+/* Exposure-time normalisation: AV_FE_EXPOSURE in av_frontend_config.flags.  The third term of the TUM photometric model
+ * I(x) = G(t * V(x) * B(x)): the exposure time t of each frame.  A camera on auto-exposure changes t from frame to frame, and both LK
+ * passes assume constant brightness between the two images they compare.  Per frame and per camera one factor
+ *   k  uint16 in Q12, 1 <= k <= 65535:  k = min(65535, max(1, floor(4096 * t_ref / t + 0.5)))
+ * computed once, on the host, in float64 (the Python frontend.quantise_exposure; t <= 0, t_ref <= 0 or a non-finite value is refused
+ * there); the range goes up to 15.9998, as the vignette gain's.  Everything after it is integer, so this text is the contract
+ * (tests/exposure_ref.py states it in NumPy).  The effective response table of a frame, for p = 0 .. 255:
+ *   r'[p] = min(65280, (response[p] * k + 2048) >> 12)              response absent: response[p] = p << 8
+ * (65280 * 65535 + 2048 < 2^32), and the pixel is that of "Photometric calibration" with r' in place of the response:
+ *   out = min(255, (r'[p] * gain[x] + (1 << 19)) >> 20)             gain absent: 4096
+ * k = 4096 gives r' = response exactly: a frame at the reference exposure is byte for byte what the photometric stage alone makes of it.
+ * It IS the photometric stage -- the kernel scales the 256-entry table of its workgroup's image while it stages it, nothing is added per
+ * pixel -- so the order of the input stage is unchanged: raw -> conversion to grey -> photometric (with exposure) -> binning -> CLAHE.
+ * Either flag turns the stage on and makes the engine own level 0.  With AV_FE_EXPOSURE alone the tables are the identity and
+ * av_frontend_set_photometric is neither required nor accepted.
+ * av_frontend_next_exposure hands over the factors of the frames of the NEXT call that hands frames over, HOST arrays k0 (cam0) and k1
+ * (cam1) of n entries: n = n_streams for av_frontend_step, _step_host and _prestage, the upload's n for av_frontend_frames_upload.
+ * AV_E_INVALID with a text: a zero factor, a null pointer, an engine without the flag; a wrong n is found by the call that consumes them.
+ * A call that runs the input stage consumes the pending factors; with none pending on an engine with the flag it is refused,
+ * AV_E_INVALID, with a text that names av_frontend_next_exposure.  A call that does not run the stage needs none: the step after an
+ * av_frontend_prestage of the same pointers (the factors given before the prestage belong to the prestaged frames), and
+ * av_frontend_step_frames.  Every call that hands frames over leaves nothing pending when it returns, whatever it returns: factors
+ * left pending across a step that skipped the stage are discarded.
+ * The factors reach the device on the call's own stream from a pinned ring, as the per-step homographies do (an upload's travel with
+ * the upload on the copy stream): no host wait, no synchronisation and no kernel launch are added, and the timing spans are those of
+ * an AV_FE_PHOTOMETRIC engine.  In the frame store an entry named twice in one upload gets its later frame with that frame's factor,
+ * corrected once (with AV_FE_CLAHE the refusal of duplicates stands).
+ * av_frontend_read_exposure: out2 = the factors (cam0, cam1) the frame of stream stream_idx's last step was corrected with; through
+ * the frame store, those of the entry it read.
+ * Not covered: estimating exposures when the camera does not report them; analogue gain as a separate input (the caller folds it into
+ * t); exposure applied ahead of a 16-bit conversion or the range scaling; per-stream reference exposures; retuned thresholds. */
+#define AV_FE_EXPOSURE 16
+int av_frontend_next_exposure(av_frontend* fe, const uint16_t* k0_host, const uint16_t* k1_host, int n);
+int av_frontend_read_exposure(av_frontend* fe, int stream_idx, uint16_t out2[2]);
 
 /* ImageProcessingPipeline.stereo_callback for every stream at once (pipeline.py:46-150).
  * Stream s reads its cam0/cam1 images (tightly packed width*height u8, device memory) at
@@ -710,6 +744,12 @@ int av_downscale_vector_path(const uint8_t* img_dev, int64_t img_stride, int n_i
  * ------------------------------------------------------------------------------------------- */
 int av_photometric(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
                    const uint16_t* response_dev, const uint16_t* gain_dev, void* stream);
+/* The same with per-image exposure factors ("Exposure-time normalisation" above): k_dev uint16[n] Q12 on the device, image i with
+ * r'[p] = min(65280, (response[p] * k_dev[i] + 2048) >> 12) in place of response[p]; NULL = none (then exactly av_photometric).  All
+ * three of response_dev, gain_dev and k_dev are optional, but not all three NULL; the other checks are av_photometric's.  A factor of 0
+ * is not refused here (it blacks the image out); the engine refuses it. */
+int av_photometric_exposure(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                            const uint16_t* response_dev, const uint16_t* gain_dev, const uint16_t* k_dev, void* stream);
 /* TEST-ONLY observable, not part of the supported interface (it may change or go without notice): 1 if av_photometric with these
  * arguments takes 16 pixels per lane, 0 if one (or if the arguments are not a valid call).  The launcher's own rule, exported so that
  * tests/test_gpu_photometric_op.py can assert which body a case reached.  Pure host function. */

@@ -21,6 +21,7 @@ AV_FE_INPUTS_PERSIST = 1
 AV_FE_RANSAC = 2
 AV_FE_CLAHE = 4
 AV_FE_PHOTOMETRIC = 8
+AV_FE_EXPOSURE = 16
 AV_PHOTOMETRIC_RESPONSE_MAX = 65280
 AV_CLAHE_MAX_TILES = 16
 AV_GRAY16_SHIFT, AV_GRAY16_WINDOW, AV_GRAY16_AUTO = 0, 1, 2
@@ -298,6 +299,9 @@ SIGNATURES = {
     'av_frontend_set_photometric': (C.c_int, [_P, _P, _P, _P, _P]),
     'av_frontend_read_photometric': (C.c_int, [_P, C.c_int, _P, _P]),
     'av_photometric': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
+    'av_photometric_exposure': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    'av_frontend_next_exposure': (C.c_int, [_P, _P, _P, C.c_int]),
+    'av_frontend_read_exposure': (C.c_int, [_P, C.c_int, _P]),
     'av_photometric_vector_path': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P]),
     'av_frontend_enable_timing': (C.c_int, [_P, C.c_int]),
     'av_frontend_read_timing': (C.c_int, [_P, C.POINTER(C.c_double * 4), C.POINTER(C.c_int32 * 4)]),

@@ -82,6 +82,11 @@ class ConfigEuRoC(object):
         self.cam1_response = None
         self.cam0_vignette = None
         self.cam1_vignette = None
+        # exposure-time normalisation between frames (no counterpart in the reference; "Exposure-time normalisation" in
+        # include/airvision.h): the reference exposure time t_ref, a float in the unit of the exposures the entry points are then
+        # handed with every frame (FrontendEngine.step(..., exposure=(e0, e1)); the drop-in reads `exposure` off the image messages).
+        # Every frame is scaled by t_ref / t inside the photometric stage.  None: off, and the front-end is the reference's, bit for bit.
+        self.exposure_reference = None
         # scaling of 16-bit grey samples (image_format 'gray16' only; no counterpart in the reference; "Range scaling of 16-bit grey" in
         # include/airvision.h): 'shift' = min(255, v >> gray16_shift), 'window' = gray16_window = (lo, hi) mapped to 0 .. 255 for every
         # image, 'auto' = a range per stereo pair from the pair's own histogram on the GPU: gray16_auto_clip = the parts per million of

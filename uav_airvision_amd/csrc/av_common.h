@@ -346,8 +346,10 @@ int av_launch_downscale(const FrameSet& src, const FrameSet& dst, int n_groups, 
 // device, one per camera, null = that part is the identity (at least one part is given; cameras that differ in their parts take one
 // launch each).  Sets and list as av_launch_to_gray8 -- the destination's list, a negative entry skips the group -- but dst may be src:
 // a source with a list (the destination's own) is read through it, which is the in-place call on a listed set.
+// k0 / k1: the exposure factors of the launch ("Exposure-time normalisation"), uint16 [n_groups] Q12 on the device, by GROUP of the
+// launch (not by entry of a list), one array per camera; null = off (both or neither for two cameras).  With them no table is required.
 int av_launch_photometric(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
-                          const uint16_t* gain0, const uint16_t* gain1, hipStream_t st);
+                          const uint16_t* gain0, const uint16_t* gain1, const uint16_t* k0, const uint16_t* k1, hipStream_t st);
 // range16.hip: n_groups 16-bit grey frames of one camera or of two to tightly packed 8-bit grey through a window instead of a shift
 // ("Range scaling of 16-bit grey" in include/airvision.h).  Sets and list as av_launch_to_gray8 -- the destination's list, a negative
 // entry skips the group (its histogram, its record and its pixels).  A group is the images of one FrameSet group: the two cameras'

@@ -662,7 +662,8 @@ struct av_frontend {
         bool l0_in_place = true;                 // false if the pyramid launcher had to write padded level-0 copies (unaligned geometry)
         std::vector<int> prev;                   // host: slot of every stream's previous frame (-1: none yet)
         struct Up { uint8_t* pin = nullptr; int* idx_h = nullptr; int* idx_d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false;
-                    uint8_t* raw_d = nullptr; };      // raw_d: grey_chain's `raw` when a stage writes the store; idx_h / idx_d then hold its `first` list behind the entries' own
+                    uint8_t* raw_d = nullptr;                                 // raw_d: grey_chain's `raw` when a stage writes the store; idx_h / idx_d then hold its `first` list behind the entries' own
+                    uint16_t* k_h = nullptr; uint16_t* k_d = nullptr; };      // AV_FE_EXPOSURE: the upload's factors [2][cap], pinned and on the device, by position in the upload
         uint8_t* gray_d = nullptr; size_t gray_cap = 0;       // grey_chain's `gray_full` of ONE upload (uploads are serialised on the copy stream: one scratch serves the whole ring)
         uint8_t* mosaic_d = nullptr; size_t mosaic_cap = 0;   // grey_chain's `mosaic` of one upload, likewise (packed mosaics only)
         uint32_t* range_d = nullptr; size_t range_cap = 0;    // grey_chain's `range` of one upload, likewise (AV_GRAY16_AUTO only): histograms, then records
@@ -670,6 +671,7 @@ struct av_frontend {
         hipEvent_t uploaded = nullptr; bool any_upload = false;      // copy stream: the newest upload's kernels have finished
         hipEvent_t stepped = nullptr; bool any_step = false;          // step stream: the newest step has finished
         long long frames_uploaded = 0;
+        std::vector<uint16_t> k;                 // AV_FE_EXPOSURE, host: [n_slots][2] the factors the frame in each entry was corrected with (0: none yet)
     } fs;
     std::vector<void*> allocs;
     double* dH = nullptr;
@@ -706,6 +708,14 @@ struct av_frontend {
     // handed, ph_resp / ph_gain: null = that part is the identity for that camera.  photo_set: the tables have been given (a step before that is refused)
     bool photo = false, photo_set = false; uint16_t* ph_resp_buf = nullptr; uint16_t* ph_gain_buf[2] = {nullptr, nullptr};
     const uint16_t* ph_resp[2] = {nullptr, nullptr}; const uint16_t* ph_gain[2] = {nullptr, nullptr};
+    // AV_FE_EXPOSURE ("Exposure-time normalisation" in include/airvision.h): the stage is on with either flag (photo); photo_tables = the
+    // engine has AV_FE_PHOTOMETRIC and wants its tables.  ex_pend: what av_frontend_next_exposure left for the next call that hands
+    // frames over, [2][n] by camera.  The step paths: a pinned ring ex_h [2][S] with one event per slot, like hH, and the factors on the
+    // device ex_d [2][S], copied on the call's own stream ahead of the stage's launch.  Host copies for av_frontend_read_exposure:
+    // ex_slot_k [2][2][S] by cam0's pyramid slot (a prestaged frame's factors wait there for its step), ex_last [S][2] of every stream's last step
+    bool expo = false, photo_tables = false, ex_pending = false;
+    std::vector<uint16_t> ex_pend, ex_slot_k, ex_last; int ex_pend_n = 0;
+    uint16_t* ex_h[8] = {nullptr}; hipEvent_t ex_ev[8]; int ex_slot = 0; uint16_t* ex_d = nullptr;
     // av_frontend_set_gray16_scale ("Range scaling of 16-bit grey" in include/airvision.h): the settings, and for
     // AV_GRAY16_AUTO the step paths' histograms [S][4096] (zero between launches) and records [2][S][4] -- by cam0's pyramid slot, so
     // that a prestaged frame does not replace the records of the step before it (the frame store: FrameStore::range_d)
@@ -810,10 +820,11 @@ uint8_t* eq_slot(const av_frontend* fe, int slot) { return fe->eq + (size_t)slot
 //   mosaic     the caller's 8-bit mosaic scratch, between the two passes of a packed mosaic's conversion (n frames per camera, no list)
 //   lut        the look-up tables of one equalisation
 //   range      gray16_scale = AV_GRAY16_AUTO: the caller's histograms [n][4096] (zero, and left zero) and records [n][4], by group
+//   k0, k1     AV_FE_EXPOSURE: the exposure factors of the n groups on the device, one array per camera, by group; else null
 // *level0 = the set the pyramid launch reads: l0 if any stage ran (fe->own_l0: the engine then owns level 0, which outlives the call
 // whatever the caller's frames do), else raw.
 int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, const int* first, const FrameSet& gray_full, const FrameSet& mosaic,
-               uint8_t* lut, uint32_t* range_hist, uint32_t* range_rec, hipStream_t st, FrameSet* level0)
+               uint8_t* lut, uint32_t* range_hist, uint32_t* range_rec, const uint16_t* k0, const uint16_t* k1, hipStream_t st, FrameSet* level0)
 {
     const av_frontend_config& c = fe->cfg;
     const bool conv = fe->fmt != AV_PIX_GRAY8, bin = fe->ds > 1;
@@ -833,7 +844,7 @@ int grey_chain(av_frontend* fe, const FrameSet& raw, int n, const FrameSet& l0, 
         // after a conversion: in place on its target, through the list that target was written through (`first` for l0, none for
         // gray_full); without one: out of the raw frames, which are the caller's and are never written
         const FrameSet& to = conv ? at : bin ? gray_full : l0_first;
-        if ((rc = av_launch_photometric(at, to, n, fe->in_w, fe->in_h, fe->ph_resp[0], fe->ph_resp[1], fe->ph_gain[0], fe->ph_gain[1], st))) return rc;
+        if ((rc = av_launch_photometric(at, to, n, fe->in_w, fe->in_h, fe->ph_resp[0], fe->ph_resp[1], fe->ph_gain[0], fe->ph_gain[1], k0, k1, st))) return rc;
         at = to;
     }
     if (bin && (rc = av_launch_downscale(at, l0_first, n, fe->in_w, fe->in_h, fe->ds, st))) return rc;
@@ -854,12 +865,24 @@ int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64
     const FeDev& d = fe->d;
     const int64_t hw = (int64_t)d.w * d.h, in_hw = (int64_t)fe->in_w * fe->in_h;
     Span sp(fe, 0, st);
+    const uint16_t* k0 = nullptr; const uint16_t* k1 = nullptr;
+    if (fe->expo) {                          // the pending factors (the entry point has checked them) go to the device ahead of the stage, on this stream
+        const int S = d.S, slot = fe->ex_slot;
+        fe->ex_slot = (slot + 1) & 7;
+        AV_HIP(hipEventSynchronize(fe->ex_ev[slot]));
+        memcpy(fe->ex_h[slot], fe->ex_pend.data(), sizeof(uint16_t) * 2 * S);
+        AV_HIP(hipMemcpyAsync(fe->ex_d, fe->ex_h[slot], sizeof(uint16_t) * 2 * S, hipMemcpyHostToDevice, st));
+        AV_HIP(hipEventRecord(fe->ex_ev[slot], st));
+        memcpy(fe->ex_slot_k.data() + (size_t)cur * 2 * S, fe->ex_pend.data(), sizeof(uint16_t) * 2 * S);
+        fe->ex_pending = false;
+        k0 = fe->ex_d; k1 = fe->ex_d + S;
+    }
     const FrameSet l0 = fe->own_l0 ? FrameSet{{eq_slot(fe, cur), eq_slot(fe, 2)}, hw, nullptr} : FrameSet{};
     const FrameSet gray = fe->gray_full ? FrameSet{{fe->gray_full, fe->gray_full + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
     const FrameSet mosaic = fe->mosaic ? FrameSet{{fe->mosaic, fe->mosaic + (size_t)d.S * in_hw}, in_hw, nullptr} : FrameSet{};
     FrameSet level0;
     int rc = grey_chain(fe, av_frames(img0, img1, img_stride), d.S, l0, nullptr, gray, mosaic, fe->eq_lut, fe->g16_hist,
-                        fe->g16_rec ? fe->g16_rec + (size_t)cur * 4 * d.S : nullptr, st, &level0);
+                        fe->g16_rec ? fe->g16_rec + (size_t)cur * 4 * d.S : nullptr, k0, k1, st, &level0);
     if (rc) return rc;
     return av_launch_pyramid(level0, d.S, fe->geom, fe->pyr, 3 * fe->lay.bytes, fe->lay.bytes, cur, 2, st, !(inputs_persist || fe->own_l0), wrote_l0);
 }
@@ -900,6 +923,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
                 continue;
             }
             fe->fs.prev[s] = slots[s];
+            if (fe->expo) { fe->ex_last[2 * s] = fe->fs.k[2 * (size_t)slots[s]]; fe->ex_last[2 * s + 1] = fe->fs.k[2 * (size_t)slots[s] + 1]; }
         }
         if (sh.first) {
             any_first = true;
@@ -933,6 +957,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         if (fe->pre_on && fe->pre_img0 == img0 && fe->pre_img1 == img1 && fe->pre_stride == img_stride) wrote_l0 = fe->pre_wrote_l0;      // built by av_frontend_prestage
         else if ((rc = input_stage(fe, img0, img1, img_stride, cur, inputs_persist, st, &wrote_l0))) return rc;
         fe->pre_on = false;
+        if (fe->expo) for (int s = 0; s < S; ++s) { fe->ex_last[2 * s] = fe->ex_slot_k[((size_t)cur * 2 + 0) * S + s]; fe->ex_last[2 * s + 1] = fe->ex_slot_k[((size_t)cur * 2 + 1) * S + s]; }
         if (fe->own_l0) { img0 = eq_slot(fe, cur); img1 = eq_slot(fe, 2); img_stride = (int64_t)d.w * d.h; }      // from here on the engine's own grey (equalised) images are the step's inputs
         fe->l0_img[cur] = wrote_l0 ? nullptr : img0; fe->l0_img[2] = wrote_l0 ? nullptr : img1;
         fe->l0_stride[cur] = fe->l0_stride[2] = img_stride;
@@ -1136,11 +1161,16 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     }
     fe->fmt = cfg->pixel_format; fe->fmt_shift = cfg->gray16_shift;
     fe->ds = ds; fe->in_w = in_w; fe->in_h = in_h; fe->frame_bytes = av_pixfmt_frame_bytes(fe->fmt, in_w, in_h);
-    fe->photo = (cfg->flags & AV_FE_PHOTOMETRIC) != 0;
+    fe->photo_tables = (cfg->flags & AV_FE_PHOTOMETRIC) != 0; fe->expo = (cfg->flags & AV_FE_EXPOSURE) != 0;
+    fe->photo = fe->photo_tables || fe->expo;          // either flag turns the stage on
     fe->own_l0 = clahe || fe->fmt != AV_PIX_GRAY8 || ds > 1 || fe->photo;
     if (fe->own_l0) A(fe->eq, (size_t)3 * S * w * h)
     if (ds > 1 && (fe->fmt != AV_PIX_GRAY8 || fe->photo)) A(fe->gray_full, (size_t)2 * S * in_w * in_h)
-    if (fe->photo) A(fe->ph_resp_buf, 2 * 256)
+    if (fe->photo_tables) A(fe->ph_resp_buf, 2 * 256)
+    if (fe->expo) {
+        A(fe->ex_d, 2 * S)
+        fe->ex_slot_k.assign((size_t)4 * S, 0); fe->ex_last.assign((size_t)2 * S, 0);
+    }
     if (av_pixfmt_packed_depth(fe->fmt) && av_pixfmt_is_bayer(fe->fmt)) A(fe->mosaic, (size_t)2 * S * in_w * in_h)
     if (clahe) {
         A(fe->eq_lut, (size_t)2 * S * cfg->clahe_tiles_x * cfg->clahe_tiles_y * 256)
@@ -1150,6 +1180,14 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     for (int i = 0; i < 8; ++i) {
         if (hipHostMalloc((void**)&fe->hH[i], sizeof(double) * (9 * S + S + (ransac ? 19 * S : 0)), hipHostMallocDefault) != hipSuccess ||
             hipEventCreateWithFlags(&fe->hH_ev[i], hipEventDisableTiming) != hipSuccess) {
+            av_set_error("av_frontend_create: pinned staging allocation failed");
+            av_frontend_destroy(fe);
+            return AV_E_HIP;
+        }
+    }
+    for (int i = 0; i < 8 && fe->expo; ++i) {
+        if (hipHostMalloc((void**)&fe->ex_h[i], sizeof(uint16_t) * 2 * S, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&fe->ex_ev[i], hipEventDisableTiming) != hipSuccess) {
             av_set_error("av_frontend_create: pinned staging allocation failed");
             av_frontend_destroy(fe);
             return AV_E_HIP;
@@ -1190,6 +1228,8 @@ AV_EXPORT void av_frontend_destroy(av_frontend* fe)
         if (u.idx_h) (void)hipHostFree(u.idx_h);
         if (u.idx_d) (void)hipFree(u.idx_d);
         if (u.raw_d) (void)hipFree(u.raw_d);
+        if (u.k_h) (void)hipHostFree(u.k_h);
+        if (u.k_d) (void)hipFree(u.k_d);
         if (u.done) (void)hipEventDestroy(u.done);
     }
     if (fe->fs.gray_d) (void)hipFree(fe->fs.gray_d);
@@ -1200,6 +1240,9 @@ AV_EXPORT void av_frontend_destroy(av_frontend* fe)
     if (fe->copy_stream) (void)hipStreamDestroy(fe->copy_stream);
     for (int i = 0; i < 8; ++i) {
         if (fe->hH[i]) { (void)hipHostFree(fe->hH[i]); (void)hipEventDestroy(fe->hH_ev[i]); }
+    }
+    for (int i = 0; i < 8; ++i) {
+        if (fe->ex_h[i]) { (void)hipHostFree(fe->ex_h[i]); (void)hipEventDestroy(fe->ex_ev[i]); }
     }
     for (int i = 0; i < 2; ++i) {
         av_frontend::ReadSlot& r = fe->rd[i];
@@ -1235,9 +1278,30 @@ AV_EXPORT int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_
 // AV_FE_PHOTOMETRIC: an engine with the flag takes no frame before it has its tables
 static int photo_ready(const av_frontend* fe, const char* who)
 {
-    if (!fe->photo || fe->photo_set) return AV_OK;
+    if (!fe->photo_tables || fe->photo_set) return AV_OK;
     av_set_error("%s: the engine was created with AV_FE_PHOTOMETRIC but has no tables yet: call av_frontend_set_photometric first", who);
     return AV_E_INVALID;
+}
+
+// AV_FE_EXPOSURE: every call that hands frames over leaves nothing pending when it returns, whatever it returns
+struct ExpoDone {
+    av_frontend* fe;
+    ~ExpoDone() { if (fe) fe->ex_pending = false; }
+};
+// ... and one that runs the input stage on n frames needs the factors of exactly those (runs = false: the step after a prestage of the
+// same images, which needs none and discards what is pending)
+static int expo_ready(av_frontend* fe, const char* who, int n, bool runs)
+{
+    if (!fe->expo || !runs) return AV_OK;
+    if (!fe->ex_pending) {
+        av_set_error("%s: the engine was created with AV_FE_EXPOSURE and has no exposure factors for these frames: call av_frontend_next_exposure first", who);
+        return AV_E_INVALID;
+    }
+    if (fe->ex_pend_n != n) {
+        av_set_error("%s: av_frontend_next_exposure gave the factors of %d frames, this call hands over %d", who, fe->ex_pend_n, n);
+        return AV_E_INVALID;
+    }
+    return AV_OK;
 }
 
 // The pyramids of the images the NEXT av_frontend_step will get, enqueued now (behind the step just enqueued): that step then starts
@@ -1248,9 +1312,10 @@ static int photo_ready(const av_frontend* fe, const char* who)
 // Needs AV_FE_INPUTS_PERSIST (the images are read again by the step itself); a step that comes with other images builds its own.
 AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride, void* stream)
 {
+    const ExpoDone done{fe};
     if (!fe || !img0_dev || !img1_dev || img_stride < fe->frame_bytes) { av_set_error("av_frontend_prestage: bad arguments"); return AV_E_INVALID; }
     if (!(fe->cfg.flags & AV_FE_INPUTS_PERSIST)) { av_set_error("av_frontend_prestage: the engine was created without AV_FE_INPUTS_PERSIST"); return AV_E_INVALID; }
-    if (photo_ready(fe, "av_frontend_prestage")) return AV_E_INVALID;
+    if (photo_ready(fe, "av_frontend_prestage") || expo_ready(fe, "av_frontend_prestage", fe->d.S, true)) return AV_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     AV_HIP(hipSetDevice(fe->device));
     bool wrote_l0 = true;
@@ -1267,22 +1332,26 @@ AV_EXPORT int av_frontend_prestage(av_frontend* fe, const uint8_t* img0_dev, con
 AV_EXPORT int av_frontend_step(av_frontend* fe, const uint8_t* img0_dev, const uint8_t* img1_dev, int64_t img_stride,
                                const double* timestamps, void* stream)
 {
+    const ExpoDone done{fe};
     if (!fe || !img0_dev || !img1_dev || !timestamps || img_stride < fe->frame_bytes) {
         av_set_error("av_frontend_step: bad arguments");
         return AV_E_INVALID;
     }
     if (photo_ready(fe, "av_frontend_step")) return AV_E_INVALID;
+    const bool prestaged = fe->pre_on && fe->pre_img0 == img0_dev && fe->pre_img1 == img1_dev && fe->pre_stride == img_stride;      // (step_impl: it then skips the stage)
+    if (expo_ready(fe, "av_frontend_step", fe->d.S, !prestaged)) return AV_E_INVALID;
     return step_impl(fe, img0_dev, img1_dev, img_stride, timestamps, (hipStream_t)stream, (fe->cfg.flags & AV_FE_INPUTS_PERSIST) != 0);
 }
 
 AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, const uint8_t* img1_host, int64_t img_stride,
                                     const double* timestamps, void* stream)
 {
+    const ExpoDone done{fe};
     if (!fe || !img0_host || !img1_host || !timestamps || img_stride < fe->frame_bytes) {
         av_set_error("av_frontend_step_host: bad arguments");
         return AV_E_INVALID;
     }
-    if (photo_ready(fe, "av_frontend_step_host")) return AV_E_INVALID;
+    if (photo_ready(fe, "av_frontend_step_host") || expo_ready(fe, "av_frontend_step_host", fe->d.S, true)) return AV_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t img_bytes = (size_t)fe->frame_bytes;                  // the staging slots carry the frames in their own format and size
     const int S = fe->d.S;
@@ -1339,6 +1408,7 @@ AV_EXPORT int av_frontend_frames_reserve(av_frontend* fe, int n_slots)
     AV_HIP(hipEventCreateWithFlags(&fs.stepped, hipEventDisableTiming));
     if (!fe->copy_stream) AV_HIP(hipStreamCreateWithFlags(&fe->copy_stream, hipStreamNonBlocking));
     fs.prev.assign((size_t)d.S, -1);
+    if (fe->expo) fs.k.assign((size_t)2 * n_slots, 0);
     fs.n_slots = n_slots;
     return AV_OK;
 }
@@ -1347,6 +1417,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
                                         int64_t img_stride, void* stream)
 {
     (void)stream;
+    const ExpoDone done{fe};
     if (!fe || n < 0 || (n > 0 && (!slots || !img0_host || !img1_host)) || img_stride < fe->frame_bytes) {
         av_set_error("av_frontend_frames_upload: bad arguments");
         return AV_E_INVALID;
@@ -1355,6 +1426,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     if (!fs.n_slots) { av_set_error("av_frontend_frames_upload: no frame store (av_frontend_frames_reserve first)"); return AV_E_INVALID; }
     if (photo_ready(fe, "av_frontend_frames_upload")) return AV_E_INVALID;
     if (n == 0) return AV_OK;
+    if (expo_ready(fe, "av_frontend_frames_upload", n, true)) return AV_E_INVALID;
     for (int i = 0; i < n; ++i)
         if (slots[i] < 0 || slots[i] >= fs.n_slots) { av_set_error("av_frontend_frames_upload: entry %d outside the store (%d entries)", slots[i], fs.n_slots); return AV_E_INVALID; }
     if (fe->clahe) {                 // the entries are equalised where they lie: one named twice would be equalised twice, or half
@@ -1377,11 +1449,16 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     if ((size_t)n > u.cap) {
         if (u.pin) { (void)hipHostFree(u.pin); (void)hipHostFree(u.idx_h); (void)hipFree(u.idx_d); u.pin = nullptr; u.idx_h = nullptr; u.idx_d = nullptr; }
         if (u.raw_d) { (void)hipFree(u.raw_d); u.raw_d = nullptr; }
+        if (u.k_h) { (void)hipHostFree(u.k_h); (void)hipFree(u.k_d); u.k_h = nullptr; u.k_d = nullptr; }
         const size_t cap = (size_t)n + 16;
         AV_HIP(hipHostMalloc((void**)&u.pin, cap * 2 * fb, hipHostMallocDefault));
         AV_HIP(hipHostMalloc((void**)&u.idx_h, (raw ? 2 : 1) * cap * sizeof(int), hipHostMallocDefault));
         AV_HIP(hipMalloc((void**)&u.idx_d, (raw ? 2 : 1) * cap * sizeof(int)));
         if (raw) AV_HIP(hipMalloc((void**)&u.raw_d, cap * 2 * fb));
+        if (fe->expo) {
+            AV_HIP(hipHostMalloc((void**)&u.k_h, cap * 2 * sizeof(uint16_t), hipHostMallocDefault));
+            AV_HIP(hipMalloc((void**)&u.k_d, cap * 2 * sizeof(uint16_t)));
+        }
         if (!u.done) AV_HIP(hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
         u.cap = cap;
     }
@@ -1421,6 +1498,12 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     if (fs.any_step) AV_HIP(hipStreamWaitEvent(cs, fs.stepped, 0));
     AV_HIP(hipMemcpyAsync(u.idx_d, u.idx_h, sizeof(int) * (raw ? 2 : 1) * n, hipMemcpyHostToDevice, cs));
     int rc;
+    if (fe->expo) {                  // the upload's factors travel with it: [2][n] by position; an entry keeps those of the last frame that names it
+        memcpy(u.k_h, fe->ex_pend.data(), sizeof(uint16_t) * 2 * n);
+        AV_HIP(hipMemcpyAsync(u.k_d, u.k_h, sizeof(uint16_t) * 2 * n, hipMemcpyHostToDevice, cs));
+        for (int i = 0; i < n; ++i) { fs.k[2 * (size_t)slots[i]] = u.k_h[i]; fs.k[2 * (size_t)slots[i] + 1] = u.k_h[n + i]; }
+        fe->ex_pending = false;
+    }
     if (raw) AV_HIP(hipMemcpyAsync(u.raw_d, u.pin, (size_t)n * 2 * fb, hipMemcpyHostToDevice, cs));      // to the ring entry's device buffer in one copy: the grey chain takes them into their store entries
     for (int i = 0; i < n && !raw;) {                                // 8-bit grey at full size: straight into the entries, runs of consecutive ones in one copy
         int j = i + 1;
@@ -1437,7 +1520,7 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     const FrameSet mosaic = fs.mosaic_d ? FrameSet{{fs.mosaic_d, fs.mosaic_d + in_hw}, (int64_t)(2 * in_hw), nullptr} : FrameSet{};
     FrameSet level0;
     if ((rc = grey_chain(fe, raw ? av_frames(u.raw_d, u.raw_d + fb, (int64_t)(2 * fb)) : l0, n, l0, raw ? u.idx_d + n : nullptr, gray, mosaic, fe->fs_lut,
-                         fs.range_d, fs.range_d ? fs.range_d + fs.range_cap * 4096 : nullptr, cs, &level0))) return rc;
+                         fs.range_d, fs.range_d ? fs.range_d + fs.range_cap * 4096 : nullptr, fe->expo ? u.k_d : nullptr, fe->expo ? u.k_d + n : nullptr, cs, &level0))) return rc;
     bool wrote_l0 = true;
     if ((rc = av_launch_pyramid(level0, n, fe->geom, fs.pyr, 2 * fe->lay.bytes, fe->lay.bytes, 0, 1, cs, false, &wrote_l0))) return rc;
     fs.l0_in_place = !wrote_l0;
@@ -1704,7 +1787,7 @@ AV_EXPORT int av_frontend_set_photometric(av_frontend* fe, const uint16_t* respo
                                           const uint16_t* response1_host, const uint16_t* gain1_host)
 {
     if (!fe) { av_set_error("av_frontend_set_photometric: bad arguments"); return AV_E_INVALID; }
-    if (!fe->photo) { av_set_error("av_frontend_set_photometric: the engine was created without AV_FE_PHOTOMETRIC"); return AV_E_INVALID; }
+    if (!fe->photo_tables) { av_set_error("av_frontend_set_photometric: the engine was created without AV_FE_PHOTOMETRIC"); return AV_E_INVALID; }
     if (fe->fed) {
         av_set_error("av_frontend_set_photometric: the engine has already been handed a frame (step, prestage or frames_upload): the frames in it "
                      "would disagree with the new tables; set the tables of an engine before its first frame");
@@ -1751,7 +1834,7 @@ AV_EXPORT int av_frontend_set_photometric(av_frontend* fe, const uint16_t* respo
 AV_EXPORT int av_frontend_read_photometric(av_frontend* fe, int cam, uint16_t* response_out_host, uint16_t* gain_out_host)
 {
     if (!fe || cam < 0 || cam > 1) { av_set_error("av_frontend_read_photometric: bad arguments"); return AV_E_INVALID; }
-    if (!fe->photo || !fe->photo_set) { av_set_error("av_frontend_read_photometric: no tables are set (AV_FE_PHOTOMETRIC and av_frontend_set_photometric)"); return AV_E_INVALID; }
+    if (!fe->photo_tables || !fe->photo_set) { av_set_error("av_frontend_read_photometric: no tables are set (AV_FE_PHOTOMETRIC and av_frontend_set_photometric)"); return AV_E_INVALID; }
     AV_HIP(hipSetDevice(fe->device));
     const size_t in_hw = (size_t)fe->in_w * fe->in_h;
     if (response_out_host) {
@@ -1762,6 +1845,29 @@ AV_EXPORT int av_frontend_read_photometric(av_frontend* fe, int cam, uint16_t* r
         if (fe->ph_gain[cam]) AV_HIP(hipMemcpy(gain_out_host, fe->ph_gain[cam], in_hw * sizeof(uint16_t), hipMemcpyDeviceToHost));
         else for (size_t i = 0; i < in_hw; ++i) gain_out_host[i] = 4096;
     }
+    return AV_OK;
+}
+
+// ---- exposure-time normalisation ("Exposure-time normalisation" in include/airvision.h) ----------------------------------------------
+AV_EXPORT int av_frontend_next_exposure(av_frontend* fe, const uint16_t* k0_host, const uint16_t* k1_host, int n)
+{
+    if (!fe || !k0_host || !k1_host || n <= 0) { av_set_error("av_frontend_next_exposure: bad arguments (a null pointer, or n = %d)", n); return AV_E_INVALID; }
+    if (!fe->expo) { av_set_error("av_frontend_next_exposure: the engine was created without AV_FE_EXPOSURE"); return AV_E_INVALID; }
+    for (int i = 0; i < n; ++i)
+        if (!k0_host[i] || !k1_host[i]) { av_set_error("av_frontend_next_exposure: the factor of cam%d of frame %d is 0 (1 .. 65535 in Q12)", k0_host[i] ? 1 : 0, i); return AV_E_INVALID; }
+    fe->ex_pend.resize((size_t)2 * n);
+    memcpy(fe->ex_pend.data(), k0_host, sizeof(uint16_t) * n);
+    memcpy(fe->ex_pend.data() + n, k1_host, sizeof(uint16_t) * n);
+    fe->ex_pend_n = n; fe->ex_pending = true;
+    return AV_OK;
+}
+
+AV_EXPORT int av_frontend_read_exposure(av_frontend* fe, int stream_idx, uint16_t out2[2])
+{
+    if (!fe || !out2 || stream_idx < 0 || stream_idx >= fe->d.S) { av_set_error("av_frontend_read_exposure: bad arguments"); return AV_E_INVALID; }
+    if (!fe->expo) { av_set_error("av_frontend_read_exposure: the engine was created without AV_FE_EXPOSURE"); return AV_E_INVALID; }
+    if (!fe->stepped) { av_set_error("av_frontend_read_exposure: no step has run"); return AV_E_INVALID; }
+    out2[0] = fe->ex_last[2 * (size_t)stream_idx]; out2[1] = fe->ex_last[2 * (size_t)stream_idx + 1];
     return AV_OK;
 }
 

@@ -5,6 +5,9 @@
 // A streaming pass (stream_pass.h): a lane's span is 16 pixels -- one uint4 of pixels and two uint4 of gains in, 16 table look-ups,
 // one uint4 out -- and the unit is one pixel.  The aligned body needs the gain bases to be whole 16-byte vectors too (ph_vector_ok).
 // The 512-byte response table of the workgroup's camera is staged into LDS once per workgroup (256 lanes, one entry each).
+// With per-frame exposure factors ("Exposure-time normalisation" in include/airvision.h; tests/exposure_ref.py) the table a workgroup
+// stages is its image's own: r'[p] = min(65280, (response[p] * k + 2048) >> 12), k uint16 Q12 of the image's group and camera -- the
+// whole per-pixel cost of the factor; span() and unit() do not know of it.  Those instances always use the LDS table.
 // In place (src == dst, same list) is correct: a lane reads its own pixels before it writes them and no lane reads another's.
 // Workgroup order: image-minor (id = block * n_img + image).  The gain map is one per camera for ALL images of a launch, so the
 // workgroups in flight at any time read the same few KB of it from L2 while the pixels stream; with the image-major order of
@@ -20,13 +23,14 @@ struct PhArgs {
     int npix, vec;                                 // (stream_pass.h; vec: the gain bases are whole vectors as well)
     const uint16_t* resp0; const uint16_t* resp1;  // [256] Q8 per camera
     const uint16_t* gain0; const uint16_t* gain1;  // [npix] Q12 per camera
+    const uint16_t* k0; const uint16_t* k1;        // [n_groups] Q12 per camera: exposure factors by group of the launch (instances with HAS_EXPOSURE)
 };
 
-__shared__ uint16_t ph_tab[256];               // the response table of the workgroup's camera (instances with one)
+__shared__ uint16_t ph_tab[256];               // the response table of the workgroup's camera (instances with one), or of its image (HAS_EXPOSURE)
 
 __device__ __forceinline__ uint32_t ph_out(uint32_t r, uint32_t g) { return min(255u, (r * g + (1u << 19)) >> 20); }      // r <= 65280: r * g + 2^19 < 2^32
 
-template <bool HAS_RESPONSE, bool HAS_GAIN>
+template <bool HAS_RESPONSE, bool HAS_GAIN, bool HAS_EXPOSURE>
 struct PhOp {
     using Args = PhArgs;
     static constexpr int SPAN = PH_LANE, UNIT = 1, UNROLL = 4;
@@ -34,14 +38,19 @@ struct PhOp {
     const uint16_t* gain;
     __device__ __forceinline__ PhOp(const PhArgs& a, const FrameAt& f, int, int tid) : gain(f.cam ? a.gain1 : a.gain0)
     {
-        if constexpr (HAS_RESPONSE) {
+        if constexpr (HAS_EXPOSURE) {
+            const uint32_t k = (f.cam ? a.k1 : a.k0)[f.g];                        // 65280 * 65535 + 2048 < 2^32
+            const uint32_t base = HAS_RESPONSE ? (uint32_t)(f.cam ? a.resp1 : a.resp0)[tid] : (uint32_t)tid << 8;
+            ph_tab[tid] = (uint16_t)min(65280u, (base * k + 2048u) >> 12);
+            __syncthreads();
+        } else if constexpr (HAS_RESPONSE) {
             ph_tab[tid] = (f.cam ? a.resp1 : a.resp0)[tid];
             __syncthreads();
         }
     }
     __device__ __forceinline__ uint32_t resp(uint32_t p) const
     {
-        if constexpr (HAS_RESPONSE) return ph_tab[p];
+        if constexpr (HAS_RESPONSE || HAS_EXPOSURE) return ph_tab[p];
         else return p << 8;
     }
     __device__ __forceinline__ void span(const uint8_t* src, uint8_t* dst, int p) const
@@ -74,19 +83,24 @@ bool ph_vector_ok(const FrameSet& src, const FrameSet& dst, int n_groups, const 
 }
 
 int ph_launch(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
-              const uint16_t* gain0, const uint16_t* gain1, hipStream_t st)
+              const uint16_t* gain0, const uint16_t* gain1, const uint16_t* k0, const uint16_t* k1, hipStream_t st)
 {
     PhArgs a;
     memset(&a, 0, sizeof(a));
     a.npix = w * h;
-    a.resp0 = resp0; a.resp1 = resp1; a.gain0 = gain0; a.gain1 = gain1;
+    a.resp0 = resp0; a.resp1 = resp1; a.gain0 = gain0; a.gain1 = gain1; a.k0 = k0; a.k1 = k1;
     a.vec = ph_vector_ok(src, dst, n_groups, gain0, gain1);
     const unsigned n_wg = av_frame_place(&a.place, src, dst, n_groups, (a.npix + 256 * PH_LANE - 1) / (256 * PH_LANE), 1, "av_photometric", w, h);
     if (!n_wg) return AV_E_INVALID;
     const dim3 grid(n_wg), block(256);
-    if (resp0 && gain0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, true>>), grid, block, 0, st, a);
-    else if (resp0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, false>>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((stream_pass_kernel<PhOp<false, true>>), grid, block, 0, st, a);
+    if (k0) {
+        if (resp0 && gain0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, true, true>>), grid, block, 0, st, a);
+        else if (resp0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, false, true>>), grid, block, 0, st, a);
+        else if (gain0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<false, true, true>>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((stream_pass_kernel<PhOp<false, false, true>>), grid, block, 0, st, a);
+    } else if (resp0 && gain0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, true, false>>), grid, block, 0, st, a);
+    else if (resp0) hipLaunchKernelGGL((stream_pass_kernel<PhOp<true, false, false>>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((stream_pass_kernel<PhOp<false, true, false>>), grid, block, 0, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -94,27 +108,29 @@ int ph_launch(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int
 }  // namespace
 
 int av_launch_photometric(const FrameSet& src, const FrameSet& dst, int n_groups, int w, int h, const uint16_t* resp0, const uint16_t* resp1,
-                          const uint16_t* gain0, const uint16_t* gain1, hipStream_t st)
+                          const uint16_t* gain0, const uint16_t* gain1, const uint16_t* k0, const uint16_t* k1, hipStream_t st)
 {
     if (n_groups <= 0) return AV_OK;
     if (src.map && src.map != dst.map) { av_set_error("av_photometric: a listed source is read through the destination's list"); return AV_E_INVALID; }
     const bool two = src.base[1] != nullptr;
+    if (two && (k0 != nullptr) != (k1 != nullptr)) { av_set_error("av_photometric: exposure factors for one camera of two"); return AV_E_INVALID; }
     if (!two) {
-        if (!resp0 && !gain0) { av_set_error("av_photometric: neither a response table nor a gain map"); return AV_E_INVALID; }
-        return ph_launch(src, dst, n_groups, w, h, resp0, nullptr, gain0, nullptr, st);
+        if (!resp0 && !gain0 && !k0) { av_set_error("av_photometric: neither a response table nor a gain map nor exposure factors"); return AV_E_INVALID; }
+        return ph_launch(src, dst, n_groups, w, h, resp0, nullptr, gain0, nullptr, k0, nullptr, st);
     }
     if ((resp0 != nullptr) == (resp1 != nullptr) && (gain0 != nullptr) == (gain1 != nullptr)) {      // both cameras have the same parts: one launch
-        if (!resp0 && !gain0) { av_set_error("av_photometric: neither a response table nor a gain map"); return AV_E_INVALID; }
-        return ph_launch(src, dst, n_groups, w, h, resp0, resp1, gain0, gain1, st);
+        if (!resp0 && !gain0 && !k0) { av_set_error("av_photometric: neither a response table nor a gain map nor exposure factors"); return AV_E_INVALID; }
+        return ph_launch(src, dst, n_groups, w, h, resp0, resp1, gain0, gain1, k0, k1, st);
     }
-    // the cameras differ in which parts they have: one launch per camera, each with its own kernel (a camera with neither part is
-    // the identity: copied if it is not in place)
+    // the cameras differ in which parts they have: one launch per camera, each with its own kernel and its own factors (a camera with
+    // no part at all is the identity: copied if it is not in place)
     const uint16_t* resp[2] = {resp0, resp1};
     const uint16_t* gain[2] = {gain0, gain1};
+    const uint16_t* k[2] = {k0, k1};
     for (int cam = 0; cam < 2; ++cam) {
         const FrameSet s1{{src.base[cam], nullptr}, src.stride, src.map}, d1{{dst.base[cam], nullptr}, dst.stride, dst.map};
-        if (resp[cam] || gain[cam]) {
-            const int rc = ph_launch(s1, d1, n_groups, w, h, resp[cam], nullptr, gain[cam], nullptr, st);
+        if (resp[cam] || gain[cam] || k[cam]) {
+            const int rc = ph_launch(s1, d1, n_groups, w, h, resp[cam], nullptr, gain[cam], nullptr, k[cam], nullptr, st);
             if (rc) return rc;
         } else if (src.base[cam] != dst.base[cam] || src.stride != dst.stride) {
             av_set_error("av_photometric: a camera without tables next to one with tables is only taken in place");
@@ -138,17 +154,21 @@ static int ph_check(const char* who, const void* in_dev, const void* out_dev, in
     return AV_OK;
 }
 
-AV_EXPORT int av_photometric(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
-                             const uint16_t* response_dev, const uint16_t* gain_dev, void* stream)
+// av_photometric and av_photometric_exposure: the same checks, `who` in the texts; k_dev null = no exposure factors
+static int ph_operator(const char* who, const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                       const uint16_t* response_dev, const uint16_t* gain_dev, bool takes_k, const uint16_t* k_dev, void* stream)
 {
-    int rc = ph_check("av_photometric", in_dev, out_dev, n, w, h, in_stride, out_stride, false);
+    int rc = ph_check(who, in_dev, out_dev, n, w, h, in_stride, out_stride, false);
     if (rc) return rc;
-    if (!response_dev && !gain_dev) { av_set_error("av_photometric: neither a response table nor a gain map (both null)"); return AV_E_INVALID; }
+    if (!response_dev && !gain_dev && !k_dev) {
+        av_set_error("%s: neither a response table nor a gain map%s", who, takes_k ? " nor exposure factors (all three null)" : " (both null)");
+        return AV_E_INVALID;
+    }
     if (n == 0) return AV_OK;
     const int64_t npix = (int64_t)w * h;
     const bool in_place = in_dev == out_dev && (n == 1 || in_stride == out_stride);      // (one image applies no stride)
     if (!in_place && av_spans_overlap(in_dev, in_stride, npix, out_dev, out_stride, npix, n)) {
-        av_set_error("av_photometric: out_dev overlaps the input without being the input itself (in place needs the same address and stride)");
+        av_set_error("%s: out_dev overlaps the input without being the input itself (in place needs the same address and stride)", who);
         return AV_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -157,10 +177,22 @@ AV_EXPORT int av_photometric(const uint8_t* in_dev, uint8_t* out_dev, int n, int
         AV_HIP(hipMemcpyAsync(tab, response_dev, sizeof(tab), hipMemcpyDeviceToHost, st));
         AV_HIP(hipStreamSynchronize(st));
         for (int i = 0; i < 256; ++i)
-            if (tab[i] > AV_PHOTOMETRIC_RESPONSE_MAX) { av_set_error("av_photometric: response[%d] = %d is above %d (255 in Q8)", i, (int)tab[i], AV_PHOTOMETRIC_RESPONSE_MAX); return AV_E_INVALID; }
+            if (tab[i] > AV_PHOTOMETRIC_RESPONSE_MAX) { av_set_error("%s: response[%d] = %d is above %d (255 in Q8)", who, i, (int)tab[i], AV_PHOTOMETRIC_RESPONSE_MAX); return AV_E_INVALID; }
     }
     return av_launch_photometric(av_frames(in_dev, nullptr, in_stride), FrameSet{{out_dev, nullptr}, out_stride, nullptr}, n, w, h,
-                                 response_dev, nullptr, gain_dev, nullptr, st);
+                                 response_dev, nullptr, gain_dev, nullptr, k_dev, nullptr, st);
+}
+
+AV_EXPORT int av_photometric(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                             const uint16_t* response_dev, const uint16_t* gain_dev, void* stream)
+{
+    return ph_operator("av_photometric", in_dev, out_dev, n, w, h, in_stride, out_stride, response_dev, gain_dev, false, nullptr, stream);
+}
+
+AV_EXPORT int av_photometric_exposure(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,
+                                      const uint16_t* response_dev, const uint16_t* gain_dev, const uint16_t* k_dev, void* stream)
+{
+    return ph_operator("av_photometric_exposure", in_dev, out_dev, n, w, h, in_stride, out_stride, response_dev, gain_dev, true, k_dev, stream);
 }
 
 AV_EXPORT int av_photometric_vector_path(const uint8_t* in_dev, uint8_t* out_dev, int n, int w, int h, int64_t in_stride, int64_t out_stride,

@@ -29,6 +29,8 @@ class ImageProcessingPipeline(object):
         # config.image_downscale 2 / 4: the callbacks still take full-size frames; the same hook shows the binned frame
         # config.cam*_response / cam*_vignette: the engine reads them from the config object; the same hook shows the corrected frame
         # config.gray16_scale 'window' / 'auto' (image_format 'gray16'): likewise; gray16_range() returns the (lo, hi) of the last frame
+        # config.exposure_reference: both image messages then carry an attribute `exposure`, the frame's exposure time in the unit of the
+        # reference (a ValueError names the message that has none); without the setting the attribute is never read
         self.use_clahe = bool(getattr(config, 'use_clahe', False))
         self.downscale = self._engine.downscale
         self.viewer = None
@@ -46,16 +48,22 @@ class ImageProcessingPipeline(object):
     def stereo_callback(self, stereo_msg):
         """pipeline.py:46-150: returns feature_msg(timestamp, [FeatureMeasurement])."""
         cam0_msg, cam1_msg = stereo_msg.cam0_msg, stereo_msg.cam1_msg
+        kw = {}
+        if self._engine.exposure:
+            for name, msg in (('cam0_msg', cam0_msg), ('cam1_msg', cam1_msg)):
+                if getattr(msg, 'exposure', None) is None:
+                    raise ValueError('config.exposure_reference is set and %s carries no attribute `exposure`' % name)
+            kw['exposure'] = ([float(cam0_msg.exposure)], [float(cam1_msg.exposure)])
         if self._engine.pixel_format != 0:
             # config.image_format (no counterpart in the reference): colour, 16-bit, mosaic or packed 10 / 12-bit frames (uint8 [h, w * d / 8])
             # go to the engine as they are and are converted to 8-bit grey on the GPU; step_host refuses a wrong dtype or shape with a ValueError naming both
-            self._engine.step_host(cam0_msg.image, cam1_msg.image, [cam0_msg.timestamp])
+            self._engine.step_host(cam0_msg.image, cam1_msg.image, [cam0_msg.timestamp], **kw)
         else:
             img0 = np.ascontiguousarray(cam0_msg.image, dtype=np.uint8)
             img1 = np.ascontiguousarray(cam1_msg.image, dtype=np.uint8)
             if img0.ndim != 2 or img0.shape != (self._engine.input_height, self._engine.input_width) or img1.shape != img0.shape:
                 raise ValueError('expected two uint8[%d,%d] images' % (self._engine.input_height, self._engine.input_width))
-            self._engine.step_host(img0, img1, [cam0_msg.timestamp])
+            self._engine.step_host(img0, img1, [cam0_msg.timestamp], **kw)
         (ids, uv), = self._engine.read_features()
         feats = []
         for k in range(len(ids)):

@@ -235,6 +235,7 @@ class FrameStager(object):
         one = frame_array(png_pixel_format(pixel_format), self.S, height, width)
         self.buf = [np.zeros((2,) + one.shape, one.dtype) for _ in range(3)]      # [slot][camera][stream]
         self.max_frames, self.threads, self.k = max_frames, threads, 0
+        self._files, self.last_files = {}, None          # last_files: [(cam0 path, cam1 path) or None per stream] of the step `next` last returned
         self.pool = ThreadPoolExecutor(1)
         self.fut = self.pool.submit(self._load, 0)
 
@@ -245,6 +246,7 @@ class FrameStager(object):
         if all(e is None for e in ent):
             return None
         ts = np.array([-1.0 if e is None else e[0] for e in ent])
+        self._files[k] = [None if e is None else (e[1], e[2]) for e in ent]
         buf = self.buf[k % 3]
         both = [None if e is None else e[1] for e in ent] + [None if e is None else e[2] for e in ent]
         decode_batch(both, buf.reshape((2 * self.S,) + buf.shape[2:]), self.threads)     # cam0 and cam1 of all streams in one threaded call
@@ -255,6 +257,7 @@ class FrameStager(object):
 
     def next(self):
         res = self.fut.result()
+        self.last_files = self._files.pop(self.k, None)
         self.k += 1
         self.fut = self.pool.submit(self._load, self.k) if res is not None else None
         return res
@@ -369,6 +372,67 @@ class SharedFrameStager(object):
         self.pool.shutdown(wait=True)
 
 
+class ExposureTimes(object):
+    """The exposure time of every frame of sequences in the EuRoC layout that hold `mav0/cam0/times.txt` and `mav0/cam1/times.txt` next
+    to each camera's `data` directory.  The layout is that of the `times.txt` of the TUM mono-VO dataset -- one line per frame,
+        <file stem> <timestamp in s> <exposure in ms>
+    separated by white space; empty lines and lines that start with `#` are skipped -- and this text is the contract: the files of
+    that dataset were not at hand to check it against.  A line is matched to its PNG by the first column, which is the file's name
+    without `.png` (compared as text).  `of(png path)` returns the exposure of that frame in ms; the file of a camera is read once, when
+    the first of its frames is asked for.  ValueError naming the times.txt: a file that is missing, a line that does not hold three
+    columns with a finite exposure > 0, a stem listed twice, a frame without a line."""
+
+    def __init__(self):
+        self._cams = {}
+
+    @staticmethod
+    def times_path(png_path):
+        return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(png_path))), 'times.txt')
+
+    @staticmethod
+    def read(path):
+        if not os.path.isfile(path):
+            raise ValueError('exposure times: %s is missing (one line per frame: <file stem> <timestamp in s> <exposure in ms>)' % path)
+        out = {}
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                col = line.split()
+                if not col or col[0].startswith('#'):
+                    continue
+                try:
+                    if len(col) != 3:
+                        raise ValueError
+                    float(col[1])
+                    e = float(col[2])
+                    if not (np.isfinite(e) and e > 0):
+                        raise ValueError
+                except ValueError:
+                    raise ValueError('exposure times: %s line %d is not <file stem> <timestamp in s> <exposure in ms> with an exposure > 0: %r' % (path, no, line.strip()))
+                if col[0] in out:
+                    raise ValueError('exposure times: %s lists frame %s twice' % (path, col[0]))
+                out[col[0]] = e
+        return out
+
+    def of(self, png_path):
+        path = self.times_path(png_path)
+        if path not in self._cams:
+            self._cams[path] = self.read(path)
+        stem = os.path.basename(png_path)
+        stem = stem[:-4] if stem.endswith('.png') else stem
+        if stem not in self._cams[path]:
+            raise ValueError('exposure times: %s has no line for frame %s' % (path, stem))
+        return self._cams[path][stem]
+
+    def check(self, datasets, max_frames=None):
+        """Every frame the datasets will hand out has its line, in both cameras' files: found before the first step."""
+        for d in datasets:
+            for k, (_t, p0, p1) in enumerate(d.stereo_files):
+                if max_frames is not None and k >= max_frames:
+                    break
+                self.of(p0), self.of(p1)
+        return self
+
+
 def replay(dataset, imu_sinks, on_stereo, max_frames=None):
     """Deterministic replay: for each stereo frame at time t deliver every IMU message with
     timestamp <= t to each sink (order of vio.py:43-44), then call on_stereo(msg)."""
@@ -425,7 +489,7 @@ def encode_frame(image, pixel_format='gray8', gains=BAYER_GAINS, shift=8):
 
 
 def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None, write_csv=True, compress_level=6, pixel_format='gray8',
-                       bayer_gains=BAYER_GAINS, gray16_shift=8, vignette=None):
+                       bayer_gains=BAYER_GAINS, gray16_shift=8, vignette=None, exposure=None):
     """Write a seeded synthetic stream (uav_airvision_amd.synth.SyntheticStream) as an EuRoC-layout directory
     `root/mav0/{cam0,cam1}/data/<ns>.png`, `imu0/data.csv`, `state_groundtruth_estimate0/data.csv`, so that the same
     reader / replay / sweep code that runs on the real dataset (which is not redistributable and not present on the build
@@ -436,7 +500,10 @@ def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None
     `pixel_format` 'gray16' / 'rgb8' / 'rgba8' writes the same frames as 16-bit grey / RGB / RGBA PNGs (encode_frame); a Bayer name
     writes the raw mosaic of the frames coloured by `bayer_gains` as 8- or 16-bit grey PNGs (16-bit samples << `gray16_shift`).
     `vignette` = (V0, V1) or (V0, V1, response_forward): every frame of cam0 / cam1 is degraded with frontend.apply_vignette before it is
-    encoded (what a vignetting lens and a non-linear sensor would have recorded); None writes the frames as they are."""
+    encoded (what a vignetting lens and a non-linear sensor would have recorded); None writes the frames as they are.
+    `exposure` = (t0, t1, t_ref): frame k of cam0 / cam1 is recorded at an exposure of t0[k] / t1[k] ms by a camera whose frames as
+    rendered are at t_ref -- frontend.apply_exposure with the ratio t / t_ref, behind the vignette and the response of `vignette` if
+    given -- and `mav0/cam0/times.txt` and `mav0/cam1/times.txt` list the frames this call wrote (`ExposureTimes` has the layout)."""
     from PIL import Image
     from . import _native as N
     if pixel_format in N.PACKED_FORMATS:
@@ -453,11 +520,28 @@ def write_euroc_layout(root, stream, groundtruth_rate_hz=200.0, frame_range=None
     for cam in ('cam0', 'cam1'):
         os.makedirs(os.path.join(root, 'mav0', cam, 'data'), exist_ok=True)
     a, b = (0, stream.n_frames) if frame_range is None else frame_range
+    times = ([], [])
     for k in range(a, b):
         m = stream.frame(k)
-        name = '%d.png' % int(round(m.timestamp * 1e9))
-        Image.fromarray(enc(deg0(m.cam0_image))).save(os.path.join(root, 'mav0', 'cam0', 'data', name), compress_level=compress_level)
-        Image.fromarray(enc(deg1(m.cam1_image))).save(os.path.join(root, 'mav0', 'cam1', 'data', name), compress_level=compress_level)
+        stem = '%d' % int(round(m.timestamp * 1e9))
+        name = stem + '.png'
+        im0, im1 = m.cam0_image, m.cam1_image
+        if exposure is not None:
+            from .frontend import apply_exposure
+            t0, t1, t_ref = exposure
+            v = (None, None, None) if vignette is None else (vignette[0], vignette[1], vignette[2] if len(vignette) > 2 else None)
+            im0 = apply_exposure(im0, float(t0[k]) / float(t_ref), v[0], v[2])
+            im1 = apply_exposure(im1, float(t1[k]) / float(t_ref), v[1], v[2])
+            times[0].append('%s %.9f %r\n' % (stem, m.timestamp, float(t0[k])))
+            times[1].append('%s %.9f %r\n' % (stem, m.timestamp, float(t1[k])))
+        else:
+            im0, im1 = deg0(im0), deg1(im1)
+        Image.fromarray(enc(im0)).save(os.path.join(root, 'mav0', 'cam0', 'data', name), compress_level=compress_level)
+        Image.fromarray(enc(im1)).save(os.path.join(root, 'mav0', 'cam1', 'data', name), compress_level=compress_level)
+    if exposure is not None:
+        for cam in (0, 1):
+            with open(os.path.join(root, 'mav0', 'cam%d' % cam, 'times.txt'), 'w') as f:
+                f.writelines(times[cam])
     if not write_csv:
         return root
     os.makedirs(os.path.join(root, 'mav0', 'imu0'), exist_ok=True)

@@ -114,7 +114,22 @@ def pack_frontend_config(config, max_corners=None):
     # 2 x 2 / 4 x 4 binning ahead of CLAHE and the pyramids; getattr: a config object without the attribute is a full-size engine
     c.image_downscale = f
     c.reserved1 = 0
+    # exposure-time normalisation (AV_FE_EXPOSURE); getattr: a config object without the attribute has none
+    if exposure_reference(config) is not None:
+        c.flags |= N.AV_FE_EXPOSURE
     return c
+
+
+def exposure_reference(config):
+    """config.exposure_reference as a float, or None (None, or a config object without the attribute): the reference exposure time
+    t_ref of "Exposure-time normalisation" in include/airvision.h.  ValueError unless it is finite and > 0."""
+    ref = getattr(config, 'exposure_reference', None)
+    if ref is None:
+        return None
+    ref = float(ref)
+    if not (np.isfinite(ref) and ref > 0):
+        raise ValueError('exposure_reference: a finite time > 0 is wanted, got %r' % (ref,))
+    return ref
 
 
 def gray16_scale_settings(config):
@@ -383,6 +398,38 @@ def apply_vignette(img_u8, vignette, response_forward=None):
     return np.clip(np.floor(x + 0.5), 0, 255).astype(np.uint8)
 
 
+def quantise_exposure(t, t_ref):
+    """Exposure times t (a number or an array, in the unit of t_ref) as the engine's factors ("Exposure-time normalisation" in
+    include/airvision.h): uint16 in Q12, k = min(65535, max(1, floor(4096 * t_ref / t + 0.5))) in float64, of t's shape.  t <= 0,
+    t_ref <= 0 or a value that is not finite is a ValueError: nothing is cast silently."""
+    a = np.asarray(t, dtype=np.float64)
+    ref = float(t_ref)
+    if not (np.isfinite(ref) and ref > 0):
+        raise ValueError('quantise_exposure: the reference exposure is finite and > 0, got %r' % (ref,))
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        bad = a.reshape(-1)[~(np.isfinite(a.reshape(-1)) & (a.reshape(-1) > 0))]
+        raise ValueError('quantise_exposure: every exposure time is finite and > 0, got %r' % (float(bad[0]),))
+    with np.errstate(over='ignore'):
+        k = np.floor(4096.0 * ref / a + 0.5)
+    return np.minimum(65535.0, np.maximum(1.0, k)).astype(np.uint16)
+
+
+def apply_exposure(img_u8, ratio, vignette=None, response_forward=None):
+    """The forward model of a frame taken at `ratio` = t / t_ref times the reference exposure, for synthesising degraded frames:
+    round(G(ratio * V * img)) clipped to 0 .. 255 -- `apply_vignette` with the irradiance scaled first.  vignette None: V = 1."""
+    x = np.asarray(img_u8).astype(np.float64) * float(ratio)
+    v = 1.0 if vignette is None else np.asarray(vignette, dtype=np.float64)
+    x = x * v
+    if callable(response_forward):
+        x = np.asarray(response_forward(x), dtype=np.float64)
+    elif response_forward is not None:
+        tab = np.asarray(response_forward, dtype=np.float64).reshape(-1)
+        if tab.shape != (256,):
+            raise ValueError('apply_exposure: response_forward is a callable or 256 values, got %d' % tab.size)
+        x = np.interp(x, np.arange(256.0), tab)
+    return np.clip(np.floor(x + 0.5), 0, 255).astype(np.uint8)
+
+
 def check_photometric(cam, response, gain, height, width):
     """The integer tables of camera `cam` as C-contiguous uint16 arrays of the shapes the engine reads ([256], [height, width]), or None
     for None.  Nothing is cast: a wrong dtype or shape is a ValueError naming the camera; so is a response entry above 65280."""
@@ -410,6 +457,8 @@ RANSAC_COUNT_NAMES = ('after_ransac', 'cam0_set', 'cam1_set', 'path')
 
 
 class FrontendEngine(object):
+    exposure, _exposure_ref, _pre = False, None, None      # (off unless the constructor finds config.exposure_reference)
+
     def __init__(self, config, n_streams=1, device=0, max_corners=None, inputs_persist=False):
         """The image size is config.cam0_resolution: any width x height of up to AV_MAX_IMAGE_PIXELS = 2^24 pixels.  max_corners:
         capacity for the FAST corners of one image (None: 8192 at 752 x 480, scaled by the pixel count above that).
@@ -447,7 +496,15 @@ class FrontendEngine(object):
         samples are scaled through config.gray16_window = (lo, hi), or through a range the GPU takes from every stereo pair's own
         histogram (config.gray16_auto_clip ppm at each end, config.gray16_auto_min_span), instead of config.gray16_shift -- `gray16_range`
         is the arithmetic in NumPy, `read_range` returns the ranges of the last step.  Any other image_format with such a scale is a
-        ValueError naming both settings."""
+        ValueError naming both settings.
+
+        config.exposure_reference = t_ref (a config object without the attribute, or None: off): exposure-time normalisation
+        ("Exposure-time normalisation" in include/airvision.h).  The engine is created with AV_FE_EXPOSURE, `exposure` is True, and
+        `step`, `prestage`, `step_host` and `frames_upload` then REQUIRE the exposure times of the frames they are handed: the keyword
+        exposure=(e0, e1), float arrays [n_streams] ([n] for an upload) in the unit of t_ref, one per camera, quantised by
+        `quantise_exposure`; or exposure_q=(k0, k1), ready uint16 factors.  A call that needs them and gets neither is a ValueError (a
+        `step` with the tensors of the last `prestage` needs none); a keyword on an engine without the switch is a ValueError too.
+        `read_exposure` returns the factors a stream's last frame was corrected with."""
         self.config = config
         self.n_streams = int(n_streams)
         self.device = int(device)
@@ -459,6 +516,8 @@ class FrontendEngine(object):
         photo = [photometric_tables(getattr(config, 'cam%d_response' % cam, None), getattr(config, 'cam%d_vignette' % cam, None)) for cam in (0, 1)]
         photo = [check_photometric(cam, r, g, self._cfg.height, self._cfg.width) for cam, (r, g) in enumerate(photo)]
         self.photometric = any(t is not None for pair in photo for t in pair)
+        self._exposure_ref = exposure_reference(config)
+        self.exposure = self._exposure_ref is not None
         g16 = gray16_scale_settings(config)
         self.gray16_scale = {v: k for k, v in N.GRAY16_SCALES.items()}[g16[0]]
         if self.photometric:
@@ -519,9 +578,46 @@ class FrontendEngine(object):
         N.check(N.lib().av_frontend_push_imu_batch(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                    g.ctypes.data_as(C.c_void_p), len(si)))
 
-    def step(self, img0, img1, timestamps):
-        """img0/img1: uint8 cuda tensors [S,h,w] (contiguous); timestamps: S floats.  Enqueues only."""
+    def _next_exposure(self, who, n, exposure, exposure_q, needed=True):
+        """Hands the factors of the next call's n frames to the engine (av_frontend_next_exposure).  ValueError: a keyword on an engine
+        without config.exposure_reference, both keywords, none where the call needs them, a shape other than [n], factors that are not
+        uint16 or hold a zero."""
+        if not self.exposure:
+            if exposure is not None or exposure_q is not None:
+                raise ValueError('%s: exposure given to an engine without config.exposure_reference' % who)
+            return
+        if exposure is not None and exposure_q is not None:
+            raise ValueError('%s: exposure= and exposure_q= are alternatives' % who)
+        if exposure is None and exposure_q is None:
+            if needed:
+                raise ValueError('%s: the engine has config.exposure_reference = %r and needs exposure=(e0, e1) (or exposure_q=(k0, k1)) with every frame' % (who, self._exposure_ref))
+            return
+        if exposure is not None:
+            k = [quantise_exposure(np.atleast_1d(np.asarray(e, dtype=np.float64)), self._exposure_ref) for e in exposure]
+        else:
+            k = [np.atleast_1d(np.asarray(q)) for q in exposure_q]
+            for q in k:
+                if q.dtype != np.uint16:
+                    raise ValueError('%s: exposure_q holds uint16 factors (quantise_exposure makes them), got %s' % (who, q.dtype))
+        if len(k) != 2 or any(q.shape != (n,) for q in k):
+            raise ValueError('%s: one array of %d exposures per camera is wanted, got shapes %s' % (who, n, [tuple(q.shape) for q in k]))
+        if any(int(q.min()) == 0 for q in k):
+            raise ValueError('%s: an exposure factor of 0 (1 .. 65535 in Q12)' % who)
+        k0, k1 = np.ascontiguousarray(k[0]), np.ascontiguousarray(k[1])
+        N.check(N.lib().av_frontend_next_exposure(self._h, k0.ctypes.data_as(C.c_void_p), k1.ctypes.data_as(C.c_void_p), n))
+
+    def read_exposure(self, stream=0):
+        """(k0, k1): the Q12 factors the frame of `stream`'s last step was corrected with (av_frontend_read_exposure); through the frame
+        store those of the entry it read.  Refused (AirvisionError, AV_E_INVALID) without config.exposure_reference and before a step."""
+        out = (C.c_uint16 * 2)()
+        N.check(N.lib().av_frontend_read_exposure(self._h, int(stream), out))
+        return int(out[0]), int(out[1])
+
+    def step(self, img0, img1, timestamps, exposure=None, exposure_q=None):
+        """img0/img1: uint8 cuda tensors [S,h,w] (contiguous); timestamps: S floats.  Enqueues only.  exposure / exposure_q: class
+        docstring."""
         S = self.n_streams
+        pre = self._pre is not None and self._pre[0].data_ptr() == img0.data_ptr() and self._pre[1].data_ptr() == img1.data_ptr()      # built by `prestage`: the step skips the stage
         if self.pixel_format != N.AV_PIX_GRAY8:
             check_device_frames('step: img0', img0, self.pixel_format, S, self.input_height, self.input_width)
             check_device_frames('step: img1', img1, self.pixel_format, S, self.input_height, self.input_width)
@@ -530,11 +626,13 @@ class FrontendEngine(object):
             assert tuple(img0.shape) == (S, self.input_height, self.input_width) == tuple(img1.shape), (img0.shape, img1.shape)
             assert img0.is_contiguous() and img1.is_contiguous()
         ts = (C.c_double * S)(*[float(t) for t in timestamps])
+        self._next_exposure('step', S, exposure, exposure_q, needed=not pre)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_step(self._h, N.dptr(img0), N.dptr(img1), self._frame_bytes, ts, self._stream()))
         self._keep = (self._keep[1] if self._keep else None, (img0, img1))       # this frame's and the previous frame's tensors stay alive
+        self._pre = None
 
-    def prestage(self, img0, img1):
+    def prestage(self, img0, img1, exposure=None, exposure_q=None):
         """Build the pyramids of the NEXT step's images now (av_frontend_prestage): `step` with the same tensors then starts with its
         tracking launch.  Same results; the engine must have been created with inputs_persist=True."""
         S = self.n_streams
@@ -544,11 +642,12 @@ class FrontendEngine(object):
         else:
             assert img0.is_cuda and img1.is_cuda and img0.dtype == torch.uint8 and img1.dtype == torch.uint8
             assert tuple(img0.shape) == (S, self.input_height, self.input_width) == tuple(img1.shape) and img0.is_contiguous() and img1.is_contiguous()
+        self._next_exposure('prestage', S, exposure, exposure_q)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_prestage(self._h, N.dptr(img0), N.dptr(img1), self._frame_bytes, self._stream()))
         self._pre = (img0, img1)                                                # alive until the step that uses them
 
-    def step_host(self, img0, img1, timestamps):
+    def step_host(self, img0, img1, timestamps, exposure=None, exposure_q=None):
         """numpy uint8 [S,h,w] (or [h,w] when S == 1); frames of config.image_format otherwise (class docstring)."""
         S = self.n_streams
         if self.pixel_format != N.AV_PIX_GRAY8:
@@ -558,6 +657,7 @@ class FrontendEngine(object):
             a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(S, self.input_height, self.input_width)
             a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(S, self.input_height, self.input_width)
         ts = (C.c_double * S)(*[float(t) for t in np.atleast_1d(timestamps)])
+        self._next_exposure('step_host', S, exposure, exposure_q)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_step_host(self._h, a0.ctypes.data_as(C.c_void_p), a1.ctypes.data_as(C.c_void_p),
                                                   self._frame_bytes, ts, self._stream()))
@@ -611,7 +711,7 @@ class FrontendEngine(object):
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_frames_reserve(self._h, int(n_slots)))
 
-    def frames_upload(self, slots, img0, img1):
+    def frames_upload(self, slots, img0, img1, exposure=None, exposure_q=None):
         """Put host frames into the store: slots int32[n], img0 / img1 uint8[n,h,w] (C-contiguous).  Copy, pyramids and FAST of
         every frame happen once, here, on the engine's copy stream; the arrays are free again on return."""
         sl = np.ascontiguousarray(slots, dtype=np.int32)
@@ -624,6 +724,7 @@ class FrontendEngine(object):
         else:
             a0 = np.ascontiguousarray(img0, dtype=np.uint8).reshape(n, self.input_height, self.input_width)
             a1 = np.ascontiguousarray(img1, dtype=np.uint8).reshape(n, self.input_height, self.input_width)
+        self._next_exposure('frames_upload', n, exposure, exposure_q)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_frontend_frames_upload(self._h, sl.ctypes.data_as(C.c_void_p), n, a0.ctypes.data_as(C.c_void_p),
                                                       a1.ctypes.data_as(C.c_void_p), self._frame_bytes, self._stream()))

@@ -375,19 +375,22 @@ def downscale(img, factor, out=None, device=0):
     return out
 
 
-def photometric(images, response=None, gain=None, out=None, device=0):
+def photometric(images, response=None, gain=None, out=None, device=0, exposure=None):
     """Photometric calibration of 8-bit grey frames (av_photometric; the arithmetic is written out in include/airvision.h):
     out = min(255, (response[p] * gain[x] + 2^19) >> 20).  images: uint8 [n, h, w] or [h, w], a cuda tensor or anything torch.as_tensor
     takes.  A cuda tensor is read where it lies: each image must be contiguous, the images may be any distance apart, at any address.
     response: uint16[256] in Q8 (entries <= 65280) or None; gain: uint16 [h, w] in Q12, one map for all images, or None
     (frontend.photometric_tables makes both); a cuda tensor (torch.uint16, or torch.int16 holding the same bits) is used where it lies.
     At least one of the two.  Returns a uint8 cuda tensor of images' shape -- `out` itself if given (uint8 cuda, that shape, each image
-    contiguous); out may be the input itself (in place), any other overlap is refused."""
+    contiguous); out may be the input itself (in place), any other overlap is refused.
+    exposure: the exposure factors of the images ("Exposure-time normalisation" in include/airvision.h; av_photometric_exposure), uint16
+    [n] in Q12 as frontend.quantise_exposure makes them -- a host array or a cuda tensor -- image i then goes through the table
+    min(65280, (response[p] * k[i] + 2048) >> 12).  With them neither a response nor a gain is required."""
     t = torch.as_tensor(images)
     if t.dtype != torch.uint8 or t.dim() not in (2, 3):
         raise ValueError('photometric: images are torch.uint8 [n, h, w] or [h, w], got %s %s' % (t.dtype, tuple(t.shape)))
-    if response is None and gain is None:
-        raise ValueError('photometric: neither a response table nor a gain map')
+    if response is None and gain is None and exposure is None:
+        raise ValueError('photometric: neither a response table nor a gain map nor exposure factors')
     t = t.to(_dev(device))
     batched = t.dim() == 3
     tb = t if batched else t.unsqueeze(0)
@@ -407,6 +410,7 @@ def photometric(images, response=None, gain=None, out=None, device=0):
         return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(_dev(device))
     r = None if response is None else table(response, 'response', (256,))
     g = None if gain is None else table(gain, 'gain', (h, w))
+    k = None if exposure is None else table(exposure, 'exposure', (n,))
     oshape = tuple(t.shape)
     if out is None:
         out = torch.empty(oshape, dtype=torch.uint8, device=_dev(device))
@@ -418,8 +422,12 @@ def photometric(images, response=None, gain=None, out=None, device=0):
     in_stride = tb.stride(0) if n > 1 else h * w
     out_stride = ob.stride(0) if n > 1 else h * w
     with torch.cuda.device(device):
-        N.check(N.lib().av_photometric(N.dptr(tb), N.dptr(ob), n, w, h, in_stride, out_stride, None if r is None else N.dptr(r),
-                                       None if g is None else N.dptr(g), N.current_stream()))
+        if k is None:
+            N.check(N.lib().av_photometric(N.dptr(tb), N.dptr(ob), n, w, h, in_stride, out_stride, None if r is None else N.dptr(r),
+                                           None if g is None else N.dptr(g), N.current_stream()))
+        else:
+            N.check(N.lib().av_photometric_exposure(N.dptr(tb), N.dptr(ob), n, w, h, in_stride, out_stride, None if r is None else N.dptr(r),
+                                                    None if g is None else N.dptr(g), N.dptr(k), N.current_stream()))
     return out
 
 

@@ -66,7 +66,7 @@ class BatchedRunner(object):
         self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features)
         self.frames_done = np.zeros(self.S, np.int64)
         self._fstream = None
-        self.plan, self.steps_done = None, 0
+        self.plan, self.steps_done, self.times = None, 0, None
 
     def close(self):
         self.eng.close(); self.flt.close()
@@ -79,6 +79,14 @@ class BatchedRunner(object):
         staged = all(hasattr(d, 'stereo_files') for d in datasets)
         self.plan = None
         stager = None
+        # config.exposure_reference: the exposure of every frame comes from the sequences' times.txt (euroc.ExposureTimes), read -- and
+        # checked for every frame of the run -- before the first step; without the setting the files are never opened
+        self.times = None
+        if self.eng.exposure:
+            from .euroc import ExposureTimes
+            if not staged:
+                raise ValueError('config.exposure_reference needs datasets that list their files (mav0/cam*/times.txt are matched to them by name)')
+            self.times = ExposureTimes().check(datasets, max_frames)
         if staged and share_frames:
             self.plan = SharedFramePlan(datasets, max_frames=max_frames)
             self.eng.frames_reserve(self.plan.n_slots)
@@ -118,15 +126,21 @@ class BatchedRunner(object):
             for s in np.nonzero(out[:, 0] > 0.5)[0]:
                 traj[s].append(out[s, 1:9].copy())
 
+        times, t_ref = self.times, getattr(eng, '_exposure_ref', None)
+
+        def upload(k):                                    # the new frames of step k, each with the exposures of its own two files
+            kw = {} if times is None else dict(exposure=([times.of(e[1]) for e in plan.new[k]], [times.of(e[2]) for e in plan.new[k]]))
+            eng.frames_upload(*stager.get(k), **kw)
+
         if plan is not None and plan.n_steps:
-            eng.frames_upload(*stager.get(0))
+            upload(0)
         step = 0
         while True:
             if plan is not None:
                 if step >= plan.n_steps:
                     break
                 if step + 1 < plan.n_steps:               # the NEXT step's new frames go up before this step is enqueued: copy,
-                    eng.frames_upload(*stager.get(step + 1))      # pyramids and FAST of step k+1 run beside the kernels of step k
+                    upload(step + 1)                      # pyramids and FAST of step k+1 run beside the kernels of step k
                 frame_ts = plan.ts[step]
             elif staged:
                 nxt = stager.next()
@@ -175,6 +189,9 @@ class BatchedRunner(object):
                 flt.push_imu(idx, tt, gy, ac)
             if plan is not None:
                 eng.step_frames(plan.slots[step], ts_e)
+            elif times is not None:                       # (a finished stream idles on blank images at the reference exposure)
+                fl = stager.last_files
+                eng.step_host(img0, img1, ts_e, exposure=([t_ref if f is None else times.of(f[0]) for f in fl], [t_ref if f is None else times.of(f[1]) for f in fl]))
             else:
                 eng.step_host(img0, img1, ts_e)
             if on_step is not None:
@@ -300,6 +317,10 @@ def make_parser():
                     help='vignette map of cam0 for every stream: a 16-bit grey PNG of the frame size, normalised by its maximum; every pixel is divided by it on the GPU '
                          '(config.cam0_vignette; default: none)')
     ap.add_argument('--vignette1', metavar='PNG', default=None, help='the same for cam1 (config.cam1_vignette)')
+    ap.add_argument('--exposure-reference', type=float, default=None, metavar='MS',
+                    help='exposure-time normalisation: every frame is scaled by MS / its own exposure on the GPU, inside the photometric stage '
+                         '(config.exposure_reference; default: off).  The exposures are read from mav0/cam0/times.txt and mav0/cam1/times.txt of every '
+                         'sequence: one line per frame, <file stem> <timestamp in s> <exposure in ms>')
     ap.add_argument('--gray16-shift', type=int, default=None, metavar='N',
                     help='16-bit frames, grey or Bayer: sample = min(255, v >> N), 0 .. 8 (config.gray16_shift, default 8)')
     ap.add_argument('--gray16-scale', choices=['shift', 'window', 'auto'], default=None,
@@ -332,6 +353,8 @@ def apply_args(cfg, args):
         v = getattr(args, arg, None)                            # (a setting already on the config object stays unless the switch is given)
         if v is not None:
             setattr(cfg, attr, tuple(v) if isinstance(v, list) else v)
+    if getattr(args, 'exposure_reference', None) is not None:      # (a reference already on the config object stays unless the switch is given)
+        cfg.exposure_reference = float(args.exposure_reference)
     if getattr(args, 'downscale', None) is not None:          # (a factor already set on the config object stays unless the switch is given)
         cfg.image_downscale = int(args.downscale)
     for cam in (0, 1):                                         # (a mask already set on the config object stays unless the switch is given)
@@ -417,6 +440,8 @@ def main(argv=None):
         photo = {k: (os.fspath(v) if isinstance(v, (str, os.PathLike)) else 'array') for k, v in photo.items() if v is not None}
         if photo:
             rep['photometric'] = photo
+        if getattr(cfg, 'exposure_reference', None) is not None:
+            rep['exposure_reference'] = float(cfg.exposure_reference)
         print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
