@@ -11,8 +11,7 @@
 //
 // MI355X mapping: one 256-thread workgroup per 64x48 tile; the 72x56 pixel tile and the 72x50 score tile live in
 // LDS (every image byte is read from HBM once + halo, scores never go to HBM).  Three phases per tile, all of them
-// working on DWORDS of four horizontally adjacent pixels (the kernel is LDS-latency bound, not VALU bound: byte-wide
-// LDS reads were 4x the instructions):
+// working on DWORDS of four horizontally adjacent pixels (byte-wide LDS reads were 4x the instructions):
 //  (1) the 4-pixel necessary test: a lane reads the five dwords that hold the compass pixels of its four positions,
 //      survivors are compacted into a wave-private LDS list with ballots (no atomics, no barrier before phase 2);
 //  (2) the ~200-op corner score for the compacted candidates only (dense lanes instead of a divergent early-out);
@@ -24,7 +23,14 @@
 // detector (av_fast_detect) appends them to one flat list per image with one returning atomic per tile.
 // A survivor is one packed word, score << B | (2^B - 1 - raster) (av_common.h): B is an argument of the launch -- 19 for av_fast_detect and
 // for engines of up to 2^19 pixels, whose words are what they always were, 24 for av_fast_detect_wide and larger engines.
-// Bound: HBM read of the image (w*h bytes) -- the score arithmetic is ~200 VALU ops per candidate.
+// Bound: VALU instruction issue, not the image read (profiles/fast_diet/README.md).  The image is 0.74 GB per step of 2,048 stereo
+// streams, 0.15 ms at the rate of a copy; the kernel takes 1.22 ms alone (8 x that), issues 778 VALU instructions per wavefront
+// (phase 1 about 75 per 64 quads, phase 2 84 per 64 candidates of which 56 are the packed minima / maxima, phase 3 about 60 per
+// 64 quads) and its wavefronts wait on instruction issue for 46 % of their cycles.
+// So the bookkeeping around the arithmetic is kept out of the per-pixel path: a thread owns one dword column of the tile (one
+// division in the kernel, every LDS address of staging and phase 1 is 4 * thread + a constant), which positions of a quad can be
+// corners is a per-lane constant, the row / column / image-edge tests run only in the tiles where they can bind (decided per
+// workgroup), a candidate is stored as the LDS offset of its pixel, and phase 3 claims its slots with one LDS atomic per wavefront.
 #include <stdlib.h>
 
 #include "av_common.h"
@@ -84,8 +90,8 @@ __device__ __forceinline__ int fast_score(const uint8_t* c, int t)
     av_h2 D[8];                                     // BIAS + v - ring[j], BIAS + v - ring[j + 8]: 1 .. 511
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const uint32_t pk = (uint32_t)c[DY[j] * PW + DX[j]] | ((uint32_t)c[DY[j + 8] * PW + DX[j + 8]] << 16);
-        D[j] = __builtin_bit_cast(av_h2, vb - __builtin_bit_cast(av_us2, pk));
+        const av_us2 pk = {(unsigned short)c[DY[j] * PW + DX[j]], (unsigned short)c[DY[j + 8] * PW + DX[j + 8]]};     // one byte load per half
+        D[j] = __builtin_bit_cast(av_h2, vb - pk);
     }
     av_h2 L2[8], H2[8], L4[8], H4[8];               // min / max over 2 and over 4 consecutive ring positions
 #pragma unroll
@@ -110,11 +116,18 @@ __device__ __forceinline__ int fast_score(const uint8_t* c, int t)
     return m > t ? m - 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
+// A dword of four bytes -> 0xFF in every byte that is not zero (mask bytes: any non-zero value means "keep").
+__device__ __forceinline__ uint32_t nz_bytes(uint32_t m)
+{
+    const uint32_t hb = (((m & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | m) & 0x80808080u;      // no carry leaves a byte: 0x7F + 0x7F = 0xFE
+    return (hb >> 7) * 0xFFu;
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void fast_kernel(FastArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t pix[PH * PW + 16];     // +16: the last quad of the last row reads one dword past it
     __shared__ __attribute__((aligned(16))) uint8_t sc[SH * SP];
-    // candidate lists, one private segment per wavefront (a wavefront visits every fourth chunk of 64 quads, 4 positions each)
+    // candidate lists, one private segment per wavefront (a wavefront judges at most 64 lanes x 4 rows x 4 positions)
     constexpr int NQ = SH * PWD;                                  // 900 quad positions
     constexpr int SEG = ((NQ + 255) / 256) * 64 * 4;
     __shared__ uint16_t cand[4 * SEG];
@@ -130,43 +143,79 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
     const uint8_t* img = a.img + img_i * a.img_stride;
     const int x0 = bx * TW, y0 = by * TH;
     const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    // Who owns what.  Staging and phase 1: thread t < 252 owns dword column cq = t % 18 of the pixel / score tile and rows
+    // rq + 14 j (56 = 4 x 14 pixel rows, 50 score rows): the ONE division of the kernel, and every LDS address of the two stages
+    // is 4 t plus a constant.  Phase 3: 256 = 16 x 16, thread t owns quad column q3 = t % 16 and rows t / 16 + 16 it.
+    constexpr int NOWN = 14 * PWD;                              // 252
+    const int rq = tid / PWD, cq = tid - rq * PWD;
+    const bool owner = tid < NOWN;
+    const int r3 = tid >> 4, q3 = tid & 15;
+    // What can bind in this tile, decided once per workgroup: pixels past the right / bottom edge of the image (ragged), score rows
+    // outside y in [3, h - 3) (edge_y).
+    const bool ragged = x0 + TW > a.w || y0 + TH > a.h;
+    const bool edge_y = y0 < 4 || y0 + TH + 4 > a.h;
 
     // pixel tile: 56 rows x 72 bytes from (x0-4, y0-4) (x0 is a multiple of 64, so x0-4 is dword aligned when pitch and base are)
     uint32_t* pixw = reinterpret_cast<uint32_t*>(pix);
-    // The mask bytes of the four pixels each lane will judge in phase 3 are fetched NOW, with the pixel tile: a mask read
-    // behind the non-max suppression was a dependent HBM round trip in the middle of every tile.
+    // allow[it]: which of the four pixels a lane judges in iteration it of phase 3 may become keypoints at all.  With a mask that
+    // can be read as dwords it is the mask dword (a quad is then wholly inside or wholly outside the image: outside reads as 0),
+    // fetched NOW, with the pixel tile: a mask read behind the non-max suppression was a dependent HBM round trip in the middle of
+    // every tile.  Without one only a ragged tile has pixels to refuse (0xFF per pixel inside the image).  A tile that is neither
+    // never looks at it.
     constexpr int NIT3 = (TW / 4) * TH / 256;
-    uint32_t mask4[NIT3];
+    uint32_t allow[NIT3];
     const bool mask_dw = a.mask && (((a.w | (int)(a.mask_stride & 3) | (int)(reinterpret_cast<uintptr_t>(a.mask) & 3)) & 3) == 0);
+    const bool use_allow = mask_dw || ragged;
 #pragma unroll
-    for (int it = 0; it < NIT3; ++it) {
-        const int i = tid + 256 * it;
-        const int r = i / (TW / 4), x = x0 + 4 * (i - r * (TW / 4)), y = y0 + r;
-        mask4[it] = 0xFFFFFFFFu;
-        if (mask_dw) mask4[it] = (x + 4 <= a.w && y < a.h) ? *reinterpret_cast<const uint32_t*>(a.mask + img_i * a.mask_stride + (size_t)y * a.w + x) : 0u;
+    for (int it = 0; it < NIT3; ++it) allow[it] = 0xFFFFFFFFu;
+    if (mask_dw) {
+        const int x = x0 + 4 * q3;
+        const uint8_t* mp = a.mask + img_i * a.mask_stride + x;
+#pragma unroll
+        for (int it = 0; it < NIT3; ++it) {
+            const int y = y0 + r3 + 16 * it;
+            allow[it] = (x + 4 <= a.w && y < a.h) ? *reinterpret_cast<const uint32_t*>(mp + (size_t)y * a.w) : 0u;
+        }
+    } else if (ragged) {
+#pragma unroll
+        for (int it = 0; it < NIT3; ++it) {
+            const int left = a.w - (x0 + 4 * q3);                  // pixels of the quad inside the image
+            allow[it] = (y0 + r3 + 16 * it < a.h && left > 0) ? (left >= 4 ? 0xFFFFFFFFu : 0xFFFFFFFFu >> (8 * (4 - left))) : 0u;
+        }
     }
     // Tile rows as dwords whenever rows, stride and base are dword aligned (then a dword lies wholly inside or wholly outside the
     // valid columns): all four loads of a thread are issued in one basic block -- as a loop the compiler waited for every load
-    // before issuing the next (one dword in flight per thread); rows above / below the valid rows are clamped, dwords left /
-    // right of the valid columns read as zero.  Pixels outside the image never reach a valid output (corners need x, y in
-    // [3, dim - 3)), so clamp vs reflect vs zero is immaterial.
+    // before issuing the next (one dword in flight per thread).  A tile whose 72 x 56 pixels all exist (image or frame) adds a
+    // constant row stride to one address; in the others rows above / below the valid rows are clamped and dwords left / right of
+    // the valid columns read as zero.  Pixels outside the image never reach a valid output (corners need x, y in [3, dim - 3)),
+    // so clamp vs reflect vs zero is immaterial.
     const bool dw_rows = ((a.img_pitch | a.w | (int)(a.img_stride & 3) | (int)(reinterpret_cast<uintptr_t>(a.img) & 3)) & 3) == 0;
     if (dw_rows) {
-        constexpr int NLD = (PH * PWD + 255) / 256;
-        uint32_t v[NLD]; bool in[NLD];
+        if (owner) {
+            constexpr int NLD = PH / 14;
+            uint32_t v[NLD];
+            const int xb = x0 - 4 + 4 * cq;
+            const bool whole = y0 - 4 >= -a.border && y0 + TH + 4 <= a.h + a.border && x0 - 4 >= -a.border && x0 + TW + 4 <= a.w + a.border;
+            if (whole) {
+                const uint8_t* p = img + (ptrdiff_t)(y0 - 4 + rq) * a.img_pitch + xb;
 #pragma unroll
-        for (int it = 0; it < NLD; ++it) {
-            const int i = min(tid + 256 * it, PH * PWD - 1);
-            const int r = i / PWD, c = i - r * PWD;
-            const int xb = x0 - 4 + 4 * c;
-            const int y = min(max(y0 - 4 + r, -a.border), a.h + a.border - 1);
-            in[it] = xb >= -a.border && xb + 4 <= a.w + a.border;
-            v[it] = *reinterpret_cast<const uint32_t*>(in[it] ? img + (ptrdiff_t)y * a.img_pitch + xb : img);
-        }
+                for (int j = 0; j < NLD; ++j) v[j] = *reinterpret_cast<const uint32_t*>(p + (ptrdiff_t)(14 * j) * a.img_pitch);
+            } else {
+                const bool in = xb >= -a.border && xb + 4 <= a.w + a.border;
 #pragma unroll
-        for (int it = 0; it < NLD; ++it) {
-            const int i = tid + 256 * it;
-            if (i < PH * PWD) pixw[i] = in[it] ? v[it] : 0u;
+                for (int j = 0; j < NLD; ++j) {
+                    const int y = min(max(y0 - 4 + rq + 14 * j, -a.border), a.h + a.border - 1);
+                    v[j] = *reinterpret_cast<const uint32_t*>(in ? img + (ptrdiff_t)y * a.img_pitch + xb : img);
+                }
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) v[j] = in ? v[j] : 0u;
+            }
+#pragma unroll
+            for (int j = 0; j < NLD; ++j) pixw[tid + NOWN * j] = v[j];
+        } else {
+            pixw[PH * PWD + tid - NOWN] = 0;
         }
     } else {
         for (int i = tid; i < PH * PW; i += 256) {
@@ -174,57 +223,65 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
             int y = min(max(y0 - 4 + r, 0), a.h - 1), x = min(max(x0 - 4 + c, 0), a.w - 1);
             pix[i] = img[(size_t)y * a.img_pitch + x];
         }
+        if (tid < 4) pixw[PH * PWD + tid] = 0;
     }
-    if (tid < 4) pixw[PH * PWD + tid] = 0;
+    // Which of the lane's four positions pc = 4 cq + k can be corners at all (bit 7 of byte k): columns 3 .. TW + 4 of the tile that
+    // lie in x in [3, w - 3).  The column is the lane's for the whole of phase 1, so this is computed once.
+    uint32_t V = 0;
+    {
+        const int lo = max(3, 7 - x0), hi = min(TW + 4, a.w - x0);          // x = x0 - 4 + pc in [3, w - 3)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) V |= (4 * cq + k >= lo && 4 * cq + k <= hi) ? 0x80u << (8 * k) : 0u;
+    }
     __syncthreads();
     // Phase 1: cheap necessary condition on the 4 compass pixels of the ring (any 9-arc contains at least two of them) for the
-    // four positions pc = 4q .. 4q+3 of score row sr (pixel row sr+3): dwords U (3 rows up), D (3 rows down), L, C, R of the row.
+    // four positions pc = 4 cq .. 4 cq + 3 of score row sr = rq + 14 it (pixel row sr + 3): dwords U (3 rows up), D (3 rows down),
+    // L, C, R of the row.  Quad i = sr * PWD + cq = tid + 252 it is dword i of the score tile and dword i + 3 PWD of the pixel tile.
     uint32_t* scw = reinterpret_cast<uint32_t*>(sc);
-    const int lane = tid & 63, wave = tid >> 6;
+    uint16_t* seg = cand + wave * SEG;
     int wcnt = 0;                                   // candidates found by this wavefront so far (wavefront-uniform)
     const int t = a.threshold;
-    for (int i0 = 0; i0 < NQ; i0 += 256) {
-        const int i = i0 + tid;
-        bool cf[4] = {false, false, false, false};
-        int sr = 0, q = 0;
-        if (i < NQ) {
-            sr = i / PWD; q = i - sr * PWD;
+#pragma unroll
+    for (int it = 0; it < (SH + 13) / 14; ++it) {
+        const int i = tid + NOWN * it;
+        uint32_t m = 0;                             // bit 7 of byte k: position k passes the test and can be a corner
+        if (14 * (it + 1) <= SH ? owner : tid < (SH - 14 * it) * PWD) {
             scw[i] = 0;
-            const int y = y0 - 1 + sr;
-            if (y >= 3 && y < a.h - 3) {
-                const uint32_t* rowc = pixw + (sr + 3) * PWD + q;
-                const uint32_t C = rowc[0], L = q > 0 ? rowc[-1] : 0u, R = rowc[1];
-                const uint32_t U = rowc[-3 * PWD], D = rowc[3 * PWD];
-                const uint32_t R3 = __builtin_amdgcn_alignbyte(R, C, 3), L3 = __builtin_amdgcn_alignbyte(C, L, 1);      // p[+3], p[-3] of the four positions
-                // Packed 16-bit lanes, two pixels per register.  Any 9-arc of the 16-ring holds at least one pixel of EVERY
-                // antipodal pair, so "centre brighter than one of (p0, p8) AND than one of (p4, p12)" -- or the same for darker --
-                // is necessary for a corner (OpenCV's own first rejection tests):
-                //   bright: min(max(d0, d8), max(d4, d12)) > t     dark: max(min(d0, d8), min(d4, d12)) < -t
-                auto half = [](uint32_t x, int hi) -> av_s2 { return __builtin_bit_cast(av_s2, __builtin_amdgcn_perm(0, x, hi ? 0x0C030C02u : 0x0C010C00u)); };
-                const av_s2 tt = {(short)t, (short)t}, zz = {0, 0};
-                uint32_t fl[2];
-#pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    const av_s2 c = half(C, hf);
-                    const av_s2 d0 = c - half(D, hf), d8 = c - half(U, hf), d4 = c - half(R3, hf), d12 = c - half(L3, hf);
-                    const av_s2 mb = __builtin_elementwise_min(__builtin_elementwise_max(d0, d8), __builtin_elementwise_max(d4, d12));
-                    const av_s2 md = __builtin_elementwise_max(__builtin_elementwise_min(d0, d8), __builtin_elementwise_min(d4, d12));
-                    const av_s2 val = __builtin_elementwise_max(mb, zz - md);
-                    fl[hf] = __builtin_bit_cast(uint32_t, tt - val);             // negative (bit 15 of its half set) iff val > t
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int pc = 4 * q + k, x = x0 - 4 + pc;
-                    const bool hit = (fl[k >> 1] >> (15 + 16 * (k & 1))) & 1u;
-                    cf[k] = hit && pc >= 3 && pc <= TW + 4 && x >= 3 && x < a.w - 3;
-                }
+            uint32_t Vr = V;
+            if (edge_y) {
+                const int y = y0 - 1 + rq + 14 * it;
+                Vr = (y >= 3 && y < a.h - 3) ? V : 0u;
             }
+            const uint32_t* rowc = pixw + i + 3 * PWD;
+            // (the dword left of quad 0 belongs to the row above: it only feeds positions 0 .. 2, which V rules out)
+            const uint32_t C = rowc[0], Lw = rowc[-1], R = rowc[1];
+            const uint32_t U = rowc[-3 * PWD], D = rowc[3 * PWD];
+            const uint32_t R3 = __builtin_amdgcn_alignbyte(R, C, 3), L3 = __builtin_amdgcn_alignbyte(C, Lw, 1);      // p[+3], p[-3] of the four positions
+            // Packed 16-bit lanes, two pixels per register.  Any 9-arc of the 16-ring holds at least one pixel of EVERY
+            // antipodal pair, so "centre brighter than one of (p0, p8) AND than one of (p4, p12)" -- or the same for darker --
+            // is necessary for a corner (OpenCV's own first rejection tests):
+            //   bright: min(max(d0, d8), max(d4, d12)) > t     dark: max(min(d0, d8), min(d4, d12)) < -t
+            auto half = [](uint32_t x, int hi) -> av_s2 { return __builtin_bit_cast(av_s2, __builtin_amdgcn_perm(0, x, hi ? 0x0C030C02u : 0x0C010C00u)); };
+            const av_s2 tt = {(short)t, (short)t}, zz = {0, 0};
+            uint32_t fl[2];
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const av_s2 c = half(C, hf);
+                const av_s2 d0 = c - half(D, hf), d8 = c - half(U, hf), d4 = c - half(R3, hf), d12 = c - half(L3, hf);
+                const av_s2 mb = __builtin_elementwise_min(__builtin_elementwise_max(d0, d8), __builtin_elementwise_max(d4, d12));
+                const av_s2 md = __builtin_elementwise_max(__builtin_elementwise_min(d0, d8), __builtin_elementwise_min(d4, d12));
+                const av_s2 val = __builtin_elementwise_max(mb, zz - md);
+                fl[hf] = __builtin_bit_cast(uint32_t, tt - val);             // negative (bit 15 of its half set) iff val > t
+            }
+            m = __builtin_amdgcn_perm(fl[1], fl[0], 0x07050301u) & Vr;       // the four sign bytes side by side
         }
-        // ordered compaction into this wavefront's own segment: no LDS atomic, no cross-lane broadcast
+        // ordered compaction into this wavefront's own segment: no LDS atomic, no cross-lane broadcast.  A candidate is the byte
+        // offset of its centre in the pixel tile (at most 3,815); its score byte lies 3 PW before that offset in the score tile.
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const unsigned long long b = __ballot(cf[k]);
-            if (cf[k]) cand[wave * SEG + wcnt + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0))] = (uint16_t)(sr * SP + 4 * q + k);
+            const bool hit = (m & (0x80u << (8 * k))) != 0;
+            const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
+            if (__builtin_amdgcn_inverse_ballot_w64(b)) (seg + wcnt)[__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u))] = (uint16_t)(4 * i + 3 * PW + k);
             wcnt += __popcll(b);
         }
     }
@@ -234,55 +291,73 @@ __global__ __launch_bounds__(256) void fast_kernel(FastArgs a)
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (int k = lane; k < wcnt; k += 64) {
-        const int i = cand[wave * SEG + k];
-        const int sr = i / SP, pc = i - sr * SP;
-        sc[i] = (uint8_t)fast_score(&pix[(sr + 3) * PW + pc], t);
+        const int o = seg[k];
+        sc[o - 3 * PW] = (uint8_t)fast_score(&pix[o], t);
     }
     __syncthreads();
     // Phase 3: 3x3 non-max suppression + mask; survivors go to an LDS list first so that the tile issues
-    // ONE returning global atomic per output list it touches (a 64x16 tile overlaps <= 4 grid cells)
-    // instead of one per keypoint.
+    // ONE returning global atomic per output list it touches instead of one per keypoint.
     __shared__ uint32_t surv_word[TCAP];
     __shared__ int nsurv, flat_base;
     if (tid == 0) nsurv = 0;
     __syncthreads();
-    // quads of the tile interior: columns pc = 4q .. 4q+3, q = 1..16 (x = x0 .. x0+63), score rows sr = 1..48 (y = y0 .. y0+47)
+    // quads of the tile interior: columns pc = 4q .. 4q+3, q = 1 + q3 (x = x0 + 4 q3 ..), score rows sr = 1 + r3 + 16 it (y = y0 + r3 + 16 it)
+    const uint32_t* s3 = scw + (r3 + 1) * SPD + 1 + q3;
+    const uint32_t ones = (1u << a.rbits) - 1u;
+    const uint32_t rb0 = ones - (uint32_t)((y0 + r3) * a.w + x0 + 4 * q3);       // raster part of the word of pixel 0 of the quad, it = 0
 #pragma unroll
-    for (int it = 0; it < (TW / 4) * TH / 256; ++it) {
-        const int i = tid + 256 * it;
-        const int r = i / (TW / 4), q = 1 + (i - r * (TW / 4));
-        const uint32_t* rowc = scw + (r + 1) * SPD + q;
+    for (int it = 0; it < NIT3; ++it) {
+        const uint32_t* rowc = s3 + 16 * SPD * it;
         const uint32_t B = rowc[0];
-        if (B == 0) continue;                                 // no positive score among the four pixels
-        // per score row the 6-byte window [pc-1 .. pc+4] as (lo, hi): pixel k sees bytes k, k+1, k+2
-        uint32_t lo[3], hi[3];
+        uint32_t gb = 0;                                      // byte k != 0: pixel k is a keypoint
+        if (B != 0) {                                         // a positive score among the four pixels (most quads have none)
+            // Byte w of the 6-byte window [pc-1 .. pc+4] of a score row is byte 3 of the dword before (w = 0), the row's dword (1 .. 4)
+            // or byte 0 of the dword after (5); pixel k sees w = k (left), k + 1 (centre), k + 2 (right).  Strict 3x3 maximum test
+            // for the four pixels at once, two pixels per register (packed u16), every pair one v_perm of the dwords as loaded.
+            typedef unsigned short av_u2 __attribute__((ext_vector_type(2)));
+            uint32_t A[3], M[3], N[3];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const uint32_t* rp = rowc + (d - 1) * SPD;
-            const uint32_t A = rp[-1], Bm = rp[0], Cn = rp[1];
-            lo[d] = __builtin_amdgcn_alignbyte(Bm, A, 3); hi[d] = __builtin_amdgcn_alignbyte(Cn, Bm, 3);
+            for (int d = 0; d < 3; ++d) {
+                const uint32_t* rp = rowc + (d - 1) * SPD;
+                A[d] = rp[-1]; M[d] = d == 1 ? B : rp[0]; N[d] = rp[1];
+            }
+            auto p01 = [&](int d) -> av_u2 { return __builtin_bit_cast(av_u2, __builtin_amdgcn_perm(M[d], A[d], 0x0C040C03u)); };
+            auto p12 = [&](int d) -> av_u2 { return __builtin_bit_cast(av_u2, __builtin_amdgcn_perm(0, M[d], 0x0C010C00u)); };
+            auto p23 = [&](int d) -> av_u2 { return __builtin_bit_cast(av_u2, __builtin_amdgcn_perm(0, M[d], 0x0C020C01u)); };
+            auto p34 = [&](int d) -> av_u2 { return __builtin_bit_cast(av_u2, __builtin_amdgcn_perm(0, M[d], 0x0C030C02u)); };
+            auto p45 = [&](int d) -> av_u2 { return __builtin_bit_cast(av_u2, __builtin_amdgcn_perm(N[d], M[d], 0x0C040C03u)); };
+            // (scores are 0 .. 254: as half-precision bit patterns they order like the integers -- one v_pk_maximum3_f16 per three, see fast_score)
+            auto mx3 = [](av_u2 x, av_u2 y, av_u2 z) -> av_u2 { return __builtin_bit_cast(av_u2, h2_max3(__builtin_bit_cast(av_h2, x), __builtin_bit_cast(av_h2, y), __builtin_bit_cast(av_h2, z))); };
+            const av_u2 n01 = mx3(mx3(p01(0), p12(0), p23(0)), mx3(p01(2), p12(2), p23(2)), mx3(p01(1), p23(1), p23(1)));
+            const av_u2 n23 = mx3(mx3(p23(0), p34(0), p45(0)), mx3(p23(2), p34(2), p45(2)), mx3(p23(1), p45(1), p45(1)));
+            const av_u2 g01 = __builtin_elementwise_sub_sat(p12(1), n01), g23 = __builtin_elementwise_sub_sat(p34(1), n23);
+            // half k & 1 of g(k >> 1) != 0: score > all 8 neighbours; the differences are below 256, their low bytes side by side
+            gb = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, g23), __builtin_bit_cast(uint32_t, g01), 0x06040200u);
+            if (use_allow) gb &= mask_dw ? nz_bytes(allow[it]) : allow[it];
+            if (a.mask && !mask_dw && gb != 0) {              // a mask that only bytes can read: looked at for the keypoints alone
+                const uint8_t* mp = a.mask + img_i * a.mask_stride + (size_t)(y0 + r3 + 16 * it) * a.w + x0 + 4 * q3;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if ((gb >> (8 * k)) & 0xFFu) gb = mp[k] != 0 ? gb : gb & ~(0xFFu << (8 * k));
+            }
         }
-        // strict 3x3 maximum test for the four pixels at once, two pixels per register (packed u16): byte w of the 8-byte
-        // window (lo, hi) of a row is column pc - 1 + w; pixel k sees w = k (left), k + 1 (centre), k + 2 (right)
-        typedef unsigned short av_u2 __attribute__((ext_vector_type(2)));
-        auto pair = [&](int d, uint32_t sel) -> av_u2 { return __builtin_bit_cast(av_u2, __builtin_amdgcn_perm(hi[d], lo[d], sel)); };
-        constexpr uint32_t P01 = 0x0C010C00u, P12 = 0x0C020C01u, P23 = 0x0C030C02u, P34 = 0x0C040C03u, P45 = 0x0C050C04u;
-        // (scores are 0 .. 254: as half-precision bit patterns they order like the integers -- one v_pk_maximum3_f16 per three, see fast_score)
-        auto mx3 = [](av_u2 x, av_u2 y, av_u2 z) -> av_u2 { return __builtin_bit_cast(av_u2, h2_max3(__builtin_bit_cast(av_h2, x), __builtin_bit_cast(av_h2, y), __builtin_bit_cast(av_h2, z))); };
-        const av_u2 n01 = mx3(mx3(pair(0, P01), pair(0, P12), pair(0, P23)), mx3(pair(2, P01), pair(2, P12), pair(2, P23)), mx3(pair(1, P01), pair(1, P23), pair(1, P23)));
-        const av_u2 n23 = mx3(mx3(pair(0, P23), pair(0, P34), pair(0, P45)), mx3(pair(2, P23), pair(2, P34), pair(2, P45)), mx3(pair(1, P23), pair(1, P45), pair(1, P45)));
-        const av_u2 g01 = __builtin_elementwise_sub_sat(pair(1, P12), n01), g23 = __builtin_elementwise_sub_sat(pair(1, P34), n23);
-        const uint32_t gt[2] = {__builtin_bit_cast(uint32_t, g01), __builtin_bit_cast(uint32_t, g23)};      // half k & 1 of gt[k >> 1] != 0: score > all 8 neighbours
+        // one compaction per wavefront: a ballot per pixel position, the lane counts below, ONE LDS atomic by one lane for the lot
+        unsigned long long bk[4];
+        int tot = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { bk[k] = __builtin_amdgcn_ballot_w64(((gb >> (8 * k)) & 0xFFu) != 0); tot += __popcll(bk[k]); }
+        if (tot == 0) continue;                               // (wavefront-uniform)
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&nsurv, tot);         // LDS atomic; a tile has <= TCAP strict maxima
+        base = __builtin_amdgcn_readfirstlane(base);
+        const uint32_t rb = rb0 - (uint32_t)(16 * it * a.w);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int s = (int)((B >> (8 * k)) & 0xFF);
-            const int x = x0 + 4 * (q - 1) + k, y = y0 + r;
-            bool keep = ((gt[k >> 1] >> (16 * (k & 1))) & 0xFFFFu) != 0 && x < a.w && y < a.h;
-            if (keep && a.mask) keep = mask_dw ? ((mask4[it] >> (8 * k)) & 0xFF) != 0 : a.mask[img_i * a.mask_stride + (size_t)y * a.w + x] != 0;
-            if (keep) {
-                const int slot = atomicAdd(&nsurv, 1);            // LDS atomic; a tile has <= TCAP strict maxima
-                surv_word[slot] = ((uint32_t)s << a.rbits) | (((1u << a.rbits) - 1u) - (uint32_t)(y * a.w + x));
+            if (__builtin_amdgcn_inverse_ballot_w64(bk[k])) {
+                const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(bk[k] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bk[k], (unsigned)base));
+                surv_word[slot] = (((B >> (8 * k)) & 0xFFu) << a.rbits) | (rb - k);
             }
+            base += __popcll(bk[k]);
         }
     }
     __syncthreads();
