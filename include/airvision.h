@@ -931,6 +931,40 @@ int  av_msckf_batch_device_resident(const av_msckf_batch* b);     /* 1: state + 
 int  av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_dev, const double* uv_dev, const int32_t* n_feat_dev, int cap,
                                const double* timestamps, double* out, void* msg_stream, void* stream);
 int  av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, int n, void* stream);
+/* Odometry covariance: the uncertainty of what a step publishes, per stream and step, riding the step's one read-back.
+ * The record is the 15 x 15 symmetric matrix C = J P[0:21, 0:21] J^T, P = state_cov AT THE MOMENT OF publish (msckf.py:845-867): the
+ * pruning update and the removal of its two camera states are in, online_reset (:821-843) has not taken effect -- on a reset step
+ * av_msckf_batch_get_cov returns the re-initialised matrix, this record the one the pose was published with.
+ * Error coordinates, in this order:
+ *   rows  0:3   p        IMU position in the world frame
+ *   rows  3:6   theta    rotation error of R_wb = to_rotation(q)^T applied on the RIGHT (body frame): R_wb,true = R_wb (I + [theta]x);
+ *                        this is the filter's own error state delta-theta (q <- dq (x) q, msckf.py:576-579)
+ *   rows  6:9   v        velocity in the world frame (what the reference publishes as body_velocity with T_imu_body = I)
+ *   rows  9:12  p_c      position of cam0 in the world frame, t_c_w = p + R_wb t_cam0_imu
+ *   rows 12:15  theta_c  rotation error of R_wc = (R_imu_cam0 R_wb^T)^T, applied on the right (cam0 frame)
+ * With the reference's error-state order (theta 0:3, b_g 3:6, v 6:9, b_a 9:12, p 12:15, theta_ext 15:18, t_ext 18:21), R_ic = R_imu_cam0
+ * and t_ci = t_cam0_imu as published with the pose, the non-zero blocks of J are
+ *   J[0:3, 12:15] = I;  J[3:6, 0:3] = I;  J[6:9, 6:9] = I;
+ *   J[9:12, 12:15] = I;  J[9:12, 0:3] = -R_wb [t_ci]x;  J[9:12, 18:21] = R_wb;
+ *   J[12:15, 0:3] = R_ic;  J[12:15, 15:18] = I
+ * (from the injection rules q <- dq (x) q, R_ic <- R(dq_ext) R_ic, t_ci += dt, msckf.py:568-595; checked against central differences of
+ * those maps, tests/test_odom_cov_ref.py).  Entries of rows and columns 0:9 are the selected entries of P, bit for bit.
+ * On the wire: the upper triangle, row-major, AV_ODOM_COV_DOUBLES = 120 doubles per stream ((0,0) .. (0,14), (1,1) .. (14,14)).  Where
+ * the step's `published` is not 1 (no gravity yet, no frame, a stopped stream) all 120 are NaN.
+ * av_msckf_batch_set_odom_cov(b, enable): before the batch's first step (AV_E_INVALID afterwards).  Off (the default) the step launches
+ * and reads back exactly what it did without the feature; on, the last per-stream kernel of the step is the instance that also writes
+ * the records (no launch more) and one more asynchronous copy brings them to a pinned buffer of the step's ring slot: no wait and no
+ * allocation inside a step.  Device-resident filter only: enabling it under AV_MSCKF_STORE=host is AV_E_INVALID, with a text that names
+ * AV_MSCKF_STORE.
+ * av_msckf_batch_next_odom_cov(b, cov_host): hands over the destination, n_streams * AV_ODOM_COV_DOUBLES doubles, of the records of
+ * the NEXT av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires (step: on return; submit: once
+ * av_msckf_batch_wait has let it retire) and must stay valid until then.  Stream groups each fill their own part.  AV_E_INVALID while
+ * the feature is off.  A step without a destination computes its records and drops them.
+ * Known limits: no conjugation for T_imu_body != I; the right (body-frame) rotation convention only -- the world-frame one is the
+ * similarity by R_wb; no bias or extrinsic blocks; no innovation statistics; nothing on the host-bookkeeping path. */
+#define AV_ODOM_COV_DOUBLES 120
+int  av_msckf_batch_set_odom_cov(av_msckf_batch* b, int enable);
+int  av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host);
 int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);     /* [state dim, camera states, map features] */
 /* Full host-side state of one stream -- every target of measurement_update's injection (msckf.py:568-595), for parity tests
  * (SURVEY 8b get_state): imu32 = [imu_state.timestamp, orientation q(4, JPL xyzw), position(3), velocity(3), gyro_bias(3),

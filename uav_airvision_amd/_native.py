@@ -260,6 +260,8 @@ SIGNATURES = {
     'av_msckf_batch_submit_dev': (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     'av_msckf_batch_wait': (C.c_int, [_P, C.c_int]),
     'av_msckf_batch_get_cov': (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    'av_msckf_batch_set_odom_cov': (C.c_int, [_P, C.c_int]),
+    'av_msckf_batch_next_odom_cov': (C.c_int, [_P, _P]),
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_msckf_batch_launch_shape': (C.c_int, [_P, C.POINTER(C.c_int32 * 17)]),

@@ -158,3 +158,7 @@ class ConfigEuRoC(object):
         self.cam1_resolution = np.array([752, 480])
 
         self.T_imu_body = np.identity(4)
+
+        # no reference counterpart: the drop-in MSCKF keeps the 15 x 15 odometry covariance of its last published result in
+        # `last_covariance` (needs T_imu_body = identity; include/airvision.h, "Odometry covariance")
+        self.publish_covariance = False

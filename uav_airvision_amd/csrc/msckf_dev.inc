@@ -18,6 +18,8 @@
 //   ... the same chain for the pruning update ...
 //   dk_finish    per stream: injection, removal of the two camera states (covariance rows/columns, frames, links), online
 //                reset, publish
+//   dk_finish_cov  (instead of dk_finish when av_msckf_batch_set_odom_cov is on) the same, and between the publish and the reset the
+//                stream's odometry-covariance record (120 doubles), read back next to the pose
 //
 // Per-stream capacity failures are recorded in the stream's state (DState::failed) and stop that stream only.
 
@@ -550,7 +552,70 @@ __global__ __launch_bounds__(256, 5) void dk_mid(DevArgs a)
 // dk_finish: the pruning update lands in the state, the two camera states leave (msckf.py:774-786), online_reset (:821-843),
 // publish (:845-867)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s)
+// Odometry covariance (include/airvision.h, "Odometry covariance"): C = J P[0:21, 0:21] J^T of the stream as it is PUBLISHED -- the
+// pruning update and the camera removal are in, online_reset has not run -- in the error coordinates p, theta, v, p_c, theta_c.  The upper
+// triangle, row-major, 120 doubles; NaN where the step does not publish.  The first wavefront of the workgroup does the work: the 21 x 21
+// block and the six rows of J that are not selections (record rows 9:15) are staged in LDS, every entry of the triangle is computed once.
+// Entries of rows 0:9 x columns 0:9 are copies of the entries of P they select; rows 0:9 x columns 9:15 are one 21-term sum (the zeros of J
+// multiply to exact zeros), the 6 x 6 corner is two nested ones.
+constexpr int ODOM_COV_DOUBLES = 120;
+__device__ __forceinline__ void dev_odom_cov(const DevArgs& a, int s, const DState* D, double* rec)
+{
+    __shared__ double Ps[IMU_DIM * IMU_DIM], Jl[6 * IMU_DIM];
+    const int tid = threadIdx.x, N = IMU_DIM;
+    if (!(D->active && !D->failed)) {                        // (workgroup-uniform: nobody writes the state between the removal's barrier and the reset's)
+        if (tid < 64) for (int e = tid; e < ODOM_COV_DOUBLES; e += 64) rec[e] = __longlong_as_double(0x7ff8000000000000LL);
+        return;
+    }
+    const double* P = a.P + (size_t)s * a.pstride;
+    for (int i = tid; i < N * N; i += (int)blockDim.x) { const int r = i / N, c = i - r * N; Ps[i] = P[(size_t)r * a.ld + c]; }
+    for (int i = tid; i < 6 * N; i += (int)blockDim.x) Jl[i] = 0.0;
+    __syncthreads();
+    if (tid == 0) {
+        double Rbw[9];                                        // to_rotation(q): world -> body; R_wb is its transpose
+        h_to_rotation(D->q, Rbw);
+        const double tx = D->t_ci[0], ty = D->t_ci[1], tz = D->t_ci[2];
+        for (int r = 0; r < 3; ++r) {
+            const double r0 = Rbw[r], r1 = Rbw[3 + r], r2 = Rbw[6 + r];      // row r of R_wb
+            // p_c = p + R_wb t_ci:  d p  -  R_wb [t_ci]x d theta  +  R_wb d t_ci
+            Jl[r * N + 0] = -(r1 * tz - r2 * ty); Jl[r * N + 1] = -(r2 * tx - r0 * tz); Jl[r * N + 2] = -(r0 * ty - r1 * tx);
+            Jl[r * N + 12 + r] = 1.0;
+            Jl[r * N + 18] = r0; Jl[r * N + 19] = r1; Jl[r * N + 20] = r2;
+            // theta_c = R_ic d theta + d theta_ext
+            for (int c = 0; c < 3; ++c) Jl[(3 + r) * N + c] = D->R_ic[r * 3 + c];
+            Jl[(3 + r) * N + 15 + r] = 1.0;
+        }
+    }
+    __syncthreads();
+    if (tid < 64) {
+        for (int e = tid; e < ODOM_COV_DOUBLES; e += 64) {
+            int i = 0, j = e;
+            while (j >= 15 - i) { j -= 15 - i; ++i; }
+            j += i;                                           // entry (i, j), i <= j, of the 15 x 15 record
+            const int si = i < 3 ? 12 + i : (i < 6 ? i - 3 : i);      // state index that record row i selects (i < 9)
+            double v;
+            if (j < 9) {
+                const int sj = j < 3 ? 12 + j : (j < 6 ? j - 3 : j);
+                v = Ps[si * N + sj];
+            } else if (i < 9) {
+                v = 0.0;
+                for (int l = 0; l < N; ++l) v += Ps[si * N + l] * Jl[(j - 9) * N + l];
+            } else {
+                v = 0.0;
+                for (int k = 0; k < N; ++k) {
+                    double m = 0.0;
+                    for (int l = 0; l < N; ++l) m += Ps[k * N + l] * Jl[(j - 9) * N + l];
+                    v += Jl[(i - 9) * N + k] * m;
+                }
+            }
+            rec[e] = v;
+        }
+    }
+}
+
+// COV: the instance that also writes the stream's odometry-covariance record (dk_finish_cov); false: dk_finish as it always was
+template <bool COV>
+__device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* odom)
 {
     __shared__ int red[8], s_reset;
     const int tid = threadIdx.x;
@@ -599,6 +664,7 @@ __device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s)
         }
         s_reset = reset;
     }
+    if constexpr (COV) dev_odom_cov(a, s, D, odom + (size_t)s * ODOM_COV_DOUBLES);      // reads P and the state: before the reset's barrier
     __syncthreads();
     if (s_reset) {
         AvsTeam T; T.red = red;
@@ -617,7 +683,13 @@ __device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s)
 __global__ __launch_bounds__(256, 5) void dk_finish(DevArgs a)
 {
     AV_FILTER_PRIO();
-    dk_finish_body(a, blockIdx.x);
+    dk_finish_body<false>(a, blockIdx.x, nullptr);
+}
+// dk_finish + the odometry-covariance record of every stream (av_msckf_batch_set_odom_cov), odom = [S][ODOM_COV_DOUBLES]
+__global__ __launch_bounds__(256, 5) void dk_finish_cov(DevArgs a, double* odom)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<true>(a, blockIdx.x, odom);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -645,6 +717,7 @@ struct DevSlot {
     long long* ids_h = nullptr; double* uv_h = nullptr; int* n_h = nullptr;      // pinned staging of a feature message that arrives in host arrays
     long long* ids_d = nullptr; double* uv_d = nullptr; int* n_d = nullptr;      // the message on the device (copied from the host arrays or from the front-end's buffers)
     double* out_h = nullptr; int* cnt_h = nullptr;                                // pinned landing zones of the step's only read-back
+    double* odom_h = nullptr;                                                     // [S][ODOM_COV_DOUBLES] pinned, the odometry-covariance records of the step (NULL: the feature is off)
     hipEvent_t done = nullptr;
     hipEvent_t t0[2] = {nullptr, nullptr}, t1[2] = {nullptr, nullptr}; bool t_used[2] = {false, false};      // av_msckf_batch_work: device time of the two phase chains
     bool in_flight = false;
@@ -656,6 +729,7 @@ struct DevPath {
     DevSlot slot[DEV_RING];
     double* out_d = nullptr; int* stacked0 = nullptr; int* stacked1 = nullptr; UpdArgs* updbase = nullptr; UpdArgs* upd = nullptr;
     DCov* cov_d = nullptr;           // [S] dk_begin -> dk_cov
+    double* odom_d = nullptr;        // [S][ODOM_COV_DOUBLES] dk_finish_cov's records (NULL: av_msckf_batch_set_odom_cov is off)
     int dk_wg = 0;                   // AV_DK_WG read when the path is prepared: 64 / 256 = workgroup size of the per-stream kernels, 0 = by the group's stream count
     int launched_wg = 0;             // workgroup size dev_enqueue launched them with in the last enqueued step (0: no step yet); av_msckf_batch_launch_shape
     int* cols = nullptr; int* blk_row = nullptr; int* blk_len = nullptr; int* clist = nullptr; int* again = nullptr;

@@ -91,6 +91,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
         DA(A.st, S) DA(A.cam_id, S * cs) DA(A.cam_q, S * cs * 4) DA(A.cam_p, S * cs * 3) DA(A.cam_qn, S * cs * 4) DA(A.ncam, S) DA(A.nstate, S) DA(A.grav, S * 3)
         DA(A.n_cand, S) DA(A.over, S) DA(A.cnt, 32) DA(d->out_d, S * 12) DA(d->cov_d, S) DA(d->stacked0, S) DA(d->stacked1, S) DA(d->updbase, S) DA(d->upd, S * 2)
         DA(d->cols, S * 6 * cs) DA(d->clist, S + 8) DA(d->work, S * 8)
+        if (b->odom_cov) DA(d->odom_d, S * ODOM_COV_DOUBLES)
         DAF(A.pos_of, S * A.ns, 0xFF) DAF(A.order, S * A.ns, 0xFF) DA(A.fr_n, S * A.ns) DA(A.hdr, S * AVS_HDR_WORDS) DA(A.births, S)
     }
     DA(A.fr_id, ne) DA(A.fr_z, ne * 4) DA(A.fr_fslot, ne) DA(A.fr_prev, ne) DA(A.fr_next, ne)
@@ -106,6 +107,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
             if ((rc = dev_pinned(d, &sl.ctl_h, S)) || (rc = dev_pinned(d, &sl.out_h, S * 12)) || (rc = dev_pinned(d, &sl.cnt_h, 16))) return rc;
             DA(sl.ctl_d, S) DA(sl.n_d, S)
             if ((rc = dev_pinned(d, &sl.n_h, S))) return rc;
+            if (b->odom_cov && (rc = dev_pinned(d, &sl.odom_h, S * ODOM_COV_DOUBLES))) return rc;
             AV_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
             for (int ph = 0; ph < 2; ++ph) { AV_HIP(hipEventCreate(&sl.t0[ph])); AV_HIP(hipEventCreate(&sl.t1[ph])); }
         }
@@ -518,15 +520,19 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     if ((rc = dev_phase(b, 1, stm, sl, a.cnt))) return rc;
     if (b->debug_capture && (rc = dev_debug_capture(b, 1, stm))) return rc;
     a.stacked = d->stacked1;
-    hipLaunchKernelGGL(dk_finish, dim3(S), dim3(dk_wg), 0, stm, a);
+    // (with the odometry covariance on, the instance that also writes every stream's record: the same launch, one more read-back)
+    if (d->odom_d) hipLaunchKernelGGL(dk_finish_cov, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d);
+    else hipLaunchKernelGGL(dk_finish, dim3(S), dim3(dk_wg), 0, stm, a);
     AV_LAUNCH_CHECK();
     AV_HIP(hipMemcpyAsync(sl.out_h, d->out_d, sizeof(double) * 12 * S, hipMemcpyDeviceToHost, stm));
+    if (d->odom_d) AV_HIP(hipMemcpyAsync(sl.odom_h, d->odom_d, sizeof(double) * ODOM_COV_DOUBLES * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(sl.cnt_h, a.cnt, sizeof(int) * 16, hipMemcpyDeviceToHost, stm));
     return AV_OK;
 }
 
-// wait for the step queued on slot k and hand its published poses to the caller
-int dev_finish(av_msckf_batch* b, int k, double* out)
+// wait for the step queued on slot k and hand its published poses to the caller (cov: where the step's odometry-covariance records
+// go, S * ODOM_COV_DOUBLES doubles; NULL: the step has no destination and the records are dropped)
+int dev_finish(av_msckf_batch* b, int k, double* out, double* cov)
 {
     DevPath* d = b->dev;
     DevSlot& sl = d->slot[k];
@@ -534,6 +540,7 @@ int dev_finish(av_msckf_batch* b, int k, double* out)
     AV_HIP(hipEventSynchronize(sl.done));
     sl.in_flight = false;
     memcpy(out, sl.out_h, sizeof(double) * 12 * b->S);
+    if (cov && sl.odom_h) memcpy(cov, sl.odom_h, sizeof(double) * ODOM_COV_DOUBLES * b->S);
     for (int i = 0; i < 16; ++i) d->hint[i] = sl.cnt_h[i];
     d->have_hint = true;
     for (int ph = 0; ph < 2; ++ph) if (sl.t_used[ph]) {       // the whole step has retired: both phases' event pairs of this slot are complete

@@ -18,7 +18,7 @@ import numpy as np
 from feature import BaseFeature
 from utils import Isometry3d, to_rotation
 from uav_airvision_amd import _native as N
-from uav_airvision_amd.msckf_ops import BatchedMSCKF
+from uav_airvision_amd.msckf_ops import BatchedMSCKF, unpack_odom_cov
 
 _vio_result = namedtuple('vio_result', ['timestamp', 'pose', 'velocity', 'cam0_pose'])
 
@@ -96,7 +96,13 @@ class MSCKF(object):
     def __init__(self, config, device=0, rows_cap=None, write_trajectory=True):
         self.config = config
         self.optimization_config = config.optimization_config
-        self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap)
+        # config.publish_covariance = True (no reference counterpart; default off): `last_covariance` holds the 15 x 15 odometry
+        # covariance (p, theta, v, p_c, theta_c; include/airvision.h) of the last published result.  vio_result is unchanged.
+        self._cov_on = bool(getattr(config, 'publish_covariance', False))
+        self.last_covariance = None
+        if self._cov_on and not np.array_equal(np.asarray(config.T_imu_body, dtype=np.float64), np.identity(4)):
+            raise ValueError('config.publish_covariance needs config.T_imu_body = identity: the covariance is not conjugated into a body frame')
+        self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap, odom_cov=self._cov_on)
         self.state_server = StateServer(self._flt)
         self.map_server = _MapView(self._flt)
         # class-level statics the reference sets in its constructor (msckf.py:128-150), kept for code that reads them
@@ -142,7 +148,9 @@ class MSCKF(object):
         if n:
             ids[0, :n] = [f.id for f in feats]
             uv[0, :n] = [(f.u0, f.v0, f.u1, f.v1) for f in feats]
-        out = self._flt.step(ids, uv, [n], [feature_msg.timestamp])
+        out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None)
+        if self._cov_on and out[0, 0] == 1.0:
+            self.last_covariance = unpack_odom_cov(self._flt.last_cov[0])
         if self._capture:
             ups = []
             for phase in (0, 1):

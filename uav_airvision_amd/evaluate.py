@@ -76,3 +76,31 @@ def rte(est, ref, delta=10, max_dt=0.01):
     dQ = Q[delta:] - Q[:-delta]
     e = np.linalg.norm(dP - dQ, axis=1)
     return dict(rmse=float(np.sqrt((e ** 2).mean())), mean=float(e.mean()), std=float(e.std()), n=int(len(e)))
+
+
+def nees(est, cov_pos, ref, align=True, max_dt=0.01):
+    """Normalised estimation error squared of the position: per pose e^T Sigma^-1 e, e = the position error after the ATE alignment
+    (umeyama_se3 of the estimated positions onto the reference), Sigma = the pose's 3 x 3 position covariance rotated by the same
+    alignment (R Sigma R^T).  A consistent estimator gives a mean of 3 (chi-square, 3 degrees of freedom).
+    est, ref: float[n, 3] matched positions, or float[n, >= 4] with columns t, px, py, pz (associated by timestamp as in `ate`);
+    cov_pos: float[n, 3, 3], one per row of est.  align=False: both are in the same frame already.
+    Returns (per_pose float[m], mean); poses whose covariance is not finite or not positive definite are left out (the filter's first
+    pose is published with the initial covariance, whose position block is exactly zero)."""
+    est, ref, cov_pos = np.asarray(est, dtype=np.float64), np.asarray(ref, dtype=np.float64), np.asarray(cov_pos, dtype=np.float64)
+    if est.shape[1] >= 4:
+        ie, ir = associate(est[:, 0], ref[:, 0], max_dt)
+        P, Q, Sg = est[ie, 1:4], ref[ir, 1:4], cov_pos[ie]
+    else:
+        P, Q, Sg = est, ref, cov_pos
+    ok = np.isfinite(Sg).all(axis=(1, 2)) & np.isfinite(P).all(axis=1)
+    ok[ok] = np.linalg.eigvalsh(0.5 * (Sg[ok] + np.swapaxes(Sg[ok], 1, 2)))[:, 0] > 0
+    P, Q, Sg = P[ok], Q[ok], Sg[ok]
+    if len(P) < 3:
+        raise ValueError('fewer than 3 poses with a covariance')
+    if align:
+        R, t = umeyama_se3(P, Q)
+        P = P @ R.T + t
+        Sg = R @ Sg @ R.T
+    e = P - Q
+    per = np.einsum('ni,ni->n', e, np.linalg.solve(Sg, e[:, :, None])[:, :, 0])
+    return per, float(per.mean())

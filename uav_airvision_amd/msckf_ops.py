@@ -269,19 +269,46 @@ class MsckfDevice(object):
         return dx
 
 
+# ---- odometry covariance (include/airvision.h, "Odometry covariance") --------------------------------------------------------
+ODOM_COV_DIM = 15
+ODOM_COV_DOUBLES = 120             # AV_ODOM_COV_DOUBLES: the upper triangle of the 15 x 15 record, row-major
+# error coordinates of the record, in order: (name, slice)
+ODOM_COV_FIELDS = (('p', slice(0, 3)), ('theta', slice(3, 6)), ('v', slice(6, 9)), ('p_c', slice(9, 12)), ('theta_c', slice(12, 15)))
+_ODOM_IU = np.triu_indices(ODOM_COV_DIM)
+
+
+def unpack_odom_cov(a):
+    """float64[..., 120] records as a step returns them -> exactly symmetric float64[..., 15, 15] (NaN records stay NaN)."""
+    a = np.asarray(a, dtype=np.float64)
+    assert a.shape[-1] == ODOM_COV_DOUBLES, a.shape
+    C_ = np.empty(a.shape[:-1] + (ODOM_COV_DIM, ODOM_COV_DIM))
+    C_[..., _ODOM_IU[0], _ODOM_IU[1]] = a
+    C_[..., _ODOM_IU[1], _ODOM_IU[0]] = a
+    return C_
+
+
+def pack_odom_cov(Cm):
+    """float64[..., 15, 15] -> the wire form float64[..., 120] (the upper triangle, row-major)."""
+    Cm = np.asarray(Cm, dtype=np.float64)
+    assert Cm.shape[-2:] == (ODOM_COV_DIM, ODOM_COV_DIM), Cm.shape
+    return np.ascontiguousarray(Cm[..., _ODOM_IU[0], _ODOM_IU[1]])
+
+
 class BatchedMSCKF(object):
     """S independent filters stepped together (av_msckf_batch_* C ABI): C++ bookkeeping inside the
     library, one batched launch per numeric phase.  Mirrors MSCKF.imu_callback / feature_callback
     (reference: src/msckf.py:162-228) for many streams at once."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False):
         """rows_cap: rows of the per-stream block buffer.  None = sized by the library from the capacity of the first
         feature message (the camera-pruning update stacks 5 rows per feature, the lost-feature update at most 1500 + one
         block); `max_features`, when given, sizes it up front instead.  With the automatic size a later step with a wider
         `ids.shape[1]` REBUILDS the block buffers and the device-resident observation store for the wider message (drains the
         batch, synchronises the device, grows by at least x1.5, keeps the outgrown allocations until close) -- pass
         max_features when the width of the feature arrays can vary.  An explicit rows_cap is never grown.
-        config.max_cam_state_size <= 24 (reference: 20)."""
+        config.max_cam_state_size <= 24 (reference: 20).
+        odom_cov=True: every step also computes the covariance of what it publishes (ODOM_COV_FIELDS; `step / submit / submit_dev(...,
+        cov=)`, `last_cov`, `unpack_odom_cov`).  Device-resident filter only."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -304,6 +331,34 @@ class BatchedMSCKF(object):
                 float(config.observation_noise), float(config.position_std_threshold), _d(config.velocity),
                 _d([o.huber_epsilon, o.estimation_precision, o.initial_damping, o.outer_loop_max_iteration, o.inner_loop_max_iteration, o.translation_threshold]),
                 self.device, C.byref(self._h)))
+            self.odom_cov = bool(odom_cov)
+            self.last_cov = None           # the records array of the most recent step that was given one (float64[S, 120])
+            if self.odom_cov:
+                try:
+                    N.check(N.lib().av_msckf_batch_set_odom_cov(self._h, 1))
+                except Exception:
+                    self.close()
+                    raise
+
+    def set_odom_cov(self, enable):
+        """av_msckf_batch_set_odom_cov: before the first step only."""
+        N.check(N.lib().av_msckf_batch_set_odom_cov(self._h, 1 if enable else 0))
+        self.odom_cov = bool(enable)
+
+    def _next_cov(self, cov):
+        """The records array of the next step (None: the step has none), handed to the library.  cov: None, True (allocate) or a
+        C-contiguous float64[S, 120] array."""
+        if cov is None or cov is False:
+            return None
+        if not self.odom_cov:
+            raise ValueError('cov= needs BatchedMSCKF(..., odom_cov=True)')
+        if cov is True:
+            cov = np.full((self.S, ODOM_COV_DOUBLES), np.nan)
+        if not (isinstance(cov, np.ndarray) and cov.dtype == np.float64 and cov.shape == (self.S, ODOM_COV_DOUBLES) and cov.flags['C_CONTIGUOUS']):
+            raise ValueError('cov must be a C-contiguous float64[%d, %d] array' % (self.S, ODOM_COV_DOUBLES))
+        N.check(N.lib().av_msckf_batch_next_odom_cov(self._h, cov.ctypes.data_as(C.c_void_p)))
+        self.last_cov = cov
+        return cov
 
     def close(self):
         if self._h:
@@ -327,56 +382,61 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_push_imu(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                 g.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), len(si)))
 
-    def step(self, ids, uv, n_feat, timestamps):
+    def step(self, ids, uv, n_feat, timestamps, cov=None):
         """ids int64[S,cap], uv float64[S,cap,4], n_feat int32[S], timestamps float64[S] (host arrays).
-        Returns float64[S,12]: published, t, p(3), q(4), v(3)."""
+        Returns float64[S,12]: published, t, p(3), q(4), v(3).  cov (odom_cov=True): a float64[S,120] array that takes the step's
+        odometry-covariance records, or True to have one allocated; it is `last_cov` afterwards."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         cap = ids.shape[1]
         out = np.zeros((self.S, 12))
+        cov = self._next_cov(cov)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_step(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                 nf.ctypes.data_as(C.c_void_p), cap, ts.ctypes.data_as(C.c_void_p),
                                                 out.ctypes.data_as(C.c_void_p), N.current_stream()))
         return out
 
-    def submit(self, ids, uv, n_feat, timestamps):
+    def submit(self, ids, uv, n_feat, timestamps, cov=None):
         """Queue one step (av_msckf_batch_submit) and return its float64[S,12] output array, which is filled once the
         step has retired -- i.e. after a `wait(k)` that leaves fewer than the steps submitted after it pending.  The
-        stream groups of the batch run behind their queues independently of each other."""
+        stream groups of the batch run behind their queues independently of each other.  cov: as in `step`; the array (`last_cov`) is
+        filled when the step retires, like the output array."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         out = np.zeros((self.S, 12))
+        cov = self._next_cov(cov)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_submit(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                   nf.ctypes.data_as(C.c_void_p), ids.shape[1], ts.ctypes.data_as(C.c_void_p),
                                                   out.ctypes.data_as(C.c_void_p), N.current_stream()))
-        self._inflight.append((ids, uv, nf, ts, out))          # the library reads / writes these until the step retires
+        self._inflight.append((ids, uv, nf, ts, out, cov))     # the library reads / writes these until the step retires
         return out
 
     def device_resident(self):
         """True when the filter state and the observation map live on the device (the default; `submit_dev` needs it)."""
         return N.lib().av_msckf_batch_device_resident(self._h) == 1
 
-    def submit_dev(self, engine, timestamps, msg_stream=None):
+    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None):
         """Queue one step on the feature message `engine` (a FrontendEngine with the same streams) has just published, read
         where it lies on the device (av_msckf_batch_submit_dev): no host round trip between the front-end and the filter.
         msg_stream: the stream handle the engine's step ran on (default: torch's current stream, i.e. call this right after
         `engine.step` on the same stream).  The filter's kernels run on the current stream / the stream groups' own streams.
-        Returns the float64[S,12] output array, filled once a `wait` has let the step retire."""
+        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov: as in `submit`."""
         ids, uv, n, cap = engine.features_dev()
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         assert ts.shape == (self.S,) and engine.n_streams == self.S
         out = np.zeros((self.S, 12))
+        cov = self._next_cov(cov)
         with torch.cuda.device(self.device):
             ms = N.current_stream() if msg_stream is None else msg_stream
             N.check(N.lib().av_msckf_batch_submit_dev(self._h, ids, uv, n, cap, ts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
                                                       ms, N.current_stream()))
-        self._inflight.append((ts, out))
+        self._inflight.append((ts, out, cov))
         return out
 
     def wait(self, max_pending=0):

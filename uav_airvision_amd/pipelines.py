@@ -188,13 +188,17 @@ class _OutView(object):
 
 class FilterSet(object):
     """One BatchedMSCKF per part of an EngineSet, driven by the same workers (a part's front-end step, its prestage and its filter
-    hand-over stay in order on the part's thread)."""
+    hand-over stay in order on the part's thread).  Keywords go to every part's BatchedMSCKF: odom_cov=True switches the odometry
+    covariance on, `submit_dev(..., cov=True)` then gives every part a records array and `last_cov` joins them ([S, 120] once the
+    step has retired), as the returned view joins the poses."""
 
     def __init__(self, config, engine_set, device=0, **kw):
         from .msckf_ops import BatchedMSCKF
         self.es = engine_set
         self.parts = engine_set.parts
         self.flts = [BatchedMSCKF(config, hi - lo, device=device, **kw) for lo, hi in self.parts]
+        self.odom_cov = bool(kw.get('odom_cov', False))
+        self.last_cov = None
 
     def device_resident(self):
         return all(f.device_resident() for f in self.flts)
@@ -204,16 +208,25 @@ class FilterSet(object):
             if len(rows[0]):
                 self.es.pipes[p].put(lambda f=self.flts[p], r=rows: f.push_imu(*r))
 
-    def submit_dev(self, engine_set, timestamps, msg_stream=None):
+    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None):
         assert engine_set is self.es
+        if cov is not None and cov is not True:
+            raise ValueError('FilterSet.submit_dev: cov is None or True (every part allocates its own records array)')
+        if cov and not self.odom_cov:
+            raise ValueError('cov= needs FilterSet(..., odom_cov=True)')
         ts = np.asarray(timestamps, dtype=np.float64)
         out = _OutView(len(self.parts))
+        covs = _OutView(len(self.parts)) if cov else None
+        if cov:
+            self.last_cov = covs
         for p, (lo, hi) in enumerate(self.parts):
             def job(p=p, t=np.ascontiguousarray(ts[lo:hi])):
                 w = self.es.pipes[p]
                 ms = N.current_stream()                      # the part's front-end stream: the message is copied behind its step
                 with torch.cuda.stream(w.fstream):
-                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms)
+                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, cov=cov)
+                    if cov:
+                        covs.parts[p] = self.flts[p].last_cov
             self.es.pipes[p].put(job)
         return out
 

@@ -56,14 +56,18 @@ class BatchedRunner(object):
     trajectory per stream in the reference's output-line layout (msckf.py:152-158: t = imu_state.timestamp).
     `on_step(step, timestamps, ids, uv, n_feat, out)` -- optional, called once per step with the published feature
     arrays of the front-end and the filter's float64[k, 12] output of the same step (parity tests); without it the
-    filter runs one step behind the front-end (queued), the way bench.py pipelines them."""
+    filter runs one step behind the front-end (queued), the way bench.py pipelines them.
+    odom_cov=True: every step also brings the odometry covariance of what it publishes (BatchedMSCKF(odom_cov=True)); after `run`,
+    `cov_rows[s]` is float64[n, 121], one row `t` + the 120-double record per row of stream s's trajectory."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False):
         from .frontend import FrontendEngine
         from .msckf_ops import BatchedMSCKF
         self.config, self.S, self.device = config, int(n_streams), int(device)
         self.eng = FrontendEngine(config, n_streams=self.S, device=self.device)
-        self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features)
+        self.odom_cov = bool(odom_cov)
+        self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features, odom_cov=self.odom_cov)
+        self.cov_rows = None
         self.frames_done = np.zeros(self.S, np.int64)
         self._fstream = None
         self.plan, self.steps_done, self.times = None, 0, None
@@ -122,9 +126,14 @@ class BatchedRunner(object):
         inflight = []                                     # outputs of submitted steps that have not been recorded yet
         dev = flt.device_resident()
 
-        def record(out):
+        covs = [[] for _ in range(S)]
+        want = True if self.odom_cov else None
+
+        def record(out, cov=None):
             for s in np.nonzero(out[:, 0] > 0.5)[0]:
                 traj[s].append(out[s, 1:9].copy())
+                if cov is not None:
+                    covs[s].append(np.concatenate([out[s, 1:2], cov[s]]))
 
         times, t_ref = self.times, getattr(eng, '_exposure_ref', None)
 
@@ -197,8 +206,8 @@ class BatchedRunner(object):
             if on_step is not None:
                 ids, uv, n = eng.read_features_raw()
                 n[ts_f < 0] = 0
-                out = flt.step(ids, uv, n, ts_f)
-                record(out)
+                out = flt.step(ids, uv, n, ts_f, cov=want)
+                record(out, flt.last_cov)
                 on_step(step, ts_f, ids, uv, n, out)
             elif dev:
                 # the filter reads the published message where it lies on the device; nothing of this step is waited for here:
@@ -210,28 +219,30 @@ class BatchedRunner(object):
                     self._fstream = torch.cuda.Stream(device=self.device)
                 ms = N.current_stream()                   # the stream the front-end's step was enqueued on
                 with torch.cuda.stream(self._fstream):    # the filter's kernels (one group: here) overlap the next frame's front-end
-                    inflight.append(flt.submit_dev(eng, ts_f, msg_stream=ms))
+                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want), flt.last_cov))
                 flt.wait(2)
                 while len(inflight) > 2:
-                    record(inflight.pop(0))
+                    record(*inflight.pop(0))
             else:
                 eng.read_features_begin(step & 1)
                 ids, uv, n = eng.read_features_end(step & 1)
                 n[ts_f < 0] = 0
-                inflight.append(flt.submit(ids, uv, n, ts_f))
+                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want), flt.last_cov))
                 flt.wait(1)                               # at most one step behind: the next frames are decoded meanwhile
                 while len(inflight) > 1:
-                    record(inflight.pop(0))
+                    record(*inflight.pop(0))
             step += 1
         flt.wait(0)
-        for out in inflight:
-            record(out)
+        for pair in inflight:
+            record(*pair)
         self.steps_done = step
+        self.cov_rows = [np.array(c, dtype=np.float64).reshape(-1, 121) for c in covs] if self.odom_cov else None
         return [np.array(t, dtype=np.float64).reshape(-1, 8) for t in traj]
 
 
-def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None):
+def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None):
     """Open (path, offset) pairs as EuRoC datasets and run them as one batch; returns (trajectories, datasets).
+    cov_rows (a list): the batch runs with the odometry covariance on and the list receives, per stream, float64[n, 121] rows `t` + record.
     stats (a dict) receives the batch's stream-frames, steps, distinct frames decoded and the seconds its stepping loop took."""
     import time
     from .euroc import EuRoCDataset
@@ -240,10 +251,12 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
         ds = EuRoCDataset(p)
         ds.set_starttime(o)
         dss.append(ds)
-    r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap)
+    r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap, odom_cov=cov_rows is not None)
     try:
         t0 = time.perf_counter()
         trajs = r.run(dss, max_frames=max_frames, on_step=on_step, share_frames=share_frames)
+        if cov_rows is not None:
+            cov_rows.extend(r.cov_rows)
         if stats is not None:
             stats['seconds'] = stats.get('seconds', 0.0) + time.perf_counter() - t0
             stats['stream_frames'] = stats.get('stream_frames', 0) + int(r.frames_done.sum())
@@ -293,6 +306,10 @@ def make_parser():
     ap.add_argument('--grid', nargs=3, type=int, default=None, metavar=('ROWS', 'COLS', 'MAX'), help='feature grid (default 4 5 5; 10 15 10 = the 1500-feature sweep)')
     ap.add_argument('--out', default='results/txts')
     ap.add_argument('--no-share-frames', action='store_true', help="round 4's per-stream staging instead of the shared frame store (A/B)")
+    ap.add_argument('--covariance', action='store_true',
+                    help='also write, next to every trajectory file, output_<sequence>_offset<o>_cov.txt: per published pose one line `t` + the 120 numbers of its '
+                         'odometry covariance (upper triangle of the 15 x 15 matrix over p, theta, v, p_c, theta_c; include/airvision.h); with ground truth the '
+                         'report gains anees_pos, the mean normalised position error squared (3 for a consistent filter)')
     ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
     ap.add_argument('--ransac-threshold', type=float, default=None, metavar='T', help='inlier error in pixels (config.ransac_threshold, default 3)')
     ap.add_argument('--clahe', action='store_true', help='equalise every frame (CLAHE) ahead of the pyramids, LK and FAST (config.use_clahe; off = the reference front-end)')
@@ -374,7 +391,8 @@ def main(argv=None):
     import torch.distributed as dist
     from . import shard
     from .config import ConfigEuRoC
-    from .evaluate import ate, format_state_line, rte
+    from .evaluate import ate, format_state_line, nees, rte
+    from .msckf_ops import unpack_odom_cov
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -399,7 +417,7 @@ def main(argv=None):
         ap.error('--root or --make-synthetic is required')
     jobs = shard.broadcast_object([(s, o) for s in args.sequences for o in args.offsets] if rank == 0 else None)
     mine = shard.partition(len(jobs), world, rank)
-    local_traj, report, stats = {}, {}, {}
+    local_traj, local_cov, report, stats = {}, {}, {}, {}
     import time
     if world > 1:
         dist.barrier()
@@ -407,23 +425,33 @@ def main(argv=None):
     for b0 in range(0, len(mine), args.batch):
         chunk = mine[b0:b0 + args.batch]
         cfg.image_format = batch_pixel_format([os.path.join(root, jobs[j][0]) for j in chunk], args.pixel_format)
+        cov_rows = [] if args.covariance else None
         trajs, dss = run_batched(cfg, [os.path.join(root, jobs[j][0]) for j in chunk], [jobs[j][1] for j in chunk], device=local, max_frames=args.max_frames,
-                                 share_frames=not args.no_share_frames, stats=stats)
-        for j, traj, ds in zip(chunk, trajs, dss):
+                                 share_frames=not args.no_share_frames, stats=stats, **({'cov_rows': cov_rows} if args.covariance else {}))
+        for i, (j, traj, ds) in enumerate(zip(chunk, trajs, dss)):
             local_traj[j] = traj
+            if cov_rows is not None:
+                local_cov[j] = cov_rows[i]
             gt = ds.groundtruth_array()
             if len(gt) and len(traj) > 20:
                 a, r = ate(traj, gt), rte(traj, gt)
                 report[j] = dict(sequence=jobs[j][0], offset=jobs[j][1], frames=len(traj), ate_rmse=a['rmse'], ate_mean=a['mean'], rte_rmse=r['rmse'])
+                if cov_rows is not None:
+                    report[j]['anees_pos'] = nees(traj, unpack_odom_cov(cov_rows[i][:, 1:])[:, 0:3, 0:3], gt)[1]
     elapsed = shard.max_over_ranks(time.perf_counter() - t_all)          # barrier before, max over ranks after: the bench contract's clock
     allt = shard.gather_trajectories(local_traj, len(jobs), world, rank)
-    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats})
+    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov})
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         for j, (seq, off) in enumerate(jobs):
             with open(os.path.join(args.out, 'output_%s_offset%d.txt' % (seq, int(off))), 'w') as f:
                 for row in allt[j]:
                     f.write(format_state_line(row[0], row[1:4], row[4:8]))
+        for r in per_rank if args.covariance else []:
+            for j, rows in r['cov'].items():
+                with open(os.path.join(args.out, 'output_%s_offset%d_cov.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
+                    for row in rows:
+                        f.write('%.6f ' % row[0] + ' '.join('%.9e' % v for v in row[1:]) + '\n')
         rep = sweep_report(jobs, per_rank, elapsed, world)
         if cfg.use_clahe:
             rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
