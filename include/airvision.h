@@ -1068,6 +1068,10 @@ int  av_msckf_batch_work(av_msckf_batch* b, int enable, double out8[8]);
  * Analytic per gated feature / per update (upd_stack_kernel), tile padding not counted.  No reference counterpart: bench.py's
  * roofline_msckf.executed. */
 int  av_msckf_batch_work_executed(av_msckf_batch* b, double out2[2]);
+/* Lifecycle-test entry (tests only; needs no GPU): what the objects of this process hold at this moment, out4 = [bytes of device memory,
+ * bytes of pinned host memory, events, streams].  Every acquisition and release of the library passes through these counts (the
+ * process-lifetime diagnostics behind AV_LK_PROF / AV_DEV_FPROF / AV_DEV_UPROF excepted): all four are zero once every object is destroyed. */
+int  av_debug_live_resources(int64_t out4[4]);
 
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart): when enabled, every
  * launch group of av_frontend_step is bracketed by a HIP event pair ON THE STEP'S STREAM.

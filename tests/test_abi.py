@@ -65,6 +65,17 @@ def test_host_only_entry_points_work_without_a_gpu():
     assert b'gfx950' in N.lib().av_version()
 
 
+def test_live_resource_counts_are_readable_without_a_gpu():
+    """av_debug_live_resources (tests only): declared, exported and bound like every other entry; nothing is alive in a process
+    that has created nothing."""
+    from uav_airvision_amd import _native as N
+    assert 'av_debug_live_resources' in _header_functions() and 'av_debug_live_resources' in N.SIGNATURES
+    out = (ctypes.c_int64 * 4)(-1, -1, -1, -1)
+    assert N.lib().av_debug_live_resources(ctypes.byref(out)) == 0
+    assert list(out) == [0, 0, 0, 0]
+    assert N.lib().av_debug_live_resources(None) == N.AV_E_INVALID
+
+
 def test_product_code_never_imports_the_oracle():
     pkg = os.path.join(ROOT, 'uav_airvision_amd')
     for base, _dirs, files in os.walk(pkg):

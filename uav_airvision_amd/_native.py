@@ -287,6 +287,7 @@ SIGNATURES = {
     'av_msckf_predict_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6),
     'av_msckf_batch_work': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 8)]),
     'av_msckf_batch_work_executed': (C.c_int, [_P, C.POINTER(C.c_double * 2)]),
+    'av_debug_live_resources': (C.c_int, [C.POINTER(C.c_int64 * 4)]),
     'av_msckf_batch_get_state': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 32), _P, _P, C.c_int, C.POINTER(C.c_int32)]),
     'av_msckf_batch_stream_status': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_int]),
     'av_frontend_read_ransac_counts': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 4), _P]),

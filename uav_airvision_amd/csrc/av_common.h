@@ -10,15 +10,7 @@
 #define AV_EXPORT extern "C" __attribute__((visibility("default")))
 
 // ---- error plumbing ---------------------------------------------------------------------------
-void av_set_error(const char* fmt, ...);
-#define AV_HIP(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            av_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return AV_E_HIP;                                                                      \
-        }                                                                                         \
-    } while (0)
+#include "av_resources.h"          // av_set_error, AV_HIP; the owner of device memory, pinned memory, events and streams
 #define AV_LAUNCH_CHECK()                                                                         \
     do {                                                                                          \
         hipError_t e_ = hipGetLastError();                                                        \

@@ -673,9 +673,9 @@ struct av_frontend {
         long long frames_uploaded = 0;
         std::vector<uint16_t> k;                 // AV_FE_EXPOSURE, host: [n_slots][2] the factors the frame in each entry was corrected with (0: none yet)
     } fs;
-    std::vector<void*> allocs;
+    AvResources res;                   // owns every device and pinned block, event and stream named in this structure
     double* dH = nullptr;
-    double* hH[8] = {nullptr}; hipEvent_t hH_ev[8]; int hH_slot = 0;
+    PinnedRing<double, 8> hH;          // the step's homographies (+ store maps, + AV_FE_RANSAC's rotations and frame numbers) on their way to dH
     int parity = 0;                    // index of the "prev" grid buffer; cam0 prev pyramid slot
     std::vector<StreamHost> streams;
     bool any_first = true;
@@ -715,7 +715,7 @@ struct av_frontend {
     // ex_slot_k [2][2][S] by cam0's pyramid slot (a prestaged frame's factors wait there for its step), ex_last [S][2] of every stream's last step
     bool expo = false, photo_tables = false, ex_pending = false;
     std::vector<uint16_t> ex_pend, ex_slot_k, ex_last; int ex_pend_n = 0;
-    uint16_t* ex_h[8] = {nullptr}; hipEvent_t ex_ev[8]; int ex_slot = 0; uint16_t* ex_d = nullptr;
+    PinnedRing<uint16_t, 8> ex_h; uint16_t* ex_d = nullptr;
     // av_frontend_set_gray16_scale ("Range scaling of 16-bit grey" in include/airvision.h): the settings, and for
     // AV_GRAY16_AUTO the step paths' histograms [S][4096] (zero between launches) and records [2][S][4] -- by cam0's pyramid slot, so
     // that a prestaged frame does not replace the records of the step before it (the frame store: FrameStore::range_d)
@@ -726,17 +726,6 @@ struct av_frontend {
 };
 
 namespace {
-
-template <typename T>
-int dev_alloc(av_frontend* fe, T** p, size_t count, int fill = 0)
-{
-    void* q = nullptr;
-    AV_HIP(hipMalloc(&q, count * sizeof(T) + 256));
-    AV_HIP(hipMemset(q, fill, count * sizeof(T) + 256));
-    fe->allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return AV_OK;
-}
 
 // Rpc (optional): [cam0_R_p_c, cam1_R_p_c] of imu_processor.py:56-65, 18 doubles
 int integrate_imu(av_frontend* fe, int s, double t_curr, double* H, double* Rpc = nullptr)
@@ -867,12 +856,13 @@ int input_stage(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64
     Span sp(fe, 0, st);
     const uint16_t* k0 = nullptr; const uint16_t* k1 = nullptr;
     if (fe->expo) {                          // the pending factors (the entry point has checked them) go to the device ahead of the stage, on this stream
-        const int S = d.S, slot = fe->ex_slot;
-        fe->ex_slot = (slot + 1) & 7;
-        AV_HIP(hipEventSynchronize(fe->ex_ev[slot]));
-        memcpy(fe->ex_h[slot], fe->ex_pend.data(), sizeof(uint16_t) * 2 * S);
-        AV_HIP(hipMemcpyAsync(fe->ex_d, fe->ex_h[slot], sizeof(uint16_t) * 2 * S, hipMemcpyHostToDevice, st));
-        AV_HIP(hipEventRecord(fe->ex_ev[slot], st));
+        const int S = d.S;
+        uint16_t* ex_h = nullptr;
+        int rc = fe->ex_h.take(&ex_h);
+        if (rc) return rc;
+        memcpy(ex_h, fe->ex_pend.data(), sizeof(uint16_t) * 2 * S);
+        AV_HIP(hipMemcpyAsync(fe->ex_d, ex_h, sizeof(uint16_t) * 2 * S, hipMemcpyHostToDevice, st));
+        if ((rc = fe->ex_h.sent(st))) return rc;
         memcpy(fe->ex_slot_k.data() + (size_t)cur * 2 * S, fe->ex_pend.data(), sizeof(uint16_t) * 2 * S);
         fe->ex_pending = false;
         k0 = fe->ex_d; k1 = fe->ex_d + S;
@@ -905,10 +895,9 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     const bool frames = slots != nullptr;
     AV_HIP(hipSetDevice(fe->device));
     // host: IMU rotation prediction -> homographies
-    const int slot = fe->hH_slot;
-    fe->hH_slot = (slot + 1) & 7;
-    AV_HIP(hipEventSynchronize(fe->hH_ev[slot]));
-    double* hH = fe->hH[slot];
+    int rc;
+    double* hH = nullptr;
+    if ((rc = fe->hH.take(&hH))) return rc;
     bool any_first = false;
     int* hmap = reinterpret_cast<int*>(hH + (size_t)9 * S);      // [2][S] behind the homographies: this frame's / the previous frame's store entry
     double* hR = hH + (size_t)10 * S;                            // AV_FE_RANSAC: [S][18] rotations, then [S] frame numbers
@@ -939,12 +928,11 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
     }
     if (fe->ransac) AV_HIP(hipMemcpyAsync(fe->dH, hH, sizeof(double) * 28 * S + sizeof(int) * S, hipMemcpyHostToDevice, st));
     else AV_HIP(hipMemcpyAsync(fe->dH, hH, sizeof(double) * 9 * S + (frames ? sizeof(int) * 2 * S : 0), hipMemcpyHostToDevice, st));
-    AV_HIP(hipEventRecord(fe->hH_ev[slot], st));
+    if ((rc = fe->hH.sent(st))) return rc;
     AV_HIP(hipMemsetAsync(fe->zero_region, 0, fe->zero_bytes, st));
 
     const int par = fe->parity;              // prev grid buffer / prev cam0 pyramid slot
     const int cur = par ^ 1;                 // curr cam0 pyramid slot (0/1), cam1 pyramid is slot 2
-    int rc;
     ImgView prev0, cur0, cur1;               // cam0 of the previous frame, cam0 and cam1 of this one
     if (frames) {
         // pyramids, level-0 images and FAST lists of both cameras lie in the store, built when the frame was uploaded
@@ -1068,7 +1056,7 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     AV_HIP(hipSetDevice(device));
     av_frontend* fe = new (std::nothrow) av_frontend(n_streams);
     if (!fe) { av_set_error("out of host memory"); return AV_E_INVALID; }
-    fe->cfg = *cfg; fe->device = device;
+    fe->cfg = *cfg; fe->device = fe->res.device = device;
     int rc = av_pyramid_layout(cfg->width, cfg->height, cfg->lk_levels, &fe->lay);
     if (rc) { delete fe; return rc; }
     fe->geom = av_make_geom(fe->lay);
@@ -1112,13 +1100,13 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     for (int i = 0; i < 9; ++i) { d.R0to1[i] = cfg->R0to1[i]; d.E[i] = cfg->E[i]; d.I3[i] = (i % 4 == 0) ? 1.0 : 0.0; }
     d.epi_thr = cfg->stereo_threshold * cfg->norm_unit;
 
-#define A(ptr, n) if ((rc = dev_alloc(fe, &(ptr), (size_t)(n)))) { av_frontend_destroy(fe); return rc; }
+#define A(ptr, n) if ((rc = fe->res.dev(&(ptr), (size_t)(n)))) { av_frontend_destroy(fe); return rc; }
     for (int b = 0; b < 2; ++b) {
         A(d.feat_id[b], S * d.MAXF) A(d.feat_life[b], S * d.MAXF) A(d.feat_p0[b], 2 * S * d.MAXF) A(d.feat_p1[b], 2 * S * d.MAXF)
         A(d.feat_cell[b], S * d.MAXF) A(d.n_feat[b], S)
     }
     A(d.next_id, S)
-    if ((rc = dev_alloc(fe, &d.first_frame, (size_t)S, 1))) { av_frontend_destroy(fe); return rc; }   // bytes 0x01 -> non-zero ints
+    if ((rc = fe->res.dev(&d.first_frame, (size_t)S, 1))) { av_frontend_destroy(fe); return rc; }   // bytes 0x01 -> non-zero ints
     A(fe->dH, 9 * S + S + (ransac ? 19 * S : 0))      // + [2][S] ints: the frame-store maps of the step (step_impl); AV_FE_RANSAC: + [S][18] rotations, [S] frame numbers
     d.Hmat = fe->dH;
     A(d.trk_prev, 2 * S * d.NT) A(d.trk_next, 2 * S * d.NT) A(d.trk_status, S * d.NT)
@@ -1132,7 +1120,7 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         av_frontend_destroy(fe); return AV_E_INVALID;
     }
     A(d.tile_kp, (size_t)S * d.n_tiles * d.tile_cap) A(d.tile_count, (size_t)S * d.n_tiles)
-    if ((rc = dev_alloc(fe, &d.mask, (size_t)S * w * h, 1))) { av_frontend_destroy(fe); return rc; }
+    if ((rc = fe->res.dev(&d.mask, (size_t)S * w * h, 1))) { av_frontend_destroy(fe); return rc; }
     A(d.cand_key, (size_t)S * d.CC) A(d.cand_p0, 2 * (size_t)S * d.CC) A(d.cand_init, 2 * (size_t)S * d.CC) A(d.cand_p1, 2 * (size_t)S * d.CC)
     A(d.cand_st, (size_t)S * d.CC) A(d.cand_back, 2 * (size_t)S * d.CC) A(d.cand_st2, (size_t)S * d.CC) A(d.cand_inl, (size_t)S * d.CC)
     A(d.cand_off, S * (C + 1))
@@ -1177,83 +1165,19 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         fe->clahe = true;
     }
 #undef A
-    for (int i = 0; i < 8; ++i) {
-        if (hipHostMalloc((void**)&fe->hH[i], sizeof(double) * (9 * S + S + (ransac ? 19 * S : 0)), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&fe->hH_ev[i], hipEventDisableTiming) != hipSuccess) {
-            av_set_error("av_frontend_create: pinned staging allocation failed");
-            av_frontend_destroy(fe);
-            return AV_E_HIP;
-        }
-    }
-    for (int i = 0; i < 8 && fe->expo; ++i) {
-        if (hipHostMalloc((void**)&fe->ex_h[i], sizeof(uint16_t) * 2 * S, hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&fe->ex_ev[i], hipEventDisableTiming) != hipSuccess) {
-            av_set_error("av_frontend_create: pinned staging allocation failed");
-            av_frontend_destroy(fe);
-            return AV_E_HIP;
-        }
-    }
-    for (int i = 0; i < 2; ++i) {
+    rc = fe->hH.create(fe->res, 9 * (size_t)S + S + (ransac ? 19 * (size_t)S : 0));
+    if (!rc && fe->expo) rc = fe->ex_h.create(fe->res, 2 * (size_t)S);
+    for (int i = 0; i < 2 && !rc; ++i) {
         av_frontend::ReadSlot& r = fe->rd[i];
-        if (hipHostMalloc((void**)&r.n, sizeof(int) * S, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&r.ids, sizeof(long long) * (size_t)S * d.MAXF, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&r.uv, sizeof(double) * 4 * (size_t)S * d.MAXF, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&r.cnt, sizeof(int) * (size_t)S * NCNT, hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess) {
-            av_set_error("av_frontend_create: pinned read-back staging allocation failed");
-            av_frontend_destroy(fe);
-            return AV_E_HIP;
-        }
+        if (!(rc = fe->res.pinned(&r.n, (size_t)S)) && !(rc = fe->res.pinned(&r.ids, (size_t)S * d.MAXF)) && !(rc = fe->res.pinned(&r.uv, 4 * (size_t)S * d.MAXF)) &&
+            !(rc = fe->res.pinned(&r.cnt, (size_t)S * NCNT))) rc = fe->res.event(&r.ev, hipEventDisableTiming);
     }
+    if (rc) { av_frontend_destroy(fe); return rc; }
     *out = fe;
     return AV_OK;
 }
 
-AV_EXPORT void av_frontend_destroy(av_frontend* fe)
-{
-    if (!fe) return;
-    (void)hipSetDevice(fe->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : fe->allocs) (void)hipFree(p);
-    for (hipEvent_t e : fe->ev) (void)hipEventDestroy(e);
-    for (int i = 0; i < 3; ++i) {
-        av_frontend::HostSlot& h = fe->hs[i];
-        if (h.pin) (void)hipHostFree(h.pin);
-        if (h.dev) (void)hipFree(h.dev);
-        if (h.copied) (void)hipEventDestroy(h.copied);
-        if (h.consumed) (void)hipEventDestroy(h.consumed);
-    }
-    for (av_frontend::FrameStore::Up& u : fe->fs.up) {
-        if (u.pin) (void)hipHostFree(u.pin);
-        if (u.idx_h) (void)hipHostFree(u.idx_h);
-        if (u.idx_d) (void)hipFree(u.idx_d);
-        if (u.raw_d) (void)hipFree(u.raw_d);
-        if (u.k_h) (void)hipHostFree(u.k_h);
-        if (u.k_d) (void)hipFree(u.k_d);
-        if (u.done) (void)hipEventDestroy(u.done);
-    }
-    if (fe->fs.gray_d) (void)hipFree(fe->fs.gray_d);
-    if (fe->fs.mosaic_d) (void)hipFree(fe->fs.mosaic_d);
-    if (fe->fs.range_d) (void)hipFree(fe->fs.range_d);
-    if (fe->fs.uploaded) (void)hipEventDestroy(fe->fs.uploaded);
-    if (fe->fs.stepped) (void)hipEventDestroy(fe->fs.stepped);
-    if (fe->copy_stream) (void)hipStreamDestroy(fe->copy_stream);
-    for (int i = 0; i < 8; ++i) {
-        if (fe->hH[i]) { (void)hipHostFree(fe->hH[i]); (void)hipEventDestroy(fe->hH_ev[i]); }
-    }
-    for (int i = 0; i < 8; ++i) {
-        if (fe->ex_h[i]) { (void)hipHostFree(fe->ex_h[i]); (void)hipEventDestroy(fe->ex_ev[i]); }
-    }
-    for (int i = 0; i < 2; ++i) {
-        av_frontend::ReadSlot& r = fe->rd[i];
-        if (r.n) (void)hipHostFree(r.n);
-        if (r.ids) (void)hipHostFree(r.ids);
-        if (r.uv) (void)hipHostFree(r.uv);
-        if (r.cnt) (void)hipHostFree(r.cnt);
-        if (r.ev) (void)hipEventDestroy(r.ev);
-    }
-    delete fe;
-}
+AV_EXPORT void av_frontend_destroy(av_frontend* fe) { delete fe; }      // (~AvResources waits for the device and releases)
 
 AV_EXPORT int av_frontend_push_imu(av_frontend* fe, int stream, double timestamp, const double gyro[3])
 {
@@ -1358,12 +1282,11 @@ AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, c
     AV_HIP(hipSetDevice(fe->device));
     av_frontend::HostSlot& h = fe->hs[fe->hs_next];
     fe->hs_next = (fe->hs_next + 1) % 3;
-    if (!fe->copy_stream) AV_HIP(hipStreamCreateWithFlags(&fe->copy_stream, hipStreamNonBlocking));
-    if (!h.pin) {
-        AV_HIP(hipHostMalloc((void**)&h.pin, 2 * img_bytes * S, hipHostMallocDefault));
-        AV_HIP(hipMalloc((void**)&h.dev, 2 * img_bytes * S));
-        AV_HIP(hipEventCreateWithFlags(&h.copied, hipEventDisableTiming));
-        AV_HIP(hipEventCreateWithFlags(&h.consumed, hipEventDisableTiming));
+    int rc0;
+    if (!fe->copy_stream && (rc0 = fe->res.stream(&fe->copy_stream, hipStreamNonBlocking, 0))) return rc0;
+    if (!h.consumed) {                       // (the last of the four: a slot whose set-up failed halfway is set up again, what it got before stays with the owner)
+        if ((rc0 = fe->res.pinned_bytes(&h.pin, 2 * img_bytes * S)) || (rc0 = fe->res.dev_bytes(&h.dev, 2 * img_bytes * S)) ||
+            (rc0 = fe->res.event(&h.copied, hipEventDisableTiming)) || (rc0 = fe->res.event(&h.consumed, hipEventDisableTiming))) return rc0;
     }
     // the slot was filled three calls ago and last read two calls ago (as that step's previous cam0 image): wait for the
     // step recorded after it -- every earlier step on the stream has then retired too
@@ -1381,7 +1304,7 @@ AV_EXPORT int av_frontend_step_host(av_frontend* fe, const uint8_t* img0_host, c
     if (rc) return rc;
     // `consumed` of the slot filled ONE call ago is recorded now: this step was the last reader of its cam0 image
     av_frontend::HostSlot& hp = fe->hs[(fe->hs_next + 1) % 3];
-    if (hp.pin) { AV_HIP(hipEventRecord(hp.consumed, st)); hp.used = true; }
+    if (hp.consumed) { AV_HIP(hipEventRecord(hp.consumed, st)); hp.used = true; }
     AV_HIP(hipEventRecord(h.consumed, st));
     h.used = true;
     return AV_OK;
@@ -1401,12 +1324,11 @@ AV_EXPORT int av_frontend_frames_reserve(av_frontend* fe, int n_slots)
     const FeDev& d = fe->d;
     const size_t hw = (size_t)d.w * d.h;
     int rc;
-    if ((rc = dev_alloc(fe, &fs.img, (size_t)n_slots * 2 * hw)) || (rc = dev_alloc(fe, &fs.pyr, (size_t)n_slots * 2 * fe->lay.bytes)) ||
-        (rc = dev_alloc(fe, &fs.tile_kp, (size_t)n_slots * d.n_tiles * d.tile_cap)) || (rc = dev_alloc(fe, &fs.tile_count, (size_t)n_slots * d.n_tiles))) return rc;
-    if (fe->clahe && (rc = dev_alloc(fe, &fe->fs_lut, (size_t)n_slots * 2 * fe->cfg.clahe_tiles_x * fe->cfg.clahe_tiles_y * 256))) return rc;
-    AV_HIP(hipEventCreateWithFlags(&fs.uploaded, hipEventDisableTiming));
-    AV_HIP(hipEventCreateWithFlags(&fs.stepped, hipEventDisableTiming));
-    if (!fe->copy_stream) AV_HIP(hipStreamCreateWithFlags(&fe->copy_stream, hipStreamNonBlocking));
+    if ((rc = fe->res.dev(&fs.img, (size_t)n_slots * 2 * hw)) || (rc = fe->res.dev(&fs.pyr, (size_t)n_slots * 2 * fe->lay.bytes)) ||
+        (rc = fe->res.dev(&fs.tile_kp, (size_t)n_slots * d.n_tiles * d.tile_cap)) || (rc = fe->res.dev(&fs.tile_count, (size_t)n_slots * d.n_tiles))) return rc;
+    if (fe->clahe && (rc = fe->res.dev(&fe->fs_lut, (size_t)n_slots * 2 * fe->cfg.clahe_tiles_x * fe->cfg.clahe_tiles_y * 256))) return rc;
+    if ((rc = fe->res.event(&fs.uploaded, hipEventDisableTiming)) || (rc = fe->res.event(&fs.stepped, hipEventDisableTiming))) return rc;
+    if (!fe->copy_stream && (rc = fe->res.stream(&fe->copy_stream, hipStreamNonBlocking, 0))) return rc;
     fs.prev.assign((size_t)d.S, -1);
     if (fe->expo) fs.k.assign((size_t)2 * n_slots, 0);
     fs.n_slots = n_slots;
@@ -1446,40 +1368,25 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     av_frontend::FrameStore::Up& u = fs.up[fs.up_next];
     fs.up_next = (fs.up_next + 1) % 4;
     if (u.used) AV_HIP(hipEventSynchronize(u.done));                // the staging area's previous upload has left it
+    AvResources& res = fe->res;
+    int rc;
     if ((size_t)n > u.cap) {
-        if (u.pin) { (void)hipHostFree(u.pin); (void)hipHostFree(u.idx_h); (void)hipFree(u.idx_d); u.pin = nullptr; u.idx_h = nullptr; u.idx_d = nullptr; }
-        if (u.raw_d) { (void)hipFree(u.raw_d); u.raw_d = nullptr; }
-        if (u.k_h) { (void)hipHostFree(u.k_h); (void)hipFree(u.k_d); u.k_h = nullptr; u.k_d = nullptr; }
+        u.cap = 0;                   // (a failure below leaves the entry empty: the next upload builds it again)
+        res.free_pinned(u.pin); res.free_pinned(u.idx_h); res.free_dev(u.idx_d); res.free_dev(u.raw_d); res.free_pinned(u.k_h); res.free_dev(u.k_d);
         const size_t cap = (size_t)n + 16;
-        AV_HIP(hipHostMalloc((void**)&u.pin, cap * 2 * fb, hipHostMallocDefault));
-        AV_HIP(hipHostMalloc((void**)&u.idx_h, (raw ? 2 : 1) * cap * sizeof(int), hipHostMallocDefault));
-        AV_HIP(hipMalloc((void**)&u.idx_d, (raw ? 2 : 1) * cap * sizeof(int)));
-        if (raw) AV_HIP(hipMalloc((void**)&u.raw_d, cap * 2 * fb));
-        if (fe->expo) {
-            AV_HIP(hipHostMalloc((void**)&u.k_h, cap * 2 * sizeof(uint16_t), hipHostMallocDefault));
-            AV_HIP(hipMalloc((void**)&u.k_d, cap * 2 * sizeof(uint16_t)));
-        }
-        if (!u.done) AV_HIP(hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
+        if ((rc = res.pinned_bytes(&u.pin, cap * 2 * fb)) || (rc = res.pinned_bytes(&u.idx_h, (raw ? 2 : 1) * cap * sizeof(int))) ||
+            (rc = res.dev_bytes(&u.idx_d, (raw ? 2 : 1) * cap * sizeof(int))) || (raw && (rc = res.dev_bytes(&u.raw_d, cap * 2 * fb))) ||
+            (fe->expo && ((rc = res.pinned_bytes(&u.k_h, cap * 2 * sizeof(uint16_t))) || (rc = res.dev_bytes(&u.k_d, cap * 2 * sizeof(uint16_t))))) ||
+            (!u.done && (rc = res.event(&u.done, hipEventDisableTiming)))) return rc;
         u.cap = cap;
     }
-    // grows only.  Earlier uploads' launches on the copy stream may still read the old scratch, so the copy stream is drained before it is
-    // freed: the caller stalls once per growth (an upload larger than any before it), never otherwise
-    if ((conv || fe->photo) && bin && (size_t)n > fs.gray_cap) {
-        if (fs.gray_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.gray_d); fs.gray_d = nullptr; fs.gray_cap = 0; }
-        AV_HIP(hipMalloc((void**)&fs.gray_d, ((size_t)n + 16) * 2 * in_hw));
-        fs.gray_cap = (size_t)n + 16;
-    }
-    if (fe->mosaic && (size_t)n > fs.mosaic_cap) {                  // a packed mosaic format: the same rule for the store's mosaic scratch
-        if (fs.mosaic_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.mosaic_d); fs.mosaic_d = nullptr; fs.mosaic_cap = 0; }
-        AV_HIP(hipMalloc((void**)&fs.mosaic_d, ((size_t)n + 16) * 2 * in_hw));
-        fs.mosaic_cap = (size_t)n + 16;
-    }
-    if (fe->g16.mode == AV_GRAY16_AUTO && (size_t)n > fs.range_cap) {      // the same rule for the store's histograms and records; zeroed once, on the copy stream
-        if (fs.range_d) { AV_HIP(hipStreamSynchronize(fe->copy_stream)); (void)hipFree(fs.range_d); fs.range_d = nullptr; fs.range_cap = 0; }
-        const size_t cap = (size_t)n + 16;
-        AV_HIP(hipMalloc((void**)&fs.range_d, cap * AV_GRAY16_WORK_WORDS * sizeof(uint32_t)));
-        AV_HIP(hipMemsetAsync(fs.range_d, 0, cap * AV_GRAY16_WORK_WORDS * sizeof(uint32_t), fe->copy_stream));
-        fs.range_cap = cap;
+    // The store's scratches follow AvResources::regrow: earlier uploads' launches on the copy stream may still read the old block, so the
+    // caller stalls once per growth (an upload larger than any before it), never otherwise
+    if ((conv || fe->photo) && bin && (rc = res.regrow(&fs.gray_d, &fs.gray_cap, (size_t)n, 2 * in_hw, fe->copy_stream))) return rc;
+    if (fe->mosaic && (rc = res.regrow(&fs.mosaic_d, &fs.mosaic_cap, (size_t)n, 2 * in_hw, fe->copy_stream))) return rc;      // a packed mosaic format
+    if (fe->g16.mode == AV_GRAY16_AUTO && (size_t)n > fs.range_cap) {      // the histograms and records; zeroed once, on the copy stream
+        if ((rc = res.regrow(&fs.range_d, &fs.range_cap, (size_t)n, AV_GRAY16_WORK_WORDS * sizeof(uint32_t), fe->copy_stream))) return rc;
+        AV_HIP(hipMemsetAsync(fs.range_d, 0, fs.range_cap * AV_GRAY16_WORK_WORDS * sizeof(uint32_t), fe->copy_stream));
     }
 #pragma omp parallel for schedule(static) num_threads(n >= 8 ? 8 : 1)
     for (int i = 0; i < 2 * n; ++i) {
@@ -1497,7 +1404,6 @@ AV_EXPORT int av_frontend_frames_upload(av_frontend* fe, const int32_t* slots, i
     // and run beside whatever the caller enqueues next -- upload the frames of step k + 1 before enqueueing step k and the two overlap.
     if (fs.any_step) AV_HIP(hipStreamWaitEvent(cs, fs.stepped, 0));
     AV_HIP(hipMemcpyAsync(u.idx_d, u.idx_h, sizeof(int) * (raw ? 2 : 1) * n, hipMemcpyHostToDevice, cs));
-    int rc;
     if (fe->expo) {                  // the upload's factors travel with it: [2][n] by position; an entry keeps those of the last frame that names it
         memcpy(u.k_h, fe->ex_pend.data(), sizeof(uint16_t) * 2 * n);
         AV_HIP(hipMemcpyAsync(u.k_d, u.k_h, sizeof(uint16_t) * 2 * n, hipMemcpyHostToDevice, cs));
@@ -1712,7 +1618,7 @@ AV_EXPORT int av_frontend_set_gray16_scale(av_frontend* fe, int scale, int lo, i
     if (scale == AV_GRAY16_AUTO && !fe->g16_rec) {      // histograms [S][4096] and records [2][S][4], zeroed; once per engine
         AV_HIP(hipSetDevice(fe->device));
         int rc;
-        if ((rc = dev_alloc(fe, &fe->g16_hist, (size_t)fe->d.S * 4096)) || (rc = dev_alloc(fe, &fe->g16_rec, (size_t)2 * fe->d.S * 4))) return rc;
+        if ((rc = fe->res.dev(&fe->g16_hist, (size_t)fe->d.S * 4096)) || (rc = fe->res.dev(&fe->g16_rec, (size_t)2 * fe->d.S * 4))) return rc;
     }
     fe->g16.mode = scale; fe->g16.lo = lo; fe->g16.hi = hi; fe->g16.ppm_lo = clip_lo_ppm; fe->g16.ppm_hi = clip_hi_ppm; fe->g16.min_span = min_span;
     return AV_OK;
@@ -1764,7 +1670,7 @@ AV_EXPORT int av_frontend_set_masks(av_frontend* fe, const uint8_t* mask0_host, 
                 bin[(size_t)y * d.w + x] = v;
             }
         int rc;
-        if (!fe->smask_buf[cam] && (rc = dev_alloc(fe, &fe->smask_buf[cam], hw))) return rc;
+        if (!fe->smask_buf[cam] && (rc = fe->res.dev(&fe->smask_buf[cam], hw))) return rc;
         AV_HIP(hipMemcpy(fe->smask_buf[cam], bin.data(), hw, hipMemcpyHostToDevice));
         set[cam] = fe->smask_buf[cam];
     }
@@ -1821,7 +1727,7 @@ AV_EXPORT int av_frontend_set_photometric(av_frontend* fe, const uint16_t* respo
         }
         if (gain[cam]) {
             int rc;
-            if (!fe->ph_gain_buf[cam] && (rc = dev_alloc(fe, &fe->ph_gain_buf[cam], in_hw))) return rc;
+            if (!fe->ph_gain_buf[cam] && (rc = fe->res.dev(&fe->ph_gain_buf[cam], in_hw))) return rc;
             AV_HIP(hipMemcpy(fe->ph_gain_buf[cam], gain[cam], in_hw * sizeof(uint16_t), hipMemcpyHostToDevice));
             new_gain[cam] = fe->ph_gain_buf[cam];
         }
@@ -1876,12 +1782,13 @@ AV_EXPORT int av_frontend_enable_timing(av_frontend* fe, int max_spans)
     if (!fe || max_spans < 0) { av_set_error("av_frontend_enable_timing: bad arguments"); return AV_E_INVALID; }
     AV_HIP(hipSetDevice(fe->device));
     AV_HIP(hipDeviceSynchronize());
-    for (hipEvent_t e : fe->ev) (void)hipEventDestroy(e);
+    for (size_t i = fe->ev.size(); i-- > 0;) fe->res.free_event(fe->ev[i]);
     fe->ev.clear(); fe->ev_cls.clear(); fe->ev_used = 0;
     fe->timing = max_spans > 0;
     for (int i = 0; i < 2 * max_spans; ++i) {
-        hipEvent_t e;
-        AV_HIP(hipEventCreate(&e));
+        hipEvent_t e = nullptr;
+        int rc = fe->res.event(&e, hipEventDefault);
+        if (rc) return rc;
         fe->ev.push_back(e);
     }
     fe->ev_cls.assign((size_t)max_spans, 0);

@@ -24,6 +24,7 @@
 // contraction is <= 141^3 and is latency-, not throughput-bound at this size.
 #include <math.h>
 
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -2341,21 +2342,8 @@ struct av_msckf {
     int max_cam = 0, ld = 0, rows_cap = 0, n = IMU_DIM;
     double* P = nullptr; double* Pn = nullptr; double* T = nullptr; double* Kt = nullptr; double* W = nullptr;
     double* Hblk = nullptr; double* rblk = nullptr; double* dx = nullptr; double* chi2 = nullptr; double* scratch = nullptr; int* cols_dev = nullptr;
-    std::vector<void*> allocs;
+    AvResources res;
 };
-
-namespace {
-template <typename T>
-int mk_alloc(av_msckf* c, T** p, size_t count)
-{
-    void* q = nullptr;
-    AV_HIP(hipMalloc(&q, count * sizeof(T) + 256));
-    AV_HIP(hipMemset(q, 0, count * sizeof(T) + 256));
-    c->allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return AV_OK;
-}
-}  // namespace
 
 AV_EXPORT int av_msckf_create(int max_cam_states, int rows_cap, const double* chi2_table_100, int device, av_msckf** out)
 {
@@ -2363,31 +2351,24 @@ AV_EXPORT int av_msckf_create(int max_cam_states, int rows_cap, const double* ch
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { av_set_error("av_msckf_create: no HIP device visible"); return AV_E_NODEVICE; }
     AV_HIP(hipSetDevice(device));
-    av_msckf* c = new (std::nothrow) av_msckf();
+    std::unique_ptr<av_msckf> c(new (std::nothrow) av_msckf());      // an error return below releases what the object holds by then
     if (!c) { av_set_error("out of host memory"); return AV_E_INVALID; }
-    c->device = device; c->max_cam = max_cam_states; c->rows_cap = rows_cap;
+    c->device = c->res.device = device; c->max_cam = max_cam_states; c->rows_cap = rows_cap;
     const int nmax = IMU_DIM + 6 * (max_cam_states + 1);
     c->ld = (nmax + 7) & ~7;
     int rc;
-#define A(p, cnt) if ((rc = mk_alloc(c, &(p), (size_t)(cnt)))) { av_msckf_destroy(c); return rc; }
+#define A(p, cnt) if ((rc = c->res.dev(&(p), (size_t)(cnt)))) return rc;
     A(c->P, (size_t)c->ld * c->ld) A(c->Pn, (size_t)c->ld * c->ld) A(c->T, (size_t)c->ld * c->ld) A(c->Kt, (size_t)c->ld * c->ld)
     A(c->scratch, (size_t)c->ld * c->ld)
     A(c->W, (size_t)rows_cap * (c->ld + 1)) A(c->Hblk, (size_t)rows_cap * c->ld) A(c->rblk, rows_cap) A(c->dx, c->ld) A(c->chi2, 100)
     A(c->cols_dev, c->ld)
 #undef A
     AV_HIP(hipMemcpy(c->chi2, chi2_table_100, sizeof(double) * 100, hipMemcpyHostToDevice));
-    *out = c;
+    *out = c.release();
     return AV_OK;
 }
 
-AV_EXPORT void av_msckf_destroy(av_msckf* c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : c->allocs) (void)hipFree(p);
-    delete c;
-}
+AV_EXPORT void av_msckf_destroy(av_msckf* c) { delete c; }      // (~AvResources waits for the device and releases)
 
 AV_EXPORT int av_msckf_ld(const av_msckf* c) { return c ? c->ld : AV_E_INVALID; }
 AV_EXPORT int av_msckf_dim(const av_msckf* c) { return c ? c->n : AV_E_INVALID; }

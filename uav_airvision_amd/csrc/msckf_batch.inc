@@ -261,76 +261,6 @@ struct BStream {
     std::vector<double> dbg_gamma[2], dbg_dx[2], dbg_P[2]; int dbg_rows[2] = {0, 0}, dbg_n[2] = {0, 0};
 };
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr; size_t cap = 0;
-    T* stage = nullptr; size_t stage_cap = 0;          // pinned staging: async H2D without a sync per upload
-    // Growth never frees inside a step: hipFree synchronises the whole device and queued copies / kernels of this or of
-    // another stream group may still read the old allocation, so outgrown buffers are parked here until release().
-    // sub_reserve() sizes every buffer for the worst case of a message capacity before the first step; `growths`
-    // counts the (unexpected) reallocations after that and is reported by av_msckf_batch_counters.
-    std::vector<void*> old_dev, old_host;
-    long long growths = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return AV_OK;
-        const size_t ncap = n + n / 2 + 64;
-        T* q = nullptr;
-        AV_HIP(hipMalloc((void**)&q, ncap * sizeof(T)));
-        if (p) { old_dev.push_back(p); ++growths; }
-        p = q; cap = ncap;
-        return AV_OK;
-    }
-    int ensure_stage(size_t n)
-    {
-        if (n <= stage_cap) return AV_OK;
-        const size_t ncap = n + n / 2 + 64;
-        T* q = nullptr;
-        AV_HIP(hipHostMalloc((void**)&q, ncap * sizeof(T), hipHostMallocMapped));
-        if (stage) { old_host.push_back(stage); ++growths; }
-        stage = q; stage_cap = ncap;
-        return AV_OK;
-    }
-    int reserve(size_t n, bool with_stage) { int rc = ensure(n); if (!rc && with_stage) rc = ensure_stage(n); return rc; }
-    // The staging buffer is reused by the next upload of the SAME buffer; every phase of the step synchronises the
-    // stream (gate flags / delta_x / variances come back) before any buffer is uploaded again, so the copy has landed.
-    int upload(const std::vector<T>& h, hipStream_t st)
-    {
-        int rc = ensure(h.size());
-        if (rc) return rc;
-        if (h.empty()) return AV_OK;
-        if ((rc = ensure_stage(h.size()))) return rc;
-        memcpy(stage, h.data(), h.size() * sizeof(T));
-        AV_HIP(hipMemcpyAsync(p, stage, h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-        return AV_OK;
-    }
-    // Fill the pinned staging buffer in place (no intermediate std::vector), then commit(n) enqueues the copy.
-    int stage_for(size_t n, hipStream_t st, T** out)
-    {
-        (void)st;
-        int rc = ensure(n);
-        if (rc) return rc;
-        if ((rc = ensure_stage(n))) return rc;
-        *out = stage;
-        return AV_OK;
-    }
-    int commit(size_t n, hipStream_t st)
-    {
-        if (n == 0) return AV_OK;
-        AV_HIP(hipMemcpyAsync(p, stage, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return AV_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        if (stage) (void)hipHostFree(stage);
-        for (void* q : old_dev) (void)hipFree(q);
-        for (void* q : old_host) (void)hipHostFree(q);
-        old_dev.clear(); old_host.clear();
-        p = nullptr; stage = nullptr; cap = stage_cap = 0;
-    }
-};
-
 }  // namespace
 
 #include "msckf_store.h"
@@ -344,15 +274,18 @@ struct av_msckf_batch {
     std::vector<BStream> st;
     size_t pstride = 0, hstride = 0, rstride = 0, wstride = 0;
     double *P = nullptr, *Pn = nullptr, *T = nullptr, *Kt = nullptr, *W = nullptr, *Hblk = nullptr, *rblk = nullptr, *dx = nullptr, *scratch = nullptr, *chi2_dev = nullptr, *pvar = nullptr;
-    DevBuf<PropArgs> d_prop; DevBuf<int> d_first; DevBuf<AugArgs> d_aug; DevBuf<RemArgs> d_rem; DevBuf<UpdArgs> d_upd;
-    DevBuf<int> d_clist, d_flist, d_obs_off, d_obs_cam, d_fstream, d_dof, d_rowoff, d_pass, d_valid, d_blk_row, d_blk_len, d_ncam, d_cols;
-    DevBuf<double> d_obs_z, d_pos, d_gamma, d_cam_q, d_cam_p, d_cam_qn, d_grav;
+    // Owns every device and pinned block, event and stream of this batch or group, the DevPath's and the DevBufs' included (declared
+    // ahead of them: they register with it).  Outgrown blocks stay with it until destroy: nothing frees inside a run.
+    AvResources res;
+    DevBuf<PropArgs> d_prop{res}; DevBuf<int> d_first{res}; DevBuf<AugArgs> d_aug{res}; DevBuf<RemArgs> d_rem{res}; DevBuf<UpdArgs> d_upd{res};
+    DevBuf<int> d_clist{res}, d_flist{res}, d_obs_off{res}, d_obs_cam{res}, d_fstream{res}, d_dof{res}, d_rowoff{res}, d_pass{res}, d_valid{res}, d_blk_row{res},
+                d_blk_len{res}, d_ncam{res}, d_cols{res};
+    DevBuf<double> d_obs_z{res}, d_pos{res}, d_gamma{res}, d_cam_q{res}, d_cam_p{res}, d_cam_qn{res}, d_grav{res};
     // triangulation launch (own buffers: its results stay on the device for the feature kernels queued right behind it)
-    DevBuf<int> d_tobs_off, d_tobs_cam, d_tfs, d_tvalid, d_tri_idx, d_rbeg, d_stacked;
-    DevBuf<double> d_tobs_z, d_tpos;
-    DevBuf<UpdArgs> d_updbase;
+    DevBuf<int> d_tobs_off{res}, d_tobs_cam{res}, d_tfs{res}, d_tvalid{res}, d_tri_idx{res}, d_rbeg{res}, d_stacked{res};
+    DevBuf<double> d_tobs_z{res}, d_tpos{res};
+    DevBuf<UpdArgs> d_updbase{res};
     double *h_dx = nullptr, *h_pv = nullptr;    // pinned landing zones of the per-step read-backs
-    std::vector<void*> allocs;
     int reserved_cap = 0;                       // message capacity (features per stream) the buffers below are sized for
     // counters of av_msckf_batch_counters (sub-batch; the parent sums its groups)
     long long n_steps = 0, n_prune_stream_steps = 0, n_update_stream_steps = 0, n_two_pass_streams = 0;
@@ -454,17 +387,6 @@ struct FeatRef {
     int s; FMeta* f; int fs = -1; int dof; int n = 0; int first = 0;      // fs: the feature's slot in its stream's FeatStore::meta
     void add(ObsPool& p, int ci, const double* zz) { if (n == 0) first = (int)p.cam.size(); p.cam.push_back(ci); p.z.push_back(zz); ++n; }
 };
-
-int b_alloc(av_msckf_batch* b, double** p, size_t count)
-{
-    void* q = nullptr;
-    AV_HIP(hipMalloc(&q, count * sizeof(double) + 256));
-    AV_HIP(hipMemset(q, 0, count * sizeof(double) + 256));
-    AV_HIP(hipStreamSynchronize(nullptr));      // (the fill runs on the null stream; the groups' streams are non-blocking)
-    b->allocs.push_back(q);
-    *p = reinterpret_cast<double*>(q);
-    return AV_OK;
-}
 
 void b_fail_stream(av_msckf_batch* b, int s, int rc, const char* fmt, ...)
 {
@@ -1181,20 +1103,20 @@ int b_chain_finish(av_msckf_batch* b, std::vector<FeatRef>& refs, ChainCtx& ctx)
 }  // namespace
 
 static void sub_destroy(av_msckf_batch* b);
-namespace { void dev_release(DevPath* d); int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
+namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
 
 // Stream for the filter's kernels.  AV_MSCKF_CUS="first:count" confines them to `count` compute units starting at CU `first`
 // (hipExtStreamCreateWithCUMask) -- together with a complementary mask on the caller's front-end stream this partitions the
 // chip, so that the filter's latency-bound kernels never queue behind the front-end's resident workgroups.  Without the
 // variable: an ordinary stream, at the highest priority for the host-bookkeeping path, at the default priority otherwise.
-static hipError_t make_filter_stream(hipStream_t* out, bool host_store)
+static int make_filter_stream(AvResources& res, hipStream_t* out, bool host_store)
 {
     const char* e = getenv("AV_MSCKF_CUS");
     int first = 0, count = 0;
     if (e && sscanf(e, "%d:%d", &first, &count) == 2 && count > 0) {
         uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int c = first; c < first + count && c < 256; ++c) mask[c >> 5] |= 1u << (c & 31);
-        return hipExtStreamCreateWithCUMask(out, 8, mask);
+        return res.stream_on_cus(out, 8, mask);
     }
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -1202,7 +1124,7 @@ static hipError_t make_filter_stream(hipStream_t* out, bool host_store)
     // front-end's kernels keep their speed (11.5 instead of 16 ms of spans per 2,048-stream step) and the complete path gains
     // (DESIGN.md section 7: 131 k vs 114 k frames/s).  The host-bookkeeping path (AV_MSCKF_STORE=host) keeps the highest priority:
     // its launches are interleaved with host phases and must be scheduled at once.
-    return hipStreamCreateWithPriority(out, hipStreamNonBlocking, host_store ? hi : (lo + hi) / 2);
+    return res.stream(out, hipStreamNonBlocking, host_store ? hi : (lo + hi) / 2);
 }
 
 // Rows of the overflow pool behind the last stream's block-buffer region (device-resident path).  A stream whose lost-feature
@@ -1251,9 +1173,10 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
     AV_HIP(hipSetDevice(device));
     setenv("OMP_WAIT_POLICY", "passive", 0);      // idle OpenMP workers must not spin next to the HIP runtime threads
     setenv("KMP_BLOCKTIME", "0", 0);
-    av_msckf_batch* b = new (std::nothrow) av_msckf_batch(n_streams);
+    struct Guard { av_msckf_batch* b; ~Guard() { sub_destroy(b); } } guard{new (std::nothrow) av_msckf_batch(n_streams)};      // until *out = b: no return leaves a live batch behind
+    av_msckf_batch* b = guard.b;
     if (!b) { av_set_error("out of host memory"); return AV_E_INVALID; }
-    b->device = device; b->S = n_streams; b->max_cam = max_cam_states; b->cam_slots = max_cam_states + 1; b->rows_cap = rows_cap;
+    b->device = b->res.device = device; b->S = n_streams; b->max_cam = max_cam_states; b->cam_slots = max_cam_states + 1; b->rows_cap = rows_cap;
     b->ld = ((IMU_DIM + 6 * b->cam_slots) + 7) & ~7;
     for (int i = 0; i < 3; ++i) { b->gravity0[i] = gravity[i]; b->vel0[i] = velocity0[i]; }
     for (int i = 0; i < 16; ++i) b->T01[i] = T_cam0_cam1_rowmajor44[i];
@@ -1270,25 +1193,24 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
     const size_t S = n_streams;
     b->pstride = (size_t)b->ld * b->ld; b->hstride = (size_t)rows_cap * b->ld; b->rstride = rows_cap; b->wstride = (size_t)rows_cap * (b->ld + 1);
     int rc;
-#define A(p, cnt) if ((rc = b_alloc(b, &(p), (size_t)(cnt)))) { sub_destroy(b); return rc; }
+#define A(p, cnt) if ((rc = b->res.dev(&(p), (size_t)(cnt)))) return rc;
     A(b->P, S * b->pstride) A(b->Pn, S * b->pstride) A(b->T, S * b->pstride) A(b->Kt, S * b->pstride) A(b->scratch, S * b->pstride)
     if (rows_cap > 0) { const size_t pool = b_pool_rows(b, rows_cap); A(b->W, S * b->wstride) A(b->Hblk, S * b->hstride + pool * b->ld) A(b->rblk, S * b->rstride + pool) }
     A(b->dx, S * b->ld) A(b->chi2_dev, 100) A(b->pvar, 3 * S)
 #undef A
     AV_HIP(hipMemcpy(b->chi2_dev, chi2_table_100, sizeof(double) * 100, hipMemcpyHostToDevice));
-    AV_HIP(hipHostMalloc((void**)&b->h_dx, sizeof(double) * S * b->ld + 64, hipHostMallocDefault));
-    AV_HIP(hipHostMalloc((void**)&b->h_pv, sizeof(double) * 3 * S + 64, hipHostMallocDefault));
-    for (int i = 0; i < 4; ++i) { AV_HIP(make_filter_stream(&b->aux[i], host_store)); AV_HIP(hipEventCreateWithFlags(&b->ev_join[i], hipEventDisableTiming)); }
-    AV_HIP(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-    AV_HIP(hipEventCreateWithFlags(&b->ev_wait, hipEventDisableTiming | hipEventBlockingSync));
-    for (int i = 0; i < 2; ++i) { AV_HIP(hipEventCreate(&b->ev_t0[i])); AV_HIP(hipEventCreate(&b->ev_t1[i])); }
+    if ((rc = b->res.pinned(&b->h_dx, S * b->ld)) || (rc = b->res.pinned(&b->h_pv, 3 * S))) return rc;
+    for (int i = 0; i < 4; ++i) if ((rc = make_filter_stream(b->res, &b->aux[i], host_store)) || (rc = b->res.event(&b->ev_join[i], hipEventDisableTiming))) return rc;
+    if ((rc = b->res.event(&b->ev_fork, hipEventDisableTiming)) || (rc = b->res.event(&b->ev_wait, hipEventDisableTiming | hipEventBlockingSync))) return rc;
+    for (int i = 0; i < 2; ++i) if ((rc = b->res.event(&b->ev_t0[i], hipEventDefault)) || (rc = b->res.event(&b->ev_t1[i], hipEventDefault))) return rc;
     for (int s = 0; s < n_streams; ++s) {
         BStream& T = b->st[s];
         for (int i = 0; i < 3; ++i) { T.gravity[i] = gravity[i]; T.v[i] = velocity0[i]; T.t_ci[i] = b->t_ci0[i]; }
         for (int i = 0; i < 9; ++i) T.R_ic[i] = b->R_ic0[i];
-        if ((rc = b_reset_cov(b, s, nullptr))) { sub_destroy(b); return rc; }
+        if ((rc = b_reset_cov(b, s, nullptr))) return rc;
     }
-    if (b->pool_on) { b->dev = new (std::nothrow) DevPath(); if (!b->dev) { sub_destroy(b); av_set_error("out of host memory"); return AV_E_INVALID; } }
+    if (b->pool_on) { b->dev = new (std::nothrow) DevPath(); if (!b->dev) { av_set_error("out of host memory"); return AV_E_INVALID; } }
+    guard.b = nullptr;
     *out = b;
     return AV_OK;
 }
@@ -1296,23 +1218,8 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
 static void sub_destroy(av_msckf_batch* b)
 {
     if (!b) return;
-    (void)hipSetDevice(b->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : b->allocs) (void)hipFree(p);
-    for (int i = 0; i < 4; ++i) { if (b->aux[i]) (void)hipStreamDestroy(b->aux[i]); if (b->ev_join[i]) (void)hipEventDestroy(b->ev_join[i]); }
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->ev_wait) (void)hipEventDestroy(b->ev_wait);
-    for (int i = 0; i < 2; ++i) { if (b->ev_t0[i]) (void)hipEventDestroy(b->ev_t0[i]); if (b->ev_t1[i]) (void)hipEventDestroy(b->ev_t1[i]); }
-    b->d_clist.release(); b->d_prop.release(); b->d_first.release(); b->d_aug.release(); b->d_rem.release(); b->d_upd.release();
-    b->d_obs_off.release(); b->d_obs_cam.release(); b->d_fstream.release(); b->d_dof.release(); b->d_rowoff.release(); b->d_pass.release();
-    b->d_valid.release(); b->d_flist.release(); b->d_cols.release(); b->d_blk_row.release(); b->d_blk_len.release(); b->d_ncam.release(); b->d_obs_z.release(); b->d_pos.release();
-    b->d_gamma.release(); b->d_cam_q.release(); b->d_cam_p.release(); b->d_cam_qn.release(); b->d_grav.release();
-    b->d_tobs_off.release(); b->d_tobs_cam.release(); b->d_tfs.release(); b->d_tvalid.release(); b->d_tri_idx.release(); b->d_rbeg.release();
-    b->d_stacked.release(); b->d_tobs_z.release(); b->d_tpos.release(); b->d_updbase.release();
-    if (b->h_dx) (void)hipHostFree(b->h_dx);
-    if (b->h_pv) (void)hipHostFree(b->h_pv);
-    dev_release(b->dev);
-    for (int i = 0; i < 4; ++i) if (b->ev_msg[i]) (void)hipEventDestroy(b->ev_msg[i]);
+    b->res.release();                 // (the group's worker has been joined by the caller)
+    delete b->dev;
     delete b;
 }
 
@@ -1356,7 +1263,7 @@ static int sub_reserve(av_msckf_batch* b, int cap)
     if (cap <= b->reserved_cap) return AV_OK;
     if (b->rows_cap == 0 || (b->rows_cap_auto && 5 * cap > b->rows_cap)) {
         // rows_cap 0 at create = size the block buffers from the message capacity; a later, wider message grows them (they hold
-        // per-phase scratch only; the outgrown allocations stay parked in `allocs` until destroy: no free inside a run)
+        // per-phase scratch only; the outgrown allocations stay with the owner until destroy: no free inside a run)
         if (b->rows_cap_auto) { int rcw = b_wait(b, nullptr); if (rcw) return rcw; AV_HIP(hipDeviceSynchronize()); }
         b->rows_cap_auto = true;
         {   // a regrow is geometric (x1.5 at least): a message that widens by 64 features at a time must not rebuild every time
@@ -1367,7 +1274,7 @@ static int sub_reserve(av_msckf_batch* b, int cap)
         b->hstride = (size_t)b->rows_cap * b->ld; b->rstride = b->rows_cap; b->wstride = (size_t)b->rows_cap * (b->ld + 1);
         int rc0;
         const size_t pool = b_pool_rows(b, b->rows_cap);
-        if ((rc0 = b_alloc(b, &b->W, Sn * b->wstride)) || (rc0 = b_alloc(b, &b->Hblk, Sn * b->hstride + pool * b->ld)) || (rc0 = b_alloc(b, &b->rblk, Sn * b->rstride + pool))) return rc0;
+        if ((rc0 = b->res.dev(&b->W, Sn * b->wstride)) || (rc0 = b->res.dev(&b->Hblk, Sn * b->hstride + pool * b->ld)) || (rc0 = b->res.dev(&b->rblk, Sn * b->rstride + pool))) return rc0;
     }
     if (5 * cap > b->rows_cap) {
         av_set_error("batched MSCKF: rows_cap %d cannot hold the camera-pruning update of %d features per message (5 rows each: need >= %d)",
@@ -1393,15 +1300,7 @@ static int sub_reserve(av_msckf_batch* b, int cap)
     return AV_OK;
 }
 
-static long long sub_growths(const av_msckf_batch* b)
-{
-    return b->d_clist.growths + b->d_prop.growths + b->d_first.growths + b->d_aug.growths + b->d_rem.growths + b->d_upd.growths + b->d_flist.growths +
-           b->d_obs_off.growths + b->d_obs_cam.growths + b->d_fstream.growths + b->d_dof.growths + b->d_rowoff.growths + b->d_pass.growths +
-           b->d_valid.growths + b->d_blk_row.growths + b->d_blk_len.growths + b->d_ncam.growths + b->d_cols.growths + b->d_obs_z.growths +
-           b->d_pos.growths + b->d_gamma.growths + b->d_cam_q.growths + b->d_cam_p.growths + b->d_cam_qn.growths + b->d_grav.growths +
-           b->d_tobs_off.growths + b->d_tobs_cam.growths + b->d_tobs_z.growths + b->d_tfs.growths + b->d_tvalid.growths + b->d_tpos.growths +
-           b->d_tri_idx.growths + b->d_rbeg.growths + b->d_stacked.growths + b->d_updbase.growths;
-}
+static long long sub_growths(const av_msckf_batch* b) { return b->res.growths(); }
 
 // feature_callback for every stream (msckf.py:177-228).  Features of stream s: ids[s*cap + k], uv[(s*cap+k)*4 ..], k < n_feat[s]
 // (host arrays).  out[s*12 ..] = published, t, p(3), q(4), v(3) of the IMU state.
@@ -1886,7 +1785,7 @@ AV_EXPORT int av_msckf_batch_create(int n_streams, int max_cam_states, int rows_
                           obs_noise, position_std_threshold, velocity0, opt6, device, host_store, out);
     av_msckf_batch* p = new (std::nothrow) av_msckf_batch(0);
     if (!p) { av_set_error("out of host memory"); return AV_E_INVALID; }
-    p->device = device; p->S = n_streams; p->per_sub = (n_streams + G - 1) / G;
+    p->device = p->res.device = device; p->S = n_streams; p->per_sub = (n_streams + G - 1) / G;
     // a group's workers sleep while its kernels run, so the groups together may hold twice the core budget
     const int share = 2 * host_thread_budget() / G < 1 ? 1 : 2 * host_thread_budget() / G;
     for (int s0 = 0; s0 < n_streams; s0 += p->per_sub) {
@@ -1897,7 +1796,7 @@ AV_EXPORT int av_msckf_batch_create(int n_streams, int max_cam_states, int rows_
         if (rc == AV_OK) {
             // highest priority: the filter's kernels are short, latency-bound and on the step's critical path; the
             // front-end's throughput kernels (other streams) fill whatever they leave free
-            if (make_filter_stream(&g->own, host_store) != hipSuccess) { av_set_error("hipStreamCreate failed"); rc = AV_E_HIP; }
+            rc = make_filter_stream(g->res, &g->own, host_store);
         }
         if (rc) { if (g) sub_destroy(g); av_msckf_batch_destroy(p); return rc; }
         g->host_cap = share;
@@ -1918,10 +1817,8 @@ AV_EXPORT void av_msckf_batch_destroy(av_msckf_batch* b)
             g->wcv.notify_all();
             g->worker.join();
         }
-        if (g->own) { (void)hipSetDevice(g->device); (void)hipStreamSynchronize(g->own); (void)hipStreamDestroy(g->own); }
         sub_destroy(g);
     }
-    for (int i = 0; i < 4; ++i) if (b->ev_msg[i]) (void)hipEventDestroy(b->ev_msg[i]);
     delete b;
 }
 
@@ -2045,7 +1942,7 @@ AV_EXPORT int av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_de
     if ((rc = av_msckf_batch_wait(b, b->subs.empty() ? DEV_RING - 2 : DEV_RING - 1))) return rc;
     const int k = (int)(b->dev_seq++ % DEV_RING);
     hipStream_t ms = (hipStream_t)msg_stream;
-    if (!b->ev_msg[k]) AV_HIP(hipEventCreateWithFlags(&b->ev_msg[k], hipEventDisableTiming));
+    if (!b->ev_msg[k] && (rc = b->res.event(&b->ev_msg[k], hipEventDisableTiming))) return rc;
     size_t s0 = 0;
     for (av_msckf_batch* g : parts) {
         DevSlot& sl = g->dev->slot[k];
@@ -2290,14 +2187,15 @@ AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int c
     hipStream_t stm = (hipStream_t)stream;
     AV_HIP(hipSetDevice(c->device));
     // one device allocation for everything the kernels need besides the caller's arrays, released on every way out
-    struct Arena { char* p = nullptr; size_t used = 0; ~Arena() { if (p) (void)hipFree(p); }
+    struct Arena { AvScratch mem; char* p = nullptr; size_t used = 0;
                    size_t take(size_t bytes) { const size_t o = used; used += (bytes + 255) / 256 * 256; return o; } } ar;
     const size_t nimu = (size_t)(n_imu > 0 ? n_imu : 1), ncs = (size_t)S * cam_stride;
     const size_t o_st = ar.take(sizeof(DState) * S), o_ctl = ar.take(sizeof(DCtl) * S), o_imu = ar.take(sizeof(DImu) * nimu), o_prop = ar.take(sizeof(PropArgs) * nimu),
                  o_cov = ar.take(sizeof(DCov) * S), o_cnt = ar.take(sizeof(int) * 16), o_id = ar.take(sizeof(long long) * ncs), o_nc = ar.take(sizeof(int) * S),
                  o_ns = ar.take(sizeof(int) * S), o_gr = ar.take(sizeof(double) * 3 * S), o_ops = ar.take(sizeof(int) * S), o_rm = ar.take(sizeof(int) * 2 * S),
                  o_red = ar.take(sizeof(int) * 2 * S), o_scr = ar.take(any_ops ? sizeof(double) * (size_t)p_stride * S : 8);
-    AV_HIP(hipMalloc((void**)&ar.p, ar.used));
+    { const int rca = ar.mem.alloc(ar.used); if (rca) return rca; }
+    ar.p = static_cast<char*>(ar.mem.p);
     std::vector<DState> st((size_t)S); std::vector<DCtl> ct((size_t)S); std::vector<DImu> im(nimu);
     std::vector<int> ops((size_t)S), rm((size_t)2 * S), red((size_t)2 * S, -1);
     memset(st.data(), 0, sizeof(DState) * S); memset(ct.data(), 0, sizeof(DCtl) * S); memset(im.data(), 0, sizeof(DImu) * nimu);

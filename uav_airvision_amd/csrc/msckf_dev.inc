@@ -734,7 +734,6 @@ struct DevPath {
     int launched_wg = 0;             // workgroup size dev_enqueue launched them with in the last enqueued step (0: no step yet); av_msckf_batch_launch_shape
     int* cols = nullptr; int* blk_row = nullptr; int* blk_len = nullptr; int* clist = nullptr; int* again = nullptr;
     double* work = nullptr; double* gamma = nullptr; int* pass = nullptr;
-    std::vector<void*> dev_allocs, host_allocs;
     int hint[16] = {0};              // list lengths of the last finished step (grids of the next one are sized from them; the kernels stride anyway)
     bool have_hint = false;
     long long growths = 0, steps = 0;

@@ -7,40 +7,6 @@ namespace {
 
 constexpr int DEV_KCH = 136;       // stacked rows one back-end pass takes directly (74.6 KB of LDS for the factor: two workgroups per CU)
 
-template <typename T>
-int dev_alloc(DevPath* d, T** p, size_t count, int fill = 0)
-{
-    void* q = nullptr;
-    AV_HIP(hipMalloc(&q, count * sizeof(T) + 256));
-    AV_HIP(hipMemset(q, fill, count * sizeof(T) + 256));
-    AV_HIP(hipStreamSynchronize(nullptr));      // the fill runs on the null stream; the buffer is used on non-blocking streams that do not wait for it
-    d->dev_allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return AV_OK;
-}
-template <typename T>
-int dev_pinned(DevPath* d, T** p, size_t count)
-{
-    void* q = nullptr;
-    AV_HIP(hipHostMalloc(&q, count * sizeof(T) + 64, hipHostMallocDefault));
-    memset(q, 0, count * sizeof(T) + 64);
-    d->host_allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return AV_OK;
-}
-
-void dev_release(DevPath* d)
-{
-    if (!d) return;
-    for (int k = 0; k < DEV_RING; ++k) {
-        if (d->slot[k].done) (void)hipEventDestroy(d->slot[k].done);
-        for (int ph = 0; ph < 2; ++ph) { if (d->slot[k].t0[ph]) (void)hipEventDestroy(d->slot[k].t0[ph]); if (d->slot[k].t1[ph]) (void)hipEventDestroy(d->slot[k].t1[ph]); }
-    }
-    for (void* p : d->dev_allocs) (void)hipFree(p);
-    for (void* p : d->host_allocs) (void)hipHostFree(p);
-    delete d;
-}
-
 // copy of the store of every stream into arrays built for a larger message capacity (a wider feature message arrived)
 __global__ __launch_bounds__(256) void dk_migrate(DevArgs o, DevArgs n)
 {
@@ -85,8 +51,8 @@ int dev_reserve(av_msckf_batch* b, int cap)
     A.hcells = hc;
     if ((size_t)S * A.FS >= (1u << 31) || S * (size_t)A.obs_stride >= (1u << 31)) { av_set_error("batched MSCKF: %zu streams x %d features exceed the 32-bit feature index", S, cap); return AV_E_CAPACITY; }
     const size_t nf = S * (size_t)A.FS + 8, no = S * (size_t)A.obs_stride + 8, ne = S * (size_t)A.ns * cap, nm = S * (size_t)A.mcap;
-#define DA(ptr, cnt) if ((rc = dev_alloc(d, &(ptr), (size_t)(cnt)))) return rc;
-#define DAF(ptr, cnt, fill) if ((rc = dev_alloc(d, &(ptr), (size_t)(cnt), fill))) return rc;
+#define DA(ptr, cnt) if ((rc = b->res.dev(&(ptr), (size_t)(cnt)))) return rc;
+#define DAF(ptr, cnt, fill) if ((rc = b->res.dev(&(ptr), (size_t)(cnt), fill))) return rc;
     if (!grow) {
         DA(A.st, S) DA(A.cam_id, S * cs) DA(A.cam_q, S * cs * 4) DA(A.cam_p, S * cs * 3) DA(A.cam_qn, S * cs * 4) DA(A.ncam, S) DA(A.nstate, S) DA(A.grav, S * 3)
         DA(A.n_cand, S) DA(A.over, S) DA(A.cnt, 32) DA(d->out_d, S * 12) DA(d->cov_d, S) DA(d->stacked0, S) DA(d->stacked1, S) DA(d->updbase, S) DA(d->upd, S * 2)
@@ -104,15 +70,15 @@ int dev_reserve(av_msckf_batch* b, int cap)
     for (int k = 0; k < DEV_RING; ++k) {
         DevSlot& sl = d->slot[k];
         if (!grow) {
-            if ((rc = dev_pinned(d, &sl.ctl_h, S)) || (rc = dev_pinned(d, &sl.out_h, S * 12)) || (rc = dev_pinned(d, &sl.cnt_h, 16))) return rc;
+            if ((rc = b->res.pinned(&sl.ctl_h, S)) || (rc = b->res.pinned(&sl.out_h, S * 12)) || (rc = b->res.pinned(&sl.cnt_h, 16))) return rc;
             DA(sl.ctl_d, S) DA(sl.n_d, S)
-            if ((rc = dev_pinned(d, &sl.n_h, S))) return rc;
-            if (b->odom_cov && (rc = dev_pinned(d, &sl.odom_h, S * ODOM_COV_DOUBLES))) return rc;
-            AV_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-            for (int ph = 0; ph < 2; ++ph) { AV_HIP(hipEventCreate(&sl.t0[ph])); AV_HIP(hipEventCreate(&sl.t1[ph])); }
+            if ((rc = b->res.pinned(&sl.n_h, S))) return rc;
+            if (b->odom_cov && (rc = b->res.pinned(&sl.odom_h, S * ODOM_COV_DOUBLES))) return rc;
+            if ((rc = b->res.event(&sl.done, hipEventDisableTiming | hipEventBlockingSync))) return rc;
+            for (int ph = 0; ph < 2; ++ph) if ((rc = b->res.event(&sl.t0[ph], hipEventDefault)) || (rc = b->res.event(&sl.t1[ph], hipEventDefault))) return rc;
         }
         DA(sl.ids_d, S * cap) DA(sl.uv_d, S * cap * 4)
-        if ((rc = dev_pinned(d, &sl.ids_h, S * cap)) || (rc = dev_pinned(d, &sl.uv_h, S * cap * 4))) return rc;
+        if ((rc = b->res.pinned(&sl.ids_h, S * cap)) || (rc = b->res.pinned(&sl.uv_h, S * cap * 4))) return rc;
     }
 #undef DA
 #undef DAF
@@ -419,7 +385,7 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
     if (n_imu > sl.imu_cap) {          // (sized generously at the first step; grows if a frame ever spans more IMU samples)
         const size_t ncap = n_imu + n_imu / 2 + (size_t)S * 16 + 64;
         if (sl.imu_cap) { AV_HIP(hipStreamSynchronize(stm)); ++d->growths; }
-        if ((rc = dev_pinned(d, &sl.imu_h, ncap)) || (rc = dev_alloc(d, &sl.imu_d, ncap)) || (rc = dev_alloc(d, &sl.prop_d, ncap))) return rc;
+        if ((rc = b->res.pinned(&sl.imu_h, ncap)) || (rc = b->res.dev(&sl.imu_d, ncap)) || (rc = b->res.dev(&sl.prop_d, ncap))) return rc;
         sl.imu_cap = ncap;
     }
     size_t w = 0;

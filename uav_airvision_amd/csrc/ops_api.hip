@@ -15,6 +15,13 @@ void av_set_error(const char* fmt, ...)
 
 AV_EXPORT const char* av_last_error(void) { return g_err; }
 AV_EXPORT const char* av_version(void) { return "airvision-hip 0.1 (gfx950, round 1)"; }
+// tests only: what every AvResources and AvScratch of the process holds at this moment (av_resources.h)
+AV_EXPORT int av_debug_live_resources(int64_t out4[4])
+{
+    if (!out4) { av_set_error("av_debug_live_resources: bad arguments"); return AV_E_INVALID; }
+    for (int i = 0; i < 4; ++i) out4[i] = av_live_counts[i].load(std::memory_order_relaxed);
+    return AV_OK;
+}
 AV_EXPORT int av_device_count(void)
 {
     int n = 0;

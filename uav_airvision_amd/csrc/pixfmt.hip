@@ -182,13 +182,12 @@ AV_EXPORT int av_to_gray8(const void* img_dev, int64_t img_stride_bytes, int n_i
     }
     const FrameSet src = av_frames(in, nullptr, img_stride_bytes), dst{{out_dev, nullptr}, out_stride, nullptr};
     if (packed && bayer) {                         // the operator owns no scratch: one for this call, freed once the stream has passed it (the call waits)
-        uint8_t* scratch = nullptr;
+        AvScratch scratch;
         const int64_t mstride = (npix + 15) & ~(int64_t)15;      // whole vectors apart: the vector paths of both passes stay open to a batch
-        AV_HIP(hipMalloc((void**)&scratch, (size_t)n_img * mstride));
-        const FrameSet mosaic{{scratch, nullptr}, mstride, nullptr};
+        if ((rc = scratch.alloc((size_t)n_img * mstride))) return rc;
+        const FrameSet mosaic{{static_cast<uint8_t*>(scratch.p), nullptr}, mstride, nullptr};
         rc = av_launch_to_gray8(src, dst, n_img, w, h, pixel_format, shift, st, &mosaic);
         const hipError_t done = hipStreamSynchronize(st);
-        (void)hipFree(scratch);
         if (!rc && done != hipSuccess) { av_set_error("av_to_gray8: %s", hipGetErrorString(done)); return AV_E_HIP; }
         return rc;
     }

@@ -224,14 +224,14 @@ AV_EXPORT int av_to_gray8_range(const void* img_dev, int64_t img_stride_bytes, i
         return av_launch_gray16_range(src, dst, n_groups, w, h, r, st);
     }
     // without them: histograms and records for this call, freed once the stream has passed them (the call waits)
-    uint32_t* buf = nullptr;
+    AvScratch scratch;
     const size_t words = (size_t)n_groups * AV_GRAY16_WORK_WORDS;
-    AV_HIP(hipMalloc((void**)&buf, words * sizeof(uint32_t)));
+    if ((rc = scratch.alloc(words * sizeof(uint32_t)))) return rc;
+    uint32_t* buf = static_cast<uint32_t*>(scratch.p);
     hipError_t done = hipMemsetAsync(buf, 0, words * sizeof(uint32_t), st);
     r.hist = buf; r.rec = buf + (size_t)n_groups * R16_BINS;
     if (done == hipSuccess) rc = av_launch_gray16_range(src, dst, n_groups, w, h, r, st);
     const hipError_t waited = hipStreamSynchronize(st);
-    (void)hipFree(buf);
     if (!rc && (done != hipSuccess || waited != hipSuccess)) { av_set_error("av_to_gray8_range: %s", hipGetErrorString(done != hipSuccess ? done : waited)); return AV_E_HIP; }
     return rc;
 }
