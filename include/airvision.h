@@ -965,6 +965,47 @@ int  av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, i
 #define AV_ODOM_COV_DOUBLES 120
 int  av_msckf_batch_set_odom_cov(av_msckf_batch* b, int enable);
 int  av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host);
+/* Landmark map: the 3-D positions of the features a step triangulates and uses, per stream and step, riding the step's read-back.
+ * Off by default.  On, every step yields for every stream a count pair n[s][2] and up to `cap` records of AV_LANDMARK_BYTES = 40 bytes:
+ *   id      the feature id of the front-end message
+ *   p       its position in the filter's world frame, exactly the doubles the filter used: what the triangulation wrote for a feature
+ *           triangulated in this step, the stored position of one fixed in an earlier step.  Positions are never re-estimated after the
+ *           update (as in the reference).
+ *   n_obs   camera states that observed the feature when it was evaluated
+ *   flags   AV_LM_USED      its rows went into the update
+ *           AV_LM_REJECTED  it was evaluated and the chi-square gate rejected it.  Neither bit: the feature lies beyond the 1,500-row cut
+ *                           of the lost-feature update (msckf.py:667-668), where the reference never evaluates it; the feature whose
+ *                           rows take the running sum over 1,500 is still USED.
+ *           AV_LM_TRACKED   the record comes from the pruning update and the feature stays in the map
+ *           AV_LM_NEW       the position was triangulated in this step
+ * Records of the lost-feature update (msckf.py:614-676) come first, in map (dict) order: every candidate whose position is valid (the
+ * reference's `processed` list).  These features leave the map in this step: the positions are final.  Records of the pruning update
+ * (msckf.py:712-786) follow, in map order: only the candidates whose position was first obtained in this step (TRACKED | NEW).  A feature
+ * fixed in an earlier pruning step is not republished; when it is lost it appears once more among the lost-feature records, with the same
+ * position bits and without NEW.  Not published: candidates check_motion held back, candidates whose triangulation failed, pruning
+ * candidates with a single removed observation.
+ * Counts: n[s][0] = records the step had, n[s][1] = records written = min(n[s][0], cap); on overflow the first `cap` records in the order
+ * above are written and the rest dropped; records past n[s][1] are unspecified.  A stream that is inactive, failed or stopped in this
+ * step has n = {0, 0}.  A step that ends in online_reset still publishes what its two updates used.
+ * av_msckf_batch_set_landmarks(b, cap): cap records per stream and step, 0 = off; before the batch's first step (AV_E_INVALID afterwards).
+ * Off, the step launches and reads back exactly what it did without the feature; on, two per-stream kernels of the step are the instances
+ * that also write the records (no launch more) and two more asynchronous copies bring records and counts to pinned buffers of the step's
+ * ring slot: no wait and no allocation inside a step.  Device-resident filter only: under AV_MSCKF_STORE=host a non-zero cap is
+ * AV_E_INVALID, with a text that names AV_MSCKF_STORE.
+ * av_msckf_batch_next_landmarks(b, rec, n): hands over the destination -- n_streams * cap records and n_streams * 2 counts -- of the NEXT
+ * av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps
+ * its own destination.  Stream groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination
+ * computes its records and drops them.
+ * Known limits: positions as triangulated, not refined by the update; no per-landmark covariance; carried pruning features are not
+ * republished; nothing on the host-bookkeeping path. */
+#define AV_LANDMARK_BYTES 40
+#define AV_LM_USED     1
+#define AV_LM_REJECTED 2
+#define AV_LM_TRACKED  4
+#define AV_LM_NEW      8
+typedef struct av_landmark { int64_t id; double p[3]; int32_t flags; int32_t n_obs; } av_landmark;
+int  av_msckf_batch_set_landmarks(av_msckf_batch* b, int cap);
+int  av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t* n);
 int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);     /* [state dim, camera states, map features] */
 /* Full host-side state of one stream -- every target of measurement_update's injection (msckf.py:568-595), for parity tests
  * (SURVEY 8b get_state): imu32 = [imu_state.timestamp, orientation q(4, JPL xyzw), position(3), velocity(3), gyro_bias(3),

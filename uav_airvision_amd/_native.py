@@ -183,6 +183,10 @@ class PyrLayout(C.Structure):
                 ('bytes', C.c_int64)]
 
 
+class Landmark(C.Structure):                     # av_landmark (AV_LANDMARK_BYTES = 40)
+    _fields_ = [('id', C.c_int64), ('p', C.c_double * 3), ('flags', C.c_int32), ('n_obs', C.c_int32)]
+
+
 class FrontendConfig(C.Structure):
     _fields_ = [('width', C.c_int32), ('height', C.c_int32),
                 ('grid_row', C.c_int32), ('grid_col', C.c_int32),
@@ -262,6 +266,8 @@ SIGNATURES = {
     'av_msckf_batch_get_cov': (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     'av_msckf_batch_set_odom_cov': (C.c_int, [_P, C.c_int]),
     'av_msckf_batch_next_odom_cov': (C.c_int, [_P, _P]),
+    'av_msckf_batch_set_landmarks': (C.c_int, [_P, C.c_int]),
+    'av_msckf_batch_next_landmarks': (C.c_int, [_P, _P, _P]),
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_msckf_batch_launch_shape': (C.c_int, [_P, C.POINTER(C.c_int32 * 17)]),

@@ -162,3 +162,7 @@ class ConfigEuRoC(object):
         # no reference counterpart: the drop-in MSCKF keeps the 15 x 15 odometry covariance of its last published result in
         # `last_covariance` (needs T_imu_body = identity; include/airvision.h, "Odometry covariance")
         self.publish_covariance = False
+        # no reference counterpart: the drop-in MSCKF keeps the landmark records of its last feature_callback in `last_landmarks`
+        # (up to landmark_cap per frame, positions in the world frame of the published pose; include/airvision.h, "Landmark map")
+        self.publish_landmarks = False
+        self.landmark_cap = 256

@@ -316,11 +316,14 @@ struct av_msckf_batch {
     DevPath* dev = nullptr;                     // device-resident state + observation store (msckf_dev.inc); NULL: the host-bookkeeping path (AV_MSCKF_STORE=host)
     long long dev_seq = 0;                      // steps submitted (ring slot = dev_seq % DEV_RING)
     hipEvent_t ev_msg[4] = {nullptr, nullptr, nullptr, nullptr};      // submit_dev: the message copy of ring slot k has been enqueued
-    struct Pending { int slot; double* out; double* cov; };
-    std::deque<Pending> direct_pending;         // one group, no worker: steps launched and not yet finished (slot, caller's out, caller's odometry-covariance array or NULL)
+    struct Pending { int slot; double* out; double* cov; av_landmark* lm; int32_t* lmn; };
+    std::deque<Pending> direct_pending;         // one group, no worker: steps launched and not yet finished (slot, caller's out, caller's odometry-covariance array or NULL, caller's landmark arrays or NULL)
     // odometry covariance (av_msckf_batch_set_odom_cov): on the batch and on every group; next_cov = the destination
     // av_msckf_batch_next_odom_cov handed over for the next step (batch only), taken by that step
     bool odom_cov = false; double* next_cov = nullptr;
+    // landmark map (av_msckf_batch_set_landmarks): records per stream and step (0: off), on the batch and on every group; next_lm /
+    // next_lmn = the destination av_msckf_batch_next_landmarks handed over for the next step (batch only), taken by that step
+    int lm_cap = 0; av_landmark* next_lm = nullptr; int32_t* next_lmn = nullptr;
     explicit av_msckf_batch(int n) : st(n) {}
 };
 
@@ -1103,7 +1106,7 @@ int b_chain_finish(av_msckf_batch* b, std::vector<FeatRef>& refs, ChainCtx& ctx)
 }  // namespace
 
 static void sub_destroy(av_msckf_batch* b);
-namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
+namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
 
 // Stream for the filter's kernels.  AV_MSCKF_CUS="first:count" confines them to `count` compute units starting at CU `first`
 // (hipExtStreamCreateWithCUMask) -- together with a complementary mask on the caller's front-end stream this partitions the
@@ -1315,8 +1318,9 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
     if (b->dev) {
         const int k = (int)(b->dev_seq++ % DEV_RING);
         double* cov = b->next_cov; b->next_cov = nullptr;
+        av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
         if ((rc = dev_launch(b, k, ids, uv, n_feat, cap, timestamps, false, nullptr, stm))) return rc;
-        return dev_finish(b, k, out, cov);
+        return dev_finish(b, k, out, cov, lm, lmn);
     }
     if ((rc = sub_reserve(b, cap))) return rc;
     ++b->n_steps;
@@ -1845,7 +1849,7 @@ int direct_drain(av_msckf_batch* b, size_t max_pending)
     while (b->direct_pending.size() > max_pending) {
         const av_msckf_batch::Pending pr = b->direct_pending.front();
         b->direct_pending.pop_front();
-        const int r = dev_finish(b, pr.slot, pr.out, pr.cov);
+        const int r = dev_finish(b, pr.slot, pr.out, pr.cov, pr.lm, pr.lmn);
         if (r && !rc) rc = r;
     }
     return rc;
@@ -1895,19 +1899,21 @@ AV_EXPORT int av_msckf_batch_submit(av_msckf_batch* b, const int64_t* ids, const
         if (rc) return rc;
         const int k = (int)(b->dev_seq++ % DEV_RING);
         double* cov = b->next_cov; b->next_cov = nullptr;
+        av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
         if ((rc = dev_launch(b, k, ids, uv, n_feat, cap, timestamps, false, nullptr, (hipStream_t)stream))) return rc;
-        b->direct_pending.push_back({k, out, cov});
+        b->direct_pending.push_back({k, out, cov, lm, lmn});
         return AV_OK;
     }
     const int k = (int)(b->dev_seq++ % DEV_RING);
     double* cov = b->next_cov; b->next_cov = nullptr;
+    av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
     for (size_t gi = 0; gi < b->subs.size(); ++gi) {
         av_msckf_batch* g = b->subs[gi];
         const size_t s0 = gi * (size_t)b->per_sub;
         av_msckf_batch::Job job;
         if (g->dev) {
             job.launch = [=] { return dev_launch(g, k, ids + s0 * cap, uv + s0 * cap * 4, n_feat + s0, cap, timestamps + s0, false, nullptr, g->own); };
-            job.finish = [=] { return dev_finish(g, k, out + s0 * 12, cov ? cov + s0 * ODOM_COV_DOUBLES : nullptr); };
+            job.finish = [=] { return dev_finish(g, k, out + s0 * 12, cov ? cov + s0 * ODOM_COV_DOUBLES : nullptr, lm ? lm + s0 * b->lm_cap : nullptr, lmn ? lmn + s0 * 2 : nullptr); };
         } else {
             job.launch = [=] { return sub_step(g, ids + s0 * cap, uv + s0 * cap * 4, n_feat + s0, cap, timestamps + s0, out + s0 * 12, g->own); };
         }
@@ -1960,9 +1966,10 @@ AV_EXPORT int av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_de
     AV_HIP(hipEventRecord(b->ev_msg[k], ms));
     hipEvent_t ready = b->ev_msg[k];
     double* cov = b->next_cov; b->next_cov = nullptr;
+    av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
     if (b->subs.empty()) {
         if ((rc = dev_launch(b, k, nullptr, nullptr, nullptr, cap, timestamps, true, ready, (hipStream_t)stream))) return rc;
-        b->direct_pending.push_back({k, out, cov});
+        b->direct_pending.push_back({k, out, cov, lm, lmn});
         return AV_OK;
     }
     s0 = 0;
@@ -1970,7 +1977,7 @@ AV_EXPORT int av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_de
         const size_t o = s0;
         av_msckf_batch::Job job;
         job.launch = [=] { return dev_launch(g, k, nullptr, nullptr, nullptr, cap, timestamps + o, true, ready, g->own); };
-        job.finish = [=] { return dev_finish(g, k, out + o * 12, cov ? cov + o * ODOM_COV_DOUBLES : nullptr); };
+        job.finish = [=] { return dev_finish(g, k, out + o * 12, cov ? cov + o * ODOM_COV_DOUBLES : nullptr, lm ? lm + o * b->lm_cap : nullptr, lmn ? lmn + o * 2 : nullptr); };
         s0 += (size_t)g->S;
         std::lock_guard<std::mutex> lk(g->wmu);
         g->jobs.push_back(std::move(job));
@@ -2030,6 +2037,35 @@ AV_EXPORT int av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host)
     if (!b || !cov_host) { av_set_error("av_msckf_batch_next_odom_cov: bad arguments"); return AV_E_INVALID; }
     if (!b->odom_cov) { av_set_error("av_msckf_batch_next_odom_cov: the odometry covariance is off (av_msckf_batch_set_odom_cov)"); return AV_E_INVALID; }
     b->next_cov = cov_host;
+    return AV_OK;
+}
+
+// Landmark map (airvision.h, "Landmark map").  set: before the batch's first step, like the odometry covariance -- the groups size
+// their record buffers when they prepare the device-resident path.  next: the destination of the next step's records and counts.
+static_assert(sizeof(av_landmark) == AV_LANDMARK_BYTES && sizeof(DLandmark) == AV_LANDMARK_BYTES, "av_landmark layout");
+static_assert(LM_USED == AV_LM_USED && LM_REJECTED == AV_LM_REJECTED && LM_TRACKED == AV_LM_TRACKED && LM_NEW == AV_LM_NEW, "AV_LM_* bits");
+AV_EXPORT int av_msckf_batch_set_landmarks(av_msckf_batch* b, int cap)
+{
+    if (!b || cap < 0 || cap > (1 << 20)) { av_set_error("av_msckf_batch_set_landmarks: bad arguments"); return AV_E_INVALID; }
+    std::vector<av_msckf_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    if (cap) for (av_msckf_batch* g : parts) if (!g->dev) {
+        av_set_error("av_msckf_batch_set_landmarks: the landmark map needs the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)");
+        return AV_E_INVALID;
+    }
+    bool stepped = b->dev_seq > 0;
+    for (av_msckf_batch* g : parts) if (g->n_steps > 0 || (g->dev && g->dev->cap > 0)) stepped = true;
+    if (stepped) { av_set_error("av_msckf_batch_set_landmarks: the batch has stepped; the landmark map is switched before the first step"); return AV_E_INVALID; }
+    b->lm_cap = cap; b->next_lm = nullptr; b->next_lmn = nullptr;
+    for (av_msckf_batch* g : parts) g->lm_cap = cap;
+    return AV_OK;
+}
+
+AV_EXPORT int av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t* n)
+{
+    if (!b || !rec || !n) { av_set_error("av_msckf_batch_next_landmarks: bad arguments"); return AV_E_INVALID; }
+    if (b->lm_cap <= 0) { av_set_error("av_msckf_batch_next_landmarks: the landmark map is off (av_msckf_batch_set_landmarks)"); return AV_E_INVALID; }
+    b->next_lm = rec; b->next_lmn = n;
     return AV_OK;
 }
 

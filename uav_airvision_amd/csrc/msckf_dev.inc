@@ -20,6 +20,9 @@
 //                reset, publish
 //   dk_finish_cov  (instead of dk_finish when av_msckf_batch_set_odom_cov is on) the same, and between the publish and the reset the
 //                stream's odometry-covariance record (120 doubles), read back next to the pose
+//   dk_mid_lm, dk_finish_lm, dk_finish_cov_lm  (instead of dk_mid / dk_finish / dk_finish_cov when av_msckf_batch_set_landmarks is on)
+//                the same, and the stream's landmark records: the lost-feature update's ahead of dk_mid's rebuild of the per-phase
+//                feature arrays, the pruning update's ahead of dk_finish's camera removal
 //
 // Per-stream capacity failures are recorded in the stream's state (DState::failed) and stop that stream only.
 
@@ -509,6 +512,72 @@ __device__ void dev_find_redundant(const DevArgs& a, int s, const DState& D, int
 }
 
 // ------------------------------------------------------------------------------------------------
+// Landmark map (include/airvision.h, "Landmark map"): the triangulated features of the step's two updates, per stream, as records of
+// 40 bytes.  The per-phase feature arrays hold one update at a time, so the lost-feature records are written by dk_mid_lm before it
+// rebuilds them and the pruning records by the dk_finish_*lm instances before the two frames leave the store.  ONE wavefront of the
+// stream's workgroup writes, 64 candidates per trip, in candidate (= dict) order: a ballot and a prefix count of "publishes" give the
+// slot, a prefix sum of 4 n_obs - 3 over the gated-in candidates, carried across trips, re-applies the 1,500-row cut of
+// msckf.py:667-668 (the device evaluates every candidate; the feature whose rows take the sum over 1,500 is still used), plain vector
+// stores write the record.  No atomics: the order is the same at both launch shapes.
+// ------------------------------------------------------------------------------------------------
+enum { LM_USED = 1, LM_REJECTED = 2, LM_TRACKED = 4, LM_NEW = 8 };
+struct DLandmark { long long id; double p[3]; int flags; int n_obs; };
+static_assert(sizeof(DLandmark) == 40, "av_landmark is 40 bytes");
+struct LmOut { DLandmark* rec; int* n; int cap; };      // [S][cap] records, [S][2] counts (had, written)
+
+// call with threadIdx.x < 64 (the first wavefront, all of its lanes).  prune = false: the lost-feature candidates, counts start at 0;
+// true: the pruning candidates that got their position in this step (dev_build_candidates left tmp_b >= 0 for them, the triangulation
+// f_valid), appended behind the lost-feature records
+__device__ __forceinline__ void dev_landmarks(const DevArgs& a, int s, const LmOut& L, bool prune)
+{
+    const int lane = threadIdx.x;
+    int* n = L.n + 2 * (size_t)s;
+    const DState* D = a.st + s;
+    if (!D->active) { if (lane == 0) { n[0] = 0; n[1] = 0; } return; }      // (wavefront-uniform)
+    const size_t f0 = (size_t)s * a.FS, mo = (size_t)s * a.mcap;
+    const int* tmp_b = a.tmp_b + (size_t)s * a.cap;
+    DLandmark* rec = L.rec + (size_t)s * L.cap;
+    const int nc = a.n_cand[s];
+    int total = prune ? n[0] : 0, rows = 0;
+    for (int base = 0; base < nc; base += 64) {
+        const int k = base + lane;
+        const size_t f = f0 + k;
+        int pub = 0, fs = 0, nobs = 0, flags = 0, gated = 0;
+        if (k < nc) {
+            fs = a.f_mslot[f];
+            const int pass = a.pass[f];
+            if (prune) {
+                pub = tmp_b[k] >= 0 && a.f_valid[f] != 0;
+                nobs = a.m_nobs[mo + fs];
+                flags = LM_TRACKED | LM_NEW | (pass ? LM_USED : LM_REJECTED);
+            } else {
+                pub = a.f_valid[f] != 0;
+                nobs = a.f_off[f + 1] - a.f_off[f];         // (the feature has left the store: its observations are the CSR's)
+                gated = pub && pass;
+                flags = a.m_init[mo + fs] ? 0 : LM_NEW;     // (the lost features' triangulation does not touch the table's flag)
+            }
+        }
+        const unsigned long long m = __ballot(pub);
+        const int slot = total + __popcll(m & ((1ull << lane) - 1ull));
+        if (!prune) {
+            const int v = gated ? 4 * nobs - 3 : 0;
+            int incl = v;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+            if (rows + incl - v <= 1500) flags |= gated ? LM_USED : LM_REJECTED;
+            rows += __shfl(incl, 63);
+        }
+        if (pub && slot < L.cap) {
+            DLandmark r;
+            r.id = a.m_id[mo + fs]; r.p[0] = a.f_pos[3 * f]; r.p[1] = a.f_pos[3 * f + 1]; r.p[2] = a.f_pos[3 * f + 2]; r.flags = flags; r.n_obs = nobs;
+            rec[slot] = r;
+        }
+        total += __popcll(m);
+    }
+    if (lane == 0) { n[0] = total; n[1] = total < L.cap ? total : L.cap; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // dk_mid: the lost-feature update lands in the state (msckf.py:568-595); then the selection half of prune_cam_state_buffer (:712-757)
 // ------------------------------------------------------------------------------------------------
 // returns (to every thread) the number of pruning candidates of stream s, -1 if the stream does not prune in this step; the
@@ -544,6 +613,15 @@ __device__ __forceinline__ int dk_mid_body(const DevArgs& a, int s, AvsStore* Vo
 __global__ __launch_bounds__(256, 5) void dk_mid(DevArgs a)
 {
     AV_FILTER_PRIO();
+    AvsStore V;
+    (void)dk_mid_body(a, blockIdx.x, &V);
+}
+// dk_mid + the landmark records of the lost-feature update (av_msckf_batch_set_landmarks), written while its feature arrays stand
+__global__ __launch_bounds__(256, 5) void dk_mid_lm(DevArgs a, LmOut L)
+{
+    AV_FILTER_PRIO();
+    if (threadIdx.x < 64) dev_landmarks(a, blockIdx.x, L, false);
+    __syncthreads();                                          // (the other wavefronts rebuild the arrays the writer reads)
     AvsStore V;
     (void)dk_mid_body(a, blockIdx.x, &V);
 }
@@ -613,9 +691,10 @@ __device__ __forceinline__ void dev_odom_cov(const DevArgs& a, int s, const DSta
     }
 }
 
-// COV: the instance that also writes the stream's odometry-covariance record (dk_finish_cov); false: dk_finish as it always was
-template <bool COV>
-__device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* odom)
+// COV: the instance that also writes the stream's odometry-covariance record (dk_finish_cov); LM: the one that also appends the pruning
+// update's landmark records (dk_finish_lm); both false: dk_finish as it always was
+template <bool COV, bool LM>
+__device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* odom, const LmOut& L)
 {
     __shared__ int red[8], s_reset;
     const int tid = threadIdx.x;
@@ -624,6 +703,15 @@ __device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* 
     if (D->active && D->prune) {
         dev_apply_update(a, s, D);                            // (a.stacked = the pruning phase's stacked rows here)
         if (tid == 0 && D->failed) D->active = 0;
+        __syncthreads();
+    }
+    if constexpr (LM) {
+        // the pruning candidates' records, while tmp_b, m_nobs and the feature arrays stand (the removal below changes them); a stream that
+        // has stopped publishes nothing, its lost-feature records of this step included
+        if (tid < 64) {
+            if (!D->active) { if (tid == 0) { L.n[2 * (size_t)s] = 0; L.n[2 * (size_t)s + 1] = 0; } }
+            else if (D->prune) dev_landmarks(a, s, L, true);
+        }
         __syncthreads();
     }
     if (D->active && D->prune) {
@@ -683,13 +771,24 @@ __device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* 
 __global__ __launch_bounds__(256, 5) void dk_finish(DevArgs a)
 {
     AV_FILTER_PRIO();
-    dk_finish_body<false>(a, blockIdx.x, nullptr);
+    dk_finish_body<false, false>(a, blockIdx.x, nullptr, LmOut{});
 }
 // dk_finish + the odometry-covariance record of every stream (av_msckf_batch_set_odom_cov), odom = [S][ODOM_COV_DOUBLES]
 __global__ __launch_bounds__(256, 5) void dk_finish_cov(DevArgs a, double* odom)
 {
     AV_FILTER_PRIO();
-    dk_finish_body<true>(a, blockIdx.x, odom);
+    dk_finish_body<true, false>(a, blockIdx.x, odom, LmOut{});
+}
+// dk_finish / dk_finish_cov + the landmark records of the pruning update (av_msckf_batch_set_landmarks)
+__global__ __launch_bounds__(256, 5) void dk_finish_lm(DevArgs a, LmOut L)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<false, true>(a, blockIdx.x, nullptr, L);
+}
+__global__ __launch_bounds__(256, 5) void dk_finish_cov_lm(DevArgs a, double* odom, LmOut L)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<true, true>(a, blockIdx.x, odom, L);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -718,6 +817,7 @@ struct DevSlot {
     long long* ids_d = nullptr; double* uv_d = nullptr; int* n_d = nullptr;      // the message on the device (copied from the host arrays or from the front-end's buffers)
     double* out_h = nullptr; int* cnt_h = nullptr;                                // pinned landing zones of the step's only read-back
     double* odom_h = nullptr;                                                     // [S][ODOM_COV_DOUBLES] pinned, the odometry-covariance records of the step (NULL: the feature is off)
+    DLandmark* lm_h = nullptr; int* lmn_h = nullptr;                              // [S][lm.cap] / [S][2] pinned, the landmark records and counts of the step (NULL: the feature is off)
     hipEvent_t done = nullptr;
     hipEvent_t t0[2] = {nullptr, nullptr}, t1[2] = {nullptr, nullptr}; bool t_used[2] = {false, false};      // av_msckf_batch_work: device time of the two phase chains
     bool in_flight = false;
@@ -730,6 +830,7 @@ struct DevPath {
     double* out_d = nullptr; int* stacked0 = nullptr; int* stacked1 = nullptr; UpdArgs* updbase = nullptr; UpdArgs* upd = nullptr;
     DCov* cov_d = nullptr;           // [S] dk_begin -> dk_cov
     double* odom_d = nullptr;        // [S][ODOM_COV_DOUBLES] dk_finish_cov's records (NULL: av_msckf_batch_set_odom_cov is off)
+    LmOut lm = {nullptr, nullptr, 0};      // [S][cap] records and [S][2] counts of dk_mid_lm / dk_finish_*lm (rec NULL: av_msckf_batch_set_landmarks is off)
     int dk_wg = 0;                   // AV_DK_WG read when the path is prepared: 64 / 256 = workgroup size of the per-stream kernels, 0 = by the group's stream count
     int launched_wg = 0;             // workgroup size dev_enqueue launched them with in the last enqueued step (0: no step yet); av_msckf_batch_launch_shape
     int* cols = nullptr; int* blk_row = nullptr; int* blk_len = nullptr; int* clist = nullptr; int* again = nullptr;

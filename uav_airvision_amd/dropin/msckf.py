@@ -18,7 +18,7 @@ import numpy as np
 from feature import BaseFeature
 from utils import Isometry3d, to_rotation
 from uav_airvision_amd import _native as N
-from uav_airvision_amd.msckf_ops import BatchedMSCKF, unpack_odom_cov
+from uav_airvision_amd.msckf_ops import BatchedMSCKF, unpack_landmarks, unpack_odom_cov
 
 _vio_result = namedtuple('vio_result', ['timestamp', 'pose', 'velocity', 'cam0_pose'])
 
@@ -102,7 +102,14 @@ class MSCKF(object):
         self.last_covariance = None
         if self._cov_on and not np.array_equal(np.asarray(config.T_imu_body, dtype=np.float64), np.identity(4)):
             raise ValueError('config.publish_covariance needs config.T_imu_body = identity: the covariance is not conjugated into a body frame')
-        self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap, odom_cov=self._cov_on)
+        # config.publish_landmarks = True (no reference counterpart; default off): `last_landmarks` holds the landmark records
+        # (msckf_ops.LANDMARK_DTYPE, at most config.landmark_cap) of the last feature_callback, positions mapped by T_imu_body into the
+        # world frame of the published pose; `last_landmarks_dropped` = records of that frame beyond the cap.  vio_result is unchanged.
+        self._lm_on = bool(getattr(config, 'publish_landmarks', False))
+        self.last_landmarks = None
+        self.last_landmarks_dropped = 0
+        self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap, odom_cov=self._cov_on, landmarks=self._lm_on,
+                                 landmark_cap=int(getattr(config, 'landmark_cap', 256)))
         self.state_server = StateServer(self._flt)
         self.map_server = _MapView(self._flt)
         # class-level statics the reference sets in its constructor (msckf.py:128-150), kept for code that reads them
@@ -148,7 +155,13 @@ class MSCKF(object):
         if n:
             ids[0, :n] = [f.id for f in feats]
             uv[0, :n] = [(f.u0, f.v0, f.u1, f.v1) for f in feats]
-        out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None)
+        out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None, landmarks=True if self._lm_on else None)
+        if self._lm_on:
+            rec, cnt = self._flt.last_landmarks
+            lm = unpack_landmarks(rec, cnt, 0).copy()
+            lm['p'] = lm['p'] @ self.T_imu_body.R.T + self.T_imu_body.t
+            self.last_landmarks = lm
+            self.last_landmarks_dropped = int(cnt[0, 0] - cnt[0, 1])
         if self._cov_on and out[0, 0] == 1.0:
             self.last_covariance = unpack_odom_cov(self._flt.last_cov[0])
         if self._capture:

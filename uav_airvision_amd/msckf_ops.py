@@ -294,12 +294,24 @@ def pack_odom_cov(Cm):
     return np.ascontiguousarray(Cm[..., _ODOM_IU[0], _ODOM_IU[1]])
 
 
+# ---- landmark map (include/airvision.h, "Landmark map") ------------------------------------------------------------------------
+LANDMARK_DTYPE = np.dtype([('id', np.int64), ('p', np.float64, (3,)), ('flags', np.int32), ('n_obs', np.int32)])      # av_landmark, AV_LANDMARK_BYTES
+assert LANDMARK_DTYPE.itemsize == 40
+LM_USED, LM_REJECTED, LM_TRACKED, LM_NEW = 1, 2, 4, 8               # AV_LM_*
+
+
+def unpack_landmarks(rec, n, s):
+    """The written records of stream `s`: rec LANDMARK_DTYPE[S, cap] and n int32[S, 2] as a step returns them -> rec[s, :n[s, 1]]
+    (n[s, 0] - n[s, 1] records were dropped to the cap)."""
+    return rec[s, :int(n[s, 1])]
+
+
 class BatchedMSCKF(object):
     """S independent filters stepped together (av_msckf_batch_* C ABI): C++ bookkeeping inside the
     library, one batched launch per numeric phase.  Mirrors MSCKF.imu_callback / feature_callback
     (reference: src/msckf.py:162-228) for many streams at once."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64):
         """rows_cap: rows of the per-stream block buffer.  None = sized by the library from the capacity of the first
         feature message (the camera-pruning update stacks 5 rows per feature, the lost-feature update at most 1500 + one
         block); `max_features`, when given, sizes it up front instead.  With the automatic size a later step with a wider
@@ -308,7 +320,9 @@ class BatchedMSCKF(object):
         max_features when the width of the feature arrays can vary.  An explicit rows_cap is never grown.
         config.max_cam_state_size <= 24 (reference: 20).
         odom_cov=True: every step also computes the covariance of what it publishes (ODOM_COV_FIELDS; `step / submit / submit_dev(...,
-        cov=)`, `last_cov`, `unpack_odom_cov`).  Device-resident filter only."""
+        cov=)`, `last_cov`, `unpack_odom_cov`).  Device-resident filter only.
+        landmarks=True: every step also publishes the features its two updates triangulated, up to landmark_cap records per stream
+        (LANDMARK_DTYPE; `step / submit / submit_dev(..., landmarks=)`, `last_landmarks`, `unpack_landmarks`).  Device-resident filter only."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -339,6 +353,39 @@ class BatchedMSCKF(object):
                 except Exception:
                     self.close()
                     raise
+            self.landmark_cap = int(landmark_cap) if landmarks else 0
+            self.last_landmarks = None     # (records LANDMARK_DTYPE[S, cap], counts int32[S, 2]) of the most recent step that was given a pair
+            if landmarks:
+                try:
+                    if self.landmark_cap < 1:
+                        raise ValueError('landmark_cap must be at least 1')
+                    N.check(N.lib().av_msckf_batch_set_landmarks(self._h, self.landmark_cap))
+                except Exception:
+                    self.landmark_cap = 0
+                    self.close()
+                    raise
+
+    def set_landmarks(self, cap):
+        """av_msckf_batch_set_landmarks: cap records per stream and step (0: off); before the first step only."""
+        N.check(N.lib().av_msckf_batch_set_landmarks(self._h, int(cap)))
+        self.landmark_cap = int(cap)
+
+    def _next_landmarks(self, lm):
+        """The (records, counts) pair of the next step (None: the step has none), handed to the library.  lm: None, True (allocate) or
+        a pair of C-contiguous arrays LANDMARK_DTYPE[S, landmark_cap], int32[S, 2]."""
+        if lm is None or lm is False:
+            return None
+        if not self.landmark_cap:
+            raise ValueError('landmarks= needs BatchedMSCKF(..., landmarks=True)')
+        if lm is True:
+            lm = (np.zeros((self.S, self.landmark_cap), dtype=LANDMARK_DTYPE), np.zeros((self.S, 2), dtype=np.int32))
+        rec, n = lm
+        if not (isinstance(rec, np.ndarray) and rec.dtype == LANDMARK_DTYPE and rec.shape == (self.S, self.landmark_cap) and rec.flags['C_CONTIGUOUS']
+                and isinstance(n, np.ndarray) and n.dtype == np.int32 and n.shape == (self.S, 2) and n.flags['C_CONTIGUOUS']):
+            raise ValueError('landmarks must be a pair of C-contiguous arrays LANDMARK_DTYPE[%d, %d], int32[%d, 2]' % (self.S, self.landmark_cap, self.S))
+        N.check(N.lib().av_msckf_batch_next_landmarks(self._h, rec.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p)))
+        self.last_landmarks = (rec, n)
+        return self.last_landmarks
 
     def set_odom_cov(self, enable):
         """av_msckf_batch_set_odom_cov: before the first step only."""
@@ -382,10 +429,12 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_push_imu(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                 g.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), len(si)))
 
-    def step(self, ids, uv, n_feat, timestamps, cov=None):
+    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None):
         """ids int64[S,cap], uv float64[S,cap,4], n_feat int32[S], timestamps float64[S] (host arrays).
         Returns float64[S,12]: published, t, p(3), q(4), v(3).  cov (odom_cov=True): a float64[S,120] array that takes the step's
-        odometry-covariance records, or True to have one allocated; it is `last_cov` afterwards."""
+        odometry-covariance records, or True to have one allocated; it is `last_cov` afterwards.  landmarks (landmarks=True): a pair of
+        arrays (LANDMARK_DTYPE[S, landmark_cap], int32[S, 2]) that takes the step's landmark records and counts, or True to have them
+        allocated; the pair is `last_landmarks` afterwards."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
@@ -393,50 +442,53 @@ class BatchedMSCKF(object):
         cap = ids.shape[1]
         out = np.zeros((self.S, 12))
         cov = self._next_cov(cov)
+        lm = self._next_landmarks(landmarks)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_step(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                 nf.ctypes.data_as(C.c_void_p), cap, ts.ctypes.data_as(C.c_void_p),
                                                 out.ctypes.data_as(C.c_void_p), N.current_stream()))
         return out
 
-    def submit(self, ids, uv, n_feat, timestamps, cov=None):
+    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None):
         """Queue one step (av_msckf_batch_submit) and return its float64[S,12] output array, which is filled once the
         step has retired -- i.e. after a `wait(k)` that leaves fewer than the steps submitted after it pending.  The
         stream groups of the batch run behind their queues independently of each other.  cov: as in `step`; the array (`last_cov`) is
-        filled when the step retires, like the output array."""
+        filled when the step retires, like the output array; landmarks: likewise."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         out = np.zeros((self.S, 12))
         cov = self._next_cov(cov)
+        lm = self._next_landmarks(landmarks)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_submit(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                   nf.ctypes.data_as(C.c_void_p), ids.shape[1], ts.ctypes.data_as(C.c_void_p),
                                                   out.ctypes.data_as(C.c_void_p), N.current_stream()))
-        self._inflight.append((ids, uv, nf, ts, out, cov))     # the library reads / writes these until the step retires
+        self._inflight.append((ids, uv, nf, ts, out, cov, lm))     # the library reads / writes these until the step retires
         return out
 
     def device_resident(self):
         """True when the filter state and the observation map live on the device (the default; `submit_dev` needs it)."""
         return N.lib().av_msckf_batch_device_resident(self._h) == 1
 
-    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None):
+    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None):
         """Queue one step on the feature message `engine` (a FrontendEngine with the same streams) has just published, read
         where it lies on the device (av_msckf_batch_submit_dev): no host round trip between the front-end and the filter.
         msg_stream: the stream handle the engine's step ran on (default: torch's current stream, i.e. call this right after
         `engine.step` on the same stream).  The filter's kernels run on the current stream / the stream groups' own streams.
-        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov: as in `submit`."""
+        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks: as in `submit`."""
         ids, uv, n, cap = engine.features_dev()
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         assert ts.shape == (self.S,) and engine.n_streams == self.S
         out = np.zeros((self.S, 12))
         cov = self._next_cov(cov)
+        lm = self._next_landmarks(landmarks)
         with torch.cuda.device(self.device):
             ms = N.current_stream() if msg_stream is None else msg_stream
             N.check(N.lib().av_msckf_batch_submit_dev(self._h, ids, uv, n, cap, ts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
                                                       ms, N.current_stream()))
-        self._inflight.append((ts, out, cov))
+        self._inflight.append((ts, out, cov, lm))
         return out
 
     def wait(self, max_pending=0):

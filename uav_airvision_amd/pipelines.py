@@ -190,7 +190,9 @@ class FilterSet(object):
     """One BatchedMSCKF per part of an EngineSet, driven by the same workers (a part's front-end step, its prestage and its filter
     hand-over stay in order on the part's thread).  Keywords go to every part's BatchedMSCKF: odom_cov=True switches the odometry
     covariance on, `submit_dev(..., cov=True)` then gives every part a records array and `last_cov` joins them ([S, 120] once the
-    step has retired), as the returned view joins the poses."""
+    step has retired), as the returned view joins the poses.  landmarks=True (with landmark_cap) switches the landmark map on,
+    `submit_dev(..., landmarks=True)` gives every part its pair of arrays and `last_landmarks` = (records view, counts view) joins them
+    ([S, landmark_cap] and [S, 2])."""
 
     def __init__(self, config, engine_set, device=0, **kw):
         from .msckf_ops import BatchedMSCKF
@@ -199,6 +201,8 @@ class FilterSet(object):
         self.flts = [BatchedMSCKF(config, hi - lo, device=device, **kw) for lo, hi in self.parts]
         self.odom_cov = bool(kw.get('odom_cov', False))
         self.last_cov = None
+        self.landmarks = bool(kw.get('landmarks', False))
+        self.last_landmarks = None
 
     def device_resident(self):
         return all(f.device_resident() for f in self.flts)
@@ -208,14 +212,21 @@ class FilterSet(object):
             if len(rows[0]):
                 self.es.pipes[p].put(lambda f=self.flts[p], r=rows: f.push_imu(*r))
 
-    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None):
+    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None, landmarks=None):
         assert engine_set is self.es
         if cov is not None and cov is not True:
             raise ValueError('FilterSet.submit_dev: cov is None or True (every part allocates its own records array)')
         if cov and not self.odom_cov:
             raise ValueError('cov= needs FilterSet(..., odom_cov=True)')
+        if landmarks is not None and landmarks is not True:
+            raise ValueError('FilterSet.submit_dev: landmarks is None or True (every part allocates its own arrays)')
+        if landmarks and not self.landmarks:
+            raise ValueError('landmarks= needs FilterSet(..., landmarks=True)')
         ts = np.asarray(timestamps, dtype=np.float64)
         out = _OutView(len(self.parts))
+        lms = (_OutView(len(self.parts)), _OutView(len(self.parts))) if landmarks else None
+        if landmarks:
+            self.last_landmarks = lms
         covs = _OutView(len(self.parts)) if cov else None
         if cov:
             self.last_cov = covs
@@ -224,7 +235,9 @@ class FilterSet(object):
                 w = self.es.pipes[p]
                 ms = N.current_stream()                      # the part's front-end stream: the message is copied behind its step
                 with torch.cuda.stream(w.fstream):
-                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, cov=cov)
+                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, cov=cov, landmarks=landmarks)
+                    if landmarks:
+                        lms[0].parts[p], lms[1].parts[p] = self.flts[p].last_landmarks
                     if cov:
                         covs.parts[p] = self.flts[p].last_cov
             self.es.pipes[p].put(job)

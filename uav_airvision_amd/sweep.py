@@ -58,16 +58,21 @@ class BatchedRunner(object):
     arrays of the front-end and the filter's float64[k, 12] output of the same step (parity tests); without it the
     filter runs one step behind the front-end (queued), the way bench.py pipelines them.
     odom_cov=True: every step also brings the odometry covariance of what it publishes (BatchedMSCKF(odom_cov=True)); after `run`,
-    `cov_rows[s]` is float64[n, 121], one row `t` + the 120-double record per row of stream s's trajectory."""
+    `cov_rows[s]` is float64[n, 121], one row `t` + the 120-double record per row of stream s's trajectory.
+    landmark_cap > 0: every step also brings its landmark records (BatchedMSCKF(landmarks=True, landmark_cap=)); after `run`,
+    `lm_rows[s]` is (float64[n] pose times, LANDMARK_DTYPE[n] records, records dropped to the cap) of stream s."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False, landmark_cap=0):
         from .frontend import FrontendEngine
         from .msckf_ops import BatchedMSCKF
         self.config, self.S, self.device = config, int(n_streams), int(device)
         self.eng = FrontendEngine(config, n_streams=self.S, device=self.device)
         self.odom_cov = bool(odom_cov)
-        self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features, odom_cov=self.odom_cov)
+        self.landmark_cap = int(landmark_cap)
+        self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features, odom_cov=self.odom_cov,
+                                landmarks=self.landmark_cap > 0, landmark_cap=max(1, self.landmark_cap))
         self.cov_rows = None
+        self.lm_rows = None
         self.frames_done = np.zeros(self.S, np.int64)
         self._fstream = None
         self.plan, self.steps_done, self.times = None, 0, None
@@ -129,11 +134,19 @@ class BatchedRunner(object):
         covs = [[] for _ in range(S)]
         want = True if self.odom_cov else None
 
-        def record(out, cov=None):
+        lms = [[[], [], 0] for _ in range(S)]             # per stream: pose times, record arrays, records dropped to the cap
+        want_lm = True if self.landmark_cap > 0 else None
+
+        def record(out, cov=None, lm=None):
             for s in np.nonzero(out[:, 0] > 0.5)[0]:
                 traj[s].append(out[s, 1:9].copy())
                 if cov is not None:
                     covs[s].append(np.concatenate([out[s, 1:2], cov[s]]))
+                if lm is not None and lm[1][s, 1] > 0:
+                    rec = lm[0][s, :lm[1][s, 1]].copy()
+                    lms[s][0].append(np.full(len(rec), out[s, 1])); lms[s][1].append(rec)
+                if lm is not None:
+                    lms[s][2] += int(lm[1][s, 0] - lm[1][s, 1])
 
         times, t_ref = self.times, getattr(eng, '_exposure_ref', None)
 
@@ -206,8 +219,8 @@ class BatchedRunner(object):
             if on_step is not None:
                 ids, uv, n = eng.read_features_raw()
                 n[ts_f < 0] = 0
-                out = flt.step(ids, uv, n, ts_f, cov=want)
-                record(out, flt.last_cov)
+                out = flt.step(ids, uv, n, ts_f, cov=want, landmarks=want_lm)
+                record(out, flt.last_cov, flt.last_landmarks)
                 on_step(step, ts_f, ids, uv, n, out)
             elif dev:
                 # the filter reads the published message where it lies on the device; nothing of this step is waited for here:
@@ -219,7 +232,7 @@ class BatchedRunner(object):
                     self._fstream = torch.cuda.Stream(device=self.device)
                 ms = N.current_stream()                   # the stream the front-end's step was enqueued on
                 with torch.cuda.stream(self._fstream):    # the filter's kernels (one group: here) overlap the next frame's front-end
-                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want), flt.last_cov))
+                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want, landmarks=want_lm), flt.last_cov, flt.last_landmarks))
                 flt.wait(2)
                 while len(inflight) > 2:
                     record(*inflight.pop(0))
@@ -227,7 +240,7 @@ class BatchedRunner(object):
                 eng.read_features_begin(step & 1)
                 ids, uv, n = eng.read_features_end(step & 1)
                 n[ts_f < 0] = 0
-                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want), flt.last_cov))
+                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want, landmarks=want_lm), flt.last_cov, flt.last_landmarks))
                 flt.wait(1)                               # at most one step behind: the next frames are decoded meanwhile
                 while len(inflight) > 1:
                     record(*inflight.pop(0))
@@ -237,12 +250,17 @@ class BatchedRunner(object):
             record(*pair)
         self.steps_done = step
         self.cov_rows = [np.array(c, dtype=np.float64).reshape(-1, 121) for c in covs] if self.odom_cov else None
+        if self.landmark_cap > 0:
+            from .msckf_ops import LANDMARK_DTYPE
+            self.lm_rows = [(np.concatenate(t) if t else np.zeros(0), np.concatenate(r) if r else np.zeros(0, LANDMARK_DTYPE), d) for t, r, d in lms]
         return [np.array(t, dtype=np.float64).reshape(-1, 8) for t in traj]
 
 
-def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None):
+def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None, lm_rows=None, landmark_cap=64):
     """Open (path, offset) pairs as EuRoC datasets and run them as one batch; returns (trajectories, datasets).
     cov_rows (a list): the batch runs with the odometry covariance on and the list receives, per stream, float64[n, 121] rows `t` + record.
+    lm_rows (a list): the batch runs with the landmark map on (landmark_cap records per stream and step) and the list receives, per
+    stream, (pose times float64[n], records LANDMARK_DTYPE[n], records dropped to the cap).
     stats (a dict) receives the batch's stream-frames, steps, distinct frames decoded and the seconds its stepping loop took."""
     import time
     from .euroc import EuRoCDataset
@@ -251,12 +269,14 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
         ds = EuRoCDataset(p)
         ds.set_starttime(o)
         dss.append(ds)
-    r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap, odom_cov=cov_rows is not None)
+    r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap, odom_cov=cov_rows is not None, landmark_cap=landmark_cap if lm_rows is not None else 0)
     try:
         t0 = time.perf_counter()
         trajs = r.run(dss, max_frames=max_frames, on_step=on_step, share_frames=share_frames)
         if cov_rows is not None:
             cov_rows.extend(r.cov_rows)
+        if lm_rows is not None:
+            lm_rows.extend(r.lm_rows)
         if stats is not None:
             stats['seconds'] = stats.get('seconds', 0.0) + time.perf_counter() - t0
             stats['stream_frames'] = stats.get('stream_frames', 0) + int(r.frames_done.sum())
@@ -310,6 +330,11 @@ def make_parser():
                     help='also write, next to every trajectory file, output_<sequence>_offset<o>_cov.txt: per published pose one line `t` + the 120 numbers of its '
                          'odometry covariance (upper triangle of the 15 x 15 matrix over p, theta, v, p_c, theta_c; include/airvision.h); with ground truth the '
                          'report gains anees_pos, the mean normalised position error squared (3 for a consistent filter)')
+    ap.add_argument('--landmarks', action='store_true',
+                    help='also write, next to every trajectory file, output_<sequence>_offset<o>_map.txt: the landmark records of every step, one line '
+                         '`t id x y z flags n_obs` each (t = the time of the pose of the step; include/airvision.h, "Landmark map"); the report states how many '
+                         'records were dropped to the cap')
+    ap.add_argument('--landmark-cap', type=int, default=64, metavar='N', help='--landmarks: records per stream and step (default 64)')
     ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
     ap.add_argument('--ransac-threshold', type=float, default=None, metavar='T', help='inlier error in pixels (config.ransac_threshold, default 3)')
     ap.add_argument('--clahe', action='store_true', help='equalise every frame (CLAHE) ahead of the pyramids, LK and FAST (config.use_clahe; off = the reference front-end)')
@@ -417,7 +442,7 @@ def main(argv=None):
         ap.error('--root or --make-synthetic is required')
     jobs = shard.broadcast_object([(s, o) for s in args.sequences for o in args.offsets] if rank == 0 else None)
     mine = shard.partition(len(jobs), world, rank)
-    local_traj, local_cov, report, stats = {}, {}, {}, {}
+    local_traj, local_cov, local_lm, report, stats = {}, {}, {}, {}, {}
     import time
     if world > 1:
         dist.barrier()
@@ -426,12 +451,16 @@ def main(argv=None):
         chunk = mine[b0:b0 + args.batch]
         cfg.image_format = batch_pixel_format([os.path.join(root, jobs[j][0]) for j in chunk], args.pixel_format)
         cov_rows = [] if args.covariance else None
+        lm_rows = [] if args.landmarks else None
         trajs, dss = run_batched(cfg, [os.path.join(root, jobs[j][0]) for j in chunk], [jobs[j][1] for j in chunk], device=local, max_frames=args.max_frames,
-                                 share_frames=not args.no_share_frames, stats=stats, **({'cov_rows': cov_rows} if args.covariance else {}))
+                                 share_frames=not args.no_share_frames, stats=stats, **({'cov_rows': cov_rows} if args.covariance else {}),
+                                 **({'lm_rows': lm_rows, 'landmark_cap': args.landmark_cap} if args.landmarks else {}))
         for i, (j, traj, ds) in enumerate(zip(chunk, trajs, dss)):
             local_traj[j] = traj
             if cov_rows is not None:
                 local_cov[j] = cov_rows[i]
+            if lm_rows is not None:
+                local_lm[j] = lm_rows[i]
             gt = ds.groundtruth_array()
             if len(gt) and len(traj) > 20:
                 a, r = ate(traj, gt), rte(traj, gt)
@@ -440,7 +469,7 @@ def main(argv=None):
                     report[j]['anees_pos'] = nees(traj, unpack_odom_cov(cov_rows[i][:, 1:])[:, 0:3, 0:3], gt)[1]
     elapsed = shard.max_over_ranks(time.perf_counter() - t_all)          # barrier before, max over ranks after: the bench contract's clock
     allt = shard.gather_trajectories(local_traj, len(jobs), world, rank)
-    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov})
+    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm})
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         for j, (seq, off) in enumerate(jobs):
@@ -452,7 +481,17 @@ def main(argv=None):
                 with open(os.path.join(args.out, 'output_%s_offset%d_cov.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
                     for row in rows:
                         f.write('%.6f ' % row[0] + ' '.join('%.9e' % v for v in row[1:]) + '\n')
+        lm_dropped = {}
+        for r in per_rank if args.landmarks else []:
+            for j, (ts, recs, dropped) in r['lm'].items():
+                lm_dropped[j] = (len(recs), int(dropped))
+                with open(os.path.join(args.out, 'output_%s_offset%d_map.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
+                    for t, rec in zip(ts, recs):
+                        f.write('%.6f %d %.9f %.9f %.9f %d %d\n' % (t, rec['id'], rec['p'][0], rec['p'][1], rec['p'][2], rec['flags'], rec['n_obs']))
         rep = sweep_report(jobs, per_rank, elapsed, world)
+        if args.landmarks:
+            rep['landmarks'] = dict(cap=args.landmark_cap, records=[lm_dropped.get(j, (0, 0))[0] for j in range(len(jobs))],
+                                    dropped_to_cap=[lm_dropped.get(j, (0, 0))[1] for j in range(len(jobs))])
         if cfg.use_clahe:
             rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
         if args.pixel_format != 'gray8':
