@@ -1006,6 +1006,50 @@ int  av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host);
 typedef struct av_landmark { int64_t id; double p[3]; int32_t flags; int32_t n_obs; } av_landmark;
 int  av_msckf_batch_set_landmarks(av_msckf_batch* b, int cap);
 int  av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t* n);
+/* Innovation statistics: what the chi-square gates of a step's two measurement updates decided and how large the corrections were, per
+ * stream and step, riding the step's read-back.  Off by default.  On, every step yields for every stream one av_filter_stats of
+ * AV_FILTER_STATS_BYTES = 128 bytes: two blocks of 64 bytes, upd[0] the lost-feature update (remove_lost_features, msckf.py:614-676),
+ * upd[1] the pruning update (prune_cam_state_buffer, msckf.py:712-786).  Per block, over the update's candidates in map (dict) order:
+ *   n_cand      candidates of the update: lost features with at least three observations; features seen from both camera states that go
+ *   n_pos       ... of them with a valid position (triangulated in this step or in an earlier one; check_motion or a failed
+ *               triangulation leave none)
+ *   n_eval      ... of them the reference would have gated.  Lost-feature update: those its loop reaches before msckf.py:667-668 breaks
+ *               it, i.e. the candidates ahead of which at most 1,500 accepted rows are stacked (the candidate whose rows take the sum
+ *               over 1,500 is still evaluated and, if accepted, used).  Pruning update: n_eval = n_pos.
+ *   n_pass      evaluated and accepted by the gate (gamma < chi2.ppf(0.05, dof)): the features whose rows the update used
+ *   dof_eval    sum of the gate's dof over the evaluated;  dof_pass  over the accepted
+ *   gamma_eval  sum of the Mahalanobis values gamma = r^T (H P H^T + observation_noise I)^-1 r over the evaluated;  gamma_pass  over the accepted
+ *   rows        rows of the stacked update as applied (before any compression), 0 if none was applied
+ *   flags       AV_FS_RAN  an update was applied to the state;  AV_FS_CUT  the 1,500-row cut left candidates unevaluated (n_eval < n_pos)
+ *   dx_pos      |delta_x[12:15]| of the applied update, the position correction in metres; 0 if none
+ *   dx_rot      |delta_x[0:3]|, the orientation correction in radians; 0 if none
+ * The gate's dof is the reference's, not the residual's dimension: a feature seen from M camera states has a residual of 4 M - 3 rows
+ * (stereo observations, three dimensions projected out) and is gated with dof = M - 1 in the lost-feature update and with dof = the
+ * number of involved camera states (always 2) in the pruning update.  The residual dimension follows from the record: over n features
+ * with dof sum d it is 4 d + n for the lost-feature update (M = dof + 1) and 4 d - 3 n for the pruning update (M = dof); for the
+ * accepted features that is `rows`.  gamma_pass is a sum over a distribution the gate has truncated; gamma_eval is not.
+ * Values are those of the device's evaluation: every candidate is gated against the covariance before the update, as in the reference.
+ * A stream that takes no part in the step -- inactive, no frame, failed, or stopped in this step -- gets 128 zero bytes; on a step without
+ * camera pruning upd[1] is zero.  The sums are formed in a fixed order: the same bytes at every launch shape and in every run.
+ * av_msckf_batch_set_stats(b, enable): before the batch's first step (AV_E_INVALID afterwards).  Off, the step launches and reads back
+ * exactly what it did without the feature; on, two per-stream kernels of the step are the instances that also write the blocks (no
+ * launch more) and one more asynchronous copy brings them to a pinned buffer of the step's ring slot: no wait and no allocation inside a
+ * step.  Device-resident filter only: under AV_MSCKF_STORE=host enabling is AV_E_INVALID, with a text that names AV_MSCKF_STORE.
+ * av_msckf_batch_next_stats(b, rec_host): hands over the destination -- n_streams records -- of the NEXT av_msckf_batch_step / _submit /
+ * _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps its own destination.  Stream
+ * groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination computes its records and drops them.
+ * Known limits: sums only, no per-feature values; the gate's dof is the reference's; positions and rows are those of the device's
+ * evaluation; nothing on the host-bookkeeping path. */
+#define AV_FILTER_STATS_BYTES 128
+#define AV_FS_RAN 1
+#define AV_FS_CUT 2
+typedef struct av_update_stats {
+    int32_t n_cand, n_pos, n_eval, n_pass, dof_eval, dof_pass, rows, flags;
+    double gamma_eval, gamma_pass, dx_pos, dx_rot;
+} av_update_stats;
+typedef struct av_filter_stats { av_update_stats upd[2]; } av_filter_stats;
+int  av_msckf_batch_set_stats(av_msckf_batch* b, int enable);
+int  av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host);
 int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);     /* [state dim, camera states, map features] */
 /* Full host-side state of one stream -- every target of measurement_update's injection (msckf.py:568-595), for parity tests
  * (SURVEY 8b get_state): imu32 = [imu_state.timestamp, orientation q(4, JPL xyzw), position(3), velocity(3), gyro_bias(3),

@@ -187,6 +187,15 @@ class Landmark(C.Structure):                     # av_landmark (AV_LANDMARK_BYTE
     _fields_ = [('id', C.c_int64), ('p', C.c_double * 3), ('flags', C.c_int32), ('n_obs', C.c_int32)]
 
 
+class UpdateStats(C.Structure):                  # av_update_stats (64 bytes)
+    _fields_ = [(n, C.c_int32) for n in ('n_cand', 'n_pos', 'n_eval', 'n_pass', 'dof_eval', 'dof_pass', 'rows', 'flags')] + \
+               [(n, C.c_double) for n in ('gamma_eval', 'gamma_pass', 'dx_pos', 'dx_rot')]
+
+
+class FilterStats(C.Structure):                  # av_filter_stats (AV_FILTER_STATS_BYTES = 128)
+    _fields_ = [('upd', UpdateStats * 2)]
+
+
 class FrontendConfig(C.Structure):
     _fields_ = [('width', C.c_int32), ('height', C.c_int32),
                 ('grid_row', C.c_int32), ('grid_col', C.c_int32),
@@ -268,6 +277,8 @@ SIGNATURES = {
     'av_msckf_batch_next_odom_cov': (C.c_int, [_P, _P]),
     'av_msckf_batch_set_landmarks': (C.c_int, [_P, C.c_int]),
     'av_msckf_batch_next_landmarks': (C.c_int, [_P, _P, _P]),
+    'av_msckf_batch_set_stats': (C.c_int, [_P, C.c_int]),
+    'av_msckf_batch_next_stats': (C.c_int, [_P, _P]),
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_msckf_batch_launch_shape': (C.c_int, [_P, C.POINTER(C.c_int32 * 17)]),

@@ -166,3 +166,6 @@ class ConfigEuRoC(object):
         # (up to landmark_cap per frame, positions in the world frame of the published pose; include/airvision.h, "Landmark map")
         self.publish_landmarks = False
         self.landmark_cap = 256
+        # no reference counterpart: the drop-in MSCKF keeps the innovation statistics of its last feature_callback in `last_innovation`
+        # (msckf_ops.FILTER_STATS_DTYPE[2]: the lost-feature and the pruning update; include/airvision.h, "Innovation statistics")
+        self.publish_innovation = False

@@ -316,14 +316,17 @@ struct av_msckf_batch {
     DevPath* dev = nullptr;                     // device-resident state + observation store (msckf_dev.inc); NULL: the host-bookkeeping path (AV_MSCKF_STORE=host)
     long long dev_seq = 0;                      // steps submitted (ring slot = dev_seq % DEV_RING)
     hipEvent_t ev_msg[4] = {nullptr, nullptr, nullptr, nullptr};      // submit_dev: the message copy of ring slot k has been enqueued
-    struct Pending { int slot; double* out; double* cov; av_landmark* lm; int32_t* lmn; };
-    std::deque<Pending> direct_pending;         // one group, no worker: steps launched and not yet finished (slot, caller's out, caller's odometry-covariance array or NULL, caller's landmark arrays or NULL)
+    struct Pending { int slot; double* out; double* cov; av_landmark* lm; int32_t* lmn; av_filter_stats* stats; };
+    std::deque<Pending> direct_pending;         // one group, no worker: steps launched and not yet finished (slot, caller's out, caller's odometry-covariance array or NULL, caller's landmark arrays or NULL, caller's innovation-statistics array or NULL)
     // odometry covariance (av_msckf_batch_set_odom_cov): on the batch and on every group; next_cov = the destination
     // av_msckf_batch_next_odom_cov handed over for the next step (batch only), taken by that step
     bool odom_cov = false; double* next_cov = nullptr;
     // landmark map (av_msckf_batch_set_landmarks): records per stream and step (0: off), on the batch and on every group; next_lm /
     // next_lmn = the destination av_msckf_batch_next_landmarks handed over for the next step (batch only), taken by that step
     int lm_cap = 0; av_landmark* next_lm = nullptr; int32_t* next_lmn = nullptr;
+    // innovation statistics (av_msckf_batch_set_stats): on the batch and on every group; next_stats = the destination
+    // av_msckf_batch_next_stats handed over for the next step (batch only), taken by that step
+    bool stats_on = false; av_filter_stats* next_stats = nullptr;
     explicit av_msckf_batch(int n) : st(n) {}
 };
 
@@ -1106,7 +1109,7 @@ int b_chain_finish(av_msckf_batch* b, std::vector<FeatRef>& refs, ChainCtx& ctx)
 }  // namespace
 
 static void sub_destroy(av_msckf_batch* b);
-namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
+namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn, av_filter_stats* stats); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
 
 // Stream for the filter's kernels.  AV_MSCKF_CUS="first:count" confines them to `count` compute units starting at CU `first`
 // (hipExtStreamCreateWithCUMask) -- together with a complementary mask on the caller's front-end stream this partitions the
@@ -1319,8 +1322,9 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
         const int k = (int)(b->dev_seq++ % DEV_RING);
         double* cov = b->next_cov; b->next_cov = nullptr;
         av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
+        av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
         if ((rc = dev_launch(b, k, ids, uv, n_feat, cap, timestamps, false, nullptr, stm))) return rc;
-        return dev_finish(b, k, out, cov, lm, lmn);
+        return dev_finish(b, k, out, cov, lm, lmn, fst);
     }
     if ((rc = sub_reserve(b, cap))) return rc;
     ++b->n_steps;
@@ -1849,7 +1853,7 @@ int direct_drain(av_msckf_batch* b, size_t max_pending)
     while (b->direct_pending.size() > max_pending) {
         const av_msckf_batch::Pending pr = b->direct_pending.front();
         b->direct_pending.pop_front();
-        const int r = dev_finish(b, pr.slot, pr.out, pr.cov, pr.lm, pr.lmn);
+        const int r = dev_finish(b, pr.slot, pr.out, pr.cov, pr.lm, pr.lmn, pr.stats);
         if (r && !rc) rc = r;
     }
     return rc;
@@ -1900,20 +1904,22 @@ AV_EXPORT int av_msckf_batch_submit(av_msckf_batch* b, const int64_t* ids, const
         const int k = (int)(b->dev_seq++ % DEV_RING);
         double* cov = b->next_cov; b->next_cov = nullptr;
         av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
+        av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
         if ((rc = dev_launch(b, k, ids, uv, n_feat, cap, timestamps, false, nullptr, (hipStream_t)stream))) return rc;
-        b->direct_pending.push_back({k, out, cov, lm, lmn});
+        b->direct_pending.push_back({k, out, cov, lm, lmn, fst});
         return AV_OK;
     }
     const int k = (int)(b->dev_seq++ % DEV_RING);
     double* cov = b->next_cov; b->next_cov = nullptr;
     av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
+    av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
     for (size_t gi = 0; gi < b->subs.size(); ++gi) {
         av_msckf_batch* g = b->subs[gi];
         const size_t s0 = gi * (size_t)b->per_sub;
         av_msckf_batch::Job job;
         if (g->dev) {
             job.launch = [=] { return dev_launch(g, k, ids + s0 * cap, uv + s0 * cap * 4, n_feat + s0, cap, timestamps + s0, false, nullptr, g->own); };
-            job.finish = [=] { return dev_finish(g, k, out + s0 * 12, cov ? cov + s0 * ODOM_COV_DOUBLES : nullptr, lm ? lm + s0 * b->lm_cap : nullptr, lmn ? lmn + s0 * 2 : nullptr); };
+            job.finish = [=] { return dev_finish(g, k, out + s0 * 12, cov ? cov + s0 * ODOM_COV_DOUBLES : nullptr, lm ? lm + s0 * b->lm_cap : nullptr, lmn ? lmn + s0 * 2 : nullptr, fst ? fst + s0 : nullptr); };
         } else {
             job.launch = [=] { return sub_step(g, ids + s0 * cap, uv + s0 * cap * 4, n_feat + s0, cap, timestamps + s0, out + s0 * 12, g->own); };
         }
@@ -1967,9 +1973,10 @@ AV_EXPORT int av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_de
     hipEvent_t ready = b->ev_msg[k];
     double* cov = b->next_cov; b->next_cov = nullptr;
     av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
+    av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
     if (b->subs.empty()) {
         if ((rc = dev_launch(b, k, nullptr, nullptr, nullptr, cap, timestamps, true, ready, (hipStream_t)stream))) return rc;
-        b->direct_pending.push_back({k, out, cov, lm, lmn});
+        b->direct_pending.push_back({k, out, cov, lm, lmn, fst});
         return AV_OK;
     }
     s0 = 0;
@@ -1977,7 +1984,7 @@ AV_EXPORT int av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_de
         const size_t o = s0;
         av_msckf_batch::Job job;
         job.launch = [=] { return dev_launch(g, k, nullptr, nullptr, nullptr, cap, timestamps + o, true, ready, g->own); };
-        job.finish = [=] { return dev_finish(g, k, out + o * 12, cov ? cov + o * ODOM_COV_DOUBLES : nullptr, lm ? lm + o * b->lm_cap : nullptr, lmn ? lmn + o * 2 : nullptr); };
+        job.finish = [=] { return dev_finish(g, k, out + o * 12, cov ? cov + o * ODOM_COV_DOUBLES : nullptr, lm ? lm + o * b->lm_cap : nullptr, lmn ? lmn + o * 2 : nullptr, fst ? fst + o : nullptr); };
         s0 += (size_t)g->S;
         std::lock_guard<std::mutex> lk(g->wmu);
         g->jobs.push_back(std::move(job));
@@ -2066,6 +2073,36 @@ AV_EXPORT int av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec,
     if (!b || !rec || !n) { av_set_error("av_msckf_batch_next_landmarks: bad arguments"); return AV_E_INVALID; }
     if (b->lm_cap <= 0) { av_set_error("av_msckf_batch_next_landmarks: the landmark map is off (av_msckf_batch_set_landmarks)"); return AV_E_INVALID; }
     b->next_lm = rec; b->next_lmn = n;
+    return AV_OK;
+}
+
+// Innovation statistics (airvision.h, "Innovation statistics").  set: before the batch's first step, like the other two outputs -- the
+// groups size their buffers when they prepare the device-resident path.  next: the destination of the next step's records.
+static_assert(sizeof(av_update_stats) == 64 && sizeof(av_filter_stats) == AV_FILTER_STATS_BYTES && sizeof(DUpdStats) == sizeof(av_update_stats), "av_filter_stats layout");
+static_assert(offsetof(av_update_stats, gamma_eval) == offsetof(DUpdStats, gamma_eval) && offsetof(av_update_stats, dx_rot) == offsetof(DUpdStats, dx_rot) && offsetof(av_update_stats, flags) == offsetof(DUpdStats, flags), "av_update_stats fields");
+static_assert(FS_RAN == AV_FS_RAN && FS_CUT == AV_FS_CUT, "AV_FS_* bits");
+AV_EXPORT int av_msckf_batch_set_stats(av_msckf_batch* b, int enable)
+{
+    if (!b) { av_set_error("av_msckf_batch_set_stats: bad arguments"); return AV_E_INVALID; }
+    std::vector<av_msckf_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    if (enable) for (av_msckf_batch* g : parts) if (!g->dev) {
+        av_set_error("av_msckf_batch_set_stats: the innovation statistics need the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)");
+        return AV_E_INVALID;
+    }
+    bool stepped = b->dev_seq > 0;
+    for (av_msckf_batch* g : parts) if (g->n_steps > 0 || (g->dev && g->dev->cap > 0)) stepped = true;
+    if (stepped) { av_set_error("av_msckf_batch_set_stats: the batch has stepped; the innovation statistics are switched before the first step"); return AV_E_INVALID; }
+    b->stats_on = enable != 0; b->next_stats = nullptr;
+    for (av_msckf_batch* g : parts) g->stats_on = enable != 0;
+    return AV_OK;
+}
+
+AV_EXPORT int av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host)
+{
+    if (!b || !rec_host) { av_set_error("av_msckf_batch_next_stats: bad arguments"); return AV_E_INVALID; }
+    if (!b->stats_on) { av_set_error("av_msckf_batch_next_stats: the innovation statistics are off (av_msckf_batch_set_stats)"); return AV_E_INVALID; }
+    b->next_stats = rec_host;
     return AV_OK;
 }
 

@@ -23,6 +23,8 @@
 //   dk_mid_lm, dk_finish_lm, dk_finish_cov_lm  (instead of dk_mid / dk_finish / dk_finish_cov when av_msckf_batch_set_landmarks is on)
 //                the same, and the stream's landmark records: the lost-feature update's ahead of dk_mid's rebuild of the per-phase
 //                feature arrays, the pruning update's ahead of dk_finish's camera removal
+//   dk_mid_st, dk_mid_lm_st, dk_finish_st, dk_finish_cov_st, dk_finish_lm_st, dk_finish_cov_lm_st  (instead of the six above when
+//                av_msckf_batch_set_stats is on) the same, and the stream's innovation statistics of the update that has just run
 //
 // Per-stream capacity failures are recorded in the stream's state (DState::failed) and stop that stream only.
 
@@ -578,6 +580,81 @@ __device__ __forceinline__ void dev_landmarks(const DevArgs& a, int s, const LmO
 }
 
 // ------------------------------------------------------------------------------------------------
+// Innovation statistics (include/airvision.h, "Innovation statistics"): what the gates of the step's two updates decided, per stream, as
+// two blocks of 64 bytes.  Like the landmark records they are taken while the per-phase arrays of the update stand: block 0 by the
+// dk_mid_*st instances before dk_mid rebuilds them, block 1 by the dk_finish_*st instances.  ONE wavefront of the stream's workgroup
+// works, 64 candidates per trip in candidate (= dict) order.  Counts: ballots.  The 1,500-row cut: dev_landmarks' prefix sum of 4 n_obs - 3
+// over the gated-in candidates, carried across trips.  Sums of dof and gamma: lane l adds the candidates k = l, l + 64, l + 128, ... in
+// ascending k into its own accumulators (a candidate that does not count adds nothing, not a zero), then ONE butterfly over the
+// wavefront, x += shfl_xor(x, d) for d = 32, 16, 8, 4, 2, 1 in this order, leaves the same bits in every lane.  Only the first 64
+// threads of the workgroup take part, so the 64- and the 256-thread launch add in the same order and write the same bytes.  No atomics,
+// no LDS; lane 0 writes the block with plain vector stores.
+// ------------------------------------------------------------------------------------------------
+enum { FS_RAN = 1, FS_CUT = 2 };
+struct DUpdStats { int n_cand, n_pos, n_eval, n_pass, dof_eval, dof_pass, rows, flags; double gamma_eval, gamma_pass, dx_pos, dx_rot; };
+static_assert(sizeof(DUpdStats) == 64, "av_update_stats is 64 bytes");
+
+// call with threadIdx.x < 64: `blocks` blocks of stream s, from block `first` on, become zero bytes (8 lanes x 8 bytes per block)
+__device__ __forceinline__ void dev_stats_zero(DUpdStats* out, int s, int first, int blocks)
+{
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(out + 2 * (size_t)s + first);
+    if ((int)threadIdx.x < 8 * blocks) w[threadIdx.x] = 0ull;
+}
+// call with threadIdx.x < 64 (the first wavefront, all of its lanes) for an active stream, with a.stacked / a.dx those of the update the
+// candidates belong to.  prune = false: block 0, the lost-feature update; true: block 1, the pruning update (no row cut)
+__device__ __forceinline__ void dev_stats(const DevArgs& a, int s, DUpdStats* out, bool prune)
+{
+    const int lane = threadIdx.x;
+    const size_t f0 = (size_t)s * a.FS;
+    const int nc = a.n_cand[s];
+    int n_pos = 0, n_eval = 0, n_pass = 0, rows = 0;
+    int dof_e = 0, dof_p = 0;
+    double g_e = 0.0, g_p = 0.0;
+    for (int base = 0; base < nc; base += 64) {
+        const int k = base + lane;
+        const size_t f = f0 + k;
+        int valid = 0, gated = 0, nobs = 0, dof = 0;
+        double g = 0.0;
+        if (k < nc) {
+            valid = a.f_valid[f] != 0;
+            if (valid) { gated = a.pass[f] != 0; nobs = a.f_off[f + 1] - a.f_off[f]; dof = a.f_dof[f]; g = a.gamma[f]; }
+        }
+        int ev = valid;
+        if (!prune) {
+            const int v = gated ? 4 * nobs - 3 : 0;
+            int incl = v;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+            ev = valid && rows + incl - v <= 1500;            // (the reference reaches this candidate: msckf.py:667-668)
+            rows += __shfl(incl, 63);
+        }
+        const int ps = ev && gated;
+        n_pos += __popcll(__ballot(valid)); n_eval += __popcll(__ballot(ev)); n_pass += __popcll(__ballot(ps));
+        if (ev) { dof_e += dof; g_e += g; }
+        if (ps) { dof_p += dof; g_p += g; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        dof_e += __shfl_xor(dof_e, d); dof_p += __shfl_xor(dof_p, d);
+        g_e += __shfl_xor(g_e, d); g_p += __shfl_xor(g_p, d);
+    }
+    if (lane == 0) {
+        const int st = a.stacked[s];
+        DUpdStats r;
+        r.n_cand = nc; r.n_pos = n_pos; r.n_eval = n_eval; r.n_pass = n_pass; r.dof_eval = dof_e; r.dof_pass = dof_p;
+        r.rows = st > 0 ? st : 0;
+        r.flags = (st > 0 ? FS_RAN : 0) | (n_eval < n_pos ? FS_CUT : 0);
+        r.gamma_eval = g_e; r.gamma_pass = g_p; r.dx_pos = 0.0; r.dx_rot = 0.0;
+        if (st > 0) {                                         // (the delta_x dev_apply_update injects)
+            const double* dx = a.dx + (size_t)s * a.ld;
+            r.dx_rot = sqrt(dx[0] * dx[0] + dx[1] * dx[1] + dx[2] * dx[2]);
+            r.dx_pos = sqrt(dx[12] * dx[12] + dx[13] * dx[13] + dx[14] * dx[14]);
+        }
+        out[2 * (size_t)s + (prune ? 1 : 0)] = r;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // dk_mid: the lost-feature update lands in the state (msckf.py:568-595); then the selection half of prune_cam_state_buffer (:712-757)
 // ------------------------------------------------------------------------------------------------
 // returns (to every thread) the number of pruning candidates of stream s, -1 if the stream does not prune in this step; the
@@ -625,6 +702,24 @@ __global__ __launch_bounds__(256, 5) void dk_mid_lm(DevArgs a, LmOut L)
     AvsStore V;
     (void)dk_mid_body(a, blockIdx.x, &V);
 }
+// dk_mid / dk_mid_lm + block 0 of the innovation statistics (av_msckf_batch_set_stats): the lost-feature update's gates, read while its
+// feature arrays stand; a stream that takes no part in the step gets zeros
+template <bool LM>
+__device__ __forceinline__ void dk_mid_st_body(const DevArgs& a, const LmOut& L, DUpdStats* st)
+{
+    AV_FILTER_PRIO();
+    const int s = blockIdx.x;
+    if (threadIdx.x < 64) {
+        if constexpr (LM) dev_landmarks(a, s, L, false);
+        if (a.st[s].active) dev_stats(a, s, st, false);       // (wavefront-uniform)
+        else dev_stats_zero(st, s, 0, 1);
+    }
+    __syncthreads();                                          // (the other wavefronts rebuild the arrays the first one reads)
+    AvsStore V;
+    (void)dk_mid_body(a, s, &V);
+}
+__global__ __launch_bounds__(256, 5) void dk_mid_st(DevArgs a, DUpdStats* st) { dk_mid_st_body<false>(a, LmOut{}, st); }
+__global__ __launch_bounds__(256, 5) void dk_mid_lm_st(DevArgs a, LmOut L, DUpdStats* st) { dk_mid_st_body<true>(a, L, st); }
 
 // ------------------------------------------------------------------------------------------------
 // dk_finish: the pruning update lands in the state, the two camera states leave (msckf.py:774-786), online_reset (:821-843),
@@ -692,9 +787,10 @@ __device__ __forceinline__ void dev_odom_cov(const DevArgs& a, int s, const DSta
 }
 
 // COV: the instance that also writes the stream's odometry-covariance record (dk_finish_cov); LM: the one that also appends the pruning
-// update's landmark records (dk_finish_lm); both false: dk_finish as it always was
-template <bool COV, bool LM>
-__device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* odom, const LmOut& L)
+// update's landmark records (dk_finish_lm); STATS: the one that also writes block 1 of the innovation statistics (dk_finish_st); all
+// false: dk_finish as it always was
+template <bool COV, bool LM, bool STATS = false>
+__device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* odom, const LmOut& L, DUpdStats* stats = nullptr)
 {
     __shared__ int red[8], s_reset;
     const int tid = threadIdx.x;
@@ -711,6 +807,16 @@ __device__ __forceinline__ void dk_finish_body(const DevArgs& a, int s, double* 
         if (tid < 64) {
             if (!D->active) { if (tid == 0) { L.n[2 * (size_t)s] = 0; L.n[2 * (size_t)s + 1] = 0; } }
             else if (D->prune) dev_landmarks(a, s, L, true);
+        }
+        __syncthreads();
+    }
+    if constexpr (STATS) {
+        // the pruning update's gates, while its feature arrays stand; no pruning in this step: a zero block; a stream that has stopped or
+        // takes no part: both blocks zero, the lost-feature block of this step included
+        if (tid < 64) {
+            if (!D->active) dev_stats_zero(stats, s, 0, 2);
+            else if (D->prune) dev_stats(a, s, stats, true);
+            else dev_stats_zero(stats, s, 1, 1);
         }
         __syncthreads();
     }
@@ -790,6 +896,27 @@ __global__ __launch_bounds__(256, 5) void dk_finish_cov_lm(DevArgs a, double* od
     AV_FILTER_PRIO();
     dk_finish_body<true, true>(a, blockIdx.x, odom, L);
 }
+// the four above + block 1 of the innovation statistics (av_msckf_batch_set_stats)
+__global__ __launch_bounds__(256, 5) void dk_finish_st(DevArgs a, DUpdStats* st)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<false, false, true>(a, blockIdx.x, nullptr, LmOut{}, st);
+}
+__global__ __launch_bounds__(256, 5) void dk_finish_cov_st(DevArgs a, double* odom, DUpdStats* st)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<true, false, true>(a, blockIdx.x, odom, LmOut{}, st);
+}
+__global__ __launch_bounds__(256, 5) void dk_finish_lm_st(DevArgs a, LmOut L, DUpdStats* st)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<false, true, true>(a, blockIdx.x, nullptr, L, st);
+}
+__global__ __launch_bounds__(256, 5) void dk_finish_cov_lm_st(DevArgs a, double* odom, LmOut L, DUpdStats* st)
+{
+    AV_FILTER_PRIO();
+    dk_finish_body<true, true, true>(a, blockIdx.x, odom, L, st);
+}
 
 // ------------------------------------------------------------------------------------------------
 // dk_prune_probe: parity tests only (av_msckf_predict_ops_dev; no step launches it).  Per stream, on the window as it stands:
@@ -818,6 +945,7 @@ struct DevSlot {
     double* out_h = nullptr; int* cnt_h = nullptr;                                // pinned landing zones of the step's only read-back
     double* odom_h = nullptr;                                                     // [S][ODOM_COV_DOUBLES] pinned, the odometry-covariance records of the step (NULL: the feature is off)
     DLandmark* lm_h = nullptr; int* lmn_h = nullptr;                              // [S][lm.cap] / [S][2] pinned, the landmark records and counts of the step (NULL: the feature is off)
+    DUpdStats* stats_h = nullptr;                                                 // [S][2] pinned, the innovation statistics of the step (NULL: the feature is off)
     hipEvent_t done = nullptr;
     hipEvent_t t0[2] = {nullptr, nullptr}, t1[2] = {nullptr, nullptr}; bool t_used[2] = {false, false};      // av_msckf_batch_work: device time of the two phase chains
     bool in_flight = false;
@@ -831,6 +959,7 @@ struct DevPath {
     DCov* cov_d = nullptr;           // [S] dk_begin -> dk_cov
     double* odom_d = nullptr;        // [S][ODOM_COV_DOUBLES] dk_finish_cov's records (NULL: av_msckf_batch_set_odom_cov is off)
     LmOut lm = {nullptr, nullptr, 0};      // [S][cap] records and [S][2] counts of dk_mid_lm / dk_finish_*lm (rec NULL: av_msckf_batch_set_landmarks is off)
+    DUpdStats* stats_d = nullptr;    // [S][2] blocks of the dk_mid_*st / dk_finish_*st instances (NULL: av_msckf_batch_set_stats is off)
     int dk_wg = 0;                   // AV_DK_WG read when the path is prepared: 64 / 256 = workgroup size of the per-stream kernels, 0 = by the group's stream count
     int launched_wg = 0;             // workgroup size dev_enqueue launched them with in the last enqueued step (0: no step yet); av_msckf_batch_launch_shape
     int* cols = nullptr; int* blk_row = nullptr; int* blk_len = nullptr; int* clist = nullptr; int* again = nullptr;

@@ -59,6 +59,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
         DA(d->cols, S * 6 * cs) DA(d->clist, S + 8) DA(d->work, S * 8)
         if (b->odom_cov) DA(d->odom_d, S * ODOM_COV_DOUBLES)
         if (b->lm_cap > 0) { DA(d->lm.rec, S * b->lm_cap) DA(d->lm.n, S * 2) d->lm.cap = b->lm_cap; }
+        if (b->stats_on) DA(d->stats_d, S * 2)
         DAF(A.pos_of, S * A.ns, 0xFF) DAF(A.order, S * A.ns, 0xFF) DA(A.fr_n, S * A.ns) DA(A.hdr, S * AVS_HDR_WORDS) DA(A.births, S)
     }
     DA(A.fr_id, ne) DA(A.fr_z, ne * 4) DA(A.fr_fslot, ne) DA(A.fr_prev, ne) DA(A.fr_next, ne)
@@ -76,6 +77,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
             if ((rc = b->res.pinned(&sl.n_h, S))) return rc;
             if (b->odom_cov && (rc = b->res.pinned(&sl.odom_h, S * ODOM_COV_DOUBLES))) return rc;
             if (b->lm_cap > 0 && ((rc = b->res.pinned(&sl.lm_h, S * b->lm_cap)) || (rc = b->res.pinned(&sl.lmn_h, S * 2)))) return rc;
+            if (b->stats_on && (rc = b->res.pinned(&sl.stats_h, S * 2))) return rc;
             if ((rc = b->res.event(&sl.done, hipEventDisableTiming | hipEventBlockingSync))) return rc;
             for (int ph = 0; ph < 2; ++ph) if ((rc = b->res.event(&sl.t0[ph], hipEventDefault)) || (rc = b->res.event(&sl.t1[ph], hipEventDefault))) return rc;
         }
@@ -484,14 +486,23 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     //  144.4 k frames/s, 5.5 against 5.0 ms of exclusive chain: a stream's ~150 candidates walk through the 16 teams of one workgroup
     //  instead of spreading over the chip.  Removed in round 5; profiles/r04/README.md keeps the numbers.)
     // (with the landmark map on, the instances that also write the records of the update that has just run: the same launches, two more read-backs)
-    if (d->lm.rec) hipLaunchKernelGGL(dk_mid_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->lm);
+    // (with the innovation statistics on, the instances that also write the stream's block of that update: the same launches, one more read-back)
+    if (d->stats_d && d->lm.rec) hipLaunchKernelGGL(dk_mid_lm_st, dim3(S), dim3(dk_wg), 0, stm, a, d->lm, d->stats_d);
+    else if (d->stats_d) hipLaunchKernelGGL(dk_mid_st, dim3(S), dim3(dk_wg), 0, stm, a, d->stats_d);
+    else if (d->lm.rec) hipLaunchKernelGGL(dk_mid_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->lm);
     else hipLaunchKernelGGL(dk_mid, dim3(S), dim3(dk_wg), 0, stm, a);
     AV_LAUNCH_CHECK();
     if ((rc = dev_phase(b, 1, stm, sl, a.cnt))) return rc;
     if (b->debug_capture && (rc = dev_debug_capture(b, 1, stm))) return rc;
     a.stacked = d->stacked1;
     // (with the odometry covariance on, the instance that also writes every stream's record: the same launch, one more read-back)
-    if (d->odom_d && d->lm.rec) hipLaunchKernelGGL(dk_finish_cov_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->lm);
+    if (d->stats_d) {
+        if (d->odom_d && d->lm.rec) hipLaunchKernelGGL(dk_finish_cov_lm_st, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->lm, d->stats_d);
+        else if (d->lm.rec) hipLaunchKernelGGL(dk_finish_lm_st, dim3(S), dim3(dk_wg), 0, stm, a, d->lm, d->stats_d);
+        else if (d->odom_d) hipLaunchKernelGGL(dk_finish_cov_st, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->stats_d);
+        else hipLaunchKernelGGL(dk_finish_st, dim3(S), dim3(dk_wg), 0, stm, a, d->stats_d);
+    }
+    else if (d->odom_d && d->lm.rec) hipLaunchKernelGGL(dk_finish_cov_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->lm);
     else if (d->lm.rec) hipLaunchKernelGGL(dk_finish_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->lm);
     else if (d->odom_d) hipLaunchKernelGGL(dk_finish_cov, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d);
     else hipLaunchKernelGGL(dk_finish, dim3(S), dim3(dk_wg), 0, stm, a);
@@ -502,14 +513,15 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
         AV_HIP(hipMemcpyAsync(sl.lm_h, d->lm.rec, sizeof(DLandmark) * (size_t)d->lm.cap * S, hipMemcpyDeviceToHost, stm));
         AV_HIP(hipMemcpyAsync(sl.lmn_h, d->lm.n, sizeof(int) * 2 * S, hipMemcpyDeviceToHost, stm));
     }
+    if (d->stats_d) AV_HIP(hipMemcpyAsync(sl.stats_h, d->stats_d, sizeof(DUpdStats) * 2 * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(sl.cnt_h, a.cnt, sizeof(int) * 16, hipMemcpyDeviceToHost, stm));
     return AV_OK;
 }
 
 // wait for the step queued on slot k and hand its published poses to the caller (cov: where the step's odometry-covariance records
 // go, S * ODOM_COV_DOUBLES doubles; lm / lmn: where its landmark records and counts go, S * lm_cap records and S * 2 ints; NULL: the
-// step has no destination and the records are dropped)
-int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn)
+// step has no destination and the records are dropped; stats: likewise for its innovation statistics, S records of AV_FILTER_STATS_BYTES)
+int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn, av_filter_stats* stats)
 {
     DevPath* d = b->dev;
     DevSlot& sl = d->slot[k];
@@ -522,6 +534,7 @@ int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* 
         memcpy(lm, sl.lm_h, sizeof(DLandmark) * (size_t)d->lm.cap * b->S);
         memcpy(lmn, sl.lmn_h, sizeof(int) * 2 * b->S);
     }
+    if (stats && sl.stats_h) memcpy(stats, sl.stats_h, sizeof(DUpdStats) * 2 * b->S);
     for (int i = 0; i < 16; ++i) d->hint[i] = sl.cnt_h[i];
     d->have_hint = true;
     for (int ph = 0; ph < 2; ++ph) if (sl.t_used[ph]) {       // the whole step has retired: both phases' event pairs of this slot are complete

@@ -108,8 +108,12 @@ class MSCKF(object):
         self._lm_on = bool(getattr(config, 'publish_landmarks', False))
         self.last_landmarks = None
         self.last_landmarks_dropped = 0
+        # config.publish_innovation = True (no reference counterpart; default off): `last_innovation` holds the two innovation-statistics
+        # blocks (msckf_ops.FILTER_STATS_DTYPE[2], see msckf_ops.unpack_filter_stats) of the last feature_callback.  vio_result is unchanged.
+        self._stats_on = bool(getattr(config, 'publish_innovation', False))
+        self.last_innovation = None
         self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap, odom_cov=self._cov_on, landmarks=self._lm_on,
-                                 landmark_cap=int(getattr(config, 'landmark_cap', 256)))
+                                 landmark_cap=int(getattr(config, 'landmark_cap', 256)), stats=self._stats_on)
         self.state_server = StateServer(self._flt)
         self.map_server = _MapView(self._flt)
         # class-level statics the reference sets in its constructor (msckf.py:128-150), kept for code that reads them
@@ -155,7 +159,10 @@ class MSCKF(object):
         if n:
             ids[0, :n] = [f.id for f in feats]
             uv[0, :n] = [(f.u0, f.v0, f.u1, f.v1) for f in feats]
-        out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None, landmarks=True if self._lm_on else None)
+        out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None, landmarks=True if self._lm_on else None,
+                             stats=True if self._stats_on else None)
+        if self._stats_on:
+            self.last_innovation = self._flt.last_stats[0].copy()
         if self._lm_on:
             rec, cnt = self._flt.last_landmarks
             lm = unpack_landmarks(rec, cnt, 0).copy()

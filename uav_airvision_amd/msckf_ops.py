@@ -306,12 +306,49 @@ def unpack_landmarks(rec, n, s):
     return rec[s, :int(n[s, 1])]
 
 
+# ---- innovation statistics (include/airvision.h, "Innovation statistics") ------------------------------------------------------
+_FS_INTS = ('n_cand', 'n_pos', 'n_eval', 'n_pass', 'dof_eval', 'dof_pass', 'rows', 'flags')
+_FS_DOUBLES = ('gamma_eval', 'gamma_pass', 'dx_pos', 'dx_rot')
+FILTER_STATS_DTYPE = np.dtype([(n, np.int32) for n in _FS_INTS] + [(n, np.float64) for n in _FS_DOUBLES])      # av_update_stats; a step's records: [S, 2]
+assert FILTER_STATS_DTYPE.itemsize == 64
+FILTER_STATS_BYTES = 128                                            # AV_FILTER_STATS_BYTES: block 0 the lost-feature update, block 1 the pruning update
+FS_RAN, FS_CUT = 1, 2                                               # AV_FS_*
+
+
+def filter_stats_rows(rec):
+    """(rows of the evaluated features' residuals, rows of the accepted ones) of records FILTER_STATS_DTYPE[..., 2]: the gate's dof is
+    M - 1 in the lost-feature update and M in the pruning update, a residual has 4 M - 3 rows -> 4 dof + n and 4 dof - 3 n."""
+    rec = np.asarray(rec)
+    k = np.array([1, -3], dtype=np.int64)
+    return (4 * rec['dof_eval'].astype(np.int64) + k * rec['n_eval'], 4 * rec['dof_pass'].astype(np.int64) + k * rec['n_pass'])
+
+
+def unpack_filter_stats(rec):
+    """Records FILTER_STATS_DTYPE[..., 2] as a step returns them -> a dict of arrays of that shape: every field of the record, and per block
+    rows_eval   rows of the residuals of the evaluated features (from the dof sums; for the accepted ones that is `rows`)
+    nis_dof     gamma_eval / dof_eval: the normalised innovation in the units of the gate (the reference's dof, not the residual's dimension)
+    nis_rows    gamma_eval / rows_eval: the normalised innovation per residual dimension, near 1 for a consistent filter
+    reject_rate 1 - n_pass / n_eval
+    with NaN where nothing was evaluated."""
+    rec = np.asarray(rec)
+    out = {n: rec[n] for n in FILTER_STATS_DTYPE.names}
+    rows_eval, _ = filter_stats_rows(rec)
+    ne = rec['n_eval'].astype(np.float64)
+    nothing = rec['n_eval'] <= 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out['rows_eval'] = rows_eval
+        out['nis_dof'] = np.where(nothing, np.nan, rec['gamma_eval'] / rec['dof_eval'])
+        out['nis_rows'] = np.where(nothing, np.nan, rec['gamma_eval'] / rows_eval)
+        out['reject_rate'] = np.where(nothing, np.nan, 1.0 - rec['n_pass'] / ne)
+    return out
+
+
 class BatchedMSCKF(object):
     """S independent filters stepped together (av_msckf_batch_* C ABI): C++ bookkeeping inside the
     library, one batched launch per numeric phase.  Mirrors MSCKF.imu_callback / feature_callback
     (reference: src/msckf.py:162-228) for many streams at once."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64, stats=False):
         """rows_cap: rows of the per-stream block buffer.  None = sized by the library from the capacity of the first
         feature message (the camera-pruning update stacks 5 rows per feature, the lost-feature update at most 1500 + one
         block); `max_features`, when given, sizes it up front instead.  With the automatic size a later step with a wider
@@ -322,7 +359,9 @@ class BatchedMSCKF(object):
         odom_cov=True: every step also computes the covariance of what it publishes (ODOM_COV_FIELDS; `step / submit / submit_dev(...,
         cov=)`, `last_cov`, `unpack_odom_cov`).  Device-resident filter only.
         landmarks=True: every step also publishes the features its two updates triangulated, up to landmark_cap records per stream
-        (LANDMARK_DTYPE; `step / submit / submit_dev(..., landmarks=)`, `last_landmarks`, `unpack_landmarks`).  Device-resident filter only."""
+        (LANDMARK_DTYPE; `step / submit / submit_dev(..., landmarks=)`, `last_landmarks`, `unpack_landmarks`).  Device-resident filter only.
+        stats=True: every step also publishes the innovation statistics of its two updates, FILTER_STATS_DTYPE[S, 2] (`step / submit /
+        submit_dev(..., stats=)`, `last_stats`, `unpack_filter_stats`).  Device-resident filter only."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -364,6 +403,35 @@ class BatchedMSCKF(object):
                     self.landmark_cap = 0
                     self.close()
                     raise
+            self.stats = bool(stats)
+            self.last_stats = None         # the records array of the most recent step that was given one (FILTER_STATS_DTYPE[S, 2])
+            if self.stats:
+                try:
+                    N.check(N.lib().av_msckf_batch_set_stats(self._h, 1))
+                except Exception:
+                    self.stats = False
+                    self.close()
+                    raise
+
+    def set_stats(self, enable):
+        """av_msckf_batch_set_stats: before the first step only."""
+        N.check(N.lib().av_msckf_batch_set_stats(self._h, 1 if enable else 0))
+        self.stats = bool(enable)
+
+    def _next_stats(self, st):
+        """The records array of the next step (None: the step has none), handed to the library.  st: None, True (allocate) or a
+        C-contiguous FILTER_STATS_DTYPE[S, 2] array."""
+        if st is None or st is False:
+            return None
+        if not self.stats:
+            raise ValueError('stats= needs BatchedMSCKF(..., stats=True)')
+        if st is True:
+            st = np.zeros((self.S, 2), dtype=FILTER_STATS_DTYPE)
+        if not (isinstance(st, np.ndarray) and st.dtype == FILTER_STATS_DTYPE and st.shape == (self.S, 2) and st.flags['C_CONTIGUOUS']):
+            raise ValueError('stats must be a C-contiguous FILTER_STATS_DTYPE[%d, 2] array' % self.S)
+        N.check(N.lib().av_msckf_batch_next_stats(self._h, st.ctypes.data_as(C.c_void_p)))
+        self.last_stats = st
+        return st
 
     def set_landmarks(self, cap):
         """av_msckf_batch_set_landmarks: cap records per stream and step (0: off); before the first step only."""
@@ -429,12 +497,13 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_push_imu(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                 g.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), len(si)))
 
-    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None):
+    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None):
         """ids int64[S,cap], uv float64[S,cap,4], n_feat int32[S], timestamps float64[S] (host arrays).
         Returns float64[S,12]: published, t, p(3), q(4), v(3).  cov (odom_cov=True): a float64[S,120] array that takes the step's
         odometry-covariance records, or True to have one allocated; it is `last_cov` afterwards.  landmarks (landmarks=True): a pair of
         arrays (LANDMARK_DTYPE[S, landmark_cap], int32[S, 2]) that takes the step's landmark records and counts, or True to have them
-        allocated; the pair is `last_landmarks` afterwards."""
+        allocated; the pair is `last_landmarks` afterwards.  stats (stats=True): a FILTER_STATS_DTYPE[S, 2] array that takes the step's
+        innovation statistics, or True to have one allocated; it is `last_stats` afterwards."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
@@ -443,17 +512,18 @@ class BatchedMSCKF(object):
         out = np.zeros((self.S, 12))
         cov = self._next_cov(cov)
         lm = self._next_landmarks(landmarks)
+        fst = self._next_stats(stats)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_step(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                 nf.ctypes.data_as(C.c_void_p), cap, ts.ctypes.data_as(C.c_void_p),
                                                 out.ctypes.data_as(C.c_void_p), N.current_stream()))
         return out
 
-    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None):
+    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None):
         """Queue one step (av_msckf_batch_submit) and return its float64[S,12] output array, which is filled once the
         step has retired -- i.e. after a `wait(k)` that leaves fewer than the steps submitted after it pending.  The
         stream groups of the batch run behind their queues independently of each other.  cov: as in `step`; the array (`last_cov`) is
-        filled when the step retires, like the output array; landmarks: likewise."""
+        filled when the step retires, like the output array; landmarks, stats: likewise."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
@@ -461,34 +531,36 @@ class BatchedMSCKF(object):
         out = np.zeros((self.S, 12))
         cov = self._next_cov(cov)
         lm = self._next_landmarks(landmarks)
+        fst = self._next_stats(stats)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_submit(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                   nf.ctypes.data_as(C.c_void_p), ids.shape[1], ts.ctypes.data_as(C.c_void_p),
                                                   out.ctypes.data_as(C.c_void_p), N.current_stream()))
-        self._inflight.append((ids, uv, nf, ts, out, cov, lm))     # the library reads / writes these until the step retires
+        self._inflight.append((ids, uv, nf, ts, out, cov, lm, fst))     # the library reads / writes these until the step retires
         return out
 
     def device_resident(self):
         """True when the filter state and the observation map live on the device (the default; `submit_dev` needs it)."""
         return N.lib().av_msckf_batch_device_resident(self._h) == 1
 
-    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None):
+    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None):
         """Queue one step on the feature message `engine` (a FrontendEngine with the same streams) has just published, read
         where it lies on the device (av_msckf_batch_submit_dev): no host round trip between the front-end and the filter.
         msg_stream: the stream handle the engine's step ran on (default: torch's current stream, i.e. call this right after
         `engine.step` on the same stream).  The filter's kernels run on the current stream / the stream groups' own streams.
-        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks: as in `submit`."""
+        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks, stats: as in `submit`."""
         ids, uv, n, cap = engine.features_dev()
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         assert ts.shape == (self.S,) and engine.n_streams == self.S
         out = np.zeros((self.S, 12))
         cov = self._next_cov(cov)
         lm = self._next_landmarks(landmarks)
+        fst = self._next_stats(stats)
         with torch.cuda.device(self.device):
             ms = N.current_stream() if msg_stream is None else msg_stream
             N.check(N.lib().av_msckf_batch_submit_dev(self._h, ids, uv, n, cap, ts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
                                                       ms, N.current_stream()))
-        self._inflight.append((ts, out, cov, lm))
+        self._inflight.append((ts, out, cov, lm, fst))
         return out
 
     def wait(self, max_pending=0):

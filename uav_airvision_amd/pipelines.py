@@ -192,7 +192,8 @@ class FilterSet(object):
     covariance on, `submit_dev(..., cov=True)` then gives every part a records array and `last_cov` joins them ([S, 120] once the
     step has retired), as the returned view joins the poses.  landmarks=True (with landmark_cap) switches the landmark map on,
     `submit_dev(..., landmarks=True)` gives every part its pair of arrays and `last_landmarks` = (records view, counts view) joins them
-    ([S, landmark_cap] and [S, 2])."""
+    ([S, landmark_cap] and [S, 2]).  stats=True switches the innovation statistics on, `submit_dev(..., stats=True)` gives every part
+    its records array and `last_stats` joins them ([S, 2] of FILTER_STATS_DTYPE)."""
 
     def __init__(self, config, engine_set, device=0, **kw):
         from .msckf_ops import BatchedMSCKF
@@ -203,6 +204,8 @@ class FilterSet(object):
         self.last_cov = None
         self.landmarks = bool(kw.get('landmarks', False))
         self.last_landmarks = None
+        self.stats = bool(kw.get('stats', False))
+        self.last_stats = None
 
     def device_resident(self):
         return all(f.device_resident() for f in self.flts)
@@ -212,7 +215,7 @@ class FilterSet(object):
             if len(rows[0]):
                 self.es.pipes[p].put(lambda f=self.flts[p], r=rows: f.push_imu(*r))
 
-    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None, landmarks=None):
+    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None):
         assert engine_set is self.es
         if cov is not None and cov is not True:
             raise ValueError('FilterSet.submit_dev: cov is None or True (every part allocates its own records array)')
@@ -222,8 +225,15 @@ class FilterSet(object):
             raise ValueError('FilterSet.submit_dev: landmarks is None or True (every part allocates its own arrays)')
         if landmarks and not self.landmarks:
             raise ValueError('landmarks= needs FilterSet(..., landmarks=True)')
+        if stats is not None and stats is not True:
+            raise ValueError('FilterSet.submit_dev: stats is None or True (every part allocates its own records array)')
+        if stats and not self.stats:
+            raise ValueError('stats= needs FilterSet(..., stats=True)')
         ts = np.asarray(timestamps, dtype=np.float64)
         out = _OutView(len(self.parts))
+        fsts = _OutView(len(self.parts)) if stats else None
+        if stats:
+            self.last_stats = fsts
         lms = (_OutView(len(self.parts)), _OutView(len(self.parts))) if landmarks else None
         if landmarks:
             self.last_landmarks = lms
@@ -235,7 +245,9 @@ class FilterSet(object):
                 w = self.es.pipes[p]
                 ms = N.current_stream()                      # the part's front-end stream: the message is copied behind its step
                 with torch.cuda.stream(w.fstream):
-                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, cov=cov, landmarks=landmarks)
+                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, cov=cov, landmarks=landmarks, stats=stats)
+                    if stats:
+                        fsts.parts[p] = self.flts[p].last_stats
                     if landmarks:
                         lms[0].parts[p], lms[1].parts[p] = self.flts[p].last_landmarks
                     if cov:

@@ -60,9 +60,11 @@ class BatchedRunner(object):
     odom_cov=True: every step also brings the odometry covariance of what it publishes (BatchedMSCKF(odom_cov=True)); after `run`,
     `cov_rows[s]` is float64[n, 121], one row `t` + the 120-double record per row of stream s's trajectory.
     landmark_cap > 0: every step also brings its landmark records (BatchedMSCKF(landmarks=True, landmark_cap=)); after `run`,
-    `lm_rows[s]` is (float64[n] pose times, LANDMARK_DTYPE[n] records, records dropped to the cap) of stream s."""
+    `lm_rows[s]` is (float64[n] pose times, LANDMARK_DTYPE[n] records, records dropped to the cap) of stream s.
+    innovation=True: every step also brings its innovation statistics (BatchedMSCKF(stats=True)); after `run`, `nis_rows[s]` is
+    (float64[n] pose times, FILTER_STATS_DTYPE[n, 2] records), one per row of stream s's trajectory."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False, landmark_cap=0):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False, landmark_cap=0, innovation=False):
         from .frontend import FrontendEngine
         from .msckf_ops import BatchedMSCKF
         self.config, self.S, self.device = config, int(n_streams), int(device)
@@ -70,7 +72,9 @@ class BatchedRunner(object):
         self.odom_cov = bool(odom_cov)
         self.landmark_cap = int(landmark_cap)
         self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features, odom_cov=self.odom_cov,
-                                landmarks=self.landmark_cap > 0, landmark_cap=max(1, self.landmark_cap))
+                                landmarks=self.landmark_cap > 0, landmark_cap=max(1, self.landmark_cap), stats=bool(innovation))
+        self.innovation = bool(innovation)
+        self.nis_rows = None
         self.cov_rows = None
         self.lm_rows = None
         self.frames_done = np.zeros(self.S, np.int64)
@@ -137,7 +141,10 @@ class BatchedRunner(object):
         lms = [[[], [], 0] for _ in range(S)]             # per stream: pose times, record arrays, records dropped to the cap
         want_lm = True if self.landmark_cap > 0 else None
 
-        def record(out, cov=None, lm=None):
+        nis = [[[], []] for _ in range(S)]                # per stream: pose times, the step's two blocks
+        want_nis = True if self.innovation else None
+
+        def record(out, cov=None, lm=None, fst=None):
             for s in np.nonzero(out[:, 0] > 0.5)[0]:
                 traj[s].append(out[s, 1:9].copy())
                 if cov is not None:
@@ -147,6 +154,8 @@ class BatchedRunner(object):
                     lms[s][0].append(np.full(len(rec), out[s, 1])); lms[s][1].append(rec)
                 if lm is not None:
                     lms[s][2] += int(lm[1][s, 0] - lm[1][s, 1])
+                if fst is not None:
+                    nis[s][0].append(out[s, 1]); nis[s][1].append(fst[s].copy())
 
         times, t_ref = self.times, getattr(eng, '_exposure_ref', None)
 
@@ -219,8 +228,8 @@ class BatchedRunner(object):
             if on_step is not None:
                 ids, uv, n = eng.read_features_raw()
                 n[ts_f < 0] = 0
-                out = flt.step(ids, uv, n, ts_f, cov=want, landmarks=want_lm)
-                record(out, flt.last_cov, flt.last_landmarks)
+                out = flt.step(ids, uv, n, ts_f, cov=want, landmarks=want_lm, stats=want_nis)
+                record(out, flt.last_cov, flt.last_landmarks, flt.last_stats)
                 on_step(step, ts_f, ids, uv, n, out)
             elif dev:
                 # the filter reads the published message where it lies on the device; nothing of this step is waited for here:
@@ -232,7 +241,7 @@ class BatchedRunner(object):
                     self._fstream = torch.cuda.Stream(device=self.device)
                 ms = N.current_stream()                   # the stream the front-end's step was enqueued on
                 with torch.cuda.stream(self._fstream):    # the filter's kernels (one group: here) overlap the next frame's front-end
-                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want, landmarks=want_lm), flt.last_cov, flt.last_landmarks))
+                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want, landmarks=want_lm, stats=want_nis), flt.last_cov, flt.last_landmarks, flt.last_stats))
                 flt.wait(2)
                 while len(inflight) > 2:
                     record(*inflight.pop(0))
@@ -240,7 +249,7 @@ class BatchedRunner(object):
                 eng.read_features_begin(step & 1)
                 ids, uv, n = eng.read_features_end(step & 1)
                 n[ts_f < 0] = 0
-                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want, landmarks=want_lm), flt.last_cov, flt.last_landmarks))
+                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want, landmarks=want_lm, stats=want_nis), flt.last_cov, flt.last_landmarks, flt.last_stats))
                 flt.wait(1)                               # at most one step behind: the next frames are decoded meanwhile
                 while len(inflight) > 1:
                     record(*inflight.pop(0))
@@ -253,14 +262,19 @@ class BatchedRunner(object):
         if self.landmark_cap > 0:
             from .msckf_ops import LANDMARK_DTYPE
             self.lm_rows = [(np.concatenate(t) if t else np.zeros(0), np.concatenate(r) if r else np.zeros(0, LANDMARK_DTYPE), d) for t, r, d in lms]
+        if self.innovation:
+            from .msckf_ops import FILTER_STATS_DTYPE
+            self.nis_rows = [(np.array(t, dtype=np.float64), np.array(r, dtype=FILTER_STATS_DTYPE).reshape(-1, 2)) for t, r in nis]
         return [np.array(t, dtype=np.float64).reshape(-1, 8) for t in traj]
 
 
-def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None, lm_rows=None, landmark_cap=64):
+def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None, lm_rows=None, landmark_cap=64, nis_rows=None):
     """Open (path, offset) pairs as EuRoC datasets and run them as one batch; returns (trajectories, datasets).
     cov_rows (a list): the batch runs with the odometry covariance on and the list receives, per stream, float64[n, 121] rows `t` + record.
     lm_rows (a list): the batch runs with the landmark map on (landmark_cap records per stream and step) and the list receives, per
     stream, (pose times float64[n], records LANDMARK_DTYPE[n], records dropped to the cap).
+    nis_rows (a list): the batch runs with the innovation statistics on and the list receives, per stream, (pose times float64[n], records
+    FILTER_STATS_DTYPE[n, 2]).
     stats (a dict) receives the batch's stream-frames, steps, distinct frames decoded and the seconds its stepping loop took."""
     import time
     from .euroc import EuRoCDataset
@@ -269,7 +283,8 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
         ds = EuRoCDataset(p)
         ds.set_starttime(o)
         dss.append(ds)
-    r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap, odom_cov=cov_rows is not None, landmark_cap=landmark_cap if lm_rows is not None else 0)
+    r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap, odom_cov=cov_rows is not None, landmark_cap=landmark_cap if lm_rows is not None else 0,
+                      innovation=nis_rows is not None)
     try:
         t0 = time.perf_counter()
         trajs = r.run(dss, max_frames=max_frames, on_step=on_step, share_frames=share_frames)
@@ -277,6 +292,8 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
             cov_rows.extend(r.cov_rows)
         if lm_rows is not None:
             lm_rows.extend(r.lm_rows)
+        if nis_rows is not None:
+            nis_rows.extend(r.nis_rows)
         if stats is not None:
             stats['seconds'] = stats.get('seconds', 0.0) + time.perf_counter() - t0
             stats['stream_frames'] = stats.get('stream_frames', 0) + int(r.frames_done.sum())
@@ -334,6 +351,11 @@ def make_parser():
                     help='also write, next to every trajectory file, output_<sequence>_offset<o>_map.txt: the landmark records of every step, one line '
                          '`t id x y z flags n_obs` each (t = the time of the pose of the step; include/airvision.h, "Landmark map"); the report states how many '
                          'records were dropped to the cap')
+    ap.add_argument('--innovation', action='store_true',
+                    help='also write, next to every trajectory file, output_<sequence>_offset<o>_nis.txt: per published pose one line `t` + the sixteen integers '
+                         'and eight doubles of its two innovation-statistics blocks (lost-feature update, pruning update; include/airvision.h, "Innovation '
+                         'statistics"); the report of every stream gains nis_rows, the sum of gamma over the residual rows of all evaluated features '
+                         '(near 1 for a consistent filter; needs no ground truth), and reject_rate, the share of evaluated features the gate rejected')
     ap.add_argument('--landmark-cap', type=int, default=64, metavar='N', help='--landmarks: records per stream and step (default 64)')
     ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
     ap.add_argument('--ransac-threshold', type=float, default=None, metavar='T', help='inlier error in pixels (config.ransac_threshold, default 3)')
@@ -442,7 +464,7 @@ def main(argv=None):
         ap.error('--root or --make-synthetic is required')
     jobs = shard.broadcast_object([(s, o) for s in args.sequences for o in args.offsets] if rank == 0 else None)
     mine = shard.partition(len(jobs), world, rank)
-    local_traj, local_cov, local_lm, report, stats = {}, {}, {}, {}, {}
+    local_traj, local_cov, local_lm, local_nis, report, stats = {}, {}, {}, {}, {}, {}
     import time
     if world > 1:
         dist.barrier()
@@ -452,9 +474,11 @@ def main(argv=None):
         cfg.image_format = batch_pixel_format([os.path.join(root, jobs[j][0]) for j in chunk], args.pixel_format)
         cov_rows = [] if args.covariance else None
         lm_rows = [] if args.landmarks else None
+        nis_rows = [] if args.innovation else None
         trajs, dss = run_batched(cfg, [os.path.join(root, jobs[j][0]) for j in chunk], [jobs[j][1] for j in chunk], device=local, max_frames=args.max_frames,
                                  share_frames=not args.no_share_frames, stats=stats, **({'cov_rows': cov_rows} if args.covariance else {}),
-                                 **({'lm_rows': lm_rows, 'landmark_cap': args.landmark_cap} if args.landmarks else {}))
+                                 **({'lm_rows': lm_rows, 'landmark_cap': args.landmark_cap} if args.landmarks else {}),
+                                 **({'nis_rows': nis_rows} if args.innovation else {}))
         for i, (j, traj, ds) in enumerate(zip(chunk, trajs, dss)):
             local_traj[j] = traj
             if cov_rows is not None:
@@ -467,9 +491,12 @@ def main(argv=None):
                 report[j] = dict(sequence=jobs[j][0], offset=jobs[j][1], frames=len(traj), ate_rmse=a['rmse'], ate_mean=a['mean'], rte_rmse=r['rmse'])
                 if cov_rows is not None:
                     report[j]['anees_pos'] = nees(traj, unpack_odom_cov(cov_rows[i][:, 1:])[:, 0:3, 0:3], gt)[1]
+            if nis_rows is not None:                      # (needs no ground truth: a stream without one gets its report entry here)
+                local_nis[j] = nis_rows[i]
+                report.setdefault(j, dict(sequence=jobs[j][0], offset=jobs[j][1], frames=len(traj))).update(innovation_summary(nis_rows[i][1]))
     elapsed = shard.max_over_ranks(time.perf_counter() - t_all)          # barrier before, max over ranks after: the bench contract's clock
     allt = shard.gather_trajectories(local_traj, len(jobs), world, rank)
-    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm})
+    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm, 'nis': local_nis})
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         for j, (seq, off) in enumerate(jobs):
@@ -488,6 +515,11 @@ def main(argv=None):
                 with open(os.path.join(args.out, 'output_%s_offset%d_map.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
                     for t, rec in zip(ts, recs):
                         f.write('%.6f %d %.9f %.9f %.9f %d %d\n' % (t, rec['id'], rec['p'][0], rec['p'][1], rec['p'][2], rec['flags'], rec['n_obs']))
+        for r in per_rank if args.innovation else []:
+            for j, (ts, recs) in r['nis'].items():
+                with open(os.path.join(args.out, 'output_%s_offset%d_nis.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
+                    for t, rec in zip(ts, recs):
+                        f.write(format_nis_line(t, rec))
         rep = sweep_report(jobs, per_rank, elapsed, world)
         if args.landmarks:
             rep['landmarks'] = dict(cap=args.landmark_cap, records=[lm_dropped.get(j, (0, 0))[0] for j in range(len(jobs))],
@@ -512,6 +544,23 @@ def main(argv=None):
         print(json.dumps(rep))
     if world > 1:
         dist.destroy_process_group()
+
+
+def format_nis_line(t, rec):
+    """One line of an _nis file: `t`, then the eight integers of both blocks (lost-feature update first), then the four doubles of both."""
+    from .msckf_ops import _FS_DOUBLES, _FS_INTS
+    return '%.6f ' % t + ' '.join('%d' % rec[b][n] for b in range(2) for n in _FS_INTS) + ' ' + \
+        ' '.join('%.17g' % rec[b][n] for b in range(2) for n in _FS_DOUBLES) + '\n'
+
+
+def innovation_summary(recs):
+    """Run-wide figures of one stream from its records FILTER_STATS_DTYPE[n, 2]: nis_rows = sum of gamma_eval / sum of the evaluated
+    features' residual rows, reject_rate = 1 - sum of n_pass / sum of n_eval, both over the two updates of every pose (None: nothing evaluated)."""
+    from .msckf_ops import filter_stats_rows
+    rows = int(filter_stats_rows(recs)[0].sum()) if len(recs) else 0
+    n_eval = int(recs['n_eval'].sum()) if len(recs) else 0
+    return dict(nis_rows=float(recs['gamma_eval'].sum()) / rows if rows > 0 else None,
+                reject_rate=1.0 - int(recs['n_pass'].sum()) / n_eval if n_eval > 0 else None)
 
 
 def sweep_report(jobs, per_rank, elapsed, world):
