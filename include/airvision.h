@@ -1058,11 +1058,46 @@ int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);  
  * cam_cap = 0 only asks for imu32 and the count.  Drain (wait 0) first. */
 int  av_msckf_batch_get_state(av_msckf_batch* b, int stream_idx, double imu32[32], int64_t* cam_ids, double* cam_qp7, int cam_cap, int32_t* n_cam);
 /* A failure that concerns ONE stream (its camera window or the block list of one of its updates outgrew a fixed capacity)
- * stops that stream only: from then on it idles and its out[s*12] reads -1; the other streams of the batch keep stepping
+ * stops that stream only: from then on (until av_msckf_batch_restart) it idles and its out[s*12] reads -1; the other streams of the batch keep stepping
  * (the reference's sequences are separate processes, run.bat:4-12).  *status = 0 while the stream runs, else the
  * AV_E_* code that stopped it, with the reason in msg.  Configuration errors (rows_cap vs cap, LDS limits) and HIP errors
  * concern the whole batch and are returned by the step / wait as before. */
 int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* status, char* msg, int msg_cap);
+/* Stream restart: one stream back to "as created" while its neighbours keep stepping.  After a restart of stream s, s is bit for bit a
+ * stream of a freshly created batch / engine that is fed the same inputs from then on, and every other stream is bit for bit what it would
+ * have been without the call.  Nothing is allocated or freed.  Use it when out[s*12] reads -1 (the stream stopped), when a sequence has
+ * ended and its slot is to take the next one, or when a consumer judges from the published covariance or statistics that a stream has
+ * diverged.  A vehicle has a stream in the engine and one in the filter: restart both.
+ * av_msckf_batch_restart(b, stream_idx, n): n stream indices of the batch (of the whole batch, whatever its stream groups).  Legal at any
+ * time: before the first step (host state only: there is no device state yet) and with steps queued -- it then drains the queue first,
+ * like av_msckf_batch_launch_shape; the queued steps retire as steps of the old life and their outputs are delivered.  n = 0 is a
+ * no-op, an index listed twice counts once, an index out of range is AV_E_INVALID with nothing touched.  Device-resident filter only:
+ * under AV_MSCKF_STORE=host the call is AV_E_INVALID, with a text that names AV_MSCKF_STORE.  Returns when the device state is reset.
+ *   Reset, host:   the IMU buffer is EMPTIED -- samples pushed before the call belong to the old life, and the stream goes live again
+ *                  only after initialize_gravity_and_bias has seen 200 new samples (msckf.py:230-249); the gravity / first-image /
+ *                  initialisation-sent flags, the camera-state id counter, state and extrinsics (the batch's create-time values);
+ *                  the failure code and text (av_msckf_batch_stream_status reads 0, ""); the parity-test tap's captures.
+ *   Reset, device: the IMU state record, state dimension 21, no camera states, the stream's whole covariance region (create-time
+ *                  diagonal, zero elsewhere), the observation store (empty, insertion counter 0, header clear, arrays as allocated), the
+ *                  stream's rows of the pose, odometry-covariance, landmark and statistics buffers.  Camera-state ids and the map's
+ *                  insertion order begin again at 0.
+ *   Not reset:     av_msckf_batch_counters and av_msckf_batch_work keep accumulating over all lives; the batch's configuration, its
+ *                  output switches and capacities; every other stream.
+ * av_frontend_restart(fe, stream_idx, n, stream): the same for streams of a front-end engine.  The host state is reset at once (it is
+ * consumed inside the step calls); the device state by a small kernel on `stream`, behind what is enqueued there and ahead of the next
+ * step.  Legal between av_frontend_prestage and the step (prestaged pyramids are of images, not of stream state), with a feature
+ * read-back pending (it still delivers the old life's features), on every entry path and with the frame store.
+ *   Reset:         the stream's IMU buffer, previous time stamp, first-frame flag and frame number (AV_FE_RANSAC's draws hash it); its
+ *                  previous entry of the frame store; on the device first-frame flag, id counter (feature ids begin again at 0), both
+ *                  grids' counts, the counters of av_frontend_read_counters and av_frontend_read_ransac_counts.
+ *   Not reset:     masks, photometric tables, exposure factors, range settings and records, the frame store's frames and everything else
+ *                  that belongs to the engine and not to the stream; the message of the last step (av_frontend_features_dev) until the
+ *                  next step replaces it.
+ * Ids repeat across lives: a consumer that keys on feature or camera-state ids keeps a generation count per stream (the Python classes
+ * do: `generation`).  Known limits: the filter's restart drains the queue; no save or restore of a stream's state; nothing on the
+ * host-bookkeeping path. */
+int  av_msckf_batch_restart(av_msckf_batch* b, const int32_t* stream_idx, int n);
+int  av_frontend_restart(av_frontend* fe, const int32_t* stream_idx, int n, void* stream);
 /* Run statistics over all streams (drain first): [steps, stream-steps that ran prune_cam_state_buffer (msckf.py:712-786),
  * stream-steps whose lost-feature candidates outgrew rows_cap (device-resident filter: rows taken from the shared overflow pool;
  * AV_MSCKF_STORE=host: gated first, stored in a second pass), device-buffer

@@ -1,0 +1,270 @@
+"""Stream restart of the batched filter (include/airvision.h, "Stream restart"; BatchedMSCKF.restart): after `restart([s])` stream s is
+bit for bit a stream of a freshly created batch fed the same inputs, every other stream is bit for bit what it would have been without
+the call, and nothing is allocated.
+
+Streams and sizes are those of tests/test_gpu_filter_stats.py (filter_stats_ref.streams3: seeds 7, 100 and 101, 50 features per frame, 40
+frames), the smallest that reach a full window and a pruning update.  Three runs per configuration, computed once and shared:
+  A  the three streams for 40 frames, odometry covariance, landmark map and innovation statistics on;
+  B  the same, but after frame 26 -- past the first pruning, the window full -- the restarted slot is given a NEW seed-101 stream from
+     its first IMU sample for 30 frames; the other two keep their frames while they have any and idle afterwards;
+  C  a fresh batch of three whose restarted slot gets that seed-101 life from step 0 while the others idle.
+Every comparison between runs of the library is `view(np.uint64)` / byte equality.  B's second life is also held to a fresh LandmarkOracle
+(an OracleMSCKF that lists its landmarks) with the comparison and the bar tests/test_gpu_landmarks.py applies to a fresh stream."""
+import ctypes
+
+import pytest
+
+import filter_stats_ref as R
+import landmark_ref as L
+import restart_helpers as H
+
+pytestmark = pytest.mark.gpu
+
+N_A = R.N_FRAMES            # 40
+AT = 27                     # the restart: ahead of step 27, i.e. after frame 26
+N_NEW = 30                  # frames of the second life
+N_B = AT + N_NEW
+
+
+def _new_life(cfg):
+    from uav_airvision_amd.synth import SyntheticFeatureStream
+    return SyntheticFeatureStream(cfg, seed=101, n_frames=N_NEW, n_features=50, motion_scale=1.25)
+
+
+_CACHE = {}
+
+
+def _abc(cfg, env_name, slot):
+    """Runs A, B and C under one environment, the restart on `slot`."""
+    key = (env_name, slot)
+    if key in _CACHE:
+        return _CACHE[key]
+    env = {'wg256': {}, 'wg64': {'AV_DK_WG': '64'}, 'groups2': {'AV_MSCKF_GROUPS': '2'}}[env_name]
+    if ('A', env_name) not in _CACHE:
+        _CACHE['A', env_name] = H.run_lives(cfg, [[H.Life(0, s, N_A)] for s in R.streams3(cfg)], N_A, env=env)
+    a = _CACHE['A', env_name]
+    plan_b = [[H.Life(0, s, N_A if i != slot else AT)] for i, s in enumerate(R.streams3(cfg))]
+    plan_b[slot].append(H.Life(AT, _new_life(cfg), N_NEW))
+    ora = L.LandmarkOracle(cfg)
+    b = H.run_lives(cfg, plan_b, N_B, env=env, oracles={slot: {1: ora}})
+    plan_c = [[] for _ in range(3)]
+    plan_c[slot] = [H.Life(0, _new_life(cfg), N_NEW)]
+    c = H.run_lives(cfg, plan_c, N_NEW, env=env)
+    _CACHE[key] = (a, b, c)
+    return _CACHE[key]
+
+
+def _check_abc(cfg, env_name, slot, shape):
+    a, b, c = _abc(cfg, env_name, slot)
+    assert a['shape'] == shape and b['shape'] == shape and c['shape'] == shape, (a['shape'], b['shape'], c['shape'])
+    assert b['restarts'] == [(AT, [slot])] and b['generation'].tolist() == [1 if i == slot else 0 for i in range(3)]
+    # the window was full and had been pruned when the restart came
+    assert any(a['sts'][k][slot][1]['flags'] & R.FS_RAN for k in range(AT))
+    for k in range(N_A):
+        for s in range(3):
+            if s == slot and k >= AT:
+                continue
+            assert H.same_step(b, k, s, a, k, s) is None, ('stream %d step %d differs from the run without restart: ' % (s, k)) + str(H.same_step(b, k, s, a, k, s))
+    for k in range(N_A, N_B):                                # the neighbours have no frames left: they idle, unchanged
+        for s in range(3):
+            if s != slot:
+                assert b['outs'][k][s, 0] == 0.0 and H.same(b['outs'][k][s, 1:], a['outs'][N_A - 1][s, 1:]), (s, k)
+    for s in range(3):
+        if s != slot:
+            assert H.same_state(b['state'][s], a['state'][s]) and H.same(b['cov'][s], a['cov'][s]) and b['sizes'][s] == a['sizes'][s], s
+    # the second life: a fresh stream, step for step, in all four outputs and in the state it ends with
+    live = ran1 = 0
+    for j in range(N_NEW):
+        why = H.same_step(b, AT + j, slot, c, j, slot)
+        assert why is None, 'second life, frame %d: %s differs from a fresh batch' % (j, why)
+        live += c['outs'][j][slot, 0] == 1.0
+        ran1 += bool(c['sts'][j][slot][1]['flags'] & R.FS_RAN)
+    assert live >= 20 and ran1 >= 1 and c['sizes'][slot][1] >= 18, (live, ran1, c['sizes'])      # it reached a full window and a pruning update
+    assert H.same_state(b['state'][slot], c['state'][slot]) and H.same(b['cov'][slot], c['cov'][slot]) and b['sizes'][slot] == c['sizes'][slot]
+    assert b['state'][slot]['cam_ids'].tolist() == c['state'][slot]['cam_ids'].tolist() and len(c['state'][slot]['cam_ids']) > 0
+    # ... and the reference's
+    worst, total = 0.0, 0
+    for j in range(N_NEW):
+        rec, n = b['lms'][AT + j]
+        ref = b['refs'][AT + j][slot]
+        worst = max(worst, H.against_landmark_ref(rec, n, slot, ref, H.LM_CAP, '%s second life frame %d' % (env_name, j)))
+        total += len(ref)
+    assert total > 100, total
+    print('%s, slot %d: %d landmark records of the second life checked, largest position error / bar = %.3e' % (env_name, slot, total, worst))
+    # counters accumulate over the lives: B counts the second life's pruning steps (C's) on top of the first life's and the neighbours'
+    assert c['counters']['prune_stream_steps'] >= 1 and b['counters']['prune_stream_steps'] > c['counters']['prune_stream_steps'], (b['counters'], c['counters'])
+    assert b['counters']['steps'] == N_B and b['counters']['devbuf_growths'] == 0, b['counters']
+
+
+def test_a_restarted_stream_is_a_fresh_stream_and_its_neighbours_do_not_notice(cfg):
+    _check_abc(cfg, 'wg256', 1, [(3, 256)])
+
+
+def test_the_same_with_one_wavefront_per_stream(cfg):
+    _check_abc(cfg, 'wg64', 1, [(3, 64)])
+
+
+def test_the_same_in_the_second_of_two_stream_groups(cfg):
+    _check_abc(cfg, 'groups2', 2, [(2, 256), (1, 256)])
+
+
+def test_restart_with_steps_queued_drains_and_delivers_them(cfg):
+    """Steps 24, 25 and 26 are submitted and left in the queue; the restart comes without a wait.  The three steps' outputs are there when
+    it returns, and the whole run equals the synchronous one."""
+    _, b, _ = _abc(cfg, 'wg256', 1)
+    plan = [[H.Life(0, s, N_A if i != 1 else AT)] for i, s in enumerate(R.streams3(cfg))]
+    plan[1].append(H.Life(AT, _new_life(cfg), N_NEW))
+    seen = []
+
+    def after_restart(k, bat, run):
+        for q in (24, 25, 26):
+            for s in range(3):
+                assert H.same_step(run, q, s, b, q, s) is None, (q, s)
+        seen.append(k)
+    q = H.run_lives(cfg, plan, N_B, queued=(24, 25, 26), after_restart=after_restart)
+    assert seen == [AT]
+    for k in range(N_B):
+        for s in range(3):
+            assert H.same_step(q, k, s, b, k, s) is None, (k, s, H.same_step(q, k, s, b, k, s))
+    assert all(H.same_state(q['state'][s], b['state'][s]) for s in range(3))
+
+
+def test_a_stopped_stream_runs_again_after_restart(cfg):
+    """AV_MSCKF_POOL_ROWS=64 and a blank frame stop stream 0 (tests/test_gpu_filter_stats.py: test_idle_blank_and_stopped_streams).
+    restart([0]) clears the status; fed a new life without a blank frame -- it never needs the 64-row pool -- stream 0 publishes again
+    and equals a fresh stream bit for bit.  Stream 1 equals the run without restart throughout."""
+    from uav_airvision_amd.synth import SyntheticFeatureStream
+    n, at, n_new = 24, 19, 26
+    env = {'AV_MSCKF_POOL_ROWS': '64'}
+    kw = dict(env=env, cap=192, rows_cap=2048)
+    mk = lambda: [SyntheticFeatureStream(cfg, seed=91, n_frames=n, n_features=150), SyntheticFeatureStream(cfg, seed=92, n_frames=n, n_features=40)]
+    new = lambda: SyntheticFeatureStream(cfg, seed=100, n_frames=n_new, n_features=50)
+    s0, s1 = mk()
+    a = H.run_lives(cfg, [[H.Life(0, s0, n, blank=(17,))], [H.Life(0, s1, n)]], n, **kw)
+    assert [k for k in range(n) if a['outs'][k][0, 0] < 0] == list(range(17, n))
+    s0, s1 = mk()
+    status = {}
+
+    def before(k, bat, run):
+        if k == at:
+            status['stopped'] = bat.stream_status(0)
+
+    def after_restart(k, bat, run):
+        status['restarted'] = (bat.stream_status(0), bat.stream_status(1))
+    b = H.run_lives(cfg, [[H.Life(0, s0, at, blank=(17,)), H.Life(at, new(), n_new)], [H.Life(0, s1, n)]], at + n_new, before=before, after_restart=after_restart, **kw)
+    assert status['stopped'][0] != 0 and status['stopped'][1] != ''
+    assert status['restarted'] == ((0, ''), (0, ''))
+    c = H.run_lives(cfg, [[H.Life(0, new(), n_new)], []], n_new, **kw)
+    for k in range(n):
+        assert H.same_step(b, k, 1, a, k, 1) is None, k
+        if k < at:
+            assert H.same_step(b, k, 0, a, k, 0) is None, k
+    assert H.same_state(b['state'][1], a['state'][1]) and H.same(b['cov'][1], a['cov'][1])
+    pub = 0
+    for j in range(n_new):
+        assert H.same_step(b, at + j, 0, c, j, 0) is None, (j, H.same_step(b, at + j, 0, c, j, 0))
+        assert b['outs'][at + j][0, 0] >= 0.0 and b['status'][at + j][0] == (0, ''), j          # the new life does not stop
+        pub += b['outs'][at + j][0, 0] == 1.0
+    assert pub >= 15, pub
+    assert H.same_state(b['state'][0], c['state'][0]) and H.same(b['cov'][0], c['cov'][0]) and b['sizes'][0] == c['sizes'][0]
+    # counters accumulate over the lives: stream 0's first life (stopped at 17 in both runs) + its second (C's); stream 1 is A's
+    for name in ('prune_stream_steps', 'two_pass_streams'):
+        assert b['counters'][name] == a['counters'][name] + c['counters'][name], (name, a['counters'], b['counters'], c['counters'])
+    assert a['counters']['prune_stream_steps'] >= 1 and c['counters']['prune_stream_steps'] >= 1
+
+
+def _live():
+    from uav_airvision_amd import _native as N
+    out = (ctypes.c_int64 * 4)()
+    N.check(N.lib().av_debug_live_resources(ctypes.byref(out)))
+    return [int(v) for v in out]
+
+
+def test_edges(cfg, monkeypatch):
+    from uav_airvision_amd import _native as N
+    from uav_airvision_amd.msckf_ops import BatchedMSCKF
+    for k in H.ENV_KEYS:
+        monkeypatch.delenv(k, raising=False)
+    a, _, c = _abc(cfg, 'wg256', 1)
+    n = 12
+
+    # a restart before the first step (and before the first IMU sample) equals no restart; so do n = 0 and, later, a repeated index
+    def before(k, bat, run):
+        if k == 0:
+            bat.restart([0, 1, 2])
+            bat.restart([])
+            assert bat.generation.tolist() == [1, 1, 1]
+    e = H.run_lives(cfg, [[H.Life(0, s, n)] for s in R.streams3(cfg)], n, before=before)
+    for k in range(n):
+        for s in range(3):
+            assert H.same_step(e, k, s, a, k, s) is None, (k, s)
+
+    # an index listed twice counts once; an index out of range raises and changes nothing
+    def mid(k, bat, run):
+        if k == 8:
+            for bad in ([3], [-1], [1, 7]):
+                with pytest.raises(N.AirvisionError) as err:
+                    bat.restart(bad)
+                assert err.value.code == N.AV_E_INVALID and 'out of range' in str(err.value)
+            assert bat.generation.tolist() == [0, 0, 0]
+            bat.restart([])
+            assert bat.generation.tolist() == [0, 0, 0]
+    e = H.run_lives(cfg, [[H.Life(0, s, n)] for s in R.streams3(cfg)], n, before=mid)
+    for k in range(n):
+        for s in range(3):
+            assert H.same_step(e, k, s, a, k, s) is None, (k, s)
+    st = R.streams3(cfg)
+    twice = dict(n=0)
+
+    def dup(k, bat, run):
+        if k == 8:
+            bat.restart([2, 2, 2])
+            assert bat.generation.tolist() == [0, 0, 1]
+            assert bat.sizes(2) == (21, 0, 0) and bat.stream_status(2) == (0, '')
+            twice['n'] += 1
+    e = H.run_lives(cfg, [[H.Life(0, st[0], n)], [H.Life(0, st[1], n)], [H.Life(0, st[2], 8)]], n, before=dup)
+    assert twice['n'] == 1
+    for k in range(n):
+        for s in range(2):
+            assert H.same_step(e, k, s, a, k, s) is None, (k, s)
+        if k >= 8:
+            assert e['outs'][k][2, 0] == 0.0 and H.same(e['outs'][k][2], c['outs'][0][0]), k          # restarted and idle: the pose record of a stream that never ran
+
+    # refused on the host-bookkeeping path, with the wording of the three output switches
+    monkeypatch.setenv('AV_MSCKF_STORE', 'host')
+    bat = BatchedMSCKF(cfg, 2)
+    try:
+        with pytest.raises(N.AirvisionError) as err:
+            bat.restart([0])
+        assert err.value.code == N.AV_E_INVALID and 'AV_MSCKF_STORE' in str(err.value) and 'device-resident' in str(err.value)
+        assert bat.generation.tolist() == [0, 0]
+    finally:
+        bat.close()
+    monkeypatch.delenv('AV_MSCKF_STORE')
+
+
+def test_restart_allocates_nothing(cfg, monkeypatch):
+    """av_debug_live_resources reads the same before and after ten restarts, and what the batch holds is back at four zeros after
+    close().  The counts are the process's: objects that other tests of the same run keep alive are in them, so the batch's share is
+    the difference to the reading taken before it is created (as tests/test_gpu_filter_stats.py takes its base)."""
+    from uav_airvision_amd.msckf_ops import BatchedMSCKF
+    for k in H.ENV_KEYS:
+        monkeypatch.delenv(k, raising=False)
+    base = _live()
+    st = R.streams3(cfg)
+    bat = BatchedMSCKF(cfg, 3, odom_cov=True, landmarks=True, landmark_cap=H.LM_CAP, stats=True)
+    try:
+        lives = [H.Life(0, s, 6) for s in st]
+        for k in range(6):
+            push = [(i, m) for i, Lf in enumerate(lives) for m in Lf.imu_before(k)]
+            bat.push_imu([i for i, _ in push], [m.timestamp for _, m in push], [m.angular_velocity for _, m in push], [m.linear_acceleration for _, m in push])
+            bat.step(*H.arrays([Lf.message(k) for Lf in lives], H.CAP))
+        before = _live()
+        assert before[0] > base[0] and before[1] > base[1] and before[2] > base[2]
+        for r in range(10):
+            bat.restart([r % 3, (r + 1) % 3])
+            assert _live() == before, r
+        assert bat.generation.tolist() == [7, 7, 6]
+    finally:
+        bat.close()
+    assert [a - b for a, b in zip(_live(), base)] == [0, 0, 0, 0]

@@ -323,6 +323,8 @@ SIGNATURES = {
     'av_frontend_next_exposure': (C.c_int, [_P, _P, _P, C.c_int]),
     'av_frontend_read_exposure': (C.c_int, [_P, C.c_int, _P]),
     'av_photometric_vector_path': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    'av_msckf_batch_restart': (C.c_int, [_P, _P, C.c_int]),
+    'av_frontend_restart': (C.c_int, [_P, _P, C.c_int, _P]),
     'av_frontend_enable_timing': (C.c_int, [_P, C.c_int]),
     'av_frontend_read_timing': (C.c_int, [_P, C.POINTER(C.c_double * 4), C.POINTER(C.c_int32 * 4)]),
 }

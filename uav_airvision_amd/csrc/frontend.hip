@@ -81,6 +81,24 @@ struct FeDev {
 
 __device__ __forceinline__ bool fe_idle(const FeDev& d, int s) { return d.slot_cur != nullptr && d.slot_cur[s] < 0; }
 
+// ---- stream restart (include/airvision.h, "Stream restart"; av_frontend_restart; no step launches it): a thread per listed stream puts
+//      its device state back to what av_frontend_create made: the next frame is an initialisation, ids begin again at 0, both grids are
+//      empty, the counters read 0.  The grids' entries, the candidate arrays and the mask need nothing: the counts say how much of them
+//      is read, and finalize_kernel leaves the mask all ones after every step.  rs_counts: AV_FE_RANSAC's per-stream counts (null
+//      without the stage).  (Ahead of the step's kernels in this file, so that each of them keeps its place behind its neighbour in the
+//      code object.)
+__global__ __launch_bounds__(64) void restart_kernel(FeDev d, const int* list, int n, int* rs_counts)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int s = list[i];
+    if (s < 0 || s >= d.S) return;                           // (never: the entry checks; keeps a bad list inside the buffers)
+    d.first_frame[s] = 1; d.next_id[s] = 0;
+    d.n_feat[0][s] = 0; d.n_feat[1][s] = 0;
+    for (int k = 0; k < NCNT; ++k) d.counters[s * NCNT + k] = 0;
+    if (rs_counts) for (int k = 0; k < 4; ++k) rs_counts[4 * (size_t)s + k] = 0;
+}
+
 // the static mask byte under pixel coordinate (x, y): m[int(y)][int(x)], truncation (the reference's rule for its 7x7 mask,
 // feature_adder.py:59-62).  The callers have tested the point against the image; the clamp only keeps a NaN inside the buffer.
 __device__ __forceinline__ bool smask_valid(const FeDev& d, const uint8_t* m, float x, float y)
@@ -721,6 +739,9 @@ struct av_frontend {
     // that a prestaged frame does not replace the records of the step before it (the frame store: FrameStore::range_d)
     Range16 g16 = {AV_GRAY16_SHIFT, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr}; uint32_t* g16_hist = nullptr; uint32_t* g16_rec = nullptr;
     bool stepped = false, stepped_frames = false;      // a step has run (av_frontend_read_image has something to return); it read the frame store
+    // av_frontend_restart: the index list of a call on its way to the device, four pinned slots with an event each and a device slot
+    // [4][S] to match, taken at create so that a restart allocates nothing
+    PinnedRing<int, 4> rs_h; int* rs_d = nullptr;
 
     explicit av_frontend(int S) : streams(S) {}
 };
@@ -1167,6 +1188,7 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
 #undef A
     rc = fe->hH.create(fe->res, 9 * (size_t)S + S + (ransac ? 19 * (size_t)S : 0));
     if (!rc && fe->expo) rc = fe->ex_h.create(fe->res, 2 * (size_t)S);
+    if (!rc && !(rc = fe->rs_h.create(fe->res, (size_t)S))) rc = fe->res.dev(&fe->rs_d, 4 * (size_t)S);
     for (int i = 0; i < 2 && !rc; ++i) {
         av_frontend::ReadSlot& r = fe->rd[i];
         if (!(rc = fe->res.pinned(&r.n, (size_t)S)) && !(rc = fe->res.pinned(&r.ids, (size_t)S * d.MAXF)) && !(rc = fe->res.pinned(&r.uv, 4 * (size_t)S * d.MAXF)) &&
@@ -1447,6 +1469,43 @@ AV_EXPORT int av_frontend_step_frames(av_frontend* fe, const int32_t* slot_of_st
     for (int s = 0; s < fe->d.S; ++s)
         if (slot_of_stream[s] >= fe->fs.n_slots) { av_set_error("av_frontend_step_frames: stream %d: entry %d outside the store (%d entries)", s, slot_of_stream[s], fe->fs.n_slots); return AV_E_INVALID; }
     return step_impl(fe, nullptr, nullptr, 0, timestamps, (hipStream_t)stream, true, slot_of_stream);
+}
+
+// Stream restart (include/airvision.h, "Stream restart").  Host state is consumed inside the step calls, so it is reset at once; the
+// device state by restart_kernel on `stream`, behind whatever the caller has enqueued there (a step, a prestage, a pending read-back)
+// and ahead of the step it enqueues next.
+AV_EXPORT int av_frontend_restart(av_frontend* fe, const int32_t* stream_idx, int n, void* stream)
+{
+    if (!fe || n < 0 || (n > 0 && !stream_idx)) { av_set_error("av_frontend_restart: bad arguments"); return AV_E_INVALID; }
+    const int S = fe->d.S;
+    for (int i = 0; i < n; ++i) if (stream_idx[i] < 0 || stream_idx[i] >= S) { av_set_error("av_frontend_restart: stream %d out of range", stream_idx[i]); return AV_E_INVALID; }
+    if (n == 0) return AV_OK;
+    hipStream_t st = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(fe->device));
+    int* list = nullptr;
+    int rc = fe->rs_h.take(&list);
+    if (rc) return rc;
+    int m = 0;
+    std::vector<char> seen((size_t)S, 0);                    // a repeated index is listed once (the pinned slot holds S entries)
+    for (int i = 0; i < n; ++i) {
+        const int s = stream_idx[i];
+        if (seen[s]) continue;
+        seen[s] = 1;
+        StreamHost& sh = fe->streams[s];
+        {
+            std::lock_guard<std::mutex> g(sh.mu);
+            sh.imu.clear(); sh.t_prev = 0.0; sh.first = true; sh.frame = 0;
+        }
+        if (!fe->fs.prev.empty()) fe->fs.prev[s] = -1;
+        list[m++] = s;
+    }
+    fe->any_first = true;
+    int* list_d = fe->rs_d + (size_t)fe->rs_h.cur * S;
+    AV_HIP(hipMemcpyAsync(list_d, list, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
+    if ((rc = fe->rs_h.sent(st))) return rc;
+    hipLaunchKernelGGL(restart_kernel, dim3((m + 63) / 64), dim3(64), 0, st, fe->d, (const int*)list_d, m, fe->ransac ? fe->rs_counts : nullptr);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
 }
 
 AV_EXPORT int av_frontend_max_features(const av_frontend* fe) { return fe ? fe->d.MAXF : AV_E_INVALID; }

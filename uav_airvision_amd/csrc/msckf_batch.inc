@@ -1109,7 +1109,7 @@ int b_chain_finish(av_msckf_batch* b, std::vector<FeatRef>& refs, ChainCtx& ctx)
 }  // namespace
 
 static void sub_destroy(av_msckf_batch* b);
-namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn, av_filter_stats* stats); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); }
+namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn, av_filter_stats* stats); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm); }
 
 // Stream for the filter's kernels.  AV_MSCKF_CUS="first:count" confines them to `count` compute units starting at CU `first`
 // (hipExtStreamCreateWithCUMask) -- together with a complementary mask on the caller's front-end stream this partitions the
@@ -2133,6 +2133,53 @@ AV_EXPORT int av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, in
     if (!b || stream_idx < 0 || stream_idx >= b->S) { av_set_error("av_msckf_batch_stream_status: bad arguments"); return AV_E_INVALID; }
     if (b->subs.empty()) return sub_stream_status(b, stream_idx, status, msg, msg_cap);
     return sub_stream_status(b->subs[stream_idx / b->per_sub], stream_idx % b->per_sub, status, msg, msg_cap);
+}
+
+// Stream restart (airvision.h, "Stream restart").  One group: its listed streams (local indices, distinct, in range; the group is
+// drained) go back to what sub_create and dev_reserve made of them -- the host record here, the device state by dk_restart.
+static int sub_restart(av_msckf_batch* g, const std::vector<int>& list)
+{
+    for (const int s : list) {
+        BStream& T = g->st[s];
+        std::lock_guard<std::mutex> lk(T.mu);
+        T.imu.clear();                                       // samples pushed before the call belong to the old life
+        T.gravity_set = false; T.first_img = true; T.null_aliased = false; T.active = false;
+        T.gravity_time = 0; T.next_imu_id = 0; T.imu_id = 0; T.has_imu_id = false; T.dev_init_sent = false;
+        T.ts = 0; T.tracking_rate = 0; T.n = IMU_DIM;
+        for (int i = 0; i < 4; ++i) { T.q[i] = i == 3 ? 1.0 : 0.0; T.qn[i] = i == 3 ? 1.0 : 0.0; }
+        for (int i = 0; i < 3; ++i) { T.p[i] = 0; T.bg[i] = 0; T.ba[i] = 0; T.pn[i] = 0; T.vn[i] = 0; T.v[i] = g->vel0[i]; T.gravity[i] = g->gravity0[i]; T.t_ci[i] = g->t_ci0[i]; }
+        for (int i = 0; i < 9; ++i) T.R_ic[i] = g->R_ic0[i];
+        T.cams.clear(); T.map.clear();
+        T.failed = 0; T.fail_msg[0] = 0;
+        for (int ph = 0; ph < 2; ++ph) { T.dbg_gamma[ph].clear(); T.dbg_dx[ph].clear(); T.dbg_P[ph].clear(); T.dbg_rows[ph] = 0; T.dbg_n[ph] = 0; }
+    }
+    return dev_restart(g, list.data(), (int)list.size(), g->own);
+}
+
+AV_EXPORT int av_msckf_batch_restart(av_msckf_batch* b, const int32_t* stream_idx, int n)
+{
+    if (!b || n < 0 || (n > 0 && !stream_idx)) { av_set_error("av_msckf_batch_restart: bad arguments"); return AV_E_INVALID; }
+    for (int i = 0; i < n; ++i) if (stream_idx[i] < 0 || stream_idx[i] >= b->S) { av_set_error("av_msckf_batch_restart: stream %d out of range", stream_idx[i]); return AV_E_INVALID; }
+    std::vector<av_msckf_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    for (av_msckf_batch* g : parts) if (!g->dev) {
+        av_set_error("av_msckf_batch_restart: the stream restart needs the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)");
+        return AV_E_INVALID;
+    }
+    if (n == 0) return AV_OK;
+    int rc = av_msckf_batch_wait(b, 0);                      // queued steps belong to the old life: they retire, their outputs are delivered
+    if (rc) return rc;
+    // every index to its group and local index; a repeated index counts once
+    std::vector<std::vector<int>> lists(parts.size());
+    std::vector<char> seen((size_t)b->S, 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = stream_idx[i];
+        if (seen[s]) continue;
+        seen[s] = 1;
+        if (b->subs.empty()) lists[0].push_back(s); else lists[(size_t)(s / b->per_sub)].push_back(s % b->per_sub);
+    }
+    for (size_t gi = 0; gi < parts.size(); ++gi) if (!lists[gi].empty() && (rc = sub_restart(parts[gi], lists[gi]))) return rc;
+    return AV_OK;
 }
 
 // Parity-test tap.  capture(1): from the next step on every stream keeps, for the two update phases of its LAST step, what the

@@ -919,6 +919,71 @@ __global__ __launch_bounds__(256, 5) void dk_finish_cov_lm_st(DevArgs a, double*
 }
 
 // ------------------------------------------------------------------------------------------------
+// dk_restart: stream restart (include/airvision.h, "Stream restart"; host side: dev_restart).  No step launches it.  One workgroup per
+// LISTED stream, s = list[blockIdx.x] (the host has checked every index against S and removed repeats), on the group's own stream, so a
+// step enqueued behind it finds the stream as dev_reserve first made it:
+//   DState      zero, q = qn = identity, n = 21, first_img = 1, v / t_ci / R_ic / gravity of the batch's create call; its two run counters
+//               (n_prune_steps, n_two_pass) are handed to the host first (carry), which keeps av_msckf_batch_counters accumulating
+//   nstate, ncam, grav  21, 0, 0
+//   P           the stream's WHOLE pstride region: zero, the create-time diagonal in the 21 x 21 block.  A new batch holds zeros outside
+//               the live block, a used one the rows and columns of camera states that have left; the augmentation and the updates write
+//               what they read there, but the region is cleared rather than that argued for every kernel.
+//   store       avs_restart: empty window and map, births and the whole header zero (avs_clear alone leaves births and the sticky
+//               hdr[AVS_OVERFLOW]), every persistent array as allocated
+//   outputs     the stream's rows of out, of the odometry-covariance, landmark (records and counts) and statistics buffers: zero, as
+//               allocated.  Every step rewrites them for every stream; they are cleared so that a read of the buffers finds no old life.
+// Not touched: Pn, T, Kt, scratch, the block buffers, the per-phase feature arrays and lists, the store's scratch -- every step writes
+// what it reads of them; `work` (av_msckf_batch_work accumulates).  Overflow pool: a stream holds NO pool rows between steps.  The pool
+// is a bump counter, cnt[4] of the step's counter set, zeroed for every step by the step before it (dk_state: cnt_next); a stream's
+// share is the offset dev_build_candidates adds to its f_rowoff for that phase only.  There is nothing to hand back.
+// Plain vector stores: no atomics, no LDS (the team's scan is not used: red stays null).
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(DState) % 8 == 0, "dk_restart clears DState by 8-byte words");
+struct DRestart {
+    const int* list; int* carry;                              // [n] streams; [n][2] the counters they held
+    double v0[3], t_ci[3], gravity[3], R_ic[9];               // create-time values of the batch
+    double* odom; LmOut lm; DUpdStats* stats;                 // the optional outputs (null: off)
+};
+__global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
+{
+    const int s = r.list[blockIdx.x], tid = threadIdx.x, nt = blockDim.x;
+    if (s < 0 || s >= a.S) return;                            // (never: the host checks; keeps a bad list inside the buffers)
+    if (tid == 0) {
+        DState* Dg = a.st + s;
+        r.carry[2 * blockIdx.x] = Dg->n_prune_steps; r.carry[2 * blockIdx.x + 1] = Dg->n_two_pass;
+        DState D;
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(&D);
+        for (int i = 0; i < (int)(sizeof(DState) / 8); ++i) w[i] = 0ull;
+        D.q[3] = 1.0; D.qn[3] = 1.0; D.n = IMU_DIM; D.first_img = 1;
+        for (int i = 0; i < 3; ++i) { D.v[i] = r.v0[i]; D.t_ci[i] = r.t_ci[i]; D.gravity[i] = r.gravity[i]; }
+        for (int i = 0; i < 9; ++i) D.R_ic[i] = r.R_ic[i];
+        *Dg = D;
+        a.nstate[s] = IMU_DIM; a.ncam[s] = 0;
+        for (int i = 0; i < 3; ++i) a.grav[3 * s + i] = 0.0;
+        for (int i = 0; i < 12; ++i) a.out[(size_t)s * 12 + i] = 0.0;
+        if (r.lm.rec) { r.lm.n[2 * (size_t)s] = 0; r.lm.n[2 * (size_t)s + 1] = 0; }
+    }
+    double* P = a.P + (size_t)s * a.pstride;
+    for (size_t i = tid; i < a.pstride; i += nt) {            // reset_state_cov (msckf.py:788-798) in a cleared region
+        const int rr = (int)(i / a.ld), c = (int)(i - (size_t)rr * a.ld);
+        double v = 0.0;
+        if (rr == c && rr < IMU_DIM) { const int blk[5] = {3, 6, 9, 15, 18}; for (int k = 0; k < 5; ++k) if (rr >= blk[k] && rr < blk[k] + 3) v = a.cov0[k]; }
+        P[i] = v;
+    }
+    if (r.odom) for (int i = tid; i < ODOM_COV_DOUBLES; i += nt) r.odom[(size_t)s * ODOM_COV_DOUBLES + i] = 0.0;
+    if (r.lm.rec) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(r.lm.rec + (size_t)s * r.lm.cap);
+        for (int i = tid; i < r.lm.cap * (int)(sizeof(DLandmark) / 8); i += nt) w[i] = 0ull;
+    }
+    if (r.stats) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(r.stats + 2 * (size_t)s);
+        for (int i = tid; i < 2 * (int)(sizeof(DUpdStats) / 8); i += nt) w[i] = 0ull;
+    }
+    AvsTeam T; T.red = nullptr;
+    avs_restart(T, dev_store(a, s));
+}
+
+// ------------------------------------------------------------------------------------------------
 // dk_prune_probe: parity tests only (av_msckf_predict_ops_dev; no step launches it).  Per stream, on the window as it stands:
 // ops bit 0: dev_find_redundant -> red[2 s], red[2 s + 1]; bit 1: remove_two_cams_body for the window positions rm[2 s] < rm[2 s + 1],
 // with the workgroup's threads as dk_finish has them.  The entry has checked every position against the window.
@@ -967,4 +1032,7 @@ struct DevPath {
     int hint[16] = {0};              // list lengths of the last finished step (grids of the next one are sized from them; the kernels stride anyway)
     bool have_hint = false;
     long long growths = 0, steps = 0;
+    // stream restart (dk_restart): the index list [S] and the counters the listed streams held [S][2], on the device and pinned; taken
+    // with the rest at dev_reserve, so a restart allocates nothing
+    int* rs_list_d = nullptr; int* rs_list_h = nullptr; int* rs_carry_d = nullptr; int* rs_carry_h = nullptr;
 };

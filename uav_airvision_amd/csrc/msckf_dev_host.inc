@@ -60,6 +60,8 @@ int dev_reserve(av_msckf_batch* b, int cap)
         if (b->odom_cov) DA(d->odom_d, S * ODOM_COV_DOUBLES)
         if (b->lm_cap > 0) { DA(d->lm.rec, S * b->lm_cap) DA(d->lm.n, S * 2) d->lm.cap = b->lm_cap; }
         if (b->stats_on) DA(d->stats_d, S * 2)
+        DA(d->rs_list_d, S) DA(d->rs_carry_d, S * 2)
+        if ((rc = b->res.pinned(&d->rs_list_h, S)) || (rc = b->res.pinned(&d->rs_carry_h, S * 2))) return rc;
         DAF(A.pos_of, S * A.ns, 0xFF) DAF(A.order, S * A.ns, 0xFF) DA(A.fr_n, S * A.ns) DA(A.hdr, S * AVS_HDR_WORDS) DA(A.births, S)
     }
     DA(A.fr_id, ne) DA(A.fr_z, ne * 4) DA(A.fr_fslot, ne) DA(A.fr_prev, ne) DA(A.fr_next, ne)
@@ -542,6 +544,29 @@ int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* 
         if (hipEventElapsedTime(&ms, sl.t0[ph], sl.t1[ph]) == hipSuccess) b->w_chain_ms += ms; else ++b->w_chain_dropped;
         sl.t_used[ph] = false;
     }
+    return AV_OK;
+}
+
+// Stream restart, device side: dk_restart over the n distinct streams of `list` (local indices, checked by the caller) on `stm`, then
+// the counters those streams held, added to the group's own so that av_msckf_batch_counters keeps accumulating.  The caller has drained
+// the group; the call returns when the kernel has run, so any later step or read-back, on whatever stream, finds the new state.
+int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm)
+{
+    DevPath* d = b->dev;
+    if (n <= 0 || d->cap == 0) return AV_OK;                 // before the first step there is no device state: the host's reset is all
+    AV_HIP(hipSetDevice(b->device));
+    memcpy(d->rs_list_h, list, sizeof(int) * (size_t)n);
+    AV_HIP(hipMemcpyAsync(d->rs_list_d, d->rs_list_h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stm));
+    DRestart r; memset(&r, 0, sizeof(r));
+    r.list = d->rs_list_d; r.carry = d->rs_carry_d;
+    for (int i = 0; i < 3; ++i) { r.v0[i] = b->vel0[i]; r.t_ci[i] = b->t_ci0[i]; r.gravity[i] = b->gravity0[i]; }
+    for (int i = 0; i < 9; ++i) r.R_ic[i] = b->R_ic0[i];
+    r.odom = d->odom_d; r.lm = d->lm; r.stats = d->stats_d;
+    hipLaunchKernelGGL(dk_restart, dim3((unsigned)n), dim3(256), 0, stm, d->A, r);
+    AV_LAUNCH_CHECK();
+    AV_HIP(hipMemcpyAsync(d->rs_carry_h, d->rs_carry_d, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipStreamSynchronize(stm));
+    for (int i = 0; i < n; ++i) { b->n_prune_stream_steps += d->rs_carry_h[2 * i]; b->n_two_pass_streams += d->rs_carry_h[2 * i + 1]; }
     return AV_OK;
 }
 

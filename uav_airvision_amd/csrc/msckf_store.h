@@ -93,6 +93,26 @@ AVS_FN void avs_clear(const AvsTeam& T, const AvsStore& V)
     T.sync();
 }
 
+// Stream restart (include/airvision.h, "Stream restart"): the store as it is right after its arrays were allocated.  avs_clear empties
+// the window and the map; what it leaves alone goes too -- the insertion counter, the whole header (AVS_OVERFLOW and the spare words
+// with it), and every persistent array: frames, links, feature table and free stack are zero like a new allocation's, so that no entry
+// of an earlier life can be told from one that was never written.  The scratch arrays are not touched: no operation reads one before it
+// has written it.  Plain stores, one barrier (avs_clear's).
+AVS_FN void avs_restart(const AvsTeam& T, const AvsStore& V)
+{
+    const size_t ne = (size_t)V.ns * V.cap;
+    for (size_t i = T.tid(); i < ne; i += T.nt()) {
+        V.fr_id[i] = 0; V.fr_fslot[i] = 0; V.fr_prev[i] = 0; V.fr_next[i] = 0;
+        V.fr_z[4 * i] = 0; V.fr_z[4 * i + 1] = 0; V.fr_z[4 * i + 2] = 0; V.fr_z[4 * i + 3] = 0;
+    }
+    for (int i = T.tid(); i < V.mcap; i += T.nt()) {
+        V.m_id[i] = 0; V.m_birth[i] = 0; V.m_init[i] = 0; V.m_nobs[i] = 0; V.m_tail[i] = 0; V.free_stack[i] = 0;
+        V.m_pos[(size_t)3 * i] = 0; V.m_pos[(size_t)3 * i + 1] = 0; V.m_pos[(size_t)3 * i + 2] = 0;
+    }
+    if (T.tid() == 0) { for (int i = 0; i < AVS_HDR_WORDS; ++i) V.hdr[i] = 0; *V.births = 0; }
+    avs_clear(T, V);
+}
+
 // add_feature_observations for one message (msckf.py:425-441).  A duplicate id inside one message re-assigns the same dict
 // key: the entry keeps the position of the first occurrence and takes the measurement of the last.  Returns the frame slot
 // (to every thread), or -1 if no slot is free / -2 if the feature table is full (nothing is changed then); *tracked = the

@@ -110,5 +110,17 @@ class ImageProcessingPipeline(object):
         config.image_format, binned (config.image_downscale) and / or equalised (config.use_clahe); refused with none of them."""
         return self._engine.read_image(0, cam)
 
+    def restart(self):
+        """No counterpart in the reference: the pipeline back to "as constructed" without rebuilding the engine (FrontendEngine.restart).
+        The next stereo_callback is an initialisation and feature ids begin again at 0; `generation` counts the restarts."""
+        self._engine.restart([0])
+        self.prev_cam0_msg = None
+        self.prev_pyr0 = None
+        self.first_frame = True
+
+    @property
+    def generation(self):
+        return int(self._engine.generation[0])
+
     def close(self):
         self._engine.close()

@@ -134,6 +134,24 @@ class MSCKF(object):
     def close(self):
         self._flt.close()
 
+    def restart(self):
+        """No counterpart in the reference: the filter back to "as constructed" without rebuilding it (BatchedMSCKF.restart).  IMU
+        messages received so far are dropped -- gravity is initialised again from the next 200 -- camera-state ids begin again at 0;
+        `generation` counts the restarts.  vio_result is unchanged."""
+        self._flt.restart([0])
+        self._n_imu = 0
+        self.is_gravity_set = False
+        self.tracking_rate = None
+        self.last_covariance = None
+        self.last_landmarks = None
+        self.last_landmarks_dropped = 0
+        self.last_innovation = None
+        self.debug = {}
+
+    @property
+    def generation(self):
+        return int(self._flt.generation[0])
+
     def capture_debug(self, enable=True):
         """Parity tests: after every frame `debug['gamma']` is extended by the gating values of the frame (reference order),
         `debug['updates']` holds [(rows, delta_x, P_after)] of the frame's updates and `debug['delta_x']` the last delta_x."""

@@ -512,6 +512,7 @@ class FrontendEngine(object):
         self._cfg.flags |= N.AV_FE_INPUTS_PERSIST if inputs_persist else 0
         self._keep = None
         self._h = C.c_void_p()
+        self.generation = np.zeros(self.n_streams, dtype=np.int64)      # restarts of every stream so far (`restart`)
         masks = [check_mask(cam, getattr(config, 'cam%d_mask' % cam, None), self._cfg.height, self._cfg.width) for cam in (0, 1)]      # before any device call
         photo = [photometric_tables(getattr(config, 'cam%d_response' % cam, None), getattr(config, 'cam%d_vignette' % cam, None)) for cam in (0, 1)]
         photo = [check_photometric(cam, r, g, self._cfg.height, self._cfg.width) for cam, (r, g) in enumerate(photo)]
@@ -577,6 +578,17 @@ class FrontendEngine(object):
         assert len(si) == len(ts) == len(g)
         N.check(N.lib().av_frontend_push_imu_batch(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                    g.ctypes.data_as(C.c_void_p), len(si)))
+
+    def restart(self, streams):
+        """Put the listed streams back to "as created" while the others keep stepping (av_frontend_restart; include/airvision.h,
+        "Stream restart"): their next frame is an initialisation, their feature ids begin again at 0, their IMU buffers are emptied.
+        Enqueued on the current stream, behind the steps already there; legal between `prestage` and `step`, with a read-back
+        pending, and with the frame store.  `generation[s]` counts the restarts of stream s -- ids repeat across lives."""
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(streams, dtype=np.int64)).reshape(-1), dtype=np.int32)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_frontend_restart(self._h, idx.ctypes.data_as(C.c_void_p), len(idx), self._stream()))
+        if len(idx):
+            self.generation[np.unique(idx)] += 1
 
     def _next_exposure(self, who, n, exposure, exposure_q, needed=True):
         """Hands the factors of the next call's n frames to the engine (av_frontend_next_exposure).  ValueError: a keyword on an engine

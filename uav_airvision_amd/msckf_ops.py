@@ -375,6 +375,7 @@ class BatchedMSCKF(object):
         o = config.optimization_config
         self._h = C.c_void_p()
         self._inflight = []
+        self.generation = np.zeros(self.S, dtype=np.int64)      # restarts of every stream so far (`restart`)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_create(
                 self.S, int(config.max_cam_state_size), int(rows_cap), _d(table), _d(config.gravity),
@@ -568,6 +569,18 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_wait(self._h, int(max_pending)))
         while len(self._inflight) > max_pending:
             self._inflight.pop(0)
+
+    def restart(self, streams):
+        """Put the listed streams back to "as created" while the others keep stepping (av_msckf_batch_restart; include/airvision.h,
+        "Stream restart"): from the next step on each of them is bit for bit a stream of a new batch.  Drains the queue first (queued
+        steps retire as steps of the old life).  IMU samples pushed before the call are dropped: push the new life's samples after it.
+        `generation[s]` counts the restarts of stream s -- camera-state ids and the map's order repeat across lives."""
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(streams, dtype=np.int64)).reshape(-1), dtype=np.int32)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_batch_restart(self._h, idx.ctypes.data_as(C.c_void_p), len(idx)))
+        if len(idx):
+            self._inflight = []                              # the queue has been drained
+            self.generation[np.unique(idx)] += 1
 
     def sizes(self, s):
         o = (C.c_int32 * 3)()

@@ -105,6 +105,21 @@ class EngineSet(object):
         for p, (lo, hi) in enumerate(self.parts):
             self.pipes[p].put(lambda e=self.engs[p], a=img0[lo:hi], b=img1[lo:hi]: e.prestage(a, b))
 
+    def restart(self, streams):
+        """FrontendEngine.restart for global stream indices: every part restarts its own, on its worker, in order with its steps."""
+        idx = np.atleast_1d(np.asarray(streams, dtype=np.int64)).reshape(-1)
+        for s in idx:
+            self._locate(int(s))                             # IndexError before anything is enqueued
+        for p, rows in enumerate(self._split_rows(idx)):
+            if len(rows[0]):
+                self.pipes[p].put(lambda e=self.engs[p], r=rows[0]: e.restart(r))
+
+    @property
+    def generation(self):
+        """Restarts of every stream so far, int64[S] (the parts' arrays side by side; drains the workers)."""
+        self.drain()
+        return np.concatenate([e.generation for e in self.engs])
+
     # ---- calls that read back ------------------------------------------------------------------------------------------------------
     def drain(self):
         for w in self.pipes:
@@ -254,6 +269,22 @@ class FilterSet(object):
                         covs.parts[p] = self.flts[p].last_cov
             self.es.pipes[p].put(job)
         return out
+
+    def restart(self, streams):
+        """BatchedMSCKF.restart for global stream indices: every part restarts its own, on its worker, in order with its steps and its
+        IMU pushes (the part's filter drains its own queue)."""
+        idx = np.atleast_1d(np.asarray(streams, dtype=np.int64)).reshape(-1)
+        for s in idx:
+            self.es._locate(int(s))                          # IndexError before anything is enqueued
+        for p, rows in enumerate(self.es._split_rows(idx)):
+            if len(rows[0]):
+                self.es.pipes[p].put(lambda f=self.flts[p], r=rows[0]: f.restart(r))
+
+    @property
+    def generation(self):
+        """Restarts of every stream so far, int64[S] (the parts' arrays side by side; drains the workers)."""
+        self.es.drain()
+        return np.concatenate([f.generation for f in self.flts])
 
     def wait(self, max_pending=0):
         self.es.drain()
