@@ -1,32 +1,13 @@
 """Driver of the stream-restart tests (include/airvision.h, "Stream restart"): a BatchedMSCKF whose slots are fed LIVES -- a synthetic
 feature stream from its first IMU sample and frame, starting at some step of the batch -- with a restart of the slot between two of them.
-Its own copy of the small driver of tests/test_gpu_filter_stats.py, extended by the lives.
+The comparisons, the step arrays and the environment handling are those of tests/filter_harness.py; the lives are its own.
 
 A plan is, per slot, a list of (first step, stream, frames): the slot gets frame j of the stream at step first + j for j < frames and no
 frame (timestamp -1) at every other step.  A life that does not begin at step 0 is preceded by `restart([slot])`; the IMU samples of a life
 are pushed after that restart, each before the first frame that is not older than it (synth.replay's rule)."""
-import os
-
 import numpy as np
 
-CAP = 128
-LM_CAP = 64
-ENV_KEYS = ('AV_DK_WG', 'AV_MSCKF_GROUPS', 'AV_MSCKF_STORE', 'AV_MSCKF_POOL_ROWS')
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def same_bytes(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def same_lm(a, b, sa, sb):
-    """Stream sa of the (records, counts) pair a against stream sb of b: the counts and the written records, byte for byte."""
-    (ra, na), (rb, nb) = a, b
-    return np.array_equal(na[sa], nb[sb]) and ra[sa, :na[sa, 1]].tobytes() == rb[sb, :nb[sb, 1]].tobytes()
+from filter_harness import CAP, ENV_KEYS, LM_CAP, arrays, clean_env, push, same, same_bytes, same_lm      # noqa: F401 (the restart suites take them from here)
 
 
 def same_step(a, ka, sa, b, kb, sb):
@@ -66,21 +47,6 @@ class Life(object):
         return feature_msg_t(m.timestamp, []) if j in self.blank else m
 
 
-def arrays(msgs, cap):
-    """msgs: per slot a feature message or None (no frame)."""
-    S = len(msgs)
-    ids = np.zeros((S, cap), np.int64); uv = np.zeros((S, cap, 4)); nf = np.zeros(S, np.int32)
-    ts = np.full(S, -1.0)
-    for i, m in enumerate(msgs):
-        if m is None:
-            continue
-        ts[i] = m.timestamp
-        nf[i] = len(m.features)
-        ids[i, :nf[i]] = [f.id for f in m.features]
-        uv[i, :nf[i]] = np.array([(f.u0, f.v0, f.u1, f.v1) for f in m.features]).reshape(-1, 4)
-    return ids, uv, nf, ts
-
-
 def run_lives(cfg, plan, n_steps, env=None, cap=CAP, queued=(), before=None, after_restart=None, oracles=None, outputs=True, **kw):
     """Drives a BatchedMSCKF with len(plan) slots over n_steps steps.  queued: the steps that are `submit`ted and left in the queue (every
     other step is a synchronous `step`, which drains it).  before(k, bat, run): called ahead of step k's restarts; after_restart(k, bat,
@@ -88,65 +54,56 @@ def run_lives(cfg, plan, n_steps, env=None, cap=CAP, queued=(), before=None, aft
     alongside, run['refs'][k][slot] = its landmark list after step k.  Returns per-step outputs, covariance, landmark and statistics arrays, the final state of every slot, the
     status of every slot after every step."""
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
-    saved = {k: os.environ.get(k) for k in ENV_KEYS}
-    for k in saved:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    bat = None
-    try:
-        S = len(plan)
-        bat = BatchedMSCKF(cfg, S, odom_cov=outputs, landmarks=outputs, landmark_cap=LM_CAP, stats=outputs, **kw)
-        assert bat.device_resident()
-        run = dict(outs=[], covs=[], lms=[], sts=[], refs=[], status=[], restarts=[])
-        for k in range(n_steps):
-            if before is not None:
-                before(k, bat, run)
-            begin = [i for i in range(S) if any(L.first == k and L.first > 0 for L in plan[i])]
-            if begin:
-                bat.restart(begin)                           # (no wait ahead of it: the call drains)
-                run['restarts'].append((k, begin))
-                if after_restart is not None:
-                    after_restart(k, bat, run)
-            msgs, push = [None] * S, []
-            for i in range(S):
-                for li, L in enumerate(plan[i]):
-                    j = k - L.first
-                    if 0 <= j < L.frames:
-                        imu = L.imu_before(j)
-                        push += [(i, m) for m in imu]
-                        msgs[i] = L.message(j)
-                        ora = (oracles or {}).get(i, {}).get(li)
-                        if ora is not None:
-                            for m in imu:
-                                ora.imu_callback(m)
-                            ora.feature_callback(msgs[i])
-            if push:
-                bat.push_imu([i for i, _ in push], [m.timestamp for _, m in push], [m.angular_velocity for _, m in push],
-                             [m.linear_acceleration for _, m in push])
-            ids, uv, nf, ts = arrays(msgs, cap)
-            args = dict(cov=True, landmarks=True, stats=True) if outputs else {}
-            out = (bat.submit if k in queued else bat.step)(ids, uv, nf, ts, **args)
-            run['outs'].append(out); run['covs'].append(bat.last_cov); run['lms'].append(bat.last_landmarks); run['sts'].append(bat.last_stats)
-            run['refs'].append({i: list(o.landmarks) for i, d in (oracles or {}).items() for o in d.values()})
-            if k not in queued:
-                run['status'].append([bat.stream_status(i) for i in range(S)])
-            else:
-                run['status'].append(None)
-        bat.wait(0)
-        run['state'] = [bat.get_state(i) for i in range(S)]
-        run['cov'] = [bat.get_cov(i) for i in range(S)]
-        run['sizes'] = [bat.sizes(i) for i in range(S)]
-        run['generation'] = bat.generation.copy()
-        run['counters'] = bat.counters()
-        run['shape'] = bat.launch_shape()
-        return run
-    finally:
-        if bat is not None:
-            bat.close()
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+    with clean_env(env):
+        bat = None
+        try:
+            S = len(plan)
+            bat = BatchedMSCKF(cfg, S, odom_cov=outputs, landmarks=outputs, landmark_cap=LM_CAP, stats=outputs, **kw)
+            assert bat.device_resident()
+            run = dict(outs=[], covs=[], lms=[], sts=[], refs=[], status=[], restarts=[])
+            for k in range(n_steps):
+                if before is not None:
+                    before(k, bat, run)
+                begin = [i for i in range(S) if any(L.first == k and L.first > 0 for L in plan[i])]
+                if begin:
+                    bat.restart(begin)                           # (no wait ahead of it: the call drains)
+                    run['restarts'].append((k, begin))
+                    if after_restart is not None:
+                        after_restart(k, bat, run)
+                msgs, pushed = [None] * S, []
+                for i in range(S):
+                    for li, L in enumerate(plan[i]):
+                        j = k - L.first
+                        if 0 <= j < L.frames:
+                            imu = L.imu_before(j)
+                            pushed += [(i, m) for m in imu]
+                            msgs[i] = L.message(j)
+                            ora = (oracles or {}).get(i, {}).get(li)
+                            if ora is not None:
+                                for m in imu:
+                                    ora.imu_callback(m)
+                                ora.feature_callback(msgs[i])
+                push(bat, pushed)
+                ids, uv, nf, ts = arrays(msgs, cap)
+                args = dict(cov=True, landmarks=True, stats=True) if outputs else {}
+                out = (bat.submit if k in queued else bat.step)(ids, uv, nf, ts, **args)
+                run['outs'].append(out); run['covs'].append(bat.last_cov); run['lms'].append(bat.last_landmarks); run['sts'].append(bat.last_stats)
+                run['refs'].append({i: list(o.landmarks) for i, d in (oracles or {}).items() for o in d.values()})
+                if k not in queued:
+                    run['status'].append([bat.stream_status(i) for i in range(S)])
+                else:
+                    run['status'].append(None)
+            bat.wait(0)
+            run['state'] = [bat.get_state(i) for i in range(S)]
+            run['cov'] = [bat.get_cov(i) for i in range(S)]
+            run['sizes'] = [bat.sizes(i) for i in range(S)]
+            run['generation'] = bat.generation.copy()
+            run['counters'] = bat.counters()
+            run['shape'] = bat.launch_shape()
+            return run
+        finally:
+            if bat is not None:
+                bat.close()
 
 
 def same_state(a, b):

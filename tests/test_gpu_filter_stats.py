@@ -26,79 +26,15 @@ import os
 import numpy as np
 import pytest
 
+import filter_harness as H
 import filter_stats_ref as R
+from filter_harness import messages as _messages, push as _push, same as _same, same_bytes as _same_st, same_lm as _same_lm, schedule as _schedule, zero as _zero
 
 pytestmark = pytest.mark.gpu
 
 N_FRAMES = R.N_FRAMES
 CAP = 128
 LM_CAP = 64
-
-
-def _same(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def _same_st(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _same_lm(a, b):
-    (ra, na), (rb, nb) = a, b
-    if not (na.shape == nb.shape and np.array_equal(na, nb)):
-        return False
-    return all(ra[s, :na[s, 1]].tobytes() == rb[s, :nb[s, 1]].tobytes() for s in range(len(na)))
-
-
-def _zero(rec):
-    return not rec.tobytes().strip(b'\0')
-
-
-def _schedule(streams, n_frames):
-    """Per frame the IMU samples [(stream, msg)] that arrive before it (synth.replay's rule)."""
-    its = [iter(s.imu) for s in streams]
-    pend = [next(it, None) for it in its]
-    rows = []
-    for k in range(n_frames):
-        row = []
-        for i, st in enumerate(streams):
-            t = st.frame(k).timestamp
-            while pend[i] is not None and pend[i].timestamp <= t:
-                row.append((i, pend[i]))
-                pend[i] = next(its[i], None)
-        rows.append(row)
-    return rows
-
-
-def _arrays(msgs, cap, idle=()):
-    S = len(msgs)
-    ids = np.zeros((S, cap), np.int64); uv = np.zeros((S, cap, 4)); nf = np.zeros(S, np.int32)
-    ts = np.array([m.timestamp for m in msgs])
-    for i, m in enumerate(msgs):
-        if i in idle:
-            ts[i] = -1.0
-            continue
-        nf[i] = len(m.features)
-        ids[i, :nf[i]] = [f.id for f in m.features]
-        uv[i, :nf[i]] = np.array([(f.u0, f.v0, f.u1, f.v1) for f in m.features]).reshape(-1, 4)
-    return ids, uv, nf, ts
-
-
-def _push(bat, row):
-    if row:
-        bat.push_imu([i for i, _ in row], [m.timestamp for _, m in row], [m.angular_velocity for _, m in row], [m.linear_acceleration for _, m in row])
-
-
-def _messages(streams, n_frames, blank=None):
-    from uav_airvision_amd.synth import feature_msg_t
-    out = []
-    for k in range(n_frames):
-        msgs = [st.frame(k) for st in streams]
-        if blank:
-            msgs = [feature_msg_t(m.timestamp, []) if k in blank.get(i, ()) else m for i, m in enumerate(msgs)]
-        out.append(msgs)
-    return out
 
 
 def _reference(cfg, streams, n_frames, blank=None):
@@ -116,53 +52,9 @@ def _reference(cfg, streams, n_frames, blank=None):
     return dict(recs=recs, dx_inf=dx_inf, gammas=gammas)
 
 
-def _run(cfg, streams, n_frames, stats=True, landmarks=False, odom_cov=False, mode='step', cap=CAP, blank=None, idle=None, check=None, env=None,
-         debug=False, **kw):
-    """Drives a BatchedMSCKF over the streams.  mode: 'step' (synchronous; check(k, bat, out) runs after every step), 'queue3' (three
-    submits -- the ring's depth -- then wait(0)), 'ahead' (submit + wait(1)).  blank = {stream: frames} replaces messages by empty ones,
-    idle = {stream: frames} gives the stream no frame (timestamp -1).  debug: debug_capture on, dbg[k][s][ph] = the gammas debug_read
-    returns after the step.  Returns per-frame outputs, statistics arrays, (records, counts) pairs and covariance arrays."""
-    from uav_airvision_amd.msckf_ops import BatchedMSCKF
-    saved = {k: os.environ.get(k) for k in ('AV_DK_WG', 'AV_MSCKF_GROUPS', 'AV_MSCKF_STORE', 'AV_MSCKF_POOL_ROWS')}
-    for k in saved:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    bat = None
-    try:
-        S = len(streams)
-        rows, msgs = _schedule(streams, n_frames), _messages(streams, n_frames, blank)
-        bat = BatchedMSCKF(cfg, S, odom_cov=odom_cov, landmarks=landmarks, landmark_cap=LM_CAP, stats=stats, **kw)
-        assert bat.device_resident()
-        if debug:
-            bat.debug_capture(True)
-        outs, sts, lms, covs, dbg = [], [], [], [], []
-        for k in range(n_frames):
-            _push(bat, rows[k])
-            ids, uv, nf, ts = _arrays(msgs[k], cap, idle=[i for i in range(S) if idle and k in idle.get(i, ())])
-            args = dict(cov=True if odom_cov else None, landmarks=True if landmarks else None, stats=True if stats else None)
-            if mode == 'step':
-                out = bat.step(ids, uv, nf, ts, **args)
-            else:
-                out = bat.submit(ids, uv, nf, ts, **args)
-                if mode == 'ahead':
-                    bat.wait(1)
-                elif k % 3 == 2:
-                    bat.wait(0)
-            outs.append(out); sts.append(bat.last_stats if stats else None)
-            lms.append(bat.last_landmarks if landmarks else None); covs.append(bat.last_cov if odom_cov else None)
-            if debug:
-                dbg.append([[bat.debug_read(s, ph)[0] for ph in range(2)] for s in range(S)])
-            if check is not None:
-                check(k, bat, out)
-        bat.wait(0)
-        return dict(outs=outs, sts=sts, lms=lms, covs=covs, dbg=dbg, counters=bat.counters(), shape=bat.launch_shape())
-    finally:
-        if bat is not None:
-            bat.close()
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+def _run(cfg, streams, n_frames, stats=True, check=None, **kw):
+    """filter_harness.run with the statistics on; check(k, bat, out) runs after every step."""
+    return H.run(cfg, streams, n_frames, stats=stats, check=check and (lambda k, bat, out, cur: check(k, bat, out)), **kw)
 
 
 def _against_ref(got, ref, dx_inf, where, worst):
@@ -331,6 +223,43 @@ def test_beside_the_map_and_the_covariance_and_off(cfg):
             assert _same_st(one['sts'][k], only['sts'][k]) and _same(one['outs'][k], only['outs'][k]), (pair, k)
 
 
+def _allon3(cfg):
+    """The three streams stepped synchronously with all three outputs on, once."""
+    if 'allon' not in _CACHE:
+        _CACHE['allon'] = _run(cfg, R.streams3(cfg), N_FRAMES, landmarks=True, odom_cov=True)
+    return _CACHE['allon']
+
+
+def test_every_subset_of_the_outputs_publishes_the_all_on_bits(cfg):
+    """Every subset of {covariance, landmarks, statistics}, stepped synchronously -- every dk_mid and dk_finish instance the step can
+    launch: each output that is on is bit for bit the all-on run's, the poses of all eight runs are the same bits, and an output that
+    is off has no array."""
+    allon = _allon3(cfg)
+    for cov in (False, True):
+        for lm in (False, True):
+            for st in (False, True):
+                if cov and lm and st:
+                    continue
+                run = _sync3(cfg, 256) if (cov, lm, st) == (False, False, True) else _run(cfg, R.streams3(cfg), N_FRAMES, stats=st, landmarks=lm, odom_cov=cov)
+                for k in range(N_FRAMES):
+                    assert _same(run['outs'][k], allon['outs'][k]), (cov, lm, st, k)
+                    assert _same(run['covs'][k], allon['covs'][k]) if cov else run['covs'][k] is None, (cov, lm, st, k)
+                    assert _same_lm(run['lms'][k], allon['lms'][k]) if lm else run['lms'][k] is None, (cov, lm, st, k)
+                    assert _same_st(run['sts'][k], allon['sts'][k]) if st else run['sts'][k] is None, (cov, lm, st, k)
+
+
+def test_two_stream_groups_offset_every_output_of_a_queued_step(cfg):
+    """All three outputs on, streams {0, 1} and {2} as two groups (AV_MSCKF_GROUPS=2), three submits then wait(0): stream 2 lies in the
+    second group, so each of the four arrays is written at its own offset; bit for bit the synchronous single-group run."""
+    allon = _allon3(cfg)
+    run = _run(cfg, R.streams3(cfg), N_FRAMES, landmarks=True, odom_cov=True, mode='queue3', env={'AV_MSCKF_GROUPS': '2'})
+    assert run['shape'] == [(2, 256), (1, 256)], run['shape']
+    for k in range(N_FRAMES):
+        assert _same(run['outs'][k], allon['outs'][k]) and _same(run['covs'][k], allon['covs'][k]), k
+        assert _same_lm(run['lms'][k], allon['lms'][k]) and _same_st(run['sts'][k], allon['sts'][k]), k
+    assert sum(int(p[1][2, 1]) for p in run['lms']) > 0 and sum(int(s['n_eval'][2].sum()) for s in run['sts']) > 0
+
+
 def test_idle_blank_and_stopped_streams(cfg):
     """Stream 0 is stopped by a capacity limit (the overflow pool shrunk to 64 rows, a blank frame at 17): 128 zero bytes from that step
     on.  Stream 2 has no frame (timestamp < 0) in three steps: zero there.  Stream 1 has a blank frame at 12, which loses every track:
@@ -426,37 +355,12 @@ def test_device_handover_and_filter_set_match_a_step_run_of_the_same_messages(cf
     """2 streams, 12 rendered frames through FrontendEngine + submit_dev(stats=True); the same messages through step(); the same two
     streams as two pipelines (EngineSet + FilterSet(stats=True)), whose last_stats joins the parts' arrays."""
     import torch
-    from fe_harness import Frames
     from uav_airvision_amd import _native as N
-    from uav_airvision_amd.frontend import FrontendEngine
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.pipelines import EngineSet, FilterSet
-    from uav_airvision_amd.synth import SyntheticStream
     F, S = 12, 2
-    streams = [Frames.cached(SyntheticStream(cfg, seed=900 + u, n_frames=F)) for u in range(S)]
-    rows = _schedule(streams, F)
-    cams = []
-    for k in range(F):
-        fr = [st.frame(k) for st in streams]
-        cams.append((np.stack([m.cam0_image for m in fr]), np.stack([m.cam1_image for m in fr]), np.array([m.timestamp for m in fr])))
-    eng = FrontendEngine(cfg, n_streams=S)
-    flt = BatchedMSCKF(cfg, S, max_features=eng.max_features, stats=True)
-    msgs, outs, sts = [], [], []
-    try:
-        for k in range(F):
-            c0, c1, ts = cams[k]
-            for i, m in rows[k]:
-                eng.push_imu(i, m.timestamp, m.angular_velocity)
-            eng.step(torch.from_numpy(c0).cuda(), torch.from_numpy(c1).cuda(), ts)
-            _push(flt, rows[k])
-            outs.append(flt.submit_dev(eng, ts, msg_stream=N.current_stream(), stats=True))
-            sts.append(flt.last_stats)
-            ids, uv, n = eng.read_features_raw()
-            msgs.append((ids.copy(), uv.copy(), n.copy(), ts))
-        flt.wait(0)
-    finally:
-        flt.close()
-        eng.close()
+    h = H.handover_run(cfg, F, S, stats=True)
+    rows, cams, msgs, outs, sts = h['rows'], h['cams'], h['msgs'], h['outs'], h['sts']
     assert sum(bool(o[0, 0] == 1.0) for o in outs) >= 5 and sum(int(p['n_eval'].sum()) for p in sts) > 0
     ref = BatchedMSCKF(cfg, S, max_features=msgs[0][0].shape[1], stats=True)
     try:

@@ -18,7 +18,9 @@ import os
 import numpy as np
 import pytest
 
+import filter_harness as H
 import landmark_ref as L
+from filter_harness import push as _push, same as _same, same_lm as _same_lm
 
 pytestmark = pytest.mark.gpu
 
@@ -27,112 +29,13 @@ CAP = 128
 LM_CAP = 64
 
 
-def _same(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def _same_lm(a, b):
-    """Two (records, counts) pairs publish the same bytes: the counts, and the records up to the count."""
-    (ra, na), (rb, nb) = a, b
-    if not (na.shape == nb.shape and np.array_equal(na, nb)):
-        return False
-    return all(ra[s, :na[s, 1]].tobytes() == rb[s, :nb[s, 1]].tobytes() for s in range(len(na)))
-
-
-def _schedule(streams, n_frames):
-    """Per frame the IMU samples [(stream, msg)] that arrive before it (synth.replay's rule)."""
-    its = [iter(s.imu) for s in streams]
-    pend = [next(it, None) for it in its]
-    rows = []
-    for k in range(n_frames):
-        row = []
-        for i, st in enumerate(streams):
-            t = st.frame(k).timestamp
-            while pend[i] is not None and pend[i].timestamp <= t:
-                row.append((i, pend[i]))
-                pend[i] = next(its[i], None)
-        rows.append(row)
-    return rows
-
-
-def _arrays(msgs, cap, idle=()):
-    S = len(msgs)
-    ids = np.zeros((S, cap), np.int64); uv = np.zeros((S, cap, 4)); nf = np.zeros(S, np.int32)
-    ts = np.array([m.timestamp for m in msgs])
-    for i, m in enumerate(msgs):
-        if i in idle:
-            ts[i] = -1.0
-            continue
-        nf[i] = len(m.features)
-        ids[i, :nf[i]] = [f.id for f in m.features]
-        uv[i, :nf[i]] = np.array([(f.u0, f.v0, f.u1, f.v1) for f in m.features]).reshape(-1, 4)
-    return ids, uv, nf, ts
-
-
-def _push(bat, row):
-    if row:
-        bat.push_imu([i for i, _ in row], [m.timestamp for _, m in row], [m.angular_velocity for _, m in row], [m.linear_acceleration for _, m in row])
-
-
-def _run(cfg, streams, n_frames, landmarks=True, lm_cap=LM_CAP, odom_cov=False, mode='step', cap=CAP, oracle=False, blank=None, idle=None,
-         check=None, env=None, **kw):
-    """Drives a BatchedMSCKF over the streams.  mode: 'step' (synchronous; check(k, bat, out) runs after every step), 'queue3' (three
-    submits -- the ring's depth -- then wait(0)), 'ahead' (submit + wait(1)).  blank = {stream: frames} replaces messages by empty ones,
-    idle = {stream: frames} gives the stream no frame (timestamp -1).  oracle: a LandmarkOracle per stream runs alongside; refs[k][i] is
-    its record list, resets[k][i] whether its step ended in online_reset.  Returns per-frame outputs, (records, counts) pairs and
-    covariance arrays."""
-    from uav_airvision_amd.msckf_ops import BatchedMSCKF
-    from uav_airvision_amd.synth import feature_msg_t
-    saved = {k: os.environ.get(k) for k in ('AV_DK_WG', 'AV_MSCKF_GROUPS', 'AV_MSCKF_STORE', 'AV_MSCKF_POOL_ROWS')}
-    for k in saved:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    bat = None
-    try:
-        S = len(streams)
-        rows = _schedule(streams, n_frames)
-        bat = BatchedMSCKF(cfg, S, odom_cov=odom_cov, landmarks=landmarks, landmark_cap=lm_cap, **kw)
-        assert bat.device_resident()
-        oras = [L.LandmarkOracle(cfg) for _ in streams] if oracle else None
-        outs, lms, covs, refs, resets = [], [], [], [], []
-        for k in range(n_frames):
-            msgs = [st.frame(k) for st in streams]
-            if blank:
-                msgs = [feature_msg_t(m.timestamp, []) if k in blank.get(i, ()) else m for i, m in enumerate(msgs)]
-            _push(bat, rows[k])
-            ids, uv, nf, ts = _arrays(msgs, cap, idle=[i for i in range(S) if idle and k in idle.get(i, ())])
-            args = dict(cov=True if odom_cov else None, landmarks=True if landmarks else None)
-            if mode == 'step':
-                out = bat.step(ids, uv, nf, ts, **args)
-            else:
-                out = bat.submit(ids, uv, nf, ts, **args)
-                if mode == 'ahead':
-                    bat.wait(1)
-                elif k % 3 == 2:
-                    bat.wait(0)
-            outs.append(out); lms.append(bat.last_landmarks if landmarks else None); covs.append(bat.last_cov if odom_cov else None)
-            if oras is not None:
-                for i, m in rows[k]:
-                    oras[i].imu_callback(m)
-                ref, rs = [], []
-                for i, m in enumerate(msgs):
-                    ncam = len(oras[i].cam_states)
-                    r = oras[i].feature_callback(m)
-                    ref.append(list(oras[i].landmarks))
-                    rs.append(r is not None and ncam > 0 and len(oras[i].cam_states) == 0)
-                refs.append(ref); resets.append(rs)
-            if check is not None:
-                check(k, bat, out)
-        bat.wait(0)
-        return dict(outs=outs, lms=lms, covs=covs, refs=refs, resets=resets, counters=bat.counters(), shape=bat.launch_shape())
-    finally:
-        if bat is not None:
-            bat.close()
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+def _run(cfg, streams, n_frames, landmarks=True, oracle=False, check=None, **kw):
+    """filter_harness.run with the map on.  oracle: a LandmarkOracle per stream runs alongside; refs[k][i] is its record list, resets[k][i]
+    whether its step ended in online_reset.  check(k, bat, out) runs after every step."""
+    run = H.run(cfg, streams, n_frames, landmarks=landmarks, oracle=L.LandmarkOracle if oracle else None,
+                oracle_step=lambda ora, r, reset: (list(ora.landmarks), reset), check=check and (lambda k, bat, out, cur: check(k, bat, out)), **kw)
+    run['refs'], run['resets'] = [[x[0] for x in ref] for ref in run['refs']], [[x[1] for x in ref] for ref in run['refs']]
+    return run
 
 
 def _against_ref(rec, n, s, ref, lm_cap, where):
@@ -397,41 +300,10 @@ _HANDOVER = {}
 
 def _handover_run(cfg):
     """2 streams, 12 rendered frames through FrontendEngine + submit_dev(landmarks=True), once."""
-    import torch
-    from fe_harness import Frames
-    from uav_airvision_amd import _native as N
-    from uav_airvision_amd.frontend import FrontendEngine
-    from uav_airvision_amd.msckf_ops import BatchedMSCKF
-    from uav_airvision_amd.synth import SyntheticStream
-    if _HANDOVER:
-        return _HANDOVER
-    F, S = 12, 2
-    streams = [Frames.cached(SyntheticStream(cfg, seed=900 + u, n_frames=F)) for u in range(S)]
-    rows = _schedule(streams, F)
-    cams = []
-    for k in range(F):
-        fr = [st.frame(k) for st in streams]
-        cams.append((np.stack([m.cam0_image for m in fr]), np.stack([m.cam1_image for m in fr]), np.array([m.timestamp for m in fr])))
-    eng = FrontendEngine(cfg, n_streams=S)
-    flt = BatchedMSCKF(cfg, S, max_features=eng.max_features, landmarks=True)
-    msgs, outs, lms = [], [], []
-    try:
-        for k in range(F):
-            c0, c1, ts = cams[k]
-            for i, m in rows[k]:
-                eng.push_imu(i, m.timestamp, m.angular_velocity)
-            eng.step(torch.from_numpy(c0).cuda(), torch.from_numpy(c1).cuda(), ts)
-            _push(flt, rows[k])
-            outs.append(flt.submit_dev(eng, ts, msg_stream=N.current_stream(), landmarks=True))
-            lms.append(flt.last_landmarks)
-            ids, uv, n = eng.read_features_raw()
-            msgs.append((ids.copy(), uv.copy(), n.copy(), ts))
-        flt.wait(0)
-    finally:
-        flt.close()
-        eng.close()
-    assert sum(bool(o[0, 0] == 1.0) for o in outs) >= 5 and sum(int(p[1][:, 1].sum()) for p in lms) > 0
-    _HANDOVER.update(rows=rows, cams=cams, msgs=msgs, outs=outs, lms=lms)
+    if not _HANDOVER:
+        h = H.handover_run(cfg, landmarks=True)
+        assert sum(bool(o[0, 0] == 1.0) for o in h['outs']) >= 5 and sum(int(p[1][:, 1].sum()) for p in h['lms']) > 0
+        _HANDOVER.update(h)
     return _HANDOVER
 
 

@@ -14,21 +14,15 @@ import os
 import numpy as np
 import pytest
 
+import filter_harness as H
 import odom_cov_ref as R
+from filter_harness import bits as _bits, same as _same
 
 pytestmark = pytest.mark.gpu
 
 EPS = np.finfo(np.float64).eps
 N_FRAMES = 30                      # past the first camera-state prune (20 states)
 CAP = 128
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 def _snap_oracle(cfg):
@@ -42,106 +36,19 @@ def _snap_oracle(cfg):
             s = self.imu_state
             self.snap = dict(P=self.state_cov.copy(), q=np.array(s.orientation), R_ic=np.array(s.R_imu_cam0), t_ci=np.array(s.t_cam0_imu))
             return OracleMSCKF.publish(self, time)
+
+        def feature_callback(self, msg):
+            self.snap = None
+            return OracleMSCKF.feature_callback(self, msg)
     return SnapOracle(cfg)
 
 
-def _schedule(streams, n_frames, withhold=None):
-    """Per frame the IMU samples [(stream, msg)] that arrive before it (synth.replay's rule); withhold = {stream: k0} keeps a stream's
-    samples back until frame k0."""
-    withhold = withhold or {}
-    its = [iter(s.imu) for s in streams]
-    pend = [next(it, None) for it in its]
-    held = [[] for _ in streams]
-    rows = []
-    for k in range(n_frames):
-        row = []
-        for i, st in enumerate(streams):
-            t = st.frame(k).timestamp
-            while pend[i] is not None and pend[i].timestamp <= t:
-                held[i].append(pend[i])
-                pend[i] = next(its[i], None)
-            if k >= withhold.get(i, 0):
-                row += [(i, m) for m in held[i]]
-                held[i] = []
-        rows.append(row)
-    return rows
-
-
-def _arrays(msgs, cap):
-    S = len(msgs)
-    ids = np.zeros((S, cap), np.int64); uv = np.zeros((S, cap, 4)); nf = np.zeros(S, np.int32)
-    for i, m in enumerate(msgs):
-        nf[i] = len(m.features)
-        ids[i, :nf[i]] = [f.id for f in m.features]
-        uv[i, :nf[i]] = np.array([(f.u0, f.v0, f.u1, f.v1) for f in m.features]).reshape(-1, 4)
-    return ids, uv, nf, np.array([m.timestamp for m in msgs])
-
-
-def _state_bits(bat, s):
-    gs = bat.get_state(s)
-    return [np.atleast_1d(np.asarray(gs[key], dtype=np.float64)) for key in sorted(gs) if key != 'cam_ids'] + [bat.get_cov(s)]
-
-
-def _run(cfg, streams, n_frames, odom_cov=True, mode='step', cap=CAP, withhold=None, oracle=False, blank=None, check=None, env=None, **kw):
-    """Drives a BatchedMSCKF over the streams.  mode: 'step' (synchronous; check(k, bat, out, cov, oras, results) runs after every
-    step), 'queue3' (three submits -- the ring's depth -- then wait(0)), 'ahead' (submit + wait(1)).  Returns per-frame outputs and record
-    arrays, the final state bits of every stream and the counters."""
-    from uav_airvision_amd.msckf_ops import BatchedMSCKF
-    from uav_airvision_amd.synth import feature_msg_t
-    saved = {k: os.environ.get(k) for k in ('AV_DK_WG', 'AV_MSCKF_GROUPS', 'AV_MSCKF_STORE', 'AV_MSCKF_POOL_ROWS')}
-    for k in saved:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    bat = None
-    try:
-        S = len(streams)
-        rows = _schedule(streams, n_frames, withhold)
-        bat = BatchedMSCKF(cfg, S, odom_cov=odom_cov, **kw)
-        assert bat.device_resident()
-        oras = [_snap_oracle(cfg) for _ in streams] if oracle else None
-        outs, covs = [], []
-        for k in range(n_frames):
-            msgs = [st.frame(k) for st in streams]
-            if blank:
-                msgs = [feature_msg_t(m.timestamp, []) if k in blank.get(i, ()) else m for i, m in enumerate(msgs)]
-            if rows[k]:
-                bat.push_imu([i for i, _ in rows[k]], [m.timestamp for _, m in rows[k]], [m.angular_velocity for _, m in rows[k]],
-                             [m.linear_acceleration for _, m in rows[k]])
-            ids, uv, nf, ts = _arrays(msgs, cap)
-            want = True if odom_cov else None
-            if mode == 'step':
-                out = bat.step(ids, uv, nf, ts, cov=want)
-            else:
-                out = bat.submit(ids, uv, nf, ts, cov=want)
-                if mode == 'ahead':
-                    bat.wait(1)
-                elif k % 3 == 2:
-                    bat.wait(0)
-            cov = bat.last_cov if odom_cov else None
-            outs.append(out); covs.append(cov)
-            if oras is not None:
-                results = []
-                for i, m in rows[k]:
-                    oras[i].imu_callback(m)
-                for i, m in enumerate(msgs):
-                    oras[i].snap = None
-                    ncam_before = len(oras[i].cam_states)
-                    r = oras[i].feature_callback(m)
-                    results.append(dict(pub=r is not None, reset=r is not None and ncam_before > 0 and len(oras[i].cam_states) == 0, snap=oras[i].snap))
-            else:
-                results = None
-            if check is not None:
-                check(k, bat, out, cov, results)
-        bat.wait(0)
-        final = [_state_bits(bat, s) for s in range(S)]
-        return dict(outs=outs, covs=covs, final=final, counters=bat.counters(), shape=bat.launch_shape())
-    finally:
-        if bat is not None:
-            bat.close()
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+def _run(cfg, streams, n_frames, odom_cov=True, oracle=False, check=None, **kw):
+    """filter_harness.run with the covariance on.  oracle: a SnapOracle per stream alongside; check(k, bat, out, cov, results) runs after
+    every step, results[i] = dict(pub, reset, snap) of stream i's oracle (None without)."""
+    return H.run(cfg, streams, n_frames, odom_cov=odom_cov, oracle=_snap_oracle if oracle else None,
+                 oracle_step=lambda ora, r, reset: dict(pub=r is not None, reset=reset, snap=ora.snap),
+                 check=check and (lambda k, bat, out, cur: check(k, bat, out, cur['cov'], cur['ref'])), **kw)
 
 
 def _streams3(cfg):
@@ -314,43 +221,10 @@ _HANDOVER = {}
 def _handover_run(cfg):
     """2 streams, 12 rendered frames through FrontendEngine + submit_dev(cov=True), once: (IMU schedule, the messages read back from the
     engine, the step outputs, the records)."""
-    import torch
-    from fe_harness import Frames
-    from uav_airvision_amd import _native as N
-    from uav_airvision_amd.frontend import FrontendEngine
-    from uav_airvision_amd.msckf_ops import BatchedMSCKF
-    from uav_airvision_amd.synth import SyntheticStream
-    if _HANDOVER:
-        return _HANDOVER
-    F, S = 12, 2
-    streams = [Frames.cached(SyntheticStream(cfg, seed=900 + u, n_frames=F)) for u in range(S)]
-    rows = _schedule(streams, F)
-    cams = []
-    for k in range(F):
-        fr = [st.frame(k) for st in streams]
-        cams.append((np.stack([m.cam0_image for m in fr]), np.stack([m.cam1_image for m in fr]), np.array([m.timestamp for m in fr])))
-    eng = FrontendEngine(cfg, n_streams=S)
-    flt = BatchedMSCKF(cfg, S, max_features=eng.max_features, odom_cov=True)
-    msgs, outs, covs = [], [], []
-    try:
-        for k in range(F):
-            c0, c1, ts = cams[k]
-            for i, m in rows[k]:
-                eng.push_imu(i, m.timestamp, m.angular_velocity)
-            eng.step(torch.from_numpy(c0).cuda(), torch.from_numpy(c1).cuda(), ts)
-            if rows[k]:
-                flt.push_imu([i for i, _ in rows[k]], [m.timestamp for _, m in rows[k]], [m.angular_velocity for _, m in rows[k]],
-                             [m.linear_acceleration for _, m in rows[k]])
-            outs.append(flt.submit_dev(eng, ts, msg_stream=N.current_stream(), cov=True))
-            covs.append(flt.last_cov)
-            ids, uv, n = eng.read_features_raw()
-            msgs.append((ids.copy(), uv.copy(), n.copy(), ts))
-        flt.wait(0)
-    finally:
-        flt.close()
-        eng.close()
-    assert sum(bool(o[0, 0] == 1.0) for o in outs) >= 5
-    _HANDOVER.update(rows=rows, cams=cams, msgs=msgs, outs=outs, covs=covs)
+    if not _HANDOVER:
+        h = H.handover_run(cfg, odom_cov=True)
+        assert sum(bool(o[0, 0] == 1.0) for o in h['outs']) >= 5
+        _HANDOVER.update(h)
     return _HANDOVER
 
 

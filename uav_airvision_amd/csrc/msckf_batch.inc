@@ -316,21 +316,18 @@ struct av_msckf_batch {
     DevPath* dev = nullptr;                     // device-resident state + observation store (msckf_dev.inc); NULL: the host-bookkeeping path (AV_MSCKF_STORE=host)
     long long dev_seq = 0;                      // steps submitted (ring slot = dev_seq % DEV_RING)
     hipEvent_t ev_msg[4] = {nullptr, nullptr, nullptr, nullptr};      // submit_dev: the message copy of ring slot k has been enqueued
-    struct Pending { int slot; double* out; double* cov; av_landmark* lm; int32_t* lmn; av_filter_stats* stats; };
-    std::deque<Pending> direct_pending;         // one group, no worker: steps launched and not yet finished (slot, caller's out, caller's odometry-covariance array or NULL, caller's landmark arrays or NULL, caller's innovation-statistics array or NULL)
-    // odometry covariance (av_msckf_batch_set_odom_cov): on the batch and on every group; next_cov = the destination
-    // av_msckf_batch_next_odom_cov handed over for the next step (batch only), taken by that step
-    bool odom_cov = false; double* next_cov = nullptr;
-    // landmark map (av_msckf_batch_set_landmarks): records per stream and step (0: off), on the batch and on every group; next_lm /
-    // next_lmn = the destination av_msckf_batch_next_landmarks handed over for the next step (batch only), taken by that step
-    int lm_cap = 0; av_landmark* next_lm = nullptr; int32_t* next_lmn = nullptr;
-    // innovation statistics (av_msckf_batch_set_stats): on the batch and on every group; next_stats = the destination
-    // av_msckf_batch_next_stats handed over for the next step (batch only), taken by that step
-    bool stats_on = false; av_filter_stats* next_stats = nullptr;
+    struct Pending { int slot; double* out; StepOuts outs; };
+    std::deque<Pending> direct_pending;         // one group, no worker: steps launched and not yet finished (slot, caller's out, caller's arrays for the optional outputs)
+    // the optional outputs (OUTS, msckf_dev.inc).  out_set: every feature's setting (av_msckf_batch_set_*), on the batch and on every
+    // group; next_outs: the destinations av_msckf_batch_next_* handed over for the next step (batch only), taken by that step
+    int out_set[N_FEAT] = {}; StepOuts next_outs;
     explicit av_msckf_batch(int n) : st(n) {}
 };
 
 namespace {
+
+// the optional outputs' destinations handed over for the next step: taken, and cleared, by the step that is being submitted
+inline StepOuts take_outs(av_msckf_batch* b) { const StepOuts o = b->next_outs; b->next_outs = StepOuts(); return o; }
 
 // ---- the kernels' argument records, the part every caller of a batch shares (the device-resident filter, the host-bookkeeping chain
 //      and its synchronous fallback); each caller adds what is its own.  TriArgs: tri_args_base (msckf.hip).
@@ -1109,7 +1106,7 @@ int b_chain_finish(av_msckf_batch* b, std::vector<FeatRef>& refs, ChainCtx& ctx)
 }  // namespace
 
 static void sub_destroy(av_msckf_batch* b);
-namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn, av_filter_stats* stats); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm); }
+namespace { int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps, bool dev_msg, hipEvent_t ready, hipStream_t stm); int dev_finish(av_msckf_batch* b, int k, double* out, const StepOuts& outs); int dev_read_state(av_msckf_batch* b, int s, DState* D); const char* dev_fail_message(int code, int* av_code); int dev_reserve(av_msckf_batch* b, int cap); int dev_upload_updbase(av_msckf_batch* b); int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm); }
 
 // Stream for the filter's kernels.  AV_MSCKF_CUS="first:count" confines them to `count` compute units starting at CU `first`
 // (hipExtStreamCreateWithCUMask) -- together with a complementary mask on the caller's front-end stream this partitions the
@@ -1320,11 +1317,9 @@ static int sub_step(av_msckf_batch* b, const int64_t* ids, const double* uv, con
     int rc;
     if (b->dev) {
         const int k = (int)(b->dev_seq++ % DEV_RING);
-        double* cov = b->next_cov; b->next_cov = nullptr;
-        av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
-        av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
+        const StepOuts outs = take_outs(b);
         if ((rc = dev_launch(b, k, ids, uv, n_feat, cap, timestamps, false, nullptr, stm))) return rc;
-        return dev_finish(b, k, out, cov, lm, lmn, fst);
+        return dev_finish(b, k, out, outs);
     }
     if ((rc = sub_reserve(b, cap))) return rc;
     ++b->n_steps;
@@ -1853,7 +1848,7 @@ int direct_drain(av_msckf_batch* b, size_t max_pending)
     while (b->direct_pending.size() > max_pending) {
         const av_msckf_batch::Pending pr = b->direct_pending.front();
         b->direct_pending.pop_front();
-        const int r = dev_finish(b, pr.slot, pr.out, pr.cov, pr.lm, pr.lmn, pr.stats);
+        const int r = dev_finish(b, pr.slot, pr.out, pr.outs);
         if (r && !rc) rc = r;
     }
     return rc;
@@ -1902,24 +1897,21 @@ AV_EXPORT int av_msckf_batch_submit(av_msckf_batch* b, const int64_t* ids, const
         int rc = direct_drain(b, DEV_RING - 2);
         if (rc) return rc;
         const int k = (int)(b->dev_seq++ % DEV_RING);
-        double* cov = b->next_cov; b->next_cov = nullptr;
-        av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
-        av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
+        const StepOuts outs = take_outs(b);
         if ((rc = dev_launch(b, k, ids, uv, n_feat, cap, timestamps, false, nullptr, (hipStream_t)stream))) return rc;
-        b->direct_pending.push_back({k, out, cov, lm, lmn, fst});
+        b->direct_pending.push_back({k, out, outs});
         return AV_OK;
     }
     const int k = (int)(b->dev_seq++ % DEV_RING);
-    double* cov = b->next_cov; b->next_cov = nullptr;
-    av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
-    av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
+    const StepOuts outs = take_outs(b);
     for (size_t gi = 0; gi < b->subs.size(); ++gi) {
         av_msckf_batch* g = b->subs[gi];
         const size_t s0 = gi * (size_t)b->per_sub;
         av_msckf_batch::Job job;
         if (g->dev) {
+            const StepOuts go = outs.at(b->out_set, s0);
             job.launch = [=] { return dev_launch(g, k, ids + s0 * cap, uv + s0 * cap * 4, n_feat + s0, cap, timestamps + s0, false, nullptr, g->own); };
-            job.finish = [=] { return dev_finish(g, k, out + s0 * 12, cov ? cov + s0 * ODOM_COV_DOUBLES : nullptr, lm ? lm + s0 * b->lm_cap : nullptr, lmn ? lmn + s0 * 2 : nullptr, fst ? fst + s0 : nullptr); };
+            job.finish = [=] { return dev_finish(g, k, out + s0 * 12, go); };
         } else {
             job.launch = [=] { return sub_step(g, ids + s0 * cap, uv + s0 * cap * 4, n_feat + s0, cap, timestamps + s0, out + s0 * 12, g->own); };
         }
@@ -1971,20 +1963,19 @@ AV_EXPORT int av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_de
     }
     AV_HIP(hipEventRecord(b->ev_msg[k], ms));
     hipEvent_t ready = b->ev_msg[k];
-    double* cov = b->next_cov; b->next_cov = nullptr;
-    av_landmark* lm = b->next_lm; int32_t* lmn = b->next_lmn; b->next_lm = nullptr; b->next_lmn = nullptr;
-    av_filter_stats* fst = b->next_stats; b->next_stats = nullptr;
+    const StepOuts outs = take_outs(b);
     if (b->subs.empty()) {
         if ((rc = dev_launch(b, k, nullptr, nullptr, nullptr, cap, timestamps, true, ready, (hipStream_t)stream))) return rc;
-        b->direct_pending.push_back({k, out, cov, lm, lmn, fst});
+        b->direct_pending.push_back({k, out, outs});
         return AV_OK;
     }
     s0 = 0;
     for (av_msckf_batch* g : b->subs) {
         const size_t o = s0;
+        const StepOuts go = outs.at(b->out_set, o);
         av_msckf_batch::Job job;
         job.launch = [=] { return dev_launch(g, k, nullptr, nullptr, nullptr, cap, timestamps + o, true, ready, g->own); };
-        job.finish = [=] { return dev_finish(g, k, out + o * 12, cov ? cov + o * ODOM_COV_DOUBLES : nullptr, lm ? lm + o * b->lm_cap : nullptr, lmn ? lmn + o * 2 : nullptr, fst ? fst + o : nullptr); };
+        job.finish = [=] { return dev_finish(g, k, out + o * 12, go); };
         s0 += (size_t)g->S;
         std::lock_guard<std::mutex> lk(g->wmu);
         g->jobs.push_back(std::move(job));
@@ -2020,91 +2011,58 @@ AV_EXPORT int av_msckf_batch_step(av_msckf_batch* b, const int64_t* ids, const d
     return av_msckf_batch_wait(b, 0);
 }
 
-// Odometry covariance (airvision.h, "Odometry covariance").  set: before the batch's first step -- the groups size their record buffers
-// when they prepare the device-resident path.  next: the destination of the next step's records, taken by that step.
-AV_EXPORT int av_msckf_batch_set_odom_cov(av_msckf_batch* b, int enable)
-{
-    if (!b) { av_set_error("av_msckf_batch_set_odom_cov: bad arguments"); return AV_E_INVALID; }
-    std::vector<av_msckf_batch*> parts = b->subs;
-    if (parts.empty()) parts.push_back(b);
-    if (enable) for (av_msckf_batch* g : parts) if (!g->dev) {
-        av_set_error("av_msckf_batch_set_odom_cov: the odometry covariance needs the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)");
-        return AV_E_INVALID;
-    }
-    bool stepped = b->dev_seq > 0;
-    for (av_msckf_batch* g : parts) if (g->n_steps > 0 || (g->dev && g->dev->cap > 0)) stepped = true;
-    if (stepped) { av_set_error("av_msckf_batch_set_odom_cov: the batch has stepped; the odometry covariance is switched before the first step"); return AV_E_INVALID; }
-    b->odom_cov = enable != 0; b->next_cov = nullptr;
-    for (av_msckf_batch* g : parts) g->odom_cov = enable != 0;
-    return AV_OK;
-}
-
-AV_EXPORT int av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host)
-{
-    if (!b || !cov_host) { av_set_error("av_msckf_batch_next_odom_cov: bad arguments"); return AV_E_INVALID; }
-    if (!b->odom_cov) { av_set_error("av_msckf_batch_next_odom_cov: the odometry covariance is off (av_msckf_batch_set_odom_cov)"); return AV_E_INVALID; }
-    b->next_cov = cov_host;
-    return AV_OK;
-}
-
-// Landmark map (airvision.h, "Landmark map").  set: before the batch's first step, like the odometry covariance -- the groups size
-// their record buffers when they prepare the device-resident path.  next: the destination of the next step's records and counts.
+// The optional per-step outputs (OUTS, msckf_dev.inc; airvision.h: "Odometry covariance", "Landmark map", "Innovation statistics").
+// set: before the batch's first step -- the groups size their buffers when they prepare the device-resident path.  next: the
+// destination of the next step's arrays, taken by that step.
 static_assert(sizeof(av_landmark) == AV_LANDMARK_BYTES && sizeof(DLandmark) == AV_LANDMARK_BYTES, "av_landmark layout");
 static_assert(LM_USED == AV_LM_USED && LM_REJECTED == AV_LM_REJECTED && LM_TRACKED == AV_LM_TRACKED && LM_NEW == AV_LM_NEW, "AV_LM_* bits");
-AV_EXPORT int av_msckf_batch_set_landmarks(av_msckf_batch* b, int cap)
-{
-    if (!b || cap < 0 || cap > (1 << 20)) { av_set_error("av_msckf_batch_set_landmarks: bad arguments"); return AV_E_INVALID; }
-    std::vector<av_msckf_batch*> parts = b->subs;
-    if (parts.empty()) parts.push_back(b);
-    if (cap) for (av_msckf_batch* g : parts) if (!g->dev) {
-        av_set_error("av_msckf_batch_set_landmarks: the landmark map needs the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)");
-        return AV_E_INVALID;
-    }
-    bool stepped = b->dev_seq > 0;
-    for (av_msckf_batch* g : parts) if (g->n_steps > 0 || (g->dev && g->dev->cap > 0)) stepped = true;
-    if (stepped) { av_set_error("av_msckf_batch_set_landmarks: the batch has stepped; the landmark map is switched before the first step"); return AV_E_INVALID; }
-    b->lm_cap = cap; b->next_lm = nullptr; b->next_lmn = nullptr;
-    for (av_msckf_batch* g : parts) g->lm_cap = cap;
-    return AV_OK;
-}
-
-AV_EXPORT int av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t* n)
-{
-    if (!b || !rec || !n) { av_set_error("av_msckf_batch_next_landmarks: bad arguments"); return AV_E_INVALID; }
-    if (b->lm_cap <= 0) { av_set_error("av_msckf_batch_next_landmarks: the landmark map is off (av_msckf_batch_set_landmarks)"); return AV_E_INVALID; }
-    b->next_lm = rec; b->next_lmn = n;
-    return AV_OK;
-}
-
-// Innovation statistics (airvision.h, "Innovation statistics").  set: before the batch's first step, like the other two outputs -- the
-// groups size their buffers when they prepare the device-resident path.  next: the destination of the next step's records.
 static_assert(sizeof(av_update_stats) == 64 && sizeof(av_filter_stats) == AV_FILTER_STATS_BYTES && sizeof(DUpdStats) == sizeof(av_update_stats), "av_filter_stats layout");
 static_assert(offsetof(av_update_stats, gamma_eval) == offsetof(DUpdStats, gamma_eval) && offsetof(av_update_stats, dx_rot) == offsetof(DUpdStats, dx_rot) && offsetof(av_update_stats, flags) == offsetof(DUpdStats, flags), "av_update_stats fields");
 static_assert(FS_RAN == AV_FS_RAN && FS_CUT == AV_FS_CUT, "AV_FS_* bits");
-AV_EXPORT int av_msckf_batch_set_stats(av_msckf_batch* b, int enable)
+
+namespace {
+
+// the body of av_msckf_batch_set_*: feature f gets `setting` on the batch and on every group (args_ok: the wrapper's own argument check)
+int batch_set_out(av_msckf_batch* b, OutFeat f, int setting, bool args_ok = true)
 {
-    if (!b) { av_set_error("av_msckf_batch_set_stats: bad arguments"); return AV_E_INVALID; }
+    const OutWords& w = out_words(f);
+    if (!b || !args_ok) { av_set_error("av_msckf_batch_set_%s: bad arguments", w.fn); return AV_E_INVALID; }
     std::vector<av_msckf_batch*> parts = b->subs;
     if (parts.empty()) parts.push_back(b);
-    if (enable) for (av_msckf_batch* g : parts) if (!g->dev) {
-        av_set_error("av_msckf_batch_set_stats: the innovation statistics need the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)");
+    if (setting) for (av_msckf_batch* g : parts) if (!g->dev) {
+        av_set_error("av_msckf_batch_set_%s: %s %s the device-resident filter; this batch runs the host-bookkeeping path (AV_MSCKF_STORE=host)", w.fn, w.noun, w.needs);
         return AV_E_INVALID;
     }
     bool stepped = b->dev_seq > 0;
     for (av_msckf_batch* g : parts) if (g->n_steps > 0 || (g->dev && g->dev->cap > 0)) stepped = true;
-    if (stepped) { av_set_error("av_msckf_batch_set_stats: the batch has stepped; the innovation statistics are switched before the first step"); return AV_E_INVALID; }
-    b->stats_on = enable != 0; b->next_stats = nullptr;
-    for (av_msckf_batch* g : parts) g->stats_on = enable != 0;
+    if (stepped) { av_set_error("av_msckf_batch_set_%s: the batch has stepped; %s %s switched before the first step", w.fn, w.noun, w.is); return AV_E_INVALID; }
+    b->out_set[f] = setting;
+    for (int i = 0; i < N_OUT; ++i) if (OUTS[i].feat == f) b->next_outs.p[i] = nullptr;
+    for (av_msckf_batch* g : parts) g->out_set[f] = setting;
     return AV_OK;
 }
 
-AV_EXPORT int av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host)
+// the body of av_msckf_batch_next_*: dst = the caller's arrays for the feature's entries of OUTS, in the table's order
+int batch_next_out(av_msckf_batch* b, OutFeat f, std::initializer_list<void*> dst)
 {
-    if (!b || !rec_host) { av_set_error("av_msckf_batch_next_stats: bad arguments"); return AV_E_INVALID; }
-    if (!b->stats_on) { av_set_error("av_msckf_batch_next_stats: the innovation statistics are off (av_msckf_batch_set_stats)"); return AV_E_INVALID; }
-    b->next_stats = rec_host;
+    const OutWords& w = out_words(f);
+    bool ok = b != nullptr;
+    for (void* p : dst) ok = ok && p;
+    if (!ok) { av_set_error("av_msckf_batch_next_%s: bad arguments", w.fn); return AV_E_INVALID; }
+    if (!b->out_set[f]) { av_set_error("av_msckf_batch_next_%s: %s %s off (av_msckf_batch_set_%s)", w.fn, w.noun, w.is, w.fn); return AV_E_INVALID; }
+    const void* const* p = dst.begin();
+    for (int i = 0; i < N_OUT; ++i) if (OUTS[i].feat == f) b->next_outs.p[i] = const_cast<void*>(*p++);
     return AV_OK;
 }
+
+}  // namespace
+
+AV_EXPORT int av_msckf_batch_set_odom_cov(av_msckf_batch* b, int enable) { return batch_set_out(b, F_COV, enable != 0); }
+AV_EXPORT int av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host) { return batch_next_out(b, F_COV, {cov_host}); }
+AV_EXPORT int av_msckf_batch_set_landmarks(av_msckf_batch* b, int cap) { return batch_set_out(b, F_LM, cap, cap >= 0 && cap <= (1 << 20)); }
+AV_EXPORT int av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t* n) { return batch_next_out(b, F_LM, {rec, n}); }
+AV_EXPORT int av_msckf_batch_set_stats(av_msckf_batch* b, int enable) { return batch_set_out(b, F_STATS, enable != 0); }
+AV_EXPORT int av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host) { return batch_next_out(b, F_STATS, {rec_host}); }
 
 AV_EXPORT int av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, int n, void* stream)
 {

@@ -1000,6 +1000,39 @@ __global__ __launch_bounds__(256) void dk_prune_probe(DevArgs a, const int* ops,
 }  // namespace
 
 // ---- host-side handles of the device-resident path (functions: msckf_dev_host.inc) ---------------------------------------------
+// The optional per-step outputs: ONE entry per array a step may carry beside its poses, in the order of their read-back on the stream.
+// A feature is what a caller switches (av_msckf_batch_set_*) and hands a destination for (av_msckf_batch_next_*); its setting is
+// 0 = off, else 1 (the landmark map: records per stream and step).  The landmark records and counts are two arrays of one feature.
+// Everything else about them -- the batch's settings and next destinations, StepOuts, the device and pinned buffers, their allocation,
+// read-back, hand-over and restart -- is an array indexed by this table or a loop over it.  A fourth output: an entry here (and in
+// KOuts), its two exported wrappers, and the kernel instances that write it (dk_mid_kernels / dk_finish_kernels, msckf_dev_host.inc).
+enum OutFeat { F_COV, F_LM, F_STATS, N_FEAT };
+enum OutArr { O_COV, O_LM, O_LMN, O_STATS, N_OUT };
+struct OutWords { const char* fn; const char* noun; const char* needs; const char* is; };      // "av_msckf_batch_set_<fn>: <noun> <needs> ...", "<noun> <is> off"
+constexpr OutWords W_COV = {"odom_cov", "the odometry covariance", "needs", "is"}, W_LM = {"landmarks", "the landmark map", "needs", "is"},
+                   W_STATS = {"stats", "the innovation statistics", "need", "are"};
+struct OutDesc {
+    OutFeat feat; size_t fixed, per_setting; OutWords w;
+    size_t bytes(const int* setting) const { return fixed + per_setting * (size_t)setting[feat]; }      // per stream
+};
+constexpr OutDesc OUTS[N_OUT] = {
+    {F_COV, ODOM_COV_DOUBLES * 8, 0, W_COV},         // covariance records
+    {F_LM, 0, AV_LANDMARK_BYTES, W_LM},              // landmark records
+    {F_LM, 2 * 4, 0, W_LM},                          // landmark counts (had, written)
+    {F_STATS, AV_FILTER_STATS_BYTES, 0, W_STATS},    // statistics records (two update blocks)
+};
+constexpr const OutWords& out_words(OutFeat f) { for (int i = 0; i < N_OUT; ++i) if (OUTS[i].feat == f) return OUTS[i].w; return OUTS[0].w; }
+// a step's destinations in the caller's memory (NULL: the step has none and the array is dropped)
+struct StepOuts {
+    void* p[N_OUT] = {};
+    StepOuts at(const int* setting, size_t s0) const      // the slice of a group whose first stream is s0
+    {
+        StepOuts g;
+        for (int i = 0; i < N_OUT; ++i) g.p[i] = p[i] ? (char*)p[i] + s0 * OUTS[i].bytes(setting) : nullptr;
+        return g;
+    }
+};
+struct KOuts { double* odom; LmOut lm; DUpdStats* stats; };      // the device arrays as the kernels' parameter lists and DRestart take them (dev_kouts)
 constexpr int DEV_RING = 3;          // steps of a stream group that may be queued at once (inputs / outputs are ring-buffered)
 struct DevSlot {
     DCtl* ctl_h = nullptr; DCtl* ctl_d = nullptr;
@@ -1008,9 +1041,7 @@ struct DevSlot {
     long long* ids_h = nullptr; double* uv_h = nullptr; int* n_h = nullptr;      // pinned staging of a feature message that arrives in host arrays
     long long* ids_d = nullptr; double* uv_d = nullptr; int* n_d = nullptr;      // the message on the device (copied from the host arrays or from the front-end's buffers)
     double* out_h = nullptr; int* cnt_h = nullptr;                                // pinned landing zones of the step's only read-back
-    double* odom_h = nullptr;                                                     // [S][ODOM_COV_DOUBLES] pinned, the odometry-covariance records of the step (NULL: the feature is off)
-    DLandmark* lm_h = nullptr; int* lmn_h = nullptr;                              // [S][lm.cap] / [S][2] pinned, the landmark records and counts of the step (NULL: the feature is off)
-    DUpdStats* stats_h = nullptr;                                                 // [S][2] pinned, the innovation statistics of the step (NULL: the feature is off)
+    char* outs_h[N_OUT] = {};                                                     // pinned landing zones of the step's optional outputs, [S] x the entry's bytes per stream (NULL: the feature is off)
     hipEvent_t done = nullptr;
     hipEvent_t t0[2] = {nullptr, nullptr}, t1[2] = {nullptr, nullptr}; bool t_used[2] = {false, false};      // av_msckf_batch_work: device time of the two phase chains
     bool in_flight = false;
@@ -1022,9 +1053,7 @@ struct DevPath {
     DevSlot slot[DEV_RING];
     double* out_d = nullptr; int* stacked0 = nullptr; int* stacked1 = nullptr; UpdArgs* updbase = nullptr; UpdArgs* upd = nullptr;
     DCov* cov_d = nullptr;           // [S] dk_begin -> dk_cov
-    double* odom_d = nullptr;        // [S][ODOM_COV_DOUBLES] dk_finish_cov's records (NULL: av_msckf_batch_set_odom_cov is off)
-    LmOut lm = {nullptr, nullptr, 0};      // [S][cap] records and [S][2] counts of dk_mid_lm / dk_finish_*lm (rec NULL: av_msckf_batch_set_landmarks is off)
-    DUpdStats* stats_d = nullptr;    // [S][2] blocks of the dk_mid_*st / dk_finish_*st instances (NULL: av_msckf_batch_set_stats is off)
+    char* outs_d[N_OUT] = {};        // what the dk_mid* / dk_finish* instances write of the optional outputs, [S] x the entry's bytes per stream (NULL: the feature is off)
     int dk_wg = 0;                   // AV_DK_WG read when the path is prepared: 64 / 256 = workgroup size of the per-stream kernels, 0 = by the group's stream count
     int launched_wg = 0;             // workgroup size dev_enqueue launched them with in the last enqueued step (0: no step yet); av_msckf_batch_launch_shape
     int* cols = nullptr; int* blk_row = nullptr; int* blk_len = nullptr; int* clist = nullptr; int* again = nullptr;

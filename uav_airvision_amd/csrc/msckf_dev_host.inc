@@ -57,9 +57,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
         DA(A.st, S) DA(A.cam_id, S * cs) DA(A.cam_q, S * cs * 4) DA(A.cam_p, S * cs * 3) DA(A.cam_qn, S * cs * 4) DA(A.ncam, S) DA(A.nstate, S) DA(A.grav, S * 3)
         DA(A.n_cand, S) DA(A.over, S) DA(A.cnt, 32) DA(d->out_d, S * 12) DA(d->cov_d, S) DA(d->stacked0, S) DA(d->stacked1, S) DA(d->updbase, S) DA(d->upd, S * 2)
         DA(d->cols, S * 6 * cs) DA(d->clist, S + 8) DA(d->work, S * 8)
-        if (b->odom_cov) DA(d->odom_d, S * ODOM_COV_DOUBLES)
-        if (b->lm_cap > 0) { DA(d->lm.rec, S * b->lm_cap) DA(d->lm.n, S * 2) d->lm.cap = b->lm_cap; }
-        if (b->stats_on) DA(d->stats_d, S * 2)
+        for (int i = 0; i < N_OUT; ++i) if (b->out_set[OUTS[i].feat]) DA(d->outs_d[i], S * OUTS[i].bytes(b->out_set))
         DA(d->rs_list_d, S) DA(d->rs_carry_d, S * 2)
         if ((rc = b->res.pinned(&d->rs_list_h, S)) || (rc = b->res.pinned(&d->rs_carry_h, S * 2))) return rc;
         DAF(A.pos_of, S * A.ns, 0xFF) DAF(A.order, S * A.ns, 0xFF) DA(A.fr_n, S * A.ns) DA(A.hdr, S * AVS_HDR_WORDS) DA(A.births, S)
@@ -77,9 +75,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
             if ((rc = b->res.pinned(&sl.ctl_h, S)) || (rc = b->res.pinned(&sl.out_h, S * 12)) || (rc = b->res.pinned(&sl.cnt_h, 16))) return rc;
             DA(sl.ctl_d, S) DA(sl.n_d, S)
             if ((rc = b->res.pinned(&sl.n_h, S))) return rc;
-            if (b->odom_cov && (rc = b->res.pinned(&sl.odom_h, S * ODOM_COV_DOUBLES))) return rc;
-            if (b->lm_cap > 0 && ((rc = b->res.pinned(&sl.lm_h, S * b->lm_cap)) || (rc = b->res.pinned(&sl.lmn_h, S * 2)))) return rc;
-            if (b->stats_on && (rc = b->res.pinned(&sl.stats_h, S * 2))) return rc;
+            for (int i = 0; i < N_OUT; ++i) if (b->out_set[OUTS[i].feat] && (rc = b->res.pinned(&sl.outs_h[i], S * OUTS[i].bytes(b->out_set)))) return rc;
             if ((rc = b->res.event(&sl.done, hipEventDisableTiming | hipEventBlockingSync))) return rc;
             for (int ph = 0; ph < 2; ++ph) if ((rc = b->res.event(&sl.t0[ph], hipEventDefault)) || (rc = b->res.event(&sl.t1[ph], hipEventDefault))) return rc;
         }
@@ -450,6 +446,36 @@ void dev_launch_predict(const DevArgs& a, int S, int dk_wg, bool append, hipStre
     else hipLaunchKernelGGL(dk_cov<256>, dim3(S), dim3(256), 0, stm, a);
 }
 
+// The named instances of dk_mid and dk_finish (profiles/filter_stats/README.md has why they are named instances), by the outputs that
+// are on: the same launches as with all off, the instance also writes those outputs' records and the step reads them back.  Every
+// instance's parameter list is DevArgs, then the ordered subset of (double* odom, LmOut, DUpdStats*) of its set bits: the order
+// dev_launch_outs pushes the arguments in.
+const void* const dk_mid_kernels[2][2] = {        // [landmarks][statistics]
+    {(const void*)dk_mid, (const void*)dk_mid_st}, {(const void*)dk_mid_lm, (const void*)dk_mid_lm_st}};
+const void* const dk_finish_kernels[2][2][2] = {  // [covariance][landmarks][statistics]
+    {{(const void*)dk_finish, (const void*)dk_finish_st}, {(const void*)dk_finish_lm, (const void*)dk_finish_lm_st}},
+    {{(const void*)dk_finish_cov, (const void*)dk_finish_cov_st}, {(const void*)dk_finish_cov_lm, (const void*)dk_finish_cov_lm_st}}};
+static_assert(std::is_same<decltype(&dk_mid_lm_st), void (*)(DevArgs, LmOut, DUpdStats*)>::value &&
+              std::is_same<decltype(&dk_finish_cov_lm_st), void (*)(DevArgs, double*, LmOut, DUpdStats*)>::value, "dev_launch_outs: covariance, landmarks, statistics");
+KOuts dev_kouts(const av_msckf_batch* b)          // the one place that gives the table's device arrays their types
+{
+    char* const* p = b->dev->outs_d;
+    return {(double*)p[O_COV], LmOut{(DLandmark*)p[O_LM], (int*)p[O_LMN], b->out_set[F_LM]}, (DUpdStats*)p[O_STATS]};
+}
+int dev_launch_outs(bool finish, const av_msckf_batch* b, DevArgs& a, int wg, hipStream_t stm)
+{
+    KOuts o = dev_kouts(b);
+    const bool cov = finish && o.odom, lm = o.lm.rec, stats = o.stats;      // (dk_mid writes no covariance record)
+    const void* kernel = finish ? dk_finish_kernels[cov][lm][stats] : dk_mid_kernels[lm][stats];
+    void* args[4] = {&a}; int n = 1;
+    if (cov) args[n++] = &o.odom;
+    if (lm) args[n++] = &o.lm;
+    if (stats) args[n++] = &o.stats;
+    AV_HIP(hipLaunchKernel(kernel, dim3(b->S), dim3(wg), args, 0, stm));
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
 // the device side of one step on slot k: uploads of the slot's staging, the kernels, the read-back of the poses (no waits, no
 // host decisions: the sequence is the same every step, which is what lets it be captured as a graph)
 int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_t stm)
@@ -487,43 +513,20 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     // (the whole pruning phase of a stream as ONE workgroup -- five launches fewer -- was built and measured in round 4: 141.3 k against
     //  144.4 k frames/s, 5.5 against 5.0 ms of exclusive chain: a stream's ~150 candidates walk through the 16 teams of one workgroup
     //  instead of spreading over the chip.  Removed in round 5; profiles/r04/README.md keeps the numbers.)
-    // (with the landmark map on, the instances that also write the records of the update that has just run: the same launches, two more read-backs)
-    // (with the innovation statistics on, the instances that also write the stream's block of that update: the same launches, one more read-back)
-    if (d->stats_d && d->lm.rec) hipLaunchKernelGGL(dk_mid_lm_st, dim3(S), dim3(dk_wg), 0, stm, a, d->lm, d->stats_d);
-    else if (d->stats_d) hipLaunchKernelGGL(dk_mid_st, dim3(S), dim3(dk_wg), 0, stm, a, d->stats_d);
-    else if (d->lm.rec) hipLaunchKernelGGL(dk_mid_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->lm);
-    else hipLaunchKernelGGL(dk_mid, dim3(S), dim3(dk_wg), 0, stm, a);
-    AV_LAUNCH_CHECK();
+    if ((rc = dev_launch_outs(false, b, a, dk_wg, stm))) return rc;
     if ((rc = dev_phase(b, 1, stm, sl, a.cnt))) return rc;
     if (b->debug_capture && (rc = dev_debug_capture(b, 1, stm))) return rc;
     a.stacked = d->stacked1;
-    // (with the odometry covariance on, the instance that also writes every stream's record: the same launch, one more read-back)
-    if (d->stats_d) {
-        if (d->odom_d && d->lm.rec) hipLaunchKernelGGL(dk_finish_cov_lm_st, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->lm, d->stats_d);
-        else if (d->lm.rec) hipLaunchKernelGGL(dk_finish_lm_st, dim3(S), dim3(dk_wg), 0, stm, a, d->lm, d->stats_d);
-        else if (d->odom_d) hipLaunchKernelGGL(dk_finish_cov_st, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->stats_d);
-        else hipLaunchKernelGGL(dk_finish_st, dim3(S), dim3(dk_wg), 0, stm, a, d->stats_d);
-    }
-    else if (d->odom_d && d->lm.rec) hipLaunchKernelGGL(dk_finish_cov_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d, d->lm);
-    else if (d->lm.rec) hipLaunchKernelGGL(dk_finish_lm, dim3(S), dim3(dk_wg), 0, stm, a, d->lm);
-    else if (d->odom_d) hipLaunchKernelGGL(dk_finish_cov, dim3(S), dim3(dk_wg), 0, stm, a, d->odom_d);
-    else hipLaunchKernelGGL(dk_finish, dim3(S), dim3(dk_wg), 0, stm, a);
-    AV_LAUNCH_CHECK();
+    if ((rc = dev_launch_outs(true, b, a, dk_wg, stm))) return rc;
     AV_HIP(hipMemcpyAsync(sl.out_h, d->out_d, sizeof(double) * 12 * S, hipMemcpyDeviceToHost, stm));
-    if (d->odom_d) AV_HIP(hipMemcpyAsync(sl.odom_h, d->odom_d, sizeof(double) * ODOM_COV_DOUBLES * S, hipMemcpyDeviceToHost, stm));
-    if (d->lm.rec) {
-        AV_HIP(hipMemcpyAsync(sl.lm_h, d->lm.rec, sizeof(DLandmark) * (size_t)d->lm.cap * S, hipMemcpyDeviceToHost, stm));
-        AV_HIP(hipMemcpyAsync(sl.lmn_h, d->lm.n, sizeof(int) * 2 * S, hipMemcpyDeviceToHost, stm));
-    }
-    if (d->stats_d) AV_HIP(hipMemcpyAsync(sl.stats_h, d->stats_d, sizeof(DUpdStats) * 2 * S, hipMemcpyDeviceToHost, stm));
+    for (int i = 0; i < N_OUT; ++i) if (d->outs_d[i]) AV_HIP(hipMemcpyAsync(sl.outs_h[i], d->outs_d[i], OUTS[i].bytes(b->out_set) * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(sl.cnt_h, a.cnt, sizeof(int) * 16, hipMemcpyDeviceToHost, stm));
     return AV_OK;
 }
 
-// wait for the step queued on slot k and hand its published poses to the caller (cov: where the step's odometry-covariance records
-// go, S * ODOM_COV_DOUBLES doubles; lm / lmn: where its landmark records and counts go, S * lm_cap records and S * 2 ints; NULL: the
-// step has no destination and the records are dropped; stats: likewise for its innovation statistics, S records of AV_FILTER_STATS_BYTES)
-int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* lm, int32_t* lmn, av_filter_stats* stats)
+// wait for the step queued on slot k and hand its published poses to the caller (outs: where the step's optional outputs go, S times
+// the entry's bytes per stream each; NULL: the step has no destination for that array and it is dropped)
+int dev_finish(av_msckf_batch* b, int k, double* out, const StepOuts& outs)
 {
     DevPath* d = b->dev;
     DevSlot& sl = d->slot[k];
@@ -531,12 +534,7 @@ int dev_finish(av_msckf_batch* b, int k, double* out, double* cov, av_landmark* 
     AV_HIP(hipEventSynchronize(sl.done));
     sl.in_flight = false;
     memcpy(out, sl.out_h, sizeof(double) * 12 * b->S);
-    if (cov && sl.odom_h) memcpy(cov, sl.odom_h, sizeof(double) * ODOM_COV_DOUBLES * b->S);
-    if (lm && lmn && sl.lm_h) {
-        memcpy(lm, sl.lm_h, sizeof(DLandmark) * (size_t)d->lm.cap * b->S);
-        memcpy(lmn, sl.lmn_h, sizeof(int) * 2 * b->S);
-    }
-    if (stats && sl.stats_h) memcpy(stats, sl.stats_h, sizeof(DUpdStats) * 2 * b->S);
+    for (int i = 0; i < N_OUT; ++i) if (outs.p[i] && sl.outs_h[i]) memcpy(outs.p[i], sl.outs_h[i], OUTS[i].bytes(b->out_set) * b->S);
     for (int i = 0; i < 16; ++i) d->hint[i] = sl.cnt_h[i];
     d->have_hint = true;
     for (int ph = 0; ph < 2; ++ph) if (sl.t_used[ph]) {       // the whole step has retired: both phases' event pairs of this slot are complete
@@ -561,7 +559,8 @@ int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm)
     r.list = d->rs_list_d; r.carry = d->rs_carry_d;
     for (int i = 0; i < 3; ++i) { r.v0[i] = b->vel0[i]; r.t_ci[i] = b->t_ci0[i]; r.gravity[i] = b->gravity0[i]; }
     for (int i = 0; i < 9; ++i) r.R_ic[i] = b->R_ic0[i];
-    r.odom = d->odom_d; r.lm = d->lm; r.stats = d->stats_d;
+    const KOuts o = dev_kouts(b);
+    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats;
     hipLaunchKernelGGL(dk_restart, dim3((unsigned)n), dim3(256), 0, stm, d->A, r);
     AV_LAUNCH_CHECK();
     AV_HIP(hipMemcpyAsync(d->rs_carry_h, d->rs_carry_d, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, stm));

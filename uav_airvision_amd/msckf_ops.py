@@ -1,5 +1,6 @@
 """Python handle of the MSCKF device context (av_msckf_* C ABI): covariance resident on the GPU, batched
 per-feature kernels, stacked update.  Used by dropin/msckf.py and dropin/feature; numpy in, numpy out."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -343,6 +344,24 @@ def unpack_filter_stats(rec):
     return out
 
 
+# The optional outputs of a step of BatchedMSCKF, one entry each.  kw: the keyword of `step / submit / submit_dev`; ctor_kw: the
+# constructor keyword that switches it on; setting: the attribute that holds its setting (falsy: off); fn: the library's
+# av_msckf_batch_set_<fn> / av_msckf_batch_next_<fn>; last: the attribute that remembers the arrays of the most recent step that was
+# given any; shapes(flt): the (dtype, shape) of every array it takes; fill: what `True` allocates them with; what(flt): its ValueError.
+# A fourth output is one more entry here (and its constructor / step keywords), beside the C table (OUTS, csrc/msckf_dev.inc).
+StepOutput = collections.namedtuple('StepOutput', 'kw ctor_kw setting fn last shapes fill what')
+STEP_OUTPUTS = (
+    StepOutput('cov', 'odom_cov', 'odom_cov', 'odom_cov', 'last_cov', lambda f: [(np.float64, (f.S, ODOM_COV_DOUBLES))], np.nan,
+               lambda f: 'cov must be a C-contiguous float64[%d, %d] array' % (f.S, ODOM_COV_DOUBLES)),
+    StepOutput('landmarks', 'landmarks', 'landmark_cap', 'landmarks', 'last_landmarks',
+               lambda f: [(LANDMARK_DTYPE, (f.S, f.landmark_cap)), (np.int32, (f.S, 2))], 0,
+               lambda f: 'landmarks must be a pair of C-contiguous arrays LANDMARK_DTYPE[%d, %d], int32[%d, 2]' % (f.S, f.landmark_cap, f.S)),
+    StepOutput('stats', 'stats', 'stats', 'stats', 'last_stats', lambda f: [(FILTER_STATS_DTYPE, (f.S, 2))], 0,
+               lambda f: 'stats must be a C-contiguous FILTER_STATS_DTYPE[%d, 2] array' % f.S),
+)
+_OUTPUT = {o.kw: o for o in STEP_OUTPUTS}
+
+
 class BatchedMSCKF(object):
     """S independent filters stepped together (av_msckf_batch_* C ABI): C++ bookkeeping inside the
     library, one batched launch per numeric phase.  Mirrors MSCKF.imu_callback / feature_callback
@@ -385,96 +404,60 @@ class BatchedMSCKF(object):
                 float(config.observation_noise), float(config.position_std_threshold), _d(config.velocity),
                 _d([o.huber_epsilon, o.estimation_precision, o.initial_damping, o.outer_loop_max_iteration, o.inner_loop_max_iteration, o.translation_threshold]),
                 self.device, C.byref(self._h)))
-            self.odom_cov = bool(odom_cov)
-            self.last_cov = None           # the records array of the most recent step that was given one (float64[S, 120])
-            if self.odom_cov:
-                try:
-                    N.check(N.lib().av_msckf_batch_set_odom_cov(self._h, 1))
-                except Exception:
-                    self.close()
-                    raise
-            self.landmark_cap = int(landmark_cap) if landmarks else 0
-            self.last_landmarks = None     # (records LANDMARK_DTYPE[S, cap], counts int32[S, 2]) of the most recent step that was given a pair
-            if landmarks:
-                try:
-                    if self.landmark_cap < 1:
-                        raise ValueError('landmark_cap must be at least 1')
-                    N.check(N.lib().av_msckf_batch_set_landmarks(self._h, self.landmark_cap))
-                except Exception:
-                    self.landmark_cap = 0
-                    self.close()
-                    raise
-            self.stats = bool(stats)
-            self.last_stats = None         # the records array of the most recent step that was given one (FILTER_STATS_DTYPE[S, 2])
-            if self.stats:
-                try:
-                    N.check(N.lib().av_msckf_batch_set_stats(self._h, 1))
-                except Exception:
-                    self.stats = False
-                    self.close()
-                    raise
+        # the optional outputs: last_* = the arrays of the most recent step that was given any (cov: float64[S, 120]; landmarks: (records
+        # LANDMARK_DTYPE[S, cap], counts int32[S, 2]); stats: FILTER_STATS_DTYPE[S, 2])
+        want = {'odom_cov': bool(odom_cov), 'landmark_cap': int(landmark_cap) if landmarks else 0, 'stats': bool(stats)}
+        for o in STEP_OUTPUTS:
+            setattr(self, o.setting, want[o.setting])
+            setattr(self, o.last, None)
+        try:
+            if landmarks and want['landmark_cap'] < 1:
+                raise ValueError('landmark_cap must be at least 1')
+            for o in STEP_OUTPUTS:
+                if want[o.setting]:
+                    self._set(o, want[o.setting])
+        except Exception:
+            self.close()
+            raise
 
-    def set_stats(self, enable):
-        """av_msckf_batch_set_stats: before the first step only."""
-        N.check(N.lib().av_msckf_batch_set_stats(self._h, 1 if enable else 0))
-        self.stats = bool(enable)
-
-    def _next_stats(self, st):
-        """The records array of the next step (None: the step has none), handed to the library.  st: None, True (allocate) or a
-        C-contiguous FILTER_STATS_DTYPE[S, 2] array."""
-        if st is None or st is False:
-            return None
-        if not self.stats:
-            raise ValueError('stats= needs BatchedMSCKF(..., stats=True)')
-        if st is True:
-            st = np.zeros((self.S, 2), dtype=FILTER_STATS_DTYPE)
-        if not (isinstance(st, np.ndarray) and st.dtype == FILTER_STATS_DTYPE and st.shape == (self.S, 2) and st.flags['C_CONTIGUOUS']):
-            raise ValueError('stats must be a C-contiguous FILTER_STATS_DTYPE[%d, 2] array' % self.S)
-        N.check(N.lib().av_msckf_batch_next_stats(self._h, st.ctypes.data_as(C.c_void_p)))
-        self.last_stats = st
-        return st
-
-    def set_landmarks(self, cap):
-        """av_msckf_batch_set_landmarks: cap records per stream and step (0: off); before the first step only."""
-        N.check(N.lib().av_msckf_batch_set_landmarks(self._h, int(cap)))
-        self.landmark_cap = int(cap)
-
-    def _next_landmarks(self, lm):
-        """The (records, counts) pair of the next step (None: the step has none), handed to the library.  lm: None, True (allocate) or
-        a pair of C-contiguous arrays LANDMARK_DTYPE[S, landmark_cap], int32[S, 2]."""
-        if lm is None or lm is False:
-            return None
-        if not self.landmark_cap:
-            raise ValueError('landmarks= needs BatchedMSCKF(..., landmarks=True)')
-        if lm is True:
-            lm = (np.zeros((self.S, self.landmark_cap), dtype=LANDMARK_DTYPE), np.zeros((self.S, 2), dtype=np.int32))
-        rec, n = lm
-        if not (isinstance(rec, np.ndarray) and rec.dtype == LANDMARK_DTYPE and rec.shape == (self.S, self.landmark_cap) and rec.flags['C_CONTIGUOUS']
-                and isinstance(n, np.ndarray) and n.dtype == np.int32 and n.shape == (self.S, 2) and n.flags['C_CONTIGUOUS']):
-            raise ValueError('landmarks must be a pair of C-contiguous arrays LANDMARK_DTYPE[%d, %d], int32[%d, 2]' % (self.S, self.landmark_cap, self.S))
-        N.check(N.lib().av_msckf_batch_next_landmarks(self._h, rec.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p)))
-        self.last_landmarks = (rec, n)
-        return self.last_landmarks
+    def _set(self, o, setting):
+        N.check(getattr(N.lib(), 'av_msckf_batch_set_' + o.fn)(self._h, int(setting)))
+        setattr(self, o.setting, setting)
 
     def set_odom_cov(self, enable):
         """av_msckf_batch_set_odom_cov: before the first step only."""
-        N.check(N.lib().av_msckf_batch_set_odom_cov(self._h, 1 if enable else 0))
-        self.odom_cov = bool(enable)
+        self._set(_OUTPUT['cov'], bool(enable))
 
-    def _next_cov(self, cov):
-        """The records array of the next step (None: the step has none), handed to the library.  cov: None, True (allocate) or a
-        C-contiguous float64[S, 120] array."""
-        if cov is None or cov is False:
+    def set_landmarks(self, cap):
+        """av_msckf_batch_set_landmarks: cap records per stream and step (0: off); before the first step only."""
+        self._set(_OUTPUT['landmarks'], int(cap))
+
+    def set_stats(self, enable):
+        """av_msckf_batch_set_stats: before the first step only."""
+        self._set(_OUTPUT['stats'], bool(enable))
+
+    def _next(self, o, value):
+        """The arrays of output `o` for the next step (None: the step has none), handed to the library.  value: None, True (allocate) or
+        the caller's C-contiguous array (landmarks: pair of arrays) of o.shapes(self)."""
+        if value is None or value is False:
             return None
-        if not self.odom_cov:
-            raise ValueError('cov= needs BatchedMSCKF(..., odom_cov=True)')
-        if cov is True:
-            cov = np.full((self.S, ODOM_COV_DOUBLES), np.nan)
-        if not (isinstance(cov, np.ndarray) and cov.dtype == np.float64 and cov.shape == (self.S, ODOM_COV_DOUBLES) and cov.flags['C_CONTIGUOUS']):
-            raise ValueError('cov must be a C-contiguous float64[%d, %d] array' % (self.S, ODOM_COV_DOUBLES))
-        N.check(N.lib().av_msckf_batch_next_odom_cov(self._h, cov.ctypes.data_as(C.c_void_p)))
-        self.last_cov = cov
-        return cov
+        if not getattr(self, o.setting):
+            raise ValueError('%s= needs BatchedMSCKF(..., %s=True)' % (o.kw, o.ctor_kw))
+        shapes = o.shapes(self)
+        if value is True:
+            arrs = tuple(np.full(shape, o.fill, dtype=dtype) for dtype, shape in shapes)
+        else:
+            arrs = tuple(value) if len(shapes) > 1 else (value,)
+        if len(arrs) != len(shapes) or not all(isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == shape and a.flags['C_CONTIGUOUS']
+                                               for a, (dtype, shape) in zip(arrs, shapes)):
+            raise ValueError(o.what(self))
+        N.check(getattr(N.lib(), 'av_msckf_batch_next_' + o.fn)(self._h, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+        setattr(self, o.last, arrs[0] if len(arrs) == 1 else arrs)
+        return getattr(self, o.last)
+
+    def _next_outputs(self, **kw):
+        """`step / submit / submit_dev`'s keywords handed to the library; the tuple of arrays the step's entry of _inflight keeps alive."""
+        return tuple(self._next(o, kw[o.kw]) for o in STEP_OUTPUTS)
 
     def close(self):
         if self._h:
@@ -511,9 +494,7 @@ class BatchedMSCKF(object):
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         cap = ids.shape[1]
         out = np.zeros((self.S, 12))
-        cov = self._next_cov(cov)
-        lm = self._next_landmarks(landmarks)
-        fst = self._next_stats(stats)
+        self._next_outputs(cov=cov, landmarks=landmarks, stats=stats)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_step(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                 nf.ctypes.data_as(C.c_void_p), cap, ts.ctypes.data_as(C.c_void_p),
@@ -530,14 +511,12 @@ class BatchedMSCKF(object):
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         out = np.zeros((self.S, 12))
-        cov = self._next_cov(cov)
-        lm = self._next_landmarks(landmarks)
-        fst = self._next_stats(stats)
+        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_submit(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                   nf.ctypes.data_as(C.c_void_p), ids.shape[1], ts.ctypes.data_as(C.c_void_p),
                                                   out.ctypes.data_as(C.c_void_p), N.current_stream()))
-        self._inflight.append((ids, uv, nf, ts, out, cov, lm, fst))     # the library reads / writes these until the step retires
+        self._inflight.append((ids, uv, nf, ts, out) + outs)     # the library reads / writes these until the step retires
         return out
 
     def device_resident(self):
@@ -554,14 +533,12 @@ class BatchedMSCKF(object):
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         assert ts.shape == (self.S,) and engine.n_streams == self.S
         out = np.zeros((self.S, 12))
-        cov = self._next_cov(cov)
-        lm = self._next_landmarks(landmarks)
-        fst = self._next_stats(stats)
+        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats)
         with torch.cuda.device(self.device):
             ms = N.current_stream() if msg_stream is None else msg_stream
             N.check(N.lib().av_msckf_batch_submit_dev(self._h, ids, uv, n, cap, ts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
                                                       ms, N.current_stream()))
-        self._inflight.append((ts, out, cov, lm, fst))
+        self._inflight.append((ts, out) + outs)
         return out
 
     def wait(self, max_pending=0):

@@ -211,16 +211,13 @@ class FilterSet(object):
     its records array and `last_stats` joins them ([S, 2] of FILTER_STATS_DTYPE)."""
 
     def __init__(self, config, engine_set, device=0, **kw):
-        from .msckf_ops import BatchedMSCKF
+        from .msckf_ops import BatchedMSCKF, STEP_OUTPUTS
         self.es = engine_set
         self.parts = engine_set.parts
         self.flts = [BatchedMSCKF(config, hi - lo, device=device, **kw) for lo, hi in self.parts]
-        self.odom_cov = bool(kw.get('odom_cov', False))
-        self.last_cov = None
-        self.landmarks = bool(kw.get('landmarks', False))
-        self.last_landmarks = None
-        self.stats = bool(kw.get('stats', False))
-        self.last_stats = None
+        for o in STEP_OUTPUTS:                               # odom_cov / landmarks / stats: on or off; last_*: the joined arrays of the last step that asked
+            setattr(self, o.ctor_kw, bool(kw.get(o.ctor_kw, False)))
+            setattr(self, o.last, None)
 
     def device_resident(self):
         return all(f.device_resident() for f in self.flts)
@@ -232,41 +229,32 @@ class FilterSet(object):
 
     def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None):
         assert engine_set is self.es
-        if cov is not None and cov is not True:
-            raise ValueError('FilterSet.submit_dev: cov is None or True (every part allocates its own records array)')
-        if cov and not self.odom_cov:
-            raise ValueError('cov= needs FilterSet(..., odom_cov=True)')
-        if landmarks is not None and landmarks is not True:
-            raise ValueError('FilterSet.submit_dev: landmarks is None or True (every part allocates its own arrays)')
-        if landmarks and not self.landmarks:
-            raise ValueError('landmarks= needs FilterSet(..., landmarks=True)')
-        if stats is not None and stats is not True:
-            raise ValueError('FilterSet.submit_dev: stats is None or True (every part allocates its own records array)')
-        if stats and not self.stats:
-            raise ValueError('stats= needs FilterSet(..., stats=True)')
+        from .msckf_ops import STEP_OUTPUTS
+        asked = {'cov': cov, 'landmarks': landmarks, 'stats': stats}
+        views = {}                                           # output -> one _OutView per array of it
+        for o in STEP_OUTPUTS:
+            if asked[o.kw] is None:
+                continue
+            if asked[o.kw] is not True:
+                what = 'records array' if len(o.shapes(self.flts[0])) == 1 else 'arrays'
+                raise ValueError('FilterSet.submit_dev: %s is None or True (every part allocates its own %s)' % (o.kw, what))
+            if not getattr(self, o.ctor_kw):
+                raise ValueError('%s= needs FilterSet(..., %s=True)' % (o.kw, o.ctor_kw))
+            views[o] = tuple(_OutView(len(self.parts)) for _ in o.shapes(self.flts[0]))
         ts = np.asarray(timestamps, dtype=np.float64)
         out = _OutView(len(self.parts))
-        fsts = _OutView(len(self.parts)) if stats else None
-        if stats:
-            self.last_stats = fsts
-        lms = (_OutView(len(self.parts)), _OutView(len(self.parts))) if landmarks else None
-        if landmarks:
-            self.last_landmarks = lms
-        covs = _OutView(len(self.parts)) if cov else None
-        if cov:
-            self.last_cov = covs
+        for o, v in views.items():
+            setattr(self, o.last, v[0] if len(v) == 1 else v)
         for p, (lo, hi) in enumerate(self.parts):
             def job(p=p, t=np.ascontiguousarray(ts[lo:hi])):
                 w = self.es.pipes[p]
                 ms = N.current_stream()                      # the part's front-end stream: the message is copied behind its step
                 with torch.cuda.stream(w.fstream):
-                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, cov=cov, landmarks=landmarks, stats=stats)
-                    if stats:
-                        fsts.parts[p] = self.flts[p].last_stats
-                    if landmarks:
-                        lms[0].parts[p], lms[1].parts[p] = self.flts[p].last_landmarks
-                    if cov:
-                        covs.parts[p] = self.flts[p].last_cov
+                    out.parts[p] = self.flts[p].submit_dev(self.es.engs[p], t, msg_stream=ms, **asked)
+                    for o, v in views.items():
+                        last = getattr(self.flts[p], o.last)
+                        for view, arr in zip(v, (last,) if len(v) == 1 else last):
+                            view.parts[p] = arr
             self.es.pipes[p].put(job)
         return out
 
