@@ -200,7 +200,7 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
 /* AV_FE_RANSAC: two-point RANSAC outlier rejection between the stereo re-match and the re-binning of the tracked features (the
  * step feature_tracker.py:135-136 leaves empty: both inlier vectors are all ones there).  A tracked feature survives iff its cam0
  * problem and its cam1 problem (av_two_point_ransac below: previous / current points of that camera, cam*_R_p_c of
- * imu_processor.py:28-67) both mark it; a rejected feature is absent from the published message and from the FAST mask.  Without
+ * imu_processor.py:28-67) both mark it; a rejected feature is absent from the published message and keeps no new corner away.  Without
  * the flag the step enqueues exactly what it always did.  Needs grid_num * grid_max <= AV_RANSAC_MAX_PAIRS. */
 #define AV_FE_RANSAC 2
 /* AV_FE_CLAHE: every frame of both cameras goes through av_clahe (below; clahe_clip_limit, clahe_tiles_x / _y of the configuration)
@@ -247,7 +247,7 @@ int av_frontend_push_imu_batch(av_frontend* fe, const int32_t* stream_idx, const
  * for both cameras.  Distortion coefficients, extrinsics, R0to1 and E are unchanged; stereo_threshold, ransac_threshold, fast_threshold,
  * the grid, lk_win and max_corners apply to the binned image as they stand.  Order of the input stage: raw frame -> conversion to grey
  * (pixel_format other than AV_PIX_GRAY8) -> binning -> CLAHE (AV_FE_CLAHE, at the binned size) -> pyramids / LK / FAST.  Everything past
- * the stage is sized by w x h: pyramids, FAST mask, cell lists, raster bits, the engine-owned level 0 ([3][n_streams][w * h], which
+ * the stage is sized by w x h: pyramids, tile and cell lists, raster bits, the engine-owned level 0 ([3][n_streams][w * h], which
  * binning always uses) and the frame store's entries.  Only the entry points' image arguments (img_stride >= width * height * bytes per
  * pixel), the staging slots of av_frontend_step_host and the pinned ring and device staging of av_frontend_frames_upload are sized by
  * the input.  With AV_PIX_GRAY8 the binning reads the caller's (or the staging slot's) frames directly; with any other format the

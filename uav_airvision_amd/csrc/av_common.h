@@ -62,15 +62,6 @@ AV_HD inline uint32_t av_ransac_hash_inl(uint32_t seed, uint32_t frame, uint32_t
 }
 
 #ifdef __HIPCC__
-// 7x7 box of the FAST mask around (int)p with numpy slice semantics (feature_adder.py:59-62): element j of the box
-__device__ __forceinline__ void av_mask_box(uint8_t* m, int w, int h, float px, float py, int j, uint8_t val)
-{
-    int fx = (int)px, fy = (int)py;
-    if (fx < 3 || fy < 3) return;                 // negative slice start => empty slice
-    int yy = fy - 3 + j / 7, xx = fx - 3 + j % 7;
-    if (yy < h && xx < w) m[(size_t)yy * w + xx] = val;
-}
-
 // cv::borderInterpolate(p, len, BORDER_REFLECT_101) for |overshoot| < len
 __device__ __forceinline__ int av_reflect101(int p, int len)
 {
@@ -276,6 +267,7 @@ int av_launch_lk(const ImgView& I, const ImgView& J, int n_set, const PyrGeom& g
                  const LKParams& p, hipStream_t st, const int* index = nullptr);
 
 // fast.hip
+constexpr int AV_FAST_TW = 64, AV_FAST_TH = 48;                      // the detector's tile: tile (x / TW, y / TH), row-major, holds pixel (x, y)
 void av_fast_tiles(int w, int h, int* tiles, int* tile_cap);         // tile count of a w x h image, entries per tile list
 // scans src.img in place, or -- src.img null -- the interior of level 0 of src.pyr with its AV_PYR_BORDER-pixel frame (g: its geometry;
 // may be null when src.img is given); image i of the launch is storage entry src.map[i] of the image, the mask and the lists
@@ -287,13 +279,12 @@ int av_launch_fast(const ImgView& src, const PyrGeom* g, const uint8_t* mask, in
                    int* overflow, int stat_stride, hipStream_t st);
 
 // ransac.hip: the engine's outlier-rejection stage (AV_FE_RANSAC), one single-wavefront workgroup per stream: both camera problems,
-// ordered compaction of cur_* to the survivors, cur_count, counts[s][4], then the FAST mask boxes of the survivors
+// ordered compaction of cur_* to the survivors, cur_count, counts[s][4]
 struct RansacStage {
-    int S, NT, MAXF, w, h;
+    int S, NT, MAXF;
     CamModel cam[2];
     const float* prev_p0; const float* prev_p1;      // the previous grid [S][MAXF][2]
     long long* cur_id; int* cur_life; float* cur_p0; float* cur_p1; int* cur_cell; const int* cur_src; int* cur_count;
-    uint8_t* mask;
     const double* Rpc;                               // [S][2][9]: cam0_R_p_c, cam1_R_p_c
     const int* frame_no;                             // [S]
     const int* slot_cur;                             // frame-store step: < 0 = the stream idles (null otherwise)

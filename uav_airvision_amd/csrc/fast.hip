@@ -37,7 +37,7 @@
 
 namespace {
 
-constexpr int TW = 64, TH = 48;
+constexpr int TW = AV_FAST_TW, TH = AV_FAST_TH;      // 64 x 48
 constexpr int PW = TW + 8, PH = TH + 8;     // pixel tile: columns x0-4 .. x0+67 (pc = x - x0 + 4), rows y0-4 .. y0+51
 constexpr int PWD = PW / 4;                 // 18 dwords per pixel row
 constexpr int SP = PW, SH = TH + 2;         // score tile: column index = pc (same dword phase as the pixels), row sr = y - y0 + 1

@@ -6,12 +6,12 @@
 //   feature_initializer.py:45-85  first frame: FAST -> stereo match all -> top-3/cell -> ids
 //   feature_tracker.py:74-177     temporal LK, bounds mask, stereo re-match, re-bin, lifetime+1
 //   stereo_matcher.py:33-115      predict -> LK fwd -> LK bwd -> gates (err<3, |dy|<20, bounds, epipolar)
-//   feature_adder.py:52-108       7x7 mask, FAST(mask), top-5/cell, stereo match, top-3/cell, ids
+//   feature_adder.py:52-108       FAST outside the 7x7 boxes of the tracked features, top-5/cell, stereo match, top-3/cell, ids
 //   feature_pruner.py:8-19        per cell keep top-5 by lifetime (stable)
 //   feature_publisher.py:90-121   undistort to normalised coords -> feature_msg
 //
 // The reference runs one stream, one frame at a time, with Python lists of FeatureMetaData.  Here
-// the per-stream state (feature grid, ids, three padded pyramids, FAST mask) lives in HBM for all S
+// the per-stream state (feature grid, ids, three padded pyramids) lives in HBM for all S
 // streams; one call to av_frontend_step enqueues ~15 batched kernels (grid.y or block = stream) and
 // never synchronises with the host.  Frames of one stream are a dependent chain (LK at t needs the
 // points of t-1), streams are independent, so S is the parallel axis that fills 256 CUs.
@@ -21,7 +21,8 @@
 //   * Python's stable `sorted(key=response/lifetime, reverse=True)` -> explicit (key, insertion index)
 //     total orders: FAST candidates by (score desc, raster asc), pruning by (lifetime desc, insertion)
 //   * ids are handed out cell-major, response-descending inside a cell
-//   * the 7x7 FAST mask follows numpy slice semantics (no masking when x<3 or y<3)
+//   * the 7x7 keep-out box of a tracked feature follows numpy slice semantics (no box at all when x<3 or y<3); the
+//     reference paints the boxes into a byte image, select_kernel tests the detector's survivors against the feature list itself
 #include <math.h>
 
 #include <deque>
@@ -60,8 +61,8 @@ struct FeDev {
     // curr_features after the tracker (insertion order)
     long long* cur_id; int* cur_life; float* cur_p0; float* cur_p1; int* cur_cell; int* cur_count;
     int* cur_src;                                         // AV_FE_RANSAC: index of every curr feature in the previous grid (null without the flag)
-    // FAST per-cell lists + mask
-    uint32_t* cell_kp; int* cell_count; uint8_t* mask;
+    // FAST per-cell lists
+    uint32_t* cell_kp; int* cell_count;
     uint32_t* tile_kp; int* tile_count; int n_tiles, tile_cap;      // FAST survivors per detector tile (fast.hip), binned into cells by select_kernel
     // candidates for new features
     uint32_t* cand_key; float* cand_p0; float* cand_init; float* cand_p1; uint8_t* cand_st; float* cand_back; uint8_t* cand_st2;
@@ -83,8 +84,8 @@ __device__ __forceinline__ bool fe_idle(const FeDev& d, int s) { return d.slot_c
 
 // ---- stream restart (include/airvision.h, "Stream restart"; av_frontend_restart; no step launches it): a thread per listed stream puts
 //      its device state back to what av_frontend_create made: the next frame is an initialisation, ids begin again at 0, both grids are
-//      empty, the counters read 0.  The grids' entries, the candidate arrays and the mask need nothing: the counts say how much of them
-//      is read, and finalize_kernel leaves the mask all ones after every step.  rs_counts: AV_FE_RANSAC's per-stream counts (null
+//      empty, the counters read 0.  The grids' entries and the candidate arrays need nothing: the counts say how much of them
+//      is read (the detector's keep-out boxes are rebuilt from curr_features in every step).  rs_counts: AV_FE_RANSAC's per-stream counts (null
 //      without the stage).  (Ahead of the step's kernels in this file, so that each of them keeps its place behind its neighbour in the
 //      code object.)
 __global__ __launch_bounds__(64) void restart_kernel(FeDev d, const int* list, int n, int* rs_counts)
@@ -219,15 +220,9 @@ __global__ __launch_bounds__(256) void track_gate_kernel(FeDev d)
     if (threadIdx.x == 0) { d.sv_count[s] = base; d.counters[s * NCNT + CNT_TRACKED] = base; }
 }
 
-// 7x7 box of the FAST mask with numpy slice semantics (feature_adder.py:59-62)
-__device__ __forceinline__ void mask_box(const FeDev& d, uint8_t* m, float px, float py, int j, uint8_t val)
-{
-    av_mask_box(m, d.w, d.h, px, py, j, val);
-}
-
-// ---- G3: stereo gate of the survivors, re-bin into curr_features, set FAST mask ----------------
-// With AV_FE_RANSAC (d.cur_src set) the features also record where they came from in the previous grid, and the mask is left to
-// the outlier-rejection stage that follows (ransac.hip): it is built from the features that survive it.
+// ---- G3: stereo gate of the survivors, re-bin into curr_features --------------------------------
+// With AV_FE_RANSAC (d.cur_src set) the features also record where they came from in the previous grid, for the outlier-rejection
+// stage that follows (ransac.hip) and compacts curr_features to those that survive it.
 __global__ __launch_bounds__(256) void rebin_kernel(FeDev d, int par)
 {
     __shared__ int lds4[4];
@@ -256,14 +251,6 @@ __global__ __launch_bounds__(256) void rebin_kernel(FeDev d, int par)
         }
     }
     if (threadIdx.x == 0) { d.cur_count[s] = base; d.counters[s * NCNT + CNT_MATCHED] = base; }
-    if (d.cur_src) return;
-    __syncthreads();
-    uint8_t* m = d.mask + (size_t)s * d.w * d.h;
-    for (int q = threadIdx.x; q < base * 49; q += NTB) {
-        int f = q / 49, j = q - f * 49;
-        const size_t o = (size_t)s * d.NT + f;
-        mask_box(d, m, d.cur_p0[2 * o], d.cur_p0[2 * o + 1], j, 0);
-    }
 }
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
@@ -276,15 +263,47 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return v;
 }
 
+// The 7x7 keep-out box of a tracked feature at p, numpy slice semantics (feature_adder.py:59-62): columns int(px) - 3 .. int(px) + 3,
+// rows likewise, cut at the right and bottom border, and NO box when int(px) < 3 or int(py) < 3 (a negative slice start is an empty
+// slice).  f(t, e) is called for every detector tile t the box touches -- at most 2 x 2, a box is smaller than a tile -- with the
+// box's entry in that tile's list: its centre relative to the tile's origin, + 3 so that it is not negative, row << 8 | column.
+template <class F>
+__device__ __forceinline__ void keepout_tiles(const FeDev& d, int ntx, float px, float py, F f)
+{
+    const int fx = (int)px, fy = (int)py;
+    if (fx < 3 || fy < 3) return;
+    const int tx0 = (fx - 3) / AV_FAST_TW, tx1 = (min(fx, d.w - 4) + 3) / AV_FAST_TW;      // (a centre beyond the image, which the tracker's
+    const int ty0 = (fy - 3) / AV_FAST_TH, ty1 = (min(fy, d.h - 4) + 3) / AV_FAST_TH;      //  gate rules out, has first > last: no tile)
+    for (int ty = ty0; ty <= ty1; ++ty)
+        for (int tx = tx0; tx <= tx1; ++tx)
+            f(ty * ntx + tx, (uint16_t)(((fy - ty * AV_FAST_TH + 3) << 8) | (fx - tx * AV_FAST_TW + 3)));
+}
+static_assert(AV_FAST_TW >= 7 && AV_FAST_TH >= 7 && AV_FAST_TW + 6 <= 256 && AV_FAST_TH + 6 <= 256, "a box touches at most 2 x 2 tiles and its entry is two bytes");
+
+// select_kernel's dynamic LDS: three per-cell arrays, one word per detector tile and the box lists, two bytes an entry and at most
+// four entries a tracked feature (NT < 4,096: below 32 KB, 2.4 KB at 300 features).  A tile's word holds the detector's count of the
+// tile in its low half and the end of the tile's box list in its high half: a count is at most a quarter of a tile's pixels, an end
+// at most 4 NT < 2^14.  (A word each would not fit beside the lists for the largest image with the largest grid.)
+size_t select_lds_bytes(const FeDev& d)
+{
+    return sizeof(int) * (size_t)(3 * d.C + 1 + d.n_tiles + 1) + sizeof(uint16_t) * 4 * (size_t)d.NT;
+}
+static_assert(AV_FAST_TW * AV_FAST_TH / 4 < 65536, "a tile's survivor count fits the low half of its word");
+
 // ---- G5: per-cell top-grid_max FAST candidates (feature_adder.py:66-80) or all of them on the
 //          first frame (feature_initializer.py:52-55), plus their stereo initial guess ----------
+// The reference's detector drops the keypoints on a pixel inside a tracked feature's 7x7 box AFTER the non-max suppression (fast.hip
+// header), reading a byte image the boxes were painted into.  Here no such image exists: the workgroup sorts the boxes of its
+// stream's curr_features (after the outlier rejection, where that stage runs) into per-tile lists in LDS, and a survivor of detector
+// tile t is tested against the few boxes that touch t.  The answer is a boolean, so the order of a list does not matter.
 __global__ __launch_bounds__(256) void select_kernel(FeDev d)
 {
     extern __shared__ int sm[];
     int* cnt = sm;               // [C]
     int* off = sm + d.C;         // [C+1]
     int* ccnt = off + d.C + 1;   // [C]   FAST keypoints per cell
-    int* tpre = ccnt + d.C;      // [n_tiles + 1] prefix of the detector's per-tile counts
+    int* tile = ccnt + d.C;      // [n_tiles + 1] per detector tile: its survivor count | end of its box list << 16 (the list begins where the tile before ends)
+    uint16_t* box = reinterpret_cast<uint16_t*>(tile + d.n_tiles + 1);           // [4 NT] the box lists, tile after tile
     const int s = blockIdx.x;
     if (fe_idle(d, s)) return;
     const int ts = d.slot_cur ? d.slot_cur[s] : s;              // storage entry of this frame's FAST lists
@@ -292,40 +311,70 @@ __global__ __launch_bounds__(256) void select_kernel(FeDev d)
     // bin the detector's per-tile survivor lists into the per-cell lists (feature_adder.py:66-71: row = y / grid_height,
     // col = x / grid_width).  The cell lists are unordered; everything below orders by (response, raster) key.
     // Dense mapping, no search: slot j of a chunk is entry (j % BK) + kb of tile j / BK; a round issues BU independent loads
-    // per thread (list word, then its mask byte) -- this loop is a chain of memory round trips, not work.
+    // per thread (the list words); the box test and the binning of a word then run out of LDS.
     {
         __shared__ int tmax;
-        const int nt = d.n_tiles;
+        const int nt = d.n_tiles, ntx = (d.w + AV_FAST_TW - 1) / AV_FAST_TW;
         const uint32_t rmask = (1u << d.rbits) - 1u;
         constexpr int BK = 32, BU = 5;
         if (threadIdx.x == 0) tmax = 0;
         for (int c = threadIdx.x; c < d.C; c += NTB) ccnt[c] = 0;
-        __syncthreads();
         int mx = 0;
-        for (int t = threadIdx.x; t < nt; t += NTB) { const int n = d.tile_count[(size_t)ts * nt + t]; tpre[t] = n; mx = max(mx, n); }
+        for (int t = threadIdx.x; t < nt; t += NTB) { const int n = d.tile_count[(size_t)ts * nt + t]; tile[t] = n; mx = max(mx, n); }
+        __syncthreads();
         if (mx > 0) atomicMax(&tmax, mx);
+        // the box lists, a counting sort by tile: count, exclusive prefix (one wavefront), fill -- a tile's cursor ends at its list's end.
+        // Nothing tracked (first frame, everything lost): every list is empty.
+        const int nf = min(d.cur_count[s], d.NT);
+        const float* fp = d.cur_p0 + 2 * (size_t)s * d.NT;
+        if (nf > 0) {
+            for (int i = threadIdx.x; i < nf; i += NTB)
+                keepout_tiles(d, ntx, fp[2 * i], fp[2 * i + 1], [&](int t, uint16_t) { atomicAdd(&tile[t], 1 << 16); });
+            __syncthreads();
+            if (threadIdx.x < 64) {
+                const int lane = threadIdx.x;
+                int carry = 0;
+                for (int t0 = 0; t0 < nt; t0 += 64) {
+                    const int t = t0 + lane, w = t < nt ? tile[t] : 0, v = w >> 16;
+                    int incl = v;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
+                    if (t < nt) tile[t] = (w & 0xFFFF) | ((carry + incl - v) << 16);
+                    carry += __shfl(incl, 63, 64);
+                }
+            }
+            __syncthreads();
+            for (int i = threadIdx.x; i < nf; i += NTB)
+                keepout_tiles(d, ntx, fp[2 * i], fp[2 * i + 1], [&](int t, uint16_t e) { box[atomicAdd(&tile[t], 1 << 16) >> 16] = e; });
+        }
         __syncthreads();
         const int maxcount = tmax;
         for (int kb = 0; kb < maxcount; kb += BK)
             for (int j0 = threadIdx.x; j0 < nt * BK; j0 += NTB * BU) {
-                uint32_t word[BU]; int x[BU], y[BU]; bool ok[BU]; uint8_t mk[BU];
+                uint32_t word[BU]; int x[BU], y[BU]; bool ok[BU];
 #pragma unroll
                 for (int u = 0; u < BU; ++u) {
                     const int j = j0 + NTB * u, t = j / BK, k = kb + (j % BK);
-                    ok[u] = j < nt * BK && k < tpre[min(t, nt - 1)];
+                    ok[u] = j < nt * BK && k < (tile[min(t, nt - 1)] & 0xFFFF);
                     word[u] = ok[u] ? d.tile_kp[((size_t)ts * nt + t) * d.tile_cap + k] : 0u;
                 }
 #pragma unroll
                 for (int u = 0; u < BU; ++u) {
                     const uint32_t raster = rmask - (word[u] & rmask);
                     y[u] = (int)(raster / (uint32_t)d.w); x[u] = (int)(raster % (uint32_t)d.w);
-                    // detect(img, mask) drops keypoints on masked pixels AFTER the non-max suppression (fast.hip header): the mask
-                    // byte is read here, for the few thousand survivors, instead of for every pixel inside the detector
-                    mk[u] = ok[u] ? d.mask[(size_t)s * d.w * d.h + (size_t)y[u] * d.w + x[u]] : (uint8_t)0;
                 }
 #pragma unroll
                 for (int u = 0; u < BU; ++u) {
-                    if (!ok[u] || mk[u] == 0) continue;
+                    if (!ok[u]) continue;
+                    // inside a box of the survivor's own tile t (tiles are row-major, fast.hip)?  |x - fx| <= 3 and |y - fy| <= 3
+                    const int t = (j0 + NTB * u) / BK;
+                    const int sx = x[u] % AV_FAST_TW + 6, sy = y[u] % AV_FAST_TH + 6;
+                    bool inside = false;
+                    for (int q = t ? tile[t - 1] >> 16 : 0, qe = tile[t] >> 16; q < qe; ++q) {
+                        const int e = box[q];
+                        inside |= (unsigned)(sx - (e & 0xFF)) <= 6u && (unsigned)(sy - (e >> 8)) <= 6u;
+                    }
+                    if (inside) continue;
                     const int cell = (y[u] / d.gh) * d.grid_col + x[u] / d.gw;
                     const int idx = atomicAdd(&ccnt[cell], 1);
                     if (idx < d.cell_cap) d.cell_kp[((size_t)s * d.C + cell) * d.cell_cap + idx] = word[u];
@@ -465,7 +514,7 @@ __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* k, int n)
     __syncthreads();
 }
 
-// ---- G7: new-feature selection + ids, prune, publish, mask restore ------------------------------
+// ---- G7: new-feature selection + ids, prune, publish --------------------------------------------
 //  feature_adder.py:82-108 / feature_initializer.py:57-85, feature_pruner.py:8-19,
 //  feature_publisher.py:90-121, pipeline.py:145-148
 __global__ __launch_bounds__(256) void finalize_kernel(FeDev d, int par)
@@ -600,13 +649,6 @@ __global__ __launch_bounds__(256) void finalize_kernel(FeDev d, int par)
         d.out_ids[o] = d.feat_id[nxt][o];
         d.out_uv[4 * o] = u0; d.out_uv[4 * o + 1] = v0;
         d.out_uv[4 * o + 2] = (double)(float)u1; d.out_uv[4 * o + 3] = (double)(float)v1;
-    }
-    // restore the FAST mask to all ones
-    uint8_t* m = d.mask + (size_t)s * d.w * d.h;
-    for (int q = threadIdx.x; q < T * 49; q += NTB) {
-        int f = q / 49, j = q - f * 49;
-        const size_t o = (size_t)s * d.NT + f;
-        mask_box(d, m, d.cur_p0[2 * o], d.cur_p0[2 * o + 1], j, 1);
     }
     if (threadIdx.x == 0) {
         d.n_feat[nxt][s] = n_out;
@@ -1011,7 +1053,7 @@ int step_impl(av_frontend* fe, const uint8_t* img0, const uint8_t* img1, int64_t
         if ((rc = av_launch_fast(cur0, &fe->geom, d.smask0, 0, S, d.w, d.h, fe->cfg.fast_threshold, d.rbits, nullptr, nullptr, 0, d.tile_kp, d.tile_count, d.counters + CNT_OVF, NCNT, st))) return rc;
     }
     { Span sp(fe, 3, st);
-      hipLaunchKernelGGL(select_kernel, dim3(S), dim3(256), sizeof(int) * (3 * d.C + 1 + d.n_tiles + 1), st, d);
+      hipLaunchKernelGGL(select_kernel, dim3(S), dim3(256), select_lds_bytes(d), st, d);
       AV_LAUNCH_CHECK(); }
     const int r1_launch = any_first ? d.CC : d.C * (d.gmax < CAND_R1 ? d.gmax : CAND_R1);
     if ((rc = lk_pair(cur0, cur1, d.cand_p0, d.cand_p1, d.cand_st, d.cand_back, d.cand_st2, d.r1_count, d.CC, r1_launch, d.r1_list))) return rc;
@@ -1136,12 +1178,13 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
     A(d.cur_id, S * d.NT) A(d.cur_life, S * d.NT) A(d.cur_p0, 2 * S * d.NT) A(d.cur_p1, 2 * S * d.NT) A(d.cur_cell, S * d.NT)
     A(d.cell_kp, (size_t)S * C * d.cell_cap)
     av_fast_tiles(w, h, &d.n_tiles, &d.tile_cap);
-    if (sizeof(int) * (size_t)(3 * C + 1 + d.n_tiles + 1) + 64 > 64 * 1024) {      // select_kernel's LDS; not reached by an image every pyramid level of which is > 16 pixels high
-        av_set_error("av_frontend_create: %d x %d has %d detector tiles, more than the selection kernel's LDS holds", w, h, d.n_tiles);
+    // select_kernel's LDS: a word per tile and the box lists (below 32 KB: NT < 4,096, checked above).  2^24 pixels in whole tiles are some 5,500
+    // tiles, 22 KB, and the per-cell arrays 3 KB at most: only a strip a few rows high, all partial tiles, with thousands of features gets here.
+    if (select_lds_bytes(d) + 64 > 64 * 1024) {
+        av_set_error("av_frontend_create: %d x %d has %d detector tiles, with %d features more than the selection kernel's LDS holds", w, h, d.n_tiles, d.NT);
         av_frontend_destroy(fe); return AV_E_INVALID;
     }
     A(d.tile_kp, (size_t)S * d.n_tiles * d.tile_cap) A(d.tile_count, (size_t)S * d.n_tiles)
-    if ((rc = fe->res.dev(&d.mask, (size_t)S * w * h, 1))) { av_frontend_destroy(fe); return rc; }
     A(d.cand_key, (size_t)S * d.CC) A(d.cand_p0, 2 * (size_t)S * d.CC) A(d.cand_init, 2 * (size_t)S * d.CC) A(d.cand_p1, 2 * (size_t)S * d.CC)
     A(d.cand_st, (size_t)S * d.CC) A(d.cand_back, 2 * (size_t)S * d.CC) A(d.cand_st2, (size_t)S * d.CC) A(d.cand_inl, (size_t)S * d.CC)
     A(d.cand_off, S * (C + 1))
@@ -1161,9 +1204,9 @@ AV_EXPORT int av_frontend_create(const av_frontend_config* cfg, int n_streams, i
         A(d.cur_src, S * d.NT) A(fe->rs_counts, 4 * S)
         RansacStage& a = fe->rs;
         memset(&a, 0, sizeof(a));
-        a.S = S; a.NT = d.NT; a.MAXF = d.MAXF; a.w = w; a.h = h; a.cam[0] = d.cam0; a.cam[1] = d.cam1;
+        a.S = S; a.NT = d.NT; a.MAXF = d.MAXF; a.cam[0] = d.cam0; a.cam[1] = d.cam1;
         a.cur_id = d.cur_id; a.cur_life = d.cur_life; a.cur_p0 = d.cur_p0; a.cur_p1 = d.cur_p1; a.cur_cell = d.cur_cell; a.cur_src = d.cur_src;
-        a.cur_count = d.cur_count; a.mask = d.mask; a.counts = fe->rs_counts;
+        a.cur_count = d.cur_count; a.counts = fe->rs_counts;
         a.Rpc = fe->dH + (size_t)10 * S; a.frame_no = reinterpret_cast<const int*>(fe->dH + (size_t)28 * S);
         a.thr = cfg->ransac_threshold; a.N = rs_N; a.seed = cfg->ransac_seed;
         fe->ransac = true;

@@ -240,16 +240,10 @@ __global__ __launch_bounds__(64, 5) void ransac_stage_kernel(RansacStage a)
         base += __popcll(b);
         __syncthreads();
     }
+    // (the detector's keep-out boxes are those of curr_features after the rejection, feature_adder.py:59-62: select_kernel reads this list)
     if (lane == 0) {
         a.cur_count[s] = base;
         counts[0] = base; counts[1] = set0; counts[2] = set1; counts[3] = path;
-    }
-    __syncthreads();
-    // the FAST mask is built from curr_features, i.e. after the rejection (feature_adder.py:59-62)
-    uint8_t* mk = a.mask + (size_t)s * a.w * a.h;
-    for (int q = lane; q < base * 49; q += 64) {
-        const int f = q / 49, j = q - f * 49;
-        av_mask_box(mk, a.w, a.h, a.cur_p0[2 * (cb + f)], a.cur_p0[2 * (cb + f) + 1], j, 0);
     }
 }
 
