@@ -1050,6 +1050,41 @@ typedef struct av_update_stats {
 typedef struct av_filter_stats { av_update_stats upd[2]; } av_filter_stats;
 int  av_msckf_batch_set_stats(av_msckf_batch* b, int enable);
 int  av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host);
+/* IMU-rate odometry: the state after every IMU sample the step's prediction integrated, per stream and step, riding the step's read-back.
+ * The published pose comes once per camera frame; these come at the rate of the IMU, for a control loop, for motion compensation of a
+ * lidar or an event camera, for a comparison with a 200 Hz ground truth.  Off by default.  On, every step yields for every stream a count
+ * pair n[s][2] = (had, written) and up to `cap` records av_imu_state of AV_IMU_STATE_BYTES = 112 bytes.  Record k describes the k-th IMU
+ * sample the prediction of THIS step integrated for the stream -- the samples with imu_state.timestamp <= t <= frame time, in order
+ * (batch_imu_processing, msckf.py:251-273):
+ *   t        the sample's time stamp
+ *   p, q, v  position, orientation (JPL xyzw) and velocity right after predict_new_state (msckf.py:341-388) for that sample: exactly the
+ *            doubles the filter holds then, in the filter's own frame and conventions, the same as the published twelve
+ *   w        the bias-corrected angular rate the sample was integrated with, gyro - gyro_bias, in the IMU frame
+ * The records are PREDICTIONS from the previous step's updated state: no measurement update lies between them.  The correction of this
+ * step's updates shows as the difference between the last record (the sample at or just before the frame time) and the step's
+ * published pose; a consumer that wants a continuous trajectory splices records and published poses in time order.
+ * Counts: had = samples integrated, written = min(had, cap).  On overflow the LAST cap samples are kept, in time order, so the record at
+ * the frame's time always survives; records past `written` are unspecified.  A sample that repeats its predecessor's stamp (dt = 0)
+ * still gets a record.  A stream with nothing to integrate in this step has n = {0, 0}: inactive, no frame, failed or stopped, its
+ * window full, or before its gravity initialisation.  A stream that stops DURING a step (a capacity limit met by one of its updates)
+ * still has that step's records: the prediction ran before the limit was met; from the next step on it reads {0, 0}.
+ * av_msckf_batch_set_imu_rate(b, cap): cap records per stream and step, 0 = off, at most 4096 (AV_E_INVALID outside 0 .. 4096); before
+ * the batch's first step (AV_E_INVALID afterwards).  Off, the step launches and reads back exactly what it did without the feature; on,
+ * one small kernel behind the first kernel of the step gathers the records from what that kernel leaves for the covariance propagation
+ * (one launch more; no kernel of the step changes) and two more asynchronous copies bring records and counts to pinned buffers of the
+ * step's ring slot: no wait and no allocation inside a step.  The records are the same bytes at every launch shape of the step.  The
+ * whole n_streams * cap * 112-byte buffer is copied whatever the counts are.  Device-resident filter only: under AV_MSCKF_STORE=host a non-zero cap is
+ * AV_E_INVALID, with a text that names AV_MSCKF_STORE.
+ * av_msckf_batch_next_imu_rate(b, rec, n): hands over the destination -- n_streams * cap records and n_streams * 2 counts -- of the NEXT
+ * av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps
+ * its own destination.  Stream groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination
+ * computes its records and drops them.
+ * Known limits: no propagation past the frame time through samples the filter has not consumed yet ("pose now"); no covariance per
+ * record; no biases in the record; records arrive with the step's read-back, not earlier; nothing on the host-bookkeeping path. */
+#define AV_IMU_STATE_BYTES 112
+typedef struct av_imu_state { double t, p[3], q[4], v[3], w[3]; } av_imu_state;
+int  av_msckf_batch_set_imu_rate(av_msckf_batch* b, int cap);
+int  av_msckf_batch_next_imu_rate(av_msckf_batch* b, av_imu_state* rec, int32_t* n);
 int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);     /* [state dim, camera states, map features] */
 /* Full host-side state of one stream -- every target of measurement_update's injection (msckf.py:568-595), for parity tests
  * (SURVEY 8b get_state): imu32 = [imu_state.timestamp, orientation q(4, JPL xyzw), position(3), velocity(3), gyro_bias(3),
@@ -1079,7 +1114,7 @@ int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* st
  *                  the failure code and text (av_msckf_batch_stream_status reads 0, ""); the parity-test tap's captures.
  *   Reset, device: the IMU state record, state dimension 21, no camera states, the stream's whole covariance region (create-time
  *                  diagonal, zero elsewhere), the observation store (empty, insertion counter 0, header clear, arrays as allocated), the
- *                  stream's rows of the pose, odometry-covariance, landmark and statistics buffers.  Camera-state ids and the map's
+ *                  stream's rows of the pose, odometry-covariance, landmark, statistics and IMU-rate buffers.  Camera-state ids and the map's
  *                  insertion order begin again at 0.
  *   Not reset:     av_msckf_batch_counters and av_msckf_batch_work keep accumulating over all lives; the batch's configuration, its
  *                  output switches and capacities; every other stream.
@@ -1172,6 +1207,15 @@ int  av_msckf_predict_ops_dev(av_msckf* ctx, int n_streams, int wg, int cam_stri
                               const double* imu, int n_imu, const double noise4[4],
                               double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
                               int32_t* redundant_out, void* stream);
+/* The same entry with the IMU-rate odometry on (tests only): the launch sequence is then the one a step begins with when
+ * av_msckf_batch_set_imu_rate is on, the record kernel behind the state kernel.  cap = 1 .. 4096 records per stream; rec_out[n_streams][cap] and n_out[n_streams][2] are HOST
+ * arrays, uploaded as the caller filled them (a pre-fill shows what the kernel did not write) and read back.  Everything else, and
+ * every result the two entries share, is as above. */
+int  av_msckf_predict_ops_dev_rate(av_msckf* ctx, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
+                                   double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
+                                   const double* imu, int n_imu, const double noise4[4],
+                                   double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
+                                   int32_t* redundant_out, void* stream, int cap, av_imu_state* rec_out, int32_t* n_out);
 /* Work done so far, for the filter stage's roofline (drain first): out8 = [algorithmic fp64 flops of the gating tests
  * (per feature with r = 4M-3 rows, n columns: 2rn^2 + 2r^2n + r^3/3; msckf.py:604-612), of the measurement updates on the
  * k = min(m, n) rows kept (S 2kn^2 + 2k^2n, Cholesky k^3/3, solve 2k^2n, (I-KH)P 4kn^2; msckf.py:562-602), of the reference's

@@ -187,6 +187,10 @@ class Landmark(C.Structure):                     # av_landmark (AV_LANDMARK_BYTE
     _fields_ = [('id', C.c_int64), ('p', C.c_double * 3), ('flags', C.c_int32), ('n_obs', C.c_int32)]
 
 
+class ImuState(C.Structure):                     # av_imu_state (AV_IMU_STATE_BYTES = 112)
+    _fields_ = [('t', C.c_double), ('p', C.c_double * 3), ('q', C.c_double * 4), ('v', C.c_double * 3), ('w', C.c_double * 3)]
+
+
 class UpdateStats(C.Structure):                  # av_update_stats (64 bytes)
     _fields_ = [(n, C.c_int32) for n in ('n_cand', 'n_pos', 'n_eval', 'n_pass', 'dof_eval', 'dof_pass', 'rows', 'flags')] + \
                [(n, C.c_double) for n in ('gamma_eval', 'gamma_pass', 'dx_pos', 'dx_rot')]
@@ -279,6 +283,8 @@ SIGNATURES = {
     'av_msckf_batch_next_landmarks': (C.c_int, [_P, _P, _P]),
     'av_msckf_batch_set_stats': (C.c_int, [_P, C.c_int]),
     'av_msckf_batch_next_stats': (C.c_int, [_P, _P]),
+    'av_msckf_batch_set_imu_rate': (C.c_int, [_P, C.c_int]),
+    'av_msckf_batch_next_imu_rate': (C.c_int, [_P, _P, _P]),
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_msckf_batch_launch_shape': (C.c_int, [_P, C.POINTER(C.c_int32 * 17)]),
@@ -302,6 +308,8 @@ SIGNATURES = {
     'av_msckf_feature_ops_dev': (C.c_int, [_P] + [C.c_int] * 7 + [_P] * 14 +[C.c_int, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                            _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     'av_msckf_predict_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6),
+    'av_msckf_predict_ops_dev_rate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6 +
+                                      [C.c_int, _P, _P]),
     'av_msckf_batch_work': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 8)]),
     'av_msckf_batch_work_executed': (C.c_int, [_P, C.POINTER(C.c_double * 2)]),
     'av_debug_live_resources': (C.c_int, [C.POINTER(C.c_int64 * 4)]),

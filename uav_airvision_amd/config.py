@@ -169,3 +169,7 @@ class ConfigEuRoC(object):
         # no reference counterpart: the drop-in MSCKF keeps the innovation statistics of its last feature_callback in `last_innovation`
         # (msckf_ops.FILTER_STATS_DTYPE[2]: the lost-feature and the pruning update; include/airvision.h, "Innovation statistics")
         self.publish_innovation = False
+        # no reference counterpart: the drop-in MSCKF keeps the IMU-rate records of its last feature_callback in `last_imu_states` (the
+        # state after every IMU sample of the frame, the last imu_rate_cap of them; include/airvision.h, "IMU-rate odometry")
+        self.publish_imu_rate = False
+        self.imu_rate_cap = 32

@@ -2019,6 +2019,9 @@ static_assert(LM_USED == AV_LM_USED && LM_REJECTED == AV_LM_REJECTED && LM_TRACK
 static_assert(sizeof(av_update_stats) == 64 && sizeof(av_filter_stats) == AV_FILTER_STATS_BYTES && sizeof(DUpdStats) == sizeof(av_update_stats), "av_filter_stats layout");
 static_assert(offsetof(av_update_stats, gamma_eval) == offsetof(DUpdStats, gamma_eval) && offsetof(av_update_stats, dx_rot) == offsetof(DUpdStats, dx_rot) && offsetof(av_update_stats, flags) == offsetof(DUpdStats, flags), "av_update_stats fields");
 static_assert(FS_RAN == AV_FS_RAN && FS_CUT == AV_FS_CUT, "AV_FS_* bits");
+static_assert(sizeof(av_imu_state) == AV_IMU_STATE_BYTES && sizeof(DImuState) == AV_IMU_STATE_BYTES, "av_imu_state layout");
+static_assert(offsetof(av_imu_state, p) == offsetof(DImuState, p) && offsetof(av_imu_state, q) == offsetof(DImuState, q) && offsetof(av_imu_state, v) == offsetof(DImuState, v) && offsetof(av_imu_state, w) == offsetof(DImuState, w), "av_imu_state fields");
+constexpr int IMU_RATE_CAP_MAX = 4096;
 
 namespace {
 
@@ -2063,6 +2066,8 @@ AV_EXPORT int av_msckf_batch_set_landmarks(av_msckf_batch* b, int cap) { return 
 AV_EXPORT int av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t* n) { return batch_next_out(b, F_LM, {rec, n}); }
 AV_EXPORT int av_msckf_batch_set_stats(av_msckf_batch* b, int enable) { return batch_set_out(b, F_STATS, enable != 0); }
 AV_EXPORT int av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host) { return batch_next_out(b, F_STATS, {rec_host}); }
+AV_EXPORT int av_msckf_batch_set_imu_rate(av_msckf_batch* b, int cap) { return batch_set_out(b, F_IR, cap, cap >= 0 && cap <= IMU_RATE_CAP_MAX); }
+AV_EXPORT int av_msckf_batch_next_imu_rate(av_msckf_batch* b, av_imu_state* rec, int32_t* n) { return batch_next_out(b, F_IR, {rec, n}); }
 
 AV_EXPORT int av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, int n, void* stream)
 {
@@ -2229,14 +2234,17 @@ AV_EXPORT int av_msckf_feature_ops_dev(av_msckf* c, int n_streams, int fs_stride
 //   imu[7]          t, w[3], a[3] per sample
 //   redundant_out[2] the two positions of the redundancy rule, -1 where it was not asked for
 // Every argument is checked before anything is launched: no input can send a kernel out of bounds.  Synchronises.
-AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
-                                       double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
-                                       const double* imu, int n_imu, const double* noise4,
-                                       double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
-                                       int32_t* redundant_out, void* stream)
+// cap > 0 (av_msckf_predict_ops_dev_rate): dev_launch_predict also launches the IMU-rate record kernel; rec_out [S][cap] and n_out [S][2]
+// go to the device as the caller filled them and come back as the kernel left them.
+static int predict_ops_dev_body(av_msckf* c, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
+                                double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
+                                const double* imu, int n_imu, const double* noise4,
+                                double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
+                                int32_t* redundant_out, void* stream, int cap, av_imu_state* rec_out, int32_t* n_out)
 {
     constexpr int SD = 43, SI = 6, CI = 6;
-    if (!c || n_streams < 1 || n_streams > 65536 || (wg != 64 && wg != 256) || cam_stride < 1 || cam_stride > 64 || n_imu < 0 || (n_imu > 0 && !imu) ||
+    if (cap < 0 || cap > IMU_RATE_CAP_MAX || (cap > 0 && (!rec_out || !n_out)) ||
+        !c || n_streams < 1 || n_streams > 65536 || (wg != 64 && wg != 256) || cam_stride < 1 || cam_stride > 64 || n_imu < 0 || (n_imu > 0 && !imu) ||
         !state_io || !state_int_io || !t_frame || !ctl || !noise4 || !cam_q_dev || !cam_p_dev || !cam_qn_dev || !P_dev || !redundant_out ||
         ld < IMU_DIM + 6 * cam_stride || p_stride < (int64_t)ld * ld) {
         av_set_error("av_msckf_predict_ops_dev: bad arguments");
@@ -2271,7 +2279,8 @@ AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int c
     const size_t o_st = ar.take(sizeof(DState) * S), o_ctl = ar.take(sizeof(DCtl) * S), o_imu = ar.take(sizeof(DImu) * nimu), o_prop = ar.take(sizeof(PropArgs) * nimu),
                  o_cov = ar.take(sizeof(DCov) * S), o_cnt = ar.take(sizeof(int) * 16), o_id = ar.take(sizeof(long long) * ncs), o_nc = ar.take(sizeof(int) * S),
                  o_ns = ar.take(sizeof(int) * S), o_gr = ar.take(sizeof(double) * 3 * S), o_ops = ar.take(sizeof(int) * S), o_rm = ar.take(sizeof(int) * 2 * S),
-                 o_red = ar.take(sizeof(int) * 2 * S), o_scr = ar.take(any_ops ? sizeof(double) * (size_t)p_stride * S : 8);
+                 o_red = ar.take(sizeof(int) * 2 * S), o_scr = ar.take(any_ops ? sizeof(double) * (size_t)p_stride * S : 8),
+                 o_ir = ar.take(sizeof(DImuState) * S * (size_t)(cap > 0 ? cap : 1)), o_irn = ar.take(sizeof(int) * 2 * S);
     { const int rca = ar.mem.alloc(ar.used); if (rca) return rca; }
     ar.p = static_cast<char*>(ar.mem.p);
     std::vector<DState> st((size_t)S); std::vector<DCtl> ct((size_t)S); std::vector<DImu> im(nimu);
@@ -2304,8 +2313,18 @@ AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int c
     AV_HIP(hipMemcpyAsync(ar.p + o_ops, ops.data(), sizeof(int) * S, hipMemcpyHostToDevice, stm));
     AV_HIP(hipMemcpyAsync(ar.p + o_rm, rm.data(), sizeof(int) * 2 * S, hipMemcpyHostToDevice, stm));
     AV_HIP(hipMemcpyAsync(ar.p + o_red, red.data(), sizeof(int) * 2 * S, hipMemcpyHostToDevice, stm));
-    dev_launch_predict(a, S, wg, false, stm);
+    IrOut ir{};
+    if (cap > 0) {
+        ir = IrOut{(DImuState*)(ar.p + o_ir), (int*)(ar.p + o_irn), cap};
+        AV_HIP(hipMemcpyAsync(ir.rec, rec_out, sizeof(DImuState) * S * (size_t)cap, hipMemcpyHostToDevice, stm));
+        AV_HIP(hipMemcpyAsync(ir.n, n_out, sizeof(int) * 2 * S, hipMemcpyHostToDevice, stm));
+    }
+    dev_launch_predict(a, S, wg, false, stm, ir);
     AV_LAUNCH_CHECK();
+    if (cap > 0) {
+        AV_HIP(hipMemcpyAsync(rec_out, ir.rec, sizeof(DImuState) * S * (size_t)cap, hipMemcpyDeviceToHost, stm));
+        AV_HIP(hipMemcpyAsync(n_out, ir.n, sizeof(int) * 2 * S, hipMemcpyDeviceToHost, stm));
+    }
     if (any_ops) {
         hipLaunchKernelGGL(dk_prune_probe, dim3(S), dim3(wg), 0, stm, a, (const int*)(ar.p + o_ops), (const int*)(ar.p + o_rm), (int*)(ar.p + o_red));
         AV_LAUNCH_CHECK();
@@ -2324,6 +2343,27 @@ AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int c
         redundant_out[2 * s] = red[2 * s]; redundant_out[2 * s + 1] = red[2 * s + 1];
     }
     return AV_OK;
+}
+AV_EXPORT int av_msckf_predict_ops_dev(av_msckf* c, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
+                                       double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
+                                       const double* imu, int n_imu, const double* noise4,
+                                       double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
+                                       int32_t* redundant_out, void* stream)
+{
+    return predict_ops_dev_body(c, n_streams, wg, cam_stride, ld, p_stride, state_io, state_int_io, t_frame, ctl, imu, n_imu, noise4,
+                                cam_q_dev, cam_p_dev, cam_qn_dev, P_dev, redundant_out, stream, 0, nullptr, nullptr);
+}
+// The same with the IMU-rate odometry on (airvision.h, "IMU-rate odometry"): cap >= 1 records per stream, rec_out [n_streams][cap] and
+// n_out [n_streams][2] HOST arrays, uploaded as the caller filled them (a pre-fill shows what the kernel did not write) and read back.
+AV_EXPORT int av_msckf_predict_ops_dev_rate(av_msckf* c, int n_streams, int wg, int cam_stride, int ld, int64_t p_stride,
+                                            double* state_io, int32_t* state_int_io, const double* t_frame, const int32_t* ctl,
+                                            const double* imu, int n_imu, const double* noise4,
+                                            double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
+                                            int32_t* redundant_out, void* stream, int cap, av_imu_state* rec_out, int32_t* n_out)
+{
+    if (cap < 1) { av_set_error("av_msckf_predict_ops_dev_rate: cap must be 1 .. %d", IMU_RATE_CAP_MAX); return AV_E_INVALID; }
+    return predict_ops_dev_body(c, n_streams, wg, cam_stride, ld, p_stride, state_io, state_int_io, t_frame, ctl, imu, n_imu, noise4,
+                                cam_q_dev, cam_p_dev, cam_qn_dev, P_dev, redundant_out, stream, cap, rec_out, n_out);
 }
 
 // Work done so far, for the filter's roofline (drain first): [algorithmic fp64 flops of the gates, of the updates without the

@@ -25,6 +25,8 @@
 //                feature arrays, the pruning update's ahead of dk_finish's camera removal
 //   dk_mid_st, dk_mid_lm_st, dk_finish_st, dk_finish_cov_st, dk_finish_lm_st, dk_finish_cov_lm_st  (instead of the six above when
 //                av_msckf_batch_set_stats is on) the same, and the stream's innovation statistics of the update that has just run
+//   dk_imu_rate  (behind dk_state, the state half of dk_predict, when av_msckf_batch_set_imu_rate is on) per stream: the state after every
+//                IMU sample of the frame, gathered from the records dk_state leaves for dk_cov
 //
 // Per-stream capacity failures are recorded in the stream's state (DState::failed) and stop that stream only.
 
@@ -281,6 +283,38 @@ __global__ __launch_bounds__(64) void dk_state(DevArgs a)
         }
         a.cov[s] = cv;
         *Dg = L;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// dk_imu_rate: IMU-rate odometry (include/airvision.h, "IMU-rate odometry"; launched behind dk_state only when av_msckf_batch_set_imu_rate
+// is on).  dk_state leaves, per IMU sample it integrated, the state after dev_predict_new_state and the bias-corrected gyro in the
+// sample's record a.prop[] (q_new, p_new, v_new, gyro: the doubles dk_cov reads), and its final word on the stream's part in the step in
+// a.cov[] (act, first, cnt).  This kernel gathers them into records of 112 bytes, the sample's stamp from a.imu[] in front: ONE wavefront
+// per stream, whatever shape the step's other kernels take, a lane per double of the stream's rows, so the stores are contiguous (a lane
+// per stream inside dk_state would write 112-byte pieces cap x 112 bytes apart).  On overflow the LAST cap samples are kept: record j is
+// sample cnt - min(cnt, cap) + j.  A stream dk_state left alone reads (0, 0).  Plain vector stores: no atomics, no LDS.
+// (As a second instance of dk_state, the body a template over a bool, the records cost no launch -- but the instance with the bool off
+//  no longer compiled to dk_state's code: 2,086 instructions against 2,083, 106 scalar registers with two spilled against 96 and none;
+//  profiles/imu_rate/README.md.)
+// ------------------------------------------------------------------------------------------------
+struct DImuState { double t, p[3], q[4], v[3], w[3]; };
+static_assert(sizeof(DImuState) == 112, "av_imu_state is 112 bytes");
+struct IrOut { DImuState* rec; int* n; int cap; };      // [S][cap] records, [S][2] counts (had, written)
+__global__ __launch_bounds__(64) void dk_imu_rate(DevArgs a, IrOut R)
+{
+    AV_FILTER_PRIO();
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const DCov cv = a.cov[s];
+    const int had = cv.act ? cv.cnt : 0, wr = had < R.cap ? had : R.cap, k0 = had - wr;
+    if (lane == 0) { R.n[2 * (size_t)s] = had; R.n[2 * (size_t)s + 1] = wr; }
+    constexpr int W = (int)(sizeof(DImuState) / 8);
+    double* out = reinterpret_cast<double*>(R.rec + (size_t)s * R.cap);
+    for (int e = lane; e < wr * W; e += 64) {
+        const int j = e / W, f = e - j * W;
+        const size_t i = (size_t)cv.first + k0 + j;
+        const PropArgs& pa = a.prop[i];
+        out[e] = f == 0 ? a.imu[i].t : (f < 4 ? pa.p_new[f - 1] : (f < 8 ? pa.q_new[f - 4] : (f < 11 ? pa.v_new[f - 8] : pa.gyro[f - 11])));
     }
 }
 
@@ -931,7 +965,8 @@ __global__ __launch_bounds__(256, 5) void dk_finish_cov_lm_st(DevArgs a, double*
 //   store       avs_restart: empty window and map, births and the whole header zero (avs_clear alone leaves births and the sticky
 //               hdr[AVS_OVERFLOW]), every persistent array as allocated
 //   outputs     the stream's rows of out, of the odometry-covariance, landmark (records and counts) and statistics buffers: zero, as
-//               allocated.  Every step rewrites them for every stream; they are cleared so that a read of the buffers finds no old life.
+//               allocated; likewise the IMU-rate records and counts.  Every step rewrites them for every stream; they are cleared so that a
+//               read of the buffers finds no old life.
 // Not touched: Pn, T, Kt, scratch, the block buffers, the per-phase feature arrays and lists, the store's scratch -- every step writes
 // what it reads of them; `work` (av_msckf_batch_work accumulates).  Overflow pool: a stream holds NO pool rows between steps.  The pool
 // is a bump counter, cnt[4] of the step's counter set, zeroed for every step by the step before it (dk_state: cnt_next); a stream's
@@ -942,7 +977,7 @@ static_assert(sizeof(DState) % 8 == 0, "dk_restart clears DState by 8-byte words
 struct DRestart {
     const int* list; int* carry;                              // [n] streams; [n][2] the counters they held
     double v0[3], t_ci[3], gravity[3], R_ic[9];               // create-time values of the batch
-    double* odom; LmOut lm; DUpdStats* stats;                 // the optional outputs (null: off)
+    double* odom; LmOut lm; DUpdStats* stats; IrOut ir;       // the optional outputs (null: off)
 };
 __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
 {
@@ -962,6 +997,7 @@ __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
         for (int i = 0; i < 3; ++i) a.grav[3 * s + i] = 0.0;
         for (int i = 0; i < 12; ++i) a.out[(size_t)s * 12 + i] = 0.0;
         if (r.lm.rec) { r.lm.n[2 * (size_t)s] = 0; r.lm.n[2 * (size_t)s + 1] = 0; }
+        if (r.ir.rec) { r.ir.n[2 * (size_t)s] = 0; r.ir.n[2 * (size_t)s + 1] = 0; }
     }
     double* P = a.P + (size_t)s * a.pstride;
     for (size_t i = tid; i < a.pstride; i += nt) {            // reset_state_cov (msckf.py:788-798) in a cleared region
@@ -978,6 +1014,10 @@ __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
     if (r.stats) {
         unsigned long long* w = reinterpret_cast<unsigned long long*>(r.stats + 2 * (size_t)s);
         for (int i = tid; i < 2 * (int)(sizeof(DUpdStats) / 8); i += nt) w[i] = 0ull;
+    }
+    if (r.ir.rec) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(r.ir.rec + (size_t)s * r.ir.cap);
+        for (int i = tid; i < r.ir.cap * (int)(sizeof(DImuState) / 8); i += nt) w[i] = 0ull;
     }
     AvsTeam T; T.red = nullptr;
     avs_restart(T, dev_store(a, s));
@@ -1002,15 +1042,17 @@ __global__ __launch_bounds__(256) void dk_prune_probe(DevArgs a, const int* ops,
 // ---- host-side handles of the device-resident path (functions: msckf_dev_host.inc) ---------------------------------------------
 // The optional per-step outputs: ONE entry per array a step may carry beside its poses, in the order of their read-back on the stream.
 // A feature is what a caller switches (av_msckf_batch_set_*) and hands a destination for (av_msckf_batch_next_*); its setting is
-// 0 = off, else 1 (the landmark map: records per stream and step).  The landmark records and counts are two arrays of one feature.
+// 0 = off, else 1 (the landmark map and the IMU-rate odometry: records per stream and step).  Their records and counts are two arrays of
+// one feature.
 // Everything else about them -- the batch's settings and next destinations, StepOuts, the device and pinned buffers, their allocation,
 // read-back, hand-over and restart -- is an array indexed by this table or a loop over it.  A fourth output: an entry here (and in
-// KOuts), its two exported wrappers, and the kernel instances that write it (dk_mid_kernels / dk_finish_kernels, msckf_dev_host.inc).
-enum OutFeat { F_COV, F_LM, F_STATS, N_FEAT };
-enum OutArr { O_COV, O_LM, O_LMN, O_STATS, N_OUT };
+// KOuts), its two exported wrappers, and the kernel instances that write it (dk_mid_kernels / dk_finish_kernels, msckf_dev_host.inc) -- or,
+// for the IMU-rate odometry, the one kernel dev_launch_predict adds behind dk_state.
+enum OutFeat { F_COV, F_LM, F_STATS, F_IR, N_FEAT };
+enum OutArr { O_COV, O_LM, O_LMN, O_STATS, O_IR, O_IRN, N_OUT };
 struct OutWords { const char* fn; const char* noun; const char* needs; const char* is; };      // "av_msckf_batch_set_<fn>: <noun> <needs> ...", "<noun> <is> off"
 constexpr OutWords W_COV = {"odom_cov", "the odometry covariance", "needs", "is"}, W_LM = {"landmarks", "the landmark map", "needs", "is"},
-                   W_STATS = {"stats", "the innovation statistics", "need", "are"};
+                   W_STATS = {"stats", "the innovation statistics", "need", "are"}, W_IR = {"imu_rate", "the IMU-rate odometry", "needs", "is"};
 struct OutDesc {
     OutFeat feat; size_t fixed, per_setting; OutWords w;
     size_t bytes(const int* setting) const { return fixed + per_setting * (size_t)setting[feat]; }      // per stream
@@ -1020,6 +1062,8 @@ constexpr OutDesc OUTS[N_OUT] = {
     {F_LM, 0, AV_LANDMARK_BYTES, W_LM},              // landmark records
     {F_LM, 2 * 4, 0, W_LM},                          // landmark counts (had, written)
     {F_STATS, AV_FILTER_STATS_BYTES, 0, W_STATS},    // statistics records (two update blocks)
+    {F_IR, 0, AV_IMU_STATE_BYTES, W_IR},             // IMU-rate records
+    {F_IR, 2 * 4, 0, W_IR},                          // IMU-rate counts (had, written)
 };
 constexpr const OutWords& out_words(OutFeat f) { for (int i = 0; i < N_OUT; ++i) if (OUTS[i].feat == f) return OUTS[i].w; return OUTS[0].w; }
 // a step's destinations in the caller's memory (NULL: the step has none and the array is dropped)
@@ -1032,7 +1076,7 @@ struct StepOuts {
         return g;
     }
 };
-struct KOuts { double* odom; LmOut lm; DUpdStats* stats; };      // the device arrays as the kernels' parameter lists and DRestart take them (dev_kouts)
+struct KOuts { double* odom; LmOut lm; DUpdStats* stats; IrOut ir; };      // the device arrays as the kernels' parameter lists and DRestart take them (dev_kouts)
 constexpr int DEV_RING = 3;          // steps of a stream group that may be queued at once (inputs / outputs are ring-buffered)
 struct DevSlot {
     DCtl* ctl_h = nullptr; DCtl* ctl_d = nullptr;

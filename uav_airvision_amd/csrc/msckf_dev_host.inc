@@ -435,12 +435,14 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
     return AV_OK;
 }
 
-// The prediction's launches of a step, in a step's order: dk_state, [dk_begin4: the frame's observations, independent of the covariance],
-// dk_cov<dk_wg>.  One place for the step (dev_enqueue, append = true) and for the parity-test entry av_msckf_predict_ops_dev (append =
+// The prediction's launches of a step, in a step's order: dk_state, [dk_imu_rate: the IMU-rate odometry, when it is on], [dk_begin4: the
+// frame's observations, independent of the covariance], dk_cov<dk_wg>.  One place for the step (dev_enqueue, append = true) and for the parity-test entry av_msckf_predict_ops_dev (append =
 // false: it has no observation store), so that the entry launches what the step launches.
-void dev_launch_predict(const DevArgs& a, int S, int dk_wg, bool append, hipStream_t stm)
+// ir.rec set (av_msckf_batch_set_imu_rate): dk_imu_rate behind dk_state, one wavefront per stream whatever dk_wg is.
+void dev_launch_predict(const DevArgs& a, int S, int dk_wg, bool append, hipStream_t stm, const IrOut& ir = IrOut{})
 {
     hipLaunchKernelGGL(dk_state, dim3((S + 63) / 64), dim3(64), 0, stm, a);     // state integration + the new camera state: a lane per stream
+    if (ir.rec) hipLaunchKernelGGL(dk_imu_rate, dim3(S), dim3(64), 0, stm, a, ir);      // the IMU-rate records, from what dk_state left for dk_cov
     if (append) hipLaunchKernelGGL(dk_begin4, dim3(S), dim3(dk_wg), 0, stm, a);
     if (dk_wg == 64) hipLaunchKernelGGL(dk_cov<64>, dim3(S), dim3(64), 0, stm, a);          // the covariance half of the prediction and of the augmentation
     else hipLaunchKernelGGL(dk_cov<256>, dim3(S), dim3(256), 0, stm, a);
@@ -460,7 +462,8 @@ static_assert(std::is_same<decltype(&dk_mid_lm_st), void (*)(DevArgs, LmOut, DUp
 KOuts dev_kouts(const av_msckf_batch* b)          // the one place that gives the table's device arrays their types
 {
     char* const* p = b->dev->outs_d;
-    return {(double*)p[O_COV], LmOut{(DLandmark*)p[O_LM], (int*)p[O_LMN], b->out_set[F_LM]}, (DUpdStats*)p[O_STATS]};
+    return {(double*)p[O_COV], LmOut{(DLandmark*)p[O_LM], (int*)p[O_LMN], b->out_set[F_LM]}, (DUpdStats*)p[O_STATS],
+            IrOut{(DImuState*)p[O_IR], (int*)p[O_IRN], b->out_set[F_IR]}};
 }
 int dev_launch_outs(bool finish, const av_msckf_batch* b, DevArgs& a, int wg, hipStream_t stm)
 {
@@ -505,7 +508,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     // stream takes: four wavefronts (one stream 0.59 against 0.78 ms per frame, 256 streams x 1,500 features 36 against 29 k frames/s).
     const int dk_wg = d->dk_wg ? d->dk_wg : (S >= 1024 ? 64 : 256);       // (AV_DK_WG=64|256 forces one: A/B runs, and the parity tests of the shape small groups do not take)
     d->launched_wg = dk_wg;
-    dev_launch_predict(a, S, dk_wg, true, stm);
+    dev_launch_predict(a, S, dk_wg, true, stm, dev_kouts(b).ir);
     AV_LAUNCH_CHECK();
     if ((rc = dev_phase(b, 0, stm, sl, a.cnt))) return rc;
     if (b->debug_capture && (rc = dev_debug_capture(b, 0, stm))) return rc;
@@ -560,7 +563,7 @@ int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm)
     for (int i = 0; i < 3; ++i) { r.v0[i] = b->vel0[i]; r.t_ci[i] = b->t_ci0[i]; r.gravity[i] = b->gravity0[i]; }
     for (int i = 0; i < 9; ++i) r.R_ic[i] = b->R_ic0[i];
     const KOuts o = dev_kouts(b);
-    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats;
+    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats; r.ir = o.ir;
     hipLaunchKernelGGL(dk_restart, dim3((unsigned)n), dim3(256), 0, stm, d->A, r);
     AV_LAUNCH_CHECK();
     AV_HIP(hipMemcpyAsync(d->rs_carry_h, d->rs_carry_d, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, stm));

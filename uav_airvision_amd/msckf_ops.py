@@ -208,7 +208,7 @@ class MsckfDevice(object):
                     ('gravity', 3), ('tracking_rate', 1))          # state_io of av_msckf_predict_ops_dev, 43 doubles
     STATE_INTS = ('n', 'ncam', 'failed', 'null_aliased', 'first_img', 'active')
 
-    def predict_ops_dev(self, streams, imu, cam_q, cam_p, cam_qn, P, noise, wg):
+    def predict_ops_dev(self, streams, imu, cam_q, cam_p, cam_qn, P, noise, wg, rate_cap=0, rate_fill=np.nan):
         """Parity-test entry (av_msckf_predict_ops_dev; tests only): the prediction of the device-resident filter -- state integration,
         covariance propagation, augmentation -- in the launch sequence a step begins with, for all `streams` at once, at wg = 64 or 256.
         streams: one dict per stream with the STATE_FIELDS (R_ic 3 x 3 or 9), n, ncam, and optionally failed, null_aliased, first_img,
@@ -216,6 +216,9 @@ class MsckfDevice(object):
         imu: float64[n_imu, 7] (t, gyro, acc).  cam_q / cam_p / cam_qn: [streams, cam_stride, 4 | 3 | 4]; P: [streams, ld, ld] (whatever
         lies outside a stream's own square is the caller's pre-fill and must come back untouched).  The library checks every count and
         position before it launches anything.
+        rate_cap >= 1: through av_msckf_predict_ops_dev_rate, the launches a step begins with when the IMU-rate odometry is on; the result
+        then also holds imu_rec IMU_STATE_DTYPE[streams, rate_cap], pre-filled with rate_fill in every double, and imu_n int32[streams, 2],
+        pre-filled with -1, as the kernel left them.
         -> dict(streams: list of dicts (STATE_FIELDS + STATE_INTS as they come back, redundant: (r0, r1) or None), cam_q, cam_p, cam_qn, P)."""
         S = len(streams)
         cam_q = np.ascontiguousarray(cam_q, dtype=np.float64)
@@ -240,9 +243,17 @@ class MsckfDevice(object):
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
         q, p, qn, Pd = up(cam_q), up(cam_p), up(cam_qn), up(P)
         hp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rate = {}
+        if rate_cap:
+            rec = np.full((S, int(rate_cap), 14), rate_fill, dtype=np.float64)
+            rate = dict(imu_rec=rec.view(IMU_STATE_DTYPE).reshape(S, int(rate_cap)), imu_n=np.full((S, 2), -1, np.int32))
         with torch.cuda.device(self.device):
-            N.check(N.lib().av_msckf_predict_ops_dev(self._h, S, int(wg), cs, ld, ld * ld, hp(sd), hp(si), hp(tf), hp(ctl), hp(imu), len(imu), _d(noise),
-                                                     N.dptr(q), N.dptr(p), N.dptr(qn), N.dptr(Pd), hp(red), self._st()))
+            args = (self._h, S, int(wg), cs, ld, ld * ld, hp(sd), hp(si), hp(tf), hp(ctl), hp(imu), len(imu), _d(noise),
+                    N.dptr(q), N.dptr(p), N.dptr(qn), N.dptr(Pd), hp(red), self._st())
+            if rate_cap:
+                N.check(N.lib().av_msckf_predict_ops_dev_rate(*(args + (int(rate_cap), hp(rec), hp(rate['imu_n'])))))
+            else:
+                N.check(N.lib().av_msckf_predict_ops_dev(*args))
             torch.cuda.synchronize()
         out = []
         for s, st in enumerate(streams):
@@ -253,7 +264,7 @@ class MsckfDevice(object):
             d.update(zip(self.STATE_INTS, (int(v) for v in si[s])))
             d['redundant'] = (int(red[s, 0]), int(red[s, 1])) if st.get('find_redundant') else None
             out.append(d)
-        return dict(streams=out, cam_q=q.cpu().numpy(), cam_p=p.cpu().numpy(), cam_qn=qn.cpu().numpy(), P=Pd.cpu().numpy())
+        return dict(streams=out, cam_q=q.cpu().numpy(), cam_p=p.cpu().numpy(), cam_qn=qn.cpu().numpy(), P=Pd.cpu().numpy(), **rate)
 
     def update(self, blk_rows, blk_lens, obs_noise):
         """Stacked EKF update on the selected blocks; returns delta_x (n doubles)."""
@@ -344,6 +355,18 @@ def unpack_filter_stats(rec):
     return out
 
 
+# ---- IMU-rate odometry (include/airvision.h, "IMU-rate odometry") --------------------------------------------------------------
+IMU_STATE_DTYPE = np.dtype([('t', np.float64), ('p', np.float64, (3,)), ('q', np.float64, (4,)), ('v', np.float64, (3,)), ('w', np.float64, (3,))])      # av_imu_state, AV_IMU_STATE_BYTES
+assert IMU_STATE_DTYPE.itemsize == 112
+IMU_RATE_CAP_MAX = 4096
+
+
+def unpack_imu_states(rec, n, s):
+    """The written records of stream `s`: rec IMU_STATE_DTYPE[S, cap] and n int32[S, 2] as a step returns them -> rec[s, :n[s, 1]], in
+    time order (n[s, 0] - n[s, 1] records, the oldest, were dropped to the cap)."""
+    return rec[s, :int(n[s, 1])]
+
+
 # The optional outputs of a step of BatchedMSCKF, one entry each.  kw: the keyword of `step / submit / submit_dev`; ctor_kw: the
 # constructor keyword that switches it on; setting: the attribute that holds its setting (falsy: off); fn: the library's
 # av_msckf_batch_set_<fn> / av_msckf_batch_next_<fn>; last: the attribute that remembers the arrays of the most recent step that was
@@ -358,6 +381,9 @@ STEP_OUTPUTS = (
                lambda f: 'landmarks must be a pair of C-contiguous arrays LANDMARK_DTYPE[%d, %d], int32[%d, 2]' % (f.S, f.landmark_cap, f.S)),
     StepOutput('stats', 'stats', 'stats', 'stats', 'last_stats', lambda f: [(FILTER_STATS_DTYPE, (f.S, 2))], 0,
                lambda f: 'stats must be a C-contiguous FILTER_STATS_DTYPE[%d, 2] array' % f.S),
+    StepOutput('imu_states', 'imu_rate', 'imu_rate_cap', 'imu_rate', 'last_imu_states',
+               lambda f: [(IMU_STATE_DTYPE, (f.S, f.imu_rate_cap)), (np.int32, (f.S, 2))], 0,
+               lambda f: 'imu_states must be a pair of C-contiguous arrays IMU_STATE_DTYPE[%d, %d], int32[%d, 2]' % (f.S, f.imu_rate_cap, f.S)),
 )
 _OUTPUT = {o.kw: o for o in STEP_OUTPUTS}
 
@@ -367,7 +393,8 @@ class BatchedMSCKF(object):
     library, one batched launch per numeric phase.  Mirrors MSCKF.imu_callback / feature_callback
     (reference: src/msckf.py:162-228) for many streams at once."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64, stats=False):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64, stats=False,
+                 imu_rate=False, imu_rate_cap=32):
         """rows_cap: rows of the per-stream block buffer.  None = sized by the library from the capacity of the first
         feature message (the camera-pruning update stacks 5 rows per feature, the lost-feature update at most 1500 + one
         block); `max_features`, when given, sizes it up front instead.  With the automatic size a later step with a wider
@@ -380,7 +407,10 @@ class BatchedMSCKF(object):
         landmarks=True: every step also publishes the features its two updates triangulated, up to landmark_cap records per stream
         (LANDMARK_DTYPE; `step / submit / submit_dev(..., landmarks=)`, `last_landmarks`, `unpack_landmarks`).  Device-resident filter only.
         stats=True: every step also publishes the innovation statistics of its two updates, FILTER_STATS_DTYPE[S, 2] (`step / submit /
-        submit_dev(..., stats=)`, `last_stats`, `unpack_filter_stats`).  Device-resident filter only."""
+        submit_dev(..., stats=)`, `last_stats`, `unpack_filter_stats`).  Device-resident filter only.
+        imu_rate=True: every step also publishes the state after every IMU sample its prediction integrated, the last imu_rate_cap
+        (1 .. 4096) of them per stream (IMU_STATE_DTYPE; `step / submit / submit_dev(..., imu_states=)`, `last_imu_states`,
+        `unpack_imu_states`).  Predictions from the previous step's state; `w` is in the IMU frame.  Device-resident filter only."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -405,14 +435,18 @@ class BatchedMSCKF(object):
                 _d([o.huber_epsilon, o.estimation_precision, o.initial_damping, o.outer_loop_max_iteration, o.inner_loop_max_iteration, o.translation_threshold]),
                 self.device, C.byref(self._h)))
         # the optional outputs: last_* = the arrays of the most recent step that was given any (cov: float64[S, 120]; landmarks: (records
-        # LANDMARK_DTYPE[S, cap], counts int32[S, 2]); stats: FILTER_STATS_DTYPE[S, 2])
-        want = {'odom_cov': bool(odom_cov), 'landmark_cap': int(landmark_cap) if landmarks else 0, 'stats': bool(stats)}
+        # LANDMARK_DTYPE[S, cap], counts int32[S, 2]); stats: FILTER_STATS_DTYPE[S, 2]; imu_states: (records IMU_STATE_DTYPE[S, cap], counts
+        # int32[S, 2]))
+        want = {'odom_cov': bool(odom_cov), 'landmark_cap': int(landmark_cap) if landmarks else 0, 'stats': bool(stats),
+                'imu_rate_cap': int(imu_rate_cap) if imu_rate else 0}
         for o in STEP_OUTPUTS:
             setattr(self, o.setting, want[o.setting])
             setattr(self, o.last, None)
         try:
             if landmarks and want['landmark_cap'] < 1:
                 raise ValueError('landmark_cap must be at least 1')
+            if imu_rate and not 1 <= want['imu_rate_cap'] <= IMU_RATE_CAP_MAX:
+                raise ValueError('imu_rate_cap must be 1 .. %d' % IMU_RATE_CAP_MAX)
             for o in STEP_OUTPUTS:
                 if want[o.setting]:
                     self._set(o, want[o.setting])
@@ -436,9 +470,13 @@ class BatchedMSCKF(object):
         """av_msckf_batch_set_stats: before the first step only."""
         self._set(_OUTPUT['stats'], bool(enable))
 
+    def set_imu_rate(self, cap):
+        """av_msckf_batch_set_imu_rate: cap records per stream and step (0: off, at most 4096); before the first step only."""
+        self._set(_OUTPUT['imu_states'], int(cap))
+
     def _next(self, o, value):
         """The arrays of output `o` for the next step (None: the step has none), handed to the library.  value: None, True (allocate) or
-        the caller's C-contiguous array (landmarks: pair of arrays) of o.shapes(self)."""
+        the caller's C-contiguous array (landmarks, imu_states: pair of arrays) of o.shapes(self)."""
         if value is None or value is False:
             return None
         if not getattr(self, o.setting):
@@ -481,37 +519,39 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_push_imu(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                 g.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), len(si)))
 
-    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None):
+    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None, imu_states=None):
         """ids int64[S,cap], uv float64[S,cap,4], n_feat int32[S], timestamps float64[S] (host arrays).
         Returns float64[S,12]: published, t, p(3), q(4), v(3).  cov (odom_cov=True): a float64[S,120] array that takes the step's
         odometry-covariance records, or True to have one allocated; it is `last_cov` afterwards.  landmarks (landmarks=True): a pair of
         arrays (LANDMARK_DTYPE[S, landmark_cap], int32[S, 2]) that takes the step's landmark records and counts, or True to have them
         allocated; the pair is `last_landmarks` afterwards.  stats (stats=True): a FILTER_STATS_DTYPE[S, 2] array that takes the step's
-        innovation statistics, or True to have one allocated; it is `last_stats` afterwards."""
+        innovation statistics, or True to have one allocated; it is `last_stats` afterwards.  imu_states (imu_rate=True): a pair of arrays
+        (IMU_STATE_DTYPE[S, imu_rate_cap], int32[S, 2]) that takes the step's IMU-rate records and counts, or True to have them allocated;
+        the pair is `last_imu_states` afterwards."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         cap = ids.shape[1]
         out = np.zeros((self.S, 12))
-        self._next_outputs(cov=cov, landmarks=landmarks, stats=stats)
+        self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_step(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                 nf.ctypes.data_as(C.c_void_p), cap, ts.ctypes.data_as(C.c_void_p),
                                                 out.ctypes.data_as(C.c_void_p), N.current_stream()))
         return out
 
-    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None):
+    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None, imu_states=None):
         """Queue one step (av_msckf_batch_submit) and return its float64[S,12] output array, which is filled once the
         step has retired -- i.e. after a `wait(k)` that leaves fewer than the steps submitted after it pending.  The
         stream groups of the batch run behind their queues independently of each other.  cov: as in `step`; the array (`last_cov`) is
-        filled when the step retires, like the output array; landmarks, stats: likewise."""
+        filled when the step retires, like the output array; landmarks, stats, imu_states: likewise."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         out = np.zeros((self.S, 12))
-        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats)
+        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_submit(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                   nf.ctypes.data_as(C.c_void_p), ids.shape[1], ts.ctypes.data_as(C.c_void_p),
@@ -523,17 +563,17 @@ class BatchedMSCKF(object):
         """True when the filter state and the observation map live on the device (the default; `submit_dev` needs it)."""
         return N.lib().av_msckf_batch_device_resident(self._h) == 1
 
-    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None):
+    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None, imu_states=None):
         """Queue one step on the feature message `engine` (a FrontendEngine with the same streams) has just published, read
         where it lies on the device (av_msckf_batch_submit_dev): no host round trip between the front-end and the filter.
         msg_stream: the stream handle the engine's step ran on (default: torch's current stream, i.e. call this right after
         `engine.step` on the same stream).  The filter's kernels run on the current stream / the stream groups' own streams.
-        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks, stats: as in `submit`."""
+        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks, stats, imu_states: as in `submit`."""
         ids, uv, n, cap = engine.features_dev()
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         assert ts.shape == (self.S,) and engine.n_streams == self.S
         out = np.zeros((self.S, 12))
-        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats)
+        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states)
         with torch.cuda.device(self.device):
             ms = N.current_stream() if msg_stream is None else msg_stream
             N.check(N.lib().av_msckf_batch_submit_dev(self._h, ids, uv, n, cap, ts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),

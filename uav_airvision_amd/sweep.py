@@ -62,9 +62,12 @@ class BatchedRunner(object):
     landmark_cap > 0: every step also brings its landmark records (BatchedMSCKF(landmarks=True, landmark_cap=)); after `run`,
     `lm_rows[s]` is (float64[n] pose times, LANDMARK_DTYPE[n] records, records dropped to the cap) of stream s.
     innovation=True: every step also brings its innovation statistics (BatchedMSCKF(stats=True)); after `run`, `nis_rows[s]` is
-    (float64[n] pose times, FILTER_STATS_DTYPE[n, 2] records), one per row of stream s's trajectory."""
+    (float64[n] pose times, FILTER_STATS_DTYPE[n, 2] records), one per row of stream s's trajectory.
+    imu_rate_cap > 0: every step also brings its IMU-rate records (BatchedMSCKF(imu_rate=True, imu_rate_cap=)); after `run`,
+    `ir_rows[s]` is (float64[n, 14] lines `t p q v w` -- the records of every publishing step, then that step's published pose with the
+    w of its last record --, records among them, records dropped to the cap) of stream s."""
 
-    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False, landmark_cap=0, innovation=False):
+    def __init__(self, config, n_streams, device=0, rows_cap=None, odom_cov=False, landmark_cap=0, innovation=False, imu_rate_cap=0):
         from .frontend import FrontendEngine
         from .msckf_ops import BatchedMSCKF
         self.config, self.S, self.device = config, int(n_streams), int(device)
@@ -72,7 +75,10 @@ class BatchedRunner(object):
         self.odom_cov = bool(odom_cov)
         self.landmark_cap = int(landmark_cap)
         self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features, odom_cov=self.odom_cov,
-                                landmarks=self.landmark_cap > 0, landmark_cap=max(1, self.landmark_cap), stats=bool(innovation))
+                                landmarks=self.landmark_cap > 0, landmark_cap=max(1, self.landmark_cap), stats=bool(innovation),
+                                imu_rate=int(imu_rate_cap) > 0, imu_rate_cap=max(1, int(imu_rate_cap)))
+        self.imu_rate_cap = int(imu_rate_cap)
+        self.ir_rows = None
         self.innovation = bool(innovation)
         self.nis_rows = None
         self.cov_rows = None
@@ -144,9 +150,20 @@ class BatchedRunner(object):
         nis = [[[], []] for _ in range(S)]                # per stream: pose times, the step's two blocks
         want_nis = True if self.innovation else None
 
-        def record(out, cov=None, lm=None, fst=None):
+        irs = [[[], 0, 0] for _ in range(S)]              # per stream: lines `t p q v w`, records among them, records dropped to the cap
+        want_ir = True if self.imu_rate_cap > 0 else None
+
+        def record(out, cov=None, lm=None, fst=None, ir=None):
             for s in np.nonzero(out[:, 0] > 0.5)[0]:
                 traj[s].append(out[s, 1:9].copy())
+                if ir is not None:                        # the step's records, then its published pose (the update's correction lies between)
+                    rec = ir[0][s, :ir[1][s, 1]]
+                    rows = np.full((len(rec) + 1, 14), np.nan)
+                    rows[:-1] = rec.view(np.float64).reshape(len(rec), 14)
+                    rows[-1, :11] = out[s, 1:12]
+                    if len(rec):
+                        rows[-1, 11:] = rec['w'][-1]
+                    irs[s][0].append(rows); irs[s][1] += len(rec); irs[s][2] += int(ir[1][s, 0] - ir[1][s, 1])
                 if cov is not None:
                     covs[s].append(np.concatenate([out[s, 1:2], cov[s]]))
                 if lm is not None and lm[1][s, 1] > 0:
@@ -228,8 +245,8 @@ class BatchedRunner(object):
             if on_step is not None:
                 ids, uv, n = eng.read_features_raw()
                 n[ts_f < 0] = 0
-                out = flt.step(ids, uv, n, ts_f, cov=want, landmarks=want_lm, stats=want_nis)
-                record(out, flt.last_cov, flt.last_landmarks, flt.last_stats)
+                out = flt.step(ids, uv, n, ts_f, cov=want, landmarks=want_lm, stats=want_nis, imu_states=want_ir)
+                record(out, flt.last_cov, flt.last_landmarks, flt.last_stats, flt.last_imu_states)
                 on_step(step, ts_f, ids, uv, n, out)
             elif dev:
                 # the filter reads the published message where it lies on the device; nothing of this step is waited for here:
@@ -241,7 +258,8 @@ class BatchedRunner(object):
                     self._fstream = torch.cuda.Stream(device=self.device)
                 ms = N.current_stream()                   # the stream the front-end's step was enqueued on
                 with torch.cuda.stream(self._fstream):    # the filter's kernels (one group: here) overlap the next frame's front-end
-                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want, landmarks=want_lm, stats=want_nis), flt.last_cov, flt.last_landmarks, flt.last_stats))
+                    inflight.append((flt.submit_dev(eng, ts_f, msg_stream=ms, cov=want, landmarks=want_lm, stats=want_nis, imu_states=want_ir),
+                                     flt.last_cov, flt.last_landmarks, flt.last_stats, flt.last_imu_states))
                 flt.wait(2)
                 while len(inflight) > 2:
                     record(*inflight.pop(0))
@@ -249,7 +267,8 @@ class BatchedRunner(object):
                 eng.read_features_begin(step & 1)
                 ids, uv, n = eng.read_features_end(step & 1)
                 n[ts_f < 0] = 0
-                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want, landmarks=want_lm, stats=want_nis), flt.last_cov, flt.last_landmarks, flt.last_stats))
+                inflight.append((flt.submit(ids, uv, n, ts_f, cov=want, landmarks=want_lm, stats=want_nis, imu_states=want_ir),
+                                 flt.last_cov, flt.last_landmarks, flt.last_stats, flt.last_imu_states))
                 flt.wait(1)                               # at most one step behind: the next frames are decoded meanwhile
                 while len(inflight) > 1:
                     record(*inflight.pop(0))
@@ -265,16 +284,21 @@ class BatchedRunner(object):
         if self.innovation:
             from .msckf_ops import FILTER_STATS_DTYPE
             self.nis_rows = [(np.array(t, dtype=np.float64), np.array(r, dtype=FILTER_STATS_DTYPE).reshape(-1, 2)) for t, r in nis]
+        if self.imu_rate_cap > 0:
+            self.ir_rows = [(np.concatenate(r) if r else np.zeros((0, 14)), n, d) for r, n, d in irs]
         return [np.array(t, dtype=np.float64).reshape(-1, 8) for t in traj]
 
 
-def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None, lm_rows=None, landmark_cap=64, nis_rows=None):
+def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None, lm_rows=None, landmark_cap=64, nis_rows=None,
+                ir_rows=None, imu_rate_cap=32):
     """Open (path, offset) pairs as EuRoC datasets and run them as one batch; returns (trajectories, datasets).
     cov_rows (a list): the batch runs with the odometry covariance on and the list receives, per stream, float64[n, 121] rows `t` + record.
     lm_rows (a list): the batch runs with the landmark map on (landmark_cap records per stream and step) and the list receives, per
     stream, (pose times float64[n], records LANDMARK_DTYPE[n], records dropped to the cap).
     nis_rows (a list): the batch runs with the innovation statistics on and the list receives, per stream, (pose times float64[n], records
     FILTER_STATS_DTYPE[n, 2]).
+    ir_rows (a list): the batch runs with the IMU-rate odometry on (the last imu_rate_cap records per stream and step) and the list
+    receives, per stream, (lines float64[n, 14] `t p q v w`, records among them, records dropped to the cap).
     stats (a dict) receives the batch's stream-frames, steps, distinct frames decoded and the seconds its stepping loop took."""
     import time
     from .euroc import EuRoCDataset
@@ -284,7 +308,7 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
         ds.set_starttime(o)
         dss.append(ds)
     r = BatchedRunner(config, len(dss), device=device, rows_cap=rows_cap, odom_cov=cov_rows is not None, landmark_cap=landmark_cap if lm_rows is not None else 0,
-                      innovation=nis_rows is not None)
+                      innovation=nis_rows is not None, imu_rate_cap=imu_rate_cap if ir_rows is not None else 0)
     try:
         t0 = time.perf_counter()
         trajs = r.run(dss, max_frames=max_frames, on_step=on_step, share_frames=share_frames)
@@ -294,6 +318,8 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
             lm_rows.extend(r.lm_rows)
         if nis_rows is not None:
             nis_rows.extend(r.nis_rows)
+        if ir_rows is not None:
+            ir_rows.extend(r.ir_rows)
         if stats is not None:
             stats['seconds'] = stats.get('seconds', 0.0) + time.perf_counter() - t0
             stats['stream_frames'] = stats.get('stream_frames', 0) + int(r.frames_done.sum())
@@ -356,6 +382,12 @@ def make_parser():
                          'and eight doubles of its two innovation-statistics blocks (lost-feature update, pruning update; include/airvision.h, "Innovation '
                          'statistics"); the report of every stream gains nis_rows, the sum of gamma over the residual rows of all evaluated features '
                          '(near 1 for a consistent filter; needs no ground truth), and reject_rate, the share of evaluated features the gate rejected')
+    ap.add_argument('--imu-rate', action='store_true',
+                    help='also write, next to every trajectory file, output_<sequence>_offset<o>_imu.txt: the state after every IMU sample the filter '
+                         'integrated, one line `t p q v w` each (p, q, v in the frame of the trajectory file, w the bias-corrected gyro in the IMU frame; '
+                         'include/airvision.h, "IMU-rate odometry"), and after the records of every step the published pose of that step as one more line; '
+                         'the report states the records dropped to the cap and, with ground truth, the ATE of this denser trajectory')
+    ap.add_argument('--imu-rate-cap', type=int, default=32, metavar='N', help='--imu-rate: records per stream and step, the last N samples (default 32, at most 4096)')
     ap.add_argument('--landmark-cap', type=int, default=64, metavar='N', help='--landmarks: records per stream and step (default 64)')
     ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
     ap.add_argument('--ransac-threshold', type=float, default=None, metavar='T', help='inlier error in pixels (config.ransac_threshold, default 3)')
@@ -464,7 +496,7 @@ def main(argv=None):
         ap.error('--root or --make-synthetic is required')
     jobs = shard.broadcast_object([(s, o) for s in args.sequences for o in args.offsets] if rank == 0 else None)
     mine = shard.partition(len(jobs), world, rank)
-    local_traj, local_cov, local_lm, local_nis, report, stats = {}, {}, {}, {}, {}, {}
+    local_traj, local_cov, local_lm, local_nis, local_ir, report, stats = {}, {}, {}, {}, {}, {}, {}
     import time
     if world > 1:
         dist.barrier()
@@ -475,20 +507,26 @@ def main(argv=None):
         cov_rows = [] if args.covariance else None
         lm_rows = [] if args.landmarks else None
         nis_rows = [] if args.innovation else None
+        ir_rows = [] if args.imu_rate else None
         trajs, dss = run_batched(cfg, [os.path.join(root, jobs[j][0]) for j in chunk], [jobs[j][1] for j in chunk], device=local, max_frames=args.max_frames,
                                  share_frames=not args.no_share_frames, stats=stats, **({'cov_rows': cov_rows} if args.covariance else {}),
                                  **({'lm_rows': lm_rows, 'landmark_cap': args.landmark_cap} if args.landmarks else {}),
-                                 **({'nis_rows': nis_rows} if args.innovation else {}))
+                                 **({'nis_rows': nis_rows} if args.innovation else {}),
+                                 **({'ir_rows': ir_rows, 'imu_rate_cap': args.imu_rate_cap} if args.imu_rate else {}))
         for i, (j, traj, ds) in enumerate(zip(chunk, trajs, dss)):
             local_traj[j] = traj
             if cov_rows is not None:
                 local_cov[j] = cov_rows[i]
             if lm_rows is not None:
                 local_lm[j] = lm_rows[i]
+            if ir_rows is not None:
+                local_ir[j] = ir_rows[i]
             gt = ds.groundtruth_array()
             if len(gt) and len(traj) > 20:
                 a, r = ate(traj, gt), rte(traj, gt)
                 report[j] = dict(sequence=jobs[j][0], offset=jobs[j][1], frames=len(traj), ate_rmse=a['rmse'], ate_mean=a['mean'], rte_rmse=r['rmse'])
+                if ir_rows is not None and len(ir_rows[i][0]) > 20:
+                    report[j]['ate_rmse_imu_rate'] = ate(ir_rows[i][0], gt)['rmse']
                 if cov_rows is not None:
                     report[j]['anees_pos'] = nees(traj, unpack_odom_cov(cov_rows[i][:, 1:])[:, 0:3, 0:3], gt)[1]
             if nis_rows is not None:                      # (needs no ground truth: a stream without one gets its report entry here)
@@ -496,7 +534,7 @@ def main(argv=None):
                 report.setdefault(j, dict(sequence=jobs[j][0], offset=jobs[j][1], frames=len(traj))).update(innovation_summary(nis_rows[i][1]))
     elapsed = shard.max_over_ranks(time.perf_counter() - t_all)          # barrier before, max over ranks after: the bench contract's clock
     allt = shard.gather_trajectories(local_traj, len(jobs), world, rank)
-    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm, 'nis': local_nis})
+    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm, 'nis': local_nis, 'ir': local_ir})
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         for j, (seq, off) in enumerate(jobs):
@@ -520,7 +558,18 @@ def main(argv=None):
                 with open(os.path.join(args.out, 'output_%s_offset%d_nis.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
                     for t, rec in zip(ts, recs):
                         f.write(format_nis_line(t, rec))
+        ir_counts = {}
+        for r in per_rank if args.imu_rate else []:
+            for j, (rows, n_rec, dropped) in r['ir'].items():
+                ir_counts[j] = (int(n_rec), int(dropped), len(rows))
+                with open(os.path.join(args.out, 'output_%s_offset%d_imu.txt' % (jobs[j][0], int(jobs[j][1]))), 'w') as f:
+                    for row in rows:
+                        f.write('%.6f ' % row[0] + ' '.join('%.9f' % v for v in row[1:]) + '\n')
         rep = sweep_report(jobs, per_rank, elapsed, world)
+        if args.imu_rate:
+            rep['imu_rate'] = dict(cap=args.imu_rate_cap, records=[ir_counts.get(j, (0, 0, 0))[0] for j in range(len(jobs))],
+                                   dropped_to_cap=[ir_counts.get(j, (0, 0, 0))[1] for j in range(len(jobs))],
+                                   lines=[ir_counts.get(j, (0, 0, 0))[2] for j in range(len(jobs))])
         if args.landmarks:
             rep['landmarks'] = dict(cap=args.landmark_cap, records=[lm_dropped.get(j, (0, 0))[0] for j in range(len(jobs))],
                                     dropped_to_cap=[lm_dropped.get(j, (0, 0))[1] for j in range(len(jobs))])
