@@ -876,8 +876,9 @@ int  av_quat_from_two_vectors(const double v0[3], const double v1[3], double q[4
 
 /* ---------------------------------------------------------------------------------------------
  * n_streams independent MSCKF filters stepped together (the throughput path of the back-end).  The
- * bookkeeping of MSCKF.feature_callback (msckf.py:177-228) runs in C++ inside the library for all
- * streams; each numeric phase is one batched launch over all streams (same kernels as av_msckf_*).
+ * whole of MSCKF.feature_callback (msckf.py:177-228) runs inside the library for all streams: state,
+ * observation map, selections and state injection live on the device, and a step is one fixed sequence
+ * of batched launches over all streams (the numeric kernels are those of av_msckf_*).
  *   R_imu_cam0_t_cam0_imu12 = [inv(T_imu_cam0)[:3,:3].T (9, row-major), inv(T_imu_cam0)[:3,3] (3)] (msckf.py:132-134)
  *   cov_init5 = [gyro_bias_cov, velocity_cov, acc_bias_cov, extrinsic_rotation_cov, extrinsic_translation_cov]
  *   noise4    = [gyro_noise, gyro_bias_noise, acc_noise, acc_bias_noise]        (config.py:71-75)
@@ -900,12 +901,12 @@ int  av_msckf_batch_push_imu(av_msckf_batch* b, const int32_t* stream_idx, const
  * The first step fixes the message capacity `cap` the device buffers are sized for; rows_cap must be >= 5*cap
  * (camera-pruning update) and >= 1664 (lost-feature update: 1500-row cut + one block), else AV_E_CAPACITY;
  * rows_cap = 0 at create sizes the block buffers from that first `cap` (max(2048, 5*cap + 64) rows).  A later step with a larger
- * cap REBUILDS them (and the device-resident observation store) for the wider message: the batch is drained and the device
+ * cap REBUILDS them (and the observation store) for the wider message: the batch is drained and the device
  * synchronised, the capacity grows geometrically (x1.5 at least) and the outgrown allocations stay parked until destroy -- pass
  * the largest cap at the first step (BatchedMSCKF(max_features=...)) when the width of the messages varies.  An explicit
  * rows_cap is never grown: a wider message than it can hold fails with AV_E_CAPACITY.
  * rows_cap rows are what each stream owns.  The lost features of one frame may need more (a blank frame drops every track at once:
- * ~4,500 rows at 150 tracks): the device-resident filter then takes the rows from a pool all streams share, allocated behind the
+ * ~4,500 rows at 150 tracks): the filter then takes the rows from a pool all streams share, allocated behind the
  * last stream's region -- max(131,072, n_streams * rows_cap) rows of ld doubles, AV_MSCKF_POOL_ROWS overrides -- and stops a
  * stream that finds the pool exhausted with AV_E_CAPACITY (av_msckf_batch_stream_status).
  * max_cam_states <= 24 (one back-end pass holds 144 columns = 6 per camera state); the reference's value is 20. */
@@ -925,9 +926,8 @@ int  av_msckf_batch_wait(av_msckf_batch* b, int max_pending);
  * copies enqueued on msg_stream -- the stream that produced them -- before the call returns, so the producer may overwrite them
  * at once; the filter's kernels run on the stream groups' own streams (a batch of one group: on `stream`) behind an event.
  * timestamps and out are host arrays and must stay valid until av_msckf_batch_wait has let the step retire.  Blocks while
- * more than two earlier steps are unfinished.  Needs the device-resident filter state (the default; AV_E_INVALID under
- * AV_MSCKF_STORE=host). */
-int  av_msckf_batch_device_resident(const av_msckf_batch* b);     /* 1: state + observation map on the device (default), 0: host bookkeeping */
+ * more than two earlier steps are unfinished. */
+int  av_msckf_batch_device_resident(const av_msckf_batch* b);     /* always 1: state + observation map live on the device (kept for callers that ask) */
 int  av_msckf_batch_submit_dev(av_msckf_batch* b, const int64_t* ids_dev, const double* uv_dev, const int32_t* n_feat_dev, int cap,
                                const double* timestamps, double* out, void* msg_stream, void* stream);
 int  av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, int n, void* stream);
@@ -954,14 +954,13 @@ int  av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, i
  * av_msckf_batch_set_odom_cov(b, enable): before the batch's first step (AV_E_INVALID afterwards).  Off (the default) the step launches
  * and reads back exactly what it did without the feature; on, the last per-stream kernel of the step is the instance that also writes
  * the records (no launch more) and one more asynchronous copy brings them to a pinned buffer of the step's ring slot: no wait and no
- * allocation inside a step.  Device-resident filter only: enabling it under AV_MSCKF_STORE=host is AV_E_INVALID, with a text that names
- * AV_MSCKF_STORE.
+ * allocation inside a step.
  * av_msckf_batch_next_odom_cov(b, cov_host): hands over the destination, n_streams * AV_ODOM_COV_DOUBLES doubles, of the records of
  * the NEXT av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires (step: on return; submit: once
  * av_msckf_batch_wait has let it retire) and must stay valid until then.  Stream groups each fill their own part.  AV_E_INVALID while
  * the feature is off.  A step without a destination computes its records and drops them.
  * Known limits: no conjugation for T_imu_body != I; the right (body-frame) rotation convention only -- the world-frame one is the
- * similarity by R_wb; no bias or extrinsic blocks; no innovation statistics; nothing on the host-bookkeeping path. */
+ * similarity by R_wb; no bias or extrinsic blocks; no innovation statistics. */
 #define AV_ODOM_COV_DOUBLES 120
 int  av_msckf_batch_set_odom_cov(av_msckf_batch* b, int enable);
 int  av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host);
@@ -990,14 +989,13 @@ int  av_msckf_batch_next_odom_cov(av_msckf_batch* b, double* cov_host);
  * av_msckf_batch_set_landmarks(b, cap): cap records per stream and step, 0 = off; before the batch's first step (AV_E_INVALID afterwards).
  * Off, the step launches and reads back exactly what it did without the feature; on, two per-stream kernels of the step are the instances
  * that also write the records (no launch more) and two more asynchronous copies bring records and counts to pinned buffers of the step's
- * ring slot: no wait and no allocation inside a step.  Device-resident filter only: under AV_MSCKF_STORE=host a non-zero cap is
- * AV_E_INVALID, with a text that names AV_MSCKF_STORE.
+ * ring slot: no wait and no allocation inside a step.
  * av_msckf_batch_next_landmarks(b, rec, n): hands over the destination -- n_streams * cap records and n_streams * 2 counts -- of the NEXT
  * av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps
  * its own destination.  Stream groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination
  * computes its records and drops them.
  * Known limits: positions as triangulated, not refined by the update; no per-landmark covariance; carried pruning features are not
- * republished; nothing on the host-bookkeeping path. */
+ * republished. */
 #define AV_LANDMARK_BYTES 40
 #define AV_LM_USED     1
 #define AV_LM_REJECTED 2
@@ -1034,12 +1032,12 @@ int  av_msckf_batch_next_landmarks(av_msckf_batch* b, av_landmark* rec, int32_t*
  * av_msckf_batch_set_stats(b, enable): before the batch's first step (AV_E_INVALID afterwards).  Off, the step launches and reads back
  * exactly what it did without the feature; on, two per-stream kernels of the step are the instances that also write the blocks (no
  * launch more) and one more asynchronous copy brings them to a pinned buffer of the step's ring slot: no wait and no allocation inside a
- * step.  Device-resident filter only: under AV_MSCKF_STORE=host enabling is AV_E_INVALID, with a text that names AV_MSCKF_STORE.
+ * step.
  * av_msckf_batch_next_stats(b, rec_host): hands over the destination -- n_streams records -- of the NEXT av_msckf_batch_step / _submit /
  * _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps its own destination.  Stream
  * groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination computes its records and drops them.
  * Known limits: sums only, no per-feature values; the gate's dof is the reference's; positions and rows are those of the device's
- * evaluation; nothing on the host-bookkeeping path. */
+ * evaluation. */
 #define AV_FILTER_STATS_BYTES 128
 #define AV_FS_RAN 1
 #define AV_FS_CUT 2
@@ -1073,14 +1071,13 @@ int  av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host);
  * one small kernel behind the first kernel of the step gathers the records from what that kernel leaves for the covariance propagation
  * (one launch more; no kernel of the step changes) and two more asynchronous copies bring records and counts to pinned buffers of the
  * step's ring slot: no wait and no allocation inside a step.  The records are the same bytes at every launch shape of the step.  The
- * whole n_streams * cap * 112-byte buffer is copied whatever the counts are.  Device-resident filter only: under AV_MSCKF_STORE=host a non-zero cap is
- * AV_E_INVALID, with a text that names AV_MSCKF_STORE.
+ * whole n_streams * cap * 112-byte buffer is copied whatever the counts are.
  * av_msckf_batch_next_imu_rate(b, rec, n): hands over the destination -- n_streams * cap records and n_streams * 2 counts -- of the NEXT
  * av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps
  * its own destination.  Stream groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination
  * computes its records and drops them.
  * Known limits: no propagation past the frame time through samples the filter has not consumed yet ("pose now"); no covariance per
- * record; no biases in the record; records arrive with the step's read-back, not earlier; nothing on the host-bookkeeping path. */
+ * record; no biases in the record; records arrive with the step's read-back, not earlier. */
 #define AV_IMU_STATE_BYTES 112
 typedef struct av_imu_state { double t, p[3], q[4], v[3], w[3]; } av_imu_state;
 int  av_msckf_batch_set_imu_rate(av_msckf_batch* b, int cap);
@@ -1106,8 +1103,8 @@ int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* st
  * av_msckf_batch_restart(b, stream_idx, n): n stream indices of the batch (of the whole batch, whatever its stream groups).  Legal at any
  * time: before the first step (host state only: there is no device state yet) and with steps queued -- it then drains the queue first,
  * like av_msckf_batch_launch_shape; the queued steps retire as steps of the old life and their outputs are delivered.  n = 0 is a
- * no-op, an index listed twice counts once, an index out of range is AV_E_INVALID with nothing touched.  Device-resident filter only:
- * under AV_MSCKF_STORE=host the call is AV_E_INVALID, with a text that names AV_MSCKF_STORE.  Returns when the device state is reset.
+ * no-op, an index listed twice counts once, an index out of range is AV_E_INVALID with nothing touched.  Returns when the device state
+ * is reset.
  *   Reset, host:   the IMU buffer is EMPTIED -- samples pushed before the call belong to the old life, and the stream goes live again
  *                  only after initialize_gravity_and_bias has seen 200 new samples (msckf.py:230-249); the gravity / first-image /
  *                  initialisation-sent flags, the camera-state id counter, state and extrinsics (the batch's create-time values);
@@ -1129,21 +1126,19 @@ int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* st
  *                  that belongs to the engine and not to the stream; the message of the last step (av_frontend_features_dev) until the
  *                  next step replaces it.
  * Ids repeat across lives: a consumer that keys on feature or camera-state ids keeps a generation count per stream (the Python classes
- * do: `generation`).  Known limits: the filter's restart drains the queue; no save or restore of a stream's state; nothing on the
- * host-bookkeeping path. */
+ * do: `generation`).  Known limits: the filter's restart drains the queue; no save or restore of a stream's state. */
 int  av_msckf_batch_restart(av_msckf_batch* b, const int32_t* stream_idx, int n);
 int  av_frontend_restart(av_frontend* fe, const int32_t* stream_idx, int n, void* stream);
 /* Run statistics over all streams (drain first): [steps, stream-steps that ran prune_cam_state_buffer (msckf.py:712-786),
- * stream-steps whose lost-feature candidates outgrew rows_cap (device-resident filter: rows taken from the shared overflow pool;
- * AV_MSCKF_STORE=host: gated first, stored in a second pass), device-buffer
+ * stream-steps whose lost-feature candidates outgrew rows_cap (rows taken from the shared overflow pool), device-buffer
  * reallocations after the first step (0 in a correctly pre-sized run), min camera states, max camera states,
  * min map features, max map features].  bench.py uses it to prove that the timed region is the steady state. */
 int  av_msckf_batch_counters(av_msckf_batch* b, int64_t out8[8]);
 /* What the batch really launched (no reference counterpart; drains the queue first): out17[0] = number of stream groups (a batch
  * without sub-batches reports 1; at most 8), and for group g out17[1 + 2g] = its stream count, out17[2 + 2g] = the workgroup size the
  * per-stream filter kernels (dk_begin4 / dk_cov / dk_mid / dk_finish) were launched with in the group's LAST enqueued step: 64 (one
- * wavefront per stream) or 256 (four); 0 before the group's first step and under AV_MSCKF_STORE=host.  The value is recorded at
- * the launch, not recomputed here.  The rule it reports is per GROUP, not per batch: a device-resident batch of n_streams >= 1,024 is
+ * wavefront per stream) or 256 (four); 0 before the group's first step.  The value is recorded at
+ * the launch, not recomputed here.  The rule it reports is per GROUP, not per batch: a batch of n_streams >= 1,024 is
  * split into 2 groups of ceil(n_streams / 2) streams (the last one holds the remainder; AV_MSCKF_GROUPS overrides the count), and
  * each group takes 64 when ITS stream count is >= 1,024, else 256 (AV_DK_WG=64|256 forces one for all groups).  So 1,023 streams run as
  * [(1023, 256)], 1,024 as [(512, 256), (512, 256)], 2,047 as [(1024, 64), (1023, 256)], and only from 2,048 streams up --
@@ -1224,7 +1219,7 @@ int  av_msckf_predict_ops_dev_rate(av_msckf* ctx, int n_streams, int wg, int cam
  * covariance update) spent on the device summed over stream groups, 0].  The time needs enable = 1 on an earlier call (two HIP
  * events per phase and group); enable = 0 switches it off, enable < 0 only reads. */
 int  av_msckf_batch_work(av_msckf_batch* b, int enable, double out8[8]);
-/* The same two stages counted as the kernels EXECUTE them (drain first; device-resident path, zeros otherwise): out2 = [fp64 flops of
+/* The same two stages counted as the kernels EXECUTE them (drain first; zeros before the first step): out2 = [fp64 flops of
  * the gating tests on the block-sparse shapes -- H_x as 4 x 6 blocks, the gate matrix from the M^2 6 x 6 blocks of P, reflectors applied
  * to it from both sides: ~0.6 MFLOP for a 21-observation track where the dense formula above says 5.5 --, fp64 flops of the updates
  * over the touched columns -- Gram compression m (nc+1)^2 + (nc+1)^3/3 where a stream stacks more rows than one pass, T^T 2 n nc k,

@@ -304,7 +304,7 @@ def _live():
 
 def test_lifecycle_and_switch(cfg, monkeypatch):
     """On: exactly one device buffer of S * 128 bytes and one pinned buffer of S * 128 bytes per ring slot more than off, nothing left
-    after close().  Off: stats= raises, next_stats is refused; the switch is refused after the first step and on the host-bookkeeping path."""
+    after close().  Off: stats= raises, next_stats is refused; the switch is refused after the first step."""
     from uav_airvision_amd import _native as N
     from uav_airvision_amd._native import AirvisionError
     from uav_airvision_amd.msckf_ops import FILTER_STATS_DTYPE, BatchedMSCKF
@@ -341,12 +341,6 @@ def test_lifecycle_and_switch(cfg, monkeypatch):
         assert b'av_msckf_batch_set_stats' in N.lib().av_last_error()
     finally:
         bat.close()
-    monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    with pytest.raises(AirvisionError, match='AV_MSCKF_STORE'):
-        BatchedMSCKF(cfg, 1, stats=True)
-    host = BatchedMSCKF(cfg, 1)
-    assert not host.device_resident()
-    host.close()
     assert _live() == base
 
 

@@ -211,7 +211,7 @@ def _live():
 def test_off_means_off(cfg, monkeypatch):
     """Off: the twelve doubles, get_state and get_cov of every step are bit-identical to the run with the records on and the launch shape
     is the same; not a byte of device or pinned memory more than the records' own buffers; imu_states= raises.  The switch is refused
-    after the first step, with a cap outside 0 .. 4096, on the host-bookkeeping path; next without set is refused."""
+    after the first step and with a cap outside 0 .. 4096; next without set is refused."""
     from uav_airvision_amd import _native as N
     from uav_airvision_amd._native import AirvisionError
     from uav_airvision_amd.msckf_ops import IMU_STATE_DTYPE, BatchedMSCKF
@@ -261,12 +261,6 @@ def test_off_means_off(cfg, monkeypatch):
         with pytest.raises(ValueError, match='imu_rate_cap'):
             BatchedMSCKF(cfg, 1, imu_rate=True, imu_rate_cap=cap)
     assert _live() == base
-    monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    with pytest.raises(AirvisionError, match='AV_MSCKF_STORE'):
-        BatchedMSCKF(cfg, 1, imu_rate=True)
-    host = BatchedMSCKF(cfg, 1)
-    assert not host.device_resident()
-    host.close()
 
 
 # ---- (vi) ----------------------------------------------------------------------------------------------------------------------------

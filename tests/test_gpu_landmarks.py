@@ -238,7 +238,7 @@ def _live():
 def test_off_means_off(cfg, monkeypatch):
     """Off: the poses are bit-identical to a run with the map on, no byte of device or pinned memory more than without the feature (the
     run with the map on holds exactly its record and count buffers more: one device pair, one pinned pair per ring slot), landmarks=
-    raises; the switch is refused after the first step and on the host-bookkeeping path."""
+    raises; the switch is refused after the first step."""
     from uav_airvision_amd import _native as N
     from uav_airvision_amd._native import AirvisionError
     from uav_airvision_amd.msckf_ops import LANDMARK_DTYPE, BatchedMSCKF
@@ -276,12 +276,6 @@ def test_off_means_off(cfg, monkeypatch):
         assert b'av_msckf_batch_set_landmarks' in N.lib().av_last_error()
     finally:
         bat.close()
-    monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    with pytest.raises(AirvisionError, match='AV_MSCKF_STORE'):
-        BatchedMSCKF(cfg, 1, landmarks=True)
-    host = BatchedMSCKF(cfg, 1)
-    assert not host.device_resident()
-    host.close()
 
 
 def test_abi_record_layout():

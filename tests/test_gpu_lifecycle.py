@@ -175,14 +175,13 @@ def test_frontend_with_every_optional_buffer_through_the_step_paths(grey):
 
 # ---- filter --------------------------------------------------------------------------------------------------------------------
 # `devbuf_growths` of counters() after filter_sequence, as the parent commit (the last one with the four hand-written allocators)
-# reports it for the same sequence on the same GPU: the wider message of the later steps rebuilds the device-resident store once;
-# the host-bookkeeping path's per-step buffers are sized by the reserve and the wider reserve reallocates them.
-PARENT_GROWTHS = {'device': 1, 'host': 37}
+# reports it for the same sequence on the same GPU: the wider message of the later steps rebuilds the device-resident store once.
+PARENT_GROWTHS = {'device': 1}
 
 
 def filter_sequence(store, on_step=lambda: None):
-    """Two streams, device-resident (store 'device', with odom_cov) or host-bookkeeping (store 'host': AV_MSCKF_STORE=host is set
-    by the caller before this): ten steps with 64-wide messages, two with 192-wide ones.  Returns counters()."""
+    """Two streams with odom_cov (store 'device': the only store there is): ten steps with 64-wide messages, two with 192-wide ones.
+    Returns counters()."""
     from uav_airvision_amd.config import ConfigEuRoC
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.synth import SyntheticFeatureStream
@@ -219,16 +218,17 @@ def filter_sequence(store, on_step=lambda: None):
         bat.close()
 
 
-@pytest.mark.parametrize('store', ['device', 'host'])
+@pytest.mark.parametrize('store', ['device'])
 def test_batched_filter_releases_everything_and_grows_as_the_parent_did(store, monkeypatch):
-    if store == 'host':
-        monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    else:
-        monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
+    monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
     counters = []
-    two_cycles(lambda peak: counters.append(filter_sequence(store, peak.sample)), (DEV, PINNED, EVENTS, STREAMS))
+    # a batch of one stream group runs on the caller's stream and owns none of its own; every group of several owns one
+    monkeypatch.delenv('AV_MSCKF_GROUPS', raising=False)
+    two_cycles(lambda peak: counters.append(filter_sequence(store, peak.sample)), (DEV, PINNED, EVENTS))
     for c in counters:
         assert c['devbuf_growths'] == PARENT_GROWTHS[store], c
+    monkeypatch.setenv('AV_MSCKF_GROUPS', '2')
+    two_cycles(lambda peak: filter_sequence(store, peak.sample), (DEV, PINNED, EVENTS, STREAMS))
 
 
 def test_single_filter_releases_everything():

@@ -144,25 +144,19 @@ def test_end_to_end_matches_reference_golden(dropin, cfg, name):
     flt.close()
 
 
-@pytest.mark.parametrize('groups,store', [(1, 'device'), (2, 'device'), (1, 'device-w64'), (1, 'host'), (2, 'host')])
+@pytest.mark.parametrize('groups,store', [(1, 'device'), (2, 'device'), (1, 'device-w64')])
 def test_batched_filters_match_reference_golden_and_oracle(cfg, groups, store, monkeypatch):
     """Three independent streams stepped together by the C++/HIP batched filter: stream 0 reproduces the
     reference's own golden run; all streams follow the numpy oracle frame by frame.  groups=2 splits the batch
     into two concurrently stepped stream groups (streams {0,1} and {2}), as large batches are by default.
-    store='host' runs the same checks through the host-bookkeeping path (AV_MSCKF_STORE=host: the observation map and the
-    selections on the host, the numeric phases by the same kernels) -- the fallback for shapes the device-resident store
-    does not cover; it stays in the library only as long as it stays tested.  store='device-w64': the per-stream kernels of the
-    device-resident path as ONE wavefront per stream (AV_DK_WG=64), the launch shape batches of 1,024 streams and more take by
+    store='device-w64': the per-stream kernels as ONE wavefront per stream (AV_DK_WG=64), the launch shape batches of 1,024 streams and more take by
     themselves -- three streams would get four wavefronts."""
     monkeypatch.setenv('AV_MSCKF_GROUPS', str(groups))
     monkeypatch.delenv('AV_DK_WG', raising=False)
     if store == 'device-w64':
         monkeypatch.setenv('AV_DK_WG', '64')
         store = 'device'
-    if store == 'host':
-        monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    else:
-        monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
+    monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
     from oracle.msckf_np import OracleMSCKF
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.synth import SyntheticFeatureStream
@@ -173,7 +167,7 @@ def test_batched_filters_match_reference_golden_and_oracle(cfg, groups, store, m
                SyntheticFeatureStream(cfg, seed=22, n_frames=n_frames, n_features=140)]
     S = len(streams)
     bat = BatchedMSCKF(cfg, S)
-    assert bat.device_resident() == (store == 'device')
+    assert bat.device_resident()
     oras = [OracleMSCKF(cfg) for _ in streams]
     its = [iter(s.imu) for s in streams]
     pend = [next(it, None) for it in its]
@@ -481,8 +475,7 @@ def test_overflow_pool_exhaustion_stops_the_stream_with_a_capacity_error(cfg, mo
                SyntheticFeatureStream(cfg, seed=92, n_frames=n_frames, n_features=40)]
     S = len(streams)
     bat = BatchedMSCKF(cfg, S, rows_cap=2048)
-    if not bat.device_resident():
-        bat.close(); pytest.skip('host-bookkeeping path (AV_MSCKF_STORE=host): no pool')
+    assert bat.device_resident()
     its = [iter(s.imu) for s in streams]
     pend = [next(it, None) for it in its]
     cap = 192
@@ -515,19 +508,12 @@ def test_overflow_pool_exhaustion_stops_the_stream_with_a_capacity_error(cfg, mo
     bat.close()
 
 
-@pytest.mark.parametrize('store', ['device', 'host'])
-def test_blank_frame_drops_every_track_at_once(cfg, store, monkeypatch):
+def test_blank_frame_drops_every_track_at_once(cfg, monkeypatch):
     """A blank / blurred frame: the feature message is empty, so every live track is lost in the same frame and the
     lost-feature candidates reserve far more rows than rows_cap (here ~3-4 k against 2048).  The reference handles any
-    number (msckf.py:614-676: gate in map order, stop after > 1500 stacked rows); the device-resident batch gives such a
-    stream rows from the overflow pool all streams share (the host-bookkeeping path gates first and stores only the stacked
-    features second).  Must equal the numpy oracle on every frame, before, at and after.
-    store='host' (AV_MSCKF_STORE=host) is the only GPU test that takes the host chain's synchronous fallback (b_blocks_and_update:
-    a stream's candidates outgrow rows_cap), at frames 17 and 18."""
-    if store == 'host':
-        monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    else:
-        monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
+    number (msckf.py:614-676: gate in map order, stop after > 1500 stacked rows); the batch gives such a
+    stream rows from the overflow pool all streams share.  Must equal the numpy oracle on every frame, before, at and after."""
+    monkeypatch.delenv('AV_MSCKF_STORE', raising=False)
     from oracle.msckf_np import OracleMSCKF
     from uav_airvision_amd.msckf_ops import BatchedMSCKF
     from uav_airvision_amd.synth import SyntheticFeatureStream, feature_msg_t
@@ -536,7 +522,7 @@ def test_blank_frame_drops_every_track_at_once(cfg, store, monkeypatch):
                SyntheticFeatureStream(cfg, seed=92, n_frames=n_frames, n_features=60)]
     S = len(streams)
     bat = BatchedMSCKF(cfg, S, rows_cap=2048)
-    assert bat.device_resident() == (store == 'device')
+    assert bat.device_resident()
     oras = [OracleMSCKF(cfg) for _ in streams]
     its = [iter(s.imu) for s in streams]
     pend = [next(it, None) for it in its]
@@ -571,12 +557,35 @@ def test_blank_frame_drops_every_track_at_once(cfg, store, monkeypatch):
             err = max(np.abs(out[i, 2:5] - s.position).max(), np.abs(out[i, 5:9] - s.orientation).max(), np.abs(out[i, 9:12] - s.velocity).max())
             assert err < 1e-6, (k, i, err)
     c = bat.counters()
-    assert c['two_pass_streams'] >= 2, c                 # the blank frames really outgrew rows_cap (pool / two-pass route taken)
+    assert c['two_pass_streams'] >= 2, c                 # the blank frames really outgrew rows_cap (pool route taken)
     assert c['devbuf_growths'] == 0, c                   # nothing was reallocated after the first step's reserve
     for i in range(S):
         P, Po = bat.get_cov(i), oras[i].state_cov
         assert np.abs(P - Po).max() <= 1e-6 * np.abs(Po).max()
     bat.close()
+
+
+def test_store_switch_no_longer_selects_a_path(cfg):
+    """AV_MSCKF_STORE=host once chose a host-bookkeeping filter.  The library no longer reads the variable: with it set a batch is
+    device-resident, the odometry covariance (which that path refused) arrives with every step, and every step's output equals,
+    bit for bit, the run with the variable unset.  25 frames of two 60-feature streams: past the first camera pruning (frame 19)."""
+    import filter_harness as H
+    from uav_airvision_amd.synth import SyntheticFeatureStream
+    n_frames = 25
+    streams = [SyntheticFeatureStream(cfg, seed=71 + i, n_frames=n_frames, n_features=60) for i in range(2)]
+
+    def check(k, bat, out, cur):
+        assert os.environ.get('AV_MSCKF_STORE') == 'host'
+        assert bat.device_resident()
+        assert cur['cov'] is not None and cur['cov'].shape == (2, 120), k
+
+    host = H.run(cfg, streams, n_frames, odom_cov=True, env={'AV_MSCKF_STORE': 'host'}, check=check)
+    unset = H.run(cfg, streams, n_frames, odom_cov=True)
+    assert host['counters']['prune_stream_steps'] > 0, host['counters']
+    assert any(np.any(c) for c in host['covs'])              # records were written, not only delivered
+    for k in range(n_frames):
+        assert H.same(host['outs'][k], unset['outs'][k]), k
+        assert H.same(host['covs'][k], unset['covs'][k]), k
 
 
 def test_default_trajectory_file_is_written_and_parses(dropin, cfg, tmp_path, monkeypatch):

@@ -206,12 +206,6 @@ def test_off_means_off(cfg, monkeypatch):
         assert b'av_msckf_batch_set_odom_cov' in N.lib().av_last_error()
     finally:
         bat.close()
-    monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    with pytest.raises(AirvisionError, match='AV_MSCKF_STORE'):
-        BatchedMSCKF(cfg, 1, odom_cov=True)
-    host = BatchedMSCKF(cfg, 1)
-    assert not host.device_resident()
-    host.close()
 
 
 # ---- (f) -------------------------------------------------------------------------------------------------------------------------

@@ -230,18 +230,6 @@ def test_edges(cfg, monkeypatch):
         if k >= 8:
             assert e['outs'][k][2, 0] == 0.0 and H.same(e['outs'][k][2], c['outs'][0][0]), k          # restarted and idle: the pose record of a stream that never ran
 
-    # refused on the host-bookkeeping path, with the wording of the three output switches
-    monkeypatch.setenv('AV_MSCKF_STORE', 'host')
-    bat = BatchedMSCKF(cfg, 2)
-    try:
-        with pytest.raises(N.AirvisionError) as err:
-            bat.restart([0])
-        assert err.value.code == N.AV_E_INVALID and 'AV_MSCKF_STORE' in str(err.value) and 'device-resident' in str(err.value)
-        assert bat.generation.tolist() == [0, 0]
-    finally:
-        bat.close()
-    monkeypatch.delenv('AV_MSCKF_STORE')
-
 
 def test_restart_allocates_nothing(cfg, monkeypatch):
     """av_debug_live_resources reads the same before and after ten restarts, and what the batch holds is back at four zeros after

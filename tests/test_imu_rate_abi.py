@@ -1,6 +1,5 @@
 """The IMU-rate record of include/airvision.h ("IMU-rate odometry") as the C compiler lays it out, against its ctypes and NumPy mirrors;
-the symbols; and the refusals that need no step of the filter (CPU: compiles a probe, creates a batch on the host-bookkeeping path and
-one that never steps -- no kernel is launched)."""
+the symbols; and the refusals that need no batch (CPU: compiles a probe, no kernel is launched)."""
 import ctypes
 import os
 import subprocess
@@ -42,7 +41,7 @@ def test_unpack_imu_states_returns_the_written_records():
 
 def test_calls_without_a_batch_are_refused_with_a_text():
     """No batch, a cap outside 0 .. 4096, no destination: AV_E_INVALID and a text that names the call, before anything is touched.  (The
-    refusals that need a batch -- the host-bookkeeping path, after the first step, next without set -- are in tests/test_gpu_imu_rate.py:
+    refusals that need a batch -- after the first step, next without set -- are in tests/test_gpu_imu_rate.py:
     creating a batch needs a device.)"""
     from uav_airvision_amd import _native as N
     lib = N.lib()

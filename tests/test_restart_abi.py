@@ -41,7 +41,7 @@ def test_header_exports_and_ctypes_rows_agree():
 def test_the_contract_is_written_down():
     text = _header()
     sec = text[text.index('/* Stream restart:'):text.index('int  av_msckf_batch_restart(')]
-    for must in ('Not reset', 'av_msckf_batch_counters', 'AV_MSCKF_STORE', 'bit for bit', 'Nothing is allocated', '200 new samples', 'generation',
+    for must in ('Not reset', 'av_msckf_batch_counters', 'bit for bit', 'Nothing is allocated', '200 new samples', 'generation',
                  'av_frontend_prestage', 'masks', 'frame store'):
         assert must in sec, must
 

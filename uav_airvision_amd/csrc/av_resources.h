@@ -205,11 +205,11 @@ struct PinnedRing {
     int sent(hipStream_t st) { AV_HIP(hipEventRecord(ev[cur], st)); return AV_OK; }
 };
 
-// A device buffer of the batched filter that is uploaded every step, with its pinned (mapped) staging.
-// Growth is geometric and never frees inside a step: hipFree synchronises the whole device and queued copies / kernels of this or of
-// another stream group may still read the old allocation, so outgrown blocks stay with the owner until it releases.
-// sub_reserve() sizes every buffer for the worst case of a message capacity before the first step; `growths`
-// counts the (unexpected) reallocations after that and is reported by av_msckf_batch_counters (AvResources::growths).
+// A device buffer that is uploaded every step, with its pinned (mapped) staging.
+// Growth is geometric and never frees inside a step: hipFree synchronises the whole device and queued copies / kernels of another
+// stream may still read the old allocation, so outgrown blocks stay with the owner until it releases.  `growths` counts the
+// reallocations after the first reserve (AvResources::growths sums them).
+// (Its user was the host-bookkeeping form of the batched filter, which is gone; tests/native/resources_harness.cpp still drives it.)
 template <typename T>
 struct DevBuf {
     AvResources* res;

@@ -1059,45 +1059,6 @@ __device__ __forceinline__ void propagate_body(const PropArgs& a, double* P11s =
 }
 
 __global__ __launch_bounds__(256) void propagate_kernel(PropArgs a) { propagate_body(a); }
-// batched: block b applies samples first[b] .. first[b+1]-1 in order (one stream per block)
-__global__ __launch_bounds__(256) void propagate_batch_kernel(const PropArgs* arr, const int* first)
-{
-    AV_FILTER_PRIO();
-    __shared__ double P11s[IMU_DIM * IMU_DIM], PhiT[IMU_DIM * IMU_DIM];
-    const int i0 = first[blockIdx.x], i1 = first[blockIdx.x + 1];
-    if (i0 >= i1) return;                                   // block-uniform
-    const int tid = threadIdx.x, N = IMU_DIM;
-    double* P = arr[i0].P; const int n = arr[i0].n, ld = arr[i0].ld;
-    for (int i = tid; i < N * N; i += 256) { int r = i / N, c = i - r * N; P11s[i] = P[(size_t)r * ld + c]; PhiT[i] = r == c ? 1.0 : 0.0; }
-    __syncthreads();
-    for (int i = i0; i < i1; ++i) propagate_body(arr[i], P11s, PhiT);
-    // cross block with the frame's accumulated transition: every element of the new block is formed in registers
-    // from the old one before anything is overwritten
-    const int nc = n - N, tot = N * nc;
-    constexpr int PER = (IMU_DIM * 6 * 31 + 255) / 256;     // up to 31 camera states
-    double acc[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int e = tid + 256 * u;
-        double s = 0;
-        if (e < tot) {
-            const int r = e / nc, c = e - r * nc;
-            for (int k = 0; k < N; ++k) s += PhiT[r * N + k] * P[(size_t)k * ld + N + c];
-        }
-        acc[u] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int e = tid + 256 * u;
-        if (e < tot) {
-            const int r = e / nc, c = e - r * nc;
-            P[(size_t)r * ld + N + c] = acc[u];
-            P[(size_t)(N + c) * ld + r] = acc[u];
-        }
-    }
-    for (int i = tid; i < N * N; i += 256) { int r = i / N, c = i - r * N; P[(size_t)r * ld + c] = P11s[i]; }
-}
 
 // ================================================================================================
 // State augmentation (msckf.py:407-423)
@@ -1146,13 +1107,10 @@ __device__ __forceinline__ void augment_body(const AugArgs& a)
 }
 
 __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) { augment_body(a); }
-__global__ __launch_bounds__(256) void augment_batch_kernel(const AugArgs* arr) { AV_FILTER_PRIO(); augment_body(arr[blockIdx.x]); }
 
 // ================================================================================================
 // Delete the 6 rows/cols of one camera state (msckf.py:774-786)
 // ================================================================================================
-struct RemArgs { double* P; double* scratch; int n, ld, start0, start1; };     // start1 < 0: only one removal
-
 __device__ __forceinline__ void remove_cam_body(double* P, double* scratch, int n, int ld, int start)
 {
     // compact into scratch, then copy back (single workgroup; n <= 147)
@@ -1188,15 +1146,6 @@ __device__ __forceinline__ void remove_two_cams_body(double* P, double* scratch,
     }
 }
 __global__ __launch_bounds__(256) void remove_cam_kernel(double* P, double* scratch, int n, int ld, int start) { remove_cam_body(P, scratch, n, ld, start); }
-// batched: two removals per stream, the second index already refers to the matrix after the first removal
-__global__ __launch_bounds__(256) void remove_cam_batch_kernel(const RemArgs* arr)
-{
-    AV_FILTER_PRIO();
-    const RemArgs a = arr[blockIdx.x];
-    if (a.start0 < 0) return;
-    remove_cam_body(a.P, a.scratch, a.n, a.ld, a.start0);
-    if (a.start1 >= 0) { __syncthreads(); remove_cam_body(a.P, a.scratch, a.n - 6, a.ld, a.start1); }
-}
 
 // ================================================================================================
 // Stacked measurement update (msckf.py:548-602), one 1024-thread workgroup.
@@ -2236,7 +2185,7 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
     UpdArgs b = a.base[s];
     b.n = n_state;
     const int nc = 6 * __popcll(used);
-    const bool dead = b.mode == 2;                      // stopped by the host (msckf_batch.inc: b_fail_stream): no update, stacked = -1
+    const bool dead = b.mode == 2;                      // a stream the host marked as stopped: no update, stacked = -1
     const int m = (overflow || dead) ? 0 : stacked;
     // (the information form holds for any m >= 1; a stream the host marked for it never needs a Cholesky round)
     const int mode = (m > 0 && b.mode == 1 && !a.no_info && nc <= INFO_NC && m <= INFO_MAXROWS) ? 1 : 0;
@@ -2287,11 +2236,6 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
     }
 }
 
-__global__ __launch_bounds__(UT) void update_back_batch_kernel(const UpdArgs* __restrict__ arr)
-{
-    const UpdArgs a = arr[blockIdx.x];
-    if (a.m > 0) update_back(a);
-}
 // LDS of the two halves for a stream with m stacked rows over nc columns
 static inline size_t update_front_lds(int m) { return sizeof(double) * (2 * (size_t)m + 8); }
 static inline size_t update_back_lds(int m, int nc) { const size_t k = upd_k(m, nc); return sizeof(double) * (k * (k + 1) / 2 + 8 + 2 * (size_t)PANEL_Q * PANEL_W); }
@@ -2305,8 +2249,7 @@ static int msckf_lds_opt_in()
         const void* fns[5] = {reinterpret_cast<const void*>(feature_kernel8),
                               reinterpret_cast<const void*>(feature_kernel<16>), reinterpret_cast<const void*>(feature_kernel<64>), reinterpret_cast<const void*>(feature_kernel<256>),
                               reinterpret_cast<const void*>(update_front_kernel)};
-        const void* fns2[3] = {reinterpret_cast<const void*>(update_back_kernel), reinterpret_cast<const void*>(update_back_batch_kernel),
-                               reinterpret_cast<const void*>(upd_info_kernel)};
+        const void* fns2[2] = {reinterpret_cast<const void*>(update_back_kernel), reinterpret_cast<const void*>(upd_info_kernel)};
         for (const void* f : fns2) {
             hipFuncAttributes at;
             hipError_t e = hipFuncGetAttributes(&at, f);
@@ -2323,13 +2266,6 @@ static int msckf_lds_opt_in()
         return (int)AV_OK;
     }();
     return rc;
-}
-
-// diag(P)[12..14] of every stream (online_reset, msckf.py:829-835)
-__global__ void pos_var_kernel(const double* P, size_t p_stride, int ld, int S, double* out)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 3 * S) { int s = i / 3, k = 12 + i % 3; out[i] = P[s * p_stride + (size_t)k * ld + k]; }
 }
 
 }  // namespace

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void dk_migrate(DevArgs o, DevArgs n)
 // Build (or rebuild for a larger capacity) everything whose size depends on the capacity of a feature message.
 int dev_reserve(av_msckf_batch* b, int cap)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     if (cap <= d->cap) return AV_OK;
     if (cap >= (1 << 24)) { av_set_error("batched MSCKF: message capacity %d exceeds the store's link format", cap); return AV_E_CAPACITY; }
     const bool grow = d->cap > 0;
@@ -146,7 +146,7 @@ DevStamps& dev_fprof_long() { static DevStamps st(getenv("AV_DEV_FPROF") && atoi
 // per-stream constants of the update kernels (pointers into the group's work buffers); rebuilt when rows_cap changes
 int dev_upload_updbase(av_msckf_batch* b)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     std::vector<UpdArgs> base((size_t)b->S);
     for (int s = 0; s < b->S; ++s) {
         UpdArgs& u = base[s] = b_upd_args(b, s);
@@ -207,7 +207,7 @@ int dev_grid_hint(const DevPath* d, int idx, int worst, int floor_teams = 256)
 // ph = 0: remove_lost_features (msckf.py:614-676), 1: prune_cam_state_buffer (:712-786).
 int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cnt_step)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     const DevArgs& A = d->A;
     const int S = b->S, cap = d->cap;
     const bool cut1500 = ph == 0;
@@ -313,7 +313,7 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
 // parity-test tap (av_msckf_batch_debug_*): what the phase that has just run computed, read back synchronously
 int dev_debug_capture(av_msckf_batch* b, int ph, hipStream_t stm)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     const DevArgs& A = d->A;
     const int S = b->S;
     AV_HIP(hipStreamSynchronize(stm));
@@ -359,7 +359,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
 int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, const int32_t* n_feat, int cap, const double* timestamps,
                bool dev_msg, hipEvent_t ready, hipStream_t stm)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     const int S = b->S;
     AV_HIP(hipSetDevice(b->device));
     int rc;
@@ -461,7 +461,7 @@ static_assert(std::is_same<decltype(&dk_mid_lm_st), void (*)(DevArgs, LmOut, DUp
               std::is_same<decltype(&dk_finish_cov_lm_st), void (*)(DevArgs, double*, LmOut, DUpdStats*)>::value, "dev_launch_outs: covariance, landmarks, statistics");
 KOuts dev_kouts(const av_msckf_batch* b)          // the one place that gives the table's device arrays their types
 {
-    char* const* p = b->dev->outs_d;
+    char* const* p = b->dev.outs_d;
     return {(double*)p[O_COV], LmOut{(DLandmark*)p[O_LM], (int*)p[O_LMN], b->out_set[F_LM]}, (DUpdStats*)p[O_STATS],
             IrOut{(DImuState*)p[O_IR], (int*)p[O_IRN], b->out_set[F_IR]}};
 }
@@ -483,7 +483,7 @@ int dev_launch_outs(bool finish, const av_msckf_batch* b, DevArgs& a, int wg, hi
 // host decisions: the sequence is the same every step, which is what lets it be captured as a graph)
 int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_t stm)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     DevSlot& sl = d->slot[k];
     const int S = b->S;
     int rc;
@@ -531,7 +531,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
 // the entry's bytes per stream each; NULL: the step has no destination for that array and it is dropped)
 int dev_finish(av_msckf_batch* b, int k, double* out, const StepOuts& outs)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     DevSlot& sl = d->slot[k];
     if (!sl.in_flight) return AV_OK;
     AV_HIP(hipEventSynchronize(sl.done));
@@ -553,7 +553,7 @@ int dev_finish(av_msckf_batch* b, int k, double* out, const StepOuts& outs)
 // the group; the call returns when the kernel has run, so any later step or read-back, on whatever stream, finds the new state.
 int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm)
 {
-    DevPath* d = b->dev;
+    DevPath* d = &b->dev;
     if (n <= 0 || d->cap == 0) return AV_OK;                 // before the first step there is no device state: the host's reset is all
     AV_HIP(hipSetDevice(b->device));
     memcpy(d->rs_list_h, list, sizeof(int) * (size_t)n);
@@ -590,7 +590,7 @@ const char* dev_fail_message(int code, int* av_code)
 int dev_read_state(av_msckf_batch* b, int s, DState* D)
 {
     AV_HIP(hipSetDevice(b->device));
-    AV_HIP(hipMemcpy(D, b->dev->A.st + s, sizeof(DState), hipMemcpyDeviceToHost));
+    AV_HIP(hipMemcpy(D, b->dev.A.st + s, sizeof(DState), hipMemcpyDeviceToHost));
     return AV_OK;
 }
 

@@ -403,14 +403,14 @@ class BatchedMSCKF(object):
         max_features when the width of the feature arrays can vary.  An explicit rows_cap is never grown.
         config.max_cam_state_size <= 24 (reference: 20).
         odom_cov=True: every step also computes the covariance of what it publishes (ODOM_COV_FIELDS; `step / submit / submit_dev(...,
-        cov=)`, `last_cov`, `unpack_odom_cov`).  Device-resident filter only.
+        cov=)`, `last_cov`, `unpack_odom_cov`).
         landmarks=True: every step also publishes the features its two updates triangulated, up to landmark_cap records per stream
-        (LANDMARK_DTYPE; `step / submit / submit_dev(..., landmarks=)`, `last_landmarks`, `unpack_landmarks`).  Device-resident filter only.
+        (LANDMARK_DTYPE; `step / submit / submit_dev(..., landmarks=)`, `last_landmarks`, `unpack_landmarks`).
         stats=True: every step also publishes the innovation statistics of its two updates, FILTER_STATS_DTYPE[S, 2] (`step / submit /
-        submit_dev(..., stats=)`, `last_stats`, `unpack_filter_stats`).  Device-resident filter only.
+        submit_dev(..., stats=)`, `last_stats`, `unpack_filter_stats`).
         imu_rate=True: every step also publishes the state after every IMU sample its prediction integrated, the last imu_rate_cap
         (1 .. 4096) of them per stream (IMU_STATE_DTYPE; `step / submit / submit_dev(..., imu_states=)`, `last_imu_states`,
-        `unpack_imu_states`).  Predictions from the previous step's state; `w` is in the IMU frame.  Device-resident filter only."""
+        `unpack_imu_states`).  Predictions from the previous step's state; `w` is in the IMU frame."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -560,7 +560,7 @@ class BatchedMSCKF(object):
         return out
 
     def device_resident(self):
-        """True when the filter state and the observation map live on the device (the default; `submit_dev` needs it)."""
+        """Always True: the filter state and the observation map live on the device.  Kept for callers that still ask."""
         return N.lib().av_msckf_batch_device_resident(self._h) == 1
 
     def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None, imu_states=None):
@@ -609,8 +609,8 @@ class BatchedMSCKF(object):
 
     def counters(self):
         """Run statistics over all streams (av_msckf_batch_counters); drains the queue first.  `two_pass_streams` counts the stream-steps
-        whose lost-feature candidates needed more rows than `rows_cap`: the device-resident filter serves them from the overflow pool all
-        streams share (AV_MSCKF_POOL_ROWS; an exhausted pool stops the stream with AV_E_CAPACITY), the host-bookkeeping path in two passes."""
+        whose lost-feature candidates needed more rows than `rows_cap`: the filter serves them from the overflow pool all
+        streams share (AV_MSCKF_POOL_ROWS; an exhausted pool stops the stream with AV_E_CAPACITY)."""
         self.wait(0)
         o = (C.c_int64 * 8)()
         N.check(N.lib().av_msckf_batch_counters(self._h, C.byref(o)))
@@ -619,7 +619,7 @@ class BatchedMSCKF(object):
     def launch_shape(self):
         """[(streams, workgroup size), ...] per stream group, as launched (av_msckf_batch_launch_shape); drains the queue first.  The
         workgroup size is what the per-stream kernels of the group's last step ran with: 64 (one wavefront per stream: groups of at least
-        1,024 streams, or AV_DK_WG=64), 256 (four), 0 before the first step and on the host-bookkeeping path."""
+        1,024 streams, or AV_DK_WG=64), 256 (four), 0 before the first step."""
         self.wait(0)
         o = (C.c_int32 * 17)()
         N.check(N.lib().av_msckf_batch_launch_shape(self._h, C.byref(o)))
