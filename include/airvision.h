@@ -1076,12 +1076,55 @@ int  av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host);
  * av_msckf_batch_step / _submit / _submit_dev; it is filled when that step retires and must stay valid until then.  A queued step keeps
  * its own destination.  Stream groups each fill their own part.  AV_E_INVALID while the feature is off.  A step without a destination
  * computes its records and drops them.
- * Known limits: no propagation past the frame time through samples the filter has not consumed yet ("pose now"); no covariance per
- * record; no biases in the record; records arrive with the step's read-back, not earlier. */
+ * Known limits: no propagation past the frame time through samples the filter has not consumed yet ("pose now") and no covariance per
+ * record here -- both are the "Forecast" below; no biases in the record; records arrive with the step's read-back, not earlier. */
 #define AV_IMU_STATE_BYTES 112
 typedef struct av_imu_state { double t, p[3], q[4], v[3], w[3]; } av_imu_state;
 int  av_msckf_batch_set_imu_rate(av_msckf_batch* b, int cap);
 int  av_msckf_batch_next_imu_rate(av_msckf_batch* b, av_imu_state* rec, int32_t* n);
+/* Forecast: the pose a step leaves, carried forward to the newest IMU sample the caller has pushed, with its covariance ("pose now").
+ * A step's published pose is the state at the camera frame's time; by the time it is read the vehicle has moved on by the front-end's
+ * latency, the queue and the step.  The IMU samples of that interval are already in the stream's buffer -- pushed, not consumed, since a
+ * step takes only samples with t <= frame time.  Off by default.  On, every step yields for every stream a count pair n[s][2] =
+ * (had, written), up to `cap` records av_imu_state, and one covariance record cov[s][AV_ODOM_COV_DOUBLES].
+ *   Pending samples  When a step is submitted for a stream with frame time t_f it takes its own samples first, exactly as without the
+ *            feature; what the stream's buffer then holds has t > t_f: the pending samples, in push order, `had` of them.  The
+ *            selection is made under the stream's lock in the same pass.  They are NOT removed: the next step consumes them as it always
+ *            would.  The forecast integrates the first written = min(had, cap) of them -- the FIRST cap, not the last: the chain cannot skip
+ *            samples, and pushing seconds of IMU ahead must not buy unbounded work per step.  had > written says "now" was not reached.
+ *            (written can fall short of min(had, cap) only when samples arrive while the step is being staged, beyond the staging's slack.)
+ *            "Submitted" is the moment the step's own samples are selected: inside the call for a batch of one stream group; for stream
+ *            groups, by each group's worker when it launches the step -- inside av_msckf_batch_step, and for _submit / _submit_dev
+ *            possibly a moment after the call returns, so samples pushed meanwhile count as pending.
+ *   Start    the state and covariance the step leaves on the device, exactly what the next step's prediction starts from: after both
+ *            updates and the camera removal; after online_reset on a reset step (the covariance then starts from the re-initialised
+ *            block; the odometry-covariance record of that step does not); with the updated biases and the null states as the update
+ *            left them.
+ *   Per sample  the state by predict_new_state (msckf.py:341-388); the 21 x 21 IMU block of the covariance by process_model's formula
+ *            (msckf.py:275-339), observability patches and symmetrisation included, with a private copy of the null states advanced as
+ *            process_model advances them.  The camera blocks of P play no part: the IMU block depends on nothing else.
+ *   Records  record k: the k-th pending sample's stamp t; p, q, v right after predict_new_state for it, in the filter's own frame;
+ *            w = gyro - gyro_bias with the updated bias.  The first record's dt is t - imu_state.timestamp as the step left it; the
+ *            forecast's reached time is the last written record's t.  Records past `written` are unspecified.
+ *   cov      the odometry covariance, in the layout and error coordinates of "Odometry covariance": the same J, at q of the LAST WRITTEN
+ *            record with R_ic and t_ci as the step leaves them, applied to the propagated block.  written = 0: that map of the state and
+ *            block the step leaves.
+ *   Read-only  The forecast writes nothing the filter reads: a run with it on is bit for bit the run with it off in every other output
+ *            and in the final state.
+ * A stream that does not publish in the step -- no frame, no gravity yet, stopped, stopped during this step -- reads n = {0, 0} and 120 NaNs.
+ * av_msckf_batch_set_forecast(b, cap): cap records per stream and step, 0 = off, at most 4096 (AV_E_INVALID outside 0 .. 4096); before the
+ * batch's first step (AV_E_INVALID afterwards).  Off, the step launches, uploads and reads back exactly what it did without the feature.
+ * On: the pending samples ride in the upload of the step's own samples, one small upload addresses them; two kernels behind the step's last
+ * one (the state chain a lane per stream, then covariance, records and counts one wavefront per stream at every launch shape; no kernel of
+ * the step changes); three more asynchronous copies bring the arrays to pinned buffers of the step's ring slot.  No wait and no allocation
+ * inside a step: the IMU staging is sized for n_streams * cap pending samples when it is first built.  The same bytes at every launch shape.
+ * av_msckf_batch_next_forecast(b, rec, n, cov): hands over the destination -- n_streams * cap records, n_streams * 2 counts, n_streams *
+ * AV_ODOM_COV_DOUBLES doubles -- of the NEXT av_msckf_batch_step / _submit / _submit_dev; filled when that step retires, valid until then.
+ * A queued step keeps its own destination.  Stream groups each fill their own part.  AV_E_INVALID while the feature is off.  A step
+ * without a destination computes its arrays and drops them.
+ * Known limits: no forecast for a stream without a frame in the step; no call of its own outside a step; no biases in the record. */
+int  av_msckf_batch_set_forecast(av_msckf_batch* b, int cap);
+int  av_msckf_batch_next_forecast(av_msckf_batch* b, av_imu_state* rec, int32_t* n, double* cov);
 int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);     /* [state dim, camera states, map features] */
 /* Full host-side state of one stream -- every target of measurement_update's injection (msckf.py:568-595), for parity tests
  * (SURVEY 8b get_state): imu32 = [imu_state.timestamp, orientation q(4, JPL xyzw), position(3), velocity(3), gyro_bias(3),
@@ -1111,7 +1154,7 @@ int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* st
  *                  the failure code and text (av_msckf_batch_stream_status reads 0, ""); the parity-test tap's captures.
  *   Reset, device: the IMU state record, state dimension 21, no camera states, the stream's whole covariance region (create-time
  *                  diagonal, zero elsewhere), the observation store (empty, insertion counter 0, header clear, arrays as allocated), the
- *                  stream's rows of the pose, odometry-covariance, landmark, statistics and IMU-rate buffers.  Camera-state ids and the map's
+ *                  stream's rows of the pose, odometry-covariance, landmark, statistics, IMU-rate and forecast buffers.  Camera-state ids and the map's
  *                  insertion order begin again at 0.
  *   Not reset:     av_msckf_batch_counters and av_msckf_batch_work keep accumulating over all lives; the batch's configuration, its
  *                  output switches and capacities; every other stream.
@@ -1211,6 +1254,15 @@ int  av_msckf_predict_ops_dev_rate(av_msckf* ctx, int n_streams, int wg, int cam
                                    const double* imu, int n_imu, const double noise4[4],
                                    double* cam_q_dev, double* cam_p_dev, double* cam_qn_dev, double* P_dev,
                                    int32_t* redundant_out, void* stream, int cap, av_imu_state* rec_out, int32_t* n_out);
+/* The forecast's two kernels (tests only; "Forecast"), launched through the helper a step launches them through.  Streams are described by
+ * the flat host arrays of av_msckf_predict_ops_dev, state_io[43] and state_int_io[6]; `active` is an INPUT here: the arrays hold the state
+ * a step LEAVES.  P_dev: the device covariances [n_streams][p_stride], leading dimension ld.  imu[n_imu][7]; pend[n_streams][2] = (first,
+ * count) of every stream's pending samples in it.  cap = 1 .. 4096.  rec_out[n_streams][cap], n_out[n_streams][2] and
+ * cov_out[n_streams][AV_ODOM_COV_DOUBLES] are HOST arrays, uploaded as the caller filled them (a pre-fill shows what the kernels did not
+ * write) and read back; state_io and state_int_io come back as the kernels left them: unchanged.  Synchronises. */
+int  av_msckf_forecast_ops_dev(av_msckf* ctx, int n_streams, int ld, int64_t p_stride, double* state_io, int32_t* state_int_io,
+                               const double* imu, int n_imu, const int32_t* pend, const double noise4[4], double* P_dev, void* stream,
+                               int cap, av_imu_state* rec_out, int32_t* n_out, double* cov_out);
 /* Work done so far, for the filter stage's roofline (drain first): out8 = [algorithmic fp64 flops of the gating tests
  * (per feature with r = 4M-3 rows, n columns: 2rn^2 + 2r^2n + r^3/3; msckf.py:604-612), of the measurement updates on the
  * k = min(m, n) rows kept (S 2kn^2 + 2k^2n, Cholesky k^3/3, solve 2k^2n, (I-KH)P 4kn^2; msckf.py:562-602), of the reference's

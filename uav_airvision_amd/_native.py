@@ -285,6 +285,8 @@ SIGNATURES = {
     'av_msckf_batch_next_stats': (C.c_int, [_P, _P]),
     'av_msckf_batch_set_imu_rate': (C.c_int, [_P, C.c_int]),
     'av_msckf_batch_next_imu_rate': (C.c_int, [_P, _P, _P]),
+    'av_msckf_batch_set_forecast': (C.c_int, [_P, C.c_int]),
+    'av_msckf_batch_next_forecast': (C.c_int, [_P, _P, _P, _P]),
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_msckf_batch_launch_shape': (C.c_int, [_P, C.POINTER(C.c_int32 * 17)]),
@@ -310,6 +312,7 @@ SIGNATURES = {
     'av_msckf_predict_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6),
     'av_msckf_predict_ops_dev_rate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6 +
                                       [C.c_int, _P, _P]),
+    'av_msckf_forecast_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, _P, _P, _P, C.c_int, _P, C.POINTER(C.c_double), _P, _P, C.c_int, _P, _P, _P]),
     'av_msckf_batch_work': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 8)]),
     'av_msckf_batch_work_executed': (C.c_int, [_P, C.POINTER(C.c_double * 2)]),
     'av_debug_live_resources': (C.c_int, [C.POINTER(C.c_int64 * 4)]),

@@ -173,3 +173,8 @@ class ConfigEuRoC(object):
         # state after every IMU sample of the frame, the last imu_rate_cap of them; include/airvision.h, "IMU-rate odometry")
         self.publish_imu_rate = False
         self.imu_rate_cap = 32
+        # no reference counterpart: the drop-in MSCKF keeps the forecast of its last feature_callback in `last_forecast` -- the pose the step
+        # leaves carried through the IMU samples pushed beyond the frame's time (the first forecast_cap of them), with its covariance
+        # (include/airvision.h, "Forecast")
+        self.publish_forecast = False
+        self.forecast_cap = 32

@@ -899,7 +899,8 @@ constexpr int PROP_LDS_DOUBLES = 5 * IMU_DIM * IMU_DIM + IMU_DIM * 12;      // F
 // NT: threads of the workgroup -- 256, or 64 (dk_cov: the device-resident filter runs a stream's covariance steps in ONE wavefront; the
 // barriers below are then wavefront-local and the scalar preparation sits on neighbouring lanes instead of on the first lanes of
 // three wavefronts)
-template <bool EXT = false, int NT = 256>
+// USER: a second caller of the same <EXT, NT> takes an instance of its own (the forecast: 1), so that the first one's LDS variables stay its alone
+template <bool EXT = false, int NT = 256, int USER = 0>
 __device__ __forceinline__ void propagate_body(const PropArgs& a, double* P11s = nullptr, double* PhiT = nullptr, double* ext = nullptr)
 {
     __shared__ double own[EXT ? 1 : PROP_LDS_DOUBLES];

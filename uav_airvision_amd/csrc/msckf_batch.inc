@@ -767,7 +767,8 @@ AV_EXPORT int av_msckf_batch_step(av_msckf_batch* b, const int64_t* ids, const d
     return av_msckf_batch_wait(b, 0);
 }
 
-// The optional per-step outputs (OUTS, msckf_dev.inc; airvision.h: "Odometry covariance", "Landmark map", "Innovation statistics").
+// The optional per-step outputs (OUTS, msckf_dev.inc; airvision.h: "Odometry covariance", "Landmark map", "Innovation statistics",
+// "IMU-rate odometry", "Forecast").
 // set: before the batch's first step -- the groups size their buffers when they prepare the device-resident path.  next: the
 // destination of the next step's arrays, taken by that step.
 static_assert(sizeof(av_landmark) == AV_LANDMARK_BYTES && sizeof(DLandmark) == AV_LANDMARK_BYTES, "av_landmark layout");
@@ -778,6 +779,8 @@ static_assert(FS_RAN == AV_FS_RAN && FS_CUT == AV_FS_CUT, "AV_FS_* bits");
 static_assert(sizeof(av_imu_state) == AV_IMU_STATE_BYTES && sizeof(DImuState) == AV_IMU_STATE_BYTES, "av_imu_state layout");
 static_assert(offsetof(av_imu_state, p) == offsetof(DImuState, p) && offsetof(av_imu_state, q) == offsetof(DImuState, q) && offsetof(av_imu_state, v) == offsetof(DImuState, v) && offsetof(av_imu_state, w) == offsetof(DImuState, w), "av_imu_state fields");
 constexpr int IMU_RATE_CAP_MAX = 4096;
+constexpr int FORECAST_CAP_MAX = 4096;
+static_assert(ODOM_COV_DOUBLES == AV_ODOM_COV_DOUBLES, "the forecast's covariance record is an odometry-covariance record");
 
 namespace {
 
@@ -820,6 +823,8 @@ AV_EXPORT int av_msckf_batch_set_stats(av_msckf_batch* b, int enable) { return b
 AV_EXPORT int av_msckf_batch_next_stats(av_msckf_batch* b, av_filter_stats* rec_host) { return batch_next_out(b, F_STATS, {rec_host}); }
 AV_EXPORT int av_msckf_batch_set_imu_rate(av_msckf_batch* b, int cap) { return batch_set_out(b, F_IR, cap, cap >= 0 && cap <= IMU_RATE_CAP_MAX); }
 AV_EXPORT int av_msckf_batch_next_imu_rate(av_msckf_batch* b, av_imu_state* rec, int32_t* n) { return batch_next_out(b, F_IR, {rec, n}); }
+AV_EXPORT int av_msckf_batch_set_forecast(av_msckf_batch* b, int cap) { return batch_set_out(b, F_FC, cap, cap >= 0 && cap <= FORECAST_CAP_MAX); }
+AV_EXPORT int av_msckf_batch_next_forecast(av_msckf_batch* b, av_imu_state* rec, int32_t* n, double* cov) { return batch_next_out(b, F_FC, {rec, n, cov}); }
 
 AV_EXPORT int av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, int n, void* stream)
 {
@@ -1111,6 +1116,83 @@ AV_EXPORT int av_msckf_predict_ops_dev_rate(av_msckf* c, int n_streams, int wg, 
     if (cap < 1) { av_set_error("av_msckf_predict_ops_dev_rate: cap must be 1 .. %d", IMU_RATE_CAP_MAX); return AV_E_INVALID; }
     return predict_ops_dev_body(c, n_streams, wg, cam_stride, ld, p_stride, state_io, state_int_io, t_frame, ctl, imu, n_imu, noise4,
                                 cam_q_dev, cam_p_dev, cam_qn_dev, P_dev, redundant_out, stream, cap, rec_out, n_out);
+}
+
+// Parity-test entry for the forecast (airvision.h, "Forecast"; tests only; no step of the filter calls it): for n_streams streams
+// described by the flat host arrays of av_msckf_predict_ops_dev -- state_io[43], state_int_io[6], of which `active` is an INPUT here: the
+// state a step leaves -- the forecast's two kernels through dev_launch_forecast, the helper dev_enqueue itself calls, on the caller's
+// device covariances.  pend[2] per stream = (first, count): its pending samples are imu[first .. first + count), of which the first
+// min(count, cap) are integrated.  rec_out [n_streams][cap], n_out [n_streams][2] and cov_out [n_streams][120] are HOST arrays, uploaded
+// as the caller filled them (a pre-fill shows what the kernels did not write) and read back.  state_io and state_int_io come back as the
+// kernels left them on the device: unchanged.  Every argument is checked before anything is launched.  Synchronises.
+AV_EXPORT int av_msckf_forecast_ops_dev(av_msckf* c, int n_streams, int ld, int64_t p_stride, double* state_io, int32_t* state_int_io,
+                                        const double* imu, int n_imu, const int32_t* pend, const double* noise4, double* P_dev, void* stream,
+                                        int cap, av_imu_state* rec_out, int32_t* n_out, double* cov_out)
+{
+    constexpr int SD = 43, SI = 6;
+    if (!c || n_streams < 1 || n_streams > 65536 || cap < 1 || cap > FORECAST_CAP_MAX || n_imu < 0 || (n_imu > 0 && !imu) || !state_io || !state_int_io ||
+        !pend || !noise4 || !P_dev || !rec_out || !n_out || !cov_out || ld < IMU_DIM || p_stride < (int64_t)ld * ld) {
+        av_set_error("av_msckf_forecast_ops_dev: bad arguments");
+        return AV_E_INVALID;
+    }
+    const int S = n_streams;
+    for (int s = 0; s < S; ++s) {
+        const int32_t* I = state_int_io + (size_t)s * SI;
+        if (I[1] < 0 || I[0] != IMU_DIM + 6 * I[1] || I[0] > ld || pend[2 * s] < 0 || pend[2 * s + 1] < 0 || (int64_t)pend[2 * s] + pend[2 * s + 1] > n_imu) {
+            av_set_error("av_msckf_forecast_ops_dev: stream %d: inconsistent sizes or samples outside their array", s);
+            return AV_E_INVALID;
+        }
+    }
+    hipStream_t stm = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(c->device));
+    struct Arena { AvScratch mem; char* p = nullptr; size_t used = 0;
+                   size_t take(size_t bytes) { const size_t o = used; used += (bytes + 255) / 256 * 256; return o; } } ar;
+    const size_t nimu = (size_t)(n_imu > 0 ? n_imu : 1);
+    const size_t o_st = ar.take(sizeof(DState) * S), o_imu = ar.take(sizeof(DImu) * nimu), o_prop = ar.take(sizeof(PropArgs) * nimu), o_pend = ar.take(sizeof(int) * 3 * S),
+                 o_rec = ar.take(sizeof(DImuState) * S * (size_t)cap), o_n = ar.take(sizeof(int) * 2 * S), o_cov = ar.take(sizeof(double) * ODOM_COV_DOUBLES * S);
+    { const int rca = ar.mem.alloc(ar.used); if (rca) return rca; }
+    ar.p = static_cast<char*>(ar.mem.p);
+    std::vector<DState> st((size_t)S); std::vector<DImu> im(nimu); std::vector<int> pd((size_t)3 * S);
+    memset(st.data(), 0, sizeof(DState) * S); memset(im.data(), 0, sizeof(DImu) * nimu);
+    for (int s = 0; s < S; ++s) {
+        const double* d = state_io + (size_t)s * SD; const int32_t* I = state_int_io + (size_t)s * SI;
+        DState& D = st[s];
+        D.ts = d[0];
+        memcpy(D.q, d + 1, 32); memcpy(D.p, d + 5, 24); memcpy(D.v, d + 8, 24); memcpy(D.bg, d + 11, 24); memcpy(D.ba, d + 14, 24);
+        memcpy(D.R_ic, d + 17, 72); memcpy(D.t_ci, d + 26, 24); memcpy(D.qn, d + 29, 32); memcpy(D.pn, d + 33, 24); memcpy(D.vn, d + 36, 24);
+        memcpy(D.gravity, d + 39, 24); D.tracking_rate = d[42];
+        D.n = I[0]; D.ncam = I[1]; D.failed = I[2]; D.null_aliased = I[3]; D.first_img = I[4]; D.active = I[5];
+        pd[3 * s] = pend[2 * s]; pd[3 * s + 1] = pend[2 * s + 1]; pd[3 * s + 2] = pend[2 * s + 1] < cap ? pend[2 * s + 1] : cap;
+    }
+    for (int i = 0; i < n_imu; ++i) { im[i].t = imu[7 * i]; for (int e = 0; e < 3; ++e) { im[i].w[e] = imu[7 * i + 1 + e]; im[i].a[e] = imu[7 * i + 4 + e]; } }
+    DevArgs a; memset(&a, 0, sizeof(a));
+    a.S = S; a.ld = ld; a.pstride = (size_t)p_stride; a.P = P_dev;
+    a.st = (DState*)(ar.p + o_st); a.imu = (const DImu*)(ar.p + o_imu); a.prop = (PropArgs*)(ar.p + o_prop);
+    for (int i = 0; i < 4; ++i) a.noise[i] = noise4[i];
+    const FcOut fc{(DImuState*)(ar.p + o_rec), (int*)(ar.p + o_n), (double*)(ar.p + o_cov), cap, (const int*)(ar.p + o_pend)};
+    AV_HIP(hipMemcpyAsync(a.st, st.data(), sizeof(DState) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_imu, im.data(), sizeof(DImu) * nimu, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_pend, pd.data(), sizeof(int) * 3 * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(fc.rec, rec_out, sizeof(DImuState) * S * (size_t)cap, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(fc.n, n_out, sizeof(int) * 2 * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(fc.cov, cov_out, sizeof(double) * ODOM_COV_DOUBLES * S, hipMemcpyHostToDevice, stm));
+    dev_launch_forecast(a, S, fc, stm);
+    AV_LAUNCH_CHECK();
+    AV_HIP(hipMemcpyAsync(rec_out, fc.rec, sizeof(DImuState) * S * (size_t)cap, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(n_out, fc.n, sizeof(int) * 2 * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(cov_out, fc.cov, sizeof(double) * ODOM_COV_DOUBLES * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(st.data(), a.st, sizeof(DState) * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipStreamSynchronize(stm));
+    for (int s = 0; s < S; ++s) {
+        double* d = state_io + (size_t)s * SD; int32_t* I = state_int_io + (size_t)s * SI;
+        const DState& D = st[s];
+        d[0] = D.ts;
+        memcpy(d + 1, D.q, 32); memcpy(d + 5, D.p, 24); memcpy(d + 8, D.v, 24); memcpy(d + 11, D.bg, 24); memcpy(d + 14, D.ba, 24);
+        memcpy(d + 17, D.R_ic, 72); memcpy(d + 26, D.t_ci, 24); memcpy(d + 29, D.qn, 32); memcpy(d + 33, D.pn, 24); memcpy(d + 36, D.vn, 24);
+        memcpy(d + 39, D.gravity, 24); d[42] = D.tracking_rate;
+        I[0] = D.n; I[1] = D.ncam; I[2] = D.failed; I[3] = D.null_aliased; I[4] = D.first_img; I[5] = D.active;
+    }
+    return AV_OK;
 }
 
 // Work done so far, for the filter's roofline (drain first): [algorithmic fp64 flops of the gates, of the updates without the

@@ -27,6 +27,8 @@
 //                av_msckf_batch_set_stats is on) the same, and the stream's innovation statistics of the update that has just run
 //   dk_imu_rate  (behind dk_state, the state half of dk_predict, when av_msckf_batch_set_imu_rate is on) per stream: the state after every
 //                IMU sample of the frame, gathered from the records dk_state leaves for dk_cov
+//   dk_forecast_state, dk_forecast_cov  (behind dk_finish*, when av_msckf_batch_set_forecast is on) per stream: the state the step leaves,
+//                carried through the IMU samples the step has NOT consumed, with the covariance of its IMU block; read-only for the filter
 //
 // Per-stream capacity failures are recorded in the stream's state (DState::failed) and stop that stream only.
 
@@ -766,6 +768,8 @@ __global__ __launch_bounds__(256, 5) void dk_mid_lm_st(DevArgs a, LmOut L, DUpdS
 // Entries of rows 0:9 x columns 0:9 are copies of the entries of P they select; rows 0:9 x columns 9:15 are one 21-term sum (the zeros of J
 // multiply to exact zeros), the 6 x 6 corner is two nested ones.
 constexpr int ODOM_COV_DOUBLES = 120;
+// (The forecast, dk_forecast_cov, takes its record through this very function: it reads a.P, a.pstride, a.ld and of *D the flags, q, R_ic and
+//  t_ci, nothing else, so a caller may hand it any 21 x 21 block and state by way of copies of the two records.)
 __device__ __forceinline__ void dev_odom_cov(const DevArgs& a, int s, const DState* D, double* rec)
 {
     __shared__ double Ps[IMU_DIM * IMU_DIM], Jl[6 * IMU_DIM];
@@ -953,6 +957,81 @@ __global__ __launch_bounds__(256, 5) void dk_finish_cov_lm_st(DevArgs a, double*
 }
 
 // ------------------------------------------------------------------------------------------------
+// Forecast (include/airvision.h, "Forecast"; launched behind the step's last per-stream kernel only when av_msckf_batch_set_forecast is
+// on): the state and the covariance of the IMU block as the step LEAVES them -- both updates, the camera removal and online_reset are in --
+// carried through the IMU samples the stream's buffer held beyond the frame time when the step was submitted.  The host stages those
+// pending samples behind the stream's own in a.imu[] and addresses them by pend[s] = (first, had, staged): had were pending, the first
+// staged = min(had, cap) of them lie at a.imu[first ..] and are integrated.  Both kernels only READ what the filter reads: DState, P, the step's own a.prop[] / a.cov[] records stay as they are.
+//   dk_forecast_state  a LANE per stream, like dk_state: the serial chain on a private copy of DState, sample by sample exactly what
+//                      dk_state does with a sample (dev_predict_new_state, the null states advanced as process_model does), one PropArgs
+//                      per sample into a.prop[first + k], the region behind the step's own records.  Nothing goes back to a.st.
+//   dk_forecast_cov    ONE wavefront per stream at every launch shape: the 21 x 21 block of P staged in LDS, propagate_body<true, 64> per
+//                      sample on that copy (the camera blocks are not needed: the IMU block depends on nothing else), the 15 x 15 record
+//                      by dev_odom_cov from the LDS copy with J at the last written record's orientation, the 112-byte records gathered
+//                      a lane per double as dk_imu_rate does, the count pair; (0, 0) and a NaN row for a stream that does not publish.
+// Plain vector stores: no atomics.
+// ------------------------------------------------------------------------------------------------
+struct FcOut { DImuState* rec; int* n; double* cov; int cap; const int* pend; };      // [S][cap] records, [S][2] counts (had, written), [S][120]; [S][3] (first, had, staged) of the slot
+__device__ __forceinline__ bool dev_forecast_publishes(const DState* D) { return D->active && !D->failed; }
+__global__ __launch_bounds__(64) void dk_forecast_state(DevArgs a, FcOut F)
+{
+    AV_FILTER_PRIO();
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.S) return;
+    if (!dev_forecast_publishes(a.st + s)) return;
+    DState L = a.st[s];                                       // a private copy of the state: never written back
+    DState* D = &L;
+    const int first = F.pend[3 * (size_t)s], st = F.pend[3 * (size_t)s + 2], wr = st < F.cap ? st : F.cap;
+    for (int k = 0; k < wr; ++k) {                            // (dk_state's loop over the frame's samples, on the copy)
+        PropArgs pa;
+        const DImu m = a.imu[first + k];
+        pa.P = nullptr; pa.n = D->n; pa.ld = a.ld; pa.dt = m.t - D->ts;
+        for (int i = 0; i < 3; ++i) { pa.gyro[i] = m.w[i] - D->bg[i]; pa.acc[i] = m.a[i] - D->ba[i]; pa.gravity[i] = D->gravity[i]; }
+        for (int i = 0; i < 4; ++i) { pa.q_old[i] = D->q[i]; pa.noise[i] = a.noise[i]; }
+        dev_predict_new_state(*D, pa.dt, pa.gyro, pa.acc);
+        for (int i = 0; i < 4; ++i) { pa.q_new[i] = D->q[i]; pa.q_null[i] = D->qn[i]; }
+        for (int i = 0; i < 3; ++i) { pa.v_null[i] = D->vn[i]; pa.p_null[i] = D->pn[i]; pa.v_new[i] = D->v[i]; pa.p_new[i] = D->p[i]; }
+        for (int i = 0; i < 4; ++i) D->qn[i] = D->q[i];
+        for (int i = 0; i < 3; ++i) { D->pn[i] = D->p[i]; D->vn[i] = D->v[i]; }
+        D->ts = m.t;
+        a.prop[first + k] = pa;
+    }
+}
+__global__ __launch_bounds__(64) void dk_forecast_cov(DevArgs a, FcOut F)
+{
+    AV_FILTER_PRIO();
+    __shared__ double P11s[IMU_DIM * IMU_DIM], PhiT[IMU_DIM * IMU_DIM], work[PROP_LDS_DOUBLES];
+    const int s = blockIdx.x, lane = threadIdx.x, N = IMU_DIM;
+    const DState* D = a.st + s;
+    double* cov = F.cov + (size_t)s * ODOM_COV_DOUBLES;
+    if (!dev_forecast_publishes(D)) {                         // (wavefront-uniform)
+        if (lane == 0) { F.n[2 * (size_t)s] = 0; F.n[2 * (size_t)s + 1] = 0; }
+        for (int e = lane; e < ODOM_COV_DOUBLES; e += 64) cov[e] = __longlong_as_double(0x7ff8000000000000LL);
+        return;
+    }
+    const int first = F.pend[3 * (size_t)s], had = F.pend[3 * (size_t)s + 1], st = F.pend[3 * (size_t)s + 2], wr = st < F.cap ? st : F.cap;
+    if (lane == 0) { F.n[2 * (size_t)s] = had; F.n[2 * (size_t)s + 1] = wr; }
+    const double* P = a.P + (size_t)s * a.pstride;
+    for (int i = lane; i < N * N; i += 64) { const int r = i / N, c = i - r * N; P11s[i] = P[(size_t)r * a.ld + c]; PhiT[i] = r == c ? 1.0 : 0.0; }
+    __syncthreads();
+    for (int k = 0; k < wr; ++k) propagate_body<true, 64, 1>(a.prop[first + k], P11s, PhiT, work);        // each ends on a barrier
+    // the 15 x 15 record by the map dk_finish_cov uses, dev_odom_cov, from the propagated block in LDS: copies of the two records it reads,
+    // P = the LDS block as stream 0 with leading dimension 21, q = the last written record's
+    DevArgs al = a; al.P = P11s; al.pstride = 0; al.ld = N;
+    DState Dl = *D;
+    if (wr > 0) for (int i = 0; i < 4; ++i) Dl.q[i] = a.prop[first + wr - 1].q_new[i];
+    dev_odom_cov(al, 0, &Dl, cov);
+    constexpr int W = (int)(sizeof(DImuState) / 8);
+    double* out = reinterpret_cast<double*>(F.rec + (size_t)s * F.cap);
+    for (int e = lane; e < wr * W; e += 64) {
+        const int j = e / W, f = e - j * W;
+        const size_t i = (size_t)first + j;
+        const PropArgs& pa = a.prop[i];
+        out[e] = f == 0 ? a.imu[i].t : (f < 4 ? pa.p_new[f - 1] : (f < 8 ? pa.q_new[f - 4] : (f < 11 ? pa.v_new[f - 8] : pa.gyro[f - 11])));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // dk_restart: stream restart (include/airvision.h, "Stream restart"; host side: dev_restart).  No step launches it.  One workgroup per
 // LISTED stream, s = list[blockIdx.x] (the host has checked every index against S and removed repeats), on the group's own stream, so a
 // step enqueued behind it finds the stream as dev_reserve first made it:
@@ -965,7 +1044,7 @@ __global__ __launch_bounds__(256, 5) void dk_finish_cov_lm_st(DevArgs a, double*
 //   store       avs_restart: empty window and map, births and the whole header zero (avs_clear alone leaves births and the sticky
 //               hdr[AVS_OVERFLOW]), every persistent array as allocated
 //   outputs     the stream's rows of out, of the odometry-covariance, landmark (records and counts) and statistics buffers: zero, as
-//               allocated; likewise the IMU-rate records and counts.  Every step rewrites them for every stream; they are cleared so that a
+//               allocated; likewise the IMU-rate and the forecast records and counts and the forecast covariance.  Every step rewrites them for every stream; they are cleared so that a
 //               read of the buffers finds no old life.
 // Not touched: Pn, T, Kt, scratch, the block buffers, the per-phase feature arrays and lists, the store's scratch -- every step writes
 // what it reads of them; `work` (av_msckf_batch_work accumulates).  Overflow pool: a stream holds NO pool rows between steps.  The pool
@@ -977,7 +1056,7 @@ static_assert(sizeof(DState) % 8 == 0, "dk_restart clears DState by 8-byte words
 struct DRestart {
     const int* list; int* carry;                              // [n] streams; [n][2] the counters they held
     double v0[3], t_ci[3], gravity[3], R_ic[9];               // create-time values of the batch
-    double* odom; LmOut lm; DUpdStats* stats; IrOut ir;       // the optional outputs (null: off)
+    double* odom; LmOut lm; DUpdStats* stats; IrOut ir; FcOut fc;      // the optional outputs (null: off)
 };
 __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
 {
@@ -998,6 +1077,7 @@ __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
         for (int i = 0; i < 12; ++i) a.out[(size_t)s * 12 + i] = 0.0;
         if (r.lm.rec) { r.lm.n[2 * (size_t)s] = 0; r.lm.n[2 * (size_t)s + 1] = 0; }
         if (r.ir.rec) { r.ir.n[2 * (size_t)s] = 0; r.ir.n[2 * (size_t)s + 1] = 0; }
+        if (r.fc.rec) { r.fc.n[2 * (size_t)s] = 0; r.fc.n[2 * (size_t)s + 1] = 0; }
     }
     double* P = a.P + (size_t)s * a.pstride;
     for (size_t i = tid; i < a.pstride; i += nt) {            // reset_state_cov (msckf.py:788-798) in a cleared region
@@ -1018,6 +1098,11 @@ __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
     if (r.ir.rec) {
         unsigned long long* w = reinterpret_cast<unsigned long long*>(r.ir.rec + (size_t)s * r.ir.cap);
         for (int i = tid; i < r.ir.cap * (int)(sizeof(DImuState) / 8); i += nt) w[i] = 0ull;
+    }
+    if (r.fc.rec) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(r.fc.rec + (size_t)s * r.fc.cap);
+        for (int i = tid; i < r.fc.cap * (int)(sizeof(DImuState) / 8); i += nt) w[i] = 0ull;
+        for (int i = tid; i < ODOM_COV_DOUBLES; i += nt) r.fc.cov[(size_t)s * ODOM_COV_DOUBLES + i] = 0.0;
     }
     AvsTeam T; T.red = nullptr;
     avs_restart(T, dev_store(a, s));
@@ -1042,17 +1127,19 @@ __global__ __launch_bounds__(256) void dk_prune_probe(DevArgs a, const int* ops,
 // ---- host-side handles of the device-resident path (functions: msckf_dev_host.inc) ---------------------------------------------
 // The optional per-step outputs: ONE entry per array a step may carry beside its poses, in the order of their read-back on the stream.
 // A feature is what a caller switches (av_msckf_batch_set_*) and hands a destination for (av_msckf_batch_next_*); its setting is
-// 0 = off, else 1 (the landmark map and the IMU-rate odometry: records per stream and step).  Their records and counts are two arrays of
-// one feature.
+// 0 = off, else 1 (the landmark map, the IMU-rate odometry and the forecast: records per stream and step).  Their records and counts are
+// two arrays of one feature; the forecast has a third, its covariance record.
 // Everything else about them -- the batch's settings and next destinations, StepOuts, the device and pinned buffers, their allocation,
-// read-back, hand-over and restart -- is an array indexed by this table or a loop over it.  A fourth output: an entry here (and in
+// read-back, hand-over and restart -- is an array indexed by this table or a loop over it.  A sixth output: an entry here (and in
 // KOuts), its two exported wrappers, and the kernel instances that write it (dk_mid_kernels / dk_finish_kernels, msckf_dev_host.inc) -- or,
-// for the IMU-rate odometry, the one kernel dev_launch_predict adds behind dk_state.
-enum OutFeat { F_COV, F_LM, F_STATS, F_IR, N_FEAT };
-enum OutArr { O_COV, O_LM, O_LMN, O_STATS, O_IR, O_IRN, N_OUT };
+// for the IMU-rate odometry, the one kernel dev_launch_predict adds behind dk_state; for the forecast, the two kernels dev_launch_forecast
+// adds behind dk_finish*.
+enum OutFeat { F_COV, F_LM, F_STATS, F_IR, F_FC, N_FEAT };
+enum OutArr { O_COV, O_LM, O_LMN, O_STATS, O_IR, O_IRN, O_FC, O_FCN, O_FCC, N_OUT };
 struct OutWords { const char* fn; const char* noun; const char* needs; const char* is; };      // "av_msckf_batch_set_<fn>: <noun> <needs> ...", "<noun> <is> off"
 constexpr OutWords W_COV = {"odom_cov", "the odometry covariance", "needs", "is"}, W_LM = {"landmarks", "the landmark map", "needs", "is"},
-                   W_STATS = {"stats", "the innovation statistics", "need", "are"}, W_IR = {"imu_rate", "the IMU-rate odometry", "needs", "is"};
+                   W_STATS = {"stats", "the innovation statistics", "need", "are"}, W_IR = {"imu_rate", "the IMU-rate odometry", "needs", "is"},
+                   W_FC = {"forecast", "the forecast", "needs", "is"};
 struct OutDesc {
     OutFeat feat; size_t fixed, per_setting; OutWords w;
     size_t bytes(const int* setting) const { return fixed + per_setting * (size_t)setting[feat]; }      // per stream
@@ -1064,6 +1151,9 @@ constexpr OutDesc OUTS[N_OUT] = {
     {F_STATS, AV_FILTER_STATS_BYTES, 0, W_STATS},    // statistics records (two update blocks)
     {F_IR, 0, AV_IMU_STATE_BYTES, W_IR},             // IMU-rate records
     {F_IR, 2 * 4, 0, W_IR},                          // IMU-rate counts (had, written)
+    {F_FC, 0, AV_IMU_STATE_BYTES, W_FC},             // forecast records
+    {F_FC, 2 * 4, 0, W_FC},                          // forecast counts (had, written)
+    {F_FC, ODOM_COV_DOUBLES * 8, 0, W_FC},           // forecast covariance record
 };
 constexpr const OutWords& out_words(OutFeat f) { for (int i = 0; i < N_OUT; ++i) if (OUTS[i].feat == f) return OUTS[i].w; return OUTS[0].w; }
 // a step's destinations in the caller's memory (NULL: the step has none and the array is dropped)
@@ -1076,12 +1166,13 @@ struct StepOuts {
         return g;
     }
 };
-struct KOuts { double* odom; LmOut lm; DUpdStats* stats; IrOut ir; };      // the device arrays as the kernels' parameter lists and DRestart take them (dev_kouts)
+struct KOuts { double* odom; LmOut lm; DUpdStats* stats; IrOut ir; FcOut fc; };      // the device arrays as the kernels' parameter lists and DRestart take them (dev_kouts)
 constexpr int DEV_RING = 3;          // steps of a stream group that may be queued at once (inputs / outputs are ring-buffered)
 struct DevSlot {
     DCtl* ctl_h = nullptr; DCtl* ctl_d = nullptr;
     DImu* imu_h = nullptr; DImu* imu_d = nullptr; size_t imu_cap = 0;
     PropArgs* prop_d = nullptr;      // [imu_cap] dk_begin -> dk_cov, one record per IMU sample
+    int* pend_h = nullptr; int* pend_d = nullptr;      // [S][3] (first, had, staged) of every stream's pending samples in imu_h / imu_d (forecast on; NULL: off)
     long long* ids_h = nullptr; double* uv_h = nullptr; int* n_h = nullptr;      // pinned staging of a feature message that arrives in host arrays
     long long* ids_d = nullptr; double* uv_d = nullptr; int* n_d = nullptr;      // the message on the device (copied from the host arrays or from the front-end's buffers)
     double* out_h = nullptr; int* cnt_h = nullptr;                                // pinned landing zones of the step's only read-back

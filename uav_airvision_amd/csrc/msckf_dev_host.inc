@@ -76,6 +76,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
             DA(sl.ctl_d, S) DA(sl.n_d, S)
             if ((rc = b->res.pinned(&sl.n_h, S))) return rc;
             for (int i = 0; i < N_OUT; ++i) if (b->out_set[OUTS[i].feat] && (rc = b->res.pinned(&sl.outs_h[i], S * OUTS[i].bytes(b->out_set)))) return rc;
+            if (b->out_set[F_FC]) { DA(sl.pend_d, S * 3) if ((rc = b->res.pinned(&sl.pend_h, S * 3))) return rc; }      // the forecast's (first, had, staged) per stream
             if ((rc = b->res.event(&sl.done, hipEventDisableTiming | hipEventBlockingSync))) return rc;
             for (int ph = 0; ph < 2; ++ph) if ((rc = b->res.event(&sl.t0[ph], hipEventDefault)) || (rc = b->res.event(&sl.t1[ph], hipEventDefault))) return rc;
         }
@@ -374,6 +375,7 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
     if (b->debug_capture) for (BStream& T : b->st) for (int ph = 0; ph < 2; ++ph) { T.dbg_gamma[ph].clear(); T.dbg_dx[ph].clear(); T.dbg_P[ph].clear(); T.dbg_rows[ph] = 0; T.dbg_n[ph] = 0; }
     // ---- control records + IMU samples of this frame (batch_imu_processing's selection, msckf.py:251-273; the arithmetic is on the device)
     size_t n_imu = 0;
+    const size_t fc_cap = (size_t)b->out_set[F_FC];
     for (int s = 0; s < S; ++s) {
         BStream& T = b->st[s];
         std::lock_guard<std::mutex> g(T.mu);
@@ -382,10 +384,14 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
         T.active = !T.failed && T.gravity_set && timestamps[s] >= 0 && T.gravity_time <= timestamps[s];
         if (!T.active) continue;
         const double t0 = T.first_img ? timestamps[s] : T.ts;
-        for (const BImu& m : T.imu) { if (m.t < t0) continue; if (m.t > timestamps[s]) break; ++n_imu; }
+        size_t pending = 0;            // forecast: the samples beyond the frame time ride behind the stream's own, the first fc_cap of them
+        for (const BImu& m : T.imu) { if (m.t < t0) continue; if (m.t > timestamps[s]) { if (!fc_cap || ++pending >= fc_cap) break; continue; } ++n_imu; }
+        n_imu += pending;
     }
     if (n_imu > sl.imu_cap) {          // (sized generously at the first step; grows if a frame ever spans more IMU samples)
-        const size_t ncap = n_imu + n_imu / 2 + (size_t)S * 16 + 64;
+        // forecast on: room for every stream's full share of pending samples from the start, so that a caller who pushes further ahead later
+        // does not make the staging grow
+        const size_t ncap = n_imu + n_imu / 2 + (size_t)S * 16 + 64 + (size_t)S * fc_cap;
         if (sl.imu_cap) { AV_HIP(hipStreamSynchronize(stm)); ++d->growths; }
         if ((rc = b->res.pinned(&sl.imu_h, ncap)) || (rc = b->res.dev(&sl.imu_d, ncap)) || (rc = b->res.dev(&sl.prop_d, ncap))) return rc;
         sl.imu_cap = ncap;
@@ -395,6 +401,7 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
         BStream& T = b->st[s];
         DCtl& C = sl.ctl_h[s];
         C.t_frame = timestamps[s]; C.active = T.active ? 1 : 0; C.has_init = 0; C.imu_first = (int)w; C.imu_cnt = 0;
+        if (fc_cap) { sl.pend_h[3 * s] = (int)w; sl.pend_h[3 * s + 1] = 0; sl.pend_h[3 * s + 2] = 0; }
         if (!T.active) continue;
         std::lock_guard<std::mutex> g(T.mu);
         if (!T.dev_init_sent) {            // first live frame of the stream: hand the device what initialize_gravity_and_bias computed (msckf.py:230-249)
@@ -414,6 +421,22 @@ int dev_launch(av_msckf_batch* b, int k, const int64_t* ids, const double* uv, c
             T.ts = m.t;
         }
         T.imu.erase(T.imu.begin(), T.imu.begin() + used);
+        if (fc_cap) {
+            // Forecast: what is left has t > the frame time -- the pending samples, in push order.  They STAY in the buffer (the next step
+            // consumes them as it always would); the first min(had, cap) of them are staged behind the stream's own samples.
+            sl.pend_h[3 * s] = (int)w;
+            const size_t had = T.imu.size();
+            size_t staged = 0;
+            for (; staged < had && staged < fc_cap && w < sl.imu_cap; ++staged) {
+                const BImu& m = T.imu[staged];
+                DImu& o = sl.imu_h[w++];
+                o.t = m.t;
+                for (int i = 0; i < 3; ++i) { o.w[i] = m.w[i]; o.a[i] = m.a[i]; }
+            }
+            // (staged < min(had, cap) only if samples were pushed between the sizing pass above and this one, past the staging's slack: the
+            //  device integrates what was staged and the count pair says so)
+            sl.pend_h[3 * s + 1] = (int)(had < (size_t)INT32_MAX ? had : (size_t)INT32_MAX); sl.pend_h[3 * s + 2] = (int)staged;
+        }
     }
     // ---- the feature message (host arrays: through the slot's pinned staging)
     if (!dev_msg) {
@@ -448,6 +471,16 @@ void dev_launch_predict(const DevArgs& a, int S, int dk_wg, bool append, hipStre
     else hipLaunchKernelGGL(dk_cov<256>, dim3(S), dim3(256), 0, stm, a);
 }
 
+// The forecast's launches (av_msckf_batch_set_forecast), behind the step's last per-stream kernel: the state chain a lane per stream, then
+// the covariance, the records and the counts one wavefront per stream whatever shape the step's other kernels take.  One place for the
+// step (dev_enqueue) and for the parity-test entry av_msckf_forecast_ops_dev.  a.imu / a.prop hold the pending samples and the room for
+// their records at fc.pend[s] = (first, had, staged): staged <= min(had, fc.cap) samples lie at a.imu[first ..].
+void dev_launch_forecast(const DevArgs& a, int S, const FcOut& fc, hipStream_t stm)
+{
+    hipLaunchKernelGGL(dk_forecast_state, dim3((S + 63) / 64), dim3(64), 0, stm, a, fc);
+    hipLaunchKernelGGL(dk_forecast_cov, dim3(S), dim3(64), 0, stm, a, fc);
+}
+
 // The named instances of dk_mid and dk_finish (profiles/filter_stats/README.md has why they are named instances), by the outputs that
 // are on: the same launches as with all off, the instance also writes those outputs' records and the step reads them back.  Every
 // instance's parameter list is DevArgs, then the ordered subset of (double* odom, LmOut, DUpdStats*) of its set bits: the order
@@ -463,7 +496,8 @@ KOuts dev_kouts(const av_msckf_batch* b)          // the one place that gives th
 {
     char* const* p = b->dev.outs_d;
     return {(double*)p[O_COV], LmOut{(DLandmark*)p[O_LM], (int*)p[O_LMN], b->out_set[F_LM]}, (DUpdStats*)p[O_STATS],
-            IrOut{(DImuState*)p[O_IR], (int*)p[O_IRN], b->out_set[F_IR]}};
+            IrOut{(DImuState*)p[O_IR], (int*)p[O_IRN], b->out_set[F_IR]},
+            FcOut{(DImuState*)p[O_FC], (int*)p[O_FCN], (double*)p[O_FCC], b->out_set[F_FC], nullptr}};
 }
 int dev_launch_outs(bool finish, const av_msckf_batch* b, DevArgs& a, int wg, hipStream_t stm)
 {
@@ -488,7 +522,8 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     const int S = b->S;
     int rc;
     AV_HIP(hipMemcpyAsync(sl.ctl_d, sl.ctl_h, sizeof(DCtl) * S, hipMemcpyHostToDevice, stm));
-    if (n_imu) AV_HIP(hipMemcpyAsync(sl.imu_d, sl.imu_h, sizeof(DImu) * n_imu, hipMemcpyHostToDevice, stm));
+    if (n_imu) AV_HIP(hipMemcpyAsync(sl.imu_d, sl.imu_h, sizeof(DImu) * n_imu, hipMemcpyHostToDevice, stm));      // (forecast on: the pending samples ride in the same upload)
+    if (sl.pend_d) AV_HIP(hipMemcpyAsync(sl.pend_d, sl.pend_h, sizeof(int) * 3 * S, hipMemcpyHostToDevice, stm));
     if (!dev_msg) {
         AV_HIP(hipMemcpyAsync(sl.n_d, sl.n_h, sizeof(int) * S, hipMemcpyHostToDevice, stm));
         AV_HIP(hipMemcpyAsync(sl.ids_d, sl.ids_h, sizeof(long long) * S * d->cap, hipMemcpyHostToDevice, stm));
@@ -521,6 +556,11 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     if (b->debug_capture && (rc = dev_debug_capture(b, 1, stm))) return rc;
     a.stacked = d->stacked1;
     if ((rc = dev_launch_outs(true, b, a, dk_wg, stm))) return rc;
+    if (sl.pend_d) {
+        FcOut fc = dev_kouts(b).fc; fc.pend = sl.pend_d;
+        dev_launch_forecast(a, S, fc, stm);
+        AV_LAUNCH_CHECK();
+    }
     AV_HIP(hipMemcpyAsync(sl.out_h, d->out_d, sizeof(double) * 12 * S, hipMemcpyDeviceToHost, stm));
     for (int i = 0; i < N_OUT; ++i) if (d->outs_d[i]) AV_HIP(hipMemcpyAsync(sl.outs_h[i], d->outs_d[i], OUTS[i].bytes(b->out_set) * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(sl.cnt_h, a.cnt, sizeof(int) * 16, hipMemcpyDeviceToHost, stm));
@@ -563,7 +603,7 @@ int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm)
     for (int i = 0; i < 3; ++i) { r.v0[i] = b->vel0[i]; r.t_ci[i] = b->t_ci0[i]; r.gravity[i] = b->gravity0[i]; }
     for (int i = 0; i < 9; ++i) r.R_ic[i] = b->R_ic0[i];
     const KOuts o = dev_kouts(b);
-    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats; r.ir = o.ir;
+    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats; r.ir = o.ir; r.fc = o.fc;
     hipLaunchKernelGGL(dk_restart, dim3((unsigned)n), dim3(256), 0, stm, d->A, r);
     AV_LAUNCH_CHECK();
     AV_HIP(hipMemcpyAsync(d->rs_carry_h, d->rs_carry_d, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, stm));

@@ -18,7 +18,7 @@ import numpy as np
 from feature import BaseFeature
 from utils import Isometry3d, to_quaternion, to_rotation
 from uav_airvision_amd import _native as N
-from uav_airvision_amd.msckf_ops import BatchedMSCKF, unpack_imu_states, unpack_landmarks, unpack_odom_cov
+from uav_airvision_amd.msckf_ops import BatchedMSCKF, unpack_forecast, unpack_imu_states, unpack_landmarks, unpack_odom_cov
 
 _vio_result = namedtuple('vio_result', ['timestamp', 'pose', 'velocity', 'cam0_pose'])
 
@@ -119,9 +119,21 @@ class MSCKF(object):
         self._ir_on = bool(getattr(config, 'publish_imu_rate', False))
         self.last_imu_states = None
         self.last_imu_states_dropped = 0
+        # config.publish_forecast = True (no reference counterpart; default off): `last_forecast` holds the forecast records
+        # (msckf_ops.IMU_STATE_DTYPE, the first config.forecast_cap of them) of the last feature_callback -- the pose the step leaves carried
+        # through the IMU messages received beyond the frame's time -- with p, q, v mapped by T_imu_body exactly as `last_imu_states` maps
+        # them; `last_forecast_pending` = (had, written).  `last_forecast_covariance` is the 15 x 15 covariance at the last record (at the
+        # frame's pose when there is none) for T_imu_body = identity only: it is not conjugated into a body frame, so it is None otherwise,
+        # and together with config.publish_covariance a T_imu_body != identity is refused as above.  vio_result is unchanged.
+        self._fc_on = bool(getattr(config, 'publish_forecast', False))
+        self._fc_cov = self._fc_on and np.array_equal(np.asarray(config.T_imu_body, dtype=np.float64), np.identity(4))
+        self.last_forecast = None
+        self.last_forecast_pending = (0, 0)
+        self.last_forecast_covariance = None
         self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap, odom_cov=self._cov_on, landmarks=self._lm_on,
                                  landmark_cap=int(getattr(config, 'landmark_cap', 256)), stats=self._stats_on, imu_rate=self._ir_on,
-                                 imu_rate_cap=int(getattr(config, 'imu_rate_cap', 32)))
+                                 imu_rate_cap=int(getattr(config, 'imu_rate_cap', 32)), forecast=self._fc_on,
+                                 forecast_cap=int(getattr(config, 'forecast_cap', 32)))
         self.state_server = StateServer(self._flt)
         self.map_server = _MapView(self._flt)
         # class-level statics the reference sets in its constructor (msckf.py:128-150), kept for code that reads them
@@ -156,6 +168,9 @@ class MSCKF(object):
         self.last_innovation = None
         self.last_imu_states = None
         self.last_imu_states_dropped = 0
+        self.last_forecast = None
+        self.last_forecast_pending = (0, 0)
+        self.last_forecast_covariance = None
         self.debug = {}
 
     @property
@@ -188,7 +203,14 @@ class MSCKF(object):
             ids[0, :n] = [f.id for f in feats]
             uv[0, :n] = [(f.u0, f.v0, f.u1, f.v1) for f in feats]
         out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None, landmarks=True if self._lm_on else None,
-                             stats=True if self._stats_on else None, imu_states=True if self._ir_on else None)
+                             stats=True if self._stats_on else None, imu_states=True if self._ir_on else None,
+                             forecast=True if self._fc_on else None)
+        if self._fc_on:
+            rec, cnt, cov = self._flt.last_forecast
+            got, C15, _ = unpack_forecast(rec, cnt, cov, 0)
+            self.last_forecast = self._to_body(got.copy())
+            self.last_forecast_pending = (int(cnt[0, 0]), int(cnt[0, 1]))
+            self.last_forecast_covariance = C15 if self._fc_cov and out[0, 0] == 1.0 else None
         if self._ir_on:
             rec, cnt = self._flt.last_imu_states
             self.last_imu_states = self._to_body(unpack_imu_states(rec, cnt, 0).copy())

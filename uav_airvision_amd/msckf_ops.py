@@ -266,6 +266,45 @@ class MsckfDevice(object):
             out.append(d)
         return dict(streams=out, cam_q=q.cpu().numpy(), cam_p=p.cpu().numpy(), cam_qn=qn.cpu().numpy(), P=Pd.cpu().numpy(), **rate)
 
+    def forecast_ops_dev(self, streams, imu, P, noise, cap, fill=np.nan):
+        """Parity-test entry (av_msckf_forecast_ops_dev; tests only): the forecast's two kernels through the helper a step launches them
+        through, for all `streams` at once.  streams: one dict per stream with the STATE_FIELDS, n, ncam, and optionally failed,
+        null_aliased, first_img, active (default 1) -- the state a step LEAVES -- and pend_first / pend_cnt (default 0 / 0): its pending
+        samples are imu[pend_first : pend_first + pend_cnt].  imu: float64[n_imu, 7]; P: [streams, ld, ld].
+        -> dict(streams: the states as they come back, P, rec IMU_STATE_DTYPE[streams, cap] pre-filled with `fill` in every double,
+        n int32[streams, 2] pre-filled with -1, cov float64[streams, 120] pre-filled with `fill`, as the kernels left them)."""
+        S = len(streams)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if P.ndim != 3 or P.shape[0] != S or P.shape[1] != P.shape[2]:
+            raise ValueError('forecast_ops_dev: inconsistent shapes')
+        ld = P.shape[1]
+        sd, si, pend = np.zeros((S, 43)), np.zeros((S, 6), np.int32), np.zeros((S, 2), np.int32)
+        for s, st in enumerate(streams):
+            o = 0
+            for name, k in self.STATE_FIELDS:
+                sd[s, o:o + k] = np.asarray(st[name], dtype=np.float64).reshape(-1)
+                o += k
+            si[s] = [st['n'], st['ncam'], st.get('failed', 0), st.get('null_aliased', 0), st.get('first_img', 0), st.get('active', 1)]
+            pend[s] = [st.get('pend_first', 0), st.get('pend_cnt', 0)]
+        imu = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 7)
+        Pd = torch.from_numpy(P).to(self.dev)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rec = np.full((S, int(cap), 14), fill, dtype=np.float64)
+        n, cov = np.full((S, 2), -1, np.int32), np.full((S, ODOM_COV_DOUBLES), fill, dtype=np.float64)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_forecast_ops_dev(self._h, S, ld, ld * ld, hp(sd), hp(si), hp(imu), len(imu), hp(pend), _d(noise), N.dptr(Pd), self._st(),
+                                                      int(cap), hp(rec), hp(n), hp(cov)))
+            torch.cuda.synchronize()
+        out = []
+        for s in range(S):
+            d, o = {}, 0
+            for name, k in self.STATE_FIELDS:
+                d[name] = sd[s, o:o + k].copy() if k > 1 else float(sd[s, o])
+                o += k
+            d.update(zip(self.STATE_INTS, (int(v) for v in si[s])))
+            out.append(d)
+        return dict(streams=out, P=Pd.cpu().numpy(), rec=rec.view(IMU_STATE_DTYPE).reshape(S, int(cap)), n=n, cov=cov)
+
     def update(self, blk_rows, blk_lens, obs_noise):
         """Stacked EKF update on the selected blocks; returns delta_x (n doubles)."""
         n = self.dim
@@ -367,11 +406,25 @@ def unpack_imu_states(rec, n, s):
     return rec[s, :int(n[s, 1])]
 
 
+# ---- forecast (include/airvision.h, "Forecast") --------------------------------------------------------------------------------
+FORECAST_CAP_MAX = 4096
+
+
+def unpack_forecast(rec, n, cov, s):
+    """The forecast of stream `s`: rec IMU_STATE_DTYPE[S, cap], n int32[S, 2] and cov float64[S, 120] as a step returns them ->
+    (rec[s, :n[s, 1]], the covariance as 15 x 15, reached_t).  The written records are the FIRST n[s, 1] pending samples in time order
+    (n[s, 0] > n[s, 1]: the cap ended the chain before the newest sample); reached_t is the last written record's stamp, None when
+    nothing was written -- the covariance is then that of the pose the step leaves, at the step's own time.  A stream that did not
+    publish reads no records, a NaN matrix and None."""
+    got = rec[s, :int(n[s, 1])]
+    return got, unpack_odom_cov(cov[s]), (float(got['t'][-1]) if len(got) else None)
+
+
 # The optional outputs of a step of BatchedMSCKF, one entry each.  kw: the keyword of `step / submit / submit_dev`; ctor_kw: the
 # constructor keyword that switches it on; setting: the attribute that holds its setting (falsy: off); fn: the library's
 # av_msckf_batch_set_<fn> / av_msckf_batch_next_<fn>; last: the attribute that remembers the arrays of the most recent step that was
 # given any; shapes(flt): the (dtype, shape) of every array it takes; fill: what `True` allocates them with; what(flt): its ValueError.
-# A fourth output is one more entry here (and its constructor / step keywords), beside the C table (OUTS, csrc/msckf_dev.inc).
+# A sixth output is one more entry here (and its constructor / step keywords), beside the C table (OUTS, csrc/msckf_dev.inc).
 StepOutput = collections.namedtuple('StepOutput', 'kw ctor_kw setting fn last shapes fill what')
 STEP_OUTPUTS = (
     StepOutput('cov', 'odom_cov', 'odom_cov', 'odom_cov', 'last_cov', lambda f: [(np.float64, (f.S, ODOM_COV_DOUBLES))], np.nan,
@@ -384,6 +437,10 @@ STEP_OUTPUTS = (
     StepOutput('imu_states', 'imu_rate', 'imu_rate_cap', 'imu_rate', 'last_imu_states',
                lambda f: [(IMU_STATE_DTYPE, (f.S, f.imu_rate_cap)), (np.int32, (f.S, 2))], 0,
                lambda f: 'imu_states must be a pair of C-contiguous arrays IMU_STATE_DTYPE[%d, %d], int32[%d, 2]' % (f.S, f.imu_rate_cap, f.S)),
+    StepOutput('forecast', 'forecast', 'forecast_cap', 'forecast', 'last_forecast',
+               lambda f: [(IMU_STATE_DTYPE, (f.S, f.forecast_cap)), (np.int32, (f.S, 2)), (np.float64, (f.S, ODOM_COV_DOUBLES))], 0,
+               lambda f: 'forecast must be a triple of C-contiguous arrays IMU_STATE_DTYPE[%d, %d], int32[%d, 2], float64[%d, %d]' %
+               (f.S, f.forecast_cap, f.S, f.S, ODOM_COV_DOUBLES)),
 )
 _OUTPUT = {o.kw: o for o in STEP_OUTPUTS}
 
@@ -394,7 +451,7 @@ class BatchedMSCKF(object):
     (reference: src/msckf.py:162-228) for many streams at once."""
 
     def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64, stats=False,
-                 imu_rate=False, imu_rate_cap=32):
+                 imu_rate=False, imu_rate_cap=32, forecast=False, forecast_cap=32):
         """rows_cap: rows of the per-stream block buffer.  None = sized by the library from the capacity of the first
         feature message (the camera-pruning update stacks 5 rows per feature, the lost-feature update at most 1500 + one
         block); `max_features`, when given, sizes it up front instead.  With the automatic size a later step with a wider
@@ -410,7 +467,11 @@ class BatchedMSCKF(object):
         submit_dev(..., stats=)`, `last_stats`, `unpack_filter_stats`).
         imu_rate=True: every step also publishes the state after every IMU sample its prediction integrated, the last imu_rate_cap
         (1 .. 4096) of them per stream (IMU_STATE_DTYPE; `step / submit / submit_dev(..., imu_states=)`, `last_imu_states`,
-        `unpack_imu_states`).  Predictions from the previous step's state; `w` is in the IMU frame."""
+        `unpack_imu_states`).  Predictions from the previous step's state; `w` is in the IMU frame.
+        forecast=True: every step also publishes the pose it leaves carried through the IMU samples pushed beyond the frame's time, the
+        first forecast_cap (1 .. 4096) of them per stream, with the covariance at the last of them (records IMU_STATE_DTYPE, counts, a
+        float64[S, 120] odometry-covariance record; `step / submit / submit_dev(..., forecast=)`, `last_forecast`, `unpack_forecast`).
+        Read-only for the filter: every other output and the state are bit for bit what they are without it."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -436,9 +497,9 @@ class BatchedMSCKF(object):
                 self.device, C.byref(self._h)))
         # the optional outputs: last_* = the arrays of the most recent step that was given any (cov: float64[S, 120]; landmarks: (records
         # LANDMARK_DTYPE[S, cap], counts int32[S, 2]); stats: FILTER_STATS_DTYPE[S, 2]; imu_states: (records IMU_STATE_DTYPE[S, cap], counts
-        # int32[S, 2]))
+        # int32[S, 2]); forecast: (records IMU_STATE_DTYPE[S, cap], counts int32[S, 2], covariance float64[S, 120]))
         want = {'odom_cov': bool(odom_cov), 'landmark_cap': int(landmark_cap) if landmarks else 0, 'stats': bool(stats),
-                'imu_rate_cap': int(imu_rate_cap) if imu_rate else 0}
+                'imu_rate_cap': int(imu_rate_cap) if imu_rate else 0, 'forecast_cap': int(forecast_cap) if forecast else 0}
         for o in STEP_OUTPUTS:
             setattr(self, o.setting, want[o.setting])
             setattr(self, o.last, None)
@@ -447,6 +508,8 @@ class BatchedMSCKF(object):
                 raise ValueError('landmark_cap must be at least 1')
             if imu_rate and not 1 <= want['imu_rate_cap'] <= IMU_RATE_CAP_MAX:
                 raise ValueError('imu_rate_cap must be 1 .. %d' % IMU_RATE_CAP_MAX)
+            if forecast and not 1 <= want['forecast_cap'] <= FORECAST_CAP_MAX:
+                raise ValueError('forecast_cap must be 1 .. %d' % FORECAST_CAP_MAX)
             for o in STEP_OUTPUTS:
                 if want[o.setting]:
                     self._set(o, want[o.setting])
@@ -474,9 +537,13 @@ class BatchedMSCKF(object):
         """av_msckf_batch_set_imu_rate: cap records per stream and step (0: off, at most 4096); before the first step only."""
         self._set(_OUTPUT['imu_states'], int(cap))
 
+    def set_forecast(self, cap):
+        """av_msckf_batch_set_forecast: cap records per stream and step (0: off, at most 4096); before the first step only."""
+        self._set(_OUTPUT['forecast'], int(cap))
+
     def _next(self, o, value):
         """The arrays of output `o` for the next step (None: the step has none), handed to the library.  value: None, True (allocate) or
-        the caller's C-contiguous array (landmarks, imu_states: pair of arrays) of o.shapes(self)."""
+        the caller's C-contiguous array (landmarks, imu_states: pair of arrays; forecast: triple) of o.shapes(self)."""
         if value is None or value is False:
             return None
         if not getattr(self, o.setting):
@@ -519,7 +586,7 @@ class BatchedMSCKF(object):
         N.check(N.lib().av_msckf_batch_push_imu(self._h, si.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p),
                                                 g.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), len(si)))
 
-    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None, imu_states=None):
+    def step(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None, imu_states=None, forecast=None):
         """ids int64[S,cap], uv float64[S,cap,4], n_feat int32[S], timestamps float64[S] (host arrays).
         Returns float64[S,12]: published, t, p(3), q(4), v(3).  cov (odom_cov=True): a float64[S,120] array that takes the step's
         odometry-covariance records, or True to have one allocated; it is `last_cov` afterwards.  landmarks (landmarks=True): a pair of
@@ -527,31 +594,33 @@ class BatchedMSCKF(object):
         allocated; the pair is `last_landmarks` afterwards.  stats (stats=True): a FILTER_STATS_DTYPE[S, 2] array that takes the step's
         innovation statistics, or True to have one allocated; it is `last_stats` afterwards.  imu_states (imu_rate=True): a pair of arrays
         (IMU_STATE_DTYPE[S, imu_rate_cap], int32[S, 2]) that takes the step's IMU-rate records and counts, or True to have them allocated;
-        the pair is `last_imu_states` afterwards."""
+        the pair is `last_imu_states` afterwards.  forecast (forecast=True): a triple of arrays (IMU_STATE_DTYPE[S, forecast_cap], int32[S, 2],
+        float64[S, 120]) that takes the step's forecast records, counts and covariance, or True to have them allocated; the triple is
+        `last_forecast` afterwards (`unpack_forecast`)."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         cap = ids.shape[1]
         out = np.zeros((self.S, 12))
-        self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states)
+        self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states, forecast=forecast)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_step(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                 nf.ctypes.data_as(C.c_void_p), cap, ts.ctypes.data_as(C.c_void_p),
                                                 out.ctypes.data_as(C.c_void_p), N.current_stream()))
         return out
 
-    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None, imu_states=None):
+    def submit(self, ids, uv, n_feat, timestamps, cov=None, landmarks=None, stats=None, imu_states=None, forecast=None):
         """Queue one step (av_msckf_batch_submit) and return its float64[S,12] output array, which is filled once the
         step has retired -- i.e. after a `wait(k)` that leaves fewer than the steps submitted after it pending.  The
         stream groups of the batch run behind their queues independently of each other.  cov: as in `step`; the array (`last_cov`) is
-        filled when the step retires, like the output array; landmarks, stats, imu_states: likewise."""
+        filled when the step retires, like the output array; landmarks, stats, imu_states, forecast: likewise."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         nf = np.ascontiguousarray(n_feat, dtype=np.int32)
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         out = np.zeros((self.S, 12))
-        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states)
+        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states, forecast=forecast)
         with torch.cuda.device(self.device):
             N.check(N.lib().av_msckf_batch_submit(self._h, ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
                                                   nf.ctypes.data_as(C.c_void_p), ids.shape[1], ts.ctypes.data_as(C.c_void_p),
@@ -563,17 +632,17 @@ class BatchedMSCKF(object):
         """Always True: the filter state and the observation map live on the device.  Kept for callers that still ask."""
         return N.lib().av_msckf_batch_device_resident(self._h) == 1
 
-    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None, imu_states=None):
+    def submit_dev(self, engine, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None, imu_states=None, forecast=None):
         """Queue one step on the feature message `engine` (a FrontendEngine with the same streams) has just published, read
         where it lies on the device (av_msckf_batch_submit_dev): no host round trip between the front-end and the filter.
         msg_stream: the stream handle the engine's step ran on (default: torch's current stream, i.e. call this right after
         `engine.step` on the same stream).  The filter's kernels run on the current stream / the stream groups' own streams.
-        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks, stats, imu_states: as in `submit`."""
+        Returns the float64[S,12] output array, filled once a `wait` has let the step retire.  cov, landmarks, stats, imu_states, forecast: as in `submit`."""
         ids, uv, n, cap = engine.features_dev()
         ts = np.ascontiguousarray(timestamps, dtype=np.float64)
         assert ts.shape == (self.S,) and engine.n_streams == self.S
         out = np.zeros((self.S, 12))
-        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states)
+        outs = self._next_outputs(cov=cov, landmarks=landmarks, stats=stats, imu_states=imu_states, forecast=forecast)
         with torch.cuda.device(self.device):
             ms = N.current_stream() if msg_stream is None else msg_stream
             N.check(N.lib().av_msckf_batch_submit_dev(self._h, ids, uv, n, cap, ts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),

@@ -210,14 +210,16 @@ class FilterSet(object):
     ([S, landmark_cap] and [S, 2]).  stats=True switches the innovation statistics on, `submit_dev(..., stats=True)` gives every part
     its records array and `last_stats` joins them ([S, 2] of FILTER_STATS_DTYPE).  imu_rate=True (with imu_rate_cap) switches the IMU-rate
     odometry on, `submit_dev(..., imu_states=True)` gives every part its pair of arrays and `last_imu_states` = (records view, counts
-    view) joins them ([S, imu_rate_cap] of IMU_STATE_DTYPE and [S, 2])."""
+    view) joins them ([S, imu_rate_cap] of IMU_STATE_DTYPE and [S, 2]).  forecast=True (with forecast_cap) switches the forecast on,
+    `submit_dev(..., forecast=True)` gives every part its triple of arrays and `last_forecast` = (records view, counts view, covariance
+    view) joins them ([S, forecast_cap] of IMU_STATE_DTYPE, [S, 2] and [S, 120])."""
 
     def __init__(self, config, engine_set, device=0, **kw):
         from .msckf_ops import BatchedMSCKF, STEP_OUTPUTS
         self.es = engine_set
         self.parts = engine_set.parts
         self.flts = [BatchedMSCKF(config, hi - lo, device=device, **kw) for lo, hi in self.parts]
-        for o in STEP_OUTPUTS:                               # odom_cov / landmarks / stats / imu_rate: on or off; last_*: the joined arrays of the last step that asked
+        for o in STEP_OUTPUTS:                               # odom_cov / landmarks / stats / imu_rate / forecast: on or off; last_*: the joined arrays of the last step that asked
             setattr(self, o.ctor_kw, bool(kw.get(o.ctor_kw, False)))
             setattr(self, o.last, None)
 
@@ -229,10 +231,10 @@ class FilterSet(object):
             if len(rows[0]):
                 self.es.pipes[p].put(lambda f=self.flts[p], r=rows: f.push_imu(*r))
 
-    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None, imu_states=None):
+    def submit_dev(self, engine_set, timestamps, msg_stream=None, cov=None, landmarks=None, stats=None, imu_states=None, forecast=None):
         assert engine_set is self.es
         from .msckf_ops import STEP_OUTPUTS
-        asked = {'cov': cov, 'landmarks': landmarks, 'stats': stats, 'imu_states': imu_states}
+        asked = {'cov': cov, 'landmarks': landmarks, 'stats': stats, 'imu_states': imu_states, 'forecast': forecast}
         views = {}                                           # output -> one _OutView per array of it
         for o in STEP_OUTPUTS:
             if asked[o.kw] is None:
