@@ -106,6 +106,30 @@ __device__ __forceinline__ int dot2_keep(uint32_t a, uint32_t b, int c)
 }
 __device__ __forceinline__ uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
 
+// The four W_BITS = 14 bilinear weights of the fractions (fa, fb), packed for v_dot2: wtop = (iw00 | iw01 << 16), wbot = (iw10 | iw11 << 16),
+//   iw00 = rn((1 - fa)(1 - fb) 2^14), iw01 = rn(fa (1 - fb) 2^14), iw10 = rn((1 - fa) fb 2^14), iw11 = 2^14 - iw00 - iw01 - iw10
+// (rn = round to nearest, ties to even: cvRound / __float2int_rn), without a conversion instruction.  Why this is exact:
+//   * Range.  fa = x - floor(x) is computed in float: the exact difference lies in [0, 1), so its rounding lies in [0, 1] (1.0 only for a
+//     tiny negative x such as -1e-7: floor = -1, x + 1 rounds to 1.0 -- the weights are then those of fa = 1, as with the conversions).
+//     1 - fa, 1 - fb lie in [0, 1] too, every product of two of them in [0, 1], and the multiplication by 2^14 is exact: 0 <= p <= 2^14.
+//   * Rounding.  p + 2^23 lies in [2^23, 2^23 + 2^14], inside the binade [2^23, 2^24) whose floats are the integers: the addition (round
+//     to nearest even, the mode every kernel of this library runs in; -ffp-contract=off: it is not fused with the multiplication) returns
+//     2^23 + n with n the integer nearest to p, and of two equally near ones the one with an even significand, which is the even n
+//     because 2^23 is even.  That is rn(p).  The float 2^23 + n has the bits 0x4B000000 + n, n <= 2^14: the low half of the word IS n.
+//   * iw11.  Only the low halves of the words are packed, and the low half of a difference depends on the low halves alone: the three
+//     biases 0x4B000000 drop out, and a sum of the three weights above 2^14 (each rounded up) gives the same negative 16-bit value.
+//   (A NaN coordinate from the caller is outside this argument and outside the contract: the oracle's floor of a NaN is undefined.)
+__device__ __forceinline__ void lk_weights(float fa, float fb, uint32_t& wtop, uint32_t& wbot)
+{
+    const float ga = 1.f - fa, gb = 1.f - fb;
+    const uint32_t u00 = __float_as_uint(ga * gb * (float)(1 << 14) + 0x1p23f);
+    const uint32_t u01 = __float_as_uint(fa * gb * (float)(1 << 14) + 0x1p23f);
+    const uint32_t u10 = __float_as_uint(ga * fb * (float)(1 << 14) + 0x1p23f);
+    const uint32_t u11 = (uint32_t)(1 << 14) - (u00 + u01 + u10);
+    wtop = __builtin_amdgcn_perm(u01, u00, 0x05040100u);
+    wbot = __builtin_amdgcn_perm(u11, u10, 0x05040100u);
+}
+
 constexpr int TILE_ROWS = 24;     // staged J tile: 24 rows x 32 bytes (window 16 rows + 4 px of drift either way)
 constexpr int TILE_COLS = 32;
 constexpr int TPITCH = 36;        // LDS row pitch in bytes (9 dwords: the 16 rows of a point fall on 16 different banks)
@@ -334,7 +358,11 @@ __device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, u
         gxp[2 * k + 1] = mid(gxp[2 * k], gxp[2 * k + 2]);
         gyp[2 * k + 1] = mid(gyp[2 * k], gyp[2 * k + 2]);
     }
-    const int rnd_i = 1 << (W_BITS - 6), rnd_d = 1 << (W_BITS - 1);      // rounding terms, one register each
+    // Lane 15 (row 15 feeds only the interpolation of row 14, through the DPP operand of the lane above, which is the pixel pair and not
+    // a weight) interpolates its derivatives with zero weights and a zero rounding term: its Ix, Iy pairs are zero, and so are its shares
+    // of a11 / a12 / a22 here and of b1 / b2 in every Newton iteration, with no select there.
+    if (r >= WIN) { wtop = 0; wbot = 0; }
+    const int rnd_i = 1 << (W_BITS - 6), rnd_d = r < WIN ? 1 << (W_BITS - 1) : 0;      // rounding terms, one register each
     // The derivative patches are kept as PAIRS of adjacent columns, (Ix[2p] | Ix[2p+1] << 16) and the same for Iy (|Ix|, |Iy| <= 4080;
     // the 16th column is zero): every window sum is then a chain of v_dot2_i32_i16 -- two columns per instruction -- instead of one
     // v_mad_i32_i16 per column (24 instead of 45 here, 16 + 7 pair packs instead of 30 in every Newton iteration; the same exact
@@ -355,7 +383,6 @@ __device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, u
         a12 = dot2(ixx[p], iyy[p], a12);
         a22 = dot2(iyy[p], iyy[p], a22);
     }
-    if (r >= WIN) { a11 = 0; a12 = 0; a22 = 0; }
 }
 
 // PTS: points per workgroup (16 = four wavefronts, 4 = one).  The wavefronts of a workgroup share nothing -- every point has its own
@@ -364,7 +391,6 @@ template <int WIN, int OCC, bool PROF = false, int PTS = 16>
 __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
 {
     static_assert(WIN == 15, "lane map is built for the reference's 15x15 window");
-    constexpr int W_BITS = 14;
     __shared__ uint32_t tile_all[PTS][TILE_DWORDS];
     // phase stamps (PROF only): cycles since the previous stamp are booked on the phase that just ended
     unsigned pt[LKP_N] = {0, 0, 0, 0, 0}, plast = 0;             // 32-bit: a wavefront lives ~10^5 cycles
@@ -402,7 +428,6 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
     const size_t pi = (size_t)s * a.cap + pidx;
     if (!direct) { prevx0 = a.prev[2 * pi]; prevy0 = a.prev[2 * pi + 1]; curx = a.next[2 * pi]; cury = a.next[2 * pi + 1]; }
     const float halfWin = (WIN - 1) * 0.5f;
-    const bool rowact = r < WIN;
     bool ok = true;
     // byte-pair selectors of v_perm: (byte o, byte o+1) zero-extended into the two 16-bit halves; o+1 == 4 = byte 0 of the next dword
     const uint32_t sel0 = 0x0C010C00u, sel1 = 0x0C020C01u, sel2 = 0x0C030C02u, sel3 = 0x0C040C03u;
@@ -415,17 +440,18 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
         if (level == a.g.levels - 1) { curx = curx * scale; cury = cury * scale; }
         else                         { curx = curx * 2.f;   cury = cury * 2.f; }
         pvx -= halfWin; pvy -= halfWin;
-        const int ipx = (int)floorf(pvx), ipy = (int)floorf(pvy);
-        if (ipx < -WIN || ipx >= w || ipy < -WIN || ipy >= h) {
+        // The floor stays a float for the fraction: an index that passes the bounds test is below 2^12 in magnitude, (float)(int)floor
+        // is the floor itself.  The bounds test is -WIN <= i < size as ONE unsigned compare per axis on the index biased by WIN (an
+        // index beyond int range converts saturated, and INT_MAX + WIN / INT_MIN + WIN both land above any size + WIN as unsigned).
+        const float fpx = floorf(pvx), fpy = floorf(pvy);
+        const int ipx = (int)fpx, ipy = (int)fpy;
+        const unsigned wlim = (unsigned)(w + WIN), hlim = (unsigned)(h + WIN);
+        if ((unsigned)ipx + WIN >= wlim || (unsigned)ipy + WIN >= hlim) {
             if (level == 0) ok = false;
             continue;
         }
-        float fa = pvx - ipx, fb = pvy - ipy;
-        int iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << W_BITS));
-        int iw01 = __float2int_rn(fa * (1.f - fb) * (1 << W_BITS));
-        int iw10 = __float2int_rn((1.f - fa) * fb * (1 << W_BITS));
-        int iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
-        uint32_t wtop = pack16(iw00, iw01), wbot = pack16(iw10, iw11);
+        uint32_t wtop, wbot;
+        lk_weights(pvx - fpx, pvy - fpy, wtop, wbot);
 
         // ---- stage the 18 x 18-byte neighbourhood of the I window: rows ipy-1 .., bytes ipx-1 .. ipx+16 of each as five dwords
         //      read at their (unaligned) byte address, so that every staged row starts at window column -1.  All bytes lie inside
@@ -494,20 +520,30 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
         }
         D = 1.f / D;
 
+        // ---- Newton iterations.  ONE exit, at the bottom, and every loop-carried value (wx, wy, their floors, the previous step, the
+        //      tile origin) updated in place: a point that is done simply drops out of the loop's execution mask with its state where the
+        //      step left it, and what distinguished the former four exits is settled once, after the loop:
+        //        converged / oscillating / trip limit ("soft"): the position stands, status untouched; oscillation takes half the last
+        //        step back; out of the image before the next trip (tested where that trip's floor is computed, at the bottom, and for
+        //        the first trip ahead of the loop): level 0 fails.
+        //      (With a `break` per case the compiler carried a copy of every state register per exit around the loop: 14 register moves
+        //      and ~45 execution-mask instructions per trip.)
         float wx = curx - halfWin, wy = cury - halfWin;
+        if (a.max_iter <= 0) continue;                         // wave-uniform: no trip, no bounds test
+        float fx = floorf(wx), fy = floorf(wy);
+        int inx = (int)fx, iny = (int)fy;
+        if ((unsigned)inx + WIN >= wlim || (unsigned)iny + WIN >= hlim) {
+            if (level == 0) ok = false;
+            continue;
+        }
         float pdx = 0.f, pdy = 0.f;
-        int X0 = 0, Y0 = 0;
-        bool staged = false;
+        int X0 = -(1 << 30), Y0 = 0;                           // no tile yet: inx - X0 is beyond any drift, the first trip stages
+        bool osc = false, soft = false;
         LK_STAMP(LKP_SETUP);
-        for (int j = 0; j < a.max_iter; ++j) {
+        for (int j = 0;;) {
             if (PROF) ++pn_iter;
-            const int inx = (int)floorf(wx), iny = (int)floorf(wy);
-            if (inx < -WIN || inx >= w || iny < -WIN || iny >= h) {
-                if (level == 0) ok = false;
-                break;
-            }
             int dx0 = inx - X0, dy0 = iny - Y0;
-            if (!staged || (unsigned)dx0 > (unsigned)(TILE_COLS - 17) || (unsigned)dy0 > (unsigned)(TILE_ROWS - 16)) {
+            if ((unsigned)dx0 > (unsigned)(TILE_COLS - 17) || (unsigned)dy0 > (unsigned)(TILE_ROWS - 16)) {
                 X0 = min(max((inx - 6) & ~3, col_lo), col_hi - TILE_COLS);
                 Y0 = min(max(iny - 4, -AV_PYR_BORDER), h + AV_PYR_BORDER - TILE_ROWS);
                 LK_STAMP(LKP_ITER);
@@ -538,15 +574,9 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
                 }
                 wave_lds_sync();
                 LK_STAMP(LKP_JSTAGE);
-                staged = true;
                 dx0 = inx - X0; dy0 = iny - Y0;
             }
-            fa = wx - inx; fb = wy - iny;
-            iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << W_BITS));
-            iw01 = __float2int_rn(fa * (1.f - fb) * (1 << W_BITS));
-            iw10 = __float2int_rn((1.f - fa) * fb * (1 << W_BITS));
-            iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
-            wtop = pack16(iw00, iw01); wbot = pack16(iw10, iw11);
+            lk_weights(wx - fx, wy - fy, wtop, wbot);
 
             // this lane's J row (dy0 + r): 16 pixels starting at byte dx0 -> 5 aligned dwords -> 4 byte-aligned dwords
             const int sh = dx0 & 3;
@@ -566,13 +596,11 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
                 b1 = dot2(dp, ixx[p], b1);
                 b2 = dot2(dp, iyy[p], b2);
             }
-            if (!rowact) { b1 = 0; b2 = 0; }
             const float fb1 = row_sum16_scaled(b1);
             const float fb2 = row_sum16_scaled(b2);
             const float dx = (A12 * fb2 - A22 * fb1) * D;
             const float dy = (A12 * fb1 - A11 * fb2) * D;
             wx += dx; wy += dy;
-            curx = wx + halfWin; cury = wy + halfWin;
             // delta.ddot(delta) <= eps^2 is an fp64 test in OpenCV.  e32 lies within 2^-22 (relative) of the exact dx^2 + dy^2, so outside
             // (eps_lo, eps_hi) the float compare decides the same way; inside (once in ~10^5 iterations) the fp64 form does.
             const float e32 = __builtin_fmaf(dx, dx, dy * dy);
@@ -581,14 +609,19 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
                 asm volatile("; fp64 step test");          // keeps the block a branch (if-converted, its fp64 instructions ran every iteration)
                 conv = (double)dx * dx + (double)dy * dy <= a.eps2;
             }
-            if (conv) break;
             // |x| < 0.01 (double) for a float x <=> |x| <= 0.01f: 0.01f = 0.00999999977... < 0.01 < the next float up
-            if (j > 0 && fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f) {
-                curx -= dx * 0.5f; cury -= dy * 0.5f;
-                break;
-            }
+            osc = !conv && j > 0 && fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f;
             pdx = dx; pdy = dy;
+            ++j;
+            soft = conv || osc || j >= a.max_iter;
+            // the next trip's floors and its bounds test
+            fx = floorf(wx); fy = floorf(wy);
+            inx = (int)fx; iny = (int)fy;
+            if (soft || (unsigned)inx + WIN >= wlim || (unsigned)iny + WIN >= hlim) break;
         }
+        if (!soft && level == 0) ok = false;
+        curx = wx + halfWin; cury = wy + halfWin;
+        if (osc) { curx -= pdx * 0.5f; cury -= pdy * 0.5f; }
         LK_STAMP(LKP_ITER);
     }
     if (r == 0) {
