@@ -87,6 +87,14 @@ int av_lk_track(const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_st
                 int w, int h, int levels,
                 const float* prev_dev, float* next_dev, uint8_t* status_dev, const int32_t* count_dev, int cap,
                 int win, int max_iter, double eps, double min_eig_threshold, void* stream);
+/* The same with level 0 read in place from the images themselves (set i: imgI_dev + i*img_stride into imgJ_dev + i*img_stride, tightly
+ * packed w*h u8, BORDER_REFLECT_101 where a window reaches over the border), as the front-end engine tracks its resident frames; the
+ * level-0 regions of the two pyramids are not read (av_pyramid_build_levels fills the others).  Same results as av_lk_track. */
+int av_lk_track_images(const uint8_t* imgI_dev, const uint8_t* imgJ_dev, int64_t img_stride,
+                       const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_stride, int n_set,
+                       int w, int h, int levels,
+                       const float* prev_dev, float* next_dev, uint8_t* status_dev, const int32_t* count_dev, int cap,
+                       int win, int max_iter, double eps, double min_eig_threshold, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cv2.FastFeatureDetector_create(threshold).detect(img, mask)   (TYPE_9_16, NMS on)

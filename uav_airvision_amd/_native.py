@@ -230,6 +230,8 @@ SIGNATURES = {
     'av_pyramid_build_levels': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     'av_lk_track': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int,
                               C.c_int, C.c_int, C.c_double, C.c_double, _P]),
+    'av_lk_track_images': (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int,
+                                     C.c_int, C.c_int, C.c_double, C.c_double, _P]),
     'av_fast_detect': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     'av_fast_detect_wide': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     'av_undistort_points': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),

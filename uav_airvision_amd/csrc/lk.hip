@@ -41,6 +41,7 @@
 #include <stdlib.h>
 
 #include "av_common.h"
+#include "lk_host.h"
 
 namespace {
 
@@ -60,6 +61,10 @@ struct LKArgs {
     // float forms of the two fp64 thresholds (av_launch_lk): minEig < min_eig (double) <=> minEig < min_eig_up, the smallest float
     // >= min_eig; the step-length test is decided in float outside (eps_lo, eps_hi) = eps2 (1 -+ 2^-18) and in fp64 inside
     float min_eig_up, eps_lo, eps_hi;
+    // the 16-lane kernel's form of minEig < min_eig_up without the division: minEig = fl(num / (2 win^2)) < min_eig_up <=> num <
+    // min_eig_num (av_lk_quotient_bound, lk_host.h: the division is monotone; NaN when the threshold is NaN: the test fails nothing).
+    // It sits in what was padding ahead of the double: no other field moves.
+    float min_eig_num;
     double min_eig;             // the general kernel's fp64 form
     int n_set, gx;              // XCD-aware 1-D launch of the 16-lane kernels: gx workgroups per point set, see lk_track_g16_body
     // Level 0 straight from the caller's image (w x h, tightly packed rows) instead of a padded copy in the pyramid: non-null =
@@ -130,6 +135,22 @@ __device__ __forceinline__ void lk_weights(float fa, float fb, uint32_t& wtop, u
     wbot = __builtin_amdgcn_perm(u11, u10, 0x05040100u);
 }
 
+// base + rows * pitch of a wave-uniform image origin, as an opaque scalar value (see the staging loops of lk_track_g16_body), and the
+// unaligned dword at a per-lane 32-bit offset from it.  The address goes through the asm as an integer and comes back as a pointer to
+// GLOBAL memory (which every image of this library is): a generic pointer out of an asm statement would be loaded from with flat_load.
+typedef const __attribute__((address_space(1))) uint8_t* av_gptr;
+__device__ __forceinline__ av_gptr lk_row_base(const uint8_t* base, int rows, int pitch)
+{
+    uint64_t p = (uint64_t)base + (uint64_t)rows * (uint64_t)pitch;
+    asm("" : "+s"(p));
+    return (av_gptr)p;
+}
+__device__ __forceinline__ uint32_t lk_load_u32(av_gptr rowbase, uint32_t off)
+{
+    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+    return *(const __attribute__((address_space(1))) u32_unaligned*)(rowbase + off);
+}
+
 constexpr int TILE_ROWS = 24;     // staged J tile: 24 rows x 32 bytes (window 16 rows + 4 px of drift either way)
 constexpr int TILE_COLS = 32;
 constexpr int TPITCH = 36;        // LDS row pitch in bytes (9 dwords: the 16 rows of a point fall on 16 different banks)
@@ -169,33 +190,125 @@ __device__ __forceinline__ float row_sum16_scaled(int v)
     return __builtin_fmaf((float)hi, 0x1p-4f, (float)lo * 0x1p-20f);
 }
 
+// The same value for a sum of SQUARES (a11, a22), in one unsigned butterfly.  Every lane's share is non-negative and at most
+// 15 x 4080^2 = 249,696,000 (15 columns, |Ix|, |Iy| <= 4080), lane 15's share is zero (lk_patch_rows), so the total S over the row is at
+// most 15 x 249,696,000 = 3,745,440,000 < 2^32: the four 32-bit additions do not wrap, v_cvt_f32_u32 rounds the exact S once (to
+// nearest even), and the multiplication by 2^-20 is exact (S = 0 stays 0, S >= 1 gives >= 2^-20: no underflow) -- (float)(S * 2^-20)
+// rounded once, what row_sum16_scaled returns, in 6 instructions instead of 12.  a12, b1 and b2 are signed: they stay with the halves.
+__device__ __forceinline__ float row_sum_sq_scaled(int a)
+{
+    uint32_t v = (uint32_t)a;
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);   // row_half_mirror
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);   // row_mirror
+    return (float)v * 0x1p-20f;
+}
+
+// sqrtf(x), correctly rounded, for x = 0 or 2^-96 <= x < inf: the instructions the compiler's own correctly rounded sqrtf executes for
+// such an x, without the ones that only serve other arguments.  The compiler's expansion (-fhip-fp32-correctly-rounded-divide-sqrt,
+// subnormals kept) is: scale x by 2^32 if x < 2^-96 (compare, multiply, select); s = v_sqrt_f32 (1 ulp); the one-ulp fix-up below;
+// scale back (multiply, select); return x itself if x is +-0 or +inf (class test, select).  For 2^-96 <= x < inf neither select
+// takes its other arm, and what is left is exactly the lines below: the same instructions on the same values, the same result.  For
+// x = +0 the compiler's form returns x = +0 through the class test; here s = v_sqrt_f32(+0) = +0, the neighbour below has the bits
+// 0xFFFFFFFF, a NaN, so that its residual is a NaN and `<= 0` is false; the neighbour above is the smallest subnormal (or zero, if it
+// were flushed), its residual fma(-tiny, 0, 0) = +0 and `> 0` is false: s = +0 stands.
+// The caller's argument is (A11 - A22)^2 + 4 A12^2 with A11, A12, A22 multiples of 2^-20 below 2^12 in magnitude (row_sum16_scaled: an
+// integer below 2^32 times 2^-20, rounded to 24 bits, which keeps it a multiple of 2^-20): the difference and A12 are 0 or at least
+// 2^-20 in magnitude, the squares 0 or at least 2^-40, at most 2^26: x is +0 or in [2^-40, 2^27], inside the range above.
+__device__ __forceinline__ float lk_sqrt_ranged(float x)
+{
+    float s = __builtin_amdgcn_sqrtf(x);
+    const float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);      // the neighbours of s
+    const float vd = __builtin_fmaf(-sd, s, x), vu = __builtin_fmaf(-su, s, x);                                    // their residuals
+    s = vd <= 0.f ? sd : s;
+    s = vu > 0.f ? su : s;
+    return s;
+}
+
 // Bilinear sample of five packed pixel (or derivative) pairs x_i = (v[c], v[c+1]) of this lane's row with the same
-// pairs of the row below (next lane, DPP row_shl:1):  o_i = (x_i . wtop + below(x_i) . wbot + rnd) >> SH.
+// pairs of the row below (next lane, DPP row_shl:1):  acc_i = x_i . wtop + below(x_i) . wbot + rnd.
 // One asm statement, for two reasons: the compiler does not fold a DPP move into v_dot2c (it has a tied accumulator),
 // and its hazard recogniser does not see into inline asm -- a DPP operand written by a VALU instruction needs 2 wait
-// states, guaranteed here by issuing the five plain dot products first.
-template <int SH>
-__device__ __forceinline__ void bilin5(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t wtop, uint32_t wbot, int rnd,
-                                       int& o0, int& o1, int& o2, int& o3, int& o4)
+// states, guaranteed here by issuing the plain dot products first.
+//
+// deriv5<G>: columns 5 G .. 5 G + 4 of BOTH derivative patches (they share the weights), returned as the packed column pairs the window
+// sums want, (Ix[2p] | Ix[2p+1] << 16) and the same for Iy, WITHOUT a shift.  OpenCV's value is (S + 2^13) >> 14, S = the weighted sum
+// of four Scharr values.  The caller hands in the Scharr values times 4 and 4 * 2^13 as rounding term, so that the accumulator is
+// 4 S + 4 * 2^13 and  (4 S + 4 * 2^13) >> 16 == (S + 2^13) >> 14  (an arithmetic shift is the floor of the division, and
+// floor(4 n / 2^16) = floor(n / 2^14) for every integer n): the wanted value is the HIGH half of the accumulator, which the v_perm that
+// packs a pair takes directly (bytes 2, 3 of either word: selector 0x07060302; for the last, half-empty pair bytes 2, 3 and zeros:
+// 0x0C0C0302).  Ranges: |Scharr| <= 16 x 255 = 4080, times 4 = 16,320 < 2^15, a signed 16-bit operand of v_dot2 like the weights
+// (0 .. 2^14, iw11 >= -2); |accumulator| <= 16,320 x (2^14 + 4) + 2^15 < 2^29; the result, |.| <= 4080, fits the half it is taken from,
+// sign included (the high half of a two's-complement word IS the word >> 16 as a 16-bit two's-complement number).
+// The pairs straddle the groups of five (4|5, 9|10 do not: 4 is carried): group 0 hands accumulator 4 on to group 1 (cx, cy).
+// Wait states: a v_dot2* result needs 3 before another VALU opcode reads it and 4 before one overwrites it, and the compiler does not
+// know what wrote this statement's outputs.  The order below (x columns, then y columns, then the packs alternating x, y) leaves at
+// least 4 instructions between every v_dot2c and the v_perm that reads or overwrites its result, and at least 4 after the last
+// v_dot2c of the statement (group 0's carried y accumulator).
+#define AV_DERIV_DOTS \
+        "v_dot2_i32_i16 %0, %10, %20, %22\n\t" \
+        "v_dot2_i32_i16 %1, %11, %20, %22\n\t" \
+        "v_dot2_i32_i16 %2, %12, %20, %22\n\t" \
+        "v_dot2_i32_i16 %3, %13, %20, %22\n\t" \
+        "v_dot2_i32_i16 %4, %14, %20, %22\n\t" \
+        "v_dot2_i32_i16 %5, %15, %20, %22\n\t" \
+        "v_dot2_i32_i16 %6, %16, %20, %22\n\t" \
+        "v_dot2_i32_i16 %7, %17, %20, %22\n\t" \
+        "v_dot2_i32_i16 %8, %18, %20, %22\n\t" \
+        "v_dot2_i32_i16 %9, %19, %20, %22\n\t" \
+        "v_dot2c_i32_i16_dpp %0, %10, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %1, %11, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %2, %12, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %3, %13, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %4, %14, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %5, %15, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %6, %16, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %7, %17, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %8, %18, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_dot2c_i32_i16_dpp %9, %19, %21 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+template <int G>
+__device__ __forceinline__ void deriv5(const uint32_t* gx, const uint32_t* gy, uint32_t wtop, uint32_t wbot, int rnd, uint32_t* ixx, uint32_t* iyy, uint32_t& cx, uint32_t& cy)
 {
-    asm("v_dot2_i32_i16 %0, %5, %10, %12\n\t"
-        "v_dot2_i32_i16 %1, %6, %10, %12\n\t"
-        "v_dot2_i32_i16 %2, %7, %10, %12\n\t"
-        "v_dot2_i32_i16 %3, %8, %10, %12\n\t"
-        "v_dot2_i32_i16 %4, %9, %10, %12\n\t"
-        "v_dot2c_i32_i16_dpp %0, %5, %11 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_dot2c_i32_i16_dpp %1, %6, %11 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_dot2c_i32_i16_dpp %2, %7, %11 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_dot2c_i32_i16_dpp %3, %8, %11 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_dot2c_i32_i16_dpp %4, %9, %11 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_ashrrev_i32 %0, %13, %0\n\t"
-        "v_ashrrev_i32 %1, %13, %1\n\t"
-        "v_ashrrev_i32 %2, %13, %2\n\t"
-        "v_ashrrev_i32 %3, %13, %3\n\t"
-        "v_ashrrev_i32 %4, %13, %4"
-        : "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "=&v"(o4)
-        : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(x4), "v"(wtop), "v"(wbot), "v"(rnd), "n"(SH));
+    uint32_t x0, x1, x2, x3, x4, y0, y1, y2, y3, y4;
+    const uint32_t hi2 = 0x07060302u, hi1 = 0x0C0C0302u;
+    if (G == 0) {            // columns 0 .. 4: pairs (0, 1), (2, 3); 4 is carried
+        asm(AV_DERIV_DOTS
+            "v_perm_b32 %0, %1, %0, %23\n\t"
+            "v_perm_b32 %5, %6, %5, %23\n\t"
+            "v_perm_b32 %2, %3, %2, %23\n\t"
+            "v_perm_b32 %7, %8, %7, %23"
+            : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3), "=&v"(x4), "=&v"(y0), "=&v"(y1), "=&v"(y2), "=&v"(y3), "=&v"(y4)
+            : "v"(gx[0]), "v"(gx[1]), "v"(gx[2]), "v"(gx[3]), "v"(gx[4]), "v"(gy[0]), "v"(gy[1]), "v"(gy[2]), "v"(gy[3]), "v"(gy[4]),
+              "v"(wtop), "v"(wbot), "v"(rnd), "s"(hi2));
+        ixx[0] = x0; iyy[0] = y0; ixx[1] = x2; iyy[1] = y2; cx = x4; cy = y4;
+    } else if (G == 1) {     // columns 5 .. 9: pairs (4, 5), (6, 7), (8, 9)
+        asm(AV_DERIV_DOTS
+            "v_perm_b32 %0, %0, %24, %23\n\t"
+            "v_perm_b32 %5, %5, %25, %23\n\t"
+            "v_perm_b32 %1, %2, %1, %23\n\t"
+            "v_perm_b32 %6, %7, %6, %23\n\t"
+            "v_perm_b32 %3, %4, %3, %23\n\t"
+            "v_perm_b32 %8, %9, %8, %23"
+            : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3), "=&v"(x4), "=&v"(y0), "=&v"(y1), "=&v"(y2), "=&v"(y3), "=&v"(y4)
+            : "v"(gx[5]), "v"(gx[6]), "v"(gx[7]), "v"(gx[8]), "v"(gx[9]), "v"(gy[5]), "v"(gy[6]), "v"(gy[7]), "v"(gy[8]), "v"(gy[9]),
+              "v"(wtop), "v"(wbot), "v"(rnd), "s"(hi2), "v"(cx), "v"(cy));
+        ixx[2] = x0; iyy[2] = y0; ixx[3] = x1; iyy[3] = y1; ixx[4] = x3; iyy[4] = y3;
+    } else {                 // columns 10 .. 14: pairs (10, 11), (12, 13), (14, the zero 16th column)
+        asm(AV_DERIV_DOTS
+            "v_perm_b32 %0, %1, %0, %23\n\t"
+            "v_perm_b32 %5, %6, %5, %23\n\t"
+            "v_perm_b32 %2, %3, %2, %23\n\t"
+            "v_perm_b32 %7, %8, %7, %23\n\t"
+            "v_perm_b32 %4, %4, %4, %24\n\t"
+            "v_perm_b32 %9, %9, %9, %24"
+            : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3), "=&v"(x4), "=&v"(y0), "=&v"(y1), "=&v"(y2), "=&v"(y3), "=&v"(y4)
+            : "v"(gx[10]), "v"(gx[11]), "v"(gx[12]), "v"(gx[13]), "v"(gx[14]), "v"(gy[10]), "v"(gy[11]), "v"(gy[12]), "v"(gy[13]), "v"(gy[14]),
+              "v"(wtop), "v"(wbot), "v"(rnd), "s"(hi2), "s"(hi1));
+        ixx[5] = x0; iyy[5] = y0; ixx[6] = x2; iyy[6] = y2; ixx[7] = x4; iyy[7] = y4;
+    }
 }
+#undef AV_DERIV_DOTS
 
 // The I patch itself is only ever used as the accumulator seed of the iteration's interpolation:
 //   ((dot + R) >> 9) - ival == (dot + R - (ival << 9)) >> 9,  seed = R - (ival << 9),  ival << 9 == acc & ~511 (acc >= 0)
@@ -292,10 +405,11 @@ __device__ __forceinline__ void jdiff5(uint32_t T0, uint32_t T1, uint32_t T2, ui
 }
 
 // This lane's row of the I patch and of the two Scharr derivative patches from staged rows r .. r+2 of the window's 18 x 18-byte
-// neighbourhood (load_row(t, B): the five dwords of staged row r + t, byte 0 = window column -1), and the lane's share of the
-// normal-equation sums.
+// neighbourhood (load_row(t, B): the five dwords of staged row r + t; byte 0 of B[0] = window column -1, and B[4] holds the row's bytes
+// 14 .. 17: the last two are the ones wanted), and the lane's share of the normal-equation sums.  lane_on: all ones in lanes 0 .. 14,
+// zero in lane 15.
 template <int WIN, typename LoadRow>
-__device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, uint32_t wbot, int ipx, int ipy, int w, int h, int r,
+__device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, uint32_t wbot, uint32_t lane_on, int ipx, int ipy, int w, int h, int r,
                                               int (&iv)[WIN], uint32_t (&ixx)[(WIN + 1) / 2], uint32_t (&iyy)[(WIN + 1) / 2], int& a11, int& a12, int& a22)
 {
     constexpr int W_BITS = 14;
@@ -308,9 +422,9 @@ __device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, u
         uint32_t B[5];
         load_row(t, B);
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {                // bytes 2k, 2k+1
-            const int b0 = 2 * k;
-            E[t][k] = __builtin_amdgcn_perm(0, B[b0 >> 2], 0x0C000C00u | (uint32_t)(b0 & 3) | ((uint32_t)((b0 & 3) + 1) << 16));
+        for (int k = 0; k < 9; ++k) {                // bytes 2k, 2k+1: of dword k >> 1 for k < 8; bytes 16, 17 are bytes 2, 3 of B[4]
+            const int b0 = k < 8 ? 2 * k : 2;
+            E[t][k] = __builtin_amdgcn_perm(0, B[k >> 1], 0x0C000C00u | (uint32_t)(b0 & 3) | ((uint32_t)((b0 & 3) + 1) << 16));
         }
     }
     // (hi half of x | lo half of y << 16): the pair one column to the right of x, given y = the next pair
@@ -324,22 +438,28 @@ __device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, u
     // Scharr on the even window columns (pairs c = 2k, 2k+1); the odd-aligned pairs are byte permutes of those:
     //   gx[c] = t0[s+1] - t0[s-1],  gy[c] = (t1[s+1] + t1[s-1]) * 3 + t1[s] * 10,  s = c+1,
     //   t0 = (row above + row below) * 3 + row * 10,  t1 = row below - row above
+    // Both are built TIMES 4 (deriv5 takes the high half of its accumulator instead of shifting it), inside the constants they are
+    // multiplied by anyway: 4 t0 = (above + below) * 12 + row * 40 <= 16 x 255 x 4 = 16,320 < 2^16 as the unsigned half it is computed
+    // in, 4 gx = 4 t0[s+1] - 4 t0[s-1] and 4 gy = (t1[s+1] + t1[s-1]) * 12 + t1[s] * 40 lie in [-16,320, 16,320], inside the signed
+    // 16-bit range: the packed arithmetic is modulo 2^16, so each half holds the two's-complement form of exactly that value.
     uint32_t gxp[WIN + 1], gyp[WIN + 1];
     {
         uint32_t t0E[9], t1E[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            t0E[k] = pk_add(pk_mul(pk_add(E[0][k], E[2][k]), 3), pk_mul(E[1][k], 10));
+            t0E[k] = pk_add(pk_mul(pk_add(E[0][k], E[2][k]), 12), pk_mul(E[1][k], 40));
             t1E[k] = pk_sub(E[2][k], E[0][k]);
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {                 // window columns (2k, 2k+1): centres O[k], left E[k], right E[k+1]
             gxp[2 * k] = pk_sub(t0E[k + 1], t0E[k]);
-            gyp[2 * k] = pk_add(pk_mul(pk_add(t1E[k + 1], t1E[k]), 3), pk_mul(mid(t1E[k], t1E[k + 1]), 10));
+            gyp[2 * k] = pk_add(pk_mul(pk_add(t1E[k + 1], t1E[k]), 12), pk_mul(mid(t1E[k], t1E[k + 1]), 40));
         }
     }
     // the derivative image is zero outside the image: only windows at the border pay for the masks
-    const bool inside = ipx >= 0 && ipx + WIN < w && ipy >= 0 && ipy + WIN < h;
+    // 0 <= ipx && ipx + WIN < w as ONE unsigned compare per axis: a negative index is above 2^31 as unsigned and any limit below it; a level
+    // no wider than the window has the limit 0, which nothing is below (the limits are wave-uniform: scalar)
+    const bool inside = (unsigned)ipx < (unsigned)max(w - WIN, 0) && (unsigned)ipy < (unsigned)max(h - WIN, 0);
     if (__builtin_amdgcn_ballot_w64(!inside) != 0) {
         // the masks are built from an opaque copy of ipx made INSIDE the block: without it the compiler hoists the 60-odd
         // compares / selects of the mask values onto the common path and keeps only the 16 ANDs in here
@@ -360,25 +480,24 @@ __device__ __forceinline__ void lk_patch_rows(LoadRow load_row, uint32_t wtop, u
     }
     // Lane 15 (row 15 feeds only the interpolation of row 14, through the DPP operand of the lane above, which is the pixel pair and not
     // a weight) interpolates its derivatives with zero weights and a zero rounding term: its Ix, Iy pairs are zero, and so are its shares
-    // of a11 / a12 / a22 here and of b1 / b2 in every Newton iteration, with no select there.
-    if (r >= WIN) { wtop = 0; wbot = 0; }
-    const int rnd_i = 1 << (W_BITS - 6), rnd_d = r < WIN ? 1 << (W_BITS - 1) : 0;      // rounding terms, one register each
+    // of a11 / a12 / a22 here and of b1 / b2 in every Newton iteration, with no select there.  The zeroing is an AND with the lane
+    // mask (x & ~0 = x, x & 0 = 0: what the three selects did, at full rate and without VCC).
+    const int rnd_i = 1 << (W_BITS - 6);
+    const uint32_t wtop_d = wtop & lane_on, wbot_d = wbot & lane_on;
+    const int rnd_d = (int)((4u << (W_BITS - 1)) & lane_on);                // 4 * 2^13: the derivatives come in times 4 (deriv5)
     // The derivative patches are kept as PAIRS of adjacent columns, (Ix[2p] | Ix[2p+1] << 16) and the same for Iy (|Ix|, |Iy| <= 4080;
     // the 16th column is zero): every window sum is then a chain of v_dot2_i32_i16 -- two columns per instruction -- instead of one
     // v_mad_i32_i16 per column (24 instead of 45 here, 16 + 7 pair packs instead of 30 in every Newton iteration; the same exact
     // integers, whatever the grouping).
-    int ixv[WIN + 1], iyv[WIN + 1];
-    ixv[WIN] = 0; iyv[WIN] = 0;
 #pragma unroll
-    for (int c = 0; c < WIN; c += 5) {
+    for (int c = 0; c < WIN; c += 5)
         bilin5_seed(px[c], px[c + 1], px[c + 2], px[c + 3], px[c + 4], wtop, wbot, rnd_i, iv[c], iv[c + 1], iv[c + 2], iv[c + 3], iv[c + 4]);
-        bilin5<W_BITS>(gxp[c], gxp[c + 1], gxp[c + 2], gxp[c + 3], gxp[c + 4], wtop, wbot, rnd_d, ixv[c], ixv[c + 1], ixv[c + 2], ixv[c + 3], ixv[c + 4]);
-        bilin5<W_BITS>(gyp[c], gyp[c + 1], gyp[c + 2], gyp[c + 3], gyp[c + 4], wtop, wbot, rnd_d, iyv[c], iyv[c + 1], iyv[c + 2], iyv[c + 3], iyv[c + 4]);
-    }
+    uint32_t cx = 0, cy = 0;
+    deriv5<0>(gxp, gyp, wtop_d, wbot_d, rnd_d, ixx, iyy, cx, cy);
+    deriv5<1>(gxp, gyp, wtop_d, wbot_d, rnd_d, ixx, iyy, cx, cy);
+    deriv5<2>(gxp, gyp, wtop_d, wbot_d, rnd_d, ixx, iyy, cx, cy);
 #pragma unroll
     for (int p = 0; p < (WIN + 1) / 2; ++p) {
-        ixx[p] = __builtin_amdgcn_perm((uint32_t)ixv[2 * p + 1], (uint32_t)ixv[2 * p], 0x05040100u);
-        iyy[p] = __builtin_amdgcn_perm((uint32_t)iyv[2 * p + 1], (uint32_t)iyv[2 * p], 0x05040100u);
         a11 = dot2(ixx[p], ixx[p], a11);
         a12 = dot2(ixx[p], iyy[p], a12);
         a22 = dot2(iyy[p], iyy[p], a22);
@@ -401,6 +520,10 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
     const int g = threadIdx.x >> 4;                 // point slot of this 16-lane group inside the workgroup
     const int r = threadIdx.x & 15;                 // window row owned by this lane (row 15 only feeds row 14)
     uint32_t* tile = tile_all[g];
+    // all ones in the lanes that own a window row, zero in lane 15 (lk_patch_rows); opaque, or the compiler turns the ANDs back into selects
+    // (not volatile: a volatile asm counts as a store to anything, and the wave-uniform loads below it would leave the scalar unit)
+    uint32_t lane_on = r < WIN ? ~0u : 0u;
+    asm("" : "+v"(lane_on));
     // Workgroup -> (point set, block of 16 points).  The dispatcher deals workgroups round-robin over the 8 XCDs (linear id mod 8,
     // MI355X_MICROARCH.md "Workgroup dispatch"), and each XCD has its own L2: with the plain (block, set) grid the ~19 workgroups of
     // one stream land on all eight XCDs and every L2 fetches that stream's two pyramids (profiles/r03/fetch_calib.json, rows32: a
@@ -437,8 +560,11 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
         const int col_lo = -AV_PYR_BORDER, col_hi = pitch - AV_PYR_BORDER;
         const float scale = __int_as_float((127 - level) << 23);       // 2^-level (written as 1. / (1 << level) it is an fp64 division per level)
         float pvx = prevx0 * scale, pvy = prevy0 * scale;
-        if (level == a.g.levels - 1) { curx = curx * scale; cury = cury * scale; }
-        else                         { curx = curx * 2.f;   cury = cury * 2.f; }
+        // the guess is scaled by 2^-level at the top level and doubled below it: ONE wave-uniform factor, chosen on the scalar unit (the
+        // asm keeps it in a scalar register: left alone the compiler selects it per lane, through VCC); the products are the same
+        uint32_t gmul = level == a.g.levels - 1 ? (uint32_t)(127 - level) << 23 : 0x40000000u;
+        asm("" : "+s"(gmul));
+        curx = curx * __uint_as_float(gmul); cury = cury * __uint_as_float(gmul);
         pvx -= halfWin; pvy -= halfWin;
         // The floor stays a float for the fraction: an index that passes the bounds test is below 2^12 in magnitude, (float)(int)floor
         // is the floor itself.  The bounds test is -WIN <= i < size as ONE unsigned compare per axis on the index biased by WIN (an
@@ -455,16 +581,18 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
 
         // ---- stage the 18 x 18-byte neighbourhood of the I window: rows ipy-1 .., bytes ipx-1 .. ipx+16 of each as five dwords
         //      read at their (unaligned) byte address, so that every staged row starts at window column -1.  All bytes lie inside
-        //      the padded pyramid row: ipx - 1 >= -16 and ipx + 16 <= w + 15 (the 5th dword is fetched 2 bytes early and shifted).
+        //      the padded pyramid row: ipx - 1 >= -16 and ipx + 16 <= w + 15 (the 5th dword is fetched 2 bytes early and stored as it
+        //      is: it holds bytes 14 .. 17 of the row, lk_patch_rows takes its upper two).
         // Lane map of both staging loops: lane r handles dword (r & 7) of rows 2k + (r >> 3): the global address is a
         // wave-uniform base (padded level origin + 2k rows, scalar) plus ONE per-lane 32-bit offset, the LDS address one
-        // per-lane base plus an immediate -- no per-load index arithmetic on the vector unit.
+        // per-lane base plus an immediate -- no per-load index arithmetic on the vector unit.  lk_row_base makes the row base opaque
+        // in a scalar register pair: handed the sum, the compiler re-associates it into (origin + lane offset) + row step, a chain of
+        // 64-bit vector additions per load.  The per-lane offsets are non-negative (bounds tests above, 16-pixel frame), below 2^31.
         const int sub = r >> 3, dwl = r & 7;
         const uint32_t tofs = (uint32_t)(sub * (TPITCH / 4) + dwl);
         LK_STAMP(LKP_HEAD);
         if (PROF) ++pn_level;
         wave_lds_sync();
-        typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
         {
             // source of this level's I rows: the padded pyramid level (origin at row -16, column -16, frame included) or, for
             // level 0 in place, the caller's image (origin at pixel (0, 0), no frame: windows over the border take the slow path)
@@ -474,25 +602,25 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
             const bool act = dwl < 5;                                    // 5 of the 8 slots of a row carry a dword
             if (!extI || (ipx >= 1 && ipx + 16 < w && ipy >= 1 && ipy + 16 < h)) {
                 const uint32_t loff = (uint32_t)(__mul24(ipy - 1 + sub + bI, pI) + (ipx - 1 + bI) + (dwl < 4 ? 4 * dwl : 14));
-                const uint32_t shamt = dwl == 4 ? 16u : 0u;
                 uint32_t sv[9];
 #pragma unroll
                 for (int k = 0; k < 9; ++k) {                               // 18 rows
                     sv[k] = 0;
-                    if (act) sv[k] = *reinterpret_cast<const u32_unaligned*>(L0 + (size_t)(2 * k) * (size_t)pI + loff);
+                    if (act) sv[k] = lk_load_u32(lk_row_base(L0, 2 * k, pI), loff);
                 }
 #pragma unroll
                 for (int k = 0; k < 9; ++k)
-                    if (act) tile[tofs + 2 * k * (TPITCH / 4)] = sv[k] >> shamt;
+                    if (act) tile[tofs + 2 * k * (TPITCH / 4)] = sv[k];
             } else if (act) {
-                // the window reaches over the image border: the bytes the padded level's BORDER_REFLECT_101 frame would hold
-                const int xb = ipx - 1 + (dwl < 4 ? 4 * dwl : 16), nbyte = dwl < 4 ? 4 : 2;
+                // the window reaches over the image border: the bytes the padded level's BORDER_REFLECT_101 frame would hold (the fifth
+                // dword: row bytes 16, 17 in ITS bytes 2, 3, where the fast path has them; its lower half is never read)
+                const int xb = ipx - 1 + (dwl < 4 ? 4 * dwl : 16), nbyte = dwl < 4 ? 4 : 2, bsh = dwl < 4 ? 0 : 16;
 #pragma unroll 1
                 for (int k = 0; k < 9; ++k) {
                     const uint8_t* row = L0 + (size_t)av_reflect101(ipy - 1 + sub + 2 * k, h) * (size_t)w;
                     uint32_t v = 0;
 #pragma unroll 1
-                    for (int bb = 0; bb < nbyte; ++bb) v |= (uint32_t)row[av_reflect101(xb + bb, w)] << (8 * bb);
+                    for (int bb = 0; bb < nbyte; ++bb) v |= (uint32_t)row[av_reflect101(xb + bb, w)] << (8 * bb + bsh);
                     tile[tofs + 2 * k * (TPITCH / 4)] = v;
                 }
             }
@@ -508,13 +636,16 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
                                const uint32_t* rowp = tile + __mul24(r + t, TPITCH / 4);
 #pragma unroll
                                for (int k = 0; k < 5; ++k) B[k] = rowp[k];
-                           }, wtop, wbot, ipx, ipy, w, h, r, iv, ixx, iyy, a11, a12, a22);
-        const float A11 = row_sum16_scaled(a11);
+                           }, wtop, wbot, lane_on, ipx, ipy, w, h, r, iv, ixx, iyy, a11, a12, a22);
+        const float A11 = row_sum_sq_scaled(a11);
         const float A12 = row_sum16_scaled(a12);
-        const float A22 = row_sum16_scaled(a22);
+        const float A22 = row_sum_sq_scaled(a22);
         float D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
-        if (minEig < a.min_eig_up || D < 1.1920928955078125e-7f) {
+        // minEig = eigNum / (2 WIN^2) is only ever compared with the threshold: fl(eigNum / 450) < min_eig_up <=> eigNum < min_eig_num
+        // (av_lk_quotient_bound, computed by lk_fill_args: the correctly rounded division by a positive constant is monotone).  eigNum is
+        // finite here (|A| < 2^12), so neither side meets a NaN of its own; a NaN threshold gives a NaN bound, and both forms are false.
+        const float eigNum = A22 + A11 - lk_sqrt_ranged((A11 - A22) * (A11 - A22) + 4.f * A12 * A12);
+        if (eigNum < a.min_eig_num || D < 1.1920928955078125e-7f) {
             if (level == 0) ok = false;
             continue;
         }
@@ -558,7 +689,7 @@ __device__ __forceinline__ bool lk_track_g16_body(const LKArgs& a)
                         uint32_t sv[TILE_ROWS / 2];
 #pragma unroll
                         for (int k = 0; k < TILE_ROWS / 2; ++k)        // 24 rows x 8 dwords
-                            sv[k] = *reinterpret_cast<const u32_unaligned*>(LJ0 + (size_t)(2 * k) * (size_t)pJ + joff);
+                            sv[k] = lk_load_u32(lk_row_base(LJ0, 2 * k, pJ), joff);
 #pragma unroll
                         for (int k = 0; k < TILE_ROWS / 2; ++k) tile[tofs + 2 * k * (TPITCH / 4)] = sv[k];
                     } else {
@@ -869,6 +1000,7 @@ static int lk_fill_args(LKArgs& a, const ImgView& I, const ImgView& J, const Pyr
     a.max_iter = p.max_iter; a.eps2 = p.eps2;
     a.min_eig_up = (float)p.min_eig;
     if ((double)a.min_eig_up < p.min_eig) a.min_eig_up = nextafterf(a.min_eig_up, INFINITY);
+    a.min_eig_num = av_lk_quotient_bound(a.min_eig_up, (float)(2 * p.win * p.win));      // read by the 16-lane kernel (win == 15) only
     if (p.eps2 >= 1e-30) { a.eps_lo = (float)(p.eps2 * (1. - 0x1p-18)); a.eps_hi = (float)(p.eps2 * (1. + 0x1p-18)); }
     else { a.eps_lo = -1.f; a.eps_hi = INFINITY; }                 // e32 may underflow: every test in fp64
     a.min_eig = p.min_eig;
@@ -923,10 +1055,12 @@ int av_launch_lk(const ImgView& I, const ImgView& J, int n_set, const PyrGeom& g
     return AV_OK;
 }
 
-AV_EXPORT int av_lk_track(const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_stride, int n_set,
-                          int w, int h, int levels,
-                          const float* prev_dev, float* next_dev, uint8_t* status_dev, const int32_t* count_dev, int cap,
-                          int win, int max_iter, double eps, double min_eig_threshold, void* stream)
+// av_lk_track and av_lk_track_images: the latter reads level 0 in place from the two image arrays (the engine's way), the former from the pyramids
+static int lk_track_api(const uint8_t* imgI_dev, const uint8_t* imgJ_dev, int64_t img_stride,
+                        const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_stride, int n_set,
+                        int w, int h, int levels,
+                        const float* prev_dev, float* next_dev, uint8_t* status_dev, const int32_t* count_dev, int cap,
+                        int win, int max_iter, double eps, double min_eig_threshold, void* stream)
 {
     av_pyr_layout lay;
     int rc = av_pyramid_layout(w, h, levels, &lay);
@@ -942,6 +1076,29 @@ AV_EXPORT int av_lk_track(const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int6
     double e = eps < 0 ? 0. : (eps > 10. ? 10. : eps);
     p.eps2 = e * e;
     p.min_eig = min_eig_threshold;
-    return av_launch_lk(ImgView{pyrI_dev, pyr_stride, nullptr, 0, nullptr}, ImgView{pyrJ_dev, pyr_stride, nullptr, 0, nullptr}, n_set, av_make_geom(lay),
+    return av_launch_lk(ImgView{pyrI_dev, pyr_stride, imgI_dev, img_stride, nullptr}, ImgView{pyrJ_dev, pyr_stride, imgJ_dev, img_stride, nullptr}, n_set, av_make_geom(lay),
                         prev_dev, next_dev, status_dev, count_dev, cap, cap, p, (hipStream_t)stream);
+}
+
+AV_EXPORT int av_lk_track(const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_stride, int n_set,
+                          int w, int h, int levels,
+                          const float* prev_dev, float* next_dev, uint8_t* status_dev, const int32_t* count_dev, int cap,
+                          int win, int max_iter, double eps, double min_eig_threshold, void* stream)
+{
+    return lk_track_api(nullptr, nullptr, 0, pyrI_dev, pyrJ_dev, pyr_stride, n_set, w, h, levels, prev_dev, next_dev, status_dev, count_dev, cap,
+                        win, max_iter, eps, min_eig_threshold, stream);
+}
+
+AV_EXPORT int av_lk_track_images(const uint8_t* imgI_dev, const uint8_t* imgJ_dev, int64_t img_stride,
+                                 const uint8_t* pyrI_dev, const uint8_t* pyrJ_dev, int64_t pyr_stride, int n_set,
+                                 int w, int h, int levels,
+                                 const float* prev_dev, float* next_dev, uint8_t* status_dev, const int32_t* count_dev, int cap,
+                                 int win, int max_iter, double eps, double min_eig_threshold, void* stream)
+{
+    if (!imgI_dev || !imgJ_dev || w <= 0 || h <= 0 || img_stride < (int64_t)w * h) {
+        av_set_error("av_lk_track_images: bad arguments");
+        return AV_E_INVALID;
+    }
+    return lk_track_api(imgI_dev, imgJ_dev, img_stride, pyrI_dev, pyrJ_dev, pyr_stride, n_set, w, h, levels, prev_dev, next_dev, status_dev, count_dev, cap,
+                        win, max_iter, eps, min_eig_threshold, stream);
 }

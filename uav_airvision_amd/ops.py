@@ -53,10 +53,12 @@ def pyramid_level(pyr_row, lay, level, with_border=False):
 
 
 def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, next_pts, winSize=(15, 15), maxLevel=3,
-                             criteria=(3, 30, 0.01), flags=4, minEigThreshold=1e-4, device=0):
+                             criteria=(3, 30, 0.01), flags=4, minEigThreshold=1e-4, device=0, level0_in_place=False):
     """cv2.calcOpticalFlowPyrLK(prev, next, prevPts, nextPts, **lk_params) on the GPU
     (reference: feature_tracker.py:102-108, stereo_matcher.py:64-74, config.py:37-44).
-    Returns (next_pts float32[N,2], status uint8[N,1], None)."""
+    Returns (next_pts float32[N,2], status uint8[N,1], None).
+    level0_in_place: level 0 is read from the images themselves (av_lk_track_images, the engine's way: the level-0 regions of the
+    pyramids are left unwritten and unread); the results are the same."""
     if not (flags & 4):
         raise ValueError('only OPTFLOW_USE_INITIAL_FLOW is implemented (the reference always sets it)')
     ctype, max_iter, eps = criteria
@@ -74,17 +76,25 @@ def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, next_pts, winSize=(15
     while eff < maxLevel and (lw + 1) // 2 > winSize[0] and (lh + 1) // 2 > winSize[1]:
         lw, lh, eff = (lw + 1) // 2, (lh + 1) // 2, eff + 1
     maxLevel = eff
-    pyr, lay = build_pyramids(imgs, maxLevel + 1, device)
     dev = _dev(device)
+    d_imgs = torch.from_numpy(imgs).to(dev)
+    if level0_in_place:          # levels 1 and up only, over a zeroed buffer: where the library leaves level 0 unwritten it holds no image
+        pyr, lay = build_pyramids(d_imgs, maxLevel + 1, device, write_level0=False,
+                                  out=torch.zeros((2, pyramid_layout(imgs.shape[2], imgs.shape[1], maxLevel + 1).bytes), dtype=torch.uint8, device=dev))
+    else:
+        pyr, lay = build_pyramids(d_imgs, maxLevel + 1, device)
     d_prev = torch.from_numpy(prev).to(dev)
     d_next = torch.from_numpy(nxt).to(dev)
     d_status = torch.zeros(n, dtype=torch.uint8, device=dev)
     d_count = torch.tensor([n], dtype=torch.int32, device=dev)
     h, w = imgs.shape[1:]
     with torch.cuda.device(device):
-        N.check(N.lib().av_lk_track(N.dptr(pyr[0]), N.dptr(pyr[1]), lay.bytes, 1, w, h, maxLevel + 1,
-                                    N.dptr(d_prev), N.dptr(d_next), N.dptr(d_status), N.dptr(d_count), n,
-                                    int(winSize[0]), max_iter, eps, float(minEigThreshold), N.current_stream()))
+        tail = (lay.bytes, 1, w, h, maxLevel + 1, N.dptr(d_prev), N.dptr(d_next), N.dptr(d_status), N.dptr(d_count), n,
+                int(winSize[0]), max_iter, eps, float(minEigThreshold), N.current_stream())
+        if level0_in_place:
+            N.check(N.lib().av_lk_track_images(N.dptr(d_imgs[0]), N.dptr(d_imgs[1]), w * h, N.dptr(pyr[0]), N.dptr(pyr[1]), *tail))
+        else:
+            N.check(N.lib().av_lk_track(N.dptr(pyr[0]), N.dptr(pyr[1]), *tail))
         torch.cuda.synchronize()
     return d_next.cpu().numpy(), d_status.cpu().numpy().reshape(-1, 1), None
 
