@@ -1110,6 +1110,393 @@ __device__ __forceinline__ void augment_body(const AugArgs& a)
 __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) { augment_body(a); }
 
 // ================================================================================================
+// dk_cov<64>'s body: the sums of propagate_body<true, 64>, of dk_cov's cross block and of augment_body<64>, term for term, in the
+// same order and with the same fused multiply-adds -- dk_cov<256>, which is built from those bodies, is its bit reference
+// (tests/test_gpu_dk_cov_chains.py) -- laid out for ONE wavefront that shares its CU with the front-end:
+//  * independent chains.  A lane's entries of a phase advance together: the loop over k is outermost and runs over the OR of the
+//    rows' masks (wave-uniform, a scalar register), the loads of a step are issued ahead of its multiply-adds, and an entry whose own
+//    mask lacks bit k skips the term by predicate.  (propagate_body walks one entry after the other, each a chain of up to 11
+//    dependent steps of ctz, address, two LDS reads, one v_fma_f64.)
+//  * the twelve rows of F that are zero by construction (3-5, 9-11, 15-20) are not stored, and neither are the same rows of Fdt^2,
+//    Fdt^3 and Phi: with a finite F they are zero and Phi's are rows of the identity, 1.0 + 0 + 0/2 + 0/6.  Their products keep the
+//    parent's form, 0 + 1.0 * x (a -0.0 comes out as +0.0).  A term F[r][k] * F[k][c] whose k is such a row is +-0 added to a sum
+//    that began at +0.0 and is never -0.0: it is left out.
+//  * G is not stored: its entries are 0, +-1 and -R^T, and T = Phi G runs over the same masks with the entry made on the spot.
+//  * no matrix Q: Phi PhiT is written into the second of two PhiT buffers (the caller swaps them per sample), the unsymmetrised
+//    P11 into P11s itself (that phase reads Phi P11, Phi and T) and is symmetrised in place, a lane per (r, c) / (c, r) pair.
+// Contraction is switched off in these functions and every fused multiply-add is written out, as read from the parent's code:
+// Phi = fma(Fdt^2, 0.5, I + Fdt) + Fdt^3 / 6;  q = fma(T[r][k] * noise, T[c][k], q);  P11 = fma(q, dt, s).  The scalar preparation
+// (quaternions, u, w1, w2, the two patches of Phi) is propagate_body's text, compiled as that is.
+// ================================================================================================
+constexpr int CVC_NN = IMU_DIM * IMU_DIM, CVC_NR = 9 * IMU_DIM;         // a 21 x 21 matrix; the nine rows that are not unit rows
+// LDS, in doubles: PhiT (a) | Phi P11 | Fdt | Fdt^2 | Phi | PhiT (b) | P11.  T (21 x 12) lies over Fdt / Fdt^2, which are dead once Phi is
+// built; J, the new rows' first 21 columns and the corner (augmentation) lie over Phi P11.
+constexpr int CVC_PHIA = 0, CVC_PP = CVC_NN, CVC_FD = 2 * CVC_NN, CVC_F2 = CVC_FD + CVC_NR, CVC_PH = CVC_F2 + CVC_NR, CVC_PHIB = CVC_PH + CVC_NR,
+              CVC_P11 = CVC_PHIB + CVC_NN, CVC_DOUBLES = CVC_P11 + CVC_NN;
+struct CovChainsLds {
+    double m[CVC_DOUBLES];
+    double Rwi[9], Rnull[9], Rnew[9], u[3], sv[3], w1[3], w2[3];
+    unsigned frow[9], fcol[IMU_DIM], prow[9], pad;      // frow / prow: per stored row
+};
+static_assert(sizeof(CovChainsLds) <= 21760, "four of dk_cov<64>'s wavefronts beside twenty of LK's on a CU");
+static_assert(IMU_DIM * 12 <= 2 * CVC_NR && 2 * 6 * IMU_DIM + 36 <= CVC_NN, "T over Fdt | Fdt^2, the augmentation's matrices over Phi P11");
+using cvc_gptr = double __attribute__((address_space(1)))*;              // P is global memory: global_load / global_store, not flat
+// entry `bytes` / 8 of a row whose start is wave-uniform: the address is a scalar base plus ONE 32-bit offset per lane (21 rows of a
+// column addressed by 21 vector pointers are 42 registers)
+__device__ __forceinline__ cvc_gptr cvc_in_row(cvc_gptr row, unsigned bytes) { return (cvc_gptr)((char __attribute__((address_space(1)))*)row + bytes); }
+
+__device__ __forceinline__ int cvc_full(int q) { return q + 3 * (q / 3); }                      // stored row 0 .. 8 -> row 0-2, 6-8, 12-14
+__device__ __forceinline__ int cvc_stored(int r) { return r - 3 * (r / 6); }                    // (of such a row only)
+__device__ __forceinline__ int cvc_unit_row(int u) { return u < 6 ? 3 + 6 * (u / 3) + u % 3 : 9 + u; }      // 0 .. 11 -> 3-5, 9-11, 15-20
+__device__ __forceinline__ double cvc_pick3(int i, double a0, double a1, double a2) { return i == 0 ? a0 : (i == 1 ? a1 : a2); }
+// the OR of n mask words in LDS: every lane reads them all, so the value is wave-uniform and goes into a scalar register
+template <int n> __device__ __forceinline__ unsigned cvc_union(const unsigned* m)
+{
+    unsigned u = 0;
+#pragma unroll
+    for (int i = 0; i < n; ++i) u |= m[i];
+    return __builtin_amdgcn_readfirstlane(u);
+}
+// G[k][c] of propagate_body (c < 12; k wave-uniform): -I, I, -R_w_i^T, I on the diagonal blocks of rows 0 .. 11, +0.0 elsewhere
+__device__ __forceinline__ double cvc_G(const double* Rwi, int k, int c)
+{
+    const int b = k / 3;
+    const bool in = k < 12 && c / 3 == b;
+    double v = c == k ? (b == 0 ? -1.0 : 1.0) : 0.0;
+    if (b == 2) v = -Rwi[(in ? c - 6 : 0) * 3 + (k - 6)];
+    return in ? v : 0.0;
+}
+
+// q[j] = sum over k < 12 of (T[r][k] * noise[k / 3]) * T[c][k], from +0.0 in ascending k, for J entries side by side
+template <int J> __device__ __forceinline__ void cvc_noise(const double* T, const double* noise, const int (&r)[J], const int (&c)[J], double (&q)[J])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < J; ++j) q[j] = 0;
+#pragma unroll 1
+    for (int b = 0; b < 4; ++b) {
+        const double nz = noise[b];
+#pragma unroll 1
+        for (int kk = 0; kk < 3; ++kk) {
+            const int k = 3 * b + kk;
+            double x[J], y[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) { x[j] = T[r[j] * 12 + k]; y[j] = T[c[j] * 12 + k]; }
+#pragma unroll
+            for (int j = 0; j < J; ++j) q[j] = __builtin_fma(x[j] * nz, y[j], q[j]);
+        }
+    }
+}
+
+// the scalar preparation of one sample: propagate_body's, at NT = 64, on the nine stored rows and without an indexable local array
+// (skw[r * 3 + c] and ska[k * 3 + c] were 184 B of scratch per lane)
+__device__ __forceinline__ void cvc_prepare(const PropArgs& a, CovChainsLds& L, int tid)
+{
+    const int N = IMU_DIM;
+    double* const F = L.m + CVC_FD;
+    for (int i = tid; i < CVC_NR; i += 64) F[i] = 0.0;
+    if (tid < 3) quat_to_rot(tid == 0 ? a.q_old : (tid == 1 ? a.q_null : a.q_new), tid == 0 ? L.Rwi : (tid == 1 ? L.Rnull : L.Rnew));
+    __syncthreads();
+    if (tid < 9) {
+        const int r = tid / 3, c = tid - 3 * r;
+        const double* w = a.gyro; const double* ac = a.acc;
+        const double* Rwi = L.Rwi;
+        const double skw = cvc_pick3(r, cvc_pick3(c, 0.0, -w[2], w[1]), cvc_pick3(c, w[2], 0.0, -w[0]), cvc_pick3(c, -w[1], w[0], 0.0));
+        F[r * N + c] = -skw;
+        F[r * N + 3 + c] = r == c ? -1.0 : 0.0;
+        double s = __builtin_fma(Rwi[r], cvc_pick3(c, 0.0, -ac[2], ac[1]), 0.0);                // R^T skew(acc)
+        s = __builtin_fma(Rwi[3 + r], cvc_pick3(c, ac[2], 0.0, -ac[0]), s);
+        s = __builtin_fma(Rwi[6 + r], cvc_pick3(c, -ac[1], ac[0], 0.0), s);
+        F[(3 + r) * N + c] = -s;                                                                // rows 6 .. 8
+        F[(3 + r) * N + 9 + c] = -Rwi[c * 3 + r];
+        F[(6 + r) * N + 6 + c] = r == c ? 1.0 : 0.0;                                            // rows 12 .. 14
+    } else if (tid == 9) {
+        const double* Rnull = L.Rnull; double* u = L.u; double* sv = L.sv;
+        for (int r = 0; r < 3; ++r) u[r] = Rnull[r * 3] * a.gravity[0] + Rnull[r * 3 + 1] * a.gravity[1] + Rnull[r * 3 + 2] * a.gravity[2];
+        double uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
+        for (int r = 0; r < 3; ++r) sv[r] = u[r] / uu;
+    } else if (tid == 22) {
+        double* w1 = L.w1; double* w2 = L.w2;
+        double dv[3] = {a.v_null[0] - a.v_new[0], a.v_null[1] - a.v_new[1], a.v_null[2] - a.v_new[2]};
+        double dp[3] = {a.dt * a.v_null[0] + a.p_null[0] - a.p_new[0], a.dt * a.v_null[1] + a.p_null[1] - a.p_new[1], a.dt * a.v_null[2] + a.p_null[2] - a.p_new[2]};
+        const double* g = a.gravity;
+        w1[0] = -dv[2] * g[1] + dv[1] * g[2]; w1[1] = dv[2] * g[0] - dv[0] * g[2]; w1[2] = -dv[1] * g[0] + dv[0] * g[1];
+        w2[0] = -dp[2] * g[1] + dp[1] * g[2]; w2[1] = dp[2] * g[0] - dp[0] * g[2]; w2[2] = -dp[1] * g[0] + dp[0] * g[1];
+    }
+    __syncthreads();
+}
+
+// the two patches of the finished Phi (propagate_body's text on the stored rows) and the rows' patterns
+__device__ __forceinline__ void cvc_patch(CovChainsLds& L, int tid)
+{
+    const int N = IMU_DIM;
+    double* const Phi = L.m + CVC_PH;
+    if (tid < 9) {                                                              // Phi[:3,:3] = R_new R_null^T
+        const double* Rnew = L.Rnew; const double* Rnull = L.Rnull;
+        int r = tid / 3, c = tid % 3; double s = 0;
+        for (int k = 0; k < 3; ++k) s += Rnew[r * 3 + k] * Rnull[c * 3 + k];
+        Phi[r * N + c] = s;
+    } else if (tid >= 9 && tid < 9 + 6) {                                       // OC-KF corrections of rows 6..8 and 12..14
+        const double* u = L.u; const double* sv = L.sv;
+        const int t6 = tid - 9, blk = t6 / 3, r = t6 % 3;
+        const int row = (blk == 0 ? 3 : 6) + r;
+        const double* wv = blk == 0 ? L.w1 : L.w2;
+        const double p0 = Phi[row * N], p1 = Phi[row * N + 1], p2 = Phi[row * N + 2];
+        const double Au = p0 * u[0] + p1 * u[1] + p2 * u[2];
+        const double d = Au - wv[r];
+        Phi[row * N] = p0 - d * sv[0]; Phi[row * N + 1] = p1 - d * sv[1]; Phi[row * N + 2] = p2 - d * sv[2];
+    } else if (tid >= 22 && tid < 22 + 9) {
+        // (columns 0 .. 2, which the two patches rewrite at this moment, count as non-zero whatever they hold)
+        const int q = tid - 22; unsigned m = 0;
+        for (int k = 0; k < N; ++k) if (Phi[q * N + k] != 0.0) m |= 1u << k;
+        L.prow[q] = m | 7u;
+    }
+    __syncthreads();
+}
+
+// One IMU sample: P11 <- sym(Phi P11 Phi^T + Phi G Qc G^T Phi^T dt) in L's P11, PhiTn <- Phi PhiT.  Ends on a barrier.
+__device__ __forceinline__ void propagate_chains(const PropArgs& a, CovChainsLds& L, const double* PhiT, double* PhiTn)
+{
+#pragma clang fp contract(off)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));                                               // (a lane's entries and their addresses are made again per sample: kept across the samples they are ~50 registers)
+    const int N = IMU_DIM;
+    double* const F = L.m + CVC_FD, * const F2 = L.m + CVC_F2, * const Phi = L.m + CVC_PH, * const T = L.m + CVC_FD, * const PP = L.m + CVC_PP,
+          * const P11 = L.m + CVC_P11;
+    constexpr unsigned STORED = 0x71C7u;                                        // rows 0-2, 6-8, 12-14
+    const double dt = a.dt;
+    cvc_prepare(a, L, tid);
+    for (int i = tid; i < CVC_NR; i += 64) F[i] *= dt;                          // Fdt
+    __syncthreads();
+    if (tid >= 22 && tid < 22 + 9) {
+        const int q = tid - 22; unsigned m = 0;
+        for (int k = 0; k < N; ++k) if (F[q * N + k] != 0.0) m |= 1u << k;
+        L.frow[q] = m & STORED;
+    } else if (tid >= 43) {
+        const int c = tid - 43; unsigned m = 0;
+        for (int q = 0; q < 9; ++q) if (F[q * N + c] != 0.0) m |= 1u << cvc_full(q);
+        L.fcol[c] = m;
+    }
+    __syncthreads();
+    int eq[3], ec[3]; bool eok[3];                                              // a lane's three entries of a nine-row matrix: stored row, column
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { const int e = tid + 64 * j; eok[j] = e < CVC_NR; const int ee = eok[j] ? e : 0; eq[j] = ee / N; ec[j] = ee - eq[j] * N; }
+    {                                                                           // Fdt^2
+        unsigned m[3]; double s[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { m[j] = eok[j] ? L.frow[eq[j]] : 0u; s[j] = 0; }
+        for (unsigned U = cvc_union<9>(L.frow); U; U &= U - 1) {
+            const int k = __builtin_ctz(U), kq = cvc_stored(k);
+            double x[3], y[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { x[j] = F[eq[j] * N + k]; y[j] = F[kq * N + ec[j]]; }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if ((m[j] >> k) & 1u) s[j] = __builtin_fma(x[j], y[j], s[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) if (eok[j]) F2[tid + 64 * j] = s[j];
+    }
+    __syncthreads();
+    {                                                                           // Fdt^3, Phi
+        unsigned m[3]; double s[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { m[j] = eok[j] ? L.fcol[ec[j]] : 0u; s[j] = 0; }
+        for (unsigned U = cvc_union<IMU_DIM>(L.fcol); U; U &= U - 1) {          // (fcol holds stored rows only)
+            const int k = __builtin_ctz(U), kq = cvc_stored(k);
+            double x[3], y[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { x[j] = F2[eq[j] * N + k]; y[j] = F[kq * N + ec[j]]; }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if ((m[j] >> k) & 1u) s[j] = __builtin_fma(x[j], y[j], s[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) if (eok[j]) {
+            const int i = tid + 64 * j;
+            Phi[i] = __builtin_fma(F2[i], 0.5, (cvc_full(eq[j]) == ec[j] ? 1.0 : 0.0) + F[i]) + s[j] / 6.;
+        }
+    }
+    __syncthreads();
+    cvc_patch(L, tid);
+    // three products with the finished Phi, side by side: T = Phi G, PP = Phi P11, PhiTn = Phi PhiT.  The nine stored rows are chains
+    // over prow; a unit row r is the single term 0 + 1.0 * X[r][c].
+    {
+        int tq[2], tc[2]; bool tok[2]; unsigned m[3], mt[2]; double sp[3], sq[3], st[2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { m[j] = eok[j] ? L.prow[eq[j]] : 0u; sp[j] = 0; sq[j] = 0; }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int e = tid + 64 * j; tok[j] = e < 9 * 12; const int ee = tok[j] ? e : 0; tq[j] = ee / 12; tc[j] = ee - tq[j] * 12;
+            mt[j] = tok[j] ? L.prow[tq[j]] : 0u; st[j] = 0;
+        }
+        for (unsigned U = cvc_union<9>(L.prow); U; U &= U - 1) {
+            const int k = __builtin_ctz(U);
+            double x[3], p[3], f[3], xt[2], g[2];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { x[j] = Phi[eq[j] * N + k]; p[j] = P11[k * N + ec[j]]; f[j] = PhiT[k * N + ec[j]]; }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { xt[j] = Phi[tq[j] * N + k]; g[j] = cvc_G(L.Rwi, k, tc[j]); }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if ((m[j] >> k) & 1u) { sp[j] = __builtin_fma(x[j], p[j], sp[j]); sq[j] = __builtin_fma(x[j], f[j], sq[j]); }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) if ((mt[j] >> k) & 1u) st[j] = __builtin_fma(xt[j], g[j], st[j]);
+        }
+        // (T lies over Fdt / Fdt^2, which nothing has read since the barrier behind Phi)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) if (eok[j]) { const int i = cvc_full(eq[j]) * N + ec[j]; PP[i] = sp[j]; PhiTn[i] = sq[j]; }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) if (tok[j]) T[cvc_full(tq[j]) * 12 + tc[j]] = st[j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = tid + 64 * j;
+            if (e < 12 * N) {
+                const int u = e / N, c = e - u * N, i = cvc_unit_row(u) * N + c;
+                PP[i] = __builtin_fma(1.0, P11[i], 0.0); PhiTn[i] = __builtin_fma(1.0, PhiT[i], 0.0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {                                           // T's unit rows: 0 + 1.0 * G[r][c]
+            const int e = tid + 64 * j;
+            if (e < 12 * 12) { const int u = e / 12, c = e - u * 12, r = cvc_unit_row(u); T[r * 12 + c] = r == c ? 1.0 : 0.0; }
+        }
+    }
+    __syncthreads();
+    // P11 <- Phi P11 Phi^T + Q, unsymmetrised, into P11 itself.  First the entries whose column c is one of the nine stored rows of Phi
+    // (three per lane: chains over prow[c]), then those whose c is a unit row (four per lane: the single term PP[r][c] * 1.0).
+    {
+        int r[3], c[3], cq[3]; bool ok[3]; unsigned m[3]; double q[3], s[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int e = tid + 64 * j; ok[j] = e < CVC_NR; const int ee = ok[j] ? e : 0; r[j] = ee / 9; cq[j] = ee - r[j] * 9; c[j] = cvc_full(cq[j]);
+            m[j] = ok[j] ? L.prow[cq[j]] : 0u; s[j] = 0;
+        }
+        cvc_noise<3>(T, a.noise, r, c, q);
+        for (unsigned U = cvc_union<9>(L.prow); U; U &= U - 1) {
+            const int k = __builtin_ctz(U);
+            double x[3], y[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { x[j] = PP[r[j] * N + k]; y[j] = Phi[cq[j] * N + k]; }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if ((m[j] >> k) & 1u) s[j] = __builtin_fma(x[j], y[j], s[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) if (ok[j]) P11[r[j] * N + c[j]] = __builtin_fma(q[j], dt, s[j]);
+    }
+    {
+        int r[4], c[4]; bool ok[4]; double q[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int e = tid + 64 * j; ok[j] = e < 12 * N; const int ee = ok[j] ? e : 0; r[j] = ee / 12; c[j] = cvc_unit_row(ee - r[j] * 12); }
+        cvc_noise<4>(T, a.noise, r, c, q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (ok[j]) { const int i = r[j] * N + c[j]; P11[i] = __builtin_fma(q[j], dt, __builtin_fma(PP[i], 1.0, 0.0)); }
+    }
+    __syncthreads();
+    // (P + P^T) / 2 in place (msckf.py:334-335): the lane of (r, c), r <= c, writes both
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const int i = tid + 64 * j, r = i / N, c = i - r * N;
+        if (i < CVC_NN && r <= c) { const double v = (P11[r * N + c] + P11[c * N + r]) / 2.; P11[r * N + c] = v; P11[c * N + r] = v; }
+    }
+    __syncthreads();
+}
+
+// dk_cov's cross block P12 <- PhiT P12, mirrored into P21: a lane per column, its 21 old entries in registers, three rows in flight;
+// every new entry the dense 21-term sum from +0.0 (PhiT is read by every lane at the same address: a broadcast)
+__device__ __forceinline__ void cross_chains(cvc_gptr P, int n, int ld, const double* PhiT)
+{
+#pragma clang fp contract(off)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));                                               // (nothing of a lane's carried in from the phases before)
+    const int N = IMU_DIM, nc = n - N;
+    for (int c0 = 0; c0 < nc; c0 += 64) {
+        const int c = c0 + tid;
+        if (c < nc) {
+            double w[IMU_DIM];
+            const unsigned cb = 8u * (unsigned)c;
+            const cvc_gptr mir = P + (size_t)(N + c) * ld;                      // the mirrored entries: row N + c, a lane's own
+#pragma unroll
+            for (int k = 0; k < N; ++k) w[k] = *cvc_in_row(P + (size_t)k * ld + N, cb);
+#pragma unroll 1
+            for (int r = 0; r < N; r += 3) {
+                const double* ph = PhiT + r * N;
+                double s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    s0 = __builtin_fma(ph[k], w[k], s0); s1 = __builtin_fma(ph[N + k], w[k], s1); s2 = __builtin_fma(ph[2 * N + k], w[k], s2);
+                    if (k % 3 == 2) __builtin_amdgcn_sched_barrier(0);          // nine reads of PhiT in flight, not all 63: w is 42 of the 96 registers
+                }
+                *cvc_in_row(P + (size_t)r * ld + N, cb) = s0; *cvc_in_row(P + (size_t)(r + 1) * ld + N, cb) = s1; *cvc_in_row(P + (size_t)(r + 2) * ld + N, cb) = s2;
+                mir[r] = s0; mir[r + 1] = s1; mir[r + 2] = s2;
+            }
+        }
+    }
+}
+
+// augment_body's sums for one wavefront: a lane per column of the six new rows, the column's 21 entries of P loaded ahead of the three
+// chains of a pass that use them; the corner reads the new rows' first 21 columns out of LDS instead of back from global memory
+__device__ __forceinline__ void augment_chains(const AugArgs& a, double* J, double* JP, double* C)
+{
+#pragma clang fp contract(off)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int N = IMU_DIM, n = a.n, ld = a.ld;
+    const cvc_gptr P = (cvc_gptr)a.P;
+    for (int i = tid; i < 6 * N; i += 64) J[i] = 0.0;
+    __syncthreads();
+    if (tid < 9) {
+        int r = tid / 3, c = tid % 3;
+        J[r * N + c] = a.R_ic[tid];
+        J[r * N + 15 + c] = r == c ? 1.0 : 0.0;
+        J[(3 + r) * N + c] = a.sk[tid];
+        J[(3 + r) * N + 12 + c] = r == c ? 1.0 : 0.0;
+        J[(3 + r) * N + 18 + c] = r == c ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    // new rows J P[:21, :n], and their mirror, the new columns: three rows to a pass (the column's 21 entries are 42 of the 96 registers;
+    // the second pass reads them again, out of the cache, and nothing the first one wrote)
+#pragma unroll 1
+    for (int h = 0; h < 6; h += 3)
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int c = c0 + tid;
+        if (c < n) {
+            double p[IMU_DIM], s[3];
+            int o = h * N;
+            asm volatile("" : "+s"(o));                      // (J is read again in every round: held in registers across the rounds it is 252 of them)
+            const double* Jr = J + o;
+            const unsigned cb = 8u * (unsigned)c;
+            const cvc_gptr mir = P + (size_t)c * ld + n + h;                    // the new columns' entries: row c, a lane's own
+#pragma unroll
+            for (int k = 0; k < N; ++k) p[k] = *cvc_in_row(P + (size_t)k * ld, cb);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) s[r] = 0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+#pragma unroll
+                for (int r = 0; r < 3; ++r) s[r] = __builtin_fma(Jr[r * N + k], p[k], s[r]);
+                if (k % 3 == 2) __builtin_amdgcn_sched_barrier(0);              // nine reads of J in flight, not all 63
+            }
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                *cvc_in_row(P + (size_t)(n + h + r) * ld, cb) = s[r]; mir[r] = s[r];
+                if (c < N) JP[(h + r) * N + c] = s[r];
+            }
+        }
+    }
+    __syncthreads();
+    // corner: (J P11) J^T, symmetrised
+    if (tid < 36) {
+        int r = tid / 6, c = tid % 6; double s = 0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s = __builtin_fma(JP[r * N + k], J[c * N + k], s);
+        C[tid] = s;
+    }
+    __syncthreads();
+    if (tid < 36) {
+        int r = tid / 6, c = tid % 6;
+        P[(size_t)(n + r) * ld + n + c] = (C[r * 6 + c] + C[c * 6 + r]) / 2.;
+    }
+}
+
+// ================================================================================================
 // Delete the 6 rows/cols of one camera state (msckf.py:774-786)
 // ================================================================================================
 __device__ __forceinline__ void remove_cam_body(double* P, double* scratch, int n, int ld, int start)

@@ -325,8 +325,9 @@ __global__ __launch_bounds__(64) void dk_imu_rate(DevArgs a, IrOut R)
 // accumulated transition, and the new camera state's rows and columns (:411-423) -- ONE wavefront per stream.  The 21 x 21 products
 // are the block-sparse sums of propagate_body; its barriers are wavefront-local here.
 // ------------------------------------------------------------------------------------------------
-// NT = 64: one wavefront per stream (large batches: what counts beside the front-end is the footprint); NT = 256: four (small batches:
-// the GPU is not full and what counts is the time one stream takes)
+// NT = 64: one wavefront per stream (large batches: what counts beside the front-end is the footprint; that instance is the explicit
+// specialisation below, this text is its bit reference); NT = 256: four (small batches: the GPU is not full and what counts is the time
+// one stream takes)
 template <int NT>
 __global__ __launch_bounds__(NT) void dk_cov(DevArgs a)
 {
@@ -369,6 +370,43 @@ __global__ __launch_bounds__(NT) void dk_cov(DevArgs a)
     }
     stamp(2);
     augment_body<NT>(cv.aa);
+}
+// The one-wavefront instance has a body of its own (msckf.hip, "dk_cov<64>'s body"): the same sums bit for bit -- the instance above is
+// what it is tested against -- as independent chains, in 96 registers without scratch and 19,120 B of LDS, so that the four wavefronts
+// a 1,024-stream group puts on a CU leave LK all twenty of its own (4 x 19,120 + 20 x 3,840 B <= 160 KiB) and a wavefront fits the
+// hole ONE retiring LK wavefront leaves on a SIMD.  Per sample: preparation | Fdt, patterns | Fdt^2 | Fdt^3, Phi | patches, pattern |
+// Phi G, Phi P11, Phi PhiT | P11 | symmetrise; then the cross block out of registers and the augmentation, a lane per column.
+// Parent body at NT = 64: 157 registers, 184 B of scratch per lane, 28,680 B of LDS, 0.58 ms per 2,048 streams alone and 1.1 ms beside the
+// front-end; this one 0.23 and 0.36 ms (profiles/dk_cov_chains/README.md).
+// (__launch_bounds__(256, 5) on a kernel launched with 64 threads: with a bound of 64 the compiler works out from the LDS size that no more
+//  than two such workgroups share a SIMD, drops the request for five, and allocates 248 registers.)
+template <>
+__global__ __launch_bounds__(256, 5) void dk_cov<64>(DevArgs a)
+{
+    AV_FILTER_PRIO();
+    __shared__ CovChainsLds L;
+    const int s = blockIdx.x, tid = threadIdx.x, N = IMU_DIM;
+    const DCov& cv = a.cov[s];                              // (read in place: a private copy, indexed by lane in the augmentation, is 184 B of scratch)
+    if (!cv.act) return;                                    // (workgroup-uniform)
+    const cvc_gptr P = (cvc_gptr)cv.aa.P;
+    const int n = cv.aa.n, ld = cv.aa.ld, cnt = cv.cnt, first = cv.first;
+    auto stamp = [&](int i) { if (a.prof && s == 0 && tid == 0) a.prof[i] = __builtin_amdgcn_s_memrealtime(); };
+    stamp(0);
+    if (cnt > 0) {
+        double* PhiT = L.m + CVC_PHIA, * PhiTn = L.m + CVC_PHIB, * const P11s = L.m + CVC_P11;
+        for (int i = tid; i < N * N; i += 64) { const int r = i / N, c = i - r * N; P11s[i] = P[(size_t)r * ld + c]; PhiT[i] = r == c ? 1.0 : 0.0; }
+        __syncthreads();
+        for (int k = 0; k < cnt; ++k) {                     // (each ends on a barrier)
+            propagate_chains(a.prop[first + k], L, PhiT, PhiTn);
+            double* const t = PhiT; PhiT = PhiTn; PhiTn = t;
+        }
+        stamp(1);
+        cross_chains(P, n, ld, PhiT);
+        for (int i = tid; i < N * N; i += 64) { const int r = i / N, c = i - r * N; P[(size_t)r * ld + c] = P11s[i]; }
+        __syncthreads();
+    }
+    stamp(2);
+    augment_chains(cv.aa, L.m + CVC_PP, L.m + CVC_PP + 6 * N, L.m + CVC_PP + 12 * N);
 }
 
 // observation CSR + per-feature records of the candidates cand[0 .. nc) of stream s (dict order), launch buckets and the
