@@ -1271,6 +1271,33 @@ int  av_msckf_predict_ops_dev_rate(av_msckf* ctx, int n_streams, int wg, int cam
 int  av_msckf_forecast_ops_dev(av_msckf* ctx, int n_streams, int ld, int64_t p_stride, double* state_io, int32_t* state_int_io,
                                const double* imu, int n_imu, const int32_t* pend, const double noise4[4], double* P_dev, void* stream,
                                int cap, av_imu_state* rec_out, int32_t* n_out, double* cov_out);
+/* Parity-test entry (tests only; no step of the filter calls it): the batched measurement update (msckf.py:548-602 with the stacking
+ * loops of :658-668 and :759-763) for n_streams streams in ONE launch sequence, exactly the one a phase of a filter step runs from the
+ * stacking decisions to the covariance update, through the helper the step itself launches it with.  phase 0 = the lost-feature phase
+ * (the `> 1500 rows` cut, Cholesky back end for every stream, streams that stack more than kch rows compressed through their Gram
+ * matrix first; kch = 0 means the filter's own, min(136, ld)), phase 1 = the pruning phase (no cut, information form for the streams that touch at
+ * most 24 columns; hld > 0: the block rows are compact, hld doubles each, and no Cholesky back end is launched, as in a step).
+ * HOST arrays, per stream s: stream_n (state dimension), stream_mode (1 = information form allowed, 2 = stopped: no update), n_cand;
+ * per candidate slot i in [s * fs_stride, s * fs_stride + n_cand[s]): obs_off[i] .. obs_off[i + 1] (n_streams * fs_stride + 1 entries)
+ * index obs_cam[n_obs] (the camera slot of every observation), pass[i] the gate flag, row_off[i] the first of its 4 M - 3 rows in the
+ * stream's region of the DEVICE block buffers: H_dev + s * h_stride (rows of hld > 0 ? hld : ld doubles) and r_dev + s * r_stride,
+ * rows_cap rows each.  P_dev: the device covariances, updated in place at P_dev + s * p_stride with leading dimension ld.  The work
+ * buffers are sized as the batched filter sizes them and released before the call returns.  Results, HOST arrays: dx_io[n_streams][ld]
+ * (uploaded as the caller filled it: a pre-fill shows what was not written), stacked_out[n_streams] (rows stacked, 0 = no update, -1 =
+ * stopped or more than 4096 blocks, -2 = a factorisation met a pivot that is not positive and finite: the update was a no-op),
+ * cols_out[n_streams][6 * cam_stride] (the touched state columns, ascending, -1 behind them) and rec_out[n_streams][5] = m, nc, mode
+ * (1 = information form), kdir (> 0: rows kept without compression), n_blk as the stacking kernel wrote them.  Checked before anything
+ * is launched (AV_E_INVALID / AV_E_CAPACITY), so that no input can send a kernel out of bounds: the counts, n <= ld, n == 21 + 6 n_cam,
+ * camera slots inside the stream's window (cam_stride <= 64), at most fs_stride candidates, observations inside obs_cam, stacked rows
+ * inside the block buffer and m <= rows_cap, at most 256 touched columns, at most 144 and at most ld rows kept by one pass, hld either
+ * 0 or >= the columns of every stream (and every updating stream then in information form), the information form's LDS <= 160 KB.
+ * ctx lends its device.  Synchronises. */
+int  av_msckf_update_ops_dev(av_msckf* ctx, int n_streams, int phase, int kch, int fs_stride, int cam_stride, int hld,
+                             const int32_t* stream_n, const int32_t* stream_mode, const int32_t* n_cand,
+                             const int32_t* obs_off, const int32_t* obs_cam, int n_obs, const int32_t* pass, const int32_t* row_off,
+                             const double* H_dev, int64_t h_stride, const double* r_dev, int64_t r_stride, int rows_cap,
+                             double* P_dev, int ld, int64_t p_stride, double obs_noise,
+                             double* dx_io, int32_t* stacked_out, int32_t* cols_out, int32_t* rec_out, void* stream);
 /* Work done so far, for the filter stage's roofline (drain first): out8 = [algorithmic fp64 flops of the gating tests
  * (per feature with r = 4M-3 rows, n columns: 2rn^2 + 2r^2n + r^3/3; msckf.py:604-612), of the measurement updates on the
  * k = min(m, n) rows kept (S 2kn^2 + 2k^2n, Cholesky k^3/3, solve 2k^2n, (I-KH)P 4kn^2; msckf.py:562-602), of the reference's

@@ -19,6 +19,9 @@ sample, in the reference's order, with the symmetrisation of the whole matrix an
 the removal loop of prune_cam_state_buffer and find_redundant_cam_states.  The IMU state is a dict of mpf arrays (IMU_FIELDS), the
 covariance an object array.  Every decision reports its relative margin in 50 digits: the `> 1e-5` rate branch, and the 0.2618 rad,
 0.4 m and 0.5 tracking-rate tests of the redundancy rule.
+
+The last part is the measurement update (measurement_update, msckf.py:548-602) written directly, the same by the push-through identity
+for stacks too long for an m x m solve, and the update of the regularised problem the row compression solves.
 """
 import numpy as np
 from mpmath import mp, mpf
@@ -504,3 +507,44 @@ def find_redundant_cam_states(cam_q, cam_p, tracking_rate):
             first += 1
         idx += 1
     return sorted(out), info
+
+
+# ---- the measurement update (oracle/msckf_np.py: measurement_update; msckf.py:548-602) -------------------------------------
+# The stacked Jacobian is zero outside the touched columns `cols`, so every function takes Hc = H[:, cols] (m x nc) and forms the
+# products with P through P[cols, :]: the same numbers as with the full-width H, without the multiplications by exact zeros.  No
+# QR (a thin QR changes nothing mathematically) and no state injection: delta_x and P+ are the results.
+def _sym(P):
+    return (P + P.T) / mpf(2)
+
+
+def measurement_update(Hc, r, P, cols, obs_noise):
+    """S = H P H^T + s^2 I, K^T = S^-1 H P, delta_x = K r, P+ = sym((I - K H) P), written directly.  -> (delta_x [n], P+ [n, n])."""
+    Hc, r, P, cols = M(Hc), M(r), M(P), list(cols)
+    m, n = len(Hc), len(P)
+    HP = Hc.dot(P[cols, :])                                  # H P, m x n
+    S = HP[:, cols].dot(Hc.T) + eye(m) * mpf(float(obs_noise))
+    Kt = solve(S, HP)                                        # K^T = S^-1 H P, m x n
+    dx = Kt.T.dot(r)
+    return dx, _sym(P - Kt.T.dot(HP))
+
+
+def measurement_update_info(Hc, r, P, cols, obs_noise, reg=None):
+    """The same two results by the push-through identity Hc^T (Hc Pcc Hc^T + s^2 I)^-1 = (A Pcc + s^2 I)^-1 Hc^T with A = Hc^T Hc,
+    b = Hc^T r:  delta_x = P[:, c] (A Pcc + s^2 I)^-1 b,  P+ = sym(P - P[:, c] (A Pcc + s^2 I)^-1 A P[c, :]).  For stacks too long for an
+    m x m solve in 50 digits.  reg: a multiple of max_i A_ii added to every diagonal entry of A (measurement_update_regularised)."""
+    Hc, r, P, cols = M(Hc), M(r), M(P), list(cols)
+    nc = len(cols)
+    A, b = Hc.T.dot(Hc), Hc.T.dot(r)
+    if reg is not None:
+        A = A + eye(nc) * (mpf(float(reg)) * max(A[i, i] for i in range(nc)))
+    Pc = P[cols, :]
+    Mx = A.dot(Pc[:, cols]) + eye(nc) * mpf(float(obs_noise))
+    X = solve(Mx, np.concatenate([A.dot(Pc), b.reshape(-1, 1)], axis=1))
+    return Pc.T.dot(X[:, -1]), _sym(P - Pc.T.dot(X[:, :-1]))
+
+
+def measurement_update_regularised(Hc, r, P, cols, obs_noise):
+    """The update of the REGULARISED problem the row compression solves (msckf_mfma.inc, above chol_mfma_body): A + E in place of
+    A = Hc^T Hc with E = 1e-12 max_i A_ii on every diagonal entry (any F with F^T F = A + E, F^T f = b stands in for (Hc, r)).  Against
+    measurement_update it shows the shift E itself causes, apart from any rounding."""
+    return measurement_update_info(Hc, r, P, cols, obs_noise, reg=1e-12)

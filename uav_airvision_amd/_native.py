@@ -314,6 +314,8 @@ SIGNATURES = {
     'av_msckf_predict_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6),
     'av_msckf_predict_ops_dev_rate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)] + [_P] * 6 +
                                       [C.c_int, _P, _P]),
+    'av_msckf_update_ops_dev': (C.c_int, [_P] + [C.c_int] * 6 + [_P] * 5 + [C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int64, C.c_double,
+                                          _P, _P, _P, _P, _P]),
     'av_msckf_forecast_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, _P, _P, _P, C.c_int, _P, C.POINTER(C.c_double), _P, _P, C.c_int, _P, _P, _P]),
     'av_msckf_batch_work': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double * 8)]),
     'av_msckf_batch_work_executed': (C.c_int, [_P, C.POINTER(C.c_double * 2)]),

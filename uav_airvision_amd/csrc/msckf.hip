@@ -2619,7 +2619,7 @@ __global__ __launch_bounds__(64) void upd_stack_kernel(StackArgs a)
         u.mode = mode; u.round = r; u.kdir = 0; u.nc = nc; u.hld = a.hld; u.cols = a.cols + (size_t)s * a.cols_stride; u.status = a.stacked + s;
         u.blk_row = a.blk_row + i0; u.blk_len = a.blk_len + i0; u.n_blk = nb; u.m = (too_many || overflow) ? 0 : m;
         if (r > 0) u.m = 0;                              // one round (Cholesky back end) or one launch (information form): round 0 only
-        else if (u.m > 0 && mode == 0) u.kdir = m <= a.kch ? m : 0;      // 0: k = upd_k(m, nc) = nc rows after the compression (m > kch >= nc compresses)
+        else if (u.m > 0 && mode == 0) u.kdir = m <= a.kch ? m : 0;      // 0: k = upd_k(m, nc): nc rows after the compression where upd_compress(m, nc) holds (always for m > 136), else all m rows
         a.out[(size_t)r * a.S + s] = u;
     }
 }

@@ -172,16 +172,30 @@ inline FeatArgs b_feat_args(const av_msckf_batch* b, bool cut1500, const double*
     return a;
 }
 
+// The work buffers of the batched update and how they are sized: per stream one p_stride (>= ld * ld doubles) each of T, Kt, Pn and
+// Sbuf, upd_w_doubles of W (the transposed copy of [H | r]: ld + 1 columns of ldt = rows_cap entries) and ld doubles of dx.  One place
+// for the batch (sub_create, sub_reserve, b_upd_args) and for the parity-test entry av_msckf_update_ops_dev.
+inline size_t upd_w_doubles(int rows_cap, int ld) { return (size_t)rows_cap * (ld + 1); }
+struct UpdBufs {
+    double *P, *Pn, *T, *Kt, *Sbuf, *W, *dx; const double *Hblk, *rblk;
+    size_t pstride, hstride, rstride, wstride; int ld, rows_cap; double obs_noise;
+};
 // A zeroed UpdArgs with the work buffers of stream s and their strides.  The caller adds n, m, nc, mode, its block lists and prof.
-inline UpdArgs b_upd_args(const av_msckf_batch* b, int s)
+inline UpdArgs upd_args_of(const UpdBufs& B, int s)
 {
     UpdArgs u; memset(&u, 0, sizeof(u));
-    u.P = b->P + (size_t)s * b->pstride; u.ld = b->ld;
-    u.Hsrc = b->Hblk + (size_t)s * b->hstride; u.rsrc = b->rblk + (size_t)s * b->rstride;
-    u.W = b->W + (size_t)s * b->wstride; u.ldt = b->rows_cap; u.T = b->T + (size_t)s * b->pstride; u.Kt = b->Kt + (size_t)s * b->pstride;
-    u.Pn = b->Pn + (size_t)s * b->pstride; u.dx = b->dx + (size_t)s * b->ld; u.obs_noise = b->obs_noise;
-    u.Sbuf = b->scratch + (size_t)s * b->pstride;          // free between the camera removals that use it
+    u.P = B.P + (size_t)s * B.pstride; u.ld = B.ld;
+    u.Hsrc = B.Hblk + (size_t)s * B.hstride; u.rsrc = B.rblk + (size_t)s * B.rstride;
+    u.W = B.W + (size_t)s * B.wstride; u.ldt = B.rows_cap; u.T = B.T + (size_t)s * B.pstride; u.Kt = B.Kt + (size_t)s * B.pstride;
+    u.Pn = B.Pn + (size_t)s * B.pstride; u.dx = B.dx + (size_t)s * B.ld; u.obs_noise = B.obs_noise;
+    u.Sbuf = B.Sbuf + (size_t)s * B.pstride;
     return u;
+}
+inline UpdArgs b_upd_args(const av_msckf_batch* b, int s)
+{
+    // (Sbuf: the removal scratch, free between the camera removals that use it)
+    const UpdBufs B{b->P, b->Pn, b->T, b->Kt, b->scratch, b->W, b->dx, b->Hblk, b->rblk, b->pstride, b->hstride, b->rstride, b->wstride, b->ld, b->rows_cap, b->obs_noise};
+    return upd_args_of(B, s);
 }
 
 // wait for the group's stream: spinning (hipStreamSynchronize) or sleeping on a blocking event (AV_MSCKF_WAIT=block)
@@ -294,7 +308,7 @@ static int sub_create(int n_streams, int max_cam_states, int rows_cap, const dou
     for (int i = 0; i < 4; ++i) b->noise[i] = noise4[i];
     b->obs_noise = obs_noise; b->pos_std_thr = position_std_threshold;
     const size_t S = n_streams;
-    b->pstride = (size_t)b->ld * b->ld; b->hstride = (size_t)rows_cap * b->ld; b->rstride = rows_cap; b->wstride = (size_t)rows_cap * (b->ld + 1);
+    b->pstride = (size_t)b->ld * b->ld; b->hstride = (size_t)rows_cap * b->ld; b->rstride = rows_cap; b->wstride = upd_w_doubles(rows_cap, b->ld);
     int rc;
 #define A(p, cnt) if ((rc = b->res.dev(&(p), (size_t)(cnt)))) return rc;
     A(b->P, S * b->pstride) A(b->Pn, S * b->pstride) A(b->T, S * b->pstride) A(b->Kt, S * b->pstride) A(b->scratch, S * b->pstride)
@@ -366,7 +380,7 @@ static int sub_reserve(av_msckf_batch* b, int cap)
             b->rows_cap = want > geo ? want : geo;
         }
         const size_t Sn = (size_t)b->S;
-        b->hstride = (size_t)b->rows_cap * b->ld; b->rstride = b->rows_cap; b->wstride = (size_t)b->rows_cap * (b->ld + 1);
+        b->hstride = (size_t)b->rows_cap * b->ld; b->rstride = b->rows_cap; b->wstride = upd_w_doubles(b->rows_cap, b->ld);
         int rc0;
         const size_t pool = b_pool_rows(b, b->rows_cap);
         if ((rc0 = b->res.dev(&b->W, Sn * b->wstride)) || (rc0 = b->res.dev(&b->Hblk, Sn * b->hstride + pool * b->ld)) || (rc0 = b->res.dev(&b->rblk, Sn * b->rstride + pool))) return rc0;
@@ -1116,6 +1130,129 @@ AV_EXPORT int av_msckf_predict_ops_dev_rate(av_msckf* c, int n_streams, int wg, 
     if (cap < 1) { av_set_error("av_msckf_predict_ops_dev_rate: cap must be 1 .. %d", IMU_RATE_CAP_MAX); return AV_E_INVALID; }
     return predict_ops_dev_body(c, n_streams, wg, cam_stride, ld, p_stride, state_io, state_int_io, t_frame, ctl, imu, n_imu, noise4,
                                 cam_q_dev, cam_p_dev, cam_qn_dev, P_dev, redundant_out, stream, cap, rec_out, n_out);
+}
+
+// Parity-test entry for the batched measurement update (tests only; no step of the filter calls it): for n_streams streams, what a phase
+// of a step launches from the stacking decisions to the covariance update -- dev_launch_update, the helper dev_phase itself calls -- on
+// the caller's candidate features, block buffers and covariances.  phase 0: the lost-feature phase's configuration (the `> 1500 rows`
+// cut, no information form, dense rows, streams with more than kch rows compressed; kch = 0: the step's own, min(136, ld)); phase 1: the pruning phase's (no cut, information
+// form for the streams that qualify; hld > 0: compact rows and NO Cholesky back end, as a step launches it).  Candidates of stream s are
+// the slots [s * fs_stride, s * fs_stride + n_cand[s]) of obs_off [n_streams * fs_stride + 1] / pass / row_off (HOST arrays; obs_cam
+// [n_obs] holds the camera slot of every observation); their rows lie in the stream's region of the DEVICE block buffers (H_dev +
+// s * h_stride, rows of hld > 0 ? hld : ld doubles; r_dev + s * r_stride; rows_cap rows each).  The work buffers are the batch's
+// (upd_args_of: ldt = rows_cap, one p_stride each), taken here and released before the entry returns.  Returns per stream delta_x
+// (dx_io [ld], uploaded as the caller filled it), stacked, the touched columns (cols_out [6 cam_stride], -1 behind them) and the record
+// upd_stack_kernel wrote (rec_out [5]: m, nc, mode, kdir, n_blk).  Every argument is checked before anything is launched -- the
+// stacking rule is repeated on the host for it --, so that no input can send a kernel out of bounds.  Synchronises.
+AV_EXPORT int av_msckf_update_ops_dev(av_msckf* c, int n_streams, int phase, int kch, int fs_stride, int cam_stride, int hld,
+                                      const int32_t* stream_n, const int32_t* stream_mode, const int32_t* n_cand,
+                                      const int32_t* obs_off, const int32_t* obs_cam, int n_obs, const int32_t* pass, const int32_t* row_off,
+                                      const double* H_dev, int64_t h_stride, const double* r_dev, int64_t r_stride, int rows_cap,
+                                      double* P_dev, int ld, int64_t p_stride, double obs_noise,
+                                      double* dx_io, int32_t* stacked_out, int32_t* cols_out, int32_t* rec_out, void* stream)
+{
+    constexpr int KMAX = 144;                    // rows one back-end pass keeps at most (BATCH_KMAX; upd_gather_kernel's row map holds 256)
+    if (!c || n_streams < 1 || n_streams > 4096 || (phase != 0 && phase != 1) || kch < 0 || kch > DEV_KCH || fs_stride < 1 || fs_stride > (1 << 20) ||
+        cam_stride < 1 || cam_stride > 64 || hld < 0 || n_obs < 0 || rows_cap < 1 || rows_cap > (1 << 20) || ld < IMU_DIM || ld > IMU_DIM + 6 * 64 ||
+        p_stride < (int64_t)ld * ld || !stream_n || !stream_mode || !n_cand || !obs_off || (n_obs > 0 && !obs_cam) || !pass || !row_off ||
+        !H_dev || !r_dev || !P_dev || !dx_io || !stacked_out || !cols_out || !rec_out || !(obs_noise > 0.0)) {
+        av_set_error("av_msckf_update_ops_dev: bad arguments");
+        return AV_E_INVALID;
+    }
+    if (phase == 0 && hld != 0) { av_set_error("av_msckf_update_ops_dev: compact rows (hld = %d) are the pruning phase's: phase 0 reads full-width rows", hld); return AV_E_INVALID; }
+    const int S = n_streams, kc = kch ? kch : dev_kch(ld), width = hld > 0 ? hld : ld;
+    const bool rounds = hld == 0, info = phase == 1;
+    if (h_stride < (int64_t)rows_cap * width || r_stride < rows_cap) { av_set_error("av_msckf_update_ops_dev: the block-buffer strides do not hold rows_cap = %d rows", rows_cap); return AV_E_INVALID; }
+    const int kmax = kc > 6 * cam_stride ? kc : 6 * cam_stride;
+    size_t lds_i = 0;
+    // the stacking rule (upd_stack_kernel) on the host: every index and size a kernel will use is known, and checked, before the launch
+    for (int s = 0; s < S; ++s) {
+        const int n = stream_n[s], nk = n_cand[s];
+        if (n > ld) { av_set_error("av_msckf_update_ops_dev: stream %d: n = %d exceeds ld = %d", s, n, ld); return AV_E_CAPACITY; }
+        if (n < IMU_DIM || (n - IMU_DIM) % 6 || (stream_mode[s] != 1 && stream_mode[s] != 2)) { av_set_error("av_msckf_update_ops_dev: stream %d: n = %d is not 21 + 6 ncam, or mode %d is not 1 or 2", s, n, stream_mode[s]); return AV_E_INVALID; }
+        const int ncam = (n - IMU_DIM) / 6;
+        if (ncam > cam_stride) { av_set_error("av_msckf_update_ops_dev: stream %d holds %d camera states, cam_stride is %d", s, ncam, cam_stride); return AV_E_CAPACITY; }
+        if (nk < 0) { av_set_error("av_msckf_update_ops_dev: stream %d: negative candidate count", s); return AV_E_INVALID; }
+        if (nk > fs_stride) { av_set_error("av_msckf_update_ops_dev: stream %d: %d candidates, fs_stride is %d", s, nk, fs_stride); return AV_E_CAPACITY; }
+        long long m = 0; int nb = 0; unsigned long long used = 0ull;
+        for (int k = 0; k < nk; ++k) {
+            const size_t i = (size_t)s * fs_stride + k;
+            const int o0 = obs_off[i], o1 = obs_off[i + 1];
+            if (o0 < 0 || o1 < o0 || o1 > n_obs || o1 - o0 > 64) { av_set_error("av_msckf_update_ops_dev: stream %d, candidate %d: observations outside their array", s, k); return AV_E_INVALID; }
+            for (int q = o0; q < o1; ++q) if (obs_cam[q] < 0 || obs_cam[q] >= ncam) { av_set_error("av_msckf_update_ops_dev: stream %d, candidate %d: camera slot %d outside the window of %d (cam_stride %d)", s, k, obs_cam[q], ncam, cam_stride); return AV_E_INVALID; }
+            const int rows = 4 * (o1 - o0) - 3;
+            if (pass[i] && rows < 1) { av_set_error("av_msckf_update_ops_dev: stream %d, candidate %d passes the gate without an observation", s, k); return AV_E_INVALID; }
+            if (!pass[i] || (phase == 0 && m > 1500)) continue;      // (behind the cut nothing is stacked; the kernel still reads the flags)
+            if (row_off[i] < 0 || (long long)row_off[i] + rows > rows_cap) { av_set_error("av_msckf_update_ops_dev: stream %d, candidate %d: rows %d .. %d outside the block buffer of %d rows", s, k, row_off[i], row_off[i] + rows, rows_cap); return AV_E_CAPACITY; }
+            m += rows; ++nb;
+            for (int q = o0; q < o1; ++q) used |= 1ull << obs_cam[q];
+        }
+        if (nb > STACK_LDS_BLOCKS || stream_mode[s] == 2 || m == 0) continue;      // the kernel's own refusals: nothing of the stream is touched
+        const int nc = 6 * __builtin_popcountll(used);
+        if (nc > MFMA_MAXCOLS) { av_set_error("av_msckf_update_ops_dev: stream %d touches %d columns, the back end holds %d", s, nc, MFMA_MAXCOLS); return AV_E_CAPACITY; }
+        if (m > rows_cap) { av_set_error("av_msckf_update_ops_dev: stream %d stacks %lld rows, ldt = rows_cap is %d", s, m, rows_cap); return AV_E_CAPACITY; }
+        const bool inf = info && nc <= INFO_NC && m <= INFO_MAXROWS;
+        if (hld > 0 && (!inf || hld < nc)) { av_set_error("av_msckf_update_ops_dev: stream %d: compact rows of %d doubles, but the stream touches %d columns or does not take the information form", s, hld, nc); return AV_E_INVALID; }
+        if (inf) { const size_t l = upd_info_lds(nc, n, (int)m); lds_i = l > lds_i ? l : lds_i; continue; }
+        const bool comp = m > kc && upd_compress((int)m, nc);
+        const long long k = m <= kc ? m : upd_k((int)m, nc);
+        if (k > KMAX || k > ld || k > kmax || (size_t)((k + 15) / 16) * 256 > (size_t)p_stride) { av_set_error("av_msckf_update_ops_dev: stream %d keeps %lld rows in one pass (at most %d, ld = %d)", s, k, KMAX, ld); return AV_E_CAPACITY; }
+        if (comp && (m > 2 * (long long)p_stride || nc + 1 > ld)) { av_set_error("av_msckf_update_ops_dev: stream %d: the row map of %lld rows does not fit its work buffer", s, m); return AV_E_CAPACITY; }
+    }
+    if (lds_i > 160 * 1024) { av_set_error("av_msckf_update_ops_dev: the information form needs %zu B of LDS, 163840 available", lds_i); return AV_E_CAPACITY; }
+    hipStream_t stm = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(c->device));
+    // one device allocation for everything the kernels need besides the caller's arrays, released on every way out
+    struct Arena { AvScratch mem; char* p = nullptr; size_t used = 0;
+                   size_t take(size_t bytes) { const size_t o = used; used += (bytes + 255) / 256 * 256; return o; } } ar;
+    const size_t nf = (size_t)S * fs_stride + 1, ps = (size_t)p_stride, ws = upd_w_doubles(rows_cap, ld), ncols = (size_t)S * 6 * cam_stride;
+    const size_t o_W = ar.take(sizeof(double) * S * ws), o_T = ar.take(sizeof(double) * S * ps), o_Kt = ar.take(sizeof(double) * S * ps),
+                 o_Pn = ar.take(sizeof(double) * S * ps), o_Sb = ar.take(sizeof(double) * S * ps), o_dx = ar.take(sizeof(double) * S * ld),
+                 o_base = ar.take(sizeof(UpdArgs) * S), o_upd = ar.take(sizeof(UpdArgs) * S), o_br = ar.take(sizeof(int) * nf), o_bl = ar.take(sizeof(int) * nf),
+                 o_cols = ar.take(sizeof(int) * ncols), o_clist = ar.take(sizeof(int) * ((size_t)S + 8)), o_cnt = ar.take(sizeof(int) * 16),
+                 o_stk = ar.take(sizeof(int) * S), o_n = ar.take(sizeof(int) * S), o_nc = ar.take(sizeof(int) * S), o_off = ar.take(sizeof(int) * nf),
+                 o_cam = ar.take(sizeof(int) * (size_t)(n_obs > 0 ? n_obs : 1)), o_pass = ar.take(sizeof(int) * nf), o_ro = ar.take(sizeof(int) * nf);
+    { const int rca = ar.mem.alloc(ar.used); if (rca) return rca; }
+    ar.p = static_cast<char*>(ar.mem.p);
+    AV_HIP(hipMemsetAsync(ar.p, 0, ar.used, stm));
+    AV_HIP(hipMemsetAsync(ar.p + o_cols, 0xFF, sizeof(int) * ncols, stm));          // -1 behind a stream's touched columns
+    const UpdBufs B{P_dev, (double*)(ar.p + o_Pn), (double*)(ar.p + o_T), (double*)(ar.p + o_Kt), (double*)(ar.p + o_Sb), (double*)(ar.p + o_W), (double*)(ar.p + o_dx),
+                    H_dev, r_dev, ps, (size_t)h_stride, (size_t)r_stride, ws, ld, rows_cap, obs_noise};
+    std::vector<UpdArgs> base((size_t)S);
+    for (int s = 0; s < S; ++s) { UpdArgs& u = base[s] = upd_args_of(B, s); u.n = stream_n[s]; u.mode = stream_mode[s]; }
+    AV_HIP(hipMemcpyAsync(ar.p + o_base, base.data(), sizeof(UpdArgs) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_dx, dx_io, sizeof(double) * S * ld, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_n, stream_n, sizeof(int) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_nc, n_cand, sizeof(int) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_off, obs_off, sizeof(int) * nf, hipMemcpyHostToDevice, stm));
+    if (n_obs > 0) AV_HIP(hipMemcpyAsync(ar.p + o_cam, obs_cam, sizeof(int) * n_obs, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_pass, pass, sizeof(int) * (nf - 1), hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(ar.p + o_ro, row_off, sizeof(int) * (nf - 1), hipMemcpyHostToDevice, stm));
+    int* cnt = (int*)(ar.p + o_cnt);
+    StackArgs sa; memset(&sa, 0, sizeof(sa));
+    sa.n_cand = (const int*)(ar.p + o_nc); sa.fs_stride = fs_stride; sa.stream_n = (const int*)(ar.p + o_n);
+    sa.pass = (const int*)(ar.p + o_pass); sa.obs_off = (const int*)(ar.p + o_off); sa.obs_cam = (const int*)(ar.p + o_cam); sa.row_off = (const int*)(ar.p + o_ro);
+    sa.blk_row = (int*)(ar.p + o_br); sa.blk_len = (int*)(ar.p + o_bl); sa.cols = (int*)(ar.p + o_cols); sa.cols_stride = 6 * cam_stride;
+    sa.base = (const UpdArgs*)(ar.p + o_base); sa.out = (UpdArgs*)(ar.p + o_upd); sa.S = S; sa.rounds = 1; sa.cut1500 = phase == 0 ? 1 : 0; sa.kch = kc;
+    sa.stacked = (int*)(ar.p + o_stk); sa.clist = (int*)(ar.p + o_clist); sa.clist_count = cnt + 6;
+    sa.hld = hld; sa.no_info = phase == 0 ? 1 : 0;
+    UpdLaunch ul;
+    ul.info = info; ul.lds_info = lds_i ? lds_i : upd_info_lds(12, IMU_DIM, 1);
+    ul.rounds = rounds; ul.n_list = (unsigned)S; ul.k1max = 6 * cam_stride + 1; ul.kmax = kmax; ul.nmax = ld;
+    { const int rcl = dev_launch_update(sa, ul, stm); if (rcl) return rcl; }
+    std::vector<UpdArgs> upd((size_t)S);
+    std::vector<int> cols(ncols);
+    AV_HIP(hipMemcpyAsync(upd.data(), ar.p + o_upd, sizeof(UpdArgs) * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(dx_io, ar.p + o_dx, sizeof(double) * S * ld, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(stacked_out, ar.p + o_stk, sizeof(int) * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(cols_out, ar.p + o_cols, sizeof(int) * ncols, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipStreamSynchronize(stm));
+    for (int s = 0; s < S; ++s) {
+        const UpdArgs& u = upd[s];
+        int32_t* r = rec_out + (size_t)5 * s;
+        r[0] = u.m; r[1] = u.nc; r[2] = u.mode; r[3] = u.kdir; r[4] = u.n_blk;
+    }
+    return AV_OK;
 }
 
 // Parity-test entry for the forecast (airvision.h, "Forecast"; tests only; no step of the filter calls it): for n_streams streams

@@ -6,6 +6,10 @@
 namespace {
 
 constexpr int DEV_KCH = 136;       // stacked rows one back-end pass takes directly (74.6 KB of LDS for the factor: two workgroups per CU)
+// ... and never more than ld: a pass of k rows keeps S, T^T and Y in [k][ld] buffers of ld * ld doubles, so with a window below 17 camera
+// states (ld < 136) a stream that stacks more than ld rows is compressed to its nc < ld columns' worth first.  (Not closed by this: such a
+// window's stream with ld < m <= 136 rows over nc columns, 2 m <= 3 nc, which upd_compress leaves uncompressed.)
+inline int dev_kch(int ld) { return DEV_KCH < ld ? DEV_KCH : ld; }
 
 // copy of the store of every stream into arrays built for a larger message capacity (a wider feature message arrived)
 __global__ __launch_bounds__(256) void dk_migrate(DevArgs o, DevArgs n)
@@ -203,6 +207,46 @@ int dev_grid_hint(const DevPath* d, int idx, int worst, int floor_teams = 256)
     return g < 1 ? 1 : (int)g;
 }
 
+// The update's launches of a phase, in a phase's order: upd_stack_kernel (the stacking decisions), [upd_info_kernel: the information
+// form, in the pruning phase], then -- where the phase can need the Cholesky back end -- upd_rowmap_kernel and the compression of the
+// long streams, upd_gather_kernel and the five back-end kernels.  One place for the step (dev_phase) and for the parity-test entry
+// av_msckf_update_ops_dev, so that the entry launches what the step launches.
+struct UpdLaunch {
+    bool info = false; size_t lds_info = 0;      // launch upd_info_kernel with this much dynamic LDS
+    bool rounds = false;                         // launch the compression and the Cholesky back end
+    unsigned n_list = 1;                         // workgroups that stride over the device-written list of long streams
+    int k1max = 1, kmax = 1, nmax = 1;           // what the grids have to cover: bordered Gram size, rows a pass keeps, state dimension
+};
+int dev_launch_update(const StackArgs& sa, const UpdLaunch& ul, hipStream_t stm)
+{
+    int rc;
+    const int S = sa.S;
+    hipLaunchKernelGGL(upd_stack_kernel, dim3(S), dim3(64), 0, stm, sa);
+    AV_LAUNCH_CHECK();
+    // (no second feature pass: a stream whose candidates outgrow its region of the block buffers takes rows from the shared pool,
+    //  dev_build_candidates -- the pass had to be launched every step and waited ~1.1 ms for a CU beside the front-end to do nothing)
+    if ((rc = msckf_lds_opt_in())) return rc;
+    if (ul.info) {
+        if (ul.lds_info > 160 * 1024) { av_set_error("batched MSCKF: information-form update needs %zu B of LDS", ul.lds_info); return AV_E_CAPACITY; }
+        hipLaunchKernelGGL(upd_info_kernel, dim3(S), dim3(256), ul.lds_info, stm, sa.out);
+        unsigned long long t[32];
+        if (dev_uprof().read(stm, t)) {                     // diagnostic (AV_DEV_UPROF=1): phase stamps of stream 0's workgroups
+            print_stamps("dk_begin stream 0", t + 16, {"imu steps", "cross block", "augment+gap", "add frame", "select lost", "candidates", "triangulate", "erase"});
+            print_stamps("upd_info stream 0", t, {"row map", "gram", "Pc", "F,G", "gauss-jordan", "scale", "P update"});
+        }
+    }
+    if (ul.rounds) {
+        hipLaunchKernelGGL(upd_rowmap_kernel, dim3(ul.n_list), dim3(64), 0, stm, sa.out, sa.clist, (const int*)sa.clist_count);
+        launch_upd_compress(sa.out, sa.clist, (const int*)sa.clist_count, ul.n_list, ul.k1max, stm);
+        hipLaunchKernelGGL(upd_gather_kernel, dim3(S), dim3(256), 0, stm, sa.out);
+        // (the factor kernel: one launch for every pass length.  Two launches -- passes of up to 96 rows with 37 KB of LDS, four
+        //  workgroups per CU, then the longer ones -- took 180 + 601 us against 659: most passes of a steady stream keep more than 96 rows)
+        launch_upd_back(sa.out, S, ul.kmax, ul.nmax, stm);
+    }
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
 // One update phase on the device: triangulate -> Jacobian / null space / gate (length buckets) -> stacking decisions -> [second
 // pass of the streams gated without storage] -> compression of the long streams -> back end / information form.
 // ph = 0: remove_lost_features (msckf.py:614-676), 1: prune_cam_state_buffer (:712-786).
@@ -266,46 +310,30 @@ int dev_phase(av_msckf_batch* b, int ph, hipStream_t stm, DevSlot& slot, int* cn
         unsigned long long t[32];
         if (dev_fprof_team().read(stm, t)) print_stamps("feature<16> team 0", t, {"jacobian", "G", "reflectors", "rows out", "gate"});
     }
-    // ---- stacking decisions
+    // ---- stacking decisions, then the update itself (dev_launch_update)
     StackArgs sa; memset(&sa, 0, sizeof(sa));
     sa.rbeg = nullptr; sa.n_cand = A.n_cand; sa.fs_stride = A.FS; sa.stream_n = A.nstate; sa.valid = A.f_valid;
     sa.pass = d->pass; sa.obs_off = A.f_off; sa.obs_cam = A.obs_cam; sa.row_off = A.f_rowoff;
     sa.blk_row = d->blk_row; sa.blk_len = d->blk_len; sa.cols = d->cols; sa.cols_stride = 6 * b->cam_slots;
-    sa.base = d->updbase; sa.out = d->upd; sa.S = S; sa.rounds = 1; sa.cut1500 = cut1500 ? 1 : 0; sa.kch = DEV_KCH; sa.stacked = ph == 0 ? d->stacked0 : d->stacked1;
+    sa.base = d->updbase; sa.out = d->upd; sa.S = S; sa.rounds = 1; sa.cut1500 = cut1500 ? 1 : 0; sa.kch = dev_kch(b->ld); sa.stacked = ph == 0 ? d->stacked0 : d->stacked1;
     sa.over = A.over; sa.row_off_w = A.f_rowoff; sa.again_list = d->again; sa.again_count = cnt + 7;
     sa.clist = d->clist; sa.clist_count = cnt + 6; sa.work = d->work;
     sa.hld = hld;
     sa.no_info = ph == 0 ? 1 : 0;           // lost features: seen from many cameras as a rule; the few-column streams of the first frames take the same back end
-    hipLaunchKernelGGL(upd_stack_kernel, dim3(S), dim3(64), 0, stm, sa);
-    AV_LAUNCH_CHECK();
-    // (no second feature pass: a stream whose candidates outgrow its region of the block buffers takes rows from the shared pool,
-    //  dev_build_candidates -- the pass had to be launched every step and waited ~1.1 ms for a CU beside the front-end to do nothing)
-    if ((rc = msckf_lds_opt_in())) return rc;
-    if (ph == 1) {
+    UpdLaunch ul;
+    ul.info = ph == 1;
+    if (ul.info) {
         const int minfo = 5 * cap < INFO_MAXROWS ? 5 * cap : INFO_MAXROWS;
-        const size_t lds_i = upd_info_lds(12, b->ld, minfo);
-        if (lds_i > 160 * 1024) { av_set_error("batched MSCKF: information-form update needs %zu B of LDS", lds_i); return AV_E_CAPACITY; }
-        hipLaunchKernelGGL(upd_info_kernel, dim3(S), dim3(256), lds_i, stm, d->upd);
-        unsigned long long t[32];
-        if (dev_uprof().read(stm, t)) {                     // diagnostic (AV_DEV_UPROF=1): phase stamps of stream 0's workgroups
-            print_stamps("dk_begin stream 0", t + 16, {"imu steps", "cross block", "augment+gap", "add frame", "select lost", "candidates", "triangulate", "erase"});
-            print_stamps("upd_info stream 0", t, {"row map", "gram", "Pc", "F,G", "gauss-jordan", "scale", "P update"});
-        }
+        ul.lds_info = upd_info_lds(12, b->ld, minfo);
     }
-    if (rounds) {
-        // workgroups stride over the device-written list of long streams, sized from the last step's list length
-        const unsigned nl = (unsigned)dev_grid_hint(d, 8 * ph + 6, S, 32);
-        const int k1max = 6 * b->cam_slots + 1;
-        hipLaunchKernelGGL(upd_rowmap_kernel, dim3(nl), dim3(64), 0, stm, d->upd, d->clist, (const int*)(cnt + 6));
-        launch_upd_compress(d->upd, d->clist, (const int*)(cnt + 6), nl, k1max, stm);
-        // rows a pass keeps: a direct stream its m <= DEV_KCH stacked rows, a compressed one its n_c <= 6 max_cam columns' worth
-        const int kmax = DEV_KCH > 6 * b->max_cam ? DEV_KCH : 6 * b->max_cam;
-        const int nmax = b->ld;
-        hipLaunchKernelGGL(upd_gather_kernel, dim3(S), dim3(256), 0, stm, d->upd);
-        // (the factor kernel: one launch for every pass length.  Two launches -- passes of up to 96 rows with 37 KB of LDS, four
-        //  workgroups per CU, then the longer ones -- took 180 + 601 us against 659: most passes of a steady stream keep more than 96 rows)
-        launch_upd_back(d->upd, S, kmax, nmax, stm);
-    }
+    ul.rounds = rounds;
+    // workgroups stride over the device-written list of long streams, sized from the last step's list length
+    ul.n_list = (unsigned)dev_grid_hint(d, 8 * ph + 6, S, 32);
+    ul.k1max = 6 * b->cam_slots + 1;
+    // rows a pass keeps: a direct stream its m <= DEV_KCH stacked rows, a compressed one its n_c <= 6 max_cam columns' worth
+    ul.kmax = DEV_KCH > 6 * b->max_cam ? DEV_KCH : 6 * b->max_cam;
+    ul.nmax = b->ld;
+    if ((rc = dev_launch_update(sa, ul, stm))) return rc;
     AV_LAUNCH_CHECK();
     if (slot.t_used[ph]) AV_HIP(hipEventRecord(slot.t1[ph], stm));
     return AV_OK;

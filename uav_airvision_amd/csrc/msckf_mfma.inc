@@ -547,7 +547,8 @@ __device__ __forceinline__ void chol_mfma_body(const UpdArgsG& a, const int k)
         }
     }
     if (!ok) {
-        // not positive definite to working precision, or not finite.  Update: L = 1e150 I (Y = L^-1 [T | r] ~ 0: delta_x = 0, P stays);
+        // not positive definite to working precision, or not finite.  Update: L = 1e150 I with ZERO for the inverses of its diagonal blocks
+        // (Y = Linv (..) = 0 exactly: delta_x = 0 and P keeps its bits; 1e-150 there left delta_x at 1e-300 of its size, not at zero);
         // compression: [F | f] = 0 (S = s^2 I, delta_x = 0, P unchanged).  The host stops the stream on the flag.
         if (lane == 0 && a.status) *a.status = UPD_BAD_PIVOT;
         if (GRAM) {
@@ -555,7 +556,7 @@ __device__ __forceinline__ void chol_mfma_body(const UpdArgsG& a, const int k)
             for (int row = lane; row < nc; row += 64) rcol[row] = 0.0;
         } else {
             for (int e = lane; e < k * k; e += 64) { const int r = e / k, c = e - r * k; if (c >= r) Sb[(size_t)r * ld + c] = r == c ? 1e150 : 0.0; }
-            for (int e = lane; e < nb * 256; e += 64) a.Pn[e] = ((e & 255) >> 4) == (e & 15) ? 1e-150 : 0.0;
+            for (int e = lane; e < nb * 256; e += 64) a.Pn[e] = 0.0;
         }
     }
 }

@@ -266,6 +266,59 @@ class MsckfDevice(object):
             out.append(d)
         return dict(streams=out, cam_q=q.cpu().numpy(), cam_p=p.cpu().numpy(), cam_qn=qn.cpu().numpy(), P=Pd.cpu().numpy(), **rate)
 
+    def update_ops_dev(self, streams, H, r, P, obs_noise, phase, kch=0, hld=0, cam_stride=None, fs_stride=None, dx_fill=np.nan):
+        """Parity-test entry (av_msckf_update_ops_dev; tests only): the batched measurement update -- stacking decisions, information
+        form, row compression, Cholesky back end -- in the launch sequence a phase of a step runs, for all `streams` at once.
+        streams: one dict per stream with n, optionally mode (1: information form allowed, default; 2: stopped), and feats: the candidate
+        features in map order, each a dict(cams: camera slot of every observation, ok: gate flag, row: first of its 4 M - 3 rows in the
+        stream's block buffer).  H: [streams, rows_cap, ld] (hld = 0) or [streams, rows_cap, hld] (compact rows), r: [streams, rows_cap],
+        P: [streams, ld, ld] (whatever lies outside a stream's n x n square is the caller's pre-fill and must come back untouched).
+        phase 0: the lost-feature configuration (cut at 1500 rows, no information form), 1: the pruning configuration; kch: rows one
+        back-end pass takes directly (0: the filter's own, min(136, ld)).  The library checks every count and index before it launches anything.
+        -> dict(dx [streams, ld] pre-filled with dx_fill, stacked [streams], cols: per stream the touched columns, rec: per stream
+        dict(m, nc, mode, kdir, n_blk) as the stacking kernel wrote it, P)."""
+        S = len(streams)
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if H.ndim != 3 or r.ndim != 2 or P.ndim != 3 or H.shape[0] != S or r.shape != H.shape[:2] or P.shape[0] != S or P.shape[1] != P.shape[2]:
+            raise ValueError('update_ops_dev: inconsistent shapes')
+        ld, rows_cap = P.shape[1], H.shape[1]
+        if H.shape[2] != (hld if hld > 0 else ld):
+            raise ValueError('update_ops_dev: rows of %d doubles, expected %d' % (H.shape[2], hld if hld > 0 else ld))
+        cs = int(cam_stride) if cam_stride is not None else max(1, (ld - 21) // 6)
+        fs = int(fs_stride) if fs_stride is not None else max([1] + [len(st['feats']) for st in streams])
+        n_s = np.array([st['n'] for st in streams], np.int32)
+        mode = np.array([st.get('mode', 1) for st in streams], np.int32)
+        n_cand = np.array([len(st['feats']) for st in streams], np.int32)
+        nf = S * fs
+        counts, ok, row = np.zeros(nf, np.int64), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
+        cams = []
+        for s, st in enumerate(streams):
+            for k, f in enumerate(st['feats'][:fs]):
+                i = s * fs + k
+                counts[i], ok[i], row[i] = len(f['cams']), int(bool(f['ok'])), f['row']
+        # (the observation CSR is laid out slot by slot, so a stream with more candidates than fs_stride still describes valid memory:
+        #  the library refuses it by its count)
+        for s, st in enumerate(streams):
+            for f in st['feats'][:fs]:
+                cams.extend(int(c) for c in f['cams'])
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        cam = np.array(cams if cams else [0], np.int32)
+        dx = np.full((S, ld), dx_fill, dtype=np.float64)
+        stacked, cols, rec = np.full(S, -99, np.int32), np.full((S, 6 * cs), -99, np.int32), np.full((S, 5), -99, np.int32)
+        up = lambda a: torch.from_numpy(a).to(self.dev)
+        Hd, rd, Pd = up(H), up(r), up(P)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_update_ops_dev(
+                self._h, S, int(phase), int(kch), fs, cs, int(hld), hp(n_s), hp(mode), hp(n_cand), hp(off), hp(cam), len(cams), hp(ok), hp(row),
+                N.dptr(Hd), rows_cap * H.shape[2], N.dptr(rd), rows_cap, rows_cap, N.dptr(Pd), ld, ld * ld, float(obs_noise),
+                hp(dx), hp(stacked), hp(cols), hp(rec), self._st()))
+            torch.cuda.synchronize()
+        return dict(dx=dx, stacked=stacked, cols=[c[c >= 0] for c in cols], P=Pd.cpu().numpy(),
+                    rec=[dict(zip(('m', 'nc', 'mode', 'kdir', 'n_blk'), (int(v) for v in q))) for q in rec])
+
     def forecast_ops_dev(self, streams, imu, P, noise, cap, fill=np.nan):
         """Parity-test entry (av_msckf_forecast_ops_dev; tests only): the forecast's two kernels through the helper a step launches them
         through, for all `streams` at once.  streams: one dict per stream with the STATE_FIELDS, n, ncam, and optionally failed,
