@@ -1133,6 +1133,54 @@ int  av_msckf_batch_next_imu_rate(av_msckf_batch* b, av_imu_state* rec, int32_t*
  * Known limits: no forecast for a stream without a frame in the step; no call of its own outside a step; no biases in the record. */
 int  av_msckf_batch_set_forecast(av_msckf_batch* b, int cap);
 int  av_msckf_batch_next_forecast(av_msckf_batch* b, av_imu_state* rec, int32_t* n, double* cov);
+/* Zero-velocity update: a stream that stands still has its velocity pinned to zero.  At rest the stereo features carry no temporal
+ * parallax, so nothing in the filter observes the velocity and the accelerometer bias: both random-walk until the vehicle moves.  Off by
+ * default; off, a step launches exactly what it launched without the feature.  On, every step runs two more kernels, one wavefront per
+ * stream at every launch shape, with no wait, no allocation and no read-back inside the step.
+ *   Detector  behind the prediction, ahead of the lost-feature update; read-only for the filter.
+ *            IMU test   over the bias-corrected samples the step consumed (n_imu of them): w_max = max |gyro|, a_dev_max =
+ *                       max | |acc| - |gravity| |.  imu_ok iff n_imu >= 1, w_max <= gyro_max and a_dev_max <= acc_dev_max.
+ *            Vision test  over the entries of the frame the step appended: an entry is tracked if the previous frame observed its
+ *                       feature, and still if (u0 - u0')^2 + (v0 - v0')^2 <= disparity_max^2 against that observation (cam0, normalised
+ *                       coordinates).  vis_ok iff n_tracked >= min_tracks and 100 n_still >= still_percent n_tracked.  The first live
+ *                       frame and the frame after an online reset have n_tracked = 0.
+ *            DETECTED = imu_ok and vis_ok.  Both are needed: a gently flying vehicle passes the IMU test.
+ *   Update   behind the step's last kernel, ahead of the forecast, for streams that are active, not stopped and DETECTED: the
+ *            reference's measurement_update (msckf.py:548-602) with H selecting state columns 6..8, r = -v and velocity_sigma^2 in
+ *            place of observation_noise.  S = P[6:9, 6:9] + sigma^2 I is inverted explicitly through its 3 x 3 Cholesky factor, S^-1 =
+ *            L^-T L^-1; gamma = r^T S^-1 r.  gate > 0 and gamma > gate: AV_ZU_GATED, nothing is touched.  S not finite or not positive
+ *            definite: AV_ZU_BAD, nothing is touched, the stream is NOT stopped.  Otherwise delta_x = P[:, 6:9] S^-1 r is injected as
+ *            every update's is (null-state aliasing included), P[i][j] -= c_i^T S^-1 c_j is computed for i <= j and mirrored -- P stays
+ *            bit-symmetric, nothing outside the n x n block is touched --, AV_ZU_APPLIED is set.
+ *   One-step lag  The update acts on the state the step LEAVES.  The 12 published doubles of the step (and its odometry covariance,
+ *            landmarks, statistics, IMU-rate records) are NOT rewritten: the pose of step k is the pre-update one.  av_msckf_batch_get_state,
+ *            av_msckf_batch_get_cov, the forecast of step k and everything in step k + 1 see the corrected state.  In the reference's
+ *            terms: feature_callback(msg), then the update.  No existing kernel of the step changes.
+ *   Record   av_zupt, one per stream, in ONE device array that every step overwrites; it is NOT delivered with the step's read-back but
+ *            read on demand.  flags, n_imu, n_tracked, n_still, w_max, a_dev_max are the detector's; v_norm (|v| before the update),
+ *            gamma and dx_pos (|delta_x[12:15]|) the update's, 0 where it did not run.  detected_total / applied_total count over the
+ *            stream's life, so a consumer that polls misses nothing.  A stream that takes no part in a step, or that stopped in it,
+ *            reads a zero record for the step; its totals stay.  av_msckf_batch_restart clears the record and the totals.
+ * av_msckf_batch_set_zupt(b, p): p = NULL switches the update off.  Before the batch's first step only (AV_E_INVALID afterwards).
+ * AV_E_INVALID unless gyro_max, acc_dev_max, disparity_max >= 0, velocity_sigma > 0, gate >= 0 (0 = no gate), all finite, min_tracks >= 0
+ * and 0 <= still_percent <= 100.
+ * av_msckf_batch_read_zupt(b, out): drains the queue, like av_msckf_batch_launch_shape, then copies n_streams records.  Off, or before the
+ * first step: zeros.
+ * Known limits: the thresholds' defaults (config.py) are starting values against the synthetic sensors, not tuned on flight data; no caller
+ * override ("landed, disarmed"); no zero-rotation or position-hold measurement; a moving scene in front of a resting camera vetoes the
+ * update; constant-velocity flight over a scene with fewer than min_tracks tracks is never declared still. */
+#define AV_ZUPT_BYTES 64
+enum { AV_ZU_IMU_OK = 1, AV_ZU_VIS_OK = 2, AV_ZU_DETECTED = 4, AV_ZU_APPLIED = 8, AV_ZU_GATED = 16, AV_ZU_BAD = 32 };
+typedef struct av_zupt {
+    int32_t flags, n_imu, n_tracked, n_still, detected_total, applied_total;
+    double w_max, a_dev_max, v_norm, gamma, dx_pos;
+} av_zupt;
+typedef struct av_zupt_params {
+    double gyro_max, acc_dev_max, disparity_max, velocity_sigma, gate;      /* rad/s, m/s^2, normalised image units, m/s, chi^2 (0: none) */
+    int32_t min_tracks, still_percent;
+} av_zupt_params;
+int  av_msckf_batch_set_zupt(av_msckf_batch* b, const av_zupt_params* p);
+int  av_msckf_batch_read_zupt(av_msckf_batch* b, av_zupt* out);
 int  av_msckf_batch_sizes(av_msckf_batch* b, int stream_idx, int32_t out3[3]);     /* [state dim, camera states, map features] */
 /* Full host-side state of one stream -- every target of measurement_update's injection (msckf.py:568-595), for parity tests
  * (SURVEY 8b get_state): imu32 = [imu_state.timestamp, orientation q(4, JPL xyzw), position(3), velocity(3), gyro_bias(3),
@@ -1162,7 +1210,8 @@ int  av_msckf_batch_stream_status(av_msckf_batch* b, int stream_idx, int32_t* st
  *                  the failure code and text (av_msckf_batch_stream_status reads 0, ""); the parity-test tap's captures.
  *   Reset, device: the IMU state record, state dimension 21, no camera states, the stream's whole covariance region (create-time
  *                  diagonal, zero elsewhere), the observation store (empty, insertion counter 0, header clear, arrays as allocated), the
- *                  stream's rows of the pose, odometry-covariance, landmark, statistics, IMU-rate and forecast buffers.  Camera-state ids and the map's
+ *                  stream's rows of the pose, odometry-covariance, landmark, statistics, IMU-rate and forecast buffers, its zero-velocity record and
+ *                  totals.  Camera-state ids and the map's
  *                  insertion order begin again at 0.
  *   Not reset:     av_msckf_batch_counters and av_msckf_batch_work keep accumulating over all lives; the batch's configuration, its
  *                  output switches and capacities; every other stream.
@@ -1271,6 +1320,15 @@ int  av_msckf_predict_ops_dev_rate(av_msckf* ctx, int n_streams, int wg, int cam
 int  av_msckf_forecast_ops_dev(av_msckf* ctx, int n_streams, int ld, int64_t p_stride, double* state_io, int32_t* state_int_io,
                                const double* imu, int n_imu, const int32_t* pend, const double noise4[4], double* P_dev, void* stream,
                                int cap, av_imu_state* rec_out, int32_t* n_out, double* cov_out);
+/* The zero-velocity update's kernel (tests only; "Zero-velocity update"), launched through the helper a step launches it through.  Streams
+ * are described by the flat host arrays of av_msckf_predict_ops_dev, state_io[43] and state_int_io[6]; `active` is an INPUT here: the
+ * arrays hold the state a step LEAVES, and come back as the kernel left them.  cam_q_dev / cam_p_dev: the device camera states
+ * [n_streams][cam_stride][4 | 3], P_dev: the device covariances [n_streams][p_stride], leading dimension ld, all updated in place.
+ * rec_io[n_streams]: HOST records, uploaded as the caller filled them -- flags carries the detector's verdict, AV_ZU_DETECTED, per stream;
+ * the totals count on from what they hold -- and read back.  Checked before anything is launched: n == 21 + 6 n_cam <= ld, n_cam <=
+ * cam_stride <= 64, p_stride >= ld * ld, the parameters as av_msckf_batch_set_zupt checks them.  Synchronises. */
+int  av_msckf_zupt_ops_dev(av_msckf* ctx, int n_streams, int cam_stride, int ld, int64_t p_stride, double* state_io, int32_t* state_int_io,
+                           double* cam_q_dev, double* cam_p_dev, double* P_dev, const av_zupt_params* params, av_zupt* rec_io, void* stream);
 /* Parity-test entry (tests only; no step of the filter calls it): the batched measurement update (msckf.py:548-602 with the stacking
  * loops of :658-668 and :759-763) for n_streams streams in ONE launch sequence, exactly the one a phase of a filter step runs from the
  * stacking decisions to the covariance update, through the helper the step itself launches it with.  phase 0 = the lost-feature phase

@@ -200,6 +200,16 @@ class FilterStats(C.Structure):                  # av_filter_stats (AV_FILTER_ST
     _fields_ = [('upd', UpdateStats * 2)]
 
 
+class Zupt(C.Structure):                         # av_zupt (AV_ZUPT_BYTES = 64)
+    _fields_ = [(n, C.c_int32) for n in ('flags', 'n_imu', 'n_tracked', 'n_still', 'detected_total', 'applied_total')] + \
+               [(n, C.c_double) for n in ('w_max', 'a_dev_max', 'v_norm', 'gamma', 'dx_pos')]
+
+
+class ZuptParams(C.Structure):                   # av_zupt_params
+    _fields_ = [(n, C.c_double) for n in ('gyro_max', 'acc_dev_max', 'disparity_max', 'velocity_sigma', 'gate')] + \
+               [('min_tracks', C.c_int32), ('still_percent', C.c_int32)]
+
+
 class FrontendConfig(C.Structure):
     _fields_ = [('width', C.c_int32), ('height', C.c_int32),
                 ('grid_row', C.c_int32), ('grid_col', C.c_int32),
@@ -289,6 +299,9 @@ SIGNATURES = {
     'av_msckf_batch_next_imu_rate': (C.c_int, [_P, _P, _P]),
     'av_msckf_batch_set_forecast': (C.c_int, [_P, C.c_int]),
     'av_msckf_batch_next_forecast': (C.c_int, [_P, _P, _P, _P]),
+    'av_msckf_batch_set_zupt': (C.c_int, [_P, C.POINTER(ZuptParams)]),
+    'av_msckf_batch_read_zupt': (C.c_int, [_P, _P]),
+    'av_msckf_zupt_ops_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(ZuptParams), _P, _P]),
     'av_msckf_batch_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32 * 3)]),
     'av_msckf_batch_counters': (C.c_int, [_P, C.POINTER(C.c_int64 * 8)]),
     'av_msckf_batch_launch_shape': (C.c_int, [_P, C.POINTER(C.c_int32 * 17)]),

@@ -178,3 +178,17 @@ class ConfigEuRoC(object):
         # (include/airvision.h, "Forecast")
         self.publish_forecast = False
         self.forecast_cap = 32
+        # no reference counterpart: the zero-velocity update (include/airvision.h, "Zero-velocity update").  A stream that passes the IMU
+        # test (gyro and | |acc| - g | below the thresholds over the frame's samples) and the vision test (at least zupt_min_tracks
+        # tracked features, zupt_still_percent of them displaced by at most zupt_max_disparity pixels against the previous frame) gets
+        # velocity = 0 as a measurement of deviation zupt_velocity_sigma, gated at zupt_gate (the 95 % quantile of chi^2 with three
+        # degrees of freedom; 0: no gate).  The thresholds are starting values against the synthetic sensors (gyro sigma 0.005 rad/s,
+        # accelerometer sigma 0.05 m/s^2), not tuned on flight data.  The drop-in MSCKF keeps the record in `last_zupt`.
+        self.use_zupt = False
+        self.zupt_gyro_threshold = 0.1
+        self.zupt_acc_threshold = 0.5
+        self.zupt_max_disparity = 0.5
+        self.zupt_min_tracks = 10
+        self.zupt_still_percent = 90
+        self.zupt_velocity_sigma = 0.05
+        self.zupt_gate = 7.815

@@ -145,6 +145,8 @@ struct av_msckf_batch {
     // the optional outputs (OUTS, msckf_dev.inc).  out_set: every feature's setting (av_msckf_batch_set_*), on the batch and on every
     // group; next_outs: the destinations av_msckf_batch_next_* handed over for the next step (batch only), taken by that step
     int out_set[N_FEAT] = {}; StepOuts next_outs;
+    // the zero-velocity update (airvision.h, "Zero-velocity update"; av_msckf_batch_set_zupt): on the batch and on every group
+    bool zupt_on = false; av_zupt_params zupt{};
     explicit av_msckf_batch(int n) : st(n) {}
 };
 
@@ -840,6 +842,52 @@ AV_EXPORT int av_msckf_batch_next_imu_rate(av_msckf_batch* b, av_imu_state* rec,
 AV_EXPORT int av_msckf_batch_set_forecast(av_msckf_batch* b, int cap) { return batch_set_out(b, F_FC, cap, cap >= 0 && cap <= FORECAST_CAP_MAX); }
 AV_EXPORT int av_msckf_batch_next_forecast(av_msckf_batch* b, av_imu_state* rec, int32_t* n, double* cov) { return batch_next_out(b, F_FC, {rec, n, cov}); }
 
+// The zero-velocity update (airvision.h, "Zero-velocity update").  Not an entry of OUTS: its record is not delivered with a step's
+// read-back, it lives in one device array per group (DevPath::zupt_d, taken at dev_reserve when the update is on) and is read on demand.
+static_assert(sizeof(av_zupt) == AV_ZUPT_BYTES && sizeof(DZupt) == AV_ZUPT_BYTES, "av_zupt layout");
+static_assert(offsetof(av_zupt, applied_total) == offsetof(DZupt, applied_total) && offsetof(av_zupt, w_max) == offsetof(DZupt, w_max) && offsetof(av_zupt, dx_pos) == offsetof(DZupt, dx_pos), "av_zupt fields");
+static_assert(ZU_IMU_OK == AV_ZU_IMU_OK && ZU_VIS_OK == AV_ZU_VIS_OK && ZU_DETECTED == AV_ZU_DETECTED && ZU_APPLIED == AV_ZU_APPLIED && ZU_GATED == AV_ZU_GATED && ZU_BAD == AV_ZU_BAD, "AV_ZU_* bits");
+static bool zupt_params_ok(const av_zupt_params* p)
+{
+    return std::isfinite(p->gyro_max) && p->gyro_max >= 0 && std::isfinite(p->acc_dev_max) && p->acc_dev_max >= 0 && std::isfinite(p->disparity_max) && p->disparity_max >= 0 &&
+           std::isfinite(p->velocity_sigma) && p->velocity_sigma > 0 && std::isfinite(p->gate) && p->gate >= 0 && p->min_tracks >= 0 && p->still_percent >= 0 && p->still_percent <= 100;
+}
+AV_EXPORT int av_msckf_batch_set_zupt(av_msckf_batch* b, const av_zupt_params* p)
+{
+    if (!b) { av_set_error("av_msckf_batch_set_zupt: bad arguments"); return AV_E_INVALID; }
+    if (p && !zupt_params_ok(p)) {
+        av_set_error("av_msckf_batch_set_zupt: parameters out of range (thresholds >= 0, velocity_sigma > 0, gate >= 0, all finite, min_tracks >= 0, still_percent 0 .. 100)");
+        return AV_E_INVALID;
+    }
+    std::vector<av_msckf_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    bool stepped = b->dev_seq > 0;
+    for (av_msckf_batch* g : parts) if (g->n_steps > 0 || g->dev.cap > 0) stepped = true;
+    if (stepped) { av_set_error("av_msckf_batch_set_zupt: the batch has stepped; the zero-velocity update is switched before the first step"); return AV_E_INVALID; }
+    b->zupt_on = p != nullptr;
+    if (p) b->zupt = *p;
+    for (av_msckf_batch* g : parts) { g->zupt_on = b->zupt_on; g->zupt = b->zupt; }
+    return AV_OK;
+}
+AV_EXPORT int av_msckf_batch_read_zupt(av_msckf_batch* b, av_zupt* out)
+{
+    if (!b || !out) { av_set_error("av_msckf_batch_read_zupt: bad arguments"); return AV_E_INVALID; }
+    const int rc = av_msckf_batch_wait(b, 0);
+    if (rc) return rc;
+    std::vector<av_msckf_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    memset(out, 0, sizeof(av_zupt) * (size_t)b->S);
+    size_t s0 = 0;
+    for (av_msckf_batch* g : parts) {
+        if (g->dev.zupt_d) {
+            AV_HIP(hipSetDevice(g->device));
+            AV_HIP(hipMemcpy(out + s0, g->dev.zupt_d, sizeof(av_zupt) * (size_t)g->S, hipMemcpyDeviceToHost));
+        }
+        s0 += (size_t)g->S;
+    }
+    return AV_OK;
+}
+
 AV_EXPORT int av_msckf_batch_get_cov(av_msckf_batch* b, int stream_idx, double* P_host, int n, void* stream)
 {
     if (!b || stream_idx < 0 || stream_idx >= b->S) { av_set_error("av_msckf_batch_get_cov: bad arguments"); return AV_E_INVALID; }
@@ -1318,6 +1366,69 @@ AV_EXPORT int av_msckf_forecast_ops_dev(av_msckf* c, int n_streams, int ld, int6
     AV_HIP(hipMemcpyAsync(rec_out, fc.rec, sizeof(DImuState) * S * (size_t)cap, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(n_out, fc.n, sizeof(int) * 2 * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(cov_out, fc.cov, sizeof(double) * ODOM_COV_DOUBLES * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipMemcpyAsync(st.data(), a.st, sizeof(DState) * S, hipMemcpyDeviceToHost, stm));
+    AV_HIP(hipStreamSynchronize(stm));
+    for (int s = 0; s < S; ++s) {
+        double* d = state_io + (size_t)s * SD; int32_t* I = state_int_io + (size_t)s * SI;
+        const DState& D = st[s];
+        d[0] = D.ts;
+        memcpy(d + 1, D.q, 32); memcpy(d + 5, D.p, 24); memcpy(d + 8, D.v, 24); memcpy(d + 11, D.bg, 24); memcpy(d + 14, D.ba, 24);
+        memcpy(d + 17, D.R_ic, 72); memcpy(d + 26, D.t_ci, 24); memcpy(d + 29, D.qn, 32); memcpy(d + 33, D.pn, 24); memcpy(d + 36, D.vn, 24);
+        memcpy(d + 39, D.gravity, 24); d[42] = D.tracking_rate;
+        I[0] = D.n; I[1] = D.ncam; I[2] = D.failed; I[3] = D.null_aliased; I[4] = D.first_img; I[5] = D.active;
+    }
+    return AV_OK;
+}
+
+// Parity-test entry for the zero-velocity update (airvision.h, "Zero-velocity update"; tests only; no step of the filter calls it): for
+// n_streams streams described by the flat host arrays of av_msckf_predict_ops_dev -- `active` an INPUT, as in av_msckf_forecast_ops_dev --
+// dk_zupt_update through dev_launch_zupt_update, the helper dev_enqueue itself calls, on the caller's device camera states and
+// covariances.  rec_io: HOST records, uploaded as the caller filled them (flags: the detector's verdict per stream) and read back.
+// Every argument is checked before anything is launched.  Synchronises.
+AV_EXPORT int av_msckf_zupt_ops_dev(av_msckf* c, int n_streams, int cam_stride, int ld, int64_t p_stride, double* state_io, int32_t* state_int_io,
+                                    double* cam_q_dev, double* cam_p_dev, double* P_dev, const av_zupt_params* params, av_zupt* rec_io, void* stream)
+{
+    constexpr int SD = 43, SI = 6;
+    if (!c || n_streams < 1 || n_streams > 65536 || cam_stride < 1 || cam_stride > 64 || !state_io || !state_int_io || !cam_q_dev || !cam_p_dev || !P_dev ||
+        !params || !rec_io || ld < IMU_DIM || ld > IMU_DIM + 6 * 64 || p_stride < (int64_t)ld * ld || !zupt_params_ok(params)) {
+        av_set_error("av_msckf_zupt_ops_dev: bad arguments");
+        return AV_E_INVALID;
+    }
+    const int S = n_streams;
+    for (int s = 0; s < S; ++s) {
+        const int32_t* I = state_int_io + (size_t)s * SI;
+        if (I[1] < 0 || I[1] > cam_stride || I[0] != IMU_DIM + 6 * I[1] || I[0] > ld) {
+            av_set_error("av_msckf_zupt_ops_dev: stream %d: n = %d, %d camera states, cam_stride %d, ld %d do not fit", s, I[0], I[1], cam_stride, ld);
+            return AV_E_INVALID;
+        }
+    }
+    hipStream_t stm = (hipStream_t)stream;
+    AV_HIP(hipSetDevice(c->device));
+    struct Arena { AvScratch mem; char* p = nullptr; size_t used = 0;
+                   size_t take(size_t bytes) { const size_t o = used; used += (bytes + 255) / 256 * 256; return o; } } ar;
+    const size_t o_st = ar.take(sizeof(DState) * S), o_rec = ar.take(sizeof(DZupt) * S);
+    { const int rca = ar.mem.alloc(ar.used); if (rca) return rca; }
+    ar.p = static_cast<char*>(ar.mem.p);
+    std::vector<DState> st((size_t)S);
+    memset(st.data(), 0, sizeof(DState) * S);
+    for (int s = 0; s < S; ++s) {
+        const double* d = state_io + (size_t)s * SD; const int32_t* I = state_int_io + (size_t)s * SI;
+        DState& D = st[s];
+        D.ts = d[0];
+        memcpy(D.q, d + 1, 32); memcpy(D.p, d + 5, 24); memcpy(D.v, d + 8, 24); memcpy(D.bg, d + 11, 24); memcpy(D.ba, d + 14, 24);
+        memcpy(D.R_ic, d + 17, 72); memcpy(D.t_ci, d + 26, 24); memcpy(D.qn, d + 29, 32); memcpy(D.pn, d + 33, 24); memcpy(D.vn, d + 36, 24);
+        memcpy(D.gravity, d + 39, 24); D.tracking_rate = d[42];
+        D.n = I[0]; D.ncam = I[1]; D.failed = I[2]; D.null_aliased = I[3]; D.first_img = I[4]; D.active = I[5];
+    }
+    DevArgs a; memset(&a, 0, sizeof(a));
+    a.S = S; a.cs = cam_stride; a.ld = ld; a.pstride = (size_t)p_stride; a.P = P_dev;
+    a.st = (DState*)(ar.p + o_st); a.cam_q = cam_q_dev; a.cam_p = cam_p_dev;
+    const ZuArgs z = dev_zu_args(*params, (DZupt*)(ar.p + o_rec));
+    AV_HIP(hipMemcpyAsync(a.st, st.data(), sizeof(DState) * S, hipMemcpyHostToDevice, stm));
+    AV_HIP(hipMemcpyAsync(z.rec, rec_io, sizeof(DZupt) * S, hipMemcpyHostToDevice, stm));
+    dev_launch_zupt_update(a, S, z, stm);
+    AV_LAUNCH_CHECK();
+    AV_HIP(hipMemcpyAsync(rec_io, z.rec, sizeof(DZupt) * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipMemcpyAsync(st.data(), a.st, sizeof(DState) * S, hipMemcpyDeviceToHost, stm));
     AV_HIP(hipStreamSynchronize(stm));
     for (int s = 0; s < S; ++s) {

@@ -29,6 +29,8 @@
 //                IMU sample of the frame, gathered from the records dk_state leaves for dk_cov
 //   dk_forecast_state, dk_forecast_cov  (behind dk_finish*, when av_msckf_batch_set_forecast is on) per stream: the state the step leaves,
 //                carried through the IMU samples the step has NOT consumed, with the covariance of its IMU block; read-only for the filter
+//   dk_zupt_detect, dk_zupt_update  (behind dk_cov / behind dk_finish*, when av_msckf_batch_set_zupt is on) per stream: is the stream at rest in
+//                this step (IMU samples and the tracks of the appended frame), and if so a velocity = 0 measurement update on the state the step leaves
 //
 // Per-stream capacity failures are recorded in the stream's state (DState::failed) and stop that stream only.
 
@@ -1070,6 +1072,148 @@ __global__ __launch_bounds__(64) void dk_forecast_cov(DevArgs a, FcOut F)
 }
 
 // ------------------------------------------------------------------------------------------------
+// Zero-velocity update (include/airvision.h, "Zero-velocity update"; both kernels launched only when av_msckf_batch_set_zupt is on).  ONE
+// wavefront per stream at every launch shape, plain vector stores, no atomics, no allocation; their arguments travel in ZuArgs, so DCtl
+// and DevArgs are what they were and the step's other kernels compile to the code they had.
+//   dk_zupt_detect  behind the prediction's launches (dk_state .. dk_begin4 .. dk_cov), ahead of the lost-feature phase: is the stream at
+//                   rest in this step?  Read-only for the filter; writes the stream's record z.rec[s] and nothing else.
+//                   IMU test: over the bias-corrected samples the step consumed, a.prop[first .. first + cnt) of a.cov[s], a lane per
+//                   sample, strided: |gyro| <= gyro_max and | |acc| - |gravity| | <= acc_dev_max for every one of them (a NaN fails), and
+//                   cnt >= 1; the two maxima go into the record.
+//                   Vision test: over the entries of the frame dk_begin4 has just appended, order[hdr[AVS_N_ORDER] - 1], a lane per entry,
+//                   strided: tracked = the entry has a previous observation (fr_prev >= 0), still = tracked and its cam0 point moved at
+//                   most disparity_max (normalised units) against that observation.  Counts by ballot and popcount: integers, the same
+//                   at every launch shape.  vis_ok = n_tracked >= min_tracks and 100 n_still >= still_percent n_tracked.
+//                   A stream that takes no part in the step (a.cov[s].act == 0) or that the append has stopped reads a zero record; its
+//                   two totals stay.
+//   dk_zupt_update  behind the step's dk_finish* instance, ahead of the forecast: for a stream that is active, not failed and DETECTED,
+//                   measurement_update (msckf.py:548-602) with H = the selection of state columns 6..8, r = -v and velocity_sigma^2 in
+//                   place of observation_noise, on the state the step LEAVES (both updates, the camera removal and online_reset are in;
+//                   the 12 published doubles are not rewritten).  S = P[6:9, 6:9] + sigma^2 I is 3 x 3: its Cholesky factor L in
+//                   registers, every lane the same; S^-1 = L^-T L^-1 is applied as such, explicitly, no QR and no general solver.
+//                   gamma = |L^-1 r|^2.  gate > 0 and gamma > gate: AV_ZU_GATED, nothing touched.  A pivot that is not positive and
+//                   finite: AV_ZU_BAD, nothing touched, the stream is not failed.  Otherwise Y = C L^-T with C = P[:, 6:9] (n x 3) and
+//                   delta_x = Y (L^-1 r) are staged in LDS (4 n doubles: 5,280 B at n = 165), one barrier, then P[i][j] -= y_i . y_j
+//                   for i <= j only, the value stored at [i][j] and [j][i]: P stays bit-symmetric and nothing outside the n x n block of
+//                   the ld-wide region is read or written.  delta_x lands through dev_inject_imu / dev_inject_cam, null-state aliasing
+//                   included: lane 0 the IMU state, a lane per camera state.
+// ------------------------------------------------------------------------------------------------
+enum { ZU_IMU_OK = 1, ZU_VIS_OK = 2, ZU_DETECTED = 4, ZU_APPLIED = 8, ZU_GATED = 16, ZU_BAD = 32 };
+struct DZupt { int flags, n_imu, n_tracked, n_still, detected_total, applied_total; double w_max, a_dev_max, v_norm, gamma, dx_pos; };
+static_assert(sizeof(DZupt) == 64, "av_zupt is 64 bytes");
+struct ZuArgs { DZupt* rec; double gyro_max, acc_dev_max, disparity_max, velocity_sigma, gate; int min_tracks, still_percent; };      // rec: [S]
+
+__global__ __launch_bounds__(64) void dk_zupt_detect(DevArgs a, ZuArgs z)
+{
+    AV_FILTER_PRIO();
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const DCov& cv = a.cov[s];
+    const DState* D = a.st + s;
+    DZupt* R = z.rec + s;
+    if (!(cv.act && D->active && !D->failed)) {               // (wavefront-uniform)
+        if (lane == 0) { R->flags = 0; R->n_imu = 0; R->n_tracked = 0; R->n_still = 0; R->w_max = 0.0; R->a_dev_max = 0.0; R->v_norm = 0.0; R->gamma = 0.0; R->dx_pos = 0.0; }
+        return;
+    }
+    const int cnt = cv.cnt, first = cv.first;
+    double w_max = 0.0, a_max = 0.0;
+    int imu_fail = 0;
+    for (int k = lane; k < cnt; k += 64) {
+        const PropArgs& pa = a.prop[first + k];
+        const double w = h_norm3(pa.gyro), ad = fabs(h_norm3(pa.acc) - h_norm3(pa.gravity));
+        if (!(w <= z.gyro_max && ad <= z.acc_dev_max)) imu_fail = 1;
+        w_max = fmax(w_max, w); a_max = fmax(a_max, ad);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { w_max = fmax(w_max, __shfl_xor(w_max, d)); a_max = fmax(a_max, __shfl_xor(a_max, d)); }
+    const int imu_ok = cnt >= 1 && __ballot(imu_fail) == 0ull;
+    const AvsStore V = dev_store(a, s);
+    const int n_order = V.hdr[AVS_N_ORDER];
+    const int slot = n_order > 0 ? V.order[n_order - 1] : -1;
+    const int ne = slot >= 0 ? V.fr_n[slot] : 0;
+    const double dm2 = z.disparity_max * z.disparity_max;
+    int n_tracked = 0, n_still = 0;
+    for (int base = 0; base < ne; base += 64) {
+        const int i = base + lane;
+        int tracked = 0, still = 0;
+        if (i < ne) {
+            const size_t e = (size_t)slot * V.cap + i;
+            const int pl = V.fr_prev[e];
+            if (pl >= 0) {
+                tracked = 1;
+                const double* z1 = V.fr_z + 4 * e;
+                const double* z0 = V.fr_z + 4 * ((size_t)avs_lslot(pl) * V.cap + avs_lidx(pl));
+                const double du = z1[0] - z0[0], dv = z1[1] - z0[1];
+                still = du * du + dv * dv <= dm2;
+            }
+        }
+        n_tracked += __popcll(__ballot(tracked)); n_still += __popcll(__ballot(still));
+    }
+    if (lane == 0) {
+        const int vis_ok = n_tracked >= z.min_tracks && 100ll * n_still >= (long long)z.still_percent * n_tracked;
+        const int det = imu_ok && vis_ok;
+        R->flags = (imu_ok ? ZU_IMU_OK : 0) | (vis_ok ? ZU_VIS_OK : 0) | (det ? ZU_DETECTED : 0);
+        R->n_imu = cnt; R->n_tracked = n_tracked; R->n_still = n_still;
+        R->detected_total += det;
+        R->w_max = w_max; R->a_dev_max = a_max; R->v_norm = 0.0; R->gamma = 0.0; R->dx_pos = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(64) void dk_zupt_update(DevArgs a, ZuArgs z)
+{
+    AV_FILTER_PRIO();
+    extern __shared__ double zu_lds[];                        // Y [n][3], delta_x [n]; the launch gives 4 ld doubles
+    const int s = blockIdx.x, lane = threadIdx.x;
+    DState* D = a.st + s;
+    DZupt* R = z.rec + s;
+    if (!(D->active && !D->failed && (R->flags & ZU_DETECTED))) return;      // (wavefront-uniform)
+    const int n = D->n, ld = a.ld, ncam = D->ncam;
+    double* P = a.P + (size_t)s * a.pstride;
+    double* Y = zu_lds; double* dxl = zu_lds + 3 * (size_t)n;
+    const double s2 = z.velocity_sigma * z.velocity_sigma;
+    const double s00 = P[(size_t)6 * ld + 6] + s2, s01 = P[(size_t)6 * ld + 7], s02 = P[(size_t)6 * ld + 8];
+    const double s11 = P[(size_t)7 * ld + 7] + s2, s12 = P[(size_t)7 * ld + 8], s22 = P[(size_t)8 * ld + 8] + s2;
+    // S = L L^T; a pivot that is not positive and finite makes everything behind it NaN
+    const double l00 = sqrt(s00), l10 = s01 / l00, l20 = s02 / l00;
+    const double d1 = s11 - l10 * l10, l11 = sqrt(d1), l21 = (s12 - l20 * l10) / l11;
+    const double d2 = s22 - l20 * l20 - l21 * l21, l22 = sqrt(d2);
+    const double v0 = D->v[0], v1 = D->v[1], v2 = D->v[2];
+    const double r0 = (-v0) / l00, r1 = (-v1 - l10 * r0) / l11, r2 = (-v2 - l20 * r0 - l21 * r1) / l22;      // L^-1 r
+    const double gamma = r0 * r0 + r1 * r1 + r2 * r2;
+    const double v_norm = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+    const bool gated = z.gate > 0.0 && gamma > z.gate;
+    const bool bad = !(s00 > 0.0 && d1 > 0.0 && d2 > 0.0 && isfinite(s00) && isfinite(d1) && isfinite(d2) && isfinite(s01) && isfinite(s02) && isfinite(s12));
+    if (gated || bad) {                                       // (wavefront-uniform: every lane holds the same numbers)
+        if (lane == 0) { R->flags |= gated ? ZU_GATED : ZU_BAD; R->v_norm = v_norm; R->gamma = gamma; }
+        return;
+    }
+    for (int i = lane; i < n; i += 64) {
+        const double* c = P + (size_t)i * ld + 6;
+        const double y0 = c[0] / l00, y1 = (c[1] - l10 * y0) / l11, y2 = (c[2] - l20 * y0 - l21 * y1) / l22;
+        Y[3 * i] = y0; Y[3 * i + 1] = y1; Y[3 * i + 2] = y2;
+        dxl[i] = y0 * r0 + y1 * r1 + y2 * r2;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int i = 0; i < n; ++i) {
+        const double y0 = Y[3 * i], y1 = Y[3 * i + 1], y2 = Y[3 * i + 2];
+        for (int j = i + lane; j < n; j += 64) {
+            const double v = P[(size_t)i * ld + j] - (y0 * Y[3 * j] + y1 * Y[3 * j + 1] + y2 * Y[3 * j + 2]);
+            P[(size_t)i * ld + j] = v; P[(size_t)j * ld + i] = v;
+        }
+    }
+    if (lane == 0) {
+        dev_inject_imu(*D, dxl);
+        R->flags |= ZU_APPLIED; R->applied_total += 1;
+        R->v_norm = v_norm; R->gamma = gamma;
+        R->dx_pos = sqrt(dxl[12] * dxl[12] + dxl[13] * dxl[13] + dxl[14] * dxl[14]);
+    }
+    if (lane < ncam) {
+        const size_t c = (size_t)s * a.cs + lane;
+        dev_inject_cam(a.cam_q + 4 * c, a.cam_p + 3 * c, dxl + IMU_DIM + 6 * lane);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // dk_restart: stream restart (include/airvision.h, "Stream restart"; host side: dev_restart).  No step launches it.  One workgroup per
 // LISTED stream, s = list[blockIdx.x] (the host has checked every index against S and removed repeats), on the group's own stream, so a
 // step enqueued behind it finds the stream as dev_reserve first made it:
@@ -1083,7 +1227,7 @@ __global__ __launch_bounds__(64) void dk_forecast_cov(DevArgs a, FcOut F)
 //               hdr[AVS_OVERFLOW]), every persistent array as allocated
 //   outputs     the stream's rows of out, of the odometry-covariance, landmark (records and counts) and statistics buffers: zero, as
 //               allocated; likewise the IMU-rate and the forecast records and counts and the forecast covariance.  Every step rewrites them for every stream; they are cleared so that a
-//               read of the buffers finds no old life.
+//               read of the buffers finds no old life.  The stream's zero-velocity record, its two run-wide totals included: zero.
 // Not touched: Pn, T, Kt, scratch, the block buffers, the per-phase feature arrays and lists, the store's scratch -- every step writes
 // what it reads of them; `work` (av_msckf_batch_work accumulates).  Overflow pool: a stream holds NO pool rows between steps.  The pool
 // is a bump counter, cnt[4] of the step's counter set, zeroed for every step by the step before it (dk_state: cnt_next); a stream's
@@ -1095,6 +1239,7 @@ struct DRestart {
     const int* list; int* carry;                              // [n] streams; [n][2] the counters they held
     double v0[3], t_ci[3], gravity[3], R_ic[9];               // create-time values of the batch
     double* odom; LmOut lm; DUpdStats* stats; IrOut ir; FcOut fc;      // the optional outputs (null: off)
+    DZupt* zupt;                                               // the zero-velocity records [S] (null: off)
 };
 __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
 {
@@ -1117,6 +1262,7 @@ __global__ __launch_bounds__(256) void dk_restart(DevArgs a, DRestart r)
         if (r.ir.rec) { r.ir.n[2 * (size_t)s] = 0; r.ir.n[2 * (size_t)s + 1] = 0; }
         if (r.fc.rec) { r.fc.n[2 * (size_t)s] = 0; r.fc.n[2 * (size_t)s + 1] = 0; }
     }
+    if (r.zupt && tid < (int)(sizeof(DZupt) / 8)) reinterpret_cast<unsigned long long*>(r.zupt + s)[tid] = 0ull;      // the record and both totals
     double* P = a.P + (size_t)s * a.pstride;
     for (size_t i = tid; i < a.pstride; i += nt) {            // reset_state_cov (msckf.py:788-798) in a cleared region
         const int rr = (int)(i / a.ld), c = (int)(i - (size_t)rr * a.ld);
@@ -1237,4 +1383,5 @@ struct DevPath {
     // stream restart (dk_restart): the index list [S] and the counters the listed streams held [S][2], on the device and pinned; taken
     // with the rest at dev_reserve, so a restart allocates nothing
     int* rs_list_d = nullptr; int* rs_list_h = nullptr; int* rs_carry_d = nullptr; int* rs_carry_h = nullptr;
+    DZupt* zupt_d = nullptr;         // [S] zero-velocity records, overwritten every step and read on demand (av_msckf_batch_read_zupt); NULL: the update is off
 };

@@ -63,6 +63,7 @@ int dev_reserve(av_msckf_batch* b, int cap)
         DA(d->cols, S * 6 * cs) DA(d->clist, S + 8) DA(d->work, S * 8)
         for (int i = 0; i < N_OUT; ++i) if (b->out_set[OUTS[i].feat]) DA(d->outs_d[i], S * OUTS[i].bytes(b->out_set))
         DA(d->rs_list_d, S) DA(d->rs_carry_d, S * 2)
+        if (b->zupt_on) DA(d->zupt_d, S)                     // the zero-velocity records: zero, like their totals
         if ((rc = b->res.pinned(&d->rs_list_h, S)) || (rc = b->res.pinned(&d->rs_carry_h, S * 2))) return rc;
         DAF(A.pos_of, S * A.ns, 0xFF) DAF(A.order, S * A.ns, 0xFF) DA(A.fr_n, S * A.ns) DA(A.hdr, S * AVS_HDR_WORDS) DA(A.births, S)
     }
@@ -509,6 +510,23 @@ void dev_launch_forecast(const DevArgs& a, int S, const FcOut& fc, hipStream_t s
     hipLaunchKernelGGL(dk_forecast_cov, dim3(S), dim3(64), 0, stm, a, fc);
 }
 
+// The zero-velocity update's two launches (av_msckf_batch_set_zupt), one wavefront per stream whatever shape the step's other kernels take:
+// the detector behind the prediction's launches and ahead of the lost-feature phase, the update behind the step's last per-stream kernel
+// and ahead of the forecast.  One place for the step (dev_enqueue) and, the update's, for the parity-test entry av_msckf_zupt_ops_dev.
+// The update stages Y and delta_x in 4 ld doubles of dynamic LDS.
+ZuArgs dev_zu_args(const av_zupt_params& p, DZupt* rec)
+{
+    return ZuArgs{rec, p.gyro_max, p.acc_dev_max, p.disparity_max, p.velocity_sigma, p.gate, p.min_tracks, p.still_percent};
+}
+void dev_launch_zupt_detect(const DevArgs& a, int S, const ZuArgs& z, hipStream_t stm)
+{
+    hipLaunchKernelGGL(dk_zupt_detect, dim3(S), dim3(64), 0, stm, a, z);
+}
+void dev_launch_zupt_update(const DevArgs& a, int S, const ZuArgs& z, hipStream_t stm)
+{
+    hipLaunchKernelGGL(dk_zupt_update, dim3(S), dim3(64), sizeof(double) * 4 * (size_t)a.ld, stm, a, z);
+}
+
 // The named instances of dk_mid and dk_finish (profiles/filter_stats/README.md has why they are named instances), by the outputs that
 // are on: the same launches as with all off, the instance also writes those outputs' records and the step reads them back.  Every
 // instance's parameter list is DevArgs, then the ordered subset of (double* odom, LmOut, DUpdStats*) of its set bits: the order
@@ -573,6 +591,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     d->launched_wg = dk_wg;
     dev_launch_predict(a, S, dk_wg, true, stm, dev_kouts(b).ir);
     AV_LAUNCH_CHECK();
+    if (d->zupt_d) { dev_launch_zupt_detect(a, S, dev_zu_args(b->zupt, d->zupt_d), stm); AV_LAUNCH_CHECK(); }
     if ((rc = dev_phase(b, 0, stm, sl, a.cnt))) return rc;
     if (b->debug_capture && (rc = dev_debug_capture(b, 0, stm))) return rc;
     a.stacked = d->stacked0;
@@ -584,6 +603,7 @@ int dev_enqueue(av_msckf_batch* b, int k, bool dev_msg, size_t n_imu, hipStream_
     if (b->debug_capture && (rc = dev_debug_capture(b, 1, stm))) return rc;
     a.stacked = d->stacked1;
     if ((rc = dev_launch_outs(true, b, a, dk_wg, stm))) return rc;
+    if (d->zupt_d) { dev_launch_zupt_update(a, S, dev_zu_args(b->zupt, d->zupt_d), stm); AV_LAUNCH_CHECK(); }      // on the state the step leaves: the forecast starts from the corrected one
     if (sl.pend_d) {
         FcOut fc = dev_kouts(b).fc; fc.pend = sl.pend_d;
         dev_launch_forecast(a, S, fc, stm);
@@ -631,7 +651,7 @@ int dev_restart(av_msckf_batch* b, const int* list, int n, hipStream_t stm)
     for (int i = 0; i < 3; ++i) { r.v0[i] = b->vel0[i]; r.t_ci[i] = b->t_ci0[i]; r.gravity[i] = b->gravity0[i]; }
     for (int i = 0; i < 9; ++i) r.R_ic[i] = b->R_ic0[i];
     const KOuts o = dev_kouts(b);
-    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats; r.ir = o.ir; r.fc = o.fc;
+    r.odom = o.odom; r.lm = o.lm; r.stats = o.stats; r.ir = o.ir; r.fc = o.fc; r.zupt = d->zupt_d;
     hipLaunchKernelGGL(dk_restart, dim3((unsigned)n), dim3(256), 0, stm, d->A, r);
     AV_LAUNCH_CHECK();
     AV_HIP(hipMemcpyAsync(d->rs_carry_h, d->rs_carry_d, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, stm));

@@ -130,10 +130,16 @@ class MSCKF(object):
         self.last_forecast = None
         self.last_forecast_pending = (0, 0)
         self.last_forecast_covariance = None
+        # config.use_zupt = True (no reference counterpart; default off): the zero-velocity update with the config's zupt_* thresholds
+        # (include/airvision.h, "Zero-velocity update").  It acts behind every feature_callback: the vio_result of a frame is the
+        # pre-update pose, state_server and the next frame see the corrected state.  `last_zupt` holds the frame's record
+        # (msckf_ops.ZUPT_DTYPE, see msckf_ops.unpack_zupt).  vio_result is unchanged.
+        self._zupt_on = bool(getattr(config, 'use_zupt', False))
+        self.last_zupt = None
         self._flt = BatchedMSCKF(config, 1, device=device, rows_cap=rows_cap, odom_cov=self._cov_on, landmarks=self._lm_on,
                                  landmark_cap=int(getattr(config, 'landmark_cap', 256)), stats=self._stats_on, imu_rate=self._ir_on,
                                  imu_rate_cap=int(getattr(config, 'imu_rate_cap', 32)), forecast=self._fc_on,
-                                 forecast_cap=int(getattr(config, 'forecast_cap', 32)))
+                                 forecast_cap=int(getattr(config, 'forecast_cap', 32)), zupt=self._zupt_on)
         self.state_server = StateServer(self._flt)
         self.map_server = _MapView(self._flt)
         # class-level statics the reference sets in its constructor (msckf.py:128-150), kept for code that reads them
@@ -171,6 +177,7 @@ class MSCKF(object):
         self.last_forecast = None
         self.last_forecast_pending = (0, 0)
         self.last_forecast_covariance = None
+        self.last_zupt = None
         self.debug = {}
 
     @property
@@ -205,6 +212,8 @@ class MSCKF(object):
         out = self._flt.step(ids, uv, [n], [feature_msg.timestamp], cov=True if self._cov_on else None, landmarks=True if self._lm_on else None,
                              stats=True if self._stats_on else None, imu_states=True if self._ir_on else None,
                              forecast=True if self._fc_on else None)
+        if self._zupt_on:
+            self.last_zupt = self._flt.read_zupt()[0].copy()
         if self._fc_on:
             rec, cnt, cov = self._flt.last_forecast
             got, C15, _ = unpack_forecast(rec, cnt, cov, 0)

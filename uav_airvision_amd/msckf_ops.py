@@ -358,6 +358,46 @@ class MsckfDevice(object):
             out.append(d)
         return dict(streams=out, P=Pd.cpu().numpy(), rec=rec.view(IMU_STATE_DTYPE).reshape(S, int(cap)), n=n, cov=cov)
 
+    def zupt_ops_dev(self, streams, cam_q, cam_p, P, params):
+        """Parity-test entry (av_msckf_zupt_ops_dev; tests only): the zero-velocity update's kernel through the helper a step launches it
+        through, for all `streams` at once.  streams: one dict per stream with the STATE_FIELDS, n, ncam, and optionally failed,
+        null_aliased, first_img, active (default 1) -- the state a step LEAVES -- and zupt_flags (default ZU_DETECTED), detected_total,
+        applied_total (default 0): the record as the detector left it.  cam_q / cam_p: [streams, cam_stride, 4 | 3]; P: [streams, ld, ld]
+        (whatever lies outside a stream's n x n square is the caller's pre-fill); params: a dict of ZUPT_PARAM_NAMES.
+        -> dict(streams: the states as they come back, cam_q, cam_p, P, rec ZUPT_DTYPE[streams])."""
+        S = len(streams)
+        cam_q = np.ascontiguousarray(cam_q, dtype=np.float64)
+        cam_p = np.ascontiguousarray(cam_p, dtype=np.float64)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if cam_q.ndim != 3 or cam_q.shape[0] != S or cam_q.shape[2] != 4 or cam_p.shape != cam_q.shape[:2] + (3,) or P.ndim != 3 or P.shape[0] != S or P.shape[1] != P.shape[2]:
+            raise ValueError('zupt_ops_dev: inconsistent shapes')
+        cs, ld = cam_q.shape[1], P.shape[1]
+        sd, si, rec = np.zeros((S, 43)), np.zeros((S, 6), np.int32), np.zeros(S, ZUPT_DTYPE)
+        for s, st in enumerate(streams):
+            o = 0
+            for name, k in self.STATE_FIELDS:
+                sd[s, o:o + k] = np.asarray(st[name], dtype=np.float64).reshape(-1)
+                o += k
+            si[s] = [st['n'], st['ncam'], st.get('failed', 0), st.get('null_aliased', 0), st.get('first_img', 0), st.get('active', 1)]
+            rec[s]['flags'] = st.get('zupt_flags', ZU_DETECTED)
+            rec[s]['detected_total'], rec[s]['applied_total'] = st.get('detected_total', 0), st.get('applied_total', 0)
+        up = lambda a: torch.from_numpy(a).to(self.dev)
+        q, p, Pd = up(cam_q), up(cam_p), up(P)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)
+        zp = _zupt_struct(params)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_zupt_ops_dev(self._h, S, cs, ld, ld * ld, hp(sd), hp(si), N.dptr(q), N.dptr(p), N.dptr(Pd), C.byref(zp), hp(rec), self._st()))
+            torch.cuda.synchronize()
+        out = []
+        for s in range(S):
+            d, o = {}, 0
+            for name, k in self.STATE_FIELDS:
+                d[name] = sd[s, o:o + k].copy() if k > 1 else float(sd[s, o])
+                o += k
+            d.update(zip(self.STATE_INTS, (int(v) for v in si[s])))
+            out.append(d)
+        return dict(streams=out, cam_q=q.cpu().numpy(), cam_p=p.cpu().numpy(), P=Pd.cpu().numpy(), rec=rec)
+
     def update(self, blk_rows, blk_lens, obs_noise):
         """Stacked EKF update on the selected blocks; returns delta_x (n doubles)."""
         n = self.dim
@@ -473,6 +513,40 @@ def unpack_forecast(rec, n, cov, s):
     return got, unpack_odom_cov(cov[s]), (float(got['t'][-1]) if len(got) else None)
 
 
+# ---- zero-velocity update (include/airvision.h, "Zero-velocity update") --------------------------------------------------------
+_ZU_INTS = ('flags', 'n_imu', 'n_tracked', 'n_still', 'detected_total', 'applied_total')
+_ZU_DOUBLES = ('w_max', 'a_dev_max', 'v_norm', 'gamma', 'dx_pos')
+ZUPT_DTYPE = np.dtype([(n, np.int32) for n in _ZU_INTS] + [(n, np.float64) for n in _ZU_DOUBLES])      # av_zupt, AV_ZUPT_BYTES
+assert ZUPT_DTYPE.itemsize == 64
+ZU_IMU_OK, ZU_VIS_OK, ZU_DETECTED, ZU_APPLIED, ZU_GATED, ZU_BAD = 1, 2, 4, 8, 16, 32      # AV_ZU_*
+ZUPT_PARAM_NAMES = ('gyro_max', 'acc_dev_max', 'disparity_max', 'velocity_sigma', 'gate', 'min_tracks', 'still_percent')      # av_zupt_params
+
+
+def zupt_params(config):
+    """The av_zupt_params of a config's zupt_* attributes as a dict (ZUPT_PARAM_NAMES): zupt_max_disparity, in pixels, becomes
+    normalised image units with 2 / (fx + fy) of cam0."""
+    fx, fy = float(config.cam0_intrinsics[0]), float(config.cam0_intrinsics[1])
+    return dict(gyro_max=float(config.zupt_gyro_threshold), acc_dev_max=float(config.zupt_acc_threshold),
+                disparity_max=float(config.zupt_max_disparity) * 2.0 / (fx + fy), velocity_sigma=float(config.zupt_velocity_sigma),
+                gate=float(config.zupt_gate), min_tracks=int(config.zupt_min_tracks), still_percent=int(config.zupt_still_percent))
+
+
+def _zupt_struct(params):
+    if set(params) != set(ZUPT_PARAM_NAMES):
+        raise ValueError('zero-velocity parameters are a dict of %s' % ', '.join(ZUPT_PARAM_NAMES))
+    return N.ZuptParams(*[(float if i < 5 else int)(params[k]) for i, k in enumerate(ZUPT_PARAM_NAMES)])
+
+
+def unpack_zupt(rec):
+    """Records ZUPT_DTYPE[...] as `read_zupt` returns them -> a dict of arrays of that shape: every field of the record, and the flags
+    as booleans imu_ok, vis_ok, detected, applied, gated, bad."""
+    rec = np.asarray(rec)
+    out = {n: rec[n] for n in ZUPT_DTYPE.names}
+    for name, bit in (('imu_ok', ZU_IMU_OK), ('vis_ok', ZU_VIS_OK), ('detected', ZU_DETECTED), ('applied', ZU_APPLIED), ('gated', ZU_GATED), ('bad', ZU_BAD)):
+        out[name] = (rec['flags'] & bit) != 0
+    return out
+
+
 # The optional outputs of a step of BatchedMSCKF, one entry each.  kw: the keyword of `step / submit / submit_dev`; ctor_kw: the
 # constructor keyword that switches it on; setting: the attribute that holds its setting (falsy: off); fn: the library's
 # av_msckf_batch_set_<fn> / av_msckf_batch_next_<fn>; last: the attribute that remembers the arrays of the most recent step that was
@@ -504,7 +578,7 @@ class BatchedMSCKF(object):
     (reference: src/msckf.py:162-228) for many streams at once."""
 
     def __init__(self, config, n_streams, device=0, rows_cap=None, max_features=None, odom_cov=False, landmarks=False, landmark_cap=64, stats=False,
-                 imu_rate=False, imu_rate_cap=32, forecast=False, forecast_cap=32):
+                 imu_rate=False, imu_rate_cap=32, forecast=False, forecast_cap=32, zupt=False):
         """rows_cap: rows of the per-stream block buffer.  None = sized by the library from the capacity of the first
         feature message (the camera-pruning update stacks 5 rows per feature, the lost-feature update at most 1500 + one
         block); `max_features`, when given, sizes it up front instead.  With the automatic size a later step with a wider
@@ -524,7 +598,10 @@ class BatchedMSCKF(object):
         forecast=True: every step also publishes the pose it leaves carried through the IMU samples pushed beyond the frame's time, the
         first forecast_cap (1 .. 4096) of them per stream, with the covariance at the last of them (records IMU_STATE_DTYPE, counts, a
         float64[S, 120] odometry-covariance record; `step / submit / submit_dev(..., forecast=)`, `last_forecast`, `unpack_forecast`).
-        Read-only for the filter: every other output and the state are bit for bit what they are without it."""
+        Read-only for the filter: every other output and the state are bit for bit what they are without it.
+        zupt=True: the zero-velocity update with the config's zupt_* attributes (`zupt_params`), or a dict of ZUPT_PARAM_NAMES: a stream
+        detected at rest gets velocity = 0 as a measurement on the state the step leaves -- the step's own published pose is the
+        pre-update one; `get_state`, `get_cov`, the forecast and the next step see the corrected state.  `read_zupt()` reads the records."""
         if rows_cap is None:
             rows_cap = 0 if max_features is None else max(2048, 5 * int(max_features) + 64)
         self.rows_cap = int(rows_cap)
@@ -566,6 +643,9 @@ class BatchedMSCKF(object):
             for o in STEP_OUTPUTS:
                 if want[o.setting]:
                     self._set(o, want[o.setting])
+            self.zupt = None                                 # the zero-velocity update's parameters (dict of ZUPT_PARAM_NAMES), None: off
+            if zupt:
+                self.set_zupt(zupt_params(config) if zupt is True else zupt)
         except Exception:
             self.close()
             raise
@@ -593,6 +673,21 @@ class BatchedMSCKF(object):
     def set_forecast(self, cap):
         """av_msckf_batch_set_forecast: cap records per stream and step (0: off, at most 4096); before the first step only."""
         self._set(_OUTPUT['forecast'], int(cap))
+
+    def set_zupt(self, params):
+        """av_msckf_batch_set_zupt: a dict of ZUPT_PARAM_NAMES (`zupt_params(config)` builds one), None: off; before the first step only."""
+        p = None if params is None else _zupt_struct(params)
+        N.check(N.lib().av_msckf_batch_set_zupt(self._h, None if p is None else C.byref(p)))
+        self.zupt = None if params is None else dict(params)
+
+    def read_zupt(self):
+        """The zero-velocity records of every stream after the last step, ZUPT_DTYPE[S] (av_msckf_batch_read_zupt; `unpack_zupt`); drains
+        the queue first.  Zeros while the update is off or before the first step."""
+        self.wait(0)
+        rec = np.zeros(self.S, ZUPT_DTYPE)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().av_msckf_batch_read_zupt(self._h, rec.ctypes.data_as(C.c_void_p)))
+        return rec
 
     def _next(self, o, value):
         """The arrays of output `o` for the next step (None: the step has none), handed to the library.  value: None, True (allocate) or

@@ -212,7 +212,8 @@ class FilterSet(object):
     odometry on, `submit_dev(..., imu_states=True)` gives every part its pair of arrays and `last_imu_states` = (records view, counts
     view) joins them ([S, imu_rate_cap] of IMU_STATE_DTYPE and [S, 2]).  forecast=True (with forecast_cap) switches the forecast on,
     `submit_dev(..., forecast=True)` gives every part its triple of arrays and `last_forecast` = (records view, counts view, covariance
-    view) joins them ([S, forecast_cap] of IMU_STATE_DTYPE, [S, 2] and [S, 120])."""
+    view) joins them ([S, forecast_cap] of IMU_STATE_DTYPE, [S, 2] and [S, 120]).  zupt=True (or a dict of msckf_ops.ZUPT_PARAM_NAMES)
+    switches the zero-velocity update on in every part; `read_zupt()` reads the records of all streams."""
 
     def __init__(self, config, engine_set, device=0, **kw):
         from .msckf_ops import BatchedMSCKF, STEP_OUTPUTS
@@ -305,6 +306,12 @@ class FilterSet(object):
     def stream_status(self, s):
         p, i = self.es._locate(s)
         return self.flts[p].stream_status(i)
+
+    def read_zupt(self):
+        """BatchedMSCKF.read_zupt over global stream indices: the parts' zero-velocity records side by side, ZUPT_DTYPE[S] (needs
+        FilterSet(..., zupt=True | parameters); zeros otherwise).  Drains the workers and every part's queue."""
+        self.wait(0)
+        return np.concatenate([f.read_zupt() for f in self.flts])
 
     def close(self):
         try:

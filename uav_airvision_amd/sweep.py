@@ -76,7 +76,8 @@ class BatchedRunner(object):
         self.landmark_cap = int(landmark_cap)
         self.flt = BatchedMSCKF(config, self.S, device=self.device, rows_cap=rows_cap, max_features=self.eng.max_features, odom_cov=self.odom_cov,
                                 landmarks=self.landmark_cap > 0, landmark_cap=max(1, self.landmark_cap), stats=bool(innovation),
-                                imu_rate=int(imu_rate_cap) > 0, imu_rate_cap=max(1, int(imu_rate_cap)))
+                                imu_rate=int(imu_rate_cap) > 0, imu_rate_cap=max(1, int(imu_rate_cap)), zupt=bool(getattr(config, 'use_zupt', False)))
+        self.zupt_totals = None                           # config.use_zupt: after `run`, int64[S, 2] (detected_total, applied_total) of every stream
         self.imu_rate_cap = int(imu_rate_cap)
         self.ir_rows = None
         self.innovation = bool(innovation)
@@ -277,6 +278,9 @@ class BatchedRunner(object):
         for pair in inflight:
             record(*pair)
         self.steps_done = step
+        if flt.zupt is not None:
+            z = flt.read_zupt()
+            self.zupt_totals = np.stack([z['detected_total'], z['applied_total']], axis=1).astype(np.int64)
         self.cov_rows = [np.array(c, dtype=np.float64).reshape(-1, 121) for c in covs] if self.odom_cov else None
         if self.landmark_cap > 0:
             from .msckf_ops import LANDMARK_DTYPE
@@ -290,8 +294,9 @@ class BatchedRunner(object):
 
 
 def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_step=None, rows_cap=None, share_frames=True, stats=None, cov_rows=None, lm_rows=None, landmark_cap=64, nis_rows=None,
-                ir_rows=None, imu_rate_cap=32):
+                ir_rows=None, imu_rate_cap=32, zupt_rows=None):
     """Open (path, offset) pairs as EuRoC datasets and run them as one batch; returns (trajectories, datasets).
+    zupt_rows (a list; config.use_zupt): receives, per stream, (detected_total, applied_total) of the zero-velocity update.
     cov_rows (a list): the batch runs with the odometry covariance on and the list receives, per stream, float64[n, 121] rows `t` + record.
     lm_rows (a list): the batch runs with the landmark map on (landmark_cap records per stream and step) and the list receives, per
     stream, (pose times float64[n], records LANDMARK_DTYPE[n], records dropped to the cap).
@@ -320,6 +325,8 @@ def run_batched(config, dataset_paths, offsets, device=0, max_frames=None, on_st
             nis_rows.extend(r.nis_rows)
         if ir_rows is not None:
             ir_rows.extend(r.ir_rows)
+        if zupt_rows is not None and r.zupt_totals is not None:
+            zupt_rows.extend((int(d), int(a)) for d, a in r.zupt_totals)
         if stats is not None:
             stats['seconds'] = stats.get('seconds', 0.0) + time.perf_counter() - t0
             stats['stream_frames'] = stats.get('stream_frames', 0) + int(r.frames_done.sum())
@@ -387,6 +394,9 @@ def make_parser():
                          'integrated, one line `t p q v w` each (p, q, v in the frame of the trajectory file, w the bias-corrected gyro in the IMU frame; '
                          'include/airvision.h, "IMU-rate odometry"), and after the records of every step the published pose of that step as one more line; '
                          'the report states the records dropped to the cap and, with ground truth, the ATE of this denser trajectory')
+    ap.add_argument('--zupt', action='store_true',
+                    help='zero-velocity update for streams at rest (config.use_zupt with the config\'s zupt_* thresholds); the report gains '
+                         '"zupt": per stream the frames detected at rest and the updates applied')
     ap.add_argument('--imu-rate-cap', type=int, default=32, metavar='N', help='--imu-rate: records per stream and step, the last N samples (default 32, at most 4096)')
     ap.add_argument('--landmark-cap', type=int, default=64, metavar='N', help='--landmarks: records per stream and step (default 64)')
     ap.add_argument('--ransac', action='store_true', help='two-point RANSAC outlier rejection on the tracked features (config.use_ransac; off = the reference front-end)')
@@ -459,6 +469,8 @@ def apply_args(cfg, args):
         for part in ('response', 'vignette'):                  # (a table already set on the config object stays unless the switch is given)
             if getattr(args, '%s%d' % (part, cam), None) is not None:
                 setattr(cfg, 'cam%d_%s' % (cam, part), getattr(args, '%s%d' % (part, cam)))
+    if getattr(args, 'zupt', False):                          # (already on the config object: stays on)
+        cfg.use_zupt = True
     return cfg
 
 
@@ -497,6 +509,7 @@ def main(argv=None):
     jobs = shard.broadcast_object([(s, o) for s in args.sequences for o in args.offsets] if rank == 0 else None)
     mine = shard.partition(len(jobs), world, rank)
     local_traj, local_cov, local_lm, local_nis, local_ir, report, stats = {}, {}, {}, {}, {}, {}, {}
+    local_zupt = {}
     import time
     if world > 1:
         dist.barrier()
@@ -508,13 +521,17 @@ def main(argv=None):
         lm_rows = [] if args.landmarks else None
         nis_rows = [] if args.innovation else None
         ir_rows = [] if args.imu_rate else None
+        zupt_rows = [] if cfg.use_zupt else None
         trajs, dss = run_batched(cfg, [os.path.join(root, jobs[j][0]) for j in chunk], [jobs[j][1] for j in chunk], device=local, max_frames=args.max_frames,
                                  share_frames=not args.no_share_frames, stats=stats, **({'cov_rows': cov_rows} if args.covariance else {}),
                                  **({'lm_rows': lm_rows, 'landmark_cap': args.landmark_cap} if args.landmarks else {}),
                                  **({'nis_rows': nis_rows} if args.innovation else {}),
-                                 **({'ir_rows': ir_rows, 'imu_rate_cap': args.imu_rate_cap} if args.imu_rate else {}))
+                                 **({'ir_rows': ir_rows, 'imu_rate_cap': args.imu_rate_cap} if args.imu_rate else {}),
+                                 **({'zupt_rows': zupt_rows} if zupt_rows is not None else {}))
         for i, (j, traj, ds) in enumerate(zip(chunk, trajs, dss)):
             local_traj[j] = traj
+            if zupt_rows:
+                local_zupt[j] = zupt_rows[i]
             if cov_rows is not None:
                 local_cov[j] = cov_rows[i]
             if lm_rows is not None:
@@ -534,7 +551,8 @@ def main(argv=None):
                 report.setdefault(j, dict(sequence=jobs[j][0], offset=jobs[j][1], frames=len(traj))).update(innovation_summary(nis_rows[i][1]))
     elapsed = shard.max_over_ranks(time.perf_counter() - t_all)          # barrier before, max over ranks after: the bench contract's clock
     allt = shard.gather_trajectories(local_traj, len(jobs), world, rank)
-    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm, 'nis': local_nis, 'ir': local_ir})
+    per_rank = shard.gather_objects({'rank': rank, 'streams': [jobs[j] for j in mine], 'report': report, 'stats': stats, 'cov': local_cov, 'lm': local_lm, 'nis': local_nis, 'ir': local_ir,
+                                     'zupt': local_zupt})
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         for j, (seq, off) in enumerate(jobs):
@@ -573,6 +591,11 @@ def main(argv=None):
         if args.landmarks:
             rep['landmarks'] = dict(cap=args.landmark_cap, records=[lm_dropped.get(j, (0, 0))[0] for j in range(len(jobs))],
                                     dropped_to_cap=[lm_dropped.get(j, (0, 0))[1] for j in range(len(jobs))])
+        if cfg.use_zupt:
+            zt = {}
+            for r in per_rank:
+                zt.update(r['zupt'])
+            rep['zupt'] = dict(detected_total=[zt.get(j, (0, 0))[0] for j in range(len(jobs))], applied_total=[zt.get(j, (0, 0))[1] for j in range(len(jobs))])
         if cfg.use_clahe:
             rep['clahe'] = dict(clip_limit=cfg.clahe_clip_limit, tiles=list(cfg.clahe_tiles))
         if args.pixel_format != 'gray8':

@@ -313,8 +313,9 @@ class SyntheticFeatureStream(object):
     `frames()` yields feature_msg(timestamp, [FeatureMeasurement-like]); `imu` as SyntheticStream."""
 
     def __init__(self, config, seed=0, n_frames=100, n_features=100, pixel_sigma=0.5, motion_scale=1.0, t0=100.0,
-                 outlier_rate=0.0, outlier_px=12.0):
-        self.base = SyntheticStream(config, seed=seed, n_frames=n_frames, motion_scale=motion_scale, t0=t0, render=False)
+                 outlier_rate=0.0, outlier_px=12.0, rest=0.0):
+        # rest: seconds of standstill after frame 0, as in SyntheticStream (0: every stream as it always was)
+        self.base = SyntheticStream(config, seed=seed, n_frames=n_frames, motion_scale=motion_scale, t0=t0, render=False, rest=rest)
         self.config = config
         self.n_frames = n_frames
         self.n_features = n_features
